@@ -17,6 +17,9 @@ scripts/msm-weierstrass.ts:19-35).
           route of src/parallel.ts:291-315); `--devices 0,0` rehearses it on one GPU.  Default route "proc" = one process
           per GPU under torch.distributed.run (what the driver launches).
 
+  --dump-outputs DIR   after the timed steps, rank 0 writes the MSM result of the last timed step as DIR/*.npy
+          (float64); the inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
 Prints ONE JSON line (rank 0).  value = non-zero signed digits (= bucket insertions, "point-adds",
 SURVEY.md section 8d) of all ranks per second.
 """
@@ -48,7 +51,11 @@ def main():
                     help="proc: one process per GPU (torch.distributed.run); ctx: one process, one multi-device context")
     ap.add_argument("--devices", default="", help="--route ctx: comma-separated device ids (default 0..N-1; ids may repeat)")
     ap.add_argument("--cpu-log2n", type=int, default=20)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the MSM result of the last timed step to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -140,7 +147,7 @@ def main():
     t0 = time.perf_counter()
     stats = []
     for s in range(args.warmup, nsets):
-        out, _ = one_step(s)
+        out, res = one_step(s)
         stats.append(out["stats"])
     t_local = time.perf_counter() - t0      # this rank's own K steps, before it waits for the others
     barrier()
@@ -158,6 +165,8 @@ def main():
     total_entries = float(entries.item())
     per_rank_ms = [float(v) for v in per_rank.cpu().tolist()]
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, params, res)
     if rank == 0:
         st0 = stats[-1]
         K, c = st0.K, st0.c
@@ -227,6 +236,19 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(path, params, res):
+    """The MSM result a caller of the timed path receives (the partial sums of all ranks combined), as float64 .npy
+    files: the affine coordinates x and y as little-endian 32-bit limbs (exact in float64) and the point-at-infinity
+    flag."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    nlimbs = params["fe_bytes"] // 4
+    limbs = lambda v: np.array([(int(v) >> (32 * i)) & 0xFFFFFFFF for i in range(nlimbs)], dtype=np.float64)
+    np.save(os.path.join(path, "result_x.npy"), limbs(res["x"]))
+    np.save(os.path.join(path, "result_y.npy"), limbs(res["y"]))
+    np.save(os.path.join(path, "result_is_zero.npy"), np.array([1.0 if res.get("isZero") else 0.0], dtype=np.float64))
 
 
 def pmc_traffic(key):

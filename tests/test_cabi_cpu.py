@@ -9,6 +9,16 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def hip_device_count():
+    """GPUs visible to the HIP runtime libmsmz.so is linked against.  torch.cuda would load torch's own copy of the
+    runtime next to it, and two runtimes in one process cannot both open the device."""
+    from msm_zprize_amd import _native
+    _native.lib()
+    hip = ctypes.CDLL("libamdhip64.so.7")   # by soname: the copy already loaded for libmsmz.so
+    n = ctypes.c_int(0)
+    return n.value if hip.hipGetDeviceCount(ctypes.byref(n)) == 0 else 0
+
+
 @pytest.fixture(scope="module")
 def lib():
     from msm_zprize_amd import build
@@ -42,8 +52,7 @@ def test_strerror_and_curve_table(lib):
 
 def test_no_cpu_fallback(lib):
     """without a visible GPU msmz_create must fail with MSMZ_ERR_NO_DEVICE, never fall back"""
-    import torch
-    if torch.cuda.is_available():
+    if hip_device_count() > 0:
         pytest.skip("a GPU is visible")
     ctx = ctypes.c_void_p()
     dev = (ctypes.c_int * 1)(0)
