@@ -127,6 +127,25 @@ int msmz_msm(msmz_ctx* ctx, uint64_t points_handle, const uint8_t* scalars_le32,
 int msmz_msm_resident(msmz_ctx* ctx, uint64_t points_handle, uint64_t scalars_handle, uint64_t n,
                       const msmz_opts* opts, uint8_t* out_xy_le, int* out_is_inf, msmz_log* log /* nullable */);
 
+/* Batched MSM: `batch` MSMs over the same first n points, out_k = sum_i scalars[k][i] * point_i, k = 0 .. batch-1 -- a
+ * prover committing to many polynomials against one SRS.  scalars_le32: batch * n * 32 bytes, vector k at offset
+ * k * n * 32 (host buffer, copied inside the call); msmz_msm_batch_resident: one scalar handle holding >= batch * n
+ * scalars, vector k = entries [k n, (k+1) n).  out_xy_le: batch * 2 * fe_bytes; out_is_inf: batch ints.  Options as
+ * msmz_msm; log (nullable) describes the whole call (stage times and counts are totals over the batch).
+ * batch == 1 returns exactly what msmz_msm / msmz_msm_resident return; batch == 0 or n == 0 is MSMZ_ERR_ARG; a scalar
+ * >= the group order in any vector fails the whole call with MSMZ_ERR_RANGE (the context stays usable).
+ * Weierstrass curves with batched-affine buckets run all problems through ONE device pipeline (one sort, one plan, one
+ * train of tree rounds, one bucket reduction, one host round trip), in consecutive sub-batches of at most 2^26 bucket
+ * entries.  Twisted Edwards (ed-on-bls12-377), MSMZ_BUCKETS_PROJECTIVE, reserved[0] = 1 and n beyond one sort pass
+ * (2^24 entries) run the problems one by one: same results, no batching gain.  A multi-device context runs the batch on
+ * every device's share of the points and adds the partial sums on the host per problem; resident scalars are first
+ * gathered to the host there. */
+int msmz_msm_batch(msmz_ctx* ctx, uint64_t points_handle, const uint8_t* scalars_le32, uint64_t n, uint32_t batch,
+                   const msmz_opts* opts, uint8_t* out_xy_le, int* out_is_inf, msmz_log* log /* nullable */);
+int msmz_msm_batch_resident(msmz_ctx* ctx, uint64_t points_handle, uint64_t scalars_handle, uint64_t n,
+                            uint32_t batch, const msmz_opts* opts, uint8_t* out_xy_le, int* out_is_inf,
+                            msmz_log* log /* nullable */);
+
 /* Host-side group addition of two canonical affine results: combines per-GPU partial sums
  * (the reference's "partition sum" step, msm-batched-affine.ts:300-307). */
 int msmz_point_add(int curve_id, const uint8_t* a_xy_le, int a_is_inf, const uint8_t* b_xy_le, int b_is_inf,

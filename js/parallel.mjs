@@ -181,7 +181,45 @@ function createCurve(params, kind) {
     return { result, log, stats: r.log };
   }
 
+  // B MSMs over the first n points in one device pipeline (msmz_msm_batch): `scalarsList` is ONE resident scalar array
+  // of >= B * n scalars (vector k = entries [k n, (k + 1) n); B = options.batch, default length / n) or an array of B
+  // host byte arrays (scalarsFromBytes format, concatenated here).  A list of resident arrays is refused.
+  async function msmBatchCommon(scalarsList, points, n, options, safe) {
+    options = options || {};
+    const opts = {
+      c: options.c || 0,
+      glv: options.glv !== undefined ? Number(options.glv) : te ? 0 : -1,
+      safe: options.useSafeAdditions !== undefined ? Number(options.useSafeAdditions) : safe,
+      buckets: options.buckets || 0,
+      reduceAffine: options.reduceAffine ? 1 : 0,
+    };
+    if (typeof points === "number") points = resident(points, n, "msmBatch points");
+    if (!(n > 0) || n > points.n) throw Error(`msmBatch: n = ${n} but the point set holds ${points.n}`);
+    let s, B;
+    if (scalarsList instanceof DeviceArray) {
+      B = options.batch !== undefined ? Number(options.batch) : Math.floor(scalarsList.n / n);
+      if (!(B > 0) || B * n > scalarsList.n) throw Error(`msmBatch: ${B} vectors of ${n} scalars, the array holds ${scalarsList.n}`);
+      s = scalarsList.handle;
+    } else {
+      if (!Array.isArray(scalarsList) || scalarsList.length === 0) throw Error("msmBatch: one resident scalar array or a list of host byte arrays");
+      if (scalarsList.some((v) => v instanceof DeviceArray || typeof v === "number"))
+        throw Error("msmBatch: a list of resident arrays is not accepted; pass ONE resident array of B * n scalars");
+      const len = scalarsList[0].length;
+      if (scalarsList.some((v) => v.length !== len)) throw Error("msmBatch: scalar vectors of unequal length");
+      if (len < 32 * n) throw Error(`msmBatch: a vector of ${len} bytes holds fewer than n = ${n} scalars`);
+      B = scalarsList.length;
+      s = Buffer.concat(scalarsList.map((v) => Buffer.from(v.buffer, v.byteOffset, 32 * n)));
+    }
+    const r = N.msmBatch(ctx, points.handle, s, n, B, fb, opts);
+    const out = [];
+    for (let k = 0; k < B; k++) out.push(decodePoint(r.xy, 2 * fb * k, r.isInf[k]));
+    return out;
+  }
+
   const Parallel = {
+    /** batched MSM: B scalar vectors against one point set (include/msmz.h msmz_msm_batch); safe additions */
+    msmBatch: (scalarsList, points, n, options) => msmBatchCommon(scalarsList, points, n, options, 1),
+    msmBatchUnsafe: (scalarsList, points, n, options) => msmBatchCommon(scalarsList, points, n, options, 0),
     /** curve-random.ts:14-92, seeded: point i = splitmix64(seed, i) * G */
     async randomPointsFast(n, { seed = 0x6d736d7an } = {}) {
       return DeviceArray.make(curve, N.randomPoints(ctx, n, BigInt(seed)), n, "points");

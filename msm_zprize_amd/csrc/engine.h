@@ -84,6 +84,7 @@ static inline int default_window(uint64_t n_points) {
 }
 
 constexpr int MSMZ_ERR_RETRY_BITS = 1000;   // internal: repeat the MSM with one more scalar bit (never leaves the engine)
+constexpr int MSMZ_ERR_BATCH_LOOP = 1001;   // internal: this batched MSM runs its problems one by one (never leaves the engine)
 
 // Host-side group addition of two canonical affine points (partial sums of index ranges / of GPUs):
 // the reference's "partition sum" on the main thread (msm-batched-affine.ts:300-307).
@@ -233,6 +234,7 @@ class Engine : public IEngine {
       b->release();
     if (h_meta_) (void)hipHostFree(h_meta_);
     if (h_final_) (void)hipHostFree(h_final_);
+    if (h_bfinal_) (void)hipHostFree(h_bfinal_);
     for (auto& e : ev_)
       if (e) (void)hipEventDestroy(e);
     if (stream_) (void)hipStreamDestroy(stream_);
@@ -435,10 +437,20 @@ class Engine : public IEngine {
       d_scalars = (const uint32_t*)sit->second.dev;
     }
     if (log) memset(log, 0, sizeof(*log));
+    const int st = msm_passes(pit->second, d_scalars, n, opt, out, out_inf, log);
+    if (log) {
+      log->stage_ms[MSMZ_ST_TOTAL] =
+          std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    }
+    return st;
+  }
+
+  // one MSM over device scalars (log: zeroed by the caller, or null)
+  int msm_passes(const Handle& pts, const uint32_t* d_scalars, uint64_t n, const msmz_opts& opt, uint8_t* out,
+                 int* out_inf, msmz_log* log) {
     // Inputs beyond what one pass sorts (2^24 entries; 2^23 points with GLV) run as consecutive index ranges whose
     // partial sums are added on the host -- the same additivity the multi-GPU split uses.
     const uint64_t per_pass = (opt.glv != 0 && !TE) ? kMaxEntriesPerPass / 2 : kMaxEntriesPerPass;
-    const Handle& pts = pit->second;
     int st = MSMZ_OK;
     uint8_t part[RW * 4];
     for (uint64_t done = 0; done < n && st == MSMZ_OK; done += per_pass) {
@@ -466,11 +478,108 @@ class Engine : public IEngine {
       }
       if (log) merge_log(log, plog, done == 0);
     }
+    return st;
+  }
+
+  // ------------------------------------------------------------------------------------------ batched msm
+  // Entries (problems x windows x entries per window) one batched pass sorts, plans and adds: slots, descriptors and
+  // references cost ~100 B per entry (BLS12-377), so a batch beyond 2^26 entries (~7 GB) runs as consecutive
+  // sub-batches.  (2^26 also keeps the 30-bit location words and the 31-bit bucket numbers far from their limits.)
+  static constexpr uint64_t kMaxBatchEntries = 1ull << 26;
+
+  // `batch` MSMs over the first n points: problem k's scalars are entries [k n, (k + 1) n) of the resident set `sh`, or
+  // vector k of the host buffer (at host_scalars + k host_stride 32; host_stride = n unless a multi-device context hands
+  // this engine its share `split` of longer vectors).  Weierstrass batched-affine plans run as ONE batched pipeline per
+  // sub-batch (msm_weierstrass_affine with nprob > 1); twisted Edwards, projective buckets, the affine first reduction
+  // level and inputs beyond one sort pass run the problems one by one.
+  int msm_batch(uint64_t ph, const uint8_t* host_scalars, uint64_t sh, uint64_t n, uint32_t batch, const msmz_opts* o,
+                uint8_t* out, int* out_inf, msmz_log* log, const GenMap* split = nullptr,
+                uint64_t host_stride = 0) override {
+    auto t_begin = std::chrono::steady_clock::now();
+    if (!out || !out_inf || n == 0 || batch == 0) return MSMZ_ERR_ARG;
+    auto pit = handles_.find(ph);
+    if (pit == handles_.end() || pit->second.kind != 0 || pit->second.n < n) return MSMZ_ERR_ARG;
+    msmz_opts opt;
+    memset(&opt, 0, sizeof(opt));
+    if (o) opt = *o;
+    // (the engine's choice of msm(): per problem size, so that batch = 1 is msm() exactly)
+    if (opt.glv < 0) opt.glv = (!TE && Fr::HAS_GLV && pit->second.has_endo && n < (1ull << 15)) ? 1 : 0;
+    if (host_stride == 0) host_stride = n;
+    if (host_scalars && host_stride < n) return MSMZ_ERR_ARG;
+    MSMZ_HIP(hipSetDevice(device_));
+    const uint64_t total = (uint64_t)batch * n;
+    const uint32_t* d_scalars = nullptr;
+    if (host_scalars) {
+      // range (< group order) is checked on the device while the scalars are sliced
+      int st = stage_.ensure(total * 32);
+      if (st) return st;
+      if (!split && host_stride == n) {
+        if ((st = copy_h2d(stage_.p, host_scalars, 32, total, nullptr))) return st;
+      } else {
+        for (uint32_t k = 0; k < batch; k++)
+          if ((st = copy_h2d(stage_.as<uint8_t>() + (size_t)k * n * 32, host_scalars + (size_t)k * host_stride * 32, 32, n,
+                             split)))
+            return st;
+      }
+      d_scalars = stage_.as<uint32_t>();
+    } else {
+      auto sit = handles_.find(sh);
+      if (sit == handles_.end() || sit->second.kind != 1 || sit->second.n < total) return MSMZ_ERR_ARG;
+      d_scalars = (const uint32_t*)sit->second.dev;
+    }
+    if (log) memset(log, 0, sizeof(*log));
+    const Handle& pts = pit->second;
+    const uint64_t per_pass = (opt.glv != 0 && !TE) ? kMaxEntriesPerPass / 2 : kMaxEntriesPerPass;
+    const bool batched = !TE && opt.buckets != MSMZ_BUCKETS_PROJECTIVE && opt.reserved[0] != 1 && reduce2d_ &&
+                         n <= per_pass && batch > 1;
+    int st = MSMZ_OK;
+    for (uint32_t done = 0; done < batch && st == MSMZ_OK;) {
+      uint32_t bs = batched ? batch_size(pts, n, opt, batch - done) : 1;
+      const uint32_t* d_sc = d_scalars + (size_t)done * n * 8;
+      msmz_log plog;
+      msmz_log* lp = log ? &plog : nullptr;
+      if (lp) memset(lp, 0, sizeof(*lp));
+      if (bs > 1) {
+        st = msm_weierstrass_affine(pts, (const uint32_t*)pts.dev, d_sc, n, opt, out + (size_t)done * RW * 4,
+                                    out_inf + done, lp, 0, bs);
+        if (st == MSMZ_ERR_RETRY_BITS) {   // a GLV half longer than assumed (see msm_passes): the whole sub-batch again
+          retries_++;
+          st = msm_weierstrass_affine(pts, (const uint32_t*)pts.dev, d_sc, n, opt, out + (size_t)done * RW * 4,
+                                      out_inf + done, lp, 1, bs);
+          if (st == MSMZ_ERR_RETRY_BITS) st = MSMZ_ERR_ARG;
+        }
+        if (st == MSMZ_ERR_BATCH_LOOP) {
+          bs = 1;
+          st = MSMZ_OK;
+        }
+      }
+      if (bs == 1) st = msm_passes(pts, d_sc, n, opt, out + (size_t)done * RW * 4, out_inf + done, lp);
+      if (st) break;
+      if (log) merge_log(log, plog, done == 0);
+      done += bs;
+    }
     if (log) {
       log->stage_ms[MSMZ_ST_TOTAL] =
           std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     }
     return st;
+  }
+
+  // problems of the next sub-batch: the window size depends on the batch size, so the plan is made again until the
+  // sub-batch fits kMaxBatchEntries; the remaining problems are then dealt into equal sub-batches
+  uint32_t batch_size(const Handle& pts, uint64_t n, const msmz_opts& opt, uint32_t remaining) {
+    uint32_t bs = remaining;
+    for (int it = 0; it < 4 && bs > 1; it++) {
+      Plan pl;
+      if (make_plan(pl, n, opt.glv != 0, opt, (uint32_t)pts.n, true, 0, true, bs) != MSMZ_OK) {
+        bs = (bs + 1) / 2;
+        continue;
+      }
+      const uint32_t fit = batch_split(remaining, (uint64_t)pl.K * pl.M, kMaxBatchEntries);
+      if (fit >= bs) break;
+      bs = fit;
+    }
+    return bs;
   }
 
   static void merge_log(msmz_log* total, const msmz_log& part, bool first) {
@@ -643,6 +752,8 @@ class Engine : public IEngine {
     bool glv, timing;
     uint32_t max_bucket = 0, n_entries = 0;
     uint32_t endo_delta = 0;    // GLV over a prefix of a set: half-1 entry i reads point record pts_n + i = (n + i) + endo_delta
+    uint32_t nprob = 1;         // batched MSM: problems (scalar vectors) sorted, planned and reduced together; nb, M, K,
+                                // Keff describe ONE problem, bucket set p * Keff + kw holds window kw of problem p
     int ei = 0;                 // next event slot
     int ev_coarse = -1, ev_sort_end = -1;
   };
@@ -744,7 +855,9 @@ class Engine : public IEngine {
   // ~75 us whatever its size and the number of rounds is log2 of the LONGEST bucket, which usually sits in a
   // partly filled top window -- so they pick the c that minimizes a small cost model fitted to this GPU
   // (ms: rounds * 0.075 + additions / 4.5e6 + reduction levels * 0.065 + buckets * 0.8e-6).
-  int choose_window(bool glv, uint32_t M, int b, bool tree_rounds) const {
+  // A batch of B problems runs the same number of tree rounds and reduction levels as one, with B times the additions
+  // and buckets: those two terms of the model are scaled by B.
+  int choose_window(bool glv, uint32_t M, int b, bool tree_rounds, uint32_t nprob = 1) const {
     int c = default_window(M);
     if (M >= (1u << 18) || no_window_model_) {
       // measured optimum of the batched-affine path from 2^18 entries per window on (profiles/r03_sweep.json): 17 without
@@ -770,8 +883,8 @@ class Engine : public IEngine {
       if (g.K > 1 && conc * lam * 1.3 + 12 > maxb) maxb = conc * lam * 1.3 + 12;
       if (maxb > M) maxb = M;
       const int rounds = ceil_log2_u64((uint64_t)(maxb < 2 ? 2 : maxb));
-      const double cost = (tree_rounds ? 0.075 * rounds : 0.0) + (double)g.K * M / 4.5e6 + 0.065 * ((cc - 1 + 1) / 2) +
-                          0.8e-6 * g.Keff * g.L;
+      const double cost = (tree_rounds ? 0.075 * rounds : 0.0) + (double)nprob * g.K * M / 4.5e6 +
+                          0.065 * ((cc - 1 + 1) / 2) + 0.8e-6 * nprob * g.Keff * g.L;
       if (cost < best) {
         best = cost;
         best_c = cc;
@@ -781,8 +894,9 @@ class Engine : public IEngine {
   }
 
   int make_plan(Plan& pl, uint64_t n64, bool glv, const msmz_opts& opt, uint32_t pts_n, bool tree_rounds = true,
-                int extra_bits = 0, bool allow_fold = false) {
+                int extra_bits = 0, bool allow_fold = false, uint32_t nprob = 1) {
     pl.n = (uint32_t)n64;
+    pl.nprob = nprob;
     pl.glv = glv;
     pl.M = glv ? 2 * pl.n : pl.n;
     // scalar bit length.  GLV halves: first attempt assumes |s_j| < 2^127 (every half seen so far; for BLS12-377 the
@@ -796,7 +910,7 @@ class Engine : public IEngine {
     } else {
       pl.b = glv_bits_assumed_ > 0 ? glv_bits_assumed_ : Fr::GLV_BITS - 1;
     }
-    pl.c = opt.c > 0 ? opt.c : choose_window(glv, pl.M, pl.b, tree_rounds);
+    pl.c = opt.c > 0 ? opt.c : choose_window(glv, pl.M, pl.b, tree_rounds, nprob);
     if (pl.c < 2) pl.c = 2;
     if (pl.c > 24) pl.c = 24;
     const Geometry g = geometry(pl.c, glv, pl.M, pl.b, allow_fold);
@@ -808,7 +922,8 @@ class Engine : public IEngine {
     pl.fold_rows = g.fold_rows;
     pl.Keff = g.Keff;
     const uint64_t nb64 = (uint64_t)pl.Keff * pl.L;
-    if (nb64 + 1 >= (1ull << 31) || (uint64_t)pl.K * pl.M >= (1ull << 32) || pl.Keff > kMaxWindows) return MSMZ_ERR_ARG;
+    if (nb64 * nprob + 1 >= (1ull << 31) || (uint64_t)nprob * pl.K * pl.M >= (1ull << 32) || pl.Keff > kMaxWindows)
+      return MSMZ_ERR_ARG;
     pl.nb = (uint32_t)nb64;
     pl.nblocks = (pl.nb + SCAN_TILE - 1) / SCAN_TILE;
     pl.timing = opt.timing != 0;
@@ -816,13 +931,25 @@ class Engine : public IEngine {
     return MSMZ_OK;
   }
 
+  // does the two-level LDS-staged sort apply to this plan (else the per-entry atomic fallback)?
+  bool sort2_applies(const Plan& pl) const {
+    const int fb = fine_bits(pl.c, pl.M);
+    const uint32_t ncb = pl.L >> fb;
+    const uint32_t ncbt = pl.L >> fine_bits_top(pl, fb);
+    const uint32_t nbins = (uint32_t)(pl.K - 1) * ncb + (ncbt << pl.spread);
+    return !force_atomic_sort_ && fb >= 0 && pl.M <= (1u << 24) && ncb <= (uint32_t)COARSE_MAX_BINS &&
+           (ncbt << pl.spread) <= (uint32_t)COARSE_MAX_BINS && nbins <= (uint32_t)SORT_MAX_BINS;
+  }
+
   // scalars -> sorted references `refs_` + bucket offsets `off_` (+ meta->max_bucket); events 0..4.  No host round trip.
+  // pl.nprob > 1 (batched MSM): problem p reads scalars [p n, (p + 1) n); its bins follow problem p - 1's in ONE exclusive
+  // scan, so refs_ / off_ come out as one dense sort of pl.nprob * nb buckets.  The two-level sort only.
   int sort_phase(Plan& pl, const uint32_t* d_scalars) {
-    const uint32_t n = pl.n, M = pl.M, L = pl.L, nb = pl.nb, nblocks = pl.nblocks;
+    const uint32_t n = pl.n, M = pl.M, L = pl.L, nb = pl.nb, nblocks = pl.nblocks, P = pl.nprob;
     const int c = pl.c, K = pl.K;
     int st;
-    if ((st = refs_.ensure((size_t)K * M * 4))) return st;
-    if ((st = off_.ensure(((size_t)nb + 1) * 4))) return st;
+    if ((st = refs_.ensure((size_t)P * K * M * 4))) return st;
+    if ((st = off_.ensure(((size_t)P * nb + 1) * 4))) return st;
     MsmMeta* d_meta = meta_.as<MsmMeta>();
     MSMZ_HIP(hipMemsetAsync(d_meta, 0, sizeof(MsmMeta), stream_));
     // two-level LDS-staged sort when the packed (fine | negate | index) word fits; else per-entry atomics.
@@ -835,21 +962,22 @@ class Engine : public IEngine {
     const uint32_t ncbt = L >> fbt;
     const uint32_t top_bin = (uint32_t)(K - 1) * ncb;
     const uint32_t nbins = top_bin + (ncbt << pl.spread);
-    const bool sort2 = !force_atomic_sort_ && fb >= 0 && M <= (1u << 24) && ncb <= (uint32_t)COARSE_MAX_BINS &&
-                       (ncbt << pl.spread) <= (uint32_t)COARSE_MAX_BINS && nbins <= (uint32_t)SORT_MAX_BINS;
+    const bool sort2 = sort2_applies(pl);
     const uint32_t n_half = pl.glv ? n : 0xffffffffu;
+    if (!sort2 && P > 1) return MSMZ_ERR_ARG;   // (msm_batch only batches plans the two-level sort handles)
     if (sort2) {
-      if ((st = packed_.ensure((size_t)K * M * 4))) return st;
-      if ((st = bins_.ensure(((size_t)nbins + 2) * 4 + kTraceBytes * nbins))) return st;
-      if ((st = counts_.ensure((size_t)nbins * 4))) return st;
+      const size_t pbins = (size_t)P * nbins;   // bins of all problems
+      if ((st = packed_.ensure((size_t)P * K * M * 4))) return st;
+      if ((st = bins_.ensure((pbins + 2) * 4 + kTraceBytes * pbins))) return st;
+      if ((st = counts_.ensure(pbins * 4))) return st;
       uint32_t* d_counts = counts_.as<uint32_t>();
-      MSMZ_HIP(hipMemsetAsync(d_counts, 0, (size_t)nbins * 4, stream_));
+      MSMZ_HIP(hipMemsetAsync(d_counts, 0, pbins * 4, stream_));
       SortGeom g{n, M, c, K, fb, pl.spread, idx_bits, ncb, fbt, ncbt, pl.fold_shift, pl.fold_rows};
       mark(pl);  // 0
       const uint32_t per_tile = pl.glv ? COARSE_TILE / 2 : COARSE_TILE;   // scalars per workgroup (k_hist and k_coarse)
       const uint32_t tiles = (n + per_tile - 1) / per_tile;
-      if ((st = tilecnt_.ensure((size_t)tiles * nbins * 2))) return st;
-      if ((st = tileoff_.ensure((size_t)tiles * nbins * 4 + kTraceBytes * tiles))) return st;   // the tiles' runs inside the bins
+      if ((st = tilecnt_.ensure((size_t)P * tiles * nbins * 2))) return st;
+      if ((st = tileoff_.ensure((size_t)P * tiles * nbins * 4 + kTraceBytes * tiles))) return st;   // the tiles' runs inside the bins
       // kernels specialized for the window size (unrolled window loop) where one is compiled: 16 / 17, the defaults of
       // large inputs; any other window size takes the generic ones
       const int cspec = (no_sort_special_ || (c != 16 && c != 17) || (pl.glv && c != 16)) ? 0 : c;
@@ -857,10 +985,10 @@ class Engine : public IEngine {
         constexpr bool G = decltype(glvc)::value;
         constexpr int C = decltype(cc)::value;
         if (!coarse)
-          hipLaunchKernelGGL((k_hist<Fr, G, C>), dim3(tiles), dim3(COARSE_T), (size_t)nbins * 4, stream_, d_counts,
+          hipLaunchKernelGGL((k_hist<Fr, G, C>), dim3(tiles, P), dim3(COARSE_T), (size_t)nbins * 4, stream_, d_counts,
                              tilecnt_.as<uint16_t>(), tileoff_.as<uint32_t>(), d_meta, d_scalars, g, nbins);
         else   // dynamic LDS <= kCoarseLdsMax (nbins <= SORT_MAX_BINS): the limit init() raised
-          hipLaunchKernelGGL((k_coarse<Fr, G, C>), dim3(tiles), dim3(COARSE_T), (size_t)2 * nbins * 4, stream_,
+          hipLaunchKernelGGL((k_coarse<Fr, G, C>), dim3(tiles, P), dim3(COARSE_T), (size_t)2 * nbins * 4, stream_,
                              packed_.as<uint32_t>(), tileoff_.as<uint32_t>(), bins_.as<uint32_t>(), tilecnt_.as<uint16_t>(),
                              d_scalars, g, nbins);
       };
@@ -882,8 +1010,19 @@ class Engine : public IEngine {
       dispatch_sort(false);
       mark(pl);  // 1
       MSMZ_HIP(hipGetLastError());
-      hipLaunchKernelGGL(k_bin_scan, dim3(1), dim3(1024), 0, stream_, bins_.as<uint32_t>(), d_counts, nbins,
-                         &d_meta->n_entries);
+      if (pbins <= (size_t)SORT_MAX_BINS) {
+        hipLaunchKernelGGL(k_bin_scan, dim3(1), dim3(1024), 0, stream_, bins_.as<uint32_t>(), d_counts, (uint32_t)pbins,
+                           &d_meta->n_entries);
+      } else {   // a batch with more bins than one workgroup scans: the three-launch scan
+        const uint32_t sblocks = (uint32_t)((pbins + SCAN_TILE - 1) / SCAN_TILE);
+        if ((st = partials_.ensure((size_t)sblocks * 4))) return st;
+        hipLaunchKernelGGL(k_scan_partials, dim3(sblocks, 1), dim3(SCAN_T), 0, stream_, partials_.as<uint32_t>(), d_counts,
+                           (uint32_t)pbins, 0, sblocks);
+        hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(SCAN_T), 0, stream_, partials_.as<uint32_t>(), sblocks,
+                           &d_meta->n_entries);
+        hipLaunchKernelGGL(k_scan_apply, dim3(sblocks, 1), dim3(SCAN_T), 0, stream_, bins_.as<uint32_t>(),
+                           partials_.as<uint32_t>(), d_counts, (uint32_t)pbins, 0, sblocks, (size_t)0, (uint32_t*)nullptr);
+      }
       mark(pl);  // 2
       MSMZ_HIP(hipGetLastError());
       dispatch_sort(true);
@@ -892,14 +1031,14 @@ class Engine : public IEngine {
       MSMZ_HIP(hipGetLastError());
       {
         const size_t lds = kFineLds;
-        hipLaunchKernelGGL(k_fine, dim3(nbins), dim3(FINE_T), lds, stream_, refs_.as<uint32_t>(), off_.as<uint32_t>(),
+        hipLaunchKernelGGL(k_fine, dim3(nbins, P), dim3(FINE_T), lds, stream_, refs_.as<uint32_t>(), off_.as<uint32_t>(),
                            &d_meta->max_bucket, packed_.as<uint32_t>(), bins_.as<uint32_t>(), fb, fbt, top_bin, nbins, idx_bits,
                            n_half, pl.endo_delta);
       }
 #ifdef MSMZ_TRACE
       // development aid: workgroup time stamps of k_coarse / k_fine (tools/wg_timeline.py)
-      if ((st = trace_dump("k_coarse", tileoff_.as<uint32_t>() + (size_t)tiles * nbins, tiles, true))) return st;
-      if ((st = trace_dump("k_fine", bins_.as<uint32_t>() + ((nbins + 2) & ~1u), nbins, false))) return st;
+      if ((st = trace_dump("k_coarse", tileoff_.as<uint32_t>() + (size_t)P * tiles * nbins, tiles, true))) return st;
+      if ((st = trace_dump("k_fine", bins_.as<uint32_t>() + ((P * nbins + 2) & ~1u), nbins, false))) return st;
 #endif
     } else {
       // fallback (window sizes whose coarse bins do not fit the LDS staging): digits materialized, one global
@@ -1060,7 +1199,7 @@ class Engine : public IEngine {
     // reduce stage 0.88 / 0.81 / 0.81 ms), at most 32 per line (5 pair-sum launches), and a chunk holds at least one
     // bucket along either direction
     uint32_t nc = 1;
-    while (nc < 32 && nc * 2 <= s.D && (uint64_t)2 * pl.Keff * s.H * nc < (1u << 18)) nc *= 2;
+    while (nc < 32 && nc * 2 <= s.D && (uint64_t)2 * pl.nprob * pl.Keff * s.H * nc < (1u << 18)) nc *= 2;
     if (r2_nc_ > 0) {
       nc = 1;
       while (nc < r2_nc_ && nc * 2 <= s.D) nc *= 2;
@@ -1080,7 +1219,7 @@ class Engine : public IEngine {
     g.NC = sp.NC;
     g.chr = sp.D / sp.NC;
     g.chc = sp.H / sp.NC;
-    g.nprob = 2u * (uint32_t)pl.Keff;
+    g.nprob = 2u * pl.nprob * (uint32_t)pl.Keff;   // (all bucket sets of a batch)
     const uint32_t lines = g.nprob * g.H;
     const uint32_t total = lines * g.NC;
     int st;
@@ -1120,8 +1259,10 @@ class Engine : public IEngine {
     MSMZ_HIP(hipGetLastError());
     return MSMZ_OK;
   }
-  // Horner over the windows with the two results of every bucket set: acc = (acc * 2^(c-b) + A) * 2^b + B
-  void finalize_weierstrass_2d(const Plan& pl, uint8_t* out, int* out_inf) {
+  // Horner over the windows with the two results of every bucket set: acc = (acc * 2^(c-b) + A) * 2^b + B.
+  // res2: the problem's 2 Keff results (default: the single MSM's, fetched behind h_final_'s first kMaxWindows records)
+  void finalize_weierstrass_2d(const Plan& pl, uint8_t* out, int* out_inf, const uint32_t* res2 = nullptr) {
+    if (!res2) res2 = h_final_ + (size_t)kMaxWindows * XW;
     using H = Host64<F>;
     typename H::Pt acc, w, t;
     host64_.set_inf(acc);
@@ -1131,7 +1272,7 @@ class Engine : public IEngine {
       const int lo = k, hi = (k == pl.K - 1) ? pl.Keff - 1 : k;
       if (which == 0 && k == pl.K - 1 && pl.fold_shift != 0) return;   // folded top window: its rows are copies, not weights
       for (int kw = lo; kw <= hi; kw++) {
-        host64_.load_pt(w, h_final_ + (size_t)(kMaxWindows + 2 * kw + which) * XW);
+        host64_.load_pt(w, res2 + (size_t)(2 * kw + which) * XW);
         host64_.add_pt(t, acc, w);
         acc = t;
       }
@@ -1189,21 +1330,26 @@ class Engine : public IEngine {
   }
 
   // ------------------------------------------------------------------------------------------ Weierstrass, affine buckets
+  // nprob > 1: a batched MSM of nprob problems over the same points (scalars of problem p at d_scalars + p n 8, results
+  // at out + p 2 FE_BYTES / out_inf[p]): one sort, one plan, one train of tree rounds and one two-dimensional reduction
+  // over nprob * Keff bucket sets.  MSMZ_ERR_BATCH_LOOP: this plan does not batch (msm_batch runs the problems one by one).
   int msm_weierstrass_affine(const Handle& pts, const uint32_t* d_points, const uint32_t* d_scalars, uint64_t n64,
-                             const msmz_opts& opt, uint8_t* out, int* out_inf, msmz_log* log, int extra_bits = 0) {
+                             const msmz_opts& opt, uint8_t* out, int* out_inf, msmz_log* log, int extra_bits = 0,
+                             uint32_t nprob = 1) {
     const bool glv = opt.glv != 0;
     if (glv && (!Fr::HAS_GLV || !pts.has_endo)) return MSMZ_ERR_UNSUPPORTED;
     Plan pl;
     const bool want_2d = opt.reserved[0] != 1 && reduce2d_;
-    int st = make_plan(pl, n64, glv, opt, (uint32_t)pts.n, true, extra_bits, want_2d);
+    int st = make_plan(pl, n64, glv, opt, (uint32_t)pts.n, true, extra_bits, want_2d, nprob);
     if (st) return st;
+    if (nprob > 1 && (!want_2d || pl.L < 2 || !sort2_applies(pl))) return MSMZ_ERR_BATCH_LOOP;
     // location words hold a record index in 30 bits
-    if ((uint64_t)pl.K * pl.M >= (1ull << 30)) return MSMZ_ERR_ARG;
+    if ((uint64_t)nprob * pl.K * pl.M >= (1ull << 30)) return MSMZ_ERR_ARG;
     // whole groups of 64 records; + the records of the batched-affine first reduction level when it is selected
     const size_t f2_records = opt.reserved[0] == 1 ? (size_t)13 * pl.Keff * ((pl.L + 1) / 2) + 256 : 0;
-    if ((st = slots_.ensure(((size_t)pl.K * pl.M + 64 + f2_records) * SlotFmt<F>::WORDS * 4))) return st;
+    if ((st = slots_.ensure(((size_t)nprob * pl.K * pl.M + 64 + f2_records) * SlotFmt<F>::WORDS * 4))) return st;
     if ((st = sort_phase(pl, d_scalars))) return st;
-    const uint32_t nb = pl.nb;
+    const uint32_t nb = pl.nb * nprob;   // buckets of all problems
     MsmMeta* d_meta = meta_.as<MsmMeta>();
 
     // ---- plan: descriptors of every pair of every round + what is left of each bucket (plan_kernels.h)
@@ -1218,7 +1364,7 @@ class Engine : public IEngine {
     pc.chunk = chunk;
     pc.nb_main = nb;
     pc.chunk_top = chunk;
-    if (!no_plan_top_ && pl.K > 1 && pl.fold_shift == 0 && chunk >= 128 &&
+    if (!no_plan_top_ && nprob == 1 && pl.K > 1 && pl.fold_shift == 0 && chunk >= 128 &&
         (uint64_t)pl.L * 10 > ((uint64_t)pl.top_range << pl.spread) * 13) {
       pc.nb_main = (uint32_t)(pl.K - 1) * pl.L;
       pc.chunk_top = chunk / 2;
@@ -1228,7 +1374,7 @@ class Engine : public IEngine {
     // chunk totals per round, then the per-workgroup scratch of the rounds beyond PLAN_RL
     const size_t pair_words = (size_t)n_chunks * (PLAN_RMAX - PLAN_RL) * PLAN_T;
     if ((st = rscan_.ensure(((size_t)PLAN_RMAX * n_chunks + pair_words) * 4 + kTraceBytes * n_chunks))) return st;
-    if ((st = desc_.ensure((size_t)pl.K * pl.M * 8))) return st;
+    if ((st = desc_.ensure((size_t)nprob * pl.K * pl.M * 8))) return st;
     if ((st = bfin_.ensure((size_t)nb * 16))) return st;
     // the batched-affine first reduction level (opt.reserved[0] = 1) wants ONE sum per bucket: no rounds skipped
     const bool f2 = opt.reserved[0] == 1 && pl.L >= 2;
@@ -1281,10 +1427,22 @@ class Engine : public IEngine {
       if ((st = reduce_2d<P>(pl, d_points))) return st;
       const int ev_red_end2 = pl.ei;
       mark(pl);
-      if ((st = fetch_window_sums<P>(pl, 0, 2u * (uint32_t)pl.Keff))) return st;
+      const uint32_t* fin = nullptr;
+      if (nprob == 1) {
+        if ((st = fetch_window_sums<P>(pl, 0, 2u * (uint32_t)pl.Keff))) return st;
+      } else {   // all problems' window results in one copy
+        const size_t words = (size_t)2 * nprob * pl.Keff * XW;
+        if ((st = ensure_batch_final(words))) return st;
+        MSMZ_HIP(hipGetLastError());
+        MSMZ_HIP(hipMemcpyAsync(h_bfinal_, final_.p, words * 4, hipMemcpyDeviceToHost, stream_));
+        MSMZ_HIP(hipMemcpyAsync(h_meta_, meta_.p, sizeof(MsmMeta), hipMemcpyDeviceToHost, stream_));
+        MSMZ_HIP(hipStreamSynchronize(stream_));
+        fin = h_bfinal_;
+      }
       auto t_host2 = std::chrono::steady_clock::now();
       if (h_meta_->error & 1u) return MSMZ_ERR_DEGENERATE;
-      finalize_weierstrass_2d(pl, out, out_inf);
+      for (uint32_t p = 0; p < nprob; p++)
+        finalize_weierstrass_2d(pl, out + (size_t)p * RW * 4, out_inf + p, fin ? fin + (size_t)2 * p * pl.Keff * XW : nullptr);
       float host_ms2 = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_host2).count();
       fill_log(log, pl, R, n_pairs, ev_plan0, ev_plan1, ev_acc_end, ev_red_end2, round_ev0, host_ms2);
       return MSMZ_OK;
@@ -1672,6 +1830,17 @@ class Engine : public IEngine {
   bool basic_2d_ = false;   // the last msmBasic call reduced its buckets two-dimensionally (two results per bucket set)
   MsmMeta* h_meta_ = nullptr;
   uint32_t* h_final_ = nullptr;
+  uint32_t* h_bfinal_ = nullptr;   // pinned: the window results of every problem of a batched MSM
+  size_t h_bfinal_words_ = 0;
+  int ensure_batch_final(size_t words) {
+    if (words <= h_bfinal_words_) return MSMZ_OK;
+    if (h_bfinal_) (void)hipHostFree(h_bfinal_);
+    h_bfinal_ = nullptr;
+    h_bfinal_words_ = 0;
+    MSMZ_HIP(hipHostMalloc(&h_bfinal_, words * 4));
+    h_bfinal_words_ = words;
+    return MSMZ_OK;
+  }
 };
 
 }  // namespace msmz

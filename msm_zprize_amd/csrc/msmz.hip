@@ -171,6 +171,17 @@ int msmz_msm_resident(msmz_ctx* c, uint64_t ph, uint64_t sh, uint64_t n, const m
   return c->engine->msm(ph, nullptr, sh, n, o, out, out_inf, log);
 }
 
+int msmz_msm_batch(msmz_ctx* c, uint64_t ph, const uint8_t* scalars, uint64_t n, uint32_t batch, const msmz_opts* o,
+                   uint8_t* out, int* out_inf, msmz_log* log) {
+  if (!c || !scalars) return MSMZ_ERR_ARG;
+  return c->engine->msm_batch(ph, scalars, 0, n, batch, o, out, out_inf, log);
+}
+int msmz_msm_batch_resident(msmz_ctx* c, uint64_t ph, uint64_t sh, uint64_t n, uint32_t batch, const msmz_opts* o,
+                            uint8_t* out, int* out_inf, msmz_log* log) {
+  if (!c) return MSMZ_ERR_ARG;
+  return c->engine->msm_batch(ph, nullptr, sh, n, batch, o, out, out_inf, log);
+}
+
 int msmz_test_set_glv_bits(msmz_ctx* c, int bits) { return c ? c->engine->test_set_glv_bits(bits) : MSMZ_ERR_ARG; }
 int msmz_test_retries(msmz_ctx* c) { return c ? c->engine->test_retries() : -1; }
 int msmz_test_field(msmz_ctx* c, int op, const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out) {

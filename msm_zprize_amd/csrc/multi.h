@@ -46,6 +46,11 @@ class IEngine {
   virtual int msm(uint64_t ph, const uint8_t* host_scalars, uint64_t sh, uint64_t n, const msmz_opts* o, uint8_t* out,
                   int* out_inf, msmz_log* log, const GenMap* split = nullptr) = 0;
   // stage-level test hooks (include/msmz_test.h)
+  // `batch` MSMs over the same first n points (msmz_msm_batch): vector k = resident entries [k n, (k + 1) n), or host
+  // buffer entries [k host_stride, k host_stride + n) (host_stride 0 = n); out: batch results, out_inf: batch flags
+  virtual int msm_batch(uint64_t ph, const uint8_t* host_scalars, uint64_t sh, uint64_t n, uint32_t batch,
+                        const msmz_opts* o, uint8_t* out, int* out_inf, msmz_log* log, const GenMap* split = nullptr,
+                        uint64_t host_stride = 0) = 0;
   virtual int test_set_glv_bits(int) { return MSMZ_ERR_UNSUPPORTED; }
   virtual int test_retries() { return 0; }
   virtual int test_field(int, const uint8_t*, const uint8_t*, uint64_t, uint8_t*) { return MSMZ_ERR_UNSUPPORTED; }
@@ -60,6 +65,17 @@ class IEngine {
 };
 
 // entries of the first n that live on shard g of G
+// Problems per sub-batch of a batched MSM: at most `cap` entries (problems x entries_per_problem) per sub-batch, and the
+// `remaining` problems dealt into equally large sub-batches (64 problems with room for 40 -> 2 x 32, not 40 + 24).
+static inline uint32_t batch_split(uint32_t remaining, uint64_t entries_per_problem, uint64_t cap) {
+  if (remaining == 0) return 0;
+  uint64_t fit = entries_per_problem ? cap / entries_per_problem : remaining;
+  if (fit < 1) fit = 1;
+  if (fit >= remaining) return remaining;
+  const uint64_t parts = (remaining + fit - 1) / fit;
+  return (uint32_t)((remaining + parts - 1) / parts);
+}
+
 static inline uint64_t shard_count(uint64_t n, uint32_t g, uint32_t G, int shift = MULTI_BLOCK_SHIFT) {
   const uint64_t blk = 1ull << shift, cycle = blk * G;
   const uint64_t full = n / cycle, rem = n % cycle;
@@ -195,7 +211,65 @@ class MultiEngine : public IEngine {
                           out_inf);
       if (st) return st;
     }
-    if (log) {   // stage times: the slowest device; counts: summed
+    if (log) merge_device_logs(log, logs, used);
+    return MSMZ_OK;
+  }
+
+  // Every engine computes the batch's partial sums over its share of the points; the host adds them per problem.
+  // Resident scalars are gathered to the host first: vector k starts at entry k n of the set, which is not a block
+  // boundary of the devices' shares unless n is a multiple of the block cycle.
+  int msm_batch(uint64_t ph, const uint8_t* host_scalars, uint64_t sh, uint64_t n, uint32_t batch, const msmz_opts* o,
+                uint8_t* out, int* out_inf, msmz_log* log, const GenMap* = nullptr, uint64_t = 0) override {
+    if (!out || !out_inf || n == 0 || batch == 0) return MSMZ_ERR_ARG;
+    auto pit = handles_.find(ph);
+    if (pit == handles_.end() || pit->second.kind != 0 || pit->second.n < n) return MSMZ_ERR_ARG;
+    std::vector<uint8_t> gathered;
+    if (!host_scalars) {
+      auto sit = handles_.find(sh);
+      if (sit == handles_.end() || sit->second.kind != 1 || sit->second.n / batch < n) return MSMZ_ERR_ARG;
+      gathered.resize((size_t)batch * n * 32);
+      if (int st = download_scalars(sh, 0, (uint64_t)batch * n, gathered.data())) return st;
+      host_scalars = gathered.data();
+    }
+    const size_t rec = 2 * (size_t)fb_;
+    std::vector<std::vector<uint8_t>> part(G_, std::vector<uint8_t>(rec * batch));
+    std::vector<std::vector<int>> pinf(G_, std::vector<int>(batch, 1));
+    std::vector<int> used(G_, 0);
+    std::vector<msmz_log> logs(G_);
+    const MHandle& pts = pit->second;
+    int st = for_all([&](uint32_t g, IEngine* e) {
+      const uint64_t cnt = shard_count(n, g, G_);
+      if (cnt == 0) return (int)MSMZ_OK;
+      used[g] = 1;
+      const GenMap split{G_, g, MULTI_BLOCK_SHIFT};   // the device copies its own blocks of every vector
+      return e->msm_batch(pts.sub[g], host_scalars, 0, cnt, batch, o, part[g].data(), pinf[g].data(), &logs[g], &split, n);
+    });
+    if (st) return st;
+    for (uint32_t k = 0; k < batch; k++) {
+      uint8_t* ok = out + (size_t)k * rec;
+      bool first = true;
+      for (uint32_t g = 0; g < G_; g++) {
+        if (!used[g]) continue;
+        const uint8_t* pk = part[g].data() + (size_t)k * rec;
+        if (first) {
+          memcpy(ok, pk, rec);
+          out_inf[k] = pinf[g][k];
+          first = false;
+          continue;
+        }
+        std::vector<uint8_t> acc(ok, ok + rec);
+        const int ai = out_inf[k];
+        st = msmz_point_add(curve_id_, ai ? nullptr : acc.data(), ai, pinf[g][k] ? nullptr : pk, pinf[g][k], ok,
+                            &out_inf[k]);
+        if (st) return st;
+      }
+    }
+    if (log) merge_device_logs(log, logs, used);
+    return MSMZ_OK;
+  }
+
+  void merge_device_logs(msmz_log* log, const std::vector<msmz_log>& logs, const std::vector<int>& used) const {
+    {   // stage times: the slowest device; counts: summed
       memset(log, 0, sizeof(*log));
       for (uint32_t g = 0; g < G_; g++) {
         if (!used[g]) continue;
@@ -214,7 +288,6 @@ class MultiEngine : public IEngine {
         log->glv = logs[g].glv;
       }
     }
-    return MSMZ_OK;
   }
 
   int test_set_glv_bits(int bits) override {

@@ -217,6 +217,11 @@ __global__ void __launch_bounds__(COARSE_T, 8) k_hist(uint32_t* counts, uint16_t
   constexpr int HALVES = GLV ? 2 : 1;
   constexpr int PER = COARSE_ITEMS / HALVES;   // scalars per thread: one workgroup = one tile of k_coarse
   const uint32_t L = 1u << (g.c - 1);
+  // batched MSM: problem blockIdx.y sorts scalar vector blockIdx.y into its own slice of the bin counts and tile rows
+  scalars += (size_t)blockIdx.y * g.n * 8;
+  counts += (size_t)blockIdx.y * nbins;
+  tile_counts += (size_t)blockIdx.y * gridDim.x * nbins;
+  tile_offs += (size_t)blockIdx.y * gridDim.x * nbins;
   for (uint32_t b = threadIdx.x; b < nbins; b += COARSE_T) s_hist[b] = 0;
   __syncthreads();
   uint32_t bad = 0;
@@ -345,8 +350,14 @@ __global__ void __launch_bounds__(COARSE_T, 8) k_coarse(uint32_t* packed_out, co
   __shared__ uint32_t s_wstart[kMaxWindowsSort + 1];   // staging offset of every window's first bin; [K] = tile total
   const uint32_t L = 1u << (g.c - 1);
 #ifdef MSMZ_TRACE
-  uint64_t* trace = reinterpret_cast<uint64_t*>(const_cast<uint32_t*>(tile_offs) + (size_t)gridDim.x * nbins);
+  uint64_t* trace = reinterpret_cast<uint64_t*>(const_cast<uint32_t*>(tile_offs) + (size_t)gridDim.x * gridDim.y * nbins);
 #endif
+  // batched MSM: problem blockIdx.y; its bins start at bin blockIdx.y * nbins of ONE scan over all problems, so the
+  // packed words of every problem land in one dense array
+  scalars += (size_t)blockIdx.y * g.n * 8;
+  bin_base += (size_t)blockIdx.y * nbins;
+  tile_counts += (size_t)blockIdx.y * gridDim.x * nbins;
+  tile_offs += (size_t)blockIdx.y * gridDim.x * nbins;
   MSMZ_STAMP(trace, 0);
   MSMZ_STAMP_HW(trace);
 
@@ -513,6 +524,13 @@ static __global__ void __launch_bounds__(FINE_T) k_fine(uint32_t* refs, uint32_t
   uint32_t* s_stage = s_dyn + (1 << FINE_MAX_BITS);          // [FINE_STAGE]
   __shared__ uint32_t s_wave[FINE_T / 64];
   __shared__ uint32_t s_wmax[FINE_T / 64];
+#ifdef MSMZ_TRACE
+  uint64_t* trace = reinterpret_cast<uint64_t*>(const_cast<uint32_t*>(bin_base) + ((gridDim.y * n_bins + 2) & ~1u));
+#endif
+  // batched MSM: problem blockIdx.y owns bins [y n_bins, (y + 1) n_bins) of the global scan and buckets
+  // [y nb, (y + 1) nb) of `off`; its last bin's end is the next problem's first offset (the same value is written twice)
+  bin_base += (size_t)blockIdx.y * n_bins;
+  off += (size_t)blockIdx.y * (((size_t)top_bin << fb) + ((size_t)(n_bins - top_bin) << fbt));
   // last bins first: the top window's bins are the only ones that are structurally above average (its digit range is
   // not a power of two, so its buckets are up to 2x denser), and the workgroups that start first should be the long ones
   const uint32_t bin = n_bins - 1u - blockIdx.x;
@@ -530,9 +548,6 @@ static __global__ void __launch_bounds__(FINE_T) k_fine(uint32_t* refs, uint32_t
   }
   const bool staged = cnt_bin <= (uint32_t)FINE_STAGE;   // the bin fits the threads' registers (and the LDS staging)
   const uint32_t imask = (1u << idx_bits) - 1u;
-#ifdef MSMZ_TRACE
-  uint64_t* trace = reinterpret_cast<uint64_t*>(const_cast<uint32_t*>(bin_base) + ((n_bins + 2) & ~1u));
-#endif
   MSMZ_STAMP(trace, 0);
   MSMZ_STAMP_HW(trace);
   for (uint32_t f = threadIdx.x; f < nfine; f += FINE_T) s_cnt[f] = 0;

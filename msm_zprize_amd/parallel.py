@@ -191,11 +191,87 @@ class _Parallel:
         """msm-batched-affine.ts:574-586."""
         return self._msm(scalars, points, N, verbose, options, 0, 0)
 
+    # -- batched MSM: many scalar vectors against one resident point set ---------------------------
+    def _msm_batch(self, scalarsList, points, N, options, safe):
+        options = dict(options or {})
+        if N <= 0 or N > len(points):
+            raise ValueError(f"msmBatch: N = {N} but the point set holds {len(points)}")
+        kind, data, B = batch_scalars(scalarsList, N, options.get("batch"))
+        opts = MsmzOpts()
+        opts.c = int(options.get("c") or 0)
+        opts.glv = int(options.get("glv", self._c.default_glv))
+        opts.safe = int(options.get("useSafeAdditions", safe))
+        opts.buckets = int(options.get("buckets", 0))
+        opts.reserved[0] = int(options.get("reduceAffine", 0))
+        fb = self._c.fe_bytes
+        out = C.create_string_buffer(2 * fb * B)
+        inf = (C.c_int * B)()
+        log = MsmzLog()
+        if kind == "resident":
+            st = lib().msmz_msm_batch_resident(self._c._ctx, points.handle, data.handle, N, B, C.byref(opts), out, inf,
+                                               C.byref(log))
+        else:
+            st = lib().msmz_msm_batch(self._c._ctx, points.handle, data, N, B, C.byref(opts), out, inf, C.byref(log))
+        check(st, "msmz_msm_batch")
+        self.lastBatchLog = log
+        raw = out.raw
+        results = []
+        for k in range(B):
+            r = {"x": int.from_bytes(raw[2 * fb * k:2 * fb * k + fb], "little"),
+                 "y": int.from_bytes(raw[2 * fb * k + fb:2 * fb * (k + 1)], "little"), "isZero": inf[k] != 0}
+            if r["isZero"] and self._c.kind == "weierstrass":
+                r["x"], r["y"] = 0, 1
+            results.append(r)
+        return results
+
+    def msmBatch(self, scalarsList, points, N, options=None):
+        """B MSMs over the first N points in one device pipeline (msmz_msm_batch): `scalarsList` is ONE resident
+        scalar array of >= B * N scalars (vector k = entries [k N, (k + 1) N); B = options["batch"], default
+        len // N) or a list of B host arrays in the scalarsFromBytes byte format.  Returns the B results, each in the
+        form of msm()["result"]; the log of the call is left in `lastBatchLog`.  Safe additions."""
+        return self._msm_batch(scalarsList, points, N, options, 1)
+
+    def msmBatchUnsafe(self, scalarsList, points, N, options=None):
+        """msmBatch with unsafe additions (msmUnsafe)."""
+        return self._msm_batch(scalarsList, points, N, options, 0)
+
     def msmProjective(self, scalars, points, N, options=None):
         """parallel.ts:69-87: no GLV, projective buckets (msm-basic.ts)."""
         options = dict(options or {})
         options["glv"] = 0
         return self._msm(scalars, points, N, True, options, 1, 1)
+
+
+def batch_scalars(scalarsList, N, batch=None):
+    """The scalar argument of msmBatch -> ("resident", array, B) or ("host", concatenated bytes, B).  The C ABI takes one
+    contiguous scalar set, so a list of separate resident arrays is refused."""
+    if N <= 0:
+        raise ValueError(f"msmBatch: N = {N}")
+    if isinstance(scalarsList, DeviceArray):
+        if scalarsList.kind != "scalars":
+            raise ValueError("msmBatch: the resident array holds points, not scalars")
+        B = len(scalarsList) // N if batch is None else int(batch)
+        if B <= 0 or B * N > len(scalarsList):
+            raise ValueError(f"msmBatch: {B} vectors of N = {N} scalars need {max(B, 1) * N}, the resident array "
+                             f"holds {len(scalarsList)}")
+        return "resident", scalarsList, B
+    if isinstance(scalarsList, (bytes, bytearray, memoryview, str)) or not hasattr(scalarsList, "__len__"):
+        raise TypeError("msmBatch: scalarsList is one resident scalar array or a list of host byte arrays")
+    vecs = list(scalarsList)
+    if not vecs:
+        raise ValueError("msmBatch: no scalar vectors")
+    if any(isinstance(v, DeviceArray) for v in vecs):
+        raise TypeError("msmBatch: a list of resident arrays is not accepted; pass ONE resident array of B * N "
+                        "scalars or a list of host byte arrays")
+    vecs = [bytes(v) for v in vecs]
+    lens = {len(v) for v in vecs}
+    if len(lens) != 1:
+        raise ValueError(f"msmBatch: scalar vectors of unequal length {sorted(lens)}")
+    if lens.pop() < 32 * N:
+        raise ValueError(f"msmBatch: a vector of {len(vecs[0])} bytes holds fewer than N = {N} scalars")
+    if batch is not None and int(batch) != len(vecs):
+        raise ValueError(f"msmBatch: batch = {batch} but {len(vecs)} vectors were given")
+    return "host", b"".join(v[:32 * N] for v in vecs), len(vecs)
 
 
 def _format_log(log):

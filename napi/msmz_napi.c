@@ -272,6 +272,55 @@ static napi_value Msm(napi_env env, napi_callback_info info) {
   return res;
 }
 
+/* msmBatch(ctx, pointsHandle, scalars (handle number of >= batch * n scalars, or one Buffer of batch vectors), n, batch,
+ * feBytes, opts) -> {xy (batch records), isInf (batch flags in a Buffer)} */
+static napi_value MsmBatch(napi_env env, napi_callback_info info) {
+  size_t argc = 7; napi_value argv[7];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  msmz_ctx* ctx; if (!get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "msmBatch");
+  uint64_t ph, n, batch, fb;
+  if (argc < 6 || !get_u64(env, argv[1], &ph) || !get_u64(env, argv[3], &n) || !get_u64(env, argv[4], &batch) ||
+      !get_u64(env, argv[5], &fb) || batch == 0 || batch > 0xffffffffu || fb > 64)
+    return throw_status(env, MSMZ_ERR_ARG, "msmBatch");
+  msmz_opts o; memset(&o, 0, sizeof(o));
+  if (argc > 6) {
+    o.c = opt_i32(env, argv[6], "c");
+    o.glv = opt_i32(env, argv[6], "glv");
+    o.safe = opt_i32(env, argv[6], "safe");
+    o.buckets = opt_i32(env, argv[6], "buckets");
+    o.reserved[0] = opt_i32(env, argv[6], "reduceAffine");
+  }
+  void* data; napi_value xy;
+  NAPI_CALL(env, napi_create_buffer(env, (size_t)(2 * fb * batch), &data, &xy));
+  int* flags = (int*)calloc((size_t)batch, sizeof(int));
+  if (!flags) return throw_status(env, MSMZ_ERR_ARG, "msmBatch");
+  bool isbuf = false; napi_is_buffer(env, argv[2], &isbuf);
+  int st;
+  if (isbuf) {
+    void* s; size_t slen;
+    if (napi_get_buffer_info(env, argv[2], &s, &slen) != napi_ok || n == 0 || slen / 32 / n < batch) {
+      free(flags);
+      return throw_status(env, MSMZ_ERR_ARG, "msmBatch");
+    }
+    st = msmz_msm_batch(ctx, ph, (const uint8_t*)s, n, (uint32_t)batch, &o, (uint8_t*)data, flags, NULL);
+  } else {
+    uint64_t sh;
+    if (!get_u64(env, argv[2], &sh)) { free(flags); return throw_status(env, MSMZ_ERR_ARG, "msmBatch"); }
+    st = msmz_msm_batch_resident(ctx, ph, sh, n, (uint32_t)batch, &o, (uint8_t*)data, flags, NULL);
+  }
+  void* fdata = NULL; napi_value inf;
+  if (st == 0 && napi_create_buffer(env, (size_t)batch, &fdata, &inf) == napi_ok)
+    for (uint64_t k = 0; k < batch; k++) ((uint8_t*)fdata)[k] = flags[k] ? 1 : 0;
+  free(flags);
+  if (st) return throw_status(env, st, "msmz_msm_batch");
+  if (!fdata) return throw_status(env, MSMZ_ERR_ARG, "msmBatch");
+  napi_value res;
+  NAPI_CALL(env, napi_create_object(env, &res));
+  napi_set_named_property(env, res, "xy", xy);
+  napi_set_named_property(env, res, "isInf", inf);
+  return res;
+}
+
 /* pointAdd(curveId, aXy|null, bXy|null, feBytes) -> {xy, isInf}  (null = infinity) */
 static napi_value PointAdd(napi_env env, napi_callback_info info) {
   size_t argc = 4; napi_value argv[4];
@@ -307,7 +356,7 @@ static napi_value Init(napi_env env, napi_value exports) {
   static const struct { const char* name; napi_callback fn; } fns[] = {
       {"create", Create}, {"destroy", Destroy}, {"uploadPoints", UploadPoints}, {"uploadScalars", UploadScalars},
       {"randomPoints", RandomPoints}, {"randomScalars", RandomScalars}, {"downloadPoints", DownloadPoints},
-      {"downloadScalars", DownloadScalars}, {"free", Free}, {"msm", Msm}, {"pointAdd", PointAdd}, {"feBytes", FeBytes}};
+      {"downloadScalars", DownloadScalars}, {"free", Free}, {"msm", Msm}, {"msmBatch", MsmBatch}, {"pointAdd", PointAdd}, {"feBytes", FeBytes}};
   for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); i++) {
     napi_value f;
     if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;
