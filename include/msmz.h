@@ -146,6 +146,32 @@ int msmz_msm_batch_resident(msmz_ctx* ctx, uint64_t points_handle, uint64_t scal
                             uint32_t batch, const msmz_opts* opts, uint8_t* out_xy_le, int* out_is_inf,
                             msmz_log* log /* nullable */);
 
+/* Fixed-base precomputation of a resident point set.  The new handle holds `factor` copies of the
+ * first n points of points_handle, copy j = 2^(c j) * P_i, so that window k of every scalar adds into bucket set
+ * floor(k / factor) with copy k mod factor: ceil(K / factor) bucket reductions per MSM instead of K, and a Horner with
+ * (factor - 1) fewer doubling runs per set.  factor 0 = all windows (one bucket set per MSM; the copies also cover the
+ * window count of the GLV retry); 1 is MSMZ_ERR_ARG; a factor above the window count is lowered to it.  opts->c /
+ * opts->glv fix the window size and the GLV choice the copies are built for (0 / -1 = the engine's choice for n; a null
+ * opts means both); opts->safe / timing play no part.  The new handle owns its memory: the source handle may be freed.
+ * Memory: factor * R records of the point stride (R = n, or 2n with GLV: the endomorphism images follow the base points in
+ * every copy), e.g. 2 GiB for 2^20 BLS12-377 points at c = 16, factor 0.
+ * Limits (MSMZ_ERR_ARG at precompute time): the records fit the 30-bit record index (factor * R < 2^30), one bucket can
+ * hold every entry of its set (min(factor, K) * n entries, 2n with GLV, below 2^26: all digits equal), and a bucket set
+ * of min(factor, K) windows of n (2n with GLV) entries fits one pass of the two-level sort (n <= 2^24 entries; a window
+ * at most 512 coarse bins, all windows at most 8192).  Twisted Edwards, MSMZ_BUCKETS_PROJECTIVE and reserved[0] = 1 are
+ * MSMZ_ERR_UNSUPPORTED, here and in every MSM over a precomputed handle.
+ * Use: msmz_msm, msmz_msm_resident, msmz_msm_batch and msmz_msm_batch_resident take the precomputed handle wherever they
+ * take points_handle, n up to its n, and return bit-identical results to the plain handle; opts.c must be 0 or the
+ * handle's c and opts.glv -1 or the handle's choice (else MSMZ_ERR_ARG).  msmz_download_points reads its records: copy j
+ * at [j R, (j + 1) R) (a multi-device context: the first n records, copy 0).  msmz_free releases it.  On a multi-device
+ * context every engine precomputes its own share of the points. */
+int msmz_precompute_points(msmz_ctx* ctx, uint64_t points_handle, uint64_t n, const msmz_opts* opts, uint32_t factor,
+                           uint64_t* handle);
+/* what a precomputed handle was built with (any pointer may be null): window size, GLV choice, copies, windows K of an
+ * MSM over it and records (factor * R, all devices) */
+int msmz_precomputed_info(msmz_ctx* ctx, uint64_t handle, int32_t* c, int32_t* glv, uint32_t* factor, uint32_t* K,
+                          uint64_t* records);
+
 /* Host-side group addition of two canonical affine results: combines per-GPU partial sums
  * (the reference's "partition sum" step, msm-batched-affine.ts:300-307). */
 int msmz_point_add(int curve_id, const uint8_t* a_xy_le, int a_is_inf, const uint8_t* b_xy_le, int b_is_inf,

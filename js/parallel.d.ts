@@ -5,7 +5,9 @@ export type CurveParams = {
   generator: { x: bigint; y: bigint }; endomorphism?: { lambda: bigint; beta: bigint };
 };
 export type BigintPoint = { x: bigint; y: bigint; isZero?: boolean };
-export interface DeviceArray extends Array<DeviceArray> { readonly n: number; readonly kind: "points" | "scalars"; free(): void }
+export interface DeviceArray extends Array<DeviceArray> { readonly n: number; readonly kind: "points" | "scalars" | "precomputed";
+  /** precomputed point sets only (msmz_precomputed_info) */
+  readonly info?: { c: number; glv: number; factor: number; K: number; records: number }; free(): void }
 export type MsmOptions = { c?: number; glv?: boolean | number; useSafeAdditions?: boolean; reduceAffine?: boolean };
 export type MsmResult = { result: BigintPoint; log: any[][]; stats: Record<string, any> };
 export interface ParallelApi {
@@ -20,6 +22,10 @@ export interface ParallelApi {
   scalarsFromBytes(scalarPtr: number, scalarInputPtr: number, n: number): Promise<void>;
   msm(scalars: DeviceArray | Uint8Array | number, points: DeviceArray | number, n: number, verbose?: boolean, options?: MsmOptions): Promise<MsmResult>;
   msmUnsafe(scalars: DeviceArray | Uint8Array | number, points: DeviceArray | number, n: number, verbose?: boolean, options?: MsmOptions): Promise<MsmResult>;
+  /** fixed-base precomputation: the result goes wherever `points` is taken (factor 0 = all windows in one bucket set) */
+  precomputePoints(points: DeviceArray, n: number, options?: { c?: number; glv?: boolean | number }, factor?: number): Promise<DeviceArray>;
+  msmBatch(scalarsList: DeviceArray | Uint8Array[], points: DeviceArray, n: number, options?: MsmOptions & { batch?: number }): Promise<BigintPoint[]>;
+  msmBatchUnsafe(scalarsList: DeviceArray | Uint8Array[], points: DeviceArray, n: number, options?: MsmOptions & { batch?: number }): Promise<BigintPoint[]>;
   msmProjective?(scalars: DeviceArray | Uint8Array, points: DeviceArray, n: number, options?: MsmOptions): Promise<MsmResult>;
 }
 export interface MsmCurve {

@@ -217,6 +217,23 @@ function createCurve(params, kind) {
   }
 
   const Parallel = {
+    /** fixed-base precomputation of the first n resident points (include/msmz.h msmz_precompute_points): a DeviceArray
+     * of kind "precomputed" that msm / msmUnsafe / msmBatch / msmBatchUnsafe take in place of the points (same results).
+     * factor = windows sharing one bucket set (0 = all; 1 is refused); options.c / options.glv fix the window size and
+     * the GLV choice (default: the engine's).  The copies' parameters are in the array's `info`. */
+    async precomputePoints(points, n, options, factor = 0) {
+      options = options || {};
+      if (!(points instanceof DeviceArray) || points.kind !== "points")
+        throw TypeError("precomputePoints: `points` is a resident point array (pointsFromBytes / randomPointsFast)");
+      if (!Number.isInteger(n) || n < 1 || n > points.n) throw Error(`precomputePoints: n = ${n} but the point set holds ${points.n}`);
+      if (!Number.isInteger(factor) || factor < 0 || factor === 1 || factor >= 2 ** 32)
+        throw Error(`precomputePoints: factor = ${factor} (0 = all windows, or 2, 3, ...)`);
+      const opts = { c: options.c || 0, glv: options.glv !== undefined ? Number(options.glv) : -1 };
+      const h = N.precomputePoints(ctx, points.handle, n, opts, factor);
+      const arr = DeviceArray.make(curve, h, n, "precomputed");
+      Object.defineProperty(arr, "info", { value: N.precomputedInfo(ctx, h) });
+      return arr;
+    },
     /** batched MSM: B scalar vectors against one point set (include/msmz.h msmz_msm_batch); safe additions */
     msmBatch: (scalarsList, points, n, options) => msmBatchCommon(scalarsList, points, n, options, 1),
     msmBatchUnsafe: (scalarsList, points, n, options) => msmBatchCommon(scalarsList, points, n, options, 0),

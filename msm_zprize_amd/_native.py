@@ -48,6 +48,10 @@ EXPORTS = {
                                  C.c_char_p, C.POINTER(C.c_int), C.POINTER(MsmzLog)]),
     "msmz_msm_batch_resident": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                           C.POINTER(MsmzOpts), C.c_char_p, C.POINTER(C.c_int), C.POINTER(MsmzLog)]),
+    "msmz_precompute_points": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(MsmzOpts), C.c_uint32,
+                                         C.POINTER(C.c_uint64)]),
+    "msmz_precomputed_info": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "msmz_point_add": (C.c_int, [C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.POINTER(C.c_int)]),
     # stage-level test hooks (include/msmz_test.h)
     "msmz_test_set_glv_bits": (C.c_int, [C.c_void_p, C.c_int]),

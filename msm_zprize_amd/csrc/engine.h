@@ -64,7 +64,18 @@ struct Handle {
   uint64_t n;
   bool has_endo;   // points: records [n, 2n) hold the endomorphism images
   void* dev;
+  // precomputed point set (msmz_precompute_points): `factor` copies, copy j = records [j R, (j + 1) R) holds 2^(c j) P_i
+  // (R = copy_stride = n, or 2 n with the endomorphism images); built for window size c and GLV choice glv.  0 = plain.
+  uint32_t factor = 0;
+  int c = 0, glv = 0;
+  uint64_t copy_stride = 0;
 };
+
+static inline int copy_bits(uint32_t F) {   // bits of a copy index below F
+  int r = 0;
+  while ((1u << r) < F) r++;
+  return r;
+}
 
 static inline int ceil_log2_u64(uint64_t x) {
   int r = 0;
@@ -359,7 +370,9 @@ class Engine : public IEngine {
     auto it = handles_.find(hd);
     if (it == handles_.end() || it->second.kind != 0 || !xy) return MSMZ_ERR_ARG;
     {
-      const uint64_t have = it->second.n * (it->second.has_endo ? 2 : 1);   // the endomorphism images stay readable
+      // the endomorphism images stay readable; a precomputed set: all its copies
+      const uint64_t have = it->second.factor ? it->second.copy_stride * it->second.factor
+                                              : it->second.n * (it->second.has_endo ? 2 : 1);
       if (first > have || count > have - first) return MSMZ_ERR_ARG;        // (no first + count: it can wrap)
     }
     if (count == 0) return MSMZ_OK;
@@ -405,6 +418,122 @@ class Engine : public IEngine {
     return MSMZ_OK;
   }
 
+  // ------------------------------------------------------------------------------------------ precomputed point sets
+  // The options of an MSM over handle `h`: a precomputed set fixes c and the GLV choice (opts->c must be 0 or its c,
+  // opts->glv -1 or its choice; a null opts means both defaults) and takes batched-affine buckets with the 2-D reduction.
+  int resolve_opts(const Handle& h, const msmz_opts* o, msmz_opts* opt) const {
+    memset(opt, 0, sizeof(*opt));
+    if (o) *opt = *o;
+    if (!h.factor) return MSMZ_OK;
+    if (!o) opt->glv = -1;
+    if (opt->buckets == MSMZ_BUCKETS_PROJECTIVE || opt->reserved[0] == 1) return MSMZ_ERR_UNSUPPORTED;
+    if ((opt->c != 0 && opt->c != h.c) || (opt->glv >= 0 && (opt->glv != 0) != (h.glv != 0))) return MSMZ_ERR_ARG;
+    opt->c = h.c;
+    opt->glv = h.glv;
+    return MSMZ_OK;
+  }
+
+  // What a precomputed set over n points is built with: c, GLV choice and copies (factor; 0 = enough copies for every
+  // window, the GLV retry's included).  Checks that its bucket sets fit one sort pass and its records the 30-bit field.
+  // bit length the windows are sized for (make_plan's pl.b): the whole scalar, or a GLV half -- the assumed bound, or
+  // with extra_bits the proven one of the retry
+  int scalar_bits(bool glv, int extra_bits) const {
+    if (!glv) return Fr::BITS;
+    if (extra_bits) return Fr::GLV_PROVEN_BITS > Fr::GLV_BITS - 1 ? Fr::GLV_PROVEN_BITS : Fr::GLV_BITS - 1;
+    return glv_bits_assumed_ > 0 ? glv_bits_assumed_ : Fr::GLV_BITS - 1;
+  }
+
+  int precompute_params(uint64_t n, const msmz_opts* o, uint32_t factor, int* c_out, int* glv_out,
+                        uint32_t* f_out, int* k_out) const override {
+    if (TE) return MSMZ_ERR_UNSUPPORTED;   // twisted Edwards runs msmBasic: no batched-affine buckets to share
+    if (n == 0 || factor == 1) return MSMZ_ERR_ARG;
+    msmz_opts opt;
+    memset(&opt, 0, sizeof(opt));
+    if (o) opt = *o; else opt.glv = -1;
+    if (opt.buckets == MSMZ_BUCKETS_PROJECTIVE || opt.reserved[0] == 1) return MSMZ_ERR_UNSUPPORTED;
+    if (opt.c < 0 || opt.c > 24) return MSMZ_ERR_ARG;
+    int glv = opt.glv;
+    if (glv < 0) glv = (Fr::HAS_GLV && n < (1ull << 15)) ? 1 : 0;   // msm()'s choice for n points
+    if (glv && !Fr::HAS_GLV) return MSMZ_ERR_UNSUPPORTED;
+    glv = glv ? 1 : 0;
+    const uint64_t M64 = glv ? 2 * n : n;
+    if (M64 > (1ull << 24)) return MSMZ_ERR_ARG;
+    const uint32_t M = (uint32_t)M64;
+    const int b0 = scalar_bits(glv != 0, 0), b1 = scalar_bits(glv != 0, 1);
+    // window size: the user's, or the model's for F copies (0: all windows in one set)
+    int c = opt.c;
+    auto windows = [&](int cc, int b) { return (b + 1 + cc - 1) / cc; };
+    if (c == 0) c = choose_window_pre(glv != 0, M, b0, 1, factor == 0 ? 1024u : factor);
+    if (c < 2) c = 2;
+    const int K0 = windows(c, b0), K1 = windows(c, b1);
+    const int Kmax = K0 > K1 ? K0 : K1;
+    const uint32_t copies = factor == 0 || factor > (uint32_t)Kmax ? (uint32_t)Kmax : factor;
+    if (copies < 2) return MSMZ_ERR_ARG;
+    if (!pre_fits(c, glv != 0, M, b0, copies) || !pre_fits(c, glv != 0, M, b1, copies)) return MSMZ_ERR_ARG;
+    const uint64_t records = (uint64_t)copies * n * (glv ? 2 : 1);
+    if (records >= (1ull << 30)) return MSMZ_ERR_ARG;   // location words: 30-bit record index
+    *c_out = c;
+    *glv_out = glv;
+    *f_out = copies;
+    if (k_out) *k_out = K0;
+    return MSMZ_OK;
+  }
+
+  // new handle: `F` copies of the first n points of `ph`, copy j = 2^(c j) P_i (+ the endomorphism images with glv)
+  int precompute_points(uint64_t ph, uint64_t n, int c, int glv, uint32_t copies, uint64_t* h) override {
+    if (TE) return MSMZ_ERR_UNSUPPORTED;
+    auto pit = handles_.find(ph);
+    if (!h || pit == handles_.end() || pit->second.kind != 0 || pit->second.factor != 0 || n == 0 || pit->second.n < n ||
+        copies < 2 || c < 2 || c > 24)
+      return MSMZ_ERR_ARG;
+    const Handle& src = pit->second;
+    if (glv && !src.has_endo) return MSMZ_ERR_UNSUPPORTED;
+    MSMZ_HIP(hipSetDevice(device_));
+    const uint64_t R = n * (glv ? 2 : 1);
+    const size_t rec = (size_t)PW_WORDS * 4;
+    void* dev = nullptr;
+    MSMZ_HIP(hipMalloc(&dev, (size_t)copies * R * rec));
+    // copy 0: the source's first n points (and their images, which follow the source's whole set)
+    hipError_t e = hipMemcpyAsync(dev, src.dev, n * rec, hipMemcpyDeviceToDevice, stream_);
+    if (e == hipSuccess && glv)
+      e = hipMemcpyAsync((uint8_t*)dev + n * rec, (const uint8_t*)src.dev + src.n * rec, n * rec, hipMemcpyDeviceToDevice,
+                         stream_);
+    for (uint32_t j = 1; j < copies && e == hipSuccess; j++) {
+      if constexpr (!TE)
+        hipLaunchKernelGGL((k_precompute_copy<F>), dim3((n + 255) / 256), dim3(256), 0, stream_,
+                           (uint32_t*)((uint8_t*)dev + j * R * rec), (const uint32_t*)((const uint8_t*)dev + (j - 1) * R * rec),
+                           (uint32_t)n, c, glv);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
+    if (e != hipSuccess) {
+      fprintf(stderr, "msmz: HIP error '%s' while precomputing a point set\n", hipGetErrorString(e));
+      (void)hipFree(dev);
+      return MSMZ_ERR_HIP;
+    }
+    Handle hd{0, n, glv != 0, dev};
+    hd.factor = copies;
+    hd.c = c;
+    hd.glv = glv;
+    hd.copy_stride = R;
+    *h = next_handle_++;
+    handles_[*h] = hd;
+    return MSMZ_OK;
+  }
+
+  int precomputed_info(uint64_t hd, int32_t* c, int32_t* glv, uint32_t* factor, uint32_t* K, uint64_t* records) override {
+    auto it = handles_.find(hd);
+    if (it == handles_.end() || it->second.factor == 0) return MSMZ_ERR_ARG;
+    const Handle& h = it->second;
+    const int b = scalar_bits(h.glv != 0, 0);
+    if (c) *c = h.c;
+    if (glv) *glv = h.glv;
+    if (factor) *factor = h.factor;
+    if (K) *K = (uint32_t)((b + 1 + h.c - 1) / h.c);
+    if (records) *records = h.copy_stride * h.factor;
+    return MSMZ_OK;
+  }
+
   // ------------------------------------------------------------------------------------------ msm
   // Largest number of (half-)scalars one pass sorts: index + negate + fine bucket bits share a 32-bit word.
   static constexpr uint64_t kMaxEntriesPerPass = 1ull << 24;
@@ -416,8 +545,8 @@ class Engine : public IEngine {
     auto pit = handles_.find(ph);
     if (pit == handles_.end() || pit->second.kind != 0 || pit->second.n < n) return MSMZ_ERR_ARG;
     msmz_opts opt;
-    memset(&opt, 0, sizeof(opt));
-    if (o) opt = *o;
+    int st0 = resolve_opts(pit->second, o, &opt);
+    if (st0) return st0;
     // glv < 0: the engine's choice.  The split halves the windows but doubles the point set (index bits, gathers, tree
     // depth); since the two-dimensional bucket reduction made the reduction cheap per window it is only ahead on the
     // smallest inputs (profiles/r03_sweep.json: 2^14 0.85 vs 0.88 ms, 2^16 1.11 vs 1.07, 2^20 3.87 vs 3.64, 2^23 23.5 vs 20.5).
@@ -500,8 +629,8 @@ class Engine : public IEngine {
     auto pit = handles_.find(ph);
     if (pit == handles_.end() || pit->second.kind != 0 || pit->second.n < n) return MSMZ_ERR_ARG;
     msmz_opts opt;
-    memset(&opt, 0, sizeof(opt));
-    if (o) opt = *o;
+    int st0 = resolve_opts(pit->second, o, &opt);
+    if (st0) return st0;
     // (the engine's choice of msm(): per problem size, so that batch = 1 is msm() exactly)
     if (opt.glv < 0) opt.glv = (!TE && Fr::HAS_GLV && pit->second.has_endo && n < (1ull << 15)) ? 1 : 0;
     if (host_stride == 0) host_stride = n;
@@ -571,7 +700,7 @@ class Engine : public IEngine {
     uint32_t bs = remaining;
     for (int it = 0; it < 4 && bs > 1; it++) {
       Plan pl;
-      if (make_plan(pl, n, opt.glv != 0, opt, (uint32_t)pts.n, true, 0, true, bs) != MSMZ_OK) {
+      if (make_plan(pl, n, opt.glv != 0, opt, (uint32_t)pts.n, true, 0, true, bs, pts.factor > 1 ? pts.factor : 1) != MSMZ_OK) {
         bs = (bs + 1) / 2;
         continue;
       }
@@ -754,6 +883,8 @@ class Engine : public IEngine {
     uint32_t endo_delta = 0;    // GLV over a prefix of a set: half-1 entry i reads point record pts_n + i = (n + i) + endo_delta
     uint32_t nprob = 1;         // batched MSM: problems (scalar vectors) sorted, planned and reduced together; nb, M, K,
                                 // Keff describe ONE problem, bucket set p * Keff + kw holds window kw of problem p
+    uint32_t F = 1;             // precomputed point set: windows per bucket set (Keff = ceil(K / F) sets); 1 = plain
+    uint32_t copy_stride = 0;   // ... and records per copy of the points
     int ei = 0;                 // next event slot
     int ev_coarse = -1, ev_sort_end = -1;
   };
@@ -777,7 +908,7 @@ class Engine : public IEngine {
     uint32_t top_range = 0;   // number of values the top window's digit can take (<= L + 1)
     int fold_shift = 0, fold_rows = 0;   // thin top window folded into its own bucket set (sort_kernels.h SortGeom)
   };
-  Geometry geometry(int c, bool glv, uint32_t M, int b, bool allow_fold = false) const {
+  Geometry geometry(int c, bool glv, uint32_t M, int b, bool allow_fold = false, uint32_t F = 1) const {
     Geometry g;
     g.c = c;
     g.K = (b + 1 + c - 1) / c;                              // msm-batched-affine.ts:96
@@ -806,12 +937,14 @@ class Engine : public IEngine {
       const uint32_t ncb0 = g.L >> fine_bits(c, M);
       const bool sort2 = !force_atomic_sort_ && M <= (1u << 24) && ncb0 <= (uint32_t)COARSE_MAX_BINS &&
                          (uint64_t)g.K * ncb0 <= (uint64_t)SORT_MAX_BINS;
-      if (allow_fold && !no_fold_ && sort2 && g.K > 1 && g.t_top <= c - 2 && b2 >= 1 && t_bound <= b2) {
+      if (F == 1 && allow_fold && !no_fold_ && sort2 && g.K > 1 && g.t_top <= c - 2 && b2 >= 1 && t_bound <= b2) {
         g.fold_shift = b2;
         g.fold_rows = c - 1 - b2;
       }
     }
-    if (g.fold_shift == 0 && !no_spread_ && g.K > 1 && g.t_top <= c - 2) {
+    // (precomputed sets, F > 1: neither -- the top window shares its bucket set with F - 1 windows; choose_window keeps
+    // it from being thin)
+    if (F == 1 && g.fold_shift == 0 && !no_spread_ && g.K > 1 && g.t_top <= c - 2) {
       g.spread = c - 1 - g.t_top;
       if (g.spread > 3) g.spread = 3;
       const int ib = ceil_log2_u64(M < 2 ? 2 : M);
@@ -827,22 +960,32 @@ class Engine : public IEngine {
   // Fine bits of the two-level sort = log2(buckets per coarse bin): as many as (1) the packed word leaves beside the
   // index and the sign, (2) k_fine's counters hold, and (3) keep an average bin inside k_fine's LDS staging (a bin of
   // 2^fb buckets holds ~M 2^fb / L entries; beyond FINE_STAGE it falls back to scattered stores: 3x slower).
-  int fine_bits(int c, uint32_t M) const {
-    const int idx_bits = ceil_log2_u64(M < 2 ? 2 : M);
+  // Precomputed sets (W = windows per bucket set > 1): a set receives W M entries and the packed index carries the copy
+  // (copy_bits(W) more bits); fb is then raised again, if the index leaves room, until a window has <= COARSE_MAX_BINS
+  // bins (k_fine sorts a denser bin unstaged); -1 when even that does not fit.
+  int fine_bits(int c, uint32_t M, uint32_t W = 1) const {
+    const int idx_bits = ceil_log2_u64(M < 2 ? 2 : M) + copy_bits(W);
     int fb = 31 - idx_bits;
     if (fb > FINE_MAX_BITS) fb = FINE_MAX_BITS;
     if (fb_cap_ > 0 && fb > fb_cap_) fb = fb_cap_;
     if (fb > c - 1) fb = c - 1;
+    const int fb_max = fb;
     const uint64_t L = 1ull << (c - 1);
-    while (fb > 0 && (((uint64_t)M << fb) / L) * 10 > (uint64_t)FINE_STAGE * 9) fb--;
+    while (fb > 0 && ((((uint64_t)M * W) << fb) / L) * 10 > (uint64_t)FINE_STAGE * 9) fb--;
+    if (W > 1) {
+      while (fb < fb_max && (L >> fb) > (uint64_t)COARSE_MAX_BINS) fb++;
+      if ((L >> fb) > (uint64_t)COARSE_MAX_BINS || fb < 0) return -1;
+    }
     return fb;
   }
+  // windows per bucket set of a plan
+  static uint32_t set_windows(const Plan& pl) { return pl.F < (uint32_t)pl.K ? pl.F : (uint32_t)pl.K; }
 
   // Fine bits of the TOP window's bins (SortGeom::fbt): its entries fall on top_range << spread buckets only (the largest
   // scalar bounds the top digit), so they are up to 2x denser than M / L; as many fine bits as keep such a bin inside
   // k_fine's staging, and no fewer than keep the window's bins inside k_coarse's 9-bit bin field.
   int fine_bits_top(const Plan& pl, int fb) const {
-    if (pl.fold_shift != 0 || no_fbt_) return fb;
+    if (pl.fold_shift != 0 || no_fbt_ || pl.F > 1) return fb;
     const uint64_t slots = (uint64_t)pl.top_range << pl.spread;
     int fbt = fb;
     while (fbt > 0 && (((uint64_t)pl.M << fbt) / slots) * 10 > (uint64_t)FINE_STAGE * 9) fbt--;
@@ -857,7 +1000,11 @@ class Engine : public IEngine {
   // (ms: rounds * 0.075 + additions / 4.5e6 + reduction levels * 0.065 + buckets * 0.8e-6).
   // A batch of B problems runs the same number of tree rounds and reduction levels as one, with B times the additions
   // and buckets: those two terms of the model are scaled by B.
-  int choose_window(bool glv, uint32_t M, int b, bool tree_rounds, uint32_t nprob = 1) const {
+  // Precomputed point sets (F > 1 windows per bucket set): the same model at every size, over the
+  // window sizes whose sets fit one sort pass, with ceil(K / F) bucket sets, buckets W = min(F, K) times longer, and the
+  // top window's concentration on its few digits (it shares a set, it is neither spread nor folded).
+  int choose_window(bool glv, uint32_t M, int b, bool tree_rounds, uint32_t nprob = 1, uint32_t F = 1) const {
+    if (F > 1) return choose_window_pre(glv, M, b, nprob, F);
     int c = default_window(M);
     if (M >= (1u << 18) || no_window_model_) {
       // measured optimum of the batched-affine path from 2^18 entries per window on (profiles/r03_sweep.json): 17 without
@@ -893,8 +1040,50 @@ class Engine : public IEngine {
     return best_c;
   }
 
+  // does a window size fit a precomputed set's sort (F windows per set; the two-level sort only)?
+  bool pre_fits(int c, bool glv, uint32_t M, int b, uint32_t F) const {
+    const Geometry g = geometry(c, glv, M, b, false, F);
+    const uint32_t W = F < (uint32_t)g.K ? F : (uint32_t)g.K;
+    const int fb = fine_bits(c, M, W);
+    if (fb < 0 || g.K > kMaxWindows || M > (1u << 24)) return false;
+    // one bucket collects the entries of all W windows of its set (every digit equal in the worst case): the tree rounds
+    // take buckets below 2^PLAN_RMAX entries
+    if ((uint64_t)W * M >= (1ull << PLAN_RMAX)) return false;
+    const uint32_t ncb = g.L >> fb;
+    return ncb <= (uint32_t)COARSE_MAX_BINS && (uint64_t)g.K * ncb <= (uint64_t)SORT_MAX_BINS;
+  }
+  int choose_window_pre(bool glv, uint32_t M, int b, uint32_t nprob, uint32_t F) const {
+    // measured (profiles/r05_precompute_c_sweep.jsonl): with every window in one set and >= 2^16 entries per window, c = 17
+    // is the fastest fitting size (2^16: 0.86 ms against 0.94 at c = 16, 16 x 2^16: 3.26 against 3.43, 2^20: 3.62 against
+    // 3.99); with fewer windows per set the model below is (16 x 2^16, F = 2: c = 15 5.98 ms, c = 17 7.76)
+    if (!glv && M >= (1u << 16) && F >= (uint32_t)geometry(17, false, M, b, false, F).K && pre_fits(17, false, M, b, F))
+      return 17;
+    int best_c = 0;
+    double best = 1e30;
+    for (int cc = 3; cc <= 20; cc++) {
+      if (!pre_fits(cc, glv, M, b, F)) continue;
+      const Geometry g = geometry(cc, glv, M, b, false, F);
+      const uint32_t W = F < (uint32_t)g.K ? F : (uint32_t)g.K;
+      const int sets = (g.K + (int)W - 1) / (int)W;
+      const int w_top = g.K - (sets - 1) * (int)W;   // windows in the top window's set
+      const double lam = (double)M * W / g.L;
+      double maxb = 1.5 * lam + 12;
+      const double top = 1.3 * (double)M / (g.top_range < 1 ? 1 : g.top_range) + (double)(w_top - 1) * M / g.L + 12;
+      if (g.K > 1 && top > maxb) maxb = top;
+      if (maxb > (double)M * W) maxb = (double)M * W;
+      const int rounds = ceil_log2_u64((uint64_t)(maxb < 2 ? 2 : maxb));
+      const double cost = 0.075 * rounds + (double)nprob * g.K * M / 4.5e6 + 0.065 * ((cc - 1 + 1) / 2) +
+                          0.8e-6 * nprob * sets * g.L;
+      if (cost < best) {
+        best = cost;
+        best_c = cc;
+      }
+    }
+    return best_c > 0 ? best_c : default_window(M);
+  }
+
   int make_plan(Plan& pl, uint64_t n64, bool glv, const msmz_opts& opt, uint32_t pts_n, bool tree_rounds = true,
-                int extra_bits = 0, bool allow_fold = false, uint32_t nprob = 1) {
+                int extra_bits = 0, bool allow_fold = false, uint32_t nprob = 1, uint32_t F = 1) {
     pl.n = (uint32_t)n64;
     pl.nprob = nprob;
     pl.glv = glv;
@@ -903,17 +1092,12 @@ class Engine : public IEngine {
     // analytic bound is 2^126); k_hist flags a longer half and the MSM is redone (extra_bits = 1) with the proven bound
     // GLV_PROVEN_BITS <= 128, which also is what the 4-word halves of glv_decompose can hold.
     static_assert(!Fr::HAS_GLV || (Fr::GLV_PROVEN_BITS <= 128 && Fr::GLV_PROVEN_BITS <= Fr::GLV_BITS), "GLV halves must fit 4 words");
-    if (!glv) {
-      pl.b = Fr::BITS;
-    } else if (extra_bits) {
-      pl.b = Fr::GLV_PROVEN_BITS > Fr::GLV_BITS - 1 ? Fr::GLV_PROVEN_BITS : Fr::GLV_BITS - 1;
-    } else {
-      pl.b = glv_bits_assumed_ > 0 ? glv_bits_assumed_ : Fr::GLV_BITS - 1;
-    }
-    pl.c = opt.c > 0 ? opt.c : choose_window(glv, pl.M, pl.b, tree_rounds, nprob);
+    pl.b = scalar_bits(glv, extra_bits);
+    pl.c = opt.c > 0 ? opt.c : choose_window(glv, pl.M, pl.b, tree_rounds, nprob, F);
     if (pl.c < 2) pl.c = 2;
     if (pl.c > 24) pl.c = 24;
-    const Geometry g = geometry(pl.c, glv, pl.M, pl.b, allow_fold);
+    pl.F = F < 1 ? 1 : F;
+    const Geometry g = geometry(pl.c, glv, pl.M, pl.b, allow_fold, pl.F);
     pl.K = g.K;
     pl.L = g.L;
     pl.spread = g.spread;
@@ -921,6 +1105,7 @@ class Engine : public IEngine {
     pl.fold_shift = g.fold_shift;
     pl.fold_rows = g.fold_rows;
     pl.Keff = g.Keff;
+    if (pl.F > 1) pl.Keff = (pl.K + (int)set_windows(pl) - 1) / (int)set_windows(pl);   // bucket sets
     const uint64_t nb64 = (uint64_t)pl.Keff * pl.L;
     if (nb64 * nprob + 1 >= (1ull << 31) || (uint64_t)nprob * pl.K * pl.M >= (1ull << 32) || pl.Keff > kMaxWindows)
       return MSMZ_ERR_ARG;
@@ -933,7 +1118,8 @@ class Engine : public IEngine {
 
   // does the two-level LDS-staged sort apply to this plan (else the per-entry atomic fallback)?
   bool sort2_applies(const Plan& pl) const {
-    const int fb = fine_bits(pl.c, pl.M);
+    const int fb = fine_bits(pl.c, pl.M, set_windows(pl));
+    if (fb < 0) return false;
     const uint32_t ncb = pl.L >> fb;
     const uint32_t ncbt = pl.L >> fine_bits_top(pl, fb);
     const uint32_t nbins = (uint32_t)(pl.K - 1) * ncb + (ncbt << pl.spread);
@@ -955,24 +1141,29 @@ class Engine : public IEngine {
     // two-level LDS-staged sort when the packed (fine | negate | index) word fits; else per-entry atomics.
     // packed word = fine bucket bits | negate | index: the narrower the index, the more fine bits fit, the
     // fewer (and longer) coarse runs the scatter writes
-    const int idx_bits = ceil_log2_u64(M < 2 ? 2 : M);
-    const int fb = fine_bits(c, M);
+    // precomputed sets: W windows per bucket set, the packed index = copy << mbits | entry
+    const uint32_t W = set_windows(pl);
+    const int mbits = ceil_log2_u64(M < 2 ? 2 : M);
+    const int idx_bits = mbits + copy_bits(W);
+    const bool sort2 = sort2_applies(pl);
+    if (!sort2 && (P > 1 || pl.F > 1)) return MSMZ_ERR_ARG;   // (msm_batch only batches plans the two-level sort handles)
+    const int fb = sort2 ? fine_bits(c, M, W) : fine_bits(c, M);
     const uint32_t ncb = L >> fb;
     const int fbt = fine_bits_top(pl, fb);
     const uint32_t ncbt = L >> fbt;
     const uint32_t top_bin = (uint32_t)(K - 1) * ncb;
-    const uint32_t nbins = top_bin + (ncbt << pl.spread);
-    const bool sort2 = sort2_applies(pl);
+    const uint32_t nbins = top_bin + (ncbt << pl.spread);   // tile-local bins (per window)
+    const uint32_t sbins = pl.F > 1 ? (uint32_t)pl.Keff * W * ncb : nbins;   // scanned bins per problem
+    const uint32_t fbins = pl.F > 1 ? (uint32_t)pl.Keff * ncb : nbins;       // k_fine's bins per problem
     const uint32_t n_half = pl.glv ? n : 0xffffffffu;
-    if (!sort2 && P > 1) return MSMZ_ERR_ARG;   // (msm_batch only batches plans the two-level sort handles)
     if (sort2) {
-      const size_t pbins = (size_t)P * nbins;   // bins of all problems
+      const size_t pbins = (size_t)P * sbins;   // bins of all problems
       if ((st = packed_.ensure((size_t)P * K * M * 4))) return st;
       if ((st = bins_.ensure((pbins + 2) * 4 + kTraceBytes * pbins))) return st;
       if ((st = counts_.ensure(pbins * 4))) return st;
       uint32_t* d_counts = counts_.as<uint32_t>();
       MSMZ_HIP(hipMemsetAsync(d_counts, 0, pbins * 4, stream_));
-      SortGeom g{n, M, c, K, fb, pl.spread, idx_bits, ncb, fbt, ncbt, pl.fold_shift, pl.fold_rows};
+      SortGeom g{n, M, c, K, fb, pl.spread, idx_bits, ncb, fbt, ncbt, pl.fold_shift, pl.fold_rows, W, mbits, sbins};
       mark(pl);  // 0
       const uint32_t per_tile = pl.glv ? COARSE_TILE / 2 : COARSE_TILE;   // scalars per workgroup (k_hist and k_coarse)
       const uint32_t tiles = (n + per_tile - 1) / per_tile;
@@ -1031,14 +1222,15 @@ class Engine : public IEngine {
       MSMZ_HIP(hipGetLastError());
       {
         const size_t lds = kFineLds;
-        hipLaunchKernelGGL(k_fine, dim3(nbins, P), dim3(FINE_T), lds, stream_, refs_.as<uint32_t>(), off_.as<uint32_t>(),
-                           &d_meta->max_bucket, packed_.as<uint32_t>(), bins_.as<uint32_t>(), fb, fbt, top_bin, nbins, idx_bits,
-                           n_half, pl.endo_delta);
+        hipLaunchKernelGGL(k_fine, dim3(fbins, P), dim3(FINE_T), lds, stream_, refs_.as<uint32_t>(), off_.as<uint32_t>(),
+                           &d_meta->max_bucket, packed_.as<uint32_t>(), bins_.as<uint32_t>(), fb, fbt,
+                           pl.F > 1 ? fbins - ncb : top_bin, fbins, idx_bits, n_half, pl.endo_delta, W, mbits,
+                           pl.copy_stride);
       }
 #ifdef MSMZ_TRACE
       // development aid: workgroup time stamps of k_coarse / k_fine (tools/wg_timeline.py)
       if ((st = trace_dump("k_coarse", tileoff_.as<uint32_t>() + (size_t)P * tiles * nbins, tiles, true))) return st;
-      if ((st = trace_dump("k_fine", bins_.as<uint32_t>() + ((P * nbins + 2) & ~1u), nbins, false))) return st;
+      if ((st = trace_dump("k_fine", bins_.as<uint32_t>() + ((P * sbins + 2) & ~1u), fbins, false))) return st;
 #endif
     } else {
       // fallback (window sizes whose coarse bins do not fit the LDS staging): digits materialized, one global
@@ -1267,28 +1459,49 @@ class Engine : public IEngine {
     typename H::Pt acc, w, t;
     host64_.set_inf(acc);
     const Split2d sp = split_2d(pl);
-    auto add_results = [&](int k, int which) {
-      // bucket sets of window k: kw = k below the top window, K-1 .. Keff-1 (its sub-windows) for the top one
-      const int lo = k, hi = (k == pl.K - 1) ? pl.Keff - 1 : k;
-      if (which == 0 && k == pl.K - 1 && pl.fold_shift != 0) return;   // folded top window: its rows are copies, not weights
-      for (int kw = lo; kw <= hi; kw++) {
-        host64_.load_pt(w, res2 + (size_t)(2 * kw + which) * XW);
-        host64_.add_pt(t, acc, w);
-        acc = t;
-      }
-    };
-    for (int k = pl.K - 1; k >= 0; k--) {
-      if (k < pl.K - 1)
-        for (int j = 0; j < pl.c - sp.b; j++) {
+    if (pl.F > 1) {
+      // precomputed point set: set s holds windows [s F, (s + 1) F) at weight 2^(c F s): acc = (acc * 2^(c F - b) + A_s) * 2^b + B_s
+      auto dbl_n = [&](int cnt) {
+        for (int j = 0; j < cnt; j++) {
           host64_.dbl(t, acc);
           acc = t;
         }
-      add_results(k, 0);   // rows: weight 2^(c k + b)
-      for (int j = 0; j < sp.b; j++) {
-        host64_.dbl(t, acc);
+      };
+      auto add = [&](int r) {
+        host64_.load_pt(w, res2 + (size_t)r * XW);
+        host64_.add_pt(t, acc, w);
         acc = t;
+      };
+      for (int s = pl.Keff - 1; s >= 0; s--) {
+        if (s < pl.Keff - 1) dbl_n(pl.c * (int)pl.F - sp.b);
+        add(2 * s);
+        dbl_n(sp.b);
+        add(2 * s + 1);
       }
-      add_results(k, 1);   // columns: weight 2^(c k)
+    } else {
+      auto add_results = [&](int k, int which) {
+        // bucket sets of window k: kw = k below the top window, K-1 .. Keff-1 (its sub-windows) for the top one
+        const int lo = k, hi = (k == pl.K - 1) ? pl.Keff - 1 : k;
+        if (which == 0 && k == pl.K - 1 && pl.fold_shift != 0) return;   // folded top window: its rows are copies, not weights
+        for (int kw = lo; kw <= hi; kw++) {
+          host64_.load_pt(w, res2 + (size_t)(2 * kw + which) * XW);
+          host64_.add_pt(t, acc, w);
+          acc = t;
+        }
+      };
+      for (int k = pl.K - 1; k >= 0; k--) {
+        if (k < pl.K - 1)
+          for (int j = 0; j < pl.c - sp.b; j++) {
+            host64_.dbl(t, acc);
+            acc = t;
+          }
+        add_results(k, 0);   // rows: weight 2^(c k + b)
+        for (int j = 0; j < sp.b; j++) {
+          host64_.dbl(t, acc);
+          acc = t;
+        }
+        add_results(k, 1);   // columns: weight 2^(c k)
+      }
     }
     Xyzz<F> fin;
     host64_.to_xyzz(fin, acc);
@@ -1340,8 +1553,13 @@ class Engine : public IEngine {
     if (glv && (!Fr::HAS_GLV || !pts.has_endo)) return MSMZ_ERR_UNSUPPORTED;
     Plan pl;
     const bool want_2d = opt.reserved[0] != 1 && reduce2d_;
-    int st = make_plan(pl, n64, glv, opt, (uint32_t)pts.n, true, extra_bits, want_2d, nprob);
+    // precomputed point set: its copies carry windows [j F, (j + 1) F) into one bucket set (two-level sort, 2-D reduction)
+    const uint32_t fac = pts.factor > 1 ? pts.factor : 1;
+    if (fac > 1 && (!want_2d || glv != (pts.glv != 0))) return MSMZ_ERR_UNSUPPORTED;
+    int st = make_plan(pl, n64, glv, opt, (uint32_t)pts.n, true, extra_bits, want_2d, nprob, fac);
     if (st) return st;
+    pl.copy_stride = (uint32_t)pts.copy_stride;
+    if (fac > 1 && !sort2_applies(pl)) return MSMZ_ERR_ARG;   // (msmz_precompute_points refuses such sets)
     if (nprob > 1 && (!want_2d || pl.L < 2 || !sort2_applies(pl))) return MSMZ_ERR_BATCH_LOOP;
     // location words hold a record index in 30 bits
     if ((uint64_t)nprob * pl.K * pl.M >= (1ull << 30)) return MSMZ_ERR_ARG;
@@ -1364,7 +1582,7 @@ class Engine : public IEngine {
     pc.chunk = chunk;
     pc.nb_main = nb;
     pc.chunk_top = chunk;
-    if (!no_plan_top_ && nprob == 1 && pl.K > 1 && pl.fold_shift == 0 && chunk >= 128 &&
+    if (!no_plan_top_ && nprob == 1 && pl.F == 1 && pl.K > 1 && pl.fold_shift == 0 && chunk >= 128 &&
         (uint64_t)pl.L * 10 > ((uint64_t)pl.top_range << pl.spread) * 13) {
       pc.nb_main = (uint32_t)(pl.K - 1) * pl.L;
       pc.chunk_top = chunk / 2;
@@ -1392,7 +1610,8 @@ class Engine : public IEngine {
     if ((st = fetch_meta(pl))) return st;      // the ONE host round trip before the final fetch
     if (h_meta_->error & 4u) return MSMZ_ERR_RANGE;
     if (h_meta_->error & 2u) return MSMZ_ERR_RETRY_BITS;
-    if (pl.max_bucket > (1u << 24)) return MSMZ_ERR_ARG;
+    // (a plain set's bucket holds <= M <= 2^24 entries; a precomputed set's up to W M < 2^PLAN_RMAX, which pre_fits checked)
+    if (pl.max_bucket > (pl.F > 1 ? (1u << PLAN_RMAX) - 1u : (1u << 24))) return MSMZ_ERR_ARG;
     const int R = (int)h_meta_->rounds;
     memcpy(h_round_pairs_, h_meta_->round_pairs, sizeof(h_round_pairs_));
     const int ev_plan1 = pl.ei;

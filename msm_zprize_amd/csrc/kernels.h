@@ -792,6 +792,7 @@ __device__ __forceinline__ bool fe_inverse_wave(Fe<F>& r, const Fe<F>& x) {
 }  // namespace msmz
 
 #include "batch_kernels.h"
+#include "precompute_kernels.h"
 
 namespace msmz {
 

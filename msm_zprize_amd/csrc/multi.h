@@ -51,6 +51,11 @@ class IEngine {
   virtual int msm_batch(uint64_t ph, const uint8_t* host_scalars, uint64_t sh, uint64_t n, uint32_t batch,
                         const msmz_opts* o, uint8_t* out, int* out_inf, msmz_log* log, const GenMap* split = nullptr,
                         uint64_t host_stride = 0) = 0;
+  // precomputed point sets (msmz_precompute_points): the parameters a set of n points is built with, then the copies
+  virtual int precompute_params(uint64_t n, const msmz_opts* o, uint32_t factor, int* c, int* glv, uint32_t* copies,
+                                int* K) const = 0;
+  virtual int precompute_points(uint64_t ph, uint64_t n, int c, int glv, uint32_t copies, uint64_t* h) = 0;
+  virtual int precomputed_info(uint64_t h, int32_t* c, int32_t* glv, uint32_t* factor, uint32_t* K, uint64_t* records) = 0;
   virtual int test_set_glv_bits(int) { return MSMZ_ERR_UNSUPPORTED; }
   virtual int test_retries() { return 0; }
   virtual int test_field(int, const uint8_t*, const uint8_t*, uint64_t, uint8_t*) { return MSMZ_ERR_UNSUPPORTED; }
@@ -268,6 +273,33 @@ class MultiEngine : public IEngine {
     return MSMZ_OK;
   }
 
+  // every engine precomputes its own share of the points (the same c, GLV choice and copies, chosen for the whole set)
+  int precompute_params(uint64_t n, const msmz_opts* o, uint32_t factor, int* c, int* glv, uint32_t* copies,
+                        int* K) const override {
+    return workers_[0]->eng->precompute_params(n, o, factor, c, glv, copies, K);
+  }
+  int precompute_points(uint64_t ph, uint64_t n, int c, int glv, uint32_t copies, uint64_t* h) override {
+    auto pit = handles_.find(ph);
+    if (!h || pit == handles_.end() || pit->second.kind != 0 || pit->second.factor != 0 || n == 0 || pit->second.n < n)
+      return MSMZ_ERR_ARG;
+    const MHandle& src = pit->second;
+    MHandle mh{0, n, std::vector<uint64_t>(G_, 0)};
+    int st = for_all([&](uint32_t g, IEngine* e) {
+      const uint64_t cnt = shard_count(n, g, G_);
+      if (cnt == 0) return (int)MSMZ_OK;
+      return e->precompute_points(src.sub[g], cnt, c, glv, copies, &mh.sub[g]);
+    });
+    mh.factor = copies;
+    mh.glv = glv;
+    return finish_handle(st, mh, h);
+  }
+  int precomputed_info(uint64_t hd, int32_t* c, int32_t* glv, uint32_t* factor, uint32_t* K, uint64_t* records) override {
+    auto it = handles_.find(hd);
+    if (it == handles_.end() || it->second.factor == 0) return MSMZ_ERR_ARG;
+    if (records) *records = (uint64_t)it->second.factor * it->second.n * (it->second.glv ? 2 : 1);
+    return workers_[0]->eng->precomputed_info(it->second.sub[0], c, glv, factor, K, nullptr);   // (shard 0 holds block 0)
+  }
+
   void merge_device_logs(msmz_log* log, const std::vector<msmz_log>& logs, const std::vector<int>& used) const {
     {   // stage times: the slowest device; counts: summed
       memset(log, 0, sizeof(*log));
@@ -326,6 +358,8 @@ class MultiEngine : public IEngine {
     int kind;
     uint64_t n;
     std::vector<uint64_t> sub;   // per-device handle (0 = that device holds nothing)
+    uint32_t factor = 0;         // precomputed point set: copies (0 = plain) and GLV choice
+    int glv = 0;
   };
 
   // one persistent host thread per device: runs the tasks posted for its engine

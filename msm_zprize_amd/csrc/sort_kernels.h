@@ -68,7 +68,22 @@ struct SortGeom {
   // hold 2^fold_rows copies ("rows") of the digit's small range, and the two-dimensional reduction's COLUMN sums are
   // exactly the per-digit sums (the row result of that set is not used).  fold_shift = 0: not folded.
   int fold_shift, fold_rows;
+  // Precomputed point sets (msmz_precompute_points): F windows share one bucket set.  Window k adds into set k / F and
+  // references copy k mod F of the points, whose index rides in the packed word above the entry's `mbits` bits.  The
+  // tile-local bins stay per window (k * ncb + coarse: the LDS layouts above are unchanged); only the GLOBAL bin order is
+  // permuted (scan_bin) so that the F bins of one set with the same coarse value are adjacent and k_fine sorts them as one
+  // bin.  `sbins` = scanned bins per problem (ceil(K / F) * F * ncb).  F = 1: the identity, sbins = nbins.
+  uint32_t F;
+  int mbits;
+  uint32_t sbins;
 };
+
+// position of tile-local bin b (window b / ncb) in the global bin scan
+__device__ __forceinline__ uint32_t scan_bin(const SortGeom& g, uint32_t b) {
+  if (g.F <= 1u) return b;
+  const uint32_t k = b / g.ncb, co = b & (g.ncb - 1u);   // (ncb is a power of two)
+  return ((k / g.F) * g.ncb + co) * g.F + k % g.F;
+}
 
 // bucket index (weight - 1) of digit l of window k inside its bucket set
 __device__ __forceinline__ uint32_t bucket_index(const SortGeom& g, int k, uint32_t l, uint32_t entry) {
@@ -219,7 +234,7 @@ __global__ void __launch_bounds__(COARSE_T, 8) k_hist(uint32_t* counts, uint16_t
   const uint32_t L = 1u << (g.c - 1);
   // batched MSM: problem blockIdx.y sorts scalar vector blockIdx.y into its own slice of the bin counts and tile rows
   scalars += (size_t)blockIdx.y * g.n * 8;
-  counts += (size_t)blockIdx.y * nbins;
+  counts += (size_t)blockIdx.y * g.sbins;
   tile_counts += (size_t)blockIdx.y * gridDim.x * nbins;
   tile_offs += (size_t)blockIdx.y * gridDim.x * nbins;
   for (uint32_t b = threadIdx.x; b < nbins; b += COARSE_T) s_hist[b] = 0;
@@ -276,7 +291,7 @@ __global__ void __launch_bounds__(COARSE_T, 8) k_hist(uint32_t* counts, uint16_t
     if (b < nbins) {
       const uint32_t v = s_hist[b];
       row[b] = (uint16_t)v;             // <= COARSE_TILE entries of a tile fall into one bin
-      if (v) r[q] = atomicAdd(&counts[b], v);
+      if (v) r[q] = atomicAdd(&counts[scan_bin(g, b)], v);
     }
   }
 #pragma unroll
@@ -355,7 +370,7 @@ __global__ void __launch_bounds__(COARSE_T, 8) k_coarse(uint32_t* packed_out, co
   // batched MSM: problem blockIdx.y; its bins start at bin blockIdx.y * nbins of ONE scan over all problems, so the
   // packed words of every problem land in one dense array
   scalars += (size_t)blockIdx.y * g.n * 8;
-  bin_base += (size_t)blockIdx.y * nbins;
+  bin_base += (size_t)blockIdx.y * g.sbins;
   tile_counts += (size_t)blockIdx.y * gridDim.x * nbins;
   tile_offs += (size_t)blockIdx.y * gridDim.x * nbins;
   MSMZ_STAMP(trace, 0);
@@ -378,7 +393,7 @@ __global__ void __launch_bounds__(COARSE_T, 8) k_coarse(uint32_t* packed_out, co
     if (per == 1) {
       // (<= 1024 bins: one bin per thread, three independent loads)
       const uint32_t cnt = b0 < nbins ? row[b0] : 0u;
-      const uint32_t gb = b0 < nbins ? bin_base[b0] + roff[b0] : 0u;
+      const uint32_t gb = b0 < nbins ? bin_base[scan_bin(g, b0)] + roff[b0] : 0u;
       ex = block_exclusive_scan<COARSE_T>(cnt, &total, s_wave);
       if (b0 < nbins) {
         s_cur[b0] = ex;
@@ -396,7 +411,7 @@ __global__ void __launch_bounds__(COARSE_T, 8) k_coarse(uint32_t* packed_out, co
       for (int q = 0; q < PB; q++) {
         const uint32_t b = (uint32_t)q * COARSE_T + threadIdx.x;
         cnt[q] = b < nbins ? row[b] : 0u;
-        gb[q] = b < nbins ? bin_base[b] + roff[b] : 0u;
+        gb[q] = b < nbins ? bin_base[scan_bin(g, b)] + roff[b] : 0u;
       }
 #pragma unroll
       for (int q = 0; q < PB; q++) {
@@ -473,6 +488,7 @@ __global__ void __launch_bounds__(COARSE_T, 8) k_coarse(uint32_t* packed_out, co
         uint32_t entry;
         if constexpr (GLV) entry = (local / COARSE_T) * g.n + blockIdx.x * COARSE_T + (local % COARSE_T);   // SC = 1
         else entry = blockIdx.x * COARSE_TILE + local;
+        if (g.F > 1u) entry |= ((uint32_t)k % g.F) << g.mbits;   // the copy of the points this window references
         packed_out[delta_k[w & 511u] + wbase + p] = ((w >> 20) << g.idx_bits) | entry;
       }
     }
@@ -515,21 +531,23 @@ __global__ void __launch_bounds__(COARSE_T, 8) k_coarse(uint32_t* packed_out, co
 // record sits at index i + endo_delta of the point set (the images follow the whole set, which may be larger than
 // the prefix this MSM covers: msm-batched-affine.ts:74-97 takes any N <= allocated).
 // Bins below `top_bin` hold 2^fb buckets each, the top window's bins (from `top_bin` on) 2^fbt.
+// Precomputed point sets (SortGeom::F = `group` > 1): bin b is the `group` consecutive scanned bins from b * group on, and
+// the packed index is copy << mbits | entry; the copy's records start at copy * copy_stride.  group = 1: mbits = idx_bits.
 static __global__ void __launch_bounds__(FINE_T) k_fine(uint32_t* refs, uint32_t* off, uint32_t* max_bucket,
                                                  const uint32_t* packed, const uint32_t* bin_base, int fb, int fbt,
                                                  uint32_t top_bin, uint32_t n_bins, int idx_bits, uint32_t n_half,
-                                                 uint32_t endo_delta) {
+                                                 uint32_t endo_delta, uint32_t group, int mbits, uint32_t copy_stride) {
   extern __shared__ uint32_t s_dyn[];
   uint32_t* s_cnt = s_dyn;                                  // [1 << FINE_MAX_BITS] counts, then running cursors
   uint32_t* s_stage = s_dyn + (1 << FINE_MAX_BITS);          // [FINE_STAGE]
   __shared__ uint32_t s_wave[FINE_T / 64];
   __shared__ uint32_t s_wmax[FINE_T / 64];
 #ifdef MSMZ_TRACE
-  uint64_t* trace = reinterpret_cast<uint64_t*>(const_cast<uint32_t*>(bin_base) + ((gridDim.y * n_bins + 2) & ~1u));
+  uint64_t* trace = reinterpret_cast<uint64_t*>(const_cast<uint32_t*>(bin_base) + ((gridDim.y * n_bins * group + 2) & ~1u));
 #endif
   // batched MSM: problem blockIdx.y owns bins [y n_bins, (y + 1) n_bins) of the global scan and buckets
   // [y nb, (y + 1) nb) of `off`; its last bin's end is the next problem's first offset (the same value is written twice)
-  bin_base += (size_t)blockIdx.y * n_bins;
+  bin_base += (size_t)blockIdx.y * n_bins * group;
   off += (size_t)blockIdx.y * (((size_t)top_bin << fb) + ((size_t)(n_bins - top_bin) << fbt));
   // last bins first: the top window's bins are the only ones that are structurally above average (its digit range is
   // not a power of two, so its buckets are up to 2x denser), and the workgroups that start first should be the long ones
@@ -539,7 +557,7 @@ static __global__ void __launch_bounds__(FINE_T) k_fine(uint32_t* refs, uint32_t
   // first bucket of the bin in `off`
   const size_t bucket0 = top ? ((size_t)top_bin << fb) + ((size_t)(bin - top_bin) << fbt) : (size_t)bin << fb;
   const uint32_t per = (nfine + FINE_T - 1) / FINE_T;        // consecutive buckets per thread (<= 2)
-  const uint32_t begin = bin_base[bin], end = bin_base[bin + 1];
+  const uint32_t begin = bin_base[bin * group], end = bin_base[(bin + 1) * group];
   const uint32_t cnt_bin = end - begin;
   if (cnt_bin == 0) {   // (the top window's bins beyond its digit range): every bucket is empty and starts at `begin`
     for (uint32_t f = threadIdx.x; f < nfine; f += FINE_T) off[bucket0 + f] = begin;
@@ -636,7 +654,10 @@ static __global__ void __launch_bounds__(FINE_T) k_fine(uint32_t* refs, uint32_t
   MSMZ_STAMP(trace, 3);
   auto to_ref = [&](uint32_t pv) {
     uint32_t idx = pv & imask;
+    const uint32_t copy = idx >> mbits;
+    idx &= (1u << mbits) - 1u;
     if (idx >= n_half) idx += endo_delta;   // endomorphism half: record index in the point set
+    idx += copy * copy_stride;
     return idx | (((pv >> idx_bits) & 1u) << 31);
   };
   if (staged) {

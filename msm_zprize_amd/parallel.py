@@ -151,6 +151,26 @@ class _Parallel:
         """Scalar.writeBigint route (submission-bls377.ts:95-102)."""
         return self.scalarsFromBytes(b"".join(int(s).to_bytes(32, "little") for s in scalars), len(scalars))
 
+    # -- precomputed point sets ---------------------------------------------------------------------
+    def precomputePoints(self, points, N, options=None, factor=0):
+        """Fixed-base precomputation of the first N resident points (msmz_precompute_points): a new DeviceArray of kind
+        "precomputed" that msm / msmUnsafe / msmBatch / msmBatchUnsafe accept in place of `points` (same results).
+        `factor` = windows sharing one bucket set (0 = all; 1 is refused); options["c"] / options["glv"] fix the window
+        size and GLV choice (default: the engine's).  The copies' parameters are in the array's `info` dict."""
+        options = dict(options or {})
+        c, glv, factor = precompute_args(points, N, options, factor)
+        opts = MsmzOpts()
+        opts.c = c
+        opts.glv = glv
+        h = C.c_uint64()
+        check(lib().msmz_precompute_points(self._c._ctx, points.handle, N, C.byref(opts), factor, C.byref(h)),
+              "msmz_precompute_points")
+        arr = DeviceArray(self._c, h.value, N, "precomputed")
+        vals = [C.c_int32(), C.c_int32(), C.c_uint32(), C.c_uint32(), C.c_uint64()]
+        check(lib().msmz_precomputed_info(self._c._ctx, h.value, *[C.byref(v) for v in vals]), "msmz_precomputed_info")
+        arr.info = dict(zip(("c", "glv", "factor", "K", "records"), (v.value for v in vals)))
+        return arr
+
     # -- the MSM --------------------------------------------------------------------------------
     def _msm(self, scalars, points, N, verbose, options, safe, buckets):
         options = dict(options or {})
@@ -240,6 +260,23 @@ class _Parallel:
         options = dict(options or {})
         options["glv"] = 0
         return self._msm(scalars, points, N, True, options, 1, 1)
+
+
+def precompute_args(points, N, options, factor):
+    """Arguments of precomputePoints -> (c, glv, factor), checked before anything reaches the device."""
+    if not isinstance(points, DeviceArray) or points.kind != "points":
+        raise TypeError("precomputePoints: `points` is a resident point array (pointsFromBytes / randomPointsFast)")
+    if isinstance(N, bool) or not isinstance(N, int) or not 1 <= N <= len(points):
+        raise ValueError(f"precomputePoints: N = {N!r} but the point set holds {len(points)}")
+    if isinstance(factor, bool) or not isinstance(factor, int) or factor < 0 or factor == 1 or factor >= 2 ** 32:
+        raise ValueError(f"precomputePoints: factor = {factor!r} (0 = all windows, or 2, 3, ...)")
+    c = int(options.get("c") or 0)
+    glv = int(options.get("glv", -1))
+    if not 0 <= c <= 24:
+        raise ValueError(f"precomputePoints: c = {c} (0 = the engine's choice, or 2..24)")
+    if glv not in (-1, 0, 1):
+        raise ValueError(f"precomputePoints: glv = {glv} (-1, 0 or 1)")
+    return c, glv, factor
 
 
 def batch_scalars(scalarsList, N, batch=None):

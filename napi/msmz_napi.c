@@ -322,6 +322,40 @@ static napi_value MsmBatch(napi_env env, napi_callback_info info) {
 }
 
 /* pointAdd(curveId, aXy|null, bXy|null, feBytes) -> {xy, isInf}  (null = infinity) */
+/* precomputePoints(ctx, pointsHandle, n, {c, glv}, factor) -> handle of a precomputed point set (msmz_precompute_points;
+   glv -1 = the engine's choice, factor 0 = all windows in one bucket set) */
+static napi_value PrecomputePoints(napi_env env, napi_callback_info info) {
+  size_t argc = 5; napi_value argv[5];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  msmz_ctx* ctx; if (argc < 5 || !get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "precomputePoints");
+  uint64_t ph, n, factor;
+  if (!get_u64(env, argv[1], &ph) || !get_u64(env, argv[2], &n) || !get_u64(env, argv[4], &factor) || factor > 0xffffffffu)
+    return throw_status(env, MSMZ_ERR_ARG, "precomputePoints");
+  msmz_opts o; memset(&o, 0, sizeof(o));
+  o.c = opt_i32(env, argv[3], "c");
+  o.glv = opt_i32(env, argv[3], "glv");
+  uint64_t h = 0;
+  int st = msmz_precompute_points(ctx, ph, n, &o, (uint32_t)factor, &h);
+  if (st) return throw_status(env, st, "msmz_precompute_points");
+  return make_handle(env, h);
+}
+
+/* precomputedInfo(ctx, handle) -> {c, glv, factor, K, records} (msmz_precomputed_info) */
+static napi_value PrecomputedInfo(napi_env env, napi_callback_info info) {
+  size_t argc = 2; napi_value argv[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  msmz_ctx* ctx; if (argc < 2 || !get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "precomputedInfo");
+  uint64_t h; if (!get_u64(env, argv[1], &h)) return throw_status(env, MSMZ_ERR_ARG, "precomputedInfo");
+  int32_t c = 0, glv = 0; uint32_t factor = 0, K = 0; uint64_t records = 0;
+  int st = msmz_precomputed_info(ctx, h, &c, &glv, &factor, &K, &records);
+  if (st) return throw_status(env, st, "msmz_precomputed_info");
+  napi_value res;
+  NAPI_CALL(env, napi_create_object(env, &res));
+  set_num(env, res, "c", c); set_num(env, res, "glv", glv); set_num(env, res, "factor", factor);
+  set_num(env, res, "K", K); set_num(env, res, "records", (double)records);
+  return res;
+}
+
 static napi_value PointAdd(napi_env env, napi_callback_info info) {
   size_t argc = 4; napi_value argv[4];
   NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -356,7 +390,8 @@ static napi_value Init(napi_env env, napi_value exports) {
   static const struct { const char* name; napi_callback fn; } fns[] = {
       {"create", Create}, {"destroy", Destroy}, {"uploadPoints", UploadPoints}, {"uploadScalars", UploadScalars},
       {"randomPoints", RandomPoints}, {"randomScalars", RandomScalars}, {"downloadPoints", DownloadPoints},
-      {"downloadScalars", DownloadScalars}, {"free", Free}, {"msm", Msm}, {"msmBatch", MsmBatch}, {"pointAdd", PointAdd}, {"feBytes", FeBytes}};
+      {"downloadScalars", DownloadScalars}, {"free", Free}, {"msm", Msm}, {"msmBatch", MsmBatch},
+      {"precomputePoints", PrecomputePoints}, {"precomputedInfo", PrecomputedInfo}, {"pointAdd", PointAdd}, {"feBytes", FeBytes}};
   for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); i++) {
     napi_value f;
     if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;
