@@ -8,8 +8,9 @@
  * engine.
  *
  * Field elements travel as fe_bytes little-endian bytes holding a Montgomery residue in the engine's memory format
- * (radix R = 2^392 for the 377/381-bit fields, 2^261 for the 255-bit ones; lazily reduced: any value in [0, 4p));
- * results are canonical (< p).
+ * (radix R = 2^392 for the 377/381-bit fields, 2^261 for the 255-bit ones).  They are lazily reduced: the field ops
+ * take any value in [0, 4p), wider than the [0, 3p) the kernels write and the point ops assume (the memory range is
+ * stated once, in msm_zprize_amd/csrc/fp.h).  Results are canonical (< p).
  */
 #ifndef MSMZ_TEST_H
 #define MSMZ_TEST_H
@@ -34,9 +35,25 @@ enum {
 enum {
   MSMZ_TP_ADD = 0,     /* accumulator + accumulator (XYZZ add / extended twisted-Edwards add), all edge cases */
   MSMZ_TP_ADD_X4 = 1,  /* the 4-lane form used by the upper reduction levels                                 */
+  MSMZ_TP_MADD = 2,    /* a + b with b stored as an input record (affine / Niels) and folded in by the mixed add */
   MSMZ_TP_DBL = 3,     /* doubling of the first operand                                                      */
   MSMZ_TP_DBL_X4 = 4   /* 2 (a + b): 4-lane addition, then the 4-lane doubling of that (general) accumulator  */
 };
+
+/* field routines on RAW register limbs (msm_zprize_amd/csrc/test_ops.h): an element is N signed int32 limbs
+ * (N = 14 for the 377/381-bit fields, 9 for the 255-bit ones; value = sum l[j] * 2^(W j), W = 28 / 29), loaded into
+ * the registers unchanged, so the caller controls the limb form.  Operands must lie inside the routine's contract
+ * (fp.h).  out_raw[i] (N int32): the output limbs, or the memory words (STORE, STORE_MULOUT), or the flag in limb 0
+ * (IS_ZERO); out_canon[i] (fe_bytes): the canonical value of that output (0 for IS_ZERO, CARRY, NORMALIZE).
+ * SLOT_MULOUT parks a mul output in a slot record and loads it back (out_raw = loaded limbs); SLOT_POINT stores (a, b)
+ * as a slot point record and loads it back (out_raw = the limbs of y, out_canon = x). */
+enum {
+  MSMZ_TFL_MUL = 0, MSMZ_TFL_SQR = 1, MSMZ_TFL_REDUCE_SMALL = 2, MSMZ_TFL_STORE = 3, MSMZ_TFL_STORE_MULOUT = 4,
+  MSMZ_TFL_IS_ZERO = 5, MSMZ_TFL_CARRY = 6, MSMZ_TFL_NORMALIZE = 7, MSMZ_TFL_INVERSE = 8, MSMZ_TFL_INVERSE_WAVE = 9,
+  MSMZ_TFL_SLOT_MULOUT = 10, MSMZ_TFL_SLOT_POINT = 11
+};
+int msmz_test_field_limbs(msmz_ctx* ctx, int op, const int32_t* a, const int32_t* b, uint64_t n, int32_t* out_raw,
+                          uint8_t* out_canon);
 
 /* GLV half-scalar bound (src/wasm/glv.ts:216-226 `maxBits`).  The engine sizes the windows for halves below 2^127 and
  * lets the slicing kernel flag a longer half, in which case the MSM is redone with windows for the analytic bound
@@ -64,6 +81,20 @@ int msmz_test_sort(msmz_ctx* ctx, const uint8_t* scalars_le32, uint64_t n, int c
  * out[i] = op(a[i], b[i]) as canonical affine, all-zero = infinity */
 int msmz_test_point(msmz_ctx* ctx, int op, const uint8_t* a_xy, const uint8_t* a_inf, const uint8_t* b_xy,
                     const uint8_t* b_inf, uint64_t n, uint8_t* out_xy);
+
+/* point arithmetic on operands in the kernels' own form (no conversion): every coordinate a lazy memory-format
+ * Montgomery residue (fe_bytes each, [0, 3p)).  a: n accumulators of 4 coordinates -- XYZZ (X, Y, ZZ, ZZZ; ZZ = 0 is
+ * infinity) or extended twisted Edwards (X, Y, Z, T).  b: n records of 4 coordinates -- an accumulator (ADD, ADD_X4,
+ * CHAIN, CHAIN_X4), an affine record (x, y, 0, 0; all zero = infinity) for MADD / MDBL, or a Niels record
+ * (y - x, y + x, 2d x y, 0) for the twisted-Edwards MADD.  neg (nullable): per element, negate the MADD / MDBL record
+ * as the bucket accumulation does.  CHAIN(_X4): L steps (L <= 4096) from r = a, r <- r + b on even steps and r <- 2r
+ * on odd ones, in registers.  out: canonical affine (x || y), all-zero = infinity (Weierstrass). */
+enum {
+  MSMZ_TPR_ADD = 0, MSMZ_TPR_ADD_X4 = 1, MSMZ_TPR_MADD = 2, MSMZ_TPR_DBL = 3, MSMZ_TPR_DBL_X4 = 4,
+  MSMZ_TPR_MDBL = 5 /* Weierstrass only */, MSMZ_TPR_CHAIN = 6, MSMZ_TPR_CHAIN_X4 = 7
+};
+int msmz_test_point_raw(msmz_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, const uint8_t* neg, uint64_t n,
+                        int L, uint8_t* out_xy);
 
 #ifdef __cplusplus
 }

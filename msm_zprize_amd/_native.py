@@ -57,10 +57,14 @@ EXPORTS = {
     "msmz_test_set_glv_bits": (C.c_int, [C.c_void_p, C.c_int]),
     "msmz_test_retries": (C.c_int, [C.c_void_p]),
     "msmz_test_field": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_uint64, C.c_char_p]),
+    "msmz_test_field_limbs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                        C.c_char_p]),
     "msmz_test_glv": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_char_p, C.c_char_p, C.c_char_p]),
     "msmz_test_digits": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "msmz_test_sort": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                  C.c_uint64, C.c_void_p, C.c_uint64]),
+    "msmz_test_point_raw": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint64, C.c_int,
+                                      C.c_char_p]),
     "msmz_test_point": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint64,
                                   C.c_char_p]),
 }

@@ -137,6 +137,7 @@ template <class F>
 MSMZ_HD void xyzz_mdbl(Xyzz<F>& r, const Affine<F>& a) {
   Fe<F> U, V, W, S, M, t;
   fe_add(U, a.y, a.y);
+  fe_carry(U);   // 2y has limbs up to 2^(W+1): 9 * 2^60 breaks N*A*B < 2^63 for the 255-bit fields
   fe_sqr(V, U);
   fe_mul(W, U, V);
   fe_mul(S, a.x, V);

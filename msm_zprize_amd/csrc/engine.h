@@ -762,6 +762,26 @@ class Engine : public IEngine {
     return MSMZ_OK;
   }
 
+  int test_field_limbs(int op, const int32_t* a, const int32_t* b, uint64_t n, int32_t* raw, uint8_t* canon) override {
+    if (!a || !b || !raw || !canon || n == 0 || n > (1u << 22) || op < 0 || op >= TFL_COUNT) return MSMZ_ERR_ARG;
+    MSMZ_HIP(hipSetDevice(device_));
+    const size_t lb = (size_t)4 * F::N * n, eb = (size_t)FE_BYTES * n;
+    uint8_t *d_in, *d_out;
+    int st = test_buffers(2 * lb, lb + eb, &d_in, &d_out);
+    if (st) return st;
+    if ((st = slots_.ensure(((size_t)n + 64) * SlotFmt<F>::WORDS * 4))) return st;
+    MSMZ_HIP(hipMemcpyAsync(d_in, a, lb, hipMemcpyHostToDevice, stream_));
+    MSMZ_HIP(hipMemcpyAsync(d_in + lb, b, lb, hipMemcpyHostToDevice, stream_));
+    hipLaunchKernelGGL((k_test_field_limbs<F>), dim3((n + 63) / 64), dim3(64), 0, stream_, (int32_t*)d_out,
+                       (uint32_t*)(d_out + lb), (const int32_t*)d_in, (const int32_t*)(d_in + lb), (uint32_t)n, op,
+                       slots_.as<uint32_t>());
+    MSMZ_HIP(hipGetLastError());
+    MSMZ_HIP(hipMemcpyAsync(raw, d_out, lb, hipMemcpyDeviceToHost, stream_));
+    MSMZ_HIP(hipMemcpyAsync(canon, d_out + lb, eb, hipMemcpyDeviceToHost, stream_));
+    MSMZ_HIP(hipStreamSynchronize(stream_));
+    return MSMZ_OK;
+  }
+
   int test_glv(const uint8_t* s, uint64_t n, uint8_t* s0, uint8_t* s1, uint8_t* neg) override {
     if (!Fr::HAS_GLV) return MSMZ_ERR_UNSUPPORTED;
     if (!s || !s0 || !s1 || !neg || n == 0 || n > (1u << 22)) return MSMZ_ERR_ARG;
@@ -865,6 +885,34 @@ class Engine : public IEngine {
     const uint64_t threads = (op == TP_ADD_X4 || op == TP_DBL_X4) ? 4 * n : n;
     hipLaunchKernelGGL((k_test_point<P, TE>), dim3((threads + 63) / 64), dim3(64), 0, stream_, (uint32_t*)d_out,
                        (const uint32_t*)d_in, (const uint32_t*)(d_in + pb), d_ai, d_bi, (uint32_t)n, op);
+    MSMZ_HIP(hipGetLastError());
+    MSMZ_HIP(hipMemcpyAsync(out, d_out, pb, hipMemcpyDeviceToHost, stream_));
+    MSMZ_HIP(hipStreamSynchronize(stream_));
+    return MSMZ_OK;
+  }
+
+  int test_point_raw(int op, const uint8_t* a, const uint8_t* b, const uint8_t* neg, uint64_t n, int L,
+                     uint8_t* out) override {
+    if (!a || !b || !out || n == 0 || n > (1u << 20) || op < 0 || op >= TPR_COUNT || L < 0 || L > 4096)
+      return MSMZ_ERR_ARG;
+    if (TE && op == TPR_MDBL) return MSMZ_ERR_UNSUPPORTED;
+    MSMZ_HIP(hipSetDevice(device_));
+    const size_t rb = (size_t)4 * FE_BYTES * n, pb = (size_t)2 * FE_BYTES * n;
+    uint8_t *d_in, *d_out;
+    int st = test_buffers(2 * rb + n, pb, &d_in, &d_out);
+    if (st) return st;
+    MSMZ_HIP(hipMemcpyAsync(d_in, a, rb, hipMemcpyHostToDevice, stream_));
+    MSMZ_HIP(hipMemcpyAsync(d_in + rb, b, rb, hipMemcpyHostToDevice, stream_));
+    uint8_t* d_neg = nullptr;
+    if (neg) {
+      d_neg = d_in + 2 * rb;
+      MSMZ_HIP(hipMemcpyAsync(d_neg, neg, n, hipMemcpyHostToDevice, stream_));
+    }
+    using P = typename std::conditional<TE, TePolicy<F>, WeierPolicy<F>>::type;
+    const bool x4 = op == TPR_ADD_X4 || op == TPR_DBL_X4 || op == TPR_CHAIN_X4;
+    const uint64_t threads = x4 ? 4 * n : n;
+    hipLaunchKernelGGL((k_test_point_raw<P, TE>), dim3((threads + 63) / 64), dim3(64), 0, stream_, (uint32_t*)d_out,
+                       (const uint32_t*)d_in, (const uint32_t*)(d_in + rb), d_neg, (uint32_t)n, op, L);
     MSMZ_HIP(hipGetLastError());
     MSMZ_HIP(hipMemcpyAsync(out, d_out, pb, hipMemcpyDeviceToHost, stream_));
     MSMZ_HIP(hipStreamSynchronize(stream_));

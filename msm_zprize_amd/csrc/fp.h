@@ -7,6 +7,10 @@
 //   memory   : NW saturated 32-bit words, little endian ( = NW/2 64-bit limbs: 6x64 for the
 //              377/381-bit fields, 4x64 for the 255-bit fields).  Values in memory are
 //              Montgomery residues x*R mod p, *lazily* reduced: any value in [0, 3p).
+//              This is THE memory range, the one every other comment refers to: every writer produces it
+//              (fe_store, slot records: [0, 3p); fe_store_mulout: (0.5p, 2.5p)) and the curve formulas rely on it
+//              (te_madd's 2Z - C reaches 7.5p, under the 8p mul bound of the 255-bit fields, only because Z < 3p).
+//              A single fe_mul / fe_sqr / fe_store also accepts [0, 4p), which the field test hooks use.
 //   registers: N signed limbs of W bits (radix 2^W, R = 2^(N*W)); a value is sum l[j]*2^(W*j),
 //              limbs may be negative / wider than W bits between operations ("lazy").
 //
@@ -17,10 +21,14 @@
 // the same limb schedule idea as the reference's w=29 wasm code (multiply-montgomery.ts:47
 // `nSafeSteps`), and the CIOS variant is kept in fp_cios.h for the A/B measurement.
 //
-// Bounds (checked in tests/test_fp_host.py, which compiles this file for the host):
+// Bounds (checked at every call inside the curve formulas by tests/test_fp_contract.py, which compiles this file and
+// curve.h for the host with traced field types and reports the worst case seen at each call site):
 //   mul/sqr inputs : |value| < 2^5 * p (2^3 * p for the 255-bit fields) and the limb magnitudes
 //                    A, B of the two operands satisfy  N*A*B + N*2^(2W) < 2^63
 //   mul/sqr output : value in (-1.5p, 0.5p), limbs 0..N-2 in [0, 2^W), top limb small signed.
+//   fe_reduce_small, fe_store, fe_is_zero : |value| < 2^4 * p, any limb form (up to four uncarried mul outputs);
+//                    fe_reduce_small / fe_store return [0, 3p) with normalized limbs
+//   fe_store_mulout: a mul/sqr output, value in (-1.5p, 0.5p)
 #pragma once
 #include <cstdint>
 
@@ -41,11 +49,12 @@
 #define MSMZ_OPAQUE_LIMB(x) (void)0
 #define MSMZ_OPAQUE_ACC(x) (void)0
 #endif
-// MSMZ_FE_ILP = 1 (set per translation unit): a column of fe_mul / fe_sqr is summed in THREE independent chains that
-// the compiler may not fuse back into one.  A back-to-back dependent v_mad_i64_i32 issues only every ~16 cycles, so a
-// kernel that runs one or two waves per SIMD (the bucket reduction: long dependent point additions, 256+ VGPRs) is
-// bound by that latency; kernels at four waves per SIMD (k_batch_add) hide it and keep the single chain, which has
-// ~70 fewer instructions per product.
+// MSMZ_FE_ILP = 1 (a per-translation-unit option; no build sets it today): a column of fe_mul / fe_sqr is summed in
+// THREE independent chains that the compiler may not fuse back into one.  A back-to-back dependent v_mad_i64_i32 issues
+// only every ~16 cycles, so a kernel that runs one or two waves per SIMD (long dependent point additions, 256+ VGPRs)
+// could be bound by that latency; kernels at four waves per SIMD (k_batch_add) hide it and keep the single chain, which
+// has ~70 fewer instructions per product.  tests/test_fp_contract.py builds its host driver both ways, so the branch
+// stays checked against the same contract.
 #ifndef MSMZ_FE_ILP
 #define MSMZ_FE_ILP 0
 #endif

@@ -76,10 +76,14 @@
 
 #define MSMZ_INST_TEST(F, Fr, P, TE, PFX)                                                                         \
   PFX template __global__ void k_test_field<F>(uint32_t*, const uint32_t*, const uint32_t*, uint32_t, int, uint32_t*); \
+  PFX template __global__ void k_test_field_limbs<F>(int32_t*, uint32_t*, const int32_t*, const int32_t*, uint32_t,  \
+                                                      int, uint32_t*);                                            \
   PFX template __global__ void k_test_glv<Fr>(uint32_t*, uint32_t*, uint8_t*, const uint32_t*, uint32_t);         \
   PFX template __global__ void k_test_digits<Fr, false>(uint32_t*, const uint32_t*, uint32_t, int, int);          \
   PFX template __global__ void k_test_point<P, TE>(uint32_t*, const uint32_t*, const uint32_t*, const uint8_t*,   \
-                                                   const uint8_t*, uint32_t, int);
+                                                   const uint8_t*, uint32_t, int);                                \
+  PFX template __global__ void k_test_point_raw<P, TE>(uint32_t*, const uint32_t*, const uint32_t*, const uint8_t*, \
+                                                       uint32_t, int, int);
 
 // sort kernels: window size 0 = any, 16 / 17 = the defaults of large inputs (window loop unrolled)
 #define MSMZ_INST_SORT(Fr, GLV, C, PFX)                                                                           \

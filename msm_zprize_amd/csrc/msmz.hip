@@ -200,6 +200,10 @@ int msmz_test_retries(msmz_ctx* c) { return c ? c->engine->test_retries() : -1; 
 int msmz_test_field(msmz_ctx* c, int op, const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out) {
   return c ? c->engine->test_field(op, a, b, n, out) : MSMZ_ERR_ARG;
 }
+int msmz_test_field_limbs(msmz_ctx* c, int op, const int32_t* a, const int32_t* b, uint64_t n, int32_t* raw,
+                          uint8_t* canon) {
+  return c ? c->engine->test_field_limbs(op, a, b, n, raw, canon) : MSMZ_ERR_ARG;
+}
 int msmz_test_glv(msmz_ctx* c, const uint8_t* s, uint64_t n, uint8_t* s0, uint8_t* s1, uint8_t* neg) {
   return c ? c->engine->test_glv(s, n, s0, s1, neg) : MSMZ_ERR_ARG;
 }
@@ -209,6 +213,10 @@ int msmz_test_digits(msmz_ctx* c, const uint8_t* s, uint64_t n, int cc, int K, i
 int msmz_test_sort(msmz_ctx* c, const uint8_t* s, uint64_t n, int cc, int glv, int force_fallback, uint32_t* geom,
                    uint32_t* off, uint64_t off_cap, uint32_t* refs, uint64_t refs_cap) {
   return c ? c->engine->test_sort(s, n, cc, glv, force_fallback, geom, off, off_cap, refs, refs_cap) : MSMZ_ERR_ARG;
+}
+int msmz_test_point_raw(msmz_ctx* c, int op, const uint8_t* a, const uint8_t* b, const uint8_t* neg, uint64_t n, int L,
+                        uint8_t* out) {
+  return c ? c->engine->test_point_raw(op, a, b, neg, n, L, out) : MSMZ_ERR_ARG;
 }
 int msmz_test_point(msmz_ctx* c, int op, const uint8_t* a, const uint8_t* ai, const uint8_t* b, const uint8_t* bi,
                     uint64_t n, uint8_t* out) {

@@ -59,12 +59,18 @@ class IEngine {
   virtual int test_set_glv_bits(int) { return MSMZ_ERR_UNSUPPORTED; }
   virtual int test_retries() { return 0; }
   virtual int test_field(int, const uint8_t*, const uint8_t*, uint64_t, uint8_t*) { return MSMZ_ERR_UNSUPPORTED; }
+  virtual int test_field_limbs(int, const int32_t*, const int32_t*, uint64_t, int32_t*, uint8_t*) {
+    return MSMZ_ERR_UNSUPPORTED;
+  }
   virtual int test_glv(const uint8_t*, uint64_t, uint8_t*, uint8_t*, uint8_t*) { return MSMZ_ERR_UNSUPPORTED; }
   virtual int test_digits(const uint8_t*, uint64_t, int, int, int, uint32_t*) { return MSMZ_ERR_UNSUPPORTED; }
   virtual int test_sort(const uint8_t*, uint64_t, int, int, int, uint32_t*, uint32_t*, uint64_t, uint32_t*, uint64_t) {
     return MSMZ_ERR_UNSUPPORTED;
   }
   virtual int test_point(int, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*, uint64_t, uint8_t*) {
+    return MSMZ_ERR_UNSUPPORTED;
+  }
+  virtual int test_point_raw(int, const uint8_t*, const uint8_t*, const uint8_t*, uint64_t, int, uint8_t*) {
     return MSMZ_ERR_UNSUPPORTED;
   }
 };
@@ -338,6 +344,9 @@ class MultiEngine : public IEngine {
   int test_field(int op, const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out) override {
     return workers_[0]->eng->test_field(op, a, b, n, out);
   }
+  int test_field_limbs(int op, const int32_t* a, const int32_t* b, uint64_t n, int32_t* raw, uint8_t* canon) override {
+    return workers_[0]->eng->test_field_limbs(op, a, b, n, raw, canon);
+  }
   int test_glv(const uint8_t* s, uint64_t n, uint8_t* s0, uint8_t* s1, uint8_t* neg) override {
     return workers_[0]->eng->test_glv(s, n, s0, s1, neg);
   }
@@ -351,6 +360,10 @@ class MultiEngine : public IEngine {
   int test_point(int op, const uint8_t* a, const uint8_t* ai, const uint8_t* b, const uint8_t* bi, uint64_t n,
                  uint8_t* out) override {
     return workers_[0]->eng->test_point(op, a, ai, b, bi, n, out);
+  }
+  int test_point_raw(int op, const uint8_t* a, const uint8_t* b, const uint8_t* neg, uint64_t n, int L,
+                     uint8_t* out) override {
+    return workers_[0]->eng->test_point_raw(op, a, b, neg, n, L, out);
   }
 
  private:

@@ -6,6 +6,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kernels.h"
+#include "test_ops.h"
 
 namespace msmz {
 
@@ -16,9 +17,13 @@ enum {   // field ops (msmz_test_field)
 enum {   // point ops (msmz_test_point)
   TP_ADD = 0, TP_ADD_X4 = 1, TP_MADD = 2, TP_DBL = 3, TP_DBL_X4 = 4
 };
+enum {   // point ops on memory-format operands (msmz_test_point_raw)
+  TPR_ADD = 0, TPR_ADD_X4 = 1, TPR_MADD = 2, TPR_DBL = 3, TPR_DBL_X4 = 4, TPR_MDBL = 5, TPR_CHAIN = 6, TPR_CHAIN_X4 = 7,
+  TPR_COUNT = 8
+};
 
 // Operands / results are NW memory words per element (little endian).  Inputs are lazy Montgomery residues: any
-// value in [0, 4p).  Results are the CANONICAL representative of the routine's output residue:
+// value in [0, 4p) for the field ops (the kernels write [0, 3p), see fp.h).  Results are the CANONICAL representative of the routine's output residue:
 //   MUL a*b/R, SQR a*a/R, ADD, SUB, INVERSE(_WAVE)  R^2/a  (0 for a = 0 mod p), ROUNDTRIP a (store -> load),
 //   IS_ZERO  1 / 0 in word 0, SLOT_ROUNDTRIP a through the slot-record format of the tree rounds.
 template <class F>
@@ -83,6 +88,62 @@ __global__ void __launch_bounds__(64) k_test_field(uint32_t* out, const uint32_t
   }
 #pragma unroll
   for (int j = 0; j < NW; j++) out[(size_t)i * NW + j] = w[j];
+}
+
+// field routines on raw register limbs (msmz_test_field_limbs): the ops of field_limbs_op (test_ops.h, the code the
+// host contract driver runs too) plus the device-only ones.  a, b, raw: N int32 limbs per element; canon: NW words.
+template <class F>
+__global__ void __launch_bounds__(64) k_test_field_limbs(int32_t* raw, uint32_t* canon, const int32_t* a_in,
+                                                         const int32_t* b_in, uint32_t n, int op, uint32_t* scratch) {
+  constexpr int N = F::N, NW = F::NW;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  // whole waves stay alive: fe_inverse_wave spreads one value over the lanes of a wave
+  const uint32_t ii = i < n ? i : n - 1;
+  Fe<F> a, b, r;
+#pragma unroll
+  for (int j = 0; j < N; j++) {
+    a.l[j] = a_in[(size_t)ii * N + j];
+    b.l[j] = b_in[(size_t)ii * N + j];
+  }
+  int32_t rl[N];
+  uint32_t cw[NW];
+  if (!field_limbs_op<F>(op, a, b, rl, cw)) {
+    fe_zero(r);
+    switch (op) {
+      case TFL_INVERSE_WAVE:
+        for (int l = 0; l < 64; l++) {
+          Fe<F> x, y;
+#pragma unroll
+          for (int j = 0; j < N; j++) x.l[j] = __shfl(a.l[j], l, 64);
+          fe_inverse_wave(y, x);
+          if ((int)(threadIdx.x & 63) == l) r = y;
+        }
+        break;
+      case TFL_SLOT_MULOUT:
+        slot_store_mulout<F>(scratch + slot_offset<F>(ii), a);
+        slot_load_fe<F>(r, scratch + slot_offset<F>(ii));
+        break;
+      case TFL_SLOT_POINT: {
+        Affine<F> p, q;
+        p.x = a;
+        p.y = b;
+        slot_store_point<F>(scratch + slot_offset<F>(ii), p, false);
+        slot_load_point<F, false>(q, scratch + slot_offset<F>(ii));
+        r = q.y;
+        fe_to_canon_words<F>(cw, q.x);
+        break;
+      }
+      default: break;
+    }
+#pragma unroll
+    for (int j = 0; j < N; j++) rl[j] = r.l[j];
+    if (op != TFL_SLOT_POINT) fe_to_canon_words<F>(cw, r);
+  }
+  if (i >= n) return;
+#pragma unroll
+  for (int j = 0; j < N; j++) raw[(size_t)i * N + j] = rl[j];
+#pragma unroll
+  for (int j = 0; j < NW; j++) canon[(size_t)i * NW + j] = cw[j];
 }
 
 // GLV decomposition of n scalars: out0/out1 = |s0|, |s1| (4 words each), neg[2i], neg[2i+1] = their signs
@@ -172,9 +233,105 @@ __global__ void __launch_bounds__(64) k_test_point(uint32_t* out, const uint32_t
       break;
     }
     case TP_DBL: P::dbl(r, a); break;
+    case TP_MADD: {   // a + b with b as the input record of the bucket accumulation (affine / Niels, memory format)
+      alignas(16) uint32_t rec[4 * NW];   // load_words reads it as 16-byte vectors
+      if constexpr (TE) {
+        Fe<F> ym, yp, kt, k;
+        fe_sub(ym, b.Y, b.X);
+        fe_add(yp, b.Y, b.X);
+        fe_set_const<F>(k, F::K2D);
+        fe_mul(kt, b.T, k);
+        fe_store<F>(rec, ym);
+        fe_store<F>(rec + NW, yp);
+        fe_store<F>(rec + 2 * NW, kt);
+      } else {
+        const bool binf = b_inf != nullptr && b_inf[ii];
+        fe_store<F>(rec, b.X);
+        fe_store<F>(rec + NW, b.Y);
+        if (binf) {
+#pragma unroll
+          for (int j = 0; j < 2 * NW; j++) rec[j] = 0;
+        }
+      }
+#pragma unroll
+      for (int j = 3 * NW; j < 4 * NW; j++) rec[j] = 0;
+      P::madd(r, a, rec, 0);
+      break;
+    }
     default: P::add(r, a, b); break;
   }
   if (i >= n || (x4 && (threadIdx.x & 3) != 0)) return;
+  uint32_t w[2 * NW];
+  if constexpr (TE) {
+    te_to_affine_canon<F>(w, r);
+  } else {
+    (void)xyzz_to_affine_canon<F>(w, r);
+  }
+#pragma unroll
+  for (int j = 0; j < 2 * NW; j++) out[(size_t)i * 2 * NW + j] = w[j];
+}
+
+// point operations on operands in the kernels' own form: every coordinate a lazy memory-format Montgomery residue,
+// loaded with fe_unpack as the kernels load it (no conversion).  a[i]: accumulator (X, Y, ZZ, ZZZ) / (X, Y, Z, T),
+// 4*NW words.  b[i]: 4*NW words -- an accumulator (ADD, CHAIN), an affine record [x | y | 0 | 0] (MADD, MDBL; all-zero =
+// infinity) or a Niels record [y-x | y+x | 2dxy | 0] (TE MADD).  neg[i] (nullable): negate the MADD / MDBL record as the
+// bucket accumulation does.  CHAIN: L steps r <- r + b (even steps), r <- 2r (odd steps) in registers, from r = a,
+// with the scalar or the 4-lane formulas.  out[i] = canonical affine (x | y) of the result; all-zero = infinity.
+template <class P, bool TE>
+__global__ void __launch_bounds__(64) k_test_point_raw(uint32_t* out, const uint32_t* a_in, const uint32_t* b_in,
+                                                       const uint8_t* neg, uint32_t n, int op, int L) {
+  using F = typename P::F;
+  using Acc = typename P::Acc;
+  constexpr int NW = F::NW;
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool x4 = op == TPR_ADD_X4 || op == TPR_DBL_X4 || op == TPR_CHAIN_X4;
+  const int s = (int)(threadIdx.x & 3);
+  const uint32_t i = x4 ? t >> 2 : t;   // a DPP quad per element for the 4-lane formulas
+  const uint32_t ii = i < n ? i : n - 1;
+  const uint32_t* arec = a_in + (size_t)ii * 4 * NW;
+  const uint32_t* brec = b_in + (size_t)ii * 4 * NW;
+  const uint32_t ng = neg != nullptr ? (uint32_t)neg[ii] & 1u : 0u;
+  auto load = [&](Acc& p, const uint32_t* rec) {
+    Fe<F>* c = reinterpret_cast<Fe<F>*>(&p);
+#pragma unroll
+    for (int k = 0; k < 4; k++) fe_unpack<F>(c[k], rec + k * NW);
+  };
+  Acc a, b, r;
+  load(a, arec);
+  switch (op) {
+    case TPR_ADD: load(b, brec); P::add(r, a, b); break;
+    case TPR_ADD_X4: load(b, brec); P::add_x4(r, a, b, s, false); break;
+    case TPR_DBL: P::dbl(r, a); break;
+    case TPR_DBL_X4: P::add_x4(r, a, a, s, true); break;
+    case TPR_MADD: P::madd(r, a, brec, ng); break;
+    case TPR_MDBL:
+      if constexpr (!TE) {
+        Affine<F> q;
+        load_affine<F>(q, brec, ng);
+        xyzz_mdbl(r, q);
+      } else {
+        r = a;
+      }
+      break;
+    case TPR_CHAIN:
+    case TPR_CHAIN_X4: {
+      load(b, brec);
+      r = a;
+#pragma unroll 1
+      for (int k = 0; k < L; k++) {
+        Acc u;
+        if (op == TPR_CHAIN) {
+          if (k & 1) P::dbl(u, r); else P::add(u, r, b);
+        } else {
+          if (k & 1) P::add_x4(u, r, r, s, true); else P::add_x4(u, r, b, s, false);
+        }
+        r = u;
+      }
+      break;
+    }
+    default: r = a; break;
+  }
+  if (i >= n || (x4 && s != 0)) return;
   uint32_t w[2 * NW];
   if constexpr (TE) {
     te_to_affine_canon<F>(w, r);
