@@ -453,7 +453,7 @@ class Engine : public IEngine {
     if (opt.buckets == MSMZ_BUCKETS_PROJECTIVE || opt.reserved[0] == 1) return MSMZ_ERR_UNSUPPORTED;
     if (opt.c < 0 || opt.c > 24) return MSMZ_ERR_ARG;
     int glv = opt.glv;
-    if (glv < 0) glv = (Fr::HAS_GLV && n < (1ull << 15)) ? 1 : 0;   // msm()'s choice for n points
+    if (glv < 0) glv = default_glv(n) ? 1 : 0;   // msm()'s choice for n points
     if (glv && !Fr::HAS_GLV) return MSMZ_ERR_UNSUPPORTED;
     glv = glv ? 1 : 0;
     const uint64_t M64 = glv ? 2 * n : n;
@@ -540,38 +540,25 @@ class Engine : public IEngine {
 
   int msm(uint64_t ph, const uint8_t* host_scalars, uint64_t sh, uint64_t n, const msmz_opts* o, uint8_t* out,
           int* out_inf, msmz_log* log, const GenMap* split = nullptr) override {
-    auto t_begin = std::chrono::steady_clock::now();
-    if (!out || !out_inf || n == 0) return MSMZ_ERR_ARG;
-    auto pit = handles_.find(ph);
-    if (pit == handles_.end() || pit->second.kind != 0 || pit->second.n < n) return MSMZ_ERR_ARG;
-    msmz_opts opt;
-    int st0 = resolve_opts(pit->second, o, &opt);
-    if (st0) return st0;
-    // glv < 0: the engine's choice.  The split halves the windows but doubles the point set (index bits, gathers, tree
-    // depth); since the two-dimensional bucket reduction made the reduction cheap per window it is only ahead on the
-    // smallest inputs (profiles/r03_sweep.json: 2^14 0.85 vs 0.88 ms, 2^16 1.11 vs 1.07, 2^20 3.87 vs 3.64, 2^23 23.5 vs 20.5).
-    if (opt.glv < 0) opt.glv = (!TE && Fr::HAS_GLV && pit->second.has_endo && n < (1ull << 15)) ? 1 : 0;
-    MSMZ_HIP(hipSetDevice(device_));
+    return msm_batch(ph, host_scalars, sh, n, 1, o, out, out_inf, log, split);
+  }
 
-    const uint32_t* d_scalars = nullptr;
-    if (host_scalars) {
-      // range (< group order) is checked on the device while the scalars are sliced
-      int st = stage_.ensure(n * 32);
-      if (st) return st;
-      if ((st = copy_h2d(stage_.p, host_scalars, 32, n, split))) return st;
-      d_scalars = stage_.as<uint32_t>();
-    } else {
-      auto sit = handles_.find(sh);
-      if (sit == handles_.end() || sit->second.kind != 1 || sit->second.n < n) return MSMZ_ERR_ARG;
-      d_scalars = (const uint32_t*)sit->second.dev;
-    }
-    if (log) memset(log, 0, sizeof(*log));
-    const int st = msm_passes(pit->second, d_scalars, n, opt, out, out_inf, log);
-    if (log) {
-      log->stage_ms[MSMZ_ST_TOTAL] =
-          std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    }
-    return st;
+  // glv < 0: the engine's choice for n points.  The split halves the windows but doubles the point set (index bits,
+  // gathers, tree depth); since the two-dimensional bucket reduction made the reduction cheap per window it is only
+  // ahead on the smallest inputs (profiles/r03_sweep.json: 2^14 0.85 vs 0.88 ms, 2^16 1.11 vs 1.07, 2^20 3.87 vs 3.64,
+  // 2^23 23.5 vs 20.5).
+  static bool default_glv(uint64_t n) { return !TE && Fr::HAS_GLV && n < (1ull << 15); }
+
+  // run(extra_bits): a GLV half longer than the assumed 127 bits (k_hist flags it) redoes the MSM with windows for the
+  // PROVEN bound (Fr::GLV_PROVEN_BITS, tools/gen_constants.py), which no half can exceed -- a second flag is an
+  // internal error
+  template <class Run>
+  int glv_retry(Run run) {
+    int st = run(0);
+    if (st != MSMZ_ERR_RETRY_BITS) return st;
+    retries_++;
+    st = run(1);
+    return st == MSMZ_ERR_RETRY_BITS ? MSMZ_ERR_ARG : st;
   }
 
   // one MSM over device scalars (log: zeroed by the caller, or null)
@@ -590,14 +577,10 @@ class Engine : public IEngine {
       msmz_log plog;
       msmz_log* lp = log ? &plog : nullptr;
       if (lp) memset(lp, 0, sizeof(*lp));
-      st = Cfg::run_msm(*this, pts, d_points, d_sc, cnt, opt, done == 0 ? out : part, done == 0 ? out_inf : &pinf, lp, 0);
-      if (st == MSMZ_ERR_RETRY_BITS) {
-        // a GLV half longer than the assumed 127 bits (k_hist flags it): redo with windows for the PROVEN bound
-        // (Fr::GLV_PROVEN_BITS, tools/gen_constants.py), which no half can exceed -- a second flag is an internal error
-        retries_++;
-        st = Cfg::run_msm(*this, pts, d_points, d_sc, cnt, opt, done == 0 ? out : part, done == 0 ? out_inf : &pinf, lp, 1);
-        if (st == MSMZ_ERR_RETRY_BITS) st = MSMZ_ERR_ARG;
-      }
+      st = glv_retry([&](int extra_bits) {
+        return Cfg::run_msm(*this, pts, d_points, d_sc, cnt, opt, done == 0 ? out : part, done == 0 ? out_inf : &pinf, lp,
+                            extra_bits);
+      });
       if (st) break;
       if (done > 0) {
         uint8_t acc[RW * 4];
@@ -631,8 +614,7 @@ class Engine : public IEngine {
     msmz_opts opt;
     int st0 = resolve_opts(pit->second, o, &opt);
     if (st0) return st0;
-    // (the engine's choice of msm(): per problem size, so that batch = 1 is msm() exactly)
-    if (opt.glv < 0) opt.glv = (!TE && Fr::HAS_GLV && pit->second.has_endo && n < (1ull << 15)) ? 1 : 0;
+    if (opt.glv < 0) opt.glv = pit->second.has_endo && default_glv(n) ? 1 : 0;   // (per problem: batch = 1 is msm())
     if (host_stride == 0) host_stride = n;
     if (host_scalars && host_stride < n) return MSMZ_ERR_ARG;
     MSMZ_HIP(hipSetDevice(device_));
@@ -659,8 +641,8 @@ class Engine : public IEngine {
     if (log) memset(log, 0, sizeof(*log));
     const Handle& pts = pit->second;
     const uint64_t per_pass = (opt.glv != 0 && !TE) ? kMaxEntriesPerPass / 2 : kMaxEntriesPerPass;
-    const bool batched = !TE && opt.buckets != MSMZ_BUCKETS_PROJECTIVE && opt.reserved[0] != 1 && reduce2d_ &&
-                         n <= per_pass && batch > 1;
+    const bool batched = !TE && opt.buckets != MSMZ_BUCKETS_PROJECTIVE && opt.reserved[0] != 1 && n <= per_pass &&
+                         batch > 1;
     int st = MSMZ_OK;
     for (uint32_t done = 0; done < batch && st == MSMZ_OK;) {
       uint32_t bs = batched ? batch_size(pts, n, opt, batch - done) : 1;
@@ -669,14 +651,10 @@ class Engine : public IEngine {
       msmz_log* lp = log ? &plog : nullptr;
       if (lp) memset(lp, 0, sizeof(*lp));
       if (bs > 1) {
-        st = msm_weierstrass_affine(pts, (const uint32_t*)pts.dev, d_sc, n, opt, out + (size_t)done * RW * 4,
-                                    out_inf + done, lp, 0, bs);
-        if (st == MSMZ_ERR_RETRY_BITS) {   // a GLV half longer than assumed (see msm_passes): the whole sub-batch again
-          retries_++;
-          st = msm_weierstrass_affine(pts, (const uint32_t*)pts.dev, d_sc, n, opt, out + (size_t)done * RW * 4,
-                                      out_inf + done, lp, 1, bs);
-          if (st == MSMZ_ERR_RETRY_BITS) st = MSMZ_ERR_ARG;
-        }
+        st = glv_retry([&](int extra_bits) {   // (a GLV half longer than assumed: the whole sub-batch again)
+          return msm_weierstrass_affine(pts, (const uint32_t*)pts.dev, d_sc, n, opt, out + (size_t)done * RW * 4,
+                                        out_inf + done, lp, extra_bits, bs);
+        });
         if (st == MSMZ_ERR_BATCH_LOOP) {
           bs = 1;
           st = MSMZ_OK;
@@ -1385,42 +1363,70 @@ class Engine : public IEngine {
     return S1 < pl.L ? S1 : pl.L;
   }
 
-  // copy the K window sums (the C entries of the last level; its rows are multiples of L and not needed) to the host
-  template <class P>
-  int fetch_window_sums(const Plan& pl, int cur, uint32_t nprob = 0) {
-    constexpr int AW = P::ACC_WORDS;
+  // copy the window results of all pl.nprob problems (the C entries of the last level; its rows are multiples of the
+  // weight unit and not needed) and the meta block to the host: one problem's behind h_final_'s first kMaxWindows
+  // records, a batch's to h_bfinal_
+  int fetch_window_sums(const Plan& pl, size_t per_problem, const uint32_t** res) {
+    const size_t words = pl.nprob * per_problem * XW;
+    uint32_t* dst = h_final_ + (size_t)kMaxWindows * XW;
+    if (pl.nprob > 1) {
+      if (int st = ensure_batch_final(words)) return st;
+      dst = h_bfinal_;
+    }
     MSMZ_HIP(hipGetLastError());
-    (void)cur;
-    if (nprob == 0) nprob = (uint32_t)pl.Keff;
-    MSMZ_HIP(hipMemcpyAsync(h_final_ + (size_t)kMaxWindows * AW, final_.p, (size_t)nprob * AW * 4,
-                            hipMemcpyDeviceToHost, stream_));
+    MSMZ_HIP(hipMemcpyAsync(dst, final_.p, words * 4, hipMemcpyDeviceToHost, stream_));
     MSMZ_HIP(hipMemcpyAsync(h_meta_, meta_.p, sizeof(MsmMeta), hipMemcpyDeviceToHost, stream_));
     MSMZ_HIP(hipStreamSynchronize(stream_));
+    *res = dst;
     return MSMZ_OK;
   }
 
-  // final sum on the host (msm-batched-affine.ts:300-322): W_k = C_k of the last level, Horner over windows
-  void finalize_weierstrass(const Plan& pl, uint8_t* out, int* out_inf) {
-    // ~K*c dependent doublings: on 64-bit limbs (host64.h), ~4x faster on a CPU core than the kernels' limb code
-    using H = Host64<F>;
-    typename H::Pt acc, w, t;
-    host64_.set_inf(acc);
-    for (int k = pl.Keff - 1; k >= 0; k--) {
-      if (k < pl.K - 1)   // windows K-1 .. Keff-1 are the sub-windows of the top window: same weight
-        for (int j = 0; j < pl.c; j++) {
-          host64_.dbl(t, acc);
-          acc = t;
-        }
-      host64_.load_pt(w, h_final_ + (size_t)(kMaxWindows + k) * XW);   // W_k = C of the last level
-      host64_.add_pt(t, acc, w);
-      acc = t;
+  // twisted Edwards as a host group of host_horner (fp.h limbs)
+  struct HostTe {
+    using Pt = TeExt<F>;
+    void set_inf(Pt& p) const { te_set_zero(p); }
+    void dbl(Pt& r, const Pt& p) const { te_add(r, p, p); }
+    void add_pt(Pt& r, const Pt& a, const Pt& b) const { te_add(r, a, b); }
+    void load_pt(Pt& p, const uint32_t* w) const {
+      fe_unpack<F>(p.X, w);
+      fe_unpack<F>(p.Y, w + NW);
+      fe_unpack<F>(p.Z, w + 2 * NW);
+      fe_unpack<F>(p.T, w + 3 * NW);
     }
-    Xyzz<F> fin;
-    host64_.to_xyzz(fin, acc);
-    uint32_t res[RW];
-    bool inf = xyzz_to_affine_canon<F>(res, fin);
-    memcpy(out, res, RW * 4);
-    *out_inf = inf ? 1 : 0;
+  };
+
+  // The end of every MSM, after its bucket reduction: fetch the window results (two_d: two per bucket set, else one),
+  // combine each problem's on the host (msm-batched-affine.ts:300-322) and fill the log.
+  int finish_msm(Plan& pl, bool two_d, uint8_t* out, int* out_inf, msmz_log* log, int R, uint64_t n_pairs, int ev_plan0,
+                 int ev_plan1, int ev_acc_end, int round_ev0) {
+    const int ev_red_end = pl.ei;
+    mark(pl);
+    const size_t per_problem = (size_t)(two_d ? 2 : 1) * pl.Keff;
+    // (the terms are listed while the device still reduces)
+    const std::vector<WindowTerm> terms =
+        window_terms(pl.c, pl.K, pl.Keff, (int)pl.F, two_d ? split_2d(pl).b : -1, pl.fold_shift != 0);
+    const uint32_t* res;
+    int st = fetch_window_sums(pl, per_problem, &res);
+    if (st) return st;
+    const auto t_host = std::chrono::steady_clock::now();
+    if (h_meta_->error & 1u) return MSMZ_ERR_DEGENERATE;
+    for (uint32_t p = 0; p < pl.nprob; p++) {
+      const uint32_t* rp = res + p * per_problem * XW;
+      uint32_t w[RW];
+      if constexpr (TE) {
+        te_to_affine_canon<F>(w, host_horner(HostTe{}, terms, rp, XW));
+        out_inf[p] = 0;
+      } else {
+        // ~K*c dependent doublings: on 64-bit limbs (host64.h), ~4x faster on a CPU core than the kernels' limb code
+        Xyzz<F> fin;
+        host64_.to_xyzz(fin, host_horner(host64_, terms, rp, XW));
+        out_inf[p] = xyzz_to_affine_canon<F>(w, fin) ? 1 : 0;
+      }
+      memcpy(out + (size_t)p * RW * 4, w, sizeof(w));
+    }
+    const float host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_host).count();
+    fill_log(log, pl, R, n_pairs, ev_plan0, ev_plan1, ev_acc_end, ev_red_end, round_ev0, host_ms);
+    return MSMZ_OK;
   }
 
   // Two-dimensional bucket reduction (reduce2d_kernels.h): line sums, then the weighted sums over H lines of 2 Keff
@@ -1499,66 +1505,6 @@ class Engine : public IEngine {
     MSMZ_HIP(hipGetLastError());
     return MSMZ_OK;
   }
-  // Horner over the windows with the two results of every bucket set: acc = (acc * 2^(c-b) + A) * 2^b + B.
-  // res2: the problem's 2 Keff results (default: the single MSM's, fetched behind h_final_'s first kMaxWindows records)
-  void finalize_weierstrass_2d(const Plan& pl, uint8_t* out, int* out_inf, const uint32_t* res2 = nullptr) {
-    if (!res2) res2 = h_final_ + (size_t)kMaxWindows * XW;
-    using H = Host64<F>;
-    typename H::Pt acc, w, t;
-    host64_.set_inf(acc);
-    const Split2d sp = split_2d(pl);
-    if (pl.F > 1) {
-      // precomputed point set: set s holds windows [s F, (s + 1) F) at weight 2^(c F s): acc = (acc * 2^(c F - b) + A_s) * 2^b + B_s
-      auto dbl_n = [&](int cnt) {
-        for (int j = 0; j < cnt; j++) {
-          host64_.dbl(t, acc);
-          acc = t;
-        }
-      };
-      auto add = [&](int r) {
-        host64_.load_pt(w, res2 + (size_t)r * XW);
-        host64_.add_pt(t, acc, w);
-        acc = t;
-      };
-      for (int s = pl.Keff - 1; s >= 0; s--) {
-        if (s < pl.Keff - 1) dbl_n(pl.c * (int)pl.F - sp.b);
-        add(2 * s);
-        dbl_n(sp.b);
-        add(2 * s + 1);
-      }
-    } else {
-      auto add_results = [&](int k, int which) {
-        // bucket sets of window k: kw = k below the top window, K-1 .. Keff-1 (its sub-windows) for the top one
-        const int lo = k, hi = (k == pl.K - 1) ? pl.Keff - 1 : k;
-        if (which == 0 && k == pl.K - 1 && pl.fold_shift != 0) return;   // folded top window: its rows are copies, not weights
-        for (int kw = lo; kw <= hi; kw++) {
-          host64_.load_pt(w, res2 + (size_t)(2 * kw + which) * XW);
-          host64_.add_pt(t, acc, w);
-          acc = t;
-        }
-      };
-      for (int k = pl.K - 1; k >= 0; k--) {
-        if (k < pl.K - 1)
-          for (int j = 0; j < pl.c - sp.b; j++) {
-            host64_.dbl(t, acc);
-            acc = t;
-          }
-        add_results(k, 0);   // rows: weight 2^(c k + b)
-        for (int j = 0; j < sp.b; j++) {
-          host64_.dbl(t, acc);
-          acc = t;
-        }
-        add_results(k, 1);   // columns: weight 2^(c k)
-      }
-    }
-    Xyzz<F> fin;
-    host64_.to_xyzz(fin, acc);
-    uint32_t res[RW];
-    bool inf = xyzz_to_affine_canon<F>(res, fin);
-    memcpy(out, res, RW * 4);
-    *out_inf = inf ? 1 : 0;
-  }
-
   void fill_log(msmz_log* log, const Plan& pl, int R, uint64_t n_pairs, int ev_plan0, int ev_plan1, int ev_acc_end,
                 int ev_red_end, int round_ev0, float host_ms) {
     if (!log) return;
@@ -1600,7 +1546,7 @@ class Engine : public IEngine {
     const bool glv = opt.glv != 0;
     if (glv && (!Fr::HAS_GLV || !pts.has_endo)) return MSMZ_ERR_UNSUPPORTED;
     Plan pl;
-    const bool want_2d = opt.reserved[0] != 1 && reduce2d_;
+    const bool want_2d = opt.reserved[0] != 1;   // else reduceAffine: the batched-affine first level (reduce_affine.h)
     // precomputed point set: its copies carry windows [j F, (j + 1) F) into one bucket set (two-level sort, 2-D reduction)
     const uint32_t fac = pts.factor > 1 ? pts.factor : 1;
     if (fac > 1 && (!want_2d || glv != (pts.glv != 0))) return MSMZ_ERR_UNSUPPORTED;
@@ -1608,7 +1554,7 @@ class Engine : public IEngine {
     if (st) return st;
     pl.copy_stride = (uint32_t)pts.copy_stride;
     if (fac > 1 && !sort2_applies(pl)) return MSMZ_ERR_ARG;   // (msmz_precompute_points refuses such sets)
-    if (nprob > 1 && (!want_2d || pl.L < 2 || !sort2_applies(pl))) return MSMZ_ERR_BATCH_LOOP;
+    if (nprob > 1 && (!want_2d || !sort2_applies(pl))) return MSMZ_ERR_BATCH_LOOP;
     // location words hold a record index in 30 bits
     if ((uint64_t)nprob * pl.K * pl.M >= (1ull << 30)) return MSMZ_ERR_ARG;
     // whole groups of 64 records; + the records of the batched-affine first reduction level when it is selected
@@ -1643,9 +1589,7 @@ class Engine : public IEngine {
     if ((st = desc_.ensure((size_t)nprob * pl.K * pl.M * 8))) return st;
     if ((st = bfin_.ensure((size_t)nb * 16))) return st;
     // the batched-affine first reduction level (opt.reserved[0] = 1) wants ONE sum per bucket: no rounds skipped
-    const bool f2 = opt.reserved[0] == 1 && pl.L >= 2;
-    const bool r2d = !f2 && reduce2d_ && pl.L >= 2;
-    const int tail_skip = f2 ? 0 : (r2d ? tail_skip_2d_ : tail_skip_);
+    const int tail_skip = want_2d ? tail_skip_2d_ : 0;
     hipLaunchKernelGGL(k_plan_count, dim3(n_chunks), dim3(PLAN_T), 0, stream_, rscan_.as<uint32_t>(), off_.as<uint32_t>(),
                        nb, n_chunks, d_meta, tail_skip, pc);
     hipLaunchKernelGGL(k_plan_emit, dim3(n_chunks), dim3(PLAN_T), 0, stream_, desc_.as<uint2>(), bfin_.as<uint4>(),
@@ -1688,67 +1632,33 @@ class Engine : public IEngine {
     mark(pl);
 
     // ---- bucket reduction
-    using P = WeierPolicy<F>;
-    if (r2d) {
+    if (want_2d) {
       // two-dimensional: row / column sums of the buckets, then two half-length weighted sums per bucket set
-      if ((st = reduce_2d<P>(pl, d_points))) return st;
-      const int ev_red_end2 = pl.ei;
-      mark(pl);
-      const uint32_t* fin = nullptr;
-      if (nprob == 1) {
-        if ((st = fetch_window_sums<P>(pl, 0, 2u * (uint32_t)pl.Keff))) return st;
-      } else {   // all problems' window results in one copy
-        const size_t words = (size_t)2 * nprob * pl.Keff * XW;
-        if ((st = ensure_batch_final(words))) return st;
-        MSMZ_HIP(hipGetLastError());
-        MSMZ_HIP(hipMemcpyAsync(h_bfinal_, final_.p, words * 4, hipMemcpyDeviceToHost, stream_));
-        MSMZ_HIP(hipMemcpyAsync(h_meta_, meta_.p, sizeof(MsmMeta), hipMemcpyDeviceToHost, stream_));
-        MSMZ_HIP(hipStreamSynchronize(stream_));
-        fin = h_bfinal_;
-      }
-      auto t_host2 = std::chrono::steady_clock::now();
-      if (h_meta_->error & 1u) return MSMZ_ERR_DEGENERATE;
-      for (uint32_t p = 0; p < nprob; p++)
-        finalize_weierstrass_2d(pl, out + (size_t)p * RW * 4, out_inf + p, fin ? fin + (size_t)2 * p * pl.Keff * XW : nullptr);
-      float host_ms2 = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_host2).count();
-      fill_log(log, pl, R, n_pairs, ev_plan0, ev_plan1, ev_acc_end, ev_red_end2, round_ev0, host_ms2);
-      return MSMZ_OK;
-    }
-    // level 1 from affine bucket sums, then XYZZ levels down to one entry per window
-    uint32_t S1 = first_group_size(pl);
-    if (f2) {   // the weight-L bucket is folded into element L/2, which must be the FIRST element of its group
+      if ((st = reduce_2d<WeierPolicy<F>>(pl, d_points))) return st;
+    } else {
+      // level 1 from affine bucket sums, then XYZZ levels down to one entry per window.  The weight-L bucket is folded
+      // into element L/2, which must be the FIRST element of its group
+      uint32_t S1 = first_group_size(pl);
       if (S1 > 8) S1 = 8;
       while (S1 > 1 && S1 * 2 > pl.L) S1 >>= 1;
-    }
-    const uint32_t groups = (pl.L + S1 - 1) / S1;   // elements are weights 0..L-1 (weight L folded into L/2)
-    if ((st = red_[0].ensure((size_t)pl.Keff * groups * XW * 4))) return st;
-    if ((st = red_[1].ensure((size_t)pl.Keff * groups * XW * 4))) return st;
-    if (f2) {
+      const uint32_t groups = (pl.L + S1 - 1) / S1;   // elements are weights 0..L-1 (weight L folded into L/2)
+      if ((st = red_[0].ensure((size_t)pl.Keff * groups * XW * 4))) return st;
+      if ((st = red_[1].ensure((size_t)pl.Keff * groups * XW * 4))) return st;
       if ((st = reduce_first_affine(pl, d_points, S1, groups, n_pairs, d_meta))) return st;
-    } else {
-      uint32_t total = pl.Keff * groups;
-      hipLaunchKernelGGL((k_reduce_first<F>), dim3((total + 127) / 128), dim3(128), 0, stream_,
-                         red_[0].as<uint32_t>(), red_[1].as<uint32_t>(), slots_.as<uint32_t>(), d_points,
-                         bfin_.as<uint4>(), pl.L, S1, groups, total);
+      int cur = 0;
+      if ((st = reduce_levels<WeierPolicy<F>>(pl, cur, groups))) return st;
     }
-    int cur = 0;
-    if ((st = reduce_levels<P>(pl, cur, groups))) return st;
-    const int ev_red_end = pl.ei;
-    mark(pl);
-    if ((st = fetch_window_sums<P>(pl, cur))) return st;
-    auto t_host0 = std::chrono::steady_clock::now();
-    if (h_meta_->error & 1u) return MSMZ_ERR_DEGENERATE;
-    finalize_weierstrass(pl, out, out_inf);
-    float host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
-    fill_log(log, pl, R, n_pairs, ev_plan0, ev_plan1, ev_acc_end, ev_red_end, round_ev0, host_ms);
-    return MSMZ_OK;
+    return finish_msm(pl, want_2d, out, out_inf, log, R, n_pairs, ev_plan0, ev_plan1, ev_acc_end, round_ev0);
   }
 
   // ------------------------------------------------------------------------------------------ msmBasic: projective / extended buckets
   // (msm-basic.ts:45-176; Weierstrass "projective fallback" parallel.ts:69-87 and the twisted-Edwards MSM)
   template <class P>
   int msm_basic(const Handle& pts, const uint32_t* d_points, const uint32_t* d_scalars, uint64_t n64, const msmz_opts& opt,
-                Plan& pl) {
+                uint8_t* out, int* out_inf, msmz_log* log) {
+    // neither msmProjective (parallel.ts:69-87) nor the twisted-Edwards path (msm-basic.ts:4) uses the endomorphism
+    if (opt.glv) return MSMZ_ERR_UNSUPPORTED;
+    Plan pl;
     int st = make_plan(pl, n64, false, opt, (uint32_t)pts.n, false);
     if (st) return st;
     if ((st = sort_phase(pl, d_scalars))) return st;
@@ -1785,126 +1695,21 @@ class Engine : public IEngine {
     }
     const int ev_acc_end = pl.ei;
     mark(pl);
-    basic_2d_ = reduce2d_ && pl.L >= 2;
-    if (basic_2d_) {
-      // every bucket is visited twice: buckets of several chunk accumulators (large inputs: Pallas 2^22 has 4,
-      // ed-on-bls12-377 2^24 has 8) are first summed into one accumulator each, in bucket order
-      const bool summed = (uint64_t)n_chunks * 2 > (uint64_t)nb * 3 && !no_bucket_sums_;
-      if (summed) {
-        if ((st = bsum_.ensure((size_t)nb * AW * 4))) return st;
-        hipLaunchKernelGGL((k_bucket_sums<P>), dim3((nb + 127) / 128), dim3(128), 0, stream_, bsum_.as<uint32_t>(),
-                           slots_.as<uint32_t>(), rscan_.as<uint32_t>(), nb);
-      }
-      if ((st = reduce_2d<P>(pl, d_points, true, summed))) return st;
-      const int ev_red_end2 = pl.ei;
-      mark(pl);
-      if ((st = fetch_window_sums<P>(pl, 0, 2u * (uint32_t)pl.Keff))) return st;
-      basic_ev_[0] = ev_plan0;
-      basic_ev_[1] = ev_plan1;
-      basic_ev_[2] = ev_acc_end;
-      basic_ev_[3] = ev_red_end2;
-      return MSMZ_OK;
+    // every bucket is visited twice: buckets of several chunk accumulators (large inputs: Pallas 2^22 has 4,
+    // ed-on-bls12-377 2^24 has 8) are first summed into one accumulator each, in bucket order
+    const bool summed = (uint64_t)n_chunks * 2 > (uint64_t)nb * 3 && !no_bucket_sums_;
+    if (summed) {
+      if ((st = bsum_.ensure((size_t)nb * AW * 4))) return st;
+      hipLaunchKernelGGL((k_bucket_sums<P>), dim3((nb + 127) / 128), dim3(128), 0, stream_, bsum_.as<uint32_t>(),
+                         slots_.as<uint32_t>(), rscan_.as<uint32_t>(), nb);
     }
-    const uint32_t S1 = first_group_size(pl);
-    const uint32_t groups = (pl.L + S1 - 1) / S1;   // elements are weights 0..L-1 (weight L folded into L/2)
-    if ((st = red_[0].ensure((size_t)pl.Keff * groups * AW * 4))) return st;
-    if ((st = red_[1].ensure((size_t)pl.Keff * groups * AW * 4))) return st;
-    {
-      uint32_t total = pl.Keff * groups;
-      hipLaunchKernelGGL((k_reduce_next<P>), dim3((total + 127) / 128), dim3(128), 0, stream_, red_[0].as<uint32_t>(),
-                         red_[1].as<uint32_t>(), slots_.as<uint32_t>(), (const uint32_t*)nullptr,
-                         rscan_.as<uint32_t>(), pl.L, S1, groups, total, pl.L);
-    }
-    int cur = 0;
-    if ((st = reduce_levels<P>(pl, cur, groups))) return st;
-    const int ev_red_end = pl.ei;
-    mark(pl);
-    if ((st = fetch_window_sums<P>(pl, cur))) return st;
-    basic_ev_[0] = ev_plan0;
-    basic_ev_[1] = ev_plan1;
-    basic_ev_[2] = ev_acc_end;
-    basic_ev_[3] = ev_red_end;
-    return MSMZ_OK;
-  }
-
-  int msm_weierstrass_projective(const Handle& pts, const uint32_t* d_points, const uint32_t* d_scalars, uint64_t n64,
-                                 const msmz_opts& opt, uint8_t* out, int* out_inf, msmz_log* log) {
-    if (opt.glv) return MSMZ_ERR_UNSUPPORTED;   // msmProjective never uses the endomorphism (parallel.ts:69-87)
-    Plan pl;
-    int st = msm_basic<WeierPolicy<F>>(pts, d_points, d_scalars, n64, opt, pl);
-    if (st) return st;
-    auto t_host0 = std::chrono::steady_clock::now();
-    if (basic_2d_) finalize_weierstrass_2d(pl, out, out_inf); else finalize_weierstrass(pl, out, out_inf);
-    float host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
-    memset(h_round_pairs_, 0, sizeof(h_round_pairs_));
-    fill_log(log, pl, 0, pl.n_entries, basic_ev_[0], basic_ev_[1], basic_ev_[2], basic_ev_[3], 0, host_ms);
-    return MSMZ_OK;
-  }
-
-  // twisted Edwards MSM (parallel.ts:179-289 -> msm-basic.ts): extended buckets, no GLV
-  int msm_twisted_edwards(const Handle& pts, const uint32_t* d_points, const uint32_t* d_scalars, uint64_t n64,
-                          const msmz_opts& opt, uint8_t* out, int* out_inf, msmz_log* log) {
-    if (opt.glv) return MSMZ_ERR_UNSUPPORTED;   // the reference's TE path has no endomorphism (msm-basic.ts:4)
-    Plan pl;
-    int st = msm_basic<TePolicy<F>>(pts, d_points, d_scalars, n64, opt, pl);
-    if (st) return st;
-    auto t_host0 = std::chrono::steady_clock::now();
-    TeExt<F> acc;
-    te_set_zero(acc);
-    auto dbl_n = [&](int n) {
-      for (int j = 0; j < n; j++) {
-        TeExt<F> t;
-        te_add(t, acc, acc);
-        acc = t;
-      }
-    };
-    if (basic_2d_) {
-      // acc = (acc * 2^(c-b) + rows) * 2^b + columns, per window (see finalize_weierstrass_2d)
-      const Split2d sp = split_2d(pl);
-      auto add_results = [&](int k, int which) {
-        const int lo = k, hi = (k == pl.K - 1) ? pl.Keff - 1 : k;
-        for (int kw = lo; kw <= hi; kw++) {
-          TeExt<F> w, t;
-          host_load_te(w, h_final_ + (size_t)(kMaxWindows + 2 * kw + which) * XW);
-          te_add(t, acc, w);
-          acc = t;
-        }
-      };
-      for (int k = pl.K - 1; k >= 0; k--) {
-        if (k < pl.K - 1) dbl_n(pl.c - sp.b);
-        add_results(k, 0);
-        dbl_n(sp.b);
-        add_results(k, 1);
-      }
-    } else {
-      for (int k = pl.Keff - 1; k >= 0; k--) {
-        if (k < pl.K - 1) dbl_n(pl.c);
-        TeExt<F> w, t;
-        host_load_te(w, h_final_ + (size_t)(kMaxWindows + k) * XW);
-        te_add(t, acc, w);
-        acc = t;
-      }
-    }
-    uint32_t res[RW];
-    te_to_affine_canon<F>(res, acc);
-    memcpy(out, res, RW * 4);
-    *out_inf = 0;
-    float host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
-    memset(h_round_pairs_, 0, sizeof(h_round_pairs_));
-    fill_log(log, pl, 0, pl.n_entries, basic_ev_[0], basic_ev_[1], basic_ev_[2], basic_ev_[3], 0, host_ms);
-    return MSMZ_OK;
-  }
-
-  static void host_load_te(TeExt<F>& p, const uint32_t* w) {
-    fe_unpack<F>(p.X, w);
-    fe_unpack<F>(p.Y, w + NW);
-    fe_unpack<F>(p.Z, w + 2 * NW);
-    fe_unpack<F>(p.T, w + 3 * NW);
+    if ((st = reduce_2d<P>(pl, d_points, true, summed))) return st;
+    return finish_msm(pl, true, out, out_inf, log, 0, pl.n_entries, ev_plan0, ev_plan1, ev_acc_end, 0);
   }
 
   // Batched-affine first level of the bucket reduction (reduce_affine.h): S - 1 chain steps and
   // a short pair tree, every launch over Keff * groups (x pairs per group) additions; results behind the tree rounds'
-  // records.  Leaves the scaled (row, tri) XYZZ records in red_[0] / red_[1] like k_reduce_first.
+  // records.  Leaves the scaled (row, tri) XYZZ records in red_[0] / red_[1] for reduce_levels.
   int reduce_first_affine(const Plan& pl, const uint32_t* d_points, uint32_t S, uint32_t groups, uint64_t tree_pairs,
                           MsmMeta* d_meta) {
     F2Geom g;
@@ -1974,13 +1779,6 @@ class Engine : public IEngine {
                            d_points, dsc, out_base, pairs, B, d_meta);
       }
     }
-  }
-
-  static void host_load_xyzz(Xyzz<F>& p, const uint32_t* w) {
-    fe_unpack<F>(p.X, w);
-    fe_unpack<F>(p.Y, w + NW);
-    fe_unpack<F>(p.ZZ, w + 2 * NW);
-    fe_unpack<F>(p.ZZZ, w + 3 * NW);
   }
 
   int ensure_gen_table() {
@@ -2067,8 +1865,6 @@ class Engine : public IEngine {
 #endif
   uint32_t coarse_wgs_ = (uint32_t)env_int("MSMZ_COARSE_WGS", 2048);
   uint32_t batch_min_wgs_ = (uint32_t)env_int("MSMZ_BATCH_WGS", 512);
-  // rounds left to the reduction's loader: at most 2 (a bucket's final-location record holds 4 partial sums)
-  int tail_skip_ = env_int("MSMZ_TAIL_SKIP", 2) > 2 ? 2 : env_int("MSMZ_TAIL_SKIP", 2);
   int chunk_shift_override_ = env_int("MSMZ_CHUNK_SHIFT", 0);
   int fb_cap_ = env_int("MSMZ_FB", 0);
   uint32_t s1_override_ = (uint32_t)env_int("MSMZ_S1", 0);
@@ -2083,7 +1879,7 @@ class Engine : public IEngine {
   bool no_plan_top_ = env_int("MSMZ_NO_PLAN_TOP", 0) != 0;            // top-window bucket sets in full-size plan chunks
   bool no_fbt_ = env_int("MSMZ_NO_FBT", 0) != 0;                     // top window's bins as wide as the others
   bool no_sort_special_ = env_int("MSMZ_NO_SORT_SPECIAL", 0) != 0;   // generic sort kernels for every window size
-  bool reduce2d_ = env_int("MSMZ_REDUCE2D", 1) != 0;          // two-dimensional bucket reduction (reduce2d_kernels.h); 0 = the grouped running sums
+  // rounds left to the 2-D reduction's loader: at most 2 (a bucket's final-location record holds 4 partial sums)
   int tail_skip_2d_ = env_int("MSMZ_TAIL_SKIP_2D", 1) > 2 ? 2 : env_int("MSMZ_TAIL_SKIP_2D", 1);
   uint32_t r2_nc_ = (uint32_t)env_int("MSMZ_R2_NC", 0);         // chunks per line (0 = automatic)
   uint32_t pairsum_x4_max_ = (uint32_t)env_int("MSMZ_PAIRSUM_X4", 16384);   // pair-sum levels with at most this many additions use DPP quads
@@ -2092,9 +1888,6 @@ class Engine : public IEngine {
   int glv_bits_assumed_ = 0;   // test hook (msmz_test_set_glv_bits): assumed bit length of a GLV half; 0 = GLV_BITS - 1
   DevBuf bsum_, f2desc_, tilecnt_, tileoff_, final_, desc_, bfin_, packed_, bins_, digits_, counts_, off_, cursor_, refs_, rscan_, partials_, slots_, red_[4], meta_, stage_, gen_table_;
   uint32_t h_round_pairs_[32] = {};
-  uint32_t h_round_base_[32] = {};
-  int basic_ev_[4] = {};
-  bool basic_2d_ = false;   // the last msmBasic call reduced its buckets two-dimensionally (two results per bucket set)
   MsmMeta* h_meta_ = nullptr;
   uint32_t* h_final_ = nullptr;
   uint32_t* h_bfinal_ = nullptr;   // pinned: the window results of every problem of a batched MSM

@@ -1,6 +1,7 @@
 // Host-only field and XYZZ arithmetic on 64-bit limbs, for the sequential tail of an MSM that runs on the
 // CPU: the Horner combination of the K window sums (msm-batched-affine.ts:300-322) -- c doublings per window,
 // ~250 dependent point doublings, where a CPU core is an order of magnitude faster than a lone GPU wave.
+// The window terms and the Horner itself (end of file) serve every MSM path.
 // The device keeps Montgomery residues a * 2^(N*W) mod p (N*W = 392 or 261, fp.h); this file multiplies them
 // with 64-bit words and the SAME Montgomery radix: NL = NW/2 word steps plus one partial step of
 // N*W - 64*NL bits, so values move between the two representations without conversion.
@@ -8,6 +9,7 @@
 #pragma once
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
 #include "fp.h"
 
@@ -248,5 +250,58 @@ struct Host64 {
     fe_unpack<F>(o.ZZZ, w);
   }
 };
+
+// ---- the Horner combination of an MSM's window results (engine.h): result `index` enters at weight 2^weight
+struct WindowTerm {
+  int weight, index;
+};
+
+// The window results of a plan in the order the Horner adds them, by falling weight.  c bits per window, K windows, the
+// top one spread over the sub-windows K-1 .. Keff-1, which share its weight; F > 1: a precomputed point set, Keff
+// bucket sets of F windows each, set s one window of c F bits at c F s.  split_b < 0: one result per bucket set
+// (reduceAffine's one-dimensional reduction); else the two of the 2-D reduction, rows (2 kw) at the window's weight
+// + split_b and columns (2 kw + 1) at its weight -- but a folded top window's rows are copies and carry no weight.
+static inline std::vector<WindowTerm> window_terms(int c, int K, int Keff, int F, int split_b, bool fold) {
+  if (F > 1) {
+    c *= F;
+    K = Keff;
+  }
+  std::vector<WindowTerm> t;
+  for (int k = K - 1; k >= 0; k--) {
+    const int top = k == K - 1 ? Keff - 1 : k;
+    if (split_b < 0) {
+      for (int kw = top; kw >= k; kw--) t.push_back({c * k, kw});
+      continue;
+    }
+    if (!fold || k < K - 1)
+      for (int kw = k; kw <= top; kw++) t.push_back({c * k + split_b, 2 * kw});
+    for (int kw = k; kw <= top; kw++) t.push_back({c * k, 2 * kw + 1});
+  }
+  return t;
+}
+
+// sum over the terms of 2^weight res[index] (records of rec_words words) in the host group G -- Host64<F>, or
+// twisted Edwards (engine.h HostTe): from infinity, double down to each term's weight and add it, then down to weight
+// 0.  One doubling per bit of the top weight, one addition per term.
+template <class G>
+typename G::Pt host_horner(const G& g, const std::vector<WindowTerm>& terms, const uint32_t* res, int rec_words) {
+  typename G::Pt acc, w, t;
+  g.set_inf(acc);
+  int prev = terms.empty() ? 0 : terms[0].weight;
+  for (const WindowTerm& term : terms) {
+    for (; prev > term.weight; prev--) {
+      g.dbl(t, acc);
+      acc = t;
+    }
+    g.load_pt(w, res + (size_t)term.index * rec_words);
+    g.add_pt(t, acc, w);
+    acc = t;
+  }
+  for (; prev > 0; prev--) {
+    g.dbl(t, acc);
+    acc = t;
+  }
+  return acc;
+}
 
 }  // namespace msmz

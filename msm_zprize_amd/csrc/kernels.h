@@ -17,10 +17,10 @@
 //                        batch inversion (product tree in LDS, one wave-wide field inversion per workgroup,
 //                        fe_inverse_wave); results in chunk-interleaved slot arrays
 //                        (msm-batched-affine.ts:232-270; curve-affine.ts:376-522; inverse.ts:220-271)
-//   k_reduce_first,      bucket reduction  sum_l l*B_l  by grouped running sums in XYZZ coordinates: first level
-//   k_reduce_quad(16),   from the (partial) bucket sums, upper levels with a quad of lanes per group / per addition,
-//   k_reduce_tail,       the last levels in one launch; k_reduce_next = first level of the msmBasic path
-//   k_reduce_next        (msm-batched-affine.ts:544-571 reduceBucketsColumnProjective)
+//   k_reduce_quad(16),   upper levels of the bucket reduction  sum_l l*B_l  (above reduce2d_kernels.h's line sums, or
+//   k_reduce_tail        reduce_affine.h's first level) by grouped running sums in XYZZ / extended coordinates, a quad
+//                        of lanes per group / per addition; the last levels in one launch
+//                        (msm-batched-affine.ts:544-571 reduceBucketsColumnProjective)
 //   k_reduce_affine_*    (reduce_affine.h) optional batched-affine first level (reduceBucketsAffine,
 //                        msm-batched-affine-single-thread.ts:522-667)
 //   k_bucket_accumulate  msmBasic path: buckets in XYZZ / extended coordinates (msm-basic.ts:106-128)
@@ -1065,106 +1065,15 @@ __device__ __forceinline__ void add_bucket(Xyzz<F>& run, uint32_t g, const uint3
   }
 }
 
-// Bucket reduction  W_k = sum_{l=1..L} l * B_l  (msm-batched-affine.ts:544-571) by grouped running sums.
-// Elements are indexed by their weight j = l in [0, L) (element 0 is empty; the one bucket of weight L is
-// folded into element L/2 twice), cut into groups of S = 2^s:
+// Upper levels of the bucket reduction  W_k = sum_{l=1..L} l * B_l  (msm-batched-affine.ts:544-571) by grouped
+// running sums.  A level's n_in entries per window are (row, C) pairs -- above the 2-D reduction the line sums with
+// C = infinity, above reduce_affine.h's first level its scaled rows and tri's -- cut into groups of S:
 //   row_a = sum_b E[aS + b],   tri_a = sum_b b * E[aS + b]          (running-sum trick, :556-559)
 //   sum_j j * E_j = sum_a tri_a + sum_a a * (S * row_a)
 // so the next level runs the same computation on the *scaled* rows S*row_a (s doublings per group) and
 // simply adds up the tri's:  C'_A = sum_b C[AS + b] + tri'_A.  After the last level (one entry per
 // window) C is W_k.  No per-level power-of-two scaling of the partial sums is needed.
-template <class F>
-__global__ void __launch_bounds__(128, MSMZ_REDUCE_OCC) k_reduce_first(uint32_t* rows, uint32_t* tris, const uint32_t* slots,
-                                                      const uint32_t* points, const uint4* bfin, uint32_t L, uint32_t S,
-                                                      uint32_t groups, uint32_t total) {
-  uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
-  uint32_t k = t / groups, a = t - k * groups;
-  Xyzz<F> run, tri, tmp;
-  xyzz_set_inf(run);
-  xyzz_set_inf(tri);
-  for (uint32_t b = S; b-- > 0;) {
-    const uint32_t j = a * S + b;           // weight; bucket l = j, j in [0, L)
-    if (j >= 1 && j < L) add_bucket<F>(run, k * L + (j - 1), slots, points, bfin);
-    if (j == L / 2 && L >= 2) {
-      // the single bucket of weight L is folded in as 2 * (L/2): keeps the element count a power of two
-      for (int twice = 0; twice < 2; twice++)
-        add_bucket<F>(run, k * L + (L - 1), slots, points, bfin);
-    }
-    if (b >= 1) {
-      xyzz_add(tmp, tri, run);
-      tri = tmp;
-    }
-  }
-  for (uint32_t s = S; s > 1; s >>= 1) {
-    xyzz_dbl(tmp, run);
-    run = tmp;
-  }
-  store_xyzz<F>(rows + (size_t)t * 4 * F::NW, run);
-  store_xyzz<F>(tris + (size_t)t * 4 * F::NW, tri);
-}
-
-// Level >= 2 on accumulator inputs (n_in entries per window), same recurrence.
-// With c_in == nullptr this is the FIRST level of the msmBasic path: element j of window k (j in [0, L],
-// n_in = L + 1) is then the sum of the partial accumulators rows_in[cscan[g] .. cscan[g+1]) of bucket
-// g = k*L + j - 1  (cscan != nullptr), element 0 is empty and bucket L is folded into element L/2 twice (n_in = L).
-template <class P>
-__global__ void __launch_bounds__(128) k_reduce_next(uint32_t* rows_out, uint32_t* c_out, const uint32_t* rows_in,
-                                                     const uint32_t* c_in, const uint32_t* cscan, uint32_t n_in,
-                                                     uint32_t S, uint32_t groups, uint32_t total, uint32_t L) {
-  constexpr int XW = P::ACC_WORDS;
-  uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
-  uint32_t k = t / groups, A = t - k * groups;
-  size_t base = (size_t)k * n_in + (size_t)A * S;
-  typename P::Acc run, tri, cs, tmp, p;
-  P::zero(run);
-  P::zero(tri);
-  P::zero(cs);
-  for (uint32_t b = S; b-- > 0;) {
-    const uint32_t e = A * S + b;
-    if (e >= n_in) continue;
-    if (cscan != nullptr) {
-      if (e >= 1) {
-        const size_t g = (size_t)k * L + (e - 1);
-        for (uint32_t q = cscan[g]; q < cscan[g + 1]; q++) {
-          P::load(p, rows_in + (size_t)q * XW);
-          P::add(tmp, run, p);
-          run = tmp;
-        }
-      }
-      if (e == L / 2 && L >= 2) {   // weight-L bucket folded in as 2 * (L/2)
-        const size_t g = (size_t)k * L + (L - 1);
-        for (int twice = 0; twice < 2; twice++)
-          for (uint32_t q = cscan[g]; q < cscan[g + 1]; q++) {
-            P::load(p, rows_in + (size_t)q * XW);
-            P::add(tmp, run, p);
-            run = tmp;
-          }
-      }
-    } else {
-      P::load(p, c_in + (base + b) * XW);
-      P::add(tmp, cs, p);
-      cs = tmp;
-      P::load(p, rows_in + (base + b) * XW);
-      P::add(tmp, run, p);
-      run = tmp;
-    }
-    if (b >= 1) {
-      P::add(tmp, tri, run);
-      tri = tmp;
-    }
-  }
-  for (uint32_t s = S; s > 1; s >>= 1) {
-    P::dbl(tmp, run);
-    run = tmp;
-  }
-  P::add(tmp, cs, tri);
-  P::store(rows_out + (size_t)t * XW, run);
-  P::store(c_out + (size_t)t * XW, tmp);
-}
-
-// Same recurrence with S = 4, one group per QUAD of lanes: the 9 accumulator additions + 2 doublings of a
+// k_reduce_quad: S = 4, one group per QUAD of lanes: the 9 accumulator additions + 2 doublings of a
 // group form a dependency graph of depth 4, so four lanes finish a group in 4 sequential point
 // operations instead of 14 (the upper reduction levels are latency-bound: few groups, long chains).
 //   step 1: L0 r0+r1        L1 b = r1+r3     L2 a = r2+r3     L3 c2+c3

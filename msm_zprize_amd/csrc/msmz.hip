@@ -22,7 +22,7 @@ struct WeierCfg {
   static constexpr bool HAS_ENDO = true;
   static int run_msm(Engine<WeierCfg>& e, const Handle& p, const uint32_t* pts, const uint32_t* s, uint64_t n,
                      const msmz_opts& o, uint8_t* out, int* oi, msmz_log* log, int extra_bits) {
-    if (o.buckets == MSMZ_BUCKETS_PROJECTIVE) return e.msm_weierstrass_projective(p, pts, s, n, o, out, oi, log);
+    if (o.buckets == MSMZ_BUCKETS_PROJECTIVE) return e.template msm_basic<WeierPolicy<F>>(p, pts, s, n, o, out, oi, log);
     return e.msm_weierstrass_affine(p, pts, s, n, o, out, oi, log, extra_bits);
   }
 };
@@ -35,7 +35,7 @@ struct TeCfg {
   static constexpr bool HAS_ENDO = false;
   static int run_msm(Engine<TeCfg>& e, const Handle& p, const uint32_t* pts, const uint32_t* s, uint64_t n,
                      const msmz_opts& o, uint8_t* out, int* oi, msmz_log* log, int) {
-    return e.msm_twisted_edwards(p, pts, s, n, o, out, oi, log);
+    return e.template msm_basic<TePolicy<F>>(p, pts, s, n, o, out, oi, log);
   }
 };
 

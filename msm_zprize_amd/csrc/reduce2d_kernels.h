@@ -1,15 +1,15 @@
 // Two-dimensional bucket reduction.  Included by kernels.h.
 //
 // The reference's running-sum reduction (msm-batched-affine.ts:544-571) walks a window's L buckets as ONE chain; the
-// grouped form of round 1-2 (k_reduce_first + quad levels) still leaves a dependency chain of 2 point additions per
-// bit of the bucket index: 13 bits above the first level = 0.55 ms of latency at 2^20, and a first level that holds
-// two XYZZ accumulators (256 VGPRs).  Here the bucket weight j in [0, L) is split into a high and a low half,
+// grouped form of round 1-2 (a first level over all L buckets + quad levels) still left a dependency chain of 2 point
+// additions per bit of the bucket index: 13 bits above the first level = 0.55 ms of latency at 2^20, and a first level
+// that holds two XYZZ accumulators (256 VGPRs).  Here the bucket weight j in [0, L) is split into a high and a low half,
 //     j = h * D + d,   h in [0, H), d in [0, D),   H = 2^ceil((c-1)/2), D = L / H,
 //     sum_j j E_j = D * sum_h h R_h + sum_d d C_d,     R_h = sum_d E[h D + d],   C_d = sum_h E[h D + d]:
 // the 2 L plain (unweighted) sums R, C are embarrassingly parallel -- any grouping, one accumulator per thread, mixed
 // additions only -- and what is left are two weighted sums over H (<= 512) entries per bucket set instead of one over
 // L: the chain is half as deep.  The host's Horner pass adds the row result at bit position c k + log2 D and the column
-// result at c k (engine.h finalize_weierstrass_2d) -- no extra doublings.  The bucket of weight L = H D is added twice
+// result at c k (host64.h window_terms) -- no extra doublings.  The bucket of weight L = H D is added twice
 // into row H/2, as before.
 //
 //   k_reduce2d_partial   thread = (problem, line, chunk): folds D / NC buckets of a row (or H / NC buckets of a column)

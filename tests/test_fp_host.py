@@ -139,3 +139,14 @@ def test_host64_matches_limb_arithmetic():
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout
     assert r.stdout.count("mismatches 0") == 3, r.stdout
+
+
+def test_window_terms_replay_the_per_path_horner_loops():
+    """csrc/host64.h window_terms + host_horner: the same doublings and additions, in the same order, as the Horner loops
+    each MSM path had (1-D, 2-D with spread / folded top windows, precomputed sets), for every plan shape"""
+    src = os.path.join(ROOT, "tests", "native", "window_terms_test.cpp")
+    exe = os.path.join(ROOT, "tests", "native", "window_terms_test")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-o", exe, src])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout
+    assert "mismatches 0" in r.stdout, r.stdout

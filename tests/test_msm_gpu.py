@@ -320,7 +320,7 @@ def test_multi_engine_context_on_one_gpu(label):
 def test_debug_environment_cannot_change_a_result(monkeypatch):
     """MSMZ_DBG used to reach the kernels; no environment variable may alter a release build's result"""
     import msm_zprize_amd as m
-    for k, v in {"MSMZ_DBG": "7", "MSMZ_FUSED": "1", "MSMZ_TAIL_SKIP": "0", "MSMZ_ATOMIC_SORT": "1"}.items():
+    for k, v in {"MSMZ_DBG": "7", "MSMZ_FUSED": "1", "MSMZ_TAIL_SKIP_2D": "0", "MSMZ_ATOMIC_SORT": "1"}.items():
         monkeypatch.setenv(k, v)
     m.startThreads()
     curve = m.Weierstrass.create(m.curves.bls12377Params)
