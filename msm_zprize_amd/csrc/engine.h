@@ -20,6 +20,7 @@
 #include "test_kernels.h"
 #include "host64.h"
 #include "multi.h"
+#include "plan.h"
 
 namespace msmz {
 
@@ -70,29 +71,6 @@ struct Handle {
   int c = 0, glv = 0;
   uint64_t copy_stride = 0;
 };
-
-static inline int copy_bits(uint32_t F) {   // bits of a copy index below F
-  int r = 0;
-  while ((1u << r) < F) r++;
-  return r;
-}
-
-static inline int ceil_log2_u64(uint64_t x) {
-  int r = 0;
-  while (((uint64_t)1 << r) < x) r++;
-  return r;
-}
-
-// default window size.  The reference's tables (msm-common.ts:8-57) were tuned for 16 CPU threads;
-// on the GPU the accumulate phase costs ~N*K additions and the reduction ~2*K*2^(c-1), and the latter
-// is latency-bound, so c stays well below log2(N).
-static inline int default_window(uint64_t n_points) {
-  int lg = ceil_log2_u64(n_points < 2 ? 2 : n_points);
-  int c = lg - 3;
-  if (c < 3) c = 3;
-  if (c > 17) c = 17;   // 2^16 buckets per window: the largest the two-level LDS sort handles in one coarse pass
-  return c;
-}
 
 constexpr int MSMZ_ERR_RETRY_BITS = 1000;   // internal: repeat the MSM with one more scalar bit (never leaves the engine)
 constexpr int MSMZ_ERR_BATCH_LOOP = 1001;   // internal: this batched MSM runs its problems one by one (never leaves the engine)
@@ -433,50 +411,10 @@ class Engine : public IEngine {
     return MSMZ_OK;
   }
 
-  // What a precomputed set over n points is built with: c, GLV choice and copies (factor; 0 = enough copies for every
-  // window, the GLV retry's included).  Checks that its bucket sets fit one sort pass and its records the 30-bit field.
-  // bit length the windows are sized for (make_plan's pl.b): the whole scalar, or a GLV half -- the assumed bound, or
-  // with extra_bits the proven one of the retry
-  int scalar_bits(bool glv, int extra_bits) const {
-    if (!glv) return Fr::BITS;
-    if (extra_bits) return Fr::GLV_PROVEN_BITS > Fr::GLV_BITS - 1 ? Fr::GLV_PROVEN_BITS : Fr::GLV_BITS - 1;
-    return glv_bits_assumed_ > 0 ? glv_bits_assumed_ : Fr::GLV_BITS - 1;
-  }
-
   int precompute_params(uint64_t n, const msmz_opts* o, uint32_t factor, int* c_out, int* glv_out,
                         uint32_t* f_out, int* k_out) const override {
     if (TE) return MSMZ_ERR_UNSUPPORTED;   // twisted Edwards runs msmBasic: no batched-affine buckets to share
-    if (n == 0 || factor == 1) return MSMZ_ERR_ARG;
-    msmz_opts opt;
-    memset(&opt, 0, sizeof(opt));
-    if (o) opt = *o; else opt.glv = -1;
-    if (opt.buckets == MSMZ_BUCKETS_PROJECTIVE || opt.reserved[0] == 1) return MSMZ_ERR_UNSUPPORTED;
-    if (opt.c < 0 || opt.c > 24) return MSMZ_ERR_ARG;
-    int glv = opt.glv;
-    if (glv < 0) glv = default_glv(n) ? 1 : 0;   // msm()'s choice for n points
-    if (glv && !Fr::HAS_GLV) return MSMZ_ERR_UNSUPPORTED;
-    glv = glv ? 1 : 0;
-    const uint64_t M64 = glv ? 2 * n : n;
-    if (M64 > (1ull << 24)) return MSMZ_ERR_ARG;
-    const uint32_t M = (uint32_t)M64;
-    const int b0 = scalar_bits(glv != 0, 0), b1 = scalar_bits(glv != 0, 1);
-    // window size: the user's, or the model's for F copies (0: all windows in one set)
-    int c = opt.c;
-    auto windows = [&](int cc, int b) { return (b + 1 + cc - 1) / cc; };
-    if (c == 0) c = choose_window_pre(glv != 0, M, b0, 1, factor == 0 ? 1024u : factor);
-    if (c < 2) c = 2;
-    const int K0 = windows(c, b0), K1 = windows(c, b1);
-    const int Kmax = K0 > K1 ? K0 : K1;
-    const uint32_t copies = factor == 0 || factor > (uint32_t)Kmax ? (uint32_t)Kmax : factor;
-    if (copies < 2) return MSMZ_ERR_ARG;
-    if (!pre_fits(c, glv != 0, M, b0, copies) || !pre_fits(c, glv != 0, M, b1, copies)) return MSMZ_ERR_ARG;
-    const uint64_t records = (uint64_t)copies * n * (glv ? 2 : 1);
-    if (records >= (1ull << 30)) return MSMZ_ERR_ARG;   // location words: 30-bit record index
-    *c_out = c;
-    *glv_out = glv;
-    *f_out = copies;
-    if (k_out) *k_out = K0;
-    return MSMZ_OK;
+    return planner_.precompute_params(n, o, factor, c_out, glv_out, f_out, k_out);
   }
 
   // new handle: `F` copies of the first n points of `ph`, copy j = 2^(c j) P_i (+ the endomorphism images with glv)
@@ -525,7 +463,7 @@ class Engine : public IEngine {
     auto it = handles_.find(hd);
     if (it == handles_.end() || it->second.factor == 0) return MSMZ_ERR_ARG;
     const Handle& h = it->second;
-    const int b = scalar_bits(h.glv != 0, 0);
+    const int b = planner_.scalar_bits(h.glv != 0, 0);
     if (c) *c = h.c;
     if (glv) *glv = h.glv;
     if (factor) *factor = h.factor;
@@ -535,19 +473,10 @@ class Engine : public IEngine {
   }
 
   // ------------------------------------------------------------------------------------------ msm
-  // Largest number of (half-)scalars one pass sorts: index + negate + fine bucket bits share a 32-bit word.
-  static constexpr uint64_t kMaxEntriesPerPass = 1ull << 24;
-
   int msm(uint64_t ph, const uint8_t* host_scalars, uint64_t sh, uint64_t n, const msmz_opts* o, uint8_t* out,
           int* out_inf, msmz_log* log, const GenMap* split = nullptr) override {
     return msm_batch(ph, host_scalars, sh, n, 1, o, out, out_inf, log, split);
   }
-
-  // glv < 0: the engine's choice for n points.  The split halves the windows but doubles the point set (index bits,
-  // gathers, tree depth); since the two-dimensional bucket reduction made the reduction cheap per window it is only
-  // ahead on the smallest inputs (profiles/r03_sweep.json: 2^14 0.85 vs 0.88 ms, 2^16 1.11 vs 1.07, 2^20 3.87 vs 3.64,
-  // 2^23 23.5 vs 20.5).
-  static bool default_glv(uint64_t n) { return !TE && Fr::HAS_GLV && n < (1ull << 15); }
 
   // run(extra_bits): a GLV half longer than the assumed 127 bits (k_hist flags it) redoes the MSM with windows for the
   // PROVEN bound (Fr::GLV_PROVEN_BITS, tools/gen_constants.py), which no half can exceed -- a second flag is an
@@ -594,11 +523,6 @@ class Engine : public IEngine {
   }
 
   // ------------------------------------------------------------------------------------------ batched msm
-  // Entries (problems x windows x entries per window) one batched pass sorts, plans and adds: slots, descriptors and
-  // references cost ~100 B per entry (BLS12-377), so a batch beyond 2^26 entries (~7 GB) runs as consecutive
-  // sub-batches.  (2^26 also keeps the 30-bit location words and the 31-bit bucket numbers far from their limits.)
-  static constexpr uint64_t kMaxBatchEntries = 1ull << 26;
-
   // `batch` MSMs over the first n points: problem k's scalars are entries [k n, (k + 1) n) of the resident set `sh`, or
   // vector k of the host buffer (at host_scalars + k host_stride 32; host_stride = n unless a multi-device context hands
   // this engine its share `split` of longer vectors).  Weierstrass batched-affine plans run as ONE batched pipeline per
@@ -614,7 +538,7 @@ class Engine : public IEngine {
     msmz_opts opt;
     int st0 = resolve_opts(pit->second, o, &opt);
     if (st0) return st0;
-    if (opt.glv < 0) opt.glv = pit->second.has_endo && default_glv(n) ? 1 : 0;   // (per problem: batch = 1 is msm())
+    if (opt.glv < 0) opt.glv = pit->second.has_endo && planner_.default_glv(n) ? 1 : 0;   // (per problem: batch = 1 is msm())
     if (host_stride == 0) host_stride = n;
     if (host_scalars && host_stride < n) return MSMZ_ERR_ARG;
     MSMZ_HIP(hipSetDevice(device_));
@@ -645,7 +569,7 @@ class Engine : public IEngine {
                          batch > 1;
     int st = MSMZ_OK;
     for (uint32_t done = 0; done < batch && st == MSMZ_OK;) {
-      uint32_t bs = batched ? batch_size(pts, n, opt, batch - done) : 1;
+      uint32_t bs = batched ? planner_.batch_size(n, opt, (uint32_t)pts.n, pts.factor, batch - done) : 1;
       const uint32_t* d_sc = d_scalars + (size_t)done * n * 8;
       msmz_log plog;
       msmz_log* lp = log ? &plog : nullptr;
@@ -670,23 +594,6 @@ class Engine : public IEngine {
           std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     }
     return st;
-  }
-
-  // problems of the next sub-batch: the window size depends on the batch size, so the plan is made again until the
-  // sub-batch fits kMaxBatchEntries; the remaining problems are then dealt into equal sub-batches
-  uint32_t batch_size(const Handle& pts, uint64_t n, const msmz_opts& opt, uint32_t remaining) {
-    uint32_t bs = remaining;
-    for (int it = 0; it < 4 && bs > 1; it++) {
-      Plan pl;
-      if (make_plan(pl, n, opt.glv != 0, opt, (uint32_t)pts.n, true, 0, true, bs, pts.factor > 1 ? pts.factor : 1) != MSMZ_OK) {
-        bs = (bs + 1) / 2;
-        continue;
-      }
-      const uint32_t fit = batch_split(remaining, (uint64_t)pl.K * pl.M, kMaxBatchEntries);
-      if (fit >= bs) break;
-      bs = fit;
-    }
-    return bs;
   }
 
   static void merge_log(msmz_log* total, const msmz_log& part, bool first) {
@@ -717,7 +624,7 @@ class Engine : public IEngine {
   int test_set_glv_bits(int bits) override {
     if (!Fr::HAS_GLV) return MSMZ_ERR_UNSUPPORTED;
     if (bits != 0 && (bits < 8 || bits > Fr::GLV_BITS - 1)) return MSMZ_ERR_ARG;
-    glv_bits_assumed_ = bits;
+    planner_.k.glv_bits_assumed = bits;
     return MSMZ_OK;
   }
   int test_retries() override { return retries_; }
@@ -809,16 +716,15 @@ class Engine : public IEngine {
     msmz_opts opt;
     memset(&opt, 0, sizeof(opt));
     opt.c = c;
+    Planner<Fr> pr = planner_;
+    pr.k.force_atomic_sort = pr.k.force_atomic_sort || force_fallback != 0;
     Plan pl;
-    int st = make_plan(pl, n, glv != 0, opt, (uint32_t)n, !TE);
+    int st = pr.make_plan(pl, n, glv != 0, opt, (uint32_t)n, !TE);
     if (st) return st;
     void* d_scalars = nullptr;
     MSMZ_HIP(hipMalloc(&d_scalars, 32 * n));
     MSMZ_HIP(hipMemcpyAsync(d_scalars, s, 32 * n, hipMemcpyHostToDevice, stream_));
-    const bool saved = force_atomic_sort_;
-    force_atomic_sort_ = saved || force_fallback != 0;
-    st = sort_phase(pl, (const uint32_t*)d_scalars);
-    force_atomic_sort_ = saved;
+    st = sort_phase(pl, pr.sort_layout(pl), (const uint32_t*)d_scalars);
     if (!st) st = fetch_meta(pl);
     if (!st && (h_meta_->error & 4u)) st = MSMZ_ERR_RANGE;
     if (!st) {
@@ -898,23 +804,6 @@ class Engine : public IEngine {
   }
 
   // ------------------------------------------------------------------------------------------ shared phases
-  struct Plan {
-    uint32_t n, M, L, nb, nblocks;
-    int c, K, b;
-    int Keff, spread;           // bucket windows incl. the top window's 2^spread sub-windows
-    int fold_shift = 0, fold_rows = 0;   // ... or the top window folded into its own bucket set (SortGeom)
-    uint32_t top_range = 1;              // values the top window's digit can take
-    bool glv, timing;
-    uint32_t max_bucket = 0, n_entries = 0;
-    uint32_t endo_delta = 0;    // GLV over a prefix of a set: half-1 entry i reads point record pts_n + i = (n + i) + endo_delta
-    uint32_t nprob = 1;         // batched MSM: problems (scalar vectors) sorted, planned and reduced together; nb, M, K,
-                                // Keff describe ONE problem, bucket set p * Keff + kw holds window kw of problem p
-    uint32_t F = 1;             // precomputed point set: windows per bucket set (Keff = ceil(K / F) sets); 1 = plain
-    uint32_t copy_stride = 0;   // ... and records per copy of the points
-    int ei = 0;                 // next event slot
-    int ev_coarse = -1, ev_sort_end = -1;
-  };
-
   void mark(Plan& pl) {
     if (pl.timing && pl.ei < kMaxEvents) (void)hipEventRecord(ev_[pl.ei], stream_);
     pl.ei++;
@@ -925,279 +814,35 @@ class Engine : public IEngine {
     return ms;
   }
 
-  // Window geometry for window size c: K windows, L buckets each, significant bits t_top of the top window's
-  // digit (from the largest scalar q - 1, or the typical GLV half), and the 2^spread sub-windows the top window
-  // is spread over when it is sparse.
-  struct Geometry {
-    int c, K, t_top, spread, Keff;
-    uint32_t L;
-    uint32_t top_range = 0;   // number of values the top window's digit can take (<= L + 1)
-    int fold_shift = 0, fold_rows = 0;   // thin top window folded into its own bucket set (sort_kernels.h SortGeom)
-  };
-  Geometry geometry(int c, bool glv, uint32_t M, int b, bool allow_fold = false, uint32_t F = 1) const {
-    Geometry g;
-    g.c = c;
-    g.K = (b + 1 + c - 1) / c;                              // msm-batched-affine.ts:96
-    g.L = 1u << (c - 1);
-    const int pos = (g.K - 1) * c;
-    g.t_top = b + 1 - pos;
-    if (!glv) {
-      uint64_t top = 0;
-      for (int j = 0; j < 64 && pos + j < 256; j++)
-        top |= (uint64_t)((Fr::Q[(pos + j) >> 5] >> ((pos + j) & 31)) & 1u) << j;
-      top += 1;   // carry from the window below
-      g.t_top = ceil_log2_u64(top + 1);
-      g.top_range = (uint32_t)(top + 1 > g.L ? g.L : top + 1);
-    } else if (Fr::GLV_TYP_BITS + 1 - pos < g.t_top) {
-      g.t_top = Fr::GLV_TYP_BITS + 1 - pos;
-      if (g.t_top < 1) g.t_top = 1;
-    }
-    g.spread = 0;
-    {
-      // a thin top window whose digit fits the COLUMN index of the two-dimensional reduction (l < D = 2^b2) is folded:
-      // 2^(c-1-b2) copies of the digit's range fill the set's buckets as evenly as any other window's.  The bound on
-      // the digit is the hard one (largest scalar; for GLV halves the bit length the windows were sized for).
-      const int b2 = (c - 1) - (c - 1 + 1) / 2;                       // low bits of Split2d
-      const int t_bound = glv ? b + 1 - pos : g.t_top;
-      // (only where the two-level sort applies: the fallback sort numbers buckets by digit alone)
-      const uint32_t ncb0 = g.L >> fine_bits(c, M);
-      const bool sort2 = !force_atomic_sort_ && M <= (1u << 24) && ncb0 <= (uint32_t)COARSE_MAX_BINS &&
-                         (uint64_t)g.K * ncb0 <= (uint64_t)SORT_MAX_BINS;
-      if (F == 1 && allow_fold && !no_fold_ && sort2 && g.K > 1 && g.t_top <= c - 2 && b2 >= 1 && t_bound <= b2) {
-        g.fold_shift = b2;
-        g.fold_rows = c - 1 - b2;
-      }
-    }
-    // (precomputed sets, F > 1: neither -- the top window shares its bucket set with F - 1 windows; choose_window keeps
-    // it from being thin)
-    if (F == 1 && g.fold_shift == 0 && !no_spread_ && g.K > 1 && g.t_top <= c - 2) {
-      g.spread = c - 1 - g.t_top;
-      if (g.spread > 3) g.spread = 3;
-      const int ib = ceil_log2_u64(M < 2 ? 2 : M);
-      (void)ib;
-      const int fbx = fine_bits(c, M);
-      while (g.spread > 0 && ((g.L >> fbx) << g.spread) > (uint32_t)COARSE_MAX_BINS) g.spread--;
-    }
-    if (g.top_range == 0) g.top_range = g.t_top >= c - 1 ? g.L : 1u << g.t_top;
-    g.Keff = g.K - 1 + (1 << g.spread);
-    return g;
-  }
-
-  // Fine bits of the two-level sort = log2(buckets per coarse bin): as many as (1) the packed word leaves beside the
-  // index and the sign, (2) k_fine's counters hold, and (3) keep an average bin inside k_fine's LDS staging (a bin of
-  // 2^fb buckets holds ~M 2^fb / L entries; beyond FINE_STAGE it falls back to scattered stores: 3x slower).
-  // Precomputed sets (W = windows per bucket set > 1): a set receives W M entries and the packed index carries the copy
-  // (copy_bits(W) more bits); fb is then raised again, if the index leaves room, until a window has <= COARSE_MAX_BINS
-  // bins (k_fine sorts a denser bin unstaged); -1 when even that does not fit.
-  int fine_bits(int c, uint32_t M, uint32_t W = 1) const {
-    const int idx_bits = ceil_log2_u64(M < 2 ? 2 : M) + copy_bits(W);
-    int fb = 31 - idx_bits;
-    if (fb > FINE_MAX_BITS) fb = FINE_MAX_BITS;
-    if (fb_cap_ > 0 && fb > fb_cap_) fb = fb_cap_;
-    if (fb > c - 1) fb = c - 1;
-    const int fb_max = fb;
-    const uint64_t L = 1ull << (c - 1);
-    while (fb > 0 && ((((uint64_t)M * W) << fb) / L) * 10 > (uint64_t)FINE_STAGE * 9) fb--;
-    if (W > 1) {
-      while (fb < fb_max && (L >> fb) > (uint64_t)COARSE_MAX_BINS) fb++;
-      if ((L >> fb) > (uint64_t)COARSE_MAX_BINS || fb < 0) return -1;
-    }
-    return fb;
-  }
-  // windows per bucket set of a plan
-  static uint32_t set_windows(const Plan& pl) { return pl.F < (uint32_t)pl.K ? pl.F : (uint32_t)pl.K; }
-
-  // Fine bits of the TOP window's bins (SortGeom::fbt): its entries fall on top_range << spread buckets only (the largest
-  // scalar bounds the top digit), so they are up to 2x denser than M / L; as many fine bits as keep such a bin inside
-  // k_fine's staging, and no fewer than keep the window's bins inside k_coarse's 9-bit bin field.
-  int fine_bits_top(const Plan& pl, int fb) const {
-    if (pl.fold_shift != 0 || no_fbt_ || pl.F > 1) return fb;
-    const uint64_t slots = (uint64_t)pl.top_range << pl.spread;
-    int fbt = fb;
-    while (fbt > 0 && (((uint64_t)pl.M << fbt) / slots) * 10 > (uint64_t)FINE_STAGE * 9) fbt--;
-    while (fbt < fb && ((pl.L >> fbt) << pl.spread) > (uint32_t)COARSE_MAX_BINS) fbt++;
-    return fbt;
-  }
-
-  // Default window size.  Large inputs (M >= 2^18: profiles/r03_sweep.json) are throughput-bound: c = log2 M - 3 capped at 17, stepped
-  // down while the top window would be nearly empty.  Smaller inputs are latency-bound -- every tree round costs
-  // ~75 us whatever its size and the number of rounds is log2 of the LONGEST bucket, which usually sits in a
-  // partly filled top window -- so they pick the c that minimizes a small cost model fitted to this GPU
-  // (ms: rounds * 0.075 + additions / 4.5e6 + reduction levels * 0.065 + buckets * 0.8e-6).
-  // A batch of B problems runs the same number of tree rounds and reduction levels as one, with B times the additions
-  // and buckets: those two terms of the model are scaled by B.
-  // Precomputed point sets (F > 1 windows per bucket set): the same model at every size, over the
-  // window sizes whose sets fit one sort pass, with ceil(K / F) bucket sets, buckets W = min(F, K) times longer, and the
-  // top window's concentration on its few digits (it shares a set, it is neither spread nor folded).
-  int choose_window(bool glv, uint32_t M, int b, bool tree_rounds, uint32_t nprob = 1, uint32_t F = 1) const {
-    if (F > 1) return choose_window_pre(glv, M, b, nprob, F);
-    int c = default_window(M);
-    if (M >= (1u << 18) || no_window_model_) {
-      // measured optimum of the batched-affine path from 2^18 entries per window on (profiles/r03_sweep.json): 17 without
-      // GLV (2^18: 1.60 ms against 1.83 at c = 15), 16 with it (128-bit halves = 8 windows exactly)
-      if (tree_rounds && !no_window_model_) c = glv ? 16 : 17;
-      for (int tries = 0; tries < 3 && c > 4; tries++) {
-        const int K0 = (b + 1 + c - 1) / c;
-        const int top_bits = b + 1 - (K0 - 1) * c;
-        if (K0 == 1 || top_bits >= c - 4) break;
-        c--;
-      }
-      return c;
-    }
-    const int lg = ceil_log2_u64(M < 2 ? 2 : M);
-    int best_c = c;
-    double best = 1e30;
-    for (int cc = (lg - 6 < 3 ? 3 : lg - 6); cc <= (lg + 2 > 17 ? 17 : lg + 2); cc++) {
-      const Geometry g = geometry(cc, glv, M, b);
-      if (g.Keff > kMaxWindows) continue;
-      const double lam = (double)M / g.L;
-      const double conc = g.t_top < cc ? (double)(1u << (cc - g.t_top)) / (1 << g.spread) : 1.0;
-      double maxb = 1.5 * lam + 12;
-      if (g.K > 1 && conc * lam * 1.3 + 12 > maxb) maxb = conc * lam * 1.3 + 12;
-      if (maxb > M) maxb = M;
-      const int rounds = ceil_log2_u64((uint64_t)(maxb < 2 ? 2 : maxb));
-      const double cost = (tree_rounds ? 0.075 * rounds : 0.0) + (double)nprob * g.K * M / 4.5e6 +
-                          0.065 * ((cc - 1 + 1) / 2) + 0.8e-6 * nprob * g.Keff * g.L;
-      if (cost < best) {
-        best = cost;
-        best_c = cc;
-      }
-    }
-    return best_c;
-  }
-
-  // does a window size fit a precomputed set's sort (F windows per set; the two-level sort only)?
-  bool pre_fits(int c, bool glv, uint32_t M, int b, uint32_t F) const {
-    const Geometry g = geometry(c, glv, M, b, false, F);
-    const uint32_t W = F < (uint32_t)g.K ? F : (uint32_t)g.K;
-    const int fb = fine_bits(c, M, W);
-    if (fb < 0 || g.K > kMaxWindows || M > (1u << 24)) return false;
-    // one bucket collects the entries of all W windows of its set (every digit equal in the worst case): the tree rounds
-    // take buckets below 2^PLAN_RMAX entries
-    if ((uint64_t)W * M >= (1ull << PLAN_RMAX)) return false;
-    const uint32_t ncb = g.L >> fb;
-    return ncb <= (uint32_t)COARSE_MAX_BINS && (uint64_t)g.K * ncb <= (uint64_t)SORT_MAX_BINS;
-  }
-  int choose_window_pre(bool glv, uint32_t M, int b, uint32_t nprob, uint32_t F) const {
-    // measured (profiles/r05_precompute_c_sweep.jsonl): with every window in one set and >= 2^16 entries per window, c = 17
-    // is the fastest fitting size (2^16: 0.86 ms against 0.94 at c = 16, 16 x 2^16: 3.26 against 3.43, 2^20: 3.62 against
-    // 3.99); with fewer windows per set the model below is (16 x 2^16, F = 2: c = 15 5.98 ms, c = 17 7.76)
-    if (!glv && M >= (1u << 16) && F >= (uint32_t)geometry(17, false, M, b, false, F).K && pre_fits(17, false, M, b, F))
-      return 17;
-    int best_c = 0;
-    double best = 1e30;
-    for (int cc = 3; cc <= 20; cc++) {
-      if (!pre_fits(cc, glv, M, b, F)) continue;
-      const Geometry g = geometry(cc, glv, M, b, false, F);
-      const uint32_t W = F < (uint32_t)g.K ? F : (uint32_t)g.K;
-      const int sets = (g.K + (int)W - 1) / (int)W;
-      const int w_top = g.K - (sets - 1) * (int)W;   // windows in the top window's set
-      const double lam = (double)M * W / g.L;
-      double maxb = 1.5 * lam + 12;
-      const double top = 1.3 * (double)M / (g.top_range < 1 ? 1 : g.top_range) + (double)(w_top - 1) * M / g.L + 12;
-      if (g.K > 1 && top > maxb) maxb = top;
-      if (maxb > (double)M * W) maxb = (double)M * W;
-      const int rounds = ceil_log2_u64((uint64_t)(maxb < 2 ? 2 : maxb));
-      const double cost = 0.075 * rounds + (double)nprob * g.K * M / 4.5e6 + 0.065 * ((cc - 1 + 1) / 2) +
-                          0.8e-6 * nprob * sets * g.L;
-      if (cost < best) {
-        best = cost;
-        best_c = cc;
-      }
-    }
-    return best_c > 0 ? best_c : default_window(M);
-  }
-
-  int make_plan(Plan& pl, uint64_t n64, bool glv, const msmz_opts& opt, uint32_t pts_n, bool tree_rounds = true,
-                int extra_bits = 0, bool allow_fold = false, uint32_t nprob = 1, uint32_t F = 1) {
-    pl.n = (uint32_t)n64;
-    pl.nprob = nprob;
-    pl.glv = glv;
-    pl.M = glv ? 2 * pl.n : pl.n;
-    // scalar bit length.  GLV halves: first attempt assumes |s_j| < 2^127 (every half seen so far; for BLS12-377 the
-    // analytic bound is 2^126); k_hist flags a longer half and the MSM is redone (extra_bits = 1) with the proven bound
-    // GLV_PROVEN_BITS <= 128, which also is what the 4-word halves of glv_decompose can hold.
-    static_assert(!Fr::HAS_GLV || (Fr::GLV_PROVEN_BITS <= 128 && Fr::GLV_PROVEN_BITS <= Fr::GLV_BITS), "GLV halves must fit 4 words");
-    pl.b = scalar_bits(glv, extra_bits);
-    pl.c = opt.c > 0 ? opt.c : choose_window(glv, pl.M, pl.b, tree_rounds, nprob, F);
-    if (pl.c < 2) pl.c = 2;
-    if (pl.c > 24) pl.c = 24;
-    pl.F = F < 1 ? 1 : F;
-    const Geometry g = geometry(pl.c, glv, pl.M, pl.b, allow_fold, pl.F);
-    pl.K = g.K;
-    pl.L = g.L;
-    pl.spread = g.spread;
-    pl.top_range = g.top_range;
-    pl.fold_shift = g.fold_shift;
-    pl.fold_rows = g.fold_rows;
-    pl.Keff = g.Keff;
-    if (pl.F > 1) pl.Keff = (pl.K + (int)set_windows(pl) - 1) / (int)set_windows(pl);   // bucket sets
-    const uint64_t nb64 = (uint64_t)pl.Keff * pl.L;
-    if (nb64 * nprob + 1 >= (1ull << 31) || (uint64_t)nprob * pl.K * pl.M >= (1ull << 32) || pl.Keff > kMaxWindows)
-      return MSMZ_ERR_ARG;
-    pl.nb = (uint32_t)nb64;
-    pl.nblocks = (pl.nb + SCAN_TILE - 1) / SCAN_TILE;
-    pl.timing = opt.timing != 0;
-    pl.endo_delta = glv ? pts_n - pl.n : 0u;
-    return MSMZ_OK;
-  }
-
-  // does the two-level LDS-staged sort apply to this plan (else the per-entry atomic fallback)?
-  bool sort2_applies(const Plan& pl) const {
-    const int fb = fine_bits(pl.c, pl.M, set_windows(pl));
-    if (fb < 0) return false;
-    const uint32_t ncb = pl.L >> fb;
-    const uint32_t ncbt = pl.L >> fine_bits_top(pl, fb);
-    const uint32_t nbins = (uint32_t)(pl.K - 1) * ncb + (ncbt << pl.spread);
-    return !force_atomic_sort_ && fb >= 0 && pl.M <= (1u << 24) && ncb <= (uint32_t)COARSE_MAX_BINS &&
-           (ncbt << pl.spread) <= (uint32_t)COARSE_MAX_BINS && nbins <= (uint32_t)SORT_MAX_BINS;
-  }
-
   // scalars -> sorted references `refs_` + bucket offsets `off_` (+ meta->max_bucket); events 0..4.  No host round trip.
   // pl.nprob > 1 (batched MSM): problem p reads scalars [p n, (p + 1) n); its bins follow problem p - 1's in ONE exclusive
   // scan, so refs_ / off_ come out as one dense sort of pl.nprob * nb buckets.  The two-level sort only.
-  int sort_phase(Plan& pl, const uint32_t* d_scalars) {
-    const uint32_t n = pl.n, M = pl.M, L = pl.L, nb = pl.nb, nblocks = pl.nblocks, P = pl.nprob;
+  // `sl`: the planner's sort layout of pl.
+  int sort_phase(Plan& pl, const SortLayout& sl, const uint32_t* d_scalars) {
+    const uint32_t n = pl.n, M = pl.M, nb = pl.nb, nblocks = pl.nblocks, P = pl.nprob;
     const int c = pl.c, K = pl.K;
     int st;
     if ((st = refs_.ensure((size_t)P * K * M * 4))) return st;
     if ((st = off_.ensure(((size_t)P * nb + 1) * 4))) return st;
     MsmMeta* d_meta = meta_.as<MsmMeta>();
     MSMZ_HIP(hipMemsetAsync(d_meta, 0, sizeof(MsmMeta), stream_));
-    // two-level LDS-staged sort when the packed (fine | negate | index) word fits; else per-entry atomics.
-    // packed word = fine bucket bits | negate | index: the narrower the index, the more fine bits fit, the
-    // fewer (and longer) coarse runs the scatter writes
-    // precomputed sets: W windows per bucket set, the packed index = copy << mbits | entry
-    const uint32_t W = set_windows(pl);
-    const int mbits = ceil_log2_u64(M < 2 ? 2 : M);
-    const int idx_bits = mbits + copy_bits(W);
-    const bool sort2 = sort2_applies(pl);
-    if (!sort2 && (P > 1 || pl.F > 1)) return MSMZ_ERR_ARG;   // (msm_batch only batches plans the two-level sort handles)
-    const int fb = sort2 ? fine_bits(c, M, W) : fine_bits(c, M);
-    const uint32_t ncb = L >> fb;
-    const int fbt = fine_bits_top(pl, fb);
-    const uint32_t ncbt = L >> fbt;
-    const uint32_t top_bin = (uint32_t)(K - 1) * ncb;
-    const uint32_t nbins = top_bin + (ncbt << pl.spread);   // tile-local bins (per window)
-    const uint32_t sbins = pl.F > 1 ? (uint32_t)pl.Keff * W * ncb : nbins;   // scanned bins per problem
-    const uint32_t fbins = pl.F > 1 ? (uint32_t)pl.Keff * ncb : nbins;       // k_fine's bins per problem
+    if (!sl.two_level && (P > 1 || pl.F > 1)) return MSMZ_ERR_ARG;   // (msm_batch only batches plans the two-level sort handles)
+    const uint32_t nbins = sl.nbins, fbins = sl.fbins;
     const uint32_t n_half = pl.glv ? n : 0xffffffffu;
-    if (sort2) {
-      const size_t pbins = (size_t)P * sbins;   // bins of all problems
+    if (sl.two_level) {
+      const SortGeom& g = sl.geom;
+      const size_t pbins = (size_t)P * g.sbins;   // bins of all problems
       if ((st = packed_.ensure((size_t)P * K * M * 4))) return st;
       if ((st = bins_.ensure((pbins + 2) * 4 + kTraceBytes * pbins))) return st;
       if ((st = counts_.ensure(pbins * 4))) return st;
       uint32_t* d_counts = counts_.as<uint32_t>();
       MSMZ_HIP(hipMemsetAsync(d_counts, 0, pbins * 4, stream_));
-      SortGeom g{n, M, c, K, fb, pl.spread, idx_bits, ncb, fbt, ncbt, pl.fold_shift, pl.fold_rows, W, mbits, sbins};
       mark(pl);  // 0
       const uint32_t per_tile = pl.glv ? COARSE_TILE / 2 : COARSE_TILE;   // scalars per workgroup (k_hist and k_coarse)
       const uint32_t tiles = (n + per_tile - 1) / per_tile;
       if ((st = tilecnt_.ensure((size_t)P * tiles * nbins * 2))) return st;
       if ((st = tileoff_.ensure((size_t)P * tiles * nbins * 4 + kTraceBytes * tiles))) return st;   // the tiles' runs inside the bins
-      // kernels specialized for the window size (unrolled window loop) where one is compiled: 16 / 17, the defaults of
-      // large inputs; any other window size takes the generic ones
-      const int cspec = (no_sort_special_ || (c != 16 && c != 17) || (pl.glv && c != 16)) ? 0 : c;
+      const int cspec = sl.cspec;
       auto launch_sort = [&](auto glvc, auto cc, bool coarse) {
         constexpr bool G = decltype(glvc)::value;
         constexpr int C = decltype(cc)::value;
@@ -1249,14 +894,13 @@ class Engine : public IEngine {
       {
         const size_t lds = kFineLds;
         hipLaunchKernelGGL(k_fine, dim3(fbins, P), dim3(FINE_T), lds, stream_, refs_.as<uint32_t>(), off_.as<uint32_t>(),
-                           &d_meta->max_bucket, packed_.as<uint32_t>(), bins_.as<uint32_t>(), fb, fbt,
-                           pl.F > 1 ? fbins - ncb : top_bin, fbins, idx_bits, n_half, pl.endo_delta, W, mbits,
-                           pl.copy_stride);
+                           &d_meta->max_bucket, packed_.as<uint32_t>(), bins_.as<uint32_t>(), g.fb, g.fbt, sl.fine_top,
+                           fbins, g.idx_bits, n_half, pl.endo_delta, g.F, g.mbits, pl.copy_stride);
       }
 #ifdef MSMZ_TRACE
       // development aid: workgroup time stamps of k_coarse / k_fine (tools/wg_timeline.py)
       if ((st = trace_dump("k_coarse", tileoff_.as<uint32_t>() + (size_t)P * tiles * nbins, tiles, true))) return st;
-      if ((st = trace_dump("k_fine", bins_.as<uint32_t>() + ((P * sbins + 2) & ~1u), fbins, false))) return st;
+      if ((st = trace_dump("k_fine", bins_.as<uint32_t>() + ((P * g.sbins + 2) & ~1u), fbins, false))) return st;
 #endif
     } else {
       // fallback (window sizes whose coarse bins do not fit the LDS staging): digits materialized, one global
@@ -1353,16 +997,6 @@ class Engine : public IEngine {
     return MSMZ_OK;
   }
 
-  uint32_t first_group_size(const Plan& pl) const {
-    if (s1_override_ > 0) return s1_override_ < pl.L ? s1_override_ : pl.L;
-    uint32_t S1 = 2;
-    // L / S1 a power of 4 saves one reduction level; with >= 2^20 buckets groups of 8 still fill the GPU
-    // (2 waves per SIMD) and halve the levels above (measured: S1 = 4 -> 1.58 ms, 8 -> 1.45 ms, 16 -> 1.94 ms)
-    if (pl.L >= 4 && (ceil_log2_u64(pl.L) & 1) == 0) S1 = 4;
-    if ((uint64_t)pl.Keff * pl.L >= (1u << 20) && pl.L >= 8) S1 = 8;
-    return S1 < pl.L ? S1 : pl.L;
-  }
-
   // copy the window results of all pl.nprob problems (the C entries of the last level; its rows are multiples of the
   // weight unit and not needed) and the meta block to the host: one problem's behind h_final_'s first kMaxWindows
   // records, a batch's to h_bfinal_
@@ -1404,7 +1038,7 @@ class Engine : public IEngine {
     const size_t per_problem = (size_t)(two_d ? 2 : 1) * pl.Keff;
     // (the terms are listed while the device still reduces)
     const std::vector<WindowTerm> terms =
-        window_terms(pl.c, pl.K, pl.Keff, (int)pl.F, two_d ? split_2d(pl).b : -1, pl.fold_shift != 0);
+        window_terms(pl.c, pl.K, pl.Keff, (int)pl.F, two_d ? planner_.split_2d(pl).b : -1, pl.fold_shift != 0);
     const uint32_t* res;
     int st = fetch_window_sums(pl, per_problem, &res);
     if (st) return st;
@@ -1431,33 +1065,11 @@ class Engine : public IEngine {
 
   // Two-dimensional bucket reduction (reduce2d_kernels.h): line sums, then the weighted sums over H lines of 2 Keff
   // problems with the upper-level kernels.  Leaves result 2 kw (rows) / 2 kw + 1 (columns) of bucket set kw in final_.
-  struct Split2d {
-    int a, b;            // c - 1 = a + b: high / low bits of the bucket weight
-    uint32_t H, D, NC;
-  };
-  Split2d split_2d(const Plan& pl) const {
-    Split2d s;
-    s.a = (pl.c - 1 + 1) / 2;
-    s.b = pl.c - 1 - s.a;
-    s.H = 1u << s.a;
-    s.D = 1u << s.b;
-    // chunks per line: so that the partial sums of all lines are ~256 K threads (measured at 2^20: 16 / 32 / 64 chunks ->
-    // reduce stage 0.88 / 0.81 / 0.81 ms), at most 32 per line (5 pair-sum launches), and a chunk holds at least one
-    // bucket along either direction
-    uint32_t nc = 1;
-    while (nc < 32 && nc * 2 <= s.D && (uint64_t)2 * pl.nprob * pl.Keff * s.H * nc < (1u << 18)) nc *= 2;
-    if (r2_nc_ > 0) {
-      nc = 1;
-      while (nc < r2_nc_ && nc * 2 <= s.D) nc *= 2;
-    }
-    s.NC = nc;
-    return s;
-  }
   // basic = true: the buckets are sums of partial accumulators (msmBasic path: slots_ + rscan_), else the affine bucket
   // sums of the tree rounds (bfin_)
   template <class P>
   int reduce_2d(const Plan& pl, const uint32_t* d_points, bool basic = false, bool summed = false) {
-    const Split2d sp = split_2d(pl);
+    const Split2d sp = planner_.split_2d(pl);
     R2Geom g;
     g.L = pl.L;
     g.H = sp.H;
@@ -1550,38 +1162,25 @@ class Engine : public IEngine {
     // precomputed point set: its copies carry windows [j F, (j + 1) F) into one bucket set (two-level sort, 2-D reduction)
     const uint32_t fac = pts.factor > 1 ? pts.factor : 1;
     if (fac > 1 && (!want_2d || glv != (pts.glv != 0))) return MSMZ_ERR_UNSUPPORTED;
-    int st = make_plan(pl, n64, glv, opt, (uint32_t)pts.n, true, extra_bits, want_2d, nprob, fac);
+    int st = planner_.make_plan(pl, n64, glv, opt, (uint32_t)pts.n, true, extra_bits, want_2d, nprob, fac);
     if (st) return st;
     pl.copy_stride = (uint32_t)pts.copy_stride;
-    if (fac > 1 && !sort2_applies(pl)) return MSMZ_ERR_ARG;   // (msmz_precompute_points refuses such sets)
-    if (nprob > 1 && (!want_2d || !sort2_applies(pl))) return MSMZ_ERR_BATCH_LOOP;
+    const SortLayout sl = planner_.sort_layout(pl);
+    if (fac > 1 && !sl.two_level) return MSMZ_ERR_ARG;   // (msmz_precompute_points refuses such sets)
+    if (nprob > 1 && (!want_2d || !sl.two_level)) return MSMZ_ERR_BATCH_LOOP;
     // location words hold a record index in 30 bits
     if ((uint64_t)nprob * pl.K * pl.M >= (1ull << 30)) return MSMZ_ERR_ARG;
     // whole groups of 64 records; + the records of the batched-affine first reduction level when it is selected
     const size_t f2_records = opt.reserved[0] == 1 ? (size_t)13 * pl.Keff * ((pl.L + 1) / 2) + 256 : 0;
     if ((st = slots_.ensure(((size_t)nprob * pl.K * pl.M + 64 + f2_records) * SlotFmt<F>::WORDS * 4))) return st;
-    if ((st = sort_phase(pl, d_scalars))) return st;
+    if ((st = sort_phase(pl, sl, d_scalars))) return st;
     const uint32_t nb = pl.nb * nprob;   // buckets of all problems
     MsmMeta* d_meta = meta_.as<MsmMeta>();
 
     // ---- plan: descriptors of every pair of every round + what is left of each bucket (plan_kernels.h)
     const int ev_plan0 = pl.ei;
     mark(pl);
-    // buckets per plan workgroup: at most PLAN_CHUNK, fewer when the windows have few (long) buckets, so that the plan
-    // still spreads over ~4 workgroups per CU
-    uint32_t chunk = PLAN_CHUNK;
-    while (chunk > 64 && (nb + chunk - 1) / chunk < 1024) chunk >>= 1;
-    // the top window's bucket sets in half-size chunks when they are denser than the others (plan_kernels.h PlanChunks)
-    PlanChunks pc;
-    pc.chunk = chunk;
-    pc.nb_main = nb;
-    pc.chunk_top = chunk;
-    if (!no_plan_top_ && nprob == 1 && pl.F == 1 && pl.K > 1 && pl.fold_shift == 0 && chunk >= 128 &&
-        (uint64_t)pl.L * 10 > ((uint64_t)pl.top_range << pl.spread) * 13) {
-      pc.nb_main = (uint32_t)(pl.K - 1) * pl.L;
-      pc.chunk_top = chunk / 2;
-    }
-    pc.n_main = (pc.nb_main + chunk - 1) / chunk;
+    const PlanChunks pc = planner_.plan_chunks(pl);
     const uint32_t n_chunks = pc.n_main + (nb - pc.nb_main + pc.chunk_top - 1) / pc.chunk_top;
     // chunk totals per round, then the per-workgroup scratch of the rounds beyond PLAN_RL
     const size_t pair_words = (size_t)n_chunks * (PLAN_RMAX - PLAN_RL) * PLAN_T;
@@ -1638,7 +1237,7 @@ class Engine : public IEngine {
     } else {
       // level 1 from affine bucket sums, then XYZZ levels down to one entry per window.  The weight-L bucket is folded
       // into element L/2, which must be the FIRST element of its group
-      uint32_t S1 = first_group_size(pl);
+      uint32_t S1 = planner_.first_group_size(pl);
       if (S1 > 8) S1 = 8;
       while (S1 > 1 && S1 * 2 > pl.L) S1 >>= 1;
       const uint32_t groups = (pl.L + S1 - 1) / S1;   // elements are weights 0..L-1 (weight L folded into L/2)
@@ -1659,9 +1258,9 @@ class Engine : public IEngine {
     // neither msmProjective (parallel.ts:69-87) nor the twisted-Edwards path (msm-basic.ts:4) uses the endomorphism
     if (opt.glv) return MSMZ_ERR_UNSUPPORTED;
     Plan pl;
-    int st = make_plan(pl, n64, false, opt, (uint32_t)pts.n, false);
+    int st = planner_.make_plan(pl, n64, false, opt, (uint32_t)pts.n, false);
     if (st) return st;
-    if ((st = sort_phase(pl, d_scalars))) return st;
+    if ((st = sort_phase(pl, planner_.sort_layout(pl), d_scalars))) return st;
     if ((st = fetch_meta(pl))) return st;
     if (h_meta_->error & 4u) return MSMZ_ERR_RANGE;
     if ((st = partials_.ensure((size_t)32 * pl.nblocks * 4))) return st;
@@ -1850,42 +1449,36 @@ class Engine : public IEngine {
 
   // shared state -------------------------------------------------------------------------------
   static constexpr int kMaxEvents = 64;
-  static constexpr int kMaxWindows = 128;
   int device_;
   hipStream_t stream_ = nullptr;
   hipEvent_t ev_[kMaxEvents] = {};
   std::map<uint64_t, Handle> handles_;
   uint64_t next_handle_ = 1;
-  // Tuning knobs.  A release build uses the constants; a development build (-DMSMZ_DEV, tools/build_variant.sh)
-  // reads MSMZ_* environment variables when the context is created.  None of them changes a result.
+  // Tuning knobs (the planning ones: PlanKnobs, plan.h).  A release build uses the constants; a development build
+  // (-DMSMZ_DEV, tools/build_variant.sh) reads MSMZ_* environment variables when the context is created.  None of them
+  // changes a result.
 #ifdef MSMZ_DEV
   static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
 #else
   static int env_int(const char*, int dflt) { return dflt; }
 #endif
-  uint32_t coarse_wgs_ = (uint32_t)env_int("MSMZ_COARSE_WGS", 2048);
   uint32_t batch_min_wgs_ = (uint32_t)env_int("MSMZ_BATCH_WGS", 512);
   int chunk_shift_override_ = env_int("MSMZ_CHUNK_SHIFT", 0);
-  int fb_cap_ = env_int("MSMZ_FB", 0);
-  uint32_t s1_override_ = (uint32_t)env_int("MSMZ_S1", 0);
   uint32_t tail_n_ = (uint32_t)env_int("MSMZ_TAIL_N", REDUCE_TAIL_N);   // entries per window at which k_reduce_tail takes over
   uint32_t quad16_max_groups_ = (uint32_t)env_int("MSMZ_QUAD16", 8192);   // levels with at most this many groups use k_reduce_quad16
   Host64<F> host64_;
-  bool no_spread_ = env_int("MSMZ_NO_SPREAD", 0) != 0;
-  bool no_fold_ = env_int("MSMZ_NO_FOLD", 0) != 0;
   bool no_bucket_sums_ = env_int("MSMZ_NO_BUCKET_SUMS", 0) != 0;
-  bool no_window_model_ = env_int("MSMZ_NO_WINDOW_MODEL", 0) != 0;
-  bool force_atomic_sort_ = env_int("MSMZ_ATOMIC_SORT", 0) != 0;
-  bool no_plan_top_ = env_int("MSMZ_NO_PLAN_TOP", 0) != 0;            // top-window bucket sets in full-size plan chunks
-  bool no_fbt_ = env_int("MSMZ_NO_FBT", 0) != 0;                     // top window's bins as wide as the others
-  bool no_sort_special_ = env_int("MSMZ_NO_SORT_SPECIAL", 0) != 0;   // generic sort kernels for every window size
   // rounds left to the 2-D reduction's loader: at most 2 (a bucket's final-location record holds 4 partial sums)
   int tail_skip_2d_ = env_int("MSMZ_TAIL_SKIP_2D", 1) > 2 ? 2 : env_int("MSMZ_TAIL_SKIP_2D", 1);
-  uint32_t r2_nc_ = (uint32_t)env_int("MSMZ_R2_NC", 0);         // chunks per line (0 = automatic)
   uint32_t pairsum_x4_max_ = (uint32_t)env_int("MSMZ_PAIRSUM_X4", 16384);   // pair-sum levels with at most this many additions use DPP quads
   int batch_b_override_ = env_int("MSMZ_BATCH_B", 0);
   int retries_ = 0;            // MSMs redone with the proven GLV bound (test hook reads it)
-  int glv_bits_assumed_ = 0;   // test hook (msmz_test_set_glv_bits): assumed bit length of a GLV half; 0 = GLV_BITS - 1
+  // window sizes, geometry, sort layout (plan.h), PlanKnobs in declaration order
+  Planner<Fr> planner_{{env_int("MSMZ_NO_SPREAD", 0) != 0, env_int("MSMZ_NO_FOLD", 0) != 0,
+                        env_int("MSMZ_NO_WINDOW_MODEL", 0) != 0, env_int("MSMZ_ATOMIC_SORT", 0) != 0,
+                        env_int("MSMZ_NO_FBT", 0) != 0, env_int("MSMZ_NO_PLAN_TOP", 0) != 0,
+                        env_int("MSMZ_NO_SORT_SPECIAL", 0) != 0, env_int("MSMZ_FB", 0), (uint32_t)env_int("MSMZ_S1", 0),
+                        (uint32_t)env_int("MSMZ_R2_NC", 0)}};
   DevBuf bsum_, f2desc_, tilecnt_, tileoff_, final_, desc_, bfin_, packed_, bins_, digits_, counts_, off_, cursor_, refs_, rscan_, partials_, slots_, red_[4], meta_, stage_, gen_table_;
   uint32_t h_round_pairs_[32] = {};
   MsmMeta* h_meta_ = nullptr;

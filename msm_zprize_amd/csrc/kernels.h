@@ -31,6 +31,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "constants_gen.h"
+#include "plan.h"
 #include "curve.h"
 #include "scalar.h"
 
@@ -408,9 +409,7 @@ __global__ void __launch_bounds__(256) k_check_scalars(uint32_t* err, const uint
 //   mode 0: v(g) = in[g]                                   (bucket sizes -> offsets)
 //   mode 1: v(g) = pairs in round r of bucket g, r = blockIdx.y, from bucket offsets `in`
 //           pairs_m(s) = floor((s + m - 1) / (2m)), m = 2^r  (number of j with j*2m + m < s)
-constexpr int SCAN_T = 256;
-constexpr int SCAN_ITEMS = 8;
-constexpr int SCAN_TILE = SCAN_T * SCAN_ITEMS;
+//   (SCAN_T threads x SCAN_ITEMS values per workgroup: plan.h)
 
 __device__ __forceinline__ uint32_t scan_value(const uint32_t* in, uint32_t g, uint32_t n, int mode, int r) {
   if (g >= n) return 0;

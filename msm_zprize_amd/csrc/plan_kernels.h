@@ -19,13 +19,10 @@
 // rounds only touch the few longest buckets but cost a full round of latency, so the reduction's loader adds the <= 4
 // partial sums such a bucket is left with).
 #pragma once
+#include "plan.h"   // PLAN_T, PLAN_PER, PLAN_CHUNK, PLAN_RMAX, PlanChunks
 
 namespace msmz {
 
-constexpr int PLAN_T = 512;
-constexpr int PLAN_PER = 2;                       // consecutive buckets per thread (counting / scan phases)
-constexpr int PLAN_CHUNK = PLAN_T * PLAN_PER;     // buckets per workgroup
-constexpr int PLAN_RMAX = 26;                     // rounds supported (bucket sizes < 2^26)
 constexpr int PLAN_RL = 6;                        // rounds whose per-bucket pair numbers sit in LDS (one thread per PAIR);
                                                   // later rounds (buckets > 64 entries) are emitted bucket by bucket
 constexpr int PLAN_TILE = 4096;                   // pairs whose owner buckets are expanded into LDS at a time
@@ -47,14 +44,7 @@ __device__ __forceinline__ uint32_t pairs_in_round(uint32_t size, int r) {   // 
   return (size + (1u << r) - 1u) >> (r + 1);
 }
 
-// chunk_pairs[r * n_chunks + chunk] = pairs of round r in the chunk's buckets, r < PLAN_RMAX
-// `chunk` <= PLAN_CHUNK buckets per workgroup (the host picks it so that there are enough workgroups for the GPU even
-// when a window has few, long buckets).
-// The buckets from `nb_main` on (the top window's bucket sets, up to 2x denser than the others) are cut into chunks of
-// `chunk_top` <= chunk buckets, so that their workgroups do not outlast the rest (a launch ends with its slowest one).
-struct PlanChunks {
-  uint32_t chunk, nb_main, n_main, chunk_top;
-};
+// chunk_pairs[r * n_chunks + chunk] = pairs of round r in the chunk's buckets, r < PLAN_RMAX; chunks as PlanChunks (plan.h)
 __device__ __forceinline__ void plan_chunk_range(const PlanChunks& pc, uint32_t nb, uint32_t& g0, uint32_t& nbk) {
   if (blockIdx.x < pc.n_main) {
     g0 = blockIdx.x * pc.chunk;

@@ -20,15 +20,9 @@
 //   then the existing upper levels (k_reduce_quad16 / k_reduce_tail) run on 2 Keff problems of H entries with
 //   rows = line sums, C = infinity.
 #pragma once
+#include "plan.h"   // R2Geom
 
 namespace msmz {
-
-struct R2Geom {
-  uint32_t L, H, D;       // buckets per set, rows, columns (H * D = L, H >= D)
-  uint32_t NC;            // chunks per line (power of two)
-  uint32_t chr, chc;      // buckets per chunk along a row (D / NC) and along a column (H / NC)
-  uint32_t nprob;         // 2 * Keff
-};
 
 template <class F>
 __global__ void __launch_bounds__(128, MSMZ_REDUCE_OCC) k_reduce2d_partial(uint32_t* part, const uint32_t* slots,

@@ -22,18 +22,11 @@
 #include <type_traits>
 #include <utility>
 
+#include "plan.h"   // limits and SortGeom
+
 namespace msmz {
 
-constexpr int COARSE_T = 1024;
-constexpr int COARSE_ITEMS = 2;                        // half-scalars (= entries per window) per thread
-constexpr int COARSE_TILE = COARSE_T * COARSE_ITEMS;   // entries per window staged by one workgroup
-constexpr int COARSE_MAX_BINS = 512;                   // bins per window (top window: incl. its sub-windows) the staging supports
-constexpr int SORT_MAX_BINS = 8192;                    // all windows: k_coarse keeps 2 words per bin in LDS (64 KB)
 constexpr int kMaxWindowsSort = 128;                   // windows a scalar can have (c >= 2)
-constexpr int FINE_MAX_BITS = 11;
-constexpr int FINE_T = 1024;
-constexpr int FINE_PER = 37;                           // entries a thread holds in registers
-constexpr int FINE_STAGE = FINE_T * FINE_PER;          // 37888 entries staged in LDS: 148 KB + 8 KB of counters (+ static) < 160 KB
 
 // Development aid (-DMSMZ_TRACE builds only): thread 0 of every workgroup stamps the 100 MHz wall clock into 16 slots
 // behind a buffer the kernel already receives; slot 15 = hardware id (which CU / XCD).  tools/wg_timeline.py reads them.
@@ -52,31 +45,6 @@ constexpr int FINE_STAGE = FINE_T * FINE_PER;          // 37888 entries staged i
 #define MSMZ_STAMP(tr, slot) do {} while (0)
 #define MSMZ_STAMP_HW(tr) do {} while (0)
 #endif
-
-struct SortGeom {
-  uint32_t n;          // scalars
-  uint32_t M;          // entries per window: n, or 2 n with GLV (entry n + i = endomorphism half of scalar i)
-  int c, K, fb, spread, idx_bits;
-  uint32_t ncb;        // coarse bins per bucket set = L >> fb
-  // The TOP window's bucket sets may use fewer fine bits (fbt <= fb, ncbt = L >> fbt bins each): its digit range is not a
-  // power of two, so its buckets are up to 2x denser than the other windows' and a bin of 2^fb of them would not fit
-  // k_fine's LDS staging.  Bins of windows 0..K-2 come first (ncb each), then the top window's sub-windows (ncbt each).
-  int fbt;
-  uint32_t ncbt;
-  // A THIN top window (its digit has only a few significant bits) can be FOLDED into its own bucket set instead of
-  // spread over sub-windows: bucket weight j = (entry mod 2^fold_rows) * 2^fold_shift + l, i.e. the L buckets of the set
-  // hold 2^fold_rows copies ("rows") of the digit's small range, and the two-dimensional reduction's COLUMN sums are
-  // exactly the per-digit sums (the row result of that set is not used).  fold_shift = 0: not folded.
-  int fold_shift, fold_rows;
-  // Precomputed point sets (msmz_precompute_points): F windows share one bucket set.  Window k adds into set k / F and
-  // references copy k mod F of the points, whose index rides in the packed word above the entry's `mbits` bits.  The
-  // tile-local bins stay per window (k * ncb + coarse: the LDS layouts above are unchanged); only the GLOBAL bin order is
-  // permuted (scan_bin) so that the F bins of one set with the same coarse value are adjacent and k_fine sorts them as one
-  // bin.  `sbins` = scanned bins per problem (ceil(K / F) * F * ncb).  F = 1: the identity, sbins = nbins.
-  uint32_t F;
-  int mbits;
-  uint32_t sbins;
-};
 
 // position of tile-local bin b (window b / ncb) in the global bin scan
 __device__ __forceinline__ uint32_t scan_bin(const SortGeom& g, uint32_t b) {
