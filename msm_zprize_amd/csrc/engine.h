@@ -33,14 +33,26 @@ namespace msmz {
     }                                                                                      \
   } while (0)
 
+// Device memory owned by one object: freed when it goes out of scope, so every error path releases it.
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr, o.bytes = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      release();
+      p = o.p, bytes = o.bytes;
+      o.p = nullptr, o.bytes = 0;
+    }
+    return *this;
+  }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
   int ensure(size_t need) {   // grow-only
     if (need <= bytes) return MSMZ_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
+    release();
     size_t sz = need + need / 8;
     if (hipMalloc(&p, sz) != hipSuccess) {
       if (hipMalloc(&p, need) != hipSuccess) return MSMZ_ERR_HIP;
@@ -64,7 +76,7 @@ struct Handle {
   int kind;        // 0 = points, 1 = scalars
   uint64_t n;
   bool has_endo;   // points: records [n, 2n) hold the endomorphism images
-  void* dev;
+  DevBuf mem;
   // precomputed point set (msmz_precompute_points): `factor` copies, copy j = records [j R, (j + 1) R) holds 2^(c j) P_i
   // (R = copy_stride = n, or 2 n with the endomorphism images); built for window size c and GLV choice glv.  0 = plain.
   uint32_t factor = 0;
@@ -72,11 +84,36 @@ struct Handle {
   uint64_t copy_stride = 0;
 };
 
-constexpr int MSMZ_ERR_RETRY_BITS = 1000;   // internal: repeat the MSM with one more scalar bit (never leaves the engine)
-constexpr int MSMZ_ERR_BATCH_LOOP = 1001;   // internal: this batched MSM runs its problems one by one (never leaves the engine)
+// Named events of an MSM's stages, created once per engine; a timed MSM records them in stream order.
+struct StageEvents {
+  hipEvent_t sort0, hist_end, scan_end, coarse_end, sort_end;   // sort: digits / histogram, scan, scatter
+  hipEvent_t plan0, plan_end;                                    // plan (incl. its host round trip)
+  hipEvent_t round_end[32];                                      // tree round r (recorded for non-empty rounds)
+  hipEvent_t acc_end, red_end;                                   // accumulation, bucket reduction
+  std::vector<hipEvent_t*> all() {
+    std::vector<hipEvent_t*> v{&sort0, &hist_end, &scan_end, &coarse_end, &sort_end, &plan0, &plan_end, &acc_end, &red_end};
+    for (hipEvent_t& e : round_end) v.push_back(&e);
+    return v;
+  }
+};
 
-// Host-side group addition of two canonical affine points (partial sums of index ranges / of GPUs):
-// the reference's "partition sum" on the main thread (msm-batched-affine.ts:300-307).
+// One MSM call's run state, beside its Plan (the planner's output): whether it is timed, its stage events, and the
+// device totals fetch_meta reads back.  n_pairs: the additions of the accumulation (the tree rounds' pairs; msmBasic:
+// the entries).
+struct Run {
+  bool timing = false;
+  StageEvents ev{};
+  uint32_t max_bucket = 0, n_entries = 0, rounds = 0;
+  uint32_t round_pairs[32] = {}, round_base[32] = {};
+  uint64_t n_pairs = 0;
+};
+
+// What an MSM attempt asks of its caller besides its status: nothing, the same MSM again with windows for the proven
+// GLV bound (a GLV half was longer than assumed), or this sub-batch's problems one by one (its plan does not batch).
+enum class Redo { NONE, PROVEN_BITS, PER_PROBLEM };
+
+// Host-side group addition of two canonical affine points (msmz_point_add; fold_partial, multi.h, folds partial MSM
+// results with it).
 template <class F, bool TE>
 static int host_point_add(const uint8_t* a, int ai, const uint8_t* b, int bi, uint8_t* out, int* oi) {
   constexpr int NW = F::NW;
@@ -140,18 +177,18 @@ class Engine : public IEngine {
   static constexpr int PW_WORDS = TE ? 4 * NW : PointFmt<F>::STRIDE;   // words between the records of a resident point set
 
  public:
-  explicit Engine(int device) : device_(device) {}
+  Engine(int curve_id, int device) : curve_id_(curve_id), device_(device) {}
 
   int init() {
     MSMZ_HIP(hipSetDevice(device_));
     MSMZ_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    for (auto& e : ev_) MSMZ_HIP(hipEventCreate(&e));
+    for (hipEvent_t* e : ev_.all()) MSMZ_HIP(hipEventCreate(e));
     MSMZ_HIP(hipHostMalloc(&h_meta_, sizeof(MsmMeta)));
-    MSMZ_HIP(hipHostMalloc(&h_final_, (size_t)3 * kMaxWindows * XW * 4));   // [kMaxWindows | up to 2 * kMaxWindows results]
+    int st;
+    if ((st = ensure_host_results((size_t)2 * kMaxWindows * XW))) return st;   // the results of one problem
     // Kernels that stage more than the default dynamic-LDS allowance get their limit raised ONCE, here, right after
     // hipSetDevice -- not lazily inside the first MSM and not on every MSM.  static + dynamic LDS is checked against
     // the device's per-workgroup LDS, so a kernel that cannot launch fails context creation with its name.
-    int st;
     if ((st = raise_lds_limit((const void*)k_fine, "k_fine", kFineLds))) return st;
     if ((st = raise_sort_limits<false, 0>()) || (st = raise_sort_limits<false, 16>()) || (st = raise_sort_limits<false, 17>())) return st;
     if constexpr (Fr::HAS_GLV) {
@@ -215,17 +252,12 @@ class Engine : public IEngine {
     return MSMZ_OK;
   }
 
-  ~Engine() override {
+  ~Engine() override {   // (the device buffers and handles free themselves after this, on this device)
     (void)hipSetDevice(device_);
-    for (auto& kv : handles_) (void)hipFree(kv.second.dev);
-    for (DevBuf* b : {&bsum_, &f2desc_, &tilecnt_, &tileoff_, &final_, &desc_, &bfin_, &packed_, &bins_, &digits_, &counts_, &off_, &cursor_, &refs_, &rscan_, &partials_, &slots_, &red_[0], &red_[1],
-                      &red_[2], &red_[3], &meta_, &stage_, &gen_table_})
-      b->release();
     if (h_meta_) (void)hipHostFree(h_meta_);
-    if (h_final_) (void)hipHostFree(h_final_);
-    if (h_bfinal_) (void)hipHostFree(h_bfinal_);
-    for (auto& e : ev_)
-      if (e) (void)hipEventDestroy(e);
+    if (h_res_) (void)hipHostFree(h_res_);
+    for (hipEvent_t* e : ev_.all())
+      if (*e) (void)hipEventDestroy(*e);
     if (stream_) (void)hipStreamDestroy(stream_);
   }
 
@@ -260,52 +292,39 @@ class Engine : public IEngine {
       if ((st = copy_h2d(d_inf, inf, 1, n, split))) return st;
     }
     const bool endo = Cfg::HAS_ENDO;
-    void* dev = nullptr;
-    MSMZ_HIP(hipMalloc(&dev, (size_t)n * PW_WORDS * 4 * (endo ? 2 : 1)));
+    Handle hd{0, n, endo};
+    if ((st = alloc_handle(hd, (size_t)n * PW_WORDS * 4 * (endo ? 2 : 1)))) return st;
     MsmMeta* d_meta = meta_.as<MsmMeta>();
     MSMZ_HIP(hipMemsetAsync(&d_meta->error, 0, 4, stream_));
     if constexpr (TE) {
-      hipLaunchKernelGGL((k_te_points_to_niels<F>), dim3((n + 255) / 256), dim3(256), 0, stream_, (uint32_t*)dev,
+      hipLaunchKernelGGL((k_te_points_to_niels<F>), dim3((n + 255) / 256), dim3(256), 0, stream_, hd.mem.as<uint32_t>(),
                          stage_.as<uint32_t>(), (uint32_t)n, &d_meta->error);
     } else {
-      hipLaunchKernelGGL((k_points_to_mont<F>), dim3((n + 255) / 256), dim3(256), 0, stream_, (uint32_t*)dev,
+      hipLaunchKernelGGL((k_points_to_mont<F>), dim3((n + 255) / 256), dim3(256), 0, stream_, hd.mem.as<uint32_t>(),
                          stage_.as<uint32_t>(), d_inf, (uint32_t)n, endo ? 1 : 0, &d_meta->error);
     }
     MSMZ_HIP(hipGetLastError());
     MSMZ_HIP(hipMemcpyAsync(&h_meta_->error, &d_meta->error, 4, hipMemcpyDeviceToHost, stream_));
     MSMZ_HIP(hipStreamSynchronize(stream_));
-    if (h_meta_->error) {   // a coordinate >= p
-      (void)hipFree(dev);
-      return MSMZ_ERR_RANGE;
-    }
-    *h = next_handle_++;
-    handles_[*h] = Handle{0, n, endo, dev};
-    return MSMZ_OK;
+    if (h_meta_->error) return MSMZ_ERR_RANGE;   // a coordinate >= p
+    return add_handle(std::move(hd), h);
   }
 
   int upload_scalars(const uint8_t* s, uint64_t n, uint64_t* h, const GenMap* split = nullptr) override {
     if (!s || !h || n == 0) return MSMZ_ERR_ARG;
     MSMZ_HIP(hipSetDevice(device_));
-    void* dev = nullptr;
-    MSMZ_HIP(hipMalloc(&dev, n * 32));
-    if (int st = copy_h2d(dev, s, 32, n, split)) {
-      (void)hipFree(dev);
-      return st;
-    }
+    Handle hd{1, n, false};
+    int st;
+    if ((st = alloc_handle(hd, n * 32)) || (st = copy_h2d(hd.mem.p, s, 32, n, split))) return st;
     MsmMeta* d_meta = meta_.as<MsmMeta>();
     MSMZ_HIP(hipMemsetAsync(&d_meta->error, 0, 4, stream_));
     hipLaunchKernelGGL((k_check_scalars<Fr>), dim3((n + 255) / 256), dim3(256), 0, stream_, &d_meta->error,
-                       (const uint32_t*)dev, (uint32_t)n);
+                       hd.mem.as<const uint32_t>(), (uint32_t)n);
     MSMZ_HIP(hipGetLastError());
     MSMZ_HIP(hipMemcpyAsync(&h_meta_->error, &d_meta->error, 4, hipMemcpyDeviceToHost, stream_));
     MSMZ_HIP(hipStreamSynchronize(stream_));
-    if (h_meta_->error) {   // a scalar >= group order
-      (void)hipFree(dev);
-      return MSMZ_ERR_RANGE;
-    }
-    *h = next_handle_++;
-    handles_[*h] = Handle{1, n, false, dev};
-    return MSMZ_OK;
+    if (h_meta_->error) return MSMZ_ERR_RANGE;   // a scalar >= group order
+    return add_handle(std::move(hd), h);
   }
 
   int random_points(uint64_t n, uint64_t seed, const GenMap& map, uint64_t* h) override {
@@ -314,33 +333,41 @@ class Engine : public IEngine {
     int st = ensure_gen_table();
     if (st) return st;
     const bool endo = Cfg::HAS_ENDO;
-    void* dev = nullptr;
-    MSMZ_HIP(hipMalloc(&dev, (size_t)n * PW_WORDS * 4 * (endo ? 2 : 1)));
+    Handle hd{0, n, endo};
+    if ((st = alloc_handle(hd, (size_t)n * PW_WORDS * 4 * (endo ? 2 : 1)))) return st;
     if constexpr (TE) {
-      hipLaunchKernelGGL((k_te_gen_points<F>), dim3((n + 127) / 128), dim3(128), 0, stream_, (uint32_t*)dev,
+      hipLaunchKernelGGL((k_te_gen_points<F>), dim3((n + 127) / 128), dim3(128), 0, stream_, hd.mem.as<uint32_t>(),
                          gen_table_.as<uint32_t>(), (uint32_t)n, seed, map);
     } else {
-      hipLaunchKernelGGL((k_gen_points<F>), dim3((n + 127) / 128), dim3(128), 0, stream_, (uint32_t*)dev,
+      hipLaunchKernelGGL((k_gen_points<F>), dim3((n + 127) / 128), dim3(128), 0, stream_, hd.mem.as<uint32_t>(),
                          gen_table_.as<uint32_t>(), (uint32_t)n, seed, endo ? 1 : 0, map);
     }
     MSMZ_HIP(hipGetLastError());
     MSMZ_HIP(hipStreamSynchronize(stream_));
-    *h = next_handle_++;
-    handles_[*h] = Handle{0, n, endo, dev};
-    return MSMZ_OK;
+    return add_handle(std::move(hd), h);
   }
 
   int random_scalars(uint64_t n, uint64_t seed, const GenMap& map, uint64_t* h) override {
     if (!h || n == 0) return MSMZ_ERR_ARG;
     MSMZ_HIP(hipSetDevice(device_));
-    void* dev = nullptr;
-    MSMZ_HIP(hipMalloc(&dev, n * 32));
-    hipLaunchKernelGGL((k_gen_scalars<Fr>), dim3((n + 255) / 256), dim3(256), 0, stream_, (uint32_t*)dev, (uint32_t)n,
-                       seed, map);
+    Handle hd{1, n, false};
+    if (int st = alloc_handle(hd, n * 32)) return st;
+    hipLaunchKernelGGL((k_gen_scalars<Fr>), dim3((n + 255) / 256), dim3(256), 0, stream_, hd.mem.as<uint32_t>(),
+                       (uint32_t)n, seed, map);
     MSMZ_HIP(hipGetLastError());
     MSMZ_HIP(hipStreamSynchronize(stream_));
+    return add_handle(std::move(hd), h);
+  }
+
+  // the device memory of a new handle (owned by it: an error before add_handle frees it)
+  int alloc_handle(Handle& hd, size_t bytes) {
+    MSMZ_HIP(hipMalloc(&hd.mem.p, bytes));
+    hd.mem.bytes = bytes;
+    return MSMZ_OK;
+  }
+  int add_handle(Handle&& hd, uint64_t* h) {
     *h = next_handle_++;
-    handles_[*h] = Handle{1, n, false, dev};
+    handles_.emplace(*h, std::move(hd));
     return MSMZ_OK;
   }
 
@@ -359,10 +386,10 @@ class Engine : public IEngine {
     if (st) return st;
     if constexpr (TE) {
       hipLaunchKernelGGL((k_te_points_from_niels<F>), dim3((count + 255) / 256), dim3(256), 0, stream_,
-                         stage_.as<uint32_t>(), (const uint32_t*)it->second.dev + first * PW_WORDS, (uint32_t)count);
+                         stage_.as<uint32_t>(), it->second.mem.template as<const uint32_t>() + first * PW_WORDS, (uint32_t)count);
     } else {
       hipLaunchKernelGGL((k_points_from_mont<F>), dim3((count + 255) / 256), dim3(256), 0, stream_,
-                         stage_.as<uint32_t>(), (const uint32_t*)it->second.dev + first * PW_WORDS, (uint32_t)count);
+                         stage_.as<uint32_t>(), it->second.mem.template as<const uint32_t>() + first * PW_WORDS, (uint32_t)count);
     }
     MSMZ_HIP(hipGetLastError());
     MSMZ_HIP(hipMemcpyAsync(xy, stage_.p, count * RW * 4, hipMemcpyDeviceToHost, stream_));
@@ -383,7 +410,7 @@ class Engine : public IEngine {
     if (first > it->second.n || count > it->second.n - first) return MSMZ_ERR_ARG;
     if (count == 0) return MSMZ_OK;
     MSMZ_HIP(hipSetDevice(device_));
-    MSMZ_HIP(hipMemcpy(s, (const uint8_t*)it->second.dev + first * 32, count * 32, hipMemcpyDeviceToHost));
+    MSMZ_HIP(hipMemcpy(s, it->second.mem.template as<const uint8_t>() + first * 32, count * 32, hipMemcpyDeviceToHost));
     return MSMZ_OK;
   }
 
@@ -391,7 +418,6 @@ class Engine : public IEngine {
     auto it = handles_.find(hd);
     if (it == handles_.end()) return MSMZ_ERR_ARG;
     (void)hipSetDevice(device_);
-    (void)hipFree(it->second.dev);
     handles_.erase(it);
     return MSMZ_OK;
   }
@@ -429,34 +455,26 @@ class Engine : public IEngine {
     MSMZ_HIP(hipSetDevice(device_));
     const uint64_t R = n * (glv ? 2 : 1);
     const size_t rec = (size_t)PW_WORDS * 4;
-    void* dev = nullptr;
-    MSMZ_HIP(hipMalloc(&dev, (size_t)copies * R * rec));
+    Handle hd{0, n, glv != 0};
+    if (int st = alloc_handle(hd, (size_t)copies * R * rec)) return st;
+    uint8_t* dev = hd.mem.as<uint8_t>();
     // copy 0: the source's first n points (and their images, which follow the source's whole set)
-    hipError_t e = hipMemcpyAsync(dev, src.dev, n * rec, hipMemcpyDeviceToDevice, stream_);
-    if (e == hipSuccess && glv)
-      e = hipMemcpyAsync((uint8_t*)dev + n * rec, (const uint8_t*)src.dev + src.n * rec, n * rec, hipMemcpyDeviceToDevice,
-                         stream_);
-    for (uint32_t j = 1; j < copies && e == hipSuccess; j++) {
+    MSMZ_HIP(hipMemcpyAsync(dev, src.mem.p, n * rec, hipMemcpyDeviceToDevice, stream_));
+    if (glv)
+      MSMZ_HIP(hipMemcpyAsync(dev + n * rec, src.mem.template as<const uint8_t>() + src.n * rec, n * rec,
+                              hipMemcpyDeviceToDevice, stream_));
+    for (uint32_t j = 1; j < copies; j++) {
       if constexpr (!TE)
         hipLaunchKernelGGL((k_precompute_copy<F>), dim3((n + 255) / 256), dim3(256), 0, stream_,
-                           (uint32_t*)((uint8_t*)dev + j * R * rec), (const uint32_t*)((const uint8_t*)dev + (j - 1) * R * rec),
-                           (uint32_t)n, c, glv);
-      e = hipGetLastError();
+                           (uint32_t*)(dev + j * R * rec), (const uint32_t*)(dev + (j - 1) * R * rec), (uint32_t)n, c, glv);
+      MSMZ_HIP(hipGetLastError());
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
-    if (e != hipSuccess) {
-      fprintf(stderr, "msmz: HIP error '%s' while precomputing a point set\n", hipGetErrorString(e));
-      (void)hipFree(dev);
-      return MSMZ_ERR_HIP;
-    }
-    Handle hd{0, n, glv != 0, dev};
+    MSMZ_HIP(hipStreamSynchronize(stream_));
     hd.factor = copies;
     hd.c = c;
     hd.glv = glv;
     hd.copy_stride = R;
-    *h = next_handle_++;
-    handles_[*h] = hd;
-    return MSMZ_OK;
+    return add_handle(std::move(hd), h);
   }
 
   int precomputed_info(uint64_t hd, int32_t* c, int32_t* glv, uint32_t* factor, uint32_t* K, uint64_t* records) override {
@@ -473,61 +491,10 @@ class Engine : public IEngine {
   }
 
   // ------------------------------------------------------------------------------------------ msm
-  int msm(uint64_t ph, const uint8_t* host_scalars, uint64_t sh, uint64_t n, const msmz_opts* o, uint8_t* out,
-          int* out_inf, msmz_log* log, const GenMap* split = nullptr) override {
-    return msm_batch(ph, host_scalars, sh, n, 1, o, out, out_inf, log, split);
-  }
-
-  // run(extra_bits): a GLV half longer than the assumed 127 bits (k_hist flags it) redoes the MSM with windows for the
-  // PROVEN bound (Fr::GLV_PROVEN_BITS, tools/gen_constants.py), which no half can exceed -- a second flag is an
-  // internal error
-  template <class Run>
-  int glv_retry(Run run) {
-    int st = run(0);
-    if (st != MSMZ_ERR_RETRY_BITS) return st;
-    retries_++;
-    st = run(1);
-    return st == MSMZ_ERR_RETRY_BITS ? MSMZ_ERR_ARG : st;
-  }
-
-  // one MSM over device scalars (log: zeroed by the caller, or null)
-  int msm_passes(const Handle& pts, const uint32_t* d_scalars, uint64_t n, const msmz_opts& opt, uint8_t* out,
-                 int* out_inf, msmz_log* log) {
-    // Inputs beyond what one pass sorts (2^24 entries; 2^23 points with GLV) run as consecutive index ranges whose
-    // partial sums are added on the host -- the same additivity the multi-GPU split uses.
-    const uint64_t per_pass = (opt.glv != 0 && !TE) ? kMaxEntriesPerPass / 2 : kMaxEntriesPerPass;
-    int st = MSMZ_OK;
-    uint8_t part[RW * 4];
-    for (uint64_t done = 0; done < n && st == MSMZ_OK; done += per_pass) {
-      const uint64_t cnt = n - done < per_pass ? n - done : per_pass;
-      const uint32_t* d_points = (const uint32_t*)pts.dev + done * PW_WORDS;
-      const uint32_t* d_sc = d_scalars + done * 8;
-      int pinf = 0;
-      msmz_log plog;
-      msmz_log* lp = log ? &plog : nullptr;
-      if (lp) memset(lp, 0, sizeof(*lp));
-      st = glv_retry([&](int extra_bits) {
-        return Cfg::run_msm(*this, pts, d_points, d_sc, cnt, opt, done == 0 ? out : part, done == 0 ? out_inf : &pinf, lp,
-                            extra_bits);
-      });
-      if (st) break;
-      if (done > 0) {
-        uint8_t acc[RW * 4];
-        memcpy(acc, out, sizeof(acc));
-        const int ai = *out_inf;
-        st = host_point_add<F, TE>(acc, ai, part, pinf, out, out_inf);
-      }
-      if (log) merge_log(log, plog, done == 0);
-    }
-    return st;
-  }
-
-  // ------------------------------------------------------------------------------------------ batched msm
   // `batch` MSMs over the first n points: problem k's scalars are entries [k n, (k + 1) n) of the resident set `sh`, or
   // vector k of the host buffer (at host_scalars + k host_stride 32; host_stride = n unless a multi-device context hands
-  // this engine its share `split` of longer vectors).  Weierstrass batched-affine plans run as ONE batched pipeline per
-  // sub-batch (msm_weierstrass_affine with nprob > 1); twisted Edwards, projective buckets, the affine first reduction
-  // level and inputs beyond one sort pass run the problems one by one.
+  // this engine its share `split` of longer vectors).  batch = 1 is msmz_msm.  Sub-batches run one after another
+  // (run_problems decides how each runs), their logs summed.
   int msm_batch(uint64_t ph, const uint8_t* host_scalars, uint64_t sh, uint64_t n, uint32_t batch, const msmz_opts* o,
                 uint8_t* out, int* out_inf, msmz_log* log, const GenMap* split = nullptr,
                 uint64_t host_stride = 0) override {
@@ -560,34 +527,20 @@ class Engine : public IEngine {
     } else {
       auto sit = handles_.find(sh);
       if (sit == handles_.end() || sit->second.kind != 1 || sit->second.n < total) return MSMZ_ERR_ARG;
-      d_scalars = (const uint32_t*)sit->second.dev;
+      d_scalars = sit->second.mem.template as<const uint32_t>();
     }
     if (log) memset(log, 0, sizeof(*log));
     const Handle& pts = pit->second;
-    const uint64_t per_pass = (opt.glv != 0 && !TE) ? kMaxEntriesPerPass / 2 : kMaxEntriesPerPass;
-    const bool batched = !TE && opt.buckets != MSMZ_BUCKETS_PROJECTIVE && opt.reserved[0] != 1 && n <= per_pass &&
-                         batch > 1;
     int st = MSMZ_OK;
     for (uint32_t done = 0; done < batch && st == MSMZ_OK;) {
-      uint32_t bs = batched ? planner_.batch_size(n, opt, (uint32_t)pts.n, pts.factor, batch - done) : 1;
-      const uint32_t* d_sc = d_scalars + (size_t)done * n * 8;
       msmz_log plog;
-      msmz_log* lp = log ? &plog : nullptr;
-      if (lp) memset(lp, 0, sizeof(*lp));
-      if (bs > 1) {
-        st = glv_retry([&](int extra_bits) {   // (a GLV half longer than assumed: the whole sub-batch again)
-          return msm_weierstrass_affine(pts, (const uint32_t*)pts.dev, d_sc, n, opt, out + (size_t)done * RW * 4,
-                                        out_inf + done, lp, extra_bits, bs);
-        });
-        if (st == MSMZ_ERR_BATCH_LOOP) {
-          bs = 1;
-          st = MSMZ_OK;
-        }
-      }
-      if (bs == 1) st = msm_passes(pts, d_sc, n, opt, out + (size_t)done * RW * 4, out_inf + done, lp);
+      memset(&plog, 0, sizeof(plog));
+      uint32_t ran = 0;
+      st = run_problems(pts, d_scalars + (size_t)done * n * 8, n, batch - done, opt, out + (size_t)done * RW * 4,
+                        out_inf + done, log ? &plog : nullptr, &ran);
       if (st) break;
-      if (log) merge_log(log, plog, done == 0);
-      done += bs;
+      if (log) merge_log(log, plog, done == 0, LogMerge::SEQUENTIAL);
+      done += ran;
     }
     if (log) {
       log->stage_ms[MSMZ_ST_TOTAL] =
@@ -596,19 +549,70 @@ class Engine : public IEngine {
     return st;
   }
 
-  static void merge_log(msmz_log* total, const msmz_log& part, bool first) {
-    if (first) {
-      *total = part;
-      return;
+  // How a shape runs is decided here.  Up to `remaining` problems over device scalars; *ran = how many it ran.
+  //  - one batched pipeline over a sub-batch of them (planner_.batch_size): Weierstrass batched-affine buckets with the
+  //    2-D reduction, n within one sort pass, and a sub-batch plan the two-level sort takes -- a plan that falls off it
+  //    (also only after the GLV retry) runs the first problem alone and the rest is decided again;
+  //  - else the first problem alone over consecutive index ranges of at most one sort pass (2^24 entries; 2^23 points
+  //    with GLV) whose partial sums are folded on the host -- the same additivity the multi-GPU split uses -- each range
+  //    with batched-affine buckets (Weierstrass) or msmBasic (projective buckets, twisted Edwards).
+  int run_problems(const Handle& pts, const uint32_t* d_scalars, uint64_t n, uint32_t remaining, const msmz_opts& opt,
+                   uint8_t* out, int* out_inf, msmz_log* log, uint32_t* ran) {
+    const bool basic = TE || opt.buckets == MSMZ_BUCKETS_PROJECTIVE;
+    const uint64_t per_pass = (opt.glv != 0 && !TE) ? kMaxEntriesPerPass / 2 : kMaxEntriesPerPass;
+    *ran = 1;
+    const uint32_t bs = !basic && opt.reserved[0] != 1 && n <= per_pass && remaining > 1
+                            ? planner_.batch_size(n, opt, (uint32_t)pts.n, pts.factor, remaining)
+                            : 1;
+    if (bs > 1) {
+      Redo redo = Redo::NONE;   // (a GLV half longer than assumed: the whole sub-batch again)
+      const int st = glv_retry(&redo, [&](int extra_bits, Redo* r) {
+        return msm_weierstrass_affine(pts, pts.mem.template as<const uint32_t>(), d_scalars, n, opt, out, out_inf, log,
+                                      extra_bits, bs, r);
+      });
+      if (st || redo != Redo::PER_PROBLEM) {
+        *ran = bs;
+        return st;
+      }
     }
-    for (int i = 0; i < MSMZ_N_STAGES; i++) total->stage_ms[i] += part.stage_ms[i];
-    for (int i = 0; i < 32; i++) total->batch_add_ms[i] += part.batch_add_ms[i];
-    total->n_entries += part.n_entries;
-    total->n_pairs += part.n_pairs;
-    total->scatter_kernel_ms += part.scatter_kernel_ms;
-    total->scatter_launches += part.scatter_launches;
-    if (part.max_bucket > total->max_bucket) total->max_bucket = part.max_bucket;
-    if (part.rounds > total->rounds) total->rounds = part.rounds;
+    uint8_t part[RW * 4];
+    int st = MSMZ_OK;
+    for (uint64_t done = 0; done < n && st == MSMZ_OK; done += per_pass) {
+      const uint64_t cnt = n - done < per_pass ? n - done : per_pass;
+      const uint32_t* d_points = pts.mem.template as<const uint32_t>() + done * PW_WORDS;
+      const uint32_t* d_sc = d_scalars + done * 8;
+      int pinf = 0;
+      msmz_log plog;
+      msmz_log* lp = log ? &plog : nullptr;
+      if (lp) memset(lp, 0, sizeof(*lp));
+      uint8_t* o = done == 0 ? out : part;
+      int* oi = done == 0 ? out_inf : &pinf;
+      if (basic) {
+        st = msm_basic(pts, d_points, d_sc, cnt, opt, o, oi, lp);
+      } else {
+        Redo redo = Redo::NONE;
+        st = glv_retry(&redo, [&](int extra_bits, Redo* r) {
+          return msm_weierstrass_affine(pts, d_points, d_sc, cnt, opt, o, oi, lp, extra_bits, 1, r);
+        });
+      }
+      if (st) break;
+      if (done > 0) st = fold_partial(curve_id_, RW * 4, out, out_inf, part, pinf);
+      if (log) merge_log(log, plog, done == 0, LogMerge::SEQUENTIAL);
+    }
+    return st;
+  }
+
+  // attempt(extra_bits, &redo): a GLV half longer than the assumed 127 bits (k_hist flags it) redoes the MSM with
+  // windows for the PROVEN bound (Fr::GLV_PROVEN_BITS, tools/gen_constants.py), which no half can exceed -- a second
+  // flag is an internal error.  *redo: what the last attempt asks beyond that (Redo::PER_PROBLEM).
+  template <class Attempt>
+  int glv_retry(Redo* redo, Attempt attempt) {
+    int st = attempt(0, redo);
+    if (*redo != Redo::PROVEN_BITS) return st;
+    retries_++;
+    *redo = Redo::NONE;
+    st = attempt(1, redo);
+    return *redo == Redo::PROVEN_BITS ? MSMZ_ERR_ARG : st;
   }
 
   // ------------------------------------------------------------------------------------------ stage-level test hooks
@@ -721,28 +725,25 @@ class Engine : public IEngine {
     Plan pl;
     int st = pr.make_plan(pl, n, glv != 0, opt, (uint32_t)n, !TE);
     if (st) return st;
-    void* d_scalars = nullptr;
-    MSMZ_HIP(hipMalloc(&d_scalars, 32 * n));
-    MSMZ_HIP(hipMemcpyAsync(d_scalars, s, 32 * n, hipMemcpyHostToDevice, stream_));
-    st = sort_phase(pl, pr.sort_layout(pl), (const uint32_t*)d_scalars);
-    if (!st) st = fetch_meta(pl);
-    if (!st && (h_meta_->error & 4u)) st = MSMZ_ERR_RANGE;
-    if (!st) {
-      const uint32_t g8[8] = {(uint32_t)pl.c, (uint32_t)pl.K, (uint32_t)pl.Keff, pl.L, pl.nb, pl.n_entries, pl.max_bucket,
-                              (uint32_t)pl.spread};
-      memcpy(geom, g8, sizeof(g8));
-      if (off) {
-        if (off_cap < (uint64_t)pl.nb + 1) st = MSMZ_ERR_ARG;
-        else if (hipMemcpy(off, off_.p, ((size_t)pl.nb + 1) * 4, hipMemcpyDeviceToHost) != hipSuccess) st = MSMZ_ERR_HIP;
-      }
-      if (!st && refs) {
-        if (refs_cap < pl.n_entries) st = MSMZ_ERR_ARG;
-        else if (pl.n_entries && hipMemcpy(refs, refs_.p, (size_t)pl.n_entries * 4, hipMemcpyDeviceToHost) != hipSuccess)
-          st = MSMZ_ERR_HIP;
-      }
+    DevBuf d_scalars;   // (freed on every return)
+    MSMZ_HIP(hipMalloc(&d_scalars.p, 32 * n));
+    MSMZ_HIP(hipMemcpyAsync(d_scalars.p, s, 32 * n, hipMemcpyHostToDevice, stream_));
+    Run run = new_run(opt);
+    if ((st = sort_phase(pl, pr.sort_layout(pl), d_scalars.as<const uint32_t>(), run, 0)) || (st = fetch_meta(run)))
+      return st;
+    if (h_meta_->error & 4u) return MSMZ_ERR_RANGE;
+    const uint32_t g8[8] = {(uint32_t)pl.c, (uint32_t)pl.K, (uint32_t)pl.Keff, pl.L, pl.nb, run.n_entries, run.max_bucket,
+                            (uint32_t)pl.spread};
+    memcpy(geom, g8, sizeof(g8));
+    if (off) {
+      if (off_cap < (uint64_t)pl.nb + 1) return MSMZ_ERR_ARG;
+      MSMZ_HIP(hipMemcpy(off, off_.p, ((size_t)pl.nb + 1) * 4, hipMemcpyDeviceToHost));
     }
-    (void)hipFree(d_scalars);
-    return st;
+    if (refs) {
+      if (refs_cap < run.n_entries) return MSMZ_ERR_ARG;
+      if (run.n_entries) MSMZ_HIP(hipMemcpy(refs, refs_.p, (size_t)run.n_entries * 4, hipMemcpyDeviceToHost));
+    }
+    return MSMZ_OK;
   }
 
   int test_point(int op, const uint8_t* a, const uint8_t* a_inf, const uint8_t* b, const uint8_t* b_inf, uint64_t n,
@@ -804,21 +805,26 @@ class Engine : public IEngine {
   }
 
   // ------------------------------------------------------------------------------------------ shared phases
-  void mark(Plan& pl) {
-    if (pl.timing && pl.ei < kMaxEvents) (void)hipEventRecord(ev_[pl.ei], stream_);
-    pl.ei++;
+  Run new_run(const msmz_opts& opt) const {
+    Run run;
+    run.timing = opt.timing != 0;
+    run.ev = ev_;
+    return run;
   }
-  float elapsed(int a, int b2) {
+  void mark(const Run& run, hipEvent_t e) {
+    if (run.timing) (void)hipEventRecord(e, stream_);
+  }
+  static float elapsed(hipEvent_t a, hipEvent_t b) {
     float ms = 0;
-    if (a >= 0 && b2 >= 0 && a < kMaxEvents && b2 < kMaxEvents) (void)hipEventElapsedTime(&ms, ev_[a], ev_[b2]);
+    (void)hipEventElapsedTime(&ms, a, b);
     return ms;
   }
 
-  // scalars -> sorted references `refs_` + bucket offsets `off_` (+ meta->max_bucket); events 0..4.  No host round trip.
-  // pl.nprob > 1 (batched MSM): problem p reads scalars [p n, (p + 1) n); its bins follow problem p - 1's in ONE exclusive
-  // scan, so refs_ / off_ come out as one dense sort of pl.nprob * nb buckets.  The two-level sort only.
-  // `sl`: the planner's sort layout of pl.
-  int sort_phase(Plan& pl, const SortLayout& sl, const uint32_t* d_scalars) {
+  // scalars -> sorted references `refs_` + bucket offsets `off_` (+ meta->max_bucket); the sort's stage events.  No host
+  // round trip.  pl.nprob > 1 (batched MSM): problem p reads scalars [p n, (p + 1) n); its bins follow problem p - 1's in
+  // ONE exclusive scan, so refs_ / off_ come out as one dense sort of pl.nprob * nb buckets.  The two-level sort only.
+  // `sl`: the planner's sort layout of pl; copy_stride: records per copy of a precomputed point set.
+  int sort_phase(const Plan& pl, const SortLayout& sl, const uint32_t* d_scalars, Run& run, uint32_t copy_stride) {
     const uint32_t n = pl.n, M = pl.M, nb = pl.nb, nblocks = pl.nblocks, P = pl.nprob;
     const int c = pl.c, K = pl.K;
     int st;
@@ -837,7 +843,7 @@ class Engine : public IEngine {
       if ((st = counts_.ensure(pbins * 4))) return st;
       uint32_t* d_counts = counts_.as<uint32_t>();
       MSMZ_HIP(hipMemsetAsync(d_counts, 0, pbins * 4, stream_));
-      mark(pl);  // 0
+      mark(run, run.ev.sort0);
       const uint32_t per_tile = pl.glv ? COARSE_TILE / 2 : COARSE_TILE;   // scalars per workgroup (k_hist and k_coarse)
       const uint32_t tiles = (n + per_tile - 1) / per_tile;
       if ((st = tilecnt_.ensure((size_t)P * tiles * nbins * 2))) return st;
@@ -870,7 +876,7 @@ class Engine : public IEngine {
         }
       };
       dispatch_sort(false);
-      mark(pl);  // 1
+      mark(run, run.ev.hist_end);
       MSMZ_HIP(hipGetLastError());
       if (pbins <= (size_t)SORT_MAX_BINS) {
         hipLaunchKernelGGL(k_bin_scan, dim3(1), dim3(1024), 0, stream_, bins_.as<uint32_t>(), d_counts, (uint32_t)pbins,
@@ -885,17 +891,16 @@ class Engine : public IEngine {
         hipLaunchKernelGGL(k_scan_apply, dim3(sblocks, 1), dim3(SCAN_T), 0, stream_, bins_.as<uint32_t>(),
                            partials_.as<uint32_t>(), d_counts, (uint32_t)pbins, 0, sblocks, (size_t)0, (uint32_t*)nullptr);
       }
-      mark(pl);  // 2
+      mark(run, run.ev.scan_end);
       MSMZ_HIP(hipGetLastError());
       dispatch_sort(true);
-      pl.ev_coarse = pl.ei;
-      mark(pl);  // 3
+      mark(run, run.ev.coarse_end);
       MSMZ_HIP(hipGetLastError());
       {
         const size_t lds = kFineLds;
         hipLaunchKernelGGL(k_fine, dim3(fbins, P), dim3(FINE_T), lds, stream_, refs_.as<uint32_t>(), off_.as<uint32_t>(),
                            &d_meta->max_bucket, packed_.as<uint32_t>(), bins_.as<uint32_t>(), g.fb, g.fbt, sl.fine_top,
-                           fbins, g.idx_bits, n_half, pl.endo_delta, g.F, g.mbits, pl.copy_stride);
+                           fbins, g.idx_bits, n_half, pl.endo_delta, g.F, g.mbits, copy_stride);
       }
 #ifdef MSMZ_TRACE
       // development aid: workgroup time stamps of k_coarse / k_fine (tools/wg_timeline.py)
@@ -913,7 +918,7 @@ class Engine : public IEngine {
       MSMZ_HIP(hipMemsetAsync(counts_.p, 0, ((size_t)nb + 1) * 4, stream_));
       MSMZ_HIP(hipMemsetAsync(cursor_.p, 0, (size_t)nb * 4, stream_));
       const uint32_t dgrid = (n + 256 * DIGITS_ITEMS - 1) / (256 * DIGITS_ITEMS);
-      mark(pl);  // 0
+      mark(run, run.ev.sort0);
       if (pl.glv) {
         if constexpr (Fr::HAS_GLV)
           hipLaunchKernelGGL((k_digits<Fr, true>), dim3(dgrid), dim3(256), 0, stream_, digits_.as<uint32_t>(),
@@ -922,7 +927,7 @@ class Engine : public IEngine {
         hipLaunchKernelGGL((k_digits<Fr, false>), dim3(dgrid), dim3(256), 0, stream_, digits_.as<uint32_t>(),
                            counts_.as<uint32_t>(), d_meta, d_scalars, n, c, K, pl.spread);
       }
-      mark(pl);  // 1
+      mark(run, run.ev.hist_end);
       MSMZ_HIP(hipGetLastError());
       hipLaunchKernelGGL(k_scan_partials, dim3(nblocks, 1), dim3(SCAN_T), 0, stream_, partials_.as<uint32_t>(),
                          counts_.as<uint32_t>(), nb, 0, nblocks);
@@ -931,29 +936,30 @@ class Engine : public IEngine {
       hipLaunchKernelGGL(k_scan_apply, dim3(nblocks, 1), dim3(SCAN_T), 0, stream_, off_.as<uint32_t>(),
                          partials_.as<uint32_t>(), counts_.as<uint32_t>(), nb, 0, nblocks, (size_t)0,
                          &d_meta->max_bucket);
-      mark(pl);  // 2
+      mark(run, run.ev.scan_end);
       MSMZ_HIP(hipGetLastError());
       {
         dim3 grid((M + 256 * 4 - 1) / (256 * 4), K);
         hipLaunchKernelGGL(k_scatter, grid, dim3(256), 0, stream_, refs_.as<uint32_t>(), cursor_.as<uint32_t>(),
                            off_.as<uint32_t>(), digits_.as<uint32_t>(), M, c, pl.spread, n_half, pl.endo_delta);
       }
-      pl.ev_coarse = pl.ei;
-      mark(pl);  // 3
+      mark(run, run.ev.coarse_end);
       MSMZ_HIP(hipGetLastError());
     }
-    pl.ev_sort_end = pl.ei;
-    mark(pl);  // 4
+    mark(run, run.ev.sort_end);
     MSMZ_HIP(hipGetLastError());
     return MSMZ_OK;
   }
 
   // read the device-side totals (one host round trip)
-  int fetch_meta(Plan& pl) {
+  int fetch_meta(Run& run) {
     MSMZ_HIP(hipMemcpyAsync(h_meta_, meta_.p, sizeof(MsmMeta), hipMemcpyDeviceToHost, stream_));
     MSMZ_HIP(hipStreamSynchronize(stream_));
-    pl.max_bucket = h_meta_->max_bucket;
-    pl.n_entries = h_meta_->n_entries;
+    run.max_bucket = h_meta_->max_bucket;
+    run.n_entries = h_meta_->n_entries;
+    run.rounds = h_meta_->rounds;
+    memcpy(run.round_pairs, h_meta_->round_pairs, sizeof(run.round_pairs));
+    memcpy(run.round_base, h_meta_->round_base, sizeof(run.round_base));
     return MSMZ_OK;
   }
 
@@ -998,20 +1004,14 @@ class Engine : public IEngine {
   }
 
   // copy the window results of all pl.nprob problems (the C entries of the last level; its rows are multiples of the
-  // weight unit and not needed) and the meta block to the host: one problem's behind h_final_'s first kMaxWindows
-  // records, a batch's to h_bfinal_
-  int fetch_window_sums(const Plan& pl, size_t per_problem, const uint32_t** res) {
+  // weight unit and not needed) to h_res_, and the meta block to the host
+  int fetch_window_sums(const Plan& pl, size_t per_problem) {
     const size_t words = pl.nprob * per_problem * XW;
-    uint32_t* dst = h_final_ + (size_t)kMaxWindows * XW;
-    if (pl.nprob > 1) {
-      if (int st = ensure_batch_final(words)) return st;
-      dst = h_bfinal_;
-    }
+    if (int st = ensure_host_results(words)) return st;
     MSMZ_HIP(hipGetLastError());
-    MSMZ_HIP(hipMemcpyAsync(dst, final_.p, words * 4, hipMemcpyDeviceToHost, stream_));
+    MSMZ_HIP(hipMemcpyAsync(h_res_, final_.p, words * 4, hipMemcpyDeviceToHost, stream_));
     MSMZ_HIP(hipMemcpyAsync(h_meta_, meta_.p, sizeof(MsmMeta), hipMemcpyDeviceToHost, stream_));
     MSMZ_HIP(hipStreamSynchronize(stream_));
-    *res = dst;
     return MSMZ_OK;
   }
 
@@ -1031,21 +1031,18 @@ class Engine : public IEngine {
 
   // The end of every MSM, after its bucket reduction: fetch the window results (two_d: two per bucket set, else one),
   // combine each problem's on the host (msm-batched-affine.ts:300-322) and fill the log.
-  int finish_msm(Plan& pl, bool two_d, uint8_t* out, int* out_inf, msmz_log* log, int R, uint64_t n_pairs, int ev_plan0,
-                 int ev_plan1, int ev_acc_end, int round_ev0) {
-    const int ev_red_end = pl.ei;
-    mark(pl);
+  int finish_msm(const Plan& pl, Run& run, bool two_d, uint8_t* out, int* out_inf, msmz_log* log) {
+    mark(run, run.ev.red_end);
     const size_t per_problem = (size_t)(two_d ? 2 : 1) * pl.Keff;
     // (the terms are listed while the device still reduces)
     const std::vector<WindowTerm> terms =
         window_terms(pl.c, pl.K, pl.Keff, (int)pl.F, two_d ? planner_.split_2d(pl).b : -1, pl.fold_shift != 0);
-    const uint32_t* res;
-    int st = fetch_window_sums(pl, per_problem, &res);
+    int st = fetch_window_sums(pl, per_problem);
     if (st) return st;
     const auto t_host = std::chrono::steady_clock::now();
     if (h_meta_->error & 1u) return MSMZ_ERR_DEGENERATE;
     for (uint32_t p = 0; p < pl.nprob; p++) {
-      const uint32_t* rp = res + p * per_problem * XW;
+      const uint32_t* rp = h_res_ + p * per_problem * XW;
       uint32_t w[RW];
       if constexpr (TE) {
         te_to_affine_canon<F>(w, host_horner(HostTe{}, terms, rp, XW));
@@ -1059,7 +1056,7 @@ class Engine : public IEngine {
       memcpy(out + (size_t)p * RW * 4, w, sizeof(w));
     }
     const float host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_host).count();
-    fill_log(log, pl, R, n_pairs, ev_plan0, ev_plan1, ev_acc_end, ev_red_end, round_ev0, host_ms);
+    fill_log(log, pl, run, host_ms);
     return MSMZ_OK;
   }
 
@@ -1117,44 +1114,44 @@ class Engine : public IEngine {
     MSMZ_HIP(hipGetLastError());
     return MSMZ_OK;
   }
-  void fill_log(msmz_log* log, const Plan& pl, int R, uint64_t n_pairs, int ev_plan0, int ev_plan1, int ev_acc_end,
-                int ev_red_end, int round_ev0, float host_ms) {
+  // the log of one MSM (or sub-batch): its plan, its run's totals and (timed) its stage events.  scatter_kernel_ms: the
+  // scatter kernel alone (k_coarse / k_scatter), without k_fine.
+  static void fill_log(msmz_log* log, const Plan& pl, const Run& run, float host_ms) {
     if (!log) return;
     log->c = pl.c;
     log->K = pl.K;
-    log->rounds = R;
+    log->rounds = (int)run.rounds;
     log->glv = pl.glv ? 1 : 0;
-    log->n_entries = pl.n_entries;
-    log->n_pairs = n_pairs;
-    log->max_bucket = pl.max_bucket;
+    log->n_entries = run.n_entries;
+    log->n_pairs = run.n_pairs;
+    log->max_bucket = run.max_bucket;
     log->stage_ms[MSMZ_ST_FINAL] = host_ms;
-    if (!pl.timing) return;
-    log->stage_ms[MSMZ_ST_DIGITS] = elapsed(0, 1);
-    log->stage_ms[MSMZ_ST_SCAN] = elapsed(1, 2);
-    log->stage_ms[MSMZ_ST_SCATTER] = elapsed(2, pl.ev_sort_end);
-    log->scatter_kernel_ms = elapsed(2, pl.ev_coarse);
+    if (!run.timing) return;
+    const StageEvents& ev = run.ev;
+    log->stage_ms[MSMZ_ST_DIGITS] = elapsed(ev.sort0, ev.hist_end);
+    log->stage_ms[MSMZ_ST_SCAN] = elapsed(ev.hist_end, ev.scan_end);
+    log->stage_ms[MSMZ_ST_SCATTER] = elapsed(ev.scan_end, ev.sort_end);
+    log->scatter_kernel_ms = elapsed(ev.scan_end, ev.coarse_end);
     log->scatter_launches = 1;
-    log->stage_ms[MSMZ_ST_PLAN] = elapsed(ev_plan0, ev_plan1);
-    log->stage_ms[MSMZ_ST_ACCUMULATE] = elapsed(ev_plan1, ev_acc_end);
-    log->stage_ms[MSMZ_ST_REDUCE] = elapsed(ev_acc_end, ev_red_end);
-    int prev = ev_plan1, rr = 0;
-    for (int r = 0; r < R && r < 32; r++) {
-      if (h_round_pairs_[r] == 0) continue;
-      int e = round_ev0 + rr;
-      if (e >= kMaxEvents) break;
-      log->batch_add_ms[r] = elapsed(prev, e);
-      prev = e;
-      rr++;
+    log->stage_ms[MSMZ_ST_PLAN] = elapsed(ev.plan0, ev.plan_end);
+    log->stage_ms[MSMZ_ST_ACCUMULATE] = elapsed(ev.plan_end, ev.acc_end);
+    log->stage_ms[MSMZ_ST_REDUCE] = elapsed(ev.acc_end, ev.red_end);
+    hipEvent_t prev = ev.plan_end;
+    for (uint32_t r = 0; r < run.rounds && r < 32; r++) {
+      if (run.round_pairs[r] == 0) continue;
+      log->batch_add_ms[r] = elapsed(prev, ev.round_end[r]);
+      prev = ev.round_end[r];
     }
   }
 
   // ------------------------------------------------------------------------------------------ Weierstrass, affine buckets
   // nprob > 1: a batched MSM of nprob problems over the same points (scalars of problem p at d_scalars + p n 8, results
   // at out + p 2 FE_BYTES / out_inf[p]): one sort, one plan, one train of tree rounds and one two-dimensional reduction
-  // over nprob * Keff bucket sets.  MSMZ_ERR_BATCH_LOOP: this plan does not batch (msm_batch runs the problems one by one).
+  // over nprob * Keff bucket sets.  *redo: Redo::PER_PROBLEM when this plan does not batch (the two-level sort only),
+  // Redo::PROVEN_BITS when a GLV half is longer than the windows were sized for (glv_retry).
   int msm_weierstrass_affine(const Handle& pts, const uint32_t* d_points, const uint32_t* d_scalars, uint64_t n64,
-                             const msmz_opts& opt, uint8_t* out, int* out_inf, msmz_log* log, int extra_bits = 0,
-                             uint32_t nprob = 1) {
+                             const msmz_opts& opt, uint8_t* out, int* out_inf, msmz_log* log, int extra_bits,
+                             uint32_t nprob, Redo* redo) {
     const bool glv = opt.glv != 0;
     if (glv && (!Fr::HAS_GLV || !pts.has_endo)) return MSMZ_ERR_UNSUPPORTED;
     Plan pl;
@@ -1164,22 +1161,24 @@ class Engine : public IEngine {
     if (fac > 1 && (!want_2d || glv != (pts.glv != 0))) return MSMZ_ERR_UNSUPPORTED;
     int st = planner_.make_plan(pl, n64, glv, opt, (uint32_t)pts.n, true, extra_bits, want_2d, nprob, fac);
     if (st) return st;
-    pl.copy_stride = (uint32_t)pts.copy_stride;
     const SortLayout sl = planner_.sort_layout(pl);
     if (fac > 1 && !sl.two_level) return MSMZ_ERR_ARG;   // (msmz_precompute_points refuses such sets)
-    if (nprob > 1 && (!want_2d || !sl.two_level)) return MSMZ_ERR_BATCH_LOOP;
+    if (nprob > 1 && (!want_2d || !sl.two_level)) {
+      *redo = Redo::PER_PROBLEM;
+      return MSMZ_OK;
+    }
     // location words hold a record index in 30 bits
     if ((uint64_t)nprob * pl.K * pl.M >= (1ull << 30)) return MSMZ_ERR_ARG;
     // whole groups of 64 records; + the records of the batched-affine first reduction level when it is selected
     const size_t f2_records = opt.reserved[0] == 1 ? (size_t)13 * pl.Keff * ((pl.L + 1) / 2) + 256 : 0;
     if ((st = slots_.ensure(((size_t)nprob * pl.K * pl.M + 64 + f2_records) * SlotFmt<F>::WORDS * 4))) return st;
-    if ((st = sort_phase(pl, sl, d_scalars))) return st;
+    Run run = new_run(opt);
+    if ((st = sort_phase(pl, sl, d_scalars, run, (uint32_t)pts.copy_stride))) return st;
     const uint32_t nb = pl.nb * nprob;   // buckets of all problems
     MsmMeta* d_meta = meta_.as<MsmMeta>();
 
     // ---- plan: descriptors of every pair of every round + what is left of each bucket (plan_kernels.h)
-    const int ev_plan0 = pl.ei;
-    mark(pl);
+    mark(run, run.ev.plan0);
     const PlanChunks pc = planner_.plan_chunks(pl);
     const uint32_t n_chunks = pc.n_main + (nb - pc.nb_main + pc.chunk_top - 1) / pc.chunk_top;
     // chunk totals per round, then the per-workgroup scratch of the rounds beyond PLAN_RL
@@ -1198,23 +1197,21 @@ class Engine : public IEngine {
 #ifdef MSMZ_TRACE
     if ((st = trace_dump("k_plan_emit", rscan_.as<uint32_t>() + (size_t)PLAN_RMAX * n_chunks + pair_words, n_chunks, false))) return st;
 #endif
-    if ((st = fetch_meta(pl))) return st;      // the ONE host round trip before the final fetch
+    if ((st = fetch_meta(run))) return st;      // the ONE host round trip before the final fetch
     if (h_meta_->error & 4u) return MSMZ_ERR_RANGE;
-    if (h_meta_->error & 2u) return MSMZ_ERR_RETRY_BITS;
+    if (h_meta_->error & 2u) {
+      *redo = Redo::PROVEN_BITS;
+      return MSMZ_OK;
+    }
     // (a plain set's bucket holds <= M <= 2^24 entries; a precomputed set's up to W M < 2^PLAN_RMAX, which pre_fits checked)
-    if (pl.max_bucket > (pl.F > 1 ? (1u << PLAN_RMAX) - 1u : (1u << 24))) return MSMZ_ERR_ARG;
-    const int R = (int)h_meta_->rounds;
-    memcpy(h_round_pairs_, h_meta_->round_pairs, sizeof(h_round_pairs_));
-    const int ev_plan1 = pl.ei;
-    mark(pl);
-    uint64_t n_pairs = 0;
-    const int round_ev0 = pl.ei;
-    for (int r = 0; r < R; r++) n_pairs += h_round_pairs_[r];
-    for (int r = 0; r < R; r++) {
-      const uint32_t pairs = h_round_pairs_[r];
+    if (run.max_bucket > (pl.F > 1 ? (1u << PLAN_RMAX) - 1u : (1u << 24))) return MSMZ_ERR_ARG;
+    mark(run, run.ev.plan_end);
+    const uint32_t R = run.rounds;
+    for (uint32_t r = 0; r < R; r++) run.n_pairs += run.round_pairs[r];
+    for (uint32_t r = 0; r < R; r++) {
+      const uint32_t pairs = run.round_pairs[r];
       if (pairs == 0) continue;
-      launch_batch_add(pairs, opt.safe != 0, d_points, desc_.as<uint2>() + h_meta_->round_base[r], h_meta_->round_base[r],
-                       d_meta);
+      launch_batch_add(pairs, opt.safe != 0, d_points, desc_.as<uint2>() + run.round_base[r], run.round_base[r], d_meta);
 #ifdef MSMZ_TRACE
       {
         char nm[32];
@@ -1225,10 +1222,9 @@ class Engine : public IEngine {
         if ((st = trace_dump(nm, d_meta + 1, wgs < 65536 ? wgs : 65536, false))) return st;
       }
 #endif
-      mark(pl);
+      mark(run, run.ev.round_end[r]);
     }
-    const int ev_acc_end = pl.ei;
-    mark(pl);
+    mark(run, run.ev.acc_end);
 
     // ---- bucket reduction
     if (want_2d) {
@@ -1243,36 +1239,36 @@ class Engine : public IEngine {
       const uint32_t groups = (pl.L + S1 - 1) / S1;   // elements are weights 0..L-1 (weight L folded into L/2)
       if ((st = red_[0].ensure((size_t)pl.Keff * groups * XW * 4))) return st;
       if ((st = red_[1].ensure((size_t)pl.Keff * groups * XW * 4))) return st;
-      if ((st = reduce_first_affine(pl, d_points, S1, groups, n_pairs, d_meta))) return st;
+      if ((st = reduce_first_affine(pl, d_points, S1, groups, run.n_pairs, d_meta))) return st;
       int cur = 0;
       if ((st = reduce_levels<WeierPolicy<F>>(pl, cur, groups))) return st;
     }
-    return finish_msm(pl, want_2d, out, out_inf, log, R, n_pairs, ev_plan0, ev_plan1, ev_acc_end, round_ev0);
+    return finish_msm(pl, run, want_2d, out, out_inf, log);
   }
 
   // ------------------------------------------------------------------------------------------ msmBasic: projective / extended buckets
   // (msm-basic.ts:45-176; Weierstrass "projective fallback" parallel.ts:69-87 and the twisted-Edwards MSM)
-  template <class P>
   int msm_basic(const Handle& pts, const uint32_t* d_points, const uint32_t* d_scalars, uint64_t n64, const msmz_opts& opt,
                 uint8_t* out, int* out_inf, msmz_log* log) {
+    using P = typename std::conditional<TE, TePolicy<F>, WeierPolicy<F>>::type;
     // neither msmProjective (parallel.ts:69-87) nor the twisted-Edwards path (msm-basic.ts:4) uses the endomorphism
     if (opt.glv) return MSMZ_ERR_UNSUPPORTED;
     Plan pl;
     int st = planner_.make_plan(pl, n64, false, opt, (uint32_t)pts.n, false);
     if (st) return st;
-    if ((st = sort_phase(pl, planner_.sort_layout(pl), d_scalars))) return st;
-    if ((st = fetch_meta(pl))) return st;
+    Run run = new_run(opt);
+    if ((st = sort_phase(pl, planner_.sort_layout(pl), d_scalars, run, 0)) || (st = fetch_meta(run))) return st;
     if (h_meta_->error & 4u) return MSMZ_ERR_RANGE;
+    run.n_pairs = run.n_entries;   // (no tree rounds: every entry is added into its chunk's accumulator)
     if ((st = partials_.ensure((size_t)32 * pl.nblocks * 4))) return st;
     constexpr int AW = P::ACC_WORDS;
     const uint32_t nb = pl.nb, nblocks = pl.nblocks;
     MsmMeta* d_meta = meta_.as<MsmMeta>();
-    const int ev_plan0 = pl.ei;
-    mark(pl);
+    mark(run, run.ev.plan0);
     // chunk offsets: cscan[g] = sum_{g' < g} ceil(size / 2^chunk_shift); chunks of 64 entries unless some bucket is
     // very long (then ~sqrt of it: bounds both the chunk and the number of partial sums one reduction thread adds)
     int chunk_shift = chunk_shift_override_ > 0 ? chunk_shift_override_ : ACC_CHUNK_SHIFT;
-    while ((1ull << (2 * chunk_shift)) < pl.max_bucket) chunk_shift++;
+    while ((1ull << (2 * chunk_shift)) < run.max_bucket) chunk_shift++;
     const int scan_mode = 2 | (chunk_shift << 4);
     if ((st = rscan_.ensure(((size_t)nb + 1) * 4))) return st;
     hipLaunchKernelGGL(k_scan_partials, dim3(nblocks, 1), dim3(SCAN_T), 0, stream_, partials_.as<uint32_t>(),
@@ -1284,16 +1280,14 @@ class Engine : public IEngine {
     MSMZ_HIP(hipMemcpyAsync(h_meta_, d_meta, sizeof(MsmMeta), hipMemcpyDeviceToHost, stream_));
     MSMZ_HIP(hipStreamSynchronize(stream_));
     const uint32_t n_chunks = h_meta_->round_pairs[0];
-    const int ev_plan1 = pl.ei;
-    mark(pl);
+    mark(run, run.ev.plan_end);
     if ((st = slots_.ensure((size_t)(n_chunks + 1) * AW * 4))) return st;
     if (n_chunks > 0) {
       hipLaunchKernelGGL((k_bucket_accumulate<P>), dim3((n_chunks + 127) / 128), dim3(128), 0, stream_,
                          slots_.as<uint32_t>(), d_points, refs_.as<uint32_t>(), off_.as<uint32_t>(),
                          rscan_.as<uint32_t>(), nb, n_chunks, chunk_shift);
     }
-    const int ev_acc_end = pl.ei;
-    mark(pl);
+    mark(run, run.ev.acc_end);
     // every bucket is visited twice: buckets of several chunk accumulators (large inputs: Pallas 2^22 has 4,
     // ed-on-bls12-377 2^24 has 8) are first summed into one accumulator each, in bucket order
     const bool summed = (uint64_t)n_chunks * 2 > (uint64_t)nb * 3 && !no_bucket_sums_;
@@ -1303,7 +1297,7 @@ class Engine : public IEngine {
                          slots_.as<uint32_t>(), rscan_.as<uint32_t>(), nb);
     }
     if ((st = reduce_2d<P>(pl, d_points, true, summed))) return st;
-    return finish_msm(pl, true, out, out_inf, log, 0, pl.n_entries, ev_plan0, ev_plan1, ev_acc_end, 0);
+    return finish_msm(pl, run, true, out, out_inf, log);
   }
 
   // Batched-affine first level of the bucket reduction (reduce_affine.h): S - 1 chain steps and
@@ -1448,10 +1442,9 @@ class Engine : public IEngine {
   }
 
   // shared state -------------------------------------------------------------------------------
-  static constexpr int kMaxEvents = 64;
-  int device_;
+  int curve_id_, device_;
   hipStream_t stream_ = nullptr;
-  hipEvent_t ev_[kMaxEvents] = {};
+  StageEvents ev_{};
   std::map<uint64_t, Handle> handles_;
   uint64_t next_handle_ = 1;
   // Tuning knobs (the planning ones: PlanKnobs, plan.h).  A release build uses the constants; a development build
@@ -1480,18 +1473,16 @@ class Engine : public IEngine {
                         env_int("MSMZ_NO_SORT_SPECIAL", 0) != 0, env_int("MSMZ_FB", 0), (uint32_t)env_int("MSMZ_S1", 0),
                         (uint32_t)env_int("MSMZ_R2_NC", 0)}};
   DevBuf bsum_, f2desc_, tilecnt_, tileoff_, final_, desc_, bfin_, packed_, bins_, digits_, counts_, off_, cursor_, refs_, rscan_, partials_, slots_, red_[4], meta_, stage_, gen_table_;
-  uint32_t h_round_pairs_[32] = {};
   MsmMeta* h_meta_ = nullptr;
-  uint32_t* h_final_ = nullptr;
-  uint32_t* h_bfinal_ = nullptr;   // pinned: the window results of every problem of a batched MSM
-  size_t h_bfinal_words_ = 0;
-  int ensure_batch_final(size_t words) {
-    if (words <= h_bfinal_words_) return MSMZ_OK;
-    if (h_bfinal_) (void)hipHostFree(h_bfinal_);
-    h_bfinal_ = nullptr;
-    h_bfinal_words_ = 0;
-    MSMZ_HIP(hipHostMalloc(&h_bfinal_, words * 4));
-    h_bfinal_words_ = words;
+  uint32_t* h_res_ = nullptr;   // pinned, grow-only: the window results of every problem of an MSM (fetch_window_sums)
+  size_t h_res_words_ = 0;
+  int ensure_host_results(size_t words) {
+    if (words <= h_res_words_) return MSMZ_OK;
+    if (h_res_) (void)hipHostFree(h_res_);
+    h_res_ = nullptr;
+    h_res_words_ = 0;
+    MSMZ_HIP(hipHostMalloc(&h_res_, words * 4));
+    h_res_words_ = words;
     return MSMZ_OK;
   }
 };

@@ -13,18 +13,13 @@ MSMZ_TE_FIELDS(X)
 
 namespace msmz {
 
-// Curve configurations: which field structs, which MSM paths.
+// Curve configurations: field structs and curve form (the engine picks the MSM path, Engine::run_problems).
 template <class F_, class Fr_>
 struct WeierCfg {
   using F = F_;
   using Fr = Fr_;
   static constexpr bool TE = false;
   static constexpr bool HAS_ENDO = true;
-  static int run_msm(Engine<WeierCfg>& e, const Handle& p, const uint32_t* pts, const uint32_t* s, uint64_t n,
-                     const msmz_opts& o, uint8_t* out, int* oi, msmz_log* log, int extra_bits) {
-    if (o.buckets == MSMZ_BUCKETS_PROJECTIVE) return e.template msm_basic<WeierPolicy<F>>(p, pts, s, n, o, out, oi, log);
-    return e.msm_weierstrass_affine(p, pts, s, n, o, out, oi, log, extra_bits);
-  }
 };
 
 template <class F_, class Fr_>
@@ -33,10 +28,6 @@ struct TeCfg {
   using Fr = Fr_;
   static constexpr bool TE = true;
   static constexpr bool HAS_ENDO = false;
-  static int run_msm(Engine<TeCfg>& e, const Handle& p, const uint32_t* pts, const uint32_t* s, uint64_t n,
-                     const msmz_opts& o, uint8_t* out, int* oi, msmz_log* log, int) {
-    return e.template msm_basic<TePolicy<F>>(p, pts, s, n, o, out, oi, log);
-  }
 };
 
 using CfgBls377 = WeierCfg<Bls377Fp, Bls377Fr>;
@@ -90,10 +81,10 @@ static IEngine* make_engine(int curve_id, int device, int* st) {
     eng = e;
   };
   switch (curve_id) {
-    case MSMZ_BLS12_377_G1: make(new Engine<CfgBls377>(device)); break;
-    case MSMZ_PALLAS: make(new Engine<CfgPallas>(device)); break;
-    case MSMZ_BLS12_381_G1: make(new Engine<CfgBls381>(device)); break;
-    case MSMZ_ED_ON_BLS12_377: make(new Engine<CfgEd377>(device)); break;
+    case MSMZ_BLS12_377_G1: make(new Engine<CfgBls377>(curve_id, device)); break;
+    case MSMZ_PALLAS: make(new Engine<CfgPallas>(curve_id, device)); break;
+    case MSMZ_BLS12_381_G1: make(new Engine<CfgBls381>(curve_id, device)); break;
+    case MSMZ_ED_ON_BLS12_377: make(new Engine<CfgEd377>(curve_id, device)); break;
     default: break;
   }
   if (*st != MSMZ_OK) {
@@ -163,12 +154,12 @@ int msmz_free(msmz_ctx* c, uint64_t h) { return c ? c->engine->free_handle(h) : 
 int msmz_msm(msmz_ctx* c, uint64_t ph, const uint8_t* scalars, uint64_t n, const msmz_opts* o, uint8_t* out,
              int* out_inf, msmz_log* log) {
   if (!c || !scalars) return MSMZ_ERR_ARG;
-  return c->engine->msm(ph, scalars, 0, n, o, out, out_inf, log);
+  return c->engine->msm_batch(ph, scalars, 0, n, 1, o, out, out_inf, log);
 }
 int msmz_msm_resident(msmz_ctx* c, uint64_t ph, uint64_t sh, uint64_t n, const msmz_opts* o, uint8_t* out,
                       int* out_inf, msmz_log* log) {
   if (!c) return MSMZ_ERR_ARG;
-  return c->engine->msm(ph, nullptr, sh, n, o, out, out_inf, log);
+  return c->engine->msm_batch(ph, nullptr, sh, n, 1, o, out, out_inf, log);
 }
 
 int msmz_msm_batch(msmz_ctx* c, uint64_t ph, const uint8_t* scalars, uint64_t n, uint32_t batch, const msmz_opts* o,

@@ -43,9 +43,6 @@ class IEngine {
   virtual int download_points(uint64_t h, uint64_t first, uint64_t count, uint8_t* xy, uint8_t* inf) = 0;
   virtual int download_scalars(uint64_t h, uint64_t first, uint64_t count, uint8_t* s) = 0;
   virtual int free_handle(uint64_t h) = 0;
-  virtual int msm(uint64_t ph, const uint8_t* host_scalars, uint64_t sh, uint64_t n, const msmz_opts* o, uint8_t* out,
-                  int* out_inf, msmz_log* log, const GenMap* split = nullptr) = 0;
-  // stage-level test hooks (include/msmz_test.h)
   // `batch` MSMs over the same first n points (msmz_msm_batch): vector k = resident entries [k n, (k + 1) n), or host
   // buffer entries [k host_stride, k host_stride + n) (host_stride 0 = n); out: batch results, out_inf: batch flags
   virtual int msm_batch(uint64_t ph, const uint8_t* host_scalars, uint64_t sh, uint64_t n, uint32_t batch,
@@ -56,6 +53,7 @@ class IEngine {
                                 int* K) const = 0;
   virtual int precompute_points(uint64_t ph, uint64_t n, int c, int glv, uint32_t copies, uint64_t* h) = 0;
   virtual int precomputed_info(uint64_t h, int32_t* c, int32_t* glv, uint32_t* factor, uint32_t* K, uint64_t* records) = 0;
+  // stage-level test hooks (include/msmz_test.h)
   virtual int test_set_glv_bits(int) { return MSMZ_ERR_UNSUPPORTED; }
   virtual int test_retries() { return 0; }
   virtual int test_field(int, const uint8_t*, const uint8_t*, uint64_t, uint8_t*) { return MSMZ_ERR_UNSUPPORTED; }
@@ -75,7 +73,6 @@ class IEngine {
   }
 };
 
-// entries of the first n that live on shard g of G
 // Problems per sub-batch of a batched MSM: at most `cap` entries (problems x entries_per_problem) per sub-batch, and the
 // `remaining` problems dealt into equally large sub-batches (64 problems with room for 40 -> 2 x 32, not 40 + 24).
 static inline uint32_t batch_split(uint32_t remaining, uint64_t entries_per_problem, uint64_t cap) {
@@ -87,12 +84,47 @@ static inline uint32_t batch_split(uint32_t remaining, uint64_t entries_per_prob
   return (uint32_t)((remaining + parts - 1) / parts);
 }
 
+// entries of the first n that live on shard g of G
 static inline uint64_t shard_count(uint64_t n, uint32_t g, uint32_t G, int shift = MULTI_BLOCK_SHIFT) {
   const uint64_t blk = 1ull << shift, cycle = blk * G;
   const uint64_t full = n / cycle, rem = n % cycle;
   uint64_t extra = rem > (uint64_t)g * blk ? rem - (uint64_t)g * blk : 0;
   if (extra > blk) extra = blk;
   return full * blk + extra;
+}
+
+// acc += part for partial MSM results of `rec` bytes (canonical affine x | y) and their infinity flags: the reference's
+// "partition sum" on the main thread (msm-batched-affine.ts:300-307).  Index ranges of one engine, devices of a context.
+static inline int fold_partial(int curve_id, size_t rec, uint8_t* acc, int* acc_inf, const uint8_t* part, int part_inf) {
+  uint8_t a[2 * 48];
+  memcpy(a, acc, rec);
+  return msmz_point_add(curve_id, *acc_inf ? nullptr : a, *acc_inf, part_inf ? nullptr : part, part_inf, acc, acc_inf);
+}
+
+// total += part for the logs of parts of one call.  SEQUENTIAL: the parts ran one after another (index ranges,
+// sub-batches), their times add; PARALLEL: side by side (devices), the slowest part's times count.  Counts add in both,
+// max_bucket and rounds take the maximum.  first: total = part.  c, K and GLV: the first sequential part's, the last
+// parallel one's.
+enum class LogMerge { SEQUENTIAL, PARALLEL };
+static inline void merge_log(msmz_log* total, const msmz_log& part, bool first, LogMerge mode) {
+  if (first) {
+    *total = part;
+    return;
+  }
+  auto time = [mode](float& t, float p) { t = mode == LogMerge::SEQUENTIAL ? t + p : (p > t ? p : t); };
+  for (int i = 0; i < MSMZ_N_STAGES; i++) time(total->stage_ms[i], part.stage_ms[i]);
+  for (int i = 0; i < 32; i++) time(total->batch_add_ms[i], part.batch_add_ms[i]);
+  time(total->scatter_kernel_ms, part.scatter_kernel_ms);
+  total->n_entries += part.n_entries;
+  total->n_pairs += part.n_pairs;
+  total->scatter_launches += part.scatter_launches;
+  if (part.max_bucket > total->max_bucket) total->max_bucket = part.max_bucket;
+  if (part.rounds > total->rounds) total->rounds = part.rounds;
+  if (mode == LogMerge::PARALLEL) {
+    total->c = part.c;
+    total->K = part.K;
+    total->glv = part.glv;
+  }
 }
 
 class MultiEngine : public IEngine {
@@ -181,66 +213,27 @@ class MultiEngine : public IEngine {
     return MSMZ_OK;
   }
 
-  int msm(uint64_t ph, const uint8_t* host_scalars, uint64_t sh, uint64_t n, const msmz_opts* o, uint8_t* out,
-          int* out_inf, msmz_log* log, const GenMap* = nullptr) override {
-    if (!out || !out_inf || n == 0) return MSMZ_ERR_ARG;
-    auto pit = handles_.find(ph);
-    if (pit == handles_.end() || pit->second.kind != 0 || pit->second.n < n) return MSMZ_ERR_ARG;
-    const MHandle* sc = nullptr;
-    if (!host_scalars) {
-      auto sit = handles_.find(sh);
-      if (sit == handles_.end() || sit->second.kind != 1 || sit->second.n < n) return MSMZ_ERR_ARG;
-      sc = &sit->second;
-    }
-    const size_t rec = 2 * (size_t)fb_;
-    std::vector<std::vector<uint8_t>> part(G_, std::vector<uint8_t>(rec));
-    std::vector<int> pinf(G_, 1), used(G_, 0);
-    std::vector<msmz_log> logs(G_);
-    const MHandle& pts = pit->second;
-    int st = for_all([&](uint32_t g, IEngine* e) {
-      const uint64_t cnt = shard_count(n, g, G_);
-      if (cnt == 0) return (int)MSMZ_OK;
-      used[g] = 1;
-      if (sc) return e->msm(pts.sub[g], nullptr, sc->sub[g], cnt, o, part[g].data(), &pinf[g], &logs[g]);
-      const GenMap split{G_, g, MULTI_BLOCK_SHIFT};   // host scalars: the device copies its own blocks of the caller's buffer
-      return e->msm(pts.sub[g], host_scalars, 0, cnt, o, part[g].data(), &pinf[g], &logs[g], &split);
-    });
-    if (st) return st;
-    // fold the partial sums (the reference's "partition sum" on the main thread, msm-batched-affine.ts:300-307)
-    bool first = true;
-    for (uint32_t g = 0; g < G_; g++) {
-      if (!used[g]) continue;
-      if (first) {
-        memcpy(out, part[g].data(), rec);
-        *out_inf = pinf[g];
-        first = false;
-        continue;
-      }
-      std::vector<uint8_t> acc(out, out + rec);
-      const int ai = *out_inf;
-      st = msmz_point_add(curve_id_, ai ? nullptr : acc.data(), ai, pinf[g] ? nullptr : part[g].data(), pinf[g], out,
-                          out_inf);
-      if (st) return st;
-    }
-    if (log) merge_device_logs(log, logs, used);
-    return MSMZ_OK;
-  }
-
-  // Every engine computes the batch's partial sums over its share of the points; the host adds them per problem.
-  // Resident scalars are gathered to the host first: vector k starts at entry k n of the set, which is not a block
-  // boundary of the devices' shares unless n is a multiple of the block cycle.
+  // Every engine computes the partial sums of the `batch` problems over its share of the points; the host adds them per
+  // problem.  Resident scalars of a batch are gathered to the host first: vector k starts at entry k n of the set, which
+  // is not a block boundary of the devices' shares unless n is a multiple of the block cycle.  (batch = 1: vector 0
+  // starts at a block boundary, each device reads its own share of the set.)
   int msm_batch(uint64_t ph, const uint8_t* host_scalars, uint64_t sh, uint64_t n, uint32_t batch, const msmz_opts* o,
                 uint8_t* out, int* out_inf, msmz_log* log, const GenMap* = nullptr, uint64_t = 0) override {
     if (!out || !out_inf || n == 0 || batch == 0) return MSMZ_ERR_ARG;
     auto pit = handles_.find(ph);
     if (pit == handles_.end() || pit->second.kind != 0 || pit->second.n < n) return MSMZ_ERR_ARG;
+    const MHandle* sc = nullptr;
     std::vector<uint8_t> gathered;
     if (!host_scalars) {
       auto sit = handles_.find(sh);
       if (sit == handles_.end() || sit->second.kind != 1 || sit->second.n / batch < n) return MSMZ_ERR_ARG;
-      gathered.resize((size_t)batch * n * 32);
-      if (int st = download_scalars(sh, 0, (uint64_t)batch * n, gathered.data())) return st;
-      host_scalars = gathered.data();
+      if (batch == 1) {
+        sc = &sit->second;
+      } else {
+        gathered.resize((size_t)batch * n * 32);
+        if (int st = download_scalars(sh, 0, (uint64_t)batch * n, gathered.data())) return st;
+        host_scalars = gathered.data();
+      }
     }
     const size_t rec = 2 * (size_t)fb_;
     std::vector<std::vector<uint8_t>> part(G_, std::vector<uint8_t>(rec * batch));
@@ -252,30 +245,27 @@ class MultiEngine : public IEngine {
       const uint64_t cnt = shard_count(n, g, G_);
       if (cnt == 0) return (int)MSMZ_OK;
       used[g] = 1;
+      if (sc) return e->msm_batch(pts.sub[g], nullptr, sc->sub[g], cnt, 1, o, part[g].data(), pinf[g].data(), &logs[g]);
       const GenMap split{G_, g, MULTI_BLOCK_SHIFT};   // the device copies its own blocks of every vector
       return e->msm_batch(pts.sub[g], host_scalars, 0, cnt, batch, o, part[g].data(), pinf[g].data(), &logs[g], &split, n);
     });
     if (st) return st;
-    for (uint32_t k = 0; k < batch; k++) {
-      uint8_t* ok = out + (size_t)k * rec;
-      bool first = true;
-      for (uint32_t g = 0; g < G_; g++) {
-        if (!used[g]) continue;
+    bool first = true;
+    for (uint32_t g = 0; g < G_; g++) {
+      if (!used[g]) continue;
+      for (uint32_t k = 0; k < batch && st == MSMZ_OK; k++) {
         const uint8_t* pk = part[g].data() + (size_t)k * rec;
         if (first) {
-          memcpy(ok, pk, rec);
+          memcpy(out + (size_t)k * rec, pk, rec);
           out_inf[k] = pinf[g][k];
-          first = false;
-          continue;
+        } else {
+          st = fold_partial(curve_id_, rec, out + (size_t)k * rec, &out_inf[k], pk, pinf[g][k]);
         }
-        std::vector<uint8_t> acc(ok, ok + rec);
-        const int ai = out_inf[k];
-        st = msmz_point_add(curve_id_, ai ? nullptr : acc.data(), ai, pinf[g][k] ? nullptr : pk, pinf[g][k], ok,
-                            &out_inf[k]);
-        if (st) return st;
       }
+      if (st) return st;
+      if (log) merge_log(log, logs[g], first, LogMerge::PARALLEL);
+      first = false;
     }
-    if (log) merge_device_logs(log, logs, used);
     return MSMZ_OK;
   }
 
@@ -304,28 +294,6 @@ class MultiEngine : public IEngine {
     if (it == handles_.end() || it->second.factor == 0) return MSMZ_ERR_ARG;
     if (records) *records = (uint64_t)it->second.factor * it->second.n * (it->second.glv ? 2 : 1);
     return workers_[0]->eng->precomputed_info(it->second.sub[0], c, glv, factor, K, nullptr);   // (shard 0 holds block 0)
-  }
-
-  void merge_device_logs(msmz_log* log, const std::vector<msmz_log>& logs, const std::vector<int>& used) const {
-    {   // stage times: the slowest device; counts: summed
-      memset(log, 0, sizeof(*log));
-      for (uint32_t g = 0; g < G_; g++) {
-        if (!used[g]) continue;
-        for (int i = 0; i < MSMZ_N_STAGES; i++)
-          if (logs[g].stage_ms[i] > log->stage_ms[i]) log->stage_ms[i] = logs[g].stage_ms[i];
-        for (int i = 0; i < 32; i++)
-          if (logs[g].batch_add_ms[i] > log->batch_add_ms[i]) log->batch_add_ms[i] = logs[g].batch_add_ms[i];
-        if (logs[g].scatter_kernel_ms > log->scatter_kernel_ms) log->scatter_kernel_ms = logs[g].scatter_kernel_ms;
-        if (logs[g].max_bucket > log->max_bucket) log->max_bucket = logs[g].max_bucket;
-        if (logs[g].rounds > log->rounds) log->rounds = logs[g].rounds;
-        log->n_entries += logs[g].n_entries;
-        log->n_pairs += logs[g].n_pairs;
-        log->scatter_launches += logs[g].scatter_launches;
-        log->c = logs[g].c;
-        log->K = logs[g].K;
-        log->glv = logs[g].glv;
-      }
-    }
   }
 
   int test_set_glv_bits(int bits) override {

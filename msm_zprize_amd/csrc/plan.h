@@ -112,15 +112,11 @@ struct Plan {
   int Keff, spread;           // bucket windows incl. the top window's 2^spread sub-windows
   int fold_shift = 0, fold_rows = 0;   // ... or the top window folded into its own bucket set (SortGeom)
   uint32_t top_range = 1;              // values the top window's digit can take
-  bool glv, timing;
-  uint32_t max_bucket = 0, n_entries = 0;
+  bool glv;
   uint32_t endo_delta = 0;    // GLV over a prefix of a set: half-1 entry i reads point record pts_n + i = (n + i) + endo_delta
   uint32_t nprob = 1;         // batched MSM: problems (scalar vectors) sorted, planned and reduced together; nb, M, K,
                               // Keff describe ONE problem, bucket set p * Keff + kw holds window kw of problem p
   uint32_t F = 1;             // precomputed point set: windows per bucket set (Keff = ceil(K / F) sets); 1 = plain
-  uint32_t copy_stride = 0;   // ... and records per copy of the points
-  int ei = 0;                 // next event slot
-  int ev_coarse = -1, ev_sort_end = -1;
 };
 
 // Window geometry for window size c: K windows, L buckets each, significant bits t_top of the top window's
@@ -388,7 +384,6 @@ struct Planner {
       return MSMZ_ERR_ARG;
     pl.nb = (uint32_t)nb64;
     pl.nblocks = (pl.nb + SCAN_TILE - 1) / SCAN_TILE;
-    pl.timing = opt.timing != 0;
     pl.endo_delta = glv ? pts_n - pl.n : 0u;
     return MSMZ_OK;
   }

@@ -16,6 +16,23 @@
 using namespace msmz;
 
 namespace old {
+// the Plan of commit 79707f1: planner output plus the engine's run state (timing, device totals, copy stride, events)
+struct Plan {
+  uint32_t n, M, L, nb, nblocks;
+  int c, K, b;
+  int Keff, spread;
+  int fold_shift = 0, fold_rows = 0;
+  uint32_t top_range = 1;
+  bool glv, timing;
+  uint32_t max_bucket = 0, n_entries = 0;
+  uint32_t endo_delta = 0;
+  uint32_t nprob = 1;
+  uint32_t F = 1;
+  uint32_t copy_stride = 0;
+  int ei = 0;
+  int ev_coarse = -1, ev_sort_end = -1;
+};
+
 // engine.h's planning members as they were at commit 79707f1 (in Engine<Cfg>; knobs were members, TE = twisted Edwards)
 template <class Fr, bool TE>
 struct Engine {
@@ -416,12 +433,12 @@ static void mismatch(const char* what, const char* fr, uint64_t n, int c, int gl
            e, knob, nprob, F);
 }
 
-static bool same_plan(const Plan& a, const Plan& b) {
+// every field of the planner's Plan (the old one's run state is no longer planner output)
+static bool same_plan(const Plan& a, const old::Plan& b) {
   return a.n == b.n && a.M == b.M && a.L == b.L && a.nb == b.nb && a.nblocks == b.nblocks && a.c == b.c && a.K == b.K &&
          a.b == b.b && a.Keff == b.Keff && a.spread == b.spread && a.fold_shift == b.fold_shift &&
-         a.fold_rows == b.fold_rows && a.top_range == b.top_range && a.glv == b.glv && a.timing == b.timing &&
-         a.max_bucket == b.max_bucket && a.n_entries == b.n_entries && a.endo_delta == b.endo_delta &&
-         a.nprob == b.nprob && a.F == b.F && a.copy_stride == b.copy_stride;
+         a.fold_rows == b.fold_rows && a.top_range == b.top_range && a.glv == b.glv && a.endo_delta == b.endo_delta &&
+         a.nprob == b.nprob && a.F == b.F;
 }
 
 static bool same_geom(const SortGeom& a, const SortGeom& b) {
@@ -481,7 +498,8 @@ static void replay(const char* name) {
           opt.glv = gc.glv;
           opt.timing = (int)(n & 1);
           auto check = [&](bool tree, bool fold, uint32_t nprob, uint32_t F) {
-            Plan a{}, b{};
+            Plan a{};
+            old::Plan b{};
             const int sa = np.make_plan(a, n, glv, opt, pts_n, tree, gc.extra, fold, nprob, F);
             const int sb = op.make_plan(b, n, glv, opt, pts_n, tree, gc.extra, fold, nprob, F);
             shapes++;
