@@ -96,6 +96,23 @@ enum {
 int msmz_test_point_raw(msmz_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, const uint8_t* neg, uint64_t n,
                         int L, uint8_t* out_xy);
 
+/* ONE launch of the tree rounds' batched-affine addition (k_batch_add, the template instance the MSM runs) with B
+ * pairs per thread (1 .. 16) and the safe (1) or unsafe (0) variant, on caller-built operands (Weierstrass only).
+ *   points_xy / points_inf (inf nullable): n_points original points as canonical affine (x || y, 2*fe_bytes), converted
+ *     to the resident point format of the MSM;
+ *   slots_xy / slots_inf (inf nullable): n_slots input slot records 0 .. n_slots-1, canonical affine, stored as the
+ *     tree rounds store their results (infinity = the all-zero record);
+ *   desc: n_pairs descriptors of two location words (operand a, operand b): 0x40000000 | i = point i, with bit 31
+ *     set = its negative; j (bit 31 clear) = slot record j.  Pair t adds a + b and writes slot record out_base + t
+ *     (out_base >= n_slots, any alignment);
+ *   out_xy: the n_pairs results as canonical affine, all-zero = infinity;  error: the meta error word after the
+ *     launch (bit 0: the unsafe variant met a zero denominator).
+ * MSMZ_ERR_ARG for a location outside the supplied arrays, B outside 1 .. 16 or out_base < n_slots; MSMZ_ERR_RANGE
+ * for a coordinate >= p. */
+int msmz_test_batch_add(msmz_ctx* ctx, int safe, int B, const uint8_t* points_xy, const uint8_t* points_inf,
+                        uint64_t n_points, const uint8_t* slots_xy, const uint8_t* slots_inf, uint64_t n_slots,
+                        const uint32_t* desc, uint64_t n_pairs, uint64_t out_base, uint8_t* out_xy, uint32_t* error);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,9 @@ EXPORTS = {
                                       C.c_char_p]),
     "msmz_test_point": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint64,
                                   C.c_char_p]),
+    "msmz_test_batch_add": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_uint64, C.c_char_p,
+                                      C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p,
+                                      C.POINTER(C.c_uint32)]),
 }
 
 _lib = None

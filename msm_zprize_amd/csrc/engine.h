@@ -804,6 +804,66 @@ class Engine : public IEngine {
     return MSMZ_OK;
   }
 
+  int test_batch_add(int safe, int B, const uint8_t* pxy, const uint8_t* pinf, uint64_t np, const uint8_t* sxy,
+                     const uint8_t* sinf, uint64_t ns, const uint32_t* desc, uint64_t n_pairs, uint64_t out_base,
+                     uint8_t* out, uint32_t* error) override {
+    if (TE) return MSMZ_ERR_UNSUPPORTED;
+    constexpr uint64_t CAP = 1u << 22;
+    if (!desc || !out || !error || (safe != 0 && safe != 1) || B < 1 || B > MSMZ_BATCH_BMAX) return MSMZ_ERR_ARG;
+    if (n_pairs == 0 || n_pairs > CAP || np > CAP || ns > CAP || (np && !pxy) || (ns && !sxy)) return MSMZ_ERR_ARG;
+    if (out_base < ns || out_base > CAP) return MSMZ_ERR_ARG;
+    // every location names a supplied operand: the kernel reads whatever its descriptors point at
+    for (uint64_t k = 0; k < 2 * n_pairs; k++) {
+      const uint32_t w = desc[k];
+      if ((w & LOC_ORIG) ? (w & 0x3fffffffu) >= np : w >= ns) return MSMZ_ERR_ARG;
+    }
+    MSMZ_HIP(hipSetDevice(device_));
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t pb = (size_t)RW * 4 * np, sb = (size_t)RW * 4 * ns, db = (size_t)8 * n_pairs;
+    const size_t o_pinf = up(pb), o_sxy = o_pinf + up(np), o_sinf = o_sxy + up(sb), o_desc = o_sinf + up(ns);
+    uint8_t *d_in, *d_out;
+    int st = test_buffers(o_desc + db, (size_t)RW * 4 * n_pairs, &d_in, &d_out);
+    if (st) return st;
+    DevBuf d_pts;   // the resident point set (freed on every return)
+    if ((st = d_pts.ensure((np ? np : 1) * PW_WORDS * 4))) return st;
+    // slot records 0 .. out_base + n_pairs - 1 in whole groups of 64, as the MSM sizes them; filled with a pattern
+    // that decodes to no result, so a record the launch leaves unwritten cannot pass for one
+    const uint32_t recs = (uint32_t)(out_base + n_pairs);
+    if ((st = slots_.ensure(((size_t)recs + 64) * SlotFmt<F>::WORDS * 4))) return st;
+    MSMZ_HIP(hipMemsetAsync(slots_.p, 0xa5, slot_words((recs + 63u) & ~63u) * 4, stream_));
+    if (np) MSMZ_HIP(hipMemcpyAsync(d_in, pxy, pb, hipMemcpyHostToDevice, stream_));
+    if (np && pinf) MSMZ_HIP(hipMemcpyAsync(d_in + o_pinf, pinf, np, hipMemcpyHostToDevice, stream_));
+    if (ns) MSMZ_HIP(hipMemcpyAsync(d_in + o_sxy, sxy, sb, hipMemcpyHostToDevice, stream_));
+    if (ns && sinf) MSMZ_HIP(hipMemcpyAsync(d_in + o_sinf, sinf, ns, hipMemcpyHostToDevice, stream_));
+    MSMZ_HIP(hipMemcpyAsync(d_in + o_desc, desc, db, hipMemcpyHostToDevice, stream_));
+    MsmMeta* d_meta = meta_.as<MsmMeta>();
+    MSMZ_HIP(hipMemsetAsync(&d_meta->error, 0, 4, stream_));
+    if constexpr (!TE) {
+      if (np)
+        hipLaunchKernelGGL((k_points_to_mont<F>), dim3((np + 255) / 256), dim3(256), 0, stream_, d_pts.as<uint32_t>(),
+                           (const uint32_t*)d_in, pinf ? d_in + o_pinf : nullptr, (uint32_t)np, 0, &d_meta->error);
+      if (ns)
+        hipLaunchKernelGGL((k_test_slots_in<F>), dim3((ns + 255) / 256), dim3(256), 0, stream_, slots_.as<uint32_t>(),
+                           (const uint32_t*)(d_in + o_sxy), sinf ? d_in + o_sinf : nullptr, (uint32_t)ns,
+                           &d_meta->error);
+      MSMZ_HIP(hipGetLastError());
+      MSMZ_HIP(hipMemcpyAsync(&h_meta_->error, &d_meta->error, 4, hipMemcpyDeviceToHost, stream_));
+      MSMZ_HIP(hipStreamSynchronize(stream_));
+      if (h_meta_->error) return MSMZ_ERR_RANGE;   // a coordinate >= p
+      launch_batch_add_b(B, (uint32_t)n_pairs, safe != 0, d_pts.as<uint32_t>(), (const uint2*)(d_in + o_desc),
+                         (uint32_t)out_base, d_meta);
+      MSMZ_HIP(hipGetLastError());
+      hipLaunchKernelGGL((k_test_slots_out<F>), dim3((n_pairs + 255) / 256), dim3(256), 0, stream_,
+                         (uint32_t*)d_out, slots_.as<uint32_t>(), (uint32_t)out_base, (uint32_t)n_pairs);
+      MSMZ_HIP(hipGetLastError());
+      MSMZ_HIP(hipMemcpyAsync(&h_meta_->error, &d_meta->error, 4, hipMemcpyDeviceToHost, stream_));
+      MSMZ_HIP(hipMemcpyAsync(out, d_out, (size_t)RW * 4 * n_pairs, hipMemcpyDeviceToHost, stream_));
+      MSMZ_HIP(hipStreamSynchronize(stream_));
+      *error = h_meta_->error;
+    }
+    return MSMZ_OK;
+  }
+
   // ------------------------------------------------------------------------------------------ shared phases
   Run new_run(const msmz_opts& opt) const {
     Run run;
@@ -1216,8 +1276,7 @@ class Engine : public IEngine {
       {
         char nm[32];
         snprintf(nm, sizeof nm, "k_batch_add round %d", r);
-        int B = 1;
-        while (B < 16 && (uint64_t)pairs >= (uint64_t)MSMZ_BATCH_T * (B * 2) * batch_min_wgs_) B *= 2;
+        const int B = batch_b(pairs);
         const uint32_t wgs = (pairs + MSMZ_BATCH_T * B - 1) / (MSMZ_BATCH_T * B);
         if ((st = trace_dump(nm, d_meta + 1, wgs < 65536 ? wgs : 65536, false))) return st;
       }
@@ -1353,15 +1412,26 @@ class Engine : public IEngine {
     return (size_t)(rec >> 6) * (SlotFmt<F>::CH * 64) * 4;
   }
 
-  // one launch of batched-affine additions: pairs `dsc[0 .. pairs)`, results in slot records out_base + t
-  void launch_batch_add(uint32_t pairs, bool safe, const uint32_t* d_points, const uint2* dsc, uint32_t out_base,
-                        MsmMeta* d_meta) {
-    constexpr int T = MSMZ_BATCH_T, OCC = MSMZ_BATCH_OCC, BMAX = MSMZ_BATCH_BMAX;
-    // pairs per thread: as many as keep >= ~2 workgroups per CU in flight, capped at BMAX = 16 (measured per round at
-    // 2^20: 7.6 M pairs B = 8..16, 3.7 M: 16, 1.8 M: 8, 0.9 M: 4, < 0.3 M: 2; 32 is slower everywhere)
+  // pairs per thread of a launch of `pairs` batched-affine additions: as many as keep >= ~2 workgroups per CU in
+  // flight, capped at BMAX = 16 (measured per round at 2^20: 7.6 M pairs B = 8..16, 3.7 M: 16, 1.8 M: 8, 0.9 M: 4,
+  // < 0.3 M: 2; 32 is slower everywhere)
+  int batch_b(uint32_t pairs) const {
+    constexpr int T = MSMZ_BATCH_T, BMAX = MSMZ_BATCH_BMAX;
     int B = 1;
     while (B < BMAX && (uint64_t)pairs >= (uint64_t)T * (B * 2) * batch_min_wgs_) B *= 2;
     if (batch_b_override_ > 0) B = batch_b_override_ < BMAX ? batch_b_override_ : BMAX;
+    return B;
+  }
+
+  // one launch of batched-affine additions: pairs `dsc[0 .. pairs)`, results in slot records out_base + t
+  void launch_batch_add(uint32_t pairs, bool safe, const uint32_t* d_points, const uint2* dsc, uint32_t out_base,
+                        MsmMeta* d_meta) {
+    launch_batch_add_b(batch_b(pairs), pairs, safe, d_points, dsc, out_base, d_meta);
+  }
+  // ... with B pairs per thread (1 <= B <= MSMZ_BATCH_BMAX)
+  void launch_batch_add_b(int B, uint32_t pairs, bool safe, const uint32_t* d_points, const uint2* dsc,
+                          uint32_t out_base, MsmMeta* d_meta) {
+    constexpr int T = MSMZ_BATCH_T, OCC = MSMZ_BATCH_OCC, BMAX = MSMZ_BATCH_BMAX;
     dim3 grid((pairs + T * B - 1) / (T * B)), block(T);
     if constexpr (!TE) {
       if (safe) {

@@ -103,6 +103,8 @@
   MSMZ_INST_SORT(Fr, true, 16, PFX)                                                                               \
   PFX template __global__ void k_test_digits<Fr, true>(uint32_t*, const uint32_t*, uint32_t, int, int);           \
   MSMZ_INST_TEST(F, Fr, WeierPolicy<F>, false, PFX)                                                               \
+  PFX template __global__ void k_test_slots_in<F>(uint32_t*, const uint32_t*, const uint8_t*, uint32_t, uint32_t*); \
+  PFX template __global__ void k_test_slots_out<F>(uint32_t*, const uint32_t*, uint32_t, uint32_t);               \
   MSMZ_INST_SCALAR(Fr, PFX)
 
 #define MSMZ_INST_MISC_TE(F, Fr, PFX)                                                              \

@@ -214,6 +214,13 @@ int msmz_test_point(msmz_ctx* c, int op, const uint8_t* a, const uint8_t* ai, co
   return c ? c->engine->test_point(op, a, ai, b, bi, n, out) : MSMZ_ERR_ARG;
 }
 
+int msmz_test_batch_add(msmz_ctx* c, int safe, int B, const uint8_t* pxy, const uint8_t* pinf, uint64_t np,
+                        const uint8_t* sxy, const uint8_t* sinf, uint64_t ns, const uint32_t* desc, uint64_t n_pairs,
+                        uint64_t out_base, uint8_t* out, uint32_t* error) {
+  return c ? c->engine->test_batch_add(safe, B, pxy, pinf, np, sxy, sinf, ns, desc, n_pairs, out_base, out, error)
+           : MSMZ_ERR_ARG;
+}
+
 int msmz_point_add(int curve_id, const uint8_t* a, int ai, const uint8_t* b, int bi, uint8_t* out, int* oi) {
   if (!out || !oi || (!a && !ai) || (!b && !bi)) return MSMZ_ERR_ARG;
   switch (curve_id) {

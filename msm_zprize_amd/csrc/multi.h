@@ -71,6 +71,10 @@ class IEngine {
   virtual int test_point_raw(int, const uint8_t*, const uint8_t*, const uint8_t*, uint64_t, int, uint8_t*) {
     return MSMZ_ERR_UNSUPPORTED;
   }
+  virtual int test_batch_add(int, int, const uint8_t*, const uint8_t*, uint64_t, const uint8_t*, const uint8_t*,
+                             uint64_t, const uint32_t*, uint64_t, uint64_t, uint8_t*, uint32_t*) {
+    return MSMZ_ERR_UNSUPPORTED;
+  }
 };
 
 // Problems per sub-batch of a batched MSM: at most `cap` entries (problems x entries_per_problem) per sub-batch, and the
@@ -332,6 +336,11 @@ class MultiEngine : public IEngine {
   int test_point_raw(int op, const uint8_t* a, const uint8_t* b, const uint8_t* neg, uint64_t n, int L,
                      uint8_t* out) override {
     return workers_[0]->eng->test_point_raw(op, a, b, neg, n, L, out);
+  }
+  int test_batch_add(int safe, int B, const uint8_t* pxy, const uint8_t* pinf, uint64_t np, const uint8_t* sxy,
+                     const uint8_t* sinf, uint64_t ns, const uint32_t* desc, uint64_t n_pairs, uint64_t out_base,
+                     uint8_t* out, uint32_t* error) override {
+    return workers_[0]->eng->test_batch_add(safe, B, pxy, pinf, np, sxy, sinf, ns, desc, n_pairs, out_base, out, error);
   }
 
  private:

@@ -342,4 +342,47 @@ __global__ void __launch_bounds__(64) k_test_point_raw(uint32_t* out, const uint
   for (int j = 0; j < 2 * NW; j++) out[(size_t)i * 2 * NW + j] = w[j];
 }
 
+// input slot records of msmz_test_batch_add: canonical affine (x | y, 2*NW words) + infinity flags (nullable) ->
+// slot records 0 .. n-1 in the tree rounds' format; a coordinate >= p raises err bit 2 (as k_points_to_mont)
+template <class F>
+__global__ void __launch_bounds__(256) k_test_slots_in(uint32_t* slots, const uint32_t* in, const uint8_t* is_inf,
+                                                       uint32_t n, uint32_t* err) {
+  constexpr int NW = F::NW;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t* w = in + (size_t)i * 2 * NW;
+  if (words_geq<NW>(w, F::PW) || words_geq<NW>(w + NW, F::PW)) atomicOr(err, 4u);
+  Fe<F> x, y;
+  Affine<F> m;
+  fe_unpack<F>(x, w);
+  fe_unpack<F>(y, w + NW);
+  fe_to_mont(m.x, x);
+  fe_to_mont(m.y, y);
+  slot_store_point<F>(slots + slot_offset<F>(i), m, is_inf != nullptr && is_inf[i] != 0);
+}
+
+// results of msmz_test_batch_add: slot records first .. first+n-1 -> canonical affine, all-zero = infinity
+template <class F>
+__global__ void __launch_bounds__(256) k_test_slots_out(uint32_t* out, const uint32_t* slots, uint32_t first,
+                                                        uint32_t n) {
+  constexpr int NW = F::NW;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Affine<F> p;
+  const bool inf = slot_load_point<F, true>(p, slots + slot_offset<F>(first + i));
+  uint32_t w[2 * NW];
+  if (inf) {
+#pragma unroll
+    for (int j = 0; j < 2 * NW; j++) w[j] = 0;
+  } else {
+    Fe<F> t;
+    fe_from_mont(t, p.x);
+    fe_to_canon_words<F>(w, t);
+    fe_from_mont(t, p.y);
+    fe_to_canon_words<F>(w + NW, t);
+  }
+#pragma unroll
+  for (int j = 0; j < 2 * NW; j++) out[(size_t)i * 2 * NW + j] = w[j];
+}
+
 }  // namespace msmz
