@@ -113,6 +113,57 @@ int msmz_test_batch_add(msmz_ctx* ctx, int safe, int B, const uint8_t* points_xy
                         uint64_t n_points, const uint8_t* slots_xy, const uint8_t* slots_inf, uint64_t n_slots,
                         const uint32_t* desc, uint64_t n_pairs, uint64_t out_base, uint8_t* out_xy, uint32_t* error);
 
+/* The bucket reduction alone, on caller-built buckets: the line sums and the weighted sums of the two-dimensional
+ * reduction (csrc/reduce2d_kernels.h) and the upper levels (k_reduce_quad / k_reduce_quad16 / k_reduce_tail), through
+ * the engine's own reduce_2d / reduce_levels and the template instances an MSM launches.  Run it before and after
+ * touching a reduction kernel: it names the problem and the line an MSM's single result point cannot.
+ *
+ * 2-D modes: window size c (2 .. 16) fixes L = 2^(c-1), H = 2^ceil((c-1)/2), D = L / H as the planner's split does;
+ * `nsets` bucket sets (1 .. 16) of L buckets, bucket g = set * L + (j - 1) holding weight j = 1 .. L.  Problem 2 s is
+ * the row problem of set s (sum_h h R_h, R_h = sum_d E[h D + d], the weight-L bucket twice in R_(H/2)), problem 2 s + 1
+ * its column problem (sum_d d C_d, C_d = sum_h E[h D + d]; its lines D .. H-1 are neutral).
+ *   MSMZ_TR_LOCATIONS (Weierstrass): points_xy / points_inf = n_points original points, slots_xy / slots_inf = n_slots
+ *     slot records (both as msmz_test_batch_add takes them); loc = 4 location words per bucket in that hook's encoding
+ *     (0x40000000 | i = point i, bit 31 = its negative; j = slot record j), read up to the first 0xffffffff
+ *     (LOC_NONE).  Drives k_reduce2d_partial.
+ *   MSMZ_TR_ACCS: points_xy = n_points points (all-zero or flagged = infinity on Weierstrass; twisted Edwards has no
+ *     flag, its neutral element is (0, 1)), each stored as an accumulator record; bucket g is the sum of records
+ *     cscan[g] .. cscan[g+1]-1 (nsets * L + 1 offsets).  Drives k_reduce2d_partial_acc with chunk ranges.
+ *   MSMZ_TR_ACCS_SUMMED: the same through k_bucket_sums and the one-accumulator-per-bucket mode of that kernel.
+ * MSMZ_TR_LEVELS: reduce_levels alone on `nsets` problems (1 .. 64) of n_in entries (1 .. 4096):  points_xy = the
+ *   nsets * n_in rows, then the nsets * n_in C inputs (n_points = 2 * nsets * n_in); result j = sum_e (C_e + e row_e).
+ * scale (nullable; ACCS, ACCS_SUMMED, LEVELS): one canonical field element lambda != 0 per input point; the record is
+ *   stored as (lambda^2 x, lambda^3 y, lambda^2, lambda^3), resp. (lambda x, lambda y, lambda, lambda x y), so that
+ *   equal points meet in different representations.
+ * Level selection, each 0 = the engine's value, for this call only: nc = chunks per line (a power of two <= D);
+ *   tail_n = entries per problem at which k_reduce_tail takes over (1 .. 4096); quad16_max = levels with at most this
+ *   many groups run k_reduce_quad16, larger ones k_reduce_quad; pairsum_x4_max = pair-sum launches of at most this many
+ *   additions run k_pairsum_x4, larger ones k_pairsum (both 1 .. 2^20).
+ * out_xy: the results as canonical affine (x || y; Weierstrass: all-zero = infinity), 2 * nsets for the 2-D modes,
+ *   nsets for LEVELS.  lines_xy (nullable, 2-D modes): the 2 * nsets * H line sums after the pair-sum launches, problem
+ *   by problem.
+ * MSMZ_ERR_ARG for anything that would read outside the supplied arrays (a location beyond its table, a cscan that
+ * decreases or ends beyond n_points, c / nsets / n_in / a threshold out of range, lambda = 0); MSMZ_ERR_RANGE for a
+ * coordinate or lambda >= p; MSMZ_ERR_UNSUPPORTED for LOCATIONS on twisted Edwards. */
+enum { MSMZ_TR_LOCATIONS = 0, MSMZ_TR_ACCS = 1, MSMZ_TR_ACCS_SUMMED = 2, MSMZ_TR_LEVELS = 3 };
+typedef struct msmz_test_reduce_args {
+  int32_t mode, c;
+  uint32_t nsets, n_in;
+  uint32_t nc, tail_n, quad16_max, pairsum_x4_max;
+  const uint8_t* points_xy;
+  const uint8_t* points_inf;
+  uint64_t n_points;
+  const uint8_t* slots_xy;
+  const uint8_t* slots_inf;
+  uint64_t n_slots;
+  const uint8_t* scale;
+  const uint32_t* loc;
+  const uint32_t* cscan;
+  uint8_t* out_xy;
+  uint8_t* lines_xy;
+} msmz_test_reduce_args;
+int msmz_test_reduce(msmz_ctx* ctx, const msmz_test_reduce_args* args);
+
 #ifdef __cplusplus
 }
 #endif

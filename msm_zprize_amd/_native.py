@@ -25,6 +25,15 @@ class MsmzLog(C.Structure):
                 ("scatter_launches", C.c_uint32), ("scatter_kernel_ms", C.c_float), ("batch_add_ms", C.c_float * 32)]
 
 
+class MsmzTestReduceArgs(C.Structure):   # msmz_test_reduce_args (include/msmz_test.h)
+    _fields_ = [("mode", C.c_int32), ("c", C.c_int32), ("nsets", C.c_uint32), ("n_in", C.c_uint32),
+                ("nc", C.c_uint32), ("tail_n", C.c_uint32), ("quad16_max", C.c_uint32), ("pairsum_x4_max", C.c_uint32),
+                ("points_xy", C.c_char_p), ("points_inf", C.c_char_p), ("n_points", C.c_uint64),
+                ("slots_xy", C.c_char_p), ("slots_inf", C.c_char_p), ("n_slots", C.c_uint64),
+                ("scale", C.c_char_p), ("loc", C.c_void_p), ("cscan", C.c_void_p),
+                ("out_xy", C.c_void_p), ("lines_xy", C.c_void_p)]
+
+
 EXPORTS = {
     # name: (restype, argtypes)
     "msmz_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int), C.c_int]),
@@ -70,6 +79,7 @@ EXPORTS = {
     "msmz_test_batch_add": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_uint64, C.c_char_p,
                                       C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p,
                                       C.POINTER(C.c_uint32)]),
+    "msmz_test_reduce": (C.c_int, [C.c_void_p, C.POINTER(MsmzTestReduceArgs)]),
 }
 
 _lib = None

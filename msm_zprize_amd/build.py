@@ -19,7 +19,7 @@ FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fno-gpu-rdc", 
 
 
 def _deps_mtime():
-    deps = [os.path.join(CSRC, f) for f in HEADERS] + [os.path.join(HERE, "..", "include", "msmz.h")]
+    deps = [os.path.join(CSRC, f) for f in HEADERS] + [os.path.join(HERE, "..", "include", h) for h in ("msmz.h", "msmz_test.h")]
     return max(os.path.getmtime(d) for d in deps)
 
 

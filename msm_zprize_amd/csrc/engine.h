@@ -864,6 +864,144 @@ class Engine : public IEngine {
     return MSMZ_OK;
   }
 
+  // The bucket reduction on caller-built buckets (msmz_test.h): the level-selection knobs hold for this call only.
+  int test_reduce(const msmz_test_reduce_args& a) override {
+    const uint32_t tail0 = tail_n_, quad0 = quad16_max_groups_, pair0 = pairsum_x4_max_, nc0 = planner_.k.r2_nc;
+    const int st = test_reduce_run(a);
+    tail_n_ = tail0, quad16_max_groups_ = quad0, pairsum_x4_max_ = pair0, planner_.k.r2_nc = nc0;
+    return st;
+  }
+  int test_reduce_run(const msmz_test_reduce_args& a) {
+    using P = typename std::conditional<TE, TePolicy<F>, WeierPolicy<F>>::type;
+    constexpr int AW = P::ACC_WORDS;
+    constexpr uint64_t CAP = 1u << 20;
+    const bool levels = a.mode == MSMZ_TR_LEVELS, locs = a.mode == MSMZ_TR_LOCATIONS;
+    if (a.mode < MSMZ_TR_LOCATIONS || a.mode > MSMZ_TR_LEVELS || !a.out_xy) return MSMZ_ERR_ARG;
+    if (TE && locs) return MSMZ_ERR_UNSUPPORTED;
+    if (a.tail_n > 4096 || a.quad16_max > CAP || a.pairsum_x4_max > CAP) return MSMZ_ERR_ARG;
+    if (a.n_points > CAP || a.n_slots > CAP || (a.n_points && !a.points_xy) || (a.n_slots && !a.slots_xy)) return MSMZ_ERR_ARG;
+    // geometry: a plan of `nsets` bucket sets of window size c, as far as reduce_2d / reduce_levels read one
+    Plan pl{};
+    pl.nprob = 1;
+    pl.F = 1;
+    uint32_t nb = 0, n_res = a.nsets, H = 0;
+    if (levels) {
+      if (a.nsets < 1 || a.nsets > 64 || a.n_in < 1 || a.n_in > 4096 || a.nc != 0) return MSMZ_ERR_ARG;
+      if (a.n_points != (uint64_t)2 * a.nsets * a.n_in) return MSMZ_ERR_ARG;
+      pl.Keff = (int)a.nsets;
+    } else {
+      if (a.c < 2 || a.c > 16 || a.nsets < 1 || a.nsets > 16) return MSMZ_ERR_ARG;
+      pl.c = a.c;
+      pl.L = 1u << (a.c - 1);
+      pl.Keff = pl.K = (int)a.nsets;
+      nb = pl.nb = a.nsets * pl.L;
+      const Split2d sp = planner_.split_2d(pl);
+      if (a.nc != 0 && ((a.nc & (a.nc - 1)) != 0 || a.nc > sp.D)) return MSMZ_ERR_ARG;
+      H = sp.H;
+      n_res = 2 * a.nsets;
+      // every location / chunk range names a supplied operand: the kernels read whatever these point at
+      if (locs) {
+        if (!a.loc) return MSMZ_ERR_ARG;
+        for (uint64_t k = 0; k < (uint64_t)4 * nb; k++) {
+          const uint32_t w = a.loc[k];
+          if (w == LOC_NONE) {
+            k |= 3;   // (the rest of this bucket's words is never read)
+            continue;
+          }
+          if ((w & LOC_ORIG) ? (w & 0x3fffffffu) >= a.n_points : w >= a.n_slots) return MSMZ_ERR_ARG;
+        }
+      } else {
+        if (!a.cscan || a.cscan[nb] > a.n_points) return MSMZ_ERR_ARG;
+        for (uint32_t g = 0; g < nb; g++)
+          if (a.cscan[g] > a.cscan[g + 1]) return MSMZ_ERR_ARG;
+      }
+    }
+    if (a.scale && locs) return MSMZ_ERR_ARG;
+    if (a.tail_n) tail_n_ = a.tail_n;
+    if (a.quad16_max) quad16_max_groups_ = a.quad16_max;
+    if (a.pairsum_x4_max) pairsum_x4_max_ = a.pairsum_x4_max;
+    if (a.nc) planner_.k.r2_nc = a.nc;
+    const uint32_t n_lines = levels || !a.lines_xy ? 0 : n_res * H;
+
+    MSMZ_HIP(hipSetDevice(device_));
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t np = a.n_points, ns = a.n_slots;
+    const size_t pb = (size_t)RW * 4 * np, sb = (size_t)RW * 4 * ns, lb = (size_t)FE_BYTES * np;
+    const size_t o_pinf = up(pb), o_scale = o_pinf + up(np), o_sxy = o_scale + up(lb), o_sinf = o_sxy + up(sb);
+    const size_t in_bytes = o_sinf + up(ns), res_bytes = up((size_t)RW * 4 * n_res);
+    uint8_t *d_in, *d_out;
+    int st = test_buffers(in_bytes, res_bytes + (size_t)RW * 4 * n_lines, &d_in, &d_out);
+    if (st) return st;
+    if (np) MSMZ_HIP(hipMemcpyAsync(d_in, a.points_xy, pb, hipMemcpyHostToDevice, stream_));
+    if (np && a.points_inf) MSMZ_HIP(hipMemcpyAsync(d_in + o_pinf, a.points_inf, np, hipMemcpyHostToDevice, stream_));
+    if (np && a.scale) MSMZ_HIP(hipMemcpyAsync(d_in + o_scale, a.scale, lb, hipMemcpyHostToDevice, stream_));
+    if (ns) MSMZ_HIP(hipMemcpyAsync(d_in + o_sxy, a.slots_xy, sb, hipMemcpyHostToDevice, stream_));
+    if (ns && a.slots_inf) MSMZ_HIP(hipMemcpyAsync(d_in + o_sinf, a.slots_inf, ns, hipMemcpyHostToDevice, stream_));
+    MsmMeta* d_meta = meta_.as<MsmMeta>();
+    MSMZ_HIP(hipMemsetAsync(&d_meta->error, 0, 4, stream_));
+    const uint8_t* d_pinf = a.points_inf ? d_in + o_pinf : nullptr;
+    // accumulator records `first .. first + n` of the input points, in the policy's memory format
+    auto accs_in = [&](uint32_t* dst, size_t first, size_t n) {
+      if (n)
+        hipLaunchKernelGGL((k_test_accs_in<P, TE>), dim3((n + 255) / 256), dim3(256), 0, stream_, dst,
+                           (const uint32_t*)d_in + first * RW, d_pinf ? d_pinf + first : nullptr,
+                           a.scale ? (const uint32_t*)(d_in + o_scale) + first * NW : nullptr, (uint32_t)n,
+                           &d_meta->error);
+    };
+    DevBuf d_pts, d_lines;   // (freed on every return)
+    if (levels) {
+      const size_t n = (size_t)a.nsets * a.n_in;
+      if ((st = red_[0].ensure(n * AW * 4)) || (st = red_[1].ensure(n * AW * 4))) return st;
+      accs_in(red_[0].as<uint32_t>(), 0, n);
+      accs_in(red_[1].as<uint32_t>(), n, n);
+    } else if (locs) {
+      if constexpr (!TE) {
+        if ((st = d_pts.ensure((np ? np : 1) * PW_WORDS * 4))) return st;
+        if ((st = bfin_.ensure((size_t)nb * 16))) return st;
+        if ((st = slots_.ensure(((size_t)ns + 64) * SlotFmt<F>::WORDS * 4))) return st;
+        MSMZ_HIP(hipMemsetAsync(slots_.p, 0xa5, slot_words(((uint32_t)ns + 63u) & ~63u) * 4, stream_));
+        MSMZ_HIP(hipMemcpyAsync(bfin_.p, a.loc, (size_t)nb * 16, hipMemcpyHostToDevice, stream_));
+        if (np)
+          hipLaunchKernelGGL((k_points_to_mont<F>), dim3((np + 255) / 256), dim3(256), 0, stream_, d_pts.as<uint32_t>(),
+                             (const uint32_t*)d_in, d_pinf, (uint32_t)np, 0, &d_meta->error);
+        if (ns)
+          hipLaunchKernelGGL((k_test_slots_in<F>), dim3((ns + 255) / 256), dim3(256), 0, stream_, slots_.as<uint32_t>(),
+                             (const uint32_t*)(d_in + o_sxy), a.slots_inf ? d_in + o_sinf : nullptr, (uint32_t)ns,
+                             &d_meta->error);
+      }
+    } else {
+      if ((st = slots_.ensure((np + 1) * AW * 4)) || (st = rscan_.ensure(((size_t)nb + 1) * 4))) return st;
+      MSMZ_HIP(hipMemcpyAsync(rscan_.p, a.cscan, ((size_t)nb + 1) * 4, hipMemcpyHostToDevice, stream_));
+      accs_in(slots_.as<uint32_t>(), 0, np);
+    }
+    MSMZ_HIP(hipGetLastError());
+    MSMZ_HIP(hipMemcpyAsync(&h_meta_->error, &d_meta->error, 4, hipMemcpyDeviceToHost, stream_));
+    MSMZ_HIP(hipStreamSynchronize(stream_));
+    if (h_meta_->error & 4u) return MSMZ_ERR_RANGE;   // a coordinate or scale >= p
+    if (h_meta_->error) return MSMZ_ERR_ARG;          // a zero scale
+
+    if (levels) {
+      int cur = 0;
+      if ((st = reduce_levels<P>(pl, cur, a.n_in, a.nsets))) return st;
+    } else {
+      const bool summed = a.mode == MSMZ_TR_ACCS_SUMMED;
+      if (summed && (st = bucket_sums<P>(nb))) return st;
+      if ((st = reduce_2d<P>(pl, d_pts.as<uint32_t>(), !locs, summed, n_lines ? &d_lines : nullptr))) return st;
+    }
+    MSMZ_HIP(hipGetLastError());
+    hipLaunchKernelGGL((k_test_accs_out<P, TE>), dim3((n_res + 63) / 64), dim3(64), 0, stream_, (uint32_t*)d_out,
+                       final_.as<uint32_t>(), n_res);
+    if (n_lines)
+      hipLaunchKernelGGL((k_test_accs_out<P, TE>), dim3((n_lines + 63) / 64), dim3(64), 0, stream_,
+                         (uint32_t*)(d_out + res_bytes), d_lines.as<uint32_t>(), n_lines);
+    MSMZ_HIP(hipGetLastError());
+    MSMZ_HIP(hipMemcpyAsync(a.out_xy, d_out, (size_t)RW * 4 * n_res, hipMemcpyDeviceToHost, stream_));
+    if (n_lines)
+      MSMZ_HIP(hipMemcpyAsync(a.lines_xy, d_out + res_bytes, (size_t)RW * 4 * n_lines, hipMemcpyDeviceToHost, stream_));
+    MSMZ_HIP(hipStreamSynchronize(stream_));
+    return MSMZ_OK;
+  }
+
   // ------------------------------------------------------------------------------------------ shared phases
   Run new_run(const msmz_opts& opt) const {
     Run run;
@@ -1124,8 +1262,10 @@ class Engine : public IEngine {
   // problems with the upper-level kernels.  Leaves result 2 kw (rows) / 2 kw + 1 (columns) of bucket set kw in final_.
   // basic = true: the buckets are sums of partial accumulators (msmBasic path: slots_ + rscan_), else the affine bucket
   // sums of the tree rounds (bfin_)
+  // lines_out (test_reduce only): receives a copy of the line sums, the rows the weighted levels start from
   template <class P>
-  int reduce_2d(const Plan& pl, const uint32_t* d_points, bool basic = false, bool summed = false) {
+  int reduce_2d(const Plan& pl, const uint32_t* d_points, bool basic = false, bool summed = false,
+                DevBuf* lines_out = nullptr) {
     const Split2d sp = planner_.split_2d(pl);
     R2Geom g;
     g.L = pl.L;
@@ -1167,6 +1307,10 @@ class Engine : public IEngine {
     }
     // upper levels: rows = line sums (weight unit 1), C = infinity (all-zero accumulator records)
     const int crow = src, ccol = src + 1;
+    if (lines_out) {
+      if ((st = lines_out->ensure((size_t)lines * XW * 4))) return st;
+      MSMZ_HIP(hipMemcpyAsync(lines_out->p, red_[crow].p, (size_t)lines * XW * 4, hipMemcpyDeviceToDevice, stream_));
+    }
     if ((st = red_[ccol].ensure((size_t)lines * XW * 4))) return st;
     hipLaunchKernelGGL((k_fill_neutral<P>), dim3((lines + 255) / 256), dim3(256), 0, stream_, red_[ccol].as<uint32_t>(), lines);
     int cur = crow >> 1;   // reduce_levels addresses rows as red_[cur * 2], C as red_[cur * 2 + 1]
@@ -1350,13 +1494,17 @@ class Engine : public IEngine {
     // every bucket is visited twice: buckets of several chunk accumulators (large inputs: Pallas 2^22 has 4,
     // ed-on-bls12-377 2^24 has 8) are first summed into one accumulator each, in bucket order
     const bool summed = (uint64_t)n_chunks * 2 > (uint64_t)nb * 3 && !no_bucket_sums_;
-    if (summed) {
-      if ((st = bsum_.ensure((size_t)nb * AW * 4))) return st;
-      hipLaunchKernelGGL((k_bucket_sums<P>), dim3((nb + 127) / 128), dim3(128), 0, stream_, bsum_.as<uint32_t>(),
-                         slots_.as<uint32_t>(), rscan_.as<uint32_t>(), nb);
-    }
+    if (summed && (st = bucket_sums<P>(nb))) return st;
     if ((st = reduce_2d<P>(pl, d_points, true, summed))) return st;
     return finish_msm(pl, run, true, out, out_inf, log);
+  }
+  // bsum_[g] = sum of the chunk accumulators slots_[rscan_[g] .. rscan_[g+1]) of bucket g < nb
+  template <class P>
+  int bucket_sums(uint32_t nb) {
+    if (int st = bsum_.ensure((size_t)nb * P::ACC_WORDS * 4)) return st;
+    hipLaunchKernelGGL((k_bucket_sums<P>), dim3((nb + 127) / 128), dim3(128), 0, stream_, bsum_.as<uint32_t>(),
+                       slots_.as<uint32_t>(), rscan_.as<uint32_t>(), nb);
+    return MSMZ_OK;
   }
 
   // Batched-affine first level of the bucket reduction (reduce_affine.h): S - 1 chain steps and

@@ -79,7 +79,10 @@
   PFX template __global__ void k_test_point<P, TE>(uint32_t*, const uint32_t*, const uint32_t*, const uint8_t*,   \
                                                    const uint8_t*, uint32_t, int);                                \
   PFX template __global__ void k_test_point_raw<P, TE>(uint32_t*, const uint32_t*, const uint32_t*, const uint8_t*, \
-                                                       uint32_t, int, int);
+                                                       uint32_t, int, int);                                       \
+  PFX template __global__ void k_test_accs_in<P, TE>(uint32_t*, const uint32_t*, const uint8_t*, const uint32_t*, \
+                                                     uint32_t, uint32_t*);                                        \
+  PFX template __global__ void k_test_accs_out<P, TE>(uint32_t*, const uint32_t*, uint32_t);
 
 // sort kernels: window size 0 = any, 16 / 17 = the defaults of large inputs (window loop unrolled)
 #define MSMZ_INST_SORT(Fr, GLV, C, PFX)                                                                           \

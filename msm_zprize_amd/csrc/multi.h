@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/msmz.h"
+#include "../../include/msmz_test.h"   // msmz_test_reduce_args
 
 namespace msmz {
 
@@ -75,6 +76,7 @@ class IEngine {
                              uint64_t, const uint32_t*, uint64_t, uint64_t, uint8_t*, uint32_t*) {
     return MSMZ_ERR_UNSUPPORTED;
   }
+  virtual int test_reduce(const msmz_test_reduce_args&) { return MSMZ_ERR_UNSUPPORTED; }
 };
 
 // Problems per sub-batch of a batched MSM: at most `cap` entries (problems x entries_per_problem) per sub-batch, and the
@@ -342,6 +344,7 @@ class MultiEngine : public IEngine {
                      uint8_t* out, uint32_t* error) override {
     return workers_[0]->eng->test_batch_add(safe, B, pxy, pinf, np, sxy, sinf, ns, desc, n_pairs, out_base, out, error);
   }
+  int test_reduce(const msmz_test_reduce_args& a) override { return workers_[0]->eng->test_reduce(a); }
 
  private:
   struct MHandle {

@@ -385,4 +385,79 @@ __global__ void __launch_bounds__(256) k_test_slots_out(uint32_t* out, const uin
   for (int j = 0; j < 2 * NW; j++) out[(size_t)i * 2 * NW + j] = w[j];
 }
 
+// accumulator records of msmz_test_reduce: canonical affine (x | y) + infinity flags (nullable; Weierstrass: an
+// all-zero record is infinity too) + scales lambda (nullable, canonical, != 0) -> records 0 .. n-1 as the policy
+// stores them: XYZZ (l^2 x, l^3 y, l^2, l^3), extended twisted Edwards (l x, l y, l, l x y).  err bit 2: a coordinate
+// or scale >= p; bit 3: a zero scale.
+template <class P, bool TE>
+__global__ void __launch_bounds__(256) k_test_accs_in(uint32_t* accs, const uint32_t* in, const uint8_t* is_inf,
+                                                      const uint32_t* scale, uint32_t n, uint32_t* err) {
+  using F = typename P::F;
+  constexpr int NW = F::NW;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t* w = in + (size_t)i * 2 * NW;
+  if (words_geq<NW>(w, F::PW) || words_geq<NW>(w + NW, F::PW)) atomicOr(err, 4u);
+  uint32_t o = 0;
+#pragma unroll
+  for (int j = 0; j < 2 * NW; j++) o |= w[j];
+  Fe<F> x, y, xm, ym, l, l2, l3;
+  fe_unpack<F>(x, w);
+  fe_unpack<F>(y, w + NW);
+  fe_to_mont(xm, x);
+  fe_to_mont(ym, y);
+  if (scale != nullptr) {
+    const uint32_t* sw = scale + (size_t)i * NW;
+    if (words_geq<NW>(sw, F::PW)) atomicOr(err, 4u);
+    uint32_t so = 0;
+#pragma unroll
+    for (int j = 0; j < NW; j++) so |= sw[j];
+    if (so == 0) atomicOr(err, 8u);
+    fe_unpack<F>(x, sw);
+    fe_to_mont(l, x);
+  } else {
+    fe_set_const<F>(l, F::ONE);
+  }
+  typename P::Acc a;
+  if constexpr (TE) {
+    Fe<F> t;
+    fe_mul(a.X, xm, l);
+    fe_mul(a.Y, ym, l);
+    a.Z = l;
+    fe_mul(t, xm, ym);
+    fe_mul(a.T, t, l);
+  } else {
+    if (o == 0 || (is_inf != nullptr && is_inf[i] != 0)) {
+      xyzz_set_inf(a);
+    } else {
+      fe_sqr(l2, l);
+      fe_mul(l3, l2, l);
+      fe_mul(a.X, xm, l2);
+      fe_mul(a.Y, ym, l3);
+      a.ZZ = l2;
+      a.ZZZ = l3;
+    }
+  }
+  P::store(accs + (size_t)i * P::ACC_WORDS, a);
+}
+
+// results of msmz_test_reduce: accumulator records 0 .. n-1 -> canonical affine (Weierstrass: all-zero = infinity)
+template <class P, bool TE>
+__global__ void __launch_bounds__(64) k_test_accs_out(uint32_t* out, const uint32_t* accs, uint32_t n) {
+  using F = typename P::F;
+  constexpr int NW = F::NW;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  typename P::Acc a;
+  P::load(a, accs + (size_t)i * P::ACC_WORDS);
+  uint32_t w[2 * NW];
+  if constexpr (TE) {
+    te_to_affine_canon<F>(w, a);
+  } else {
+    (void)xyzz_to_affine_canon<F>(w, a);
+  }
+#pragma unroll
+  for (int j = 0; j < 2 * NW; j++) out[(size_t)i * 2 * NW + j] = w[j];
+}
+
 }  // namespace msmz

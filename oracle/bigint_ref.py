@@ -425,28 +425,61 @@ def reduce_buckets_running_sum(curve, buckets):
     return total
 
 
-def reduce_buckets_2d(curve, buckets, c):
-    """The same sum the way the HIP engine forms it (msm_zprize_amd/csrc/reduce2d_kernels.h): the weight j = l is split
-    j = h * D + d with H = 2^ceil((c-1)/2) rows and D = L / H columns,
+def split_2d(c):
+    """(H, D) of window size c: H = 2^ceil((c-1)/2) rows, D = L / H columns (csrc/plan.h Planner::split_2d)."""
+    a = (c - 1 + 1) // 2
+    return 1 << a, 1 << (c - 1 - a)
+
+
+def weighted_sum(curve, xs):
+    """sum_i i * xs[i] (the upper reduction levels' result for rows xs and neutral C inputs)."""
+    return reduce_buckets_running_sum(curve, xs[1:]) if len(xs) > 1 else curve.zero
+
+
+def reduce_buckets_2d_parts(curve, buckets, c):
+    """The stages of the engine's two-dimensional reduction (msm_zprize_amd/csrc/reduce2d_kernels.h) for one bucket set:
+    the weight j = l is split j = h * D + d with H = 2^ceil((c-1)/2) rows and D = L / H columns,
         sum_j j E_j = D * sum_h h R_h + sum_d d C_d,   R_h = sum_d E[h D + d],  C_d = sum_h E[h D + d],
-    the bucket of weight L = H * D is added twice into row H / 2, and the factor D is applied as b = log2 D doublings
-    (the host's Horner pass adds the row result b bit positions above the column result).  Returns the window sum."""
+    and the bucket of weight L = H * D is added twice into row H / 2.  Returns (row line sums R_0 .. R_(H-1), column line
+    sums C_0 .. C_(H-1) -- the lines D .. H-1 of the column problem are neutral --, row result sum_h h R_h, column
+    result sum_d d C_d)."""
     L = 1 << (c - 1)
     assert len(buckets) == L
-    a = (c - 1 + 1) // 2
-    b = c - 1 - a
-    H, D = 1 << a, 1 << b
+    H, D = split_2d(c)
     E = [curve.zero] + list(buckets[:L - 1])           # E[j] = bucket of weight j, j in [0, L)
     rows = [curve.zero] * H
-    cols = [curve.zero] * D
+    cols = [curve.zero] * H
     for j in range(1, L):
         h, d = divmod(j, D)
         rows[h] = curve.add(rows[h], E[j])
         cols[d] = curve.add(cols[d], E[j])
     for _ in range(2):
         rows[H // 2] = curve.add(rows[H // 2], buckets[L - 1])
-    weighted = lambda xs: reduce_buckets_running_sum(curve, xs[1:]) if len(xs) > 1 else curve.zero   # sum_i i * xs[i]
-    A, Bc = weighted(rows), weighted(cols)
-    for _ in range(b):
+    return rows, cols, weighted_sum(curve, rows), weighted_sum(curve, cols)
+
+
+def reduce_multiples_2d(mults, c, q):
+    """reduce_buckets_2d_parts in the exponent: bucket l holds mults[l - 1] * G for one point G of order q.  Returns the
+    multiples (mod q) of the row line sums, the column line sums, the row result and the column result."""
+    L = 1 << (c - 1)
+    assert len(mults) == L
+    H, D = split_2d(c)
+    rows, cols = [0] * H, [0] * H
+    for j in range(1, L):
+        h, d = divmod(j, D)
+        rows[h] += mults[j - 1]
+        cols[d] += mults[j - 1]
+    rows[H // 2] += 2 * mults[L - 1]
+    wsum = lambda xs: sum(i * x for i, x in enumerate(xs)) % q
+    return [r % q for r in rows], [x % q for x in cols], wsum(rows), wsum(cols)
+
+
+def reduce_buckets_2d(curve, buckets, c):
+    """The window sum sum_l l * B_l the way the HIP engine forms it: the row and column results of
+    reduce_buckets_2d_parts, the factor D applied as b = log2 D doublings (the host's Horner pass adds the row result b
+    bit positions above the column result)."""
+    _, D = split_2d(c)
+    _, _, A, Bc = reduce_buckets_2d_parts(curve, buckets, c)
+    for _ in range(D.bit_length() - 1):
         A = curve.double(A)
     return curve.add(A, Bc)

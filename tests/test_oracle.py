@@ -191,3 +191,40 @@ def test_bucket_reduction_2d_equals_running_sum(label, c):
     for l, bk in enumerate(buckets, start=1):
         direct = C.add(direct, C.scale(l, bk))
     assert C.is_equal(want, direct)
+
+
+@pytest.mark.parametrize("c", [2, 3, 4, 7, 8])
+@pytest.mark.parametrize("label", ["bls12-377", "pallas", "bls12-381", "ed-on-bls12-377"])
+def test_bucket_reduction_2d_parts(label, c):
+    """The stages of the two-dimensional reduction that tests/test_reduce_gpu.py compares the device with
+    (reduce_buckets_2d_parts: line sums, row result, column result): D * rows + columns is the reference's running sum,
+    the column problem's lines D .. H-1 are neutral, the weight-L bucket sits twice in row H/2, and the same stages in
+    the exponent (reduce_multiples_2d) name the same points -- with empty buckets, negative and cancelling multiples."""
+    params = P.CURVES[label]
+    te = params["kind"] != "weierstrass"
+    C = B.TwistedEdwards(params) if te else B.ProjectiveWeierstrass(params)
+    q = params["order"]
+    rng = random.Random(7 * c + len(label))
+    L = 1 << (c - 1)
+    H, D = B.split_2d(c)
+    assert H * D == L and H >= D and H == 1 << ((c - 1 + 1) // 2)
+    mults = [0 if rng.random() < 0.2 else rng.randrange(-50, 51) for _ in range(L)]
+    mults[L - 1] = 9                                  # the weight-L bucket is never empty here
+    if L >= 4:
+        mults[1] = -mults[0]
+    buckets = [C.scale(m % q, C.one) for m in mults]
+    rows, cols, row_res, col_res = B.reduce_buckets_2d_parts(C, buckets, c)
+    assert len(rows) == H and len(cols) == H
+    zero = (lambda X: C.is_zero(X)) if te else (lambda X: X[2] % C.p == 0)
+    assert all(zero(X) for X in cols[D:])
+    total = row_res
+    for _ in range(D.bit_length() - 1):
+        total = C.double(total)
+    total = C.add(total, col_res)
+    assert C.is_equal(total, B.reduce_buckets_running_sum(C, buckets))
+    assert C.is_equal(total, B.reduce_buckets_2d(C, buckets, c))
+    mr, mc, mrr, mcr = B.reduce_multiples_2d(mults, c, q)
+    assert mr[H // 2] == (sum(mults[(H // 2) * D - 1 + d] for d in range(D) if (H // 2) * D + d >= 1) + 2 * 9) % q
+    for X, m in zip(rows + cols + [row_res, col_res], mr + mc + [mrr, mcr]):
+        assert C.is_equal(X, C.scale(m, C.one)), (label, c)
+    assert (D * mrr + mcr) % q == sum(l * m for l, m in enumerate(mults, start=1)) % q
