@@ -17,7 +17,6 @@
 #include "../../include/msmz.h"
 #include "kernels.h"
 #include "gen_kernels.h"
-#include "test_kernels.h"
 #include "host64.h"
 #include "multi.h"
 #include "plan.h"
@@ -165,8 +164,20 @@ static int host_point_add(const uint8_t* a, int ai, const uint8_t* b, int bi, ui
   return MSMZ_OK;
 }
 
+// Which kernel a level of the bucket reduction runs; none changes a result.  The engine holds one, constant, which the
+// MSM paths pass to the reduction; a test hook passes a copy with its caller's values.
+struct ReduceKnobs {
+  uint32_t tail_n;           // entries per window at which k_reduce_tail takes over
+  uint32_t quad16_max;       // levels with at most this many groups use k_reduce_quad16
+  uint32_t pairsum_x4_max;   // pair-sum levels with at most this many additions use DPP quads
+};
+
+template <class Cfg>
+class TestHooks;   // test_hooks.h
+
 template <class Cfg>
 class Engine : public IEngine {
+  friend class TestHooks<Cfg>;
   using F = typename Cfg::F;
   using Fr = typename Cfg::Fr;
   static constexpr int NW = F::NW;
@@ -196,6 +207,7 @@ class Engine : public IEngine {
     }
     return meta_.ensure(sizeof(MsmMeta) + kTraceBytes * 65536);
   }
+ private:
   template <bool GLV, int C>
   int raise_sort_limits() {
     int st;
@@ -252,6 +264,7 @@ class Engine : public IEngine {
     return MSMZ_OK;
   }
 
+ public:
   ~Engine() override {   // (the device buffers and handles free themselves after this, on this device)
     (void)hipSetDevice(device_);
     if (h_meta_) (void)hipHostFree(h_meta_);
@@ -262,24 +275,6 @@ class Engine : public IEngine {
   }
 
   // ------------------------------------------------------------------------------------------ data
-  // Host -> device copy of this engine's `n` local records of `rec` bytes.  split == nullptr: one contiguous copy.
-  // Otherwise the engine is shard `split->shard` of `split->nshards` inside a multi-device context (multi.h): its local
-  // block b is global block b * nshards + shard of the caller's buffer, so every block is copied straight from where
-  // the caller has it -- no gathered host copy in between.
-  int copy_h2d(void* dst, const uint8_t* src, size_t rec, uint64_t n, const GenMap* split) {
-    if (!split || split->nshards <= 1) {
-      MSMZ_HIP(hipMemcpyAsync(dst, src, n * rec, hipMemcpyHostToDevice, stream_));
-      return MSMZ_OK;
-    }
-    const uint64_t blk = 1ull << split->blk_shift;
-    for (uint64_t li = 0; li < n; li += blk) {
-      const uint64_t len = n - li < blk ? n - li : blk;
-      const uint64_t gi = ((li >> split->blk_shift) * split->nshards + split->shard) << split->blk_shift;
-      MSMZ_HIP(hipMemcpyAsync((uint8_t*)dst + li * rec, src + gi * rec, len * rec, hipMemcpyHostToDevice, stream_));
-    }
-    return MSMZ_OK;
-  }
-
   int upload_points(const uint8_t* xy, const uint8_t* inf, uint64_t n, uint64_t* h, const GenMap* split = nullptr) override {
     if (!xy || !h || n == 0 || n >= (1ull << (Cfg::HAS_ENDO ? 29 : 30))) return MSMZ_ERR_ARG;   // record indices (incl. endomorphism images) fit 30 bits
     MSMZ_HIP(hipSetDevice(device_));
@@ -303,10 +298,9 @@ class Engine : public IEngine {
       hipLaunchKernelGGL((k_points_to_mont<F>), dim3((n + 255) / 256), dim3(256), 0, stream_, hd.mem.as<uint32_t>(),
                          stage_.as<uint32_t>(), d_inf, (uint32_t)n, endo ? 1 : 0, &d_meta->error);
     }
-    MSMZ_HIP(hipGetLastError());
-    MSMZ_HIP(hipMemcpyAsync(&h_meta_->error, &d_meta->error, 4, hipMemcpyDeviceToHost, stream_));
-    MSMZ_HIP(hipStreamSynchronize(stream_));
-    if (h_meta_->error) return MSMZ_ERR_RANGE;   // a coordinate >= p
+    uint32_t err = 0;
+    if ((st = fetch_error(&err))) return st;
+    if (err) return MSMZ_ERR_RANGE;   // a coordinate >= p
     return add_handle(std::move(hd), h);
   }
 
@@ -320,10 +314,9 @@ class Engine : public IEngine {
     MSMZ_HIP(hipMemsetAsync(&d_meta->error, 0, 4, stream_));
     hipLaunchKernelGGL((k_check_scalars<Fr>), dim3((n + 255) / 256), dim3(256), 0, stream_, &d_meta->error,
                        hd.mem.as<const uint32_t>(), (uint32_t)n);
-    MSMZ_HIP(hipGetLastError());
-    MSMZ_HIP(hipMemcpyAsync(&h_meta_->error, &d_meta->error, 4, hipMemcpyDeviceToHost, stream_));
-    MSMZ_HIP(hipStreamSynchronize(stream_));
-    if (h_meta_->error) return MSMZ_ERR_RANGE;   // a scalar >= group order
+    uint32_t err = 0;
+    if ((st = fetch_error(&err))) return st;
+    if (err) return MSMZ_ERR_RANGE;   // a scalar >= group order
     return add_handle(std::move(hd), h);
   }
 
@@ -357,18 +350,6 @@ class Engine : public IEngine {
     MSMZ_HIP(hipGetLastError());
     MSMZ_HIP(hipStreamSynchronize(stream_));
     return add_handle(std::move(hd), h);
-  }
-
-  // the device memory of a new handle (owned by it: an error before add_handle frees it)
-  int alloc_handle(Handle& hd, size_t bytes) {
-    MSMZ_HIP(hipMalloc(&hd.mem.p, bytes));
-    hd.mem.bytes = bytes;
-    return MSMZ_OK;
-  }
-  int add_handle(Handle&& hd, uint64_t* h) {
-    *h = next_handle_++;
-    handles_.emplace(*h, std::move(hd));
-    return MSMZ_OK;
   }
 
   int download_points(uint64_t hd, uint64_t first, uint64_t count, uint8_t* xy, uint8_t* inf) override {
@@ -423,20 +404,6 @@ class Engine : public IEngine {
   }
 
   // ------------------------------------------------------------------------------------------ precomputed point sets
-  // The options of an MSM over handle `h`: a precomputed set fixes c and the GLV choice (opts->c must be 0 or its c,
-  // opts->glv -1 or its choice; a null opts means both defaults) and takes batched-affine buckets with the 2-D reduction.
-  int resolve_opts(const Handle& h, const msmz_opts* o, msmz_opts* opt) const {
-    memset(opt, 0, sizeof(*opt));
-    if (o) *opt = *o;
-    if (!h.factor) return MSMZ_OK;
-    if (!o) opt->glv = -1;
-    if (opt->buckets == MSMZ_BUCKETS_PROJECTIVE || opt->reserved[0] == 1) return MSMZ_ERR_UNSUPPORTED;
-    if ((opt->c != 0 && opt->c != h.c) || (opt->glv >= 0 && (opt->glv != 0) != (h.glv != 0))) return MSMZ_ERR_ARG;
-    opt->c = h.c;
-    opt->glv = h.glv;
-    return MSMZ_OK;
-  }
-
   int precompute_params(uint64_t n, const msmz_opts* o, uint32_t factor, int* c_out, int* glv_out,
                         uint32_t* f_out, int* k_out) const override {
     if (TE) return MSMZ_ERR_UNSUPPORTED;   // twisted Edwards runs msmBasic: no batched-affine buckets to share
@@ -549,6 +516,72 @@ class Engine : public IEngine {
     return st;
   }
 
+  // ------------------------------------------------------------------ tests (msmz_test.h; the stage hooks: test_hooks.h)
+  int test_set_glv_bits(int bits) override {
+    if (!Fr::HAS_GLV) return MSMZ_ERR_UNSUPPORTED;
+    if (bits != 0 && (bits < 8 || bits > Fr::GLV_BITS - 1)) return MSMZ_ERR_ARG;
+    planner_.k.glv_bits_assumed = bits;
+    return MSMZ_OK;
+  }
+  int test_retries() override { return retries_; }
+  ITestHooks* test_hooks() override { return &hooks_; }
+
+  // ------------------------------------------------------------------------------------------ what only the engine calls
+ private:
+  // Host -> device copy of this engine's `n` local records of `rec` bytes.  split == nullptr: one contiguous copy.
+  // Otherwise the engine is shard `split->shard` of `split->nshards` inside a multi-device context (multi.h): its local
+  // block b is global block b * nshards + shard of the caller's buffer, so every block is copied straight from where
+  // the caller has it -- no gathered host copy in between.
+  int copy_h2d(void* dst, const uint8_t* src, size_t rec, uint64_t n, const GenMap* split) {
+    if (!split || split->nshards <= 1) {
+      MSMZ_HIP(hipMemcpyAsync(dst, src, n * rec, hipMemcpyHostToDevice, stream_));
+      return MSMZ_OK;
+    }
+    const uint64_t blk = 1ull << split->blk_shift;
+    for (uint64_t li = 0; li < n; li += blk) {
+      const uint64_t len = n - li < blk ? n - li : blk;
+      const uint64_t gi = ((li >> split->blk_shift) * split->nshards + split->shard) << split->blk_shift;
+      MSMZ_HIP(hipMemcpyAsync((uint8_t*)dst + li * rec, src + gi * rec, len * rec, hipMemcpyHostToDevice, stream_));
+    }
+    return MSMZ_OK;
+  }
+
+  // *word = the meta error word as the launches queued so far leave it (one host round trip).  What a bit means is the
+  // caller's to say: it differs between the kernels that raise them.
+  int fetch_error(uint32_t* word) {
+    MSMZ_HIP(hipGetLastError());
+    MSMZ_HIP(hipMemcpyAsync(&h_meta_->error, &meta_.as<MsmMeta>()->error, 4, hipMemcpyDeviceToHost, stream_));
+    MSMZ_HIP(hipStreamSynchronize(stream_));
+    *word = h_meta_->error;
+    return MSMZ_OK;
+  }
+
+  // the device memory of a new handle (owned by it: an error before add_handle frees it)
+  int alloc_handle(Handle& hd, size_t bytes) {
+    MSMZ_HIP(hipMalloc(&hd.mem.p, bytes));
+    hd.mem.bytes = bytes;
+    return MSMZ_OK;
+  }
+  int add_handle(Handle&& hd, uint64_t* h) {
+    *h = next_handle_++;
+    handles_.emplace(*h, std::move(hd));
+    return MSMZ_OK;
+  }
+
+  // The options of an MSM over handle `h`: a precomputed set fixes c and the GLV choice (opts->c must be 0 or its c,
+  // opts->glv -1 or its choice; a null opts means both defaults) and takes batched-affine buckets with the 2-D reduction.
+  int resolve_opts(const Handle& h, const msmz_opts* o, msmz_opts* opt) const {
+    memset(opt, 0, sizeof(*opt));
+    if (o) *opt = *o;
+    if (!h.factor) return MSMZ_OK;
+    if (!o) opt->glv = -1;
+    if (opt->buckets == MSMZ_BUCKETS_PROJECTIVE || opt->reserved[0] == 1) return MSMZ_ERR_UNSUPPORTED;
+    if ((opt->c != 0 && opt->c != h.c) || (opt->glv >= 0 && (opt->glv != 0) != (h.glv != 0))) return MSMZ_ERR_ARG;
+    opt->c = h.c;
+    opt->glv = h.glv;
+    return MSMZ_OK;
+  }
+
   // How a shape runs is decided here.  Up to `remaining` problems over device scalars; *ran = how many it ran.
   //  - one batched pipeline over a sub-batch of them (planner_.batch_size): Weierstrass batched-affine buckets with the
   //    2-D reduction, n within one sort pass, and a sub-batch plan the two-level sort takes -- a plan that falls off it
@@ -613,393 +646,6 @@ class Engine : public IEngine {
     *redo = Redo::NONE;
     st = attempt(1, redo);
     return *redo == Redo::PROVEN_BITS ? MSMZ_ERR_ARG : st;
-  }
-
-  // ------------------------------------------------------------------------------------------ stage-level test hooks
-  // (include/msmz_test.h: one device routine at a time, raw outputs)
-  int test_buffers(size_t in_bytes, size_t out_bytes, uint8_t** d_in, uint8_t** d_out) {
-    int st = stage_.ensure(in_bytes + out_bytes + 256);
-    if (st) return st;
-    *d_in = stage_.as<uint8_t>();
-    *d_out = stage_.as<uint8_t>() + ((in_bytes + 255) & ~(size_t)255);
-    return MSMZ_OK;
-  }
-
-  int test_set_glv_bits(int bits) override {
-    if (!Fr::HAS_GLV) return MSMZ_ERR_UNSUPPORTED;
-    if (bits != 0 && (bits < 8 || bits > Fr::GLV_BITS - 1)) return MSMZ_ERR_ARG;
-    planner_.k.glv_bits_assumed = bits;
-    return MSMZ_OK;
-  }
-  int test_retries() override { return retries_; }
-
-  int test_field(int op, const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out) override {
-    if (!a || !b || !out || n == 0 || n > (1u << 22)) return MSMZ_ERR_ARG;
-    MSMZ_HIP(hipSetDevice(device_));
-    const size_t eb = (size_t)FE_BYTES * n;
-    uint8_t *d_in, *d_out;
-    int st = test_buffers(2 * eb, eb, &d_in, &d_out);
-    if (st) return st;
-    if ((st = slots_.ensure(((size_t)n + 64) * SlotFmt<F>::WORDS * 4))) return st;
-    MSMZ_HIP(hipMemcpyAsync(d_in, a, eb, hipMemcpyHostToDevice, stream_));
-    MSMZ_HIP(hipMemcpyAsync(d_in + eb, b, eb, hipMemcpyHostToDevice, stream_));
-    hipLaunchKernelGGL((k_test_field<F>), dim3((n + 63) / 64), dim3(64), 0, stream_, (uint32_t*)d_out,
-                       (const uint32_t*)d_in, (const uint32_t*)(d_in + eb), (uint32_t)n, op, slots_.as<uint32_t>());
-    MSMZ_HIP(hipGetLastError());
-    MSMZ_HIP(hipMemcpyAsync(out, d_out, eb, hipMemcpyDeviceToHost, stream_));
-    MSMZ_HIP(hipStreamSynchronize(stream_));
-    return MSMZ_OK;
-  }
-
-  int test_field_limbs(int op, const int32_t* a, const int32_t* b, uint64_t n, int32_t* raw, uint8_t* canon) override {
-    if (!a || !b || !raw || !canon || n == 0 || n > (1u << 22) || op < 0 || op >= TFL_COUNT) return MSMZ_ERR_ARG;
-    MSMZ_HIP(hipSetDevice(device_));
-    const size_t lb = (size_t)4 * F::N * n, eb = (size_t)FE_BYTES * n;
-    uint8_t *d_in, *d_out;
-    int st = test_buffers(2 * lb, lb + eb, &d_in, &d_out);
-    if (st) return st;
-    if ((st = slots_.ensure(((size_t)n + 64) * SlotFmt<F>::WORDS * 4))) return st;
-    MSMZ_HIP(hipMemcpyAsync(d_in, a, lb, hipMemcpyHostToDevice, stream_));
-    MSMZ_HIP(hipMemcpyAsync(d_in + lb, b, lb, hipMemcpyHostToDevice, stream_));
-    hipLaunchKernelGGL((k_test_field_limbs<F>), dim3((n + 63) / 64), dim3(64), 0, stream_, (int32_t*)d_out,
-                       (uint32_t*)(d_out + lb), (const int32_t*)d_in, (const int32_t*)(d_in + lb), (uint32_t)n, op,
-                       slots_.as<uint32_t>());
-    MSMZ_HIP(hipGetLastError());
-    MSMZ_HIP(hipMemcpyAsync(raw, d_out, lb, hipMemcpyDeviceToHost, stream_));
-    MSMZ_HIP(hipMemcpyAsync(canon, d_out + lb, eb, hipMemcpyDeviceToHost, stream_));
-    MSMZ_HIP(hipStreamSynchronize(stream_));
-    return MSMZ_OK;
-  }
-
-  int test_glv(const uint8_t* s, uint64_t n, uint8_t* s0, uint8_t* s1, uint8_t* neg) override {
-    if (!Fr::HAS_GLV) return MSMZ_ERR_UNSUPPORTED;
-    if (!s || !s0 || !s1 || !neg || n == 0 || n > (1u << 22)) return MSMZ_ERR_ARG;
-    MSMZ_HIP(hipSetDevice(device_));
-    uint8_t *d_in, *d_out;
-    int st = test_buffers(32 * n, 34 * n, &d_in, &d_out);
-    if (st) return st;
-    MSMZ_HIP(hipMemcpyAsync(d_in, s, 32 * n, hipMemcpyHostToDevice, stream_));
-    hipLaunchKernelGGL((k_test_glv<Fr>), dim3((n + 255) / 256), dim3(256), 0, stream_, (uint32_t*)d_out,
-                       (uint32_t*)(d_out + 16 * n), d_out + 32 * n, (const uint32_t*)d_in, (uint32_t)n);
-    MSMZ_HIP(hipGetLastError());
-    MSMZ_HIP(hipMemcpyAsync(s0, d_out, 16 * n, hipMemcpyDeviceToHost, stream_));
-    MSMZ_HIP(hipMemcpyAsync(s1, d_out + 16 * n, 16 * n, hipMemcpyDeviceToHost, stream_));
-    MSMZ_HIP(hipMemcpyAsync(neg, d_out + 32 * n, 2 * n, hipMemcpyDeviceToHost, stream_));
-    MSMZ_HIP(hipStreamSynchronize(stream_));
-    return MSMZ_OK;
-  }
-
-  int test_digits(const uint8_t* s, uint64_t n, int c, int K, int glv, uint32_t* digits) override {
-    if (!s || !digits || n == 0 || n > (1u << 22) || c < 2 || c > 24 || K < 1 || K > kMaxWindows) return MSMZ_ERR_ARG;
-    if (glv && !Fr::HAS_GLV) return MSMZ_ERR_UNSUPPORTED;
-    MSMZ_HIP(hipSetDevice(device_));
-    const size_t ob = (size_t)(glv ? 2 : 1) * n * K * 4;
-    uint8_t *d_in, *d_out;
-    int st = test_buffers(32 * n, ob, &d_in, &d_out);
-    if (st) return st;
-    MSMZ_HIP(hipMemcpyAsync(d_in, s, 32 * n, hipMemcpyHostToDevice, stream_));
-    if (glv) {
-      if constexpr (Fr::HAS_GLV)
-        hipLaunchKernelGGL((k_test_digits<Fr, true>), dim3((n + 255) / 256), dim3(256), 0, stream_, (uint32_t*)d_out,
-                           (const uint32_t*)d_in, (uint32_t)n, c, K);
-    } else {
-      hipLaunchKernelGGL((k_test_digits<Fr, false>), dim3((n + 255) / 256), dim3(256), 0, stream_, (uint32_t*)d_out,
-                         (const uint32_t*)d_in, (uint32_t)n, c, K);
-    }
-    MSMZ_HIP(hipGetLastError());
-    MSMZ_HIP(hipMemcpyAsync(digits, d_out, ob, hipMemcpyDeviceToHost, stream_));
-    MSMZ_HIP(hipStreamSynchronize(stream_));
-    return MSMZ_OK;
-  }
-
-  int test_sort(const uint8_t* s, uint64_t n, int c, int glv, int force_fallback, uint32_t* geom, uint32_t* off,
-                uint64_t off_cap, uint32_t* refs, uint64_t refs_cap) override {
-    if (!s || !geom || n == 0 || n > (1u << 22)) return MSMZ_ERR_ARG;
-    if (glv && !Fr::HAS_GLV) return MSMZ_ERR_UNSUPPORTED;
-    MSMZ_HIP(hipSetDevice(device_));
-    msmz_opts opt;
-    memset(&opt, 0, sizeof(opt));
-    opt.c = c;
-    Planner<Fr> pr = planner_;
-    pr.k.force_atomic_sort = pr.k.force_atomic_sort || force_fallback != 0;
-    Plan pl;
-    int st = pr.make_plan(pl, n, glv != 0, opt, (uint32_t)n, !TE);
-    if (st) return st;
-    DevBuf d_scalars;   // (freed on every return)
-    MSMZ_HIP(hipMalloc(&d_scalars.p, 32 * n));
-    MSMZ_HIP(hipMemcpyAsync(d_scalars.p, s, 32 * n, hipMemcpyHostToDevice, stream_));
-    Run run = new_run(opt);
-    if ((st = sort_phase(pl, pr.sort_layout(pl), d_scalars.as<const uint32_t>(), run, 0)) || (st = fetch_meta(run)))
-      return st;
-    if (h_meta_->error & 4u) return MSMZ_ERR_RANGE;
-    const uint32_t g8[8] = {(uint32_t)pl.c, (uint32_t)pl.K, (uint32_t)pl.Keff, pl.L, pl.nb, run.n_entries, run.max_bucket,
-                            (uint32_t)pl.spread};
-    memcpy(geom, g8, sizeof(g8));
-    if (off) {
-      if (off_cap < (uint64_t)pl.nb + 1) return MSMZ_ERR_ARG;
-      MSMZ_HIP(hipMemcpy(off, off_.p, ((size_t)pl.nb + 1) * 4, hipMemcpyDeviceToHost));
-    }
-    if (refs) {
-      if (refs_cap < run.n_entries) return MSMZ_ERR_ARG;
-      if (run.n_entries) MSMZ_HIP(hipMemcpy(refs, refs_.p, (size_t)run.n_entries * 4, hipMemcpyDeviceToHost));
-    }
-    return MSMZ_OK;
-  }
-
-  int test_point(int op, const uint8_t* a, const uint8_t* a_inf, const uint8_t* b, const uint8_t* b_inf, uint64_t n,
-                 uint8_t* out) override {
-    if (!a || !b || !out || n == 0 || n > (1u << 20)) return MSMZ_ERR_ARG;
-    MSMZ_HIP(hipSetDevice(device_));
-    const size_t pb = (size_t)2 * FE_BYTES * n;
-    uint8_t *d_in, *d_out;
-    int st = test_buffers(2 * pb + 2 * n, pb, &d_in, &d_out);
-    if (st) return st;
-    MSMZ_HIP(hipMemcpyAsync(d_in, a, pb, hipMemcpyHostToDevice, stream_));
-    MSMZ_HIP(hipMemcpyAsync(d_in + pb, b, pb, hipMemcpyHostToDevice, stream_));
-    uint8_t* d_ai = nullptr;
-    uint8_t* d_bi = nullptr;
-    if (a_inf) {
-      d_ai = d_in + 2 * pb;
-      MSMZ_HIP(hipMemcpyAsync(d_ai, a_inf, n, hipMemcpyHostToDevice, stream_));
-    }
-    if (b_inf) {
-      d_bi = d_in + 2 * pb + n;
-      MSMZ_HIP(hipMemcpyAsync(d_bi, b_inf, n, hipMemcpyHostToDevice, stream_));
-    }
-    using P = typename std::conditional<TE, TePolicy<F>, WeierPolicy<F>>::type;
-    const uint64_t threads = (op == TP_ADD_X4 || op == TP_DBL_X4) ? 4 * n : n;
-    hipLaunchKernelGGL((k_test_point<P, TE>), dim3((threads + 63) / 64), dim3(64), 0, stream_, (uint32_t*)d_out,
-                       (const uint32_t*)d_in, (const uint32_t*)(d_in + pb), d_ai, d_bi, (uint32_t)n, op);
-    MSMZ_HIP(hipGetLastError());
-    MSMZ_HIP(hipMemcpyAsync(out, d_out, pb, hipMemcpyDeviceToHost, stream_));
-    MSMZ_HIP(hipStreamSynchronize(stream_));
-    return MSMZ_OK;
-  }
-
-  int test_point_raw(int op, const uint8_t* a, const uint8_t* b, const uint8_t* neg, uint64_t n, int L,
-                     uint8_t* out) override {
-    if (!a || !b || !out || n == 0 || n > (1u << 20) || op < 0 || op >= TPR_COUNT || L < 0 || L > 4096)
-      return MSMZ_ERR_ARG;
-    if (TE && op == TPR_MDBL) return MSMZ_ERR_UNSUPPORTED;
-    MSMZ_HIP(hipSetDevice(device_));
-    const size_t rb = (size_t)4 * FE_BYTES * n, pb = (size_t)2 * FE_BYTES * n;
-    uint8_t *d_in, *d_out;
-    int st = test_buffers(2 * rb + n, pb, &d_in, &d_out);
-    if (st) return st;
-    MSMZ_HIP(hipMemcpyAsync(d_in, a, rb, hipMemcpyHostToDevice, stream_));
-    MSMZ_HIP(hipMemcpyAsync(d_in + rb, b, rb, hipMemcpyHostToDevice, stream_));
-    uint8_t* d_neg = nullptr;
-    if (neg) {
-      d_neg = d_in + 2 * rb;
-      MSMZ_HIP(hipMemcpyAsync(d_neg, neg, n, hipMemcpyHostToDevice, stream_));
-    }
-    using P = typename std::conditional<TE, TePolicy<F>, WeierPolicy<F>>::type;
-    const bool x4 = op == TPR_ADD_X4 || op == TPR_DBL_X4 || op == TPR_CHAIN_X4;
-    const uint64_t threads = x4 ? 4 * n : n;
-    hipLaunchKernelGGL((k_test_point_raw<P, TE>), dim3((threads + 63) / 64), dim3(64), 0, stream_, (uint32_t*)d_out,
-                       (const uint32_t*)d_in, (const uint32_t*)(d_in + rb), d_neg, (uint32_t)n, op, L);
-    MSMZ_HIP(hipGetLastError());
-    MSMZ_HIP(hipMemcpyAsync(out, d_out, pb, hipMemcpyDeviceToHost, stream_));
-    MSMZ_HIP(hipStreamSynchronize(stream_));
-    return MSMZ_OK;
-  }
-
-  int test_batch_add(int safe, int B, const uint8_t* pxy, const uint8_t* pinf, uint64_t np, const uint8_t* sxy,
-                     const uint8_t* sinf, uint64_t ns, const uint32_t* desc, uint64_t n_pairs, uint64_t out_base,
-                     uint8_t* out, uint32_t* error) override {
-    if (TE) return MSMZ_ERR_UNSUPPORTED;
-    constexpr uint64_t CAP = 1u << 22;
-    if (!desc || !out || !error || (safe != 0 && safe != 1) || B < 1 || B > MSMZ_BATCH_BMAX) return MSMZ_ERR_ARG;
-    if (n_pairs == 0 || n_pairs > CAP || np > CAP || ns > CAP || (np && !pxy) || (ns && !sxy)) return MSMZ_ERR_ARG;
-    if (out_base < ns || out_base > CAP) return MSMZ_ERR_ARG;
-    // every location names a supplied operand: the kernel reads whatever its descriptors point at
-    for (uint64_t k = 0; k < 2 * n_pairs; k++) {
-      const uint32_t w = desc[k];
-      if ((w & LOC_ORIG) ? (w & 0x3fffffffu) >= np : w >= ns) return MSMZ_ERR_ARG;
-    }
-    MSMZ_HIP(hipSetDevice(device_));
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t pb = (size_t)RW * 4 * np, sb = (size_t)RW * 4 * ns, db = (size_t)8 * n_pairs;
-    const size_t o_pinf = up(pb), o_sxy = o_pinf + up(np), o_sinf = o_sxy + up(sb), o_desc = o_sinf + up(ns);
-    uint8_t *d_in, *d_out;
-    int st = test_buffers(o_desc + db, (size_t)RW * 4 * n_pairs, &d_in, &d_out);
-    if (st) return st;
-    DevBuf d_pts;   // the resident point set (freed on every return)
-    if ((st = d_pts.ensure((np ? np : 1) * PW_WORDS * 4))) return st;
-    // slot records 0 .. out_base + n_pairs - 1 in whole groups of 64, as the MSM sizes them; filled with a pattern
-    // that decodes to no result, so a record the launch leaves unwritten cannot pass for one
-    const uint32_t recs = (uint32_t)(out_base + n_pairs);
-    if ((st = slots_.ensure(((size_t)recs + 64) * SlotFmt<F>::WORDS * 4))) return st;
-    MSMZ_HIP(hipMemsetAsync(slots_.p, 0xa5, slot_words((recs + 63u) & ~63u) * 4, stream_));
-    if (np) MSMZ_HIP(hipMemcpyAsync(d_in, pxy, pb, hipMemcpyHostToDevice, stream_));
-    if (np && pinf) MSMZ_HIP(hipMemcpyAsync(d_in + o_pinf, pinf, np, hipMemcpyHostToDevice, stream_));
-    if (ns) MSMZ_HIP(hipMemcpyAsync(d_in + o_sxy, sxy, sb, hipMemcpyHostToDevice, stream_));
-    if (ns && sinf) MSMZ_HIP(hipMemcpyAsync(d_in + o_sinf, sinf, ns, hipMemcpyHostToDevice, stream_));
-    MSMZ_HIP(hipMemcpyAsync(d_in + o_desc, desc, db, hipMemcpyHostToDevice, stream_));
-    MsmMeta* d_meta = meta_.as<MsmMeta>();
-    MSMZ_HIP(hipMemsetAsync(&d_meta->error, 0, 4, stream_));
-    if constexpr (!TE) {
-      if (np)
-        hipLaunchKernelGGL((k_points_to_mont<F>), dim3((np + 255) / 256), dim3(256), 0, stream_, d_pts.as<uint32_t>(),
-                           (const uint32_t*)d_in, pinf ? d_in + o_pinf : nullptr, (uint32_t)np, 0, &d_meta->error);
-      if (ns)
-        hipLaunchKernelGGL((k_test_slots_in<F>), dim3((ns + 255) / 256), dim3(256), 0, stream_, slots_.as<uint32_t>(),
-                           (const uint32_t*)(d_in + o_sxy), sinf ? d_in + o_sinf : nullptr, (uint32_t)ns,
-                           &d_meta->error);
-      MSMZ_HIP(hipGetLastError());
-      MSMZ_HIP(hipMemcpyAsync(&h_meta_->error, &d_meta->error, 4, hipMemcpyDeviceToHost, stream_));
-      MSMZ_HIP(hipStreamSynchronize(stream_));
-      if (h_meta_->error) return MSMZ_ERR_RANGE;   // a coordinate >= p
-      launch_batch_add_b(B, (uint32_t)n_pairs, safe != 0, d_pts.as<uint32_t>(), (const uint2*)(d_in + o_desc),
-                         (uint32_t)out_base, d_meta);
-      MSMZ_HIP(hipGetLastError());
-      hipLaunchKernelGGL((k_test_slots_out<F>), dim3((n_pairs + 255) / 256), dim3(256), 0, stream_,
-                         (uint32_t*)d_out, slots_.as<uint32_t>(), (uint32_t)out_base, (uint32_t)n_pairs);
-      MSMZ_HIP(hipGetLastError());
-      MSMZ_HIP(hipMemcpyAsync(&h_meta_->error, &d_meta->error, 4, hipMemcpyDeviceToHost, stream_));
-      MSMZ_HIP(hipMemcpyAsync(out, d_out, (size_t)RW * 4 * n_pairs, hipMemcpyDeviceToHost, stream_));
-      MSMZ_HIP(hipStreamSynchronize(stream_));
-      *error = h_meta_->error;
-    }
-    return MSMZ_OK;
-  }
-
-  // The bucket reduction on caller-built buckets (msmz_test.h): the level-selection knobs hold for this call only.
-  int test_reduce(const msmz_test_reduce_args& a) override {
-    const uint32_t tail0 = tail_n_, quad0 = quad16_max_groups_, pair0 = pairsum_x4_max_, nc0 = planner_.k.r2_nc;
-    const int st = test_reduce_run(a);
-    tail_n_ = tail0, quad16_max_groups_ = quad0, pairsum_x4_max_ = pair0, planner_.k.r2_nc = nc0;
-    return st;
-  }
-  int test_reduce_run(const msmz_test_reduce_args& a) {
-    using P = typename std::conditional<TE, TePolicy<F>, WeierPolicy<F>>::type;
-    constexpr int AW = P::ACC_WORDS;
-    constexpr uint64_t CAP = 1u << 20;
-    const bool levels = a.mode == MSMZ_TR_LEVELS, locs = a.mode == MSMZ_TR_LOCATIONS;
-    if (a.mode < MSMZ_TR_LOCATIONS || a.mode > MSMZ_TR_LEVELS || !a.out_xy) return MSMZ_ERR_ARG;
-    if (TE && locs) return MSMZ_ERR_UNSUPPORTED;
-    if (a.tail_n > 4096 || a.quad16_max > CAP || a.pairsum_x4_max > CAP) return MSMZ_ERR_ARG;
-    if (a.n_points > CAP || a.n_slots > CAP || (a.n_points && !a.points_xy) || (a.n_slots && !a.slots_xy)) return MSMZ_ERR_ARG;
-    // geometry: a plan of `nsets` bucket sets of window size c, as far as reduce_2d / reduce_levels read one
-    Plan pl{};
-    pl.nprob = 1;
-    pl.F = 1;
-    uint32_t nb = 0, n_res = a.nsets, H = 0;
-    if (levels) {
-      if (a.nsets < 1 || a.nsets > 64 || a.n_in < 1 || a.n_in > 4096 || a.nc != 0) return MSMZ_ERR_ARG;
-      if (a.n_points != (uint64_t)2 * a.nsets * a.n_in) return MSMZ_ERR_ARG;
-      pl.Keff = (int)a.nsets;
-    } else {
-      if (a.c < 2 || a.c > 16 || a.nsets < 1 || a.nsets > 16) return MSMZ_ERR_ARG;
-      pl.c = a.c;
-      pl.L = 1u << (a.c - 1);
-      pl.Keff = pl.K = (int)a.nsets;
-      nb = pl.nb = a.nsets * pl.L;
-      const Split2d sp = planner_.split_2d(pl);
-      if (a.nc != 0 && ((a.nc & (a.nc - 1)) != 0 || a.nc > sp.D)) return MSMZ_ERR_ARG;
-      H = sp.H;
-      n_res = 2 * a.nsets;
-      // every location / chunk range names a supplied operand: the kernels read whatever these point at
-      if (locs) {
-        if (!a.loc) return MSMZ_ERR_ARG;
-        for (uint64_t k = 0; k < (uint64_t)4 * nb; k++) {
-          const uint32_t w = a.loc[k];
-          if (w == LOC_NONE) {
-            k |= 3;   // (the rest of this bucket's words is never read)
-            continue;
-          }
-          if ((w & LOC_ORIG) ? (w & 0x3fffffffu) >= a.n_points : w >= a.n_slots) return MSMZ_ERR_ARG;
-        }
-      } else {
-        if (!a.cscan || a.cscan[nb] > a.n_points) return MSMZ_ERR_ARG;
-        for (uint32_t g = 0; g < nb; g++)
-          if (a.cscan[g] > a.cscan[g + 1]) return MSMZ_ERR_ARG;
-      }
-    }
-    if (a.scale && locs) return MSMZ_ERR_ARG;
-    if (a.tail_n) tail_n_ = a.tail_n;
-    if (a.quad16_max) quad16_max_groups_ = a.quad16_max;
-    if (a.pairsum_x4_max) pairsum_x4_max_ = a.pairsum_x4_max;
-    if (a.nc) planner_.k.r2_nc = a.nc;
-    const uint32_t n_lines = levels || !a.lines_xy ? 0 : n_res * H;
-
-    MSMZ_HIP(hipSetDevice(device_));
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t np = a.n_points, ns = a.n_slots;
-    const size_t pb = (size_t)RW * 4 * np, sb = (size_t)RW * 4 * ns, lb = (size_t)FE_BYTES * np;
-    const size_t o_pinf = up(pb), o_scale = o_pinf + up(np), o_sxy = o_scale + up(lb), o_sinf = o_sxy + up(sb);
-    const size_t in_bytes = o_sinf + up(ns), res_bytes = up((size_t)RW * 4 * n_res);
-    uint8_t *d_in, *d_out;
-    int st = test_buffers(in_bytes, res_bytes + (size_t)RW * 4 * n_lines, &d_in, &d_out);
-    if (st) return st;
-    if (np) MSMZ_HIP(hipMemcpyAsync(d_in, a.points_xy, pb, hipMemcpyHostToDevice, stream_));
-    if (np && a.points_inf) MSMZ_HIP(hipMemcpyAsync(d_in + o_pinf, a.points_inf, np, hipMemcpyHostToDevice, stream_));
-    if (np && a.scale) MSMZ_HIP(hipMemcpyAsync(d_in + o_scale, a.scale, lb, hipMemcpyHostToDevice, stream_));
-    if (ns) MSMZ_HIP(hipMemcpyAsync(d_in + o_sxy, a.slots_xy, sb, hipMemcpyHostToDevice, stream_));
-    if (ns && a.slots_inf) MSMZ_HIP(hipMemcpyAsync(d_in + o_sinf, a.slots_inf, ns, hipMemcpyHostToDevice, stream_));
-    MsmMeta* d_meta = meta_.as<MsmMeta>();
-    MSMZ_HIP(hipMemsetAsync(&d_meta->error, 0, 4, stream_));
-    const uint8_t* d_pinf = a.points_inf ? d_in + o_pinf : nullptr;
-    // accumulator records `first .. first + n` of the input points, in the policy's memory format
-    auto accs_in = [&](uint32_t* dst, size_t first, size_t n) {
-      if (n)
-        hipLaunchKernelGGL((k_test_accs_in<P, TE>), dim3((n + 255) / 256), dim3(256), 0, stream_, dst,
-                           (const uint32_t*)d_in + first * RW, d_pinf ? d_pinf + first : nullptr,
-                           a.scale ? (const uint32_t*)(d_in + o_scale) + first * NW : nullptr, (uint32_t)n,
-                           &d_meta->error);
-    };
-    DevBuf d_pts, d_lines;   // (freed on every return)
-    if (levels) {
-      const size_t n = (size_t)a.nsets * a.n_in;
-      if ((st = red_[0].ensure(n * AW * 4)) || (st = red_[1].ensure(n * AW * 4))) return st;
-      accs_in(red_[0].as<uint32_t>(), 0, n);
-      accs_in(red_[1].as<uint32_t>(), n, n);
-    } else if (locs) {
-      if constexpr (!TE) {
-        if ((st = d_pts.ensure((np ? np : 1) * PW_WORDS * 4))) return st;
-        if ((st = bfin_.ensure((size_t)nb * 16))) return st;
-        if ((st = slots_.ensure(((size_t)ns + 64) * SlotFmt<F>::WORDS * 4))) return st;
-        MSMZ_HIP(hipMemsetAsync(slots_.p, 0xa5, slot_words(((uint32_t)ns + 63u) & ~63u) * 4, stream_));
-        MSMZ_HIP(hipMemcpyAsync(bfin_.p, a.loc, (size_t)nb * 16, hipMemcpyHostToDevice, stream_));
-        if (np)
-          hipLaunchKernelGGL((k_points_to_mont<F>), dim3((np + 255) / 256), dim3(256), 0, stream_, d_pts.as<uint32_t>(),
-                             (const uint32_t*)d_in, d_pinf, (uint32_t)np, 0, &d_meta->error);
-        if (ns)
-          hipLaunchKernelGGL((k_test_slots_in<F>), dim3((ns + 255) / 256), dim3(256), 0, stream_, slots_.as<uint32_t>(),
-                             (const uint32_t*)(d_in + o_sxy), a.slots_inf ? d_in + o_sinf : nullptr, (uint32_t)ns,
-                             &d_meta->error);
-      }
-    } else {
-      if ((st = slots_.ensure((np + 1) * AW * 4)) || (st = rscan_.ensure(((size_t)nb + 1) * 4))) return st;
-      MSMZ_HIP(hipMemcpyAsync(rscan_.p, a.cscan, ((size_t)nb + 1) * 4, hipMemcpyHostToDevice, stream_));
-      accs_in(slots_.as<uint32_t>(), 0, np);
-    }
-    MSMZ_HIP(hipGetLastError());
-    MSMZ_HIP(hipMemcpyAsync(&h_meta_->error, &d_meta->error, 4, hipMemcpyDeviceToHost, stream_));
-    MSMZ_HIP(hipStreamSynchronize(stream_));
-    if (h_meta_->error & 4u) return MSMZ_ERR_RANGE;   // a coordinate or scale >= p
-    if (h_meta_->error) return MSMZ_ERR_ARG;          // a zero scale
-
-    if (levels) {
-      int cur = 0;
-      if ((st = reduce_levels<P>(pl, cur, a.n_in, a.nsets))) return st;
-    } else {
-      const bool summed = a.mode == MSMZ_TR_ACCS_SUMMED;
-      if (summed && (st = bucket_sums<P>(nb))) return st;
-      if ((st = reduce_2d<P>(pl, d_pts.as<uint32_t>(), !locs, summed, n_lines ? &d_lines : nullptr))) return st;
-    }
-    MSMZ_HIP(hipGetLastError());
-    hipLaunchKernelGGL((k_test_accs_out<P, TE>), dim3((n_res + 63) / 64), dim3(64), 0, stream_, (uint32_t*)d_out,
-                       final_.as<uint32_t>(), n_res);
-    if (n_lines)
-      hipLaunchKernelGGL((k_test_accs_out<P, TE>), dim3((n_lines + 63) / 64), dim3(64), 0, stream_,
-                         (uint32_t*)(d_out + res_bytes), d_lines.as<uint32_t>(), n_lines);
-    MSMZ_HIP(hipGetLastError());
-    MSMZ_HIP(hipMemcpyAsync(a.out_xy, d_out, (size_t)RW * 4 * n_res, hipMemcpyDeviceToHost, stream_));
-    if (n_lines)
-      MSMZ_HIP(hipMemcpyAsync(a.lines_xy, d_out + res_bytes, (size_t)RW * 4 * n_lines, hipMemcpyDeviceToHost, stream_));
-    MSMZ_HIP(hipStreamSynchronize(stream_));
-    return MSMZ_OK;
   }
 
   // ------------------------------------------------------------------------------------------ shared phases
@@ -1163,18 +809,17 @@ class Engine : public IEngine {
 
   // reduce levels on accumulator records: rows in red_[cur*2], C in red_[cur*2+1]; ends with one entry per window
   template <class P>
-  int reduce_levels(const Plan& pl, int& cur, uint32_t n_in, uint32_t nprob = 0) {
+  int reduce_levels(const ReduceKnobs& rk, int& cur, uint32_t n_in, uint32_t nprob) {
     constexpr int AW = P::ACC_WORDS;
     int st;
-    if (nprob == 0) nprob = (uint32_t)pl.Keff;   // independent weighted sums ("windows") the levels run side by side
-    while (n_in > tail_n_) {
+    while (n_in > rk.tail_n) {
       const uint32_t S = 4;   // quads handle short tails too
       uint32_t g2 = (n_in + S - 1) / S;
       int nxt = cur ^ 1;
       if ((st = red_[nxt * 2].ensure((size_t)nprob * g2 * AW * 4))) return st;
       if ((st = red_[nxt * 2 + 1].ensure((size_t)nprob * g2 * AW * 4))) return st;
       uint32_t total = nprob * g2;
-      if (total <= quad16_max_groups_) {
+      if (total <= rk.quad16_max) {
         // small level: latency-bound, one DPP quad per addition
         hipLaunchKernelGGL((k_reduce_quad16<P>), dim3((total * 16 + 63) / 64), dim3(64), 0, stream_,
                            red_[nxt * 2].as<uint32_t>(), red_[nxt * 2 + 1].as<uint32_t>(),
@@ -1261,12 +906,16 @@ class Engine : public IEngine {
   // Two-dimensional bucket reduction (reduce2d_kernels.h): line sums, then the weighted sums over H lines of 2 Keff
   // problems with the upper-level kernels.  Leaves result 2 kw (rows) / 2 kw + 1 (columns) of bucket set kw in final_.
   // basic = true: the buckets are sums of partial accumulators (msmBasic path: slots_ + rscan_), else the affine bucket
-  // sums of the tree rounds (bfin_)
-  // lines_out (test_reduce only): receives a copy of the line sums, the rows the weighted levels start from
+  // sums of the tree rounds (bfin_).  sp: the planner's split of pl (planner_.split_2d); rk: which kernel a level runs.
   template <class P>
-  int reduce_2d(const Plan& pl, const uint32_t* d_points, bool basic = false, bool summed = false,
-                DevBuf* lines_out = nullptr) {
-    const Split2d sp = planner_.split_2d(pl);
+  int reduce_2d(const Plan& pl, const Split2d& sp, const ReduceKnobs& rk, const uint32_t* d_points, bool basic = false,
+                bool summed = false) {
+    const R2Geom g = r2_geom(pl, sp);
+    int rows = 0;
+    if (int st = line_sums_2d<P>(g, rk, d_points, basic, summed, &rows)) return st;
+    return weighted_sums_2d<P>(g, rk, rows);
+  }
+  static R2Geom r2_geom(const Plan& pl, const Split2d& sp) {
     R2Geom g;
     g.L = pl.L;
     g.H = sp.H;
@@ -1275,6 +924,12 @@ class Engine : public IEngine {
     g.chr = sp.D / sp.NC;
     g.chc = sp.H / sp.NC;
     g.nprob = 2u * pl.nprob * (uint32_t)pl.Keff;   // (all bucket sets of a batch)
+    return g;
+  }
+  // first half: the partial sums of every line's chunks, then their pair sums; *rows = the red_ buffer (0 or 2) that
+  // holds the g.nprob * g.H line sums
+  template <class P>
+  int line_sums_2d(const R2Geom& g, const ReduceKnobs& rk, const uint32_t* d_points, bool basic, bool summed, int* rows) {
     const uint32_t lines = g.nprob * g.H;
     const uint32_t total = lines * g.NC;
     int st;
@@ -1295,7 +950,7 @@ class Engine : public IEngine {
     int src = 0;
     for (uint32_t n = total / 2; n >= lines && g.NC > 1; n /= 2) {
       const int dst = src ^ 2;
-      if (n <= pairsum_x4_max_) {
+      if (n <= rk.pairsum_x4_max) {
         hipLaunchKernelGGL((k_pairsum_x4<P>), dim3((n * 4 + 63) / 64), dim3(64), 0, stream_, red_[dst].as<uint32_t>(),
                            red_[src].as<uint32_t>(), n);
       } else {
@@ -1305,16 +960,19 @@ class Engine : public IEngine {
       src = dst;
       if (n == lines) break;
     }
-    // upper levels: rows = line sums (weight unit 1), C = infinity (all-zero accumulator records)
-    const int crow = src, ccol = src + 1;
-    if (lines_out) {
-      if ((st = lines_out->ensure((size_t)lines * XW * 4))) return st;
-      MSMZ_HIP(hipMemcpyAsync(lines_out->p, red_[crow].p, (size_t)lines * XW * 4, hipMemcpyDeviceToDevice, stream_));
-    }
+    *rows = src;
+    return MSMZ_OK;
+  }
+  // second half, the upper levels: rows = the line sums in red_[crow] (weight unit 1), C = infinity (all-zero records)
+  template <class P>
+  int weighted_sums_2d(const R2Geom& g, const ReduceKnobs& rk, int crow) {
+    const uint32_t lines = g.nprob * g.H;
+    const int ccol = crow + 1;
+    int st;
     if ((st = red_[ccol].ensure((size_t)lines * XW * 4))) return st;
     hipLaunchKernelGGL((k_fill_neutral<P>), dim3((lines + 255) / 256), dim3(256), 0, stream_, red_[ccol].as<uint32_t>(), lines);
     int cur = crow >> 1;   // reduce_levels addresses rows as red_[cur * 2], C as red_[cur * 2 + 1]
-    if ((st = reduce_levels<P>(pl, cur, g.H, g.nprob))) return st;
+    if ((st = reduce_levels<P>(rk, cur, g.H, g.nprob))) return st;
     MSMZ_HIP(hipGetLastError());
     return MSMZ_OK;
   }
@@ -1432,7 +1090,7 @@ class Engine : public IEngine {
     // ---- bucket reduction
     if (want_2d) {
       // two-dimensional: row / column sums of the buckets, then two half-length weighted sums per bucket set
-      if ((st = reduce_2d<WeierPolicy<F>>(pl, d_points))) return st;
+      if ((st = reduce_2d<WeierPolicy<F>>(pl, planner_.split_2d(pl), reduce_knobs_, d_points))) return st;
     } else {
       // level 1 from affine bucket sums, then XYZZ levels down to one entry per window.  The weight-L bucket is folded
       // into element L/2, which must be the FIRST element of its group
@@ -1444,7 +1102,7 @@ class Engine : public IEngine {
       if ((st = red_[1].ensure((size_t)pl.Keff * groups * XW * 4))) return st;
       if ((st = reduce_first_affine(pl, d_points, S1, groups, run.n_pairs, d_meta))) return st;
       int cur = 0;
-      if ((st = reduce_levels<WeierPolicy<F>>(pl, cur, groups))) return st;
+      if ((st = reduce_levels<WeierPolicy<F>>(reduce_knobs_, cur, groups, (uint32_t)pl.Keff))) return st;
     }
     return finish_msm(pl, run, want_2d, out, out_inf, log);
   }
@@ -1495,7 +1153,7 @@ class Engine : public IEngine {
     // ed-on-bls12-377 2^24 has 8) are first summed into one accumulator each, in bucket order
     const bool summed = (uint64_t)n_chunks * 2 > (uint64_t)nb * 3 && !no_bucket_sums_;
     if (summed && (st = bucket_sums<P>(nb))) return st;
-    if ((st = reduce_2d<P>(pl, d_points, true, summed))) return st;
+    if ((st = reduce_2d<P>(pl, planner_.split_2d(pl), reduce_knobs_, d_points, true, summed))) return st;
     return finish_msm(pl, run, true, out, out_inf, log);
   }
   // bsum_[g] = sum of the chunk accumulators slots_[rscan_[g] .. rscan_[g+1]) of bucket g < nb
@@ -1675,13 +1333,12 @@ class Engine : public IEngine {
 #endif
   uint32_t batch_min_wgs_ = (uint32_t)env_int("MSMZ_BATCH_WGS", 512);
   int chunk_shift_override_ = env_int("MSMZ_CHUNK_SHIFT", 0);
-  uint32_t tail_n_ = (uint32_t)env_int("MSMZ_TAIL_N", REDUCE_TAIL_N);   // entries per window at which k_reduce_tail takes over
-  uint32_t quad16_max_groups_ = (uint32_t)env_int("MSMZ_QUAD16", 8192);   // levels with at most this many groups use k_reduce_quad16
+  const ReduceKnobs reduce_knobs_{(uint32_t)env_int("MSMZ_TAIL_N", REDUCE_TAIL_N), (uint32_t)env_int("MSMZ_QUAD16", 8192),
+                                  (uint32_t)env_int("MSMZ_PAIRSUM_X4", 16384)};
   Host64<F> host64_;
   bool no_bucket_sums_ = env_int("MSMZ_NO_BUCKET_SUMS", 0) != 0;
   // rounds left to the 2-D reduction's loader: at most 2 (a bucket's final-location record holds 4 partial sums)
   int tail_skip_2d_ = env_int("MSMZ_TAIL_SKIP_2D", 1) > 2 ? 2 : env_int("MSMZ_TAIL_SKIP_2D", 1);
-  uint32_t pairsum_x4_max_ = (uint32_t)env_int("MSMZ_PAIRSUM_X4", 16384);   // pair-sum levels with at most this many additions use DPP quads
   int batch_b_override_ = env_int("MSMZ_BATCH_B", 0);
   int retries_ = 0;            // MSMs redone with the proven GLV bound (test hook reads it)
   // window sizes, geometry, sort layout (plan.h), PlanKnobs in declaration order
@@ -1703,6 +1360,7 @@ class Engine : public IEngine {
     h_res_words_ = words;
     return MSMZ_OK;
   }
+  TestHooks<Cfg> hooks_{*this};
 };
 
 }  // namespace msmz

@@ -24,7 +24,7 @@
 //   k_reduce_affine_*    (reduce_affine.h) optional batched-affine first level (reduceBucketsAffine,
 //                        msm-batched-affine-single-thread.ts:522-667)
 //   k_bucket_accumulate  msmBasic path: buckets in XYZZ / extended coordinates (msm-basic.ts:106-128)
-//   k_test_*             (test_kernels.h) stage-level test hooks of include/msmz_test.h
+//   k_test_*             (test_kernels.h) stage-level test hooks of include/msmz_test.h, launched from test_hooks.h
 //
 // Bucket numbering: global bucket g = k*L + (l-1) for window k and digit l in [1, L], L = 2^(c-1).
 // Sorted references: ref = point_index | (negate << 31).

@@ -8,8 +8,7 @@ MSMZ_WEIERSTRASS_FIELDS(X)
 MSMZ_TE_FIELDS(X)
 #undef X
 }  // namespace msmz
-#include "engine.h"
-#include "../../include/msmz_test.h"
+#include "test_hooks.h"
 
 namespace msmz {
 
@@ -189,40 +188,41 @@ int msmz_precomputed_info(msmz_ctx* c, uint64_t h, int32_t* cc, int32_t* glv, ui
 int msmz_test_set_glv_bits(msmz_ctx* c, int bits) { return c ? c->engine->test_set_glv_bits(bits) : MSMZ_ERR_ARG; }
 int msmz_test_retries(msmz_ctx* c) { return c ? c->engine->test_retries() : -1; }
 int msmz_test_field(msmz_ctx* c, int op, const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out) {
-  return c ? c->engine->test_field(op, a, b, n, out) : MSMZ_ERR_ARG;
+  return c ? c->engine->test_hooks()->test_field(op, a, b, n, out) : MSMZ_ERR_ARG;
 }
 int msmz_test_field_limbs(msmz_ctx* c, int op, const int32_t* a, const int32_t* b, uint64_t n, int32_t* raw,
                           uint8_t* canon) {
-  return c ? c->engine->test_field_limbs(op, a, b, n, raw, canon) : MSMZ_ERR_ARG;
+  return c ? c->engine->test_hooks()->test_field_limbs(op, a, b, n, raw, canon) : MSMZ_ERR_ARG;
 }
 int msmz_test_glv(msmz_ctx* c, const uint8_t* s, uint64_t n, uint8_t* s0, uint8_t* s1, uint8_t* neg) {
-  return c ? c->engine->test_glv(s, n, s0, s1, neg) : MSMZ_ERR_ARG;
+  return c ? c->engine->test_hooks()->test_glv(s, n, s0, s1, neg) : MSMZ_ERR_ARG;
 }
 int msmz_test_digits(msmz_ctx* c, const uint8_t* s, uint64_t n, int cc, int K, int glv, uint32_t* digits) {
-  return c ? c->engine->test_digits(s, n, cc, K, glv, digits) : MSMZ_ERR_ARG;
+  return c ? c->engine->test_hooks()->test_digits(s, n, cc, K, glv, digits) : MSMZ_ERR_ARG;
 }
 int msmz_test_sort(msmz_ctx* c, const uint8_t* s, uint64_t n, int cc, int glv, int force_fallback, uint32_t* geom,
                    uint32_t* off, uint64_t off_cap, uint32_t* refs, uint64_t refs_cap) {
-  return c ? c->engine->test_sort(s, n, cc, glv, force_fallback, geom, off, off_cap, refs, refs_cap) : MSMZ_ERR_ARG;
+  if (!c) return MSMZ_ERR_ARG;
+  return c->engine->test_hooks()->test_sort(s, n, cc, glv, force_fallback, geom, off, off_cap, refs, refs_cap);
 }
 int msmz_test_point_raw(msmz_ctx* c, int op, const uint8_t* a, const uint8_t* b, const uint8_t* neg, uint64_t n, int L,
                         uint8_t* out) {
-  return c ? c->engine->test_point_raw(op, a, b, neg, n, L, out) : MSMZ_ERR_ARG;
+  return c ? c->engine->test_hooks()->test_point_raw(op, a, b, neg, n, L, out) : MSMZ_ERR_ARG;
 }
 int msmz_test_point(msmz_ctx* c, int op, const uint8_t* a, const uint8_t* ai, const uint8_t* b, const uint8_t* bi,
                     uint64_t n, uint8_t* out) {
-  return c ? c->engine->test_point(op, a, ai, b, bi, n, out) : MSMZ_ERR_ARG;
+  return c ? c->engine->test_hooks()->test_point(op, a, ai, b, bi, n, out) : MSMZ_ERR_ARG;
 }
 
 int msmz_test_batch_add(msmz_ctx* c, int safe, int B, const uint8_t* pxy, const uint8_t* pinf, uint64_t np,
                         const uint8_t* sxy, const uint8_t* sinf, uint64_t ns, const uint32_t* desc, uint64_t n_pairs,
                         uint64_t out_base, uint8_t* out, uint32_t* error) {
-  return c ? c->engine->test_batch_add(safe, B, pxy, pinf, np, sxy, sinf, ns, desc, n_pairs, out_base, out, error)
-           : MSMZ_ERR_ARG;
+  if (!c) return MSMZ_ERR_ARG;
+  return c->engine->test_hooks()->test_batch_add(safe, B, pxy, pinf, np, sxy, sinf, ns, desc, n_pairs, out_base, out, error);
 }
 
 int msmz_test_reduce(msmz_ctx* c, const msmz_test_reduce_args* a) {
-  return c && a ? c->engine->test_reduce(*a) : MSMZ_ERR_ARG;
+  return c && a ? c->engine->test_hooks()->test_reduce(*a) : MSMZ_ERR_ARG;
 }
 
 int msmz_point_add(int curve_id, const uint8_t* a, int ai, const uint8_t* b, int bi, uint8_t* out, int* oi) {

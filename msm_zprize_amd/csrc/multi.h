@@ -20,9 +20,10 @@
 #include <vector>
 
 #include "../../include/msmz.h"
-#include "../../include/msmz_test.h"   // msmz_test_reduce_args
 
 namespace msmz {
+
+class ITestHooks;   // the stage-level test hooks of one engine (test_hooks.h)
 
 constexpr int MULTI_BLOCK_SHIFT = 16;
 
@@ -54,29 +55,10 @@ class IEngine {
                                 int* K) const = 0;
   virtual int precompute_points(uint64_t ph, uint64_t n, int c, int glv, uint32_t copies, uint64_t* h) = 0;
   virtual int precomputed_info(uint64_t h, int32_t* c, int32_t* glv, uint32_t* factor, uint32_t* K, uint64_t* records) = 0;
-  // stage-level test hooks (include/msmz_test.h)
+  // tests (include/msmz_test.h); the stage-level hooks are one engine's (a multi-device context: its first engine's)
   virtual int test_set_glv_bits(int) { return MSMZ_ERR_UNSUPPORTED; }
   virtual int test_retries() { return 0; }
-  virtual int test_field(int, const uint8_t*, const uint8_t*, uint64_t, uint8_t*) { return MSMZ_ERR_UNSUPPORTED; }
-  virtual int test_field_limbs(int, const int32_t*, const int32_t*, uint64_t, int32_t*, uint8_t*) {
-    return MSMZ_ERR_UNSUPPORTED;
-  }
-  virtual int test_glv(const uint8_t*, uint64_t, uint8_t*, uint8_t*, uint8_t*) { return MSMZ_ERR_UNSUPPORTED; }
-  virtual int test_digits(const uint8_t*, uint64_t, int, int, int, uint32_t*) { return MSMZ_ERR_UNSUPPORTED; }
-  virtual int test_sort(const uint8_t*, uint64_t, int, int, int, uint32_t*, uint32_t*, uint64_t, uint32_t*, uint64_t) {
-    return MSMZ_ERR_UNSUPPORTED;
-  }
-  virtual int test_point(int, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*, uint64_t, uint8_t*) {
-    return MSMZ_ERR_UNSUPPORTED;
-  }
-  virtual int test_point_raw(int, const uint8_t*, const uint8_t*, const uint8_t*, uint64_t, int, uint8_t*) {
-    return MSMZ_ERR_UNSUPPORTED;
-  }
-  virtual int test_batch_add(int, int, const uint8_t*, const uint8_t*, uint64_t, const uint8_t*, const uint8_t*,
-                             uint64_t, const uint32_t*, uint64_t, uint64_t, uint8_t*, uint32_t*) {
-    return MSMZ_ERR_UNSUPPORTED;
-  }
-  virtual int test_reduce(const msmz_test_reduce_args&) { return MSMZ_ERR_UNSUPPORTED; }
+  virtual ITestHooks* test_hooks() = 0;
 };
 
 // Problems per sub-batch of a batched MSM: at most `cap` entries (problems x entries_per_problem) per sub-batch, and the
@@ -315,36 +297,7 @@ class MultiEngine : public IEngine {
     for (Worker* w : workers_) r += w->eng->test_retries();
     return r;
   }
-  int test_field(int op, const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out) override {
-    return workers_[0]->eng->test_field(op, a, b, n, out);
-  }
-  int test_field_limbs(int op, const int32_t* a, const int32_t* b, uint64_t n, int32_t* raw, uint8_t* canon) override {
-    return workers_[0]->eng->test_field_limbs(op, a, b, n, raw, canon);
-  }
-  int test_glv(const uint8_t* s, uint64_t n, uint8_t* s0, uint8_t* s1, uint8_t* neg) override {
-    return workers_[0]->eng->test_glv(s, n, s0, s1, neg);
-  }
-  int test_digits(const uint8_t* s, uint64_t n, int c, int K, int glv, uint32_t* d) override {
-    return workers_[0]->eng->test_digits(s, n, c, K, glv, d);
-  }
-  int test_sort(const uint8_t* s, uint64_t n, int c, int glv, int fb, uint32_t* geom, uint32_t* off, uint64_t oc,
-                uint32_t* refs, uint64_t rc) override {
-    return workers_[0]->eng->test_sort(s, n, c, glv, fb, geom, off, oc, refs, rc);
-  }
-  int test_point(int op, const uint8_t* a, const uint8_t* ai, const uint8_t* b, const uint8_t* bi, uint64_t n,
-                 uint8_t* out) override {
-    return workers_[0]->eng->test_point(op, a, ai, b, bi, n, out);
-  }
-  int test_point_raw(int op, const uint8_t* a, const uint8_t* b, const uint8_t* neg, uint64_t n, int L,
-                     uint8_t* out) override {
-    return workers_[0]->eng->test_point_raw(op, a, b, neg, n, L, out);
-  }
-  int test_batch_add(int safe, int B, const uint8_t* pxy, const uint8_t* pinf, uint64_t np, const uint8_t* sxy,
-                     const uint8_t* sinf, uint64_t ns, const uint32_t* desc, uint64_t n_pairs, uint64_t out_base,
-                     uint8_t* out, uint32_t* error) override {
-    return workers_[0]->eng->test_batch_add(safe, B, pxy, pinf, np, sxy, sinf, ns, desc, n_pairs, out_base, out, error);
-  }
-  int test_reduce(const msmz_test_reduce_args& a) override { return workers_[0]->eng->test_reduce(a); }
+  ITestHooks* test_hooks() override { return workers_[0]->eng->test_hooks(); }
 
  private:
   struct MHandle {

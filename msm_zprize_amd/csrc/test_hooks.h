@@ -1,0 +1,387 @@
+// Stage-level test hooks (include/msmz_test.h): each runs ONE device routine of the MSM pipeline, or one phase of an
+// engine, on caller-supplied inputs and returns its raw output.  They never take part in an MSM and write to no member
+// of the engine they are given besides its device buffers.
+#pragma once
+#include "../../include/msmz_test.h"
+#include "engine.h"
+#include "test_kernels.h"
+
+namespace msmz {
+
+// The nine msmz_test_* stage entry points of an engine whatever its curve; arguments as in msmz_test.h and TestHooks.
+class ITestHooks {
+ public:
+  virtual ~ITestHooks() {}
+  virtual int test_field(int, const uint8_t*, const uint8_t*, uint64_t, uint8_t*) = 0;
+  virtual int test_field_limbs(int, const int32_t*, const int32_t*, uint64_t, int32_t*, uint8_t*) = 0;
+  virtual int test_glv(const uint8_t*, uint64_t, uint8_t*, uint8_t*, uint8_t*) = 0;
+  virtual int test_digits(const uint8_t*, uint64_t, int, int, int, uint32_t*) = 0;
+  virtual int test_sort(const uint8_t*, uint64_t, int, int, int, uint32_t*, uint32_t*, uint64_t, uint32_t*, uint64_t) = 0;
+  virtual int test_point(int, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*, uint64_t, uint8_t*) = 0;
+  virtual int test_point_raw(int, const uint8_t*, const uint8_t*, const uint8_t*, uint64_t, int, uint8_t*) = 0;
+  virtual int test_batch_add(int, int, const uint8_t*, const uint8_t*, uint64_t, const uint8_t*, const uint8_t*, uint64_t,
+                             const uint32_t*, uint64_t, uint64_t, uint8_t*, uint32_t*) = 0;
+  virtual int test_reduce(const msmz_test_reduce_args&) = 0;
+};
+
+// The regions of an engine's staging buffer that one hook call copies its host arrays into and its results out of, each
+// at 256-byte alignment.  in() / out() lay them out and return their ids; an optional array the caller left out (null)
+// gets none: id -1, device pointer null.  upload() selects the device, sizes the buffer and queues the copies in; after
+// the hook's launches, download() queues the copies out and waits for them.
+struct Staging {
+  struct Region {
+    const void* src;   // the host array copied in, or
+    void* dst;         // the host array copied out
+    size_t off, bytes;
+  };
+  int device;
+  hipStream_t stream;
+  DevBuf& buf;
+  std::vector<Region> regions;
+  size_t total = 0;
+
+  int in(const void* host, size_t bytes) { return add({host, nullptr, total, bytes}, host); }
+  int out(void* host, size_t bytes) { return add({nullptr, host, total, bytes}, host); }
+  int add(const Region& r, const void* host) {
+    if (!host) return -1;
+    regions.push_back(r);
+    total += (r.bytes + 255) & ~(size_t)255;
+    return (int)regions.size() - 1;
+  }
+  template <class T>
+  T* at(int id) const {
+    return id < 0 ? nullptr : reinterpret_cast<T*>(buf.as<uint8_t>() + regions[id].off);
+  }
+  int upload() {
+    MSMZ_HIP(hipSetDevice(device));
+    if (int st = buf.ensure(total)) return st;
+    for (const Region& r : regions)
+      if (r.src && r.bytes)
+        MSMZ_HIP(hipMemcpyAsync(buf.as<uint8_t>() + r.off, r.src, r.bytes, hipMemcpyHostToDevice, stream));
+    return MSMZ_OK;
+  }
+  int download() {
+    MSMZ_HIP(hipGetLastError());
+    for (const Region& r : regions)
+      if (r.dst && r.bytes)
+        MSMZ_HIP(hipMemcpyAsync(r.dst, buf.as<uint8_t>() + r.off, r.bytes, hipMemcpyDeviceToHost, stream));
+    MSMZ_HIP(hipStreamSynchronize(stream));
+    return MSMZ_OK;
+  }
+};
+
+// The hooks of one engine.  A friend of Engine<Cfg>: the hooks launch on its stream, into its buffers, and run its own
+// phases (sort_phase, launch_batch_add_b, bucket_sums, the two halves of reduce_2d, reduce_levels).  Its planner and its
+// reduction thresholds they only read, and vary in copies.
+template <class Cfg>
+class TestHooks : public ITestHooks {
+  using E = Engine<Cfg>;
+  using F = typename Cfg::F;
+  using Fr = typename Cfg::Fr;
+  static constexpr bool TE = Cfg::TE;
+  using P = typename std::conditional<TE, TePolicy<F>, WeierPolicy<F>>::type;
+
+ public:
+  explicit TestHooks(E& engine) : eng_(engine) {}
+
+  int test_field(int op, const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out) override {
+    if (!a || !b || !out || n == 0 || n > (1u << 22)) return MSMZ_ERR_ARG;
+    const size_t eb = (size_t)E::FE_BYTES * n;
+    Staging sg = staging();
+    const int ia = sg.in(a, eb), ib = sg.in(b, eb), io = sg.out(out, eb);
+    int st;
+    if ((st = sg.upload()) || (st = eng_.slots_.ensure(((size_t)n + 64) * SlotFmt<F>::WORDS * 4))) return st;
+    hipLaunchKernelGGL((k_test_field<F>), dim3((n + 63) / 64), dim3(64), 0, eng_.stream_, sg.at<uint32_t>(io),
+                       sg.at<const uint32_t>(ia), sg.at<const uint32_t>(ib), (uint32_t)n, op,
+                       eng_.slots_.template as<uint32_t>());
+    return sg.download();
+  }
+
+  int test_field_limbs(int op, const int32_t* a, const int32_t* b, uint64_t n, int32_t* raw, uint8_t* canon) override {
+    if (!a || !b || !raw || !canon || n == 0 || n > (1u << 22) || op < 0 || op >= TFL_COUNT) return MSMZ_ERR_ARG;
+    const size_t lb = (size_t)4 * F::N * n, eb = (size_t)E::FE_BYTES * n;
+    Staging sg = staging();
+    const int ia = sg.in(a, lb), ib = sg.in(b, lb), iraw = sg.out(raw, lb), icanon = sg.out(canon, eb);
+    int st;
+    if ((st = sg.upload()) || (st = eng_.slots_.ensure(((size_t)n + 64) * SlotFmt<F>::WORDS * 4))) return st;
+    hipLaunchKernelGGL((k_test_field_limbs<F>), dim3((n + 63) / 64), dim3(64), 0, eng_.stream_, sg.at<int32_t>(iraw),
+                       sg.at<uint32_t>(icanon), sg.at<const int32_t>(ia), sg.at<const int32_t>(ib), (uint32_t)n, op,
+                       eng_.slots_.template as<uint32_t>());
+    return sg.download();
+  }
+
+  int test_glv(const uint8_t* s, uint64_t n, uint8_t* s0, uint8_t* s1, uint8_t* neg) override {
+    if (!Fr::HAS_GLV) return MSMZ_ERR_UNSUPPORTED;
+    if (!s || !s0 || !s1 || !neg || n == 0 || n > (1u << 22)) return MSMZ_ERR_ARG;
+    Staging sg = staging();
+    const int is = sg.in(s, 32 * n), i0 = sg.out(s0, 16 * n), i1 = sg.out(s1, 16 * n), ineg = sg.out(neg, 2 * n);
+    if (int st = sg.upload()) return st;
+    hipLaunchKernelGGL((k_test_glv<Fr>), dim3((n + 255) / 256), dim3(256), 0, eng_.stream_, sg.at<uint32_t>(i0),
+                       sg.at<uint32_t>(i1), sg.at<uint8_t>(ineg), sg.at<const uint32_t>(is), (uint32_t)n);
+    return sg.download();
+  }
+
+  int test_digits(const uint8_t* s, uint64_t n, int c, int K, int glv, uint32_t* digits) override {
+    if (!s || !digits || n == 0 || n > (1u << 22) || c < 2 || c > 24 || K < 1 || K > kMaxWindows) return MSMZ_ERR_ARG;
+    if (glv && !Fr::HAS_GLV) return MSMZ_ERR_UNSUPPORTED;
+    Staging sg = staging();
+    const int is = sg.in(s, 32 * n), id = sg.out(digits, (size_t)(glv ? 2 : 1) * n * K * 4);
+    if (int st = sg.upload()) return st;
+    if (glv) {
+      if constexpr (Fr::HAS_GLV)
+        hipLaunchKernelGGL((k_test_digits<Fr, true>), dim3((n + 255) / 256), dim3(256), 0, eng_.stream_,
+                           sg.at<uint32_t>(id), sg.at<const uint32_t>(is), (uint32_t)n, c, K);
+    } else {
+      hipLaunchKernelGGL((k_test_digits<Fr, false>), dim3((n + 255) / 256), dim3(256), 0, eng_.stream_,
+                         sg.at<uint32_t>(id), sg.at<const uint32_t>(is), (uint32_t)n, c, K);
+    }
+    return sg.download();
+  }
+
+  int test_sort(const uint8_t* s, uint64_t n, int c, int glv, int force_fallback, uint32_t* geom, uint32_t* off,
+                uint64_t off_cap, uint32_t* refs, uint64_t refs_cap) override {
+    if (!s || !geom || n == 0 || n > (1u << 22)) return MSMZ_ERR_ARG;
+    if (glv && !Fr::HAS_GLV) return MSMZ_ERR_UNSUPPORTED;
+    msmz_opts opt;
+    memset(&opt, 0, sizeof(opt));
+    opt.c = c;
+    Planner<Fr> pr = eng_.planner_;
+    pr.k.force_atomic_sort = pr.k.force_atomic_sort || force_fallback != 0;
+    Plan pl;
+    int st = pr.make_plan(pl, n, glv != 0, opt, (uint32_t)n, !TE);
+    if (st) return st;
+    Staging sg = staging();
+    const int is = sg.in(s, 32 * n);
+    if ((st = sg.upload())) return st;
+    Run run = eng_.new_run(opt);
+    if ((st = eng_.sort_phase(pl, pr.sort_layout(pl), sg.at<const uint32_t>(is), run, 0)) || (st = eng_.fetch_meta(run)))
+      return st;
+    if (eng_.h_meta_->error & 4u) return MSMZ_ERR_RANGE;
+    const uint32_t g8[8] = {(uint32_t)pl.c, (uint32_t)pl.K, (uint32_t)pl.Keff, pl.L, pl.nb, run.n_entries, run.max_bucket,
+                            (uint32_t)pl.spread};
+    memcpy(geom, g8, sizeof(g8));
+    if (off) {
+      if (off_cap < (uint64_t)pl.nb + 1) return MSMZ_ERR_ARG;
+      MSMZ_HIP(hipMemcpy(off, eng_.off_.p, ((size_t)pl.nb + 1) * 4, hipMemcpyDeviceToHost));
+    }
+    if (refs) {
+      if (refs_cap < run.n_entries) return MSMZ_ERR_ARG;
+      if (run.n_entries) MSMZ_HIP(hipMemcpy(refs, eng_.refs_.p, (size_t)run.n_entries * 4, hipMemcpyDeviceToHost));
+    }
+    return MSMZ_OK;
+  }
+
+  int test_point(int op, const uint8_t* a, const uint8_t* a_inf, const uint8_t* b, const uint8_t* b_inf, uint64_t n,
+                 uint8_t* out) override {
+    if (!a || !b || !out || n == 0 || n > (1u << 20)) return MSMZ_ERR_ARG;
+    const size_t pb = (size_t)2 * E::FE_BYTES * n;
+    Staging sg = staging();
+    const int ia = sg.in(a, pb), ib = sg.in(b, pb), iai = sg.in(a_inf, n), ibi = sg.in(b_inf, n), io = sg.out(out, pb);
+    if (int st = sg.upload()) return st;
+    const uint64_t threads = (op == TP_ADD_X4 || op == TP_DBL_X4) ? 4 * n : n;
+    hipLaunchKernelGGL((k_test_point<P, TE>), dim3((threads + 63) / 64), dim3(64), 0, eng_.stream_, sg.at<uint32_t>(io),
+                       sg.at<const uint32_t>(ia), sg.at<const uint32_t>(ib), sg.at<const uint8_t>(iai),
+                       sg.at<const uint8_t>(ibi), (uint32_t)n, op);
+    return sg.download();
+  }
+
+  int test_point_raw(int op, const uint8_t* a, const uint8_t* b, const uint8_t* neg, uint64_t n, int L,
+                     uint8_t* out) override {
+    if (!a || !b || !out || n == 0 || n > (1u << 20) || op < 0 || op >= TPR_COUNT || L < 0 || L > 4096)
+      return MSMZ_ERR_ARG;
+    if (TE && op == TPR_MDBL) return MSMZ_ERR_UNSUPPORTED;
+    const size_t rb = (size_t)4 * E::FE_BYTES * n, pb = (size_t)2 * E::FE_BYTES * n;
+    Staging sg = staging();
+    const int ia = sg.in(a, rb), ib = sg.in(b, rb), ineg = sg.in(neg, n), io = sg.out(out, pb);
+    if (int st = sg.upload()) return st;
+    const bool x4 = op == TPR_ADD_X4 || op == TPR_DBL_X4 || op == TPR_CHAIN_X4;
+    const uint64_t threads = x4 ? 4 * n : n;
+    hipLaunchKernelGGL((k_test_point_raw<P, TE>), dim3((threads + 63) / 64), dim3(64), 0, eng_.stream_,
+                       sg.at<uint32_t>(io), sg.at<const uint32_t>(ia), sg.at<const uint32_t>(ib),
+                       sg.at<const uint8_t>(ineg), (uint32_t)n, op, L);
+    return sg.download();
+  }
+
+  int test_batch_add(int safe, int B, const uint8_t* pxy, const uint8_t* pinf, uint64_t np, const uint8_t* sxy,
+                     const uint8_t* sinf, uint64_t ns, const uint32_t* desc, uint64_t n_pairs, uint64_t out_base,
+                     uint8_t* out, uint32_t* error) override {
+    if (TE) return MSMZ_ERR_UNSUPPORTED;
+    constexpr uint64_t CAP = 1u << 22;
+    if (!desc || !out || !error || (safe != 0 && safe != 1) || B < 1 || B > MSMZ_BATCH_BMAX) return MSMZ_ERR_ARG;
+    if (n_pairs == 0 || n_pairs > CAP || np > CAP || ns > CAP || (np && !pxy) || (ns && !sxy)) return MSMZ_ERR_ARG;
+    if (out_base < ns || out_base > CAP) return MSMZ_ERR_ARG;
+    // every location names a supplied operand: the kernel reads whatever its descriptors point at
+    for (uint64_t k = 0; k < 2 * n_pairs; k++) {
+      const uint32_t w = desc[k];
+      if ((w & LOC_ORIG) ? (w & 0x3fffffffu) >= np : w >= ns) return MSMZ_ERR_ARG;
+    }
+    const size_t rec = (size_t)E::RW * 4;
+    Staging sg = staging();
+    const int ipxy = sg.in(pxy, rec * np), ipinf = sg.in(pinf, np), isxy = sg.in(sxy, rec * ns), isinf = sg.in(sinf, ns);
+    const int idesc = sg.in(desc, (size_t)8 * n_pairs), io = sg.out(out, rec * n_pairs);
+    int st = sg.upload();
+    if (st) return st;
+    MsmMeta* d_meta = eng_.meta_.template as<MsmMeta>();
+    MSMZ_HIP(hipMemsetAsync(&d_meta->error, 0, 4, eng_.stream_));
+    DevBuf d_pts;   // the resident point set (freed on every return)
+    uint32_t err = 0;
+    // slot records 0 .. out_base + n_pairs - 1, as the MSM sizes them
+    if ((st = load_operands(d_pts, sg.at<const uint32_t>(ipxy), sg.at<const uint8_t>(ipinf), np,
+                            sg.at<const uint32_t>(isxy), sg.at<const uint8_t>(isinf), ns, (uint32_t)(out_base + n_pairs))) ||
+        (st = eng_.fetch_error(&err)))
+      return st;
+    if (err) return MSMZ_ERR_RANGE;   // a coordinate >= p
+    eng_.launch_batch_add_b(B, (uint32_t)n_pairs, safe != 0, d_pts.as<uint32_t>(), sg.at<const uint2>(idesc),
+                          (uint32_t)out_base, d_meta);
+    MSMZ_HIP(hipGetLastError());
+    if constexpr (!TE)
+      hipLaunchKernelGGL((k_test_slots_out<F>), dim3((n_pairs + 255) / 256), dim3(256), 0, eng_.stream_,
+                         sg.at<uint32_t>(io), eng_.slots_.template as<uint32_t>(), (uint32_t)out_base, (uint32_t)n_pairs);
+    if ((st = eng_.fetch_error(error))) return st;
+    return sg.download();
+  }
+
+  // The bucket reduction on caller-built buckets (msmz_test.h).  The level-selection knobs hold for this call only: they
+  // go into copies of the engine's thresholds and planner, and the reduction takes both as arguments.
+  int test_reduce(const msmz_test_reduce_args& a) override {
+    constexpr int AW = P::ACC_WORDS, NW = F::NW, RW = E::RW;
+    constexpr uint64_t CAP = 1u << 20;
+    const bool levels = a.mode == MSMZ_TR_LEVELS, locs = a.mode == MSMZ_TR_LOCATIONS;
+    if (a.mode < MSMZ_TR_LOCATIONS || a.mode > MSMZ_TR_LEVELS || !a.out_xy) return MSMZ_ERR_ARG;
+    if (TE && locs) return MSMZ_ERR_UNSUPPORTED;
+    if (a.tail_n > 4096 || a.quad16_max > CAP || a.pairsum_x4_max > CAP) return MSMZ_ERR_ARG;
+    if (a.n_points > CAP || a.n_slots > CAP || (a.n_points && !a.points_xy) || (a.n_slots && !a.slots_xy)) return MSMZ_ERR_ARG;
+    // geometry: a plan of `nsets` bucket sets of window size c, as far as the 2-D reduction / reduce_levels read one
+    Plan pl{};
+    pl.nprob = 1;
+    pl.F = 1;
+    R2Geom g{};   // 2-D modes: the split of the bucket sets, with the caller's NC
+    uint32_t nb = 0, n_res = a.nsets;
+    if (levels) {
+      if (a.nsets < 1 || a.nsets > 64 || a.n_in < 1 || a.n_in > 4096 || a.nc != 0) return MSMZ_ERR_ARG;
+      if (a.n_points != (uint64_t)2 * a.nsets * a.n_in) return MSMZ_ERR_ARG;
+      pl.Keff = (int)a.nsets;
+    } else {
+      if (a.c < 2 || a.c > 16 || a.nsets < 1 || a.nsets > 16) return MSMZ_ERR_ARG;
+      pl.c = a.c;
+      pl.L = 1u << (a.c - 1);
+      pl.Keff = pl.K = (int)a.nsets;
+      nb = pl.nb = a.nsets * pl.L;
+      Planner<Fr> pr = eng_.planner_;
+      if (a.nc) pr.k.r2_nc = a.nc;
+      g = E::r2_geom(pl, pr.split_2d(pl));
+      if (a.nc != 0 && ((a.nc & (a.nc - 1)) != 0 || a.nc > g.D)) return MSMZ_ERR_ARG;
+      n_res = 2 * a.nsets;
+      // every location / chunk range names a supplied operand: the kernels read whatever these point at
+      if (locs) {
+        if (!a.loc) return MSMZ_ERR_ARG;
+        for (uint64_t k = 0; k < (uint64_t)4 * nb; k++) {
+          const uint32_t w = a.loc[k];
+          if (w == LOC_NONE) {
+            k |= 3;   // (the rest of this bucket's words is never read)
+            continue;
+          }
+          if ((w & LOC_ORIG) ? (w & 0x3fffffffu) >= a.n_points : w >= a.n_slots) return MSMZ_ERR_ARG;
+        }
+      } else {
+        if (!a.cscan || a.cscan[nb] > a.n_points) return MSMZ_ERR_ARG;
+        for (uint32_t g = 0; g < nb; g++)
+          if (a.cscan[g] > a.cscan[g + 1]) return MSMZ_ERR_ARG;
+      }
+    }
+    if (a.scale && locs) return MSMZ_ERR_ARG;
+    ReduceKnobs rk = eng_.reduce_knobs_;
+    if (a.tail_n) rk.tail_n = a.tail_n;
+    if (a.quad16_max) rk.quad16_max = a.quad16_max;
+    if (a.pairsum_x4_max) rk.pairsum_x4_max = a.pairsum_x4_max;
+    const uint32_t n_lines = levels || !a.lines_xy ? 0 : n_res * g.H;
+
+    const size_t np = a.n_points, ns = a.n_slots, rec = (size_t)RW * 4;
+    Staging sg = staging();
+    const int ipxy = sg.in(a.points_xy, rec * np), ipinf = sg.in(a.points_inf, np);
+    const int iscale = sg.in(a.scale, (size_t)E::FE_BYTES * np);
+    const int isxy = sg.in(a.slots_xy, rec * ns), isinf = sg.in(a.slots_inf, ns);
+    const int ires = sg.out(a.out_xy, rec * n_res), ilines = sg.out(n_lines ? a.lines_xy : nullptr, rec * n_lines);
+    int st = sg.upload();
+    if (st) return st;
+    MsmMeta* d_meta = eng_.meta_.template as<MsmMeta>();
+    MSMZ_HIP(hipMemsetAsync(&d_meta->error, 0, 4, eng_.stream_));
+    // accumulator records `first .. first + n` of the input points, in the policy's memory format
+    auto accs_in = [&](uint32_t* dst, size_t first, size_t n) {
+      const uint8_t* d_pinf = sg.at<const uint8_t>(ipinf);
+      const uint32_t* d_scale = sg.at<const uint32_t>(iscale);
+      if (n)
+        hipLaunchKernelGGL((k_test_accs_in<P, TE>), dim3((n + 255) / 256), dim3(256), 0, eng_.stream_, dst,
+                           sg.at<const uint32_t>(ipxy) + first * RW, d_pinf ? d_pinf + first : nullptr,
+                           d_scale ? d_scale + first * NW : nullptr, (uint32_t)n, &d_meta->error);
+    };
+    DevBuf d_pts;   // LOCATIONS: the resident point set (freed on every return)
+    if (levels) {
+      const size_t n = (size_t)a.nsets * a.n_in;
+      if ((st = eng_.red_[0].ensure(n * AW * 4)) || (st = eng_.red_[1].ensure(n * AW * 4))) return st;
+      accs_in(eng_.red_[0].template as<uint32_t>(), 0, n);
+      accs_in(eng_.red_[1].template as<uint32_t>(), n, n);
+    } else if (locs) {
+      if ((st = eng_.bfin_.ensure((size_t)nb * 16))) return st;
+      MSMZ_HIP(hipMemcpyAsync(eng_.bfin_.p, a.loc, (size_t)nb * 16, hipMemcpyHostToDevice, eng_.stream_));
+      if ((st = load_operands(d_pts, sg.at<const uint32_t>(ipxy), sg.at<const uint8_t>(ipinf), np,
+                              sg.at<const uint32_t>(isxy), sg.at<const uint8_t>(isinf), ns, (uint32_t)ns)))
+        return st;
+    } else {
+      if ((st = eng_.slots_.ensure((np + 1) * AW * 4)) || (st = eng_.rscan_.ensure(((size_t)nb + 1) * 4))) return st;
+      MSMZ_HIP(hipMemcpyAsync(eng_.rscan_.p, a.cscan, ((size_t)nb + 1) * 4, hipMemcpyHostToDevice, eng_.stream_));
+      accs_in(eng_.slots_.template as<uint32_t>(), 0, np);
+    }
+    uint32_t err = 0;
+    if ((st = eng_.fetch_error(&err))) return st;
+    if (err & 4u) return MSMZ_ERR_RANGE;   // a coordinate or scale >= p
+    if (err) return MSMZ_ERR_ARG;          // a zero scale
+
+    if (levels) {
+      int cur = 0;
+      if ((st = eng_.template reduce_levels<P>(rk, cur, a.n_in, a.nsets))) return st;
+    } else {
+      const bool summed = a.mode == MSMZ_TR_ACCS_SUMMED;
+      if (summed && (st = eng_.template bucket_sums<P>(nb))) return st;
+      int rows = 0;   // the red_ buffer that holds the line sums: read out here, before the weighted levels reuse it
+      if ((st = eng_.template line_sums_2d<P>(g, rk, d_pts.as<uint32_t>(), !locs, summed, &rows))) return st;
+      if (n_lines)
+        hipLaunchKernelGGL((k_test_accs_out<P, TE>), dim3((n_lines + 63) / 64), dim3(64), 0, eng_.stream_,
+                           sg.at<uint32_t>(ilines), eng_.red_[rows].template as<uint32_t>(), n_lines);
+      if ((st = eng_.template weighted_sums_2d<P>(g, rk, rows))) return st;
+    }
+    MSMZ_HIP(hipGetLastError());
+    hipLaunchKernelGGL((k_test_accs_out<P, TE>), dim3((n_res + 63) / 64), dim3(64), 0, eng_.stream_, sg.at<uint32_t>(ires),
+                       eng_.final_.template as<uint32_t>(), n_res);
+    return sg.download();
+  }
+
+ private:
+  Staging staging() const { return Staging{eng_.device_, eng_.stream_, eng_.stage_}; }
+
+  // The operands of the tree rounds as test_batch_add and the LOCATIONS mode of test_reduce take them (Weierstrass):
+  // d_pts <- the np canonical points in the resident format of an MSM; slots_ <- records 0 .. recs - 1 in whole groups
+  // of 64, filled with a pattern that decodes to no result (so a record a launch leaves unwritten cannot pass for one),
+  // then the ns canonical slot records.  A coordinate >= p raises the meta error word, which the caller has cleared.
+  int load_operands(DevBuf& d_pts, const uint32_t* d_pxy, const uint8_t* d_pinf, size_t np, const uint32_t* d_sxy,
+                    const uint8_t* d_sinf, size_t ns, uint32_t recs) {
+    int st;
+    if ((st = d_pts.ensure((np ? np : 1) * E::PW_WORDS * 4))) return st;
+    if ((st = eng_.slots_.ensure(((size_t)recs + 64) * SlotFmt<F>::WORDS * 4))) return st;
+    MSMZ_HIP(hipMemsetAsync(eng_.slots_.p, 0xa5, E::slot_words((recs + 63u) & ~63u) * 4, eng_.stream_));
+    uint32_t* d_error = &eng_.meta_.template as<MsmMeta>()->error;
+    if constexpr (!TE) {
+      if (np)
+        hipLaunchKernelGGL((k_points_to_mont<F>), dim3((np + 255) / 256), dim3(256), 0, eng_.stream_, d_pts.as<uint32_t>(),
+                           d_pxy, d_pinf, (uint32_t)np, 0, d_error);
+      if (ns)
+        hipLaunchKernelGGL((k_test_slots_in<F>), dim3((ns + 255) / 256), dim3(256), 0, eng_.stream_,
+                           eng_.slots_.template as<uint32_t>(), d_sxy, d_sinf, (uint32_t)ns, d_error);
+    }
+    return MSMZ_OK;
+  }
+
+  E& eng_;
+};
+
+}  // namespace msmz

@@ -1,5 +1,5 @@
 """The bucket reduction alone (reduce_2d / reduce_levels of csrc/engine.h and the kernels of csrc/reduce2d_kernels.h and
-csrc/kernels.h) through msmz_test_reduce, on caller-built buckets, stage by stage against oracle/bigint_ref.py.
+csrc/kernels.h) through msmz_test_reduce (csrc/test_hooks.h), on caller-built buckets, stage by stage against oracle/bigint_ref.py.
 
 A whole MSM shows the reduction only through one point: which level kernel ran is decided by thresholds a release
 build cannot move, every bucket sum of a large MSM is a distinct random point, and the row / column result of a bucket
