@@ -43,7 +43,7 @@ enum {
   MSMZ_ERR_UNSUPPORTED = 4,  /* option combination not available for this curve */
   MSMZ_ERR_DEGENERATE = 5,   /* msmUnsafe hit P + (+-P): a batch inversion saw a zero denominator
                                 (the reference traps with wasm `unreachable`, inverse.ts:198-199) */
-  MSMZ_ERR_RANGE = 6         /* a scalar is >= the group order / a coordinate is >= p */
+  MSMZ_ERR_RANGE = 6         /* a scalar is >= the group order (or >= 2^bits of msmz_opts.reserved[1]) / a coordinate is >= p */
 };
 
 enum { MSMZ_BUCKETS_AFFINE = 0, MSMZ_BUCKETS_PROJECTIVE = 1 };
@@ -59,7 +59,14 @@ typedef struct msmz_opts {
   int32_t timing;   /* 1 = fill msmz_log stage timings with HIP events (the reference's tic/toc log) */
   int32_t reserved[3]; /* reserved[0] = 1: first level of the bucket reduction by batched-affine additions
                         * (reduceBucketsAffine, msm-batched-affine-single-thread.ts:522-667) instead of XYZZ running
-                        * sums; same result, measured slower on MI355X (profiles/r02_reduce_ab.txt): default 0 */
+                        * sums; same result, measured slower on MI355X (profiles/r02_reduce_ab.txt): default 0
+                        * reserved[1] = scalar bit bound: "every scalar of this call is below 2^reserved[1]".  The windows are
+                        * sized for it (64-bit scalars at c = 17: 4 windows, not 15), and so is everything paid per window.
+                        * 0 = no bound; a value of at least the scalar field's bit length means the same; a negative value
+                        * or one above 256 is MSMZ_ERR_ARG.  A scalar >= 2^reserved[1] fails the call with MSMZ_ERR_RANGE
+                        * (checked exactly, on the device, while the scalars are sliced, like a scalar >= the group
+                        * order; a batched call fails as a whole; the context stays usable).  With glv = -1 a bound of at
+                        * most the GLV half length turns the split off.  The result is the same with and without it. */
 } msmz_opts;
 
 /* Stage timings + counts, the analogue of the `log` array msm() returns (msm-common.ts:192-230). */
@@ -152,7 +159,9 @@ int msmz_msm_batch_resident(msmz_ctx* ctx, uint64_t points_handle, uint64_t scal
  * (factor - 1) fewer doubling runs per set.  factor 0 = all windows (one bucket set per MSM; the copies also cover the
  * window count of the GLV retry); 1 is MSMZ_ERR_ARG; a factor above the window count is lowered to it.  opts->c /
  * opts->glv fix the window size and the GLV choice the copies are built for (0 / -1 = the engine's choice for n; a null
- * opts means both); opts->safe / timing play no part.  The new handle owns its memory: the source handle may be freed.
+ * opts means both); opts->reserved[1] is the scalar bit bound the copies are built for: the window count of bounded
+ * scalars (fewer copies, less memory; factor 0 = all windows of a bounded scalar; a bound that leaves a single window
+ * is MSMZ_ERR_ARG: nothing to share); opts->safe / timing play no part.  The new handle owns its memory: the source handle may be freed.
  * Memory: factor * R records of the point stride (R = n, or 2n with GLV: the endomorphism images follow the base points in
  * every copy), e.g. 2 GiB for 2^20 BLS12-377 points at c = 16, factor 0.
  * Limits (MSMZ_ERR_ARG at precompute time): the records fit the 30-bit record index (factor * R < 2^30), one bucket can
@@ -162,7 +171,8 @@ int msmz_msm_batch_resident(msmz_ctx* ctx, uint64_t points_handle, uint64_t scal
  * MSMZ_ERR_UNSUPPORTED, here and in every MSM over a precomputed handle.
  * Use: msmz_msm, msmz_msm_resident, msmz_msm_batch and msmz_msm_batch_resident take the precomputed handle wherever they
  * take points_handle, n up to its n, and return bit-identical results to the plain handle; opts.c must be 0 or the
- * handle's c and opts.glv -1 or the handle's choice (else MSMZ_ERR_ARG).  msmz_download_points reads its records: copy j
+ * handle's c, opts.glv -1 or the handle's choice and opts.reserved[1] 0 (the handle's bound applies) or the handle's
+ * bound (else MSMZ_ERR_ARG).  msmz_download_points reads its records: copy j
  * at [j R, (j + 1) R) (a multi-device context: the first n records, copy 0).  msmz_free releases it.  On a multi-device
  * context every engine precomputes its own share of the points. */
 int msmz_precompute_points(msmz_ctx* ctx, uint64_t points_handle, uint64_t n, const msmz_opts* opts, uint32_t factor,
@@ -171,6 +181,8 @@ int msmz_precompute_points(msmz_ctx* ctx, uint64_t points_handle, uint64_t n, co
  * MSM over it and records (factor * R, all devices) */
 int msmz_precomputed_info(msmz_ctx* ctx, uint64_t handle, int32_t* c, int32_t* glv, uint32_t* factor, uint32_t* K,
                           uint64_t* records);
+/* the scalar bit bound a precomputed handle was built for: 0 = none (also for a bound of at least the field's bit length) */
+int msmz_precomputed_scalar_bits(msmz_ctx* ctx, uint64_t handle, int32_t* bits);
 
 /* Host-side group addition of two canonical affine results: combines per-GPU partial sums
  * (the reference's "partition sum" step, msm-batched-affine.ts:300-307). */

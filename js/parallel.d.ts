@@ -7,8 +7,10 @@ export type CurveParams = {
 export type BigintPoint = { x: bigint; y: bigint; isZero?: boolean };
 export interface DeviceArray extends Array<DeviceArray> { readonly n: number; readonly kind: "points" | "scalars" | "precomputed";
   /** precomputed point sets only (msmz_precomputed_info) */
-  readonly info?: { c: number; glv: number; factor: number; K: number; records: number }; free(): void }
-export type MsmOptions = { c?: number; glv?: boolean | number; useSafeAdditions?: boolean; reduceAffine?: boolean };
+  readonly info?: { c: number; glv: number; factor: number; K: number; records: number; scalarBits: number }; free(): void }
+/** scalarBits: every scalar of the call is below 2^scalarBits (0 / absent = no bound); the windows are sized for it and a
+ * scalar that breaks it fails the call */
+export type MsmOptions = { c?: number; glv?: boolean | number; useSafeAdditions?: boolean; reduceAffine?: boolean; scalarBits?: number };
 export type MsmResult = { result: BigintPoint; log: any[][]; stats: Record<string, any> };
 export interface ParallelApi {
   randomPointsFast(n: number, options?: { seed?: bigint | number }): Promise<DeviceArray>;
@@ -23,7 +25,7 @@ export interface ParallelApi {
   msm(scalars: DeviceArray | Uint8Array | number, points: DeviceArray | number, n: number, verbose?: boolean, options?: MsmOptions): Promise<MsmResult>;
   msmUnsafe(scalars: DeviceArray | Uint8Array | number, points: DeviceArray | number, n: number, verbose?: boolean, options?: MsmOptions): Promise<MsmResult>;
   /** fixed-base precomputation: the result goes wherever `points` is taken (factor 0 = all windows in one bucket set) */
-  precomputePoints(points: DeviceArray, n: number, options?: { c?: number; glv?: boolean | number }, factor?: number): Promise<DeviceArray>;
+  precomputePoints(points: DeviceArray, n: number, options?: { c?: number; glv?: boolean | number; scalarBits?: number }, factor?: number): Promise<DeviceArray>;
   msmBatch(scalarsList: DeviceArray | Uint8Array[], points: DeviceArray, n: number, options?: MsmOptions & { batch?: number }): Promise<BigintPoint[]>;
   msmBatchUnsafe(scalarsList: DeviceArray | Uint8Array[], points: DeviceArray, n: number, options?: MsmOptions & { batch?: number }): Promise<BigintPoint[]>;
   msmProjective?(scalars: DeviceArray | Uint8Array, points: DeviceArray, n: number, options?: MsmOptions): Promise<MsmResult>;

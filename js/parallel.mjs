@@ -161,6 +161,15 @@ function createCurve(params, kind) {
     return p;
   }
 
+  // options.scalarBits: "every scalar of this call is below 2^scalarBits" (msmz_opts.reserved[1]); 0 / absent = no bound.
+  // Checked here, before anything reaches the device.
+  function scalarBitsArg(options, who) {
+    const bits = options.scalarBits;
+    if (bits === undefined || bits === null) return 0;
+    if (!Number.isInteger(bits) || bits < 0 || bits > 256) throw Error(`${who}: scalarBits = ${bits} (0 = no bound, or 1..256)`);
+    return bits;
+  }
+
   async function msmCommon(scalars, points, n, verbose, options, safe, buckets) {
     options = options || {};
     const opts = {
@@ -170,6 +179,7 @@ function createCurve(params, kind) {
       buckets,
       timing: verbose ? 1 : 0,
       reduceAffine: options.reduceAffine ? 1 : 0, // batched-affine first reduction level (reduceBucketsAffine)
+      scalarBits: scalarBitsArg(options, "msm"),
     };
     if (typeof points === "number") points = resident(points, n, "msm points");
     if (typeof scalars === "number") scalars = resident(scalars, n, "msm scalars");
@@ -192,6 +202,7 @@ function createCurve(params, kind) {
       safe: options.useSafeAdditions !== undefined ? Number(options.useSafeAdditions) : safe,
       buckets: options.buckets || 0,
       reduceAffine: options.reduceAffine ? 1 : 0,
+      scalarBits: scalarBitsArg(options, "msmBatch"),
     };
     if (typeof points === "number") points = resident(points, n, "msmBatch points");
     if (!(n > 0) || n > points.n) throw Error(`msmBatch: n = ${n} but the point set holds ${points.n}`);
@@ -220,7 +231,8 @@ function createCurve(params, kind) {
     /** fixed-base precomputation of the first n resident points (include/msmz.h msmz_precompute_points): a DeviceArray
      * of kind "precomputed" that msm / msmUnsafe / msmBatch / msmBatchUnsafe take in place of the points (same results).
      * factor = windows sharing one bucket set (0 = all; 1 is refused); options.c / options.glv fix the window size and
-     * the GLV choice (default: the engine's).  The copies' parameters are in the array's `info`. */
+     * the GLV choice (default: the engine's), options.scalarBits the scalar bit bound the copies are built for (fewer
+     * windows, fewer copies; MSMs over the array take that bound).  The copies' parameters are in the array's `info`. */
     async precomputePoints(points, n, options, factor = 0) {
       options = options || {};
       if (!(points instanceof DeviceArray) || points.kind !== "points")
@@ -228,7 +240,8 @@ function createCurve(params, kind) {
       if (!Number.isInteger(n) || n < 1 || n > points.n) throw Error(`precomputePoints: n = ${n} but the point set holds ${points.n}`);
       if (!Number.isInteger(factor) || factor < 0 || factor === 1 || factor >= 2 ** 32)
         throw Error(`precomputePoints: factor = ${factor} (0 = all windows, or 2, 3, ...)`);
-      const opts = { c: options.c || 0, glv: options.glv !== undefined ? Number(options.glv) : -1 };
+      const opts = { c: options.c || 0, glv: options.glv !== undefined ? Number(options.glv) : -1,
+                     scalarBits: scalarBitsArg(options, "precomputePoints") };
       const h = N.precomputePoints(ctx, points.handle, n, opts, factor);
       const arr = DeviceArray.make(curve, h, n, "precomputed");
       Object.defineProperty(arr, "info", { value: N.precomputedInfo(ctx, h) });

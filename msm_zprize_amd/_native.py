@@ -61,6 +61,7 @@ EXPORTS = {
                                          C.POINTER(C.c_uint64)]),
     "msmz_precomputed_info": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "msmz_precomputed_scalar_bits": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_int32)]),
     "msmz_point_add": (C.c_int, [C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.POINTER(C.c_int)]),
     # stage-level test hooks (include/msmz_test.h)
     "msmz_test_set_glv_bits": (C.c_int, [C.c_void_p, C.c_int]),

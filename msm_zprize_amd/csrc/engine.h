@@ -81,6 +81,7 @@ struct Handle {
   uint32_t factor = 0;
   int c = 0, glv = 0;
   uint64_t copy_stride = 0;
+  int sbits = 0;   // scalar bit bound the copies were built for (Planner::bound: 0 = none)
 };
 
 // Named events of an MSM's stages, created once per engine; a timed MSM records them in stream order.
@@ -405,13 +406,13 @@ class Engine : public IEngine {
 
   // ------------------------------------------------------------------------------------------ precomputed point sets
   int precompute_params(uint64_t n, const msmz_opts* o, uint32_t factor, int* c_out, int* glv_out,
-                        uint32_t* f_out, int* k_out) const override {
+                        uint32_t* f_out, int* k_out, int* sbits_out) const override {
     if (TE) return MSMZ_ERR_UNSUPPORTED;   // twisted Edwards runs msmBasic: no batched-affine buckets to share
-    return planner_.precompute_params(n, o, factor, c_out, glv_out, f_out, k_out);
+    return planner_.precompute_params(n, o, factor, c_out, glv_out, f_out, k_out, sbits_out);
   }
 
   // new handle: `F` copies of the first n points of `ph`, copy j = 2^(c j) P_i (+ the endomorphism images with glv)
-  int precompute_points(uint64_t ph, uint64_t n, int c, int glv, uint32_t copies, uint64_t* h) override {
+  int precompute_points(uint64_t ph, uint64_t n, int c, int glv, uint32_t copies, int sbits, uint64_t* h) override {
     if (TE) return MSMZ_ERR_UNSUPPORTED;
     auto pit = handles_.find(ph);
     if (!h || pit == handles_.end() || pit->second.kind != 0 || pit->second.factor != 0 || n == 0 || pit->second.n < n ||
@@ -441,14 +442,17 @@ class Engine : public IEngine {
     hd.c = c;
     hd.glv = glv;
     hd.copy_stride = R;
+    hd.sbits = planner_.bound(sbits);
     return add_handle(std::move(hd), h);
   }
 
-  int precomputed_info(uint64_t hd, int32_t* c, int32_t* glv, uint32_t* factor, uint32_t* K, uint64_t* records) override {
+  int precomputed_info(uint64_t hd, int32_t* c, int32_t* glv, uint32_t* factor, uint32_t* K, uint64_t* records,
+                       int32_t* sbits) override {
     auto it = handles_.find(hd);
     if (it == handles_.end() || it->second.factor == 0) return MSMZ_ERR_ARG;
     const Handle& h = it->second;
-    const int b = planner_.scalar_bits(h.glv != 0, 0);
+    const int b = planner_.scalar_bits(h.glv != 0, 0, h.sbits);
+    if (sbits) *sbits = h.sbits;
     if (c) *c = h.c;
     if (glv) *glv = h.glv;
     if (factor) *factor = h.factor;
@@ -472,7 +476,7 @@ class Engine : public IEngine {
     msmz_opts opt;
     int st0 = resolve_opts(pit->second, o, &opt);
     if (st0) return st0;
-    if (opt.glv < 0) opt.glv = pit->second.has_endo && planner_.default_glv(n) ? 1 : 0;   // (per problem: batch = 1 is msm())
+    if (opt.glv < 0) opt.glv = pit->second.has_endo && planner_.default_glv(n, opt.reserved[1]) ? 1 : 0;   // (per problem: batch = 1 is msm())
     if (host_stride == 0) host_stride = n;
     if (host_scalars && host_stride < n) return MSMZ_ERR_ARG;
     MSMZ_HIP(hipSetDevice(device_));
@@ -570,15 +574,20 @@ class Engine : public IEngine {
 
   // The options of an MSM over handle `h`: a precomputed set fixes c and the GLV choice (opts->c must be 0 or its c,
   // opts->glv -1 or its choice; a null opts means both defaults) and takes batched-affine buckets with the 2-D reduction.
+  // reserved[1], the scalar bit bound, leaves here as the planner's (Planner::bound); a precomputed set fixes it too.
   int resolve_opts(const Handle& h, const msmz_opts* o, msmz_opts* opt) const {
     memset(opt, 0, sizeof(*opt));
     if (o) *opt = *o;
+    if (opt->reserved[1] < 0 || opt->reserved[1] > 256) return MSMZ_ERR_ARG;
+    opt->reserved[1] = planner_.bound(opt->reserved[1]);
     if (!h.factor) return MSMZ_OK;
     if (!o) opt->glv = -1;
     if (opt->buckets == MSMZ_BUCKETS_PROJECTIVE || opt->reserved[0] == 1) return MSMZ_ERR_UNSUPPORTED;
     if ((opt->c != 0 && opt->c != h.c) || (opt->glv >= 0 && (opt->glv != 0) != (h.glv != 0))) return MSMZ_ERR_ARG;
+    if (opt->reserved[1] != 0 && opt->reserved[1] != h.sbits) return MSMZ_ERR_ARG;
     opt->c = h.c;
     opt->glv = h.glv;
+    opt->reserved[1] = h.sbits;
     return MSMZ_OK;
   }
 
@@ -766,10 +775,10 @@ class Engine : public IEngine {
       if (pl.glv) {
         if constexpr (Fr::HAS_GLV)
           hipLaunchKernelGGL((k_digits<Fr, true>), dim3(dgrid), dim3(256), 0, stream_, digits_.as<uint32_t>(),
-                             counts_.as<uint32_t>(), d_meta, d_scalars, n, c, K, pl.spread);
+                             counts_.as<uint32_t>(), d_meta, d_scalars, n, c, K, pl.spread, pl.sbits ? pl.sbits : 256);
       } else {
         hipLaunchKernelGGL((k_digits<Fr, false>), dim3(dgrid), dim3(256), 0, stream_, digits_.as<uint32_t>(),
-                           counts_.as<uint32_t>(), d_meta, d_scalars, n, c, K, pl.spread);
+                           counts_.as<uint32_t>(), d_meta, d_scalars, n, c, K, pl.spread, pl.sbits ? pl.sbits : 256);
       }
       mark(run, run.ev.hist_end);
       MSMZ_HIP(hipGetLastError());

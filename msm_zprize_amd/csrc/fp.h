@@ -364,6 +364,17 @@ MSMZ_HD bool words_geq(const uint32_t* a, const uint32_t* b) {
   return words_sub<NW>(t, a, b) == 0;
 }
 
+// is the 8-word value s >= 2^bits, bits in [0, 256] (256: never)?  In a kernel `bits` is the same for every lane: the
+// word masks come out of scalar compares, a lane pays 8 ANDs and ORs.
+MSMZ_HD bool words_geq_pow2(const uint32_t* s, int bits) {
+  const int bw = bits >> 5;
+  const uint32_t top = ~0u << (bits & 31);
+  uint32_t o = 0;
+#pragma unroll
+  for (int j = 0; j < 8; j++) o |= s[j] & (j > bw ? ~0u : (j == bw ? top : 0u));
+  return o != 0;
+}
+
 // words (any value in [0, 4p)) -> canonical [0, p)   (field-arithmetic.ts:112-135 `reduce`)
 template <class F>
 MSMZ_HD void words_canon(uint32_t* w) {

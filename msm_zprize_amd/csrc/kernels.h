@@ -335,7 +335,7 @@ constexpr int DIGITS_ITEMS = 8;
 
 template <class Fr, bool GLV>
 __global__ void __launch_bounds__(256) k_digits(uint32_t* digits, uint32_t* counts, MsmMeta* meta, const uint32_t* scalars,
-                                                uint32_t n, int c, int K, int spread) {
+                                                uint32_t n, int c, int K, int spread, int sbits) {
   const uint32_t L = 1u << (c - 1);
   const uint32_t M = GLV ? 2 * n : n;
   const uint32_t smask = (1u << spread) - 1u;
@@ -351,7 +351,11 @@ __global__ void __launch_bounds__(256) k_digits(uint32_t* digits, uint32_t* coun
       s[0] = a.x; s[1] = a.y; s[2] = a.z; s[3] = a.w;
       s[4] = b.x; s[5] = b.y; s[6] = b.z; s[7] = b.w;
     }
-    if (words_geq<8>(s, Fr::Q)) bad |= 4u;
+    if (words_geq<8>(s, Fr::Q) || words_geq_pow2(s, sbits)) {   // flagged, and no digit (as DigitStream::clear)
+      bad |= 4u;
+#pragma unroll
+      for (int j = 0; j < 8; j++) s[j] = 0;
+    }
     constexpr int HALVES = GLV ? 2 : 1;
     constexpr int HW = GLV ? 4 : 8;
     uint32_t h[HALVES][HW], neg[HALVES];

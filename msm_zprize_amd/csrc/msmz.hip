@@ -174,15 +174,19 @@ int msmz_msm_batch_resident(msmz_ctx* c, uint64_t ph, uint64_t sh, uint64_t n, u
 
 int msmz_precompute_points(msmz_ctx* c, uint64_t ph, uint64_t n, const msmz_opts* o, uint32_t factor, uint64_t* h) {
   if (!c || !h) return MSMZ_ERR_ARG;
-  int cc = 0, glv = 0;
+  int cc = 0, glv = 0, sbits = 0;
   uint32_t copies = 0;
-  const int st = c->engine->precompute_params(n, o, factor, &cc, &glv, &copies, nullptr);
+  const int st = c->engine->precompute_params(n, o, factor, &cc, &glv, &copies, nullptr, &sbits);
   if (st) return st;
-  return c->engine->precompute_points(ph, n, cc, glv, copies, h);
+  return c->engine->precompute_points(ph, n, cc, glv, copies, sbits, h);
 }
 int msmz_precomputed_info(msmz_ctx* c, uint64_t h, int32_t* cc, int32_t* glv, uint32_t* factor, uint32_t* K,
                           uint64_t* records) {
-  return c ? c->engine->precomputed_info(h, cc, glv, factor, K, records) : MSMZ_ERR_ARG;
+  return c ? c->engine->precomputed_info(h, cc, glv, factor, K, records, nullptr) : MSMZ_ERR_ARG;
+}
+int msmz_precomputed_scalar_bits(msmz_ctx* c, uint64_t h, int32_t* bits) {
+  if (!c || !bits) return MSMZ_ERR_ARG;
+  return c->engine->precomputed_info(h, nullptr, nullptr, nullptr, nullptr, nullptr, bits);
 }
 
 int msmz_test_set_glv_bits(msmz_ctx* c, int bits) { return c ? c->engine->test_set_glv_bits(bits) : MSMZ_ERR_ARG; }

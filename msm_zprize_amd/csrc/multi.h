@@ -51,10 +51,12 @@ class IEngine {
                         const msmz_opts* o, uint8_t* out, int* out_inf, msmz_log* log, const GenMap* split = nullptr,
                         uint64_t host_stride = 0) = 0;
   // precomputed point sets (msmz_precompute_points): the parameters a set of n points is built with, then the copies
+  // (sbits: the scalar bit bound of opts->reserved[1] as the planner normalizes it, 0 = none)
   virtual int precompute_params(uint64_t n, const msmz_opts* o, uint32_t factor, int* c, int* glv, uint32_t* copies,
-                                int* K) const = 0;
-  virtual int precompute_points(uint64_t ph, uint64_t n, int c, int glv, uint32_t copies, uint64_t* h) = 0;
-  virtual int precomputed_info(uint64_t h, int32_t* c, int32_t* glv, uint32_t* factor, uint32_t* K, uint64_t* records) = 0;
+                                int* K, int* sbits) const = 0;
+  virtual int precompute_points(uint64_t ph, uint64_t n, int c, int glv, uint32_t copies, int sbits, uint64_t* h) = 0;
+  virtual int precomputed_info(uint64_t h, int32_t* c, int32_t* glv, uint32_t* factor, uint32_t* K, uint64_t* records,
+                               int32_t* sbits) = 0;
   // tests (include/msmz_test.h); the stage-level hooks are one engine's (a multi-device context: its first engine's)
   virtual int test_set_glv_bits(int) { return MSMZ_ERR_UNSUPPORTED; }
   virtual int test_retries() { return 0; }
@@ -259,10 +261,10 @@ class MultiEngine : public IEngine {
 
   // every engine precomputes its own share of the points (the same c, GLV choice and copies, chosen for the whole set)
   int precompute_params(uint64_t n, const msmz_opts* o, uint32_t factor, int* c, int* glv, uint32_t* copies,
-                        int* K) const override {
-    return workers_[0]->eng->precompute_params(n, o, factor, c, glv, copies, K);
+                        int* K, int* sbits) const override {
+    return workers_[0]->eng->precompute_params(n, o, factor, c, glv, copies, K, sbits);
   }
-  int precompute_points(uint64_t ph, uint64_t n, int c, int glv, uint32_t copies, uint64_t* h) override {
+  int precompute_points(uint64_t ph, uint64_t n, int c, int glv, uint32_t copies, int sbits, uint64_t* h) override {
     auto pit = handles_.find(ph);
     if (!h || pit == handles_.end() || pit->second.kind != 0 || pit->second.factor != 0 || n == 0 || pit->second.n < n)
       return MSMZ_ERR_ARG;
@@ -271,17 +273,18 @@ class MultiEngine : public IEngine {
     int st = for_all([&](uint32_t g, IEngine* e) {
       const uint64_t cnt = shard_count(n, g, G_);
       if (cnt == 0) return (int)MSMZ_OK;
-      return e->precompute_points(src.sub[g], cnt, c, glv, copies, &mh.sub[g]);
+      return e->precompute_points(src.sub[g], cnt, c, glv, copies, sbits, &mh.sub[g]);
     });
     mh.factor = copies;
     mh.glv = glv;
     return finish_handle(st, mh, h);
   }
-  int precomputed_info(uint64_t hd, int32_t* c, int32_t* glv, uint32_t* factor, uint32_t* K, uint64_t* records) override {
+  int precomputed_info(uint64_t hd, int32_t* c, int32_t* glv, uint32_t* factor, uint32_t* K, uint64_t* records,
+                       int32_t* sbits) override {
     auto it = handles_.find(hd);
     if (it == handles_.end() || it->second.factor == 0) return MSMZ_ERR_ARG;
     if (records) *records = (uint64_t)it->second.factor * it->second.n * (it->second.glv ? 2 : 1);
-    return workers_[0]->eng->precomputed_info(it->second.sub[0], c, glv, factor, K, nullptr);   // (shard 0 holds block 0)
+    return workers_[0]->eng->precomputed_info(it->second.sub[0], c, glv, factor, K, nullptr, sbits);   // (shard 0 holds block 0)
   }
 
   int test_set_glv_bits(int bits) override {

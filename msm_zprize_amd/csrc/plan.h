@@ -56,6 +56,9 @@ struct SortGeom {
   uint32_t F;
   int mbits;
   uint32_t sbins;
+  // Caller-given scalar bit bound (msmz_opts.reserved[1]): a scalar >= 2^sbits is flagged like one >= the group order
+  // and contributes no digit.  256 = no bound.
+  int sbits;
 };
 
 // chunk_pairs[r * n_chunks + chunk] = pairs of round r in the chunk's buckets, r < PLAN_RMAX
@@ -117,6 +120,7 @@ struct Plan {
   uint32_t nprob = 1;         // batched MSM: problems (scalar vectors) sorted, planned and reduced together; nb, M, K,
                               // Keff describe ONE problem, bucket set p * Keff + kw holds window kw of problem p
   uint32_t F = 1;             // precomputed point set: windows per bucket set (Keff = ceil(K / F) sets); 1 = plain
+  int sbits = 0;              // caller-given scalar bit bound, normalized (Planner::bound): 0 = none
 };
 
 // Window geometry for window size c: K windows, L buckets each, significant bits t_top of the top window's
@@ -161,19 +165,31 @@ template <class Fr>
 struct Planner {
   PlanKnobs k;
 
-  // bit length the windows are sized for (make_plan's pl.b): the whole scalar, or a GLV half -- the assumed bound, or
-  // with extra_bits the proven one of the retry
-  int scalar_bits(bool glv, int extra_bits) const {
-    if (!glv) return Fr::BITS;
+  // The caller's scalar bit bound (msmz_opts.reserved[1]: every scalar of the call is below 2^bits) as the planner uses
+  // it: 0 = none, which is also what a bound of at least the field's bit length says.  (The C ABI refuses values outside
+  // [0, 256] before they get here.)
+  static int bound(int bits) { return bits <= 0 || bits >= Fr::BITS ? 0 : bits; }
+
+  // bit length the windows are sized for (make_plan's pl.b): the whole scalar (or the caller's bound on it), or a GLV
+  // half -- the assumed bound (or the caller's bound on the scalar when that is lower: a half that does not fit is
+  // flagged and redone as any other), or with extra_bits the proven one of the retry
+  int scalar_bits(bool glv, int extra_bits, int sbits = 0) const {
+    const int sb = bound(sbits);
+    if (!glv) return sb ? sb : Fr::BITS;
     if (extra_bits) return Fr::GLV_PROVEN_BITS > Fr::GLV_BITS - 1 ? Fr::GLV_PROVEN_BITS : Fr::GLV_BITS - 1;
-    return k.glv_bits_assumed > 0 ? k.glv_bits_assumed : Fr::GLV_BITS - 1;
+    const int a = k.glv_bits_assumed > 0 ? k.glv_bits_assumed : Fr::GLV_BITS - 1;
+    return sb && sb < a ? sb : a;
   }
 
   // glv < 0: the engine's choice for n points.  The split halves the windows but doubles the point set (index bits,
   // gathers, tree depth); since the two-dimensional bucket reduction made the reduction cheap per window it is only
   // ahead on the smallest inputs (profiles/r03_sweep.json: 2^14 0.85 vs 0.88 ms, 2^16 1.11 vs 1.07, 2^20 3.87 vs 3.64,
   // 2^23 23.5 vs 20.5).  (Twisted Edwards: its scalar field has no GLV.)
-  static bool default_glv(uint64_t n) { return Fr::HAS_GLV && n < (1ull << 15); }
+  // A scalar bound of at most the GLV half length: no split, it would only double the point set.
+  static bool default_glv(uint64_t n, int sbits = 0) {
+    if (bound(sbits) && bound(sbits) <= Fr::GLV_BITS - 1) return false;
+    return Fr::HAS_GLV && n < (1ull << 15);
+  }
 
   Geometry geometry(int c, bool glv, uint32_t M, int b, uint32_t F = 1) const {
     Geometry g;
@@ -183,10 +199,13 @@ struct Planner {
     const int pos = (g.K - 1) * c;
     g.t_top = b + 1 - pos;
     if (!glv) {
+      // the largest scalar: q - 1, or 2^b - 1 < q under a caller-given bound b < Fr::BITS
       uint64_t top = 0;
-      for (int j = 0; j < 64 && pos + j < 256; j++)
-        top |= (uint64_t)((Fr::Q[(pos + j) >> 5] >> ((pos + j) & 31)) & 1u) << j;
-      top += 1;   // carry from the window below
+      for (int j = 0; j < 64 && pos + j < 256; j++) {
+        const uint32_t bit = b < Fr::BITS ? (pos + j < b ? 1u : 0u) : (Fr::Q[(pos + j) >> 5] >> ((pos + j) & 31)) & 1u;
+        top |= (uint64_t)bit << j;
+      }
+      if (g.K > 1) top += 1;   // carry from the window below
       g.t_top = ceil_log2_u64(top + 1);
       g.top_range = (uint32_t)(top + 1 > g.L ? g.L : top + 1);
     } else if (Fr::GLV_TYP_BITS + 1 - pos < g.t_top) {
@@ -271,7 +290,11 @@ struct Planner {
       // measured optimum of the batched-affine path from 2^18 entries per window on (profiles/r03_sweep.json): 17 without
       // GLV (2^18: 1.60 ms against 1.83 at c = 15), 16 with it (128-bit halves = 8 windows exactly)
       if (tree_rounds && !k.no_window_model) c = glv ? 16 : 17;
-      for (int tries = 0; tries < 3 && c > 4; tries++) {
+      // Under a caller-given scalar bound (b < Fr::BITS) the batched-affine path keeps 17 whatever is left for the top
+      // window -- it is spread or folded: at 2^20 with 128-bit scalars c = 17 ran in 2.51 ms, the stepped-down 14 in 2.76
+      // (profiles/r06_short_scalars_report.jsonl)
+      const bool bounded = tree_rounds && !k.no_window_model && !glv && b < Fr::BITS;
+      for (int tries = 0; tries < 3 && c > 4 && !bounded; tries++) {
         const int K0 = (b + 1 + c - 1) / c;
         const int top_bits = b + 1 - (K0 - 1) * c;
         if (K0 == 1 || top_bits >= c - 4) break;
@@ -361,7 +384,8 @@ struct Planner {
     // analytic bound is 2^126); k_hist flags a longer half and the MSM is redone (extra_bits = 1) with the proven bound
     // GLV_PROVEN_BITS <= 128, which also is what the 4-word halves of glv_decompose can hold.
     static_assert(!Fr::HAS_GLV || (Fr::GLV_PROVEN_BITS <= 128 && Fr::GLV_PROVEN_BITS <= Fr::GLV_BITS), "GLV halves must fit 4 words");
-    pl.b = scalar_bits(glv, extra_bits);
+    pl.sbits = bound(opt.reserved[1]);
+    pl.b = scalar_bits(glv, extra_bits, pl.sbits);
     pl.c = opt.c > 0 ? opt.c : choose_window(glv, pl.M, pl.b, tree_rounds, nprob, F);
     if (pl.c < 2) pl.c = 2;
     if (pl.c > 24) pl.c = 24;
@@ -403,7 +427,7 @@ struct Planner {
     const int mbits = ceil_log2_u64(pl.M < 2 ? 2 : pl.M);
     const uint32_t sbins = pl.F > 1 ? (uint32_t)pl.Keff * W * ncb : s.nbins;
     s.geom = SortGeom{pl.n, pl.M, pl.c, pl.K, fb, pl.spread, mbits + copy_bits(W), ncb, fbt, ncbt,
-                      pl.fold_shift, pl.fold_rows, W, mbits, sbins};
+                      pl.fold_shift, pl.fold_rows, W, mbits, sbins, pl.sbits ? pl.sbits : 256};
     s.fbins = pl.F > 1 ? (uint32_t)pl.Keff * ncb : s.nbins;
     s.fine_top = pl.F > 1 ? s.fbins - ncb : top_bin;
     // kernels specialized for the window size (unrolled window loop) where one is compiled: 16 / 17, the defaults of
@@ -486,21 +510,22 @@ struct Planner {
   // What a precomputed set over n points is built with: c, GLV choice and copies (factor; 0 = enough copies for every
   // window, the GLV retry's included).  Checks that its bucket sets fit one sort pass and its records the 30-bit field.
   int precompute_params(uint64_t n, const msmz_opts* o, uint32_t factor, int* c_out, int* glv_out, uint32_t* f_out,
-                        int* k_out) const {
+                        int* k_out, int* sbits_out = nullptr) const {
     if (n == 0 || factor == 1) return MSMZ_ERR_ARG;
     msmz_opts opt;
     memset(&opt, 0, sizeof(opt));
     if (o) opt = *o; else opt.glv = -1;
     if (opt.buckets == MSMZ_BUCKETS_PROJECTIVE || opt.reserved[0] == 1) return MSMZ_ERR_UNSUPPORTED;
-    if (opt.c < 0 || opt.c > 24) return MSMZ_ERR_ARG;
+    if (opt.c < 0 || opt.c > 24 || opt.reserved[1] < 0 || opt.reserved[1] > 256) return MSMZ_ERR_ARG;
+    const int sb = bound(opt.reserved[1]);
     int glv = opt.glv;
-    if (glv < 0) glv = default_glv(n) ? 1 : 0;   // msm()'s choice for n points
+    if (glv < 0) glv = default_glv(n, sb) ? 1 : 0;   // msm()'s choice for n points
     if (glv && !Fr::HAS_GLV) return MSMZ_ERR_UNSUPPORTED;
     glv = glv ? 1 : 0;
     const uint64_t M64 = glv ? 2 * n : n;
     if (M64 > (1ull << 24)) return MSMZ_ERR_ARG;
     const uint32_t M = (uint32_t)M64;
-    const int b0 = scalar_bits(glv != 0, 0), b1 = scalar_bits(glv != 0, 1);
+    const int b0 = scalar_bits(glv != 0, 0, sb), b1 = scalar_bits(glv != 0, 1, sb);
     // window size: the user's, or the model's for F copies (0: all windows in one set)
     int c = opt.c;
     auto windows = [&](int cc, int b) { return (b + 1 + cc - 1) / cc; };
@@ -517,6 +542,7 @@ struct Planner {
     *glv_out = glv;
     *f_out = copies;
     if (k_out) *k_out = K0;
+    if (sbits_out) *sbits_out = sb;
     return MSMZ_OK;
   }
 };

@@ -53,6 +53,13 @@ __device__ __forceinline__ uint32_t scan_bin(const SortGeom& g, uint32_t b) {
   return ((k / g.F) * g.ncb + co) * g.F + k % g.F;
 }
 
+// A FOLDED top window holds digits up to 2^fold_shift only (the planner's bound on the largest scalar, or on a GLV half of
+// the assumed length).  A longer half's top digit would leave the set's buckets -- and the kernels' LDS arrays -- so it
+// is dropped, in k_hist (which flags it: the MSM is redone with the proven half length) and k_coarse alike.
+__device__ __forceinline__ bool fold_overflow(const SortGeom& g, int k, uint32_t l) {
+  return g.fold_shift != 0 && k == g.K - 1 && l > (1u << g.fold_shift);
+}
+
 // bucket index (weight - 1) of digit l of window k inside its bucket set
 __device__ __forceinline__ uint32_t bucket_index(const SortGeom& g, int k, uint32_t l, uint32_t entry) {
   if (g.fold_shift != 0 && k == g.K - 1) return ((entry & ((1u << g.fold_rows) - 1u)) << g.fold_shift) + l - 1u;
@@ -83,8 +90,10 @@ struct DigitStream {
   uint32_t neg;     // bit h: half h is negative
   uint32_t carry;   // bit h: carry into the next window of half h
 
-  // returns false when the scalar is not below the group order
-  __device__ __forceinline__ bool load(const uint32_t* scalars, uint32_t i) {
+  // returns false when the scalar is not below the group order or not below the caller's bound 2^sbits (SortGeom::sbits).
+  // Such a scalar must contribute no digit (its top digit may exceed what the window geometry assumes): callers clear()
+  // it, k_hist and k_coarse alike so that counts and staging agree.
+  __device__ __forceinline__ bool load(const uint32_t* scalars, uint32_t i, int sbits) {
     uint32_t s[8];
     const uint4* p4 = reinterpret_cast<const uint4*>(scalars + (size_t)i * 8);
     const uint4 a = p4[0], b = p4[1];
@@ -100,7 +109,7 @@ struct DigitStream {
       for (int j = 0; j < 8; j++) w[0][j] = s[j];
       neg = 0;
     }
-    return !words_geq<8>(s, Fr::Q);
+    return !(words_geq<8>(s, Fr::Q) || words_geq_pow2(s, sbits));
   }
   __device__ __forceinline__ void clear() {
 #pragma unroll
@@ -191,7 +200,8 @@ __device__ __forceinline__ uint32_t coarse_bin(const SortGeom& g, int k, uint32_
 // ------------------------------------------------------------------------------------------------ histogram
 // counts[bin] += entries; meta->error |= 2 when a scalar does not fit K windows (a GLV half above the assumed
 // bound: the host then repeats the MSM with one more bit), |= 4 when a scalar is not below the group order
-// (scalarsFromBytes' precondition, checked here instead of in a serial host loop).
+// (scalarsFromBytes' precondition, checked here instead of in a serial host loop) or not below the caller's bound
+// 2^g.sbits; such a scalar is cleared and adds to no bin.
 // C > 0: specialized for window size C (window loop unrolled, DigitStream::next_c); C = 0: any window size.
 template <class Fr, bool GLV, int C>
 __global__ void __launch_bounds__(COARSE_T, 8) k_hist(uint32_t* counts, uint16_t* tile_counts, uint32_t* tile_offs, MsmMeta* meta,
@@ -215,7 +225,10 @@ __global__ void __launch_bounds__(COARSE_T, 8) k_hist(uint32_t* counts, uint16_t
   for (int it = 0; it < PER; it++) {
     idx[it] = (blockIdx.x * PER + it) * COARSE_T + threadIdx.x;
     if (idx[it] < g.n) {
-      if (!ds[it].load(scalars, idx[it])) bad |= 4u;
+      if (!ds[it].load(scalars, idx[it], g.sbits)) {
+        bad |= 4u;
+        ds[it].clear();
+      }
     } else {
       ds[it].clear();
     }
@@ -228,6 +241,10 @@ __global__ void __launch_bounds__(COARSE_T, 8) k_hist(uint32_t* counts, uint16_t
       for (int h = 0; h < HALVES; h++) {
         uint32_t ng, l;
         if constexpr (C > 0) l = ds[it].template next_c<decltype(kk)::value, C>(h, ng); else l = ds[it].next(h, k, g.c, L, ng);
+        if (fold_overflow(g, k, l)) {
+          bad |= 2u;
+          l = 0;
+        }
         if (l != 0) atomicAdd(&s_hist[coarse_bin(g, k, l, (uint32_t)h * g.n + idx[it])], 1u);
       }
     }
@@ -349,7 +366,7 @@ __global__ void __launch_bounds__(COARSE_T, 8) k_coarse(uint32_t* packed_out, co
 #pragma unroll
   for (int s = 0; s < SC; s++) {
     idx[s] = (blockIdx.x * SC + s) * COARSE_T + threadIdx.x;
-    if (idx[s] < g.n) ds[s].load(scalars, idx[s]); else ds[s].clear();
+    if (idx[s] >= g.n || !ds[s].load(scalars, idx[s], g.sbits)) ds[s].clear();   // (out of range: no digit, as in k_hist)
   }
   {
     const uint16_t* row = tile_counts + (size_t)blockIdx.x * nbins;
@@ -424,6 +441,9 @@ __global__ void __launch_bounds__(COARSE_T, 8) k_coarse(uint32_t* packed_out, co
       for (int h = 0; h < HALVES; h++) {
         uint32_t ng, l;
         if constexpr (C > 0) l = ds[s].template next_c<decltype(kk)::value, C>(h, ng); else l = ds[s].next(h, k, g.c, L, ng);
+        if constexpr (TOP) {
+          if (fold_overflow(g, k, l)) l = 0;
+        }
         if (l != 0) {
           uint32_t bi = l - 1u, bin;
           if constexpr (TOP) {

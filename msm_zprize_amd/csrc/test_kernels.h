@@ -175,7 +175,7 @@ __global__ void __launch_bounds__(256) k_test_digits(uint32_t* digits, const uin
   constexpr int HALVES = GLV ? 2 : 1;
   const uint32_t L = 1u << (c - 1);
   DigitStream<Fr, GLV> ds;
-  ds.load(scalars, i);
+  ds.load(scalars, i, 256);
   for (int k = 0; k < K; k++) {
 #pragma unroll
     for (int h = 0; h < HALVES; h++) {

@@ -156,12 +156,15 @@ class _Parallel:
         """Fixed-base precomputation of the first N resident points (msmz_precompute_points): a new DeviceArray of kind
         "precomputed" that msm / msmUnsafe / msmBatch / msmBatchUnsafe accept in place of `points` (same results).
         `factor` = windows sharing one bucket set (0 = all; 1 is refused); options["c"] / options["glv"] fix the window
-        size and GLV choice (default: the engine's).  The copies' parameters are in the array's `info` dict."""
+        size and GLV choice (default: the engine's), options["scalarBits"] the scalar bit bound the copies are built for
+        (fewer windows, fewer copies; MSMs over the array then take that bound).  The copies' parameters are in the
+        array's `info` dict."""
         options = dict(options or {})
         c, glv, factor = precompute_args(points, N, options, factor)
         opts = MsmzOpts()
         opts.c = c
         opts.glv = glv
+        opts.reserved[1] = scalar_bits_arg(options, "precomputePoints")
         h = C.c_uint64()
         check(lib().msmz_precompute_points(self._c._ctx, points.handle, N, C.byref(opts), factor, C.byref(h)),
               "msmz_precompute_points")
@@ -169,6 +172,9 @@ class _Parallel:
         vals = [C.c_int32(), C.c_int32(), C.c_uint32(), C.c_uint32(), C.c_uint64()]
         check(lib().msmz_precomputed_info(self._c._ctx, h.value, *[C.byref(v) for v in vals]), "msmz_precomputed_info")
         arr.info = dict(zip(("c", "glv", "factor", "K", "records"), (v.value for v in vals)))
+        bits = C.c_int32()
+        check(lib().msmz_precomputed_scalar_bits(self._c._ctx, h.value, C.byref(bits)), "msmz_precomputed_scalar_bits")
+        arr.info["scalarBits"] = bits.value
         return arr
 
     # -- the MSM --------------------------------------------------------------------------------
@@ -181,6 +187,7 @@ class _Parallel:
         opts.buckets = buckets
         opts.timing = 1 if verbose else 0
         opts.reserved[0] = int(options.get("reduceAffine", 0))   # 1: batched-affine first reduction level (reduceBucketsAffine)
+        opts.reserved[1] = scalar_bits_arg(options, "msm")       # every scalar is below 2^scalarBits (0: no bound)
         fb = self._c.fe_bytes
         out = C.create_string_buffer(2 * fb)
         inf = C.c_int()
@@ -223,6 +230,7 @@ class _Parallel:
         opts.safe = int(options.get("useSafeAdditions", safe))
         opts.buckets = int(options.get("buckets", 0))
         opts.reserved[0] = int(options.get("reduceAffine", 0))
+        opts.reserved[1] = scalar_bits_arg(options, "msmBatch")
         fb = self._c.fe_bytes
         out = C.create_string_buffer(2 * fb * B)
         inf = (C.c_int * B)()
@@ -276,7 +284,20 @@ def precompute_args(points, N, options, factor):
         raise ValueError(f"precomputePoints: c = {c} (0 = the engine's choice, or 2..24)")
     if glv not in (-1, 0, 1):
         raise ValueError(f"precomputePoints: glv = {glv} (-1, 0 or 1)")
+    scalar_bits_arg(options, "precomputePoints")
     return c, glv, factor
+
+
+def scalar_bits_arg(options, who):
+    """options["scalarBits"] -> msmz_opts.reserved[1]: "every scalar of this call is below 2^scalarBits".  0 / absent = no
+    bound; a value of at least the scalar field's bit length means the same; the window count follows the bound, and a
+    scalar that breaks it fails the call (MSMZ_ERR_RANGE).  Checked before anything reaches the device."""
+    bits = options.get("scalarBits")
+    if bits is None:
+        return 0
+    if isinstance(bits, bool) or not isinstance(bits, int) or not 0 <= bits <= 256:
+        raise ValueError(f"{who}: scalarBits = {bits!r} (0 = no bound, or 1..256)")
+    return bits
 
 
 def batch_scalars(scalarsList, N, batch=None):

@@ -236,6 +236,7 @@ static napi_value Msm(napi_env env, napi_callback_info info) {
     o.buckets = opt_i32(env, argv[5], "buckets");
     o.timing = opt_i32(env, argv[5], "timing");
     o.reserved[0] = opt_i32(env, argv[5], "reduceAffine");
+    o.reserved[1] = opt_i32(env, argv[5], "scalarBits");   /* every scalar < 2^scalarBits; 0 = no bound */
   }
   void* data; napi_value xy;
   NAPI_CALL(env, napi_create_buffer(env, (size_t)(2 * fb), &data, &xy));
@@ -289,6 +290,7 @@ static napi_value MsmBatch(napi_env env, napi_callback_info info) {
     o.safe = opt_i32(env, argv[6], "safe");
     o.buckets = opt_i32(env, argv[6], "buckets");
     o.reserved[0] = opt_i32(env, argv[6], "reduceAffine");
+    o.reserved[1] = opt_i32(env, argv[6], "scalarBits");
   }
   void* data; napi_value xy;
   NAPI_CALL(env, napi_create_buffer(env, (size_t)(2 * fb * batch), &data, &xy));
@@ -322,7 +324,7 @@ static napi_value MsmBatch(napi_env env, napi_callback_info info) {
 }
 
 /* pointAdd(curveId, aXy|null, bXy|null, feBytes) -> {xy, isInf}  (null = infinity) */
-/* precomputePoints(ctx, pointsHandle, n, {c, glv}, factor) -> handle of a precomputed point set (msmz_precompute_points;
+/* precomputePoints(ctx, pointsHandle, n, {c, glv, scalarBits}, factor) -> handle of a precomputed point set (msmz_precompute_points;
    glv -1 = the engine's choice, factor 0 = all windows in one bucket set) */
 static napi_value PrecomputePoints(napi_env env, napi_callback_info info) {
   size_t argc = 5; napi_value argv[5];
@@ -334,13 +336,15 @@ static napi_value PrecomputePoints(napi_env env, napi_callback_info info) {
   msmz_opts o; memset(&o, 0, sizeof(o));
   o.c = opt_i32(env, argv[3], "c");
   o.glv = opt_i32(env, argv[3], "glv");
+  o.reserved[1] = opt_i32(env, argv[3], "scalarBits");
   uint64_t h = 0;
   int st = msmz_precompute_points(ctx, ph, n, &o, (uint32_t)factor, &h);
   if (st) return throw_status(env, st, "msmz_precompute_points");
   return make_handle(env, h);
 }
 
-/* precomputedInfo(ctx, handle) -> {c, glv, factor, K, records} (msmz_precomputed_info) */
+/* precomputedInfo(ctx, handle) -> {c, glv, factor, K, records, scalarBits} (msmz_precomputed_info,
+   msmz_precomputed_scalar_bits) */
 static napi_value PrecomputedInfo(napi_env env, napi_callback_info info) {
   size_t argc = 2; napi_value argv[2];
   NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -349,10 +353,13 @@ static napi_value PrecomputedInfo(napi_env env, napi_callback_info info) {
   int32_t c = 0, glv = 0; uint32_t factor = 0, K = 0; uint64_t records = 0;
   int st = msmz_precomputed_info(ctx, h, &c, &glv, &factor, &K, &records);
   if (st) return throw_status(env, st, "msmz_precomputed_info");
+  int32_t sbits = 0;
+  st = msmz_precomputed_scalar_bits(ctx, h, &sbits);
+  if (st) return throw_status(env, st, "msmz_precomputed_scalar_bits");
   napi_value res;
   NAPI_CALL(env, napi_create_object(env, &res));
   set_num(env, res, "c", c); set_num(env, res, "glv", glv); set_num(env, res, "factor", factor);
-  set_num(env, res, "K", K); set_num(env, res, "records", (double)records);
+  set_num(env, res, "K", K); set_num(env, res, "records", (double)records); set_num(env, res, "scalarBits", sbits);
   return res;
 }
 
