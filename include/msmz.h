@@ -17,6 +17,10 @@
  *            (BLS12-377 / BLS12-381) or 32 (Pallas, ed-on-bls12-377); optional per-point infinity flag
  *   scalar = 32 bytes little-endian, value < group order
  *   result = canonical affine x || y (both < p) + infinity flag -- "bit-exact" is defined on this.
+ * Imported forms (msmz_import_scalars / msmz_import_points, below): the same records read where the caller has them, in
+ * host or device memory, at a byte stride; scalars of 4..32 bytes (zero-extended); scalars and coordinates optionally
+ * as 64-bit-limb Montgomery residues (v * 2^256 mod q, v * 2^(8 fe_bytes) mod p).  The resident format and the results
+ * are the same whichever way the data came in.
  */
 #ifndef MSMZ_H
 #define MSMZ_H
@@ -43,7 +47,8 @@ enum {
   MSMZ_ERR_UNSUPPORTED = 4,  /* option combination not available for this curve */
   MSMZ_ERR_DEGENERATE = 5,   /* msmUnsafe hit P + (+-P): a batch inversion saw a zero denominator
                                 (the reference traps with wasm `unreachable`, inverse.ts:198-199) */
-  MSMZ_ERR_RANGE = 6         /* a scalar is >= the group order (or >= 2^bits of msmz_opts.reserved[1]) / a coordinate is >= p */
+  MSMZ_ERR_RANGE = 6         /* a scalar is >= the group order (or >= 2^bits of msmz_opts.reserved[1]) / a coordinate is >= p;
+                                imported Montgomery residues: the residue itself is >= q / >= p */
 };
 
 enum { MSMZ_BUCKETS_AFFINE = 0, MSMZ_BUCKETS_PROJECTIVE = 1 };
@@ -125,6 +130,59 @@ int msmz_download_points(msmz_ctx* ctx, uint64_t handle, uint64_t first, uint64_
                          uint8_t* is_inf /* nullable */);
 int msmz_download_scalars(msmz_ctx* ctx, uint64_t handle, uint64_t first, uint64_t count, uint8_t* scalars_le32);
 int msmz_free(msmz_ctx* ctx, uint64_t handle);
+
+/* Import: make a resident handle of records where the caller has them, in the form they have.
+ * The handles are ordinary scalar / point handles: every function that takes an uploaded one takes them, an MSM over
+ * them returns the same bytes, msmz_download_* return the canonical values.
+ *   flags 0               ptr (and is_inf) are host memory; only `width` bytes per record are copied to the GPU (a
+ *                         strided source is packed on the host first).  Scalars of width 32 at stride 0: the handle
+ *                         holds what msmz_upload_scalars leaves.
+ *   MSMZ_SRC_DEVICE       ptr (and is_inf) are memory of the context's GPU, or pinned / registered host memory it can
+ *                         read.  The engine asks the HIP runtime what the pointer is (hipPointerGetAttributes) and that the
+ *                         whole source lies inside that one allocation (hipMemGetAddressRange), and refuses anything
+ *                         else with MSMZ_ERR_ARG: no kernel is launched
+ *                         on a pointer the runtime does not know.  Ordering: `stream` (a hipStream_t) is the stream
+ *                         whose queued work produces the data -- the engine records an event on it and makes its own
+ *                         stream wait for that event, no host wait; NULL = the data is ready.  The null stream cannot be
+ *                         named by a pointer: MSMZ_SRC_DEFAULT_STREAM says "order after the device's null stream".
+ *   MSMZ_SRC_MONTGOMERY   records are 64-bit-limb Montgomery residues (arkworks / sppark style; little-endian limbs =
+ *                         little-endian bytes): scalars v * 2^256 mod q (width 32 only), coordinates
+ *                         v * 2^(8 fe_bytes) mod p.  Converted on the GPU.
+ * Every import returns after the GPU has read the source: it may be overwritten or freed at once.
+ * Errors.  MSMZ_ERR_ARG, before anything is launched: a null descriptor / pointer / handle pointer, n == 0 (scalars:
+ * n >= 2^32; points: the limits of msmz_upload_points), unknown flag bits, a stream without MSMZ_SRC_DEVICE, a pointer not
+ * 4-byte aligned, a stride that is neither 0 nor a multiple of 4 of at least the width (or is 2^24 or more), a scalar width outside 4..32
+ * or not a multiple of 4 or (Montgomery) other than 32, a point width other than 0 or 2 * fe_bytes, is_inf on a scalar
+ * source, memory the runtime does not vouch for.  MSMZ_ERR_RANGE, found by the conversion kernel: a scalar or residue
+ * >= q, a coordinate or residue >= p; no handle is created and the context stays usable.
+ * msmz_import_scalars_into writes n scalars over entries [first, first + n) of an existing scalar handle and nothing else
+ * (a batch assembled vector by vector); a handle that is not a scalar set or first + n beyond it is MSMZ_ERR_ARG; after
+ * MSMZ_ERR_RANGE the contents of [first, first + n) are unspecified.
+ * Multi-device contexts: a device source is first copied to the host, then dealt to the devices like an upload, so the
+ * result equals an upload and nothing is gained; msmz_import_scalars_into returns MSMZ_ERR_UNSUPPORTED there (a vector
+ * start is not a block boundary of the devices' shares).  Like the rest of the multi-device code this has run on several
+ * engines of ONE GPU only. */
+enum {
+  MSMZ_SRC_DEVICE = 1,
+  MSMZ_SRC_MONTGOMERY = 2,
+  MSMZ_SRC_DEFAULT_STREAM = 4   /* with MSMZ_SRC_DEVICE and a NULL stream: the data is produced on the null stream */
+};
+typedef struct msmz_src {
+  const void* ptr;        /* first record */
+  uint64_t stride;        /* bytes from one record to the next; 0 = packed (= the width) */
+  uint32_t width;         /* scalars: bytes per record, 4..32, a multiple of 4; points: 0 or 2 * fe_bytes */
+  uint32_t flags;         /* MSMZ_SRC_* */
+  void* stream;           /* MSMZ_SRC_DEVICE: the hipStream_t whose work produces the data; NULL = the data is ready */
+  const uint8_t* is_inf;  /* points only, nullable: one flag byte per point, packed, same memory space as ptr; checked but
+                             without effect on the twisted-Edwards curve, which has no point at infinity (as the
+                             is_inf of msmz_upload_points) */
+} msmz_src;
+int msmz_import_scalars(msmz_ctx* ctx, const msmz_src* src, uint64_t n, uint64_t* handle);
+int msmz_import_scalars_into(msmz_ctx* ctx, uint64_t handle, uint64_t first, const msmz_src* src, uint64_t n);
+int msmz_import_points(msmz_ctx* ctx, const msmz_src* src, uint64_t n, uint64_t* handle);
+/* a new scalar handle of n zeros, the target msmz_import_scalars_into fills (n == 0 or n >= 2^32: MSMZ_ERR_ARG; a
+ * multi-device context: MSMZ_ERR_UNSUPPORTED, as _into) */
+int msmz_alloc_scalars(msmz_ctx* ctx, uint64_t n, uint64_t* handle);
 
 /* The MSM: sum_i scalar_i * point_i over the first n entries.  Scalars either come from a host
  * buffer (copied to the GPU inside the call) or are already resident (scalars_handle).

@@ -16,7 +16,11 @@ export interface ParallelApi {
   randomPointsFast(n: number, options?: { seed?: bigint | number }): Promise<DeviceArray>;
   randomScalars(n: number, options?: { seed?: bigint | number }): Promise<DeviceArray>;
   pointsFromBytes(bytes: Uint8Array, n?: number, isInf?: Uint8Array): Promise<DeviceArray>;
+  /** coordinates as 64-bit-limb Montgomery residues v * 2^(8 feBytes) mod p, converted on the GPU */
+  pointsFromBytes(bytes: Uint8Array, n: number | undefined, options: { montgomery?: boolean; isInf?: Uint8Array }): Promise<DeviceArray>;
   scalarsFromBytes(bytes: Uint8Array, n?: number): Promise<DeviceArray>;
+  /** `width` bytes per scalar on the wire (4..32, a multiple of 4); montgomery: 32-byte records v * 2^256 mod q */
+  scalarsFromBytes(bytes: Uint8Array, n: number | undefined, options: { width?: number; montgomery?: boolean }): Promise<DeviceArray>;
   /** pointer-style routes of src/parallel.ts:89-133: pointers are numbers in a virtual address space */
   getPointer(size: number): Promise<number>;
   getScalarPointer(size: number): Promise<number>;

@@ -274,8 +274,14 @@ function createCurve(params, kind) {
         dst.host = src.host.subarray(soff, soff + count * 2 * fb); dst.count = count; dst.dirty = false; dst.inf = null;
         return;
       }
+      // (bytes, n?, {montgomery, isInf}): coordinates as 64-bit-limb Montgomery residues v * 2^(8 feBytes) mod p
+      let montgomery = false;
+      if (isInf && typeof isInf === "object" && !ArrayBuffer.isView(isInf) && !Array.isArray(isInf)) {
+        montgomery = !!isInf.montgomery; isInf = isInf.isInf;
+      }
       n = n === undefined ? Math.floor(bytes.length / (2 * fb)) : n;
       if (!(n > 0) || bytes.length < 2 * fb * n || (isInf && isInf.length < n)) throw Error(`pointsFromBytes: ${bytes.length} bytes for ${n} points`);
+      if (montgomery) return DeviceArray.make(curve, N.importPoints(ctx, Buffer.from(bytes), isInf ? Buffer.from(isInf) : null, n, true), n, "points");
       return DeviceArray.make(curve, N.uploadPoints(ctx, Buffer.from(bytes), isInf ? Buffer.from(isInf) : null, n), n, "points");
     },
     /** parallel.ts:114-133: 32 bytes little-endian per scalar */
@@ -287,6 +293,18 @@ function createCurve(params, kind) {
         dst.device = DeviceArray.make(curve, N.uploadScalars(ctx, src.host.subarray(soff, soff + count * 32), count), count, "scalars");
         dst.host = src.host.subarray(soff, soff + count * 32); dst.count = count; dst.dirty = false;
         return;
+      }
+      // (bytes, n?, {width, montgomery}): `width` bytes per scalar on the wire (4..32, a multiple of 4, zero-extended on
+      // the GPU); montgomery: 32-byte records v * 2^256 mod q.  Without them: the plain upload, as before.
+      if (count && typeof count === "object") {
+        const width = count.width === undefined ? 32 : count.width, montgomery = !!count.montgomery;
+        if (!Number.isInteger(width) || width < 4 || width > 32 || width % 4) throw Error(`scalarsFromBytes: width = ${width} (4..32 bytes, a multiple of 4)`);
+        if (montgomery && width !== 32) throw Error(`scalarsFromBytes: Montgomery scalars are 32-byte records, not ${width}`);
+        if (width !== 32 || montgomery) {
+          n = n === undefined ? Math.floor(bytes.length / width) : n;
+          if (!(n > 0) || bytes.length < width * n) throw Error(`scalarsFromBytes: ${bytes.length} bytes for ${n} scalars of ${width} bytes`);
+          return DeviceArray.make(curve, N.importScalars(ctx, Buffer.from(bytes), n, width, montgomery), n, "scalars");
+        }
       }
       n = n === undefined ? Math.floor(bytes.length / 32) : n;
       if (!(n > 0) || bytes.length < 32 * n) throw Error(`scalarsFromBytes: ${bytes.length} bytes for ${n} scalars`);

@@ -25,6 +25,14 @@ class MsmzLog(C.Structure):
                 ("scatter_launches", C.c_uint32), ("scatter_kernel_ms", C.c_float), ("batch_add_ms", C.c_float * 32)]
 
 
+MSMZ_SRC_DEVICE, MSMZ_SRC_MONTGOMERY, MSMZ_SRC_DEFAULT_STREAM = 1, 2, 4
+
+
+class MsmzSrc(C.Structure):   # msmz_src (include/msmz.h): where an imported set lies and in which form
+    _fields_ = [("ptr", C.c_void_p), ("stride", C.c_uint64), ("width", C.c_uint32), ("flags", C.c_uint32),
+                ("stream", C.c_void_p), ("is_inf", C.c_void_p)]
+
+
 class MsmzTestReduceArgs(C.Structure):   # msmz_test_reduce_args (include/msmz_test.h)
     _fields_ = [("mode", C.c_int32), ("c", C.c_int32), ("nsets", C.c_uint32), ("n_in", C.c_uint32),
                 ("nc", C.c_uint32), ("tail_n", C.c_uint32), ("quad16_max", C.c_uint32), ("pairsum_x4_max", C.c_uint32),
@@ -44,6 +52,10 @@ EXPORTS = {
     "msmz_ctx_n_devices": (C.c_int, [C.c_void_p]),
     "msmz_upload_points": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "msmz_upload_scalars": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "msmz_import_scalars": (C.c_int, [C.c_void_p, C.POINTER(MsmzSrc), C.c_uint64, C.POINTER(C.c_uint64)]),
+    "msmz_import_scalars_into": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(MsmzSrc), C.c_uint64]),
+    "msmz_alloc_scalars": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "msmz_import_points": (C.c_int, [C.c_void_p, C.POINTER(MsmzSrc), C.c_uint64, C.POINTER(C.c_uint64)]),
     "msmz_random_points": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "msmz_random_scalars": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "msmz_download_points": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_char_p, C.c_char_p]),

@@ -17,6 +17,7 @@
 #include "../../include/msmz.h"
 #include "kernels.h"
 #include "gen_kernels.h"
+#include "import_kernels.h"
 #include "host64.h"
 #include "multi.h"
 #include "plan.h"
@@ -195,6 +196,7 @@ class Engine : public IEngine {
     MSMZ_HIP(hipSetDevice(device_));
     MSMZ_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
     for (hipEvent_t* e : ev_.all()) MSMZ_HIP(hipEventCreate(e));
+    MSMZ_HIP(hipEventCreateWithFlags(&import_ev_, hipEventDisableTiming));
     MSMZ_HIP(hipHostMalloc(&h_meta_, sizeof(MsmMeta)));
     int st;
     if ((st = ensure_host_results((size_t)2 * kMaxWindows * XW))) return st;   // the results of one problem
@@ -272,6 +274,7 @@ class Engine : public IEngine {
     if (h_res_) (void)hipHostFree(h_res_);
     for (hipEvent_t* e : ev_.all())
       if (*e) (void)hipEventDestroy(*e);
+    if (import_ev_) (void)hipEventDestroy(import_ev_);
     if (stream_) (void)hipStreamDestroy(stream_);
   }
 
@@ -321,6 +324,204 @@ class Engine : public IEngine {
     return add_handle(std::move(hd), h);
   }
 
+  // ------------------------------------------------------------------------------------------ imports
+  int import_scalars(const msmz_src& s, uint64_t n, uint64_t* h, const GenMap* split = nullptr) override {
+    if (!h || n == 0 || n >> 32) return MSMZ_ERR_ARG;
+    MSMZ_HIP(hipSetDevice(device_));
+    Handle hd{1, n, false};
+    ImportView v;
+    int st;
+    {
+      uint32_t w = 0;
+      uint64_t sb = 0;
+      if ((st = src_check(&s, 0, &w, &sb))) return st;
+    }
+    if ((st = alloc_handle(hd, n * 32)) || (st = import_view(s, 0, n, split, &v))) return st;   // (allocate first: no copy is queued yet)
+    if ((st = import_scalars_to(hd.mem.as<uint32_t>(), s, v, n))) return st;
+    return add_handle(std::move(hd), h);
+  }
+
+  // a new scalar set of n zeros: the target of import_scalars_into when a batch is assembled vector by vector
+  int alloc_scalars(uint64_t n, uint64_t* h) override {
+    if (!h || n == 0 || n >> 32) return MSMZ_ERR_ARG;
+    MSMZ_HIP(hipSetDevice(device_));
+    Handle hd{1, n, false};
+    if (int st = alloc_handle(hd, n * 32)) return st;
+    MSMZ_HIP(hipMemsetAsync(hd.mem.p, 0, n * 32, stream_));
+    MSMZ_HIP(hipStreamSynchronize(stream_));
+    return add_handle(std::move(hd), h);
+  }
+
+  int import_scalars_into(uint64_t h, uint64_t first, const msmz_src& s, uint64_t n) override {
+    auto it = handles_.find(h);
+    if (it == handles_.end() || it->second.kind != 1 || n == 0) return MSMZ_ERR_ARG;
+    if (first > it->second.n || n > it->second.n - first) return MSMZ_ERR_ARG;   // (no first + n: it can wrap)
+    MSMZ_HIP(hipSetDevice(device_));
+    ImportView v;
+    if (int st = import_view(s, 0, n, nullptr, &v)) return st;
+    return import_scalars_to(it->second.mem.template as<uint32_t>() + first * 8, s, v, n);
+  }
+
+  int import_points(const msmz_src& s, uint64_t n, uint64_t* h, const GenMap* split = nullptr) override {
+    if (!h || n == 0 || n >= (1ull << (Cfg::HAS_ENDO ? 29 : 30))) return MSMZ_ERR_ARG;   // as upload_points
+    MSMZ_HIP(hipSetDevice(device_));
+    ImportView v;
+    int st;
+    const bool endo = Cfg::HAS_ENDO;
+    const int mont = (s.flags & MSMZ_SRC_MONTGOMERY) ? 1 : 0;
+    Handle hd{0, n, endo};
+    {   // (checked before the allocation, which comes before any copy is queued)
+      uint32_t w = 0;
+      uint64_t sb = 0;
+      if ((st = src_check(&s, FE_BYTES, &w, &sb))) return st;
+    }
+    if ((st = alloc_handle(hd, (size_t)n * PW_WORDS * 4 * (endo ? 2 : 1))) || (st = import_view(s, FE_BYTES, n, split, &v))) return st;
+    MsmMeta* d_meta = meta_.as<MsmMeta>();
+    MSMZ_HIP(hipMemsetAsync(&d_meta->error, 0, 4, stream_));
+    if constexpr (TE) {
+      hipLaunchKernelGGL((k_te_import_points<F>), dim3((n + 255) / 256), dim3(256), 0, stream_, hd.mem.as<uint32_t>(),
+                         v.ptr, v.stride, (uint32_t)n, mont, &d_meta->error);
+    } else {
+      hipLaunchKernelGGL((k_import_points<F>), dim3((n + 255) / 256), dim3(256), 0, stream_, hd.mem.as<uint32_t>(), v.ptr,
+                         v.stride, v.is_inf, (uint32_t)n, endo ? 1 : 0, mont, &d_meta->error);
+    }
+    uint32_t err = 0;
+    if ((st = fetch_error(&err))) return st;
+    if (err) return MSMZ_ERR_RANGE;   // a coordinate (either form) >= p
+    return add_handle(std::move(hd), h);
+  }
+
+  int gather_src(const msmz_src& s, int point_fe_bytes, uint64_t n, std::vector<uint8_t>* recs,
+                 std::vector<uint8_t>* flags) override {
+    uint32_t width = 0;
+    uint64_t stride = 0;
+    if (int st = src_check(&s, point_fe_bytes, &width, &stride)) return st;
+    if (n == 0 || n >> 32 || !recs || !flags) return MSMZ_ERR_ARG;
+    recs->resize((size_t)n * width);
+    flags->clear();
+    const uint8_t* p = (const uint8_t*)s.ptr;
+    if (!(s.flags & MSMZ_SRC_DEVICE)) {
+      for (uint64_t i = 0; i < n; i++) memcpy(recs->data() + i * width, p + i * stride, width);
+      if (s.is_inf) flags->assign(s.is_inf, s.is_inf + n);
+      return MSMZ_OK;
+    }
+    MSMZ_HIP(hipSetDevice(device_));
+    const void* dp = nullptr;
+    const void* di = nullptr;
+    int st;
+    if ((st = vouch(p, (n - 1) * stride + width, true, &dp))) return st;
+    if (s.is_inf && (st = vouch(s.is_inf, n, true, &di))) return st;
+    if (s.stream) MSMZ_HIP(hipStreamSynchronize((hipStream_t)s.stream));
+    if (s.flags & MSMZ_SRC_DEFAULT_STREAM) MSMZ_HIP(hipStreamSynchronize(nullptr));
+    MSMZ_HIP(hipMemcpy2D(recs->data(), width, dp, stride, width, n, hipMemcpyDefault));
+    if (di) {
+      flags->resize(n);
+      MSMZ_HIP(hipMemcpy(flags->data(), di, n, hipMemcpyDefault));
+    }
+    return MSMZ_OK;
+  }
+
+ private:
+  // where the import kernel reads: the caller's device memory, or the packed staging copy of a host source
+  struct ImportView {
+    const uint8_t* ptr = nullptr;
+    uint64_t stride = 0;
+    uint32_t width = 0;
+    const uint8_t* is_inf = nullptr;
+  };
+
+  // May a kernel of this device read [p, p + bytes)?  Yes only if the HIP runtime knows p as memory of this device, or
+  // as pinned / registered host memory (then *dev is its device-side address), AND the whole range lies inside the one
+  // allocation p belongs to (hipMemGetAddressRange): a range that starts in one allocation and ends in another is
+  // refused, whatever lies between.  A pointer the runtime does not know (pageable host memory, a stale or made-up
+  // address), managed memory and another device's memory are refused: nothing is launched on them.  Pinned host memory
+  // whose allocation the runtime cannot report is accepted only if the first and the last byte are both pinned and
+  // their device-side addresses are `bytes - 1` apart.  any_device: the caller only copies (gather_src).
+  int vouch(const void* p, uint64_t bytes, bool any_device, const void** dev) const {
+    hipPointerAttribute_t a;
+    memset(&a, 0, sizeof(a));
+    if (bytes == 0 || hipPointerGetAttributes(&a, p) != hipSuccess) {
+      (void)hipGetLastError();   // (an unknown pointer is an answer, not a sticky error)
+      return MSMZ_ERR_ARG;
+    }
+    if ((a.type != hipMemoryTypeDevice && a.type != hipMemoryTypeHost) || a.isManaged) return MSMZ_ERR_ARG;
+    if (a.type == hipMemoryTypeDevice && !any_device && a.device != device_) return MSMZ_ERR_ARG;
+    *dev = a.type == hipMemoryTypeHost ? a.devicePointer : p;
+    if (!*dev) return MSMZ_ERR_ARG;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)*dev) == hipSuccess) {
+      const uintptr_t lo = (uintptr_t)base, at = (uintptr_t)*dev;
+      return at >= lo && bytes <= size && at - lo <= size - bytes ? MSMZ_OK : MSMZ_ERR_ARG;
+    }
+    (void)hipGetLastError();
+    if (a.type != hipMemoryTypeHost) return MSMZ_ERR_ARG;
+    hipPointerAttribute_t z;
+    memset(&z, 0, sizeof(z));
+    if (hipPointerGetAttributes(&z, (const uint8_t*)p + (bytes - 1)) != hipSuccess) {
+      (void)hipGetLastError();
+      return MSMZ_ERR_ARG;
+    }
+    if (z.type != hipMemoryTypeHost || z.isManaged || !z.devicePointer) return MSMZ_ERR_ARG;
+    return (uintptr_t)z.devicePointer - (uintptr_t)a.devicePointer == bytes - 1 ? MSMZ_OK : MSMZ_ERR_ARG;
+  }
+
+  // Checks the source and makes it readable for the import kernel, in stream order.  Device source: the pointers are
+  // vouched for and stream_ waits for an event recorded on the producing stream (no host wait).  Host source: `width`
+  // bytes per record go to stage_ (a strided source is packed on the host first; `split`: this engine's blocks of a
+  // packed source), the flag bytes behind them.
+  int import_view(const msmz_src& s, int point_fe_bytes, uint64_t n, const GenMap* split, ImportView* v) {
+    if (int st = src_check(&s, point_fe_bytes, &v->width, &v->stride)) return st;
+    const uint8_t* p = (const uint8_t*)s.ptr;
+    if (s.flags & MSMZ_SRC_DEVICE) {
+      if (split) return MSMZ_ERR_ARG;   // (a multi-device context hands its engines host copies)
+      const void* dp = nullptr;
+      int st;
+      if ((st = vouch(p, (n - 1) * v->stride + v->width, false, &dp))) return st;
+      v->ptr = (const uint8_t*)dp;
+      if (s.is_inf) {
+        if ((st = vouch(s.is_inf, n, false, &dp))) return st;
+        v->is_inf = (const uint8_t*)dp;
+      }
+      if (s.stream || (s.flags & MSMZ_SRC_DEFAULT_STREAM)) {
+        MSMZ_HIP(hipEventRecord(import_ev_, (hipStream_t)s.stream));
+        MSMZ_HIP(hipStreamWaitEvent(stream_, import_ev_, 0));
+      }
+      return MSMZ_OK;
+    }
+    const uint32_t w = v->width;
+    if (split && v->stride != w) return MSMZ_ERR_ARG;
+    int st = stage_.ensure((size_t)n * w + n);
+    if (st) return st;
+    if (v->stride != w) {
+      import_pack_.resize((size_t)n * w);   // (lives until the import's error-word fetch has drained the stream)
+      for (uint64_t i = 0; i < n; i++) memcpy(import_pack_.data() + i * w, p + i * v->stride, w);
+      p = import_pack_.data();
+    }
+    // (a failure once a copy may be queued drains the stream: when the call returns the source is no longer read)
+    if ((st = copy_h2d(stage_.p, p, w, n, split))) return (void)hipStreamSynchronize(stream_), st;
+    if (s.is_inf) {
+      uint8_t* d_inf = stage_.as<uint8_t>() + (size_t)n * w;
+      if ((st = copy_h2d(d_inf, s.is_inf, 1, n, split))) return (void)hipStreamSynchronize(stream_), st;
+      v->is_inf = d_inf;
+    }
+    v->ptr = stage_.as<const uint8_t>();
+    v->stride = w;
+    return MSMZ_OK;
+  }
+
+  // the conversion kernel over a view, then the error-word fetch: when it returns the source has been read
+  int import_scalars_to(uint32_t* dst, const msmz_src& s, const ImportView& v, uint64_t n) {
+    MsmMeta* d_meta = meta_.as<MsmMeta>();
+    MSMZ_HIP(hipMemsetAsync(&d_meta->error, 0, 4, stream_));
+    hipLaunchKernelGGL((k_import_scalars<Fr>), dim3((n + 255) / 256), dim3(256), 0, stream_, dst, v.ptr, v.stride,
+                       (int)(v.width / 4), (uint32_t)n, (s.flags & MSMZ_SRC_MONTGOMERY) ? 1 : 0, &d_meta->error);
+    uint32_t err = 0;
+    if (int st = fetch_error(&err)) return st;
+    return err ? MSMZ_ERR_RANGE : MSMZ_OK;   // a scalar (either form) >= group order
+  }
+
+ public:
   int random_points(uint64_t n, uint64_t seed, const GenMap& map, uint64_t* h) override {
     if (!h || n == 0 || n >= (1ull << (Cfg::HAS_ENDO ? 29 : 30))) return MSMZ_ERR_ARG;   // record indices (incl. endomorphism images) fit 30 bits
     MSMZ_HIP(hipSetDevice(device_));
@@ -1330,6 +1531,8 @@ class Engine : public IEngine {
   int curve_id_, device_;
   hipStream_t stream_ = nullptr;
   StageEvents ev_{};
+  hipEvent_t import_ev_ = nullptr;      // orders stream_ behind the stream that produces an imported device source
+  std::vector<uint8_t> import_pack_;    // host packing of a strided host source
   std::map<uint64_t, Handle> handles_;
   uint64_t next_handle_ = 1;
   // Tuning knobs (the planning ones: PlanKnobs, plan.h).  A release build uses the constants; a development build

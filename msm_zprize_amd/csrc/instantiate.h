@@ -3,6 +3,7 @@
 // `extern template` declarations.
 #pragma once
 #include "gen_kernels.h"
+#include "import_kernels.h"
 #include "kernels.h"
 #include "test_kernels.h"
 
@@ -95,11 +96,13 @@
   MSMZ_INST_SORT(Fr, false, 16, PFX)                                                                              \
   MSMZ_INST_SORT(Fr, false, 17, PFX)                                                                              \
   PFX template __global__ void k_check_scalars<Fr>(uint32_t*, const uint32_t*, uint32_t);                         \
-  PFX template __global__ void k_gen_scalars<Fr>(uint32_t*, uint32_t, uint64_t, GenMap);
+  PFX template __global__ void k_gen_scalars<Fr>(uint32_t*, uint32_t, uint64_t, GenMap);                          \
+  PFX template __global__ void k_import_scalars<Fr>(uint32_t*, const uint8_t*, uint64_t, int, uint32_t, int, uint32_t*);
 
 #define MSMZ_INST_MISC(F, Fr, PFX)                                                                                \
   PFX template __global__ void k_points_to_mont<F>(uint32_t*, const uint32_t*, const uint8_t*, uint32_t, int, uint32_t*); \
   PFX template __global__ void k_points_from_mont<F>(uint32_t*, const uint32_t*, uint32_t);                       \
+  PFX template __global__ void k_import_points<F>(uint32_t*, const uint8_t*, uint64_t, const uint8_t*, uint32_t, int, int, uint32_t*); \
   PFX template __global__ void k_precompute_copy<F>(uint32_t*, const uint32_t*, uint32_t, int, int);              \
   PFX template __global__ void k_digits<Fr, true>(uint32_t*, uint32_t*, MsmMeta*, const uint32_t*, uint32_t, int, int, int, int); \
   MSMZ_INST_SORT(Fr, true, 0, PFX)                                                                                \
@@ -113,6 +116,7 @@
 #define MSMZ_INST_MISC_TE(F, Fr, PFX)                                                              \
   PFX template __global__ void k_te_points_to_niels<F>(uint32_t*, const uint32_t*, uint32_t, uint32_t*); \
   PFX template __global__ void k_te_points_from_niels<F>(uint32_t*, const uint32_t*, uint32_t);    \
+  PFX template __global__ void k_te_import_points<F>(uint32_t*, const uint8_t*, uint64_t, uint32_t, int, uint32_t*); \
   MSMZ_INST_TEST(F, Fr, TePolicy<F>, true, PFX)                                                    \
   MSMZ_INST_SCALAR(Fr, PFX)
 

@@ -136,6 +136,16 @@ int msmz_upload_points(msmz_ctx* c, const uint8_t* xy, const uint8_t* inf, uint6
 int msmz_upload_scalars(msmz_ctx* c, const uint8_t* s, uint64_t n, uint64_t* h) {
   return c ? c->engine->upload_scalars(s, n, h) : MSMZ_ERR_ARG;
 }
+int msmz_import_scalars(msmz_ctx* c, const msmz_src* s, uint64_t n, uint64_t* h) {
+  return c && s ? c->engine->import_scalars(*s, n, h) : MSMZ_ERR_ARG;
+}
+int msmz_import_scalars_into(msmz_ctx* c, uint64_t h, uint64_t first, const msmz_src* s, uint64_t n) {
+  return c && s ? c->engine->import_scalars_into(h, first, *s, n) : MSMZ_ERR_ARG;
+}
+int msmz_alloc_scalars(msmz_ctx* c, uint64_t n, uint64_t* h) { return c ? c->engine->alloc_scalars(n, h) : MSMZ_ERR_ARG; }
+int msmz_import_points(msmz_ctx* c, const msmz_src* s, uint64_t n, uint64_t* h) {
+  return c && s ? c->engine->import_points(*s, n, h) : MSMZ_ERR_ARG;
+}
 int msmz_random_points(msmz_ctx* c, uint64_t n, uint64_t seed, uint64_t* h) {
   return c ? c->engine->random_points(n, seed, GenMap{}, h) : MSMZ_ERR_ARG;
 }

@@ -33,9 +33,41 @@ struct GenMap {
   int blk_shift = MULTI_BLOCK_SHIFT;
 };
 
+// The checks of an import source (msmz_src, include/msmz.h) that need no device: flags, pointer alignment, width and
+// stride.  points: fe_bytes of the curve, 0 for a scalar source.  *width / *stride: the record's bytes and the bytes
+// from one record to the next, defaults resolved.  What the pointer points at is the engine's to ask (Engine::vouch).
+static inline int src_check(const msmz_src* s, int point_fe_bytes, uint32_t* width, uint64_t* stride) {
+  if (!s || !s->ptr) return MSMZ_ERR_ARG;
+  if (s->flags & ~(uint32_t)(MSMZ_SRC_DEVICE | MSMZ_SRC_MONTGOMERY | MSMZ_SRC_DEFAULT_STREAM)) return MSMZ_ERR_ARG;
+  const bool dev = (s->flags & MSMZ_SRC_DEVICE) != 0;
+  if (!dev && (s->stream || (s->flags & MSMZ_SRC_DEFAULT_STREAM))) return MSMZ_ERR_ARG;
+  if (s->stream && (s->flags & MSMZ_SRC_DEFAULT_STREAM)) return MSMZ_ERR_ARG;
+  uint32_t w = s->width;
+  if (point_fe_bytes) {
+    if (w != 0 && w != 2u * (uint32_t)point_fe_bytes) return MSMZ_ERR_ARG;
+    w = 2u * (uint32_t)point_fe_bytes;
+  } else {
+    if (w < 4 || w > 32 || (w & 3u) || s->is_inf) return MSMZ_ERR_ARG;
+    if ((s->flags & MSMZ_SRC_MONTGOMERY) && w != 32) return MSMZ_ERR_ARG;
+  }
+  if (s->stride != 0 && (s->stride < w || (s->stride & 3u) || (s->stride >> 24))) return MSMZ_ERR_ARG;   // (n * stride cannot wrap)
+  if ((uintptr_t)s->ptr & 3u) return MSMZ_ERR_ARG;
+  *width = w;
+  *stride = s->stride ? s->stride : w;
+  return MSMZ_OK;
+}
+
 class IEngine {
  public:
   virtual ~IEngine() {}
+  // imports (msmz_import_*): `split` as for uploads, and then the source is packed host memory
+  virtual int import_scalars(const msmz_src& s, uint64_t n, uint64_t* h, const GenMap* split = nullptr) = 0;
+  virtual int import_scalars_into(uint64_t h, uint64_t first, const msmz_src& s, uint64_t n) = 0;
+  virtual int alloc_scalars(uint64_t, uint64_t*) { return MSMZ_ERR_UNSUPPORTED; }   // (_into's target: single-device contexts)
+  virtual int import_points(const msmz_src& s, uint64_t n, uint64_t* h, const GenMap* split = nullptr) = 0;
+  // packed host copy of the n records (and flag bytes, if the source has them) of a source in either memory space
+  virtual int gather_src(const msmz_src& s, int point_fe_bytes, uint64_t n, std::vector<uint8_t>* recs,
+                         std::vector<uint8_t>* flags) = 0;
   // `split` (uploads and host-scalar MSMs): the engine is one shard of a multi-device context and `n` counts its LOCAL
   // records; the host buffer is the caller's whole array, from which the engine copies its own blocks (Engine::copy_h2d)
   virtual int upload_points(const uint8_t* xy, const uint8_t* inf, uint64_t n, uint64_t* h, const GenMap* split = nullptr) = 0;
@@ -151,6 +183,22 @@ class MultiEngine : public IEngine {
       return e->upload_scalars(s, cnt, &mh.sub[g], &split);
     });
     return finish_handle(st, mh, h);
+  }
+
+  // Correctness first: the source, wherever it is, becomes a packed host copy (made by the first engine), and every
+  // device imports its own blocks of it like an upload.  A device source gains nothing here.
+  int import_scalars(const msmz_src& s, uint64_t n, uint64_t* h, const GenMap* = nullptr) override {
+    return import_any(s, 0, n, h);
+  }
+  int import_points(const msmz_src& s, uint64_t n, uint64_t* h, const GenMap* = nullptr) override {
+    return import_any(s, fb_, n, h);
+  }
+  int import_scalars_into(uint64_t, uint64_t, const msmz_src&, uint64_t) override {
+    return MSMZ_ERR_UNSUPPORTED;   // a vector start is not a block boundary of the devices' shares
+  }
+  int gather_src(const msmz_src& s, int point_fe_bytes, uint64_t n, std::vector<uint8_t>* recs,
+                 std::vector<uint8_t>* flags) override {
+    return workers_[0]->eng->gather_src(s, point_fe_bytes, n, recs, flags);
   }
 
   int random_points(uint64_t n, uint64_t seed, const GenMap&, uint64_t* h) override {
@@ -303,6 +351,25 @@ class MultiEngine : public IEngine {
   ITestHooks* test_hooks() override { return workers_[0]->eng->test_hooks(); }
 
  private:
+  int import_any(const msmz_src& s, int point_fe_bytes, uint64_t n, uint64_t* h) {
+    if (!h || n == 0) return MSMZ_ERR_ARG;
+    std::vector<uint8_t> recs, flags;
+    if (int st = gather_src(s, point_fe_bytes, n, &recs, &flags)) return st;
+    msmz_src hs{};
+    hs.ptr = recs.data();
+    hs.width = (uint32_t)(recs.size() / n);
+    hs.flags = s.flags & MSMZ_SRC_MONTGOMERY;
+    hs.is_inf = flags.empty() ? nullptr : flags.data();
+    MHandle mh{point_fe_bytes ? 0 : 1, n, std::vector<uint64_t>(G_, 0)};
+    int st = for_all([&](uint32_t g, IEngine* e) {
+      const uint64_t cnt = shard_count(n, g, G_);
+      if (cnt == 0) return (int)MSMZ_OK;
+      const GenMap split{G_, g, MULTI_BLOCK_SHIFT};
+      return point_fe_bytes ? e->import_points(hs, cnt, &mh.sub[g], &split) : e->import_scalars(hs, cnt, &mh.sub[g], &split);
+    });
+    return finish_handle(st, mh, h);
+  }
+
   struct MHandle {
     int kind;
     uint64_t n;

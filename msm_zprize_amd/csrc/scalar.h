@@ -93,6 +93,37 @@ MSMZ_HD void glv_decompose(uint32_t* s0, uint32_t* s1, uint32_t& neg0, uint32_t&
   }
 }
 
+// r = a * 2^-256 mod q: an imported scalar in 64-bit-limb Montgomery form (a = v * 2^256 mod q) -> v.  Word-serial
+// Montgomery reduction: 8 steps of  t += (t0 * q') * q;  t >>= 32  with q' = -q^-1 mod 2^32 (Fr::QINV32), then one
+// conditional subtract.  Any a < 2^256 gives r < q: t stays below 2^256 + q after every step, so 9 words hold it, and
+// ends at most q.  r may alias a.
+template <class Fr>
+MSMZ_HD void fr_from_mont(uint32_t* r, const uint32_t* a) {
+  uint32_t t[9];
+#pragma unroll
+  for (int j = 0; j < 8; j++) t[j] = a[j];
+  t[8] = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const uint32_t m = t[0] * Fr::QINV32;
+    uint64_t c = ((uint64_t)m * Fr::Q[0] + t[0]) >> 32;   // (the low word is 0 by the choice of m)
+#pragma unroll
+    for (int j = 1; j < 8; j++) {
+      const uint64_t v = (uint64_t)m * Fr::Q[j] + t[j] + c;
+      t[j - 1] = (uint32_t)v;
+      c = v >> 32;
+    }
+    const uint64_t v = (uint64_t)t[8] + c;
+    t[7] = (uint32_t)v;
+    t[8] = (uint32_t)(v >> 32);
+  }
+  uint32_t d[8];
+  const uint32_t borrow = words_sub<8>(d, t, Fr::Q);
+  const bool sub = t[8] != 0 || borrow == 0;
+#pragma unroll
+  for (int j = 0; j < 8; j++) r[j] = sub ? d[j] : t[j];
+}
+
 // c-bit window starting at bit `pos` of an NWORDS-word little-endian integer (bits past the end are 0)
 template <int NWORDS>
 MSMZ_HD uint32_t extract_bits(const uint32_t* w, int pos, int c) {

@@ -17,7 +17,7 @@ include/msmz.h -- this module contains no arithmetic.
 import ctypes as C
 
 from . import _native
-from ._native import MsmzLog, MsmzOpts, check, lib
+from ._native import MsmzLog, MsmzOpts, MsmzSrc, check, lib
 
 _state = {"devices": None}
 
@@ -118,8 +118,9 @@ class _Parallel:
         check(lib().msmz_random_scalars(self._c._ctx, n, seed, C.byref(h)), "msmz_random_scalars")
         return DeviceArray(self._c, h.value, n, "scalars")
 
-    def pointsFromBytes(self, data, n=None, is_inf=None):
-        """parallel.ts:97-112: x||y little-endian canonical, 2*fe_bytes per point."""
+    def pointsFromBytes(self, data, n=None, is_inf=None, montgomery=False):
+        """parallel.ts:97-112: x||y little-endian canonical, 2*fe_bytes per point.  montgomery=True: the coordinates are
+        64-bit-limb Montgomery residues v * 2^(8 fe_bytes) mod p (msmz_import_points), converted on the GPU."""
         fb = self._c.fe_bytes
         n = len(data) // (2 * fb) if n is None else n
         if n <= 0 or len(data) < 2 * fb * n:
@@ -127,18 +128,112 @@ class _Parallel:
         if is_inf is not None and len(is_inf) < n:
             raise ValueError(f"pointsFromBytes: {len(is_inf)} infinity flags for {n} points")
         h = C.c_uint64()
+        if montgomery:
+            data = bytes(data)
+            flags = None if is_inf is None else bytes(is_inf)
+            src = MsmzSrc(C.cast(C.c_char_p(data), C.c_void_p), 0, 2 * fb, _native.MSMZ_SRC_MONTGOMERY, None,
+                          None if flags is None else C.cast(C.c_char_p(flags), C.c_void_p))
+            check(lib().msmz_import_points(self._c._ctx, C.byref(src), n, C.byref(h)), "msmz_import_points")
+            return DeviceArray(self._c, h.value, n, "points")
         check(lib().msmz_upload_points(self._c._ctx, bytes(data), None if is_inf is None else bytes(is_inf), n,
                                        C.byref(h)), "msmz_upload_points")
         return DeviceArray(self._c, h.value, n, "points")
 
-    def scalarsFromBytes(self, data, n=None):
-        """parallel.ts:114-133: 32 bytes little-endian per scalar."""
-        n = len(data) // 32 if n is None else n
-        if n <= 0 or len(data) < 32 * n:
-            raise ValueError(f"scalarsFromBytes: {len(data)} bytes for {n} scalars of 32 bytes")
+    def scalarsFromBytes(self, data, n=None, width=32, montgomery=False):
+        """parallel.ts:114-133: 32 bytes little-endian per scalar.  width: bytes per scalar on the wire (4..32, a multiple
+        of 4; only they cross PCIe, the resident scalars are zero-extended); montgomery=True: the records are
+        v * 2^256 mod q in 64-bit limbs (width 32).  Either goes through msmz_import_scalars; the defaults are the
+        plain upload."""
+        width = scalar_width_arg(width, montgomery, "scalarsFromBytes")
+        n = len(data) // width if n is None else n
+        if n <= 0 or len(data) < width * n:
+            raise ValueError(f"scalarsFromBytes: {len(data)} bytes for {n} scalars of {width} bytes")
         h = C.c_uint64()
+        if width != 32 or montgomery:
+            data = bytes(data)
+            src = MsmzSrc(C.cast(C.c_char_p(data), C.c_void_p), 0, width,
+                          _native.MSMZ_SRC_MONTGOMERY if montgomery else 0, None, None)
+            check(lib().msmz_import_scalars(self._c._ctx, C.byref(src), n, C.byref(h)), "msmz_import_scalars")
+            return DeviceArray(self._c, h.value, n, "scalars")
         check(lib().msmz_upload_scalars(self._c._ctx, bytes(data), n, C.byref(h)), "msmz_upload_scalars")
         return DeviceArray(self._c, h.value, n, "scalars")
+
+    # -- imports: the data where it is, in the form it has (msmz_import_*, include/msmz.h) ------------
+    def _src(self, view):
+        flags = (_native.MSMZ_SRC_DEVICE if view["device"] else 0) | (_native.MSMZ_SRC_MONTGOMERY if view["montgomery"] else 0)
+        stream = None
+        if view["device"]:
+            if view["stream"]:
+                stream = view["stream"]
+            else:   # torch's default stream is the null stream, which a pointer cannot name
+                flags |= _native.MSMZ_SRC_DEFAULT_STREAM
+        return MsmzSrc(view["ptr"], view["stride"], view["width"], flags, stream, view.get("is_inf"))
+
+    def scalarsFromTensor(self, t, montgomery=False):
+        """A resident scalar array from a torch tensor, read where it lies (msmz_import_scalars).  `t`: 2-D (n, k) with a
+        contiguous last dimension -- width = k * itemsize bytes per scalar, 4..32, little-endian, zero-extended -- or 1-D of
+        an 8-byte dtype (64-bit scalars); dimension 0 may be strided (a column view of a wider matrix).  A GPU tensor must
+        be on the context's device and is read there, ordered after the work queued on torch's current stream (no copy
+        through the host); a CPU tensor goes the host route, `width` bytes per scalar.  montgomery=True: 32-byte records
+        v * 2^256 mod q.  A process that uses GPU tensors imports torch BEFORE this package loads libmsmz.so (before
+        startThreads / the first curve): torch carries its own HIP runtime, a process drives the GPU through one copy
+        only, and the copy loaded first serves both; the other way round torch finds no GPU."""
+        view = tensor_view(t, self._c.devices, "scalars", self._c.fe_bytes, montgomery, "scalarsFromTensor")
+        h = C.c_uint64()
+        check(lib().msmz_import_scalars(self._c._ctx, C.byref(self._src(view)), view["n"], C.byref(h)),
+              "msmz_import_scalars")
+        return DeviceArray(self._c, h.value, view["n"], "scalars")
+
+    def scalarsInto(self, dst, first, t, montgomery=False):
+        """Write the scalars of tensor `t` (as scalarsFromTensor) over entries [first, first + n) of the resident scalar
+        array `dst` (msmz_import_scalars_into): a batch assembled vector by vector.  Single-device contexts."""
+        if not isinstance(dst, DeviceArray) or dst.kind != "scalars":
+            raise TypeError("scalarsInto: `dst` is a resident scalar array")
+        view = tensor_view(t, self._c.devices, "scalars", self._c.fe_bytes, montgomery, "scalarsInto")
+        if isinstance(first, bool) or not isinstance(first, int) or first < 0 or first + view["n"] > len(dst):
+            raise ValueError(f"scalarsInto: entries [{first!r}, +{view['n']}) of an array of {len(dst)}")
+        check(lib().msmz_import_scalars_into(self._c._ctx, dst.handle, first, C.byref(self._src(view)), view["n"]),
+              "msmz_import_scalars_into")
+        return dst
+
+    def pointsFromTensor(self, t, montgomery=False, is_inf=None):
+        """A resident point array from a torch tensor of n rows of 2 * fe_bytes bytes (x || y, little-endian), read where
+        it lies (msmz_import_points); montgomery=True: coordinates v * 2^(8 fe_bytes) mod p.  is_inf: optional 1-D
+        contiguous 1-byte tensor of n flags on the same device."""
+        view = tensor_view(t, self._c.devices, "points", self._c.fe_bytes, montgomery, "pointsFromTensor", is_inf)
+        h = C.c_uint64()
+        check(lib().msmz_import_points(self._c._ctx, C.byref(self._src(view)), view["n"], C.byref(h)),
+              "msmz_import_points")
+        return DeviceArray(self._c, h.value, view["n"], "points")
+
+    def _assemble(self, vecs, N):
+        """one resident set of len(vecs) * N scalars from device tensors / resident scalar arrays (msmBatch)"""
+        if len(self._c.devices) != 1:
+            raise TypeError("msmBatch: a list of resident arrays is not accepted on a multi-device context; pass ONE "
+                            "resident array of B * N scalars or a list of host byte arrays")
+        B = len(vecs)
+        h = C.c_uint64()
+        check(lib().msmz_alloc_scalars(self._c._ctx, B * N, C.byref(h)), "msmz_alloc_scalars")
+        dst = DeviceArray(self._c, h.value, B * N, "scalars")
+        try:
+            for k, v in enumerate(vecs):
+                if isinstance(v, DeviceArray):
+                    if v.kind != "scalars" or len(v) < N or v.curve is not self._c:
+                        raise ValueError(f"msmBatch: vector {k} is not a resident array of >= {N} scalars of this curve")
+                    # resident -> resident: the scalars travel as 32-byte canonical records through the host
+                    buf = C.create_string_buffer(32 * N)
+                    check(lib().msmz_download_scalars(self._c._ctx, v.handle, 0, N, buf), "msmz_download_scalars")
+                    src = MsmzSrc(C.cast(buf, C.c_void_p), 0, 32, 0, None, None)
+                    check(lib().msmz_import_scalars_into(self._c._ctx, dst.handle, k * N, C.byref(src), N),
+                          "msmz_import_scalars_into")
+                else:
+                    if len(v) < N:
+                        raise ValueError(f"msmBatch: vector {k} holds {len(v)} scalars, fewer than N = {N}")
+                    self.scalarsInto(dst, k * N, v[:N])
+        except Exception:
+            dst.free()
+            raise
+        return dst
 
     def pointsFromBigints(self, points):
         """Affine.writeBigints route (scripts/zprize23/submission-bls377.ts:90-93)."""
@@ -223,6 +318,20 @@ class _Parallel:
         options = dict(options or {})
         if N <= 0 or N > len(points):
             raise ValueError(f"msmBatch: N = {N} but the point set holds {len(points)}")
+        assembled = None
+        if hasattr(scalarsList, "dim") and hasattr(scalarsList, "data_ptr"):
+            # a bare tensor could mean B rows of N 64-bit scalars or B * N records of k bytes: the caller says which
+            raise TypeError("msmBatch: pass a list of B tensors, or one resident array made with scalarsFromTensor(t), "
+                            "not a bare tensor")
+        if is_device_list(scalarsList):
+            assembled = scalarsList = self._assemble(list(scalarsList), N)
+        try:
+            return self._msm_batch_run(scalarsList, points, N, options, safe)
+        finally:
+            if assembled is not None:
+                assembled.free()
+
+    def _msm_batch_run(self, scalarsList, points, N, options, safe):
         kind, data, B = batch_scalars(scalarsList, N, options.get("batch"))
         opts = MsmzOpts()
         opts.c = int(options.get("c") or 0)
@@ -298,6 +407,77 @@ def scalar_bits_arg(options, who):
     if isinstance(bits, bool) or not isinstance(bits, int) or not 0 <= bits <= 256:
         raise ValueError(f"{who}: scalarBits = {bits!r} (0 = no bound, or 1..256)")
     return bits
+
+
+def scalar_width_arg(width, montgomery, who):
+    """bytes per imported scalar record: 4..32, a multiple of 4; Montgomery records are 32 bytes"""
+    if isinstance(width, bool) or not isinstance(width, int) or not 4 <= width <= 32 or width % 4:
+        raise ValueError(f"{who}: width = {width!r} (4..32 bytes, a multiple of 4)")
+    if montgomery and width != 32:
+        raise ValueError(f"{who}: Montgomery scalars are 32-byte records, not {width}")
+    return width
+
+
+def is_device_list(scalarsList):
+    """msmBatch: a list whose vectors are all GPU tensors or resident scalar arrays (assembled with scalarsInto)?"""
+    if isinstance(scalarsList, (DeviceArray, bytes, bytearray, memoryview, str)) or not hasattr(scalarsList, "__len__"):
+        return False
+    if hasattr(scalarsList, "dim"):   # a bare tensor is not a list of vectors (msmBatch refuses it)
+        return False
+    vecs = list(scalarsList)
+    on_gpu = [getattr(getattr(v, "device", None), "type", None) == "cuda" for v in vecs]
+    return bool(vecs) and any(on_gpu) and all(g or isinstance(v, DeviceArray) for g, v in zip(on_gpu, vecs))
+
+
+def tensor_view(t, devices, kind, fe_bytes, montgomery, who, is_inf=None):
+    """The arguments of an import from a tensor, checked before anything reaches the device.  `t` needs the tensor
+    attributes used here (dim, shape, stride, element_size, device, data_ptr), so a fake will do; torch is imported only
+    to ask a GPU tensor's current stream.  -> dict(ptr, n, width, stride (bytes), device, stream, montgomery[, is_inf])."""
+    for a in ("dim", "shape", "stride", "element_size", "device", "data_ptr"):
+        if not hasattr(t, a):
+            raise TypeError(f"{who}: expected a torch.Tensor, got {type(t).__name__}")
+    item = int(t.element_size())
+    if t.dim() == 2:
+        n, k = int(t.shape[0]), int(t.shape[1])
+        if k > 1 and t.stride(1) != 1:
+            raise ValueError(f"{who}: the last dimension must be contiguous (stride {t.stride(1)})")
+        width = k * item
+    elif t.dim() == 1 and kind == "scalars":
+        if item != 8:
+            raise ValueError(f"{who}: a 1-D tensor holds 64-bit scalars (an 8-byte dtype), not {item}-byte elements")
+        n, width = int(t.shape[0]), 8
+    else:
+        raise ValueError(f"{who}: expected a 2-D tensor (n, k)" + (" or a 1-D tensor of an 8-byte dtype" if kind == "scalars" else ""))
+    if n <= 0:
+        raise ValueError(f"{who}: an empty tensor")
+    if kind == "scalars":
+        scalar_width_arg(width, montgomery, who)
+    elif width != 2 * fe_bytes:
+        raise ValueError(f"{who}: rows of {width} bytes, a point is {2 * fe_bytes}")
+    stride = int(t.stride(0)) * item if n > 1 else width
+    if stride < width or stride % 4 or stride >= 1 << 24:
+        raise ValueError(f"{who}: rows {stride} bytes apart (a multiple of 4, at least the width {width}, below 2^24)")
+    ptr = int(t.data_ptr())
+    if ptr == 0 or ptr % 4:
+        raise ValueError(f"{who}: the data must be 4-byte aligned")
+    on_gpu = t.device.type == "cuda"
+    if t.device.type not in ("cuda", "cpu"):
+        raise ValueError(f"{who}: tensor on {t.device}")
+    if on_gpu and (t.device.index or 0) not in devices:
+        raise ValueError(f"{who}: the tensor is on {t.device}, the context drives GPU(s) {devices}")
+    view = {"ptr": ptr, "n": n, "width": width, "stride": stride, "device": on_gpu, "stream": 0,
+            "montgomery": bool(montgomery)}
+    if is_inf is not None:
+        if kind != "points":
+            raise ValueError(f"{who}: infinity flags belong to points")
+        if (is_inf.dim() != 1 or int(is_inf.shape[0]) < n or is_inf.element_size() != 1 or
+                (n > 1 and is_inf.stride(0) != 1) or is_inf.device != t.device):
+            raise ValueError(f"{who}: is_inf is a contiguous 1-D tensor of {n} one-byte flags on {t.device}")
+        view["is_inf"] = int(is_inf.data_ptr())
+    if on_gpu:
+        import torch
+        view["stream"] = int(torch.cuda.current_stream(t.device).cuda_stream)
+    return view
 
 
 def batch_scalars(scalarsList, N, batch=None):

@@ -149,6 +149,45 @@ static napi_value UploadScalars(napi_env env, napi_callback_info info) {
   return make_handle(env, h);
 }
 
+/* importScalars(ctx, buffer, n, width, montgomery) -> handle: host records of `width` bytes, optionally 64-bit-limb
+ * Montgomery residues (msmz_import_scalars; N-API has no device pointers, so the host forms only) */
+static napi_value ImportScalars(napi_env env, napi_callback_info info) {
+  size_t argc = 5; napi_value argv[5];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  msmz_ctx* ctx; if (argc < 5 || !get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "importScalars");
+  void* s; size_t slen; NAPI_CALL(env, napi_get_buffer_info(env, argv[1], &s, &slen));
+  uint64_t n, width; bool mont = false;
+  if (!get_u64(env, argv[2], &n) || !get_u64(env, argv[3], &width) || napi_get_value_bool(env, argv[4], &mont) != napi_ok ||
+      width < 4 || width > 32 || n == 0 || slen / (size_t)width < n)
+    return throw_status(env, MSMZ_ERR_ARG, "importScalars");
+  msmz_src src = {s, 0, (uint32_t)width, mont ? MSMZ_SRC_MONTGOMERY : 0u, NULL, NULL};
+  uint64_t h = 0;
+  int st = msmz_import_scalars(ctx, &src, n, &h);
+  if (st) return throw_status(env, st, "msmz_import_scalars");
+  return make_handle(env, h);
+}
+
+/* importPoints(ctx, xyBuffer, infBufferOrNull, n, montgomery) -> handle */
+static napi_value ImportPoints(napi_env env, napi_callback_info info) {
+  size_t argc = 5; napi_value argv[5];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  msmz_ctx* ctx; if (argc < 5 || !get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "importPoints");
+  void* xy; size_t xylen; NAPI_CALL(env, napi_get_buffer_info(env, argv[1], &xy, &xylen));
+  void* inf = NULL; size_t inflen = 0; bool isbuf = false, mont = false;
+  napi_is_buffer(env, argv[2], &isbuf);
+  if (isbuf) NAPI_CALL(env, napi_get_buffer_info(env, argv[2], &inf, &inflen));
+  uint64_t n;
+  int fbc = msmz_ctx_fe_bytes(ctx);
+  if (!get_u64(env, argv[3], &n) || napi_get_value_bool(env, argv[4], &mont) != napi_ok || fbc <= 0 || n == 0 ||
+      xylen / (2 * (size_t)fbc) < n || (inf != NULL && inflen < n))
+    return throw_status(env, MSMZ_ERR_ARG, "importPoints");
+  msmz_src src = {xy, 0, 0, mont ? MSMZ_SRC_MONTGOMERY : 0u, NULL, (const uint8_t*)inf};
+  uint64_t h = 0;
+  int st = msmz_import_points(ctx, &src, n, &h);
+  if (st) return throw_status(env, st, "msmz_import_points");
+  return make_handle(env, h);
+}
+
 /* randomPoints(ctx, n, seed) / randomScalars(ctx, n, seed) -> handle */
 static napi_value random_common(napi_env env, napi_callback_info info, int scalars) {
   size_t argc = 3; napi_value argv[3];
@@ -396,6 +435,7 @@ static napi_value FeBytes(napi_env env, napi_callback_info info) {
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct { const char* name; napi_callback fn; } fns[] = {
       {"create", Create}, {"destroy", Destroy}, {"uploadPoints", UploadPoints}, {"uploadScalars", UploadScalars},
+      {"importScalars", ImportScalars}, {"importPoints", ImportPoints},
       {"randomPoints", RandomPoints}, {"randomScalars", RandomScalars}, {"downloadPoints", DownloadPoints},
       {"downloadScalars", DownloadScalars}, {"free", Free}, {"msm", Msm}, {"msmBatch", MsmBatch},
       {"precomputePoints", PrecomputePoints}, {"precomputedInfo", PrecomputedInfo}, {"pointAdd", PointAdd}, {"feBytes", FeBytes}};

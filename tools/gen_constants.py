@@ -129,7 +129,10 @@ def field_struct(name, p, nwords, N, W, extra=()):
            iarr("R2", limbs_w(R * R % p, N, W)),       # to-Montgomery factor
            iarr("R3", limbs_w(R * R * R % p, N, W)),   # fixes up a plain inverse of a Montgomery value
            iarr("P2", limbs_w(2 * p, N, W)),
-           iarr("P4", limbs_w(4 * p, N, W))]
+           iarr("P4", limbs_w(4 * p, N, W)),
+           # imported 64-bit-limb Montgomery coordinates v * R_std, R_std = 2^(32 nwords): one product with
+           # R^2 / R_std takes them to v * R, as R2 takes canonical ones
+           iarr("R2STD", limbs_w(R * R * pow(1 << (32 * nwords), -1, p) % p, N, W))]
     for nm, val in extra:
         out.append(iarr(nm, limbs_w(val * R % p, N, W)))
     out.append("};")
@@ -160,6 +163,7 @@ def main():
         L.append("struct %sFr {" % tag)
         L.append("  static constexpr int BITS = %d;" % q.bit_length())
         L.append(arr("Q", limbs(q, 8)))
+        L.append("  static constexpr uint32_t QINV32 = 0x%08xu;  // -q^-1 mod 2^32 (fr_from_mont, scalar.h)" % ((-pow(q, -1, 1 << 32)) % (1 << 32)))
         if c["kind"] == "weierstrass":
             lam = c["endomorphism"]["lambda_"]
             g = glv_device_constants(q, lam)
