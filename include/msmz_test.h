@@ -164,6 +164,41 @@ typedef struct msmz_test_reduce_args {
 } msmz_test_reduce_args;
 int msmz_test_reduce(msmz_ctx* ctx, const msmz_test_reduce_args* args);
 
+/* The schedule of the tree rounds alone (k_plan_count / k_plan_emit, csrc/plan_kernels.h), through the engine's own
+ * plan_phase, on caller-built sorted buckets (Weierstrass only).  Pure integers: no point is read.
+ *   nb, off (nb + 1 words, off[0] = 0, non-decreasing): the buckets; refs (off[nb] words; nullable when that is 0):
+ *     the sorted references, index | negate << 31, bit 30 clear;
+ *   chunk, nb_main, chunk_top: the PlanChunks of the launch (plan.h) -- buckets [0, nb_main) in workgroups of `chunk`
+ *     buckets (1 .. PLAN_CHUNK = 1024), the rest in workgroups of `chunk_top` (1 .. chunk);
+ *   tail_skip (0 .. 2): rounds = ceil(log2 max bucket) - tail_skip, at least 1 when a bucket has two entries.
+ * The hook writes the largest bucket size and error = 0 into the device meta block, as the sort would have, and launches.
+ *   meta (68 words): the device meta block after the launch -- max_bucket, n_entries, error, rounds, round_pairs[32],
+ *     round_base[32];
+ *   desc (desc_cap pairs of 2 words): {locA, locB} of every addition, round after round; as many pairs as the rule gives
+ *     for these buckets (sum over the rounds), whatever the device counted.  A location word: 0x40000000 | index, with
+ *     bit 31 = negate, is an original point; any other word is the record (result) number of an earlier pair;
+ *   bfin (bfin_cap buckets of 4 words): the locations of what the rounds leave of each bucket, then 0xffffffff;
+ *   chunk_pairs (nullable; chunk_pairs_cap words): the 26 x n_chunks table of pairs per round and workgroup,
+ *     chunk_pairs[r * n_chunks + w].
+ * MSMZ_ERR_ARG, before any launch, for anything that would read or write outside an array: a null required pointer,
+ * nb = 0 or nb > 2^22, off[0] != 0, a decreasing off, off[nb] > 2^25, a bucket of 2^26 entries or more, a reference with
+ * bit 30 set, chunk outside 1 .. 1024, chunk_top outside 1 .. chunk, nb_main > nb, tail_skip outside 0 .. 2, or a
+ * capacity below what these buckets need (desc: the pairs of all rounds; bfin: nb; chunk_pairs: 26 n_chunks);
+ * MSMZ_ERR_UNSUPPORTED on twisted Edwards (no tree rounds there). */
+typedef struct msmz_test_plan_args {
+  uint32_t nb, chunk, nb_main, chunk_top;
+  int32_t tail_skip;
+  uint32_t reserved;
+  const uint32_t* off;
+  const uint32_t* refs;
+  uint64_t desc_cap, bfin_cap, chunk_pairs_cap;
+  uint32_t* meta;
+  uint32_t* desc;
+  uint32_t* bfin;
+  uint32_t* chunk_pairs;
+} msmz_test_plan_args;
+int msmz_test_plan(msmz_ctx* ctx, const msmz_test_plan_args* args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,6 +42,14 @@ class MsmzTestReduceArgs(C.Structure):   # msmz_test_reduce_args (include/msmz_t
                 ("out_xy", C.c_void_p), ("lines_xy", C.c_void_p)]
 
 
+class MsmzTestPlanArgs(C.Structure):   # msmz_test_plan_args (include/msmz_test.h)
+    _fields_ = [("nb", C.c_uint32), ("chunk", C.c_uint32), ("nb_main", C.c_uint32), ("chunk_top", C.c_uint32),
+                ("tail_skip", C.c_int32), ("reserved", C.c_uint32),
+                ("off", C.c_void_p), ("refs", C.c_void_p),
+                ("desc_cap", C.c_uint64), ("bfin_cap", C.c_uint64), ("chunk_pairs_cap", C.c_uint64),
+                ("meta", C.c_void_p), ("desc", C.c_void_p), ("bfin", C.c_void_p), ("chunk_pairs", C.c_void_p)]
+
+
 EXPORTS = {
     # name: (restype, argtypes)
     "msmz_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int), C.c_int]),
@@ -93,6 +101,7 @@ EXPORTS = {
                                       C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p,
                                       C.POINTER(C.c_uint32)]),
     "msmz_test_reduce": (C.c_int, [C.c_void_p, C.POINTER(MsmzTestReduceArgs)]),
+    "msmz_test_plan": (C.c_int, [C.c_void_p, C.POINTER(MsmzTestPlanArgs)]),
 }
 
 _lib = None

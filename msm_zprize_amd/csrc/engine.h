@@ -1216,6 +1216,32 @@ class Engine : public IEngine {
     }
   }
 
+  // The schedule of the tree rounds (plan_kernels.h) for the sorted buckets in off_ / refs_ (nb of them, all problems'),
+  // cut into workgroups as pc says: desc_ <- one descriptor per addition of every round (room for desc_records), bfin_ <-
+  // what the rounds leave of each bucket, meta <- rounds, entries, round sizes and bases.  Reads meta->max_bucket, which
+  // the sort left.  No host round trip.
+  int plan_phase(const PlanChunks& pc, uint32_t nb, int tail_skip, size_t desc_records, Run& run) {
+    int st;
+    MsmMeta* d_meta = meta_.as<MsmMeta>();
+    mark(run, run.ev.plan0);
+    const uint32_t n_chunks = pc.n_main + (nb - pc.nb_main + pc.chunk_top - 1) / pc.chunk_top;
+    // chunk totals per round, then the per-workgroup scratch of the rounds beyond PLAN_RL
+    const size_t pair_words = (size_t)n_chunks * (PLAN_RMAX - PLAN_RL) * PLAN_T;
+    if ((st = rscan_.ensure(((size_t)PLAN_RMAX * n_chunks + pair_words) * 4 + kTraceBytes * n_chunks))) return st;
+    if ((st = desc_.ensure(desc_records * 8))) return st;
+    if ((st = bfin_.ensure((size_t)nb * 16))) return st;
+    hipLaunchKernelGGL(k_plan_count, dim3(n_chunks), dim3(PLAN_T), 0, stream_, rscan_.as<uint32_t>(), off_.as<uint32_t>(),
+                       nb, n_chunks, d_meta, tail_skip, pc);
+    hipLaunchKernelGGL(k_plan_emit, dim3(n_chunks), dim3(PLAN_T), 0, stream_, desc_.as<uint2>(), bfin_.as<uint4>(),
+                       d_meta, rscan_.as<uint32_t>(), off_.as<uint32_t>(), refs_.as<uint32_t>(), nb, n_chunks,
+                       tail_skip, rscan_.as<uint32_t>() + (size_t)PLAN_RMAX * n_chunks, pc);
+    MSMZ_HIP(hipGetLastError());
+#ifdef MSMZ_TRACE
+    if ((st = trace_dump("k_plan_emit", rscan_.as<uint32_t>() + (size_t)PLAN_RMAX * n_chunks + pair_words, n_chunks, false))) return st;
+#endif
+    return MSMZ_OK;
+  }
+
   // ------------------------------------------------------------------------------------------ Weierstrass, affine buckets
   // nprob > 1: a batched MSM of nprob problems over the same points (scalars of problem p at d_scalars + p n 8, results
   // at out + p 2 FE_BYTES / out_inf[p]): one sort, one plan, one train of tree rounds and one two-dimensional reduction
@@ -1250,25 +1276,9 @@ class Engine : public IEngine {
     MsmMeta* d_meta = meta_.as<MsmMeta>();
 
     // ---- plan: descriptors of every pair of every round + what is left of each bucket (plan_kernels.h)
-    mark(run, run.ev.plan0);
-    const PlanChunks pc = planner_.plan_chunks(pl);
-    const uint32_t n_chunks = pc.n_main + (nb - pc.nb_main + pc.chunk_top - 1) / pc.chunk_top;
-    // chunk totals per round, then the per-workgroup scratch of the rounds beyond PLAN_RL
-    const size_t pair_words = (size_t)n_chunks * (PLAN_RMAX - PLAN_RL) * PLAN_T;
-    if ((st = rscan_.ensure(((size_t)PLAN_RMAX * n_chunks + pair_words) * 4 + kTraceBytes * n_chunks))) return st;
-    if ((st = desc_.ensure((size_t)nprob * pl.K * pl.M * 8))) return st;
-    if ((st = bfin_.ensure((size_t)nb * 16))) return st;
     // the batched-affine first reduction level (opt.reserved[0] = 1) wants ONE sum per bucket: no rounds skipped
     const int tail_skip = want_2d ? tail_skip_2d_ : 0;
-    hipLaunchKernelGGL(k_plan_count, dim3(n_chunks), dim3(PLAN_T), 0, stream_, rscan_.as<uint32_t>(), off_.as<uint32_t>(),
-                       nb, n_chunks, d_meta, tail_skip, pc);
-    hipLaunchKernelGGL(k_plan_emit, dim3(n_chunks), dim3(PLAN_T), 0, stream_, desc_.as<uint2>(), bfin_.as<uint4>(),
-                       d_meta, rscan_.as<uint32_t>(), off_.as<uint32_t>(), refs_.as<uint32_t>(), nb, n_chunks,
-                       tail_skip, rscan_.as<uint32_t>() + (size_t)PLAN_RMAX * n_chunks, pc);
-    MSMZ_HIP(hipGetLastError());
-#ifdef MSMZ_TRACE
-    if ((st = trace_dump("k_plan_emit", rscan_.as<uint32_t>() + (size_t)PLAN_RMAX * n_chunks + pair_words, n_chunks, false))) return st;
-#endif
+    if ((st = plan_phase(planner_.plan_chunks(pl), nb, tail_skip, (size_t)nprob * pl.K * pl.M, run))) return st;
     if ((st = fetch_meta(run))) return st;      // the ONE host round trip before the final fetch
     if (h_meta_->error & 4u) return MSMZ_ERR_RANGE;
     if (h_meta_->error & 2u) {

@@ -25,6 +25,8 @@
 //                        msm-batched-affine-single-thread.ts:522-667)
 //   k_bucket_accumulate  msmBasic path: buckets in XYZZ / extended coordinates (msm-basic.ts:106-128)
 //   k_test_*             (test_kernels.h) stage-level test hooks of include/msmz_test.h, launched from test_hooks.h
+//                        (msmz_test_plan and msmz_test_reduce launch no kernel of their own: they run the engine's
+//                        plan_phase / reduction on caller-built buckets)
 //
 // Bucket numbering: global bucket g = k*L + (l-1) for window k and digit l in [1, L], L = 2^(c-1).
 // Sorted references: ref = point_index | (negate << 31).

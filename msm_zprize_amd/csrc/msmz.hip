@@ -239,6 +239,10 @@ int msmz_test_reduce(msmz_ctx* c, const msmz_test_reduce_args* a) {
   return c && a ? c->engine->test_hooks()->test_reduce(*a) : MSMZ_ERR_ARG;
 }
 
+int msmz_test_plan(msmz_ctx* c, const msmz_test_plan_args* a) {
+  return c && a ? c->engine->test_hooks()->test_plan(*a) : MSMZ_ERR_ARG;
+}
+
 int msmz_point_add(int curve_id, const uint8_t* a, int ai, const uint8_t* b, int bi, uint8_t* out, int* oi) {
   if (!out || !oi || (!a && !ai) || (!b && !bi)) return MSMZ_ERR_ARG;
   switch (curve_id) {

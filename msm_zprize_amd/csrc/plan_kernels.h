@@ -32,7 +32,7 @@ constexpr int PLAN_TILE = 4096;                   // pairs whose owner buckets a
 constexpr uint32_t LOC_ORIG = 0x40000000u;        // location word: bit 30 = original point (bit 31 = negate), else slot record
 constexpr uint32_t LOC_NONE = 0xffffffffu;
 
-__device__ __forceinline__ int plan_rounds(uint32_t max_bucket, int tail_skip) {
+__host__ __device__ __forceinline__ int plan_rounds(uint32_t max_bucket, int tail_skip) {
   if (max_bucket <= 1) return 0;
   const int rfull = 32 - __builtin_clz(max_bucket - 1);   // rounds m = 1, 2, 4, ... < max_bucket
   if (rfull <= 1) return rfull;
@@ -40,7 +40,7 @@ __device__ __forceinline__ int plan_rounds(uint32_t max_bucket, int tail_skip) {
   return r < 1 ? 1 : (r > PLAN_RMAX ? PLAN_RMAX : r);
 }
 
-__device__ __forceinline__ uint32_t pairs_in_round(uint32_t size, int r) {   // number of j with j*2m + m < size
+__host__ __device__ __forceinline__ uint32_t pairs_in_round(uint32_t size, int r) {   // number of j with j*2m + m < size
   return (size + (1u << r) - 1u) >> (r + 1);
 }
 

@@ -8,7 +8,7 @@
 
 namespace msmz {
 
-// The nine msmz_test_* stage entry points of an engine whatever its curve; arguments as in msmz_test.h and TestHooks.
+// The ten msmz_test_* stage entry points of an engine whatever its curve; arguments as in msmz_test.h and TestHooks.
 class ITestHooks {
  public:
   virtual ~ITestHooks() {}
@@ -22,6 +22,7 @@ class ITestHooks {
   virtual int test_batch_add(int, int, const uint8_t*, const uint8_t*, uint64_t, const uint8_t*, const uint8_t*, uint64_t,
                              const uint32_t*, uint64_t, uint64_t, uint8_t*, uint32_t*) = 0;
   virtual int test_reduce(const msmz_test_reduce_args&) = 0;
+  virtual int test_plan(const msmz_test_plan_args&) = 0;
 };
 
 // The regions of an engine's staging buffer that one hook call copies its host arrays into and its results out of, each
@@ -71,7 +72,7 @@ struct Staging {
 };
 
 // The hooks of one engine.  A friend of Engine<Cfg>: the hooks launch on its stream, into its buffers, and run its own
-// phases (sort_phase, launch_batch_add_b, bucket_sums, the two halves of reduce_2d, reduce_levels).  Its planner and its
+// phases (sort_phase, plan_phase, launch_batch_add_b, bucket_sums, the two halves of reduce_2d, reduce_levels).  Its planner and its
 // reduction thresholds they only read, and vary in copies.
 template <class Cfg>
 class TestHooks : public ITestHooks {
@@ -354,6 +355,75 @@ class TestHooks : public ITestHooks {
     hipLaunchKernelGGL((k_test_accs_out<P, TE>), dim3((n_res + 63) / 64), dim3(64), 0, eng_.stream_, sg.at<uint32_t>(ires),
                        eng_.final_.template as<uint32_t>(), n_res);
     return sg.download();
+  }
+
+  // The tree-round schedule on caller-built buckets (msmz_test.h): off / refs go where the sort would have left them,
+  // with the largest bucket in the meta block, then the engine's own plan_phase runs.  Everything the two kernels index
+  // with is checked here first: they trust off, the chunk geometry and the capacities.
+  int test_plan(const msmz_test_plan_args& a) override {
+    if (TE) return MSMZ_ERR_UNSUPPORTED;
+    constexpr uint32_t NB_CAP = 1u << 22, ENTRY_CAP = 1u << 25;
+    if (!a.off || !a.meta || !a.desc || !a.bfin || a.nb == 0 || a.nb > NB_CAP) return MSMZ_ERR_ARG;
+    if (a.tail_skip < 0 || a.tail_skip > 2 || a.chunk < 1 || a.chunk > (uint32_t)PLAN_CHUNK || a.chunk_top < 1 ||
+        a.chunk_top > a.chunk || a.nb_main > a.nb)
+      return MSMZ_ERR_ARG;
+    const uint32_t nb = a.nb;
+    if (a.off[0] != 0) return MSMZ_ERR_ARG;
+    uint32_t max_bucket = 0;
+    for (uint32_t g = 0; g < nb; g++) {
+      if (a.off[g + 1] < a.off[g] || a.off[g + 1] > ENTRY_CAP) return MSMZ_ERR_ARG;
+      const uint32_t sz = a.off[g + 1] - a.off[g];
+      if (sz >= (1u << PLAN_RMAX)) return MSMZ_ERR_ARG;
+      if (sz > max_bucket) max_bucket = sz;
+    }
+    const uint32_t n_entries = a.off[nb];
+    if (n_entries && !a.refs) return MSMZ_ERR_ARG;
+    for (uint32_t e = 0; e < n_entries; e++)
+      if (a.refs[e] & LOC_ORIG) return MSMZ_ERR_ARG;   // bit 30 is the location words' "original point" flag
+    // what the launches will write, from the same rule on the host
+    const int R = plan_rounds(max_bucket, a.tail_skip);
+    uint64_t total = 0;
+    for (uint32_t g = 0; g < nb; g++) {
+      const uint32_t sz = a.off[g + 1] - a.off[g];
+      for (int r = 0; r < R && pairs_in_round(sz, r); r++) total += pairs_in_round(sz, r);
+    }
+    PlanChunks pc;
+    pc.chunk = a.chunk;
+    pc.nb_main = a.nb_main;
+    pc.chunk_top = a.chunk_top;
+    pc.n_main = (pc.nb_main + pc.chunk - 1) / pc.chunk;
+    const uint32_t n_chunks = pc.n_main + (nb - pc.nb_main + pc.chunk_top - 1) / pc.chunk_top;
+    if (a.desc_cap < total || a.bfin_cap < nb) return MSMZ_ERR_ARG;
+    if (a.chunk_pairs && a.chunk_pairs_cap < (uint64_t)PLAN_RMAX * n_chunks) return MSMZ_ERR_ARG;
+
+    MSMZ_HIP(hipSetDevice(eng_.device_));
+    int st;
+    if ((st = eng_.off_.ensure(((size_t)nb + 1) * 4)) || (st = eng_.refs_.ensure(((size_t)n_entries + 1) * 4))) return st;
+    MSMZ_HIP(hipMemcpyAsync(eng_.off_.p, a.off, ((size_t)nb + 1) * 4, hipMemcpyHostToDevice, eng_.stream_));
+    if (n_entries)
+      MSMZ_HIP(hipMemcpyAsync(eng_.refs_.p, a.refs, (size_t)n_entries * 4, hipMemcpyHostToDevice, eng_.stream_));
+    MsmMeta hm;
+    memset(&hm, 0, sizeof(hm));
+    hm.max_bucket = max_bucket;   // (error = 0: as after a clean sort)
+    MSMZ_HIP(hipMemcpyAsync(eng_.meta_.p, &hm, sizeof(hm), hipMemcpyHostToDevice, eng_.stream_));
+    // Descriptor records: an MSM sizes them by its entries (pairs < entries); twice that here, so that a broken build
+    // that numbers a round's pairs one chunk too far still writes inside the buffer.  Both outputs are filled with a
+    // pattern that is no location, so a word the launch leaves unwritten cannot pass for one.
+    const size_t desc_records = (size_t)2 * n_entries + 64;
+    if ((st = eng_.desc_.ensure(desc_records * 8)) || (st = eng_.bfin_.ensure((size_t)nb * 16))) return st;
+    MSMZ_HIP(hipMemsetAsync(eng_.desc_.p, 0xa5, desc_records * 8, eng_.stream_));
+    MSMZ_HIP(hipMemsetAsync(eng_.bfin_.p, 0xa5, (size_t)nb * 16, eng_.stream_));
+    msmz_opts opt;
+    memset(&opt, 0, sizeof(opt));
+    Run run = eng_.new_run(opt);
+    if ((st = eng_.plan_phase(pc, nb, a.tail_skip, desc_records, run))) return st;
+    MSMZ_HIP(hipMemcpyAsync(a.meta, eng_.meta_.p, sizeof(MsmMeta), hipMemcpyDeviceToHost, eng_.stream_));
+    if (total) MSMZ_HIP(hipMemcpyAsync(a.desc, eng_.desc_.p, (size_t)total * 8, hipMemcpyDeviceToHost, eng_.stream_));
+    MSMZ_HIP(hipMemcpyAsync(a.bfin, eng_.bfin_.p, (size_t)nb * 16, hipMemcpyDeviceToHost, eng_.stream_));
+    if (a.chunk_pairs)
+      MSMZ_HIP(hipMemcpyAsync(a.chunk_pairs, eng_.rscan_.p, (size_t)PLAN_RMAX * n_chunks * 4, hipMemcpyDeviceToHost, eng_.stream_));
+    MSMZ_HIP(hipStreamSynchronize(eng_.stream_));
+    return MSMZ_OK;
   }
 
  private:
