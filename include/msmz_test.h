@@ -3,7 +3,8 @@
  * The reference tests every wasm routine against its bigint twin (src/field.test.ts:159-211,
  * src/curve-projective.test.ts:77-209, src/glv/glv-test.ts:83-125, src/testing/equivalent-wasm.ts:97-147).  These
  * entry points give the parity tests the same granularity on the device: each one runs ONE device routine of the
- * MSM pipeline on caller-supplied inputs and returns its raw output.  They are not part of the drop-in boundary and
+ * MSM pipeline, or one phase of the engine (the bucket sort, the tree-round schedule, the bucket reduction), on
+ * caller-supplied inputs and returns its raw output.  They are not part of the drop-in boundary and
  * never take part in an MSM.  Statuses and conventions as in msmz.h; on a multi-device context they use its first
  * engine.
  *
@@ -77,6 +78,62 @@ int msmz_test_digits(msmz_ctx* ctx, const uint8_t* scalars_le32, uint64_t n, int
  * force_fallback = 1 runs the one-pass atomic sort.  Capacities in words. */
 int msmz_test_sort(msmz_ctx* ctx, const uint8_t* scalars_le32, uint64_t n, int c, int glv, int force_fallback,
                    uint32_t* geom, uint32_t* off, uint64_t off_cap, uint32_t* refs, uint64_t refs_cap);
+
+/* The bucket sort alone at every geometry an MSM runs it in: the engine's own Planner::make_plan, sort_layout and
+ * sort_phase (k_hist, k_bin_scan or the three-launch scan, k_coarse, k_fine; or the fallback k_digits, k_scan_*,
+ * k_scatter), the template instances an MSM launches.  Pure integers: no point is read.  msmz_test_sort above is this
+ * hook with nprob = 1, factor = 1, pts_n = n and no bound or fold.
+ *   scalars_le32: nprob * n scalars, problem after problem;  n: 1 .. 2^22;  nprob: 1 .. 64 (a batched MSM);
+ *   c (0 = the planner's choice), glv, force_fallback: as msmz_test_sort;
+ *   scalar_bits: the caller's bound, msmz_opts.reserved[1] (0 .. 256; 0 = none);  allow_fold: the thin top window may be
+ *     folded, as an MSM on the batched-affine path allows;
+ *   pts_n >= n (0 = n): size of the point set the MSM would cover a prefix of; with GLV the second halves' references are
+ *     moved up by endo_delta = pts_n - n;
+ *   factor (0 or 1 = plain; .. 128): windows per bucket set of a precomputed point set (F of make_plan; the layout uses
+ *     min(factor, K));  copy_stride: records per copy -- window k references index + (k mod F) * copy_stride.
+ * Outputs, each nullable, capacities in words:
+ *   geom (>= MSMZ_TS_GEOM_WORDS): the geometry, indexed by the MSMZ_TS_* names below: Plan / SortGeom / SortLayout of
+ *     csrc/plan.h, F = the windows per bucket set in effect, min(factor, K); tiles = workgroups of k_hist / k_coarse per
+ *     problem.  With every other output null the hook plans only and launches nothing;
+ *   meta (3 words, no capacity): the RAW meta words after the sort -- error (bit 1 = value 2: a (half-)scalar does not
+ *     fit K windows, or its top digit left a folded window -- that digit is in no bucket; bit 2 = value 4: a scalar >=
+ *     the group order or >= 2^scalar_bits -- none of its digits is in a bucket), n_entries, max_bucket.  The error word is data: the hook returns
+ *     MSMZ_OK with it set.  max_bucket: the largest bucket size when some bucket has two entries; when none has, the
+ *     two-level sort leaves 0 and the fallback sort 1 (0 without any entry) -- every consumer treats 0 and 1 alike
+ *     (plan_rounds: no round; the msmBasic chunk size; msmz_log.max_bucket reports it as it is);
+ *   off (>= nprob * nb + 1): bucket offsets of all problems, problem p's buckets from p * nb on;
+ *   refs, packed (>= nprob * K * M each, the most entries there can be): the n_entries sorted references
+ *     (index | negate << 31), and the n_entries words k_coarse wrote, bin after bin in scan order:
+ *     ((fine << 1 | negate) << idx_bits) | (k mod F) << mbits | entry, entry = half * n + scalar index;
+ *   bins (>= nprob * sbins + 1): the scanned bin bases; bin p * sbins + s, s = ((k / F) * ncb + coarse) * F + k mod F
+ *     for window k < K - 1 or F > 1, and (K - 1) * ncb + sub * ncbt + coarse for the plain top window's sub-window sub.
+ *   packed and bins exist in the two-level sort only; with two_level = 0 they are left untouched.
+ * MSMZ_ERR_ARG, before any launch: a null scalars / args, n, nprob, c, scalar_bits or factor out of range, pts_n < n or
+ * > 2^30, an index + (F - 1) * copy_stride that leaves 31 bits, a plan make_plan refuses or with more than 2^26 entries,
+ * a capacity below the above.  MSMZ_ERR_UNSUPPORTED: GLV on a curve without endomorphism; nprob > 1 or factor > 1 where
+ * the layout is not two-level (sort_phase refuses them). */
+enum {
+  MSMZ_TS_C = 0, MSMZ_TS_K = 1, MSMZ_TS_KEFF = 2, MSMZ_TS_L = 3, MSMZ_TS_NB = 4, MSMZ_TS_FB = 5, MSMZ_TS_FBT = 6,
+  MSMZ_TS_NCB = 7, MSMZ_TS_NCBT = 8, MSMZ_TS_NBINS = 9, MSMZ_TS_SBINS = 10, MSMZ_TS_FBINS = 11, MSMZ_TS_FINE_TOP = 12,
+  MSMZ_TS_SPREAD = 13, MSMZ_TS_FOLD_SHIFT = 14, MSMZ_TS_FOLD_ROWS = 15, MSMZ_TS_F = 16, MSMZ_TS_MBITS = 17,
+  MSMZ_TS_IDX_BITS = 18, MSMZ_TS_CSPEC = 19, MSMZ_TS_TWO_LEVEL = 20, MSMZ_TS_TILES = 21,
+  MSMZ_TS_SBITS = 22 /* the bound as the kernels get it, 256 = none */, MSMZ_TS_ENDO_DELTA = 23,
+  MSMZ_TS_GEOM_WORDS = 24
+};
+typedef struct msmz_test_sort_args {
+  const uint8_t* scalars_le32;
+  uint64_t n, pts_n;
+  uint32_t nprob, factor, copy_stride;
+  int32_t c, glv, force_fallback, scalar_bits, allow_fold;
+  uint64_t geom_cap, off_cap, refs_cap, bins_cap, packed_cap;
+  uint32_t* geom;
+  uint32_t* meta;
+  uint32_t* off;
+  uint32_t* refs;
+  uint32_t* bins;
+  uint32_t* packed;
+} msmz_test_sort_args;
+int msmz_test_sort_ex(msmz_ctx* ctx, const msmz_test_sort_args* args);
 /* point arithmetic on canonical affine inputs (x || y, 2*fe_bytes; infinity flags nullable, Weierstrass only):
  * out[i] = op(a[i], b[i]) as canonical affine, all-zero = infinity */
 int msmz_test_point(msmz_ctx* ctx, int op, const uint8_t* a_xy, const uint8_t* a_inf, const uint8_t* b_xy,

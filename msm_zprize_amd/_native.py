@@ -50,6 +50,22 @@ class MsmzTestPlanArgs(C.Structure):   # msmz_test_plan_args (include/msmz_test.
                 ("meta", C.c_void_p), ("desc", C.c_void_p), ("bfin", C.c_void_p), ("chunk_pairs", C.c_void_p)]
 
 
+class MsmzTestSortArgs(C.Structure):   # msmz_test_sort_args (include/msmz_test.h)
+    _fields_ = [("scalars_le32", C.c_void_p), ("n", C.c_uint64), ("pts_n", C.c_uint64),
+                ("nprob", C.c_uint32), ("factor", C.c_uint32), ("copy_stride", C.c_uint32),
+                ("c", C.c_int32), ("glv", C.c_int32), ("force_fallback", C.c_int32), ("scalar_bits", C.c_int32),
+                ("allow_fold", C.c_int32),
+                ("geom_cap", C.c_uint64), ("off_cap", C.c_uint64), ("refs_cap", C.c_uint64), ("bins_cap", C.c_uint64),
+                ("packed_cap", C.c_uint64),
+                ("geom", C.c_void_p), ("meta", C.c_void_p), ("off", C.c_void_p), ("refs", C.c_void_p),
+                ("bins", C.c_void_p), ("packed", C.c_void_p)]
+
+
+# the geometry words of msmz_test_sort_ex, in order (MSMZ_TS_* of include/msmz_test.h)
+TEST_SORT_GEOM = ["c", "K", "Keff", "L", "nb", "fb", "fbt", "ncb", "ncbt", "nbins", "sbins", "fbins", "fine_top", "spread",
+                  "fold_shift", "fold_rows", "F", "mbits", "idx_bits", "cspec", "two_level", "tiles", "sbits", "endo_delta"]
+
+
 EXPORTS = {
     # name: (restype, argtypes)
     "msmz_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int), C.c_int]),
@@ -93,6 +109,7 @@ EXPORTS = {
     "msmz_test_digits": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "msmz_test_sort": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                  C.c_uint64, C.c_void_p, C.c_uint64]),
+    "msmz_test_sort_ex": (C.c_int, [C.c_void_p, C.POINTER(MsmzTestSortArgs)]),
     "msmz_test_point_raw": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint64, C.c_int,
                                       C.c_char_p]),
     "msmz_test_point": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint64,

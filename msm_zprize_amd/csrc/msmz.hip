@@ -219,6 +219,9 @@ int msmz_test_sort(msmz_ctx* c, const uint8_t* s, uint64_t n, int cc, int glv, i
   if (!c) return MSMZ_ERR_ARG;
   return c->engine->test_hooks()->test_sort(s, n, cc, glv, force_fallback, geom, off, off_cap, refs, refs_cap);
 }
+int msmz_test_sort_ex(msmz_ctx* c, const msmz_test_sort_args* a) {
+  return c && a ? c->engine->test_hooks()->test_sort_ex(*a) : MSMZ_ERR_ARG;
+}
 int msmz_test_point_raw(msmz_ctx* c, int op, const uint8_t* a, const uint8_t* b, const uint8_t* neg, uint64_t n, int L,
                         uint8_t* out) {
   return c ? c->engine->test_hooks()->test_point_raw(op, a, b, neg, n, L, out) : MSMZ_ERR_ARG;

@@ -8,7 +8,7 @@
 
 namespace msmz {
 
-// The ten msmz_test_* stage entry points of an engine whatever its curve; arguments as in msmz_test.h and TestHooks.
+// The eleven msmz_test_* stage entry points of an engine whatever its curve; arguments as in msmz_test.h and TestHooks.
 class ITestHooks {
  public:
   virtual ~ITestHooks() {}
@@ -17,6 +17,7 @@ class ITestHooks {
   virtual int test_glv(const uint8_t*, uint64_t, uint8_t*, uint8_t*, uint8_t*) = 0;
   virtual int test_digits(const uint8_t*, uint64_t, int, int, int, uint32_t*) = 0;
   virtual int test_sort(const uint8_t*, uint64_t, int, int, int, uint32_t*, uint32_t*, uint64_t, uint32_t*, uint64_t) = 0;
+  virtual int test_sort_ex(const msmz_test_sort_args&) = 0;
   virtual int test_point(int, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*, uint64_t, uint8_t*) = 0;
   virtual int test_point_raw(int, const uint8_t*, const uint8_t*, const uint8_t*, uint64_t, int, uint8_t*) = 0;
   virtual int test_batch_add(int, int, const uint8_t*, const uint8_t*, uint64_t, const uint8_t*, const uint8_t*, uint64_t,
@@ -139,35 +140,101 @@ class TestHooks : public ITestHooks {
     return sg.download();
   }
 
+  // msmz_test_sort: test_sort_ex with one problem, one window per bucket set, no bound, no fold, pts_n = n; a flagged
+  // scalar is MSMZ_ERR_RANGE here, and refs need room for the entries there are only
   int test_sort(const uint8_t* s, uint64_t n, int c, int glv, int force_fallback, uint32_t* geom, uint32_t* off,
                 uint64_t off_cap, uint32_t* refs, uint64_t refs_cap) override {
-    if (!s || !geom || n == 0 || n > (1u << 22)) return MSMZ_ERR_ARG;
-    if (glv && !Fr::HAS_GLV) return MSMZ_ERR_UNSUPPORTED;
-    msmz_opts opt;
-    memset(&opt, 0, sizeof(opt));
-    opt.c = c;
-    Planner<Fr> pr = eng_.planner_;
-    pr.k.force_atomic_sort = pr.k.force_atomic_sort || force_fallback != 0;
-    Plan pl;
-    int st = pr.make_plan(pl, n, glv != 0, opt, (uint32_t)n, !TE);
-    if (st) return st;
-    Staging sg = staging();
-    const int is = sg.in(s, 32 * n);
-    if ((st = sg.upload())) return st;
-    Run run = eng_.new_run(opt);
-    if ((st = eng_.sort_phase(pl, pr.sort_layout(pl), sg.at<const uint32_t>(is), run, 0)) || (st = eng_.fetch_meta(run)))
-      return st;
-    if (eng_.h_meta_->error & 4u) return MSMZ_ERR_RANGE;
-    const uint32_t g8[8] = {(uint32_t)pl.c, (uint32_t)pl.K, (uint32_t)pl.Keff, pl.L, pl.nb, run.n_entries, run.max_bucket,
-                            (uint32_t)pl.spread};
+    if (!geom) return MSMZ_ERR_ARG;
+    uint32_t gw[MSMZ_TS_GEOM_WORDS], meta[3];
+    msmz_test_sort_args a;
+    memset(&a, 0, sizeof(a));
+    a.scalars_le32 = s;
+    a.n = a.pts_n = n;
+    a.nprob = a.factor = 1;
+    a.c = c;
+    a.glv = glv;
+    a.force_fallback = force_fallback;
+    a.geom = gw;
+    a.geom_cap = MSMZ_TS_GEOM_WORDS;
+    a.meta = meta;
+    if (int st = test_sort_ex(a)) return st;
+    if (meta[0] & 4u) return MSMZ_ERR_RANGE;
+    const uint32_t nb = gw[MSMZ_TS_NB], n_entries = meta[1];
+    const uint32_t g8[8] = {gw[MSMZ_TS_C], gw[MSMZ_TS_K], gw[MSMZ_TS_KEFF], gw[MSMZ_TS_L], nb, n_entries, meta[2],
+                            gw[MSMZ_TS_SPREAD]};
     memcpy(geom, g8, sizeof(g8));
     if (off) {
-      if (off_cap < (uint64_t)pl.nb + 1) return MSMZ_ERR_ARG;
-      MSMZ_HIP(hipMemcpy(off, eng_.off_.p, ((size_t)pl.nb + 1) * 4, hipMemcpyDeviceToHost));
+      if (off_cap < (uint64_t)nb + 1) return MSMZ_ERR_ARG;
+      MSMZ_HIP(hipMemcpy(off, eng_.off_.p, ((size_t)nb + 1) * 4, hipMemcpyDeviceToHost));
     }
     if (refs) {
-      if (refs_cap < run.n_entries) return MSMZ_ERR_ARG;
-      if (run.n_entries) MSMZ_HIP(hipMemcpy(refs, eng_.refs_.p, (size_t)run.n_entries * 4, hipMemcpyDeviceToHost));
+      if (refs_cap < n_entries) return MSMZ_ERR_ARG;
+      if (n_entries) MSMZ_HIP(hipMemcpy(refs, eng_.refs_.p, (size_t)n_entries * 4, hipMemcpyDeviceToHost));
+    }
+    return MSMZ_OK;
+  }
+
+  // The bucket sort at any geometry an MSM plans (msmz_test.h): the planner's plan and layout for the caller's options,
+  // then the engine's own sort_phase.  Everything the kernels index with comes from that plan; what the caller controls
+  // beyond it (capacities, pts_n, copy_stride) is checked here before anything is launched.
+  int test_sort_ex(const msmz_test_sort_args& a) override {
+    const uint64_t n = a.n, pts_n = a.pts_n ? a.pts_n : a.n;
+    if (!a.scalars_le32 || n == 0 || n > (1u << 22) || a.nprob < 1 || a.nprob > 64) return MSMZ_ERR_ARG;
+    if (a.c < 0 || a.c > 24 || a.scalar_bits < 0 || a.scalar_bits > 256 || a.factor > (uint32_t)kMaxWindows) return MSMZ_ERR_ARG;
+    if (pts_n < n || pts_n > (1u << 30)) return MSMZ_ERR_ARG;
+    if (a.glv && !Fr::HAS_GLV) return MSMZ_ERR_UNSUPPORTED;
+    if (a.geom && a.geom_cap < MSMZ_TS_GEOM_WORDS) return MSMZ_ERR_ARG;
+    msmz_opts opt;
+    memset(&opt, 0, sizeof(opt));
+    opt.c = a.c;
+    opt.reserved[1] = a.scalar_bits;
+    Planner<Fr> pr = eng_.planner_;
+    pr.k.force_atomic_sort = pr.k.force_atomic_sort || a.force_fallback != 0;
+    Plan pl;
+    int st = pr.make_plan(pl, n, a.glv != 0, opt, (uint32_t)pts_n, !TE, 0, a.allow_fold != 0, a.nprob,
+                          a.factor > 1 ? a.factor : 1);
+    if (st) return st;
+    const SortLayout sl = pr.sort_layout(pl);
+    const SortGeom& g = sl.geom;
+    const uint64_t cap_entries = (uint64_t)pl.nprob * pl.K * pl.M;
+    if (pl.K > kMaxWindows || cap_entries > kMaxBatchEntries) return MSMZ_ERR_ARG;
+    if (!sl.two_level && (pl.nprob > 1 || pl.F > 1)) return MSMZ_ERR_UNSUPPORTED;
+    // the largest reference: the last entry (of the second half: moved up by endo_delta), in the last copy
+    const uint32_t W = Planner<Fr>::set_windows(pl);
+    if ((uint64_t)pl.M - 1 + pl.endo_delta + (uint64_t)(W - 1) * a.copy_stride >= (1ull << 31)) return MSMZ_ERR_ARG;
+    const uint32_t per_tile = pl.glv ? COARSE_TILE / 2 : COARSE_TILE;
+    const size_t n_off = (size_t)pl.nprob * pl.nb + 1, n_bins = (size_t)pl.nprob * g.sbins + 1;
+    if (a.geom) {
+      const uint32_t gw[MSMZ_TS_GEOM_WORDS] = {
+          (uint32_t)pl.c, (uint32_t)pl.K, (uint32_t)pl.Keff, pl.L, pl.nb, (uint32_t)g.fb, (uint32_t)g.fbt, g.ncb, g.ncbt,
+          sl.nbins, g.sbins, sl.fbins, sl.fine_top, (uint32_t)pl.spread, (uint32_t)pl.fold_shift, (uint32_t)pl.fold_rows,
+          W, (uint32_t)g.mbits, (uint32_t)g.idx_bits, (uint32_t)sl.cspec, sl.two_level ? 1u : 0u,
+          sl.two_level ? (pl.n + per_tile - 1) / per_tile : 0u, (uint32_t)(pl.sbits ? pl.sbits : 256), pl.endo_delta};
+      memcpy(a.geom, gw, sizeof(gw));
+    }
+    if (!a.meta && !a.off && !a.refs && !a.bins && !a.packed) return MSMZ_OK;   // the geometry only
+    if ((a.off && a.off_cap < n_off) || (a.refs && a.refs_cap < cap_entries)) return MSMZ_ERR_ARG;
+    if (sl.two_level && ((a.bins && a.bins_cap < n_bins) || (a.packed && a.packed_cap < cap_entries))) return MSMZ_ERR_ARG;
+
+    Staging sg = staging();
+    const int is = sg.in(a.scalars_le32, (size_t)32 * pl.nprob * n);
+    if ((st = sg.upload())) return st;
+    Run run = eng_.new_run(opt);
+    if ((st = eng_.sort_phase(pl, sl, sg.at<const uint32_t>(is), run, a.copy_stride)) || (st = eng_.fetch_meta(run)))
+      return st;
+    const uint32_t n_entries = run.n_entries;
+    if (n_entries > cap_entries) return MSMZ_ERR_HIP;   // (a broken count: nothing is copied by it)
+    if (a.meta) {
+      a.meta[0] = eng_.h_meta_->error;
+      a.meta[1] = n_entries;
+      a.meta[2] = run.max_bucket;
+    }
+    if (a.off) MSMZ_HIP(hipMemcpy(a.off, eng_.off_.p, n_off * 4, hipMemcpyDeviceToHost));
+    if (a.refs && n_entries) MSMZ_HIP(hipMemcpy(a.refs, eng_.refs_.p, (size_t)n_entries * 4, hipMemcpyDeviceToHost));
+    if (sl.two_level) {
+      if (a.bins) MSMZ_HIP(hipMemcpy(a.bins, eng_.bins_.p, n_bins * 4, hipMemcpyDeviceToHost));
+      if (a.packed && n_entries)
+        MSMZ_HIP(hipMemcpy(a.packed, eng_.packed_.p, (size_t)n_entries * 4, hipMemcpyDeviceToHost));
     }
     return MSMZ_OK;
   }

@@ -1,5 +1,6 @@
 """Development aid: runs only the bucket sort (test hook msmz_test_sort) on 2^log2n random BLS12-377 scalars, for the
-workgroup timelines of a -DMSMZ_TRACE build (tools/wg_timeline.py).  usage: sort_probe.py [log2n] [c] [glv]"""
+workgroup timelines of a -DMSMZ_TRACE build (tools/wg_timeline.py); msmz_test_sort_ex names the full geometry.
+usage: sort_probe.py [log2n] [c] [glv]"""
 import ctypes as C
 import os
 import sys
@@ -26,3 +27,8 @@ for _ in range(3):
     st = lib.msmz_test_sort(curve._ctx, raw.ctypes.data_as(C.c_char_p), n, c, glv, 0, geom, None, 0, None, 0)
     assert st == 0, st
 print("geometry c K Keff L nb E maxb spread:", list(geom))
+words = (C.c_uint32 * len(_native.TEST_SORT_GEOM))()
+args = _native.MsmzTestSortArgs(scalars_le32=raw.ctypes.data_as(C.c_void_p), n=n, nprob=1, c=c, glv=glv,
+                                geom=C.cast(words, C.c_void_p), geom_cap=len(words))
+assert lib.msmz_test_sort_ex(curve._ctx, C.byref(args)) == 0
+print("layout:", dict(zip(_native.TEST_SORT_GEOM, words)))
