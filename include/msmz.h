@@ -242,6 +242,38 @@ int msmz_precomputed_info(msmz_ctx* ctx, uint64_t handle, int32_t* c, int32_t* g
 /* the scalar bit bound a precomputed handle was built for: 0 = none (also for a bound of at least the field's bit length) */
 int msmz_precomputed_scalar_bits(msmz_ctx* ctx, uint64_t handle, int32_t* bits);
 
+/* Validation of a resident point set: is every point on the curve, and in the subgroup of prime
+ * order q the scalars are reduced for?  The engine checks coordinates < p on the way in (MSMZ_ERR_RANGE) and nothing
+ * else: every addition formula assumes a = 0 and never reads b, so an off-curve input is summed, silently, on some
+ * other curve, and a point with a cofactor component gives a result outside the group.  This is the reference's
+ * isOnCurve / isInSubgroup (src/curve-affine.ts:193, src/curve-projective.ts:291-303) over a resident set, on the GPU.
+ * It is a QUERY: bad points are not an error, the call returns MSMZ_OK and `out` says what was found.
+ *   what       MSMZ_CHECK_CURVE: y^2 = x^3 + b (Weierstrass), -x^2 + y^2 = 1 + d x^2 y^2 (twisted Edwards).
+ *              MSMZ_CHECK_SUBGROUP (implies CURVE): also [q]P = O for every point on the curve, q the order of the curve
+ *              parameters: one scalar multiplication per point.  Pallas has cofactor 1: there SUBGROUP equals CURVE and
+ *              no scalar multiplication is run (curve-projective.ts:295).
+ *   verdicts   nullable, count bytes: verdicts[i] describes point first + i.  Bit 0 (value 1): not on the curve.  Bit 1
+ *              (value 2): on the curve and [q]P != O.  An off-curve point never has bit 1 (the group law means nothing
+ *              for it; it is not multiplied).  With MSMZ_CHECK_CURVE alone bit 1 is never set.
+ *   out        counts of either verdict in [first, first + count) and first_bad, the smallest index -- in the set, not
+ *              relative to `first` -- with a non-zero verdict (UINT64_MAX: none).  Deterministic.
+ * A Weierstrass point flagged as infinity when it came in is on the curve and in the subgroup whatever its coordinates
+ * were (an UNFLAGGED (0, 0) is not that record: zero is stored as a non-zero multiple of p, and the point is reported
+ * off the curve, as the reference's isOnCurve reports it); the twisted-Edwards identity (0, 1) is in the subgroup.  The resident records are what is read: a set that came in by
+ * upload, import (host or device memory, canonical or Montgomery) or msmz_random_points is checked by the same code.  Of a
+ * set with endomorphism images only the n base points are checked and indexed.
+ * MSMZ_ERR_ARG, before any launch: a null ctx or out, an unknown or a scalar handle, count == 0, first + count beyond
+ * the set, what == 0 or unknown bits in it.  MSMZ_ERR_UNSUPPORTED: a precomputed handle (derived data: check the source
+ * set before precomputing).  On a multi-device context every engine checks its own share; indices are the set's. */
+enum { MSMZ_CHECK_CURVE = 1, MSMZ_CHECK_SUBGROUP = 2 };   /* SUBGROUP implies CURVE */
+typedef struct msmz_check_result {
+  uint64_t off_curve;     /* points that do not satisfy the curve equation */
+  uint64_t off_subgroup;  /* points on the curve with [q]P != O */
+  uint64_t first_bad;     /* smallest index (in the set, not relative to `first`) with a non-zero verdict; UINT64_MAX = none */
+} msmz_check_result;
+int msmz_check_points(msmz_ctx* ctx, uint64_t points_handle, uint64_t first, uint64_t count, uint32_t what,
+                      msmz_check_result* out, uint8_t* verdicts /* nullable, count bytes */);
+
 /* Host-side group addition of two canonical affine results: combines per-GPU partial sums
  * (the reference's "partition sum" step, msm-batched-affine.ts:300-307). */
 int msmz_point_add(int curve_id, const uint8_t* a_xy_le, int a_is_inf, const uint8_t* b_xy_le, int b_is_inf,

@@ -12,6 +12,7 @@ export interface DeviceArray extends Array<DeviceArray> { readonly n: number; re
  * scalar that breaks it fails the call */
 export type MsmOptions = { c?: number; glv?: boolean | number; useSafeAdditions?: boolean; reduceAffine?: boolean; scalarBits?: number };
 export type MsmResult = { result: BigintPoint; log: any[][]; stats: Record<string, any> };
+export type CheckResult = { ok: boolean; offCurve: number; offSubgroup: number; firstBad: number | null; verdicts: Uint8Array | null };
 export interface ParallelApi {
   randomPointsFast(n: number, options?: { seed?: bigint | number }): Promise<DeviceArray>;
   randomScalars(n: number, options?: { seed?: bigint | number }): Promise<DeviceArray>;
@@ -30,6 +31,9 @@ export interface ParallelApi {
   msmUnsafe(scalars: DeviceArray | Uint8Array | number, points: DeviceArray | number, n: number, verbose?: boolean, options?: MsmOptions): Promise<MsmResult>;
   /** fixed-base precomputation: the result goes wherever `points` is taken (factor 0 = all windows in one bucket set) */
   precomputePoints(points: DeviceArray, n: number, options?: { c?: number; glv?: boolean | number; scalarBits?: number }, factor?: number): Promise<DeviceArray>;
+  /** are points [first, first + n) on the curve and (subgroup, the default) in the prime-order subgroup?  verdicts: one
+   * byte per point, bit 0 = not on the curve, bit 1 = on the curve but outside the subgroup */
+  checkPoints(points: DeviceArray, n?: number, options?: { subgroup?: boolean; first?: number; verdicts?: boolean }): Promise<CheckResult>;
   msmBatch(scalarsList: DeviceArray | Uint8Array[], points: DeviceArray, n: number, options?: MsmOptions & { batch?: number }): Promise<BigintPoint[]>;
   msmBatchUnsafe(scalarsList: DeviceArray | Uint8Array[], points: DeviceArray, n: number, options?: MsmOptions & { batch?: number }): Promise<BigintPoint[]>;
   msmProjective?(scalars: DeviceArray | Uint8Array, points: DeviceArray, n: number, options?: MsmOptions): Promise<MsmResult>;

@@ -247,6 +247,21 @@ function createCurve(params, kind) {
       Object.defineProperty(arr, "info", { value: N.precomputedInfo(ctx, h) });
       return arr;
     },
+    /** validation of a resident point set (include/msmz.h msmz_check_points): are points [first, first + n) on the curve
+     * and, with subgroup (the default), in the subgroup of prime order?  isOnCurve / isInSubgroup of the reference's
+     * curve API over a whole set, on the GPU.  -> {ok, offCurve, offSubgroup, firstBad (an index of the array, null if
+     * ok), verdicts (with options.verdicts: one byte per point, bit 0 = not on the curve, bit 1 = on the curve but
+     * outside the subgroup)} */
+    async checkPoints(points, n, { subgroup = true, first = 0, verdicts = false } = {}) {
+      if (!(points instanceof DeviceArray) || points.kind !== "points")
+        throw TypeError("checkPoints: `points` is a resident point array (pointsFromBytes / randomPointsFast)");
+      if (!Number.isInteger(first) || first < 0 || first >= points.n) throw Error(`checkPoints: first = ${first} but the point set holds ${points.n}`);
+      n = n === undefined || n === null ? points.n - first : n;
+      if (!Number.isInteger(n) || n < 1 || n > points.n - first) throw Error(`checkPoints: points [${first}, +${n}) of a set of ${points.n}`);
+      const r = N.checkPoints(ctx, points.handle, first, n, subgroup ? 3 : 1, !!verdicts);
+      return { ok: r.firstBad < 0, offCurve: r.offCurve, offSubgroup: r.offSubgroup, firstBad: r.firstBad < 0 ? null : r.firstBad,
+               verdicts: r.verdicts };
+    },
     /** batched MSM: B scalar vectors against one point set (include/msmz.h msmz_msm_batch); safe additions */
     msmBatch: (scalarsList, points, n, options) => msmBatchCommon(scalarsList, points, n, options, 1),
     msmBatchUnsafe: (scalarsList, points, n, options) => msmBatchCommon(scalarsList, points, n, options, 0),

@@ -33,6 +33,14 @@ class MsmzSrc(C.Structure):   # msmz_src (include/msmz.h): where an imported set
                 ("stream", C.c_void_p), ("is_inf", C.c_void_p)]
 
 
+MSMZ_CHECK_CURVE, MSMZ_CHECK_SUBGROUP = 1, 2
+NO_INDEX = (1 << 64) - 1   # msmz_check_result.first_bad: no bad point
+
+
+class MsmzCheckResult(C.Structure):   # msmz_check_result (include/msmz.h)
+    _fields_ = [("off_curve", C.c_uint64), ("off_subgroup", C.c_uint64), ("first_bad", C.c_uint64)]
+
+
 class MsmzTestReduceArgs(C.Structure):   # msmz_test_reduce_args (include/msmz_test.h)
     _fields_ = [("mode", C.c_int32), ("c", C.c_int32), ("nsets", C.c_uint32), ("n_in", C.c_uint32),
                 ("nc", C.c_uint32), ("tail_n", C.c_uint32), ("quad16_max", C.c_uint32), ("pairsum_x4_max", C.c_uint32),
@@ -98,6 +106,8 @@ EXPORTS = {
     "msmz_precomputed_info": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "msmz_precomputed_scalar_bits": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_int32)]),
+    "msmz_check_points": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                    C.POINTER(MsmzCheckResult), C.c_char_p]),
     "msmz_point_add": (C.c_int, [C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.POINTER(C.c_int)]),
     # stage-level test hooks (include/msmz_test.h)
     "msmz_test_set_glv_bits": (C.c_int, [C.c_void_p, C.c_int]),

@@ -18,6 +18,7 @@
 #include "kernels.h"
 #include "gen_kernels.h"
 #include "import_kernels.h"
+#include "check_kernels.h"
 #include "host64.h"
 #include "multi.h"
 #include "plan.h"
@@ -272,6 +273,7 @@ class Engine : public IEngine {
     (void)hipSetDevice(device_);
     if (h_meta_) (void)hipHostFree(h_meta_);
     if (h_res_) (void)hipHostFree(h_res_);
+    if (h_check_) (void)hipHostFree(h_check_);
     for (hipEvent_t* e : ev_.all())
       if (*e) (void)hipEventDestroy(*e);
     if (import_ev_) (void)hipEventDestroy(import_ev_);
@@ -602,6 +604,47 @@ class Engine : public IEngine {
     if (it == handles_.end()) return MSMZ_ERR_ARG;
     (void)hipSetDevice(device_);
     handles_.erase(it);
+    return MSMZ_OK;
+  }
+
+  // ------------------------------------------------------------------------------------------ validation
+  // msmz_check_points: the curve equation, then (if asked, and unless the curve has cofactor 1) [q]P = O, over base
+  // points [first, first + count) of a plain point handle.  A query: bad points are reported, not refused.  Two launches,
+  // then the result record and the verdict bytes come back behind ONE host wait, like the error word of an upload.
+  int check_points(uint64_t hd, uint64_t first, uint64_t count, uint32_t what, msmz_check_result* out,
+                   uint8_t* verdicts) override {
+    if (!out || count == 0 || what == 0 || (what & ~(uint32_t)(MSMZ_CHECK_CURVE | MSMZ_CHECK_SUBGROUP))) return MSMZ_ERR_ARG;
+    auto it = handles_.find(hd);
+    if (it == handles_.end() || it->second.kind != 0) return MSMZ_ERR_ARG;
+    if (it->second.factor) return MSMZ_ERR_UNSUPPORTED;   // derived data: the source set is what a caller checks
+    if (first > it->second.n || count > it->second.n - first) return MSMZ_ERR_ARG;   // (base points only; no first + count: it can wrap)
+    MSMZ_HIP(hipSetDevice(device_));
+    if (int st = ensure_host_check(verdicts ? count : 0)) return st;
+    if (int st = check_.ensure(sizeof(CheckResult) + count)) return st;
+    CheckResult* d_res = check_.as<CheckResult>();
+    uint8_t* d_verdicts = check_.as<uint8_t>() + sizeof(CheckResult);
+    const uint32_t* recs = it->second.mem.template as<const uint32_t>() + first * PW_WORDS;
+    const dim3 grid((uint32_t)((count + 255) / 256)), block(256);
+    MSMZ_HIP(hipMemsetAsync(d_res, 0, 8, stream_));
+    MSMZ_HIP(hipMemsetAsync(&d_res->first_bad, 0xff, 4, stream_));
+    const bool chain = (what & MSMZ_CHECK_SUBGROUP) && !Fr::PRIME_ORDER;   // cofactor 1: the curve is the subgroup
+    if constexpr (TE) {
+      hipLaunchKernelGGL((k_te_check_curve<F>), grid, block, 0, stream_, d_verdicts, d_res, recs, (uint32_t)count, (uint32_t)first);
+      if (chain)
+        hipLaunchKernelGGL((k_te_check_subgroup<F, Fr>), grid, block, 0, stream_, d_verdicts, d_res, recs, (uint32_t)count, (uint32_t)first);
+    } else {
+      hipLaunchKernelGGL((k_check_curve<F>), grid, block, 0, stream_, d_verdicts, d_res, recs, (uint32_t)count, (uint32_t)first);
+      if (chain)
+        hipLaunchKernelGGL((k_check_subgroup<F, Fr>), grid, block, 0, stream_, d_verdicts, d_res, recs, (uint32_t)count, (uint32_t)first);
+    }
+    MSMZ_HIP(hipGetLastError());
+    // both land in pinned memory (a copy into the caller's pageable buffer would block the host a second time)
+    MSMZ_HIP(hipMemcpyAsync(h_check_, d_res, sizeof(CheckResult) + (verdicts ? count : 0), hipMemcpyDeviceToHost, stream_));
+    MSMZ_HIP(hipStreamSynchronize(stream_));
+    if (verdicts) memcpy(verdicts, reinterpret_cast<const uint8_t*>(h_check_) + sizeof(CheckResult), count);
+    out->off_curve = h_check_->off_curve;
+    out->off_subgroup = h_check_->off_subgroup;
+    out->first_bad = h_check_->first_bad == 0xffffffffu ? UINT64_MAX : h_check_->first_bad;
     return MSMZ_OK;
   }
 
@@ -1571,6 +1614,19 @@ class Engine : public IEngine {
                         (uint32_t)env_int("MSMZ_R2_NC", 0)}};
   DevBuf bsum_, f2desc_, tilecnt_, tileoff_, final_, desc_, bfin_, packed_, bins_, digits_, counts_, off_, cursor_, refs_, rscan_, partials_, slots_, red_[4], meta_, stage_, gen_table_;
   MsmMeta* h_meta_ = nullptr;
+  DevBuf check_;                     // check_points: its result record, then one verdict byte per point
+  CheckResult* h_check_ = nullptr;   // pinned, grow-only landing of the result record and the verdict bytes behind it
+  size_t h_check_bytes_ = 0;
+  int ensure_host_check(size_t verdict_bytes) {
+    const size_t need = sizeof(CheckResult) + verdict_bytes;
+    if (need <= h_check_bytes_) return MSMZ_OK;
+    if (h_check_) (void)hipHostFree(h_check_);
+    h_check_ = nullptr;
+    h_check_bytes_ = 0;
+    MSMZ_HIP(hipHostMalloc(&h_check_, need));
+    h_check_bytes_ = need;
+    return MSMZ_OK;
+  }
   uint32_t* h_res_ = nullptr;   // pinned, grow-only: the window results of every problem of an MSM (fetch_window_sums)
   size_t h_res_words_ = 0;
   int ensure_host_results(size_t words) {

@@ -2,6 +2,7 @@
 // unit (kern_<family>.hip with -DMSMZ_CURVE=<id>) so the build parallelizes; msmz.hip only sees
 // `extern template` declarations.
 #pragma once
+#include "check_kernels.h"
 #include "gen_kernels.h"
 #include "import_kernels.h"
 #include "kernels.h"
@@ -103,6 +104,8 @@
   PFX template __global__ void k_points_to_mont<F>(uint32_t*, const uint32_t*, const uint8_t*, uint32_t, int, uint32_t*); \
   PFX template __global__ void k_points_from_mont<F>(uint32_t*, const uint32_t*, uint32_t);                       \
   PFX template __global__ void k_import_points<F>(uint32_t*, const uint8_t*, uint64_t, const uint8_t*, uint32_t, int, int, uint32_t*); \
+  PFX template __global__ void k_check_curve<F>(uint8_t*, CheckResult*, const uint32_t*, uint32_t, uint32_t);     \
+  PFX template __global__ void k_check_subgroup<F, Fr>(uint8_t*, CheckResult*, const uint32_t*, uint32_t, uint32_t); \
   PFX template __global__ void k_precompute_copy<F>(uint32_t*, const uint32_t*, uint32_t, int, int);              \
   PFX template __global__ void k_digits<Fr, true>(uint32_t*, uint32_t*, MsmMeta*, const uint32_t*, uint32_t, int, int, int, int); \
   MSMZ_INST_SORT(Fr, true, 0, PFX)                                                                                \
@@ -117,6 +120,8 @@
   PFX template __global__ void k_te_points_to_niels<F>(uint32_t*, const uint32_t*, uint32_t, uint32_t*); \
   PFX template __global__ void k_te_points_from_niels<F>(uint32_t*, const uint32_t*, uint32_t);    \
   PFX template __global__ void k_te_import_points<F>(uint32_t*, const uint8_t*, uint64_t, uint32_t, int, uint32_t*); \
+  PFX template __global__ void k_te_check_curve<F>(uint8_t*, CheckResult*, const uint32_t*, uint32_t, uint32_t); \
+  PFX template __global__ void k_te_check_subgroup<F, Fr>(uint8_t*, CheckResult*, const uint32_t*, uint32_t, uint32_t); \
   MSMZ_INST_TEST(F, Fr, TePolicy<F>, true, PFX)                                                    \
   MSMZ_INST_SCALAR(Fr, PFX)
 

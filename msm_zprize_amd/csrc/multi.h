@@ -89,6 +89,9 @@ class IEngine {
   virtual int precompute_points(uint64_t ph, uint64_t n, int c, int glv, uint32_t copies, int sbits, uint64_t* h) = 0;
   virtual int precomputed_info(uint64_t h, int32_t* c, int32_t* glv, uint32_t* factor, uint32_t* K, uint64_t* records,
                                int32_t* sbits) = 0;
+  // msmz_check_points over base points [first, first + count) of a plain point handle
+  virtual int check_points(uint64_t h, uint64_t first, uint64_t count, uint32_t what, msmz_check_result* out,
+                           uint8_t* verdicts) = 0;
   // tests (include/msmz_test.h); the stage-level hooks are one engine's (a multi-device context: its first engine's)
   virtual int test_set_glv_bits(int) { return MSMZ_ERR_UNSUPPORTED; }
   virtual int test_retries() { return 0; }
@@ -333,6 +336,48 @@ class MultiEngine : public IEngine {
     if (it == handles_.end() || it->second.factor == 0) return MSMZ_ERR_ARG;
     if (records) *records = (uint64_t)it->second.factor * it->second.n * (it->second.glv ? 2 : 1);
     return workers_[0]->eng->precomputed_info(it->second.sub[0], c, glv, factor, K, nullptr, sbits);   // (shard 0 holds block 0)
+  }
+
+  // Every engine checks its own share: the set indices [first, first + count) that live on device g are one contiguous
+  // range of its local array (the local order is the set order), [shard_count(first), shard_count(first + count)).  Local
+  // indices go back to set indices through the block split, as in download_points.
+  int check_points(uint64_t hd, uint64_t first, uint64_t count, uint32_t what, msmz_check_result* out,
+                   uint8_t* verdicts) override {
+    if (!out || count == 0 || what == 0 || (what & ~(uint32_t)(MSMZ_CHECK_CURVE | MSMZ_CHECK_SUBGROUP))) return MSMZ_ERR_ARG;
+    auto it = handles_.find(hd);
+    if (it == handles_.end() || it->second.kind != 0) return MSMZ_ERR_ARG;
+    if (it->second.factor) return MSMZ_ERR_UNSUPPORTED;
+    if (first > it->second.n || count > it->second.n - first) return MSMZ_ERR_ARG;
+    const MHandle& mh = it->second;
+    std::vector<msmz_check_result> res(G_, msmz_check_result{0, 0, UINT64_MAX});
+    std::vector<std::vector<uint8_t>> local(G_);
+    std::vector<uint64_t> lo(G_), cnt(G_);
+    for (uint32_t g = 0; g < G_; g++) {
+      lo[g] = shard_count(first, g, G_);
+      cnt[g] = shard_count(first + count, g, G_) - lo[g];
+      if (verdicts) local[g].resize(cnt[g]);
+    }
+    int st = for_all([&](uint32_t g, IEngine* e) {
+      if (cnt[g] == 0) return (int)MSMZ_OK;
+      return e->check_points(mh.sub[g], lo[g], cnt[g], what, &res[g], verdicts ? local[g].data() : nullptr);
+    });
+    if (st) return st;
+    *out = msmz_check_result{0, 0, UINT64_MAX};
+    const uint64_t mask = (1ull << MULTI_BLOCK_SHIFT) - 1;
+    for (uint32_t g = 0; g < G_; g++) {
+      out->off_curve += res[g].off_curve;
+      out->off_subgroup += res[g].off_subgroup;
+      if (res[g].first_bad == UINT64_MAX) continue;
+      const uint64_t li = res[g].first_bad;
+      const uint64_t gi = ((((li >> MULTI_BLOCK_SHIFT) * G_ + g) << MULTI_BLOCK_SHIFT)) | (li & mask);
+      if (gi < out->first_bad) out->first_bad = gi;
+    }
+    if (!verdicts) return MSMZ_OK;
+    return for_range(mh, first, count, [&](IEngine*, uint64_t, uint64_t li, uint64_t gi, uint64_t len) {
+      const uint32_t g = (uint32_t)((gi >> MULTI_BLOCK_SHIFT) % G_);
+      memcpy(verdicts + (gi - first), local[g].data() + (li - lo[g]), len);
+      return (int)MSMZ_OK;
+    });
   }
 
   int test_set_glv_bits(int bits) override {

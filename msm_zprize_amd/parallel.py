@@ -17,7 +17,7 @@ include/msmz.h -- this module contains no arithmetic.
 import ctypes as C
 
 from . import _native
-from ._native import MsmzLog, MsmzOpts, MsmzSrc, check, lib
+from ._native import MsmzCheckResult, MsmzLog, MsmzOpts, MsmzSrc, check, lib
 
 _state = {"devices": None}
 
@@ -118,9 +118,14 @@ class _Parallel:
         check(lib().msmz_random_scalars(self._c._ctx, n, seed, C.byref(h)), "msmz_random_scalars")
         return DeviceArray(self._c, h.value, n, "scalars")
 
-    def pointsFromBytes(self, data, n=None, is_inf=None, montgomery=False):
+    def pointsFromBytes(self, data, n=None, is_inf=None, montgomery=False, check=None):
         """parallel.ts:97-112: x||y little-endian canonical, 2*fe_bytes per point.  montgomery=True: the coordinates are
-        64-bit-limb Montgomery residues v * 2^(8 fe_bytes) mod p (msmz_import_points), converted on the GPU."""
+        64-bit-limb Montgomery residues v * 2^(8 fe_bytes) mod p (msmz_import_points), converted on the GPU.
+        check="curve" / "subgroup": validate the new set on the GPU (checkPoints); a set that fails is freed and
+        ValueError names its first bad point.  None (the default) validates nothing."""
+        what = check_arg(check, "pointsFromBytes")
+        if what:
+            return self._checked(self.pointsFromBytes(data, n, is_inf, montgomery), what, "pointsFromBytes")
         fb = self._c.fe_bytes
         n = len(data) // (2 * fb) if n is None else n
         if n <= 0 or len(data) < 2 * fb * n:
@@ -133,9 +138,9 @@ class _Parallel:
             flags = None if is_inf is None else bytes(is_inf)
             src = MsmzSrc(C.cast(C.c_char_p(data), C.c_void_p), 0, 2 * fb, _native.MSMZ_SRC_MONTGOMERY, None,
                           None if flags is None else C.cast(C.c_char_p(flags), C.c_void_p))
-            check(lib().msmz_import_points(self._c._ctx, C.byref(src), n, C.byref(h)), "msmz_import_points")
+            _native.check(lib().msmz_import_points(self._c._ctx, C.byref(src), n, C.byref(h)), "msmz_import_points")
             return DeviceArray(self._c, h.value, n, "points")
-        check(lib().msmz_upload_points(self._c._ctx, bytes(data), None if is_inf is None else bytes(is_inf), n,
+        _native.check(lib().msmz_upload_points(self._c._ctx, bytes(data), None if is_inf is None else bytes(is_inf), n,
                                        C.byref(h)), "msmz_upload_points")
         return DeviceArray(self._c, h.value, n, "points")
 
@@ -196,15 +201,44 @@ class _Parallel:
               "msmz_import_scalars_into")
         return dst
 
-    def pointsFromTensor(self, t, montgomery=False, is_inf=None):
+    def pointsFromTensor(self, t, montgomery=False, is_inf=None, check=None):
         """A resident point array from a torch tensor of n rows of 2 * fe_bytes bytes (x || y, little-endian), read where
         it lies (msmz_import_points); montgomery=True: coordinates v * 2^(8 fe_bytes) mod p.  is_inf: optional 1-D
-        contiguous 1-byte tensor of n flags on the same device."""
+        contiguous 1-byte tensor of n flags on the same device.  check: as pointsFromBytes."""
+        what = check_arg(check, "pointsFromTensor")
+        if what:
+            return self._checked(self.pointsFromTensor(t, montgomery, is_inf), what, "pointsFromTensor")
         view = tensor_view(t, self._c.devices, "points", self._c.fe_bytes, montgomery, "pointsFromTensor", is_inf)
         h = C.c_uint64()
-        check(lib().msmz_import_points(self._c._ctx, C.byref(self._src(view)), view["n"], C.byref(h)),
+        _native.check(lib().msmz_import_points(self._c._ctx, C.byref(self._src(view)), view["n"], C.byref(h)),
               "msmz_import_points")
         return DeviceArray(self._c, h.value, view["n"], "points")
+
+    # -- validation (msmz_check_points, include/msmz.h) ---------------------------------------------
+    def checkPoints(self, points, N=None, subgroup=True, first=0, verdicts=False):
+        """Are points [first, first + N) of a resident point array on the curve and (subgroup=True) in the subgroup of
+        prime order?  isOnCurve / isInSubgroup of the reference's curve API over a whole set, on the GPU.  Returns a
+        CheckResult: ok, offCurve, offSubgroup, firstBad (an index of the array, None if ok) and, with verdicts=True,
+        `verdicts`: N bytes, bit 0 = not on the curve, bit 1 = on the curve but outside the subgroup."""
+        first, N, what = check_points_args(points, N, subgroup, first)
+        res = MsmzCheckResult()
+        buf = C.create_string_buffer(N) if verdicts else None
+        check(lib().msmz_check_points(self._c._ctx, points.handle, first, N, what, C.byref(res), buf), "msmz_check_points")
+        bad = None if res.first_bad == _native.NO_INDEX else int(res.first_bad)
+        return CheckResult(bad is None, int(res.off_curve), int(res.off_subgroup), bad, buf.raw if verdicts else None)
+
+    def _checked(self, arr, what, who):
+        try:
+            res = self.checkPoints(arr, subgroup=bool(what & _native.MSMZ_CHECK_SUBGROUP))
+        except Exception:
+            arr.free()   # the check itself failed: the new set does not outlive the call either
+            raise
+        if not res.ok:
+            arr.free()
+            raise ValueError(f"{who}: point {res.firstBad} is not {'on the curve' if res.offCurve else 'in the subgroup'} "
+                             f"(firstBad = {res.firstBad}; {res.offCurve} off the curve, {res.offSubgroup} outside the "
+                             f"subgroup)")
+        return arr
 
     def _assemble(self, vecs, N):
         """one resident set of len(vecs) * N scalars from device tensors / resident scalar arrays (msmBatch)"""
@@ -377,6 +411,43 @@ class _Parallel:
         options = dict(options or {})
         options["glv"] = 0
         return self._msm(scalars, points, N, True, options, 1, 1)
+
+
+class CheckResult:
+    """What checkPoints found (msmz_check_result)."""
+
+    def __init__(self, ok, offCurve, offSubgroup, firstBad, verdicts=None):
+        self.ok, self.offCurve, self.offSubgroup, self.firstBad, self.verdicts = ok, offCurve, offSubgroup, firstBad, verdicts
+
+    def __repr__(self):
+        return (f"CheckResult(ok={self.ok}, offCurve={self.offCurve}, offSubgroup={self.offSubgroup}, "
+                f"firstBad={self.firstBad})")
+
+
+def check_points_args(points, N, subgroup, first):
+    """Arguments of checkPoints -> (first, N, what), checked before anything reaches the device."""
+    if not isinstance(points, DeviceArray) or points.kind != "points":
+        raise TypeError("checkPoints: `points` is a resident point array (pointsFromBytes / randomPointsFast); a "
+                        "precomputed array is derived data: check the set it was made from")
+    if isinstance(first, bool) or not isinstance(first, int) or not 0 <= first < len(points):
+        raise ValueError(f"checkPoints: first = {first!r} but the point set holds {len(points)}")
+    if N is None:
+        N = len(points) - first
+    if isinstance(N, bool) or not isinstance(N, int) or not 1 <= N <= len(points) - first:
+        raise ValueError(f"checkPoints: points [{first}, +{N!r}) of a set of {len(points)}")
+    what = _native.MSMZ_CHECK_CURVE | (_native.MSMZ_CHECK_SUBGROUP if subgroup else 0)
+    return first, N, what
+
+
+def check_arg(check, who):
+    """check= of pointsFromBytes / pointsFromTensor -> the `what` bits of msmz_check_points (0: no validation)"""
+    if check is None:
+        return 0
+    if check == "curve":
+        return _native.MSMZ_CHECK_CURVE
+    if check == "subgroup":
+        return _native.MSMZ_CHECK_CURVE | _native.MSMZ_CHECK_SUBGROUP
+    raise ValueError(f'{who}: check = {check!r} (None, "curve" or "subgroup")')
 
 
 def precompute_args(points, N, options, factor):

@@ -402,6 +402,32 @@ static napi_value PrecomputedInfo(napi_env env, napi_callback_info info) {
   return res;
 }
 
+/* checkPoints(ctx, pointsHandle, first, count, what, wantVerdicts) -> {offCurve, offSubgroup, firstBad, verdicts}
+   (msmz_check_points; what: 1 = curve, 3 = curve + subgroup; firstBad -1 = none; verdicts: Buffer or null) */
+static napi_value CheckPoints(napi_env env, napi_callback_info info) {
+  size_t argc = 6; napi_value argv[6];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  msmz_ctx* ctx; if (argc < 6 || !get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "checkPoints");
+  uint64_t h, first, count, what;
+  if (!get_u64(env, argv[1], &h) || !get_u64(env, argv[2], &first) || !get_u64(env, argv[3], &count) ||
+      !get_u64(env, argv[4], &what) || what > 0xffffffffu || count > 0xffffffffu)
+    return throw_status(env, MSMZ_ERR_ARG, "checkPoints");
+  bool want = false;
+  NAPI_CALL(env, napi_get_value_bool(env, argv[5], &want));
+  void* data = NULL; napi_value buf;
+  if (want) NAPI_CALL(env, napi_create_buffer(env, (size_t)count, &data, &buf));
+  else NAPI_CALL(env, napi_get_null(env, &buf));
+  msmz_check_result r;
+  int st = msmz_check_points(ctx, h, first, count, (uint32_t)what, &r, (uint8_t*)data);
+  if (st) return throw_status(env, st, "msmz_check_points");
+  napi_value res;
+  NAPI_CALL(env, napi_create_object(env, &res));
+  set_num(env, res, "offCurve", (double)r.off_curve); set_num(env, res, "offSubgroup", (double)r.off_subgroup);
+  set_num(env, res, "firstBad", r.first_bad == UINT64_MAX ? -1.0 : (double)r.first_bad);
+  NAPI_CALL(env, napi_set_named_property(env, res, "verdicts", buf));
+  return res;
+}
+
 static napi_value PointAdd(napi_env env, napi_callback_info info) {
   size_t argc = 4; napi_value argv[4];
   NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -438,7 +464,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"importScalars", ImportScalars}, {"importPoints", ImportPoints},
       {"randomPoints", RandomPoints}, {"randomScalars", RandomScalars}, {"downloadPoints", DownloadPoints},
       {"downloadScalars", DownloadScalars}, {"free", Free}, {"msm", Msm}, {"msmBatch", MsmBatch},
-      {"precomputePoints", PrecomputePoints}, {"precomputedInfo", PrecomputedInfo}, {"pointAdd", PointAdd}, {"feBytes", FeBytes}};
+      {"precomputePoints", PrecomputePoints}, {"precomputedInfo", PrecomputedInfo}, {"checkPoints", CheckPoints}, {"pointAdd", PointAdd}, {"feBytes", FeBytes}};
   for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); i++) {
     napi_value f;
     if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;

@@ -164,6 +164,7 @@ def main():
         L.append("  static constexpr int BITS = %d;" % q.bit_length())
         L.append(arr("Q", limbs(q, 8)))
         L.append("  static constexpr uint32_t QINV32 = 0x%08xu;  // -q^-1 mod 2^32 (fr_from_mont, scalar.h)" % ((-pow(q, -1, 1 << 32)) % (1 << 32)))
+        L.append("  static constexpr bool PRIME_ORDER = %s;  // true iff the cofactor is 1, i.e. the whole curve is the subgroup (check_kernels.h)" % ("true" if c["cofactor"] == 1 else "false"))
         if c["kind"] == "weierstrass":
             lam = c["endomorphism"]["lambda_"]
             g = glv_device_constants(q, lam)
