@@ -274,6 +274,37 @@ typedef struct msmz_check_result {
 int msmz_check_points(msmz_ctx* ctx, uint64_t points_handle, uint64_t first, uint64_t count, uint32_t what,
                       msmz_check_result* out, uint8_t* verdicts /* nullable, count bytes */);
 
+/* Per-point scalar multiplication of resident point sets:
+ *     out_i = [s_i] P_i (+ Q_i),   i = 0 .. n-1,   P_i = record first_p + i of points_handle, s_i and Q_i likewise
+ * -- a NEW point set made from resident ones: IPA generator folding (G'_i = G_lo,i + [u] G_hi,i: one handle as P and Q,
+ * first_p = n, first_q = 0, the broadcast u), SRS re-randomisation (P_i -> [tau^i] P_i), fixed-base vectors.
+ * Result: a new plain point handle of n base points, exactly what msmz_upload_points of the same affine points leaves
+ * (the endomorphism images behind them on the Weierstrass curves, Niels records on the twisted Edwards curve); every
+ * function that takes a point handle takes it.  It owns its memory, and the call returns after the GPU has finished.
+ * Values: [0]P, [s]O and P + (-P) are the point at infinity (Weierstrass: the all-zero record, is_inf = 1 on download;
+ * ed-on-bls12-377: the identity (0, 1)).  The addition of Q is complete: Q = [s]P (a doubling), Q = -[s]P and either
+ * operand at infinity are covered.  The inputs need not lie in the subgroup: a point of small order multiplies to what
+ * the group law gives.  Of sets with endomorphism images only the base points are read.  Scalars are read whole: plain
+ * double-and-add over all bits of the group order's length, one thread per point, 64 points sharing one field inversion.
+ * MSMZ_ERR_ARG, before any launch: a null ctx, descriptor or out_handle; n == 0; an unknown handle or one of the wrong
+ * kind; a range [first, first + n) beyond its set; scalars_handle == 0 with a null `scalar`; n beyond the limit of
+ * msmz_upload_points.  MSMZ_ERR_UNSUPPORTED: a precomputed handle as P or Q.  MSMZ_ERR_RANGE: the broadcast scalar >= q
+ * (checked on the host), or a resident scalar >= q (found by the kernel; no handle is created, the context stays usable).
+ * Multi-device contexts: every engine multiplies its own share and the result is dealt like an upload.  Sets are dealt in
+ * blocks of 2^16 records, so index i of P, s and Q lives on one device only when first_p == first_s == first_q == 0: any
+ * other combination is MSMZ_ERR_UNSUPPORTED there.  Like the rest of the multi-device code this has run as several
+ * engines on ONE GPU only. */
+typedef struct msmz_mul {
+  uint64_t points_handle;   /* plain point handle: P */
+  uint64_t first_p;         /* P_i = record first_p + i */
+  uint64_t scalars_handle;  /* scalar handle, or 0 = one scalar for all i (`scalar`) */
+  uint64_t first_s;
+  const uint8_t* scalar;    /* 32 bytes little-endian, < q; read only when scalars_handle == 0 */
+  uint64_t addend_handle;   /* plain point handle Q, or 0 = no addend; may equal points_handle */
+  uint64_t first_q;
+} msmz_mul;
+int msmz_points_mul(msmz_ctx* ctx, const msmz_mul* m, uint64_t n, uint64_t* out_handle);
+
 /* Host-side group addition of two canonical affine results: combines per-GPU partial sums
  * (the reference's "partition sum" step, msm-batched-affine.ts:300-307). */
 int msmz_point_add(int curve_id, const uint8_t* a_xy_le, int a_is_inf, const uint8_t* b_xy_le, int b_is_inf,

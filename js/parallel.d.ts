@@ -34,6 +34,10 @@ export interface ParallelApi {
   /** are points [first, first + n) on the curve and (subgroup, the default) in the prime-order subgroup?  verdicts: one
    * byte per point, bit 0 = not on the curve, bit 1 = on the curve but outside the subgroup */
   checkPoints(points: DeviceArray, n?: number, options?: { subgroup?: boolean; first?: number; verdicts?: boolean }): Promise<CheckResult>;
+  /** a new point array: out[i] = [s_i] points[firstPoint + i] (+ addend[firstAddend + i]); scalars: a resident scalar
+   * array or one bigint below the group order for every point; addend may be `points` itself (an IPA fold) */
+  mulPoints(scalars: DeviceArray | bigint, points: DeviceArray, n?: number,
+            options?: { addend?: DeviceArray | null; firstPoint?: number; firstScalar?: number; firstAddend?: number }): Promise<DeviceArray>;
   msmBatch(scalarsList: DeviceArray | Uint8Array[], points: DeviceArray, n: number, options?: MsmOptions & { batch?: number }): Promise<BigintPoint[]>;
   msmBatchUnsafe(scalarsList: DeviceArray | Uint8Array[], points: DeviceArray, n: number, options?: MsmOptions & { batch?: number }): Promise<BigintPoint[]>;
   msmProjective?(scalars: DeviceArray | Uint8Array, points: DeviceArray, n: number, options?: MsmOptions): Promise<MsmResult>;

@@ -262,6 +262,33 @@ function createCurve(params, kind) {
       return { ok: r.firstBad < 0, offCurve: r.offCurve, offSubgroup: r.offSubgroup, firstBad: r.firstBad < 0 ? null : r.firstBad,
                verdicts: r.verdicts };
     },
+    /** per-point scalar multiplication (include/msmz.h msmz_points_mul): a new resident point array,
+     * out[i] = [s_i] points[firstPoint + i] (+ addend[firstAddend + i]), i < n.  `scalars` is a resident scalar array
+     * (s_i = scalars[firstScalar + i]) or a bigint below the group order: one scalar for every point.  `addend` may be
+     * `points` itself (an IPA fold: mulPoints(u, G, n, {addend: G, firstPoint: n})).  The result is an ordinary point
+     * array. */
+    async mulPoints(scalars, points, n, { addend = null, firstPoint = 0, firstScalar = 0, firstAddend = 0 } = {}) {
+      if (!(points instanceof DeviceArray) || points.kind !== "points")
+        throw TypeError("mulPoints: `points` is a resident point array (pointsFromBytes / randomPointsFast)");
+      if (addend !== null && (!(addend instanceof DeviceArray) || addend.kind !== "points"))
+        throw TypeError("mulPoints: `addend` is a resident point array or null");
+      const broadcast = typeof scalars === "bigint";
+      if (!broadcast && (!(scalars instanceof DeviceArray) || scalars.kind !== "scalars"))
+        throw TypeError("mulPoints: `scalars` is a resident scalar array or a bigint (one scalar for every point)");
+      if (broadcast && (scalars < 0n || scalars >= params.order)) throw Error(`mulPoints: the scalar ${scalars} is not in [0, group order)`);
+      const ranges = [["firstPoint", firstPoint, points], ["firstScalar", firstScalar, broadcast ? null : scalars], ["firstAddend", firstAddend, addend]];
+      for (const [name, first, arr] of ranges) {
+        if (!Number.isInteger(first) || first < 0 || (arr === null ? first !== 0 : first >= arr.n))
+          throw Error(`mulPoints: ${name} = ${first}` + (arr === null ? " without the array it indexes" : ` but the array holds ${arr.n}`));
+      }
+      if (n === undefined || n === null) n = Math.min(...ranges.filter((r) => r[2] !== null).map(([, first, arr]) => arr.n - first));
+      if (!Number.isInteger(n) || n < 1) throw Error(`mulPoints: n = ${n}`);
+      for (const [name, first, arr] of ranges)
+        if (arr !== null && n > arr.n - first) throw Error(`mulPoints: entries [${first}, +${n}) from ${name} of an array of ${arr.n}`);
+      const h = N.mulPoints(ctx, points.handle, firstPoint, broadcast ? Buffer.from(bigintToBytes(scalars, 32)) : scalars.handle,
+                            firstScalar, addend === null ? 0 : addend.handle, firstAddend, n);
+      return DeviceArray.make(curve, h, n, "points");
+    },
     /** batched MSM: B scalar vectors against one point set (include/msmz.h msmz_msm_batch); safe additions */
     msmBatch: (scalarsList, points, n, options) => msmBatchCommon(scalarsList, points, n, options, 1),
     msmBatchUnsafe: (scalarsList, points, n, options) => msmBatchCommon(scalarsList, points, n, options, 0),

@@ -41,6 +41,11 @@ class MsmzCheckResult(C.Structure):   # msmz_check_result (include/msmz.h)
     _fields_ = [("off_curve", C.c_uint64), ("off_subgroup", C.c_uint64), ("first_bad", C.c_uint64)]
 
 
+class MsmzMul(C.Structure):   # msmz_mul (include/msmz.h): out_i = [s_i] P_i (+ Q_i)
+    _fields_ = [("points_handle", C.c_uint64), ("first_p", C.c_uint64), ("scalars_handle", C.c_uint64),
+                ("first_s", C.c_uint64), ("scalar", C.c_char_p), ("addend_handle", C.c_uint64), ("first_q", C.c_uint64)]
+
+
 class MsmzTestReduceArgs(C.Structure):   # msmz_test_reduce_args (include/msmz_test.h)
     _fields_ = [("mode", C.c_int32), ("c", C.c_int32), ("nsets", C.c_uint32), ("n_in", C.c_uint32),
                 ("nc", C.c_uint32), ("tail_n", C.c_uint32), ("quad16_max", C.c_uint32), ("pairsum_x4_max", C.c_uint32),
@@ -108,6 +113,7 @@ EXPORTS = {
     "msmz_precomputed_scalar_bits": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_int32)]),
     "msmz_check_points": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                     C.POINTER(MsmzCheckResult), C.c_char_p]),
+    "msmz_points_mul": (C.c_int, [C.c_void_p, C.POINTER(MsmzMul), C.c_uint64, C.POINTER(C.c_uint64)]),
     "msmz_point_add": (C.c_int, [C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.POINTER(C.c_int)]),
     # stage-level test hooks (include/msmz_test.h)
     "msmz_test_set_glv_bits": (C.c_int, [C.c_void_p, C.c_int]),

@@ -19,6 +19,7 @@
 #include "gen_kernels.h"
 #include "import_kernels.h"
 #include "check_kernels.h"
+#include "mul_kernels.h"
 #include "host64.h"
 #include "multi.h"
 #include "plan.h"
@@ -646,6 +647,57 @@ class Engine : public IEngine {
     out->off_subgroup = h_check_->off_subgroup;
     out->first_bad = h_check_->first_bad == 0xffffffffu ? UINT64_MAX : h_check_->first_bad;
     return MSMZ_OK;
+  }
+
+  // ------------------------------------------------------------------------------------------ per-point multiplication
+  // msmz_points_mul: a new plain point handle, record i = [s_i] P_i (+ Q_i).  One launch; the error word (a resident
+  // scalar >= q) comes back behind the ONE host wait, like that of an upload.
+  int points_mul(const msmz_mul& m, uint64_t n, uint64_t* h) override {
+    if (!h || n == 0 || n >= (1ull << (Cfg::HAS_ENDO ? 29 : 30))) return MSMZ_ERR_ARG;   // as random_points
+    auto pit = handles_.find(m.points_handle);
+    if (pit == handles_.end() || pit->second.kind != 0) return MSMZ_ERR_ARG;
+    auto qit = handles_.end(), sit = handles_.end();
+    if (m.addend_handle) {
+      qit = handles_.find(m.addend_handle);
+      if (qit == handles_.end() || qit->second.kind != 0) return MSMZ_ERR_ARG;
+    }
+    if (m.scalars_handle) {
+      sit = handles_.find(m.scalars_handle);
+      if (sit == handles_.end() || sit->second.kind != 1) return MSMZ_ERR_ARG;
+    } else if (!m.scalar) {
+      return MSMZ_ERR_ARG;
+    }
+    if (pit->second.factor || (m.addend_handle && qit->second.factor)) return MSMZ_ERR_UNSUPPORTED;   // derived data
+    auto beyond = [n](const Handle& s, uint64_t first) { return first > s.n || n > s.n - first; };   // (no first + n: it can wrap)
+    if (beyond(pit->second, m.first_p) || (m.addend_handle && beyond(qit->second, m.first_q)) ||
+        (m.scalars_handle && beyond(sit->second, m.first_s)))
+      return MSMZ_ERR_ARG;
+    MulScalar bc{};
+    if (!m.scalars_handle) {
+      memcpy(bc.w, m.scalar, 32);
+      if (words_geq<8>(bc.w, Fr::Q)) return MSMZ_ERR_RANGE;
+    }
+    MSMZ_HIP(hipSetDevice(device_));
+    const bool endo = Cfg::HAS_ENDO;
+    Handle hd{0, n, endo};
+    if (int st = alloc_handle(hd, (size_t)n * PW_WORDS * 4 * (endo ? 2 : 1))) return st;
+    MsmMeta* d_meta = meta_.as<MsmMeta>();
+    MSMZ_HIP(hipMemsetAsync(&d_meta->error, 0, 4, stream_));
+    const uint32_t* P = pit->second.mem.template as<const uint32_t>() + m.first_p * PW_WORDS;
+    const uint32_t* Q = m.addend_handle ? qit->second.mem.template as<const uint32_t>() + m.first_q * PW_WORDS : nullptr;
+    const uint32_t* S = m.scalars_handle ? sit->second.mem.template as<const uint32_t>() + m.first_s * 8 : nullptr;
+    const dim3 grid((uint32_t)((n + 255) / 256)), block(256);   // whole blocks: every wave reaches the inversion entire
+    if constexpr (TE) {
+      hipLaunchKernelGGL((k_te_points_mul<F, Fr>), grid, block, 0, stream_, hd.mem.as<uint32_t>(), P, S, bc, Q, (uint32_t)n,
+                         &d_meta->error);
+    } else {
+      hipLaunchKernelGGL((k_points_mul<F, Fr>), grid, block, 0, stream_, hd.mem.as<uint32_t>(), P, S, bc, Q, (uint32_t)n,
+                         endo ? 1 : 0, &d_meta->error);
+    }
+    uint32_t err = 0;
+    if (int st = fetch_error(&err)) return st;
+    if (err) return MSMZ_ERR_RANGE;   // a resident scalar >= group order
+    return add_handle(std::move(hd), h);
   }
 
   // ------------------------------------------------------------------------------------------ precomputed point sets

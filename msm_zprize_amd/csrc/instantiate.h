@@ -6,6 +6,7 @@
 #include "gen_kernels.h"
 #include "import_kernels.h"
 #include "kernels.h"
+#include "mul_kernels.h"
 #include "test_kernels.h"
 
 // curve ids as in include/msmz.h
@@ -107,6 +108,7 @@
   PFX template __global__ void k_check_curve<F>(uint8_t*, CheckResult*, const uint32_t*, uint32_t, uint32_t);     \
   PFX template __global__ void k_check_subgroup<F, Fr>(uint8_t*, CheckResult*, const uint32_t*, uint32_t, uint32_t); \
   PFX template __global__ void k_precompute_copy<F>(uint32_t*, const uint32_t*, uint32_t, int, int);              \
+  PFX template __global__ void k_points_mul<F, Fr>(uint32_t*, const uint32_t*, const uint32_t*, MulScalar, const uint32_t*, uint32_t, int, uint32_t*); \
   PFX template __global__ void k_digits<Fr, true>(uint32_t*, uint32_t*, MsmMeta*, const uint32_t*, uint32_t, int, int, int, int); \
   MSMZ_INST_SORT(Fr, true, 0, PFX)                                                                                \
   MSMZ_INST_SORT(Fr, true, 16, PFX)                                                                               \
@@ -122,6 +124,7 @@
   PFX template __global__ void k_te_import_points<F>(uint32_t*, const uint8_t*, uint64_t, uint32_t, int, uint32_t*); \
   PFX template __global__ void k_te_check_curve<F>(uint8_t*, CheckResult*, const uint32_t*, uint32_t, uint32_t); \
   PFX template __global__ void k_te_check_subgroup<F, Fr>(uint8_t*, CheckResult*, const uint32_t*, uint32_t, uint32_t); \
+  PFX template __global__ void k_te_points_mul<F, Fr>(uint32_t*, const uint32_t*, const uint32_t*, MulScalar, const uint32_t*, uint32_t, uint32_t*); \
   MSMZ_INST_TEST(F, Fr, TePolicy<F>, true, PFX)                                                    \
   MSMZ_INST_SCALAR(Fr, PFX)
 

@@ -204,6 +204,10 @@ int msmz_check_points(msmz_ctx* c, uint64_t ph, uint64_t first, uint64_t count, 
   return c ? c->engine->check_points(ph, first, count, what, out, verdicts) : MSMZ_ERR_ARG;
 }
 
+int msmz_points_mul(msmz_ctx* c, const msmz_mul* m, uint64_t n, uint64_t* h) {
+  return c && m ? c->engine->points_mul(*m, n, h) : MSMZ_ERR_ARG;
+}
+
 int msmz_test_set_glv_bits(msmz_ctx* c, int bits) { return c ? c->engine->test_set_glv_bits(bits) : MSMZ_ERR_ARG; }
 int msmz_test_retries(msmz_ctx* c) { return c ? c->engine->test_retries() : -1; }
 int msmz_test_field(msmz_ctx* c, int op, const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out) {

@@ -92,6 +92,8 @@ class IEngine {
   // msmz_check_points over base points [first, first + count) of a plain point handle
   virtual int check_points(uint64_t h, uint64_t first, uint64_t count, uint32_t what, msmz_check_result* out,
                            uint8_t* verdicts) = 0;
+  // msmz_points_mul: a new plain point handle, record i = [s_i] P_i (+ Q_i)
+  virtual int points_mul(const msmz_mul& m, uint64_t n, uint64_t* h) = 0;
   // tests (include/msmz_test.h); the stage-level hooks are one engine's (a multi-device context: its first engine's)
   virtual int test_set_glv_bits(int) { return MSMZ_ERR_UNSUPPORTED; }
   virtual int test_retries() { return 0; }
@@ -378,6 +380,42 @@ class MultiEngine : public IEngine {
       memcpy(verdicts + (gi - first), local[g].data() + (li - lo[g]), len);
       return (int)MSMZ_OK;
     });
+  }
+
+  // Every engine multiplies its own share of the points; the result is dealt like an upload.  Index i of P, s and Q lives
+  // on one device only when all three ranges start at a block-cycle boundary; only first = 0 is taken.
+  int points_mul(const msmz_mul& m, uint64_t n, uint64_t* h) override {
+    if (!h || n == 0) return MSMZ_ERR_ARG;
+    auto pit = handles_.find(m.points_handle);
+    if (pit == handles_.end() || pit->second.kind != 0) return MSMZ_ERR_ARG;
+    auto qit = handles_.end(), sit = handles_.end();
+    if (m.addend_handle) {
+      qit = handles_.find(m.addend_handle);
+      if (qit == handles_.end() || qit->second.kind != 0) return MSMZ_ERR_ARG;
+    }
+    if (m.scalars_handle) {
+      sit = handles_.find(m.scalars_handle);
+      if (sit == handles_.end() || sit->second.kind != 1) return MSMZ_ERR_ARG;
+    } else if (!m.scalar) {
+      return MSMZ_ERR_ARG;
+    }
+    if (pit->second.factor || (m.addend_handle && qit->second.factor)) return MSMZ_ERR_UNSUPPORTED;
+    auto beyond = [n](const MHandle& s, uint64_t first) { return first > s.n || n > s.n - first; };
+    if (beyond(pit->second, m.first_p) || (m.addend_handle && beyond(qit->second, m.first_q)) ||
+        (m.scalars_handle && beyond(sit->second, m.first_s)))
+      return MSMZ_ERR_ARG;
+    if (m.first_p || (m.scalars_handle && m.first_s) || (m.addend_handle && m.first_q)) return MSMZ_ERR_UNSUPPORTED;
+    MHandle mh{0, n, std::vector<uint64_t>(G_, 0)};
+    int st = for_all([&](uint32_t g, IEngine* e) {
+      const uint64_t cnt = shard_count(n, g, G_);
+      if (cnt == 0) return (int)MSMZ_OK;
+      msmz_mul sub = m;
+      sub.points_handle = pit->second.sub[g];
+      sub.scalars_handle = m.scalars_handle ? sit->second.sub[g] : 0;
+      sub.addend_handle = m.addend_handle ? qit->second.sub[g] : 0;
+      return e->points_mul(sub, cnt, &mh.sub[g]);
+    });
+    return finish_handle(st, mh, h);
   }
 
   int test_set_glv_bits(int bits) override {

@@ -17,7 +17,7 @@ include/msmz.h -- this module contains no arithmetic.
 import ctypes as C
 
 from . import _native
-from ._native import MsmzCheckResult, MsmzLog, MsmzOpts, MsmzSrc, check, lib
+from ._native import MsmzCheckResult, MsmzLog, MsmzMul, MsmzOpts, MsmzSrc, check, lib
 
 _state = {"devices": None}
 
@@ -226,6 +226,19 @@ class _Parallel:
         check(lib().msmz_check_points(self._c._ctx, points.handle, first, N, what, C.byref(res), buf), "msmz_check_points")
         bad = None if res.first_bad == _native.NO_INDEX else int(res.first_bad)
         return CheckResult(bad is None, int(res.off_curve), int(res.off_subgroup), bad, buf.raw if verdicts else None)
+
+    # -- per-point multiplication (msmz_points_mul, include/msmz.h) -----------------------------------
+    def mulPoints(self, scalars, points, N=None, addend=None, firstPoint=0, firstScalar=0, firstAddend=0):
+        """A new resident point array: out[i] = [s_i] points[firstPoint + i] (+ addend[firstAddend + i]), i < N.
+        `scalars` is a resident scalar array (s_i = scalars[firstScalar + i]) or a Python int below the group order:
+        one scalar for every point.  `addend` may be `points` itself (an IPA fold: mulPoints(u, G, N, addend=G,
+        firstPoint=N)).  The result is an ordinary point array: msm, msmBatch, precomputePoints, checkPoints take it."""
+        a = mul_points_args(scalars, points, N, addend, firstPoint, firstScalar, firstAddend, self._c.params["order"])
+        m = MsmzMul(points.handle, a["firstPoint"], 0 if a["scalar"] is not None else scalars.handle, a["firstScalar"],
+                    a["scalar"], 0 if addend is None else addend.handle, a["firstAddend"])
+        h = C.c_uint64()
+        check(lib().msmz_points_mul(self._c._ctx, C.byref(m), a["N"], C.byref(h)), "msmz_points_mul")
+        return DeviceArray(self._c, h.value, a["N"], "points")
 
     def _checked(self, arr, what, who):
         try:
@@ -437,6 +450,39 @@ def check_points_args(points, N, subgroup, first):
         raise ValueError(f"checkPoints: points [{first}, +{N!r}) of a set of {len(points)}")
     what = _native.MSMZ_CHECK_CURVE | (_native.MSMZ_CHECK_SUBGROUP if subgroup else 0)
     return first, N, what
+
+
+def mul_points_args(scalars, points, N, addend, firstPoint, firstScalar, firstAddend, order):
+    """Arguments of mulPoints -> dict(N, firstPoint, firstScalar, firstAddend, scalar), checked before anything reaches
+    the device.  scalar: the 32 little-endian bytes of a broadcast scalar, None for a resident scalar array."""
+    if not isinstance(points, DeviceArray) or points.kind != "points":
+        raise TypeError("mulPoints: `points` is a resident point array (pointsFromBytes / randomPointsFast); a "
+                        "precomputed array is derived data")
+    if addend is not None and (not isinstance(addend, DeviceArray) or addend.kind != "points"):
+        raise TypeError("mulPoints: `addend` is a resident point array or None")
+    broadcast = isinstance(scalars, int) and not isinstance(scalars, bool)
+    if not broadcast and (not isinstance(scalars, DeviceArray) or scalars.kind != "scalars"):
+        raise TypeError("mulPoints: `scalars` is a resident scalar array or an int (one scalar for every point)")
+    if broadcast and not 0 <= scalars < order:
+        raise ValueError(f"mulPoints: the scalar {scalars} is not in [0, group order)")
+    firsts = {"firstPoint": (firstPoint, points), "firstScalar": (firstScalar, None if broadcast else scalars),
+              "firstAddend": (firstAddend, addend)}
+    for name, (first, arr) in firsts.items():
+        if isinstance(first, bool) or not isinstance(first, int) or first < 0:
+            raise ValueError(f"mulPoints: {name} = {first!r}")
+        if arr is None and first != 0:
+            raise ValueError(f"mulPoints: {name} = {first} without the array it indexes")
+        if arr is not None and first >= len(arr):
+            raise ValueError(f"mulPoints: {name} = {first} but the array holds {len(arr)}")
+    if N is None:
+        N = min(len(arr) - first for first, arr in firsts.values() if arr is not None)
+    if isinstance(N, bool) or not isinstance(N, int) or N < 1:
+        raise ValueError(f"mulPoints: N = {N!r}")
+    for name, (first, arr) in firsts.items():
+        if arr is not None and N > len(arr) - first:
+            raise ValueError(f"mulPoints: entries [{first}, +{N}) of {name[5:].lower()}s that hold {len(arr)}")
+    return {"N": N, "firstPoint": firstPoint, "firstScalar": firstScalar, "firstAddend": firstAddend,
+            "scalar": scalars.to_bytes(32, "little") if broadcast else None}
 
 
 def check_arg(check, who):

@@ -428,6 +428,32 @@ static napi_value CheckPoints(napi_env env, napi_callback_info info) {
   return res;
 }
 
+/* mulPoints(ctx, pointsHandle, firstPoint, scalarsHandle | 32-byte Buffer, firstScalar, addendHandle (0 = none),
+   firstAddend, n) -> handle of a new point set, record i = [s_i] P_i (+ Q_i)  (msmz_points_mul; a Buffer is the one
+   scalar, little-endian, for every point) */
+static napi_value MulPoints(napi_env env, napi_callback_info info) {
+  size_t argc = 8; napi_value argv[8];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  msmz_ctx* ctx; if (argc < 8 || !get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "mulPoints");
+  msmz_mul m; memset(&m, 0, sizeof(m));
+  uint64_t n;
+  if (!get_u64(env, argv[1], &m.points_handle) || !get_u64(env, argv[2], &m.first_p) || !get_u64(env, argv[4], &m.first_s) ||
+      !get_u64(env, argv[5], &m.addend_handle) || !get_u64(env, argv[6], &m.first_q) || !get_u64(env, argv[7], &n))
+    return throw_status(env, MSMZ_ERR_ARG, "mulPoints");
+  bool isbuf = false; napi_is_buffer(env, argv[3], &isbuf);
+  if (isbuf) {
+    void* s; size_t slen;
+    if (napi_get_buffer_info(env, argv[3], &s, &slen) != napi_ok || slen != 32) return throw_status(env, MSMZ_ERR_ARG, "mulPoints");
+    m.scalar = (const uint8_t*)s;
+  } else if (!get_u64(env, argv[3], &m.scalars_handle) || m.scalars_handle == 0) {
+    return throw_status(env, MSMZ_ERR_ARG, "mulPoints");
+  }
+  uint64_t h = 0;
+  int st = msmz_points_mul(ctx, &m, n, &h);
+  if (st) return throw_status(env, st, "msmz_points_mul");
+  return make_handle(env, h);
+}
+
 static napi_value PointAdd(napi_env env, napi_callback_info info) {
   size_t argc = 4; napi_value argv[4];
   NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -464,7 +490,8 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"importScalars", ImportScalars}, {"importPoints", ImportPoints},
       {"randomPoints", RandomPoints}, {"randomScalars", RandomScalars}, {"downloadPoints", DownloadPoints},
       {"downloadScalars", DownloadScalars}, {"free", Free}, {"msm", Msm}, {"msmBatch", MsmBatch},
-      {"precomputePoints", PrecomputePoints}, {"precomputedInfo", PrecomputedInfo}, {"checkPoints", CheckPoints}, {"pointAdd", PointAdd}, {"feBytes", FeBytes}};
+      {"precomputePoints", PrecomputePoints}, {"precomputedInfo", PrecomputedInfo}, {"checkPoints", CheckPoints},
+      {"mulPoints", MulPoints}, {"pointAdd", PointAdd}, {"feBytes", FeBytes}};
   for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); i++) {
     napi_value f;
     if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;
