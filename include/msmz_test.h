@@ -5,8 +5,9 @@
  * entry points give the parity tests the same granularity on the device: each one runs ONE device routine of the
  * MSM pipeline, or one phase of the engine (the bucket sort, the tree-round schedule, the bucket reduction), on
  * caller-supplied inputs and returns its raw output.  They are not part of the drop-in boundary and
- * never take part in an MSM.  Statuses and conventions as in msmz.h; on a multi-device context they use its first
- * engine.
+ * never take part in an MSM (two pairs only steer and count one: msmz_test_set_glv_bits / _retries and
+ * msmz_test_set_limits / _passes make ordinary inputs take the engine's rare host paths).  Statuses and conventions
+ * as in msmz.h; on a multi-device context they use its first engine.
  *
  * Field elements travel as fe_bytes little-endian bytes holding a Montgomery residue in the engine's memory format
  * (radix R = 2^392 for the 377/381-bit fields, 2^261 for the 255-bit ones).  They are lazily reduced: the field ops
@@ -63,6 +64,20 @@ int msmz_test_field_limbs(msmz_ctx* ctx, int op, const int32_t* a, const int32_t
  * redone MSM must still equal the oracle.  msmz_test_retries = number of MSMs (per-engine passes) redone so far. */
 int msmz_test_set_glv_bits(msmz_ctx* ctx, int bits);
 int msmz_test_retries(msmz_ctx* ctx);
+/* The engine cuts a call into several device pipelines at two size limits, which ordinary test inputs never reach:
+ * one index-range pass sorts at most 2^24 (half-)scalars, the partial sums of the passes folded on the host, and one
+ * batched pass takes at most 2^26 entries, a longer batch running as consecutive sub-batches.
+ * Lower the engine's two size limits for later calls on this context; 0 = the built-in value.
+ *   pass_entries : (half-)scalars one index-range pass takes, 2 .. 2^24 (kMaxEntriesPerPass);
+ *                  with GLV a pass takes pass_entries / 2 points, as with the built-in value.
+ *   batch_entries: entries (problems x K x M) one batched pass takes, 1 .. 2^26 (kMaxBatchEntries).
+ * MSMZ_ERR_ARG outside those ranges. The limits can only be lowered. Neither changes a result.  A precomputed set
+ * longer than a lowered pass limit is not supported (production refuses such sets at 2^24). */
+int msmz_test_set_limits(msmz_ctx* ctx, uint64_t pass_entries, uint64_t batch_entries);
+/* Totals since the context was created (either pointer nullable; a multi-device context: summed over its engines):
+ *   range_passes: iterations of run_problems' range loop (an ordinary single-problem MSM adds 1);
+ *   sub_batches : batched pipelines (more than one problem) that ran to a result (not PER_PROBLEM). */
+int msmz_test_passes(msmz_ctx* ctx, uint64_t* range_passes, uint64_t* sub_batches);
 /* out[i] = op(a[i], b[i]) for i < n; a, b, out: n * fe_bytes */
 int msmz_test_field(msmz_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out);
 /* GLV split of n 32-byte scalars: s0, s1 = magnitudes (16 bytes each), neg = 2 sign bytes per scalar

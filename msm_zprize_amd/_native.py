@@ -118,6 +118,8 @@ EXPORTS = {
     # stage-level test hooks (include/msmz_test.h)
     "msmz_test_set_glv_bits": (C.c_int, [C.c_void_p, C.c_int]),
     "msmz_test_retries": (C.c_int, [C.c_void_p]),
+    "msmz_test_set_limits": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
+    "msmz_test_passes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "msmz_test_field": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_uint64, C.c_char_p]),
     "msmz_test_field_limbs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                         C.c_char_p]),

@@ -824,6 +824,17 @@ class Engine : public IEngine {
     return MSMZ_OK;
   }
   int test_retries() override { return retries_; }
+  int test_set_limits(uint64_t pass_entries, uint64_t batch_entries) override {
+    if (pass_entries != 0 && (pass_entries < 2 || pass_entries > kMaxEntriesPerPass)) return MSMZ_ERR_ARG;
+    if (batch_entries > kMaxBatchEntries) return MSMZ_ERR_ARG;
+    pass_entries_ = pass_entries ? pass_entries : kMaxEntriesPerPass;
+    planner_.k.batch_entries = batch_entries;
+    return MSMZ_OK;
+  }
+  void test_passes(uint64_t* range_passes, uint64_t* sub_batches) override {
+    if (range_passes) *range_passes = range_passes_;
+    if (sub_batches) *sub_batches = sub_batches_;
+  }
   ITestHooks* test_hooks() override { return &hooks_; }
 
   // ------------------------------------------------------------------------------------------ what only the engine calls
@@ -897,7 +908,7 @@ class Engine : public IEngine {
   int run_problems(const Handle& pts, const uint32_t* d_scalars, uint64_t n, uint32_t remaining, const msmz_opts& opt,
                    uint8_t* out, int* out_inf, msmz_log* log, uint32_t* ran) {
     const bool basic = TE || opt.buckets == MSMZ_BUCKETS_PROJECTIVE;
-    const uint64_t per_pass = (opt.glv != 0 && !TE) ? kMaxEntriesPerPass / 2 : kMaxEntriesPerPass;
+    const uint64_t per_pass = (opt.glv != 0 && !TE) ? pass_entries_ / 2 : pass_entries_;
     *ran = 1;
     const uint32_t bs = !basic && opt.reserved[0] != 1 && n <= per_pass && remaining > 1
                             ? planner_.batch_size(n, opt, (uint32_t)pts.n, pts.factor, remaining)
@@ -909,6 +920,7 @@ class Engine : public IEngine {
                                       extra_bits, bs, r);
       });
       if (st || redo != Redo::PER_PROBLEM) {
+        if (!st) sub_batches_++;
         *ran = bs;
         return st;
       }
@@ -917,6 +929,7 @@ class Engine : public IEngine {
     int st = MSMZ_OK;
     for (uint64_t done = 0; done < n && st == MSMZ_OK; done += per_pass) {
       const uint64_t cnt = n - done < per_pass ? n - done : per_pass;
+      range_passes_++;
       const uint32_t* d_points = pts.mem.template as<const uint32_t>() + done * PW_WORDS;
       const uint32_t* d_sc = d_scalars + done * 8;
       int pinf = 0;
@@ -1658,6 +1671,10 @@ class Engine : public IEngine {
   int tail_skip_2d_ = env_int("MSMZ_TAIL_SKIP_2D", 1) > 2 ? 2 : env_int("MSMZ_TAIL_SKIP_2D", 1);
   int batch_b_override_ = env_int("MSMZ_BATCH_B", 0);
   int retries_ = 0;            // MSMs redone with the proven GLV bound (test hook reads it)
+  // (half-)scalars one index-range pass of run_problems takes: kMaxEntriesPerPass unless msmz_test_set_limits lowered
+  // it (the capacity checks keep the constant); what msmz_test_passes reports
+  uint64_t pass_entries_ = kMaxEntriesPerPass;
+  uint64_t range_passes_ = 0, sub_batches_ = 0;
   // window sizes, geometry, sort layout (plan.h), PlanKnobs in declaration order
   Planner<Fr> planner_{{env_int("MSMZ_NO_SPREAD", 0) != 0, env_int("MSMZ_NO_FOLD", 0) != 0,
                         env_int("MSMZ_NO_WINDOW_MODEL", 0) != 0, env_int("MSMZ_ATOMIC_SORT", 0) != 0,

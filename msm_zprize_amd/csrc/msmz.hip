@@ -210,6 +210,14 @@ int msmz_points_mul(msmz_ctx* c, const msmz_mul* m, uint64_t n, uint64_t* h) {
 
 int msmz_test_set_glv_bits(msmz_ctx* c, int bits) { return c ? c->engine->test_set_glv_bits(bits) : MSMZ_ERR_ARG; }
 int msmz_test_retries(msmz_ctx* c) { return c ? c->engine->test_retries() : -1; }
+int msmz_test_set_limits(msmz_ctx* c, uint64_t pass_entries, uint64_t batch_entries) {
+  return c ? c->engine->test_set_limits(pass_entries, batch_entries) : MSMZ_ERR_ARG;
+}
+int msmz_test_passes(msmz_ctx* c, uint64_t* range_passes, uint64_t* sub_batches) {
+  if (!c) return MSMZ_ERR_ARG;
+  c->engine->test_passes(range_passes, sub_batches);
+  return MSMZ_OK;
+}
 int msmz_test_field(msmz_ctx* c, int op, const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out) {
   return c ? c->engine->test_hooks()->test_field(op, a, b, n, out) : MSMZ_ERR_ARG;
 }

@@ -97,6 +97,11 @@ class IEngine {
   // tests (include/msmz_test.h); the stage-level hooks are one engine's (a multi-device context: its first engine's)
   virtual int test_set_glv_bits(int) { return MSMZ_ERR_UNSUPPORTED; }
   virtual int test_retries() { return 0; }
+  virtual int test_set_limits(uint64_t, uint64_t) { return MSMZ_ERR_UNSUPPORTED; }
+  virtual void test_passes(uint64_t* range_passes, uint64_t* sub_batches) {
+    if (range_passes) *range_passes = 0;
+    if (sub_batches) *sub_batches = 0;
+  }
   virtual ITestHooks* test_hooks() = 0;
 };
 
@@ -430,6 +435,25 @@ class MultiEngine : public IEngine {
     int r = 0;
     for (Worker* w : workers_) r += w->eng->test_retries();
     return r;
+  }
+  int test_set_limits(uint64_t pass_entries, uint64_t batch_entries) override {
+    int st = MSMZ_OK;
+    for (Worker* w : workers_) {
+      const int s = w->eng->test_set_limits(pass_entries, batch_entries);
+      if (s && !st) st = s;
+    }
+    return st;
+  }
+  void test_passes(uint64_t* range_passes, uint64_t* sub_batches) override {
+    uint64_t rp = 0, sb = 0;
+    for (Worker* w : workers_) {
+      uint64_t r = 0, s = 0;
+      w->eng->test_passes(&r, &s);
+      rp += r;
+      sb += s;
+    }
+    if (range_passes) *range_passes = rp;
+    if (sub_batches) *sub_batches = sb;
   }
   ITestHooks* test_hooks() override { return workers_[0]->eng->test_hooks(); }
 

@@ -159,6 +159,7 @@ struct PlanKnobs {
   int fb_cap = 0;
   uint32_t s1_override = 0, r2_nc = 0;   // first reduction group, chunks per line of the 2-D reduction (0 = automatic)
   int glv_bits_assumed = 0;       // test hook (msmz_test_set_glv_bits): assumed bit length of a GLV half; 0 = GLV_BITS - 1
+  uint64_t batch_entries = 0;     // test hook (msmz_test_set_limits): entries per sub-batch; 0 = kMaxBatchEntries
 };
 
 template <class Fr>
@@ -490,8 +491,8 @@ struct Planner {
   }
 
   // problems of the next sub-batch over a point set of pts_n points (`factor` copies; <= 1: plain): the window size
-  // depends on the batch size, so the plan is made again until the sub-batch fits kMaxBatchEntries; the remaining
-  // problems are then dealt into equal sub-batches
+  // depends on the batch size, so the plan is made again until the sub-batch fits kMaxBatchEntries (or the lower cap
+  // of k.batch_entries); the remaining problems are then dealt into equal sub-batches
   uint32_t batch_size(uint64_t n, const msmz_opts& opt, uint32_t pts_n, uint32_t factor, uint32_t remaining) const {
     uint32_t bs = remaining;
     for (int it = 0; it < 4 && bs > 1; it++) {
@@ -500,7 +501,8 @@ struct Planner {
         bs = (bs + 1) / 2;
         continue;
       }
-      const uint32_t fit = batch_split(remaining, (uint64_t)pl.K * pl.M, kMaxBatchEntries);
+      const uint32_t fit =
+          batch_split(remaining, (uint64_t)pl.K * pl.M, k.batch_entries ? k.batch_entries : kMaxBatchEntries);
       if (fit >= bs) break;
       bs = fit;
     }

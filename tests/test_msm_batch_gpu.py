@@ -45,6 +45,14 @@ def _enc(scalars):
     return b"".join(int(s).to_bytes(32, "little") for s in scalars)
 
 
+def _sub_batches(curve):
+    """batched pipelines the context ran to a result so far (msmz_test_passes)"""
+    from msm_zprize_amd._native import lib
+    sb = C.c_uint64()
+    assert lib().msmz_test_passes(curve._ctx, None, C.byref(sb)) == 0
+    return sb.value
+
+
 def _loop_resident(curve, vecs, pts, n, opts, safe):
     """msmz_msm_resident once per vector"""
     out = []
@@ -137,8 +145,10 @@ def test_batch_large_split(curves):
         t = prng.sum_of_products_mod(prng.scalars_np(22, n, q, first=k * n), a, q)
         want.append(_strip(c_oracle.scale(c, t, gen)))
     for glv in (0, 1):
+        before = _sub_batches(curve)
         got = [_strip(r) for r in curve.Parallel.msmBatchUnsafe(sc, pts, n, {"glv": glv})]
         assert got == want, glv
+        assert _sub_batches(curve) >= before + 2, glv   # (the split path was taken)
     log = curve.Parallel.lastBatchLog
     assert log.n_entries > B * n   # totals over the batch
     sc.free()

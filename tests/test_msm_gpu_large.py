@@ -54,6 +54,15 @@ def _strip(p):
     return {"x": p["x"], "y": p["y"], "isZero": bool(p.get("isZero", False))}
 
 
+def _range_passes(curve):
+    """index-range passes the context ran so far (msmz_test_passes)"""
+    import ctypes as C
+    from msm_zprize_amd._native import lib
+    rp = C.c_uint64()
+    assert lib().msmz_test_passes(curve._ctx, C.byref(rp), None) == 0
+    return rp.value
+
+
 def test_config2_bls12_377_2e20_no_glv_affine(mod):
     """BASELINE configs[1]: BLS12-377 G1, 2^20, no GLV, affine buckets -- plus the variants"""
     curve = mod.Weierstrass.create(mod.curves.bls12377Params)
@@ -148,9 +157,12 @@ def test_inputs_beyond_one_sorting_pass(mod):
     n = 1 << 25
     pts = curve.Parallel.randomPointsFast(n, 61)
     sc = curve.Parallel.randomScalars(n, 62)
+    before = _range_passes(curve)
     assert curve.Parallel.msmUnsafe(sc, pts, n, False, {"glv": 0})["result"] == _expected("bls12-377", 61, 62, n)
+    assert _range_passes(curve) == before + 2
     h = 1 << 24
     assert curve.Parallel.msmUnsafe(sc, pts, h, False, {"glv": 1})["result"] == _expected("bls12-377", 61, 62, h)
+    assert _range_passes(curve) == before + 4   # (each call ran exactly two index-range passes)
     pts.free(); sc.free()
     curve.close()
 

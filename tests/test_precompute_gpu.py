@@ -239,12 +239,14 @@ def test_precomputed_batch(curves, label, B):
 
 
 def test_precomputed_batch_split(curves):
-    """B = 64 vectors of 2^16 scalars over a precomputed set: more entries than one batched pass takes (sub-batches);
-    closed form"""
+    """B = 69 vectors of 2^16 scalars over a precomputed set: more entries than one batched pass takes (sub-batches of
+    35 and 34 vectors); closed form.  (The set is built with c = 17, K = 15 windows, so up to 68 vectors are
+    68 x 15 x 2^16 <= 2^26 entries and run as ONE pipeline: the 64 vectors this test used to run never split, which
+    the sub-batch counter showed.)"""
     curve = curves("bls12-377")
     c = P.CURVES["bls12-377"]
     q = c["order"]
-    n, B = 1 << 16, 64
+    n, B = 1 << 16, 69
     pts = curve.Parallel.randomPointsFast(n, 21)
     sc = curve.Parallel.randomScalars(B * n, 22)
     a = prng.multipliers_np(21, n)
@@ -252,7 +254,13 @@ def test_precomputed_batch_split(curves):
     want = [_strip(c_oracle.scale(c, prng.sum_of_products_mod(prng.scalars_np(22, n, q, first=k * n), a, q), gen))
             for k in range(B)]
     pre = curve.Parallel.precomputePoints(pts, n, {"glv": 0}, 0)
+    from msm_zprize_amd._native import lib
+    L = lib()
+    sb0, sb1 = C.c_uint64(), C.c_uint64()
+    assert L.msmz_test_passes(curve._ctx, None, C.byref(sb0)) == 0
     assert [_strip(r) for r in curve.Parallel.msmBatchUnsafe(sc, pre, n)] == want
+    assert L.msmz_test_passes(curve._ctx, None, C.byref(sb1)) == 0
+    assert sb1.value >= sb0.value + 2   # (sub-batches: the split path was taken)
     pre.free()
     sc.free()
     pts.free()

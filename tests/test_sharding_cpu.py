@@ -72,17 +72,43 @@ def test_shard_range_partition():
             assert max(sizes) - min(sizes) <= 1
 
 
-def test_point_add_host_only():
-    """msmz_point_add is pure host code: works without a GPU, matches the oracle's group law"""
+@pytest.mark.parametrize("label", ["bls12-377", "pallas", "bls12-381", "ed-on-bls12-377"])
+def test_point_add_host_only(label):
+    """msmz_point_add is pure host code: works without a GPU, matches the oracle's group law on every curve.  It is the
+    fold of the engine's partial sums (index-range passes, devices), so the cases are the fold's: P + Q, the doubling
+    P + P, P + (-P), and the identity on either side and on both.  Twisted Edwards has no infinity flag: its identity is
+    the point (0, 1), and a null operand is refused."""
+    import ctypes as C
     from msm_zprize_amd import curves, sharding
+    from msm_zprize_amd._native import lib
     from oracle import bigint_ref as B, params as P
-    c = P.BLS12_377
-    A = B.AffineWeierstrass(c)
-    G = A.one
-    p2, p3 = A.scale(2, G), A.scale(3, G)
-    d = lambda t: {"x": t[0], "y": t[1], "isZero": t[2]}
-    pc = curves.bls12377Params
-    assert sharding.point_add(pc, d(G), d(p2)) == d(p3)
-    assert sharding.point_add(pc, d(G), d(G)) == d(p2)
-    assert sharding.point_add(pc, d(G), d(A.negate(G)))["isZero"]
-    assert sharding.point_add(pc, sharding.identity(pc), d(p3)) == d(p3)
+    c, pc = P.CURVES[label], curves.BY_LABEL[label]
+    rng = random.Random(label)
+    k1, k2 = rng.randrange(1, c["order"]), rng.randrange(1, c["order"])
+    if c["kind"] == "weierstrass":
+        A = B.AffineWeierstrass(c)
+        d = lambda t: {"x": t[0], "y": t[1], "isZero": t[2]}
+        p1, p2, zero = A.scale(k1, A.one), A.scale(k2, A.one), A.zero
+        add, neg = A.add, A.negate
+    else:
+        T = B.TwistedEdwards(c)
+        d = lambda t: dict(zip("xy", T.to_affine(t)), isZero=False)
+        p1, p2, zero = T.scale(k1, T.one), T.scale(k2, T.one), T.zero
+        add, neg = T.add, T.negate
+        assert d(zero) == sharding.identity(pc) == {"x": 0, "y": 1, "isZero": False}
+    cases = [(p1, p2), (p2, p1), (p1, p1), (p1, neg(p1)), (neg(p2), p2), (zero, p1), (p1, zero), (zero, zero)]
+    for a, b in cases:
+        assert sharding.point_add(pc, d(a), d(b)) == d(add(a, b)), (label, cases.index((a, b)))
+    assert sharding.point_add(pc, d(p1), d(neg(p1))) == sharding.identity(pc)
+    assert sharding.point_add(pc, sharding.identity(pc), d(p2)) == d(p2)
+    # null operands: Weierstrass takes one with its infinity flag and refuses one without; twisted Edwards refuses both
+    fb = pc["fe_bytes"]
+    xy = int(d(p1)["x"]).to_bytes(fb, "little") + int(d(p1)["y"]).to_bytes(fb, "little")
+    out, inf = C.create_string_buffer(2 * fb), C.c_int()
+    assert lib().msmz_point_add(pc["curve_id"], None, 0, xy, 0, out, C.byref(inf)) == 1   # MSMZ_ERR_ARG
+    assert lib().msmz_point_add(pc["curve_id"], xy, 0, None, 0, out, C.byref(inf)) == 1
+    want = 1 if c["kind"] == "twisted-edwards" else 0
+    assert lib().msmz_point_add(pc["curve_id"], None, 1, xy, 0, out, C.byref(inf)) == want
+    assert lib().msmz_point_add(pc["curve_id"], xy, 0, None, 1, out, C.byref(inf)) == want
+    if not want:
+        assert out.raw == xy and inf.value == 0
