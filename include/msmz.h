@@ -211,6 +211,36 @@ int msmz_msm_batch_resident(msmz_ctx* ctx, uint64_t points_handle, uint64_t scal
                             uint32_t batch, const msmz_opts* opts, uint8_t* out_xy_le, int* out_is_inf,
                             msmz_log* log /* nullable */);
 
+/* Segmented MSM: every problem has its own range of ONE resident point set and ONE resident scalar
+ * set,
+ *     out_k = sum_{i < n_k} scalar[first_s_k + i] * P[first_p_k + i],   k = 0 .. n_segs - 1
+ * -- the L = <a_lo, G_hi> and R = <a_hi, G_lo> of an IPA round over the halves of one SRS, or commitments to columns of
+ * different lengths against one SRS.  Segments may overlap or repeat.  Only the base points of a set are addressed: the
+ * endomorphism images and the copies of a precomputed set are reached by the engine.  out_xy_le: n_segs * 2 * fe_bytes,
+ * out_is_inf: n_segs ints, in the caller's order, as msmz_msm_batch lays them out.  Options mean what they mean for
+ * msmz_msm_batch_resident (reserved[1], safe and timing included); log (nullable) describes the whole call, totals merged
+ * as the batch merges them.  One segment {0, 0, n} returns exactly the bytes and status of msmz_msm_resident; n_segs
+ * segments {0, k n, n} exactly those of msmz_msm_batch_resident.
+ * How it runs: the segments are dealt into length classes (same floor(log2 n_k)).  On Weierstrass curves with
+ * batched-affine buckets the segments of a class go through ONE device pipeline, sized for the class's longest segment,
+ * in consecutive sub-batches as a batch; twisted Edwards, MSMZ_BUCKETS_PROJECTIVE, reserved[0] = 1, a length beyond one
+ * sort pass and a class of one run segment by segment.  Same results either way.
+ * MSMZ_ERR_ARG, before any launch: a null ctx, segs, out_xy_le or out_is_inf; n_segs == 0; a segment with n == 0; an
+ * unknown handle or one of the wrong kind; a range beyond its set (tested without wrap-around); a precomputed handle:
+ * first_p + n beyond the n it was built for, or options that contradict it (as msmz_msm).  MSMZ_ERR_RANGE: a scalar >= q
+ * (or >= 2^reserved[1]) inside any segment fails the whole call, the context stays usable; a bad scalar no segment covers
+ * is not read.  MSMZ_ERR_DEGENERATE: as msmUnsafe.  MSMZ_ERR_UNSUPPORTED: a multi-device context (sets are dealt in blocks
+ * of 2^16 records, and a range is not a prefix of a device's share: the stance of msmz_import_scalars_into), and on a
+ * precomputed handle the combinations unsupported in every MSM over one. */
+typedef struct msmz_segment {
+  uint64_t first_p;   /* first base point of the problem */
+  uint64_t first_s;   /* first scalar of the problem */
+  uint64_t n;         /* its length, >= 1 */
+} msmz_segment;
+int msmz_msm_segments(msmz_ctx* ctx, uint64_t points_handle, uint64_t scalars_handle, const msmz_segment* segs,
+                      uint32_t n_segs, const msmz_opts* opts, uint8_t* out_xy_le, int* out_is_inf,
+                      msmz_log* log /* nullable */);
+
 /* Fixed-base precomputation of a resident point set.  The new handle holds `factor` copies of the
  * first n points of points_handle, copy j = 2^(c j) * P_i, so that window k of every scalar adds into bucket set
  * floor(k / factor) with copy k mod factor: ceil(K / factor) bucket reductions per MSM instead of K, and a Horner with

@@ -40,6 +40,9 @@ export interface ParallelApi {
             options?: { addend?: DeviceArray | null; firstPoint?: number; firstScalar?: number; firstAddend?: number }): Promise<DeviceArray>;
   msmBatch(scalarsList: DeviceArray | Uint8Array[], points: DeviceArray, n: number, options?: MsmOptions & { batch?: number }): Promise<BigintPoint[]>;
   msmBatchUnsafe(scalarsList: DeviceArray | Uint8Array[], points: DeviceArray, n: number, options?: MsmOptions & { batch?: number }): Promise<BigintPoint[]>;
+  /** one MSM per segment [firstPoint, firstScalar, n] of one resident scalar array and one resident point array */
+  msmSegments(scalars: DeviceArray, points: DeviceArray, segments: [number, number, number][], options?: MsmOptions): Promise<BigintPoint[]>;
+  msmSegmentsUnsafe(scalars: DeviceArray, points: DeviceArray, segments: [number, number, number][], options?: MsmOptions): Promise<BigintPoint[]>;
   msmProjective?(scalars: DeviceArray | Uint8Array, points: DeviceArray, n: number, options?: MsmOptions): Promise<MsmResult>;
 }
 export interface MsmCurve {

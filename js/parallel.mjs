@@ -227,6 +227,41 @@ function createCurve(params, kind) {
     return out;
   }
 
+  // One MSM per segment (msmz_msm_segments): `segments` is an array of [firstPoint, firstScalar, n]; result k =
+  // sum_{i < n} scalars[firstScalar + i] * points[firstPoint + i] over ONE resident scalar array and ONE resident point
+  // array (plain or precomputed).  Checked here, before anything reaches the device.
+  async function msmSegmentsCommon(scalars, points, segments, options, safe) {
+    options = options || {};
+    const opts = {
+      c: options.c || 0,
+      glv: options.glv !== undefined ? Number(options.glv) : te ? 0 : -1,
+      safe: options.useSafeAdditions !== undefined ? Number(options.useSafeAdditions) : safe,
+      buckets: options.buckets || 0,
+      reduceAffine: options.reduceAffine ? 1 : 0,
+      scalarBits: scalarBitsArg(options, "msmSegments"),
+    };
+    if (!(points instanceof DeviceArray) || (points.kind !== "points" && points.kind !== "precomputed"))
+      throw TypeError("msmSegments: `points` is a resident point array (plain or precomputed)");
+    if (!(scalars instanceof DeviceArray) || scalars.kind !== "scalars")
+      throw TypeError("msmSegments: `scalars` is a resident scalar array; host scalars are uploaded first");
+    if (!Array.isArray(segments) || segments.length === 0 || segments.length >= 2 ** 32)
+      throw Error("msmSegments: `segments` is a non-empty array of [firstPoint, firstScalar, n]");
+    const table = Buffer.alloc(24 * segments.length);
+    segments.forEach((seg, k) => {
+      if (!Array.isArray(seg) || seg.length !== 3) throw TypeError(`msmSegments: segment ${k} is not [firstPoint, firstScalar, n]`);
+      const [firstPoint, firstScalar, n] = seg;
+      for (const v of seg) if (!Number.isInteger(v) || v < 0) throw Error(`msmSegments: segment ${k}: ${v}`);
+      if (n < 1) throw Error(`msmSegments: segment ${k}: n = ${n}`);
+      if (firstPoint + n > points.n) throw Error(`msmSegments: segment ${k}: points [${firstPoint}, +${n}) of a set of ${points.n}`);
+      if (firstScalar + n > scalars.n) throw Error(`msmSegments: segment ${k}: scalars [${firstScalar}, +${n}) of a set of ${scalars.n}`);
+      seg.forEach((v, j) => table.writeBigUInt64LE(BigInt(v), 24 * k + 8 * j));
+    });
+    const r = N.msmSegments(ctx, points.handle, scalars.handle, table, segments.length, fb, opts);
+    const out = [];
+    for (let k = 0; k < segments.length; k++) out.push(decodePoint(r.xy, 2 * fb * k, r.isInf[k]));
+    return out;
+  }
+
   const Parallel = {
     /** fixed-base precomputation of the first n resident points (include/msmz.h msmz_precompute_points): a DeviceArray
      * of kind "precomputed" that msm / msmUnsafe / msmBatch / msmBatchUnsafe take in place of the points (same results).
@@ -292,6 +327,10 @@ function createCurve(params, kind) {
     /** batched MSM: B scalar vectors against one point set (include/msmz.h msmz_msm_batch); safe additions */
     msmBatch: (scalarsList, points, n, options) => msmBatchCommon(scalarsList, points, n, options, 1),
     msmBatchUnsafe: (scalarsList, points, n, options) => msmBatchCommon(scalarsList, points, n, options, 0),
+    /** segmented MSM: every problem its own range [firstPoint, firstScalar, n] of one point set and one scalar set
+     * (include/msmz.h msmz_msm_segments), e.g. the L and R of an IPA round: [[n, 0, n], [0, n, n]]; safe additions */
+    msmSegments: (scalars, points, segments, options) => msmSegmentsCommon(scalars, points, segments, options, 1),
+    msmSegmentsUnsafe: (scalars, points, segments, options) => msmSegmentsCommon(scalars, points, segments, options, 0),
     /** curve-random.ts:14-92, seeded: point i = splitmix64(seed, i) * G */
     async randomPointsFast(n, { seed = 0x6d736d7an } = {}) {
       return DeviceArray.make(curve, N.randomPoints(ctx, n, BigInt(seed)), n, "points");

@@ -46,6 +46,10 @@ class MsmzMul(C.Structure):   # msmz_mul (include/msmz.h): out_i = [s_i] P_i (+ 
                 ("first_s", C.c_uint64), ("scalar", C.c_char_p), ("addend_handle", C.c_uint64), ("first_q", C.c_uint64)]
 
 
+class MsmzSegment(C.Structure):   # msmz_segment (include/msmz.h): one problem of msmz_msm_segments
+    _fields_ = [("first_p", C.c_uint64), ("first_s", C.c_uint64), ("n", C.c_uint64)]
+
+
 class MsmzTestReduceArgs(C.Structure):   # msmz_test_reduce_args (include/msmz_test.h)
     _fields_ = [("mode", C.c_int32), ("c", C.c_int32), ("nsets", C.c_uint32), ("n_in", C.c_uint32),
                 ("nc", C.c_uint32), ("tail_n", C.c_uint32), ("quad16_max", C.c_uint32), ("pairsum_x4_max", C.c_uint32),
@@ -106,6 +110,8 @@ EXPORTS = {
                                  C.c_char_p, C.POINTER(C.c_int), C.POINTER(MsmzLog)]),
     "msmz_msm_batch_resident": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                           C.POINTER(MsmzOpts), C.c_char_p, C.POINTER(C.c_int), C.POINTER(MsmzLog)]),
+    "msmz_msm_segments": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(MsmzSegment), C.c_uint32,
+                                    C.POINTER(MsmzOpts), C.c_char_p, C.POINTER(C.c_int), C.POINTER(MsmzLog)]),
     "msmz_precompute_points": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(MsmzOpts), C.c_uint32,
                                          C.POINTER(C.c_uint64)]),
     "msmz_precomputed_info": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),

@@ -206,6 +206,9 @@ class Engine : public IEngine {
     // hipSetDevice -- not lazily inside the first MSM and not on every MSM.  static + dynamic LDS is checked against
     // the device's per-workgroup LDS, so a kernel that cannot launch fails context creation with its name.
     if ((st = raise_lds_limit((const void*)k_fine, "k_fine", kFineLds))) return st;
+    if constexpr (!TE) {
+      if ((st = raise_lds_limit((const void*)k_fine_seg, "k_fine_seg", kFineLds))) return st;
+    }
     if ((st = raise_sort_limits<false, 0>()) || (st = raise_sort_limits<false, 16>()) || (st = raise_sort_limits<false, 17>())) return st;
     if constexpr (Fr::HAS_GLV) {
       if ((st = raise_sort_limits<true, 0>()) || (st = raise_sort_limits<true, 16>())) return st;
@@ -217,7 +220,12 @@ class Engine : public IEngine {
   int raise_sort_limits() {
     int st;
     if ((st = raise_lds_limit((const void*)k_coarse<Fr, GLV, C>, GLV ? "k_coarse<glv>" : "k_coarse", kCoarseLdsMax))) return st;
-    return raise_lds_limit((const void*)k_hist<Fr, GLV, C>, GLV ? "k_hist<glv>" : "k_hist", kHistLdsMax);
+    if ((st = raise_lds_limit((const void*)k_hist<Fr, GLV, C>, GLV ? "k_hist<glv>" : "k_hist", kHistLdsMax))) return st;
+    if constexpr (!TE) {   // the segmented variants (msm_segments: the batched pipeline is Weierstrass only)
+      if ((st = raise_lds_limit((const void*)k_coarse_seg<Fr, GLV, C>, GLV ? "k_coarse_seg<glv>" : "k_coarse_seg", kCoarseLdsMax))) return st;
+      if ((st = raise_lds_limit((const void*)k_hist_seg<Fr, GLV, C>, GLV ? "k_hist_seg<glv>" : "k_hist_seg", kHistLdsMax))) return st;
+    }
+    return MSMZ_OK;
   }
   // dynamic LDS the sort kernels may be launched with (sort_phase never asks for more: SORT_MAX_BINS caps nbins)
   static constexpr size_t kFineLds = ((size_t)(1 << FINE_MAX_BITS) + FINE_STAGE) * 4;
@@ -275,6 +283,7 @@ class Engine : public IEngine {
     if (h_meta_) (void)hipHostFree(h_meta_);
     if (h_res_) (void)hipHostFree(h_res_);
     if (h_check_) (void)hipHostFree(h_check_);
+    if (h_segs_) (void)hipHostFree(h_segs_);
     for (hipEvent_t* e : ev_.all())
       if (*e) (void)hipEventDestroy(*e);
     if (import_ev_) (void)hipEventDestroy(import_ev_);
@@ -816,6 +825,58 @@ class Engine : public IEngine {
     return st;
   }
 
+  // msmz_msm_segments: problem k = scalars [first_s, first_s + n) of `sh` times base points [first_p, first_p + n) of `ph`.
+  // The segments are dealt into length classes (segment_classes, multi.h); run_segments decides how each class runs, for
+  // its longest segment; results go back through the permutation, logs are summed as msm_batch sums them.
+  int msm_segments(uint64_t ph, uint64_t sh, const msmz_segment* segs, uint32_t n_segs, const msmz_opts* o, uint8_t* out,
+                   int* out_inf, msmz_log* log) override {
+    auto t_begin = std::chrono::steady_clock::now();
+    if (!segs || !out || !out_inf || n_segs == 0) return MSMZ_ERR_ARG;
+    auto pit = handles_.find(ph), sit = handles_.find(sh);
+    if (pit == handles_.end() || pit->second.kind != 0 || sit == handles_.end() || sit->second.kind != 1) return MSMZ_ERR_ARG;
+    const Handle& pts = pit->second;
+    const Handle& sc = sit->second;
+    std::vector<uint64_t> lens(n_segs);
+    for (uint32_t k = 0; k < n_segs; k++) {
+      const msmz_segment& s = segs[k];   // (no first + n: it can wrap)
+      if (s.n == 0 || s.first_p > pts.n || s.n > pts.n - s.first_p || s.first_s > sc.n || s.n > sc.n - s.first_s)
+        return MSMZ_ERR_ARG;
+      lens[k] = s.n;
+    }
+    msmz_opts opt;
+    if (int st = resolve_opts(pts, o, &opt)) return st;
+    MSMZ_HIP(hipSetDevice(device_));
+    if (log) memset(log, 0, sizeof(*log));
+    std::vector<uint32_t> order, starts;
+    segment_classes(lens.data(), n_segs, &order, &starts);
+    const bool fits32 = !(sc.n >> 32);   // the descriptors of the batched pipeline hold 32-bit offsets
+    int st = MSMZ_OK;
+    bool first = true;
+    for (size_t ci = 0; ci + 1 < starts.size() && st == MSMZ_OK; ci++) {
+      const uint32_t lo = starts[ci], hi = starts[ci + 1];
+      uint64_t n_max = 0;
+      for (uint32_t j = lo; j < hi; j++) n_max = lens[order[j]] > n_max ? lens[order[j]] : n_max;
+      msmz_opts copt = opt;
+      if (copt.glv < 0) copt.glv = pts.has_endo && planner_.default_glv(n_max, copt.reserved[1]) ? 1 : 0;   // (as msm_batch, per class)
+      for (uint32_t done = lo; done < hi && st == MSMZ_OK;) {
+        msmz_log plog;
+        memset(&plog, 0, sizeof(plog));
+        uint32_t ran = 0;
+        st = run_segments(pts, sc.mem.template as<const uint32_t>(), segs, order.data() + done, hi - done, n_max, fits32, copt,
+                          out, out_inf, log ? &plog : nullptr, &ran);
+        if (st) break;
+        if (log) merge_log(log, plog, first, LogMerge::SEQUENTIAL);
+        first = false;
+        done += ran;
+      }
+    }
+    if (log) {
+      log->stage_ms[MSMZ_ST_TOTAL] =
+          std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    }
+    return st;
+  }
+
   // ------------------------------------------------------------------ tests (msmz_test.h; the stage hooks: test_hooks.h)
   int test_set_glv_bits(int bits) override {
     if (!Fr::HAS_GLV) return MSMZ_ERR_UNSUPPORTED;
@@ -905,8 +966,9 @@ class Engine : public IEngine {
   //  - else the first problem alone over consecutive index ranges of at most one sort pass (2^24 entries; 2^23 points
   //    with GLV) whose partial sums are folded on the host -- the same additivity the multi-GPU split uses -- each range
   //    with batched-affine buckets (Weierstrass) or msmBasic (projective buckets, twisted Edwards).
+  // first_p (a segment run alone, remaining = 1): the problem's points start at record first_p of the set.
   int run_problems(const Handle& pts, const uint32_t* d_scalars, uint64_t n, uint32_t remaining, const msmz_opts& opt,
-                   uint8_t* out, int* out_inf, msmz_log* log, uint32_t* ran) {
+                   uint8_t* out, int* out_inf, msmz_log* log, uint32_t* ran, uint64_t first_p = 0) {
     const bool basic = TE || opt.buckets == MSMZ_BUCKETS_PROJECTIVE;
     const uint64_t per_pass = (opt.glv != 0 && !TE) ? pass_entries_ / 2 : pass_entries_;
     *ran = 1;
@@ -930,7 +992,7 @@ class Engine : public IEngine {
     for (uint64_t done = 0; done < n && st == MSMZ_OK; done += per_pass) {
       const uint64_t cnt = n - done < per_pass ? n - done : per_pass;
       range_passes_++;
-      const uint32_t* d_points = pts.mem.template as<const uint32_t>() + done * PW_WORDS;
+      const uint32_t* d_points = pts.mem.template as<const uint32_t>() + (first_p + done) * PW_WORDS;
       const uint32_t* d_sc = d_scalars + done * 8;
       int pinf = 0;
       msmz_log plog;
@@ -952,6 +1014,55 @@ class Engine : public IEngine {
     }
     return st;
   }
+
+  // The next segments of one length class (order[0 .. remaining): indices into segs; n_max: the class's longest): the
+  // decision of run_problems, taken for n_max.  Either a sub-batch of them in ONE batched pipeline planned for n_max, the
+  // kernels reading each problem's offsets and length from a descriptor table (SegDesc; filled from pinned memory in
+  // stream order, no host wait) -- or the first segment alone through the range loop of run_problems, the base pointers
+  // advanced to it.  Results go to out / out_inf at the segments' own indices.  batchable: the offsets fit the table.
+  int run_segments(const Handle& pts, const uint32_t* d_scalars, const msmz_segment* segs, const uint32_t* order,
+                   uint32_t remaining, uint64_t n_max, bool batchable, const msmz_opts& opt, uint8_t* out, int* out_inf,
+                   msmz_log* log, uint32_t* ran) {
+    const bool basic = TE || opt.buckets == MSMZ_BUCKETS_PROJECTIVE;
+    const uint64_t per_pass = (opt.glv != 0 && !TE) ? pass_entries_ / 2 : pass_entries_;
+    *ran = 1;
+    const uint32_t most = remaining < kMaxSegProblems ? remaining : kMaxSegProblems;
+    const uint32_t bs = !basic && opt.reserved[0] != 1 && n_max <= per_pass && most > 1 && batchable
+                            ? planner_.batch_size(n_max, opt, (uint32_t)pts.n, pts.factor, most)
+                            : 1;
+    if (bs > 1) {
+      int st;
+      if ((st = ensure_host_segs(bs)) || (st = segs_.ensure((size_t)bs * sizeof(SegDesc)))) return st;
+      for (uint32_t p = 0; p < bs; p++) {
+        const msmz_segment& s = segs[order[p]];
+        h_segs_[p] = SegDesc{(uint32_t)s.first_s, (uint32_t)s.first_p, (uint32_t)s.n};
+      }
+      MSMZ_HIP(hipMemcpyAsync(segs_.p, h_segs_, (size_t)bs * sizeof(SegDesc), hipMemcpyHostToDevice, stream_));
+      std::vector<uint8_t> res((size_t)bs * RW * 4);
+      std::vector<int> inf(bs, 0);
+      Redo redo = Redo::NONE;
+      st = glv_retry(&redo, [&](int extra_bits, Redo* r) {
+        return msm_weierstrass_affine(pts, pts.mem.template as<const uint32_t>(), d_scalars, n_max, opt, res.data(),
+                                      inf.data(), log, extra_bits, bs, r, segs_.as<const SegDesc>());
+      });
+      if (st || redo != Redo::PER_PROBLEM) {
+        if (!st) {
+          sub_batches_++;
+          for (uint32_t p = 0; p < bs; p++) {
+            memcpy(out + (size_t)order[p] * RW * 4, res.data() + (size_t)p * RW * 4, RW * 4);
+            out_inf[order[p]] = inf[p];
+          }
+        }
+        *ran = bs;
+        return st;
+      }
+    }
+    const msmz_segment& s = segs[order[0]];
+    uint32_t one = 0;
+    return run_problems(pts, d_scalars + s.first_s * 8, s.n, 1, opt, out + (size_t)order[0] * RW * 4, out_inf + order[0], log,
+                        &one, s.first_p);
+  }
+  static constexpr uint32_t kMaxSegProblems = 32768;   // problems of one pipeline = gridDim.y of the sort kernels
 
   // attempt(extra_bits, &redo): a GLV half longer than the assumed 127 bits (k_hist flags it) redoes the MSM with
   // windows for the PROVEN bound (Fr::GLV_PROVEN_BITS, tools/gen_constants.py), which no half can exceed -- a second
@@ -986,7 +1097,9 @@ class Engine : public IEngine {
   // round trip.  pl.nprob > 1 (batched MSM): problem p reads scalars [p n, (p + 1) n); its bins follow problem p - 1's in
   // ONE exclusive scan, so refs_ / off_ come out as one dense sort of pl.nprob * nb buckets.  The two-level sort only.
   // `sl`: the planner's sort layout of pl; copy_stride: records per copy of a precomputed point set.
-  int sort_phase(const Plan& pl, const SortLayout& sl, const uint32_t* d_scalars, Run& run, uint32_t copy_stride) {
+  // d_segs (segmented MSM): problem p's descriptor; d_scalars is then the whole set, pl.n the longest segment.
+  int sort_phase(const Plan& pl, const SortLayout& sl, const uint32_t* d_scalars, Run& run, uint32_t copy_stride,
+                 const SegDesc* d_segs = nullptr) {
     const uint32_t n = pl.n, M = pl.M, nb = pl.nb, nblocks = pl.nblocks, P = pl.nprob;
     const int c = pl.c, K = pl.K;
     int st;
@@ -995,6 +1108,7 @@ class Engine : public IEngine {
     MsmMeta* d_meta = meta_.as<MsmMeta>();
     MSMZ_HIP(hipMemsetAsync(d_meta, 0, sizeof(MsmMeta), stream_));
     if (!sl.two_level && (P > 1 || pl.F > 1)) return MSMZ_ERR_ARG;   // (msm_batch only batches plans the two-level sort handles)
+    if (d_segs && (TE || !sl.two_level)) return MSMZ_ERR_ARG;         // (run_segments: the batched pipeline only)
     const uint32_t nbins = sl.nbins, fbins = sl.fbins;
     const uint32_t n_half = pl.glv ? n : 0xffffffffu;
     if (sl.two_level) {
@@ -1014,6 +1128,18 @@ class Engine : public IEngine {
       auto launch_sort = [&](auto glvc, auto cc, bool coarse) {
         constexpr bool G = decltype(glvc)::value;
         constexpr int C = decltype(cc)::value;
+        if constexpr (!TE) {
+          if (d_segs) {
+            if (!coarse)
+              hipLaunchKernelGGL((k_hist_seg<Fr, G, C>), dim3(tiles, P), dim3(COARSE_T), (size_t)nbins * 4, stream_, d_counts,
+                                 tilecnt_.as<uint16_t>(), tileoff_.as<uint32_t>(), d_meta, d_scalars, g, nbins, d_segs);
+            else
+              hipLaunchKernelGGL((k_coarse_seg<Fr, G, C>), dim3(tiles, P), dim3(COARSE_T), (size_t)2 * nbins * 4, stream_,
+                                 packed_.as<uint32_t>(), tileoff_.as<uint32_t>(), bins_.as<uint32_t>(),
+                                 tilecnt_.as<uint16_t>(), d_scalars, g, nbins, d_segs);
+            return;
+          }
+        }
         if (!coarse)
           hipLaunchKernelGGL((k_hist<Fr, G, C>), dim3(tiles, P), dim3(COARSE_T), (size_t)nbins * 4, stream_, d_counts,
                              tilecnt_.as<uint16_t>(), tileoff_.as<uint32_t>(), d_meta, d_scalars, g, nbins);
@@ -1060,9 +1186,14 @@ class Engine : public IEngine {
       MSMZ_HIP(hipGetLastError());
       {
         const size_t lds = kFineLds;
-        hipLaunchKernelGGL(k_fine, dim3(fbins, P), dim3(FINE_T), lds, stream_, refs_.as<uint32_t>(), off_.as<uint32_t>(),
-                           &d_meta->max_bucket, packed_.as<uint32_t>(), bins_.as<uint32_t>(), g.fb, g.fbt, sl.fine_top,
-                           fbins, g.idx_bits, n_half, pl.endo_delta, g.F, g.mbits, copy_stride);
+        if (d_segs)
+          hipLaunchKernelGGL(k_fine_seg, dim3(fbins, P), dim3(FINE_T), lds, stream_, refs_.as<uint32_t>(),
+                             off_.as<uint32_t>(), &d_meta->max_bucket, packed_.as<uint32_t>(), bins_.as<uint32_t>(), g.fb,
+                             g.fbt, sl.fine_top, fbins, g.idx_bits, n_half, pl.endo_delta, g.F, g.mbits, copy_stride, d_segs);
+        else
+          hipLaunchKernelGGL(k_fine, dim3(fbins, P), dim3(FINE_T), lds, stream_, refs_.as<uint32_t>(), off_.as<uint32_t>(),
+                             &d_meta->max_bucket, packed_.as<uint32_t>(), bins_.as<uint32_t>(), g.fb, g.fbt, sl.fine_top,
+                             fbins, g.idx_bits, n_half, pl.endo_delta, g.F, g.mbits, copy_stride);
       }
 #ifdef MSMZ_TRACE
       // development aid: workgroup time stamps of k_coarse / k_fine (tools/wg_timeline.py)
@@ -1355,9 +1486,11 @@ class Engine : public IEngine {
   // at out + p 2 FE_BYTES / out_inf[p]): one sort, one plan, one train of tree rounds and one two-dimensional reduction
   // over nprob * Keff bucket sets.  *redo: Redo::PER_PROBLEM when this plan does not batch (the two-level sort only),
   // Redo::PROVEN_BITS when a GLV half is longer than the windows were sized for (glv_retry).
+  // d_segs (run_segments): the nprob problems are segments of the scalar and point sets; n64 is the longest, d_points and
+  // d_scalars the sets' starts.  Only the sort reads the table: what follows sees one dense sort, as for a batch.
   int msm_weierstrass_affine(const Handle& pts, const uint32_t* d_points, const uint32_t* d_scalars, uint64_t n64,
                              const msmz_opts& opt, uint8_t* out, int* out_inf, msmz_log* log, int extra_bits,
-                             uint32_t nprob, Redo* redo) {
+                             uint32_t nprob, Redo* redo, const SegDesc* d_segs = nullptr) {
     const bool glv = opt.glv != 0;
     if (glv && (!Fr::HAS_GLV || !pts.has_endo)) return MSMZ_ERR_UNSUPPORTED;
     Plan pl;
@@ -1379,7 +1512,7 @@ class Engine : public IEngine {
     const size_t f2_records = opt.reserved[0] == 1 ? (size_t)13 * pl.Keff * ((pl.L + 1) / 2) + 256 : 0;
     if ((st = slots_.ensure(((size_t)nprob * pl.K * pl.M + 64 + f2_records) * SlotFmt<F>::WORDS * 4))) return st;
     Run run = new_run(opt);
-    if ((st = sort_phase(pl, sl, d_scalars, run, (uint32_t)pts.copy_stride))) return st;
+    if ((st = sort_phase(pl, sl, d_scalars, run, (uint32_t)pts.copy_stride, d_segs))) return st;
     const uint32_t nb = pl.nb * nprob;   // buckets of all problems
     MsmMeta* d_meta = meta_.as<MsmMeta>();
 
@@ -1694,6 +1827,18 @@ class Engine : public IEngine {
     h_check_bytes_ = 0;
     MSMZ_HIP(hipHostMalloc(&h_check_, need));
     h_check_bytes_ = need;
+    return MSMZ_OK;
+  }
+  DevBuf segs_;                  // run_segments: the descriptor table of a sub-batch ...
+  SegDesc* h_segs_ = nullptr;    // ... and its pinned, grow-only host copy (rewritten only after the sub-batch's final fetch)
+  size_t h_segs_n_ = 0;
+  int ensure_host_segs(size_t n) {
+    if (n <= h_segs_n_) return MSMZ_OK;
+    if (h_segs_) (void)hipHostFree(h_segs_);
+    h_segs_ = nullptr;
+    h_segs_n_ = 0;
+    MSMZ_HIP(hipHostMalloc(&h_segs_, n * sizeof(SegDesc)));
+    h_segs_n_ = n;
     return MSMZ_OK;
   }
   uint32_t* h_res_ = nullptr;   // pinned, grow-only: the window results of every problem of an MSM (fetch_window_sums)

@@ -92,6 +92,11 @@
   PFX template __global__ void k_hist<Fr, GLV, C>(uint32_t*, uint16_t*, uint32_t*, MsmMeta*, const uint32_t*, SortGeom, uint32_t); \
   PFX template __global__ void k_coarse<Fr, GLV, C>(uint32_t*, const uint32_t*, const uint32_t*, const uint16_t*, const uint32_t*, SortGeom, uint32_t);
 
+// ... and their segmented variants (msmz_msm_segments: the batched pipeline, Weierstrass curves only)
+#define MSMZ_INST_SORT_SEG(Fr, GLV, C, PFX)                                                                       \
+  PFX template __global__ void k_hist_seg<Fr, GLV, C>(uint32_t*, uint16_t*, uint32_t*, MsmMeta*, const uint32_t*, SortGeom, uint32_t, const SegDesc*); \
+  PFX template __global__ void k_coarse_seg<Fr, GLV, C>(uint32_t*, const uint32_t*, const uint32_t*, const uint16_t*, const uint32_t*, SortGeom, uint32_t, const SegDesc*);
+
 #define MSMZ_INST_SCALAR(Fr, PFX)                                                                                 \
   PFX template __global__ void k_digits<Fr, false>(uint32_t*, uint32_t*, MsmMeta*, const uint32_t*, uint32_t, int, int, int, int); \
   MSMZ_INST_SORT(Fr, false, 0, PFX)                                                                               \
@@ -112,6 +117,11 @@
   PFX template __global__ void k_digits<Fr, true>(uint32_t*, uint32_t*, MsmMeta*, const uint32_t*, uint32_t, int, int, int, int); \
   MSMZ_INST_SORT(Fr, true, 0, PFX)                                                                                \
   MSMZ_INST_SORT(Fr, true, 16, PFX)                                                                               \
+  MSMZ_INST_SORT_SEG(Fr, true, 0, PFX)                                                                            \
+  MSMZ_INST_SORT_SEG(Fr, true, 16, PFX)                                                                           \
+  MSMZ_INST_SORT_SEG(Fr, false, 0, PFX)                                                                           \
+  MSMZ_INST_SORT_SEG(Fr, false, 16, PFX)                                                                          \
+  MSMZ_INST_SORT_SEG(Fr, false, 17, PFX)                                                                          \
   PFX template __global__ void k_test_digits<Fr, true>(uint32_t*, const uint32_t*, uint32_t, int, int);           \
   MSMZ_INST_TEST(F, Fr, WeierPolicy<F>, false, PFX)                                                               \
   PFX template __global__ void k_test_slots_in<F>(uint32_t*, const uint32_t*, const uint8_t*, uint32_t, uint32_t*); \

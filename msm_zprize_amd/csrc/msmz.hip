@@ -182,6 +182,12 @@ int msmz_msm_batch_resident(msmz_ctx* c, uint64_t ph, uint64_t sh, uint64_t n, u
   return c->engine->msm_batch(ph, nullptr, sh, n, batch, o, out, out_inf, log);
 }
 
+int msmz_msm_segments(msmz_ctx* c, uint64_t ph, uint64_t sh, const msmz_segment* segs, uint32_t n_segs, const msmz_opts* o,
+                      uint8_t* out, int* out_inf, msmz_log* log) {
+  if (!c || !segs || !out || !out_inf || n_segs == 0) return MSMZ_ERR_ARG;
+  return c->engine->msm_segments(ph, sh, segs, n_segs, o, out, out_inf, log);
+}
+
 int msmz_precompute_points(msmz_ctx* c, uint64_t ph, uint64_t n, const msmz_opts* o, uint32_t factor, uint64_t* h) {
   if (!c || !h) return MSMZ_ERR_ARG;
   int cc = 0, glv = 0, sbits = 0;

@@ -82,6 +82,9 @@ class IEngine {
   virtual int msm_batch(uint64_t ph, const uint8_t* host_scalars, uint64_t sh, uint64_t n, uint32_t batch,
                         const msmz_opts* o, uint8_t* out, int* out_inf, msmz_log* log, const GenMap* split = nullptr,
                         uint64_t host_stride = 0) = 0;
+  // msmz_msm_segments: problem k = scalars [first_s, first_s + n) of `sh` times base points [first_p, first_p + n) of `ph`
+  virtual int msm_segments(uint64_t ph, uint64_t sh, const msmz_segment* segs, uint32_t n_segs, const msmz_opts* o,
+                           uint8_t* out, int* out_inf, msmz_log* log) = 0;
   // precomputed point sets (msmz_precompute_points): the parameters a set of n points is built with, then the copies
   // (sbits: the scalar bit bound of opts->reserved[1] as the planner normalizes it, 0 = none)
   virtual int precompute_params(uint64_t n, const msmz_opts* o, uint32_t factor, int* c, int* glv, uint32_t* copies,
@@ -114,6 +117,29 @@ static inline uint32_t batch_split(uint32_t remaining, uint64_t entries_per_prob
   if (fit >= remaining) return remaining;
   const uint64_t parts = (remaining + fit - 1) / fit;
   return (uint32_t)((remaining + parts - 1) / parts);
+}
+
+// Length classes of a segmented MSM (msmz_msm_segments): segments whose lengths have the same floor(log2 n) -- within 2x
+// of each other, which bounds what sizing one pipeline for the longest wastes on the shortest.  order: the segment indices
+// class after class (shortest class first), caller order kept inside a class; starts: class i = order[starts[i] ..
+// starts[i + 1]).  Lengths are >= 1.
+static inline void segment_classes(const uint64_t* n, uint32_t count, std::vector<uint32_t>* order,
+                                   std::vector<uint32_t>* starts) {
+  auto bits = [](uint64_t x) {
+    int b = 0;
+    while (x >>= 1) b++;
+    return b;
+  };
+  uint32_t per[65] = {};
+  for (uint32_t k = 0; k < count; k++) per[bits(n[k]) + 1]++;
+  starts->clear();
+  for (int b = 0; b < 64; b++) {
+    if (per[b + 1]) starts->push_back(per[b]);
+    per[b + 1] += per[b];   // -> first position of class b + 1; per[b] is class b's
+  }
+  starts->push_back(count);
+  order->assign(count, 0);
+  for (uint32_t k = 0; k < count; k++) (*order)[per[bits(n[k])]++] = k;
 }
 
 // entries of the first n that live on shard g of G
@@ -315,6 +341,10 @@ class MultiEngine : public IEngine {
       first = false;
     }
     return MSMZ_OK;
+  }
+
+  int msm_segments(uint64_t, uint64_t, const msmz_segment*, uint32_t, const msmz_opts*, uint8_t*, int*, msmz_log*) override {
+    return MSMZ_ERR_UNSUPPORTED;   // a range is not a prefix of a device's share (as import_scalars_into)
   }
 
   // every engine precomputes its own share of the points (the same c, GLV choice and copies, chosen for the whole set)

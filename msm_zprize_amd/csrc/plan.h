@@ -61,6 +61,12 @@ struct SortGeom {
   int sbits;
 };
 
+// One problem of a segmented MSM (msmz_msm_segments) as the sort kernels read it: its scalars are entries
+// [first_s, first_s + n) of the scalar set, its points records [first_p, first_p + n) of the point set's base points.
+struct SegDesc {
+  uint32_t first_s, first_p, n;
+};
+
 // chunk_pairs[r * n_chunks + chunk] = pairs of round r in the chunk's buckets, r < PLAN_RMAX
 // `chunk` <= PLAN_CHUNK buckets per workgroup (the host picks it so that there are enough workgroups for the GPU even
 // when a window has few, long buckets).

@@ -203,18 +203,38 @@ __device__ __forceinline__ uint32_t coarse_bin(const SortGeom& g, int k, uint32_
 // (scalarsFromBytes' precondition, checked here instead of in a serial host loop) or not below the caller's bound
 // 2^g.sbits; such a scalar is cleared and adds to no bin.
 // C > 0: specialized for window size C (window loop unrolled, DigitStream::next_c); C = 0: any window size.
-template <class Fr, bool GLV, int C>
-__global__ void __launch_bounds__(COARSE_T, 8) k_hist(uint32_t* counts, uint16_t* tile_counts, uint32_t* tile_offs, MsmMeta* meta,
-                                                 const uint32_t* scalars, SortGeom g, uint32_t nbins) {
+// SEG (segmented MSM, msmz_msm_segments): problem blockIdx.y is segment blockIdx.y of the descriptor table `segs`: its
+// scalars start at entry first_s of the set and only its first n <= g.n are read; g (and with it every entry index
+// h * g.n + idx) stays that of the longest segment.  The descriptor is the same for the whole workgroup: scalar registers.
+template <class Fr, bool GLV, int C, bool SEG>
+__device__ __forceinline__ void hist_tile(uint32_t* counts, uint16_t* tile_counts, uint32_t* tile_offs, MsmMeta* meta,
+                                          const uint32_t* scalars, SortGeom g, uint32_t nbins, const SegDesc* segs) {
   extern __shared__ uint32_t s_hist[];
   constexpr int HALVES = GLV ? 2 : 1;
   constexpr int PER = COARSE_ITEMS / HALVES;   // scalars per thread: one workgroup = one tile of k_coarse
   const uint32_t L = 1u << (g.c - 1);
   // batched MSM: problem blockIdx.y sorts scalar vector blockIdx.y into its own slice of the bin counts and tile rows
-  scalars += (size_t)blockIdx.y * g.n * 8;
+  uint32_t n_own = g.n;   // scalars of this problem
+  if constexpr (SEG) {
+    const SegDesc d = segs[blockIdx.y];
+    n_own = __builtin_amdgcn_readfirstlane(d.n);
+    scalars += (size_t)__builtin_amdgcn_readfirstlane(d.first_s) * 8;
+  } else {
+    scalars += (size_t)blockIdx.y * g.n * 8;
+  }
   counts += (size_t)blockIdx.y * g.sbins;
   tile_counts += (size_t)blockIdx.y * gridDim.x * nbins;
   tile_offs += (size_t)blockIdx.y * gridDim.x * nbins;
+  if constexpr (SEG) {
+    // a tile wholly past the segment's end (the grid is sized for the longest): zero rows, no scalar read
+    if (blockIdx.x * (uint32_t)(PER * COARSE_T) >= n_own) {
+      for (uint32_t b = threadIdx.x; b < nbins; b += COARSE_T) {
+        tile_counts[(size_t)blockIdx.x * nbins + b] = 0;
+        tile_offs[(size_t)blockIdx.x * nbins + b] = 0;
+      }
+      return;
+    }
+  }
   for (uint32_t b = threadIdx.x; b < nbins; b += COARSE_T) s_hist[b] = 0;
   __syncthreads();
   uint32_t bad = 0;
@@ -224,7 +244,7 @@ __global__ void __launch_bounds__(COARSE_T, 8) k_hist(uint32_t* counts, uint16_t
 #pragma unroll
   for (int it = 0; it < PER; it++) {
     idx[it] = (blockIdx.x * PER + it) * COARSE_T + threadIdx.x;
-    if (idx[it] < g.n) {
+    if (idx[it] < n_own) {
       if (!ds[it].load(scalars, idx[it], g.sbits)) {
         bad |= 4u;
         ds[it].clear();
@@ -285,6 +305,17 @@ __global__ void __launch_bounds__(COARSE_T, 8) k_hist(uint32_t* counts, uint16_t
     if (b < nbins) roff[b] = r[q];
   }
 }
+template <class Fr, bool GLV, int C>
+__global__ void __launch_bounds__(COARSE_T, 8) k_hist(uint32_t* counts, uint16_t* tile_counts, uint32_t* tile_offs, MsmMeta* meta,
+                                                 const uint32_t* scalars, SortGeom g, uint32_t nbins) {
+  hist_tile<Fr, GLV, C, false>(counts, tile_counts, tile_offs, meta, scalars, g, nbins, nullptr);
+}
+template <class Fr, bool GLV, int C>
+__global__ void __launch_bounds__(COARSE_T, 8) k_hist_seg(uint32_t* counts, uint16_t* tile_counts, uint32_t* tile_offs,
+                                                          MsmMeta* meta, const uint32_t* scalars, SortGeom g, uint32_t nbins,
+                                                          const SegDesc* segs) {
+  hist_tile<Fr, GLV, C, true>(counts, tile_counts, tile_offs, meta, scalars, g, nbins, segs);
+}
 
 // exclusive scan of nbins <= SORT_MAX_BINS counts by one workgroup; base[nbins] = total = number of entries
 static __global__ void __launch_bounds__(1024) k_bin_scan(uint32_t* base, const uint32_t* counts, uint32_t nbins,
@@ -335,12 +366,23 @@ static __global__ void __launch_bounds__(1024) k_bin_scan(uint32_t* base, const 
 //            offset), stage them in LDS in bin order, write every bin's entries as one contiguous run.  Double-buffered
 //            staging: 1 barrier per window.
 // Algorithmic HBM bytes: 32 B read per scalar + 4 B written per entry.  Dynamic LDS: 2 * nbins words.
-template <class Fr, bool GLV, int C>
-__global__ void __launch_bounds__(COARSE_T, 8) k_coarse(uint32_t* packed_out, const uint32_t* tile_offs, const uint32_t* bin_base,
-                                                        const uint16_t* tile_counts, const uint32_t* scalars, SortGeom g,
-                                                        uint32_t nbins) {
+// SEG: as hist_tile.  A tile wholly past its segment's end has no entry (k_hist left it zero rows): the workgroup leaves
+// at once -- the whole workgroup, before any barrier.
+template <class Fr, bool GLV, int C, bool SEG>
+__device__ __forceinline__ void coarse_tile(uint32_t* packed_out, const uint32_t* tile_offs, const uint32_t* bin_base,
+                                            const uint16_t* tile_counts, const uint32_t* scalars, const SortGeom& g,
+                                            uint32_t nbins, const SegDesc* segs) {
   constexpr int HALVES = GLV ? 2 : 1;
   constexpr int SC = COARSE_ITEMS / HALVES;           // scalars per thread
+  uint32_t n_own = g.n;   // scalars of this problem
+  if constexpr (SEG) {
+    const SegDesc d = segs[blockIdx.y];
+    n_own = __builtin_amdgcn_readfirstlane(d.n);
+    if (blockIdx.x * (uint32_t)(SC * COARSE_T) >= n_own) return;
+    scalars += (size_t)__builtin_amdgcn_readfirstlane(d.first_s) * 8;
+  } else {
+    scalars += (size_t)blockIdx.y * g.n * 8;
+  }
   extern __shared__ uint32_t s_dyn[];
   uint32_t* s_cur = s_dyn;                  // [nbins] cursor: next staging position of the bin (starts at its staging offset)
   uint32_t* s_delta = s_dyn + nbins;        // [nbins] (global index of the tile's run in the bin) - (staging offset)
@@ -354,7 +396,6 @@ __global__ void __launch_bounds__(COARSE_T, 8) k_coarse(uint32_t* packed_out, co
 #endif
   // batched MSM: problem blockIdx.y; its bins start at bin blockIdx.y * nbins of ONE scan over all problems, so the
   // packed words of every problem land in one dense array
-  scalars += (size_t)blockIdx.y * g.n * 8;
   bin_base += (size_t)blockIdx.y * g.sbins;
   tile_counts += (size_t)blockIdx.y * gridDim.x * nbins;
   tile_offs += (size_t)blockIdx.y * gridDim.x * nbins;
@@ -366,7 +407,7 @@ __global__ void __launch_bounds__(COARSE_T, 8) k_coarse(uint32_t* packed_out, co
 #pragma unroll
   for (int s = 0; s < SC; s++) {
     idx[s] = (blockIdx.x * SC + s) * COARSE_T + threadIdx.x;
-    if (idx[s] >= g.n || !ds[s].load(scalars, idx[s], g.sbits)) ds[s].clear();   // (out of range: no digit, as in k_hist)
+    if (idx[s] >= n_own || !ds[s].load(scalars, idx[s], g.sbits)) ds[s].clear();   // (out of range: no digit, as in k_hist)
   }
   {
     const uint16_t* row = tile_counts + (size_t)blockIdx.x * nbins;
@@ -513,6 +554,19 @@ __global__ void __launch_bounds__(COARSE_T, 8) k_coarse(uint32_t* packed_out, co
   }
   MSMZ_STAMP(trace, 4);
 }
+template <class Fr, bool GLV, int C>
+__global__ void __launch_bounds__(COARSE_T, 8) k_coarse(uint32_t* packed_out, const uint32_t* tile_offs, const uint32_t* bin_base,
+                                                        const uint16_t* tile_counts, const uint32_t* scalars, SortGeom g,
+                                                        uint32_t nbins) {
+  coarse_tile<Fr, GLV, C, false>(packed_out, tile_offs, bin_base, tile_counts, scalars, g, nbins, nullptr);
+}
+template <class Fr, bool GLV, int C>
+__global__ void __launch_bounds__(COARSE_T, 8) k_coarse_seg(uint32_t* packed_out, const uint32_t* tile_offs,
+                                                            const uint32_t* bin_base, const uint16_t* tile_counts,
+                                                            const uint32_t* scalars, SortGeom g, uint32_t nbins,
+                                                            const SegDesc* segs) {
+  coarse_tile<Fr, GLV, C, true>(packed_out, tile_offs, bin_base, tile_counts, scalars, g, nbins, segs);
+}
 
 // ------------------------------------------------------------------------------------------------ fine sort
 // `n_half` / `endo_delta`: with GLV the entry index i >= n_half is the endomorphism half of point i - n_half; its
@@ -521,11 +575,16 @@ __global__ void __launch_bounds__(COARSE_T, 8) k_coarse(uint32_t* packed_out, co
 // Bins below `top_bin` hold 2^fb buckets each, the top window's bins (from `top_bin` on) 2^fbt.
 // Precomputed point sets (SortGeom::F = `group` > 1): bin b is the `group` consecutive scanned bins from b * group on, and
 // the packed index is copy << mbits | entry; the copy's records start at copy * copy_stride.  group = 1: mbits = idx_bits.
-static __global__ void __launch_bounds__(FINE_T) k_fine(uint32_t* refs, uint32_t* off, uint32_t* max_bucket,
-                                                 const uint32_t* packed, const uint32_t* bin_base, int fb, int fbt,
-                                                 uint32_t top_bin, uint32_t n_bins, int idx_bits, uint32_t n_half,
-                                                 uint32_t endo_delta, uint32_t group, int mbits, uint32_t copy_stride) {
+// SEG (segmented MSM): the points of problem blockIdx.y start at record first_p of the set (its descriptor in `segs`):
+// added to every record index last, behind the endomorphism and copy terms; n_half stays the longest segment's.
+template <bool SEG>
+static __device__ __forceinline__ void fine_bin(uint32_t* refs, uint32_t* off, uint32_t* max_bucket, const uint32_t* packed,
+                                                const uint32_t* bin_base, int fb, int fbt, uint32_t top_bin, uint32_t n_bins,
+                                                int idx_bits, uint32_t n_half, uint32_t endo_delta, uint32_t group, int mbits,
+                                                uint32_t copy_stride, const SegDesc* segs) {
   extern __shared__ uint32_t s_dyn[];
+  uint32_t first_p = 0;
+  if constexpr (SEG) first_p = __builtin_amdgcn_readfirstlane(segs[blockIdx.y].first_p);
   uint32_t* s_cnt = s_dyn;                                  // [1 << FINE_MAX_BITS] counts, then running cursors
   uint32_t* s_stage = s_dyn + (1 << FINE_MAX_BITS);          // [FINE_STAGE]
   __shared__ uint32_t s_wave[FINE_T / 64];
@@ -646,6 +705,7 @@ static __global__ void __launch_bounds__(FINE_T) k_fine(uint32_t* refs, uint32_t
     idx &= (1u << mbits) - 1u;
     if (idx >= n_half) idx += endo_delta;   // endomorphism half: record index in the point set
     idx += copy * copy_stride;
+    if constexpr (SEG) idx += first_p;
     return idx | (((pv >> idx_bits) & 1u) << 31);
   };
   if (staged) {
@@ -680,6 +740,21 @@ static __global__ void __launch_bounds__(FINE_T) k_fine(uint32_t* refs, uint32_t
     MSMZ_STAMP(trace, 4);
     MSMZ_STAMP(trace, 5);
   }
+}
+static __global__ void __launch_bounds__(FINE_T) k_fine(uint32_t* refs, uint32_t* off, uint32_t* max_bucket,
+                                                 const uint32_t* packed, const uint32_t* bin_base, int fb, int fbt,
+                                                 uint32_t top_bin, uint32_t n_bins, int idx_bits, uint32_t n_half,
+                                                 uint32_t endo_delta, uint32_t group, int mbits, uint32_t copy_stride) {
+  fine_bin<false>(refs, off, max_bucket, packed, bin_base, fb, fbt, top_bin, n_bins, idx_bits, n_half, endo_delta, group,
+                  mbits, copy_stride, nullptr);
+}
+static __global__ void __launch_bounds__(FINE_T) k_fine_seg(uint32_t* refs, uint32_t* off, uint32_t* max_bucket,
+                                                     const uint32_t* packed, const uint32_t* bin_base, int fb, int fbt,
+                                                     uint32_t top_bin, uint32_t n_bins, int idx_bits, uint32_t n_half,
+                                                     uint32_t endo_delta, uint32_t group, int mbits, uint32_t copy_stride,
+                                                     const SegDesc* segs) {
+  fine_bin<true>(refs, off, max_bucket, packed, bin_base, fb, fbt, top_bin, n_bins, idx_bits, n_half, endo_delta, group,
+                 mbits, copy_stride, segs);
 }
 
 }  // namespace msmz

@@ -17,7 +17,7 @@ include/msmz.h -- this module contains no arithmetic.
 import ctypes as C
 
 from . import _native
-from ._native import MsmzCheckResult, MsmzLog, MsmzMul, MsmzOpts, MsmzSrc, check, lib
+from ._native import MsmzCheckResult, MsmzLog, MsmzMul, MsmzOpts, MsmzSegment, MsmzSrc, check, lib
 
 _state = {"devices": None}
 
@@ -419,6 +419,48 @@ class _Parallel:
         """msmBatch with unsafe additions (msmUnsafe)."""
         return self._msm_batch(scalarsList, points, N, options, 0)
 
+    # -- segmented MSM: every problem its own range of one point set and one scalar set -------------
+    def _msm_segments(self, scalars, points, segments, options, safe):
+        options = dict(options or {})
+        segs = msm_segments_args(scalars, points, segments)
+        B = len(segs)
+        table = (MsmzSegment * B)(*[MsmzSegment(p, s, n) for p, s, n in segs])
+        opts = MsmzOpts()
+        opts.c = int(options.get("c") or 0)
+        opts.glv = int(options.get("glv", self._c.default_glv))
+        opts.safe = int(options.get("useSafeAdditions", safe))
+        opts.buckets = int(options.get("buckets", 0))
+        opts.reserved[0] = int(options.get("reduceAffine", 0))
+        opts.reserved[1] = scalar_bits_arg(options, "msmSegments")
+        fb = self._c.fe_bytes
+        out = C.create_string_buffer(2 * fb * B)
+        inf = (C.c_int * B)()
+        log = MsmzLog()
+        check(lib().msmz_msm_segments(self._c._ctx, points.handle, scalars.handle, table, B, C.byref(opts), out, inf,
+                                      C.byref(log)), "msmz_msm_segments")
+        self.lastBatchLog = log
+        raw = out.raw
+        results = []
+        for k in range(B):
+            r = {"x": int.from_bytes(raw[2 * fb * k:2 * fb * k + fb], "little"),
+                 "y": int.from_bytes(raw[2 * fb * k + fb:2 * fb * (k + 1)], "little"), "isZero": inf[k] != 0}
+            if r["isZero"] and self._c.kind == "weierstrass":
+                r["x"], r["y"] = 0, 1
+            results.append(r)
+        return results
+
+    def msmSegments(self, scalars, points, segments, options=None):
+        """One MSM per segment (msmz_msm_segments): `segments` is a sequence of (firstPoint, firstScalar, N), result k =
+        sum_{i < N} scalars[firstScalar + i] * points[firstPoint + i] over ONE resident scalar array and ONE resident
+        point array (plain or precomputed).  Segments may overlap or repeat and differ in length; segments of similar
+        length share one device pipeline.  An IPA round: msmSegments(a, G, [(n, 0, n), (0, n, n)]) is L and R.  Returns
+        the results in the caller's order, in the form of msmBatch; the log is left in `lastBatchLog`.  Safe additions."""
+        return self._msm_segments(scalars, points, segments, options, 1)
+
+    def msmSegmentsUnsafe(self, scalars, points, segments, options=None):
+        """msmSegments with unsafe additions (msmUnsafe)."""
+        return self._msm_segments(scalars, points, segments, options, 0)
+
     def msmProjective(self, scalars, points, N, options=None):
         """parallel.ts:69-87: no GLV, projective buckets (msm-basic.ts)."""
         options = dict(options or {})
@@ -483,6 +525,39 @@ def mul_points_args(scalars, points, N, addend, firstPoint, firstScalar, firstAd
             raise ValueError(f"mulPoints: entries [{first}, +{N}) of {name[5:].lower()}s that hold {len(arr)}")
     return {"N": N, "firstPoint": firstPoint, "firstScalar": firstScalar, "firstAddend": firstAddend,
             "scalar": scalars.to_bytes(32, "little") if broadcast else None}
+
+
+def msm_segments_args(scalars, points, segments):
+    """Arguments of msmSegments -> [(firstPoint, firstScalar, N), ...] as ints, checked before anything reaches the
+    device."""
+    if not isinstance(points, DeviceArray) or points.kind not in ("points", "precomputed"):
+        raise TypeError("msmSegments: `points` is a resident point array (plain or precomputed)")
+    if not isinstance(scalars, DeviceArray) or scalars.kind != "scalars":
+        raise TypeError("msmSegments: `scalars` is a resident scalar array (scalarsFromBytes / scalarsFromTensor); "
+                        "host scalars are uploaded first")
+    if isinstance(segments, (str, bytes, bytearray, DeviceArray)) or not hasattr(segments, "__len__"):
+        raise TypeError("msmSegments: `segments` is a sequence of (firstPoint, firstScalar, N)")
+    segs = list(segments)
+    if not segs:
+        raise ValueError("msmSegments: no segments")
+    if len(segs) >= 2 ** 32:
+        raise ValueError(f"msmSegments: {len(segs)} segments")
+    out = []
+    for k, seg in enumerate(segs):
+        if isinstance(seg, (str, bytes, bytearray)) or not hasattr(seg, "__len__") or len(seg) != 3:
+            raise TypeError(f"msmSegments: segment {k} is not (firstPoint, firstScalar, N): {seg!r}")
+        firstPoint, firstScalar, N = seg
+        for name, v in (("firstPoint", firstPoint), ("firstScalar", firstScalar), ("N", N)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError(f"msmSegments: segment {k}: {name} = {v!r}")
+        if N < 1:
+            raise ValueError(f"msmSegments: segment {k}: N = {N}")
+        if firstPoint + N > len(points):
+            raise ValueError(f"msmSegments: segment {k}: points [{firstPoint}, +{N}) of a set of {len(points)}")
+        if firstScalar + N > len(scalars):
+            raise ValueError(f"msmSegments: segment {k}: scalars [{firstScalar}, +{N}) of a set of {len(scalars)}")
+        out.append((firstPoint, firstScalar, N))
+    return out
 
 
 def check_arg(check, who):

@@ -362,6 +362,49 @@ static napi_value MsmBatch(napi_env env, napi_callback_info info) {
   return res;
 }
 
+/* msmSegments(ctx, pointsHandle, scalarsHandle, segs (Buffer: per segment firstPoint, firstScalar, n as three
+ * little-endian uint64 = msmz_segment), count, feBytes, opts) -> {xy (count records), isInf (count flags in a Buffer)} */
+static napi_value MsmSegments(napi_env env, napi_callback_info info) {
+  size_t argc = 7; napi_value argv[7];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  msmz_ctx* ctx; if (!get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "msmSegments");
+  uint64_t ph, sh, count, fb;
+  if (argc < 6 || !get_u64(env, argv[1], &ph) || !get_u64(env, argv[2], &sh) || !get_u64(env, argv[4], &count) ||
+      !get_u64(env, argv[5], &fb) || count == 0 || count > 0xffffffffu || fb > 64)
+    return throw_status(env, MSMZ_ERR_ARG, "msmSegments");
+  void* sp; size_t slen;
+  if (napi_get_buffer_info(env, argv[3], &sp, &slen) != napi_ok || slen / sizeof(msmz_segment) < count)
+    return throw_status(env, MSMZ_ERR_ARG, "msmSegments");
+  msmz_opts o; memset(&o, 0, sizeof(o));
+  if (argc > 6) {
+    o.c = opt_i32(env, argv[6], "c");
+    o.glv = opt_i32(env, argv[6], "glv");
+    o.safe = opt_i32(env, argv[6], "safe");
+    o.buckets = opt_i32(env, argv[6], "buckets");
+    o.reserved[0] = opt_i32(env, argv[6], "reduceAffine");
+    o.reserved[1] = opt_i32(env, argv[6], "scalarBits");
+  }
+  void* data; napi_value xy;
+  NAPI_CALL(env, napi_create_buffer(env, (size_t)(2 * fb * count), &data, &xy));
+  int* flags = (int*)calloc((size_t)count, sizeof(int));
+  msmz_segment* segs = (msmz_segment*)malloc((size_t)count * sizeof(msmz_segment));   /* (a Buffer need not be aligned) */
+  if (!flags || !segs) { free(flags); free(segs); return throw_status(env, MSMZ_ERR_ARG, "msmSegments"); }
+  memcpy(segs, sp, (size_t)count * sizeof(msmz_segment));
+  const int st = msmz_msm_segments(ctx, ph, sh, segs, (uint32_t)count, &o, (uint8_t*)data, flags, NULL);
+  free(segs);
+  void* fdata = NULL; napi_value inf;
+  if (st == 0 && napi_create_buffer(env, (size_t)count, &fdata, &inf) == napi_ok)
+    for (uint64_t k = 0; k < count; k++) ((uint8_t*)fdata)[k] = flags[k] ? 1 : 0;
+  free(flags);
+  if (st) return throw_status(env, st, "msmz_msm_segments");
+  if (!fdata) return throw_status(env, MSMZ_ERR_ARG, "msmSegments");
+  napi_value res;
+  NAPI_CALL(env, napi_create_object(env, &res));
+  napi_set_named_property(env, res, "xy", xy);
+  napi_set_named_property(env, res, "isInf", inf);
+  return res;
+}
+
 /* pointAdd(curveId, aXy|null, bXy|null, feBytes) -> {xy, isInf}  (null = infinity) */
 /* precomputePoints(ctx, pointsHandle, n, {c, glv, scalarBits}, factor) -> handle of a precomputed point set (msmz_precompute_points;
    glv -1 = the engine's choice, factor 0 = all windows in one bucket set) */
@@ -489,7 +532,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"create", Create}, {"destroy", Destroy}, {"uploadPoints", UploadPoints}, {"uploadScalars", UploadScalars},
       {"importScalars", ImportScalars}, {"importPoints", ImportPoints},
       {"randomPoints", RandomPoints}, {"randomScalars", RandomScalars}, {"downloadPoints", DownloadPoints},
-      {"downloadScalars", DownloadScalars}, {"free", Free}, {"msm", Msm}, {"msmBatch", MsmBatch},
+      {"downloadScalars", DownloadScalars}, {"free", Free}, {"msm", Msm}, {"msmBatch", MsmBatch}, {"msmSegments", MsmSegments},
       {"precomputePoints", PrecomputePoints}, {"precomputedInfo", PrecomputedInfo}, {"checkPoints", CheckPoints},
       {"mulPoints", MulPoints}, {"pointAdd", PointAdd}, {"feBytes", FeBytes}};
   for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); i++) {
