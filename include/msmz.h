@@ -335,6 +335,53 @@ typedef struct msmz_mul {
 } msmz_mul;
 int msmz_points_mul(msmz_ctx* ctx, const msmz_mul* m, uint64_t n, uint64_t* out_handle);
 
+/* Arithmetic mod q over resident scalar sets: linear combinations, inner products and powers of
+ * one ratio, so that a prover's witness fold a' = a_lo + u^-1 a_hi, its cross terms <a_lo, b_hi>, a random linear
+ * combination of columns sum_k r^k col_k or the vector (1, z, z^2, ...) never leave the device.  The reference has no
+ * analogue: its scalars live in wasm memory and its callers do this arithmetic with bigints.
+ * Values: a scalar set holds 32-byte little-endian values below q, and every result written here is again below q:
+ * MSM, msmz_points_mul, msmz_download_scalars and msmz_import_scalars_into take such a set unchanged.
+ *
+ * msmz_scalars_combine: out_i = x.c_i * x.v_i (+ y.c_i * y.v_i), i < n; y nullable.  v_i = entry first + i of `handle`;
+ * c_i = entry coeff_first + i of `coeff_handle`, or with coeff_handle == 0 the one scalar `coeff` for every i (NULL = 1).
+ * *out_handle == 0 on entry: a new scalar handle of n entries (first_out must be 0).  Otherwise entries
+ * [first_out, first_out + n) of that handle are overwritten and nothing else.  In place: the destination range may
+ * coincide exactly with any input range (a[0, n/2) = a[0, n/2) + u^-1 a[n/2, n): x = {a, 0}, y = {a, n/2, coeff u^-1},
+ * *out_handle = a, first_out = 0) or be disjoint from it; a partial overlap with an input range of the same handle is
+ * MSMZ_ERR_ARG.  A product with a broadcast coefficient costs one Montgomery multiplication, one with a resident
+ * coefficient two; coeff == NULL costs none.
+ *
+ * msmz_scalars_dot: sum_i x_i * y_i mod q over entries first_x + i and first_y + i (y_handle == 0: sum_i x_i, first_y
+ * must be 0) as 32 bytes little-endian, below q.  x and y may be the same handle and may overlap.  The sum is exact, so
+ * two calls return the same bytes.
+ *
+ * msmz_scalars_powers: a new scalar handle of n entries, entry i = base * ratio^i (base NULL = 1; 0^0 = 1).
+ *
+ * MSMZ_ERR_ARG, before any launch: a null ctx, x, out_handle, out_le32 or ratio_le32; n == 0 or n >= 2^32; an unknown
+ * handle or one that is not a scalar set; a range [first, first + n) beyond its set; first_out != 0 with a new handle; a
+ * partial overlap of the destination with an input.  MSMZ_ERR_RANGE: a broadcast coefficient, base or ratio >= q (checked
+ * on the host, nothing is launched), or a resident entry >= q inside an addressed range (found by the kernel; entries
+ * outside the ranges are not read).  After MSMZ_ERR_RANGE no handle is created, *out_handle is as it was, the context
+ * stays usable and the contents of an in-place destination range are unspecified (as after msmz_import_scalars_into).
+ * Each call returns after the GPU has finished, behind one host wait.
+ * Multi-device contexts: sets are dealt in blocks of 2^16 entries, so entry i of every operand lives on one device only
+ * when every first is 0.  combine then runs per engine into a new handle or over a WHOLE existing one (n its length), dot
+ * runs per engine and the host adds the engines' sums mod q, powers deals its entries like msmz_random_scalars; any
+ * non-zero first, or a destination of another length, is MSMZ_ERR_UNSUPPORTED there.  Like the rest of the multi-device
+ * code this has run as several engines on ONE GPU only. */
+typedef struct msmz_scalar_term {   /* c (.) v */
+  uint64_t handle;         /* v: a scalar handle ... */
+  uint64_t first;          /* ... and its first entry */
+  uint64_t coeff_handle;   /* c as a resident vector, or 0 = one scalar for all i (`coeff`) */
+  uint64_t coeff_first;
+  const uint8_t* coeff;    /* 32 bytes little-endian, < q; read only when coeff_handle == 0; NULL = 1 */
+} msmz_scalar_term;
+int msmz_scalars_combine(msmz_ctx* ctx, const msmz_scalar_term* x, const msmz_scalar_term* y, uint64_t n,
+                         uint64_t first_out, uint64_t* out_handle);
+int msmz_scalars_dot(msmz_ctx* ctx, uint64_t x_handle, uint64_t first_x, uint64_t y_handle, uint64_t first_y, uint64_t n,
+                     uint8_t* out_le32);
+int msmz_scalars_powers(msmz_ctx* ctx, const uint8_t* base_le32, const uint8_t* ratio_le32, uint64_t n, uint64_t* handle);
+
 /* Host-side group addition of two canonical affine results: combines per-GPU partial sums
  * (the reference's "partition sum" step, msm-batched-affine.ts:300-307). */
 int msmz_point_add(int curve_id, const uint8_t* a_xy_le, int a_is_inf, const uint8_t* b_xy_le, int b_is_inf,

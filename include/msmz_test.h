@@ -78,6 +78,11 @@ int msmz_test_set_limits(msmz_ctx* ctx, uint64_t pass_entries, uint64_t batch_en
  *   range_passes: iterations of run_problems' range loop (an ordinary single-problem MSM adds 1);
  *   sub_batches : batched pipelines (more than one problem) that ran to a result (not PER_PROBLEM). */
 int msmz_test_passes(msmz_ctx* ctx, uint64_t* range_passes, uint64_t* sub_batches);
+/* The geometry of msmz_scalars_dot (csrc/scalar_kernels.h), so a test can size itself at its edges (either pointer
+ * nullable; needs no context):
+ *   tile_elements    : elements one workgroup of the first level sums into one partial sum (SDOT_TILE);
+ *   partials_per_pass: partial sums the second level's one workgroup takes per pass of its loop (SDOT_PASS). */
+void msmz_test_scalar_dot_geometry(uint32_t* tile_elements, uint32_t* partials_per_pass);
 /* out[i] = op(a[i], b[i]) for i < n; a, b, out: n * fe_bytes */
 int msmz_test_field(msmz_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out);
 /* GLV split of n 32-byte scalars: s0, s1 = magnitudes (16 bytes each), neg = 2 sign bytes per scalar

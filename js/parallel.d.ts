@@ -38,6 +38,15 @@ export interface ParallelApi {
    * array or one bigint below the group order for every point; addend may be `points` itself (an IPA fold) */
   mulPoints(scalars: DeviceArray | bigint, points: DeviceArray, n?: number,
             options?: { addend?: DeviceArray | null; firstPoint?: number; firstScalar?: number; firstAddend?: number }): Promise<DeviceArray>;
+  /** out[firstOut + i] = a_i x[firstX + i] (+ b_i y[firstY + i]) mod the group order; a, b: one bigint for every entry or
+   * a resident scalar array; without `out` a new array, with it that range is overwritten (it may be an input's range
+   * exactly, or apart from it) */
+  combineScalars(a: DeviceArray | bigint, x: DeviceArray, b?: DeviceArray | bigint | null, y?: DeviceArray | null, n?: number,
+                 options?: { firstX?: number; firstY?: number; out?: DeviceArray | null; firstOut?: number; firstA?: number; firstB?: number }): Promise<DeviceArray>;
+  /** sum_i x[firstX + i] y[firstY + i] mod the group order (y null: the sum of x) */
+  innerProduct(x: DeviceArray, y?: DeviceArray | null, n?: number, options?: { firstX?: number; firstY?: number }): Promise<bigint>;
+  /** a new scalar array: entry i = base ratio^i mod the group order */
+  scalarPowers(ratio: bigint, n: number, base?: bigint): Promise<DeviceArray>;
   msmBatch(scalarsList: DeviceArray | Uint8Array[], points: DeviceArray, n: number, options?: MsmOptions & { batch?: number }): Promise<BigintPoint[]>;
   msmBatchUnsafe(scalarsList: DeviceArray | Uint8Array[], points: DeviceArray, n: number, options?: MsmOptions & { batch?: number }): Promise<BigintPoint[]>;
   /** one MSM per segment [firstPoint, firstScalar, n] of one resident scalar array and one resident point array */

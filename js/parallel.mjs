@@ -324,6 +324,73 @@ function createCurve(params, kind) {
                             firstScalar, addend === null ? 0 : addend.handle, firstAddend, n);
       return DeviceArray.make(curve, h, n, "points");
     },
+    /** arithmetic mod the group order over resident scalar arrays (include/msmz.h msmz_scalars_combine):
+     * out[firstOut + i] = a_i x[firstX + i] (+ b_i y[firstY + i]), i < n.  `a` and `b` are bigints below the group order
+     * (one coefficient for every entry) or resident scalar arrays (a_i = a[firstA + i]).  Without `out` the result is a
+     * new scalar array; with it, entries [firstOut, firstOut + n) of `out` are overwritten, and `out` may be an input
+     * when the range is exactly that input's or apart from it (an IPA fold in place:
+     * combineScalars(1n, v, uinv, v, n, {firstY: n, out: v})).  Returns the array written. */
+    async combineScalars(a, x, b = null, y = null, n, { firstX = 0, firstY = 0, out = null, firstOut = 0, firstA = 0, firstB = 0 } = {}) {
+      const isScalars = (v) => v instanceof DeviceArray && v.kind === "scalars";
+      if (!isScalars(x)) throw TypeError("combineScalars: `x` is a resident scalar array");
+      if ((b === null) !== (y === null)) throw TypeError("combineScalars: `b` and `y` come together");
+      if (y !== null && !isScalars(y)) throw TypeError("combineScalars: `y` is a resident scalar array or null");
+      if (out !== null && !isScalars(out)) throw TypeError("combineScalars: `out` is a resident scalar array or null");
+      const ranges = [["firstX", firstX, x], ["firstY", firstY, y]];
+      const coeff = (name, c, first, used) => {
+        if (!used) { ranges.push([name, first, null]); return null; }
+        if (typeof c === "bigint") {
+          if (c < 0n || c >= params.order) throw Error(`combineScalars: the coefficient ${c} is not in [0, group order)`);
+          ranges.push([name, first, null]);
+          return c === 1n ? null : Buffer.from(bigintToBytes(c, 32));
+        }
+        if (!isScalars(c)) throw TypeError("combineScalars: a coefficient is a bigint (one for every entry) or a resident scalar array");
+        ranges.push([name, first, c]);
+        return c.handle;
+      };
+      const ca = coeff("firstA", a, firstA, true), cb = coeff("firstB", b, firstB, y !== null);
+      ranges.push(["firstOut", firstOut, out]);
+      for (const [name, first, arr] of ranges) {
+        if (!Number.isInteger(first) || first < 0 || (arr === null ? first !== 0 : first >= arr.n))
+          throw Error(`combineScalars: ${name} = ${first}` + (arr === null ? " without the array it indexes" : ` but the array holds ${arr.n}`));
+      }
+      if (n === undefined || n === null) n = Math.min(...ranges.filter((r) => r[2] !== null).map(([, first, arr]) => arr.n - first));
+      if (!Number.isInteger(n) || n < 1 || n >= 2 ** 32) throw Error(`combineScalars: n = ${n}`);
+      for (const [name, first, arr] of ranges)
+        if (arr !== null && n > arr.n - first) throw Error(`combineScalars: entries [${first}, +${n}) from ${name} of an array of ${arr.n}`);
+      if (out !== null)
+        for (const [name, first, arr] of ranges.slice(0, -1))
+          if (arr !== null && arr.handle === out.handle && first !== firstOut && Math.abs(first - firstOut) < n)
+            throw Error(`combineScalars: the destination [${firstOut}, +${n}) overlaps the input range [${first}, +${n}) (${name}) in part`);
+      const h = N.scalarsCombine(ctx, x.handle, firstX, ca, firstA, y === null ? 0 : y.handle, firstY, cb, firstB, n, firstOut,
+                                 out === null ? 0 : out.handle);
+      return out === null ? DeviceArray.make(curve, h, n, "scalars") : out;
+    },
+    /** sum_i x[firstX + i] y[firstY + i] mod the group order (y null: sum_i x[firstX + i]) as a bigint
+     * (msmz_scalars_dot); x and y may be one array and may overlap */
+    async innerProduct(x, y = null, n, { firstX = 0, firstY = 0 } = {}) {
+      const isScalars = (v) => v instanceof DeviceArray && v.kind === "scalars";
+      if (!isScalars(x) || (y !== null && !isScalars(y))) throw TypeError("innerProduct: `x` and `y` are resident scalar arrays (y may be null)");
+      const ranges = [["firstX", firstX, x], ["firstY", firstY, y]];
+      for (const [name, first, arr] of ranges)
+        if (!Number.isInteger(first) || first < 0 || (arr === null ? first !== 0 : first >= arr.n)) throw Error(`innerProduct: ${name} = ${first}`);
+      if (n === undefined || n === null) n = Math.min(...ranges.filter((r) => r[2] !== null).map(([, first, arr]) => arr.n - first));
+      if (!Number.isInteger(n) || n < 1 || n >= 2 ** 32) throw Error(`innerProduct: n = ${n}`);
+      for (const [name, first, arr] of ranges)
+        if (arr !== null && n > arr.n - first) throw Error(`innerProduct: entries [${first}, +${n}) from ${name} of an array of ${arr.n}`);
+      const r = N.scalarsDot(ctx, x.handle, firstX, y === null ? 0 : y.handle, firstY, n);
+      return bytesToBigint(r, 0, 32);
+    },
+    /** a new resident scalar array: entry i = base ratio^i mod the group order (msmz_scalars_powers; 0^0 = 1) */
+    async scalarPowers(ratio, n, base = 1n) {
+      for (const [name, v] of [["ratio", ratio], ["base", base]]) {
+        if (typeof v !== "bigint") throw TypeError(`scalarPowers: \`${name}\` is a bigint`);
+        if (v < 0n || v >= params.order) throw Error(`scalarPowers: ${name} = ${v} is not in [0, group order)`);
+      }
+      if (!Number.isInteger(n) || n < 1 || n >= 2 ** 32) throw Error(`scalarPowers: n = ${n}`);
+      const h = N.scalarsPowers(ctx, Buffer.from(bigintToBytes(base, 32)), Buffer.from(bigintToBytes(ratio, 32)), n);
+      return DeviceArray.make(curve, h, n, "scalars");
+    },
     /** batched MSM: B scalar vectors against one point set (include/msmz.h msmz_msm_batch); safe additions */
     msmBatch: (scalarsList, points, n, options) => msmBatchCommon(scalarsList, points, n, options, 1),
     msmBatchUnsafe: (scalarsList, points, n, options) => msmBatchCommon(scalarsList, points, n, options, 0),

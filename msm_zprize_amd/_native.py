@@ -46,6 +46,11 @@ class MsmzMul(C.Structure):   # msmz_mul (include/msmz.h): out_i = [s_i] P_i (+ 
                 ("first_s", C.c_uint64), ("scalar", C.c_char_p), ("addend_handle", C.c_uint64), ("first_q", C.c_uint64)]
 
 
+class MsmzScalarTerm(C.Structure):   # msmz_scalar_term (include/msmz.h): one term c (.) v of msmz_scalars_combine
+    _fields_ = [("handle", C.c_uint64), ("first", C.c_uint64), ("coeff_handle", C.c_uint64), ("coeff_first", C.c_uint64),
+                ("coeff", C.c_char_p)]
+
+
 class MsmzSegment(C.Structure):   # msmz_segment (include/msmz.h): one problem of msmz_msm_segments
     _fields_ = [("first_p", C.c_uint64), ("first_s", C.c_uint64), ("n", C.c_uint64)]
 
@@ -120,12 +125,17 @@ EXPORTS = {
     "msmz_check_points": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                     C.POINTER(MsmzCheckResult), C.c_char_p]),
     "msmz_points_mul": (C.c_int, [C.c_void_p, C.POINTER(MsmzMul), C.c_uint64, C.POINTER(C.c_uint64)]),
+    "msmz_scalars_combine": (C.c_int, [C.c_void_p, C.POINTER(MsmzScalarTerm), C.POINTER(MsmzScalarTerm), C.c_uint64,
+                                       C.c_uint64, C.POINTER(C.c_uint64)]),
+    "msmz_scalars_dot": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_char_p]),
+    "msmz_scalars_powers": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "msmz_point_add": (C.c_int, [C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.POINTER(C.c_int)]),
     # stage-level test hooks (include/msmz_test.h)
     "msmz_test_set_glv_bits": (C.c_int, [C.c_void_p, C.c_int]),
     "msmz_test_retries": (C.c_int, [C.c_void_p]),
     "msmz_test_set_limits": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
     "msmz_test_passes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "msmz_test_scalar_dot_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "msmz_test_field": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_uint64, C.c_char_p]),
     "msmz_test_field_limbs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                         C.c_char_p]),

@@ -20,6 +20,7 @@
 #include "import_kernels.h"
 #include "check_kernels.h"
 #include "mul_kernels.h"
+#include "scalar_kernels.h"
 #include "host64.h"
 #include "multi.h"
 #include "plan.h"
@@ -706,6 +707,119 @@ class Engine : public IEngine {
     uint32_t err = 0;
     if (int st = fetch_error(&err)) return st;
     if (err) return MSMZ_ERR_RANGE;   // a resident scalar >= group order
+    return add_handle(std::move(hd), h);
+  }
+
+  // ------------------------------------------------------------------------------------------ scalar-set arithmetic
+  // msmz_scalars_combine: out_i = x.c_i x.v_i (+ y.c_i y.v_i) into a new scalar handle or over a range of an existing
+  // one.  One launch; the error word (a resident record >= q) comes back behind the ONE host wait.
+  int scalars_combine(const msmz_scalar_term& x, const msmz_scalar_term* y, uint64_t n, uint64_t first_out,
+                      uint64_t* out_handle) override {
+    if (!out_handle || n == 0 || n >> 32) return MSMZ_ERR_ARG;
+    const bool fresh = *out_handle == 0;
+    if (fresh && first_out != 0) return MSMZ_ERR_ARG;
+    auto beyond = [n](const Handle& s, uint64_t first) { return first > s.n || n > s.n - first; };   // (no first + n: it can wrap)
+    // a range of a scalar set -> its first record; a partial overlap with the destination is refused
+    auto range = [&](uint64_t h, uint64_t first, const uint32_t** p) {
+      auto it = handles_.find(h);
+      if (it == handles_.end() || it->second.kind != 1 || beyond(it->second, first)) return false;
+      if (!fresh && h == *out_handle && first != first_out && (first > first_out ? first - first_out : first_out - first) < n)
+        return false;
+      *p = it->second.mem.template as<const uint32_t>() + first * 8;
+      return true;
+    };
+    ScalarTerm t[2] = {};
+    const msmz_scalar_term* in[2] = {&x, y};
+    for (int k = 0; k < 2; k++) {
+      if (!in[k]) continue;
+      if (!range(in[k]->handle, in[k]->first, &t[k].v)) return MSMZ_ERR_ARG;
+      if (in[k]->coeff_handle && !range(in[k]->coeff_handle, in[k]->coeff_first, &t[k].c)) return MSMZ_ERR_ARG;
+    }
+    uint32_t* out = nullptr;
+    if (!fresh) {
+      auto it = handles_.find(*out_handle);
+      if (it == handles_.end() || it->second.kind != 1 || beyond(it->second, first_out)) return MSMZ_ERR_ARG;
+      out = it->second.mem.template as<uint32_t>() + first_out * 8;
+    }
+    for (int k = 0; k < 2; k++) {
+      if (!in[k] || in[k]->coeff_handle) continue;
+      if (!in[k]->coeff) {
+        t[k].unit = 1;
+        continue;
+      }
+      uint32_t c[8];
+      memcpy(c, in[k]->coeff, 32);
+      if (words_geq<8>(c, Fr::Q)) return MSMZ_ERR_RANGE;
+      fr_to_mont<Fr>(t[k].k.w, c);
+    }
+    MSMZ_HIP(hipSetDevice(device_));
+    Handle hd{1, n, false};
+    if (fresh) {
+      if (int st = alloc_handle(hd, n * 32)) return st;
+      out = hd.mem.as<uint32_t>();
+    }
+    MsmMeta* d_meta = meta_.as<MsmMeta>();
+    MSMZ_HIP(hipMemsetAsync(&d_meta->error, 0, 4, stream_));
+    hipLaunchKernelGGL((k_scalars_combine<Fr>), dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream_, out, t[0], t[1],
+                       (uint32_t)n, &d_meta->error);
+    uint32_t err = 0;
+    if (int st = fetch_error(&err)) return st;
+    if (err) return MSMZ_ERR_RANGE;   // a resident record >= group order
+    return fresh ? add_handle(std::move(hd), out_handle) : (int)MSMZ_OK;
+  }
+
+  // msmz_scalars_dot: one partial sum per tile, one workgroup folds them; the result and the error word share a
+  // 64-byte record in front of the partial sums and come back in ONE copy behind ONE host wait.
+  int scalars_dot(uint64_t xh, uint64_t first_x, uint64_t yh, uint64_t first_y, uint64_t n, uint8_t* out) override {
+    if (!out || n == 0 || n >> 32) return MSMZ_ERR_ARG;
+    auto xit = handles_.find(xh);
+    if (xit == handles_.end() || xit->second.kind != 1) return MSMZ_ERR_ARG;
+    auto yit = handles_.end();
+    if (yh) {
+      yit = handles_.find(yh);
+      if (yit == handles_.end() || yit->second.kind != 1) return MSMZ_ERR_ARG;
+    } else if (first_y) {
+      return MSMZ_ERR_ARG;
+    }
+    auto beyond = [n](const Handle& s, uint64_t first) { return first > s.n || n > s.n - first; };
+    if (beyond(xit->second, first_x) || (yh && beyond(yit->second, first_y))) return MSMZ_ERR_ARG;
+    MSMZ_HIP(hipSetDevice(device_));
+    const uint32_t tiles = (uint32_t)((n + SDOT_TILE - 1) / SDOT_TILE);
+    if (int st = sdot_.ensure(64 + (size_t)tiles * 32)) return st;
+    uint32_t* d_res = sdot_.as<uint32_t>();   // words 0..7: the result, word 8: the error word, from word 16: the partial sums
+    MSMZ_HIP(hipMemsetAsync(d_res, 0, 64, stream_));
+    const uint32_t* X = xit->second.mem.template as<const uint32_t>() + first_x * 8;
+    const uint32_t* Y = yh ? yit->second.mem.template as<const uint32_t>() + first_y * 8 : nullptr;
+    hipLaunchKernelGGL((k_scalars_dot<Fr>), dim3(tiles), dim3(SDOT_THREADS), 0, stream_, d_res + 16, X, Y, (uint32_t)n, d_res + 8);
+    hipLaunchKernelGGL((k_scalars_dot_fold<Fr>), dim3(1), dim3(SDOT_THREADS), 0, stream_, d_res, d_res + 16, tiles, Y ? 1 : 0);
+    MSMZ_HIP(hipGetLastError());
+    MSMZ_HIP(hipMemcpyAsync(h_res_, d_res, 64, hipMemcpyDeviceToHost, stream_));   // (pinned: init sized it for far more)
+    MSMZ_HIP(hipStreamSynchronize(stream_));
+    if (h_res_[8]) return MSMZ_ERR_RANGE;   // a resident record >= group order
+    memcpy(out, h_res_, 32);
+    return MSMZ_OK;
+  }
+
+  // msmz_scalars_powers: a new scalar handle, local entry i = base ratio^(set index of i).  The host builds the table of
+  // ratio^(2^k) with fr.h; it travels as a kernel argument.
+  int scalars_powers(const uint8_t* base, const uint8_t* ratio, uint64_t n, const GenMap& map, uint64_t* h) override {
+    if (!h || !ratio || n == 0 || n >> 32) return MSMZ_ERR_ARG;
+    FrConst b{};
+    uint32_t r[8];
+    b.w[0] = 1;
+    if (base) memcpy(b.w, base, 32);
+    memcpy(r, ratio, 32);
+    if (words_geq<8>(b.w, Fr::Q) || words_geq<8>(r, Fr::Q)) return MSMZ_ERR_RANGE;
+    FrPowTable table;
+    fr_pow_table<Fr>(table, r);
+    MSMZ_HIP(hipSetDevice(device_));
+    Handle hd{1, n, false};
+    if (int st = alloc_handle(hd, n * 32)) return st;
+    const uint64_t threads = (n + SPOW_RUN - 1) / SPOW_RUN;
+    hipLaunchKernelGGL((k_scalars_powers<Fr>), dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, stream_,
+                       hd.mem.as<uint32_t>(), b, table, (uint32_t)n, map);
+    MSMZ_HIP(hipGetLastError());
+    MSMZ_HIP(hipStreamSynchronize(stream_));
     return add_handle(std::move(hd), h);
   }
 
@@ -1816,6 +1930,7 @@ class Engine : public IEngine {
                         (uint32_t)env_int("MSMZ_R2_NC", 0)}};
   DevBuf bsum_, f2desc_, tilecnt_, tileoff_, final_, desc_, bfin_, packed_, bins_, digits_, counts_, off_, cursor_, refs_, rscan_, partials_, slots_, red_[4], meta_, stage_, gen_table_;
   MsmMeta* h_meta_ = nullptr;
+  DevBuf sdot_;                      // scalars_dot: its result record, then one partial sum per tile
   DevBuf check_;                     // check_points: its result record, then one verdict byte per point
   CheckResult* h_check_ = nullptr;   // pinned, grow-only landing of the result record and the verdict bytes behind it
   size_t h_check_bytes_ = 0;

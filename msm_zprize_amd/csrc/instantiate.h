@@ -7,6 +7,7 @@
 #include "import_kernels.h"
 #include "kernels.h"
 #include "mul_kernels.h"
+#include "scalar_kernels.h"
 #include "test_kernels.h"
 
 // curve ids as in include/msmz.h
@@ -104,7 +105,11 @@
   MSMZ_INST_SORT(Fr, false, 17, PFX)                                                                              \
   PFX template __global__ void k_check_scalars<Fr>(uint32_t*, const uint32_t*, uint32_t);                         \
   PFX template __global__ void k_gen_scalars<Fr>(uint32_t*, uint32_t, uint64_t, GenMap);                          \
-  PFX template __global__ void k_import_scalars<Fr>(uint32_t*, const uint8_t*, uint64_t, int, uint32_t, int, uint32_t*);
+  PFX template __global__ void k_import_scalars<Fr>(uint32_t*, const uint8_t*, uint64_t, int, uint32_t, int, uint32_t*); \
+  PFX template __global__ void k_scalars_combine<Fr>(uint32_t*, ScalarTerm, ScalarTerm, uint32_t, uint32_t*);     \
+  PFX template __global__ void k_scalars_dot<Fr>(uint32_t*, const uint32_t*, const uint32_t*, uint32_t, uint32_t*); \
+  PFX template __global__ void k_scalars_dot_fold<Fr>(uint32_t*, const uint32_t*, uint32_t, int);                 \
+  PFX template __global__ void k_scalars_powers<Fr>(uint32_t*, FrConst, FrPowTable, uint32_t, GenMap);
 
 #define MSMZ_INST_MISC(F, Fr, PFX)                                                                                \
   PFX template __global__ void k_points_to_mont<F>(uint32_t*, const uint32_t*, const uint8_t*, uint32_t, int, uint32_t*); \

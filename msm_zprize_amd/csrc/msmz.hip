@@ -214,6 +214,21 @@ int msmz_points_mul(msmz_ctx* c, const msmz_mul* m, uint64_t n, uint64_t* h) {
   return c && m ? c->engine->points_mul(*m, n, h) : MSMZ_ERR_ARG;
 }
 
+int msmz_scalars_combine(msmz_ctx* c, const msmz_scalar_term* x, const msmz_scalar_term* y, uint64_t n, uint64_t first_out,
+                         uint64_t* out_handle) {
+  return c && x && out_handle ? c->engine->scalars_combine(*x, y, n, first_out, out_handle) : MSMZ_ERR_ARG;
+}
+int msmz_scalars_dot(msmz_ctx* c, uint64_t xh, uint64_t first_x, uint64_t yh, uint64_t first_y, uint64_t n, uint8_t* out) {
+  return c && out ? c->engine->scalars_dot(xh, first_x, yh, first_y, n, out) : MSMZ_ERR_ARG;
+}
+int msmz_scalars_powers(msmz_ctx* c, const uint8_t* base, const uint8_t* ratio, uint64_t n, uint64_t* h) {
+  return c && ratio && h ? c->engine->scalars_powers(base, ratio, n, GenMap{}, h) : MSMZ_ERR_ARG;
+}
+void msmz_test_scalar_dot_geometry(uint32_t* tile_elements, uint32_t* partials_per_pass) {
+  if (tile_elements) *tile_elements = SDOT_TILE;
+  if (partials_per_pass) *partials_per_pass = SDOT_PASS;
+}
+
 int msmz_test_set_glv_bits(msmz_ctx* c, int bits) { return c ? c->engine->test_set_glv_bits(bits) : MSMZ_ERR_ARG; }
 int msmz_test_retries(msmz_ctx* c) { return c ? c->engine->test_retries() : -1; }
 int msmz_test_set_limits(msmz_ctx* c, uint64_t pass_entries, uint64_t batch_entries) {

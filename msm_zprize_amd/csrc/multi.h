@@ -20,6 +20,8 @@
 #include <vector>
 
 #include "../../include/msmz.h"
+#include "constants_gen.h"
+#include "fr.h"
 
 namespace msmz {
 
@@ -97,6 +99,12 @@ class IEngine {
                            uint8_t* verdicts) = 0;
   // msmz_points_mul: a new plain point handle, record i = [s_i] P_i (+ Q_i)
   virtual int points_mul(const msmz_mul& m, uint64_t n, uint64_t* h) = 0;
+  // msmz_scalars_combine / _dot / _powers: arithmetic mod q over resident scalar sets (scalar_kernels.h); `map` as for
+  // random_scalars
+  virtual int scalars_combine(const msmz_scalar_term& x, const msmz_scalar_term* y, uint64_t n, uint64_t first_out,
+                              uint64_t* out_handle) = 0;
+  virtual int scalars_dot(uint64_t xh, uint64_t first_x, uint64_t yh, uint64_t first_y, uint64_t n, uint8_t* out) = 0;
+  virtual int scalars_powers(const uint8_t* base, const uint8_t* ratio, uint64_t n, const GenMap& map, uint64_t* h) = 0;
   // tests (include/msmz_test.h); the stage-level hooks are one engine's (a multi-device context: its first engine's)
   virtual int test_set_glv_bits(int) { return MSMZ_ERR_UNSUPPORTED; }
   virtual int test_retries() { return 0; }
@@ -140,6 +148,17 @@ static inline void segment_classes(const uint64_t* n, uint32_t count, std::vecto
   starts->push_back(count);
   order->assign(count, 0);
   for (uint32_t k = 0; k < count; k++) (*order)[per[bits(n[k])]++] = k;
+}
+
+// acc = acc + part mod the group order of curve `curve_id` (8 words each, below q): the per-device sums of a dot product
+static inline int fold_scalar(int curve_id, uint32_t* acc, const uint32_t* part) {
+  switch (curve_id) {
+    case MSMZ_BLS12_377_G1: fr_add<Bls377Fr>(acc, acc, part); return MSMZ_OK;
+    case MSMZ_PALLAS: fr_add<PallasFr>(acc, acc, part); return MSMZ_OK;
+    case MSMZ_BLS12_381_G1: fr_add<Bls381Fr>(acc, acc, part); return MSMZ_OK;
+    case MSMZ_ED_ON_BLS12_377: fr_add<Ed377Fr>(acc, acc, part); return MSMZ_OK;
+    default: return MSMZ_ERR_UNSUPPORTED;
+  }
 }
 
 // entries of the first n that live on shard g of G
@@ -449,6 +468,90 @@ class MultiEngine : public IEngine {
       sub.scalars_handle = m.scalars_handle ? sit->second.sub[g] : 0;
       sub.addend_handle = m.addend_handle ? qit->second.sub[g] : 0;
       return e->points_mul(sub, cnt, &mh.sub[g]);
+    });
+    return finish_handle(st, mh, h);
+  }
+
+  // Every engine combines its own share.  Entry i of every operand and of the destination lives on one device only when
+  // all ranges start at 0 (as points_mul), and an existing destination is then written whole: n is its length.
+  int scalars_combine(const msmz_scalar_term& x, const msmz_scalar_term* y, uint64_t n, uint64_t first_out,
+                      uint64_t* out_handle) override {
+    if (!out_handle || n == 0 || n >> 32) return MSMZ_ERR_ARG;
+    const bool fresh = *out_handle == 0;
+    if (fresh && first_out != 0) return MSMZ_ERR_ARG;
+    auto scalars = [&](uint64_t h, uint64_t first) -> const MHandle* {
+      auto it = handles_.find(h);
+      if (it == handles_.end() || it->second.kind != 1 || first > it->second.n || n > it->second.n - first) return nullptr;
+      return &it->second;
+    };
+    const msmz_scalar_term* in[2] = {&x, y};
+    const MHandle* v[2] = {nullptr, nullptr};
+    const MHandle* c[2] = {nullptr, nullptr};
+    bool shifted = first_out != 0;
+    for (int k = 0; k < 2; k++) {
+      if (!in[k]) continue;
+      if (!(v[k] = scalars(in[k]->handle, in[k]->first))) return MSMZ_ERR_ARG;
+      if (in[k]->coeff_handle && !(c[k] = scalars(in[k]->coeff_handle, in[k]->coeff_first))) return MSMZ_ERR_ARG;
+      shifted = shifted || in[k]->first || (in[k]->coeff_handle && in[k]->coeff_first);
+    }
+    const MHandle* dst = nullptr;
+    if (!fresh && !(dst = scalars(*out_handle, first_out))) return MSMZ_ERR_ARG;
+    if (shifted || (dst && dst->n != n)) return MSMZ_ERR_UNSUPPORTED;
+    MHandle mh{1, n, std::vector<uint64_t>(G_, 0)};
+    int st = for_all([&](uint32_t g, IEngine* e) {
+      const uint64_t cnt = shard_count(n, g, G_);
+      if (cnt == 0) return (int)MSMZ_OK;
+      msmz_scalar_term sub[2];
+      for (int k = 0; k < 2; k++) {
+        if (!in[k]) continue;
+        sub[k] = *in[k];
+        sub[k].handle = v[k]->sub[g];
+        sub[k].coeff_handle = c[k] ? c[k]->sub[g] : 0;
+      }
+      if (dst) mh.sub[g] = dst->sub[g];
+      return e->scalars_combine(sub[0], y ? &sub[1] : nullptr, cnt, 0, &mh.sub[g]);
+    });
+    if (dst) return st;   // (written in place: the handle stays the caller's)
+    return finish_handle(st, mh, out_handle);
+  }
+
+  // every engine sums over its own share (both ranges from 0: a prefix of every share); the host adds the sums mod q
+  int scalars_dot(uint64_t xh, uint64_t first_x, uint64_t yh, uint64_t first_y, uint64_t n, uint8_t* out) override {
+    if (!out || n == 0 || n >> 32) return MSMZ_ERR_ARG;
+    auto xit = handles_.find(xh);
+    if (xit == handles_.end() || xit->second.kind != 1) return MSMZ_ERR_ARG;
+    auto yit = handles_.end();
+    if (yh) {
+      yit = handles_.find(yh);
+      if (yit == handles_.end() || yit->second.kind != 1) return MSMZ_ERR_ARG;
+    } else if (first_y) {
+      return MSMZ_ERR_ARG;
+    }
+    auto beyond = [n](const MHandle& s, uint64_t first) { return first > s.n || n > s.n - first; };
+    if (beyond(xit->second, first_x) || (yh && beyond(yit->second, first_y))) return MSMZ_ERR_ARG;
+    if (first_x || first_y) return MSMZ_ERR_UNSUPPORTED;
+    std::vector<uint32_t> part((size_t)G_ * 8, 0);
+    int st = for_all([&](uint32_t g, IEngine* e) {
+      const uint64_t cnt = shard_count(n, g, G_);
+      if (cnt == 0) return (int)MSMZ_OK;
+      return e->scalars_dot(xit->second.sub[g], 0, yh ? yit->second.sub[g] : 0, 0, cnt,
+                            reinterpret_cast<uint8_t*>(part.data() + (size_t)g * 8));
+    });
+    if (st) return st;
+    uint32_t acc[8] = {};
+    for (uint32_t g = 0; g < G_; g++)
+      if ((st = fold_scalar(curve_id_, acc, part.data() + (size_t)g * 8))) return st;
+    memcpy(out, acc, 32);
+    return MSMZ_OK;
+  }
+
+  int scalars_powers(const uint8_t* base, const uint8_t* ratio, uint64_t n, const GenMap&, uint64_t* h) override {
+    if (!h || !ratio || n == 0 || n >> 32) return MSMZ_ERR_ARG;
+    MHandle mh{1, n, std::vector<uint64_t>(G_, 0)};
+    int st = for_all([&](uint32_t g, IEngine* e) {
+      const uint64_t cnt = shard_count(n, g, G_);
+      if (cnt == 0) return (int)MSMZ_OK;
+      return e->scalars_powers(base, ratio, cnt, GenMap{G_, g, MULTI_BLOCK_SHIFT}, &mh.sub[g]);
     });
     return finish_handle(st, mh, h);
   }

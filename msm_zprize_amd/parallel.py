@@ -17,7 +17,7 @@ include/msmz.h -- this module contains no arithmetic.
 import ctypes as C
 
 from . import _native
-from ._native import MsmzCheckResult, MsmzLog, MsmzMul, MsmzOpts, MsmzSegment, MsmzSrc, check, lib
+from ._native import MsmzCheckResult, MsmzLog, MsmzMul, MsmzOpts, MsmzScalarTerm, MsmzSegment, MsmzSrc, check, lib
 
 _state = {"devices": None}
 
@@ -239,6 +239,45 @@ class _Parallel:
         h = C.c_uint64()
         check(lib().msmz_points_mul(self._c._ctx, C.byref(m), a["N"], C.byref(h)), "msmz_points_mul")
         return DeviceArray(self._c, h.value, a["N"], "points")
+
+    # -- arithmetic mod q over resident scalar arrays (msmz_scalars_*, include/msmz.h) -----------------
+    def combineScalars(self, a, x, b=None, y=None, N=None, firstX=0, firstY=0, out=None, firstOut=0, firstA=0, firstB=0):
+        """out[firstOut + i] = a_i x[firstX + i] (+ b_i y[firstY + i]) mod the group order, i < N.  `a` and `b` are Python
+        ints below the group order (one coefficient for every i) or resident scalar arrays (a_i = a[firstA + i]).
+        out=None: a new resident scalar array of N entries; otherwise entries [firstOut, firstOut + N) of `out` are
+        overwritten, and `out` may be `x`, `y` or a coefficient array when the range is exactly theirs or apart from it
+        (an IPA fold in place: combineScalars(1, v, uinv, v, N, firstY=N, out=v)).  Returns the array written."""
+        t = combine_scalars_args(a, x, b, y, N, firstX, firstY, out, firstOut, firstA, firstB, self._c.params["order"])
+        terms = [MsmzScalarTerm(v.handle, fv, 0 if c is None else c.handle, fc, k) for v, fv, c, fc, k in t["terms"]]
+        h = C.c_uint64(0 if out is None else out.handle)
+        check(lib().msmz_scalars_combine(self._c._ctx, C.byref(terms[0]), C.byref(terms[1]) if len(terms) > 1 else None,
+                                         t["N"], t["firstOut"], C.byref(h)), "msmz_scalars_combine")
+        return DeviceArray(self._c, h.value, t["N"], "scalars") if out is None else out
+
+    def innerProduct(self, x, y=None, N=None, firstX=0, firstY=0):
+        """sum_i x[firstX + i] y[firstY + i] mod the group order (y=None: sum_i x[firstX + i]) as a Python int; x and y
+        may be one array and may overlap."""
+        t = combine_scalars_args(1, x, None if y is None else 1, y, N, firstX, firstY, None, 0, 0, 0,
+                                 self._c.params["order"], "innerProduct")
+        buf = C.create_string_buffer(32)
+        check(lib().msmz_scalars_dot(self._c._ctx, x.handle, firstX, 0 if y is None else y.handle, firstY, t["N"], buf),
+              "msmz_scalars_dot")
+        return int.from_bytes(buf.raw, "little")
+
+    def scalarPowers(self, ratio, N, base=1):
+        """A new resident scalar array: entry i = base ratio^i mod the group order (0^0 = 1)."""
+        q = self._c.params["order"]
+        for name, v in (("ratio", ratio), ("base", base)):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise TypeError(f"scalarPowers: `{name}` is an int")
+            if not 0 <= v < q:
+                raise ValueError(f"scalarPowers: {name} = {v} is not in [0, group order)")
+        if isinstance(N, bool) or not isinstance(N, int) or not 1 <= N < 1 << 32:
+            raise ValueError(f"scalarPowers: N = {N!r}")
+        h = C.c_uint64()
+        check(lib().msmz_scalars_powers(self._c._ctx, base.to_bytes(32, "little"), ratio.to_bytes(32, "little"), N,
+                                        C.byref(h)), "msmz_scalars_powers")
+        return DeviceArray(self._c, h.value, N, "scalars")
 
     def _checked(self, arr, what, who):
         try:
@@ -558,6 +597,63 @@ def msm_segments_args(scalars, points, segments):
             raise ValueError(f"msmSegments: segment {k}: scalars [{firstScalar}, +{N}) of a set of {len(scalars)}")
         out.append((firstPoint, firstScalar, N))
     return out
+
+
+def combine_scalars_args(a, x, b, y, N, firstX, firstY, out, firstOut, firstA, firstB, order, who="combineScalars"):
+    """Arguments of combineScalars -> dict(N, firstOut, terms), checked before anything reaches the device.  terms: one
+    or two of (array, first, coefficient array or None, its first, 32 little-endian bytes of a broadcast coefficient or
+    None: a coefficient array, or the coefficient 1)."""
+    def scalars(v):
+        return isinstance(v, DeviceArray) and v.kind == "scalars"
+
+    if not scalars(x):
+        raise TypeError(f"{who}: `x` is a resident scalar array")
+    if (b is None) != (y is None):
+        raise TypeError(f"{who}: `b` and `y` come together")
+    if y is not None and not scalars(y):
+        raise TypeError(f"{who}: `y` is a resident scalar array or None")
+    if out is not None and not scalars(out):
+        raise TypeError(f"{who}: `out` is a resident scalar array or None")
+    ranges = [("firstX", firstX, x), ("firstY", firstY, y)]
+    coeffs = []
+    for name, first_name, c, first in (("a", "firstA", a, firstA), ("b", "firstB", b, firstB)):
+        if name == "b" and y is None:
+            ranges.append((first_name, first, None))
+            continue
+        if isinstance(c, int) and not isinstance(c, bool):
+            if not 0 <= c < order:
+                raise ValueError(f"{who}: the coefficient {name} = {c} is not in [0, group order)")
+            coeffs.append((None, None if c == 1 else c.to_bytes(32, "little")))   # (1: no product at all)
+            ranges.append((first_name, first, None))
+        elif scalars(c):
+            coeffs.append((c, None))
+            ranges.append((first_name, first, c))
+        else:
+            raise TypeError(f"{who}: `{name}` is an int (one coefficient for every entry) or a resident scalar array")
+    ranges.append(("firstOut", firstOut, out))
+    for name, first, arr in ranges:
+        if isinstance(first, bool) or not isinstance(first, int) or first < 0:
+            raise ValueError(f"{who}: {name} = {first!r}")
+        if arr is None and first != 0:
+            raise ValueError(f"{who}: {name} = {first} without the array it indexes")
+        if arr is not None and first >= len(arr):
+            raise ValueError(f"{who}: {name} = {first} but the array holds {len(arr)}")
+    if N is None:
+        N = min(len(arr) - first for _, first, arr in ranges if arr is not None)
+    if isinstance(N, bool) or not isinstance(N, int) or not 1 <= N < 1 << 32:
+        raise ValueError(f"{who}: N = {N!r}")
+    for name, first, arr in ranges:
+        if arr is not None and N > len(arr) - first:
+            raise ValueError(f"{who}: entries [{first}, +{N}) from {name} of an array of {len(arr)}")
+    if out is not None:
+        for name, first, arr in ranges[:-1]:
+            if arr is not None and arr.handle == out.handle and first != firstOut and abs(first - firstOut) < N:
+                raise ValueError(f"{who}: the destination [{firstOut}, +{N}) overlaps the input range [{first}, +{N}) "
+                                 f"({name}) in part; it may be that range exactly or apart from it")
+    terms = [(x, firstX) + (coeffs[0][0], firstA if coeffs[0][0] is not None else 0, coeffs[0][1])]
+    if y is not None:
+        terms.append((y, firstY) + (coeffs[1][0], firstB if coeffs[1][0] is not None else 0, coeffs[1][1]))
+    return {"N": N, "firstOut": firstOut, "terms": terms}
 
 
 def check_arg(check, who):

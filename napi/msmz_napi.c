@@ -497,6 +497,74 @@ static napi_value MulPoints(napi_env env, napi_callback_info info) {
   return make_handle(env, h);
 }
 
+/* a coefficient argument of scalarsCombine: a 32-byte Buffer (one scalar for every entry, little-endian), null (1), or
+   the handle of a resident scalar array */
+static int get_coeff(napi_env env, napi_value v, msmz_scalar_term* t) {
+  bool isbuf = false; napi_is_buffer(env, v, &isbuf);
+  if (isbuf) {
+    void* s; size_t slen;
+    if (napi_get_buffer_info(env, v, &s, &slen) != napi_ok || slen != 32) return 0;
+    t->coeff = (const uint8_t*)s;
+    return 1;
+  }
+  napi_valuetype ty;
+  if (napi_typeof(env, v, &ty) != napi_ok) return 0;
+  if (ty == napi_null || ty == napi_undefined) return 1;
+  return get_u64(env, v, &t->coeff_handle) && t->coeff_handle != 0;
+}
+
+/* scalarsCombine(ctx, xHandle, xFirst, xCoeff, xCoeffFirst, yHandle (0 = no second term), yFirst, yCoeff, yCoeffFirst, n,
+   firstOut, outHandle (0 = a new array)) -> handle of the array written: entry i = xCoeff_i x_i (+ yCoeff_i y_i)
+   (msmz_scalars_combine) */
+static napi_value ScalarsCombine(napi_env env, napi_callback_info info) {
+  size_t argc = 12; napi_value argv[12];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  msmz_ctx* ctx; if (argc < 12 || !get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "scalarsCombine");
+  msmz_scalar_term x, y; memset(&x, 0, sizeof(x)); memset(&y, 0, sizeof(y));
+  uint64_t n, first_out, h = 0;
+  if (!get_u64(env, argv[1], &x.handle) || !get_u64(env, argv[2], &x.first) || !get_coeff(env, argv[3], &x) ||
+      !get_u64(env, argv[4], &x.coeff_first) || !get_u64(env, argv[5], &y.handle) || !get_u64(env, argv[6], &y.first) ||
+      !get_coeff(env, argv[7], &y) || !get_u64(env, argv[8], &y.coeff_first) || !get_u64(env, argv[9], &n) ||
+      !get_u64(env, argv[10], &first_out) || !get_u64(env, argv[11], &h))
+    return throw_status(env, MSMZ_ERR_ARG, "scalarsCombine");
+  int st = msmz_scalars_combine(ctx, &x, y.handle ? &y : NULL, n, first_out, &h);
+  if (st) return throw_status(env, st, "msmz_scalars_combine");
+  return make_handle(env, h);
+}
+
+/* scalarsDot(ctx, xHandle, xFirst, yHandle (0 = the plain sum of x), yFirst, n) -> 32-byte Buffer, little-endian
+   (msmz_scalars_dot) */
+static napi_value ScalarsDot(napi_env env, napi_callback_info info) {
+  size_t argc = 6; napi_value argv[6];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  msmz_ctx* ctx; if (argc < 6 || !get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "scalarsDot");
+  uint64_t xh, fx, yh, fy, n;
+  if (!get_u64(env, argv[1], &xh) || !get_u64(env, argv[2], &fx) || !get_u64(env, argv[3], &yh) || !get_u64(env, argv[4], &fy) ||
+      !get_u64(env, argv[5], &n))
+    return throw_status(env, MSMZ_ERR_ARG, "scalarsDot");
+  void* data; napi_value buf;
+  NAPI_CALL(env, napi_create_buffer(env, 32, &data, &buf));
+  int st = msmz_scalars_dot(ctx, xh, fx, yh, fy, n, (uint8_t*)data);
+  if (st) return throw_status(env, st, "msmz_scalars_dot");
+  return buf;
+}
+
+/* scalarsPowers(ctx, base (32-byte Buffer or null = 1), ratio (32-byte Buffer), n) -> handle of a new scalar array, entry
+   i = base ratio^i (msmz_scalars_powers) */
+static napi_value ScalarsPowers(napi_env env, napi_callback_info info) {
+  size_t argc = 4; napi_value argv[4];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  msmz_ctx* ctx; if (argc < 4 || !get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "scalarsPowers");
+  msmz_scalar_term base, ratio; memset(&base, 0, sizeof(base)); memset(&ratio, 0, sizeof(ratio));
+  uint64_t n, h = 0;
+  if (!get_coeff(env, argv[1], &base) || base.coeff_handle || !get_coeff(env, argv[2], &ratio) || !ratio.coeff ||
+      !get_u64(env, argv[3], &n))
+    return throw_status(env, MSMZ_ERR_ARG, "scalarsPowers");
+  int st = msmz_scalars_powers(ctx, base.coeff, ratio.coeff, n, &h);
+  if (st) return throw_status(env, st, "msmz_scalars_powers");
+  return make_handle(env, h);
+}
+
 static napi_value PointAdd(napi_env env, napi_callback_info info) {
   size_t argc = 4; napi_value argv[4];
   NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -534,7 +602,8 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"randomPoints", RandomPoints}, {"randomScalars", RandomScalars}, {"downloadPoints", DownloadPoints},
       {"downloadScalars", DownloadScalars}, {"free", Free}, {"msm", Msm}, {"msmBatch", MsmBatch}, {"msmSegments", MsmSegments},
       {"precomputePoints", PrecomputePoints}, {"precomputedInfo", PrecomputedInfo}, {"checkPoints", CheckPoints},
-      {"mulPoints", MulPoints}, {"pointAdd", PointAdd}, {"feBytes", FeBytes}};
+      {"mulPoints", MulPoints}, {"scalarsCombine", ScalarsCombine}, {"scalarsDot", ScalarsDot},
+      {"scalarsPowers", ScalarsPowers}, {"pointAdd", PointAdd}, {"feBytes", FeBytes}};
   for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); i++) {
     napi_value f;
     if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;

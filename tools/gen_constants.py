@@ -164,6 +164,8 @@ def main():
         L.append("  static constexpr int BITS = %d;" % q.bit_length())
         L.append(arr("Q", limbs(q, 8)))
         L.append("  static constexpr uint32_t QINV32 = 0x%08xu;  // -q^-1 mod 2^32 (fr_from_mont, scalar.h)" % ((-pow(q, -1, 1 << 32)) % (1 << 32)))
+        L.append(arr("R2", limbs(pow(2, 512, q), 8)) + "   // 2^512 mod q: fr_mont_mul by it multiplies by 2^256 (fr.h)")
+        L.append(arr("ONE", limbs(pow(2, 256, q), 8)) + "  // 2^256 mod q: the Montgomery form of 1")
         L.append("  static constexpr bool PRIME_ORDER = %s;  // true iff the cofactor is 1, i.e. the whole curve is the subgroup (check_kernels.h)" % ("true" if c["cofactor"] == 1 else "false"))
         if c["kind"] == "weierstrass":
             lam = c["endomorphism"]["lambda_"]
