@@ -382,6 +382,50 @@ int msmz_scalars_dot(msmz_ctx* ctx, uint64_t x_handle, uint64_t first_x, uint64_
                      uint8_t* out_le32);
 int msmz_scalars_powers(msmz_ctx* ctx, const uint8_t* base_le32, const uint8_t* ratio_le32, uint64_t n, uint64_t* handle);
 
+/* What is sequential in the index, and inversion, over resident scalar sets.
+ *
+ * msmz_scalars_recurrence: the first-order linear recurrence y_i = a_i * y_(i-1) + b_i mod q, i = 0 .. n-1, from
+ * y_(-1) = init; with MSMZ_REC_REVERSE y_i = a_i * y_(i+1) + b_i, i = n-1 .. 0, from y_n = init.  Output entry
+ * first_out + i is y_i; with MSMZ_REC_EXCLUSIVE it is the value the step at i started from (y_(i-1) forward, y_(i+1)
+ * reverse), so the first entry in scan order is init.  last_le32 (nullable) receives the final y (y_(n-1) forward, y_0
+ * reverse), the same with or without EXCLUSIVE; it comes back in the copy that brings the error word: one host wait.
+ *
+ *   use                  multiplier           addend         flags                 result
+ *   prefix sums          a NULL               b resident     -                     running sums
+ *   prefix products      a resident           none           -                     running products
+ *   grand product        a resident           none           EXCLUSIVE             Z_0 = 1, Z_(i+1) = Z_i a_i; last = the full product
+ *   division by X - z    a = z (broadcast)    b = p          REVERSE | EXCLUSIVE   entry i = coefficient i of the quotient
+ *                                                                                  (entry n-1 = 0); last = p(z)
+ * The quotient of the last row is a scalar set of n entries: an MSM takes it against the same n points as p.
+ * A broadcast multiplier without an addend gives init * a^(i+1).  No multiplier and no addend is MSMZ_ERR_ARG.
+ *
+ * msmz_scalars_inverse: out_i = x_i^-1 mod q over entries [first, first + n) of `handle`; 0 -> 0 (the convention of
+ * arkworks' batch_inversion), and *n_zero (nullable) receives the number of zero entries in the range.
+ *
+ * Output, errors and in-place operation are those of msmz_scalars_combine: *out_handle == 0 makes a new handle of n
+ * entries (first_out must be 0), otherwise [first_out, first_out + n) of that handle is overwritten and nothing else;
+ * the destination may coincide exactly with an input range or be disjoint from it, a partial overlap is MSMZ_ERR_ARG;
+ * results are below q.  MSMZ_ERR_ARG before any launch: a null ctx, r or out_handle; n == 0 or n >= 2^32; unknown flag
+ * bits; an unknown handle or one that is not a scalar set; a range beyond its set.  MSMZ_ERR_RANGE: a broadcast a or
+ * init >= q (found on the host, nothing is launched) or a resident entry >= q inside an addressed range (found by the
+ * kernel; entries outside are not read); then no handle is created, *out_handle, *last_le32 and *n_zero are as they
+ * were and an in-place destination is unspecified.
+ * Multi-device contexts: inverse is element-wise and takes the route of combine (every first 0, a new handle or a
+ * whole existing one; anything else MSMZ_ERR_UNSUPPORTED).  recurrence is MSMZ_ERR_UNSUPPORTED there: consecutive
+ * blocks of 2^16 entries live on different devices and the dependency crosses every block boundary. */
+enum { MSMZ_REC_REVERSE = 1, MSMZ_REC_EXCLUSIVE = 2 };
+typedef struct msmz_scalar_rec {
+  uint64_t a_handle, a_first;  /* multipliers a_i as a resident range, or a_handle == 0: one scalar `a` for every i */
+  const uint8_t* a;            /* 32 bytes little-endian, < q; read only when a_handle == 0; NULL = 1 */
+  uint64_t b_handle, b_first;  /* addends b_i as a resident range, or b_handle == 0: none (b_i = 0) */
+  const uint8_t* init;         /* the value before the first step; NULL = 0 with an addend, 1 without one */
+  uint32_t flags;              /* MSMZ_REC_* */
+} msmz_scalar_rec;
+int msmz_scalars_recurrence(msmz_ctx* ctx, const msmz_scalar_rec* r, uint64_t n, uint64_t first_out,
+                            uint64_t* out_handle, uint8_t* last_le32);
+int msmz_scalars_inverse(msmz_ctx* ctx, uint64_t handle, uint64_t first, uint64_t n, uint64_t first_out,
+                         uint64_t* out_handle, uint64_t* n_zero);
+
 /* Host-side group addition of two canonical affine results: combines per-GPU partial sums
  * (the reference's "partition sum" step, msm-batched-affine.ts:300-307). */
 int msmz_point_add(int curve_id, const uint8_t* a_xy_le, int a_is_inf, const uint8_t* b_xy_le, int b_is_inf,

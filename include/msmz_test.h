@@ -83,6 +83,12 @@ int msmz_test_passes(msmz_ctx* ctx, uint64_t* range_passes, uint64_t* sub_batche
  *   tile_elements    : elements one workgroup of the first level sums into one partial sum (SDOT_TILE);
  *   partials_per_pass: partial sums the second level's one workgroup takes per pass of its loop (SDOT_PASS). */
 void msmz_test_scalar_dot_geometry(uint32_t* tile_elements, uint32_t* partials_per_pass);
+/* The geometry of msmz_scalars_recurrence and msmz_scalars_inverse (csrc/scan_kernels.h), for the same purpose (every
+ * pointer nullable; needs no context):
+ *   rec_tile : scan positions one workgroup composes into one aggregate map (SREC_TILE);
+ *   rec_pass : tile aggregates the one workgroup of the carry launch takes per pass of its loop (SREC_PASS);
+ *   inv_chunk: elements that share one field inversion, one wave's share (SINV_CHUNK). */
+void msmz_test_scalar_scan_geometry(uint32_t* rec_tile, uint32_t* rec_pass, uint32_t* inv_chunk);
 /* out[i] = op(a[i], b[i]) for i < n; a, b, out: n * fe_bytes */
 int msmz_test_field(msmz_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out);
 /* GLV split of n 32-byte scalars: s0, s1 = magnitudes (16 bytes each), neg = 2 sign bytes per scalar

@@ -47,6 +47,22 @@ export interface ParallelApi {
   innerProduct(x: DeviceArray, y?: DeviceArray | null, n?: number, options?: { firstX?: number; firstY?: number }): Promise<bigint>;
   /** a new scalar array: entry i = base ratio^i mod the group order */
   scalarPowers(ratio: bigint, n: number, base?: bigint): Promise<DeviceArray>;
+  /** y_i = a_i y_(i-1) + b_i mod the group order from y_(-1) = init (reverse: y_i = a_i y_(i+1) + b_i from y_n = init);
+   * a: a resident scalar array, one bigint for every entry or null (1); b: a resident scalar array or null; entry i of the
+   * result is y_i, with `exclusive` the value before the step at i -> [the array written, the final y] */
+  scalarRecurrence(a: DeviceArray | bigint | null, b: DeviceArray | null, n?: number,
+                   options?: { init?: bigint | null; reverse?: boolean; exclusive?: boolean; firstA?: number; firstB?: number;
+                               out?: DeviceArray | null; firstOut?: number }): Promise<[DeviceArray, bigint]>;
+  /** running products -> [array, the full product]; exclusive: entry 0 is 1 */
+  prefixProducts(x: DeviceArray, n?: number, options?: { exclusive?: boolean; init?: bigint | null; reverse?: boolean; first?: number;
+                                                          out?: DeviceArray | null; firstOut?: number }): Promise<[DeviceArray, bigint]>;
+  /** running sums -> [array, the full sum] */
+  prefixSums(x: DeviceArray, n?: number, options?: { exclusive?: boolean; init?: bigint | null; reverse?: boolean; first?: number;
+                                                      out?: DeviceArray | null; firstOut?: number }): Promise<[DeviceArray, bigint]>;
+  /** (p(X) - p(z)) / (X - z) -> [the quotient's n coefficients (the top one 0), p(z)] */
+  divideByLinear(p: DeviceArray, z: bigint, n?: number, options?: { first?: number }): Promise<[DeviceArray, bigint]>;
+  /** out[firstOut + i] = x[first + i]^-1 mod the group order, 0 -> 0 -> [the array written, the number of zeros] */
+  invertScalars(x: DeviceArray, n?: number, options?: { first?: number; out?: DeviceArray | null; firstOut?: number }): Promise<[DeviceArray, number]>;
   msmBatch(scalarsList: DeviceArray | Uint8Array[], points: DeviceArray, n: number, options?: MsmOptions & { batch?: number }): Promise<BigintPoint[]>;
   msmBatchUnsafe(scalarsList: DeviceArray | Uint8Array[], points: DeviceArray, n: number, options?: MsmOptions & { batch?: number }): Promise<BigintPoint[]>;
   /** one MSM per segment [firstPoint, firstScalar, n] of one resident scalar array and one resident point array */

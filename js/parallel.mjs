@@ -62,6 +62,25 @@ function bigintToBytes(x, len) {
   return out;
 }
 
+/** the range checks shared by scalarRecurrence and invertScalars: ranges = [[name, first, array or null], ...], the last
+ * one the destination -> n */
+function scanRanges(who, ranges, n, out, firstOut) {
+  for (const [name, first, arr] of ranges) {
+    if (!Number.isInteger(first) || first < 0 || (arr === null ? first !== 0 : first >= arr.n))
+      throw Error(`${who}: ${name} = ${first}` + (arr === null ? " without the array it indexes" : ` but the array holds ${arr.n}`));
+  }
+  if ((n === undefined || n === null) && ranges.some((r) => r[2] !== null))
+    n = Math.min(...ranges.filter((r) => r[2] !== null).map(([, first, arr]) => arr.n - first));
+  if (!Number.isInteger(n) || n < 1 || n >= 2 ** 32) throw Error(`${who}: n = ${n}`);
+  for (const [name, first, arr] of ranges)
+    if (arr !== null && n > arr.n - first) throw Error(`${who}: entries [${first}, +${n}) from ${name} of an array of ${arr.n}`);
+  if (out !== null)
+    for (const [name, first, arr] of ranges.slice(0, -1))
+      if (arr !== null && arr.handle === out.handle && first !== firstOut && Math.abs(first - firstOut) < n)
+        throw Error(`${who}: the destination [${firstOut}, +${n}) overlaps the input range [${first}, +${n}) (${name}) in part`);
+  return n;
+}
+
 /** A GPU-resident input array; destructures like the reference's pointer arrays: `let [ptr] = ...` */
 class DeviceArray extends Array {
   static make(curve, handle, n, kind) {
@@ -390,6 +409,53 @@ function createCurve(params, kind) {
       if (!Number.isInteger(n) || n < 1 || n >= 2 ** 32) throw Error(`scalarPowers: n = ${n}`);
       const h = N.scalarsPowers(ctx, Buffer.from(bigintToBytes(base, 32)), Buffer.from(bigintToBytes(ratio, 32)), n);
       return DeviceArray.make(curve, h, n, "scalars");
+    },
+    /** the first-order linear recurrence y_i = a_i y_(i-1) + b_i mod the group order, i < n, from y_(-1) = init
+     * (include/msmz.h msmz_scalars_recurrence; reverse: y_i = a_i y_(i+1) + b_i from y_n = init).  `a`: a resident scalar
+     * array (a_i = a[firstA + i]), a bigint (one multiplier for every entry) or null (1); `b`: a resident scalar array or
+     * null (no addend); not both null.  init null: 0n with an addend, 1n without.  out[firstOut + i] = y_i, or with
+     * `exclusive` the value the step at i started from.  Without `out` the result is a new array; `out` may be `a` or `b`
+     * when the range is exactly theirs or apart from it.  Returns [the array written, the final y]. */
+    async scalarRecurrence(a, b, n, { init = null, reverse = false, exclusive = false, firstA = 0, firstB = 0, out = null, firstOut = 0 } = {}) {
+      const isScalars = (v) => v instanceof DeviceArray && v.kind === "scalars";
+      const broadcast = typeof a === "bigint";
+      if (a !== null && !broadcast && !isScalars(a)) throw TypeError("scalarRecurrence: `a` is a resident scalar array, a bigint or null");
+      if (b !== null && !isScalars(b)) throw TypeError("scalarRecurrence: `b` is a resident scalar array or null");
+      if (a === null && b === null) throw TypeError("scalarRecurrence: neither a multiplier nor an addend");
+      if (out !== null && !isScalars(out)) throw TypeError("scalarRecurrence: `out` is a resident scalar array or null");
+      if (init !== null && typeof init !== "bigint") throw TypeError("scalarRecurrence: `init` is a bigint or null");
+      for (const [name, v] of [["a", broadcast ? a : null], ["init", init]])
+        if (v !== null && (v < 0n || v >= params.order)) throw Error(`scalarRecurrence: ${name} = ${v} is not in [0, group order)`);
+      n = scanRanges("scalarRecurrence", [["firstA", firstA, isScalars(a) ? a : null], ["firstB", firstB, b], ["firstOut", firstOut, out]], n, out, firstOut);
+      const r = N.scalarsRecurrence(ctx, broadcast ? Buffer.from(bigintToBytes(a, 32)) : a === null ? null : a.handle, firstA,
+                                    b === null ? 0 : b.handle, firstB, init === null ? null : Buffer.from(bigintToBytes(init, 32)),
+                                    (reverse ? 1 : 0) | (exclusive ? 2 : 0), n, firstOut, out === null ? 0 : out.handle);
+      return [out === null ? DeviceArray.make(curve, r.handle, n, "scalars") : out, bytesToBigint(r.last, 0, 32)];
+    },
+    /** running products of x[first + i]: [array, the full product]; exclusive: entry 0 is 1 (a grand product column) */
+    prefixProducts(x, n, { exclusive = false, init = null, reverse = false, first = 0, out = null, firstOut = 0 } = {}) {
+      return this.scalarRecurrence(x, null, n, { init, reverse, exclusive, firstA: first, out, firstOut });
+    },
+    /** running sums of x[first + i]: [array, the full sum] */
+    prefixSums(x, n, { exclusive = false, init = null, reverse = false, first = 0, out = null, firstOut = 0 } = {}) {
+      return this.scalarRecurrence(null, x, n, { init, reverse, exclusive, firstB: first, out, firstOut });
+    },
+    /** (p(X) - p(z)) / (X - z) for the coefficients p[first + i], i < n, lowest degree first: [quotient, p(z)].  The
+     * quotient has n entries, the top one 0: an MSM takes it against the same n points as p (a KZG opening proof). */
+    async divideByLinear(p, z, n, { first = 0 } = {}) {
+      if (typeof z !== "bigint") throw TypeError("divideByLinear: `z` is a bigint");
+      if (!(p instanceof DeviceArray) || p.kind !== "scalars") throw TypeError("divideByLinear: `p` is a resident scalar array");
+      return this.scalarRecurrence(z, p, n, { init: 0n, reverse: true, exclusive: true, firstB: first });
+    },
+    /** out[firstOut + i] = x[first + i]^-1 mod the group order, 0 -> 0 (msmz_scalars_inverse): [the array written, the
+     * number of zeros].  `out` may be `x` over exactly the same range (in place) or apart from it. */
+    async invertScalars(x, n, { first = 0, out = null, firstOut = 0 } = {}) {
+      const isScalars = (v) => v instanceof DeviceArray && v.kind === "scalars";
+      if (!isScalars(x)) throw TypeError("invertScalars: `x` is a resident scalar array");
+      if (out !== null && !isScalars(out)) throw TypeError("invertScalars: `out` is a resident scalar array or null");
+      n = scanRanges("invertScalars", [["first", first, x], ["firstOut", firstOut, out]], n, out, firstOut);
+      const r = N.scalarsInverse(ctx, x.handle, first, n, firstOut, out === null ? 0 : out.handle);
+      return [out === null ? DeviceArray.make(curve, r.handle, n, "scalars") : out, r.zeros];
     },
     /** batched MSM: B scalar vectors against one point set (include/msmz.h msmz_msm_batch); safe additions */
     msmBatch: (scalarsList, points, n, options) => msmBatchCommon(scalarsList, points, n, options, 1),

@@ -51,6 +51,14 @@ class MsmzScalarTerm(C.Structure):   # msmz_scalar_term (include/msmz.h): one te
                 ("coeff", C.c_char_p)]
 
 
+MSMZ_REC_REVERSE, MSMZ_REC_EXCLUSIVE = 1, 2
+
+
+class MsmzScalarRec(C.Structure):   # msmz_scalar_rec (include/msmz.h): y_i = a_i y_(i-1) + b_i
+    _fields_ = [("a_handle", C.c_uint64), ("a_first", C.c_uint64), ("a", C.c_char_p), ("b_handle", C.c_uint64),
+                ("b_first", C.c_uint64), ("init", C.c_char_p), ("flags", C.c_uint32)]
+
+
 class MsmzSegment(C.Structure):   # msmz_segment (include/msmz.h): one problem of msmz_msm_segments
     _fields_ = [("first_p", C.c_uint64), ("first_s", C.c_uint64), ("n", C.c_uint64)]
 
@@ -129,6 +137,10 @@ EXPORTS = {
                                        C.c_uint64, C.POINTER(C.c_uint64)]),
     "msmz_scalars_dot": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_char_p]),
     "msmz_scalars_powers": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "msmz_scalars_recurrence": (C.c_int, [C.c_void_p, C.POINTER(MsmzScalarRec), C.c_uint64, C.c_uint64,
+                                          C.POINTER(C.c_uint64), C.c_char_p]),
+    "msmz_scalars_inverse": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_uint64)]),
     "msmz_point_add": (C.c_int, [C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.POINTER(C.c_int)]),
     # stage-level test hooks (include/msmz_test.h)
     "msmz_test_set_glv_bits": (C.c_int, [C.c_void_p, C.c_int]),
@@ -136,6 +148,7 @@ EXPORTS = {
     "msmz_test_set_limits": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
     "msmz_test_passes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "msmz_test_scalar_dot_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "msmz_test_scalar_scan_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "msmz_test_field": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_uint64, C.c_char_p]),
     "msmz_test_field_limbs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                         C.c_char_p]),

@@ -823,6 +823,123 @@ class Engine : public IEngine {
     return add_handle(std::move(hd), h);
   }
 
+  // A range of n entries of a scalar set for msmz_scalars_recurrence / _inverse -> its first record; false: not a scalar
+  // set, beyond it, or overlapping the destination [first_out, +n) of *out_handle in part (fresh: no destination yet).
+  bool scan_range(uint64_t h, uint64_t first, uint64_t n, bool fresh, uint64_t out_handle, uint64_t first_out,
+                  const uint32_t** p) {
+    auto it = handles_.find(h);
+    if (it == handles_.end() || it->second.kind != 1 || first > it->second.n || n > it->second.n - first) return false;
+    if (!fresh && h == out_handle && first != first_out && (first > first_out ? first - first_out : first_out - first) < n)
+      return false;
+    *p = it->second.mem.template as<const uint32_t>() + first * 8;
+    return true;
+  }
+
+  // msmz_scalars_recurrence: three launches (tile aggregates, ONE workgroup of carries, apply); the final value and the
+  // error word share a 64-byte record in front of the scratch and come back in ONE copy behind ONE host wait.
+  int scalars_recurrence(const msmz_scalar_rec& r, uint64_t n, uint64_t first_out, uint64_t* out_handle,
+                         uint8_t* last) override {
+    if (!out_handle || n == 0 || n >> 32 || (r.flags & ~(uint32_t)(MSMZ_REC_REVERSE | MSMZ_REC_EXCLUSIVE)))
+      return MSMZ_ERR_ARG;
+    if (!r.a_handle && !r.a && !r.b_handle) return MSMZ_ERR_ARG;   // y_i = y_(i-1): nothing to do
+    const bool fresh = *out_handle == 0;
+    if (fresh && first_out != 0) return MSMZ_ERR_ARG;
+    const uint32_t *A = nullptr, *B = nullptr;
+    if (r.a_handle && !scan_range(r.a_handle, r.a_first, n, fresh, *out_handle, first_out, &A)) return MSMZ_ERR_ARG;
+    if (r.b_handle && !scan_range(r.b_handle, r.b_first, n, fresh, *out_handle, first_out, &B)) return MSMZ_ERR_ARG;
+    uint32_t* out = nullptr;
+    if (!fresh) {
+      auto it = handles_.find(*out_handle);
+      if (it == handles_.end() || it->second.kind != 1 || first_out > it->second.n || n > it->second.n - first_out)
+        return MSMZ_ERR_ARG;
+      out = it->second.mem.template as<uint32_t>() + first_out * 8;
+    }
+    FrConst k{}, init{};
+    if (!r.a_handle && r.a) {
+      uint32_t c[8];
+      memcpy(c, r.a, 32);
+      if (words_geq<8>(c, Fr::Q)) return MSMZ_ERR_RANGE;
+      fr_to_mont<Fr>(k.w, c);
+    }
+    if (r.init) {
+      memcpy(init.w, r.init, 32);
+      if (words_geq<8>(init.w, Fr::Q)) return MSMZ_ERR_RANGE;
+    } else if (!B) {
+      init.w[0] = 1;
+    }
+    MSMZ_HIP(hipSetDevice(device_));
+    Handle hd{1, n, false};
+    if (fresh) {
+      if (int st = alloc_handle(hd, n * 32)) return st;
+      out = hd.mem.as<uint32_t>();
+    }
+    const uint32_t tiles = (uint32_t)((n + SREC_TILE - 1) / SREC_TILE);
+    // words 0..7: the final value, word 8: the error word; then the aggregates' A, their B, and tiles + 1 incoming values
+    if (int st = sscan_.ensure(64 + ((size_t)tiles * 3 + 1) * 32)) return st;
+    uint32_t* d_res = sscan_.as<uint32_t>();
+    uint32_t* aggA = d_res + 16;
+    uint32_t* aggB = aggA + (size_t)tiles * 8;
+    uint32_t* incoming = aggB + (size_t)tiles * 8;
+    MSMZ_HIP(hipMemsetAsync(d_res, 0, 64, stream_));
+    const uint32_t nn = (uint32_t)n, flags = r.flags;
+    const dim3 grid(tiles), block(SREC_THREADS);
+#define MSMZ_REC_LAUNCH(AM, HB)                                                                                          \
+  do {                                                                                                                   \
+    hipLaunchKernelGGL((k_scalars_rec_tile<Fr, AM, HB>), grid, block, 0, stream_, aggA, aggB, A, B, k, nn, flags, d_res + 8); \
+    hipLaunchKernelGGL((k_scalars_rec_carry<Fr, AM != SREC_A_NONE, HB>), dim3(1), block, 0, stream_, incoming, d_res,    \
+                       (const uint32_t*)aggA, (const uint32_t*)aggB, init, tiles);                                       \
+    hipLaunchKernelGGL((k_scalars_rec_apply<Fr, AM, HB>), grid, block, 0, stream_, out, A, B, k, (const uint32_t*)incoming, \
+                       nn, flags);                                                                                       \
+  } while (0)
+    if (A && B) MSMZ_REC_LAUNCH(SREC_A_RESIDENT, true);
+    else if (A) MSMZ_REC_LAUNCH(SREC_A_RESIDENT, false);
+    else if (r.a && B) MSMZ_REC_LAUNCH(SREC_A_BROADCAST, true);
+    else if (r.a) MSMZ_REC_LAUNCH(SREC_A_BROADCAST, false);
+    else MSMZ_REC_LAUNCH(SREC_A_NONE, true);
+#undef MSMZ_REC_LAUNCH
+    MSMZ_HIP(hipGetLastError());
+    MSMZ_HIP(hipMemcpyAsync(h_res_, d_res, 64, hipMemcpyDeviceToHost, stream_));   // (pinned: init sized it for far more)
+    MSMZ_HIP(hipStreamSynchronize(stream_));
+    if (h_res_[8]) return MSMZ_ERR_RANGE;   // a resident record >= group order
+    if (last) memcpy(last, h_res_, 32);
+    return fresh ? add_handle(std::move(hd), out_handle) : (int)MSMZ_OK;
+  }
+
+  // msmz_scalars_inverse: one launch; the error word and the zero count share the record
+  int scalars_inverse(uint64_t h, uint64_t first, uint64_t n, uint64_t first_out, uint64_t* out_handle,
+                      uint64_t* n_zero) override {
+    if (!out_handle || n == 0 || n >> 32) return MSMZ_ERR_ARG;
+    const bool fresh = *out_handle == 0;
+    if (fresh && first_out != 0) return MSMZ_ERR_ARG;
+    const uint32_t* X = nullptr;
+    if (!scan_range(h, first, n, fresh, *out_handle, first_out, &X)) return MSMZ_ERR_ARG;
+    uint32_t* out = nullptr;
+    if (!fresh) {
+      auto it = handles_.find(*out_handle);
+      if (it == handles_.end() || it->second.kind != 1 || first_out > it->second.n || n > it->second.n - first_out)
+        return MSMZ_ERR_ARG;
+      out = it->second.mem.template as<uint32_t>() + first_out * 8;
+    }
+    MSMZ_HIP(hipSetDevice(device_));
+    Handle hd{1, n, false};
+    if (fresh) {
+      if (int st = alloc_handle(hd, n * 32)) return st;
+      out = hd.mem.as<uint32_t>();
+    }
+    if (int st = sscan_.ensure(64)) return st;
+    uint32_t* d_res = sscan_.as<uint32_t>();   // word 8: the error word, word 9: the zeros
+    MSMZ_HIP(hipMemsetAsync(d_res, 0, 64, stream_));
+    const uint64_t per_block = (uint64_t)SINV_THREADS * SINV_E;
+    hipLaunchKernelGGL((k_scalars_inverse<Fr>), dim3((uint32_t)((n + per_block - 1) / per_block)), dim3(SINV_THREADS), 0,
+                       stream_, out, X, (uint32_t)n, d_res);
+    MSMZ_HIP(hipGetLastError());
+    MSMZ_HIP(hipMemcpyAsync(h_res_, d_res, 64, hipMemcpyDeviceToHost, stream_));
+    MSMZ_HIP(hipStreamSynchronize(stream_));
+    if (h_res_[8]) return MSMZ_ERR_RANGE;   // a resident record >= group order
+    if (n_zero) *n_zero = h_res_[9];
+    return fresh ? add_handle(std::move(hd), out_handle) : (int)MSMZ_OK;
+  }
+
   // ------------------------------------------------------------------------------------------ precomputed point sets
   int precompute_params(uint64_t n, const msmz_opts* o, uint32_t factor, int* c_out, int* glv_out,
                         uint32_t* f_out, int* k_out, int* sbits_out) const override {
@@ -1931,6 +2048,7 @@ class Engine : public IEngine {
   DevBuf bsum_, f2desc_, tilecnt_, tileoff_, final_, desc_, bfin_, packed_, bins_, digits_, counts_, off_, cursor_, refs_, rscan_, partials_, slots_, red_[4], meta_, stage_, gen_table_;
   MsmMeta* h_meta_ = nullptr;
   DevBuf sdot_;                      // scalars_dot: its result record, then one partial sum per tile
+  DevBuf sscan_;                     // scalars_recurrence / _inverse: the result record, then aggregates and incoming values
   DevBuf check_;                     // check_points: its result record, then one verdict byte per point
   CheckResult* h_check_ = nullptr;   // pinned, grow-only landing of the result record and the verdict bytes behind it
   size_t h_check_bytes_ = 0;

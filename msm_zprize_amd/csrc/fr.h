@@ -1,14 +1,16 @@
 // Arithmetic in the scalar field F_q on 8 saturated 32-bit words, little endian -- the format of a resident scalar set
-// (msmz_scalars_combine / _dot / _powers, include/msmz.h).  Operands and results are canonical
-// (< q) unless a comment says otherwise, so whatever these functions write is what an upload would have left.
+// (msmz_scalars_combine / _dot / _powers and msmz_scalars_recurrence / _inverse, include/msmz.h; DESIGN.md sections 18
+// and 19).  Operands and results are canonical (< q) unless a comment says otherwise, so whatever these functions write
+// is what an upload would have left.
 //
 // Saturated words, not the lazy limbs of fp.h: the kernels built on this file (scalar_kernels.h) move 64 to 160 bytes
 // per Montgomery product and sit at the memory bound, the values have to be canonical in memory anyway (a lazy form
 // would need a normalisation on every load and store), and q < 2^255 on all four curves, so a sum of two operands fits
 // the 8 words without a ninth.  fp_cios.h shows the schedule; this is its 8-word instance over Fr::Q / Fr::QINV32.
 //
-// Host and device (MSMZ_HD); tests/native/scalar_ops_test.cpp compiles it for the CPU.  Every loop is fully unrolled
-// and every array index is a constant after unrolling: nothing here indexes a register array dynamically.
+// Host and device (MSMZ_HD); tests/native/scalar_ops_test.cpp and scalar_scan_test.cpp compile it for the CPU.  Every
+// loop over words is fully unrolled and every array index is a constant after unrolling: nothing here indexes a
+// register array dynamically.
 #pragma once
 #include <cstdint>
 #include "fp.h"
@@ -88,6 +90,83 @@ MSMZ_HD void fr_mul(uint32_t* r, const uint32_t* a, const uint32_t* b) {
   uint32_t t[8];
   fr_mont_mul<Fr>(t, a, b);
   fr_mont_mul<Fr>(r, t, Fr::R2);
+}
+
+// ---------------------------------------------------------------------------------------------- inversion
+// word w of q - 2, the exponent of Fermat's inversion: a constant of Fr (the borrow of "- 2" runs up from word 0)
+template <class Fr>
+MSMZ_HD constexpr uint32_t fr_qm2_word(int w) {
+  uint32_t borrow = 2, r = 0;
+  for (int j = 0; j <= w; j++) {
+    r = Fr::Q[j] - borrow;
+    borrow = Fr::Q[j] < borrow ? 1u : 0u;
+  }
+  return r;
+}
+
+// r = x^-1 mod q = x^(q - 2); 0 -> 0.  Operand canonical, result CANONICAL: x goes to Montgomery form (one product),
+// 256 squarings and one product per set bit of q - 2 follow (about 380 products in all), and a product with the plain 1
+// leaves Montgomery form.  The exponent is a constant of Fr (its words come from Fr::Q in constant memory, one per 32
+// steps), so every lane of a kernel takes the same path whatever x is.  r may alias x.
+template <class Fr>
+MSMZ_HD void fr_inv(uint32_t* r, const uint32_t* x) {
+  uint32_t xm[8], acc[8], one[8];
+  fr_to_mont<Fr>(xm, x);
+#pragma unroll
+  for (int j = 0; j < 8; j++) acc[j] = Fr::ONE[j], one[j] = j == 0 ? 1u : 0u;
+#pragma unroll 1
+  for (int w = 7; w >= 0; w--) {
+    const uint32_t e = fr_qm2_word<Fr>(w);
+#pragma unroll 1
+    for (int k = 31; k >= 0; k--) {
+      fr_mont_mul<Fr>(acc, acc, acc);
+      if ((e >> k) & 1u) fr_mont_mul<Fr>(acc, acc, xm);
+    }
+  }
+  fr_mont_mul<Fr>(r, acc, one);
+}
+
+// ---------------------------------------------------------------------------------------------- affine maps
+// y -> A y + B over F_q, the element of a first-order linear recurrence (msmz_scalars_recurrence; scan_kernels.h).
+// Forms: A is kept in MONTGOMERY form (A 2^256 mod q), B and every y are canonical.  Then
+//     apply:    A (.) y = fr_mont_mul(A, y)   is canonical,                                        one product
+//     compose:  A2 (.) A1                     is again in Montgomery form,  A2 (.) B1 is canonical: two products
+// and no conversion ever happens between maps.  HA = false: A is 1 for every map in play (a running sum) and the field
+// is neither read nor written; HB = false: B is 0 (a running product).
+struct FrMap {
+  uint32_t A[8];
+  uint32_t B[8];
+};
+
+template <class Fr, bool HA, bool HB>
+MSMZ_HD void fr_map_identity(FrMap& m) {
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    if (HA) m.A[j] = Fr::ONE[j];
+    if (HB) m.B[j] = 0;
+  }
+}
+
+// r = g o f, f applied first: (A_g, B_g) o (A_f, B_f) = (A_g A_f, A_g B_f + B_g).  r may alias g or f.
+template <class Fr, bool HA, bool HB>
+MSMZ_HD void fr_map_compose(FrMap& r, const FrMap& g, const FrMap& f) {
+  if (HB) {
+    uint32_t t[8];
+    if (HA) {
+      fr_mont_mul<Fr>(t, g.A, f.B);
+      fr_add<Fr>(r.B, t, g.B);
+    } else {
+      fr_add<Fr>(r.B, f.B, g.B);
+    }
+  }
+  if (HA) fr_mont_mul<Fr>(r.A, g.A, f.A);
+}
+
+// y = m(y) = A y + B
+template <class Fr, bool HA, bool HB>
+MSMZ_HD void fr_map_apply(uint32_t* y, const FrMap& m) {
+  if (HA) fr_mont_mul<Fr>(y, m.A, y);
+  if (HB) fr_add<Fr>(y, y, m.B);
 }
 
 // ---------------------------------------------------------------------------------------------- powers of one ratio

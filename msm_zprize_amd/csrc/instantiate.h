@@ -8,6 +8,7 @@
 #include "kernels.h"
 #include "mul_kernels.h"
 #include "scalar_kernels.h"
+#include "scan_kernels.h"
 #include "test_kernels.h"
 
 // curve ids as in include/msmz.h
@@ -98,6 +99,11 @@
   PFX template __global__ void k_hist_seg<Fr, GLV, C>(uint32_t*, uint16_t*, uint32_t*, MsmMeta*, const uint32_t*, SortGeom, uint32_t, const SegDesc*); \
   PFX template __global__ void k_coarse_seg<Fr, GLV, C>(uint32_t*, const uint32_t*, const uint32_t*, const uint16_t*, const uint32_t*, SortGeom, uint32_t, const SegDesc*);
 
+// the recurrence kernels of one mode (scan_kernels.h): AM = how the multiplier arrives, HB = is there an addend
+#define MSMZ_INST_SCAN(Fr, AM, HB, PFX)                                                                           \
+  PFX template __global__ void k_scalars_rec_tile<Fr, AM, HB>(uint32_t*, uint32_t*, const uint32_t*, const uint32_t*, FrConst, uint32_t, uint32_t, uint32_t*); \
+  PFX template __global__ void k_scalars_rec_apply<Fr, AM, HB>(uint32_t*, const uint32_t*, const uint32_t*, FrConst, const uint32_t*, uint32_t, uint32_t);
+
 #define MSMZ_INST_SCALAR(Fr, PFX)                                                                                 \
   PFX template __global__ void k_digits<Fr, false>(uint32_t*, uint32_t*, MsmMeta*, const uint32_t*, uint32_t, int, int, int, int); \
   MSMZ_INST_SORT(Fr, false, 0, PFX)                                                                               \
@@ -109,7 +115,16 @@
   PFX template __global__ void k_scalars_combine<Fr>(uint32_t*, ScalarTerm, ScalarTerm, uint32_t, uint32_t*);     \
   PFX template __global__ void k_scalars_dot<Fr>(uint32_t*, const uint32_t*, const uint32_t*, uint32_t, uint32_t*); \
   PFX template __global__ void k_scalars_dot_fold<Fr>(uint32_t*, const uint32_t*, uint32_t, int);                 \
-  PFX template __global__ void k_scalars_powers<Fr>(uint32_t*, FrConst, FrPowTable, uint32_t, GenMap);
+  PFX template __global__ void k_scalars_powers<Fr>(uint32_t*, FrConst, FrPowTable, uint32_t, GenMap);                \
+  MSMZ_INST_SCAN(Fr, SREC_A_NONE, true, PFX)                                                                      \
+  MSMZ_INST_SCAN(Fr, SREC_A_BROADCAST, false, PFX)                                                                \
+  MSMZ_INST_SCAN(Fr, SREC_A_BROADCAST, true, PFX)                                                                 \
+  MSMZ_INST_SCAN(Fr, SREC_A_RESIDENT, false, PFX)                                                                 \
+  MSMZ_INST_SCAN(Fr, SREC_A_RESIDENT, true, PFX)                                                                  \
+  PFX template __global__ void k_scalars_rec_carry<Fr, false, true>(uint32_t*, uint32_t*, const uint32_t*, const uint32_t*, FrConst, uint32_t); \
+  PFX template __global__ void k_scalars_rec_carry<Fr, true, false>(uint32_t*, uint32_t*, const uint32_t*, const uint32_t*, FrConst, uint32_t); \
+  PFX template __global__ void k_scalars_rec_carry<Fr, true, true>(uint32_t*, uint32_t*, const uint32_t*, const uint32_t*, FrConst, uint32_t); \
+  PFX template __global__ void k_scalars_inverse<Fr>(uint32_t*, const uint32_t*, uint32_t, uint32_t*);
 
 #define MSMZ_INST_MISC(F, Fr, PFX)                                                                                \
   PFX template __global__ void k_points_to_mont<F>(uint32_t*, const uint32_t*, const uint8_t*, uint32_t, int, uint32_t*); \

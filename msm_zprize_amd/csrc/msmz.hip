@@ -224,9 +224,22 @@ int msmz_scalars_dot(msmz_ctx* c, uint64_t xh, uint64_t first_x, uint64_t yh, ui
 int msmz_scalars_powers(msmz_ctx* c, const uint8_t* base, const uint8_t* ratio, uint64_t n, uint64_t* h) {
   return c && ratio && h ? c->engine->scalars_powers(base, ratio, n, GenMap{}, h) : MSMZ_ERR_ARG;
 }
+int msmz_scalars_recurrence(msmz_ctx* c, const msmz_scalar_rec* r, uint64_t n, uint64_t first_out, uint64_t* out_handle,
+                            uint8_t* last) {
+  return c && r && out_handle ? c->engine->scalars_recurrence(*r, n, first_out, out_handle, last) : MSMZ_ERR_ARG;
+}
+int msmz_scalars_inverse(msmz_ctx* c, uint64_t h, uint64_t first, uint64_t n, uint64_t first_out, uint64_t* out_handle,
+                         uint64_t* n_zero) {
+  return c && out_handle ? c->engine->scalars_inverse(h, first, n, first_out, out_handle, n_zero) : MSMZ_ERR_ARG;
+}
 void msmz_test_scalar_dot_geometry(uint32_t* tile_elements, uint32_t* partials_per_pass) {
   if (tile_elements) *tile_elements = SDOT_TILE;
   if (partials_per_pass) *partials_per_pass = SDOT_PASS;
+}
+void msmz_test_scalar_scan_geometry(uint32_t* rec_tile, uint32_t* rec_pass, uint32_t* inv_chunk) {
+  if (rec_tile) *rec_tile = SREC_TILE;
+  if (rec_pass) *rec_pass = SREC_PASS;
+  if (inv_chunk) *inv_chunk = SINV_CHUNK;
 }
 
 int msmz_test_set_glv_bits(msmz_ctx* c, int bits) { return c ? c->engine->test_set_glv_bits(bits) : MSMZ_ERR_ARG; }

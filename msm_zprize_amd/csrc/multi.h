@@ -105,6 +105,11 @@ class IEngine {
                               uint64_t* out_handle) = 0;
   virtual int scalars_dot(uint64_t xh, uint64_t first_x, uint64_t yh, uint64_t first_y, uint64_t n, uint8_t* out) = 0;
   virtual int scalars_powers(const uint8_t* base, const uint8_t* ratio, uint64_t n, const GenMap& map, uint64_t* h) = 0;
+  // msmz_scalars_recurrence / _inverse: a scan of affine maps and Montgomery's trick (scan_kernels.h)
+  virtual int scalars_recurrence(const msmz_scalar_rec& r, uint64_t n, uint64_t first_out, uint64_t* out_handle,
+                                 uint8_t* last) = 0;
+  virtual int scalars_inverse(uint64_t h, uint64_t first, uint64_t n, uint64_t first_out, uint64_t* out_handle,
+                              uint64_t* n_zero) = 0;
   // tests (include/msmz_test.h); the stage-level hooks are one engine's (a multi-device context: its first engine's)
   virtual int test_set_glv_bits(int) { return MSMZ_ERR_UNSUPPORTED; }
   virtual int test_retries() { return 0; }
@@ -554,6 +559,50 @@ class MultiEngine : public IEngine {
       return e->scalars_powers(base, ratio, cnt, GenMap{G_, g, MULTI_BLOCK_SHIFT}, &mh.sub[g]);
     });
     return finish_handle(st, mh, h);
+  }
+
+  // A recurrence is sequential in the set index, and consecutive blocks of a set live on different engines: the
+  // dependency would cross every block boundary.  Refused (after the checks that need no handle).
+  int scalars_recurrence(const msmz_scalar_rec& r, uint64_t n, uint64_t, uint64_t* out_handle, uint8_t*) override {
+    if (!out_handle || n == 0 || n >> 32 || (r.flags & ~(uint32_t)(MSMZ_REC_REVERSE | MSMZ_REC_EXCLUSIVE)) ||
+        (!r.a_handle && !r.a && !r.b_handle))
+      return MSMZ_ERR_ARG;
+    return MSMZ_ERR_UNSUPPORTED;
+  }
+
+  // element-wise: every engine inverts its own share, as scalars_combine (all ranges from 0, an existing destination
+  // written whole); the zero counts add up
+  int scalars_inverse(uint64_t h, uint64_t first, uint64_t n, uint64_t first_out, uint64_t* out_handle,
+                      uint64_t* n_zero) override {
+    if (!out_handle || n == 0 || n >> 32) return MSMZ_ERR_ARG;
+    const bool fresh = *out_handle == 0;
+    if (fresh && first_out != 0) return MSMZ_ERR_ARG;
+    auto scalars = [&](uint64_t hh, uint64_t f) -> const MHandle* {
+      auto it = handles_.find(hh);
+      if (it == handles_.end() || it->second.kind != 1 || f > it->second.n || n > it->second.n - f) return nullptr;
+      return &it->second;
+    };
+    const MHandle* src = scalars(h, first);
+    if (!src) return MSMZ_ERR_ARG;
+    const MHandle* dst = nullptr;
+    if (!fresh && !(dst = scalars(*out_handle, first_out))) return MSMZ_ERR_ARG;
+    if (dst && *out_handle == h && first != first_out && (first > first_out ? first - first_out : first_out - first) < n)
+      return MSMZ_ERR_ARG;
+    if (first || first_out || (dst && dst->n != n)) return MSMZ_ERR_UNSUPPORTED;
+    MHandle mh{1, n, std::vector<uint64_t>(G_, 0)};
+    std::vector<uint64_t> zeros(G_, 0);
+    int st = for_all([&](uint32_t g, IEngine* e) {
+      const uint64_t cnt = shard_count(n, g, G_);
+      if (cnt == 0) return (int)MSMZ_OK;
+      if (dst) mh.sub[g] = dst->sub[g];
+      return e->scalars_inverse(src->sub[g], 0, cnt, 0, &mh.sub[g], &zeros[g]);
+    });
+    if (!st && n_zero) {
+      *n_zero = 0;
+      for (uint64_t z : zeros) *n_zero += z;
+    }
+    if (dst) return st;   // (written in place: the handle stays the caller's)
+    return finish_handle(st, mh, out_handle);
   }
 
   int test_set_glv_bits(int bits) override {

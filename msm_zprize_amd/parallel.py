@@ -17,7 +17,8 @@ include/msmz.h -- this module contains no arithmetic.
 import ctypes as C
 
 from . import _native
-from ._native import MsmzCheckResult, MsmzLog, MsmzMul, MsmzOpts, MsmzScalarTerm, MsmzSegment, MsmzSrc, check, lib
+from ._native import (MsmzCheckResult, MsmzLog, MsmzMul, MsmzOpts, MsmzScalarRec, MsmzScalarTerm, MsmzSegment, MsmzSrc, check,
+                      lib)
 
 _state = {"devices": None}
 
@@ -278,6 +279,54 @@ class _Parallel:
         check(lib().msmz_scalars_powers(self._c._ctx, base.to_bytes(32, "little"), ratio.to_bytes(32, "little"), N,
                                         C.byref(h)), "msmz_scalars_powers")
         return DeviceArray(self._c, h.value, N, "scalars")
+
+    # -- recurrences and inversion over resident scalar arrays (msmz_scalars_recurrence / _inverse) ---
+    def scalarRecurrence(self, a, b, N=None, init=None, reverse=False, exclusive=False, firstA=0, firstB=0, out=None,
+                         firstOut=0):
+        """y_i = a_i y_(i-1) + b_i mod the group order, i < N, from y_(-1) = init (reverse=True: y_i = a_i y_(i+1) + b_i
+        from y_N = init, highest i first).  `a`: a resident scalar array (a_i = a[firstA + i]), a Python int (one
+        multiplier for every i) or None (1); `b`: a resident scalar array or None (no addend); not both None.  init=None
+        is 0 with an addend and 1 without.  out[firstOut + i] = y_i, or with exclusive=True the value the step at i
+        started from.  out=None: a new array of N entries; otherwise `out` may be `a` or `b` when the range is exactly
+        theirs or apart from it.  Returns (the array written, the final y as an int)."""
+        t = scalar_recurrence_args(a, b, N, init, reverse, exclusive, firstA, firstB, out, firstOut, self._c.params["order"])
+        rec = MsmzScalarRec(t["aHandle"], t["firstA"], t["a"], t["bHandle"], t["firstB"], t["init"], t["flags"])
+        h = C.c_uint64(0 if out is None else out.handle)
+        last = C.create_string_buffer(32)
+        check(lib().msmz_scalars_recurrence(self._c._ctx, C.byref(rec), t["N"], t["firstOut"], C.byref(h), last),
+              "msmz_scalars_recurrence")
+        arr = DeviceArray(self._c, h.value, t["N"], "scalars") if out is None else out
+        return arr, int.from_bytes(last.raw, "little")
+
+    def prefixProducts(self, x, N=None, exclusive=False, init=None, reverse=False, first=0, out=None, firstOut=0):
+        """Running products of x[first + i]: (array, the full product).  exclusive=True: entry 0 is init (1), entry i the
+        product of the i entries before it -- a grand product column Z."""
+        return self.scalarRecurrence(x, None, N, init, reverse, exclusive, first, 0, out, firstOut)
+
+    def prefixSums(self, x, N=None, exclusive=False, init=None, reverse=False, first=0, out=None, firstOut=0):
+        """Running sums of x[first + i]: (array, the full sum)."""
+        return self.scalarRecurrence(None, x, N, init, reverse, exclusive, 0, first, out, firstOut)
+
+    def divideByLinear(self, p, z, N=None, first=0):
+        """(p(X) - p(z)) / (X - z) for the polynomial with coefficients p[first + i], i < N (lowest degree first):
+        (quotient, p(z)).  The quotient is a new array of N entries whose top entry is 0, so an MSM takes it against the
+        same N points as p: a KZG opening proof."""
+        if isinstance(z, bool) or not isinstance(z, int):
+            raise TypeError("divideByLinear: `z` is an int")
+        if not isinstance(p, DeviceArray) or p.kind != "scalars":
+            raise TypeError("divideByLinear: `p` is a resident scalar array")
+        return self.scalarRecurrence(z, p, N, 0, True, True, 0, first)
+
+    def invertScalars(self, x, N=None, first=0, out=None, firstOut=0):
+        """out[firstOut + i] = x[first + i]^-1 mod the group order, 0 -> 0: (the array written, the number of zeros).
+        out=None: a new array; `out` may be `x` over exactly the same range (in place) or apart from it."""
+        t = invert_scalars_args(x, N, first, out, firstOut)
+        h = C.c_uint64(0 if out is None else out.handle)
+        zeros = C.c_uint64(0)
+        check(lib().msmz_scalars_inverse(self._c._ctx, x.handle, t["first"], t["N"], t["firstOut"], C.byref(h),
+                                         C.byref(zeros)), "msmz_scalars_inverse")
+        arr = DeviceArray(self._c, h.value, t["N"], "scalars") if out is None else out
+        return arr, int(zeros.value)
 
     def _checked(self, arr, what, who):
         try:
@@ -654,6 +703,75 @@ def combine_scalars_args(a, x, b, y, N, firstX, firstY, out, firstOut, firstA, f
     if y is not None:
         terms.append((y, firstY) + (coeffs[1][0], firstB if coeffs[1][0] is not None else 0, coeffs[1][1]))
     return {"N": N, "firstOut": firstOut, "terms": terms}
+
+
+def _scan_ranges(who, ranges, N, out, firstOut):
+    """the shared range checks of scalarRecurrence and invertScalars: ranges = [(name, first, array or None)], the last
+    one the destination -> N"""
+    for name, first, arr in ranges:
+        if isinstance(first, bool) or not isinstance(first, int) or first < 0:
+            raise ValueError(f"{who}: {name} = {first!r}")
+        if arr is None and first != 0:
+            raise ValueError(f"{who}: {name} = {first} without the array it indexes")
+        if arr is not None and first >= len(arr):
+            raise ValueError(f"{who}: {name} = {first} but the array holds {len(arr)}")
+    if N is None:
+        N = min(len(arr) - first for _, first, arr in ranges if arr is not None)
+    if isinstance(N, bool) or not isinstance(N, int) or not 1 <= N < 1 << 32:
+        raise ValueError(f"{who}: N = {N!r}")
+    for name, first, arr in ranges:
+        if arr is not None and N > len(arr) - first:
+            raise ValueError(f"{who}: entries [{first}, +{N}) from {name} of an array of {len(arr)}")
+    if out is not None:
+        for name, first, arr in ranges[:-1]:
+            if arr is not None and arr.handle == out.handle and first != firstOut and abs(first - firstOut) < N:
+                raise ValueError(f"{who}: the destination [{firstOut}, +{N}) overlaps the input range [{first}, +{N}) "
+                                 f"({name}) in part; it may be that range exactly or apart from it")
+    return N
+
+
+def scalar_recurrence_args(a, b, N, init, reverse, exclusive, firstA, firstB, out, firstOut, order,
+                           who="scalarRecurrence"):
+    """Arguments of scalarRecurrence -> dict(N, firstOut, aHandle, firstA, a, bHandle, firstB, init, flags), checked before
+    anything reaches the device.  a / init: the 32 little-endian bytes of a broadcast value, or None."""
+    def scalars(v):
+        return isinstance(v, DeviceArray) and v.kind == "scalars"
+
+    broadcast = isinstance(a, int) and not isinstance(a, bool)
+    if a is not None and not broadcast and not scalars(a):
+        raise TypeError(f"{who}: `a` is a resident scalar array, an int (one multiplier for every entry) or None (1)")
+    if b is not None and not scalars(b):
+        raise TypeError(f"{who}: `b` is a resident scalar array or None (no addend)")
+    if a is None and b is None:
+        raise TypeError(f"{who}: neither a multiplier nor an addend: nothing to do")
+    if out is not None and not scalars(out):
+        raise TypeError(f"{who}: `out` is a resident scalar array or None")
+    if init is not None and (isinstance(init, bool) or not isinstance(init, int)):
+        raise TypeError(f"{who}: `init` is an int or None")
+    for name, v in (("reverse", reverse), ("exclusive", exclusive)):
+        if not isinstance(v, bool):
+            raise TypeError(f"{who}: `{name}` is a bool")
+    for name, v in (("a", a if broadcast else None), ("init", init)):
+        if v is not None and not 0 <= v < order:
+            raise ValueError(f"{who}: {name} = {v} is not in [0, group order)")
+    ranges = [("firstA", firstA, a if scalars(a) else None), ("firstB", firstB, b), ("firstOut", firstOut, out)]
+    if N is None and not scalars(a) and b is None and out is None:
+        raise ValueError(f"{who}: N is needed when no array gives the length")
+    N = _scan_ranges(who, ranges, N, out, firstOut)
+    return {"N": N, "firstOut": firstOut, "aHandle": a.handle if scalars(a) else 0, "firstA": firstA,
+            "a": a.to_bytes(32, "little") if broadcast else None, "bHandle": 0 if b is None else b.handle,
+            "firstB": firstB, "init": None if init is None else init.to_bytes(32, "little"),
+            "flags": (_native.MSMZ_REC_REVERSE if reverse else 0) | (_native.MSMZ_REC_EXCLUSIVE if exclusive else 0)}
+
+
+def invert_scalars_args(x, N, first, out, firstOut, who="invertScalars"):
+    """Arguments of invertScalars -> dict(N, first, firstOut), checked before anything reaches the device."""
+    if not isinstance(x, DeviceArray) or x.kind != "scalars":
+        raise TypeError(f"{who}: `x` is a resident scalar array")
+    if out is not None and (not isinstance(out, DeviceArray) or out.kind != "scalars"):
+        raise TypeError(f"{who}: `out` is a resident scalar array or None")
+    N = _scan_ranges(who, [("first", first, x), ("firstOut", firstOut, out)], N, out, firstOut)
+    return {"N": N, "first": first, "firstOut": firstOut}
 
 
 def check_arg(check, who):

@@ -565,6 +565,61 @@ static napi_value ScalarsPowers(napi_env env, napi_callback_info info) {
   return make_handle(env, h);
 }
 
+/* a 32-byte Buffer (a scalar, little-endian) -> *out, null / undefined -> NULL */
+static int get_scalar_or_null(napi_env env, napi_value v, const uint8_t** out) {
+  msmz_scalar_term t; memset(&t, 0, sizeof(t));
+  if (!get_coeff(env, v, &t) || t.coeff_handle) return 0;
+  *out = t.coeff;
+  return 1;
+}
+
+/* scalarsRecurrence(ctx, a (handle, 32-byte Buffer = one multiplier for every entry, or null = 1), aFirst, bHandle (0 = no
+   addend), bFirst, init (32-byte Buffer or null), flags (1 = reverse, 2 = exclusive), n, firstOut, outHandle (0 = a new
+   array)) -> {handle, last}: the array written and the final value as a 32-byte Buffer  (msmz_scalars_recurrence) */
+static napi_value ScalarsRecurrence(napi_env env, napi_callback_info info) {
+  size_t argc = 10; napi_value argv[10];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  msmz_ctx* ctx; if (argc < 10 || !get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "scalarsRecurrence");
+  msmz_scalar_rec r; memset(&r, 0, sizeof(r));
+  msmz_scalar_term a; memset(&a, 0, sizeof(a));
+  uint64_t flags, n, first_out, h = 0;
+  if (!get_coeff(env, argv[1], &a) || !get_u64(env, argv[2], &r.a_first) || !get_u64(env, argv[3], &r.b_handle) ||
+      !get_u64(env, argv[4], &r.b_first) || !get_scalar_or_null(env, argv[5], &r.init) || !get_u64(env, argv[6], &flags) ||
+      flags >> 32 || !get_u64(env, argv[7], &n) || !get_u64(env, argv[8], &first_out) || !get_u64(env, argv[9], &h))
+    return throw_status(env, MSMZ_ERR_ARG, "scalarsRecurrence");
+  r.a_handle = a.coeff_handle;
+  r.a = a.coeff;
+  r.flags = (uint32_t)flags;
+  void* data; napi_value last, res;
+  NAPI_CALL(env, napi_create_buffer(env, 32, &data, &last));
+  int st = msmz_scalars_recurrence(ctx, &r, n, first_out, &h, (uint8_t*)data);
+  if (st) return throw_status(env, st, "msmz_scalars_recurrence");
+  NAPI_CALL(env, napi_create_object(env, &res));
+  NAPI_CALL(env, napi_set_named_property(env, res, "handle", make_handle(env, h)));
+  NAPI_CALL(env, napi_set_named_property(env, res, "last", last));
+  return res;
+}
+
+/* scalarsInverse(ctx, handle, first, n, firstOut, outHandle (0 = a new array)) -> {handle, zeros}: the array written,
+   entry i = x_i^-1 (0 -> 0), and the number of zero entries  (msmz_scalars_inverse) */
+static napi_value ScalarsInverse(napi_env env, napi_callback_info info) {
+  size_t argc = 6; napi_value argv[6];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  msmz_ctx* ctx; if (argc < 6 || !get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "scalarsInverse");
+  uint64_t xh, first, n, first_out, h = 0, zeros = 0;
+  if (!get_u64(env, argv[1], &xh) || !get_u64(env, argv[2], &first) || !get_u64(env, argv[3], &n) ||
+      !get_u64(env, argv[4], &first_out) || !get_u64(env, argv[5], &h))
+    return throw_status(env, MSMZ_ERR_ARG, "scalarsInverse");
+  int st = msmz_scalars_inverse(ctx, xh, first, n, first_out, &h, &zeros);
+  if (st) return throw_status(env, st, "msmz_scalars_inverse");
+  napi_value res, z;
+  NAPI_CALL(env, napi_create_object(env, &res));
+  NAPI_CALL(env, napi_create_double(env, (double)zeros, &z));
+  NAPI_CALL(env, napi_set_named_property(env, res, "handle", make_handle(env, h)));
+  NAPI_CALL(env, napi_set_named_property(env, res, "zeros", z));
+  return res;
+}
+
 static napi_value PointAdd(napi_env env, napi_callback_info info) {
   size_t argc = 4; napi_value argv[4];
   NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -603,7 +658,8 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"downloadScalars", DownloadScalars}, {"free", Free}, {"msm", Msm}, {"msmBatch", MsmBatch}, {"msmSegments", MsmSegments},
       {"precomputePoints", PrecomputePoints}, {"precomputedInfo", PrecomputedInfo}, {"checkPoints", CheckPoints},
       {"mulPoints", MulPoints}, {"scalarsCombine", ScalarsCombine}, {"scalarsDot", ScalarsDot},
-      {"scalarsPowers", ScalarsPowers}, {"pointAdd", PointAdd}, {"feBytes", FeBytes}};
+      {"scalarsPowers", ScalarsPowers}, {"scalarsRecurrence", ScalarsRecurrence}, {"scalarsInverse", ScalarsInverse},
+      {"pointAdd", PointAdd}, {"feBytes", FeBytes}};
   for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); i++) {
     napi_value f;
     if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;
