@@ -1,5 +1,6 @@
-// Host-side MSM engine: owns the device buffers of one GPU, sequences the kernels on one HIP stream
-// and finishes the K window sums on the host.  This replaces the reference's SPMD worker runtime
+// Host-side MSM engine: the pipeline of one GPU (sort, plan, tree rounds, bucket reduction) over the resident sets of
+// ResidentSets (resident.h), from which it derives; it owns the pipeline's device buffers, sequences the kernels on the
+// one HIP stream and finishes the K window sums on the host.  This replaces the reference's SPMD worker runtime
 // (src/threads/threads.ts:132-359, src/parallel.ts:291-320) and the JS orchestration inside
 // `msm` (src/msm-batched-affine.ts:74-328): barriers between phases become stream order, the
 // per-thread bucket split (msm-common.ts:88-188) becomes grid sizing.
@@ -10,83 +11,17 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <type_traits>
 #include <vector>
 
 #include "../../include/msmz.h"
 #include "kernels.h"
-#include "gen_kernels.h"
-#include "import_kernels.h"
-#include "check_kernels.h"
-#include "mul_kernels.h"
-#include "scalar_kernels.h"
 #include "host64.h"
 #include "multi.h"
 #include "plan.h"
+#include "resident.h"
 
 namespace msmz {
-
-#define MSMZ_HIP(x)                                                                        \
-  do {                                                                                     \
-    hipError_t e_ = (x);                                                                   \
-    if (e_ != hipSuccess) {                                                                \
-      fprintf(stderr, "msmz: HIP error '%s' from `%s` at %s:%d\n", hipGetErrorString(e_), #x, __FILE__, __LINE__); \
-      return MSMZ_ERR_HIP;                                                                 \
-    }                                                                                      \
-  } while (0)
-
-// Device memory owned by one object: freed when it goes out of scope, so every error path releases it.
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  DevBuf() = default;
-  DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr, o.bytes = 0; }
-  DevBuf& operator=(DevBuf&& o) noexcept {
-    if (this != &o) {
-      release();
-      p = o.p, bytes = o.bytes;
-      o.p = nullptr, o.bytes = 0;
-    }
-    return *this;
-  }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }
-  int ensure(size_t need) {   // grow-only
-    if (need <= bytes) return MSMZ_OK;
-    release();
-    size_t sz = need + need / 8;
-    if (hipMalloc(&p, sz) != hipSuccess) {
-      if (hipMalloc(&p, need) != hipSuccess) return MSMZ_ERR_HIP;
-      sz = need;
-    }
-    bytes = sz;
-    return MSMZ_OK;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-  template <class T>
-  T* as() const {
-    return reinterpret_cast<T*>(p);
-  }
-};
-
-struct Handle {
-  int kind;        // 0 = points, 1 = scalars
-  uint64_t n;
-  bool has_endo;   // points: records [n, 2n) hold the endomorphism images
-  DevBuf mem;
-  // precomputed point set (msmz_precompute_points): `factor` copies, copy j = records [j R, (j + 1) R) holds 2^(c j) P_i
-  // (R = copy_stride = n, or 2 n with the endomorphism images); built for window size c and GLV choice glv.  0 = plain.
-  uint32_t factor = 0;
-  int c = 0, glv = 0;
-  uint64_t copy_stride = 0;
-  int sbits = 0;   // scalar bit bound the copies were built for (Planner::bound: 0 = none)
-};
 
 // Named events of an MSM's stages, created once per engine; a timed MSM records them in stream order.
 struct StageEvents {
@@ -181,28 +116,25 @@ template <class Cfg>
 class TestHooks;   // test_hooks.h
 
 template <class Cfg>
-class Engine : public IEngine {
+class Engine : public ResidentSets<Cfg> {
   friend class TestHooks<Cfg>;
-  using F = typename Cfg::F;
-  using Fr = typename Cfg::Fr;
-  static constexpr int NW = F::NW;
-  static constexpr int RW = 2 * NW;      // affine record words
+  using Base = ResidentSets<Cfg>;
+  // what the pipeline uses of the resident sets: the curve's types and record sizes, the device and its stream, the
+  // handle table, the staging buffer, the meta block with its pinned landing, and the pinned results
+  using typename Base::F;
+  using typename Base::Fr;
+  using Base::NW, Base::RW, Base::FE_BYTES, Base::TE, Base::PW_WORDS;
+  using Base::device_, Base::stream_, Base::handles_, Base::stage_, Base::meta_, Base::h_meta_, Base::h_res_;
+  using Base::copy_h2d, Base::fetch_error, Base::new_handle, Base::add_handle;
   static constexpr int XW = 4 * NW;      // XYZZ / extended record words
-  static constexpr int FE_BYTES = NW * 4;
-  static constexpr bool TE = Cfg::TE;
-  static constexpr int PW_WORDS = TE ? 4 * NW : PointFmt<F>::STRIDE;   // words between the records of a resident point set
-
  public:
-  Engine(int curve_id, int device) : curve_id_(curve_id), device_(device) {}
+  Engine(int curve_id, int device) : Base(device), curve_id_(curve_id) {}
 
   int init() {
-    MSMZ_HIP(hipSetDevice(device_));
-    MSMZ_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    for (hipEvent_t* e : ev_.all()) MSMZ_HIP(hipEventCreate(e));
-    MSMZ_HIP(hipEventCreateWithFlags(&import_ev_, hipEventDisableTiming));
-    MSMZ_HIP(hipHostMalloc(&h_meta_, sizeof(MsmMeta)));
     int st;
-    if ((st = ensure_host_results((size_t)2 * kMaxWindows * XW))) return st;   // the results of one problem
+    if ((st = Base::init_sets())) return st;
+    for (hipEvent_t* e : ev_.all()) MSMZ_HIP(hipEventCreate(e));
+    if ((st = h_res_.ensure((size_t)2 * kMaxWindows * XW * 4))) return st;   // the results of one problem
     // Kernels that stage more than the default dynamic-LDS allowance get their limit raised ONCE, here, right after
     // hipSetDevice -- not lazily inside the first MSM and not on every MSM.  static + dynamic LDS is checked against
     // the device's per-workgroup LDS, so a kernel that cannot launch fails context creation with its name.
@@ -279,665 +211,10 @@ class Engine : public IEngine {
   }
 
  public:
-  ~Engine() override {   // (the device buffers and handles free themselves after this, on this device)
+  ~Engine() override {   // (the pipeline's buffers free themselves after this, on this device; then the base's turn)
     (void)hipSetDevice(device_);
-    if (h_meta_) (void)hipHostFree(h_meta_);
-    if (h_res_) (void)hipHostFree(h_res_);
-    if (h_check_) (void)hipHostFree(h_check_);
-    if (h_segs_) (void)hipHostFree(h_segs_);
     for (hipEvent_t* e : ev_.all())
       if (*e) (void)hipEventDestroy(*e);
-    if (import_ev_) (void)hipEventDestroy(import_ev_);
-    if (stream_) (void)hipStreamDestroy(stream_);
-  }
-
-  // ------------------------------------------------------------------------------------------ data
-  int upload_points(const uint8_t* xy, const uint8_t* inf, uint64_t n, uint64_t* h, const GenMap* split = nullptr) override {
-    if (!xy || !h || n == 0 || n >= (1ull << (Cfg::HAS_ENDO ? 29 : 30))) return MSMZ_ERR_ARG;   // record indices (incl. endomorphism images) fit 30 bits
-    MSMZ_HIP(hipSetDevice(device_));
-    int st = stage_.ensure(n * RW * 4 + n);
-    if (st) return st;
-    if ((st = copy_h2d(stage_.p, xy, (size_t)RW * 4, n, split))) return st;
-    uint8_t* d_inf = nullptr;
-    if (inf) {
-      d_inf = stage_.as<uint8_t>() + n * RW * 4;
-      if ((st = copy_h2d(d_inf, inf, 1, n, split))) return st;
-    }
-    const bool endo = Cfg::HAS_ENDO;
-    Handle hd{0, n, endo};
-    if ((st = alloc_handle(hd, (size_t)n * PW_WORDS * 4 * (endo ? 2 : 1)))) return st;
-    MsmMeta* d_meta = meta_.as<MsmMeta>();
-    MSMZ_HIP(hipMemsetAsync(&d_meta->error, 0, 4, stream_));
-    if constexpr (TE) {
-      hipLaunchKernelGGL((k_te_points_to_niels<F>), dim3((n + 255) / 256), dim3(256), 0, stream_, hd.mem.as<uint32_t>(),
-                         stage_.as<uint32_t>(), (uint32_t)n, &d_meta->error);
-    } else {
-      hipLaunchKernelGGL((k_points_to_mont<F>), dim3((n + 255) / 256), dim3(256), 0, stream_, hd.mem.as<uint32_t>(),
-                         stage_.as<uint32_t>(), d_inf, (uint32_t)n, endo ? 1 : 0, &d_meta->error);
-    }
-    uint32_t err = 0;
-    if ((st = fetch_error(&err))) return st;
-    if (err) return MSMZ_ERR_RANGE;   // a coordinate >= p
-    return add_handle(std::move(hd), h);
-  }
-
-  int upload_scalars(const uint8_t* s, uint64_t n, uint64_t* h, const GenMap* split = nullptr) override {
-    if (!s || !h || n == 0) return MSMZ_ERR_ARG;
-    MSMZ_HIP(hipSetDevice(device_));
-    Handle hd{1, n, false};
-    int st;
-    if ((st = alloc_handle(hd, n * 32)) || (st = copy_h2d(hd.mem.p, s, 32, n, split))) return st;
-    MsmMeta* d_meta = meta_.as<MsmMeta>();
-    MSMZ_HIP(hipMemsetAsync(&d_meta->error, 0, 4, stream_));
-    hipLaunchKernelGGL((k_check_scalars<Fr>), dim3((n + 255) / 256), dim3(256), 0, stream_, &d_meta->error,
-                       hd.mem.as<const uint32_t>(), (uint32_t)n);
-    uint32_t err = 0;
-    if ((st = fetch_error(&err))) return st;
-    if (err) return MSMZ_ERR_RANGE;   // a scalar >= group order
-    return add_handle(std::move(hd), h);
-  }
-
-  // ------------------------------------------------------------------------------------------ imports
-  int import_scalars(const msmz_src& s, uint64_t n, uint64_t* h, const GenMap* split = nullptr) override {
-    if (!h || n == 0 || n >> 32) return MSMZ_ERR_ARG;
-    MSMZ_HIP(hipSetDevice(device_));
-    Handle hd{1, n, false};
-    ImportView v;
-    int st;
-    {
-      uint32_t w = 0;
-      uint64_t sb = 0;
-      if ((st = src_check(&s, 0, &w, &sb))) return st;
-    }
-    if ((st = alloc_handle(hd, n * 32)) || (st = import_view(s, 0, n, split, &v))) return st;   // (allocate first: no copy is queued yet)
-    if ((st = import_scalars_to(hd.mem.as<uint32_t>(), s, v, n))) return st;
-    return add_handle(std::move(hd), h);
-  }
-
-  // a new scalar set of n zeros: the target of import_scalars_into when a batch is assembled vector by vector
-  int alloc_scalars(uint64_t n, uint64_t* h) override {
-    if (!h || n == 0 || n >> 32) return MSMZ_ERR_ARG;
-    MSMZ_HIP(hipSetDevice(device_));
-    Handle hd{1, n, false};
-    if (int st = alloc_handle(hd, n * 32)) return st;
-    MSMZ_HIP(hipMemsetAsync(hd.mem.p, 0, n * 32, stream_));
-    MSMZ_HIP(hipStreamSynchronize(stream_));
-    return add_handle(std::move(hd), h);
-  }
-
-  int import_scalars_into(uint64_t h, uint64_t first, const msmz_src& s, uint64_t n) override {
-    auto it = handles_.find(h);
-    if (it == handles_.end() || it->second.kind != 1 || n == 0) return MSMZ_ERR_ARG;
-    if (first > it->second.n || n > it->second.n - first) return MSMZ_ERR_ARG;   // (no first + n: it can wrap)
-    MSMZ_HIP(hipSetDevice(device_));
-    ImportView v;
-    if (int st = import_view(s, 0, n, nullptr, &v)) return st;
-    return import_scalars_to(it->second.mem.template as<uint32_t>() + first * 8, s, v, n);
-  }
-
-  int import_points(const msmz_src& s, uint64_t n, uint64_t* h, const GenMap* split = nullptr) override {
-    if (!h || n == 0 || n >= (1ull << (Cfg::HAS_ENDO ? 29 : 30))) return MSMZ_ERR_ARG;   // as upload_points
-    MSMZ_HIP(hipSetDevice(device_));
-    ImportView v;
-    int st;
-    const bool endo = Cfg::HAS_ENDO;
-    const int mont = (s.flags & MSMZ_SRC_MONTGOMERY) ? 1 : 0;
-    Handle hd{0, n, endo};
-    {   // (checked before the allocation, which comes before any copy is queued)
-      uint32_t w = 0;
-      uint64_t sb = 0;
-      if ((st = src_check(&s, FE_BYTES, &w, &sb))) return st;
-    }
-    if ((st = alloc_handle(hd, (size_t)n * PW_WORDS * 4 * (endo ? 2 : 1))) || (st = import_view(s, FE_BYTES, n, split, &v))) return st;
-    MsmMeta* d_meta = meta_.as<MsmMeta>();
-    MSMZ_HIP(hipMemsetAsync(&d_meta->error, 0, 4, stream_));
-    if constexpr (TE) {
-      hipLaunchKernelGGL((k_te_import_points<F>), dim3((n + 255) / 256), dim3(256), 0, stream_, hd.mem.as<uint32_t>(),
-                         v.ptr, v.stride, (uint32_t)n, mont, &d_meta->error);
-    } else {
-      hipLaunchKernelGGL((k_import_points<F>), dim3((n + 255) / 256), dim3(256), 0, stream_, hd.mem.as<uint32_t>(), v.ptr,
-                         v.stride, v.is_inf, (uint32_t)n, endo ? 1 : 0, mont, &d_meta->error);
-    }
-    uint32_t err = 0;
-    if ((st = fetch_error(&err))) return st;
-    if (err) return MSMZ_ERR_RANGE;   // a coordinate (either form) >= p
-    return add_handle(std::move(hd), h);
-  }
-
-  int gather_src(const msmz_src& s, int point_fe_bytes, uint64_t n, std::vector<uint8_t>* recs,
-                 std::vector<uint8_t>* flags) override {
-    uint32_t width = 0;
-    uint64_t stride = 0;
-    if (int st = src_check(&s, point_fe_bytes, &width, &stride)) return st;
-    if (n == 0 || n >> 32 || !recs || !flags) return MSMZ_ERR_ARG;
-    recs->resize((size_t)n * width);
-    flags->clear();
-    const uint8_t* p = (const uint8_t*)s.ptr;
-    if (!(s.flags & MSMZ_SRC_DEVICE)) {
-      for (uint64_t i = 0; i < n; i++) memcpy(recs->data() + i * width, p + i * stride, width);
-      if (s.is_inf) flags->assign(s.is_inf, s.is_inf + n);
-      return MSMZ_OK;
-    }
-    MSMZ_HIP(hipSetDevice(device_));
-    const void* dp = nullptr;
-    const void* di = nullptr;
-    int st;
-    if ((st = vouch(p, (n - 1) * stride + width, true, &dp))) return st;
-    if (s.is_inf && (st = vouch(s.is_inf, n, true, &di))) return st;
-    if (s.stream) MSMZ_HIP(hipStreamSynchronize((hipStream_t)s.stream));
-    if (s.flags & MSMZ_SRC_DEFAULT_STREAM) MSMZ_HIP(hipStreamSynchronize(nullptr));
-    MSMZ_HIP(hipMemcpy2D(recs->data(), width, dp, stride, width, n, hipMemcpyDefault));
-    if (di) {
-      flags->resize(n);
-      MSMZ_HIP(hipMemcpy(flags->data(), di, n, hipMemcpyDefault));
-    }
-    return MSMZ_OK;
-  }
-
- private:
-  // where the import kernel reads: the caller's device memory, or the packed staging copy of a host source
-  struct ImportView {
-    const uint8_t* ptr = nullptr;
-    uint64_t stride = 0;
-    uint32_t width = 0;
-    const uint8_t* is_inf = nullptr;
-  };
-
-  // May a kernel of this device read [p, p + bytes)?  Yes only if the HIP runtime knows p as memory of this device, or
-  // as pinned / registered host memory (then *dev is its device-side address), AND the whole range lies inside the one
-  // allocation p belongs to (hipMemGetAddressRange): a range that starts in one allocation and ends in another is
-  // refused, whatever lies between.  A pointer the runtime does not know (pageable host memory, a stale or made-up
-  // address), managed memory and another device's memory are refused: nothing is launched on them.  Pinned host memory
-  // whose allocation the runtime cannot report is accepted only if the first and the last byte are both pinned and
-  // their device-side addresses are `bytes - 1` apart.  any_device: the caller only copies (gather_src).
-  int vouch(const void* p, uint64_t bytes, bool any_device, const void** dev) const {
-    hipPointerAttribute_t a;
-    memset(&a, 0, sizeof(a));
-    if (bytes == 0 || hipPointerGetAttributes(&a, p) != hipSuccess) {
-      (void)hipGetLastError();   // (an unknown pointer is an answer, not a sticky error)
-      return MSMZ_ERR_ARG;
-    }
-    if ((a.type != hipMemoryTypeDevice && a.type != hipMemoryTypeHost) || a.isManaged) return MSMZ_ERR_ARG;
-    if (a.type == hipMemoryTypeDevice && !any_device && a.device != device_) return MSMZ_ERR_ARG;
-    *dev = a.type == hipMemoryTypeHost ? a.devicePointer : p;
-    if (!*dev) return MSMZ_ERR_ARG;
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)*dev) == hipSuccess) {
-      const uintptr_t lo = (uintptr_t)base, at = (uintptr_t)*dev;
-      return at >= lo && bytes <= size && at - lo <= size - bytes ? MSMZ_OK : MSMZ_ERR_ARG;
-    }
-    (void)hipGetLastError();
-    if (a.type != hipMemoryTypeHost) return MSMZ_ERR_ARG;
-    hipPointerAttribute_t z;
-    memset(&z, 0, sizeof(z));
-    if (hipPointerGetAttributes(&z, (const uint8_t*)p + (bytes - 1)) != hipSuccess) {
-      (void)hipGetLastError();
-      return MSMZ_ERR_ARG;
-    }
-    if (z.type != hipMemoryTypeHost || z.isManaged || !z.devicePointer) return MSMZ_ERR_ARG;
-    return (uintptr_t)z.devicePointer - (uintptr_t)a.devicePointer == bytes - 1 ? MSMZ_OK : MSMZ_ERR_ARG;
-  }
-
-  // Checks the source and makes it readable for the import kernel, in stream order.  Device source: the pointers are
-  // vouched for and stream_ waits for an event recorded on the producing stream (no host wait).  Host source: `width`
-  // bytes per record go to stage_ (a strided source is packed on the host first; `split`: this engine's blocks of a
-  // packed source), the flag bytes behind them.
-  int import_view(const msmz_src& s, int point_fe_bytes, uint64_t n, const GenMap* split, ImportView* v) {
-    if (int st = src_check(&s, point_fe_bytes, &v->width, &v->stride)) return st;
-    const uint8_t* p = (const uint8_t*)s.ptr;
-    if (s.flags & MSMZ_SRC_DEVICE) {
-      if (split) return MSMZ_ERR_ARG;   // (a multi-device context hands its engines host copies)
-      const void* dp = nullptr;
-      int st;
-      if ((st = vouch(p, (n - 1) * v->stride + v->width, false, &dp))) return st;
-      v->ptr = (const uint8_t*)dp;
-      if (s.is_inf) {
-        if ((st = vouch(s.is_inf, n, false, &dp))) return st;
-        v->is_inf = (const uint8_t*)dp;
-      }
-      if (s.stream || (s.flags & MSMZ_SRC_DEFAULT_STREAM)) {
-        MSMZ_HIP(hipEventRecord(import_ev_, (hipStream_t)s.stream));
-        MSMZ_HIP(hipStreamWaitEvent(stream_, import_ev_, 0));
-      }
-      return MSMZ_OK;
-    }
-    const uint32_t w = v->width;
-    if (split && v->stride != w) return MSMZ_ERR_ARG;
-    int st = stage_.ensure((size_t)n * w + n);
-    if (st) return st;
-    if (v->stride != w) {
-      import_pack_.resize((size_t)n * w);   // (lives until the import's error-word fetch has drained the stream)
-      for (uint64_t i = 0; i < n; i++) memcpy(import_pack_.data() + i * w, p + i * v->stride, w);
-      p = import_pack_.data();
-    }
-    // (a failure once a copy may be queued drains the stream: when the call returns the source is no longer read)
-    if ((st = copy_h2d(stage_.p, p, w, n, split))) return (void)hipStreamSynchronize(stream_), st;
-    if (s.is_inf) {
-      uint8_t* d_inf = stage_.as<uint8_t>() + (size_t)n * w;
-      if ((st = copy_h2d(d_inf, s.is_inf, 1, n, split))) return (void)hipStreamSynchronize(stream_), st;
-      v->is_inf = d_inf;
-    }
-    v->ptr = stage_.as<const uint8_t>();
-    v->stride = w;
-    return MSMZ_OK;
-  }
-
-  // the conversion kernel over a view, then the error-word fetch: when it returns the source has been read
-  int import_scalars_to(uint32_t* dst, const msmz_src& s, const ImportView& v, uint64_t n) {
-    MsmMeta* d_meta = meta_.as<MsmMeta>();
-    MSMZ_HIP(hipMemsetAsync(&d_meta->error, 0, 4, stream_));
-    hipLaunchKernelGGL((k_import_scalars<Fr>), dim3((n + 255) / 256), dim3(256), 0, stream_, dst, v.ptr, v.stride,
-                       (int)(v.width / 4), (uint32_t)n, (s.flags & MSMZ_SRC_MONTGOMERY) ? 1 : 0, &d_meta->error);
-    uint32_t err = 0;
-    if (int st = fetch_error(&err)) return st;
-    return err ? MSMZ_ERR_RANGE : MSMZ_OK;   // a scalar (either form) >= group order
-  }
-
- public:
-  int random_points(uint64_t n, uint64_t seed, const GenMap& map, uint64_t* h) override {
-    if (!h || n == 0 || n >= (1ull << (Cfg::HAS_ENDO ? 29 : 30))) return MSMZ_ERR_ARG;   // record indices (incl. endomorphism images) fit 30 bits
-    MSMZ_HIP(hipSetDevice(device_));
-    int st = ensure_gen_table();
-    if (st) return st;
-    const bool endo = Cfg::HAS_ENDO;
-    Handle hd{0, n, endo};
-    if ((st = alloc_handle(hd, (size_t)n * PW_WORDS * 4 * (endo ? 2 : 1)))) return st;
-    if constexpr (TE) {
-      hipLaunchKernelGGL((k_te_gen_points<F>), dim3((n + 127) / 128), dim3(128), 0, stream_, hd.mem.as<uint32_t>(),
-                         gen_table_.as<uint32_t>(), (uint32_t)n, seed, map);
-    } else {
-      hipLaunchKernelGGL((k_gen_points<F>), dim3((n + 127) / 128), dim3(128), 0, stream_, hd.mem.as<uint32_t>(),
-                         gen_table_.as<uint32_t>(), (uint32_t)n, seed, endo ? 1 : 0, map);
-    }
-    MSMZ_HIP(hipGetLastError());
-    MSMZ_HIP(hipStreamSynchronize(stream_));
-    return add_handle(std::move(hd), h);
-  }
-
-  int random_scalars(uint64_t n, uint64_t seed, const GenMap& map, uint64_t* h) override {
-    if (!h || n == 0) return MSMZ_ERR_ARG;
-    MSMZ_HIP(hipSetDevice(device_));
-    Handle hd{1, n, false};
-    if (int st = alloc_handle(hd, n * 32)) return st;
-    hipLaunchKernelGGL((k_gen_scalars<Fr>), dim3((n + 255) / 256), dim3(256), 0, stream_, hd.mem.as<uint32_t>(),
-                       (uint32_t)n, seed, map);
-    MSMZ_HIP(hipGetLastError());
-    MSMZ_HIP(hipStreamSynchronize(stream_));
-    return add_handle(std::move(hd), h);
-  }
-
-  int download_points(uint64_t hd, uint64_t first, uint64_t count, uint8_t* xy, uint8_t* inf) override {
-    auto it = handles_.find(hd);
-    if (it == handles_.end() || it->second.kind != 0 || !xy) return MSMZ_ERR_ARG;
-    {
-      // the endomorphism images stay readable; a precomputed set: all its copies
-      const uint64_t have = it->second.factor ? it->second.copy_stride * it->second.factor
-                                              : it->second.n * (it->second.has_endo ? 2 : 1);
-      if (first > have || count > have - first) return MSMZ_ERR_ARG;        // (no first + count: it can wrap)
-    }
-    if (count == 0) return MSMZ_OK;
-    MSMZ_HIP(hipSetDevice(device_));
-    int st = stage_.ensure(count * RW * 4);
-    if (st) return st;
-    if constexpr (TE) {
-      hipLaunchKernelGGL((k_te_points_from_niels<F>), dim3((count + 255) / 256), dim3(256), 0, stream_,
-                         stage_.as<uint32_t>(), it->second.mem.template as<const uint32_t>() + first * PW_WORDS, (uint32_t)count);
-    } else {
-      hipLaunchKernelGGL((k_points_from_mont<F>), dim3((count + 255) / 256), dim3(256), 0, stream_,
-                         stage_.as<uint32_t>(), it->second.mem.template as<const uint32_t>() + first * PW_WORDS, (uint32_t)count);
-    }
-    MSMZ_HIP(hipGetLastError());
-    MSMZ_HIP(hipMemcpyAsync(xy, stage_.p, count * RW * 4, hipMemcpyDeviceToHost, stream_));
-    MSMZ_HIP(hipStreamSynchronize(stream_));
-    if (inf) {
-      for (uint64_t i = 0; i < count; i++) {
-        bool z = !TE;   // twisted Edwards has no point at infinity: the identity is the affine point (0, 1)
-        for (int j = 0; j < RW * 4; j++) z = z && xy[i * RW * 4 + j] == 0;
-        inf[i] = z ? 1 : 0;
-      }
-    }
-    return MSMZ_OK;
-  }
-
-  int download_scalars(uint64_t hd, uint64_t first, uint64_t count, uint8_t* s) override {
-    auto it = handles_.find(hd);
-    if (it == handles_.end() || it->second.kind != 1 || !s) return MSMZ_ERR_ARG;
-    if (first > it->second.n || count > it->second.n - first) return MSMZ_ERR_ARG;
-    if (count == 0) return MSMZ_OK;
-    MSMZ_HIP(hipSetDevice(device_));
-    MSMZ_HIP(hipMemcpy(s, it->second.mem.template as<const uint8_t>() + first * 32, count * 32, hipMemcpyDeviceToHost));
-    return MSMZ_OK;
-  }
-
-  int free_handle(uint64_t hd) override {
-    auto it = handles_.find(hd);
-    if (it == handles_.end()) return MSMZ_ERR_ARG;
-    (void)hipSetDevice(device_);
-    handles_.erase(it);
-    return MSMZ_OK;
-  }
-
-  // ------------------------------------------------------------------------------------------ validation
-  // msmz_check_points: the curve equation, then (if asked, and unless the curve has cofactor 1) [q]P = O, over base
-  // points [first, first + count) of a plain point handle.  A query: bad points are reported, not refused.  Two launches,
-  // then the result record and the verdict bytes come back behind ONE host wait, like the error word of an upload.
-  int check_points(uint64_t hd, uint64_t first, uint64_t count, uint32_t what, msmz_check_result* out,
-                   uint8_t* verdicts) override {
-    if (!out || count == 0 || what == 0 || (what & ~(uint32_t)(MSMZ_CHECK_CURVE | MSMZ_CHECK_SUBGROUP))) return MSMZ_ERR_ARG;
-    auto it = handles_.find(hd);
-    if (it == handles_.end() || it->second.kind != 0) return MSMZ_ERR_ARG;
-    if (it->second.factor) return MSMZ_ERR_UNSUPPORTED;   // derived data: the source set is what a caller checks
-    if (first > it->second.n || count > it->second.n - first) return MSMZ_ERR_ARG;   // (base points only; no first + count: it can wrap)
-    MSMZ_HIP(hipSetDevice(device_));
-    if (int st = ensure_host_check(verdicts ? count : 0)) return st;
-    if (int st = check_.ensure(sizeof(CheckResult) + count)) return st;
-    CheckResult* d_res = check_.as<CheckResult>();
-    uint8_t* d_verdicts = check_.as<uint8_t>() + sizeof(CheckResult);
-    const uint32_t* recs = it->second.mem.template as<const uint32_t>() + first * PW_WORDS;
-    const dim3 grid((uint32_t)((count + 255) / 256)), block(256);
-    MSMZ_HIP(hipMemsetAsync(d_res, 0, 8, stream_));
-    MSMZ_HIP(hipMemsetAsync(&d_res->first_bad, 0xff, 4, stream_));
-    const bool chain = (what & MSMZ_CHECK_SUBGROUP) && !Fr::PRIME_ORDER;   // cofactor 1: the curve is the subgroup
-    if constexpr (TE) {
-      hipLaunchKernelGGL((k_te_check_curve<F>), grid, block, 0, stream_, d_verdicts, d_res, recs, (uint32_t)count, (uint32_t)first);
-      if (chain)
-        hipLaunchKernelGGL((k_te_check_subgroup<F, Fr>), grid, block, 0, stream_, d_verdicts, d_res, recs, (uint32_t)count, (uint32_t)first);
-    } else {
-      hipLaunchKernelGGL((k_check_curve<F>), grid, block, 0, stream_, d_verdicts, d_res, recs, (uint32_t)count, (uint32_t)first);
-      if (chain)
-        hipLaunchKernelGGL((k_check_subgroup<F, Fr>), grid, block, 0, stream_, d_verdicts, d_res, recs, (uint32_t)count, (uint32_t)first);
-    }
-    MSMZ_HIP(hipGetLastError());
-    // both land in pinned memory (a copy into the caller's pageable buffer would block the host a second time)
-    MSMZ_HIP(hipMemcpyAsync(h_check_, d_res, sizeof(CheckResult) + (verdicts ? count : 0), hipMemcpyDeviceToHost, stream_));
-    MSMZ_HIP(hipStreamSynchronize(stream_));
-    if (verdicts) memcpy(verdicts, reinterpret_cast<const uint8_t*>(h_check_) + sizeof(CheckResult), count);
-    out->off_curve = h_check_->off_curve;
-    out->off_subgroup = h_check_->off_subgroup;
-    out->first_bad = h_check_->first_bad == 0xffffffffu ? UINT64_MAX : h_check_->first_bad;
-    return MSMZ_OK;
-  }
-
-  // ------------------------------------------------------------------------------------------ per-point multiplication
-  // msmz_points_mul: a new plain point handle, record i = [s_i] P_i (+ Q_i).  One launch; the error word (a resident
-  // scalar >= q) comes back behind the ONE host wait, like that of an upload.
-  int points_mul(const msmz_mul& m, uint64_t n, uint64_t* h) override {
-    if (!h || n == 0 || n >= (1ull << (Cfg::HAS_ENDO ? 29 : 30))) return MSMZ_ERR_ARG;   // as random_points
-    auto pit = handles_.find(m.points_handle);
-    if (pit == handles_.end() || pit->second.kind != 0) return MSMZ_ERR_ARG;
-    auto qit = handles_.end(), sit = handles_.end();
-    if (m.addend_handle) {
-      qit = handles_.find(m.addend_handle);
-      if (qit == handles_.end() || qit->second.kind != 0) return MSMZ_ERR_ARG;
-    }
-    if (m.scalars_handle) {
-      sit = handles_.find(m.scalars_handle);
-      if (sit == handles_.end() || sit->second.kind != 1) return MSMZ_ERR_ARG;
-    } else if (!m.scalar) {
-      return MSMZ_ERR_ARG;
-    }
-    if (pit->second.factor || (m.addend_handle && qit->second.factor)) return MSMZ_ERR_UNSUPPORTED;   // derived data
-    auto beyond = [n](const Handle& s, uint64_t first) { return first > s.n || n > s.n - first; };   // (no first + n: it can wrap)
-    if (beyond(pit->second, m.first_p) || (m.addend_handle && beyond(qit->second, m.first_q)) ||
-        (m.scalars_handle && beyond(sit->second, m.first_s)))
-      return MSMZ_ERR_ARG;
-    MulScalar bc{};
-    if (!m.scalars_handle) {
-      memcpy(bc.w, m.scalar, 32);
-      if (words_geq<8>(bc.w, Fr::Q)) return MSMZ_ERR_RANGE;
-    }
-    MSMZ_HIP(hipSetDevice(device_));
-    const bool endo = Cfg::HAS_ENDO;
-    Handle hd{0, n, endo};
-    if (int st = alloc_handle(hd, (size_t)n * PW_WORDS * 4 * (endo ? 2 : 1))) return st;
-    MsmMeta* d_meta = meta_.as<MsmMeta>();
-    MSMZ_HIP(hipMemsetAsync(&d_meta->error, 0, 4, stream_));
-    const uint32_t* P = pit->second.mem.template as<const uint32_t>() + m.first_p * PW_WORDS;
-    const uint32_t* Q = m.addend_handle ? qit->second.mem.template as<const uint32_t>() + m.first_q * PW_WORDS : nullptr;
-    const uint32_t* S = m.scalars_handle ? sit->second.mem.template as<const uint32_t>() + m.first_s * 8 : nullptr;
-    const dim3 grid((uint32_t)((n + 255) / 256)), block(256);   // whole blocks: every wave reaches the inversion entire
-    if constexpr (TE) {
-      hipLaunchKernelGGL((k_te_points_mul<F, Fr>), grid, block, 0, stream_, hd.mem.as<uint32_t>(), P, S, bc, Q, (uint32_t)n,
-                         &d_meta->error);
-    } else {
-      hipLaunchKernelGGL((k_points_mul<F, Fr>), grid, block, 0, stream_, hd.mem.as<uint32_t>(), P, S, bc, Q, (uint32_t)n,
-                         endo ? 1 : 0, &d_meta->error);
-    }
-    uint32_t err = 0;
-    if (int st = fetch_error(&err)) return st;
-    if (err) return MSMZ_ERR_RANGE;   // a resident scalar >= group order
-    return add_handle(std::move(hd), h);
-  }
-
-  // ------------------------------------------------------------------------------------------ scalar-set arithmetic
-  // msmz_scalars_combine: out_i = x.c_i x.v_i (+ y.c_i y.v_i) into a new scalar handle or over a range of an existing
-  // one.  One launch; the error word (a resident record >= q) comes back behind the ONE host wait.
-  int scalars_combine(const msmz_scalar_term& x, const msmz_scalar_term* y, uint64_t n, uint64_t first_out,
-                      uint64_t* out_handle) override {
-    if (!out_handle || n == 0 || n >> 32) return MSMZ_ERR_ARG;
-    const bool fresh = *out_handle == 0;
-    if (fresh && first_out != 0) return MSMZ_ERR_ARG;
-    auto beyond = [n](const Handle& s, uint64_t first) { return first > s.n || n > s.n - first; };   // (no first + n: it can wrap)
-    // a range of a scalar set -> its first record; a partial overlap with the destination is refused
-    auto range = [&](uint64_t h, uint64_t first, const uint32_t** p) {
-      auto it = handles_.find(h);
-      if (it == handles_.end() || it->second.kind != 1 || beyond(it->second, first)) return false;
-      if (!fresh && h == *out_handle && first != first_out && (first > first_out ? first - first_out : first_out - first) < n)
-        return false;
-      *p = it->second.mem.template as<const uint32_t>() + first * 8;
-      return true;
-    };
-    ScalarTerm t[2] = {};
-    const msmz_scalar_term* in[2] = {&x, y};
-    for (int k = 0; k < 2; k++) {
-      if (!in[k]) continue;
-      if (!range(in[k]->handle, in[k]->first, &t[k].v)) return MSMZ_ERR_ARG;
-      if (in[k]->coeff_handle && !range(in[k]->coeff_handle, in[k]->coeff_first, &t[k].c)) return MSMZ_ERR_ARG;
-    }
-    uint32_t* out = nullptr;
-    if (!fresh) {
-      auto it = handles_.find(*out_handle);
-      if (it == handles_.end() || it->second.kind != 1 || beyond(it->second, first_out)) return MSMZ_ERR_ARG;
-      out = it->second.mem.template as<uint32_t>() + first_out * 8;
-    }
-    for (int k = 0; k < 2; k++) {
-      if (!in[k] || in[k]->coeff_handle) continue;
-      if (!in[k]->coeff) {
-        t[k].unit = 1;
-        continue;
-      }
-      uint32_t c[8];
-      memcpy(c, in[k]->coeff, 32);
-      if (words_geq<8>(c, Fr::Q)) return MSMZ_ERR_RANGE;
-      fr_to_mont<Fr>(t[k].k.w, c);
-    }
-    MSMZ_HIP(hipSetDevice(device_));
-    Handle hd{1, n, false};
-    if (fresh) {
-      if (int st = alloc_handle(hd, n * 32)) return st;
-      out = hd.mem.as<uint32_t>();
-    }
-    MsmMeta* d_meta = meta_.as<MsmMeta>();
-    MSMZ_HIP(hipMemsetAsync(&d_meta->error, 0, 4, stream_));
-    hipLaunchKernelGGL((k_scalars_combine<Fr>), dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream_, out, t[0], t[1],
-                       (uint32_t)n, &d_meta->error);
-    uint32_t err = 0;
-    if (int st = fetch_error(&err)) return st;
-    if (err) return MSMZ_ERR_RANGE;   // a resident record >= group order
-    return fresh ? add_handle(std::move(hd), out_handle) : (int)MSMZ_OK;
-  }
-
-  // msmz_scalars_dot: one partial sum per tile, one workgroup folds them; the result and the error word share a
-  // 64-byte record in front of the partial sums and come back in ONE copy behind ONE host wait.
-  int scalars_dot(uint64_t xh, uint64_t first_x, uint64_t yh, uint64_t first_y, uint64_t n, uint8_t* out) override {
-    if (!out || n == 0 || n >> 32) return MSMZ_ERR_ARG;
-    auto xit = handles_.find(xh);
-    if (xit == handles_.end() || xit->second.kind != 1) return MSMZ_ERR_ARG;
-    auto yit = handles_.end();
-    if (yh) {
-      yit = handles_.find(yh);
-      if (yit == handles_.end() || yit->second.kind != 1) return MSMZ_ERR_ARG;
-    } else if (first_y) {
-      return MSMZ_ERR_ARG;
-    }
-    auto beyond = [n](const Handle& s, uint64_t first) { return first > s.n || n > s.n - first; };
-    if (beyond(xit->second, first_x) || (yh && beyond(yit->second, first_y))) return MSMZ_ERR_ARG;
-    MSMZ_HIP(hipSetDevice(device_));
-    const uint32_t tiles = (uint32_t)((n + SDOT_TILE - 1) / SDOT_TILE);
-    if (int st = sdot_.ensure(64 + (size_t)tiles * 32)) return st;
-    uint32_t* d_res = sdot_.as<uint32_t>();   // words 0..7: the result, word 8: the error word, from word 16: the partial sums
-    MSMZ_HIP(hipMemsetAsync(d_res, 0, 64, stream_));
-    const uint32_t* X = xit->second.mem.template as<const uint32_t>() + first_x * 8;
-    const uint32_t* Y = yh ? yit->second.mem.template as<const uint32_t>() + first_y * 8 : nullptr;
-    hipLaunchKernelGGL((k_scalars_dot<Fr>), dim3(tiles), dim3(SDOT_THREADS), 0, stream_, d_res + 16, X, Y, (uint32_t)n, d_res + 8);
-    hipLaunchKernelGGL((k_scalars_dot_fold<Fr>), dim3(1), dim3(SDOT_THREADS), 0, stream_, d_res, d_res + 16, tiles, Y ? 1 : 0);
-    MSMZ_HIP(hipGetLastError());
-    MSMZ_HIP(hipMemcpyAsync(h_res_, d_res, 64, hipMemcpyDeviceToHost, stream_));   // (pinned: init sized it for far more)
-    MSMZ_HIP(hipStreamSynchronize(stream_));
-    if (h_res_[8]) return MSMZ_ERR_RANGE;   // a resident record >= group order
-    memcpy(out, h_res_, 32);
-    return MSMZ_OK;
-  }
-
-  // msmz_scalars_powers: a new scalar handle, local entry i = base ratio^(set index of i).  The host builds the table of
-  // ratio^(2^k) with fr.h; it travels as a kernel argument.
-  int scalars_powers(const uint8_t* base, const uint8_t* ratio, uint64_t n, const GenMap& map, uint64_t* h) override {
-    if (!h || !ratio || n == 0 || n >> 32) return MSMZ_ERR_ARG;
-    FrConst b{};
-    uint32_t r[8];
-    b.w[0] = 1;
-    if (base) memcpy(b.w, base, 32);
-    memcpy(r, ratio, 32);
-    if (words_geq<8>(b.w, Fr::Q) || words_geq<8>(r, Fr::Q)) return MSMZ_ERR_RANGE;
-    FrPowTable table;
-    fr_pow_table<Fr>(table, r);
-    MSMZ_HIP(hipSetDevice(device_));
-    Handle hd{1, n, false};
-    if (int st = alloc_handle(hd, n * 32)) return st;
-    const uint64_t threads = (n + SPOW_RUN - 1) / SPOW_RUN;
-    hipLaunchKernelGGL((k_scalars_powers<Fr>), dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, stream_,
-                       hd.mem.as<uint32_t>(), b, table, (uint32_t)n, map);
-    MSMZ_HIP(hipGetLastError());
-    MSMZ_HIP(hipStreamSynchronize(stream_));
-    return add_handle(std::move(hd), h);
-  }
-
-  // A range of n entries of a scalar set for msmz_scalars_recurrence / _inverse -> its first record; false: not a scalar
-  // set, beyond it, or overlapping the destination [first_out, +n) of *out_handle in part (fresh: no destination yet).
-  bool scan_range(uint64_t h, uint64_t first, uint64_t n, bool fresh, uint64_t out_handle, uint64_t first_out,
-                  const uint32_t** p) {
-    auto it = handles_.find(h);
-    if (it == handles_.end() || it->second.kind != 1 || first > it->second.n || n > it->second.n - first) return false;
-    if (!fresh && h == out_handle && first != first_out && (first > first_out ? first - first_out : first_out - first) < n)
-      return false;
-    *p = it->second.mem.template as<const uint32_t>() + first * 8;
-    return true;
-  }
-
-  // msmz_scalars_recurrence: three launches (tile aggregates, ONE workgroup of carries, apply); the final value and the
-  // error word share a 64-byte record in front of the scratch and come back in ONE copy behind ONE host wait.
-  int scalars_recurrence(const msmz_scalar_rec& r, uint64_t n, uint64_t first_out, uint64_t* out_handle,
-                         uint8_t* last) override {
-    if (!out_handle || n == 0 || n >> 32 || (r.flags & ~(uint32_t)(MSMZ_REC_REVERSE | MSMZ_REC_EXCLUSIVE)))
-      return MSMZ_ERR_ARG;
-    if (!r.a_handle && !r.a && !r.b_handle) return MSMZ_ERR_ARG;   // y_i = y_(i-1): nothing to do
-    const bool fresh = *out_handle == 0;
-    if (fresh && first_out != 0) return MSMZ_ERR_ARG;
-    const uint32_t *A = nullptr, *B = nullptr;
-    if (r.a_handle && !scan_range(r.a_handle, r.a_first, n, fresh, *out_handle, first_out, &A)) return MSMZ_ERR_ARG;
-    if (r.b_handle && !scan_range(r.b_handle, r.b_first, n, fresh, *out_handle, first_out, &B)) return MSMZ_ERR_ARG;
-    uint32_t* out = nullptr;
-    if (!fresh) {
-      auto it = handles_.find(*out_handle);
-      if (it == handles_.end() || it->second.kind != 1 || first_out > it->second.n || n > it->second.n - first_out)
-        return MSMZ_ERR_ARG;
-      out = it->second.mem.template as<uint32_t>() + first_out * 8;
-    }
-    FrConst k{}, init{};
-    if (!r.a_handle && r.a) {
-      uint32_t c[8];
-      memcpy(c, r.a, 32);
-      if (words_geq<8>(c, Fr::Q)) return MSMZ_ERR_RANGE;
-      fr_to_mont<Fr>(k.w, c);
-    }
-    if (r.init) {
-      memcpy(init.w, r.init, 32);
-      if (words_geq<8>(init.w, Fr::Q)) return MSMZ_ERR_RANGE;
-    } else if (!B) {
-      init.w[0] = 1;
-    }
-    MSMZ_HIP(hipSetDevice(device_));
-    Handle hd{1, n, false};
-    if (fresh) {
-      if (int st = alloc_handle(hd, n * 32)) return st;
-      out = hd.mem.as<uint32_t>();
-    }
-    const uint32_t tiles = (uint32_t)((n + SREC_TILE - 1) / SREC_TILE);
-    // words 0..7: the final value, word 8: the error word; then the aggregates' A, their B, and tiles + 1 incoming values
-    if (int st = sscan_.ensure(64 + ((size_t)tiles * 3 + 1) * 32)) return st;
-    uint32_t* d_res = sscan_.as<uint32_t>();
-    uint32_t* aggA = d_res + 16;
-    uint32_t* aggB = aggA + (size_t)tiles * 8;
-    uint32_t* incoming = aggB + (size_t)tiles * 8;
-    MSMZ_HIP(hipMemsetAsync(d_res, 0, 64, stream_));
-    const uint32_t nn = (uint32_t)n, flags = r.flags;
-    const dim3 grid(tiles), block(SREC_THREADS);
-#define MSMZ_REC_LAUNCH(AM, HB)                                                                                          \
-  do {                                                                                                                   \
-    hipLaunchKernelGGL((k_scalars_rec_tile<Fr, AM, HB>), grid, block, 0, stream_, aggA, aggB, A, B, k, nn, flags, d_res + 8); \
-    hipLaunchKernelGGL((k_scalars_rec_carry<Fr, AM != SREC_A_NONE, HB>), dim3(1), block, 0, stream_, incoming, d_res,    \
-                       (const uint32_t*)aggA, (const uint32_t*)aggB, init, tiles);                                       \
-    hipLaunchKernelGGL((k_scalars_rec_apply<Fr, AM, HB>), grid, block, 0, stream_, out, A, B, k, (const uint32_t*)incoming, \
-                       nn, flags);                                                                                       \
-  } while (0)
-    if (A && B) MSMZ_REC_LAUNCH(SREC_A_RESIDENT, true);
-    else if (A) MSMZ_REC_LAUNCH(SREC_A_RESIDENT, false);
-    else if (r.a && B) MSMZ_REC_LAUNCH(SREC_A_BROADCAST, true);
-    else if (r.a) MSMZ_REC_LAUNCH(SREC_A_BROADCAST, false);
-    else MSMZ_REC_LAUNCH(SREC_A_NONE, true);
-#undef MSMZ_REC_LAUNCH
-    MSMZ_HIP(hipGetLastError());
-    MSMZ_HIP(hipMemcpyAsync(h_res_, d_res, 64, hipMemcpyDeviceToHost, stream_));   // (pinned: init sized it for far more)
-    MSMZ_HIP(hipStreamSynchronize(stream_));
-    if (h_res_[8]) return MSMZ_ERR_RANGE;   // a resident record >= group order
-    if (last) memcpy(last, h_res_, 32);
-    return fresh ? add_handle(std::move(hd), out_handle) : (int)MSMZ_OK;
-  }
-
-  // msmz_scalars_inverse: one launch; the error word and the zero count share the record
-  int scalars_inverse(uint64_t h, uint64_t first, uint64_t n, uint64_t first_out, uint64_t* out_handle,
-                      uint64_t* n_zero) override {
-    if (!out_handle || n == 0 || n >> 32) return MSMZ_ERR_ARG;
-    const bool fresh = *out_handle == 0;
-    if (fresh && first_out != 0) return MSMZ_ERR_ARG;
-    const uint32_t* X = nullptr;
-    if (!scan_range(h, first, n, fresh, *out_handle, first_out, &X)) return MSMZ_ERR_ARG;
-    uint32_t* out = nullptr;
-    if (!fresh) {
-      auto it = handles_.find(*out_handle);
-      if (it == handles_.end() || it->second.kind != 1 || first_out > it->second.n || n > it->second.n - first_out)
-        return MSMZ_ERR_ARG;
-      out = it->second.mem.template as<uint32_t>() + first_out * 8;
-    }
-    MSMZ_HIP(hipSetDevice(device_));
-    Handle hd{1, n, false};
-    if (fresh) {
-      if (int st = alloc_handle(hd, n * 32)) return st;
-      out = hd.mem.as<uint32_t>();
-    }
-    if (int st = sscan_.ensure(64)) return st;
-    uint32_t* d_res = sscan_.as<uint32_t>();   // word 8: the error word, word 9: the zeros
-    MSMZ_HIP(hipMemsetAsync(d_res, 0, 64, stream_));
-    const uint64_t per_block = (uint64_t)SINV_THREADS * SINV_E;
-    hipLaunchKernelGGL((k_scalars_inverse<Fr>), dim3((uint32_t)((n + per_block - 1) / per_block)), dim3(SINV_THREADS), 0,
-                       stream_, out, X, (uint32_t)n, d_res);
-    MSMZ_HIP(hipGetLastError());
-    MSMZ_HIP(hipMemcpyAsync(h_res_, d_res, 64, hipMemcpyDeviceToHost, stream_));
-    MSMZ_HIP(hipStreamSynchronize(stream_));
-    if (h_res_[8]) return MSMZ_ERR_RANGE;   // a resident record >= group order
-    if (n_zero) *n_zero = h_res_[9];
-    return fresh ? add_handle(std::move(hd), out_handle) : (int)MSMZ_OK;
   }
 
   // ------------------------------------------------------------------------------------------ precomputed point sets
@@ -950,17 +227,15 @@ class Engine : public IEngine {
   // new handle: `F` copies of the first n points of `ph`, copy j = 2^(c j) P_i (+ the endomorphism images with glv)
   int precompute_points(uint64_t ph, uint64_t n, int c, int glv, uint32_t copies, int sbits, uint64_t* h) override {
     if (TE) return MSMZ_ERR_UNSUPPORTED;
-    auto pit = handles_.find(ph);
-    if (!h || pit == handles_.end() || pit->second.kind != 0 || pit->second.factor != 0 || n == 0 || pit->second.n < n ||
-        copies < 2 || c < 2 || c > 24)
-      return MSMZ_ERR_ARG;
-    const Handle& src = pit->second;
+    const Handle* plain = handles_.get(ph, 0);
+    if (!h || !plain || plain->factor != 0 || n == 0 || plain->n < n || copies < 2 || c < 2 || c > 24) return MSMZ_ERR_ARG;
+    const Handle& src = *plain;
     if (glv && !src.has_endo) return MSMZ_ERR_UNSUPPORTED;
     MSMZ_HIP(hipSetDevice(device_));
     const uint64_t R = n * (glv ? 2 : 1);
     const size_t rec = (size_t)PW_WORDS * 4;
-    Handle hd{0, n, glv != 0};
-    if (int st = alloc_handle(hd, (size_t)copies * R * rec)) return st;
+    Handle hd;
+    if (int st = new_handle(&hd, 0, n, glv != 0, (size_t)copies * R * rec)) return st;
     uint8_t* dev = hd.mem.as<uint8_t>();
     // copy 0: the source's first n points (and their images, which follow the source's whole set)
     MSMZ_HIP(hipMemcpyAsync(dev, src.mem.p, n * rec, hipMemcpyDeviceToDevice, stream_));
@@ -984,9 +259,9 @@ class Engine : public IEngine {
 
   int precomputed_info(uint64_t hd, int32_t* c, int32_t* glv, uint32_t* factor, uint32_t* K, uint64_t* records,
                        int32_t* sbits) override {
-    auto it = handles_.find(hd);
-    if (it == handles_.end() || it->second.factor == 0) return MSMZ_ERR_ARG;
-    const Handle& h = it->second;
+    const Handle* pre = handles_.get(hd, 0);
+    if (!pre || pre->factor == 0) return MSMZ_ERR_ARG;
+    const Handle& h = *pre;
     const int b = planner_.scalar_bits(h.glv != 0, 0, h.sbits);
     if (sbits) *sbits = h.sbits;
     if (c) *c = h.c;
@@ -1007,12 +282,12 @@ class Engine : public IEngine {
                 uint64_t host_stride = 0) override {
     auto t_begin = std::chrono::steady_clock::now();
     if (!out || !out_inf || n == 0 || batch == 0) return MSMZ_ERR_ARG;
-    auto pit = handles_.find(ph);
-    if (pit == handles_.end() || pit->second.kind != 0 || pit->second.n < n) return MSMZ_ERR_ARG;
+    const Handle* pp = handles_.get(ph, 0);
+    if (!pp || !in_range(0, n, pp->n)) return MSMZ_ERR_ARG;
+    const Handle& pts = *pp;
     msmz_opts opt;
-    int st0 = resolve_opts(pit->second, o, &opt);
-    if (st0) return st0;
-    if (opt.glv < 0) opt.glv = pit->second.has_endo && planner_.default_glv(n, opt.reserved[1]) ? 1 : 0;   // (per problem: batch = 1 is msm())
+    if (int st = resolve_opts(pts, o, &opt)) return st;
+    if (opt.glv < 0) opt.glv = pts.has_endo && planner_.default_glv(n, opt.reserved[1]) ? 1 : 0;   // (per problem: batch = 1 is msm())
     if (host_stride == 0) host_stride = n;
     if (host_scalars && host_stride < n) return MSMZ_ERR_ARG;
     MSMZ_HIP(hipSetDevice(device_));
@@ -1026,18 +301,15 @@ class Engine : public IEngine {
         if ((st = copy_h2d(stage_.p, host_scalars, 32, total, nullptr))) return st;
       } else {
         for (uint32_t k = 0; k < batch; k++)
-          if ((st = copy_h2d(stage_.as<uint8_t>() + (size_t)k * n * 32, host_scalars + (size_t)k * host_stride * 32, 32, n,
+          if ((st = copy_h2d(stage_.template as<uint8_t>() + (size_t)k * n * 32, host_scalars + (size_t)k * host_stride * 32, 32, n,
                              split)))
             return st;
       }
-      d_scalars = stage_.as<uint32_t>();
-    } else {
-      auto sit = handles_.find(sh);
-      if (sit == handles_.end() || sit->second.kind != 1 || sit->second.n < total) return MSMZ_ERR_ARG;
-      d_scalars = sit->second.mem.template as<const uint32_t>();
+      d_scalars = stage_.template as<uint32_t>();
+    } else if (!(d_scalars = handles_.range(sh, 1, 0, total, 8))) {
+      return MSMZ_ERR_ARG;
     }
     if (log) memset(log, 0, sizeof(*log));
-    const Handle& pts = pit->second;
     int st = MSMZ_OK;
     for (uint32_t done = 0; done < batch && st == MSMZ_OK;) {
       msmz_log plog;
@@ -1049,10 +321,7 @@ class Engine : public IEngine {
       if (log) merge_log(log, plog, done == 0, LogMerge::SEQUENTIAL);
       done += ran;
     }
-    if (log) {
-      log->stage_ms[MSMZ_ST_TOTAL] =
-          std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    }
+    stamp_total(log, t_begin);
     return st;
   }
 
@@ -1063,15 +332,14 @@ class Engine : public IEngine {
                    int* out_inf, msmz_log* log) override {
     auto t_begin = std::chrono::steady_clock::now();
     if (!segs || !out || !out_inf || n_segs == 0) return MSMZ_ERR_ARG;
-    auto pit = handles_.find(ph), sit = handles_.find(sh);
-    if (pit == handles_.end() || pit->second.kind != 0 || sit == handles_.end() || sit->second.kind != 1) return MSMZ_ERR_ARG;
-    const Handle& pts = pit->second;
-    const Handle& sc = sit->second;
+    const Handle *pp = handles_.get(ph, 0), *sp = handles_.get(sh, 1);
+    if (!pp || !sp) return MSMZ_ERR_ARG;
+    const Handle& pts = *pp;
+    const Handle& sc = *sp;
     std::vector<uint64_t> lens(n_segs);
     for (uint32_t k = 0; k < n_segs; k++) {
-      const msmz_segment& s = segs[k];   // (no first + n: it can wrap)
-      if (s.n == 0 || s.first_p > pts.n || s.n > pts.n - s.first_p || s.first_s > sc.n || s.n > sc.n - s.first_s)
-        return MSMZ_ERR_ARG;
+      const msmz_segment& s = segs[k];
+      if (s.n == 0 || !in_range(s.first_p, s.n, pts.n) || !in_range(s.first_s, s.n, sc.n)) return MSMZ_ERR_ARG;
       lens[k] = s.n;
     }
     msmz_opts opt;
@@ -1101,10 +369,7 @@ class Engine : public IEngine {
         done += ran;
       }
     }
-    if (log) {
-      log->stage_ms[MSMZ_ST_TOTAL] =
-          std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    }
+    stamp_total(log, t_begin);
     return st;
   }
 
@@ -1131,46 +396,6 @@ class Engine : public IEngine {
 
   // ------------------------------------------------------------------------------------------ what only the engine calls
  private:
-  // Host -> device copy of this engine's `n` local records of `rec` bytes.  split == nullptr: one contiguous copy.
-  // Otherwise the engine is shard `split->shard` of `split->nshards` inside a multi-device context (multi.h): its local
-  // block b is global block b * nshards + shard of the caller's buffer, so every block is copied straight from where
-  // the caller has it -- no gathered host copy in between.
-  int copy_h2d(void* dst, const uint8_t* src, size_t rec, uint64_t n, const GenMap* split) {
-    if (!split || split->nshards <= 1) {
-      MSMZ_HIP(hipMemcpyAsync(dst, src, n * rec, hipMemcpyHostToDevice, stream_));
-      return MSMZ_OK;
-    }
-    const uint64_t blk = 1ull << split->blk_shift;
-    for (uint64_t li = 0; li < n; li += blk) {
-      const uint64_t len = n - li < blk ? n - li : blk;
-      const uint64_t gi = ((li >> split->blk_shift) * split->nshards + split->shard) << split->blk_shift;
-      MSMZ_HIP(hipMemcpyAsync((uint8_t*)dst + li * rec, src + gi * rec, len * rec, hipMemcpyHostToDevice, stream_));
-    }
-    return MSMZ_OK;
-  }
-
-  // *word = the meta error word as the launches queued so far leave it (one host round trip).  What a bit means is the
-  // caller's to say: it differs between the kernels that raise them.
-  int fetch_error(uint32_t* word) {
-    MSMZ_HIP(hipGetLastError());
-    MSMZ_HIP(hipMemcpyAsync(&h_meta_->error, &meta_.as<MsmMeta>()->error, 4, hipMemcpyDeviceToHost, stream_));
-    MSMZ_HIP(hipStreamSynchronize(stream_));
-    *word = h_meta_->error;
-    return MSMZ_OK;
-  }
-
-  // the device memory of a new handle (owned by it: an error before add_handle frees it)
-  int alloc_handle(Handle& hd, size_t bytes) {
-    MSMZ_HIP(hipMalloc(&hd.mem.p, bytes));
-    hd.mem.bytes = bytes;
-    return MSMZ_OK;
-  }
-  int add_handle(Handle&& hd, uint64_t* h) {
-    *h = next_handle_++;
-    handles_.emplace(*h, std::move(hd));
-    return MSMZ_OK;
-  }
-
   // The options of an MSM over handle `h`: a precomputed set fixes c and the GLV choice (opts->c must be 0 or its c,
   // opts->glv -1 or its choice; a null opts means both defaults) and takes batched-affine buckets with the 2-D reduction.
   // reserved[1], the scalar bit bound, leaves here as the planner's (Planner::bound); a precomputed set fixes it too.
@@ -1190,6 +415,27 @@ class Engine : public IEngine {
     return MSMZ_OK;
   }
 
+  static void stamp_total(msmz_log* log, std::chrono::steady_clock::time_point t0) {
+    if (!log) return;
+    log->stage_ms[MSMZ_ST_TOTAL] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+
+  // What run_problems and run_segments decide from: msmBasic or batched-affine buckets, the (half-)scalars of one index
+  // range pass, and how many of `candidates` problems of n entries run as ONE batched pipeline (1: the first alone).
+  struct Shape {
+    bool basic;
+    uint64_t per_pass;
+    uint32_t bs;
+  };
+  Shape shape(uint64_t n, uint32_t candidates, const msmz_opts& opt, const Handle& pts) const {
+    const bool basic = TE || opt.buckets == MSMZ_BUCKETS_PROJECTIVE;
+    const uint64_t per_pass = (opt.glv != 0 && !TE) ? pass_entries_ / 2 : pass_entries_;
+    const uint32_t bs = !basic && opt.reserved[0] != 1 && n <= per_pass && candidates > 1
+                            ? planner_.batch_size(n, opt, (uint32_t)pts.n, pts.factor, candidates)
+                            : 1;
+    return {basic, per_pass, bs};
+  }
+
   // How a shape runs is decided here.  Up to `remaining` problems over device scalars; *ran = how many it ran.
   //  - one batched pipeline over a sub-batch of them (planner_.batch_size): Weierstrass batched-affine buckets with the
   //    2-D reduction, n within one sort pass, and a sub-batch plan the two-level sort takes -- a plan that falls off it
@@ -1200,28 +446,24 @@ class Engine : public IEngine {
   // first_p (a segment run alone, remaining = 1): the problem's points start at record first_p of the set.
   int run_problems(const Handle& pts, const uint32_t* d_scalars, uint64_t n, uint32_t remaining, const msmz_opts& opt,
                    uint8_t* out, int* out_inf, msmz_log* log, uint32_t* ran, uint64_t first_p = 0) {
-    const bool basic = TE || opt.buckets == MSMZ_BUCKETS_PROJECTIVE;
-    const uint64_t per_pass = (opt.glv != 0 && !TE) ? pass_entries_ / 2 : pass_entries_;
+    const Shape sh = shape(n, remaining, opt, pts);
     *ran = 1;
-    const uint32_t bs = !basic && opt.reserved[0] != 1 && n <= per_pass && remaining > 1
-                            ? planner_.batch_size(n, opt, (uint32_t)pts.n, pts.factor, remaining)
-                            : 1;
-    if (bs > 1) {
+    if (sh.bs > 1) {
       Redo redo = Redo::NONE;   // (a GLV half longer than assumed: the whole sub-batch again)
       const int st = glv_retry(&redo, [&](int extra_bits, Redo* r) {
         return msm_weierstrass_affine(pts, pts.mem.template as<const uint32_t>(), d_scalars, n, opt, out, out_inf, log,
-                                      extra_bits, bs, r);
+                                      extra_bits, sh.bs, r);
       });
       if (st || redo != Redo::PER_PROBLEM) {
         if (!st) sub_batches_++;
-        *ran = bs;
+        *ran = sh.bs;
         return st;
       }
     }
     uint8_t part[RW * 4];
     int st = MSMZ_OK;
-    for (uint64_t done = 0; done < n && st == MSMZ_OK; done += per_pass) {
-      const uint64_t cnt = n - done < per_pass ? n - done : per_pass;
+    for (uint64_t done = 0; done < n && st == MSMZ_OK; done += sh.per_pass) {
+      const uint64_t cnt = n - done < sh.per_pass ? n - done : sh.per_pass;
       range_passes_++;
       const uint32_t* d_points = pts.mem.template as<const uint32_t>() + (first_p + done) * PW_WORDS;
       const uint32_t* d_sc = d_scalars + done * 8;
@@ -1231,7 +473,7 @@ class Engine : public IEngine {
       if (lp) memset(lp, 0, sizeof(*lp));
       uint8_t* o = done == 0 ? out : part;
       int* oi = done == 0 ? out_inf : &pinf;
-      if (basic) {
+      if (sh.basic) {
         st = msm_basic(pts, d_points, d_sc, cnt, opt, o, oi, lp);
       } else {
         Redo redo = Redo::NONE;
@@ -1254,21 +496,17 @@ class Engine : public IEngine {
   int run_segments(const Handle& pts, const uint32_t* d_scalars, const msmz_segment* segs, const uint32_t* order,
                    uint32_t remaining, uint64_t n_max, bool batchable, const msmz_opts& opt, uint8_t* out, int* out_inf,
                    msmz_log* log, uint32_t* ran) {
-    const bool basic = TE || opt.buckets == MSMZ_BUCKETS_PROJECTIVE;
-    const uint64_t per_pass = (opt.glv != 0 && !TE) ? pass_entries_ / 2 : pass_entries_;
-    *ran = 1;
     const uint32_t most = remaining < kMaxSegProblems ? remaining : kMaxSegProblems;
-    const uint32_t bs = !basic && opt.reserved[0] != 1 && n_max <= per_pass && most > 1 && batchable
-                            ? planner_.batch_size(n_max, opt, (uint32_t)pts.n, pts.factor, most)
-                            : 1;
+    const uint32_t bs = shape(n_max, batchable ? most : 1, opt, pts).bs;
+    *ran = 1;
     if (bs > 1) {
       int st;
-      if ((st = ensure_host_segs(bs)) || (st = segs_.ensure((size_t)bs * sizeof(SegDesc)))) return st;
+      if ((st = h_segs_.ensure((size_t)bs * sizeof(SegDesc))) || (st = segs_.ensure((size_t)bs * sizeof(SegDesc)))) return st;
       for (uint32_t p = 0; p < bs; p++) {
         const msmz_segment& s = segs[order[p]];
-        h_segs_[p] = SegDesc{(uint32_t)s.first_s, (uint32_t)s.first_p, (uint32_t)s.n};
+        h_segs_.template as<SegDesc>()[p] = SegDesc{(uint32_t)s.first_s, (uint32_t)s.first_p, (uint32_t)s.n};
       }
-      MSMZ_HIP(hipMemcpyAsync(segs_.p, h_segs_, (size_t)bs * sizeof(SegDesc), hipMemcpyHostToDevice, stream_));
+      MSMZ_HIP(hipMemcpyAsync(segs_.p, h_segs_.p, (size_t)bs * sizeof(SegDesc), hipMemcpyHostToDevice, stream_));
       std::vector<uint8_t> res((size_t)bs * RW * 4);
       std::vector<int> inf(bs, 0);
       Redo redo = Redo::NONE;
@@ -1336,7 +574,7 @@ class Engine : public IEngine {
     int st;
     if ((st = refs_.ensure((size_t)P * K * M * 4))) return st;
     if ((st = off_.ensure(((size_t)P * nb + 1) * 4))) return st;
-    MsmMeta* d_meta = meta_.as<MsmMeta>();
+    MsmMeta* d_meta = meta_.template as<MsmMeta>();
     MSMZ_HIP(hipMemsetAsync(d_meta, 0, sizeof(MsmMeta), stream_));
     if (!sl.two_level && (P > 1 || pl.F > 1)) return MSMZ_ERR_ARG;   // (msm_batch only batches plans the two-level sort handles)
     if (d_segs && (TE || !sl.two_level)) return MSMZ_ERR_ARG;         // (run_segments: the batched pipeline only)
@@ -1477,7 +715,7 @@ class Engine : public IEngine {
 
   // read the device-side totals (one host round trip)
   int fetch_meta(Run& run) {
-    MSMZ_HIP(hipMemcpyAsync(h_meta_, meta_.p, sizeof(MsmMeta), hipMemcpyDeviceToHost, stream_));
+    MSMZ_HIP(hipMemcpyAsync(h_meta_.p, meta_.p, sizeof(MsmMeta), hipMemcpyDeviceToHost, stream_));
     MSMZ_HIP(hipStreamSynchronize(stream_));
     run.max_bucket = h_meta_->max_bucket;
     run.n_entries = h_meta_->n_entries;
@@ -1530,10 +768,10 @@ class Engine : public IEngine {
   // weight unit and not needed) to h_res_, and the meta block to the host
   int fetch_window_sums(const Plan& pl, size_t per_problem) {
     const size_t words = pl.nprob * per_problem * XW;
-    if (int st = ensure_host_results(words)) return st;
+    if (int st = h_res_.ensure(words * 4)) return st;
     MSMZ_HIP(hipGetLastError());
-    MSMZ_HIP(hipMemcpyAsync(h_res_, final_.p, words * 4, hipMemcpyDeviceToHost, stream_));
-    MSMZ_HIP(hipMemcpyAsync(h_meta_, meta_.p, sizeof(MsmMeta), hipMemcpyDeviceToHost, stream_));
+    MSMZ_HIP(hipMemcpyAsync(h_res_.p, final_.p, words * 4, hipMemcpyDeviceToHost, stream_));
+    MSMZ_HIP(hipMemcpyAsync(h_meta_.p, meta_.p, sizeof(MsmMeta), hipMemcpyDeviceToHost, stream_));
     MSMZ_HIP(hipStreamSynchronize(stream_));
     return MSMZ_OK;
   }
@@ -1565,7 +803,7 @@ class Engine : public IEngine {
     const auto t_host = std::chrono::steady_clock::now();
     if (h_meta_->error & 1u) return MSMZ_ERR_DEGENERATE;
     for (uint32_t p = 0; p < pl.nprob; p++) {
-      const uint32_t* rp = h_res_ + p * per_problem * XW;
+      const uint32_t* rp = h_res_.template as<const uint32_t>() + p * per_problem * XW;
       uint32_t w[RW];
       if constexpr (TE) {
         te_to_affine_canon<F>(w, host_horner(HostTe{}, terms, rp, XW));
@@ -1692,7 +930,7 @@ class Engine : public IEngine {
   // the sort left.  No host round trip.
   int plan_phase(const PlanChunks& pc, uint32_t nb, int tail_skip, size_t desc_records, Run& run) {
     int st;
-    MsmMeta* d_meta = meta_.as<MsmMeta>();
+    MsmMeta* d_meta = meta_.template as<MsmMeta>();
     mark(run, run.ev.plan0);
     const uint32_t n_chunks = pc.n_main + (nb - pc.nb_main + pc.chunk_top - 1) / pc.chunk_top;
     // chunk totals per round, then the per-workgroup scratch of the rounds beyond PLAN_RL
@@ -1745,7 +983,7 @@ class Engine : public IEngine {
     Run run = new_run(opt);
     if ((st = sort_phase(pl, sl, d_scalars, run, (uint32_t)pts.copy_stride, d_segs))) return st;
     const uint32_t nb = pl.nb * nprob;   // buckets of all problems
-    MsmMeta* d_meta = meta_.as<MsmMeta>();
+    MsmMeta* d_meta = meta_.template as<MsmMeta>();
 
     // ---- plan: descriptors of every pair of every round + what is left of each bucket (plan_kernels.h)
     // the batched-affine first reduction level (opt.reserved[0] = 1) wants ONE sum per bucket: no rounds skipped
@@ -1816,7 +1054,7 @@ class Engine : public IEngine {
     if ((st = partials_.ensure((size_t)32 * pl.nblocks * 4))) return st;
     constexpr int AW = P::ACC_WORDS;
     const uint32_t nb = pl.nb, nblocks = pl.nblocks;
-    MsmMeta* d_meta = meta_.as<MsmMeta>();
+    MsmMeta* d_meta = meta_.template as<MsmMeta>();
     mark(run, run.ev.plan0);
     // chunk offsets: cscan[g] = sum_{g' < g} ceil(size / 2^chunk_shift); chunks of 64 entries unless some bucket is
     // very long (then ~sqrt of it: bounds both the chunk and the number of partial sums one reduction thread adds)
@@ -1830,7 +1068,7 @@ class Engine : public IEngine {
                        d_meta->round_pairs);
     hipLaunchKernelGGL(k_scan_apply, dim3(nblocks, 1), dim3(SCAN_T), 0, stream_, rscan_.as<uint32_t>(),
                        partials_.as<uint32_t>(), off_.as<uint32_t>(), nb, scan_mode, nblocks, (size_t)0, (uint32_t*)nullptr);
-    MSMZ_HIP(hipMemcpyAsync(h_meta_, d_meta, sizeof(MsmMeta), hipMemcpyDeviceToHost, stream_));
+    MSMZ_HIP(hipMemcpyAsync(h_meta_.p, d_meta, sizeof(MsmMeta), hipMemcpyDeviceToHost, stream_));
     MSMZ_HIP(hipStreamSynchronize(stream_));
     const uint32_t n_chunks = h_meta_->round_pairs[0];
     mark(run, run.ev.plan_end);
@@ -1942,81 +1180,9 @@ class Engine : public IEngine {
     }
   }
 
-  int ensure_gen_table() {
-    if (gen_table_.p) return MSMZ_OK;
-    int st = gen_table_.ensure((size_t)GEN_WINDOWS * GEN_TABLE * RW * 4);
-    if (st) return st;
-    // bases 2^(13 k) * G computed on the host, multiples on the device
-    uint32_t bases[GEN_WINDOWS * RW];
-    Affine<F> ga;
-    fe_set_const<F>(ga.x, F::GX);
-    fe_set_const<F>(ga.y, F::GY);
-    if constexpr (TE) {
-      TeExt<F> g;
-      g.X = ga.x;
-      g.Y = ga.y;
-      fe_set_const<F>(g.Z, F::ONE);
-      fe_mul(g.T, ga.x, ga.y);
-      for (int k = 0; k < GEN_WINDOWS; k++) {
-        Fe<F> zi, x, y;
-        fe_inverse(zi, g.Z);
-        fe_mul(x, g.X, zi);
-        fe_mul(y, g.Y, zi);
-        fe_store<F>(bases + k * RW, x);
-        fe_store<F>(bases + k * RW + NW, y);
-        for (int j = 0; j < GEN_BITS; j++) {
-          TeExt<F> t;
-          te_add(t, g, g);
-          g = t;
-        }
-      }
-    } else {
-      Xyzz<F> g;
-      xyzz_from_affine(g, ga);
-      for (int k = 0; k < GEN_WINDOWS; k++) {
-        Affine<F> a;
-        host_xyzz_to_affine_mont(a, g);
-        fe_store<F>(bases + k * RW, a.x);
-        fe_store<F>(bases + k * RW + NW, a.y);
-        for (int j = 0; j < GEN_BITS; j++) {
-          Xyzz<F> t;
-          xyzz_dbl(t, g);
-          g = t;
-        }
-      }
-    }
-    st = stage_.ensure(sizeof(bases));
-    if (st) return st;
-    MSMZ_HIP(hipMemcpyAsync(stage_.p, bases, sizeof(bases), hipMemcpyHostToDevice, stream_));
-    if constexpr (TE) {
-      hipLaunchKernelGGL((k_te_gen_table<F>), dim3((GEN_WINDOWS * GEN_TABLE + 127) / 128), dim3(128), 0, stream_,
-                         gen_table_.as<uint32_t>(), stage_.as<uint32_t>());
-    } else {
-      hipLaunchKernelGGL((k_gen_table<F>), dim3((GEN_WINDOWS * GEN_TABLE + 127) / 128), dim3(128), 0, stream_,
-                         gen_table_.as<uint32_t>(), stage_.as<uint32_t>());
-    }
-    MSMZ_HIP(hipGetLastError());
-    MSMZ_HIP(hipStreamSynchronize(stream_));
-    return MSMZ_OK;
-  }
-
-  static void host_xyzz_to_affine_mont(Affine<F>& a, const Xyzz<F>& p) {
-    Fe<F> zi3, t, zi2;
-    fe_inverse(zi3, p.ZZZ);
-    fe_mul(t, zi3, p.ZZ);
-    fe_sqr(zi2, t);
-    fe_mul(a.x, p.X, zi2);
-    fe_mul(a.y, p.Y, zi3);
-  }
-
   // shared state -------------------------------------------------------------------------------
-  int curve_id_, device_;
-  hipStream_t stream_ = nullptr;
+  int curve_id_;
   StageEvents ev_{};
-  hipEvent_t import_ev_ = nullptr;      // orders stream_ behind the stream that produces an imported device source
-  std::vector<uint8_t> import_pack_;    // host packing of a strided host source
-  std::map<uint64_t, Handle> handles_;
-  uint64_t next_handle_ = 1;
   // Tuning knobs (the planning ones: PlanKnobs, plan.h).  A release build uses the constants; a development build
   // (-DMSMZ_DEV, tools/build_variant.sh) reads MSMZ_* environment variables when the context is created.  None of them
   // changes a result.
@@ -2045,46 +1211,9 @@ class Engine : public IEngine {
                         env_int("MSMZ_NO_FBT", 0) != 0, env_int("MSMZ_NO_PLAN_TOP", 0) != 0,
                         env_int("MSMZ_NO_SORT_SPECIAL", 0) != 0, env_int("MSMZ_FB", 0), (uint32_t)env_int("MSMZ_S1", 0),
                         (uint32_t)env_int("MSMZ_R2_NC", 0)}};
-  DevBuf bsum_, f2desc_, tilecnt_, tileoff_, final_, desc_, bfin_, packed_, bins_, digits_, counts_, off_, cursor_, refs_, rscan_, partials_, slots_, red_[4], meta_, stage_, gen_table_;
-  MsmMeta* h_meta_ = nullptr;
-  DevBuf sdot_;                      // scalars_dot: its result record, then one partial sum per tile
-  DevBuf sscan_;                     // scalars_recurrence / _inverse: the result record, then aggregates and incoming values
-  DevBuf check_;                     // check_points: its result record, then one verdict byte per point
-  CheckResult* h_check_ = nullptr;   // pinned, grow-only landing of the result record and the verdict bytes behind it
-  size_t h_check_bytes_ = 0;
-  int ensure_host_check(size_t verdict_bytes) {
-    const size_t need = sizeof(CheckResult) + verdict_bytes;
-    if (need <= h_check_bytes_) return MSMZ_OK;
-    if (h_check_) (void)hipHostFree(h_check_);
-    h_check_ = nullptr;
-    h_check_bytes_ = 0;
-    MSMZ_HIP(hipHostMalloc(&h_check_, need));
-    h_check_bytes_ = need;
-    return MSMZ_OK;
-  }
-  DevBuf segs_;                  // run_segments: the descriptor table of a sub-batch ...
-  SegDesc* h_segs_ = nullptr;    // ... and its pinned, grow-only host copy (rewritten only after the sub-batch's final fetch)
-  size_t h_segs_n_ = 0;
-  int ensure_host_segs(size_t n) {
-    if (n <= h_segs_n_) return MSMZ_OK;
-    if (h_segs_) (void)hipHostFree(h_segs_);
-    h_segs_ = nullptr;
-    h_segs_n_ = 0;
-    MSMZ_HIP(hipHostMalloc(&h_segs_, n * sizeof(SegDesc)));
-    h_segs_n_ = n;
-    return MSMZ_OK;
-  }
-  uint32_t* h_res_ = nullptr;   // pinned, grow-only: the window results of every problem of an MSM (fetch_window_sums)
-  size_t h_res_words_ = 0;
-  int ensure_host_results(size_t words) {
-    if (words <= h_res_words_) return MSMZ_OK;
-    if (h_res_) (void)hipHostFree(h_res_);
-    h_res_ = nullptr;
-    h_res_words_ = 0;
-    MSMZ_HIP(hipHostMalloc(&h_res_, words * 4));
-    h_res_words_ = words;
-    return MSMZ_OK;
-  }
+  DevBuf bsum_, f2desc_, tilecnt_, tileoff_, final_, desc_, bfin_, packed_, bins_, digits_, counts_, off_, cursor_, refs_, rscan_, partials_, slots_, red_[4];
+  DevBuf segs_;         // run_segments: the descriptor table of a sub-batch ...
+  PinnedBuf h_segs_;    // ... and its pinned host copy (rewritten only after the sub-batch's final fetch)
   TestHooks<Cfg> hooks_{*this};
 };
 

@@ -1,0 +1,108 @@
+// What a context is to the C ABI (msmz.hip): the interface one engine (ResidentSets / Engine, resident.h / engine.h) and
+// the multi-device context (MultiEngine, multi.h) both implement, with the two small things its signatures need -- how a
+// device-side generator maps local to global indices, and the checks of an import source that need no device.
+#pragma once
+#include <cstdint>
+#include <vector>
+
+#include "../../include/msmz.h"
+
+namespace msmz {
+
+class ITestHooks;   // the stage-level test hooks of one engine (test_hooks.h)
+
+constexpr int MULTI_BLOCK_SHIFT = 16;
+
+// how device-side generators map a local index to the global (seeded) index
+struct GenMap {
+  uint32_t nshards = 1, shard = 0;
+  int blk_shift = MULTI_BLOCK_SHIFT;
+};
+
+// The checks of an import source (msmz_src, include/msmz.h) that need no device: flags, pointer alignment, width and
+// stride.  points: fe_bytes of the curve, 0 for a scalar source.  *width / *stride: the record's bytes and the bytes
+// from one record to the next, defaults resolved.  What the pointer points at is the engine's to ask (ResidentSets::vouch).
+static inline int src_check(const msmz_src* s, int point_fe_bytes, uint32_t* width, uint64_t* stride) {
+  if (!s || !s->ptr) return MSMZ_ERR_ARG;
+  if (s->flags & ~(uint32_t)(MSMZ_SRC_DEVICE | MSMZ_SRC_MONTGOMERY | MSMZ_SRC_DEFAULT_STREAM)) return MSMZ_ERR_ARG;
+  const bool dev = (s->flags & MSMZ_SRC_DEVICE) != 0;
+  if (!dev && (s->stream || (s->flags & MSMZ_SRC_DEFAULT_STREAM))) return MSMZ_ERR_ARG;
+  if (s->stream && (s->flags & MSMZ_SRC_DEFAULT_STREAM)) return MSMZ_ERR_ARG;
+  uint32_t w = s->width;
+  if (point_fe_bytes) {
+    if (w != 0 && w != 2u * (uint32_t)point_fe_bytes) return MSMZ_ERR_ARG;
+    w = 2u * (uint32_t)point_fe_bytes;
+  } else {
+    if (w < 4 || w > 32 || (w & 3u) || s->is_inf) return MSMZ_ERR_ARG;
+    if ((s->flags & MSMZ_SRC_MONTGOMERY) && w != 32) return MSMZ_ERR_ARG;
+  }
+  if (s->stride != 0 && (s->stride < w || (s->stride & 3u) || (s->stride >> 24))) return MSMZ_ERR_ARG;   // (n * stride cannot wrap)
+  if ((uintptr_t)s->ptr & 3u) return MSMZ_ERR_ARG;
+  *width = w;
+  *stride = s->stride ? s->stride : w;
+  return MSMZ_OK;
+}
+
+class IEngine {
+ public:
+  virtual ~IEngine() {}
+  // imports (msmz_import_*): `split` as for uploads, and then the source is packed host memory
+  virtual int import_scalars(const msmz_src& s, uint64_t n, uint64_t* h, const GenMap* split = nullptr) = 0;
+  virtual int import_scalars_into(uint64_t h, uint64_t first, const msmz_src& s, uint64_t n) = 0;
+  virtual int alloc_scalars(uint64_t, uint64_t*) { return MSMZ_ERR_UNSUPPORTED; }   // (_into's target: single-device contexts)
+  virtual int import_points(const msmz_src& s, uint64_t n, uint64_t* h, const GenMap* split = nullptr) = 0;
+  // packed host copy of the n records (and flag bytes, if the source has them) of a source in either memory space
+  virtual int gather_src(const msmz_src& s, int point_fe_bytes, uint64_t n, std::vector<uint8_t>* recs,
+                         std::vector<uint8_t>* flags) = 0;
+  // `split` (uploads and host-scalar MSMs): the engine is one shard of a multi-device context and `n` counts its LOCAL
+  // records; the host buffer is the caller's whole array, from which the engine copies its own blocks (ResidentSets::copy_h2d)
+  virtual int upload_points(const uint8_t* xy, const uint8_t* inf, uint64_t n, uint64_t* h, const GenMap* split = nullptr) = 0;
+  virtual int upload_scalars(const uint8_t* s, uint64_t n, uint64_t* h, const GenMap* split = nullptr) = 0;
+  virtual int random_points(uint64_t n, uint64_t seed, const GenMap& map, uint64_t* h) = 0;
+  virtual int random_scalars(uint64_t n, uint64_t seed, const GenMap& map, uint64_t* h) = 0;
+  virtual int download_points(uint64_t h, uint64_t first, uint64_t count, uint8_t* xy, uint8_t* inf) = 0;
+  virtual int download_scalars(uint64_t h, uint64_t first, uint64_t count, uint8_t* s) = 0;
+  virtual int free_handle(uint64_t h) = 0;
+  // `batch` MSMs over the same first n points (msmz_msm_batch): vector k = resident entries [k n, (k + 1) n), or host
+  // buffer entries [k host_stride, k host_stride + n) (host_stride 0 = n); out: batch results, out_inf: batch flags
+  virtual int msm_batch(uint64_t ph, const uint8_t* host_scalars, uint64_t sh, uint64_t n, uint32_t batch,
+                        const msmz_opts* o, uint8_t* out, int* out_inf, msmz_log* log, const GenMap* split = nullptr,
+                        uint64_t host_stride = 0) = 0;
+  // msmz_msm_segments: problem k = scalars [first_s, first_s + n) of `sh` times base points [first_p, first_p + n) of `ph`
+  virtual int msm_segments(uint64_t ph, uint64_t sh, const msmz_segment* segs, uint32_t n_segs, const msmz_opts* o,
+                           uint8_t* out, int* out_inf, msmz_log* log) = 0;
+  // precomputed point sets (msmz_precompute_points): the parameters a set of n points is built with, then the copies
+  // (sbits: the scalar bit bound of opts->reserved[1] as the planner normalizes it, 0 = none)
+  virtual int precompute_params(uint64_t n, const msmz_opts* o, uint32_t factor, int* c, int* glv, uint32_t* copies,
+                                int* K, int* sbits) const = 0;
+  virtual int precompute_points(uint64_t ph, uint64_t n, int c, int glv, uint32_t copies, int sbits, uint64_t* h) = 0;
+  virtual int precomputed_info(uint64_t h, int32_t* c, int32_t* glv, uint32_t* factor, uint32_t* K, uint64_t* records,
+                               int32_t* sbits) = 0;
+  // msmz_check_points over base points [first, first + count) of a plain point handle
+  virtual int check_points(uint64_t h, uint64_t first, uint64_t count, uint32_t what, msmz_check_result* out,
+                           uint8_t* verdicts) = 0;
+  // msmz_points_mul: a new plain point handle, record i = [s_i] P_i (+ Q_i)
+  virtual int points_mul(const msmz_mul& m, uint64_t n, uint64_t* h) = 0;
+  // msmz_scalars_combine / _dot / _powers: arithmetic mod q over resident scalar sets (scalar_kernels.h); `map` as for
+  // random_scalars
+  virtual int scalars_combine(const msmz_scalar_term& x, const msmz_scalar_term* y, uint64_t n, uint64_t first_out,
+                              uint64_t* out_handle) = 0;
+  virtual int scalars_dot(uint64_t xh, uint64_t first_x, uint64_t yh, uint64_t first_y, uint64_t n, uint8_t* out) = 0;
+  virtual int scalars_powers(const uint8_t* base, const uint8_t* ratio, uint64_t n, const GenMap& map, uint64_t* h) = 0;
+  // msmz_scalars_recurrence / _inverse: a scan of affine maps and Montgomery's trick (scan_kernels.h)
+  virtual int scalars_recurrence(const msmz_scalar_rec& r, uint64_t n, uint64_t first_out, uint64_t* out_handle,
+                                 uint8_t* last) = 0;
+  virtual int scalars_inverse(uint64_t h, uint64_t first, uint64_t n, uint64_t first_out, uint64_t* out_handle,
+                              uint64_t* n_zero) = 0;
+  // tests (include/msmz_test.h); the stage-level hooks are one engine's (a multi-device context: its first engine's)
+  virtual int test_set_glv_bits(int) { return MSMZ_ERR_UNSUPPORTED; }
+  virtual int test_retries() { return 0; }
+  virtual int test_set_limits(uint64_t, uint64_t) { return MSMZ_ERR_UNSUPPORTED; }
+  virtual void test_passes(uint64_t* range_passes, uint64_t* sub_batches) {
+    if (range_passes) *range_passes = 0;
+    if (sub_batches) *sub_batches = 0;
+  }
+  virtual ITestHooks* test_hooks() = 0;
+};
+
+}  // namespace msmz

@@ -22,104 +22,10 @@
 #include "../../include/msmz.h"
 #include "constants_gen.h"
 #include "fr.h"
+#include "iengine.h"
+#include "ranges.h"
 
 namespace msmz {
-
-class ITestHooks;   // the stage-level test hooks of one engine (test_hooks.h)
-
-constexpr int MULTI_BLOCK_SHIFT = 16;
-
-// how device-side generators map a local index to the global (seeded) index
-struct GenMap {
-  uint32_t nshards = 1, shard = 0;
-  int blk_shift = MULTI_BLOCK_SHIFT;
-};
-
-// The checks of an import source (msmz_src, include/msmz.h) that need no device: flags, pointer alignment, width and
-// stride.  points: fe_bytes of the curve, 0 for a scalar source.  *width / *stride: the record's bytes and the bytes
-// from one record to the next, defaults resolved.  What the pointer points at is the engine's to ask (Engine::vouch).
-static inline int src_check(const msmz_src* s, int point_fe_bytes, uint32_t* width, uint64_t* stride) {
-  if (!s || !s->ptr) return MSMZ_ERR_ARG;
-  if (s->flags & ~(uint32_t)(MSMZ_SRC_DEVICE | MSMZ_SRC_MONTGOMERY | MSMZ_SRC_DEFAULT_STREAM)) return MSMZ_ERR_ARG;
-  const bool dev = (s->flags & MSMZ_SRC_DEVICE) != 0;
-  if (!dev && (s->stream || (s->flags & MSMZ_SRC_DEFAULT_STREAM))) return MSMZ_ERR_ARG;
-  if (s->stream && (s->flags & MSMZ_SRC_DEFAULT_STREAM)) return MSMZ_ERR_ARG;
-  uint32_t w = s->width;
-  if (point_fe_bytes) {
-    if (w != 0 && w != 2u * (uint32_t)point_fe_bytes) return MSMZ_ERR_ARG;
-    w = 2u * (uint32_t)point_fe_bytes;
-  } else {
-    if (w < 4 || w > 32 || (w & 3u) || s->is_inf) return MSMZ_ERR_ARG;
-    if ((s->flags & MSMZ_SRC_MONTGOMERY) && w != 32) return MSMZ_ERR_ARG;
-  }
-  if (s->stride != 0 && (s->stride < w || (s->stride & 3u) || (s->stride >> 24))) return MSMZ_ERR_ARG;   // (n * stride cannot wrap)
-  if ((uintptr_t)s->ptr & 3u) return MSMZ_ERR_ARG;
-  *width = w;
-  *stride = s->stride ? s->stride : w;
-  return MSMZ_OK;
-}
-
-class IEngine {
- public:
-  virtual ~IEngine() {}
-  // imports (msmz_import_*): `split` as for uploads, and then the source is packed host memory
-  virtual int import_scalars(const msmz_src& s, uint64_t n, uint64_t* h, const GenMap* split = nullptr) = 0;
-  virtual int import_scalars_into(uint64_t h, uint64_t first, const msmz_src& s, uint64_t n) = 0;
-  virtual int alloc_scalars(uint64_t, uint64_t*) { return MSMZ_ERR_UNSUPPORTED; }   // (_into's target: single-device contexts)
-  virtual int import_points(const msmz_src& s, uint64_t n, uint64_t* h, const GenMap* split = nullptr) = 0;
-  // packed host copy of the n records (and flag bytes, if the source has them) of a source in either memory space
-  virtual int gather_src(const msmz_src& s, int point_fe_bytes, uint64_t n, std::vector<uint8_t>* recs,
-                         std::vector<uint8_t>* flags) = 0;
-  // `split` (uploads and host-scalar MSMs): the engine is one shard of a multi-device context and `n` counts its LOCAL
-  // records; the host buffer is the caller's whole array, from which the engine copies its own blocks (Engine::copy_h2d)
-  virtual int upload_points(const uint8_t* xy, const uint8_t* inf, uint64_t n, uint64_t* h, const GenMap* split = nullptr) = 0;
-  virtual int upload_scalars(const uint8_t* s, uint64_t n, uint64_t* h, const GenMap* split = nullptr) = 0;
-  virtual int random_points(uint64_t n, uint64_t seed, const GenMap& map, uint64_t* h) = 0;
-  virtual int random_scalars(uint64_t n, uint64_t seed, const GenMap& map, uint64_t* h) = 0;
-  virtual int download_points(uint64_t h, uint64_t first, uint64_t count, uint8_t* xy, uint8_t* inf) = 0;
-  virtual int download_scalars(uint64_t h, uint64_t first, uint64_t count, uint8_t* s) = 0;
-  virtual int free_handle(uint64_t h) = 0;
-  // `batch` MSMs over the same first n points (msmz_msm_batch): vector k = resident entries [k n, (k + 1) n), or host
-  // buffer entries [k host_stride, k host_stride + n) (host_stride 0 = n); out: batch results, out_inf: batch flags
-  virtual int msm_batch(uint64_t ph, const uint8_t* host_scalars, uint64_t sh, uint64_t n, uint32_t batch,
-                        const msmz_opts* o, uint8_t* out, int* out_inf, msmz_log* log, const GenMap* split = nullptr,
-                        uint64_t host_stride = 0) = 0;
-  // msmz_msm_segments: problem k = scalars [first_s, first_s + n) of `sh` times base points [first_p, first_p + n) of `ph`
-  virtual int msm_segments(uint64_t ph, uint64_t sh, const msmz_segment* segs, uint32_t n_segs, const msmz_opts* o,
-                           uint8_t* out, int* out_inf, msmz_log* log) = 0;
-  // precomputed point sets (msmz_precompute_points): the parameters a set of n points is built with, then the copies
-  // (sbits: the scalar bit bound of opts->reserved[1] as the planner normalizes it, 0 = none)
-  virtual int precompute_params(uint64_t n, const msmz_opts* o, uint32_t factor, int* c, int* glv, uint32_t* copies,
-                                int* K, int* sbits) const = 0;
-  virtual int precompute_points(uint64_t ph, uint64_t n, int c, int glv, uint32_t copies, int sbits, uint64_t* h) = 0;
-  virtual int precomputed_info(uint64_t h, int32_t* c, int32_t* glv, uint32_t* factor, uint32_t* K, uint64_t* records,
-                               int32_t* sbits) = 0;
-  // msmz_check_points over base points [first, first + count) of a plain point handle
-  virtual int check_points(uint64_t h, uint64_t first, uint64_t count, uint32_t what, msmz_check_result* out,
-                           uint8_t* verdicts) = 0;
-  // msmz_points_mul: a new plain point handle, record i = [s_i] P_i (+ Q_i)
-  virtual int points_mul(const msmz_mul& m, uint64_t n, uint64_t* h) = 0;
-  // msmz_scalars_combine / _dot / _powers: arithmetic mod q over resident scalar sets (scalar_kernels.h); `map` as for
-  // random_scalars
-  virtual int scalars_combine(const msmz_scalar_term& x, const msmz_scalar_term* y, uint64_t n, uint64_t first_out,
-                              uint64_t* out_handle) = 0;
-  virtual int scalars_dot(uint64_t xh, uint64_t first_x, uint64_t yh, uint64_t first_y, uint64_t n, uint8_t* out) = 0;
-  virtual int scalars_powers(const uint8_t* base, const uint8_t* ratio, uint64_t n, const GenMap& map, uint64_t* h) = 0;
-  // msmz_scalars_recurrence / _inverse: a scan of affine maps and Montgomery's trick (scan_kernels.h)
-  virtual int scalars_recurrence(const msmz_scalar_rec& r, uint64_t n, uint64_t first_out, uint64_t* out_handle,
-                                 uint8_t* last) = 0;
-  virtual int scalars_inverse(uint64_t h, uint64_t first, uint64_t n, uint64_t first_out, uint64_t* out_handle,
-                              uint64_t* n_zero) = 0;
-  // tests (include/msmz_test.h); the stage-level hooks are one engine's (a multi-device context: its first engine's)
-  virtual int test_set_glv_bits(int) { return MSMZ_ERR_UNSUPPORTED; }
-  virtual int test_retries() { return 0; }
-  virtual int test_set_limits(uint64_t, uint64_t) { return MSMZ_ERR_UNSUPPORTED; }
-  virtual void test_passes(uint64_t* range_passes, uint64_t* sub_batches) {
-    if (range_passes) *range_passes = 0;
-    if (sub_batches) *sub_batches = 0;
-  }
-  virtual ITestHooks* test_hooks() = 0;
-};
 
 // Problems per sub-batch of a batched MSM: at most `cap` entries (problems x entries_per_problem) per sub-batch, and the
 // `remaining` problems dealt into equally large sub-batches (64 problems with room for 40 -> 2 x 32, not 40 + 24).
@@ -222,27 +128,19 @@ class MultiEngine : public IEngine {
 
   int upload_points(const uint8_t* xy, const uint8_t* inf, uint64_t n, uint64_t* h, const GenMap* = nullptr) override {
     if (!xy || !h || n == 0) return MSMZ_ERR_ARG;
-    MHandle mh{0, n, std::vector<uint64_t>(G_, 0)};
-    int st = for_all([&](uint32_t g, IEngine* e) {
-      const uint64_t cnt = shard_count(n, g, G_);
-      if (cnt == 0) return (int)MSMZ_OK;
+    return make_set(0, n, h, [&](uint32_t g, IEngine* e, uint64_t cnt, uint64_t* sub) {
       // every device copies its own blocks straight out of the caller's buffer (no gathered host copy)
       const GenMap split{G_, g, MULTI_BLOCK_SHIFT};
-      return e->upload_points(xy, inf, cnt, &mh.sub[g], &split);
+      return e->upload_points(xy, inf, cnt, sub, &split);
     });
-    return finish_handle(st, mh, h);
   }
 
   int upload_scalars(const uint8_t* s, uint64_t n, uint64_t* h, const GenMap* = nullptr) override {
     if (!s || !h || n == 0) return MSMZ_ERR_ARG;
-    MHandle mh{1, n, std::vector<uint64_t>(G_, 0)};
-    int st = for_all([&](uint32_t g, IEngine* e) {
-      const uint64_t cnt = shard_count(n, g, G_);
-      if (cnt == 0) return (int)MSMZ_OK;
+    return make_set(1, n, h, [&](uint32_t g, IEngine* e, uint64_t cnt, uint64_t* sub) {
       const GenMap split{G_, g, MULTI_BLOCK_SHIFT};
-      return e->upload_scalars(s, cnt, &mh.sub[g], &split);
+      return e->upload_scalars(s, cnt, sub, &split);
     });
-    return finish_handle(st, mh, h);
   }
 
   // Correctness first: the source, wherever it is, becomes a packed host copy (made by the first engine), and every
@@ -263,41 +161,31 @@ class MultiEngine : public IEngine {
 
   int random_points(uint64_t n, uint64_t seed, const GenMap&, uint64_t* h) override {
     if (!h || n == 0) return MSMZ_ERR_ARG;
-    MHandle mh{0, n, std::vector<uint64_t>(G_, 0)};
-    int st = for_all([&](uint32_t g, IEngine* e) {
-      const uint64_t cnt = shard_count(n, g, G_);
-      if (cnt == 0) return (int)MSMZ_OK;
-      return e->random_points(cnt, seed, GenMap{G_, g, MULTI_BLOCK_SHIFT}, &mh.sub[g]);
+    return make_set(0, n, h, [&](uint32_t g, IEngine* e, uint64_t cnt, uint64_t* sub) {
+      return e->random_points(cnt, seed, GenMap{G_, g, MULTI_BLOCK_SHIFT}, sub);
     });
-    return finish_handle(st, mh, h);
   }
 
   int random_scalars(uint64_t n, uint64_t seed, const GenMap&, uint64_t* h) override {
     if (!h || n == 0) return MSMZ_ERR_ARG;
-    MHandle mh{1, n, std::vector<uint64_t>(G_, 0)};
-    int st = for_all([&](uint32_t g, IEngine* e) {
-      const uint64_t cnt = shard_count(n, g, G_);
-      if (cnt == 0) return (int)MSMZ_OK;
-      return e->random_scalars(cnt, seed, GenMap{G_, g, MULTI_BLOCK_SHIFT}, &mh.sub[g]);
+    return make_set(1, n, h, [&](uint32_t g, IEngine* e, uint64_t cnt, uint64_t* sub) {
+      return e->random_scalars(cnt, seed, GenMap{G_, g, MULTI_BLOCK_SHIFT}, sub);
     });
-    return finish_handle(st, mh, h);
   }
 
   int download_points(uint64_t hd, uint64_t first, uint64_t count, uint8_t* xy, uint8_t* inf) override {
-    auto it = handles_.find(hd);
-    if (it == handles_.end() || it->second.kind != 0 || !xy) return MSMZ_ERR_ARG;
-    if (first > it->second.n || count > it->second.n - first) return MSMZ_ERR_ARG;   // (first + count can wrap)
+    const MHandle* pts = range(hd, 0, first, count);
+    if (!pts || !xy) return MSMZ_ERR_ARG;
     const size_t rec = 2 * (size_t)fb_;
-    return for_range(it->second, first, count, [&](IEngine* e, uint64_t sub, uint64_t li, uint64_t gi, uint64_t len) {
+    return for_range(*pts, first, count, [&](IEngine* e, uint64_t sub, uint64_t li, uint64_t gi, uint64_t len) {
       return e->download_points(sub, li, len, xy + (gi - first) * rec, inf ? inf + (gi - first) : nullptr);
     });
   }
 
   int download_scalars(uint64_t hd, uint64_t first, uint64_t count, uint8_t* s) override {
-    auto it = handles_.find(hd);
-    if (it == handles_.end() || it->second.kind != 1 || !s) return MSMZ_ERR_ARG;
-    if (first > it->second.n || count > it->second.n - first) return MSMZ_ERR_ARG;
-    return for_range(it->second, first, count, [&](IEngine* e, uint64_t sub, uint64_t li, uint64_t gi, uint64_t len) {
+    const MHandle* sc = range(hd, 1, first, count);
+    if (!sc || !s) return MSMZ_ERR_ARG;
+    return for_range(*sc, first, count, [&](IEngine* e, uint64_t sub, uint64_t li, uint64_t gi, uint64_t len) {
       return e->download_scalars(sub, li, len, s + (gi - first) * 32);
     });
   }
@@ -305,8 +193,7 @@ class MultiEngine : public IEngine {
   int free_handle(uint64_t hd) override {
     auto it = handles_.find(hd);
     if (it == handles_.end()) return MSMZ_ERR_ARG;
-    for (uint32_t g = 0; g < G_; g++)
-      if (it->second.sub[g]) (void)workers_[g]->eng->free_handle(it->second.sub[g]);
+    free_shares(it->second);
     handles_.erase(it);
     return MSMZ_OK;
   }
@@ -318,15 +205,15 @@ class MultiEngine : public IEngine {
   int msm_batch(uint64_t ph, const uint8_t* host_scalars, uint64_t sh, uint64_t n, uint32_t batch, const msmz_opts* o,
                 uint8_t* out, int* out_inf, msmz_log* log, const GenMap* = nullptr, uint64_t = 0) override {
     if (!out || !out_inf || n == 0 || batch == 0) return MSMZ_ERR_ARG;
-    auto pit = handles_.find(ph);
-    if (pit == handles_.end() || pit->second.kind != 0 || pit->second.n < n) return MSMZ_ERR_ARG;
+    const MHandle* pp = range(ph, 0, 0, n);
+    if (!pp) return MSMZ_ERR_ARG;
     const MHandle* sc = nullptr;
     std::vector<uint8_t> gathered;
     if (!host_scalars) {
-      auto sit = handles_.find(sh);
-      if (sit == handles_.end() || sit->second.kind != 1 || sit->second.n / batch < n) return MSMZ_ERR_ARG;
+      const MHandle* all = get(sh, 1);
+      if (!all || all->n / batch < n) return MSMZ_ERR_ARG;
       if (batch == 1) {
-        sc = &sit->second;
+        sc = all;
       } else {
         gathered.resize((size_t)batch * n * 32);
         if (int st = download_scalars(sh, 0, (uint64_t)batch * n, gathered.data())) return st;
@@ -338,10 +225,8 @@ class MultiEngine : public IEngine {
     std::vector<std::vector<int>> pinf(G_, std::vector<int>(batch, 1));
     std::vector<int> used(G_, 0);
     std::vector<msmz_log> logs(G_);
-    const MHandle& pts = pit->second;
-    int st = for_all([&](uint32_t g, IEngine* e) {
-      const uint64_t cnt = shard_count(n, g, G_);
-      if (cnt == 0) return (int)MSMZ_OK;
+    const MHandle& pts = *pp;
+    int st = for_shares(n, [&](uint32_t g, IEngine* e, uint64_t cnt) {
       used[g] = 1;
       if (sc) return e->msm_batch(pts.sub[g], nullptr, sc->sub[g], cnt, 1, o, part[g].data(), pinf[g].data(), &logs[g]);
       const GenMap split{G_, g, MULTI_BLOCK_SHIFT};   // the device copies its own blocks of every vector
@@ -377,14 +262,11 @@ class MultiEngine : public IEngine {
     return workers_[0]->eng->precompute_params(n, o, factor, c, glv, copies, K, sbits);
   }
   int precompute_points(uint64_t ph, uint64_t n, int c, int glv, uint32_t copies, int sbits, uint64_t* h) override {
-    auto pit = handles_.find(ph);
-    if (!h || pit == handles_.end() || pit->second.kind != 0 || pit->second.factor != 0 || n == 0 || pit->second.n < n)
-      return MSMZ_ERR_ARG;
-    const MHandle& src = pit->second;
-    MHandle mh{0, n, std::vector<uint64_t>(G_, 0)};
-    int st = for_all([&](uint32_t g, IEngine* e) {
-      const uint64_t cnt = shard_count(n, g, G_);
-      if (cnt == 0) return (int)MSMZ_OK;
+    const MHandle* plain = get(ph, 0);
+    if (!h || !plain || plain->factor != 0 || n == 0 || plain->n < n) return MSMZ_ERR_ARG;
+    const MHandle& src = *plain;
+    MHandle mh = new_set(0, n);
+    int st = for_shares(n, [&](uint32_t g, IEngine* e, uint64_t cnt) {
       return e->precompute_points(src.sub[g], cnt, c, glv, copies, sbits, &mh.sub[g]);
     });
     mh.factor = copies;
@@ -393,10 +275,10 @@ class MultiEngine : public IEngine {
   }
   int precomputed_info(uint64_t hd, int32_t* c, int32_t* glv, uint32_t* factor, uint32_t* K, uint64_t* records,
                        int32_t* sbits) override {
-    auto it = handles_.find(hd);
-    if (it == handles_.end() || it->second.factor == 0) return MSMZ_ERR_ARG;
-    if (records) *records = (uint64_t)it->second.factor * it->second.n * (it->second.glv ? 2 : 1);
-    return workers_[0]->eng->precomputed_info(it->second.sub[0], c, glv, factor, K, nullptr, sbits);   // (shard 0 holds block 0)
+    const MHandle* pre = get(hd, 0);
+    if (!pre || pre->factor == 0) return MSMZ_ERR_ARG;
+    if (records) *records = (uint64_t)pre->factor * pre->n * (pre->glv ? 2 : 1);
+    return workers_[0]->eng->precomputed_info(pre->sub[0], c, glv, factor, K, nullptr, sbits);   // (shard 0 holds block 0)
   }
 
   // Every engine checks its own share: the set indices [first, first + count) that live on device g are one contiguous
@@ -405,11 +287,11 @@ class MultiEngine : public IEngine {
   int check_points(uint64_t hd, uint64_t first, uint64_t count, uint32_t what, msmz_check_result* out,
                    uint8_t* verdicts) override {
     if (!out || count == 0 || what == 0 || (what & ~(uint32_t)(MSMZ_CHECK_CURVE | MSMZ_CHECK_SUBGROUP))) return MSMZ_ERR_ARG;
-    auto it = handles_.find(hd);
-    if (it == handles_.end() || it->second.kind != 0) return MSMZ_ERR_ARG;
-    if (it->second.factor) return MSMZ_ERR_UNSUPPORTED;
-    if (first > it->second.n || count > it->second.n - first) return MSMZ_ERR_ARG;
-    const MHandle& mh = it->second;
+    const MHandle* pts = get(hd, 0);
+    if (!pts) return MSMZ_ERR_ARG;
+    if (pts->factor) return MSMZ_ERR_UNSUPPORTED;
+    if (!in_range(first, count, pts->n)) return MSMZ_ERR_ARG;
+    const MHandle& mh = *pts;
     std::vector<msmz_check_result> res(G_, msmz_check_result{0, 0, UINT64_MAX});
     std::vector<std::vector<uint8_t>> local(G_);
     std::vector<uint64_t> lo(G_), cnt(G_);
@@ -445,36 +327,21 @@ class MultiEngine : public IEngine {
   // on one device only when all three ranges start at a block-cycle boundary; only first = 0 is taken.
   int points_mul(const msmz_mul& m, uint64_t n, uint64_t* h) override {
     if (!h || n == 0) return MSMZ_ERR_ARG;
-    auto pit = handles_.find(m.points_handle);
-    if (pit == handles_.end() || pit->second.kind != 0) return MSMZ_ERR_ARG;
-    auto qit = handles_.end(), sit = handles_.end();
-    if (m.addend_handle) {
-      qit = handles_.find(m.addend_handle);
-      if (qit == handles_.end() || qit->second.kind != 0) return MSMZ_ERR_ARG;
-    }
-    if (m.scalars_handle) {
-      sit = handles_.find(m.scalars_handle);
-      if (sit == handles_.end() || sit->second.kind != 1) return MSMZ_ERR_ARG;
-    } else if (!m.scalar) {
-      return MSMZ_ERR_ARG;
-    }
-    if (pit->second.factor || (m.addend_handle && qit->second.factor)) return MSMZ_ERR_UNSUPPORTED;
-    auto beyond = [n](const MHandle& s, uint64_t first) { return first > s.n || n > s.n - first; };
-    if (beyond(pit->second, m.first_p) || (m.addend_handle && beyond(qit->second, m.first_q)) ||
-        (m.scalars_handle && beyond(sit->second, m.first_s)))
+    const MHandle* P = get(m.points_handle, 0);
+    const MHandle* Q = m.addend_handle ? get(m.addend_handle, 0) : nullptr;
+    const MHandle* S = m.scalars_handle ? get(m.scalars_handle, 1) : nullptr;
+    if (!P || (m.addend_handle && !Q) || (m.scalars_handle ? !S : !m.scalar)) return MSMZ_ERR_ARG;
+    if (P->factor || (Q && Q->factor)) return MSMZ_ERR_UNSUPPORTED;
+    if (!in_range(m.first_p, n, P->n) || (Q && !in_range(m.first_q, n, Q->n)) || (S && !in_range(m.first_s, n, S->n)))
       return MSMZ_ERR_ARG;
     if (m.first_p || (m.scalars_handle && m.first_s) || (m.addend_handle && m.first_q)) return MSMZ_ERR_UNSUPPORTED;
-    MHandle mh{0, n, std::vector<uint64_t>(G_, 0)};
-    int st = for_all([&](uint32_t g, IEngine* e) {
-      const uint64_t cnt = shard_count(n, g, G_);
-      if (cnt == 0) return (int)MSMZ_OK;
-      msmz_mul sub = m;
-      sub.points_handle = pit->second.sub[g];
-      sub.scalars_handle = m.scalars_handle ? sit->second.sub[g] : 0;
-      sub.addend_handle = m.addend_handle ? qit->second.sub[g] : 0;
-      return e->points_mul(sub, cnt, &mh.sub[g]);
+    return make_set(0, n, h, [&](uint32_t g, IEngine* e, uint64_t cnt, uint64_t* sub) {
+      msmz_mul mine = m;
+      mine.points_handle = P->sub[g];
+      mine.scalars_handle = S ? S->sub[g] : 0;
+      mine.addend_handle = Q ? Q->sub[g] : 0;
+      return e->points_mul(mine, cnt, sub);
     });
-    return finish_handle(st, mh, h);
   }
 
   // Every engine combines its own share.  Entry i of every operand and of the destination lives on one device only when
@@ -484,28 +351,21 @@ class MultiEngine : public IEngine {
     if (!out_handle || n == 0 || n >> 32) return MSMZ_ERR_ARG;
     const bool fresh = *out_handle == 0;
     if (fresh && first_out != 0) return MSMZ_ERR_ARG;
-    auto scalars = [&](uint64_t h, uint64_t first) -> const MHandle* {
-      auto it = handles_.find(h);
-      if (it == handles_.end() || it->second.kind != 1 || first > it->second.n || n > it->second.n - first) return nullptr;
-      return &it->second;
-    };
     const msmz_scalar_term* in[2] = {&x, y};
     const MHandle* v[2] = {nullptr, nullptr};
     const MHandle* c[2] = {nullptr, nullptr};
     bool shifted = first_out != 0;
     for (int k = 0; k < 2; k++) {
       if (!in[k]) continue;
-      if (!(v[k] = scalars(in[k]->handle, in[k]->first))) return MSMZ_ERR_ARG;
-      if (in[k]->coeff_handle && !(c[k] = scalars(in[k]->coeff_handle, in[k]->coeff_first))) return MSMZ_ERR_ARG;
+      if (!(v[k] = range(in[k]->handle, 1, in[k]->first, n))) return MSMZ_ERR_ARG;
+      if (in[k]->coeff_handle && !(c[k] = range(in[k]->coeff_handle, 1, in[k]->coeff_first, n))) return MSMZ_ERR_ARG;
       shifted = shifted || in[k]->first || (in[k]->coeff_handle && in[k]->coeff_first);
     }
     const MHandle* dst = nullptr;
-    if (!fresh && !(dst = scalars(*out_handle, first_out))) return MSMZ_ERR_ARG;
+    if (!fresh && !(dst = range(*out_handle, 1, first_out, n))) return MSMZ_ERR_ARG;
     if (shifted || (dst && dst->n != n)) return MSMZ_ERR_UNSUPPORTED;
-    MHandle mh{1, n, std::vector<uint64_t>(G_, 0)};
-    int st = for_all([&](uint32_t g, IEngine* e) {
-      const uint64_t cnt = shard_count(n, g, G_);
-      if (cnt == 0) return (int)MSMZ_OK;
+    MHandle mh = new_set(1, n);
+    int st = for_shares(n, [&](uint32_t g, IEngine* e, uint64_t cnt) {
       msmz_scalar_term sub[2];
       for (int k = 0; k < 2; k++) {
         if (!in[k]) continue;
@@ -523,23 +383,14 @@ class MultiEngine : public IEngine {
   // every engine sums over its own share (both ranges from 0: a prefix of every share); the host adds the sums mod q
   int scalars_dot(uint64_t xh, uint64_t first_x, uint64_t yh, uint64_t first_y, uint64_t n, uint8_t* out) override {
     if (!out || n == 0 || n >> 32) return MSMZ_ERR_ARG;
-    auto xit = handles_.find(xh);
-    if (xit == handles_.end() || xit->second.kind != 1) return MSMZ_ERR_ARG;
-    auto yit = handles_.end();
-    if (yh) {
-      yit = handles_.find(yh);
-      if (yit == handles_.end() || yit->second.kind != 1) return MSMZ_ERR_ARG;
-    } else if (first_y) {
-      return MSMZ_ERR_ARG;
-    }
-    auto beyond = [n](const MHandle& s, uint64_t first) { return first > s.n || n > s.n - first; };
-    if (beyond(xit->second, first_x) || (yh && beyond(yit->second, first_y))) return MSMZ_ERR_ARG;
+    if (!yh && first_y) return MSMZ_ERR_ARG;
+    const MHandle* X = range(xh, 1, first_x, n);
+    const MHandle* Y = yh ? range(yh, 1, first_y, n) : nullptr;
+    if (!X || (yh && !Y)) return MSMZ_ERR_ARG;
     if (first_x || first_y) return MSMZ_ERR_UNSUPPORTED;
     std::vector<uint32_t> part((size_t)G_ * 8, 0);
-    int st = for_all([&](uint32_t g, IEngine* e) {
-      const uint64_t cnt = shard_count(n, g, G_);
-      if (cnt == 0) return (int)MSMZ_OK;
-      return e->scalars_dot(xit->second.sub[g], 0, yh ? yit->second.sub[g] : 0, 0, cnt,
+    int st = for_shares(n, [&](uint32_t g, IEngine* e, uint64_t cnt) {
+      return e->scalars_dot(X->sub[g], 0, Y ? Y->sub[g] : 0, 0, cnt,
                             reinterpret_cast<uint8_t*>(part.data() + (size_t)g * 8));
     });
     if (st) return st;
@@ -552,13 +403,9 @@ class MultiEngine : public IEngine {
 
   int scalars_powers(const uint8_t* base, const uint8_t* ratio, uint64_t n, const GenMap&, uint64_t* h) override {
     if (!h || !ratio || n == 0 || n >> 32) return MSMZ_ERR_ARG;
-    MHandle mh{1, n, std::vector<uint64_t>(G_, 0)};
-    int st = for_all([&](uint32_t g, IEngine* e) {
-      const uint64_t cnt = shard_count(n, g, G_);
-      if (cnt == 0) return (int)MSMZ_OK;
-      return e->scalars_powers(base, ratio, cnt, GenMap{G_, g, MULTI_BLOCK_SHIFT}, &mh.sub[g]);
+    return make_set(1, n, h, [&](uint32_t g, IEngine* e, uint64_t cnt, uint64_t* sub) {
+      return e->scalars_powers(base, ratio, cnt, GenMap{G_, g, MULTI_BLOCK_SHIFT}, sub);
     });
-    return finish_handle(st, mh, h);
   }
 
   // A recurrence is sequential in the set index, and consecutive blocks of a set live on different engines: the
@@ -577,23 +424,15 @@ class MultiEngine : public IEngine {
     if (!out_handle || n == 0 || n >> 32) return MSMZ_ERR_ARG;
     const bool fresh = *out_handle == 0;
     if (fresh && first_out != 0) return MSMZ_ERR_ARG;
-    auto scalars = [&](uint64_t hh, uint64_t f) -> const MHandle* {
-      auto it = handles_.find(hh);
-      if (it == handles_.end() || it->second.kind != 1 || f > it->second.n || n > it->second.n - f) return nullptr;
-      return &it->second;
-    };
-    const MHandle* src = scalars(h, first);
+    const MHandle* src = range(h, 1, first, n);
     if (!src) return MSMZ_ERR_ARG;
     const MHandle* dst = nullptr;
-    if (!fresh && !(dst = scalars(*out_handle, first_out))) return MSMZ_ERR_ARG;
-    if (dst && *out_handle == h && first != first_out && (first > first_out ? first - first_out : first_out - first) < n)
-      return MSMZ_ERR_ARG;
+    if (!fresh && !(dst = range(*out_handle, 1, first_out, n))) return MSMZ_ERR_ARG;
+    if (dst && *out_handle == h && partial_overlap(first, first_out, n)) return MSMZ_ERR_ARG;
     if (first || first_out || (dst && dst->n != n)) return MSMZ_ERR_UNSUPPORTED;
-    MHandle mh{1, n, std::vector<uint64_t>(G_, 0)};
+    MHandle mh = new_set(1, n);
     std::vector<uint64_t> zeros(G_, 0);
-    int st = for_all([&](uint32_t g, IEngine* e) {
-      const uint64_t cnt = shard_count(n, g, G_);
-      if (cnt == 0) return (int)MSMZ_OK;
+    int st = for_shares(n, [&](uint32_t g, IEngine* e, uint64_t cnt) {
       if (dst) mh.sub[g] = dst->sub[g];
       return e->scalars_inverse(src->sub[g], 0, cnt, 0, &mh.sub[g], &zeros[g]);
     });
@@ -606,12 +445,7 @@ class MultiEngine : public IEngine {
   }
 
   int test_set_glv_bits(int bits) override {
-    int st = MSMZ_OK;
-    for (Worker* w : workers_) {
-      const int s = w->eng->test_set_glv_bits(bits);
-      if (s && !st) st = s;
-    }
-    return st;
+    return on_every([&](IEngine* e) { return e->test_set_glv_bits(bits); });
   }
   int test_retries() override {
     int r = 0;
@@ -619,12 +453,7 @@ class MultiEngine : public IEngine {
     return r;
   }
   int test_set_limits(uint64_t pass_entries, uint64_t batch_entries) override {
-    int st = MSMZ_OK;
-    for (Worker* w : workers_) {
-      const int s = w->eng->test_set_limits(pass_entries, batch_entries);
-      if (s && !st) st = s;
-    }
-    return st;
+    return on_every([&](IEngine* e) { return e->test_set_limits(pass_entries, batch_entries); });
   }
   void test_passes(uint64_t* range_passes, uint64_t* sub_batches) override {
     uint64_t rp = 0, sb = 0;
@@ -649,14 +478,10 @@ class MultiEngine : public IEngine {
     hs.width = (uint32_t)(recs.size() / n);
     hs.flags = s.flags & MSMZ_SRC_MONTGOMERY;
     hs.is_inf = flags.empty() ? nullptr : flags.data();
-    MHandle mh{point_fe_bytes ? 0 : 1, n, std::vector<uint64_t>(G_, 0)};
-    int st = for_all([&](uint32_t g, IEngine* e) {
-      const uint64_t cnt = shard_count(n, g, G_);
-      if (cnt == 0) return (int)MSMZ_OK;
+    return make_set(point_fe_bytes ? 0 : 1, n, h, [&](uint32_t g, IEngine* e, uint64_t cnt, uint64_t* sub) {
       const GenMap split{G_, g, MULTI_BLOCK_SHIFT};
-      return point_fe_bytes ? e->import_points(hs, cnt, &mh.sub[g], &split) : e->import_scalars(hs, cnt, &mh.sub[g], &split);
+      return point_fe_bytes ? e->import_points(hs, cnt, sub, &split) : e->import_scalars(hs, cnt, sub, &split);
     });
-    return finish_handle(st, mh, h);
   }
 
   struct MHandle {
@@ -716,6 +541,46 @@ class MultiEngine : public IEngine {
     }
   };
 
+  // a set of n records of `kind` that no engine holds a share of yet
+  MHandle new_set(int kind, uint64_t n) const { return MHandle{kind, n, std::vector<uint64_t>(G_, 0)}; }
+  // a new set whose shares the engines make: fn(g, engine, entries of its share, where its handle goes)
+  int make_set(int kind, uint64_t n, uint64_t* h, const std::function<int(uint32_t, IEngine*, uint64_t, uint64_t*)>& fn) {
+    MHandle mh = new_set(kind, n);
+    const int st = for_shares(n, [&](uint32_t g, IEngine* e, uint64_t cnt) { return fn(g, e, cnt, &mh.sub[g]); });
+    return finish_handle(st, mh, h);
+  }
+  // the set `h` if it is of `kind`, or null; `range`: and if [first, first + n) lies inside it
+  const MHandle* get(uint64_t h, int kind) const {
+    auto it = handles_.find(h);
+    return it == handles_.end() || it->second.kind != kind ? nullptr : &it->second;
+  }
+  const MHandle* range(uint64_t h, int kind, uint64_t first, uint64_t n) const {
+    const MHandle* mh = get(h, kind);
+    return mh && in_range(first, n, mh->n) ? mh : nullptr;
+  }
+  void free_shares(const MHandle& mh) {
+    for (uint32_t g = 0; g < G_; g++)
+      if (mh.sub[g]) (void)workers_[g]->eng->free_handle(mh.sub[g]);
+  }
+
+  // fn(engine) on every engine, one after another; the first non-zero status wins
+  int on_every(const std::function<int(IEngine*)>& fn) {
+    int st = MSMZ_OK;
+    for (Worker* w : workers_) {
+      const int s = fn(w->eng);
+      if (s && !st) st = s;
+    }
+    return st;
+  }
+
+  // for_all over the engines that hold a share of the first n entries of a set: fn(g, engine, entries of its share)
+  int for_shares(uint64_t n, const std::function<int(uint32_t, IEngine*, uint64_t)>& fn) {
+    return for_all([&](uint32_t g, IEngine* e) {
+      const uint64_t cnt = shard_count(n, g, G_);
+      return cnt ? fn(g, e, cnt) : (int)MSMZ_OK;
+    });
+  }
+
   // run fn(g, engine) on every device's thread concurrently; first non-zero status wins
   int for_all(const std::function<int(uint32_t, IEngine*)>& fn) {
     for (uint32_t g = 0; g < G_; g++) {
@@ -750,11 +615,7 @@ class MultiEngine : public IEngine {
   }
 
   int finish_handle(int st, MHandle& mh, uint64_t* h) {
-    if (st) {
-      for (uint32_t g = 0; g < G_; g++)
-        if (mh.sub[g]) (void)workers_[g]->eng->free_handle(mh.sub[g]);
-      return st;
-    }
+    if (st) return free_shares(mh), st;
     *h = next_handle_++;
     handles_[*h] = std::move(mh);
     return MSMZ_OK;

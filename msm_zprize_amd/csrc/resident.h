@@ -1,0 +1,766 @@
+// The resident sets of one engine: point and scalar sets kept on one GPU under handles, and every operation on them
+// that is not an MSM -- uploads, imports from host or device memory, generators, downloads, the point checks, per-point
+// multiplication and the arithmetic mod q over scalar sets.  One HIP stream; every entry point returns with the stream
+// drained.  Engine<Cfg> (engine.h) derives from this and adds the MSM pipeline, which runs on the same stream and reports
+// through the same error word.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <vector>
+
+#include "../../include/msmz.h"
+#include "kernels.h"
+#include "gen_kernels.h"
+#include "import_kernels.h"
+#include "check_kernels.h"
+#include "mul_kernels.h"
+#include "scalar_kernels.h"
+#include "iengine.h"
+#include "store.h"
+
+namespace msmz {
+
+template <class Cfg>
+class ResidentSets : public IEngine {
+ protected:
+  using F = typename Cfg::F;
+  using Fr = typename Cfg::Fr;
+  static constexpr int NW = F::NW;
+  static constexpr int RW = 2 * NW;      // affine record words
+  static constexpr int FE_BYTES = NW * 4;
+  static constexpr bool TE = Cfg::TE;
+  static constexpr int PW_WORDS = TE ? 4 * NW : PointFmt<F>::STRIDE;   // words between the records of a resident point set
+
+  explicit ResidentSets(int device) : device_(device) {}
+
+  // the device, the stream, and the pinned landing of the meta block (Engine::init goes on from here)
+  int init_sets() {
+    MSMZ_HIP(hipSetDevice(device_));
+    MSMZ_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    MSMZ_HIP(hipEventCreateWithFlags(&import_ev_, hipEventDisableTiming));
+    return h_meta_.ensure(sizeof(MsmMeta));
+  }
+
+ public:
+  ~ResidentSets() override {   // (the device buffers and handles free themselves after this, on this device)
+    (void)hipSetDevice(device_);
+    if (import_ev_) (void)hipEventDestroy(import_ev_);
+    if (stream_) (void)hipStreamDestroy(stream_);
+  }
+
+  // ------------------------------------------------------------------------------------------ data
+  int upload_points(const uint8_t* xy, const uint8_t* inf, uint64_t n, uint64_t* h, const GenMap* split = nullptr) override {
+    if (!xy || !h || !points_fit(n)) return MSMZ_ERR_ARG;
+    MSMZ_HIP(hipSetDevice(device_));
+    int st = stage_.ensure(n * RW * 4 + n);
+    if (st) return st;
+    if ((st = copy_h2d(stage_.p, xy, (size_t)RW * 4, n, split))) return st;
+    uint8_t* d_inf = nullptr;
+    if (inf) {
+      d_inf = stage_.as<uint8_t>() + n * RW * 4;
+      if ((st = copy_h2d(d_inf, inf, 1, n, split))) return st;
+    }
+    Handle hd;
+    if ((st = new_points(n, &hd))) return st;
+    st = checked([&](uint32_t* d_err) {   // a coordinate >= p
+      if constexpr (TE) {
+        hipLaunchKernelGGL((k_te_points_to_niels<F>), dim3((n + 255) / 256), dim3(256), 0, stream_, hd.mem.as<uint32_t>(),
+                           stage_.as<uint32_t>(), (uint32_t)n, d_err);
+      } else {
+        hipLaunchKernelGGL((k_points_to_mont<F>), dim3((n + 255) / 256), dim3(256), 0, stream_, hd.mem.as<uint32_t>(),
+                           stage_.as<uint32_t>(), d_inf, (uint32_t)n, hd.has_endo ? 1 : 0, d_err);
+      }
+    });
+    return st ? st : add_handle(std::move(hd), h);
+  }
+
+  int upload_scalars(const uint8_t* s, uint64_t n, uint64_t* h, const GenMap* split = nullptr) override {
+    if (!s || !h || n == 0) return MSMZ_ERR_ARG;
+    MSMZ_HIP(hipSetDevice(device_));
+    Handle hd;
+    int st;
+    if ((st = new_scalars(n, &hd)) || (st = copy_h2d(hd.mem.p, s, 32, n, split))) return st;
+    st = checked([&](uint32_t* d_err) {   // a scalar >= group order
+      hipLaunchKernelGGL((k_check_scalars<Fr>), dim3((n + 255) / 256), dim3(256), 0, stream_, d_err,
+                         hd.mem.as<const uint32_t>(), (uint32_t)n);
+    });
+    return st ? st : add_handle(std::move(hd), h);
+  }
+
+  // ------------------------------------------------------------------------------------------ imports
+  int import_scalars(const msmz_src& s, uint64_t n, uint64_t* h, const GenMap* split = nullptr) override {
+    if (!h || n == 0 || n >> 32) return MSMZ_ERR_ARG;
+    MSMZ_HIP(hipSetDevice(device_));
+    Handle hd;
+    ImportView v;
+    int st;   // (the source is checked before the allocation, which comes before any copy is queued)
+    if ((st = src_check(&s, 0, &v.width, &v.stride)) || (st = new_scalars(n, &hd)) || (st = import_view(s, 0, n, split, &v)))
+      return st;
+    if ((st = import_scalars_to(hd.mem.as<uint32_t>(), s, v, n))) return st;
+    return add_handle(std::move(hd), h);
+  }
+
+  // a new scalar set of n zeros: the target of import_scalars_into when a batch is assembled vector by vector
+  int alloc_scalars(uint64_t n, uint64_t* h) override {
+    if (!h || n == 0 || n >> 32) return MSMZ_ERR_ARG;
+    MSMZ_HIP(hipSetDevice(device_));
+    Handle hd;
+    if (int st = new_scalars(n, &hd)) return st;
+    MSMZ_HIP(hipMemsetAsync(hd.mem.p, 0, n * 32, stream_));
+    MSMZ_HIP(hipStreamSynchronize(stream_));
+    return add_handle(std::move(hd), h);
+  }
+
+  int import_scalars_into(uint64_t h, uint64_t first, const msmz_src& s, uint64_t n) override {
+    uint32_t* dst = handles_.range(h, 1, first, n, 8);
+    if (!dst || n == 0) return MSMZ_ERR_ARG;
+    MSMZ_HIP(hipSetDevice(device_));
+    ImportView v;
+    if (int st = import_view(s, 0, n, nullptr, &v)) return st;
+    return import_scalars_to(dst, s, v, n);
+  }
+
+  int import_points(const msmz_src& s, uint64_t n, uint64_t* h, const GenMap* split = nullptr) override {
+    if (!h || !points_fit(n)) return MSMZ_ERR_ARG;
+    MSMZ_HIP(hipSetDevice(device_));
+    ImportView v;
+    int st;
+    const int mont = (s.flags & MSMZ_SRC_MONTGOMERY) ? 1 : 0;
+    Handle hd;   // (the source is checked before the allocation, which comes before any copy is queued)
+    if ((st = src_check(&s, FE_BYTES, &v.width, &v.stride)) || (st = new_points(n, &hd)) ||
+        (st = import_view(s, FE_BYTES, n, split, &v)))
+      return st;
+    st = checked([&](uint32_t* d_err) {   // a coordinate (either form) >= p
+      if constexpr (TE) {
+        hipLaunchKernelGGL((k_te_import_points<F>), dim3((n + 255) / 256), dim3(256), 0, stream_, hd.mem.as<uint32_t>(),
+                           v.ptr, v.stride, (uint32_t)n, mont, d_err);
+      } else {
+        hipLaunchKernelGGL((k_import_points<F>), dim3((n + 255) / 256), dim3(256), 0, stream_, hd.mem.as<uint32_t>(), v.ptr,
+                           v.stride, v.is_inf, (uint32_t)n, hd.has_endo ? 1 : 0, mont, d_err);
+      }
+    });
+    return st ? st : add_handle(std::move(hd), h);
+  }
+
+  int gather_src(const msmz_src& s, int point_fe_bytes, uint64_t n, std::vector<uint8_t>* recs,
+                 std::vector<uint8_t>* flags) override {
+    uint32_t width = 0;
+    uint64_t stride = 0;
+    if (int st = src_check(&s, point_fe_bytes, &width, &stride)) return st;
+    if (n == 0 || n >> 32 || !recs || !flags) return MSMZ_ERR_ARG;
+    recs->resize((size_t)n * width);
+    flags->clear();
+    const uint8_t* p = (const uint8_t*)s.ptr;
+    if (!(s.flags & MSMZ_SRC_DEVICE)) {
+      for (uint64_t i = 0; i < n; i++) memcpy(recs->data() + i * width, p + i * stride, width);
+      if (s.is_inf) flags->assign(s.is_inf, s.is_inf + n);
+      return MSMZ_OK;
+    }
+    MSMZ_HIP(hipSetDevice(device_));
+    const void* dp = nullptr;
+    const void* di = nullptr;
+    int st;
+    if ((st = vouch(p, (n - 1) * stride + width, true, &dp))) return st;
+    if (s.is_inf && (st = vouch(s.is_inf, n, true, &di))) return st;
+    if (s.stream) MSMZ_HIP(hipStreamSynchronize((hipStream_t)s.stream));
+    if (s.flags & MSMZ_SRC_DEFAULT_STREAM) MSMZ_HIP(hipStreamSynchronize(nullptr));
+    MSMZ_HIP(hipMemcpy2D(recs->data(), width, dp, stride, width, n, hipMemcpyDefault));
+    if (di) {
+      flags->resize(n);
+      MSMZ_HIP(hipMemcpy(flags->data(), di, n, hipMemcpyDefault));
+    }
+    return MSMZ_OK;
+  }
+
+  int random_points(uint64_t n, uint64_t seed, const GenMap& map, uint64_t* h) override {
+    if (!h || !points_fit(n)) return MSMZ_ERR_ARG;
+    MSMZ_HIP(hipSetDevice(device_));
+    int st = ensure_gen_table();
+    if (st) return st;
+    Handle hd;
+    if ((st = new_points(n, &hd))) return st;
+    if constexpr (TE) {
+      hipLaunchKernelGGL((k_te_gen_points<F>), dim3((n + 127) / 128), dim3(128), 0, stream_, hd.mem.as<uint32_t>(),
+                         gen_table_.as<uint32_t>(), (uint32_t)n, seed, map);
+    } else {
+      hipLaunchKernelGGL((k_gen_points<F>), dim3((n + 127) / 128), dim3(128), 0, stream_, hd.mem.as<uint32_t>(),
+                         gen_table_.as<uint32_t>(), (uint32_t)n, seed, hd.has_endo ? 1 : 0, map);
+    }
+    MSMZ_HIP(hipGetLastError());
+    MSMZ_HIP(hipStreamSynchronize(stream_));
+    return add_handle(std::move(hd), h);
+  }
+
+  int random_scalars(uint64_t n, uint64_t seed, const GenMap& map, uint64_t* h) override {
+    if (!h || n == 0) return MSMZ_ERR_ARG;
+    MSMZ_HIP(hipSetDevice(device_));
+    Handle hd;
+    if (int st = new_scalars(n, &hd)) return st;
+    hipLaunchKernelGGL((k_gen_scalars<Fr>), dim3((n + 255) / 256), dim3(256), 0, stream_, hd.mem.as<uint32_t>(),
+                       (uint32_t)n, seed, map);
+    MSMZ_HIP(hipGetLastError());
+    MSMZ_HIP(hipStreamSynchronize(stream_));
+    return add_handle(std::move(hd), h);
+  }
+
+  int download_points(uint64_t hd, uint64_t first, uint64_t count, uint8_t* xy, uint8_t* inf) override {
+    const Handle* pts = handles_.get(hd, 0);
+    if (!pts || !xy) return MSMZ_ERR_ARG;
+    // the endomorphism images stay readable; a precomputed set: all its copies
+    const uint64_t have = pts->factor ? pts->copy_stride * pts->factor : pts->n * (pts->has_endo ? 2 : 1);
+    if (!in_range(first, count, have)) return MSMZ_ERR_ARG;
+    if (count == 0) return MSMZ_OK;
+    MSMZ_HIP(hipSetDevice(device_));
+    int st = stage_.ensure(count * RW * 4);
+    if (st) return st;
+    const uint32_t* recs = pts->mem.template as<const uint32_t>() + first * PW_WORDS;
+    if constexpr (TE) {
+      hipLaunchKernelGGL((k_te_points_from_niels<F>), dim3((count + 255) / 256), dim3(256), 0, stream_,
+                         stage_.as<uint32_t>(), recs, (uint32_t)count);
+    } else {
+      hipLaunchKernelGGL((k_points_from_mont<F>), dim3((count + 255) / 256), dim3(256), 0, stream_,
+                         stage_.as<uint32_t>(), recs, (uint32_t)count);
+    }
+    MSMZ_HIP(hipGetLastError());
+    MSMZ_HIP(hipMemcpyAsync(xy, stage_.p, count * RW * 4, hipMemcpyDeviceToHost, stream_));
+    MSMZ_HIP(hipStreamSynchronize(stream_));
+    if (inf) {
+      for (uint64_t i = 0; i < count; i++) {
+        bool z = !TE;   // twisted Edwards has no point at infinity: the identity is the affine point (0, 1)
+        for (int j = 0; j < RW * 4; j++) z = z && xy[i * RW * 4 + j] == 0;
+        inf[i] = z ? 1 : 0;
+      }
+    }
+    return MSMZ_OK;
+  }
+
+  int download_scalars(uint64_t hd, uint64_t first, uint64_t count, uint8_t* s) override {
+    const uint32_t* src = handles_.range(hd, 1, first, count, 8);
+    if (!src || !s) return MSMZ_ERR_ARG;
+    if (count == 0) return MSMZ_OK;
+    MSMZ_HIP(hipSetDevice(device_));
+    MSMZ_HIP(hipMemcpy(s, src, count * 32, hipMemcpyDeviceToHost));
+    return MSMZ_OK;
+  }
+
+  int free_handle(uint64_t hd) override {
+    if (!handles_.known(hd)) return MSMZ_ERR_ARG;
+    (void)hipSetDevice(device_);
+    handles_.erase(hd);
+    return MSMZ_OK;
+  }
+
+  // ------------------------------------------------------------------------------------------ validation
+  // msmz_check_points: the curve equation, then (if asked, and unless the curve has cofactor 1) [q]P = O, over base
+  // points [first, first + count) of a plain point handle.  A query: bad points are reported, not refused.  Two launches,
+  // then the result record and the verdict bytes come back behind ONE host wait, like the error word of an upload.
+  int check_points(uint64_t hd, uint64_t first, uint64_t count, uint32_t what, msmz_check_result* out,
+                   uint8_t* verdicts) override {
+    if (!out || count == 0 || what == 0 || (what & ~(uint32_t)(MSMZ_CHECK_CURVE | MSMZ_CHECK_SUBGROUP))) return MSMZ_ERR_ARG;
+    const Handle* pts = handles_.get(hd, 0);
+    if (!pts) return MSMZ_ERR_ARG;
+    if (pts->factor) return MSMZ_ERR_UNSUPPORTED;   // derived data: the source set is what a caller checks
+    const uint32_t* recs = handles_.range(hd, 0, first, count, PW_WORDS);   // (base points only)
+    if (!recs) return MSMZ_ERR_ARG;
+    MSMZ_HIP(hipSetDevice(device_));
+    if (int st = h_check_.ensure(sizeof(CheckResult) + (verdicts ? count : 0))) return st;
+    if (int st = check_.ensure(sizeof(CheckResult) + count)) return st;
+    CheckResult* d_res = check_.as<CheckResult>();
+    uint8_t* d_verdicts = check_.as<uint8_t>() + sizeof(CheckResult);
+    const dim3 grid((uint32_t)((count + 255) / 256)), block(256);
+    MSMZ_HIP(hipMemsetAsync(d_res, 0, 8, stream_));
+    MSMZ_HIP(hipMemsetAsync(&d_res->first_bad, 0xff, 4, stream_));
+    const bool chain = (what & MSMZ_CHECK_SUBGROUP) && !Fr::PRIME_ORDER;   // cofactor 1: the curve is the subgroup
+    if constexpr (TE) {
+      hipLaunchKernelGGL((k_te_check_curve<F>), grid, block, 0, stream_, d_verdicts, d_res, recs, (uint32_t)count, (uint32_t)first);
+      if (chain)
+        hipLaunchKernelGGL((k_te_check_subgroup<F, Fr>), grid, block, 0, stream_, d_verdicts, d_res, recs, (uint32_t)count, (uint32_t)first);
+    } else {
+      hipLaunchKernelGGL((k_check_curve<F>), grid, block, 0, stream_, d_verdicts, d_res, recs, (uint32_t)count, (uint32_t)first);
+      if (chain)
+        hipLaunchKernelGGL((k_check_subgroup<F, Fr>), grid, block, 0, stream_, d_verdicts, d_res, recs, (uint32_t)count, (uint32_t)first);
+    }
+    MSMZ_HIP(hipGetLastError());
+    // both land in pinned memory (a copy into the caller's pageable buffer would block the host a second time)
+    MSMZ_HIP(hipMemcpyAsync(h_check_.p, d_res, sizeof(CheckResult) + (verdicts ? count : 0), hipMemcpyDeviceToHost, stream_));
+    MSMZ_HIP(hipStreamSynchronize(stream_));
+    const CheckResult* res = h_check_.as<const CheckResult>();
+    if (verdicts) memcpy(verdicts, h_check_.as<const uint8_t>() + sizeof(CheckResult), count);
+    out->off_curve = res->off_curve;
+    out->off_subgroup = res->off_subgroup;
+    out->first_bad = res->first_bad == 0xffffffffu ? UINT64_MAX : res->first_bad;
+    return MSMZ_OK;
+  }
+
+  // ------------------------------------------------------------------------------------------ per-point multiplication
+  // msmz_points_mul: a new plain point handle, record i = [s_i] P_i (+ Q_i).  One launch; the error word (a resident
+  // scalar >= q) comes back behind the ONE host wait, like that of an upload.
+  int points_mul(const msmz_mul& m, uint64_t n, uint64_t* h) override {
+    if (!h || !points_fit(n)) return MSMZ_ERR_ARG;
+    const Handle* pts = handles_.get(m.points_handle, 0);
+    const Handle* add = m.addend_handle ? handles_.get(m.addend_handle, 0) : nullptr;
+    if (!pts || (m.addend_handle && !add)) return MSMZ_ERR_ARG;
+    if (m.scalars_handle ? !handles_.get(m.scalars_handle, 1) : !m.scalar) return MSMZ_ERR_ARG;
+    if (pts->factor || (add && add->factor)) return MSMZ_ERR_UNSUPPORTED;   // derived data
+    const uint32_t* P = handles_.range(m.points_handle, 0, m.first_p, n, PW_WORDS);
+    const uint32_t* Q = add ? handles_.range(m.addend_handle, 0, m.first_q, n, PW_WORDS) : nullptr;
+    const uint32_t* S = m.scalars_handle ? handles_.range(m.scalars_handle, 1, m.first_s, n, 8) : nullptr;
+    if (!P || (add && !Q) || (m.scalars_handle && !S)) return MSMZ_ERR_ARG;
+    MulScalar bc{};
+    if (!S)
+      if (int st = read_fr(m.scalar, bc.w, false)) return st;
+    MSMZ_HIP(hipSetDevice(device_));
+    Handle hd;
+    if (int st = new_points(n, &hd)) return st;
+    const dim3 grid((uint32_t)((n + 255) / 256)), block(256);   // whole blocks: every wave reaches the inversion entire
+    const int st = checked([&](uint32_t* d_err) {   // a resident scalar >= group order
+      if constexpr (TE) {
+        hipLaunchKernelGGL((k_te_points_mul<F, Fr>), grid, block, 0, stream_, hd.mem.as<uint32_t>(), P, S, bc, Q, (uint32_t)n,
+                           d_err);
+      } else {
+        hipLaunchKernelGGL((k_points_mul<F, Fr>), grid, block, 0, stream_, hd.mem.as<uint32_t>(), P, S, bc, Q, (uint32_t)n,
+                           hd.has_endo ? 1 : 0, d_err);
+      }
+    });
+    return st ? st : add_handle(std::move(hd), h);
+  }
+
+  // ------------------------------------------------------------------------------------------ scalar-set arithmetic
+  // msmz_scalars_combine: out_i = x.c_i x.v_i (+ y.c_i y.v_i) into a new scalar handle or over a range of an existing
+  // one.  One launch; the error word (a resident record >= q) comes back behind the ONE host wait.
+  int scalars_combine(const msmz_scalar_term& x, const msmz_scalar_term* y, uint64_t n, uint64_t first_out,
+                      uint64_t* out_handle) override {
+    if (!out_handle || n == 0 || n >> 32) return MSMZ_ERR_ARG;
+    ScalarTerm t[2] = {};
+    const msmz_scalar_term* in[2] = {&x, y};
+    std::vector<Source> srcs;
+    for (int k = 0; k < 2; k++) {
+      if (!in[k]) continue;
+      srcs.push_back({in[k]->handle, in[k]->first, &t[k].v});
+      if (in[k]->coeff_handle) srcs.push_back({in[k]->coeff_handle, in[k]->coeff_first, &t[k].c});
+    }
+    uint32_t* out = nullptr;
+    if (int st = resolve(srcs, n, first_out, *out_handle, &out)) return st;
+    for (int k = 0; k < 2; k++) {
+      if (!in[k] || in[k]->coeff_handle) continue;
+      if (!in[k]->coeff) t[k].unit = 1;
+      else if (int st = read_fr(in[k]->coeff, t[k].k.w, true)) return st;
+    }
+    MSMZ_HIP(hipSetDevice(device_));
+    Handle hd;
+    if (int st = fresh_out(n, &hd, &out)) return st;
+    const int st = checked([&](uint32_t* d_err) {   // a resident record >= group order
+      hipLaunchKernelGGL((k_scalars_combine<Fr>), dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream_, out, t[0], t[1],
+                         (uint32_t)n, d_err);
+    });
+    return st || !hd.mem.p ? st : add_handle(std::move(hd), out_handle);
+  }
+
+  // msmz_scalars_dot: one partial sum per tile, one workgroup folds them; the result and the error word share a
+  // 64-byte record in front of the partial sums and come back in ONE copy behind ONE host wait.
+  int scalars_dot(uint64_t xh, uint64_t first_x, uint64_t yh, uint64_t first_y, uint64_t n, uint8_t* out) override {
+    if (!out || n == 0 || n >> 32) return MSMZ_ERR_ARG;
+    if (!handles_.get(xh, 1) || (yh ? !handles_.get(yh, 1) : first_y != 0)) return MSMZ_ERR_ARG;
+    const uint32_t* X = handles_.range(xh, 1, first_x, n, 8);
+    const uint32_t* Y = yh ? handles_.range(yh, 1, first_y, n, 8) : nullptr;
+    if (!X || (yh && !Y)) return MSMZ_ERR_ARG;
+    MSMZ_HIP(hipSetDevice(device_));
+    const uint32_t tiles = (uint32_t)((n + SDOT_TILE - 1) / SDOT_TILE);
+    // words 0..7: the result, word 8: the error word, from word 16: the partial sums
+    const int st = recorded(sdot_, 64 + (size_t)tiles * 32, [&](uint32_t* d_res) {
+      hipLaunchKernelGGL((k_scalars_dot<Fr>), dim3(tiles), dim3(SDOT_THREADS), 0, stream_, d_res + 16, X, Y, (uint32_t)n, d_res + 8);
+      hipLaunchKernelGGL((k_scalars_dot_fold<Fr>), dim3(1), dim3(SDOT_THREADS), 0, stream_, d_res, d_res + 16, tiles, Y ? 1 : 0);
+    });
+    if (st) return st;
+    memcpy(out, h_res_.p, 32);
+    return MSMZ_OK;
+  }
+
+  // msmz_scalars_powers: a new scalar handle, local entry i = base ratio^(set index of i).  The host builds the table of
+  // ratio^(2^k) with fr.h; it travels as a kernel argument.
+  int scalars_powers(const uint8_t* base, const uint8_t* ratio, uint64_t n, const GenMap& map, uint64_t* h) override {
+    if (!h || !ratio || n == 0 || n >> 32) return MSMZ_ERR_ARG;
+    FrConst b{};
+    uint32_t r[8];
+    b.w[0] = 1;
+    int st;
+    if ((base && (st = read_fr(base, b.w, false))) || (st = read_fr(ratio, r, false))) return st;
+    FrPowTable table;
+    fr_pow_table<Fr>(table, r);
+    MSMZ_HIP(hipSetDevice(device_));
+    Handle hd;
+    if ((st = new_scalars(n, &hd))) return st;
+    const uint64_t threads = (n + SPOW_RUN - 1) / SPOW_RUN;
+    hipLaunchKernelGGL((k_scalars_powers<Fr>), dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, stream_,
+                       hd.mem.as<uint32_t>(), b, table, (uint32_t)n, map);
+    MSMZ_HIP(hipGetLastError());
+    MSMZ_HIP(hipStreamSynchronize(stream_));
+    return add_handle(std::move(hd), h);
+  }
+
+  // msmz_scalars_recurrence: three launches (tile aggregates, ONE workgroup of carries, apply); the final value and the
+  // error word share a 64-byte record in front of the scratch and come back in ONE copy behind ONE host wait.
+  int scalars_recurrence(const msmz_scalar_rec& r, uint64_t n, uint64_t first_out, uint64_t* out_handle,
+                         uint8_t* last) override {
+    if (!out_handle || n == 0 || n >> 32 || (r.flags & ~(uint32_t)(MSMZ_REC_REVERSE | MSMZ_REC_EXCLUSIVE)))
+      return MSMZ_ERR_ARG;
+    if (!r.a_handle && !r.a && !r.b_handle) return MSMZ_ERR_ARG;   // y_i = y_(i-1): nothing to do
+    const uint32_t *A = nullptr, *B = nullptr;
+    std::vector<Source> srcs;
+    if (r.a_handle) srcs.push_back({r.a_handle, r.a_first, &A});
+    if (r.b_handle) srcs.push_back({r.b_handle, r.b_first, &B});
+    uint32_t* out = nullptr;
+    if (int st = resolve(srcs, n, first_out, *out_handle, &out)) return st;
+    FrConst k{}, init{};
+    if (!r.a_handle && r.a)
+      if (int st = read_fr(r.a, k.w, true)) return st;
+    if (r.init) {
+      if (int st = read_fr(r.init, init.w, false)) return st;
+    } else if (!B) {
+      init.w[0] = 1;
+    }
+    MSMZ_HIP(hipSetDevice(device_));
+    Handle hd;
+    if (int st = fresh_out(n, &hd, &out)) return st;
+    const uint32_t tiles = (uint32_t)((n + SREC_TILE - 1) / SREC_TILE);
+    // words 0..7: the final value, word 8: the error word; then the aggregates' A, their B, and tiles + 1 incoming values
+    const int st = recorded(sscan_, 64 + ((size_t)tiles * 3 + 1) * 32, [&](uint32_t* d_res) {
+      uint32_t* aggA = d_res + 16;
+      uint32_t* aggB = aggA + (size_t)tiles * 8;
+      uint32_t* incoming = aggB + (size_t)tiles * 8;
+      const uint32_t nn = (uint32_t)n, flags = r.flags;
+      const dim3 grid(tiles), block(SREC_THREADS);
+#define MSMZ_REC_LAUNCH(AM, HB)                                                                                          \
+  do {                                                                                                                   \
+    hipLaunchKernelGGL((k_scalars_rec_tile<Fr, AM, HB>), grid, block, 0, stream_, aggA, aggB, A, B, k, nn, flags, d_res + 8); \
+    hipLaunchKernelGGL((k_scalars_rec_carry<Fr, AM != SREC_A_NONE, HB>), dim3(1), block, 0, stream_, incoming, d_res,    \
+                       (const uint32_t*)aggA, (const uint32_t*)aggB, init, tiles);                                       \
+    hipLaunchKernelGGL((k_scalars_rec_apply<Fr, AM, HB>), grid, block, 0, stream_, out, A, B, k, (const uint32_t*)incoming, \
+                       nn, flags);                                                                                       \
+  } while (0)
+      if (A && B) MSMZ_REC_LAUNCH(SREC_A_RESIDENT, true);
+      else if (A) MSMZ_REC_LAUNCH(SREC_A_RESIDENT, false);
+      else if (r.a && B) MSMZ_REC_LAUNCH(SREC_A_BROADCAST, true);
+      else if (r.a) MSMZ_REC_LAUNCH(SREC_A_BROADCAST, false);
+      else MSMZ_REC_LAUNCH(SREC_A_NONE, true);
+#undef MSMZ_REC_LAUNCH
+    });
+    if (st) return st;
+    if (last) memcpy(last, h_res_.p, 32);
+    return hd.mem.p ? add_handle(std::move(hd), out_handle) : (int)MSMZ_OK;
+  }
+
+  // msmz_scalars_inverse: one launch; the error word and the zero count share the record
+  int scalars_inverse(uint64_t h, uint64_t first, uint64_t n, uint64_t first_out, uint64_t* out_handle,
+                      uint64_t* n_zero) override {
+    if (!out_handle || n == 0 || n >> 32) return MSMZ_ERR_ARG;
+    const uint32_t* X = nullptr;
+    uint32_t* out = nullptr;
+    if (int st = resolve({{h, first, &X}}, n, first_out, *out_handle, &out)) return st;
+    MSMZ_HIP(hipSetDevice(device_));
+    Handle hd;
+    if (int st = fresh_out(n, &hd, &out)) return st;
+    const uint64_t per_block = (uint64_t)SINV_THREADS * SINV_E;
+    const int st = recorded(sscan_, 64, [&](uint32_t* d_res) {   // word 8: the error word, word 9: the zeros
+      hipLaunchKernelGGL((k_scalars_inverse<Fr>), dim3((uint32_t)((n + per_block - 1) / per_block)), dim3(SINV_THREADS), 0,
+                         stream_, out, X, (uint32_t)n, d_res);
+    });
+    if (st) return st;
+    if (n_zero) *n_zero = h_res_.template as<const uint32_t>()[9];
+    return hd.mem.p ? add_handle(std::move(hd), out_handle) : (int)MSMZ_OK;
+  }
+
+ protected:
+  // Host -> device copy of this engine's `n` local records of `rec` bytes.  split == nullptr: one contiguous copy.
+  // Otherwise the engine is shard `split->shard` of `split->nshards` inside a multi-device context (multi.h): its local
+  // block b is global block b * nshards + shard of the caller's buffer, so every block is copied straight from where
+  // the caller has it -- no gathered host copy in between.
+  int copy_h2d(void* dst, const uint8_t* src, size_t rec, uint64_t n, const GenMap* split) {
+    if (!split || split->nshards <= 1) {
+      MSMZ_HIP(hipMemcpyAsync(dst, src, n * rec, hipMemcpyHostToDevice, stream_));
+      return MSMZ_OK;
+    }
+    const uint64_t blk = 1ull << split->blk_shift;
+    for (uint64_t li = 0; li < n; li += blk) {
+      const uint64_t len = n - li < blk ? n - li : blk;
+      const uint64_t gi = ((li >> split->blk_shift) * split->nshards + split->shard) << split->blk_shift;
+      MSMZ_HIP(hipMemcpyAsync((uint8_t*)dst + li * rec, src + gi * rec, len * rec, hipMemcpyHostToDevice, stream_));
+    }
+    return MSMZ_OK;
+  }
+
+  // *word = the meta error word as the launches queued so far leave it (one host round trip).  What a bit means is the
+  // caller's to say: it differs between the kernels that raise them.
+  int fetch_error(uint32_t* word) {
+    MSMZ_HIP(hipGetLastError());
+    MSMZ_HIP(hipMemcpyAsync(&h_meta_->error, &meta_.as<MsmMeta>()->error, 4, hipMemcpyDeviceToHost, stream_));
+    MSMZ_HIP(hipStreamSynchronize(stream_));
+    *word = h_meta_->error;
+    return MSMZ_OK;
+  }
+
+  // record indices of a point set (incl. the endomorphism images) fit 30 bits
+  static bool points_fit(uint64_t n) { return n != 0 && n < (1ull << (Cfg::HAS_ENDO ? 29 : 30)); }
+
+  // a new handle and its device memory (owned by it: an error before add_handle frees it)
+  int new_handle(Handle* hd, int kind, uint64_t n, bool endo, size_t bytes) {
+    *hd = Handle{kind, n, endo};
+    MSMZ_HIP(hipMalloc(&hd->mem.p, bytes));
+    hd->mem.bytes = bytes;
+    return MSMZ_OK;
+  }
+  int new_points(uint64_t n, Handle* hd) {
+    if (!points_fit(n)) return MSMZ_ERR_ARG;
+    return new_handle(hd, 0, n, Cfg::HAS_ENDO, (size_t)n * PW_WORDS * 4 * (Cfg::HAS_ENDO ? 2 : 1));
+  }
+  int new_scalars(uint64_t n, Handle* hd) { return new_handle(hd, 1, n, false, n * 32); }
+  // the memory of a fresh destination (resolve left *out null): hd owns it until add_handle
+  int fresh_out(uint64_t n, Handle* hd, uint32_t** out) {
+    if (*out) return MSMZ_OK;
+    if (int st = new_scalars(n, hd)) return st;
+    *out = hd->mem.template as<uint32_t>();
+    return MSMZ_OK;
+  }
+  int add_handle(Handle&& hd, uint64_t* h) {
+    *h = handles_.add(std::move(hd));
+    return MSMZ_OK;
+  }
+
+ private:
+  // zeroes the error word, runs launch(its device address), fetches it: MSMZ_ERR_RANGE if a kernel raised a bit
+  template <class Launch>
+  int checked(Launch launch) {
+    uint32_t* d_err = &meta_.as<MsmMeta>()->error;
+    MSMZ_HIP(hipMemsetAsync(d_err, 0, 4, stream_));
+    launch(d_err);
+    uint32_t err = 0;
+    if (int st = fetch_error(&err)) return st;
+    return err ? MSMZ_ERR_RANGE : MSMZ_OK;
+  }
+
+  // The 64-byte result record of dot, recurrence and inverse at the head of `buf` (`bytes` with its scratch): zeroed in
+  // stream order, written by launch(its device address), copied to h_res_ (pinned: Engine::init sized it for far more)
+  // behind ONE wait.  Word 8 is the error word: MSMZ_ERR_RANGE if a resident record was >= the group order.
+  template <class Launch>
+  int recorded(DevBuf& buf, size_t bytes, Launch launch) {
+    if (int st = buf.ensure(bytes)) return st;
+    MSMZ_HIP(hipMemsetAsync(buf.p, 0, 64, stream_));
+    launch(buf.as<uint32_t>());
+    MSMZ_HIP(hipGetLastError());
+    MSMZ_HIP(hipMemcpyAsync(h_res_.p, buf.p, 64, hipMemcpyDeviceToHost, stream_));
+    MSMZ_HIP(hipStreamSynchronize(stream_));
+    return h_res_.template as<const uint32_t>()[8] ? MSMZ_ERR_RANGE : MSMZ_OK;
+  }
+
+  // a broadcast scalar of the caller's (32 bytes, canonical): out = its words, or its Montgomery form; >= q is refused
+  static int read_fr(const uint8_t* src, uint32_t out[8], bool to_mont) {
+    uint32_t c[8];
+    memcpy(c, src, 32);
+    if (words_geq<8>(c, Fr::Q)) return MSMZ_ERR_RANGE;
+    if (to_mont) fr_to_mont<Fr>(out, c);
+    else memcpy(out, c, 32);
+    return MSMZ_OK;
+  }
+
+  // The operands of combine, recurrence and inverse.  Every source is a range of n records of a scalar set that does
+  // not overlap the destination in part (entry i is read, then written: equal starts are in place).  The destination:
+  // records [first_out, first_out + n) of `out_handle`, or, for out_handle == 0, a fresh set -- first_out must be 0 and
+  // *out stays null, for the caller to allocate once every check has passed.
+  struct Source {
+    uint64_t handle, first;
+    const uint32_t** p;
+  };
+  int resolve(const std::vector<Source>& srcs, uint64_t n, uint64_t first_out, uint64_t out_handle, uint32_t** out) {
+    if (out_handle == 0 && first_out != 0) return MSMZ_ERR_ARG;
+    for (const Source& s : srcs) {
+      if (s.handle == out_handle && partial_overlap(s.first, first_out, n)) return MSMZ_ERR_ARG;
+      if (!(*s.p = handles_.range(s.handle, 1, s.first, n, 8))) return MSMZ_ERR_ARG;
+    }
+    if (out_handle && !(*out = handles_.range(out_handle, 1, first_out, n, 8))) return MSMZ_ERR_ARG;
+    return MSMZ_OK;
+  }
+
+  // where the import kernel reads: the caller's device memory, or the packed staging copy of a host source
+  struct ImportView {
+    const uint8_t* ptr = nullptr;
+    uint64_t stride = 0;
+    uint32_t width = 0;
+    const uint8_t* is_inf = nullptr;
+  };
+
+  // May a kernel of this device read [p, p + bytes)?  Yes only if the HIP runtime knows p as memory of this device, or
+  // as pinned / registered host memory (then *dev is its device-side address), AND the whole range lies inside the one
+  // allocation p belongs to (hipMemGetAddressRange): a range that starts in one allocation and ends in another is
+  // refused, whatever lies between.  A pointer the runtime does not know (pageable host memory, a stale or made-up
+  // address), managed memory and another device's memory are refused: nothing is launched on them.  Pinned host memory
+  // whose allocation the runtime cannot report is accepted only if the first and the last byte are both pinned and
+  // their device-side addresses are `bytes - 1` apart.  any_device: the caller only copies (gather_src).
+  int vouch(const void* p, uint64_t bytes, bool any_device, const void** dev) const {
+    hipPointerAttribute_t a;
+    memset(&a, 0, sizeof(a));
+    if (bytes == 0 || hipPointerGetAttributes(&a, p) != hipSuccess) {
+      (void)hipGetLastError();   // (an unknown pointer is an answer, not a sticky error)
+      return MSMZ_ERR_ARG;
+    }
+    if ((a.type != hipMemoryTypeDevice && a.type != hipMemoryTypeHost) || a.isManaged) return MSMZ_ERR_ARG;
+    if (a.type == hipMemoryTypeDevice && !any_device && a.device != device_) return MSMZ_ERR_ARG;
+    *dev = a.type == hipMemoryTypeHost ? a.devicePointer : p;
+    if (!*dev) return MSMZ_ERR_ARG;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)*dev) == hipSuccess) {
+      const uintptr_t lo = (uintptr_t)base, at = (uintptr_t)*dev;
+      return at >= lo && bytes <= size && at - lo <= size - bytes ? MSMZ_OK : MSMZ_ERR_ARG;
+    }
+    (void)hipGetLastError();
+    if (a.type != hipMemoryTypeHost) return MSMZ_ERR_ARG;
+    hipPointerAttribute_t z;
+    memset(&z, 0, sizeof(z));
+    if (hipPointerGetAttributes(&z, (const uint8_t*)p + (bytes - 1)) != hipSuccess) {
+      (void)hipGetLastError();
+      return MSMZ_ERR_ARG;
+    }
+    if (z.type != hipMemoryTypeHost || z.isManaged || !z.devicePointer) return MSMZ_ERR_ARG;
+    return (uintptr_t)z.devicePointer - (uintptr_t)a.devicePointer == bytes - 1 ? MSMZ_OK : MSMZ_ERR_ARG;
+  }
+
+  // Checks the source and makes it readable for the import kernel, in stream order.  Device source: the pointers are
+  // vouched for and stream_ waits for an event recorded on the producing stream (no host wait).  Host source: `width`
+  // bytes per record go to stage_ (a strided source is packed on the host first; `split`: this engine's blocks of a
+  // packed source), the flag bytes behind them.
+  int import_view(const msmz_src& s, int point_fe_bytes, uint64_t n, const GenMap* split, ImportView* v) {
+    if (int st = src_check(&s, point_fe_bytes, &v->width, &v->stride)) return st;
+    const uint8_t* p = (const uint8_t*)s.ptr;
+    if (s.flags & MSMZ_SRC_DEVICE) {
+      if (split) return MSMZ_ERR_ARG;   // (a multi-device context hands its engines host copies)
+      const void* dp = nullptr;
+      int st;
+      if ((st = vouch(p, (n - 1) * v->stride + v->width, false, &dp))) return st;
+      v->ptr = (const uint8_t*)dp;
+      if (s.is_inf) {
+        if ((st = vouch(s.is_inf, n, false, &dp))) return st;
+        v->is_inf = (const uint8_t*)dp;
+      }
+      if (s.stream || (s.flags & MSMZ_SRC_DEFAULT_STREAM)) {
+        MSMZ_HIP(hipEventRecord(import_ev_, (hipStream_t)s.stream));
+        MSMZ_HIP(hipStreamWaitEvent(stream_, import_ev_, 0));
+      }
+      return MSMZ_OK;
+    }
+    const uint32_t w = v->width;
+    if (split && v->stride != w) return MSMZ_ERR_ARG;
+    int st = stage_.ensure((size_t)n * w + n);
+    if (st) return st;
+    if (v->stride != w) {
+      import_pack_.resize((size_t)n * w);   // (lives until the import's error-word fetch has drained the stream)
+      for (uint64_t i = 0; i < n; i++) memcpy(import_pack_.data() + i * w, p + i * v->stride, w);
+      p = import_pack_.data();
+    }
+    // (a failure once a copy may be queued drains the stream: when the call returns the source is no longer read)
+    if ((st = copy_h2d(stage_.p, p, w, n, split))) return (void)hipStreamSynchronize(stream_), st;
+    if (s.is_inf) {
+      uint8_t* d_inf = stage_.as<uint8_t>() + (size_t)n * w;
+      if ((st = copy_h2d(d_inf, s.is_inf, 1, n, split))) return (void)hipStreamSynchronize(stream_), st;
+      v->is_inf = d_inf;
+    }
+    v->ptr = stage_.as<const uint8_t>();
+    v->stride = w;
+    return MSMZ_OK;
+  }
+
+  // the conversion kernel over a view, then the error-word fetch: when it returns the source has been read
+  int import_scalars_to(uint32_t* dst, const msmz_src& s, const ImportView& v, uint64_t n) {
+    return checked([&](uint32_t* d_err) {   // a scalar (either form) >= group order
+      hipLaunchKernelGGL((k_import_scalars<Fr>), dim3((n + 255) / 256), dim3(256), 0, stream_, dst, v.ptr, v.stride,
+                         (int)(v.width / 4), (uint32_t)n, (s.flags & MSMZ_SRC_MONTGOMERY) ? 1 : 0, d_err);
+    });
+  }
+
+  int ensure_gen_table() {
+    if (gen_table_.p) return MSMZ_OK;
+    int st = gen_table_.ensure((size_t)GEN_WINDOWS * GEN_TABLE * RW * 4);
+    if (st) return st;
+    // bases 2^(13 k) * G computed on the host, multiples on the device
+    uint32_t bases[GEN_WINDOWS * RW];
+    Affine<F> ga;
+    fe_set_const<F>(ga.x, F::GX);
+    fe_set_const<F>(ga.y, F::GY);
+    if constexpr (TE) {
+      TeExt<F> g;
+      g.X = ga.x;
+      g.Y = ga.y;
+      fe_set_const<F>(g.Z, F::ONE);
+      fe_mul(g.T, ga.x, ga.y);
+      for (int k = 0; k < GEN_WINDOWS; k++) {
+        Fe<F> zi, x, y;
+        fe_inverse(zi, g.Z);
+        fe_mul(x, g.X, zi);
+        fe_mul(y, g.Y, zi);
+        fe_store<F>(bases + k * RW, x);
+        fe_store<F>(bases + k * RW + NW, y);
+        for (int j = 0; j < GEN_BITS; j++) {
+          TeExt<F> t;
+          te_add(t, g, g);
+          g = t;
+        }
+      }
+    } else {
+      Xyzz<F> g;
+      xyzz_from_affine(g, ga);
+      for (int k = 0; k < GEN_WINDOWS; k++) {
+        Affine<F> a;
+        host_xyzz_to_affine_mont(a, g);
+        fe_store<F>(bases + k * RW, a.x);
+        fe_store<F>(bases + k * RW + NW, a.y);
+        for (int j = 0; j < GEN_BITS; j++) {
+          Xyzz<F> t;
+          xyzz_dbl(t, g);
+          g = t;
+        }
+      }
+    }
+    st = stage_.ensure(sizeof(bases));
+    if (st) return st;
+    MSMZ_HIP(hipMemcpyAsync(stage_.p, bases, sizeof(bases), hipMemcpyHostToDevice, stream_));
+    if constexpr (TE) {
+      hipLaunchKernelGGL((k_te_gen_table<F>), dim3((GEN_WINDOWS * GEN_TABLE + 127) / 128), dim3(128), 0, stream_,
+                         gen_table_.as<uint32_t>(), stage_.as<uint32_t>());
+    } else {
+      hipLaunchKernelGGL((k_gen_table<F>), dim3((GEN_WINDOWS * GEN_TABLE + 127) / 128), dim3(128), 0, stream_,
+                         gen_table_.as<uint32_t>(), stage_.as<uint32_t>());
+    }
+    MSMZ_HIP(hipGetLastError());
+    MSMZ_HIP(hipStreamSynchronize(stream_));
+    return MSMZ_OK;
+  }
+
+  static void host_xyzz_to_affine_mont(Affine<F>& a, const Xyzz<F>& p) {
+    Fe<F> zi3, t, zi2;
+    fe_inverse(zi3, p.ZZZ);
+    fe_mul(t, zi3, p.ZZ);
+    fe_sqr(zi2, t);
+    fe_mul(a.x, p.X, zi2);
+    fe_mul(a.y, p.Y, zi3);
+  }
+
+ protected:
+  int device_;
+  hipStream_t stream_ = nullptr;
+  HandleTable handles_;
+  DevBuf stage_;                       // host data on its way to a kernel, results on their way back
+  DevBuf meta_;                        // MsmMeta: the error word every kernel here reports through; the pipeline's totals
+  PinnedOne<MsmMeta> h_meta_;          // ... and its pinned landing
+  PinnedBuf h_res_;                    // pinned landing of a result record here, of the window results of an MSM
+
+ private:
+  hipEvent_t import_ev_ = nullptr;     // orders stream_ behind the stream that produces an imported device source
+  std::vector<uint8_t> import_pack_;   // host packing of a strided host source
+  DevBuf gen_table_;
+  DevBuf sdot_;                        // scalars_dot: its result record, then one partial sum per tile
+  DevBuf sscan_;                       // scalars_recurrence / _inverse: the result record, then aggregates and incoming values
+  DevBuf check_;                       // check_points: its result record, then one verdict byte per point
+  PinnedBuf h_check_;                  // pinned landing of the result record and the verdict bytes behind it
+};
+
+}  // namespace msmz
