@@ -62,18 +62,24 @@ function bigintToBytes(x, len) {
   return out;
 }
 
-/** the range checks shared by scalarRecurrence and invertScalars: ranges = [[name, first, array or null], ...], the last
- * one the destination -> n */
-function scanRanges(who, ranges, n, out, firstOut) {
+/** a scalar as the addon takes it: 32 bytes, little-endian */
+const scalarBuf = (v) => Buffer.from(bigintToBytes(v, 32));
+
+/** the range checks of every operation over resident arrays: ranges = [[name, first, array or null], ...] -> n (absent:
+ * what the shortest array leaves).  Every `first` is an index of its array, and 0 without one; 1 <= n < limit fits every
+ * array from its `first`.  With `out` the last range is the destination: it may be an input's range exactly or apart
+ * from it, never overlap it in part. */
+function scanRanges(who, ranges, n, out = null, limit = 2 ** 32) {
   for (const [name, first, arr] of ranges) {
     if (!Number.isInteger(first) || first < 0 || (arr === null ? first !== 0 : first >= arr.n))
       throw Error(`${who}: ${name} = ${first}` + (arr === null ? " without the array it indexes" : ` but the array holds ${arr.n}`));
   }
   if ((n === undefined || n === null) && ranges.some((r) => r[2] !== null))
     n = Math.min(...ranges.filter((r) => r[2] !== null).map(([, first, arr]) => arr.n - first));
-  if (!Number.isInteger(n) || n < 1 || n >= 2 ** 32) throw Error(`${who}: n = ${n}`);
+  if (!Number.isInteger(n) || n < 1 || n >= limit) throw Error(`${who}: n = ${n}`);
   for (const [name, first, arr] of ranges)
     if (arr !== null && n > arr.n - first) throw Error(`${who}: entries [${first}, +${n}) from ${name} of an array of ${arr.n}`);
+  const firstOut = ranges[ranges.length - 1][1];
   if (out !== null)
     for (const [name, first, arr] of ranges.slice(0, -1))
       if (arr !== null && arr.handle === out.handle && first !== firstOut && Math.abs(first - firstOut) < n)
@@ -96,6 +102,8 @@ class DeviceArray extends Array {
     this.handle = null;
   }
 }
+const isScalars = (v) => v instanceof DeviceArray && v.kind === "scalars";
+const isPoints = (v) => v instanceof DeviceArray && v.kind === "points";
 
 // ---------------------------------------------------------------------------------------------------------------
 // Pointer-style routes of the reference (src/parallel.ts:89-133, src/curve-affine.ts:290-308, Scalar.writeBigint):
@@ -180,6 +188,10 @@ function createCurve(params, kind) {
     return p;
   }
 
+  function decodePoints(r, count) {   // the {xy, isInf} of the addon's msmBatch / msmSegments -> count results
+    return Array.from({ length: count }, (_, k) => decodePoint(r.xy, 2 * fb * k, r.isInf[k]));
+  }
+
   // options.scalarBits: "every scalar of this call is below 2^scalarBits" (msmz_opts.reserved[1]); 0 / absent = no bound.
   // Checked here, before anything reaches the device.
   function scalarBitsArg(options, who) {
@@ -189,17 +201,33 @@ function createCurve(params, kind) {
     return bits;
   }
 
-  async function msmCommon(scalars, points, n, verbose, options, safe, buckets) {
-    options = options || {};
-    const opts = {
+  // the options of an MSM call as the addon takes them; buckets undefined: options.buckets
+  function msmOpts(options, who, safe, buckets, timing = 0) {
+    return {
       c: options.c || 0,
       glv: options.glv !== undefined ? Number(options.glv) : te ? 0 : -1,   // -1: GLV below 2^21 points (include/msmz.h)
       safe: options.useSafeAdditions !== undefined ? Number(options.useSafeAdditions) : safe,
-      buckets,
-      timing: verbose ? 1 : 0,
+      buckets: buckets === undefined ? options.buckets || 0 : buckets,
+      timing,
       reduceAffine: options.reduceAffine ? 1 : 0, // batched-affine first reduction level (reduceBucketsAffine)
-      scalarBits: scalarBitsArg(options, "msm"),
+      scalarBits: scalarBitsArg(options, who),
     };
+  }
+
+  // the pointer form (ptr, inputPtr, n) of pointsFromBytes / scalarsFromBytes: the bytes were put behind inputPtr with
+  // memoryBytes.set, the converted (Montgomery, GPU-resident) records end up behind ptr.  Range errors (a coordinate >= p)
+  // surface here, like every upload.
+  function fromPointer(who, ptr, inputPtr, count, size, upload, kind) {
+    const [dst, doff] = space.find(ptr), [src, soff] = space.find(inputPtr);
+    if (doff !== 0 || src.host === null || soff + count * size > src.size) throw Error(`${who}(ptr, inputPtr, n): bad pointers`);
+    if (dst.device) dst.device.free();
+    const bytes = src.host.subarray(soff, soff + count * size);
+    dst.device = DeviceArray.make(curve, upload(bytes), count, kind);
+    dst.host = bytes; dst.count = count; dst.dirty = false; dst.inf = null;
+  }
+
+  async function msmCommon(scalars, points, n, verbose, options, safe, buckets) {
+    const opts = msmOpts(options || {}, "msm", safe, buckets, verbose ? 1 : 0);
     if (typeof points === "number") points = resident(points, n, "msm points");
     if (typeof scalars === "number") scalars = resident(scalars, n, "msm scalars");
     const s = scalars instanceof DeviceArray ? scalars.handle : scalars; // Buffer = host scalars
@@ -215,14 +243,7 @@ function createCurve(params, kind) {
   // host byte arrays (scalarsFromBytes format, concatenated here).  A list of resident arrays is refused.
   async function msmBatchCommon(scalarsList, points, n, options, safe) {
     options = options || {};
-    const opts = {
-      c: options.c || 0,
-      glv: options.glv !== undefined ? Number(options.glv) : te ? 0 : -1,
-      safe: options.useSafeAdditions !== undefined ? Number(options.useSafeAdditions) : safe,
-      buckets: options.buckets || 0,
-      reduceAffine: options.reduceAffine ? 1 : 0,
-      scalarBits: scalarBitsArg(options, "msmBatch"),
-    };
+    const opts = msmOpts(options, "msmBatch", safe);
     if (typeof points === "number") points = resident(points, n, "msmBatch points");
     if (!(n > 0) || n > points.n) throw Error(`msmBatch: n = ${n} but the point set holds ${points.n}`);
     let s, B;
@@ -240,28 +261,17 @@ function createCurve(params, kind) {
       B = scalarsList.length;
       s = Buffer.concat(scalarsList.map((v) => Buffer.from(v.buffer, v.byteOffset, 32 * n)));
     }
-    const r = N.msmBatch(ctx, points.handle, s, n, B, fb, opts);
-    const out = [];
-    for (let k = 0; k < B; k++) out.push(decodePoint(r.xy, 2 * fb * k, r.isInf[k]));
-    return out;
+    return decodePoints(N.msmBatch(ctx, points.handle, s, n, B, fb, opts), B);
   }
 
   // One MSM per segment (msmz_msm_segments): `segments` is an array of [firstPoint, firstScalar, n]; result k =
   // sum_{i < n} scalars[firstScalar + i] * points[firstPoint + i] over ONE resident scalar array and ONE resident point
   // array (plain or precomputed).  Checked here, before anything reaches the device.
   async function msmSegmentsCommon(scalars, points, segments, options, safe) {
-    options = options || {};
-    const opts = {
-      c: options.c || 0,
-      glv: options.glv !== undefined ? Number(options.glv) : te ? 0 : -1,
-      safe: options.useSafeAdditions !== undefined ? Number(options.useSafeAdditions) : safe,
-      buckets: options.buckets || 0,
-      reduceAffine: options.reduceAffine ? 1 : 0,
-      scalarBits: scalarBitsArg(options, "msmSegments"),
-    };
+    const opts = msmOpts(options || {}, "msmSegments", safe);
     if (!(points instanceof DeviceArray) || (points.kind !== "points" && points.kind !== "precomputed"))
       throw TypeError("msmSegments: `points` is a resident point array (plain or precomputed)");
-    if (!(scalars instanceof DeviceArray) || scalars.kind !== "scalars")
+    if (!isScalars(scalars))
       throw TypeError("msmSegments: `scalars` is a resident scalar array; host scalars are uploaded first");
     if (!Array.isArray(segments) || segments.length === 0 || segments.length >= 2 ** 32)
       throw Error("msmSegments: `segments` is a non-empty array of [firstPoint, firstScalar, n]");
@@ -275,10 +285,7 @@ function createCurve(params, kind) {
       if (firstScalar + n > scalars.n) throw Error(`msmSegments: segment ${k}: scalars [${firstScalar}, +${n}) of a set of ${scalars.n}`);
       seg.forEach((v, j) => table.writeBigUInt64LE(BigInt(v), 24 * k + 8 * j));
     });
-    const r = N.msmSegments(ctx, points.handle, scalars.handle, table, segments.length, fb, opts);
-    const out = [];
-    for (let k = 0; k < segments.length; k++) out.push(decodePoint(r.xy, 2 * fb * k, r.isInf[k]));
-    return out;
+    return decodePoints(N.msmSegments(ctx, points.handle, scalars.handle, table, segments.length, fb, opts), segments.length);
   }
 
   const Parallel = {
@@ -289,7 +296,7 @@ function createCurve(params, kind) {
      * windows, fewer copies; MSMs over the array take that bound).  The copies' parameters are in the array's `info`. */
     async precomputePoints(points, n, options, factor = 0) {
       options = options || {};
-      if (!(points instanceof DeviceArray) || points.kind !== "points")
+      if (!isPoints(points))
         throw TypeError("precomputePoints: `points` is a resident point array (pointsFromBytes / randomPointsFast)");
       if (!Number.isInteger(n) || n < 1 || n > points.n) throw Error(`precomputePoints: n = ${n} but the point set holds ${points.n}`);
       if (!Number.isInteger(factor) || factor < 0 || factor === 1 || factor >= 2 ** 32)
@@ -307,7 +314,7 @@ function createCurve(params, kind) {
      * ok), verdicts (with options.verdicts: one byte per point, bit 0 = not on the curve, bit 1 = on the curve but
      * outside the subgroup)} */
     async checkPoints(points, n, { subgroup = true, first = 0, verdicts = false } = {}) {
-      if (!(points instanceof DeviceArray) || points.kind !== "points")
+      if (!isPoints(points))
         throw TypeError("checkPoints: `points` is a resident point array (pointsFromBytes / randomPointsFast)");
       if (!Number.isInteger(first) || first < 0 || first >= points.n) throw Error(`checkPoints: first = ${first} but the point set holds ${points.n}`);
       n = n === undefined || n === null ? points.n - first : n;
@@ -322,24 +329,17 @@ function createCurve(params, kind) {
      * `points` itself (an IPA fold: mulPoints(u, G, n, {addend: G, firstPoint: n})).  The result is an ordinary point
      * array. */
     async mulPoints(scalars, points, n, { addend = null, firstPoint = 0, firstScalar = 0, firstAddend = 0 } = {}) {
-      if (!(points instanceof DeviceArray) || points.kind !== "points")
+      if (!isPoints(points))
         throw TypeError("mulPoints: `points` is a resident point array (pointsFromBytes / randomPointsFast)");
-      if (addend !== null && (!(addend instanceof DeviceArray) || addend.kind !== "points"))
+      if (addend !== null && !isPoints(addend))
         throw TypeError("mulPoints: `addend` is a resident point array or null");
       const broadcast = typeof scalars === "bigint";
-      if (!broadcast && (!(scalars instanceof DeviceArray) || scalars.kind !== "scalars"))
+      if (!broadcast && !isScalars(scalars))
         throw TypeError("mulPoints: `scalars` is a resident scalar array or a bigint (one scalar for every point)");
       if (broadcast && (scalars < 0n || scalars >= params.order)) throw Error(`mulPoints: the scalar ${scalars} is not in [0, group order)`);
-      const ranges = [["firstPoint", firstPoint, points], ["firstScalar", firstScalar, broadcast ? null : scalars], ["firstAddend", firstAddend, addend]];
-      for (const [name, first, arr] of ranges) {
-        if (!Number.isInteger(first) || first < 0 || (arr === null ? first !== 0 : first >= arr.n))
-          throw Error(`mulPoints: ${name} = ${first}` + (arr === null ? " without the array it indexes" : ` but the array holds ${arr.n}`));
-      }
-      if (n === undefined || n === null) n = Math.min(...ranges.filter((r) => r[2] !== null).map(([, first, arr]) => arr.n - first));
-      if (!Number.isInteger(n) || n < 1) throw Error(`mulPoints: n = ${n}`);
-      for (const [name, first, arr] of ranges)
-        if (arr !== null && n > arr.n - first) throw Error(`mulPoints: entries [${first}, +${n}) from ${name} of an array of ${arr.n}`);
-      const h = N.mulPoints(ctx, points.handle, firstPoint, broadcast ? Buffer.from(bigintToBytes(scalars, 32)) : scalars.handle,
+      n = scanRanges("mulPoints", [["firstPoint", firstPoint, points], ["firstScalar", firstScalar, broadcast ? null : scalars],
+                                   ["firstAddend", firstAddend, addend]], n, null, Infinity);   // (no bound on n here)
+      const h = N.mulPoints(ctx, points.handle, firstPoint, broadcast ? scalarBuf(scalars) : scalars.handle,
                             firstScalar, addend === null ? 0 : addend.handle, firstAddend, n);
       return DeviceArray.make(curve, h, n, "points");
     },
@@ -350,7 +350,6 @@ function createCurve(params, kind) {
      * when the range is exactly that input's or apart from it (an IPA fold in place:
      * combineScalars(1n, v, uinv, v, n, {firstY: n, out: v})).  Returns the array written. */
     async combineScalars(a, x, b = null, y = null, n, { firstX = 0, firstY = 0, out = null, firstOut = 0, firstA = 0, firstB = 0 } = {}) {
-      const isScalars = (v) => v instanceof DeviceArray && v.kind === "scalars";
       if (!isScalars(x)) throw TypeError("combineScalars: `x` is a resident scalar array");
       if ((b === null) !== (y === null)) throw TypeError("combineScalars: `b` and `y` come together");
       if (y !== null && !isScalars(y)) throw TypeError("combineScalars: `y` is a resident scalar array or null");
@@ -361,7 +360,7 @@ function createCurve(params, kind) {
         if (typeof c === "bigint") {
           if (c < 0n || c >= params.order) throw Error(`combineScalars: the coefficient ${c} is not in [0, group order)`);
           ranges.push([name, first, null]);
-          return c === 1n ? null : Buffer.from(bigintToBytes(c, 32));
+          return c === 1n ? null : scalarBuf(c);
         }
         if (!isScalars(c)) throw TypeError("combineScalars: a coefficient is a bigint (one for every entry) or a resident scalar array");
         ranges.push([name, first, c]);
@@ -369,18 +368,7 @@ function createCurve(params, kind) {
       };
       const ca = coeff("firstA", a, firstA, true), cb = coeff("firstB", b, firstB, y !== null);
       ranges.push(["firstOut", firstOut, out]);
-      for (const [name, first, arr] of ranges) {
-        if (!Number.isInteger(first) || first < 0 || (arr === null ? first !== 0 : first >= arr.n))
-          throw Error(`combineScalars: ${name} = ${first}` + (arr === null ? " without the array it indexes" : ` but the array holds ${arr.n}`));
-      }
-      if (n === undefined || n === null) n = Math.min(...ranges.filter((r) => r[2] !== null).map(([, first, arr]) => arr.n - first));
-      if (!Number.isInteger(n) || n < 1 || n >= 2 ** 32) throw Error(`combineScalars: n = ${n}`);
-      for (const [name, first, arr] of ranges)
-        if (arr !== null && n > arr.n - first) throw Error(`combineScalars: entries [${first}, +${n}) from ${name} of an array of ${arr.n}`);
-      if (out !== null)
-        for (const [name, first, arr] of ranges.slice(0, -1))
-          if (arr !== null && arr.handle === out.handle && first !== firstOut && Math.abs(first - firstOut) < n)
-            throw Error(`combineScalars: the destination [${firstOut}, +${n}) overlaps the input range [${first}, +${n}) (${name}) in part`);
+      n = scanRanges("combineScalars", ranges, n, out);
       const h = N.scalarsCombine(ctx, x.handle, firstX, ca, firstA, y === null ? 0 : y.handle, firstY, cb, firstB, n, firstOut,
                                  out === null ? 0 : out.handle);
       return out === null ? DeviceArray.make(curve, h, n, "scalars") : out;
@@ -388,15 +376,8 @@ function createCurve(params, kind) {
     /** sum_i x[firstX + i] y[firstY + i] mod the group order (y null: sum_i x[firstX + i]) as a bigint
      * (msmz_scalars_dot); x and y may be one array and may overlap */
     async innerProduct(x, y = null, n, { firstX = 0, firstY = 0 } = {}) {
-      const isScalars = (v) => v instanceof DeviceArray && v.kind === "scalars";
       if (!isScalars(x) || (y !== null && !isScalars(y))) throw TypeError("innerProduct: `x` and `y` are resident scalar arrays (y may be null)");
-      const ranges = [["firstX", firstX, x], ["firstY", firstY, y]];
-      for (const [name, first, arr] of ranges)
-        if (!Number.isInteger(first) || first < 0 || (arr === null ? first !== 0 : first >= arr.n)) throw Error(`innerProduct: ${name} = ${first}`);
-      if (n === undefined || n === null) n = Math.min(...ranges.filter((r) => r[2] !== null).map(([, first, arr]) => arr.n - first));
-      if (!Number.isInteger(n) || n < 1 || n >= 2 ** 32) throw Error(`innerProduct: n = ${n}`);
-      for (const [name, first, arr] of ranges)
-        if (arr !== null && n > arr.n - first) throw Error(`innerProduct: entries [${first}, +${n}) from ${name} of an array of ${arr.n}`);
+      n = scanRanges("innerProduct", [["firstX", firstX, x], ["firstY", firstY, y]], n);
       const r = N.scalarsDot(ctx, x.handle, firstX, y === null ? 0 : y.handle, firstY, n);
       return bytesToBigint(r, 0, 32);
     },
@@ -407,7 +388,7 @@ function createCurve(params, kind) {
         if (v < 0n || v >= params.order) throw Error(`scalarPowers: ${name} = ${v} is not in [0, group order)`);
       }
       if (!Number.isInteger(n) || n < 1 || n >= 2 ** 32) throw Error(`scalarPowers: n = ${n}`);
-      const h = N.scalarsPowers(ctx, Buffer.from(bigintToBytes(base, 32)), Buffer.from(bigintToBytes(ratio, 32)), n);
+      const h = N.scalarsPowers(ctx, scalarBuf(base), scalarBuf(ratio), n);
       return DeviceArray.make(curve, h, n, "scalars");
     },
     /** the first-order linear recurrence y_i = a_i y_(i-1) + b_i mod the group order, i < n, from y_(-1) = init
@@ -417,7 +398,6 @@ function createCurve(params, kind) {
      * `exclusive` the value the step at i started from.  Without `out` the result is a new array; `out` may be `a` or `b`
      * when the range is exactly theirs or apart from it.  Returns [the array written, the final y]. */
     async scalarRecurrence(a, b, n, { init = null, reverse = false, exclusive = false, firstA = 0, firstB = 0, out = null, firstOut = 0 } = {}) {
-      const isScalars = (v) => v instanceof DeviceArray && v.kind === "scalars";
       const broadcast = typeof a === "bigint";
       if (a !== null && !broadcast && !isScalars(a)) throw TypeError("scalarRecurrence: `a` is a resident scalar array, a bigint or null");
       if (b !== null && !isScalars(b)) throw TypeError("scalarRecurrence: `b` is a resident scalar array or null");
@@ -426,9 +406,9 @@ function createCurve(params, kind) {
       if (init !== null && typeof init !== "bigint") throw TypeError("scalarRecurrence: `init` is a bigint or null");
       for (const [name, v] of [["a", broadcast ? a : null], ["init", init]])
         if (v !== null && (v < 0n || v >= params.order)) throw Error(`scalarRecurrence: ${name} = ${v} is not in [0, group order)`);
-      n = scanRanges("scalarRecurrence", [["firstA", firstA, isScalars(a) ? a : null], ["firstB", firstB, b], ["firstOut", firstOut, out]], n, out, firstOut);
-      const r = N.scalarsRecurrence(ctx, broadcast ? Buffer.from(bigintToBytes(a, 32)) : a === null ? null : a.handle, firstA,
-                                    b === null ? 0 : b.handle, firstB, init === null ? null : Buffer.from(bigintToBytes(init, 32)),
+      n = scanRanges("scalarRecurrence", [["firstA", firstA, isScalars(a) ? a : null], ["firstB", firstB, b], ["firstOut", firstOut, out]], n, out);
+      const r = N.scalarsRecurrence(ctx, broadcast ? scalarBuf(a) : a === null ? null : a.handle, firstA,
+                                    b === null ? 0 : b.handle, firstB, init === null ? null : scalarBuf(init),
                                     (reverse ? 1 : 0) | (exclusive ? 2 : 0), n, firstOut, out === null ? 0 : out.handle);
       return [out === null ? DeviceArray.make(curve, r.handle, n, "scalars") : out, bytesToBigint(r.last, 0, 32)];
     },
@@ -444,16 +424,15 @@ function createCurve(params, kind) {
      * quotient has n entries, the top one 0: an MSM takes it against the same n points as p (a KZG opening proof). */
     async divideByLinear(p, z, n, { first = 0 } = {}) {
       if (typeof z !== "bigint") throw TypeError("divideByLinear: `z` is a bigint");
-      if (!(p instanceof DeviceArray) || p.kind !== "scalars") throw TypeError("divideByLinear: `p` is a resident scalar array");
+      if (!isScalars(p)) throw TypeError("divideByLinear: `p` is a resident scalar array");
       return this.scalarRecurrence(z, p, n, { init: 0n, reverse: true, exclusive: true, firstB: first });
     },
     /** out[firstOut + i] = x[first + i]^-1 mod the group order, 0 -> 0 (msmz_scalars_inverse): [the array written, the
      * number of zeros].  `out` may be `x` over exactly the same range (in place) or apart from it. */
     async invertScalars(x, n, { first = 0, out = null, firstOut = 0 } = {}) {
-      const isScalars = (v) => v instanceof DeviceArray && v.kind === "scalars";
       if (!isScalars(x)) throw TypeError("invertScalars: `x` is a resident scalar array");
       if (out !== null && !isScalars(out)) throw TypeError("invertScalars: `out` is a resident scalar array or null");
-      n = scanRanges("invertScalars", [["first", first, x], ["firstOut", firstOut, out]], n, out, firstOut);
+      n = scanRanges("invertScalars", [["first", first, x], ["firstOut", firstOut, out]], n, out);
       const r = N.scalarsInverse(ctx, x.handle, first, n, firstOut, out === null ? 0 : out.handle);
       return [out === null ? DeviceArray.make(curve, r.handle, n, "scalars") : out, r.zeros];
     },
@@ -479,15 +458,8 @@ function createCurve(params, kind) {
      * reference's (pointPtr, pointInputPtr, n): the bytes were put behind pointInputPtr with Field.memoryBytes.set,
      * the converted (Montgomery, GPU-resident) points end up behind pointPtr. */
     async pointsFromBytes(bytes, n, isInf) {
-      if (typeof bytes === "number") {
-        const [dst, doff] = space.find(bytes), [src, soff] = space.find(n), count = isInf;
-        if (doff !== 0 || src.host === null || soff + count * 2 * fb > src.size) throw Error("pointsFromBytes(ptr, inputPtr, n): bad pointers");
-        if (dst.device) dst.device.free();
-        // range errors (a coordinate >= p) surface here, like every upload
-        dst.device = DeviceArray.make(curve, N.uploadPoints(ctx, src.host.subarray(soff, soff + count * 2 * fb), null, count), count, "points");
-        dst.host = src.host.subarray(soff, soff + count * 2 * fb); dst.count = count; dst.dirty = false; dst.inf = null;
-        return;
-      }
+      if (typeof bytes === "number")   // (pointPtr, pointInputPtr, n)
+        return fromPointer("pointsFromBytes", bytes, n, isInf, 2 * fb, (b) => N.uploadPoints(ctx, b, null, isInf), "points");
       // (bytes, n?, {montgomery, isInf}): coordinates as 64-bit-limb Montgomery residues v * 2^(8 feBytes) mod p
       let montgomery = false;
       if (isInf && typeof isInf === "object" && !ArrayBuffer.isView(isInf) && !Array.isArray(isInf)) {
@@ -500,14 +472,8 @@ function createCurve(params, kind) {
     },
     /** parallel.ts:114-133: 32 bytes little-endian per scalar */
     async scalarsFromBytes(bytes, n, count) {
-      if (typeof bytes === "number") {   // (scalarPtr, scalarInputPtr, n): parallel.ts:114-133
-        const [dst, doff] = space.find(bytes), [src, soff] = space.find(n);
-        if (doff !== 0 || src.host === null || soff + count * 32 > src.size) throw Error("scalarsFromBytes(ptr, inputPtr, n): bad pointers");
-        if (dst.device) dst.device.free();
-        dst.device = DeviceArray.make(curve, N.uploadScalars(ctx, src.host.subarray(soff, soff + count * 32), count), count, "scalars");
-        dst.host = src.host.subarray(soff, soff + count * 32); dst.count = count; dst.dirty = false;
-        return;
-      }
+      if (typeof bytes === "number")   // (scalarPtr, scalarInputPtr, n): parallel.ts:114-133
+        return fromPointer("scalarsFromBytes", bytes, n, count, 32, (b) => N.uploadScalars(ctx, b, count), "scalars");
       // (bytes, n?, {width, montgomery}): `width` bytes per scalar on the wire (4..32, a multiple of 4, zero-extended on
       // the GPU); montgomery: 32-byte records v * 2^256 mod q.  Without them: the plain upload, as before.
       if (count && typeof count === "object") {

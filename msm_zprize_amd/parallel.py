@@ -17,8 +17,8 @@ include/msmz.h -- this module contains no arithmetic.
 import ctypes as C
 
 from . import _native
-from ._native import (MsmzCheckResult, MsmzLog, MsmzMul, MsmzOpts, MsmzScalarRec, MsmzScalarTerm, MsmzSegment, MsmzSrc, check,
-                      lib)
+from ._native import MsmzCheckResult, MsmzLog, MsmzMul, MsmzOpts, MsmzScalarRec, MsmzScalarTerm, MsmzSegment, MsmzSrc, lib
+from ._native import check as _check   # (`check=` is a public keyword of pointsFromBytes / pointsFromTensor)
 
 _state = {"devices": None}
 
@@ -60,8 +60,26 @@ class DeviceArray:
 
     def free(self):
         if self.handle is not None:
-            check(lib().msmz_free(self.curve._ctx, self.handle), "msmz_free")
+            _check(lib().msmz_free(self.curve._ctx, self.handle), "msmz_free")
             self.handle = None
+
+
+def _is_int(v):
+    """an int, and not a bool"""
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def _is_array(v, *kinds):
+    """a resident array of one of `kinds`"""
+    return isinstance(v, DeviceArray) and v.kind in kinds
+
+
+def _resident(curve, kind, n, name, *args, after=(), out=None):
+    """msmz_<name>(ctx, *args, &handle, *after) -> the resident array the call made: n entries of `kind`.  With `out` the
+    call writes into that array (its handle goes in) and `out` comes back: the "out given or new" convention."""
+    h = C.c_uint64(0 if out is None else out.handle)
+    _check(getattr(lib(), name)(curve._ctx, *args, C.byref(h), *after), name)
+    return DeviceArray(curve, h.value, n, kind) if out is None else out
 
 
 class _Scalar:
@@ -74,7 +92,7 @@ class _Scalar:
         """readBigint over a range (scripts/msm-weierstrass.ts:74-78)."""
         count = arr.n - first if count is None else count
         buf = C.create_string_buffer(32 * count)
-        check(lib().msmz_download_scalars(self._c._ctx, arr.handle, first, count, buf), "msmz_download_scalars")
+        _check(lib().msmz_download_scalars(self._c._ctx, arr.handle, first, count, buf), "msmz_download_scalars")
         raw = buf.raw
         return [int.from_bytes(raw[32 * i:32 * i + 32], "little") for i in range(count)]
 
@@ -92,14 +110,9 @@ class _Affine:
         fb = self._c.fe_bytes
         buf = C.create_string_buffer(2 * fb * count)
         inf = C.create_string_buffer(count)
-        check(lib().msmz_download_points(self._c._ctx, arr.handle, first, count, buf, inf), "msmz_download_points")
-        raw = buf.raw
-        out = []
-        for i in range(count):
-            x = int.from_bytes(raw[2 * fb * i:2 * fb * i + fb], "little")
-            y = int.from_bytes(raw[2 * fb * i + fb:2 * fb * (i + 1)], "little")
-            out.append({"x": x, "y": y, "isZero": inf.raw[i] != 0})
-        return out
+        _check(lib().msmz_download_points(self._c._ctx, arr.handle, first, count, buf, inf), "msmz_download_points")
+        raw, flags = buf.raw, inf.raw
+        return [self._c._point(raw, i, flags[i] != 0, zero_rule=False) for i in range(count)]
 
 
 class _Parallel:
@@ -110,14 +123,10 @@ class _Parallel:
 
     # -- inputs ---------------------------------------------------------------------------------
     def randomPointsFast(self, n, seed=0x6D736D7A):
-        h = C.c_uint64()
-        check(lib().msmz_random_points(self._c._ctx, n, seed, C.byref(h)), "msmz_random_points")
-        return DeviceArray(self._c, h.value, n, "points")
+        return _resident(self._c, "points", n, "msmz_random_points", n, seed)
 
     def randomScalars(self, n, seed=0x6D736D7A):
-        h = C.c_uint64()
-        check(lib().msmz_random_scalars(self._c._ctx, n, seed, C.byref(h)), "msmz_random_scalars")
-        return DeviceArray(self._c, h.value, n, "scalars")
+        return _resident(self._c, "scalars", n, "msmz_random_scalars", n, seed)
 
     def pointsFromBytes(self, data, n=None, is_inf=None, montgomery=False, check=None):
         """parallel.ts:97-112: x||y little-endian canonical, 2*fe_bytes per point.  montgomery=True: the coordinates are
@@ -133,17 +142,12 @@ class _Parallel:
             raise ValueError(f"pointsFromBytes: {len(data)} bytes for {n} points of {2 * fb} bytes")
         if is_inf is not None and len(is_inf) < n:
             raise ValueError(f"pointsFromBytes: {len(is_inf)} infinity flags for {n} points")
-        h = C.c_uint64()
+        data, flags = bytes(data), None if is_inf is None else bytes(is_inf)
         if montgomery:
-            data = bytes(data)
-            flags = None if is_inf is None else bytes(is_inf)
             src = MsmzSrc(C.cast(C.c_char_p(data), C.c_void_p), 0, 2 * fb, _native.MSMZ_SRC_MONTGOMERY, None,
                           None if flags is None else C.cast(C.c_char_p(flags), C.c_void_p))
-            _native.check(lib().msmz_import_points(self._c._ctx, C.byref(src), n, C.byref(h)), "msmz_import_points")
-            return DeviceArray(self._c, h.value, n, "points")
-        _native.check(lib().msmz_upload_points(self._c._ctx, bytes(data), None if is_inf is None else bytes(is_inf), n,
-                                       C.byref(h)), "msmz_upload_points")
-        return DeviceArray(self._c, h.value, n, "points")
+            return _resident(self._c, "points", n, "msmz_import_points", C.byref(src), n)
+        return _resident(self._c, "points", n, "msmz_upload_points", data, flags, n)
 
     def scalarsFromBytes(self, data, n=None, width=32, montgomery=False):
         """parallel.ts:114-133: 32 bytes little-endian per scalar.  width: bytes per scalar on the wire (4..32, a multiple
@@ -154,15 +158,12 @@ class _Parallel:
         n = len(data) // width if n is None else n
         if n <= 0 or len(data) < width * n:
             raise ValueError(f"scalarsFromBytes: {len(data)} bytes for {n} scalars of {width} bytes")
-        h = C.c_uint64()
+        data = bytes(data)
         if width != 32 or montgomery:
-            data = bytes(data)
             src = MsmzSrc(C.cast(C.c_char_p(data), C.c_void_p), 0, width,
                           _native.MSMZ_SRC_MONTGOMERY if montgomery else 0, None, None)
-            check(lib().msmz_import_scalars(self._c._ctx, C.byref(src), n, C.byref(h)), "msmz_import_scalars")
-            return DeviceArray(self._c, h.value, n, "scalars")
-        check(lib().msmz_upload_scalars(self._c._ctx, bytes(data), n, C.byref(h)), "msmz_upload_scalars")
-        return DeviceArray(self._c, h.value, n, "scalars")
+            return _resident(self._c, "scalars", n, "msmz_import_scalars", C.byref(src), n)
+        return _resident(self._c, "scalars", n, "msmz_upload_scalars", data, n)
 
     # -- imports: the data where it is, in the form it has (msmz_import_*, include/msmz.h) ------------
     def _src(self, view):
@@ -185,21 +186,18 @@ class _Parallel:
         startThreads / the first curve): torch carries its own HIP runtime, a process drives the GPU through one copy
         only, and the copy loaded first serves both; the other way round torch finds no GPU."""
         view = tensor_view(t, self._c.devices, "scalars", self._c.fe_bytes, montgomery, "scalarsFromTensor")
-        h = C.c_uint64()
-        check(lib().msmz_import_scalars(self._c._ctx, C.byref(self._src(view)), view["n"], C.byref(h)),
-              "msmz_import_scalars")
-        return DeviceArray(self._c, h.value, view["n"], "scalars")
+        return _resident(self._c, "scalars", view["n"], "msmz_import_scalars", C.byref(self._src(view)), view["n"])
 
     def scalarsInto(self, dst, first, t, montgomery=False):
         """Write the scalars of tensor `t` (as scalarsFromTensor) over entries [first, first + n) of the resident scalar
         array `dst` (msmz_import_scalars_into): a batch assembled vector by vector.  Single-device contexts."""
-        if not isinstance(dst, DeviceArray) or dst.kind != "scalars":
+        if not _is_array(dst, "scalars"):
             raise TypeError("scalarsInto: `dst` is a resident scalar array")
         view = tensor_view(t, self._c.devices, "scalars", self._c.fe_bytes, montgomery, "scalarsInto")
-        if isinstance(first, bool) or not isinstance(first, int) or first < 0 or first + view["n"] > len(dst):
+        if not _is_int(first) or first < 0 or first + view["n"] > len(dst):
             raise ValueError(f"scalarsInto: entries [{first!r}, +{view['n']}) of an array of {len(dst)}")
-        check(lib().msmz_import_scalars_into(self._c._ctx, dst.handle, first, C.byref(self._src(view)), view["n"]),
-              "msmz_import_scalars_into")
+        _check(lib().msmz_import_scalars_into(self._c._ctx, dst.handle, first, C.byref(self._src(view)), view["n"]),
+               "msmz_import_scalars_into")
         return dst
 
     def pointsFromTensor(self, t, montgomery=False, is_inf=None, check=None):
@@ -210,10 +208,7 @@ class _Parallel:
         if what:
             return self._checked(self.pointsFromTensor(t, montgomery, is_inf), what, "pointsFromTensor")
         view = tensor_view(t, self._c.devices, "points", self._c.fe_bytes, montgomery, "pointsFromTensor", is_inf)
-        h = C.c_uint64()
-        _native.check(lib().msmz_import_points(self._c._ctx, C.byref(self._src(view)), view["n"], C.byref(h)),
-              "msmz_import_points")
-        return DeviceArray(self._c, h.value, view["n"], "points")
+        return _resident(self._c, "points", view["n"], "msmz_import_points", C.byref(self._src(view)), view["n"])
 
     # -- validation (msmz_check_points, include/msmz.h) ---------------------------------------------
     def checkPoints(self, points, N=None, subgroup=True, first=0, verdicts=False):
@@ -224,7 +219,7 @@ class _Parallel:
         first, N, what = check_points_args(points, N, subgroup, first)
         res = MsmzCheckResult()
         buf = C.create_string_buffer(N) if verdicts else None
-        check(lib().msmz_check_points(self._c._ctx, points.handle, first, N, what, C.byref(res), buf), "msmz_check_points")
+        _check(lib().msmz_check_points(self._c._ctx, points.handle, first, N, what, C.byref(res), buf), "msmz_check_points")
         bad = None if res.first_bad == _native.NO_INDEX else int(res.first_bad)
         return CheckResult(bad is None, int(res.off_curve), int(res.off_subgroup), bad, buf.raw if verdicts else None)
 
@@ -237,9 +232,7 @@ class _Parallel:
         a = mul_points_args(scalars, points, N, addend, firstPoint, firstScalar, firstAddend, self._c.params["order"])
         m = MsmzMul(points.handle, a["firstPoint"], 0 if a["scalar"] is not None else scalars.handle, a["firstScalar"],
                     a["scalar"], 0 if addend is None else addend.handle, a["firstAddend"])
-        h = C.c_uint64()
-        check(lib().msmz_points_mul(self._c._ctx, C.byref(m), a["N"], C.byref(h)), "msmz_points_mul")
-        return DeviceArray(self._c, h.value, a["N"], "points")
+        return _resident(self._c, "points", a["N"], "msmz_points_mul", C.byref(m), a["N"])
 
     # -- arithmetic mod q over resident scalar arrays (msmz_scalars_*, include/msmz.h) -----------------
     def combineScalars(self, a, x, b=None, y=None, N=None, firstX=0, firstY=0, out=None, firstOut=0, firstA=0, firstB=0):
@@ -250,10 +243,8 @@ class _Parallel:
         (an IPA fold in place: combineScalars(1, v, uinv, v, N, firstY=N, out=v)).  Returns the array written."""
         t = combine_scalars_args(a, x, b, y, N, firstX, firstY, out, firstOut, firstA, firstB, self._c.params["order"])
         terms = [MsmzScalarTerm(v.handle, fv, 0 if c is None else c.handle, fc, k) for v, fv, c, fc, k in t["terms"]]
-        h = C.c_uint64(0 if out is None else out.handle)
-        check(lib().msmz_scalars_combine(self._c._ctx, C.byref(terms[0]), C.byref(terms[1]) if len(terms) > 1 else None,
-                                         t["N"], t["firstOut"], C.byref(h)), "msmz_scalars_combine")
-        return DeviceArray(self._c, h.value, t["N"], "scalars") if out is None else out
+        return _resident(self._c, "scalars", t["N"], "msmz_scalars_combine", C.byref(terms[0]),
+                         C.byref(terms[1]) if len(terms) > 1 else None, t["N"], t["firstOut"], out=out)
 
     def innerProduct(self, x, y=None, N=None, firstX=0, firstY=0):
         """sum_i x[firstX + i] y[firstY + i] mod the group order (y=None: sum_i x[firstX + i]) as a Python int; x and y
@@ -261,24 +252,21 @@ class _Parallel:
         t = combine_scalars_args(1, x, None if y is None else 1, y, N, firstX, firstY, None, 0, 0, 0,
                                  self._c.params["order"], "innerProduct")
         buf = C.create_string_buffer(32)
-        check(lib().msmz_scalars_dot(self._c._ctx, x.handle, firstX, 0 if y is None else y.handle, firstY, t["N"], buf),
-              "msmz_scalars_dot")
+        _check(lib().msmz_scalars_dot(self._c._ctx, x.handle, firstX, 0 if y is None else y.handle, firstY, t["N"], buf),
+               "msmz_scalars_dot")
         return int.from_bytes(buf.raw, "little")
 
     def scalarPowers(self, ratio, N, base=1):
         """A new resident scalar array: entry i = base ratio^i mod the group order (0^0 = 1)."""
         q = self._c.params["order"]
         for name, v in (("ratio", ratio), ("base", base)):
-            if isinstance(v, bool) or not isinstance(v, int):
+            if not _is_int(v):
                 raise TypeError(f"scalarPowers: `{name}` is an int")
             if not 0 <= v < q:
                 raise ValueError(f"scalarPowers: {name} = {v} is not in [0, group order)")
-        if isinstance(N, bool) or not isinstance(N, int) or not 1 <= N < 1 << 32:
+        if not _is_int(N) or not 1 <= N < 1 << 32:
             raise ValueError(f"scalarPowers: N = {N!r}")
-        h = C.c_uint64()
-        check(lib().msmz_scalars_powers(self._c._ctx, base.to_bytes(32, "little"), ratio.to_bytes(32, "little"), N,
-                                        C.byref(h)), "msmz_scalars_powers")
-        return DeviceArray(self._c, h.value, N, "scalars")
+        return _resident(self._c, "scalars", N, "msmz_scalars_powers", base.to_bytes(32, "little"), ratio.to_bytes(32, "little"), N)
 
     # -- recurrences and inversion over resident scalar arrays (msmz_scalars_recurrence / _inverse) ---
     def scalarRecurrence(self, a, b, N=None, init=None, reverse=False, exclusive=False, firstA=0, firstB=0, out=None,
@@ -291,11 +279,9 @@ class _Parallel:
         theirs or apart from it.  Returns (the array written, the final y as an int)."""
         t = scalar_recurrence_args(a, b, N, init, reverse, exclusive, firstA, firstB, out, firstOut, self._c.params["order"])
         rec = MsmzScalarRec(t["aHandle"], t["firstA"], t["a"], t["bHandle"], t["firstB"], t["init"], t["flags"])
-        h = C.c_uint64(0 if out is None else out.handle)
         last = C.create_string_buffer(32)
-        check(lib().msmz_scalars_recurrence(self._c._ctx, C.byref(rec), t["N"], t["firstOut"], C.byref(h), last),
-              "msmz_scalars_recurrence")
-        arr = DeviceArray(self._c, h.value, t["N"], "scalars") if out is None else out
+        arr = _resident(self._c, "scalars", t["N"], "msmz_scalars_recurrence", C.byref(rec), t["N"], t["firstOut"],
+                        after=(last,), out=out)
         return arr, int.from_bytes(last.raw, "little")
 
     def prefixProducts(self, x, N=None, exclusive=False, init=None, reverse=False, first=0, out=None, firstOut=0):
@@ -311,9 +297,9 @@ class _Parallel:
         """(p(X) - p(z)) / (X - z) for the polynomial with coefficients p[first + i], i < N (lowest degree first):
         (quotient, p(z)).  The quotient is a new array of N entries whose top entry is 0, so an MSM takes it against the
         same N points as p: a KZG opening proof."""
-        if isinstance(z, bool) or not isinstance(z, int):
+        if not _is_int(z):
             raise TypeError("divideByLinear: `z` is an int")
-        if not isinstance(p, DeviceArray) or p.kind != "scalars":
+        if not _is_array(p, "scalars"):
             raise TypeError("divideByLinear: `p` is a resident scalar array")
         return self.scalarRecurrence(z, p, N, 0, True, True, 0, first)
 
@@ -321,11 +307,9 @@ class _Parallel:
         """out[firstOut + i] = x[first + i]^-1 mod the group order, 0 -> 0: (the array written, the number of zeros).
         out=None: a new array; `out` may be `x` over exactly the same range (in place) or apart from it."""
         t = invert_scalars_args(x, N, first, out, firstOut)
-        h = C.c_uint64(0 if out is None else out.handle)
         zeros = C.c_uint64(0)
-        check(lib().msmz_scalars_inverse(self._c._ctx, x.handle, t["first"], t["N"], t["firstOut"], C.byref(h),
-                                         C.byref(zeros)), "msmz_scalars_inverse")
-        arr = DeviceArray(self._c, h.value, t["N"], "scalars") if out is None else out
+        arr = _resident(self._c, "scalars", t["N"], "msmz_scalars_inverse", x.handle, t["first"], t["N"], t["firstOut"],
+                        after=(C.byref(zeros),), out=out)
         return arr, int(zeros.value)
 
     def _checked(self, arr, what, who):
@@ -347,9 +331,7 @@ class _Parallel:
             raise TypeError("msmBatch: a list of resident arrays is not accepted on a multi-device context; pass ONE "
                             "resident array of B * N scalars or a list of host byte arrays")
         B = len(vecs)
-        h = C.c_uint64()
-        check(lib().msmz_alloc_scalars(self._c._ctx, B * N, C.byref(h)), "msmz_alloc_scalars")
-        dst = DeviceArray(self._c, h.value, B * N, "scalars")
+        dst = _resident(self._c, "scalars", B * N, "msmz_alloc_scalars", B * N)
         try:
             for k, v in enumerate(vecs):
                 if isinstance(v, DeviceArray):
@@ -357,10 +339,10 @@ class _Parallel:
                         raise ValueError(f"msmBatch: vector {k} is not a resident array of >= {N} scalars of this curve")
                     # resident -> resident: the scalars travel as 32-byte canonical records through the host
                     buf = C.create_string_buffer(32 * N)
-                    check(lib().msmz_download_scalars(self._c._ctx, v.handle, 0, N, buf), "msmz_download_scalars")
+                    _check(lib().msmz_download_scalars(self._c._ctx, v.handle, 0, N, buf), "msmz_download_scalars")
                     src = MsmzSrc(C.cast(buf, C.c_void_p), 0, 32, 0, None, None)
-                    check(lib().msmz_import_scalars_into(self._c._ctx, dst.handle, k * N, C.byref(src), N),
-                          "msmz_import_scalars_into")
+                    _check(lib().msmz_import_scalars_into(self._c._ctx, dst.handle, k * N, C.byref(src), N),
+                           "msmz_import_scalars_into")
                 else:
                     if len(v) < N:
                         raise ValueError(f"msmBatch: vector {k} holds {len(v)} scalars, fewer than N = {N}")
@@ -391,35 +373,21 @@ class _Parallel:
         array's `info` dict."""
         options = dict(options or {})
         c, glv, factor = precompute_args(points, N, options, factor)
-        opts = MsmzOpts()
-        opts.c = c
-        opts.glv = glv
-        opts.reserved[1] = scalar_bits_arg(options, "precomputePoints")
-        h = C.c_uint64()
-        check(lib().msmz_precompute_points(self._c._ctx, points.handle, N, C.byref(opts), factor, C.byref(h)),
-              "msmz_precompute_points")
-        arr = DeviceArray(self._c, h.value, N, "precomputed")
+        # only c, glv and the bit bound reach the library: the MSM-only fields stay 0, whatever `options` holds
+        opts = msm_opts({"c": c, "glv": glv, "scalarBits": options.get("scalarBits")}, "precomputePoints", glv, safe=0, buckets=0)
+        arr = _resident(self._c, "precomputed", N, "msmz_precompute_points", points.handle, N, C.byref(opts), factor)
         vals = [C.c_int32(), C.c_int32(), C.c_uint32(), C.c_uint32(), C.c_uint64()]
-        check(lib().msmz_precomputed_info(self._c._ctx, h.value, *[C.byref(v) for v in vals]), "msmz_precomputed_info")
+        _check(lib().msmz_precomputed_info(self._c._ctx, arr.handle, *[C.byref(v) for v in vals]), "msmz_precomputed_info")
         arr.info = dict(zip(("c", "glv", "factor", "K", "records"), (v.value for v in vals)))
         bits = C.c_int32()
-        check(lib().msmz_precomputed_scalar_bits(self._c._ctx, h.value, C.byref(bits)), "msmz_precomputed_scalar_bits")
+        _check(lib().msmz_precomputed_scalar_bits(self._c._ctx, arr.handle, C.byref(bits)), "msmz_precomputed_scalar_bits")
         arr.info["scalarBits"] = bits.value
         return arr
 
     # -- the MSM --------------------------------------------------------------------------------
     def _msm(self, scalars, points, N, verbose, options, safe, buckets):
-        options = dict(options or {})
-        opts = MsmzOpts()
-        opts.c = int(options.get("c") or 0)
-        opts.glv = int(options.get("glv", self._c.default_glv))
-        opts.safe = int(options.get("useSafeAdditions", safe))
-        opts.buckets = buckets
-        opts.timing = 1 if verbose else 0
-        opts.reserved[0] = int(options.get("reduceAffine", 0))   # 1: batched-affine first reduction level (reduceBucketsAffine)
-        opts.reserved[1] = scalar_bits_arg(options, "msm")       # every scalar is below 2^scalarBits (0: no bound)
-        fb = self._c.fe_bytes
-        out = C.create_string_buffer(2 * fb)
+        opts = msm_opts(dict(options or {}), "msm", self._c.default_glv, safe, buckets, 1 if verbose else 0)
+        out = C.create_string_buffer(2 * self._c.fe_bytes)
         inf = C.c_int()
         log = MsmzLog()
         if N <= 0 or N > len(points):
@@ -432,13 +400,8 @@ class _Parallel:
         else:
             st = lib().msmz_msm(self._c._ctx, points.handle, bytes(scalars), N, C.byref(opts), out, C.byref(inf),
                                 C.byref(log))
-        check(st, "msmz_msm")
-        raw = out.raw
-        result = {"x": int.from_bytes(raw[:fb], "little"), "y": int.from_bytes(raw[fb:], "little"),
-                  "isZero": inf.value != 0}
-        if result["isZero"] and self._c.kind == "weierstrass":
-            result["x"], result["y"] = 0, 1   # bigint/projective-weierstrass.ts:210 toAffine of zero
-        return {"result": result, "log": _format_log(log), "stats": log}
+        _check(st, "msmz_msm")
+        return {"result": self._c._point(out.raw, 0, inf.value != 0), "log": _format_log(log), "stats": log}
 
     def msm(self, scalars, points, N, verbose=False, options=None):
         """Safe additions (msm-batched-affine.ts:74-328 with useSafeAdditions = true)."""
@@ -468,33 +431,23 @@ class _Parallel:
 
     def _msm_batch_run(self, scalarsList, points, N, options, safe):
         kind, data, B = batch_scalars(scalarsList, N, options.get("batch"))
-        opts = MsmzOpts()
-        opts.c = int(options.get("c") or 0)
-        opts.glv = int(options.get("glv", self._c.default_glv))
-        opts.safe = int(options.get("useSafeAdditions", safe))
-        opts.buckets = int(options.get("buckets", 0))
-        opts.reserved[0] = int(options.get("reduceAffine", 0))
-        opts.reserved[1] = scalar_bits_arg(options, "msmBatch")
-        fb = self._c.fe_bytes
-        out = C.create_string_buffer(2 * fb * B)
+        opts = msm_opts(options, "msmBatch", self._c.default_glv, safe)
+        if kind == "resident":
+            return self._many(B, "msmz_msm_batch", lambda *res: lib().msmz_msm_batch_resident(
+                self._c._ctx, points.handle, data.handle, N, B, C.byref(opts), *res))
+        return self._many(B, "msmz_msm_batch", lambda *res: lib().msmz_msm_batch(
+            self._c._ctx, points.handle, data, N, B, C.byref(opts), *res))
+
+    def _many(self, B, name, call):
+        """the tail of msmBatch and msmSegments: `call(out, is_inf, log)` is the library call -> its B results; the log of
+        the call is left in `lastBatchLog`"""
+        out = C.create_string_buffer(2 * self._c.fe_bytes * B)
         inf = (C.c_int * B)()
         log = MsmzLog()
-        if kind == "resident":
-            st = lib().msmz_msm_batch_resident(self._c._ctx, points.handle, data.handle, N, B, C.byref(opts), out, inf,
-                                               C.byref(log))
-        else:
-            st = lib().msmz_msm_batch(self._c._ctx, points.handle, data, N, B, C.byref(opts), out, inf, C.byref(log))
-        check(st, "msmz_msm_batch")
+        _check(call(out, inf, C.byref(log)), name)
         self.lastBatchLog = log
         raw = out.raw
-        results = []
-        for k in range(B):
-            r = {"x": int.from_bytes(raw[2 * fb * k:2 * fb * k + fb], "little"),
-                 "y": int.from_bytes(raw[2 * fb * k + fb:2 * fb * (k + 1)], "little"), "isZero": inf[k] != 0}
-            if r["isZero"] and self._c.kind == "weierstrass":
-                r["x"], r["y"] = 0, 1
-            results.append(r)
-        return results
+        return [self._c._point(raw, k, inf[k] != 0) for k in range(B)]
 
     def msmBatch(self, scalarsList, points, N, options=None):
         """B MSMs over the first N points in one device pipeline (msmz_msm_batch): `scalarsList` is ONE resident
@@ -513,29 +466,9 @@ class _Parallel:
         segs = msm_segments_args(scalars, points, segments)
         B = len(segs)
         table = (MsmzSegment * B)(*[MsmzSegment(p, s, n) for p, s, n in segs])
-        opts = MsmzOpts()
-        opts.c = int(options.get("c") or 0)
-        opts.glv = int(options.get("glv", self._c.default_glv))
-        opts.safe = int(options.get("useSafeAdditions", safe))
-        opts.buckets = int(options.get("buckets", 0))
-        opts.reserved[0] = int(options.get("reduceAffine", 0))
-        opts.reserved[1] = scalar_bits_arg(options, "msmSegments")
-        fb = self._c.fe_bytes
-        out = C.create_string_buffer(2 * fb * B)
-        inf = (C.c_int * B)()
-        log = MsmzLog()
-        check(lib().msmz_msm_segments(self._c._ctx, points.handle, scalars.handle, table, B, C.byref(opts), out, inf,
-                                      C.byref(log)), "msmz_msm_segments")
-        self.lastBatchLog = log
-        raw = out.raw
-        results = []
-        for k in range(B):
-            r = {"x": int.from_bytes(raw[2 * fb * k:2 * fb * k + fb], "little"),
-                 "y": int.from_bytes(raw[2 * fb * k + fb:2 * fb * (k + 1)], "little"), "isZero": inf[k] != 0}
-            if r["isZero"] and self._c.kind == "weierstrass":
-                r["x"], r["y"] = 0, 1
-            results.append(r)
-        return results
+        opts = msm_opts(options, "msmSegments", self._c.default_glv, safe)
+        return self._many(B, "msmz_msm_segments", lambda *res: lib().msmz_msm_segments(
+            self._c._ctx, points.handle, scalars.handle, table, B, C.byref(opts), *res))
 
     def msmSegments(self, scalars, points, segments, options=None):
         """One MSM per segment (msmz_msm_segments): `segments` is a sequence of (firstPoint, firstScalar, N), result k =
@@ -569,14 +502,14 @@ class CheckResult:
 
 def check_points_args(points, N, subgroup, first):
     """Arguments of checkPoints -> (first, N, what), checked before anything reaches the device."""
-    if not isinstance(points, DeviceArray) or points.kind != "points":
+    if not _is_array(points, "points"):
         raise TypeError("checkPoints: `points` is a resident point array (pointsFromBytes / randomPointsFast); a "
                         "precomputed array is derived data: check the set it was made from")
-    if isinstance(first, bool) or not isinstance(first, int) or not 0 <= first < len(points):
+    if not _is_int(first) or not 0 <= first < len(points):
         raise ValueError(f"checkPoints: first = {first!r} but the point set holds {len(points)}")
     if N is None:
         N = len(points) - first
-    if isinstance(N, bool) or not isinstance(N, int) or not 1 <= N <= len(points) - first:
+    if not _is_int(N) or not 1 <= N <= len(points) - first:
         raise ValueError(f"checkPoints: points [{first}, +{N!r}) of a set of {len(points)}")
     what = _native.MSMZ_CHECK_CURVE | (_native.MSMZ_CHECK_SUBGROUP if subgroup else 0)
     return first, N, what
@@ -585,32 +518,18 @@ def check_points_args(points, N, subgroup, first):
 def mul_points_args(scalars, points, N, addend, firstPoint, firstScalar, firstAddend, order):
     """Arguments of mulPoints -> dict(N, firstPoint, firstScalar, firstAddend, scalar), checked before anything reaches
     the device.  scalar: the 32 little-endian bytes of a broadcast scalar, None for a resident scalar array."""
-    if not isinstance(points, DeviceArray) or points.kind != "points":
+    if not _is_array(points, "points"):
         raise TypeError("mulPoints: `points` is a resident point array (pointsFromBytes / randomPointsFast); a "
                         "precomputed array is derived data")
-    if addend is not None and (not isinstance(addend, DeviceArray) or addend.kind != "points"):
+    if addend is not None and not _is_array(addend, "points"):
         raise TypeError("mulPoints: `addend` is a resident point array or None")
-    broadcast = isinstance(scalars, int) and not isinstance(scalars, bool)
-    if not broadcast and (not isinstance(scalars, DeviceArray) or scalars.kind != "scalars"):
+    broadcast = _is_int(scalars)
+    if not broadcast and not _is_array(scalars, "scalars"):
         raise TypeError("mulPoints: `scalars` is a resident scalar array or an int (one scalar for every point)")
     if broadcast and not 0 <= scalars < order:
         raise ValueError(f"mulPoints: the scalar {scalars} is not in [0, group order)")
-    firsts = {"firstPoint": (firstPoint, points), "firstScalar": (firstScalar, None if broadcast else scalars),
-              "firstAddend": (firstAddend, addend)}
-    for name, (first, arr) in firsts.items():
-        if isinstance(first, bool) or not isinstance(first, int) or first < 0:
-            raise ValueError(f"mulPoints: {name} = {first!r}")
-        if arr is None and first != 0:
-            raise ValueError(f"mulPoints: {name} = {first} without the array it indexes")
-        if arr is not None and first >= len(arr):
-            raise ValueError(f"mulPoints: {name} = {first} but the array holds {len(arr)}")
-    if N is None:
-        N = min(len(arr) - first for first, arr in firsts.values() if arr is not None)
-    if isinstance(N, bool) or not isinstance(N, int) or N < 1:
-        raise ValueError(f"mulPoints: N = {N!r}")
-    for name, (first, arr) in firsts.items():
-        if arr is not None and N > len(arr) - first:
-            raise ValueError(f"mulPoints: entries [{first}, +{N}) of {name[5:].lower()}s that hold {len(arr)}")
+    N = _ranges("mulPoints", [("firstPoint", firstPoint, points), ("firstScalar", firstScalar, None if broadcast else scalars),
+                              ("firstAddend", firstAddend, addend)], N, limit=None)
     return {"N": N, "firstPoint": firstPoint, "firstScalar": firstScalar, "firstAddend": firstAddend,
             "scalar": scalars.to_bytes(32, "little") if broadcast else None}
 
@@ -618,9 +537,9 @@ def mul_points_args(scalars, points, N, addend, firstPoint, firstScalar, firstAd
 def msm_segments_args(scalars, points, segments):
     """Arguments of msmSegments -> [(firstPoint, firstScalar, N), ...] as ints, checked before anything reaches the
     device."""
-    if not isinstance(points, DeviceArray) or points.kind not in ("points", "precomputed"):
+    if not _is_array(points, "points", "precomputed"):
         raise TypeError("msmSegments: `points` is a resident point array (plain or precomputed)")
-    if not isinstance(scalars, DeviceArray) or scalars.kind != "scalars":
+    if not _is_array(scalars, "scalars"):
         raise TypeError("msmSegments: `scalars` is a resident scalar array (scalarsFromBytes / scalarsFromTensor); "
                         "host scalars are uploaded first")
     if isinstance(segments, (str, bytes, bytearray, DeviceArray)) or not hasattr(segments, "__len__"):
@@ -636,7 +555,7 @@ def msm_segments_args(scalars, points, segments):
             raise TypeError(f"msmSegments: segment {k} is not (firstPoint, firstScalar, N): {seg!r}")
         firstPoint, firstScalar, N = seg
         for name, v in (("firstPoint", firstPoint), ("firstScalar", firstScalar), ("N", N)):
-            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            if not _is_int(v) or v < 0:
                 raise ValueError(f"msmSegments: segment {k}: {name} = {v!r}")
         if N < 1:
             raise ValueError(f"msmSegments: segment {k}: N = {N}")
@@ -653,7 +572,7 @@ def combine_scalars_args(a, x, b, y, N, firstX, firstY, out, firstOut, firstA, f
     or two of (array, first, coefficient array or None, its first, 32 little-endian bytes of a broadcast coefficient or
     None: a coefficient array, or the coefficient 1)."""
     def scalars(v):
-        return isinstance(v, DeviceArray) and v.kind == "scalars"
+        return _is_array(v, "scalars")
 
     if not scalars(x):
         raise TypeError(f"{who}: `x` is a resident scalar array")
@@ -669,7 +588,7 @@ def combine_scalars_args(a, x, b, y, N, firstX, firstY, out, firstOut, firstA, f
         if name == "b" and y is None:
             ranges.append((first_name, first, None))
             continue
-        if isinstance(c, int) and not isinstance(c, bool):
+        if _is_int(c):
             if not 0 <= c < order:
                 raise ValueError(f"{who}: the coefficient {name} = {c} is not in [0, group order)")
             coeffs.append((None, None if c == 1 else c.to_bytes(32, "little")))   # (1: no product at all)
@@ -679,37 +598,20 @@ def combine_scalars_args(a, x, b, y, N, firstX, firstY, out, firstOut, firstA, f
             ranges.append((first_name, first, c))
         else:
             raise TypeError(f"{who}: `{name}` is an int (one coefficient for every entry) or a resident scalar array")
-    ranges.append(("firstOut", firstOut, out))
-    for name, first, arr in ranges:
-        if isinstance(first, bool) or not isinstance(first, int) or first < 0:
-            raise ValueError(f"{who}: {name} = {first!r}")
-        if arr is None and first != 0:
-            raise ValueError(f"{who}: {name} = {first} without the array it indexes")
-        if arr is not None and first >= len(arr):
-            raise ValueError(f"{who}: {name} = {first} but the array holds {len(arr)}")
-    if N is None:
-        N = min(len(arr) - first for _, first, arr in ranges if arr is not None)
-    if isinstance(N, bool) or not isinstance(N, int) or not 1 <= N < 1 << 32:
-        raise ValueError(f"{who}: N = {N!r}")
-    for name, first, arr in ranges:
-        if arr is not None and N > len(arr) - first:
-            raise ValueError(f"{who}: entries [{first}, +{N}) from {name} of an array of {len(arr)}")
-    if out is not None:
-        for name, first, arr in ranges[:-1]:
-            if arr is not None and arr.handle == out.handle and first != firstOut and abs(first - firstOut) < N:
-                raise ValueError(f"{who}: the destination [{firstOut}, +{N}) overlaps the input range [{first}, +{N}) "
-                                 f"({name}) in part; it may be that range exactly or apart from it")
+    N = _ranges(who, ranges + [("firstOut", firstOut, out)], N, out)
     terms = [(x, firstX) + (coeffs[0][0], firstA if coeffs[0][0] is not None else 0, coeffs[0][1])]
     if y is not None:
         terms.append((y, firstY) + (coeffs[1][0], firstB if coeffs[1][0] is not None else 0, coeffs[1][1]))
     return {"N": N, "firstOut": firstOut, "terms": terms}
 
 
-def _scan_ranges(who, ranges, N, out, firstOut):
-    """the shared range checks of scalarRecurrence and invertScalars: ranges = [(name, first, array or None)], the last
-    one the destination -> N"""
+def _ranges(who, ranges, N, out=None, limit=1 << 32):
+    """The range checks of every operation over resident arrays: ranges = [(name, first, array or None)] -> N (None: what
+    the shortest array leaves).  Every `first` is an index of its array, and 0 without one; 1 <= N < limit (None: no
+    bound) fits every array from its `first`.  With `out` the last range is the destination: it may be an input's range
+    exactly or apart from it, never overlap it in part."""
     for name, first, arr in ranges:
-        if isinstance(first, bool) or not isinstance(first, int) or first < 0:
+        if not _is_int(first) or first < 0:
             raise ValueError(f"{who}: {name} = {first!r}")
         if arr is None and first != 0:
             raise ValueError(f"{who}: {name} = {first} without the array it indexes")
@@ -717,12 +619,13 @@ def _scan_ranges(who, ranges, N, out, firstOut):
             raise ValueError(f"{who}: {name} = {first} but the array holds {len(arr)}")
     if N is None:
         N = min(len(arr) - first for _, first, arr in ranges if arr is not None)
-    if isinstance(N, bool) or not isinstance(N, int) or not 1 <= N < 1 << 32:
+    if not _is_int(N) or N < 1 or (limit is not None and N >= limit):
         raise ValueError(f"{who}: N = {N!r}")
     for name, first, arr in ranges:
         if arr is not None and N > len(arr) - first:
             raise ValueError(f"{who}: entries [{first}, +{N}) from {name} of an array of {len(arr)}")
     if out is not None:
+        firstOut = ranges[-1][1]
         for name, first, arr in ranges[:-1]:
             if arr is not None and arr.handle == out.handle and first != firstOut and abs(first - firstOut) < N:
                 raise ValueError(f"{who}: the destination [{firstOut}, +{N}) overlaps the input range [{first}, +{N}) "
@@ -735,9 +638,9 @@ def scalar_recurrence_args(a, b, N, init, reverse, exclusive, firstA, firstB, ou
     """Arguments of scalarRecurrence -> dict(N, firstOut, aHandle, firstA, a, bHandle, firstB, init, flags), checked before
     anything reaches the device.  a / init: the 32 little-endian bytes of a broadcast value, or None."""
     def scalars(v):
-        return isinstance(v, DeviceArray) and v.kind == "scalars"
+        return _is_array(v, "scalars")
 
-    broadcast = isinstance(a, int) and not isinstance(a, bool)
+    broadcast = _is_int(a)
     if a is not None and not broadcast and not scalars(a):
         raise TypeError(f"{who}: `a` is a resident scalar array, an int (one multiplier for every entry) or None (1)")
     if b is not None and not scalars(b):
@@ -746,7 +649,7 @@ def scalar_recurrence_args(a, b, N, init, reverse, exclusive, firstA, firstB, ou
         raise TypeError(f"{who}: neither a multiplier nor an addend: nothing to do")
     if out is not None and not scalars(out):
         raise TypeError(f"{who}: `out` is a resident scalar array or None")
-    if init is not None and (isinstance(init, bool) or not isinstance(init, int)):
+    if init is not None and not _is_int(init):
         raise TypeError(f"{who}: `init` is an int or None")
     for name, v in (("reverse", reverse), ("exclusive", exclusive)):
         if not isinstance(v, bool):
@@ -757,7 +660,7 @@ def scalar_recurrence_args(a, b, N, init, reverse, exclusive, firstA, firstB, ou
     ranges = [("firstA", firstA, a if scalars(a) else None), ("firstB", firstB, b), ("firstOut", firstOut, out)]
     if N is None and not scalars(a) and b is None and out is None:
         raise ValueError(f"{who}: N is needed when no array gives the length")
-    N = _scan_ranges(who, ranges, N, out, firstOut)
+    N = _ranges(who, ranges, N, out)
     return {"N": N, "firstOut": firstOut, "aHandle": a.handle if scalars(a) else 0, "firstA": firstA,
             "a": a.to_bytes(32, "little") if broadcast else None, "bHandle": 0 if b is None else b.handle,
             "firstB": firstB, "init": None if init is None else init.to_bytes(32, "little"),
@@ -766,11 +669,11 @@ def scalar_recurrence_args(a, b, N, init, reverse, exclusive, firstA, firstB, ou
 
 def invert_scalars_args(x, N, first, out, firstOut, who="invertScalars"):
     """Arguments of invertScalars -> dict(N, first, firstOut), checked before anything reaches the device."""
-    if not isinstance(x, DeviceArray) or x.kind != "scalars":
+    if not _is_array(x, "scalars"):
         raise TypeError(f"{who}: `x` is a resident scalar array")
-    if out is not None and (not isinstance(out, DeviceArray) or out.kind != "scalars"):
+    if out is not None and not _is_array(out, "scalars"):
         raise TypeError(f"{who}: `out` is a resident scalar array or None")
-    N = _scan_ranges(who, [("first", first, x), ("firstOut", firstOut, out)], N, out, firstOut)
+    N = _ranges(who, [("first", first, x), ("firstOut", firstOut, out)], N, out)
     return {"N": N, "first": first, "firstOut": firstOut}
 
 
@@ -787,11 +690,11 @@ def check_arg(check, who):
 
 def precompute_args(points, N, options, factor):
     """Arguments of precomputePoints -> (c, glv, factor), checked before anything reaches the device."""
-    if not isinstance(points, DeviceArray) or points.kind != "points":
+    if not _is_array(points, "points"):
         raise TypeError("precomputePoints: `points` is a resident point array (pointsFromBytes / randomPointsFast)")
-    if isinstance(N, bool) or not isinstance(N, int) or not 1 <= N <= len(points):
+    if not _is_int(N) or not 1 <= N <= len(points):
         raise ValueError(f"precomputePoints: N = {N!r} but the point set holds {len(points)}")
-    if isinstance(factor, bool) or not isinstance(factor, int) or factor < 0 or factor == 1 or factor >= 2 ** 32:
+    if not _is_int(factor) or factor < 0 or factor == 1 or factor >= 2 ** 32:
         raise ValueError(f"precomputePoints: factor = {factor!r} (0 = all windows, or 2, 3, ...)")
     c = int(options.get("c") or 0)
     glv = int(options.get("glv", -1))
@@ -803,6 +706,21 @@ def precompute_args(points, N, options, factor):
     return c, glv, factor
 
 
+def msm_opts(options, who, glv, safe, buckets=None, timing=0):
+    """`options` of an MSM call -> msmz_opts.  glv, safe: what holds without options["glv"] / ["useSafeAdditions"];
+    buckets: None takes options["buckets"]; reserved[0] = reduceAffine (1: batched-affine first reduction level,
+    reduceBucketsAffine), reserved[1] = scalarBits (every scalar is below 2^scalarBits; 0: no bound)."""
+    opts = MsmzOpts()
+    opts.c = int(options.get("c") or 0)
+    opts.glv = int(options.get("glv", glv))
+    opts.safe = int(options.get("useSafeAdditions", safe))
+    opts.buckets = int(options.get("buckets", 0)) if buckets is None else buckets
+    opts.timing = timing
+    opts.reserved[0] = int(options.get("reduceAffine", 0))
+    opts.reserved[1] = scalar_bits_arg(options, who)
+    return opts
+
+
 def scalar_bits_arg(options, who):
     """options["scalarBits"] -> msmz_opts.reserved[1]: "every scalar of this call is below 2^scalarBits".  0 / absent = no
     bound; a value of at least the scalar field's bit length means the same; the window count follows the bound, and a
@@ -810,14 +728,14 @@ def scalar_bits_arg(options, who):
     bits = options.get("scalarBits")
     if bits is None:
         return 0
-    if isinstance(bits, bool) or not isinstance(bits, int) or not 0 <= bits <= 256:
+    if not _is_int(bits) or not 0 <= bits <= 256:
         raise ValueError(f"{who}: scalarBits = {bits!r} (0 = no bound, or 1..256)")
     return bits
 
 
 def scalar_width_arg(width, montgomery, who):
     """bytes per imported scalar record: 4..32, a multiple of 4; Montgomery records are 32 bytes"""
-    if isinstance(width, bool) or not isinstance(width, int) or not 4 <= width <= 32 or width % 4:
+    if not _is_int(width) or not 4 <= width <= 32 or width % 4:
         raise ValueError(f"{who}: width = {width!r} (4..32 bytes, a multiple of 4)")
     if montgomery and width != 32:
         raise ValueError(f"{who}: Montgomery scalars are 32-byte records, not {width}")
@@ -942,7 +860,7 @@ class _Curve:
         ctx = C.c_void_p()
         devs = _state["devices"]
         self.devices = list(devs)
-        check(lib().msmz_create(C.byref(ctx), params["curve_id"], (C.c_int * len(devs))(*devs), len(devs)), "msmz_create")
+        _check(lib().msmz_create(C.byref(ctx), params["curve_id"], (C.c_int * len(devs))(*devs), len(devs)), "msmz_create")
         self._ctx = ctx
         self.Scalar = _Scalar(self)
         self.Affine = _Affine(self)
@@ -966,13 +884,20 @@ class _Curve:
         za, zb = bool(a.get("isZero")), bool(b.get("isZero"))
         out = C.create_string_buffer(2 * fb)
         inf = C.c_int()
-        check(lib().msmz_point_add(self.params["curve_id"], None if za else enc(a), int(za), None if zb else enc(b),
-                                   int(zb), out, C.byref(inf)), "msmz_point_add")
-        r = {"x": int.from_bytes(out.raw[:fb], "little"), "y": int.from_bytes(out.raw[fb:], "little"),
-             "isZero": inf.value != 0}
-        if r["isZero"] and self.kind == "weierstrass":
-            r["x"], r["y"] = 0, 1
-        return r
+        _check(lib().msmz_point_add(self.params["curve_id"], None if za else enc(a), int(za), None if zb else enc(b),
+                                    int(zb), out, C.byref(inf)), "msmz_point_add")
+        return self._point(out.raw, 0, inf.value != 0)
+
+    def _point(self, raw, k, is_zero, zero_rule=True):
+        """record k of `raw` (x || y, little-endian) and its infinity flag -> {"x", "y", "isZero"}.  zero_rule: the zero of
+        a Weierstrass curve reads (0, 1) (bigint/projective-weierstrass.ts:210 toAffine of zero); a downloaded input set
+        keeps the bytes it holds."""
+        fb = self.fe_bytes
+        x = int.from_bytes(raw[2 * fb * k:2 * fb * k + fb], "little")
+        y = int.from_bytes(raw[2 * fb * k + fb:2 * fb * (k + 1)], "little")
+        if is_zero and zero_rule and self.kind == "weierstrass":
+            x, y = 0, 1
+        return {"x": x, "y": y, "isZero": is_zero}
 
 
 class Weierstrass:

@@ -8,6 +8,7 @@
 #define NAPI_VERSION 6
 #include <node_api.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -23,19 +24,13 @@
   } while (0)
 
 static napi_value throw_status(napi_env env, int st, const char* where) {
-  char msg[256];
-  strcpy(msg, where);
-  strcat(msg, ": ");
-  strncat(msg, msmz_strerror(st), sizeof(msg) - strlen(msg) - 1);
-  char code[16];
-  int n = 0, v = st;
-  char tmp[16];
-  do { tmp[n++] = (char)('0' + v % 10); v /= 10; } while (v);
-  for (int i = 0; i < n; i++) code[i] = tmp[n - 1 - i];
-  code[n] = 0;
+  char msg[256], code[16];
+  snprintf(msg, sizeof(msg), "%s: %s", where, msmz_strerror(st));
+  snprintf(code, sizeof(code), "%d", st);
   napi_throw_error(env, code, msg);
   return NULL;
 }
+#define BAD_ARG(env, where) throw_status((env), MSMZ_ERR_ARG, (where))
 
 static int get_u64(napi_env env, napi_value v, uint64_t* out) {
   napi_valuetype t;
@@ -57,6 +52,43 @@ static int get_ctx(napi_env env, napi_value v, msmz_ctx** ctx) {
   return *ctx != NULL;
 }
 
+/* The arguments of a call into argv[MAX_ARGS] (those not passed read as undefined): at least `need` of them, and, with
+   `ctx`, the context in the first.  0: a short list or no context -- the caller refuses. */
+#define MAX_ARGS 12
+static int get_args(napi_env env, napi_callback_info info, size_t need, napi_value* argv, msmz_ctx** ctx) {
+  size_t argc = MAX_ARGS;
+  if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok || argc < need) return 0;
+  return ctx == NULL || get_ctx(env, argv[0], ctx);
+}
+
+/* A Buffer -> 1 and its (*data, *len); anything else -> 0 and (NULL, 0): an optional Buffer argument. */
+static int opt_buffer(napi_env env, napi_value v, void** data, size_t* len) {
+  bool isbuf = false;
+  *data = NULL; *len = 0;
+  return napi_is_buffer(env, v, &isbuf) == napi_ok && isbuf && napi_get_buffer_info(env, v, data, len) == napi_ok;
+}
+
+/* A 32-byte Buffer (a scalar, little-endian) -> *out; null / undefined -> NULL.  0 for anything else. */
+static int scalar_or_null(napi_env env, napi_value v, const uint8_t** out) {
+  void* p; size_t len; napi_valuetype t;
+  *out = NULL;
+  if (opt_buffer(env, v, &p, &len)) { *out = (const uint8_t*)p; return len == 32; }
+  return napi_typeof(env, v, &t) == napi_ok && (t == napi_null || t == napi_undefined);
+}
+
+/* ... or the handle of a resident scalar array: the coefficient of scalarsCombine, the multiplier of scalarsRecurrence,
+   the scalars of mulPoints */
+static int scalar_or_handle(napi_env env, napi_value v, const uint8_t** scalar, uint64_t* handle) {
+  return scalar_or_null(env, v, scalar) || (get_u64(env, v, handle) && *handle != 0);
+}
+
+/* The feBytes a caller passes is the library's for this context / curve, or the call is refused: the Buffers a point goes
+   into are sized from the library's number, the one the C ABI writes by. */
+static int is_fe_bytes(napi_env env, napi_value v, int fe) {
+  uint64_t fb;
+  return fe > 0 && get_u64(env, v, &fb) && fb == (uint64_t)fe;
+}
+
 static void ctx_finalize(napi_env env, void* data, void* hint) {
   (void)env; (void)hint;
   msmz_ctx** slot = (msmz_ctx**)data;
@@ -66,25 +98,25 @@ static void ctx_finalize(napi_env env, void* data, void* hint) {
 
 /* create(curveId, deviceId | [deviceIds]) -> ctx   (an array = one engine per listed GPU, startThreads(n)) */
 static napi_value Create(napi_env env, napi_callback_info info) {
-  size_t argc = 2; napi_value argv[2];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  napi_value argv[MAX_ARGS];
+  if (!get_args(env, info, 1, argv, NULL)) return BAD_ARG(env, "msmz_create");
   int32_t curve = 0, devs[MSMZ_MAX_DEVICES] = {0};
   uint32_t ndev = 1;
   NAPI_CALL(env, napi_get_value_int32(env, argv[0], &curve));
-  if (argc > 1) {
-    bool is_arr = false;
-    NAPI_CALL(env, napi_is_array(env, argv[1], &is_arr));
-    if (is_arr) {
-      NAPI_CALL(env, napi_get_array_length(env, argv[1], &ndev));
-      if (ndev < 1 || ndev > MSMZ_MAX_DEVICES) return throw_status(env, MSMZ_ERR_ARG, "msmz_create");
-      for (uint32_t i = 0; i < ndev; i++) {
-        napi_value v;
-        NAPI_CALL(env, napi_get_element(env, argv[1], i, &v));
-        NAPI_CALL(env, napi_get_value_int32(env, v, &devs[i]));
-      }
-    } else {
-      NAPI_CALL(env, napi_get_value_int32(env, argv[1], &devs[0]));
+  bool is_arr = false;
+  NAPI_CALL(env, napi_is_array(env, argv[1], &is_arr));
+  if (is_arr) {
+    NAPI_CALL(env, napi_get_array_length(env, argv[1], &ndev));
+    if (ndev < 1 || ndev > MSMZ_MAX_DEVICES) return BAD_ARG(env, "msmz_create");
+    for (uint32_t i = 0; i < ndev; i++) {
+      napi_value v;
+      NAPI_CALL(env, napi_get_element(env, argv[1], i, &v));
+      NAPI_CALL(env, napi_get_value_int32(env, v, &devs[i]));
     }
+  } else {
+    napi_valuetype t;
+    NAPI_CALL(env, napi_typeof(env, argv[1], &t));
+    if (t != napi_undefined) NAPI_CALL(env, napi_get_value_int32(env, argv[1], &devs[0]));
   }
   msmz_ctx* ctx = NULL;
   int st = msmz_create(&ctx, curve, devs, (int)ndev);
@@ -98,10 +130,9 @@ static napi_value Create(napi_env env, napi_callback_info info) {
 
 /* destroy(ctx) */
 static napi_value Destroy(napi_env env, napi_callback_info info) {
-  size_t argc = 1; napi_value argv[1];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  napi_value argv[MAX_ARGS];
   void* p = NULL;
-  if (napi_get_value_external(env, argv[0], &p) == napi_ok && p) {
+  if (get_args(env, info, 1, argv, NULL) && napi_get_value_external(env, argv[0], &p) == napi_ok && p) {
     msmz_ctx** slot = (msmz_ctx**)p;
     if (*slot) msmz_destroy(*slot);
     *slot = NULL;
@@ -115,22 +146,20 @@ static napi_value make_handle(napi_env env, uint64_t h) {
   return v;
 }
 
+/* n point records (2 * fe_bytes each) and, if given, n infinity flags are in the Buffers? */
+static int covers_points(msmz_ctx* ctx, uint64_t n, size_t xylen, const void* inf, size_t inflen) {
+  const int fe = msmz_ctx_fe_bytes(ctx);
+  return fe > 0 && n != 0 && xylen / (2 * (size_t)fe) >= n && (inf == NULL || inflen >= n);
+}
+
 /* uploadPoints(ctx, xyBuffer, infBufferOrNull, n) -> handle */
 static napi_value UploadPoints(napi_env env, napi_callback_info info) {
-  size_t argc = 4; napi_value argv[4];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  msmz_ctx* ctx; if (!get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "uploadPoints");
-  void* xy; size_t xylen; NAPI_CALL(env, napi_get_buffer_info(env, argv[1], &xy, &xylen));
-  void* inf = NULL; size_t inflen = 0; bool isbuf = false;
-  napi_is_buffer(env, argv[2], &isbuf);
-  if (isbuf) NAPI_CALL(env, napi_get_buffer_info(env, argv[2], &inf, &inflen));
-  uint64_t n; if (!get_u64(env, argv[3], &n)) return throw_status(env, MSMZ_ERR_ARG, "uploadPoints");
-  {
-    int fbc = msmz_ctx_fe_bytes(ctx);   /* buffers must cover n records: 2 * fe_bytes each (+ one flag byte) */
-    if (fbc <= 0 || n == 0 || xylen / (2 * (size_t)fbc) < n || (inf != NULL && inflen < n))
-      return throw_status(env, MSMZ_ERR_ARG, "uploadPoints");
-  }
-  uint64_t h = 0;
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  if (!get_args(env, info, 4, argv, &ctx)) return BAD_ARG(env, "uploadPoints");
+  void *xy, *inf; size_t xylen, inflen; uint64_t n, h = 0;
+  NAPI_CALL(env, napi_get_buffer_info(env, argv[1], &xy, &xylen));
+  opt_buffer(env, argv[2], &inf, &inflen);
+  if (!get_u64(env, argv[3], &n) || !covers_points(ctx, n, xylen, inf, inflen)) return BAD_ARG(env, "uploadPoints");
   int st = msmz_upload_points(ctx, (const uint8_t*)xy, (const uint8_t*)inf, n, &h);
   if (st) return throw_status(env, st, "msmz_upload_points");
   return make_handle(env, h);
@@ -138,12 +167,11 @@ static napi_value UploadPoints(napi_env env, napi_callback_info info) {
 
 /* uploadScalars(ctx, buffer, n) -> handle */
 static napi_value UploadScalars(napi_env env, napi_callback_info info) {
-  size_t argc = 3; napi_value argv[3];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  msmz_ctx* ctx; if (!get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "uploadScalars");
-  void* s; size_t slen; NAPI_CALL(env, napi_get_buffer_info(env, argv[1], &s, &slen));
-  uint64_t n; if (!get_u64(env, argv[2], &n) || slen < 32 * n) return throw_status(env, MSMZ_ERR_ARG, "uploadScalars");
-  uint64_t h = 0;
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  if (!get_args(env, info, 3, argv, &ctx)) return BAD_ARG(env, "uploadScalars");
+  void* s; size_t slen; uint64_t n, h = 0;
+  NAPI_CALL(env, napi_get_buffer_info(env, argv[1], &s, &slen));
+  if (!get_u64(env, argv[2], &n) || slen < 32 * n) return BAD_ARG(env, "uploadScalars");
   int st = msmz_upload_scalars(ctx, (const uint8_t*)s, n, &h);
   if (st) return throw_status(env, st, "msmz_upload_scalars");
   return make_handle(env, h);
@@ -152,16 +180,14 @@ static napi_value UploadScalars(napi_env env, napi_callback_info info) {
 /* importScalars(ctx, buffer, n, width, montgomery) -> handle: host records of `width` bytes, optionally 64-bit-limb
  * Montgomery residues (msmz_import_scalars; N-API has no device pointers, so the host forms only) */
 static napi_value ImportScalars(napi_env env, napi_callback_info info) {
-  size_t argc = 5; napi_value argv[5];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  msmz_ctx* ctx; if (argc < 5 || !get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "importScalars");
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  if (!get_args(env, info, 5, argv, &ctx)) return BAD_ARG(env, "importScalars");
   void* s; size_t slen; NAPI_CALL(env, napi_get_buffer_info(env, argv[1], &s, &slen));
-  uint64_t n, width; bool mont = false;
+  uint64_t n, width, h = 0; bool mont = false;
   if (!get_u64(env, argv[2], &n) || !get_u64(env, argv[3], &width) || napi_get_value_bool(env, argv[4], &mont) != napi_ok ||
       width < 4 || width > 32 || n == 0 || slen / (size_t)width < n)
-    return throw_status(env, MSMZ_ERR_ARG, "importScalars");
+    return BAD_ARG(env, "importScalars");
   msmz_src src = {s, 0, (uint32_t)width, mont ? MSMZ_SRC_MONTGOMERY : 0u, NULL, NULL};
-  uint64_t h = 0;
   int st = msmz_import_scalars(ctx, &src, n, &h);
   if (st) return throw_status(env, st, "msmz_import_scalars");
   return make_handle(env, h);
@@ -169,20 +195,15 @@ static napi_value ImportScalars(napi_env env, napi_callback_info info) {
 
 /* importPoints(ctx, xyBuffer, infBufferOrNull, n, montgomery) -> handle */
 static napi_value ImportPoints(napi_env env, napi_callback_info info) {
-  size_t argc = 5; napi_value argv[5];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  msmz_ctx* ctx; if (argc < 5 || !get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "importPoints");
-  void* xy; size_t xylen; NAPI_CALL(env, napi_get_buffer_info(env, argv[1], &xy, &xylen));
-  void* inf = NULL; size_t inflen = 0; bool isbuf = false, mont = false;
-  napi_is_buffer(env, argv[2], &isbuf);
-  if (isbuf) NAPI_CALL(env, napi_get_buffer_info(env, argv[2], &inf, &inflen));
-  uint64_t n;
-  int fbc = msmz_ctx_fe_bytes(ctx);
-  if (!get_u64(env, argv[3], &n) || napi_get_value_bool(env, argv[4], &mont) != napi_ok || fbc <= 0 || n == 0 ||
-      xylen / (2 * (size_t)fbc) < n || (inf != NULL && inflen < n))
-    return throw_status(env, MSMZ_ERR_ARG, "importPoints");
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  if (!get_args(env, info, 5, argv, &ctx)) return BAD_ARG(env, "importPoints");
+  void *xy, *inf; size_t xylen, inflen; uint64_t n, h = 0; bool mont = false;
+  NAPI_CALL(env, napi_get_buffer_info(env, argv[1], &xy, &xylen));
+  opt_buffer(env, argv[2], &inf, &inflen);
+  if (!get_u64(env, argv[3], &n) || napi_get_value_bool(env, argv[4], &mont) != napi_ok ||
+      !covers_points(ctx, n, xylen, inf, inflen))
+    return BAD_ARG(env, "importPoints");
   msmz_src src = {xy, 0, 0, mont ? MSMZ_SRC_MONTGOMERY : 0u, NULL, (const uint8_t*)inf};
-  uint64_t h = 0;
   int st = msmz_import_points(ctx, &src, n, &h);
   if (st) return throw_status(env, st, "msmz_import_points");
   return make_handle(env, h);
@@ -190,12 +211,10 @@ static napi_value ImportPoints(napi_env env, napi_callback_info info) {
 
 /* randomPoints(ctx, n, seed) / randomScalars(ctx, n, seed) -> handle */
 static napi_value random_common(napi_env env, napi_callback_info info, int scalars) {
-  size_t argc = 3; napi_value argv[3];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  msmz_ctx* ctx; if (!get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "random");
-  uint64_t n, seed;
-  if (!get_u64(env, argv[1], &n) || !get_u64(env, argv[2], &seed)) return throw_status(env, MSMZ_ERR_ARG, "random");
-  uint64_t h = 0;
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  uint64_t n, seed, h = 0;
+  if (!get_args(env, info, 3, argv, &ctx) || !get_u64(env, argv[1], &n) || !get_u64(env, argv[2], &seed))
+    return BAD_ARG(env, "random");
   int st = scalars ? msmz_random_scalars(ctx, n, seed, &h) : msmz_random_points(ctx, n, seed, &h);
   if (st) return throw_status(env, st, scalars ? "msmz_random_scalars" : "msmz_random_points");
   return make_handle(env, h);
@@ -205,26 +224,23 @@ static napi_value RandomScalars(napi_env env, napi_callback_info info) { return 
 
 /* downloadPoints(ctx, handle, first, count, feBytes) -> Buffer(xy) ; downloadScalars(ctx, handle, first, count) */
 static napi_value DownloadPoints(napi_env env, napi_callback_info info) {
-  size_t argc = 5; napi_value argv[5];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  msmz_ctx* ctx; if (!get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "downloadPoints");
-  uint64_t h, first, count, fb;
-  if (!get_u64(env, argv[1], &h) || !get_u64(env, argv[2], &first) || !get_u64(env, argv[3], &count) ||
-      !get_u64(env, argv[4], &fb))
-    return throw_status(env, MSMZ_ERR_ARG, "downloadPoints");
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  uint64_t h, first, count;
+  if (!get_args(env, info, 5, argv, &ctx) || !get_u64(env, argv[1], &h) || !get_u64(env, argv[2], &first) ||
+      !get_u64(env, argv[3], &count) || !is_fe_bytes(env, argv[4], msmz_ctx_fe_bytes(ctx)))
+    return BAD_ARG(env, "downloadPoints");
   void* data; napi_value buf;
-  NAPI_CALL(env, napi_create_buffer(env, (size_t)(2 * fb * count), &data, &buf));
+  NAPI_CALL(env, napi_create_buffer(env, 2 * (size_t)msmz_ctx_fe_bytes(ctx) * (size_t)count, &data, &buf));
   int st = msmz_download_points(ctx, h, first, count, (uint8_t*)data, NULL);
   if (st) return throw_status(env, st, "msmz_download_points");
   return buf;
 }
 static napi_value DownloadScalars(napi_env env, napi_callback_info info) {
-  size_t argc = 4; napi_value argv[4];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  msmz_ctx* ctx; if (!get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "downloadScalars");
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
   uint64_t h, first, count;
-  if (!get_u64(env, argv[1], &h) || !get_u64(env, argv[2], &first) || !get_u64(env, argv[3], &count))
-    return throw_status(env, MSMZ_ERR_ARG, "downloadScalars");
+  if (!get_args(env, info, 4, argv, &ctx) || !get_u64(env, argv[1], &h) || !get_u64(env, argv[2], &first) ||
+      !get_u64(env, argv[3], &count))
+    return BAD_ARG(env, "downloadScalars");
   void* data; napi_value buf;
   NAPI_CALL(env, napi_create_buffer(env, (size_t)(32 * count), &data, &buf));
   int st = msmz_download_scalars(ctx, h, first, count, (uint8_t*)data);
@@ -233,10 +249,9 @@ static napi_value DownloadScalars(napi_env env, napi_callback_info info) {
 }
 
 static napi_value Free(napi_env env, napi_callback_info info) {
-  size_t argc = 2; napi_value argv[2];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  msmz_ctx* ctx; if (!get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "free");
-  uint64_t h; if (!get_u64(env, argv[1], &h)) return throw_status(env, MSMZ_ERR_ARG, "free");
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  uint64_t h;
+  if (!get_args(env, info, 2, argv, &ctx) || !get_u64(env, argv[1], &h)) return BAD_ARG(env, "free");
   int st = msmz_free(ctx, h);
   if (st) return throw_status(env, st, "msmz_free");
   return NULL;
@@ -255,48 +270,82 @@ static int32_t opt_i32(napi_env env, napi_value obj, const char* key) {
   return r;
 }
 
+/* {c, glv, safe, buckets, timing, reduceAffine, scalarBits} -> msmz_opts; a key that is absent, and anything that is no
+   object, leaves 0.  scalarBits: every scalar < 2^scalarBits; 0 = no bound */
+static void get_opts(napi_env env, napi_value obj, msmz_opts* o) {
+  memset(o, 0, sizeof(*o));
+  o->c = opt_i32(env, obj, "c");
+  o->glv = opt_i32(env, obj, "glv");
+  o->safe = opt_i32(env, obj, "safe");
+  o->buckets = opt_i32(env, obj, "buckets");
+  o->timing = opt_i32(env, obj, "timing");
+  o->reserved[0] = opt_i32(env, obj, "reduceAffine");
+  o->reserved[1] = opt_i32(env, obj, "scalarBits");
+}
+
 static void set_num(napi_env env, napi_value obj, const char* key, double v) {
   napi_value n; napi_create_double(env, v, &n); napi_set_named_property(env, obj, key, n);
 }
 
+/* {xy, isInf} of one point */
+static napi_value point_result(napi_env env, napi_value xy, int is_inf) {
+  napi_value res, inf;
+  NAPI_CALL(env, napi_create_object(env, &res));
+  NAPI_CALL(env, napi_get_boolean(env, is_inf != 0, &inf));
+  NAPI_CALL(env, napi_set_named_property(env, res, "xy", xy));
+  NAPI_CALL(env, napi_set_named_property(env, res, "isInf", inf));
+  return res;
+}
+
+/* The results of a call that gives `count` points: many_begin makes the Buffer for the records (count * 2 fe_bytes of
+   the context's curve) and the flag array the C ABI writes; many_results turns the call's status into the error, or
+   {xy (count records), isInf (count flags in a Buffer)}, and frees the flag array on every path.  Nothing returns
+   between the two. */
+typedef struct { napi_value xy; uint8_t* data; int* flags; uint64_t count; } many;
+static int many_begin(napi_env env, msmz_ctx* ctx, uint64_t count, many* m) {
+  void* data;
+  m->count = count;
+  m->flags = (int*)calloc((size_t)count, sizeof(int));
+  if (m->flags && napi_create_buffer(env, 2 * (size_t)msmz_ctx_fe_bytes(ctx) * (size_t)count, &data, &m->xy) == napi_ok) {
+    m->data = (uint8_t*)data;
+    return 1;
+  }
+  free(m->flags);
+  return 0;
+}
+static napi_value many_results(napi_env env, many* m, int st, const char* where) {
+  void* fdata = NULL; napi_value inf, res;
+  if (st == 0 && napi_create_buffer(env, (size_t)m->count, &fdata, &inf) == napi_ok)
+    for (uint64_t k = 0; k < m->count; k++) ((uint8_t*)fdata)[k] = m->flags[k] ? 1 : 0;
+  free(m->flags);
+  if (st) return throw_status(env, st, where);
+  if (!fdata) return BAD_ARG(env, where);
+  NAPI_CALL(env, napi_create_object(env, &res));
+  NAPI_CALL(env, napi_set_named_property(env, res, "xy", m->xy));
+  NAPI_CALL(env, napi_set_named_property(env, res, "isInf", inf));
+  return res;
+}
+
 /* msm(ctx, pointsHandle, scalars (handle number or Buffer), n, feBytes, opts) -> {xy, isInf, log} */
 static napi_value Msm(napi_env env, napi_callback_info info) {
-  size_t argc = 6; napi_value argv[6];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  msmz_ctx* ctx; if (!get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "msm");
-  uint64_t ph, n, fb;
-  if (!get_u64(env, argv[1], &ph) || !get_u64(env, argv[3], &n) || !get_u64(env, argv[4], &fb))
-    return throw_status(env, MSMZ_ERR_ARG, "msm");
-  msmz_opts o; memset(&o, 0, sizeof(o));
-  if (argc > 5) {
-    o.c = opt_i32(env, argv[5], "c");
-    o.glv = opt_i32(env, argv[5], "glv");
-    o.safe = opt_i32(env, argv[5], "safe");
-    o.buckets = opt_i32(env, argv[5], "buckets");
-    o.timing = opt_i32(env, argv[5], "timing");
-    o.reserved[0] = opt_i32(env, argv[5], "reduceAffine");
-    o.reserved[1] = opt_i32(env, argv[5], "scalarBits");   /* every scalar < 2^scalarBits; 0 = no bound */
-  }
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  uint64_t ph, n, sh = 0;
+  if (!get_args(env, info, 5, argv, &ctx) || !get_u64(env, argv[1], &ph) || !get_u64(env, argv[3], &n) ||
+      !is_fe_bytes(env, argv[4], msmz_ctx_fe_bytes(ctx)))
+    return BAD_ARG(env, "msm");
+  void* s; size_t slen;
+  const int host = opt_buffer(env, argv[2], &s, &slen);   /* a Buffer = host scalars */
+  if (host ? slen < 32 * n : !get_u64(env, argv[2], &sh)) return BAD_ARG(env, "msm");
+  msmz_opts o; get_opts(env, argv[5], &o);
   void* data; napi_value xy;
-  NAPI_CALL(env, napi_create_buffer(env, (size_t)(2 * fb), &data, &xy));
+  NAPI_CALL(env, napi_create_buffer(env, 2 * (size_t)msmz_ctx_fe_bytes(ctx), &data, &xy));
   int is_inf = 0; msmz_log log;
-  bool isbuf = false; napi_is_buffer(env, argv[2], &isbuf);
-  int st;
-  if (isbuf) {
-    void* s; size_t slen; NAPI_CALL(env, napi_get_buffer_info(env, argv[2], &s, &slen));
-    if (slen < 32 * n) return throw_status(env, MSMZ_ERR_ARG, "msm");
-    st = msmz_msm(ctx, ph, (const uint8_t*)s, n, &o, (uint8_t*)data, &is_inf, &log);
-  } else {
-    uint64_t sh; if (!get_u64(env, argv[2], &sh)) return throw_status(env, MSMZ_ERR_ARG, "msm");
-    st = msmz_msm_resident(ctx, ph, sh, n, &o, (uint8_t*)data, &is_inf, &log);
-  }
+  int st = host ? msmz_msm(ctx, ph, (const uint8_t*)s, n, &o, (uint8_t*)data, &is_inf, &log)
+                : msmz_msm_resident(ctx, ph, sh, n, &o, (uint8_t*)data, &is_inf, &log);
   if (st) return throw_status(env, st, "msmz_msm");
-  napi_value res, jlog, inf, stages, rounds;
-  NAPI_CALL(env, napi_create_object(env, &res));
+  napi_value res = point_result(env, xy, is_inf), jlog, stages, rounds;
+  if (!res) return NULL;
   NAPI_CALL(env, napi_create_object(env, &jlog));
-  napi_get_boolean(env, is_inf != 0, &inf);
-  napi_set_named_property(env, res, "xy", xy);
-  napi_set_named_property(env, res, "isInf", inf);
   static const char* names[MSMZ_N_STAGES] = {"digits", "scan", "scatter", "plan", "accumulate", "reduce", "final", "total"};
   NAPI_CALL(env, napi_create_object(env, &stages));
   for (int i = 0; i < MSMZ_N_STAGES; i++) set_num(env, stages, names[i], log.stage_ms[i]);
@@ -315,111 +364,51 @@ static napi_value Msm(napi_env env, napi_callback_info info) {
 /* msmBatch(ctx, pointsHandle, scalars (handle number of >= batch * n scalars, or one Buffer of batch vectors), n, batch,
  * feBytes, opts) -> {xy (batch records), isInf (batch flags in a Buffer)} */
 static napi_value MsmBatch(napi_env env, napi_callback_info info) {
-  size_t argc = 7; napi_value argv[7];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  msmz_ctx* ctx; if (!get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "msmBatch");
-  uint64_t ph, n, batch, fb;
-  if (argc < 6 || !get_u64(env, argv[1], &ph) || !get_u64(env, argv[3], &n) || !get_u64(env, argv[4], &batch) ||
-      !get_u64(env, argv[5], &fb) || batch == 0 || batch > 0xffffffffu || fb > 64)
-    return throw_status(env, MSMZ_ERR_ARG, "msmBatch");
-  msmz_opts o; memset(&o, 0, sizeof(o));
-  if (argc > 6) {
-    o.c = opt_i32(env, argv[6], "c");
-    o.glv = opt_i32(env, argv[6], "glv");
-    o.safe = opt_i32(env, argv[6], "safe");
-    o.buckets = opt_i32(env, argv[6], "buckets");
-    o.reserved[0] = opt_i32(env, argv[6], "reduceAffine");
-    o.reserved[1] = opt_i32(env, argv[6], "scalarBits");
-  }
-  void* data; napi_value xy;
-  NAPI_CALL(env, napi_create_buffer(env, (size_t)(2 * fb * batch), &data, &xy));
-  int* flags = (int*)calloc((size_t)batch, sizeof(int));
-  if (!flags) return throw_status(env, MSMZ_ERR_ARG, "msmBatch");
-  bool isbuf = false; napi_is_buffer(env, argv[2], &isbuf);
-  int st;
-  if (isbuf) {
-    void* s; size_t slen;
-    if (napi_get_buffer_info(env, argv[2], &s, &slen) != napi_ok || n == 0 || slen / 32 / n < batch) {
-      free(flags);
-      return throw_status(env, MSMZ_ERR_ARG, "msmBatch");
-    }
-    st = msmz_msm_batch(ctx, ph, (const uint8_t*)s, n, (uint32_t)batch, &o, (uint8_t*)data, flags, NULL);
-  } else {
-    uint64_t sh;
-    if (!get_u64(env, argv[2], &sh)) { free(flags); return throw_status(env, MSMZ_ERR_ARG, "msmBatch"); }
-    st = msmz_msm_batch_resident(ctx, ph, sh, n, (uint32_t)batch, &o, (uint8_t*)data, flags, NULL);
-  }
-  void* fdata = NULL; napi_value inf;
-  if (st == 0 && napi_create_buffer(env, (size_t)batch, &fdata, &inf) == napi_ok)
-    for (uint64_t k = 0; k < batch; k++) ((uint8_t*)fdata)[k] = flags[k] ? 1 : 0;
-  free(flags);
-  if (st) return throw_status(env, st, "msmz_msm_batch");
-  if (!fdata) return throw_status(env, MSMZ_ERR_ARG, "msmBatch");
-  napi_value res;
-  NAPI_CALL(env, napi_create_object(env, &res));
-  napi_set_named_property(env, res, "xy", xy);
-  napi_set_named_property(env, res, "isInf", inf);
-  return res;
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  uint64_t ph, n, batch, sh = 0;
+  if (!get_args(env, info, 6, argv, &ctx) || !get_u64(env, argv[1], &ph) || !get_u64(env, argv[3], &n) ||
+      !get_u64(env, argv[4], &batch) || !is_fe_bytes(env, argv[5], msmz_ctx_fe_bytes(ctx)) || batch == 0 || batch > 0xffffffffu)
+    return BAD_ARG(env, "msmBatch");
+  void* s; size_t slen;
+  const int host = opt_buffer(env, argv[2], &s, &slen);
+  if (host ? (n == 0 || slen / 32 / n < batch) : !get_u64(env, argv[2], &sh)) return BAD_ARG(env, "msmBatch");
+  msmz_opts o; get_opts(env, argv[6], &o);
+  many m;
+  if (!many_begin(env, ctx, batch, &m)) return BAD_ARG(env, "msmBatch");
+  int st = host ? msmz_msm_batch(ctx, ph, (const uint8_t*)s, n, (uint32_t)batch, &o, m.data, m.flags, NULL)
+                : msmz_msm_batch_resident(ctx, ph, sh, n, (uint32_t)batch, &o, m.data, m.flags, NULL);
+  return many_results(env, &m, st, "msmz_msm_batch");
 }
 
 /* msmSegments(ctx, pointsHandle, scalarsHandle, segs (Buffer: per segment firstPoint, firstScalar, n as three
  * little-endian uint64 = msmz_segment), count, feBytes, opts) -> {xy (count records), isInf (count flags in a Buffer)} */
 static napi_value MsmSegments(napi_env env, napi_callback_info info) {
-  size_t argc = 7; napi_value argv[7];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  msmz_ctx* ctx; if (!get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "msmSegments");
-  uint64_t ph, sh, count, fb;
-  if (argc < 6 || !get_u64(env, argv[1], &ph) || !get_u64(env, argv[2], &sh) || !get_u64(env, argv[4], &count) ||
-      !get_u64(env, argv[5], &fb) || count == 0 || count > 0xffffffffu || fb > 64)
-    return throw_status(env, MSMZ_ERR_ARG, "msmSegments");
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  uint64_t ph, sh, count;
+  if (!get_args(env, info, 6, argv, &ctx) || !get_u64(env, argv[1], &ph) || !get_u64(env, argv[2], &sh) ||
+      !get_u64(env, argv[4], &count) || !is_fe_bytes(env, argv[5], msmz_ctx_fe_bytes(ctx)) || count == 0 || count > 0xffffffffu)
+    return BAD_ARG(env, "msmSegments");
   void* sp; size_t slen;
-  if (napi_get_buffer_info(env, argv[3], &sp, &slen) != napi_ok || slen / sizeof(msmz_segment) < count)
-    return throw_status(env, MSMZ_ERR_ARG, "msmSegments");
-  msmz_opts o; memset(&o, 0, sizeof(o));
-  if (argc > 6) {
-    o.c = opt_i32(env, argv[6], "c");
-    o.glv = opt_i32(env, argv[6], "glv");
-    o.safe = opt_i32(env, argv[6], "safe");
-    o.buckets = opt_i32(env, argv[6], "buckets");
-    o.reserved[0] = opt_i32(env, argv[6], "reduceAffine");
-    o.reserved[1] = opt_i32(env, argv[6], "scalarBits");
-  }
-  void* data; napi_value xy;
-  NAPI_CALL(env, napi_create_buffer(env, (size_t)(2 * fb * count), &data, &xy));
-  int* flags = (int*)calloc((size_t)count, sizeof(int));
+  if (!opt_buffer(env, argv[3], &sp, &slen) || slen / sizeof(msmz_segment) < count) return BAD_ARG(env, "msmSegments");
+  msmz_opts o; get_opts(env, argv[6], &o);
   msmz_segment* segs = (msmz_segment*)malloc((size_t)count * sizeof(msmz_segment));   /* (a Buffer need not be aligned) */
-  if (!flags || !segs) { free(flags); free(segs); return throw_status(env, MSMZ_ERR_ARG, "msmSegments"); }
+  many m;
+  if (!segs || !many_begin(env, ctx, count, &m)) { free(segs); return BAD_ARG(env, "msmSegments"); }
   memcpy(segs, sp, (size_t)count * sizeof(msmz_segment));
-  const int st = msmz_msm_segments(ctx, ph, sh, segs, (uint32_t)count, &o, (uint8_t*)data, flags, NULL);
+  const int st = msmz_msm_segments(ctx, ph, sh, segs, (uint32_t)count, &o, m.data, m.flags, NULL);
   free(segs);
-  void* fdata = NULL; napi_value inf;
-  if (st == 0 && napi_create_buffer(env, (size_t)count, &fdata, &inf) == napi_ok)
-    for (uint64_t k = 0; k < count; k++) ((uint8_t*)fdata)[k] = flags[k] ? 1 : 0;
-  free(flags);
-  if (st) return throw_status(env, st, "msmz_msm_segments");
-  if (!fdata) return throw_status(env, MSMZ_ERR_ARG, "msmSegments");
-  napi_value res;
-  NAPI_CALL(env, napi_create_object(env, &res));
-  napi_set_named_property(env, res, "xy", xy);
-  napi_set_named_property(env, res, "isInf", inf);
-  return res;
+  return many_results(env, &m, st, "msmz_msm_segments");
 }
 
-/* pointAdd(curveId, aXy|null, bXy|null, feBytes) -> {xy, isInf}  (null = infinity) */
 /* precomputePoints(ctx, pointsHandle, n, {c, glv, scalarBits}, factor) -> handle of a precomputed point set (msmz_precompute_points;
    glv -1 = the engine's choice, factor 0 = all windows in one bucket set) */
 static napi_value PrecomputePoints(napi_env env, napi_callback_info info) {
-  size_t argc = 5; napi_value argv[5];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  msmz_ctx* ctx; if (argc < 5 || !get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "precomputePoints");
-  uint64_t ph, n, factor;
-  if (!get_u64(env, argv[1], &ph) || !get_u64(env, argv[2], &n) || !get_u64(env, argv[4], &factor) || factor > 0xffffffffu)
-    return throw_status(env, MSMZ_ERR_ARG, "precomputePoints");
-  msmz_opts o; memset(&o, 0, sizeof(o));
-  o.c = opt_i32(env, argv[3], "c");
-  o.glv = opt_i32(env, argv[3], "glv");
-  o.reserved[1] = opt_i32(env, argv[3], "scalarBits");
-  uint64_t h = 0;
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  uint64_t ph, n, factor, h = 0;
+  if (!get_args(env, info, 5, argv, &ctx) || !get_u64(env, argv[1], &ph) || !get_u64(env, argv[2], &n) ||
+      !get_u64(env, argv[4], &factor) || factor > 0xffffffffu)
+    return BAD_ARG(env, "precomputePoints");
+  msmz_opts o; get_opts(env, argv[3], &o);
   int st = msmz_precompute_points(ctx, ph, n, &o, (uint32_t)factor, &h);
   if (st) return throw_status(env, st, "msmz_precompute_points");
   return make_handle(env, h);
@@ -428,10 +417,9 @@ static napi_value PrecomputePoints(napi_env env, napi_callback_info info) {
 /* precomputedInfo(ctx, handle) -> {c, glv, factor, K, records, scalarBits} (msmz_precomputed_info,
    msmz_precomputed_scalar_bits) */
 static napi_value PrecomputedInfo(napi_env env, napi_callback_info info) {
-  size_t argc = 2; napi_value argv[2];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  msmz_ctx* ctx; if (argc < 2 || !get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "precomputedInfo");
-  uint64_t h; if (!get_u64(env, argv[1], &h)) return throw_status(env, MSMZ_ERR_ARG, "precomputedInfo");
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  uint64_t h;
+  if (!get_args(env, info, 2, argv, &ctx) || !get_u64(env, argv[1], &h)) return BAD_ARG(env, "precomputedInfo");
   int32_t c = 0, glv = 0; uint32_t factor = 0, K = 0; uint64_t records = 0;
   int st = msmz_precomputed_info(ctx, h, &c, &glv, &factor, &K, &records);
   if (st) return throw_status(env, st, "msmz_precomputed_info");
@@ -448,13 +436,11 @@ static napi_value PrecomputedInfo(napi_env env, napi_callback_info info) {
 /* checkPoints(ctx, pointsHandle, first, count, what, wantVerdicts) -> {offCurve, offSubgroup, firstBad, verdicts}
    (msmz_check_points; what: 1 = curve, 3 = curve + subgroup; firstBad -1 = none; verdicts: Buffer or null) */
 static napi_value CheckPoints(napi_env env, napi_callback_info info) {
-  size_t argc = 6; napi_value argv[6];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  msmz_ctx* ctx; if (argc < 6 || !get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "checkPoints");
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
   uint64_t h, first, count, what;
-  if (!get_u64(env, argv[1], &h) || !get_u64(env, argv[2], &first) || !get_u64(env, argv[3], &count) ||
-      !get_u64(env, argv[4], &what) || what > 0xffffffffu || count > 0xffffffffu)
-    return throw_status(env, MSMZ_ERR_ARG, "checkPoints");
+  if (!get_args(env, info, 6, argv, &ctx) || !get_u64(env, argv[1], &h) || !get_u64(env, argv[2], &first) ||
+      !get_u64(env, argv[3], &count) || !get_u64(env, argv[4], &what) || what > 0xffffffffu || count > 0xffffffffu)
+    return BAD_ARG(env, "checkPoints");
   bool want = false;
   NAPI_CALL(env, napi_get_value_bool(env, argv[5], &want));
   void* data = NULL; napi_value buf;
@@ -475,58 +461,33 @@ static napi_value CheckPoints(napi_env env, napi_callback_info info) {
    firstAddend, n) -> handle of a new point set, record i = [s_i] P_i (+ Q_i)  (msmz_points_mul; a Buffer is the one
    scalar, little-endian, for every point) */
 static napi_value MulPoints(napi_env env, napi_callback_info info) {
-  size_t argc = 8; napi_value argv[8];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  msmz_ctx* ctx; if (argc < 8 || !get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "mulPoints");
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
   msmz_mul m; memset(&m, 0, sizeof(m));
-  uint64_t n;
-  if (!get_u64(env, argv[1], &m.points_handle) || !get_u64(env, argv[2], &m.first_p) || !get_u64(env, argv[4], &m.first_s) ||
-      !get_u64(env, argv[5], &m.addend_handle) || !get_u64(env, argv[6], &m.first_q) || !get_u64(env, argv[7], &n))
-    return throw_status(env, MSMZ_ERR_ARG, "mulPoints");
-  bool isbuf = false; napi_is_buffer(env, argv[3], &isbuf);
-  if (isbuf) {
-    void* s; size_t slen;
-    if (napi_get_buffer_info(env, argv[3], &s, &slen) != napi_ok || slen != 32) return throw_status(env, MSMZ_ERR_ARG, "mulPoints");
-    m.scalar = (const uint8_t*)s;
-  } else if (!get_u64(env, argv[3], &m.scalars_handle) || m.scalars_handle == 0) {
-    return throw_status(env, MSMZ_ERR_ARG, "mulPoints");
-  }
-  uint64_t h = 0;
+  uint64_t n, h = 0;
+  if (!get_args(env, info, 8, argv, &ctx) || !get_u64(env, argv[1], &m.points_handle) || !get_u64(env, argv[2], &m.first_p) ||
+      !get_u64(env, argv[4], &m.first_s) || !get_u64(env, argv[5], &m.addend_handle) || !get_u64(env, argv[6], &m.first_q) ||
+      !get_u64(env, argv[7], &n) || !scalar_or_handle(env, argv[3], &m.scalar, &m.scalars_handle) ||
+      (!m.scalar && !m.scalars_handle))
+    return BAD_ARG(env, "mulPoints");
   int st = msmz_points_mul(ctx, &m, n, &h);
   if (st) return throw_status(env, st, "msmz_points_mul");
   return make_handle(env, h);
 }
 
-/* a coefficient argument of scalarsCombine: a 32-byte Buffer (one scalar for every entry, little-endian), null (1), or
-   the handle of a resident scalar array */
-static int get_coeff(napi_env env, napi_value v, msmz_scalar_term* t) {
-  bool isbuf = false; napi_is_buffer(env, v, &isbuf);
-  if (isbuf) {
-    void* s; size_t slen;
-    if (napi_get_buffer_info(env, v, &s, &slen) != napi_ok || slen != 32) return 0;
-    t->coeff = (const uint8_t*)s;
-    return 1;
-  }
-  napi_valuetype ty;
-  if (napi_typeof(env, v, &ty) != napi_ok) return 0;
-  if (ty == napi_null || ty == napi_undefined) return 1;
-  return get_u64(env, v, &t->coeff_handle) && t->coeff_handle != 0;
-}
-
 /* scalarsCombine(ctx, xHandle, xFirst, xCoeff, xCoeffFirst, yHandle (0 = no second term), yFirst, yCoeff, yCoeffFirst, n,
    firstOut, outHandle (0 = a new array)) -> handle of the array written: entry i = xCoeff_i x_i (+ yCoeff_i y_i)
-   (msmz_scalars_combine) */
+   (msmz_scalars_combine).  A coefficient: a 32-byte Buffer (one scalar for every entry, little-endian), null (1), or
+   the handle of a resident scalar array */
 static napi_value ScalarsCombine(napi_env env, napi_callback_info info) {
-  size_t argc = 12; napi_value argv[12];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  msmz_ctx* ctx; if (argc < 12 || !get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "scalarsCombine");
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
   msmz_scalar_term x, y; memset(&x, 0, sizeof(x)); memset(&y, 0, sizeof(y));
   uint64_t n, first_out, h = 0;
-  if (!get_u64(env, argv[1], &x.handle) || !get_u64(env, argv[2], &x.first) || !get_coeff(env, argv[3], &x) ||
-      !get_u64(env, argv[4], &x.coeff_first) || !get_u64(env, argv[5], &y.handle) || !get_u64(env, argv[6], &y.first) ||
-      !get_coeff(env, argv[7], &y) || !get_u64(env, argv[8], &y.coeff_first) || !get_u64(env, argv[9], &n) ||
-      !get_u64(env, argv[10], &first_out) || !get_u64(env, argv[11], &h))
-    return throw_status(env, MSMZ_ERR_ARG, "scalarsCombine");
+  if (!get_args(env, info, 12, argv, &ctx) || !get_u64(env, argv[1], &x.handle) || !get_u64(env, argv[2], &x.first) ||
+      !scalar_or_handle(env, argv[3], &x.coeff, &x.coeff_handle) || !get_u64(env, argv[4], &x.coeff_first) ||
+      !get_u64(env, argv[5], &y.handle) || !get_u64(env, argv[6], &y.first) ||
+      !scalar_or_handle(env, argv[7], &y.coeff, &y.coeff_handle) || !get_u64(env, argv[8], &y.coeff_first) ||
+      !get_u64(env, argv[9], &n) || !get_u64(env, argv[10], &first_out) || !get_u64(env, argv[11], &h))
+    return BAD_ARG(env, "scalarsCombine");
   int st = msmz_scalars_combine(ctx, &x, y.handle ? &y : NULL, n, first_out, &h);
   if (st) return throw_status(env, st, "msmz_scalars_combine");
   return make_handle(env, h);
@@ -535,13 +496,11 @@ static napi_value ScalarsCombine(napi_env env, napi_callback_info info) {
 /* scalarsDot(ctx, xHandle, xFirst, yHandle (0 = the plain sum of x), yFirst, n) -> 32-byte Buffer, little-endian
    (msmz_scalars_dot) */
 static napi_value ScalarsDot(napi_env env, napi_callback_info info) {
-  size_t argc = 6; napi_value argv[6];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  msmz_ctx* ctx; if (argc < 6 || !get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "scalarsDot");
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
   uint64_t xh, fx, yh, fy, n;
-  if (!get_u64(env, argv[1], &xh) || !get_u64(env, argv[2], &fx) || !get_u64(env, argv[3], &yh) || !get_u64(env, argv[4], &fy) ||
-      !get_u64(env, argv[5], &n))
-    return throw_status(env, MSMZ_ERR_ARG, "scalarsDot");
+  if (!get_args(env, info, 6, argv, &ctx) || !get_u64(env, argv[1], &xh) || !get_u64(env, argv[2], &fx) ||
+      !get_u64(env, argv[3], &yh) || !get_u64(env, argv[4], &fy) || !get_u64(env, argv[5], &n))
+    return BAD_ARG(env, "scalarsDot");
   void* data; napi_value buf;
   NAPI_CALL(env, napi_create_buffer(env, 32, &data, &buf));
   int st = msmz_scalars_dot(ctx, xh, fx, yh, fy, n, (uint8_t*)data);
@@ -552,43 +511,29 @@ static napi_value ScalarsDot(napi_env env, napi_callback_info info) {
 /* scalarsPowers(ctx, base (32-byte Buffer or null = 1), ratio (32-byte Buffer), n) -> handle of a new scalar array, entry
    i = base ratio^i (msmz_scalars_powers) */
 static napi_value ScalarsPowers(napi_env env, napi_callback_info info) {
-  size_t argc = 4; napi_value argv[4];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  msmz_ctx* ctx; if (argc < 4 || !get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "scalarsPowers");
-  msmz_scalar_term base, ratio; memset(&base, 0, sizeof(base)); memset(&ratio, 0, sizeof(ratio));
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  const uint8_t *base, *ratio;
   uint64_t n, h = 0;
-  if (!get_coeff(env, argv[1], &base) || base.coeff_handle || !get_coeff(env, argv[2], &ratio) || !ratio.coeff ||
-      !get_u64(env, argv[3], &n))
-    return throw_status(env, MSMZ_ERR_ARG, "scalarsPowers");
-  int st = msmz_scalars_powers(ctx, base.coeff, ratio.coeff, n, &h);
+  if (!get_args(env, info, 4, argv, &ctx) || !scalar_or_null(env, argv[1], &base) || !scalar_or_null(env, argv[2], &ratio) ||
+      !ratio || !get_u64(env, argv[3], &n))
+    return BAD_ARG(env, "scalarsPowers");
+  int st = msmz_scalars_powers(ctx, base, ratio, n, &h);
   if (st) return throw_status(env, st, "msmz_scalars_powers");
   return make_handle(env, h);
-}
-
-/* a 32-byte Buffer (a scalar, little-endian) -> *out, null / undefined -> NULL */
-static int get_scalar_or_null(napi_env env, napi_value v, const uint8_t** out) {
-  msmz_scalar_term t; memset(&t, 0, sizeof(t));
-  if (!get_coeff(env, v, &t) || t.coeff_handle) return 0;
-  *out = t.coeff;
-  return 1;
 }
 
 /* scalarsRecurrence(ctx, a (handle, 32-byte Buffer = one multiplier for every entry, or null = 1), aFirst, bHandle (0 = no
    addend), bFirst, init (32-byte Buffer or null), flags (1 = reverse, 2 = exclusive), n, firstOut, outHandle (0 = a new
    array)) -> {handle, last}: the array written and the final value as a 32-byte Buffer  (msmz_scalars_recurrence) */
 static napi_value ScalarsRecurrence(napi_env env, napi_callback_info info) {
-  size_t argc = 10; napi_value argv[10];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  msmz_ctx* ctx; if (argc < 10 || !get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "scalarsRecurrence");
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
   msmz_scalar_rec r; memset(&r, 0, sizeof(r));
-  msmz_scalar_term a; memset(&a, 0, sizeof(a));
   uint64_t flags, n, first_out, h = 0;
-  if (!get_coeff(env, argv[1], &a) || !get_u64(env, argv[2], &r.a_first) || !get_u64(env, argv[3], &r.b_handle) ||
-      !get_u64(env, argv[4], &r.b_first) || !get_scalar_or_null(env, argv[5], &r.init) || !get_u64(env, argv[6], &flags) ||
-      flags >> 32 || !get_u64(env, argv[7], &n) || !get_u64(env, argv[8], &first_out) || !get_u64(env, argv[9], &h))
-    return throw_status(env, MSMZ_ERR_ARG, "scalarsRecurrence");
-  r.a_handle = a.coeff_handle;
-  r.a = a.coeff;
+  if (!get_args(env, info, 10, argv, &ctx) || !scalar_or_handle(env, argv[1], &r.a, &r.a_handle) ||
+      !get_u64(env, argv[2], &r.a_first) || !get_u64(env, argv[3], &r.b_handle) || !get_u64(env, argv[4], &r.b_first) ||
+      !scalar_or_null(env, argv[5], &r.init) || !get_u64(env, argv[6], &flags) || flags >> 32 ||
+      !get_u64(env, argv[7], &n) || !get_u64(env, argv[8], &first_out) || !get_u64(env, argv[9], &h))
+    return BAD_ARG(env, "scalarsRecurrence");
   r.flags = (uint32_t)flags;
   void* data; napi_value last, res;
   NAPI_CALL(env, napi_create_buffer(env, 32, &data, &last));
@@ -603,49 +548,44 @@ static napi_value ScalarsRecurrence(napi_env env, napi_callback_info info) {
 /* scalarsInverse(ctx, handle, first, n, firstOut, outHandle (0 = a new array)) -> {handle, zeros}: the array written,
    entry i = x_i^-1 (0 -> 0), and the number of zero entries  (msmz_scalars_inverse) */
 static napi_value ScalarsInverse(napi_env env, napi_callback_info info) {
-  size_t argc = 6; napi_value argv[6];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  msmz_ctx* ctx; if (argc < 6 || !get_ctx(env, argv[0], &ctx)) return throw_status(env, MSMZ_ERR_ARG, "scalarsInverse");
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
   uint64_t xh, first, n, first_out, h = 0, zeros = 0;
-  if (!get_u64(env, argv[1], &xh) || !get_u64(env, argv[2], &first) || !get_u64(env, argv[3], &n) ||
-      !get_u64(env, argv[4], &first_out) || !get_u64(env, argv[5], &h))
-    return throw_status(env, MSMZ_ERR_ARG, "scalarsInverse");
+  if (!get_args(env, info, 6, argv, &ctx) || !get_u64(env, argv[1], &xh) || !get_u64(env, argv[2], &first) ||
+      !get_u64(env, argv[3], &n) || !get_u64(env, argv[4], &first_out) || !get_u64(env, argv[5], &h))
+    return BAD_ARG(env, "scalarsInverse");
   int st = msmz_scalars_inverse(ctx, xh, first, n, first_out, &h, &zeros);
   if (st) return throw_status(env, st, "msmz_scalars_inverse");
-  napi_value res, z;
+  napi_value res;
   NAPI_CALL(env, napi_create_object(env, &res));
-  NAPI_CALL(env, napi_create_double(env, (double)zeros, &z));
   NAPI_CALL(env, napi_set_named_property(env, res, "handle", make_handle(env, h)));
-  NAPI_CALL(env, napi_set_named_property(env, res, "zeros", z));
+  set_num(env, res, "zeros", (double)zeros);
   return res;
 }
 
+/* pointAdd(curveId, aXy|null, bXy|null, feBytes) -> {xy, isInf}  (null = infinity).  Refused: a curve id the library does
+   not know, a feBytes that is not that curve's, an input Buffer shorter than the 2 * fe_bytes the library reads */
 static napi_value PointAdd(napi_env env, napi_callback_info info) {
-  size_t argc = 4; napi_value argv[4];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  int32_t curve; NAPI_CALL(env, napi_get_value_int32(env, argv[0], &curve));
-  uint64_t fb; if (!get_u64(env, argv[3], &fb)) return throw_status(env, MSMZ_ERR_ARG, "pointAdd");
-  void *a = NULL, *b = NULL; size_t la, lb; bool ia = false, ib = false;
-  napi_is_buffer(env, argv[1], &ia); napi_is_buffer(env, argv[2], &ib);
-  if (ia) NAPI_CALL(env, napi_get_buffer_info(env, argv[1], &a, &la));
-  if (ib) NAPI_CALL(env, napi_get_buffer_info(env, argv[2], &b, &lb));
+  napi_value argv[MAX_ARGS];
+  int32_t curve;
+  if (!get_args(env, info, 4, argv, NULL) || napi_get_value_int32(env, argv[0], &curve) != napi_ok ||
+      !is_fe_bytes(env, argv[3], msmz_curve_fe_bytes(curve)))
+    return BAD_ARG(env, "pointAdd");
+  const size_t rec = 2 * (size_t)msmz_curve_fe_bytes(curve);
+  void *a, *b; size_t la, lb;
+  if ((opt_buffer(env, argv[1], &a, &la) && la < rec) || (opt_buffer(env, argv[2], &b, &lb) && lb < rec))
+    return BAD_ARG(env, "pointAdd");
   void* data; napi_value xy;
-  NAPI_CALL(env, napi_create_buffer(env, (size_t)(2 * fb), &data, &xy));
+  NAPI_CALL(env, napi_create_buffer(env, rec, &data, &xy));
   int is_inf = 0;
   int st = msmz_point_add(curve, (const uint8_t*)a, a == NULL, (const uint8_t*)b, b == NULL, (uint8_t*)data, &is_inf);
   if (st) return throw_status(env, st, "msmz_point_add");
-  napi_value res, inf;
-  NAPI_CALL(env, napi_create_object(env, &res));
-  napi_get_boolean(env, is_inf != 0, &inf);
-  napi_set_named_property(env, res, "xy", xy);
-  napi_set_named_property(env, res, "isInf", inf);
-  return res;
+  return point_result(env, xy, is_inf);
 }
 
 static napi_value FeBytes(napi_env env, napi_callback_info info) {
-  size_t argc = 1; napi_value argv[1];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  int32_t curve; NAPI_CALL(env, napi_get_value_int32(env, argv[0], &curve));
+  napi_value argv[MAX_ARGS];
+  int32_t curve;
+  if (!get_args(env, info, 1, argv, NULL) || napi_get_value_int32(env, argv[0], &curve) != napi_ok) return BAD_ARG(env, "feBytes");
   napi_value v; napi_create_int32(env, msmz_curve_fe_bytes(curve), &v);
   return v;
 }
