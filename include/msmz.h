@@ -426,6 +426,53 @@ int msmz_scalars_recurrence(msmz_ctx* ctx, const msmz_scalar_rec* r, uint64_t n,
 int msmz_scalars_inverse(msmz_ctx* ctx, uint64_t handle, uint64_t first, uint64_t n, uint64_t first_out,
                          uint64_t* out_handle, uint64_t* n_zero);
 
+/* Number-theoretic transforms over resident scalar sets: a polynomial goes from coefficient
+ * form to evaluation form and back without leaving the device.
+ *
+ * msmz_scalars_ntt runs `count` transforms of length n = 2^log_n.  Input vector k is entries [first + k * n_in,
+ * first + (k + 1) * n_in) of `handle`, continued with zeros to n entries; output vector k is entries [first_out + k * n,
+ * first_out + (k + 1) * n).  Input and output are in natural order, always.
+ *   forward:  out_k = sum_i x_i (g w^k)^i            (g = 1 without MSMZ_NTT_COSET)
+ *   inverse:  x_i = g^-i n^-1 sum_k X_k w^(-i k)      (MSMZ_NTT_INVERSE; n_in must be n or 0)
+ * inverse(forward(x)) == x byte for byte.  Results are below q, like everything the scalar-set calls write.
+ * w is `root`, a primitive n-th root of unity (the host checks root^(n/2) == q - 1, for n = 1 root == 1), or with
+ * root == NULL the default root that msmz_scalars_root_of_unity returns: W^(2^(S - log_n)) with S the 2-adicity of q - 1
+ * and W = G^((q - 1) / 2^S), G = 22 (BLS12-377), 5 (Pallas), 7 (BLS12-381), 5 (ed-on-bls12-377): quadratic
+ * non-residues, believed (not verified against those libraries) to be the generators arkworks, pasta_curves and
+ * bls12_381 use; pass `root` if your stack's differs.  S = 47, 32, 32 and 1 in that order, so ed-on-bls12-377 has
+ * transforms of length 1 and 2 only.
+ *
+ * Output, in-place operation and errors follow msmz_scalars_combine.  *out_handle == 0 makes a new set of count * n
+ * entries (first_out must be 0); otherwise [first_out, first_out + count * n) of that handle is overwritten and nothing
+ * else.  The whole source range [first, first + count * n_in) and the whole destination range are disjoint, or, with
+ * n_in == n, the same range (in place); anything between is MSMZ_ERR_ARG.
+ * MSMZ_ERR_ARG before any launch: a null ctx, t or out_handle; unknown flag bits; count == 0; count * n >= 2^32;
+ * n_in > n; n_in != n with MSMZ_NTT_INVERSE; shift without MSMZ_NTT_COSET or the flag without shift; a zero shift; an
+ * unknown handle or one that is not a scalar set; a range beyond its set; first_out != 0 with a new handle; a root that
+ * is not a primitive n-th root of unity.  MSMZ_ERR_RANGE: root or shift >= q (found on the host, nothing is launched),
+ * or a resident entry >= q inside the source range (found by the first pass, which reads every addressed entry;
+ * entries outside are not read); then no handle is created, *out_handle is as it was, an in-place destination is
+ * unspecified and the context stays usable.  MSMZ_ERR_UNSUPPORTED: log_n > S; or a multi-device context -- the
+ * butterflies cross every boundary between blocks of 2^16 entries (the stance of msmz_scalars_recurrence).
+ * One host wait per call.  A transform of more than 2^10 entries goes through scratch memory of the engine, count * n
+ * entries for up to 2^16 and twice that above; it grows on demand and is kept.  The twiddle tables (about 3 sqrt(n)
+ * entries) of the last eight (log_n, root, direction) are kept too. */
+enum { MSMZ_NTT_INVERSE = 1, MSMZ_NTT_COSET = 2 };
+typedef struct msmz_ntt {
+  uint64_t handle, first;  /* input: `count` vectors of n_in entries each, vector k at first + k * n_in */
+  uint32_t log_n;          /* transform length n = 2^log_n */
+  uint32_t flags;          /* MSMZ_NTT_* */
+  uint64_t n_in;           /* entries read per vector, 1 <= n_in <= n; the rest count as 0.  0 means n.
+                              Must be n (or 0) with MSMZ_NTT_INVERSE */
+  uint32_t count;          /* number of transforms, >= 1; output vector k at first_out + k * n */
+  const uint8_t* root;     /* nullable: a primitive n-th root of unity, 32 bytes LE, < q.  NULL = the default root */
+  const uint8_t* shift;    /* MSMZ_NTT_COSET: the coset shift g != 0, 32 bytes LE, < q; must be NULL without the flag */
+} msmz_ntt;
+int msmz_scalars_ntt(msmz_ctx* ctx, const msmz_ntt* t, uint64_t first_out, uint64_t* out_handle);
+/* the default primitive 2^log_n-th root of unity of a curve's scalar field; needs no context.  MSMZ_ERR_ARG: an unknown
+ * curve or a null pointer; MSMZ_ERR_UNSUPPORTED: log_n > S */
+int msmz_scalars_root_of_unity(int curve_id, uint32_t log_n, uint8_t* out_le32);
+
 /* Host-side group addition of two canonical affine results: combines per-GPU partial sums
  * (the reference's "partition sum" step, msm-batched-affine.ts:300-307). */
 int msmz_point_add(int curve_id, const uint8_t* a_xy_le, int a_is_inf, const uint8_t* b_xy_le, int b_is_inf,

@@ -89,6 +89,14 @@ void msmz_test_scalar_dot_geometry(uint32_t* tile_elements, uint32_t* partials_p
  *   rec_pass : tile aggregates the one workgroup of the carry launch takes per pass of its loop (SREC_PASS);
  *   inv_chunk: elements that share one field inversion, one wave's share (SINV_CHUNK). */
 void msmz_test_scalar_scan_geometry(uint32_t* rec_tile, uint32_t* rec_pass, uint32_t* inv_chunk);
+/* The plan of msmz_scalars_ntt for a transform of 2^log_n entries (csrc/ntt_plan.h), so a test can size itself at the
+ * edges of the plan; neither call needs a context.
+ *   msmz_test_ntt_plan: *n_passes = the launches of the transform, stages[j] = the stages pass j runs in LDS (8 words,
+ *     zero beyond n_passes); their sum is log_n.  MSMZ_ERR_ARG: an unknown curve, a null pointer or log_n > 32;
+ *     MSMZ_ERR_UNSUPPORTED: log_n above the 2-adicity of the curve's scalar field.
+ *   msmz_test_ntt_geometry: *pass_log = the most stages one pass runs (NTT_PASS_LOG; a tile is 2^pass_log entries). */
+int msmz_test_ntt_plan(int curve_id, uint32_t log_n, uint32_t* n_passes, uint32_t* stages);
+void msmz_test_ntt_geometry(uint32_t* pass_log);
 /* out[i] = op(a[i], b[i]) for i < n; a, b, out: n * fe_bytes */
 int msmz_test_field(msmz_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out);
 /* GLV split of n 32-byte scalars: s0, s1 = magnitudes (16 bytes each), neg = 2 sign bytes per scalar

@@ -5,6 +5,11 @@ export type CurveParams = {
   generator: { x: bigint; y: bigint }; endomorphism?: { lambda: bigint; beta: bigint };
 };
 export type BigintPoint = { x: bigint; y: bigint; isZero?: boolean };
+export interface NttOptions { inverse?: boolean; shift?: bigint | null; root?: bigint | null; nIn?: number | null; count?: number;
+                              first?: number; out?: DeviceArray | null; firstOut?: number }
+/** the checked arguments of Parallel.ntt (host only) */
+export function nttArgs(x: { handle: unknown; n: number; kind: string }, logN: number, options: NttOptions | undefined, order: bigint):
+  { logN: number; flags: number; nIn: number; count: number; first: number; firstOut: number; root: bigint | null; shift: bigint | null };
 export interface DeviceArray extends Array<DeviceArray> { readonly n: number; readonly kind: "points" | "scalars" | "precomputed";
   /** precomputed point sets only (msmz_precomputed_info) */
   readonly info?: { c: number; glv: number; factor: number; K: number; records: number; scalarBits: number }; free(): void }
@@ -63,6 +68,11 @@ export interface ParallelApi {
   divideByLinear(p: DeviceArray, z: bigint, n?: number, options?: { first?: number }): Promise<[DeviceArray, bigint]>;
   /** out[firstOut + i] = x[first + i]^-1 mod the group order, 0 -> 0 -> [the array written, the number of zeros] */
   invertScalars(x: DeviceArray, n?: number, options?: { first?: number; out?: DeviceArray | null; firstOut?: number }): Promise<[DeviceArray, number]>;
+  /** `count` number-theoretic transforms of length 2^logN over resident scalar arrays, natural order in and out
+   * (msmz_scalars_ntt); returns the array written */
+  ntt(x: DeviceArray, logN: number, options?: NttOptions): Promise<DeviceArray>;
+  /** the default primitive 2^logN-th root of unity of the scalar field (msmz_scalars_root_of_unity) */
+  rootOfUnity(logN: number): bigint;
   msmBatch(scalarsList: DeviceArray | Uint8Array[], points: DeviceArray, n: number, options?: MsmOptions & { batch?: number }): Promise<BigintPoint[]>;
   msmBatchUnsafe(scalarsList: DeviceArray | Uint8Array[], points: DeviceArray, n: number, options?: MsmOptions & { batch?: number }): Promise<BigintPoint[]>;
   /** one MSM per segment [firstPoint, firstScalar, n] of one resident scalar array and one resident point array */

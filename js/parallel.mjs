@@ -87,6 +87,43 @@ function scanRanges(who, ranges, n, out = null, limit = 2 ** 32) {
   return n;
 }
 
+/** The arguments of Parallel.ntt -> {logN, flags, nIn, count, first, firstOut, root, shift}, checked before anything
+ * reaches the device (msm_zprize_amd/parallel.py ntt_args is the same function).  root / shift: a bigint or null.  Whether
+ * `root` is a primitive root of unity, and whether the field has transforms of this length, is the library's to say. */
+export function nttArgs(x, logN, { inverse = false, shift = null, root = null, nIn = null, count = 1, first = 0, out = null, firstOut = 0 } = {}, order) {
+  const who = "ntt";
+  // (anything with the three fields of a resident array will do here: Parallel.ntt asks for the real thing first)
+  const isScalars = (v) => v !== null && typeof v === "object" && v.kind === "scalars" && Number.isInteger(v.n) && v.handle !== undefined;
+  if (!isScalars(x)) throw TypeError(`${who}: \`x\` is a resident scalar array`);
+  if (out !== null && !isScalars(out)) throw TypeError(`${who}: \`out\` is a resident scalar array or null`);
+  if (typeof inverse !== "boolean") throw TypeError(`${who}: \`inverse\` is a boolean`);
+  for (const [name, v] of [["shift", shift], ["root", root]]) {
+    if (v !== null && typeof v !== "bigint") throw TypeError(`${who}: \`${name}\` is a bigint or null`);
+    if (v !== null && (v < 0n || v >= order)) throw Error(`${who}: ${name} = ${v} is not in [0, group order)`);
+  }
+  if (shift === 0n) throw Error(`${who}: the coset shift is not 0`);
+  if (!Number.isInteger(logN) || logN < 0 || logN >= 32) throw Error(`${who}: logN = ${logN} (0..31)`);
+  const n = 2 ** logN;
+  if (!Number.isInteger(count) || count < 1 || count * n >= 2 ** 32)
+    throw Error(`${who}: count = ${count} transforms of ${n} entries (1 <= count, count * n < 2^32)`);
+  if (nIn === null) nIn = n;
+  if (!Number.isInteger(nIn) || nIn < 1 || nIn > n) throw Error(`${who}: nIn = ${nIn} (1..${n})`);
+  if (inverse && nIn !== n) throw Error(`${who}: an inverse transform reads whole vectors (nIn = ${nIn}, n = ${n})`);
+  for (const [name, v, arr] of [["first", first, x], ["firstOut", firstOut, out]]) {
+    if (!Number.isInteger(v) || v < 0) throw Error(`${who}: ${name} = ${v}`);
+    if (arr === null && v !== 0) throw Error(`${who}: ${name} = ${v} without the array it indexes`);
+  }
+  if (count * nIn > x.n - first) throw Error(`${who}: entries [${first}, +${count * nIn}) of an array of ${x.n}`);
+  if (out !== null) {
+    if (count * n > out.n - firstOut) throw Error(`${who}: entries [${firstOut}, +${count * n}) of an array of ${out.n}`);
+    const same = first === firstOut && nIn === n;
+    const apart = first + count * nIn <= firstOut || firstOut + count * n <= first;
+    if (out.handle === x.handle && !same && !apart)
+      throw Error(`${who}: the destination [${firstOut}, +${count * n}) overlaps the source [${first}, +${count * nIn}) in part`);
+  }
+  return { logN, flags: (inverse ? 1 : 0) | (shift !== null ? 2 : 0), nIn, count, first, firstOut, root, shift };
+}
+
 /** A GPU-resident input array; destructures like the reference's pointer arrays: `let [ptr] = ...` */
 class DeviceArray extends Array {
   static make(curve, handle, n, kind) {
@@ -435,6 +472,26 @@ function createCurve(params, kind) {
       n = scanRanges("invertScalars", [["first", first, x], ["firstOut", firstOut, out]], n, out);
       const r = N.scalarsInverse(ctx, x.handle, first, n, firstOut, out === null ? 0 : out.handle);
       return [out === null ? DeviceArray.make(curve, r.handle, n, "scalars") : out, r.zeros];
+    },
+    /** `count` number-theoretic transforms of length n = 2^logN mod the group order, natural order in and out
+     * (include/msmz.h msmz_scalars_ntt).  Input vector k is x[first + k nIn .. first + (k + 1) nIn) continued with zeros
+     * (nIn null: n), output vector k is out[firstOut + k n .. firstOut + (k + 1) n).  Forward: out_k = sum_i x_i (g w^k)^i;
+     * inverse: x_i = g^-i n^-1 sum_k X_k w^(-i k).  `shift` is the coset shift g (a bigint, not 0n; null: 1), `root` a
+     * primitive n-th root of unity (null: rootOfUnity(logN)).  Without `out` the result is a new array of count n entries;
+     * `out` may be `x` over exactly the source range (in place, nIn = n) or apart from it.  Returns the array written. */
+    async ntt(x, logN, options = {}) {
+      if (!isScalars(x)) throw TypeError("ntt: `x` is a resident scalar array");
+      if (options.out !== undefined && options.out !== null && !isScalars(options.out)) throw TypeError("ntt: `out` is a resident scalar array or null");
+      const t = nttArgs(x, logN, options, params.order);
+      const out = options.out === undefined ? null : options.out;
+      const h = N.scalarsNtt(ctx, x.handle, t.first, t.logN, t.flags, t.nIn, t.count, t.root === null ? null : scalarBuf(t.root),
+                             t.shift === null ? null : scalarBuf(t.shift), t.firstOut, out === null ? 0 : out.handle);
+      return out === null ? DeviceArray.make(curve, h, t.count * 2 ** t.logN, "scalars") : out;
+    },
+    /** the default primitive 2^logN-th root of unity of the scalar field as a bigint (msmz_scalars_root_of_unity) */
+    rootOfUnity(logN) {
+      if (!Number.isInteger(logN) || logN < 0 || logN >= 2 ** 32) throw Error(`rootOfUnity: logN = ${logN}`);
+      return bytesToBigint(N.scalarsRootOfUnity(params.curveId, logN), 0, 32);
     },
     /** batched MSM: B scalar vectors against one point set (include/msmz.h msmz_msm_batch); safe additions */
     msmBatch: (scalarsList, points, n, options) => msmBatchCommon(scalarsList, points, n, options, 1),

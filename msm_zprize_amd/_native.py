@@ -59,6 +59,14 @@ class MsmzScalarRec(C.Structure):   # msmz_scalar_rec (include/msmz.h): y_i = a_
                 ("b_first", C.c_uint64), ("init", C.c_char_p), ("flags", C.c_uint32)]
 
 
+MSMZ_NTT_INVERSE, MSMZ_NTT_COSET = 1, 2
+
+
+class MsmzNtt(C.Structure):   # msmz_ntt (include/msmz.h): `count` transforms of length 2^log_n
+    _fields_ = [("handle", C.c_uint64), ("first", C.c_uint64), ("log_n", C.c_uint32), ("flags", C.c_uint32),
+                ("n_in", C.c_uint64), ("count", C.c_uint32), ("root", C.c_char_p), ("shift", C.c_char_p)]
+
+
 class MsmzSegment(C.Structure):   # msmz_segment (include/msmz.h): one problem of msmz_msm_segments
     _fields_ = [("first_p", C.c_uint64), ("first_s", C.c_uint64), ("n", C.c_uint64)]
 
@@ -141,6 +149,8 @@ EXPORTS = {
                                           C.POINTER(C.c_uint64), C.c_char_p]),
     "msmz_scalars_inverse": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64),
                                        C.POINTER(C.c_uint64)]),
+    "msmz_scalars_ntt": (C.c_int, [C.c_void_p, C.POINTER(MsmzNtt), C.c_uint64, C.POINTER(C.c_uint64)]),
+    "msmz_scalars_root_of_unity": (C.c_int, [C.c_int, C.c_uint32, C.c_char_p]),
     "msmz_point_add": (C.c_int, [C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.POINTER(C.c_int)]),
     # stage-level test hooks (include/msmz_test.h)
     "msmz_test_set_glv_bits": (C.c_int, [C.c_void_p, C.c_int]),
@@ -149,6 +159,8 @@ EXPORTS = {
     "msmz_test_passes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "msmz_test_scalar_dot_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "msmz_test_scalar_scan_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "msmz_test_ntt_plan": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "msmz_test_ntt_geometry": (None, [C.POINTER(C.c_uint32)]),
     "msmz_test_field": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_uint64, C.c_char_p]),
     "msmz_test_field_limbs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                         C.c_char_p]),

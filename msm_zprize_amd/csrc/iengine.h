@@ -94,6 +94,8 @@ class IEngine {
                                  uint8_t* last) = 0;
   virtual int scalars_inverse(uint64_t h, uint64_t first, uint64_t n, uint64_t first_out, uint64_t* out_handle,
                               uint64_t* n_zero) = 0;
+  // msmz_scalars_ntt: number-theoretic transforms over ranges of a scalar set (ntt_kernels.h)
+  virtual int scalars_ntt(const msmz_ntt& t, uint64_t first_out, uint64_t* out_handle) = 0;
   // tests (include/msmz_test.h); the stage-level hooks are one engine's (a multi-device context: its first engine's)
   virtual int test_set_glv_bits(int) { return MSMZ_ERR_UNSUPPORTED; }
   virtual int test_retries() { return 0; }

@@ -7,6 +7,7 @@
 #include "import_kernels.h"
 #include "kernels.h"
 #include "mul_kernels.h"
+#include "ntt_kernels.h"
 #include "scalar_kernels.h"
 #include "scan_kernels.h"
 #include "test_kernels.h"
@@ -124,7 +125,8 @@
   PFX template __global__ void k_scalars_rec_carry<Fr, false, true>(uint32_t*, uint32_t*, const uint32_t*, const uint32_t*, FrConst, uint32_t); \
   PFX template __global__ void k_scalars_rec_carry<Fr, true, false>(uint32_t*, uint32_t*, const uint32_t*, const uint32_t*, FrConst, uint32_t); \
   PFX template __global__ void k_scalars_rec_carry<Fr, true, true>(uint32_t*, uint32_t*, const uint32_t*, const uint32_t*, FrConst, uint32_t); \
-  PFX template __global__ void k_scalars_inverse<Fr>(uint32_t*, const uint32_t*, uint32_t, uint32_t*);
+  PFX template __global__ void k_scalars_inverse<Fr>(uint32_t*, const uint32_t*, uint32_t, uint32_t*);         \
+  PFX template __global__ void k_ntt_pass<Fr>(NttArgs);
 
 #define MSMZ_INST_MISC(F, Fr, PFX)                                                                                \
   PFX template __global__ void k_points_to_mont<F>(uint32_t*, const uint32_t*, const uint8_t*, uint32_t, int, uint32_t*); \

@@ -232,6 +232,45 @@ int msmz_scalars_inverse(msmz_ctx* c, uint64_t h, uint64_t first, uint64_t n, ui
                          uint64_t* n_zero) {
   return c && out_handle ? c->engine->scalars_inverse(h, first, n, first_out, out_handle, n_zero) : MSMZ_ERR_ARG;
 }
+int msmz_scalars_ntt(msmz_ctx* c, const msmz_ntt* t, uint64_t first_out, uint64_t* out_handle) {
+  return c && t && out_handle ? c->engine->scalars_ntt(*t, first_out, out_handle) : MSMZ_ERR_ARG;
+}
+
+// the 2-adicity of a curve's scalar field, or -1; w (nullable): the default 2^log_n-th root of unity, log_n <= that
+static int ntt_two_adicity(int curve_id, uint32_t log_n, uint32_t* w) {
+  auto of = [&](auto fr) {
+    using Fr = decltype(fr);
+    if (w && log_n <= (uint32_t)Fr::TWO_ADICITY) fr_root_of_unity<Fr>(w, log_n);
+    return (int)Fr::TWO_ADICITY;
+  };
+  switch (curve_id) {
+    case MSMZ_BLS12_377_G1: return of(Bls377Fr{});
+    case MSMZ_PALLAS: return of(PallasFr{});
+    case MSMZ_BLS12_381_G1: return of(Bls381Fr{});
+    case MSMZ_ED_ON_BLS12_377: return of(Ed377Fr{});
+    default: return -1;
+  }
+}
+int msmz_scalars_root_of_unity(int curve_id, uint32_t log_n, uint8_t* out_le32) {
+  uint32_t w[8];
+  const int S = ntt_two_adicity(curve_id, log_n, w);
+  if (S < 0 || !out_le32) return MSMZ_ERR_ARG;
+  if (log_n > (uint32_t)S) return MSMZ_ERR_UNSUPPORTED;
+  memcpy(out_le32, w, 32);
+  return MSMZ_OK;
+}
+int msmz_test_ntt_plan(int curve_id, uint32_t log_n, uint32_t* n_passes, uint32_t* stages) {
+  const int S = ntt_two_adicity(curve_id, 0, nullptr);
+  if (S < 0 || !n_passes || !stages || log_n > (uint32_t)NTT_MAX_LOG) return MSMZ_ERR_ARG;
+  if (log_n > (uint32_t)S) return MSMZ_ERR_UNSUPPORTED;
+  const NttPlan p = ntt_plan(log_n);
+  *n_passes = p.n_passes;
+  for (uint32_t j = 0; j < 8; j++) stages[j] = j < p.n_passes ? p.pass[j].s : 0;
+  return MSMZ_OK;
+}
+void msmz_test_ntt_geometry(uint32_t* pass_log) {
+  if (pass_log) *pass_log = NTT_PASS_LOG;
+}
 void msmz_test_scalar_dot_geometry(uint32_t* tile_elements, uint32_t* partials_per_pass) {
   if (tile_elements) *tile_elements = SDOT_TILE;
   if (partials_per_pass) *partials_per_pass = SDOT_PASS;

@@ -444,6 +444,15 @@ class MultiEngine : public IEngine {
     return finish_handle(st, mh, out_handle);
   }
 
+  // The butterflies of a transform cross every boundary between blocks of 2^16 entries, and consecutive blocks live on
+  // different engines: refused, as a recurrence is (after the checks that need no handle).
+  int scalars_ntt(const msmz_ntt& t, uint64_t, uint64_t* out_handle) override {
+    if (!out_handle || t.count == 0 || (t.flags & ~(uint32_t)(MSMZ_NTT_INVERSE | MSMZ_NTT_COSET)) ||
+        ((t.flags & MSMZ_NTT_COSET) != 0) != (t.shift != nullptr))
+      return MSMZ_ERR_ARG;
+    return MSMZ_ERR_UNSUPPORTED;
+  }
+
   int test_set_glv_bits(int bits) override {
     return on_every([&](IEngine* e) { return e->test_set_glv_bits(bits); });
   }

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <deque>
 #include <vector>
 
 #include "../../include/msmz.h"
@@ -16,6 +17,7 @@
 #include "check_kernels.h"
 #include "mul_kernels.h"
 #include "scalar_kernels.h"
+#include "ntt_kernels.h"
 #include "iengine.h"
 #include "store.h"
 
@@ -471,6 +473,80 @@ class ResidentSets : public IEngine {
     return hd.mem.p ? add_handle(std::move(hd), out_handle) : (int)MSMZ_OK;
   }
 
+  // msmz_scalars_ntt: one launch per pass of the plan (ntt_plan.h), in stream order, from the source through scratch to
+  // the destination; the error word (a resident record >= q, raised by the first pass) comes back behind the ONE host
+  // wait.  Twiddle tables: built on the device by k_scalars_powers in the same stream, cached per (log_n, root as used).
+  int scalars_ntt(const msmz_ntt& t, uint64_t first_out, uint64_t* out_handle) override {
+    const bool inverse = t.flags & MSMZ_NTT_INVERSE, coset = t.flags & MSMZ_NTT_COSET;
+    if (!out_handle || t.count == 0 || (t.flags & ~(uint32_t)(MSMZ_NTT_INVERSE | MSMZ_NTT_COSET)) || coset != (t.shift != nullptr))
+      return MSMZ_ERR_ARG;
+    if (t.log_n > (uint32_t)Fr::TWO_ADICITY) return MSMZ_ERR_UNSUPPORTED;
+    if (t.log_n >= 32) return MSMZ_ERR_ARG;
+    const uint64_t n = 1ull << t.log_n, total = n * t.count, n_in = t.n_in ? t.n_in : n;
+    if (total >> 32 || n_in > n || (inverse && n_in != n)) return MSMZ_ERR_ARG;
+    const uint32_t* X = nullptr;
+    uint32_t* out = nullptr;
+    if (int st = resolve({{t.handle, t.first, &X, n_in * t.count}}, total, first_out, *out_handle, &out)) return st;
+    uint32_t w[8], g[8];
+    if (t.root) {
+      if (int st = read_fr(t.root, w, false)) return st;
+      if (!fr_is_primitive_root<Fr>(w, t.log_n)) return MSMZ_ERR_ARG;
+    } else {
+      fr_root_of_unity<Fr>(w, t.log_n);
+    }
+    if (coset) {
+      if (int st = read_fr(t.shift, g, false)) return st;
+      uint32_t any = 0;
+      for (int j = 0; j < 8; j++) any |= g[j];
+      if (!any) return MSMZ_ERR_ARG;
+    }
+    NttCall call{};
+    call.plan = ntt_plan(t.log_n);
+    call.inverse = inverse;
+    call.n_in = n_in;
+    call.count = t.count;
+    if (inverse) {   // the inverse root, n^-1 and g^-1: three host inversions
+      uint32_t nn[8] = {};
+      nn[t.log_n >> 5] = 1u << (t.log_n & 31);
+      fr_inv<Fr>(nn, nn);
+      fr_to_mont<Fr>(call.ninv.w, nn);
+      fr_inv<Fr>(w, w);
+      if (coset) fr_inv<Fr>(g, g);
+    }
+    MSMZ_HIP(hipSetDevice(device_));
+    const uint32_t P = call.plan.n_passes;
+    // every allocation first: once a table build is queued nothing below returns before the stream is drained
+    NttTableSpec lo, hi;
+    if (coset) ntt_two_level_specs<Fr>(call.plan, g, inverse ? call.ninv.w : Fr::ONE, &lo, &hi);
+    if (int st = ntt_scratch_.ensure((size_t)(P > 2 ? 2 : P - 1) * total * 32)) return st;
+    if (int st = sscan_.ensure(64)) return st;
+    if (coset)
+      if (int st = ntt_coset_.ensure((size_t)(lo.count + hi.count) * 32)) return st;
+    Handle hd;
+    if (int st = fresh_out(total, &hd, &out)) return st;
+    if (int st = ntt_twiddles(call.plan, w, &call.twiddles)) return st;
+    if (coset) {
+      ntt_fill(ntt_coset_.as<uint32_t>(), lo);
+      ntt_fill(ntt_coset_.as<uint32_t>() + lo.count * 8, hi);
+      call.coset = ntt_coset_.as<const uint32_t>();
+    }
+    const int st = recorded(sscan_, 64, [&](uint32_t* d_res) {   // word 8: the error word
+      call.err = d_res + 8;
+      uint32_t* scratch[2] = {ntt_scratch_.as<uint32_t>(), ntt_scratch_.as<uint32_t>() + (size_t)total * 8};
+      const uint32_t* src = X;
+      uint64_t stride = n_in;
+      for (uint32_t j = 0; j < P; j++) {
+        uint32_t* dst = j + 1 == P ? out : scratch[j & 1];
+        const NttArgs a = ntt_pass_args(call, j, src, stride, dst);
+        const dim3 grid(ntt_pass_tiles(a.pass), t.count < 65535u ? t.count : 65535u);
+        hipLaunchKernelGGL((k_ntt_pass<Fr>), grid, dim3(NTT_THREADS), 0, stream_, a);
+        src = dst;
+        stride = n;
+      }
+    });
+    return st || !hd.mem.p ? st : add_handle(std::move(hd), out_handle);
+  }
+
  protected:
   // Host -> device copy of this engine's `n` local records of `rec` bytes.  split == nullptr: one contiguous copy.
   // Otherwise the engine is shard `split->shard` of `split->nshards` inside a multi-device context (multi.h): its local
@@ -563,19 +639,21 @@ class ResidentSets : public IEngine {
     return MSMZ_OK;
   }
 
-  // The operands of combine, recurrence and inverse.  Every source is a range of n records of a scalar set that does
+  // The operands of combine, recurrence, inverse and ntt.  Every source is a range of n records of a scalar set that does
   // not overlap the destination in part (entry i is read, then written: equal starts are in place).  The destination:
   // records [first_out, first_out + n) of `out_handle`, or, for out_handle == 0, a fresh set -- first_out must be 0 and
   // *out stays null, for the caller to allocate once every check has passed.
   struct Source {
     uint64_t handle, first;
     const uint32_t** p;
+    uint64_t n = 0;   // records, where they differ from the destination's (a transform of zero-padded vectors); 0 = n
   };
   int resolve(const std::vector<Source>& srcs, uint64_t n, uint64_t first_out, uint64_t out_handle, uint32_t** out) {
     if (out_handle == 0 && first_out != 0) return MSMZ_ERR_ARG;
     for (const Source& s : srcs) {
-      if (s.handle == out_handle && partial_overlap(s.first, first_out, n)) return MSMZ_ERR_ARG;
-      if (!(*s.p = handles_.range(s.handle, 1, s.first, n, 8))) return MSMZ_ERR_ARG;
+      const uint64_t len = s.n ? s.n : n;
+      if (s.handle == out_handle && ranges_clash(s.first, len, first_out, n)) return MSMZ_ERR_ARG;
+      if (!(*s.p = handles_.range(s.handle, 1, s.first, len, 8))) return MSMZ_ERR_ARG;
     }
     if (out_handle && !(*out = handles_.range(out_handle, 1, first_out, n, 8))) return MSMZ_ERR_ARG;
     return MSMZ_OK;
@@ -677,6 +755,54 @@ class ResidentSets : public IEngine {
     });
   }
 
+  // a table of powers (ntt_kernels.h) into device memory, queued on stream_: k_scalars_powers from the spec's base
+  void ntt_fill(uint32_t* dst, const NttTableSpec& s) {
+    FrPowTable table;
+    fr_pow_table<Fr>(table, s.ratio);
+    FrConst base;
+    memcpy(base.w, s.base, 32);
+    const uint64_t threads = (s.count + SPOW_RUN - 1) / SPOW_RUN;
+    hipLaunchKernelGGL((k_scalars_powers<Fr>), dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, stream_, dst, base,
+                       table, (uint32_t)s.count, GenMap{});
+  }
+
+  // *tables = the three twiddle tables of `plan` for the root w (the inverse root of an inverse transform), from the
+  // cache or built now.  At most NTT_CACHE sets are kept, the oldest goes first; all are freed with the engine.
+  static constexpr size_t NTT_CACHE = 8;
+  struct NttTwiddles {
+    uint32_t log_n;
+    uint32_t w[8];
+    DevBuf mem;
+  };
+  int ntt_twiddles(const NttPlan& plan, const uint32_t* w, const uint32_t** tables) {
+    for (const NttTwiddles& c : ntt_cache_) {
+      if (c.log_n == plan.log_n && !memcmp(c.w, w, 32)) {
+        *tables = c.mem.template as<const uint32_t>();
+        return MSMZ_OK;
+      }
+    }
+    NttTwiddles c;
+    c.log_n = plan.log_n;
+    memcpy(c.w, w, 32);
+    if (int st = c.mem.ensure((size_t)ntt_twiddle_entries(plan) * 32)) return st;
+    NttTableSpec spec[3];
+    ntt_twiddle_specs<Fr>(plan, w, spec);
+    uint32_t* at = c.mem.template as<uint32_t>();
+    for (int k = 0; k < 3; k++) {
+      ntt_fill(at, spec[k]);
+      at += spec[k].count * 8;
+    }
+    if (hipGetLastError() != hipSuccess) return (void)hipStreamSynchronize(stream_), MSMZ_ERR_HIP;   // (c frees its memory)
+    if (ntt_cache_.size() == NTT_CACHE) {
+      // (the set that leaves may still be read by a transform in flight only if the stream has work: every entry point
+      // returns with the stream drained, so it has none)
+      ntt_cache_.pop_front();
+    }
+    ntt_cache_.push_back(std::move(c));
+    *tables = ntt_cache_.back().mem.template as<const uint32_t>();
+    return MSMZ_OK;
+  }
+
   int ensure_gen_table() {
     if (gen_table_.p) return MSMZ_OK;
     int st = gen_table_.ensure((size_t)GEN_WINDOWS * GEN_TABLE * RW * 4);
@@ -759,6 +885,9 @@ class ResidentSets : public IEngine {
   DevBuf gen_table_;
   DevBuf sdot_;                        // scalars_dot: its result record, then one partial sum per tile
   DevBuf sscan_;                       // scalars_recurrence / _inverse: the result record, then aggregates and incoming values
+  DevBuf ntt_scratch_;                 // scalars_ntt: one or two copies of the batch between the passes of a plan
+  DevBuf ntt_coset_;                   // ... and the two-level powers of the coset shift of the call in progress
+  std::deque<NttTwiddles> ntt_cache_;  // ... and the twiddle tables of the last NTT_CACHE (log_n, root) pairs
   DevBuf check_;                       // check_points: its result record, then one verdict byte per point
   PinnedBuf h_check_;                  // pinned landing of the result record and the verdict bytes behind it
 };

@@ -17,7 +17,7 @@ include/msmz.h -- this module contains no arithmetic.
 import ctypes as C
 
 from . import _native
-from ._native import MsmzCheckResult, MsmzLog, MsmzMul, MsmzOpts, MsmzScalarRec, MsmzScalarTerm, MsmzSegment, MsmzSrc, lib
+from ._native import MsmzCheckResult, MsmzLog, MsmzMul, MsmzNtt, MsmzOpts, MsmzScalarRec, MsmzScalarTerm, MsmzSegment, MsmzSrc, lib
 from ._native import check as _check   # (`check=` is a public keyword of pointsFromBytes / pointsFromTensor)
 
 _state = {"devices": None}
@@ -311,6 +311,26 @@ class _Parallel:
         arr = _resident(self._c, "scalars", t["N"], "msmz_scalars_inverse", x.handle, t["first"], t["N"], t["firstOut"],
                         after=(C.byref(zeros),), out=out)
         return arr, int(zeros.value)
+
+    # -- number-theoretic transforms over resident scalar arrays (msmz_scalars_ntt) ------------------
+    def ntt(self, x, logN, inverse=False, shift=None, root=None, nIn=None, count=1, first=0, out=None, firstOut=0):
+        """`count` transforms of length n = 2^logN mod the group order, natural order in and out.  Input vector k is
+        x[first + k nIn : first + (k + 1) nIn] continued with zeros (nIn=None: n); output vector k is
+        out[firstOut + k n : firstOut + (k + 1) n].  Forward: out_k = sum_i x_i (g w^k)^i; inverse=True:
+        x_i = g^-i n^-1 sum_k X_k w^(-i k) (nIn must be n).  `shift` is the coset shift g (an int, not 0; None: 1), `root` a
+        primitive n-th root of unity w (None: rootOfUnity(logN)).  out=None: a new array of count n entries; otherwise
+        `out` may be `x` over exactly the source range (in place, nIn = n) or apart from it.  Returns the array written."""
+        t = ntt_args(x, logN, inverse, shift, root, nIn, count, first, out, firstOut, self._c.params["order"])
+        arg = MsmzNtt(x.handle, t["first"], t["logN"], t["flags"], t["nIn"], t["count"], t["root"], t["shift"])
+        return _resident(self._c, "scalars", t["count"] << t["logN"], "msmz_scalars_ntt", C.byref(arg), t["firstOut"], out=out)
+
+    def rootOfUnity(self, logN):
+        """The default primitive 2^logN-th root of unity of the scalar field (msmz_scalars_root_of_unity) as an int."""
+        if not _is_int(logN) or not 0 <= logN < 1 << 32:
+            raise ValueError(f"rootOfUnity: logN = {logN!r}")
+        buf = C.create_string_buffer(32)
+        _check(lib().msmz_scalars_root_of_unity(self._c.params["curve_id"], logN, buf), "msmz_scalars_root_of_unity")
+        return int.from_bytes(buf.raw, "little")
 
     def _checked(self, arr, what, who):
         try:
@@ -675,6 +695,55 @@ def invert_scalars_args(x, N, first, out, firstOut, who="invertScalars"):
         raise TypeError(f"{who}: `out` is a resident scalar array or None")
     N = _ranges(who, [("first", first, x), ("firstOut", firstOut, out)], N, out)
     return {"N": N, "first": first, "firstOut": firstOut}
+
+
+def ntt_args(x, logN, inverse, shift, root, nIn, count, first, out, firstOut, order, who="ntt"):
+    """Arguments of ntt -> dict(logN, flags, nIn, count, first, firstOut, root, shift), checked before anything reaches
+    the device.  root / shift: the 32 little-endian bytes, or None.  Whether `root` is a primitive root of unity, and
+    whether the field has transforms of this length at all, is the library's to say."""
+    if not _is_array(x, "scalars"):
+        raise TypeError(f"{who}: `x` is a resident scalar array")
+    if out is not None and not _is_array(out, "scalars"):
+        raise TypeError(f"{who}: `out` is a resident scalar array or None")
+    if not isinstance(inverse, bool):
+        raise TypeError(f"{who}: `inverse` is a bool")
+    for name, v in (("shift", shift), ("root", root)):
+        if v is not None and not _is_int(v):
+            raise TypeError(f"{who}: `{name}` is an int or None")
+        if v is not None and not 0 <= v < order:
+            raise ValueError(f"{who}: {name} = {v} is not in [0, group order)")
+    if shift == 0:
+        raise ValueError(f"{who}: the coset shift is not 0")
+    if not _is_int(logN) or not 0 <= logN < 32:
+        raise ValueError(f"{who}: logN = {logN!r} (0..31)")
+    n = 1 << logN
+    if not _is_int(count) or count < 1 or count * n >= 1 << 32:
+        raise ValueError(f"{who}: count = {count!r} transforms of {n} entries (1 <= count, count * n < 2^32)")
+    if nIn is None:
+        nIn = n
+    if not _is_int(nIn) or not 1 <= nIn <= n:
+        raise ValueError(f"{who}: nIn = {nIn!r} (1..{n})")
+    if inverse and nIn != n:
+        raise ValueError(f"{who}: an inverse transform reads whole vectors (nIn = {nIn}, n = {n})")
+    for name, v, arr in (("first", first, x), ("firstOut", firstOut, out)):
+        if not _is_int(v) or v < 0:
+            raise ValueError(f"{who}: {name} = {v!r}")
+        if arr is None and v != 0:
+            raise ValueError(f"{who}: {name} = {v} without the array it indexes")
+    if count * nIn > len(x) - first:
+        raise ValueError(f"{who}: entries [{first}, +{count * nIn}) of an array of {len(x)}")
+    if out is not None:
+        if count * n > len(out) - firstOut:
+            raise ValueError(f"{who}: entries [{firstOut}, +{count * n}) of an array of {len(out)}")
+        same = first == firstOut and nIn == n
+        apart = first + count * nIn <= firstOut or firstOut + count * n <= first
+        if out.handle == x.handle and not same and not apart:
+            raise ValueError(f"{who}: the destination [{firstOut}, +{count * n}) overlaps the source [{first}, "
+                             f"+{count * nIn}) in part; it may be that range exactly (nIn = n) or apart from it")
+    return {"logN": logN, "flags": (_native.MSMZ_NTT_INVERSE if inverse else 0) | (_native.MSMZ_NTT_COSET if shift is not None else 0),
+            "nIn": nIn, "count": count, "first": first, "firstOut": firstOut,
+            "root": None if root is None else root.to_bytes(32, "little"),
+            "shift": None if shift is None else shift.to_bytes(32, "little")}
 
 
 def check_arg(check, who):

@@ -562,6 +562,41 @@ static napi_value ScalarsInverse(napi_env env, napi_callback_info info) {
   return res;
 }
 
+/* scalarsNtt(ctx, handle, first, logN, flags (1 = inverse, 2 = coset), nIn (0 = n), count, root (32-byte Buffer or null =
+   the default root), shift (32-byte Buffer with the coset flag, else null), firstOut, outHandle (0 = a new array)) ->
+   handle of the array written: count transforms of length 2^logN  (msmz_scalars_ntt) */
+static napi_value ScalarsNtt(napi_env env, napi_callback_info info) {
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  msmz_ntt t; memset(&t, 0, sizeof(t));
+  uint64_t log_n, flags, count, first_out, h = 0;
+  if (!get_args(env, info, 11, argv, &ctx) || !get_u64(env, argv[1], &t.handle) || !get_u64(env, argv[2], &t.first) ||
+      !get_u64(env, argv[3], &log_n) || log_n >> 32 || !get_u64(env, argv[4], &flags) || flags >> 32 ||
+      !get_u64(env, argv[5], &t.n_in) || !get_u64(env, argv[6], &count) || count >> 32 ||
+      !scalar_or_null(env, argv[7], &t.root) || !scalar_or_null(env, argv[8], &t.shift) ||
+      !get_u64(env, argv[9], &first_out) || !get_u64(env, argv[10], &h))
+    return BAD_ARG(env, "scalarsNtt");
+  t.log_n = (uint32_t)log_n; t.flags = (uint32_t)flags; t.count = (uint32_t)count;
+  int st = msmz_scalars_ntt(ctx, &t, first_out, &h);
+  if (st) return throw_status(env, st, "msmz_scalars_ntt");
+  return make_handle(env, h);
+}
+
+/* scalarsRootOfUnity(curveId, logN) -> 32-byte Buffer, little-endian: the default primitive 2^logN-th root of unity of the
+   curve's scalar field  (msmz_scalars_root_of_unity; no context) */
+static napi_value ScalarsRootOfUnity(napi_env env, napi_callback_info info) {
+  napi_value argv[MAX_ARGS];
+  int32_t curve;
+  uint64_t log_n;
+  if (!get_args(env, info, 2, argv, NULL) || napi_get_value_int32(env, argv[0], &curve) != napi_ok ||
+      !get_u64(env, argv[1], &log_n) || log_n >> 32)
+    return BAD_ARG(env, "scalarsRootOfUnity");
+  void* data; napi_value buf;
+  NAPI_CALL(env, napi_create_buffer(env, 32, &data, &buf));
+  int st = msmz_scalars_root_of_unity(curve, (uint32_t)log_n, (uint8_t*)data);
+  if (st) return throw_status(env, st, "msmz_scalars_root_of_unity");
+  return buf;
+}
+
 /* pointAdd(curveId, aXy|null, bXy|null, feBytes) -> {xy, isInf}  (null = infinity).  Refused: a curve id the library does
    not know, a feBytes that is not that curve's, an input Buffer shorter than the 2 * fe_bytes the library reads */
 static napi_value PointAdd(napi_env env, napi_callback_info info) {
@@ -599,6 +634,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"precomputePoints", PrecomputePoints}, {"precomputedInfo", PrecomputedInfo}, {"checkPoints", CheckPoints},
       {"mulPoints", MulPoints}, {"scalarsCombine", ScalarsCombine}, {"scalarsDot", ScalarsDot},
       {"scalarsPowers", ScalarsPowers}, {"scalarsRecurrence", ScalarsRecurrence}, {"scalarsInverse", ScalarsInverse},
+      {"scalarsNtt", ScalarsNtt}, {"scalarsRootOfUnity", ScalarsRootOfUnity},
       {"pointAdd", PointAdd}, {"feBytes", FeBytes}};
   for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); i++) {
     napi_value f;

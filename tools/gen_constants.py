@@ -139,6 +139,10 @@ def field_struct(name, p, nwords, N, W, extra=()):
     return "\n".join(out)
 
 
+# multiplicative generators of the scalar fields as arkworks (bls12-377, ed-on-bls12-377), pasta_curves and bls12_381 use
+NTT_GENERATOR = {"bls12-377": 22, "pallas": 5, "bls12-381": 7, "ed-on-bls12-377": 5}
+
+
 def main():
     import random
     rng = random.Random(1234)
@@ -166,6 +170,15 @@ def main():
         L.append("  static constexpr uint32_t QINV32 = 0x%08xu;  // -q^-1 mod 2^32 (fr_from_mont, scalar.h)" % ((-pow(q, -1, 1 << 32)) % (1 << 32)))
         L.append(arr("R2", limbs(pow(2, 512, q), 8)) + "   // 2^512 mod q: fr_mont_mul by it multiplies by 2^256 (fr.h)")
         L.append(arr("ONE", limbs(pow(2, 256, q), 8)) + "  // 2^256 mod q: the Montgomery form of 1")
+        # 2-adic roots of unity (ntt_kernels.h): S = the 2-adicity of q - 1, W = G^((q - 1) / 2^S) for the multiplicative
+        # generator G the common libraries use; W has order exactly 2^S iff G is a quadratic non-residue
+        G = NTT_GENERATOR[c["label"]]
+        S = ((q - 1) & -(q - 1)).bit_length() - 1
+        assert pow(G, (q - 1) // 2, q) == q - 1, "the NTT generator must be a quadratic non-residue"
+        W = pow(G, (q - 1) >> S, q)
+        assert pow(W, 1 << (S - 1), q) == q - 1
+        L.append("  static constexpr int TWO_ADICITY = %d;  // q - 1 = 2^TWO_ADICITY * odd: the longest transform is 2^TWO_ADICITY (ntt_kernels.h)" % S)
+        L.append(arr("ROOT_MAX", limbs(W, 8)) + "  // %d^((q - 1) / 2^TWO_ADICITY): a primitive 2^TWO_ADICITY-th root of unity, canonical" % G)
         L.append("  static constexpr bool PRIME_ORDER = %s;  // true iff the cofactor is 1, i.e. the whole curve is the subgroup (check_kernels.h)" % ("true" if c["cofactor"] == 1 else "false"))
         if c["kind"] == "weierstrass":
             lam = c["endomorphism"]["lambda_"]
