@@ -415,4 +415,130 @@ MSMZ_HD void te_to_affine_canon(uint32_t* w, const TeExt<F>& p) {
   fe_to_canon_words<F>(w + F::NW, t);
 }
 
+// ------------------------------------------------------------------------------------------------ curve equations
+// y^2 = x^3 + b for a finite affine point in the lazy Montgomery form of the resident records     [1M + 2S]
+template <class F>
+MSMZ_HD bool weier_on_curve(const Affine<F>& a) {
+  Fe<F> yy, xx, xxx, b, t;
+  fe_sqr(yy, a.y);
+  fe_sqr(xx, a.x);
+  fe_mul(xxx, xx, a.x);
+  fe_set_const<F>(b, F::B);
+  fe_sub(t, yy, xxx);
+  fe_sub(t, t, b);
+  fe_carry(t);
+  return fe_is_zero(t);
+}
+
+// -x^2 + y^2 = 1 + d x^2 y^2                                                                       [2M + 2S]
+template <class F>
+MSMZ_HD bool te_on_curve(const Fe<F>& x, const Fe<F>& y) {
+  Fe<F> xx, yy, xy, d, t, one;
+  fe_sqr(xx, x);
+  fe_sqr(yy, y);
+  fe_mul(xy, xx, yy);
+  fe_set_const<F>(d, F::D);
+  fe_mul(t, xy, d);
+  fe_set_const<F>(one, F::ONE);
+  fe_sub(yy, yy, xx);
+  fe_sub(yy, yy, one);
+  fe_sub(yy, yy, t);
+  fe_carry(yy);
+  return fe_is_zero(yy);
+}
+
+// ------------------------------------------------------------------------------------------------ the group, once
+// What the two curve forms share, under one static interface, host and device: code that walks a scalar, checks a
+// point or builds a table is written once over a group G.  Every member forwards to the formulas above.
+//   Acc    the accumulator: XYZZ / extended coordinates
+//   Base   a point as the mixed addition takes it: affine + infinity flag / Niels form
+// x and y arguments are lazy Montgomery residues.  `denominator` is what one inversion turns into affine coordinates
+// (affine_from_inverse); to_affine_canon returns true for the point at infinity (Weierstrass only).
+template <class F_>
+struct WeierGroup {
+  using F = F_;
+  using Acc = Xyzz<F>;
+  struct Base {
+    Affine<F> a;
+    bool inf;
+  };
+  static constexpr bool TE = false;
+  static MSMZ_HD void set_identity(Acc& p) { xyzz_set_inf(p); }
+  static MSMZ_HD bool is_identity(const Acc& p) { return xyzz_is_inf(p); }
+  static MSMZ_HD void dbl(Acc& r, const Acc& p) { xyzz_dbl(r, p); }
+  static MSMZ_HD void add(Acc& r, const Acc& p, const Acc& q) { xyzz_add(r, p, q); }
+  static MSMZ_HD void madd(Acc& r, const Acc& p, const Base& b) { xyzz_madd(r, p, b.a, b.inf); }
+  // p + the finite affine point (x, y)
+  static MSMZ_HD void add_affine(Acc& r, const Acc& p, const Fe<F>& x, const Fe<F>& y) {
+    xyzz_madd(r, p, Affine<F>{x, y}, false);
+  }
+  static MSMZ_HD void from_affine(Acc& p, const Fe<F>& x, const Fe<F>& y) { xyzz_from_affine(p, Affine<F>{x, y}); }
+  static MSMZ_HD void base_from_affine(Base& b, const Fe<F>& x, const Fe<F>& y, bool inf) { b = Base{{x, y}, inf}; }
+  static MSMZ_HD bool on_curve(const Fe<F>& x, const Fe<F>& y) { return weier_on_curve(Affine<F>{x, y}); }
+  static MSMZ_HD const Fe<F>& denominator(const Acc& p) { return p.ZZZ; }
+  static MSMZ_HD void affine_from_inverse(Fe<F>& x, Fe<F>& y, const Acc& p, const Fe<F>& zi3) {
+    Fe<F> t, zi2;
+    fe_mul(t, zi3, p.ZZ);   // 1 / Z   (ZZ / ZZZ = 1 / Z)
+    fe_sqr(zi2, t);         // 1 / ZZ
+    fe_mul(x, p.X, zi2);
+    fe_mul(y, p.Y, zi3);
+  }
+  static MSMZ_HD bool to_affine_canon(uint32_t* w, const Acc& p) { return xyzz_to_affine_canon<F>(w, p); }
+};
+
+// The identity is the affine point (0, 1): there is no infinity flag, and `inf` arguments are not read.  The doubling is
+// the unified te_add(p, p): a = -1 is a square mod p and d is not, so the addition law has no exceptional pair on this
+// curve (Hisil-Wong-Carter-Dawson 2008, section 3) -- the 2- and 4-torsion points included -- and Z never vanishes.
+template <class F_>
+struct TeGroup {
+  using F = F_;
+  using Acc = TeExt<F>;
+  using Base = TeNiels<F>;
+  static constexpr bool TE = true;
+  static MSMZ_HD void set_identity(Acc& p) { te_set_zero(p); }
+  static MSMZ_HD bool is_identity(const Acc& p) {
+    Fe<F> d;
+    fe_sub(d, p.Y, p.Z);
+    fe_carry(d);
+    return fe_is_zero(p.X) && fe_is_zero(d);   // X = 0 alone also holds for (0, -1): the identity has Y = Z
+  }
+  static MSMZ_HD void dbl(Acc& r, const Acc& p) { te_add(r, p, p); }
+  static MSMZ_HD void add(Acc& r, const Acc& p, const Acc& q) { te_add(r, p, q); }
+  static MSMZ_HD void madd(Acc& r, const Acc& p, const Base& b) { te_madd(r, p, b, 0); }
+  static MSMZ_HD void add_affine(Acc& r, const Acc& p, const Fe<F>& x, const Fe<F>& y) {
+    Acc q;
+    from_affine(q, x, y);
+    te_add(r, p, q);
+  }
+  static MSMZ_HD void from_affine(Acc& p, const Fe<F>& x, const Fe<F>& y) {
+    p.X = x;
+    p.Y = y;
+    fe_set_const<F>(p.Z, F::ONE);
+    fe_mul(p.T, x, y);
+  }
+  // the Niels form (y - x, y + x, 2d x y) that the resident records hold
+  static MSMZ_HD void base_from_affine(Base& b, const Fe<F>& x, const Fe<F>& y, bool /*inf*/) {
+    Fe<F> t, k;
+    fe_sub(b.ym, y, x);
+    fe_add(b.yp, y, x);
+    fe_mul(t, x, y);
+    fe_set_const<F>(k, F::K2D);
+    fe_mul(b.kt, t, k);
+  }
+  static MSMZ_HD bool on_curve(const Fe<F>& x, const Fe<F>& y) {
+    Fe<F> yc = y;   // (y = (y - x) + x of a record: two lazy values added)
+    fe_carry(yc);
+    return te_on_curve<F>(x, yc);
+  }
+  static MSMZ_HD const Fe<F>& denominator(const Acc& p) { return p.Z; }
+  static MSMZ_HD void affine_from_inverse(Fe<F>& x, Fe<F>& y, const Acc& p, const Fe<F>& zi) {
+    fe_mul(x, p.X, zi);
+    fe_mul(y, p.Y, zi);
+  }
+  static MSMZ_HD bool to_affine_canon(uint32_t* w, const Acc& p) {
+    te_to_affine_canon<F>(w, p);
+    return false;
+  }
+};
+
 }  // namespace msmz

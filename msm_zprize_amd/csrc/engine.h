@@ -53,54 +53,32 @@ enum class Redo { NONE, PROVEN_BITS, PER_PROBLEM };
 
 // Host-side group addition of two canonical affine points (msmz_point_add; fold_partial, multi.h, folds partial MSM
 // results with it).
-template <class F, bool TE>
+template <class G>
 static int host_point_add(const uint8_t* a, int ai, const uint8_t* b, int bi, uint8_t* out, int* oi) {
+  using F = typename G::F;
   constexpr int NW = F::NW;
-  if constexpr (TE) {
-    auto load = [](TeExt<F>& p, const uint8_t* xy) {
-      uint32_t w[2 * NW];
-      memcpy(w, xy, sizeof(w));
-      Fe<F> x, y;
-      fe_unpack<F>(x, w);
-      fe_unpack<F>(y, w + NW);
-      fe_to_mont(p.X, x);
-      fe_to_mont(p.Y, y);
-      fe_set_const<F>(p.Z, F::ONE);
-      fe_mul(p.T, p.X, p.Y);
-    };
-    if (!a || !b) return MSMZ_ERR_ARG;   // twisted Edwards has no infinity flag: the identity is (0, 1)
-    TeExt<F> p, q, r;
-    load(p, a);
-    load(q, b);
-    te_add(r, p, q);
+  if (G::TE && (!a || !b)) return MSMZ_ERR_ARG;   // twisted Edwards has no infinity flag: the identity is (0, 1)
+  auto load = [](typename G::Acc& p, const uint8_t* xy, bool inf) {
+    if (inf) {
+      G::set_identity(p);
+      return;
+    }
     uint32_t w[2 * NW];
-    te_to_affine_canon<F>(w, r);
-    memcpy(out, w, sizeof(w));
-    *oi = 0;
-  } else {
-    auto load = [](Xyzz<F>& p, const uint8_t* xy, int inf) {
-      if (inf) {
-        xyzz_set_inf(p);
-        return;
-      }
-      uint32_t w[2 * NW];
-      memcpy(w, xy, sizeof(w));
-      Affine<F> t, m;
-      fe_unpack<F>(t.x, w);
-      fe_unpack<F>(t.y, w + NW);
-      fe_to_mont(m.x, t.x);
-      fe_to_mont(m.y, t.y);
-      xyzz_from_affine(p, m);
-    };
-    Xyzz<F> p, q, r;
-    load(p, a, ai);
-    load(q, b, bi);
-    xyzz_add(r, p, q);
-    uint32_t w[2 * NW];
-    bool inf = xyzz_to_affine_canon<F>(w, r);
-    memcpy(out, w, sizeof(w));
-    *oi = inf ? 1 : 0;
-  }
+    memcpy(w, xy, sizeof(w));
+    Fe<F> x, y, xm, ym;
+    fe_unpack<F>(x, w);
+    fe_unpack<F>(y, w + NW);
+    fe_to_mont(xm, x);
+    fe_to_mont(ym, y);
+    G::from_affine(p, xm, ym);
+  };
+  typename G::Acc p, q, r;
+  load(p, a, !G::TE && ai);
+  load(q, b, !G::TE && bi);
+  G::add(r, p, q);
+  uint32_t w[2 * NW];
+  *oi = G::to_affine_canon(w, r) ? 1 : 0;
+  memcpy(out, w, sizeof(w));
   return MSMZ_OK;
 }
 
@@ -1041,7 +1019,7 @@ class Engine : public ResidentSets<Cfg> {
   // (msm-basic.ts:45-176; Weierstrass "projective fallback" parallel.ts:69-87 and the twisted-Edwards MSM)
   int msm_basic(const Handle& pts, const uint32_t* d_points, const uint32_t* d_scalars, uint64_t n64, const msmz_opts& opt,
                 uint8_t* out, int* out_inf, msmz_log* log) {
-    using P = typename std::conditional<TE, TePolicy<F>, WeierPolicy<F>>::type;
+    using P = typename Cfg::P;
     // neither msmProjective (parallel.ts:69-87) nor the twisted-Edwards path (msm-basic.ts:4) uses the endomorphism
     if (opt.glv) return MSMZ_ERR_UNSUPPORTED;
     Plan pl;

@@ -32,72 +32,64 @@ MSMZ_HD uint64_t splitmix64(uint64_t seed, uint64_t index) {
   return z ^ (z >> 31);
 }
 
-template <class F>
-__device__ __forceinline__ void xyzz_to_affine_mont(Affine<F>& a, const Xyzz<F>& p) {
-  Fe<F> zi3, t, zi2;
-  fe_inverse(zi3, p.ZZZ);
-  fe_mul(t, zi3, p.ZZ);
-  fe_sqr(zi2, t);
-  fe_mul(a.x, p.X, zi2);
-  fe_mul(a.y, p.Y, zi3);
+// Montgomery affine coordinates of an accumulator that is not the point at infinity
+template <class P>
+__device__ __forceinline__ void gen_to_affine(Fe<typename P::F>& x, Fe<typename P::F>& y, const typename P::Acc& acc) {
+  Fe<typename P::F> inv;
+  fe_inverse(inv, P::denominator(acc));
+  P::affine_from_inverse(x, y, acc, inv);
 }
 
-// table[k * GEN_TABLE + w] = w * base_k (affine record; w = 0 -> infinity record)
-template <class F>
+// table[k * GEN_TABLE + w] = w * base_k as an affine [x | y] record of 2*NW words; w = 0: the all-zero record of the
+// point at infinity (Weierstrass) / the identity (0, 1) (twisted Edwards)
+template <class P>
 __global__ void __launch_bounds__(128) k_gen_table(uint32_t* table, const uint32_t* bases) {
+  using F = typename P::F;
   constexpr int RW = 2 * F::NW;
   uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= GEN_WINDOWS * GEN_TABLE) return;
   uint32_t k = t / GEN_TABLE, w = t % GEN_TABLE;
   Affine<F> base;
   load_affine<F>(base, bases + (size_t)k * RW, 0);
-  Xyzz<F> acc, tmp;
-  xyzz_set_inf(acc);
+  typename P::Acc acc, tmp;
+  P::set_identity(acc);
   for (int bit = GEN_BITS - 1; bit >= 0; bit--) {
-    xyzz_dbl(tmp, acc);
+    P::dbl(tmp, acc);
     acc = tmp;
     if ((w >> bit) & 1u) {
-      xyzz_madd(tmp, acc, base, false);
+      P::add_affine(tmp, acc, base.x, base.y);
       acc = tmp;
     }
   }
   Affine<F> a;
-  bool inf = xyzz_is_inf(acc);
-  if (!inf) xyzz_to_affine_mont(a, acc);
+  const bool inf = !P::TE && P::is_identity(acc);
+  if (!inf) gen_to_affine<P>(a.x, a.y, acc);
   store_affine<F>(table + (size_t)t * RW, a, inf);
 }
 
-template <class F>
+template <class P>
 __global__ void __launch_bounds__(128) k_gen_points(uint32_t* out, const uint32_t* table, uint32_t n, uint64_t seed,
                                                     int endo, GenMap map) {
+  using F = typename P::F;
   constexpr int RW = 2 * F::NW;
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   uint64_t a = splitmix64(seed, gen_global_index(i, map));
-  Xyzz<F> acc, tmp;
-  xyzz_set_inf(acc);
+  typename P::Acc acc, tmp;
+  P::set_identity(acc);
 #pragma unroll 1
   for (int k = 0; k < GEN_WINDOWS; k++) {
     uint32_t w = (uint32_t)(a >> (GEN_BITS * k)) & (GEN_TABLE - 1);
     if (w == 0) continue;
     Affine<F> p;
     load_affine<F>(p, table + ((size_t)k * GEN_TABLE + w) * RW, 0);
-    xyzz_madd(tmp, acc, p, false);
+    P::add_affine(tmp, acc, p.x, p.y);
     acc = tmp;
   }
-  Affine<F> r;
-  bool inf = xyzz_is_inf(acc);
-  if (!inf) xyzz_to_affine_mont(r, acc);
-  store_affine<F>(out + (size_t)i * PointFmt<F>::STRIDE, r, inf);
-  if (endo) {
-    Fe<F> beta, bx;
-    fe_set_const<F>(beta, F::BETA);
-    if (!inf) {
-      fe_mul(bx, r.x, beta);
-      r.x = bx;
-    }
-    store_affine<F>(out + ((size_t)n + i) * PointFmt<F>::STRIDE, r, inf);
-  }
+  Fe<F> x, y;
+  const bool inf = !P::TE && P::is_identity(acc);
+  if (!inf) gen_to_affine<P>(x, y, acc);
+  P::store_resident(out, i, n, x, y, inf, endo);
 }
 
 template <class Fr>
@@ -125,126 +117,6 @@ __global__ void __launch_bounds__(256) k_gen_scalars(uint32_t* out, uint32_t n, 
   uint4* o = reinterpret_cast<uint4*>(out + (size_t)i * 8);
   o[0] = make_uint4(w[0], w[1], w[2], w[3]);
   o[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
-
-// ------------------------------------------------------------------------------------------------ twisted Edwards
-// Device records of twisted-Edwards input points are "Niels" form + x:  [y-x | y+x | 2d*x*y | x]
-// (4*NW words).  The reference stores extended (X, Y, Z=1, T) instead (parallel.ts:209-232).
-template <class F>
-__device__ __forceinline__ void te_store_niels(uint32_t* rec, const Fe<F>& x, const Fe<F>& y) {
-  Fe<F> ym, yp, t, k, kt;
-  fe_sub(ym, y, x);
-  fe_add(yp, y, x);
-  fe_mul(t, x, y);
-  fe_set_const<F>(k, F::K2D);
-  fe_mul(kt, t, k);
-  uint32_t w[2 * F::NW];
-  fe_store<F>(w, ym);
-  fe_store<F>(w + F::NW, yp);
-  store_words<F>(rec, w);
-  fe_store<F>(w, kt);
-  fe_store<F>(w + F::NW, x);
-  store_words<F>(rec + 2 * F::NW, w);
-}
-
-// canonical (x | y) -> Niels records
-template <class F>
-__global__ void __launch_bounds__(256) k_te_points_to_niels(uint32_t* out, const uint32_t* in, uint32_t n,
-                                                            uint32_t* err) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  {
-    uint32_t w[2 * F::NW];
-    load_words<F>(w, in + (size_t)i * 2 * F::NW);
-    if (words_geq<F::NW>(w, F::PW) || words_geq<F::NW>(w + F::NW, F::PW)) atomicOr(err, 4u);
-  }
-  Affine<F> p;
-  load_affine<F>(p, in + (size_t)i * 2 * F::NW, 0);
-  Fe<F> x, y;
-  fe_to_mont(x, p.x);
-  fe_to_mont(y, p.y);
-  te_store_niels<F>(out + (size_t)i * 4 * F::NW, x, y);
-}
-
-// Niels records -> canonical (x | y):  x is stored, y = (y - x) + x
-template <class F>
-__global__ void __launch_bounds__(256) k_te_points_from_niels(uint32_t* out, const uint32_t* in, uint32_t n) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  Fe<F> ym, yp, kt, x, y, t;
-  load_fe4<F>(ym, yp, kt, x, in + (size_t)i * 4 * F::NW);
-  fe_add(y, ym, x);
-  uint32_t w[2 * F::NW];
-  fe_from_mont(t, x);
-  fe_to_canon_words<F>(w, t);
-  fe_from_mont(t, y);
-  fe_to_canon_words<F>(w + F::NW, t);
-  store_words<F>(out + (size_t)i * 2 * F::NW, w);
-}
-
-template <class F>
-__device__ __forceinline__ void te_from_affine(TeExt<F>& p, const Affine<F>& a) {
-  p.X = a.x;
-  p.Y = a.y;
-  fe_set_const<F>(p.Z, F::ONE);
-  fe_mul(p.T, a.x, a.y);
-}
-
-template <class F>
-__device__ __forceinline__ void te_to_affine_mont(Affine<F>& a, const TeExt<F>& p) {
-  Fe<F> zi;
-  fe_inverse(zi, p.Z);
-  fe_mul(a.x, p.X, zi);
-  fe_mul(a.y, p.Y, zi);
-}
-
-// table[k * GEN_TABLE + w] = w * base_k as affine [x | y] records (w = 0 -> the identity (0, 1))
-template <class F>
-__global__ void __launch_bounds__(128) k_te_gen_table(uint32_t* table, const uint32_t* bases) {
-  constexpr int RW = 2 * F::NW;
-  uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= GEN_WINDOWS * GEN_TABLE) return;
-  uint32_t k = t / GEN_TABLE, w = t % GEN_TABLE;
-  Affine<F> base;
-  load_affine<F>(base, bases + (size_t)k * RW, 0);
-  TeExt<F> b, acc, tmp;
-  te_from_affine(b, base);
-  te_set_zero(acc);
-  for (int bit = GEN_BITS - 1; bit >= 0; bit--) {
-    te_add(tmp, acc, acc);
-    acc = tmp;
-    if ((w >> bit) & 1u) {
-      te_add(tmp, acc, b);
-      acc = tmp;
-    }
-  }
-  Affine<F> a;
-  te_to_affine_mont(a, acc);
-  store_affine<F>(table + (size_t)t * RW, a, false);
-}
-
-template <class F>
-__global__ void __launch_bounds__(128) k_te_gen_points(uint32_t* out, const uint32_t* table, uint32_t n, uint64_t seed,
-                                                       GenMap map) {
-  constexpr int RW = 2 * F::NW;
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  uint64_t a = splitmix64(seed, gen_global_index(i, map));
-  TeExt<F> acc, tmp, q;
-  te_set_zero(acc);
-#pragma unroll 1
-  for (int k = 0; k < GEN_WINDOWS; k++) {
-    uint32_t w = (uint32_t)(a >> (GEN_BITS * k)) & (GEN_TABLE - 1);
-    if (w == 0) continue;
-    Affine<F> p;
-    load_affine<F>(p, table + ((size_t)k * GEN_TABLE + w) * RW, 0);
-    te_from_affine(q, p);
-    te_add(tmp, acc, q);
-    acc = tmp;
-  }
-  Affine<F> r;
-  te_to_affine_mont(r, acc);
-  te_store_niels<F>(out + (size_t)i * 4 * F::NW, r.x, r.y);
 }
 
 }  // namespace msmz

@@ -3,7 +3,6 @@
 // 64-bit-limb Montgomery -- to the resident formats the MSM kernels read.  Streaming kernels: one thread per record, no
 // LDS, no scratch.  The engine launches them only on pointers the HIP runtime has classified (Engine::vouch).
 #pragma once
-#include "gen_kernels.h"
 #include "kernels.h"
 
 namespace msmz {
@@ -41,39 +40,14 @@ __device__ __forceinline__ void import_factor(Fe<F>& c, int mont) {
   for (int j = 0; j < F::N; j++) c.l[j] = mont ? F::R2STD[j] : F::R2[j];
 }
 
-// (x | y) records of 2 NW words at src + i * stride -> resident point records, exactly as k_points_to_mont writes them
-// (flagged points all-zero; with `endo`, records [n, 2n) hold (beta x, y)).  The raw words of either form must be < p.
-template <class F>
+// (x | y) records of 2 NW words at src + i * stride -> resident point records, exactly as k_points_to_resident writes
+// them (Weierstrass: flagged points all-zero; with `endo`, records [n, 2n) hold (beta x, y)).  The raw words of either
+// form must be < p.
+template <class P>
 __global__ void __launch_bounds__(256) k_import_points(uint32_t* out, const uint8_t* src, uint64_t stride,
                                                        const uint8_t* is_inf, uint32_t n, int endo, int mont,
                                                        uint32_t* err) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  uint32_t w[2 * F::NW];
-  import_load<2 * F::NW>(w, src, stride, i, 2 * F::NW);
-  if (words_geq<F::NW>(w, F::PW) || words_geq<F::NW>(w + F::NW, F::PW)) atomicOr(err, 4u);
-  Affine<F> p, m;
-  fe_unpack<F>(p.x, w);
-  fe_unpack<F>(p.y, w + F::NW);
-  const bool flagged = is_inf != nullptr && is_inf[i] != 0;
-  Fe<F> f;
-  import_factor<F>(f, mont);
-  fe_mul(m.x, p.x, f);
-  fe_mul(m.y, p.y, f);
-  store_affine<F>(out + (size_t)i * PointFmt<F>::STRIDE, m, flagged);
-  if (endo) {
-    Fe<F> beta, bx;
-    fe_set_const<F>(beta, F::BETA);
-    fe_mul(bx, m.x, beta);
-    m.x = bx;
-    store_affine<F>(out + ((size_t)n + i) * PointFmt<F>::STRIDE, m, flagged);
-  }
-}
-
-// twisted Edwards: (x | y) records -> Niels records, as k_te_points_to_niels
-template <class F>
-__global__ void __launch_bounds__(256) k_te_import_points(uint32_t* out, const uint8_t* src, uint64_t stride, uint32_t n,
-                                                          int mont, uint32_t* err) {
+  using F = typename P::F;
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   uint32_t w[2 * F::NW];
@@ -82,10 +56,11 @@ __global__ void __launch_bounds__(256) k_te_import_points(uint32_t* out, const u
   Fe<F> px, py, f, x, y;
   fe_unpack<F>(px, w);
   fe_unpack<F>(py, w + F::NW);
+  const bool flagged = is_inf != nullptr && is_inf[i] != 0;
   import_factor<F>(f, mont);
   fe_mul(x, px, f);
   fe_mul(y, py, f);
-  te_store_niels<F>(out + (size_t)i * 4 * F::NW, x, y);
+  P::store_resident(out, i, n, x, y, flagged, endo);
 }
 
 }  // namespace msmz

@@ -76,19 +76,19 @@
 
 #define MSMZ_INST_REDUCE_TE(F, Fr, PFX) MSMZ_INST_POLICY(TePolicy<F>, PFX)
 
-#define MSMZ_INST_TEST(F, Fr, P, TE, PFX)                                                                         \
+#define MSMZ_INST_TEST(F, Fr, P, PFX)                                                                             \
   PFX template __global__ void k_test_field<F>(uint32_t*, const uint32_t*, const uint32_t*, uint32_t, int, uint32_t*); \
   PFX template __global__ void k_test_field_limbs<F>(int32_t*, uint32_t*, const int32_t*, const int32_t*, uint32_t,  \
                                                       int, uint32_t*);                                            \
   PFX template __global__ void k_test_glv<Fr>(uint32_t*, uint32_t*, uint8_t*, const uint32_t*, uint32_t);         \
   PFX template __global__ void k_test_digits<Fr, false>(uint32_t*, const uint32_t*, uint32_t, int, int);          \
-  PFX template __global__ void k_test_point<P, TE>(uint32_t*, const uint32_t*, const uint32_t*, const uint8_t*,   \
+  PFX template __global__ void k_test_point<P>(uint32_t*, const uint32_t*, const uint32_t*, const uint8_t*,   \
                                                    const uint8_t*, uint32_t, int);                                \
-  PFX template __global__ void k_test_point_raw<P, TE>(uint32_t*, const uint32_t*, const uint32_t*, const uint8_t*, \
+  PFX template __global__ void k_test_point_raw<P>(uint32_t*, const uint32_t*, const uint32_t*, const uint8_t*, \
                                                        uint32_t, int, int);                                       \
-  PFX template __global__ void k_test_accs_in<P, TE>(uint32_t*, const uint32_t*, const uint8_t*, const uint32_t*, \
+  PFX template __global__ void k_test_accs_in<P>(uint32_t*, const uint32_t*, const uint8_t*, const uint32_t*, \
                                                      uint32_t, uint32_t*);                                        \
-  PFX template __global__ void k_test_accs_out<P, TE>(uint32_t*, const uint32_t*, uint32_t);
+  PFX template __global__ void k_test_accs_out<P>(uint32_t*, const uint32_t*, uint32_t);
 
 // sort kernels: window size 0 = any, 16 / 17 = the defaults of large inputs (window loop unrolled)
 #define MSMZ_INST_SORT(Fr, GLV, C, PFX)                                                                           \
@@ -128,14 +128,21 @@
   PFX template __global__ void k_scalars_inverse<Fr>(uint32_t*, const uint32_t*, uint32_t, uint32_t*);         \
   PFX template __global__ void k_ntt_pass<Fr>(NttArgs);
 
+// every curve, by policy P = WeierPolicy<F> / TePolicy<F>
+#define MSMZ_INST_MISC_P(F, Fr, P, PFX)                                                                           \
+  PFX template __global__ void k_points_to_resident<P>(uint32_t*, const uint32_t*, const uint8_t*, uint32_t, int, uint32_t*); \
+  PFX template __global__ void k_points_from_resident<P>(uint32_t*, const uint32_t*, uint32_t);                   \
+  PFX template __global__ void k_import_points<P>(uint32_t*, const uint8_t*, uint64_t, const uint8_t*, uint32_t, int, int, uint32_t*); \
+  PFX template __global__ void k_check_curve<P>(uint8_t*, CheckResult*, const uint32_t*, uint32_t, uint32_t);     \
+  PFX template __global__ void k_check_subgroup<P, Fr>(uint8_t*, CheckResult*, const uint32_t*, uint32_t, uint32_t); \
+  PFX template __global__ void k_points_mul<P, Fr>(uint32_t*, const uint32_t*, const uint32_t*, MulScalar, const uint32_t*, uint32_t, int, uint32_t*); \
+  MSMZ_INST_TEST(F, Fr, P, PFX)                                                                                   \
+  MSMZ_INST_SCALAR(Fr, PFX)
+
+// ... and what only the Weierstrass pipeline has
 #define MSMZ_INST_MISC(F, Fr, PFX)                                                                                \
-  PFX template __global__ void k_points_to_mont<F>(uint32_t*, const uint32_t*, const uint8_t*, uint32_t, int, uint32_t*); \
-  PFX template __global__ void k_points_from_mont<F>(uint32_t*, const uint32_t*, uint32_t);                       \
-  PFX template __global__ void k_import_points<F>(uint32_t*, const uint8_t*, uint64_t, const uint8_t*, uint32_t, int, int, uint32_t*); \
-  PFX template __global__ void k_check_curve<F>(uint8_t*, CheckResult*, const uint32_t*, uint32_t, uint32_t);     \
-  PFX template __global__ void k_check_subgroup<F, Fr>(uint8_t*, CheckResult*, const uint32_t*, uint32_t, uint32_t); \
+  MSMZ_INST_MISC_P(F, Fr, WeierPolicy<F>, PFX)                                                                    \
   PFX template __global__ void k_precompute_copy<F>(uint32_t*, const uint32_t*, uint32_t, int, int);              \
-  PFX template __global__ void k_points_mul<F, Fr>(uint32_t*, const uint32_t*, const uint32_t*, MulScalar, const uint32_t*, uint32_t, int, uint32_t*); \
   PFX template __global__ void k_digits<Fr, true>(uint32_t*, uint32_t*, MsmMeta*, const uint32_t*, uint32_t, int, int, int, int); \
   MSMZ_INST_SORT(Fr, true, 0, PFX)                                                                                \
   MSMZ_INST_SORT(Fr, true, 16, PFX)                                                                               \
@@ -145,28 +152,16 @@
   MSMZ_INST_SORT_SEG(Fr, false, 16, PFX)                                                                          \
   MSMZ_INST_SORT_SEG(Fr, false, 17, PFX)                                                                          \
   PFX template __global__ void k_test_digits<Fr, true>(uint32_t*, const uint32_t*, uint32_t, int, int);           \
-  MSMZ_INST_TEST(F, Fr, WeierPolicy<F>, false, PFX)                                                               \
   PFX template __global__ void k_test_slots_in<F>(uint32_t*, const uint32_t*, const uint8_t*, uint32_t, uint32_t*); \
-  PFX template __global__ void k_test_slots_out<F>(uint32_t*, const uint32_t*, uint32_t, uint32_t);               \
-  MSMZ_INST_SCALAR(Fr, PFX)
+  PFX template __global__ void k_test_slots_out<F>(uint32_t*, const uint32_t*, uint32_t, uint32_t);
 
-#define MSMZ_INST_MISC_TE(F, Fr, PFX)                                                              \
-  PFX template __global__ void k_te_points_to_niels<F>(uint32_t*, const uint32_t*, uint32_t, uint32_t*); \
-  PFX template __global__ void k_te_points_from_niels<F>(uint32_t*, const uint32_t*, uint32_t);    \
-  PFX template __global__ void k_te_import_points<F>(uint32_t*, const uint8_t*, uint64_t, uint32_t, int, uint32_t*); \
-  PFX template __global__ void k_te_check_curve<F>(uint8_t*, CheckResult*, const uint32_t*, uint32_t, uint32_t); \
-  PFX template __global__ void k_te_check_subgroup<F, Fr>(uint8_t*, CheckResult*, const uint32_t*, uint32_t, uint32_t); \
-  PFX template __global__ void k_te_points_mul<F, Fr>(uint32_t*, const uint32_t*, const uint32_t*, MulScalar, const uint32_t*, uint32_t, uint32_t*); \
-  MSMZ_INST_TEST(F, Fr, TePolicy<F>, true, PFX)                                                    \
-  MSMZ_INST_SCALAR(Fr, PFX)
+#define MSMZ_INST_MISC_TE(F, Fr, PFX) MSMZ_INST_MISC_P(F, Fr, TePolicy<F>, PFX)
 
-#define MSMZ_INST_GEN(F, Fr, PFX)                                                \
-  PFX template __global__ void k_gen_table<F>(uint32_t*, const uint32_t*);       \
-  PFX template __global__ void k_gen_points<F>(uint32_t*, const uint32_t*, uint32_t, uint64_t, int, GenMap);
-
-#define MSMZ_INST_GEN_TE(F, Fr, PFX)                                             \
-  PFX template __global__ void k_te_gen_table<F>(uint32_t*, const uint32_t*);    \
-  PFX template __global__ void k_te_gen_points<F>(uint32_t*, const uint32_t*, uint32_t, uint64_t, GenMap);
+#define MSMZ_INST_GEN_P(P, PFX)                                                  \
+  PFX template __global__ void k_gen_table<P>(uint32_t*, const uint32_t*);       \
+  PFX template __global__ void k_gen_points<P>(uint32_t*, const uint32_t*, uint32_t, uint64_t, int, GenMap);
+#define MSMZ_INST_GEN(F, Fr, PFX) MSMZ_INST_GEN_P(WeierPolicy<F>, PFX)
+#define MSMZ_INST_GEN_TE(F, Fr, PFX) MSMZ_INST_GEN_P(TePolicy<F>, PFX)
 
 #define MSMZ_EXTERN extern
 #define MSMZ_DEFINE

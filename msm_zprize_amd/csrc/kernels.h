@@ -1,7 +1,7 @@
 // HIP kernels of the Pippenger MSM pipeline (gfx950, wave64).  One kernel family per row of the
 // hot-path table:
 //
-//   k_points_to_mont     upload: canonical bytes -> lazy Montgomery residues (+ endomorphism copy)
+//   k_points_to_resident upload: canonical bytes -> resident records of lazy Montgomery residues (+ endomorphism copy)
 //                        (parallel.ts:97-112 pointsFromBytes, field-msm.ts:183-185, wasm/curve.ts:90-103)
 //   k_hist, k_bin_scan,  (sort_kernels.h) GLV split + signed c-bit digits + coarse-bin histogram, bin offsets, and the
 //   k_coarse, k_fine     counting sort of point *indices* into bucket order in two LDS-staged passes; the digits are
@@ -252,77 +252,27 @@ __device__ __forceinline__ void slot_store_point(uint32_t* rec, const Affine<F>&
   slot_store_chunks<S::CH>(rec, w);
 }
 
+// four field elements: an accumulator record, a twisted-Edwards resident record
 template <class F>
-__device__ __forceinline__ void load_xyzz(Xyzz<F>& p, const uint32_t* rec) {
+__device__ __forceinline__ void load_fe4(Fe<F>& a, Fe<F>& b, Fe<F>& c, Fe<F>& d, const uint32_t* rec) {
   uint32_t w[2 * F::NW];
   load_words<F>(w, rec);
-  fe_unpack<F>(p.X, w);
-  fe_unpack<F>(p.Y, w + F::NW);
+  fe_unpack<F>(a, w);
+  fe_unpack<F>(b, w + F::NW);
   load_words<F>(w, rec + 2 * F::NW);
-  fe_unpack<F>(p.ZZ, w);
-  fe_unpack<F>(p.ZZZ, w + F::NW);
+  fe_unpack<F>(c, w);
+  fe_unpack<F>(d, w + F::NW);
 }
 
 template <class F>
-__device__ __forceinline__ void store_xyzz(uint32_t* rec, const Xyzz<F>& p) {
+__device__ __forceinline__ void store_fe4(uint32_t* rec, const Fe<F>& a, const Fe<F>& b, const Fe<F>& c, const Fe<F>& d) {
   uint32_t w[2 * F::NW];
-  fe_store<F>(w, p.X);
-  fe_store<F>(w + F::NW, p.Y);
+  fe_store<F>(w, a);
+  fe_store<F>(w + F::NW, b);
   store_words<F>(rec, w);
-  fe_store<F>(w, p.ZZ);
-  fe_store<F>(w + F::NW, p.ZZZ);
+  fe_store<F>(w, c);
+  fe_store<F>(w + F::NW, d);
   store_words<F>(rec + 2 * F::NW, w);
-}
-
-// ------------------------------------------------------------------------------------------------ upload
-// in : n records of 2*NW canonical little-endian words (x | y), optional infinity flags
-// out: n records in memory format; with `endo`, records [n, 2n) hold (beta*x, y)
-template <class F>
-__global__ void __launch_bounds__(256) k_points_to_mont(uint32_t* out, const uint32_t* in, const uint8_t* is_inf,
-                                                        uint32_t n, int endo, uint32_t* err) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  Affine<F> p, m;
-  {
-    // coordinates must be canonical (< p); flagged here instead of in a serial host loop
-    uint32_t w[2 * F::NW];
-    load_words<F>(w, in + (size_t)i * 2 * F::NW);
-    if (words_geq<F::NW>(w, F::PW) || words_geq<F::NW>(w + F::NW, F::PW)) atomicOr(err, 4u);
-  }
-  bool inf = load_affine<F>(p, in + (size_t)i * 2 * F::NW, 0);
-  (void)inf;
-  bool flagged = is_inf != nullptr && is_inf[i] != 0;
-  fe_to_mont(m.x, p.x);
-  fe_to_mont(m.y, p.y);
-  store_affine<F>(out + (size_t)i * PointFmt<F>::STRIDE, m, flagged);
-  if (endo) {
-    Fe<F> beta, bx;
-    fe_set_const<F>(beta, F::BETA);
-    fe_mul(bx, m.x, beta);
-    m.x = bx;
-    store_affine<F>(out + ((size_t)n + i) * PointFmt<F>::STRIDE, m, flagged);
-  }
-}
-
-// memory-format records -> canonical affine words (for downloads / tests)
-template <class F>
-__global__ void __launch_bounds__(256) k_points_from_mont(uint32_t* out, const uint32_t* in, uint32_t n) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  Affine<F> p;
-  bool inf = load_affine<F>(p, in + (size_t)i * PointFmt<F>::STRIDE, 0);
-  uint32_t w[2 * F::NW];
-  if (inf) {
-#pragma unroll
-    for (int j = 0; j < 2 * F::NW; j++) w[j] = 0;
-  } else {
-    Fe<F> t;
-    fe_from_mont(t, p.x);
-    fe_to_canon_words<F>(w, t);
-    fe_from_mont(t, p.y);
-    fe_to_canon_words<F>(w + F::NW, t);
-  }
-  store_words<F>(out + (size_t)i * 2 * F::NW, w);
 }
 
 // ------------------------------------------------------------------------------------------------ digits (fallback sort)
@@ -948,71 +898,165 @@ __device__ __forceinline__ void te_add_x4(TeExt<F>& r, const TeExt<F>& p, const 
 }
 
 // ------------------------------------------------------------------------------------------------ group policies
-// The bucket accumulation of the msmBasic path and the bucket reduction are written once over a small
-// "group policy": accumulator type + how to fold an input point record into it.
-//   WeierPolicy : XYZZ accumulators, inputs = affine records [x | y] (2*NW words)
-//   TePolicy    : extended twisted-Edwards accumulators, inputs = Niels records [y-x | y+x | 2dxy] (3*NW words)
+// Every kernel that works on resident point records or on accumulator records is written once over a "group policy":
+// the group of curve.h (accumulator type, formulas) plus the device record formats.
+//   WeierPolicy : XYZZ accumulators; resident records = affine [x | y] (2*NW words, padded to PointFmt::STRIDE), the
+//                 all-zero record is the point at infinity; a set with the endomorphism holds (beta x, y) at n + i
+//   TePolicy    : extended twisted-Edwards accumulators; resident records = Niels form + x, [y-x | y+x | 2dxy | x]
+//                 (4*NW words: 16-byte aligned loads; x makes the record invertible: y = (y - x) + x).  The reference
+//                 stores extended (X, Y, Z=1, T) instead (parallel.ts:209-232).
+// IN_WORDS = words between the records of a resident point set.  Resident side: load_base (returns true for the
+// infinity record), load_resident_affine (the same), store_resident (record i of a set of n from Montgomery x, y;
+// `flagged` = the point at infinity), store_normalised (the same from an accumulator and the inverse of its
+// denominator; `dead` = store the identity).  Accumulator side: load, store, add_x4, and madd of a record with the
+// negation bit of a sorted reference.
 template <class F_>
-struct WeierPolicy {
+struct WeierPolicy : WeierGroup<F_> {
+  using G = WeierGroup<F_>;
   using F = F_;
-  using Acc = Xyzz<F>;
-  static constexpr int IN_WORDS = PointFmt<F>::STRIDE;   // words between the records of a resident point set
+  using typename G::Acc;
+  using typename G::Base;
+  using G::madd;
+  static constexpr int IN_WORDS = PointFmt<F>::STRIDE;
   static constexpr int ACC_WORDS = 4 * F::NW;
   static constexpr int ACC_OCC = 1;   // k_bucket_accumulate: no register cap (the XYZZ mixed addition spills below ~120)
-  static __device__ __forceinline__ void zero(Acc& a) { xyzz_set_inf(a); }
-  static __device__ __forceinline__ void add(Acc& r, const Acc& a, const Acc& b) { xyzz_add(r, a, b); }
-  static __device__ __forceinline__ void dbl(Acc& r, const Acc& a) { xyzz_dbl(r, a); }
   static __device__ __forceinline__ void add_x4(Acc& r, const Acc& a, const Acc& b, int s, bool dbl) { xyzz_add_x4(r, a, b, s, dbl); }
   static __device__ __forceinline__ void madd(Acc& r, const Acc& a, const uint32_t* rec, uint32_t neg) {
     Affine<F> p;
     bool inf = load_affine<F>(p, rec, neg);
     xyzz_madd(r, a, p, inf);
   }
-  static __device__ __forceinline__ void load(Acc& a, const uint32_t* rec) { load_xyzz<F>(a, rec); }
-  static __device__ __forceinline__ void store(uint32_t* rec, const Acc& a) { store_xyzz<F>(rec, a); }
+  static __device__ __forceinline__ void load(Acc& a, const uint32_t* rec) { load_fe4<F>(a.X, a.Y, a.ZZ, a.ZZZ, rec); }
+  static __device__ __forceinline__ void store(uint32_t* rec, const Acc& a) { store_fe4<F>(rec, a.X, a.Y, a.ZZ, a.ZZZ); }
+  static __device__ __forceinline__ bool load_base(Base& b, const uint32_t* rec) {
+    return b.inf = load_affine<F>(b.a, rec, 0);
+  }
+  static __device__ __forceinline__ bool load_resident_affine(Fe<F>& x, Fe<F>& y, const uint32_t* rec) {
+    Affine<F> a;
+    const bool inf = load_affine<F>(a, rec, 0);
+    x = a.x;
+    y = a.y;
+    return inf;
+  }
+  static __device__ __forceinline__ void store_resident(uint32_t* out, uint32_t i, uint32_t n, const Fe<F>& x,
+                                                        const Fe<F>& y, bool flagged, int endo) {
+    Affine<F> m{x, y};
+    store_affine<F>(out + (size_t)i * IN_WORDS, m, flagged);
+    if (endo) {
+      if (!flagged) {
+        Fe<F> beta;
+        fe_set_const<F>(beta, F::BETA);
+        fe_mul(m.x, x, beta);
+      }
+      store_affine<F>(out + ((size_t)n + i) * IN_WORDS, m, flagged);
+    }
+  }
+  static __device__ __forceinline__ void store_normalised(uint32_t* out, uint32_t i, uint32_t n, const Acc& a,
+                                                          const Fe<F>& zi3, bool dead, int endo) {
+    Fe<F> x, y;
+    fe_zero(x);
+    fe_zero(y);
+    if (!dead) G::affine_from_inverse(x, y, a, zi3);
+    store_resident(out, i, n, x, y, dead, endo);
+  }
 };
 
-template <class F>
-__device__ __forceinline__ void load_fe4(Fe<F>& a, Fe<F>& b, Fe<F>& c, Fe<F>& d, const uint32_t* rec) {
-  uint32_t w[2 * F::NW];
-  load_words<F>(w, rec);
-  fe_unpack<F>(a, w);
-  fe_unpack<F>(b, w + F::NW);
-  load_words<F>(w, rec + 2 * F::NW);
-  fe_unpack<F>(c, w);
-  fe_unpack<F>(d, w + F::NW);
-}
-
 template <class F_>
-struct TePolicy {
+struct TePolicy : TeGroup<F_> {
+  using G = TeGroup<F_>;
   using F = F_;
-  using Acc = TeExt<F>;
-  static constexpr int IN_WORDS = 4 * F::NW;   // Niels record padded to 4 field elements (16-byte aligned loads)
+  using typename G::Acc;
+  using typename G::Base;
+  using G::madd;
+  static constexpr int IN_WORDS = 4 * F::NW;
   static constexpr int ACC_WORDS = 4 * F::NW;
   // k_bucket_accumulate: no register cap (a cap for 5 waves per SIMD -- 91 registers, no spills -- measured 1 % slower
   // in a same-box A/B at 2^24, 6 waves spill)
   static constexpr int ACC_OCC = 1;
-  static __device__ __forceinline__ void zero(Acc& a) { te_set_zero(a); }
-  static __device__ __forceinline__ void add(Acc& r, const Acc& a, const Acc& b) { te_add(r, a, b); }
-  static __device__ __forceinline__ void dbl(Acc& r, const Acc& a) { te_add(r, a, a); }
   static __device__ __forceinline__ void add_x4(Acc& r, const Acc& a, const Acc& b, int s, bool dbl) { te_add_x4(r, a, b, s, dbl); }
   static __device__ __forceinline__ void madd(Acc& r, const Acc& a, const uint32_t* rec, uint32_t neg) {
-    TeNiels<F> n;
-    Fe<F> pad;
-    load_fe4<F>(n.ym, n.yp, n.kt, pad, rec);
+    Base n;
+    Fe<F> x;
+    load_fe4<F>(n.ym, n.yp, n.kt, x, rec);
     te_madd(r, a, n, neg);
   }
   static __device__ __forceinline__ void load(Acc& a, const uint32_t* rec) { load_fe4<F>(a.X, a.Y, a.Z, a.T, rec); }
-  static __device__ __forceinline__ void store(uint32_t* rec, const Acc& a) {
-    uint32_t w[2 * F::NW];
-    fe_store<F>(w, a.X);
-    fe_store<F>(w + F::NW, a.Y);
-    store_words<F>(rec, w);
-    fe_store<F>(w, a.Z);
-    fe_store<F>(w + F::NW, a.T);
-    store_words<F>(rec + 2 * F::NW, w);
+  static __device__ __forceinline__ void store(uint32_t* rec, const Acc& a) { store_fe4<F>(rec, a.X, a.Y, a.Z, a.T); }
+  static __device__ __forceinline__ bool load_base(Base& b, const uint32_t* rec) {
+    Fe<F> x;
+    load_fe4<F>(b.ym, b.yp, b.kt, x, rec);
+    return false;
+  }
+  static __device__ __forceinline__ bool load_resident_affine(Fe<F>& x, Fe<F>& y, const uint32_t* rec) {
+    Base b;
+    load_fe4<F>(b.ym, b.yp, b.kt, x, rec);
+    fe_add(y, b.ym, x);
+    return false;
+  }
+  static __device__ __forceinline__ void store_resident(uint32_t* out, uint32_t i, uint32_t /*n*/, const Fe<F>& x,
+                                                        const Fe<F>& y, bool /*flagged*/, int /*endo*/) {
+    Base b;
+    G::base_from_affine(b, x, y, false);
+    store_fe4<F>(out + (size_t)i * IN_WORDS, b.ym, b.yp, b.kt, x);
+  }
+  static __device__ __forceinline__ void store_normalised(uint32_t* out, uint32_t i, uint32_t n, const Acc& a,
+                                                          const Fe<F>& zi, bool dead, int endo) {
+    Fe<F> x, y;
+    if (dead) {
+      fe_zero(x);
+      fe_set_const<F>(y, F::ONE);
+    } else {
+      G::affine_from_inverse(x, y, a, zi);
+    }
+    store_resident(out, i, n, x, y, false, endo);
   }
 };
+
+// ------------------------------------------------------------------------------------------------ upload / download
+// in : n records of 2*NW canonical little-endian words (x | y), optional infinity flags
+// out: n resident records; with `endo`, records [n, 2n) hold (beta*x, y)
+template <class P>
+__global__ void __launch_bounds__(256) k_points_to_resident(uint32_t* out, const uint32_t* in, const uint8_t* is_inf,
+                                                            uint32_t n, int endo, uint32_t* err) {
+  using F = typename P::F;
+  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  {
+    // coordinates must be canonical (< p); flagged here instead of in a serial host loop
+    uint32_t w[2 * F::NW];
+    load_words<F>(w, in + (size_t)i * 2 * F::NW);
+    if (words_geq<F::NW>(w, F::PW) || words_geq<F::NW>(w + F::NW, F::PW)) atomicOr(err, 4u);
+  }
+  Affine<F> p;
+  load_affine<F>(p, in + (size_t)i * 2 * F::NW, 0);
+  const bool flagged = is_inf != nullptr && is_inf[i] != 0;
+  Fe<F> x, y;
+  fe_to_mont(x, p.x);
+  fe_to_mont(y, p.y);
+  P::store_resident(out, i, n, x, y, flagged, endo);
+}
+
+// resident records -> canonical affine words (for downloads / tests); the point at infinity: all-zero
+template <class P>
+__global__ void __launch_bounds__(256) k_points_from_resident(uint32_t* out, const uint32_t* in, uint32_t n) {
+  using F = typename P::F;
+  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Fe<F> x, y;
+  const bool inf = P::load_resident_affine(x, y, in + (size_t)i * P::IN_WORDS);
+  uint32_t w[2 * F::NW];
+  if (inf) {
+#pragma unroll
+    for (int j = 0; j < 2 * F::NW; j++) w[j] = 0;
+  } else {
+    Fe<F> t;
+    fe_from_mont(t, x);
+    fe_to_canon_words<F>(w, t);
+    fe_from_mont(t, y);
+    fe_to_canon_words<F>(w + F::NW, t);
+  }
+  store_words<F>(out + (size_t)i * 2 * F::NW, w);
+}
 
 // ------------------------------------------------------------------------------------------------ msmBasic accumulation
 // Bucket accumulation without batch inversion (msm-basic.ts:106-128: addMixed / subMixed into projective
@@ -1040,7 +1084,7 @@ __global__ void __launch_bounds__(128, P::ACC_OCC) k_bucket_accumulate(uint32_t*
   const uint32_t start = off[lo] + ((t - cscan[lo]) << chunk_shift);
   const uint32_t end = min(start + (1u << chunk_shift), off[lo + 1]);
   typename P::Acc acc, tmp;
-  P::zero(acc);
+  P::set_identity(acc);
   for (uint32_t p = start; p < end; p++) {
     const uint32_t rf = refs[p];
     P::madd(tmp, acc, points + (size_t)(rf & REF_IDX) * P::IN_WORDS, rf >> 31);
@@ -1108,8 +1152,8 @@ __global__ void __launch_bounds__(64, MSMZ_REDUCE_OCC) k_reduce_quad(uint32_t* r
   const uint32_t e = A * 4 + q;
   const int lane = threadIdx.x & 63, base_lane = lane & ~3;
   Acc r, c, v, w, got;
-  P::zero(r);
-  P::zero(c);
+  P::set_identity(r);
+  P::set_identity(c);
   if (live && e < n_in) {
     P::load(r, rows_in + ((size_t)k * n_in + e) * XW);
     P::load(c, c_in + ((size_t)k * n_in + e) * XW);
@@ -1124,9 +1168,9 @@ __global__ void __launch_bounds__(64, MSMZ_REDUCE_OCC) k_reduce_quad(uint32_t* r
   {
     const int src[4] = {2, 0, 2, 3};
     quad_fetch<P>(got, q == 0 ? c : v, base_lane + src[q]);
-    if (q == 3) P::zero(got);
+    if (q == 3) P::set_identity(got);
     Acc lhs = (q == 1) ? c : v;
-    if (q == 3) P::zero(lhs);
+    if (q == 3) P::set_identity(lhs);
     P::add(w, lhs, got);                // L0 row, L1 c01, L2 2a, L3 0
   }
   // step 3: pub = {-, b, -, c23} (the step-1 results v); src = {0, 3, 1, 3}
@@ -1156,8 +1200,8 @@ __device__ __forceinline__ void reduce_group16(uint32_t* rows_out, uint32_t* c_o
   using Acc = typename P::Acc;
   const uint32_t e = A * 4 + q;
   Acc r, c, v, w, got;
-  P::zero(r);
-  P::zero(c);
+  P::set_identity(r);
+  P::set_identity(c);
   if (live && e < n_in) {
     P::load(r, rows_in + (size_t)e * XW);
     P::load(c, c_in + (size_t)e * XW);
@@ -1170,9 +1214,9 @@ __device__ __forceinline__ void reduce_group16(uint32_t* rows_out, uint32_t* c_o
   {
     const int src[4] = {2, 0, 2, 3};
     quad_fetch<P>(got, q == 0 ? c : v, base_lane + 4 * src[q]);
-    if (q == 3) P::zero(got);
+    if (q == 3) P::set_identity(got);
     Acc lhs = (q == 1) ? c : v;
-    if (q == 3) P::zero(lhs);
+    if (q == 3) P::set_identity(lhs);
     P::add_x4(w, lhs, got, s, q == 2);      // L0 row, L1 c01, L2 2a, L3 0
   }
   {

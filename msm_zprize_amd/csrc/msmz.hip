@@ -12,11 +12,12 @@ MSMZ_TE_FIELDS(X)
 
 namespace msmz {
 
-// Curve configurations: field structs and curve form (the engine picks the MSM path, Engine::run_problems).
+// Curve configurations: field structs, group policy (kernels.h) and curve form (the engine picks the MSM path, Engine::run_problems).
 template <class F_, class Fr_>
 struct WeierCfg {
   using F = F_;
   using Fr = Fr_;
+  using P = WeierPolicy<F>;
   static constexpr bool TE = false;
   static constexpr bool HAS_ENDO = true;
 };
@@ -25,6 +26,7 @@ template <class F_, class Fr_>
 struct TeCfg {
   using F = F_;
   using Fr = Fr_;
+  using P = TePolicy<F>;
   static constexpr bool TE = true;
   static constexpr bool HAS_ENDO = false;
 };
@@ -339,10 +341,10 @@ int msmz_test_plan(msmz_ctx* c, const msmz_test_plan_args* a) {
 int msmz_point_add(int curve_id, const uint8_t* a, int ai, const uint8_t* b, int bi, uint8_t* out, int* oi) {
   if (!out || !oi || (!a && !ai) || (!b && !bi)) return MSMZ_ERR_ARG;
   switch (curve_id) {
-    case MSMZ_BLS12_377_G1: return host_point_add<Bls377Fp, false>(a, ai, b, bi, out, oi);
-    case MSMZ_PALLAS: return host_point_add<PallasFp, false>(a, ai, b, bi, out, oi);
-    case MSMZ_BLS12_381_G1: return host_point_add<Bls381Fp, false>(a, ai, b, bi, out, oi);
-    case MSMZ_ED_ON_BLS12_377: return host_point_add<Ed377Fp, true>(a, 0, b, 0, out, oi);
+    case MSMZ_BLS12_377_G1: return host_point_add<CfgBls377::P>(a, ai, b, bi, out, oi);
+    case MSMZ_PALLAS: return host_point_add<CfgPallas::P>(a, ai, b, bi, out, oi);
+    case MSMZ_BLS12_381_G1: return host_point_add<CfgBls381::P>(a, ai, b, bi, out, oi);
+    case MSMZ_ED_ON_BLS12_377: return host_point_add<CfgEd377::P>(a, 0, b, 0, out, oi);
     default: return MSMZ_ERR_UNSUPPORTED;
   }
 }

@@ -71,7 +71,7 @@ __global__ void __launch_bounds__(128, MSMZ_REDUCE_OCC) k_reduce2d_partial(uint3
     // the single bucket of weight L = H D is folded in as 2 * (H/2) * D
     for (int twice = 0; twice < 2; twice++) add_bucket<F>(acc, kw * g.L + (g.L - 1), slots, points, bfin);
   }
-  store_xyzz<F>(part + ((size_t)(prob * g.H + line) * g.NC + chunk) * 4 * F::NW, acc);
+  WeierPolicy<F>::store(part + ((size_t)(prob * g.H + line) * g.NC + chunk) * 4 * F::NW, acc);
 }
 
 // The same partial sums for the msmBasic path (msm-basic.ts:106-128 buckets in XYZZ / extended coordinates): bucket g is
@@ -106,7 +106,7 @@ __global__ void __launch_bounds__(128, MSMZ_REDUCE_OCC) k_reduce2d_partial_acc(u
     chunk = v - (v / g.NC) * g.NC;
   }
   typename P::Acc acc, tmp, p;
-  P::zero(acc);
+  P::set_identity(acc);
   auto add_bucket_acc = [&](size_t gb) {
     const uint32_t q0 = cscan ? cscan[gb] : (uint32_t)gb, q1 = cscan ? cscan[gb + 1] : (uint32_t)gb + 1u;
     for (uint32_t q = q0; q < q1; q++) {
@@ -155,7 +155,7 @@ __global__ void __launch_bounds__(128, MSMZ_REDUCE_OCC) k_bucket_sums(uint32_t* 
   const uint32_t gb = blockIdx.x * blockDim.x + threadIdx.x;
   if (gb >= nb) return;
   typename P::Acc acc, tmp, p;
-  P::zero(acc);
+  P::set_identity(acc);
   const uint32_t q0 = cscan[gb], q1 = cscan[gb + 1];
   if (q1 > q0) {
     P::load(acc, accs + (size_t)q0 * XW);
@@ -175,7 +175,7 @@ __global__ void __launch_bounds__(256) k_fill_neutral(uint32_t* out, uint32_t n)
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n) return;
   typename P::Acc z;
-  P::zero(z);
+  P::set_identity(z);
   P::store(out + (size_t)t * P::ACC_WORDS, z);
 }
 
@@ -201,8 +201,8 @@ __global__ void __launch_bounds__(64, MSMZ_Q16_OCC) k_pairsum_x4(uint32_t* out, 
   const int s = (int)(t & 3);
   const bool live = i < n_out;
   typename P::Acc a, b, r;
-  P::zero(a);
-  P::zero(b);
+  P::set_identity(a);
+  P::set_identity(b);
   if (live) {
     P::load(a, in + (size_t)(2 * i) * XW);
     P::load(b, in + (size_t)(2 * i + 1) * XW);

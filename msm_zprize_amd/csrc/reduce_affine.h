@@ -99,8 +99,8 @@ __global__ void __launch_bounds__(128) k_reduce_affine_finish(uint32_t* rows, ui
     xyzz_dbl(tmp, row);
     row = tmp;
   }
-  store_xyzz<F>(rows + (size_t)t * 4 * F::NW, row);
-  store_xyzz<F>(tris + (size_t)t * 4 * F::NW, tri);
+  WeierPolicy<F>::store(rows + (size_t)t * 4 * F::NW, row);
+  WeierPolicy<F>::store(tris + (size_t)t * 4 * F::NW, tri);
 }
 
 }  // namespace msmz

@@ -31,8 +31,9 @@ class ResidentSets : public IEngine {
   static constexpr int NW = F::NW;
   static constexpr int RW = 2 * NW;      // affine record words
   static constexpr int FE_BYTES = NW * 4;
+  using P = typename Cfg::P;             // the group policy: formulas and record formats (kernels.h)
   static constexpr bool TE = Cfg::TE;
-  static constexpr int PW_WORDS = TE ? 4 * NW : PointFmt<F>::STRIDE;   // words between the records of a resident point set
+  static constexpr int PW_WORDS = P::IN_WORDS;   // words between the records of a resident point set
 
   explicit ResidentSets(int device) : device_(device) {}
 
@@ -66,13 +67,8 @@ class ResidentSets : public IEngine {
     Handle hd;
     if ((st = new_points(n, &hd))) return st;
     st = checked([&](uint32_t* d_err) {   // a coordinate >= p
-      if constexpr (TE) {
-        hipLaunchKernelGGL((k_te_points_to_niels<F>), dim3((n + 255) / 256), dim3(256), 0, stream_, hd.mem.as<uint32_t>(),
-                           stage_.as<uint32_t>(), (uint32_t)n, d_err);
-      } else {
-        hipLaunchKernelGGL((k_points_to_mont<F>), dim3((n + 255) / 256), dim3(256), 0, stream_, hd.mem.as<uint32_t>(),
-                           stage_.as<uint32_t>(), d_inf, (uint32_t)n, hd.has_endo ? 1 : 0, d_err);
-      }
+      hipLaunchKernelGGL((k_points_to_resident<P>), dim3((n + 255) / 256), dim3(256), 0, stream_, hd.mem.as<uint32_t>(),
+                         stage_.as<uint32_t>(), d_inf, (uint32_t)n, hd.has_endo ? 1 : 0, d_err);
     });
     return st ? st : add_handle(std::move(hd), h);
   }
@@ -134,13 +130,8 @@ class ResidentSets : public IEngine {
         (st = import_view(s, FE_BYTES, n, split, &v)))
       return st;
     st = checked([&](uint32_t* d_err) {   // a coordinate (either form) >= p
-      if constexpr (TE) {
-        hipLaunchKernelGGL((k_te_import_points<F>), dim3((n + 255) / 256), dim3(256), 0, stream_, hd.mem.as<uint32_t>(),
-                           v.ptr, v.stride, (uint32_t)n, mont, d_err);
-      } else {
-        hipLaunchKernelGGL((k_import_points<F>), dim3((n + 255) / 256), dim3(256), 0, stream_, hd.mem.as<uint32_t>(), v.ptr,
-                           v.stride, v.is_inf, (uint32_t)n, hd.has_endo ? 1 : 0, mont, d_err);
-      }
+      hipLaunchKernelGGL((k_import_points<P>), dim3((n + 255) / 256), dim3(256), 0, stream_, hd.mem.as<uint32_t>(), v.ptr,
+                         v.stride, v.is_inf, (uint32_t)n, hd.has_endo ? 1 : 0, mont, d_err);
     });
     return st ? st : add_handle(std::move(hd), h);
   }
@@ -182,13 +173,8 @@ class ResidentSets : public IEngine {
     if (st) return st;
     Handle hd;
     if ((st = new_points(n, &hd))) return st;
-    if constexpr (TE) {
-      hipLaunchKernelGGL((k_te_gen_points<F>), dim3((n + 127) / 128), dim3(128), 0, stream_, hd.mem.as<uint32_t>(),
-                         gen_table_.as<uint32_t>(), (uint32_t)n, seed, map);
-    } else {
-      hipLaunchKernelGGL((k_gen_points<F>), dim3((n + 127) / 128), dim3(128), 0, stream_, hd.mem.as<uint32_t>(),
-                         gen_table_.as<uint32_t>(), (uint32_t)n, seed, hd.has_endo ? 1 : 0, map);
-    }
+    hipLaunchKernelGGL((k_gen_points<P>), dim3((n + 127) / 128), dim3(128), 0, stream_, hd.mem.as<uint32_t>(),
+                       gen_table_.as<uint32_t>(), (uint32_t)n, seed, hd.has_endo ? 1 : 0, map);
     MSMZ_HIP(hipGetLastError());
     MSMZ_HIP(hipStreamSynchronize(stream_));
     return add_handle(std::move(hd), h);
@@ -217,13 +203,8 @@ class ResidentSets : public IEngine {
     int st = stage_.ensure(count * RW * 4);
     if (st) return st;
     const uint32_t* recs = pts->mem.template as<const uint32_t>() + first * PW_WORDS;
-    if constexpr (TE) {
-      hipLaunchKernelGGL((k_te_points_from_niels<F>), dim3((count + 255) / 256), dim3(256), 0, stream_,
-                         stage_.as<uint32_t>(), recs, (uint32_t)count);
-    } else {
-      hipLaunchKernelGGL((k_points_from_mont<F>), dim3((count + 255) / 256), dim3(256), 0, stream_,
-                         stage_.as<uint32_t>(), recs, (uint32_t)count);
-    }
+    hipLaunchKernelGGL((k_points_from_resident<P>), dim3((count + 255) / 256), dim3(256), 0, stream_,
+                       stage_.as<uint32_t>(), recs, (uint32_t)count);
     MSMZ_HIP(hipGetLastError());
     MSMZ_HIP(hipMemcpyAsync(xy, stage_.p, count * RW * 4, hipMemcpyDeviceToHost, stream_));
     MSMZ_HIP(hipStreamSynchronize(stream_));
@@ -274,15 +255,9 @@ class ResidentSets : public IEngine {
     MSMZ_HIP(hipMemsetAsync(d_res, 0, 8, stream_));
     MSMZ_HIP(hipMemsetAsync(&d_res->first_bad, 0xff, 4, stream_));
     const bool chain = (what & MSMZ_CHECK_SUBGROUP) && !Fr::PRIME_ORDER;   // cofactor 1: the curve is the subgroup
-    if constexpr (TE) {
-      hipLaunchKernelGGL((k_te_check_curve<F>), grid, block, 0, stream_, d_verdicts, d_res, recs, (uint32_t)count, (uint32_t)first);
-      if (chain)
-        hipLaunchKernelGGL((k_te_check_subgroup<F, Fr>), grid, block, 0, stream_, d_verdicts, d_res, recs, (uint32_t)count, (uint32_t)first);
-    } else {
-      hipLaunchKernelGGL((k_check_curve<F>), grid, block, 0, stream_, d_verdicts, d_res, recs, (uint32_t)count, (uint32_t)first);
-      if (chain)
-        hipLaunchKernelGGL((k_check_subgroup<F, Fr>), grid, block, 0, stream_, d_verdicts, d_res, recs, (uint32_t)count, (uint32_t)first);
-    }
+    hipLaunchKernelGGL((k_check_curve<P>), grid, block, 0, stream_, d_verdicts, d_res, recs, (uint32_t)count, (uint32_t)first);
+    if (chain)
+      hipLaunchKernelGGL((k_check_subgroup<P, Fr>), grid, block, 0, stream_, d_verdicts, d_res, recs, (uint32_t)count, (uint32_t)first);
     MSMZ_HIP(hipGetLastError());
     // both land in pinned memory (a copy into the caller's pageable buffer would block the host a second time)
     MSMZ_HIP(hipMemcpyAsync(h_check_.p, d_res, sizeof(CheckResult) + (verdicts ? count : 0), hipMemcpyDeviceToHost, stream_));
@@ -305,10 +280,10 @@ class ResidentSets : public IEngine {
     if (!pts || (m.addend_handle && !add)) return MSMZ_ERR_ARG;
     if (m.scalars_handle ? !handles_.get(m.scalars_handle, 1) : !m.scalar) return MSMZ_ERR_ARG;
     if (pts->factor || (add && add->factor)) return MSMZ_ERR_UNSUPPORTED;   // derived data
-    const uint32_t* P = handles_.range(m.points_handle, 0, m.first_p, n, PW_WORDS);
-    const uint32_t* Q = add ? handles_.range(m.addend_handle, 0, m.first_q, n, PW_WORDS) : nullptr;
+    const uint32_t* d_p = handles_.range(m.points_handle, 0, m.first_p, n, PW_WORDS);
+    const uint32_t* d_q = add ? handles_.range(m.addend_handle, 0, m.first_q, n, PW_WORDS) : nullptr;
     const uint32_t* S = m.scalars_handle ? handles_.range(m.scalars_handle, 1, m.first_s, n, 8) : nullptr;
-    if (!P || (add && !Q) || (m.scalars_handle && !S)) return MSMZ_ERR_ARG;
+    if (!d_p || (add && !d_q) || (m.scalars_handle && !S)) return MSMZ_ERR_ARG;
     MulScalar bc{};
     if (!S)
       if (int st = read_fr(m.scalar, bc.w, false)) return st;
@@ -317,13 +292,8 @@ class ResidentSets : public IEngine {
     if (int st = new_points(n, &hd)) return st;
     const dim3 grid((uint32_t)((n + 255) / 256)), block(256);   // whole blocks: every wave reaches the inversion entire
     const int st = checked([&](uint32_t* d_err) {   // a resident scalar >= group order
-      if constexpr (TE) {
-        hipLaunchKernelGGL((k_te_points_mul<F, Fr>), grid, block, 0, stream_, hd.mem.as<uint32_t>(), P, S, bc, Q, (uint32_t)n,
-                           d_err);
-      } else {
-        hipLaunchKernelGGL((k_points_mul<F, Fr>), grid, block, 0, stream_, hd.mem.as<uint32_t>(), P, S, bc, Q, (uint32_t)n,
-                           hd.has_endo ? 1 : 0, d_err);
-      }
+      hipLaunchKernelGGL((k_points_mul<P, Fr>), grid, block, 0, stream_, hd.mem.as<uint32_t>(), d_p, S, bc, d_q, (uint32_t)n,
+                         hd.has_endo ? 1 : 0, d_err);
     });
     return st ? st : add_handle(std::move(hd), h);
   }
@@ -809,65 +779,30 @@ class ResidentSets : public IEngine {
     if (st) return st;
     // bases 2^(13 k) * G computed on the host, multiples on the device
     uint32_t bases[GEN_WINDOWS * RW];
-    Affine<F> ga;
-    fe_set_const<F>(ga.x, F::GX);
-    fe_set_const<F>(ga.y, F::GY);
-    if constexpr (TE) {
-      TeExt<F> g;
-      g.X = ga.x;
-      g.Y = ga.y;
-      fe_set_const<F>(g.Z, F::ONE);
-      fe_mul(g.T, ga.x, ga.y);
-      for (int k = 0; k < GEN_WINDOWS; k++) {
-        Fe<F> zi, x, y;
-        fe_inverse(zi, g.Z);
-        fe_mul(x, g.X, zi);
-        fe_mul(y, g.Y, zi);
-        fe_store<F>(bases + k * RW, x);
-        fe_store<F>(bases + k * RW + NW, y);
-        for (int j = 0; j < GEN_BITS; j++) {
-          TeExt<F> t;
-          te_add(t, g, g);
-          g = t;
-        }
-      }
-    } else {
-      Xyzz<F> g;
-      xyzz_from_affine(g, ga);
-      for (int k = 0; k < GEN_WINDOWS; k++) {
-        Affine<F> a;
-        host_xyzz_to_affine_mont(a, g);
-        fe_store<F>(bases + k * RW, a.x);
-        fe_store<F>(bases + k * RW + NW, a.y);
-        for (int j = 0; j < GEN_BITS; j++) {
-          Xyzz<F> t;
-          xyzz_dbl(t, g);
-          g = t;
-        }
+    Fe<F> gx, gy;
+    fe_set_const<F>(gx, F::GX);
+    fe_set_const<F>(gy, F::GY);
+    typename P::Acc g, t;
+    P::from_affine(g, gx, gy);
+    for (int k = 0; k < GEN_WINDOWS; k++) {
+      Fe<F> inv, x, y;
+      fe_inverse(inv, P::denominator(g));
+      P::affine_from_inverse(x, y, g, inv);
+      fe_store<F>(bases + k * RW, x);
+      fe_store<F>(bases + k * RW + NW, y);
+      for (int j = 0; j < GEN_BITS; j++) {
+        P::dbl(t, g);
+        g = t;
       }
     }
     st = stage_.ensure(sizeof(bases));
     if (st) return st;
     MSMZ_HIP(hipMemcpyAsync(stage_.p, bases, sizeof(bases), hipMemcpyHostToDevice, stream_));
-    if constexpr (TE) {
-      hipLaunchKernelGGL((k_te_gen_table<F>), dim3((GEN_WINDOWS * GEN_TABLE + 127) / 128), dim3(128), 0, stream_,
-                         gen_table_.as<uint32_t>(), stage_.as<uint32_t>());
-    } else {
-      hipLaunchKernelGGL((k_gen_table<F>), dim3((GEN_WINDOWS * GEN_TABLE + 127) / 128), dim3(128), 0, stream_,
-                         gen_table_.as<uint32_t>(), stage_.as<uint32_t>());
-    }
+    hipLaunchKernelGGL((k_gen_table<P>), dim3((GEN_WINDOWS * GEN_TABLE + 127) / 128), dim3(128), 0, stream_,
+                       gen_table_.as<uint32_t>(), stage_.as<uint32_t>());
     MSMZ_HIP(hipGetLastError());
     MSMZ_HIP(hipStreamSynchronize(stream_));
     return MSMZ_OK;
-  }
-
-  static void host_xyzz_to_affine_mont(Affine<F>& a, const Xyzz<F>& p) {
-    Fe<F> zi3, t, zi2;
-    fe_inverse(zi3, p.ZZZ);
-    fe_mul(t, zi3, p.ZZ);
-    fe_sqr(zi2, t);
-    fe_mul(a.x, p.X, zi2);
-    fe_mul(a.y, p.Y, zi3);
   }
 
  protected:

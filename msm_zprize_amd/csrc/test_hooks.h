@@ -81,7 +81,7 @@ class TestHooks : public ITestHooks {
   using F = typename Cfg::F;
   using Fr = typename Cfg::Fr;
   static constexpr bool TE = Cfg::TE;
-  using P = typename std::conditional<TE, TePolicy<F>, WeierPolicy<F>>::type;
+  using P = typename Cfg::P;
 
  public:
   explicit TestHooks(E& engine) : eng_(engine) {}
@@ -247,7 +247,7 @@ class TestHooks : public ITestHooks {
     const int ia = sg.in(a, pb), ib = sg.in(b, pb), iai = sg.in(a_inf, n), ibi = sg.in(b_inf, n), io = sg.out(out, pb);
     if (int st = sg.upload()) return st;
     const uint64_t threads = (op == TP_ADD_X4 || op == TP_DBL_X4) ? 4 * n : n;
-    hipLaunchKernelGGL((k_test_point<P, TE>), dim3((threads + 63) / 64), dim3(64), 0, eng_.stream_, sg.at<uint32_t>(io),
+    hipLaunchKernelGGL((k_test_point<P>), dim3((threads + 63) / 64), dim3(64), 0, eng_.stream_, sg.at<uint32_t>(io),
                        sg.at<const uint32_t>(ia), sg.at<const uint32_t>(ib), sg.at<const uint8_t>(iai),
                        sg.at<const uint8_t>(ibi), (uint32_t)n, op);
     return sg.download();
@@ -264,7 +264,7 @@ class TestHooks : public ITestHooks {
     if (int st = sg.upload()) return st;
     const bool x4 = op == TPR_ADD_X4 || op == TPR_DBL_X4 || op == TPR_CHAIN_X4;
     const uint64_t threads = x4 ? 4 * n : n;
-    hipLaunchKernelGGL((k_test_point_raw<P, TE>), dim3((threads + 63) / 64), dim3(64), 0, eng_.stream_,
+    hipLaunchKernelGGL((k_test_point_raw<P>), dim3((threads + 63) / 64), dim3(64), 0, eng_.stream_,
                        sg.at<uint32_t>(io), sg.at<const uint32_t>(ia), sg.at<const uint32_t>(ib),
                        sg.at<const uint8_t>(ineg), (uint32_t)n, op, L);
     return sg.download();
@@ -379,7 +379,7 @@ class TestHooks : public ITestHooks {
       const uint8_t* d_pinf = sg.at<const uint8_t>(ipinf);
       const uint32_t* d_scale = sg.at<const uint32_t>(iscale);
       if (n)
-        hipLaunchKernelGGL((k_test_accs_in<P, TE>), dim3((n + 255) / 256), dim3(256), 0, eng_.stream_, dst,
+        hipLaunchKernelGGL((k_test_accs_in<P>), dim3((n + 255) / 256), dim3(256), 0, eng_.stream_, dst,
                            sg.at<const uint32_t>(ipxy) + first * RW, d_pinf ? d_pinf + first : nullptr,
                            d_scale ? d_scale + first * NW : nullptr, (uint32_t)n, &d_meta->error);
     };
@@ -414,12 +414,12 @@ class TestHooks : public ITestHooks {
       int rows = 0;   // the red_ buffer that holds the line sums: read out here, before the weighted levels reuse it
       if ((st = eng_.template line_sums_2d<P>(g, rk, d_pts.as<uint32_t>(), !locs, summed, &rows))) return st;
       if (n_lines)
-        hipLaunchKernelGGL((k_test_accs_out<P, TE>), dim3((n_lines + 63) / 64), dim3(64), 0, eng_.stream_,
+        hipLaunchKernelGGL((k_test_accs_out<P>), dim3((n_lines + 63) / 64), dim3(64), 0, eng_.stream_,
                            sg.at<uint32_t>(ilines), eng_.red_[rows].template as<uint32_t>(), n_lines);
       if ((st = eng_.template weighted_sums_2d<P>(g, rk, rows))) return st;
     }
     MSMZ_HIP(hipGetLastError());
-    hipLaunchKernelGGL((k_test_accs_out<P, TE>), dim3((n_res + 63) / 64), dim3(64), 0, eng_.stream_, sg.at<uint32_t>(ires),
+    hipLaunchKernelGGL((k_test_accs_out<P>), dim3((n_res + 63) / 64), dim3(64), 0, eng_.stream_, sg.at<uint32_t>(ires),
                        eng_.final_.template as<uint32_t>(), n_res);
     return sg.download();
   }
@@ -509,7 +509,7 @@ class TestHooks : public ITestHooks {
     uint32_t* d_error = &eng_.meta_.template as<MsmMeta>()->error;
     if constexpr (!TE) {
       if (np)
-        hipLaunchKernelGGL((k_points_to_mont<F>), dim3((np + 255) / 256), dim3(256), 0, eng_.stream_, d_pts.as<uint32_t>(),
+        hipLaunchKernelGGL((k_points_to_resident<P>), dim3((np + 255) / 256), dim3(256), 0, eng_.stream_, d_pts.as<uint32_t>(),
                            d_pxy, d_pinf, (uint32_t)np, 0, d_error);
       if (ns)
         hipLaunchKernelGGL((k_test_slots_in<F>), dim3((ns + 255) / 256), dim3(256), 0, eng_.stream_,

@@ -188,7 +188,7 @@ __global__ void __launch_bounds__(256) k_test_digits(uint32_t* digits, const uin
 
 // point operations on pairs of canonical-affine inputs converted to the accumulator type of policy P:
 //   out[i] = canonical affine (x | y) of op(a_i, b_i); all-zero = infinity (Weierstrass)
-template <class P, bool TE>
+template <class P>
 __global__ void __launch_bounds__(64) k_test_point(uint32_t* out, const uint32_t* a_in, const uint32_t* b_in,
                                                    const uint8_t* a_inf, const uint8_t* b_inf, uint32_t n, int op) {
   using F = typename P::F;
@@ -204,21 +204,7 @@ __global__ void __launch_bounds__(64) k_test_point(uint32_t* out, const uint32_t
     fe_unpack<F>(y, in + (size_t)ii * 2 * NW + NW);
     fe_to_mont(xm, x);
     fe_to_mont(ym, y);
-    if constexpr (TE) {
-      p.X = xm;
-      p.Y = ym;
-      fe_set_const<F>(p.Z, F::ONE);
-      fe_mul(p.T, xm, ym);
-    } else {
-      if (inf != nullptr && inf[ii]) {
-        xyzz_set_inf(p);
-      } else {
-        Affine<F> a;
-        a.x = xm;
-        a.y = ym;
-        xyzz_from_affine(p, a);
-      }
-    }
+    if (!P::TE && inf != nullptr && inf[ii]) P::set_identity(p); else P::from_affine(p, xm, ym);
   };
   Acc a, b, r;
   load(a, a_in, a_inf);
@@ -235,7 +221,7 @@ __global__ void __launch_bounds__(64) k_test_point(uint32_t* out, const uint32_t
     case TP_DBL: P::dbl(r, a); break;
     case TP_MADD: {   // a + b with b as the input record of the bucket accumulation (affine / Niels, memory format)
       alignas(16) uint32_t rec[4 * NW];   // load_words reads it as 16-byte vectors
-      if constexpr (TE) {
+      if constexpr (P::TE) {
         Fe<F> ym, yp, kt, k;
         fe_sub(ym, b.Y, b.X);
         fe_add(yp, b.Y, b.X);
@@ -262,11 +248,7 @@ __global__ void __launch_bounds__(64) k_test_point(uint32_t* out, const uint32_t
   }
   if (i >= n || (x4 && (threadIdx.x & 3) != 0)) return;
   uint32_t w[2 * NW];
-  if constexpr (TE) {
-    te_to_affine_canon<F>(w, r);
-  } else {
-    (void)xyzz_to_affine_canon<F>(w, r);
-  }
+  (void)P::to_affine_canon(w, r);
 #pragma unroll
   for (int j = 0; j < 2 * NW; j++) out[(size_t)i * 2 * NW + j] = w[j];
 }
@@ -277,7 +259,7 @@ __global__ void __launch_bounds__(64) k_test_point(uint32_t* out, const uint32_t
 // infinity) or a Niels record [y-x | y+x | 2dxy | 0] (TE MADD).  neg[i] (nullable): negate the MADD / MDBL record as the
 // bucket accumulation does.  CHAIN: L steps r <- r + b (even steps), r <- 2r (odd steps) in registers, from r = a,
 // with the scalar or the 4-lane formulas.  out[i] = canonical affine (x | y) of the result; all-zero = infinity.
-template <class P, bool TE>
+template <class P>
 __global__ void __launch_bounds__(64) k_test_point_raw(uint32_t* out, const uint32_t* a_in, const uint32_t* b_in,
                                                        const uint8_t* neg, uint32_t n, int op, int L) {
   using F = typename P::F;
@@ -305,7 +287,7 @@ __global__ void __launch_bounds__(64) k_test_point_raw(uint32_t* out, const uint
     case TPR_DBL_X4: P::add_x4(r, a, a, s, true); break;
     case TPR_MADD: P::madd(r, a, brec, ng); break;
     case TPR_MDBL:
-      if constexpr (!TE) {
+      if constexpr (!P::TE) {
         Affine<F> q;
         load_affine<F>(q, brec, ng);
         xyzz_mdbl(r, q);
@@ -333,17 +315,13 @@ __global__ void __launch_bounds__(64) k_test_point_raw(uint32_t* out, const uint
   }
   if (i >= n || (x4 && s != 0)) return;
   uint32_t w[2 * NW];
-  if constexpr (TE) {
-    te_to_affine_canon<F>(w, r);
-  } else {
-    (void)xyzz_to_affine_canon<F>(w, r);
-  }
+  (void)P::to_affine_canon(w, r);
 #pragma unroll
   for (int j = 0; j < 2 * NW; j++) out[(size_t)i * 2 * NW + j] = w[j];
 }
 
 // input slot records of msmz_test_batch_add: canonical affine (x | y, 2*NW words) + infinity flags (nullable) ->
-// slot records 0 .. n-1 in the tree rounds' format; a coordinate >= p raises err bit 2 (as k_points_to_mont)
+// slot records 0 .. n-1 in the tree rounds' format; a coordinate >= p raises err bit 2 (as k_points_to_resident)
 template <class F>
 __global__ void __launch_bounds__(256) k_test_slots_in(uint32_t* slots, const uint32_t* in, const uint8_t* is_inf,
                                                        uint32_t n, uint32_t* err) {
@@ -389,7 +367,7 @@ __global__ void __launch_bounds__(256) k_test_slots_out(uint32_t* out, const uin
 // all-zero record is infinity too) + scales lambda (nullable, canonical, != 0) -> records 0 .. n-1 as the policy
 // stores them: XYZZ (l^2 x, l^3 y, l^2, l^3), extended twisted Edwards (l x, l y, l, l x y).  err bit 2: a coordinate
 // or scale >= p; bit 3: a zero scale.
-template <class P, bool TE>
+template <class P>
 __global__ void __launch_bounds__(256) k_test_accs_in(uint32_t* accs, const uint32_t* in, const uint8_t* is_inf,
                                                       const uint32_t* scale, uint32_t n, uint32_t* err) {
   using F = typename P::F;
@@ -419,7 +397,7 @@ __global__ void __launch_bounds__(256) k_test_accs_in(uint32_t* accs, const uint
     fe_set_const<F>(l, F::ONE);
   }
   typename P::Acc a;
-  if constexpr (TE) {
+  if constexpr (P::TE) {
     Fe<F> t;
     fe_mul(a.X, xm, l);
     fe_mul(a.Y, ym, l);
@@ -442,7 +420,7 @@ __global__ void __launch_bounds__(256) k_test_accs_in(uint32_t* accs, const uint
 }
 
 // results of msmz_test_reduce: accumulator records 0 .. n-1 -> canonical affine (Weierstrass: all-zero = infinity)
-template <class P, bool TE>
+template <class P>
 __global__ void __launch_bounds__(64) k_test_accs_out(uint32_t* out, const uint32_t* accs, uint32_t n) {
   using F = typename P::F;
   constexpr int NW = F::NW;
@@ -451,11 +429,7 @@ __global__ void __launch_bounds__(64) k_test_accs_out(uint32_t* out, const uint3
   typename P::Acc a;
   P::load(a, accs + (size_t)i * P::ACC_WORDS);
   uint32_t w[2 * NW];
-  if constexpr (TE) {
-    te_to_affine_canon<F>(w, a);
-  } else {
-    (void)xyzz_to_affine_canon<F>(w, a);
-  }
+  (void)P::to_affine_canon(w, a);
 #pragma unroll
   for (int j = 0; j < 2 * NW; j++) out[(size_t)i * 2 * NW + j] = w[j];
 }

@@ -1,5 +1,5 @@
 // Host-side driver for msm_zprize_amd/csrc/check_kernels.h: the curve equations and the chain [q]P the validation
-// kernels run (k_check_curve / k_check_subgroup and their twisted-Edwards twins), compiled for the CPU from the same
+// kernels run (k_check_curve / k_check_subgroup) over the groups of curve.h, compiled for the CPU from the same
 // templates.  Driven by tests/test_check_points_cpu.py through stdin/stdout: one point per line
 //   <curve> <x hex> <y hex> <flagged as infinity: 0 / 1>
 // in canonical form; it is brought to the resident record's form (lazy Montgomery words, Niels form on the twisted
@@ -33,28 +33,31 @@ template <class F> static void to_mont(Fe<F>& r, const std::string& h) {
 }
 
 template <class F, class Fr> static int weier(const std::string& xs, const std::string& ys, int inf) {
+  using G = WeierGroup<F>;
   if (inf) return 0;   // the all-zero record
-  Affine<F> m, a;
-  to_mont<F>(m.x, xs); to_mont<F>(m.y, ys);
+  Fe<F> mx, my, x, y;
+  to_mont<F>(mx, xs); to_mont<F>(my, ys);
   uint32_t w[2 * F::NW];
-  fe_store<F>(w, m.x); fe_store<F>(w + F::NW, m.y);
+  fe_store<F>(w, mx); fe_store<F>(w + F::NW, my);
   if (words_point_is_inf<F>(w)) return 0;   // load_affine: the all-zero record is the point at infinity
-  fe_unpack<F>(a.x, w); fe_unpack<F>(a.y, w + F::NW);
-  if (!weier_on_curve<F>(a)) return CHECK_OFF_CURVE;
+  fe_unpack<F>(x, w); fe_unpack<F>(y, w + F::NW);
+  if (!G::on_curve(x, y)) return CHECK_OFF_CURVE;
   if (Fr::PRIME_ORDER) return 0;
-  return point_times_order_is_zero<F, Fr>(a) ? 0 : CHECK_OFF_SUBGROUP;
+  typename G::Base b;
+  G::base_from_affine(b, x, y, false);
+  return group_times_order_is_zero<G, Fr>(b) ? 0 : CHECK_OFF_SUBGROUP;
 }
 
 template <class F, class Fr> static int te(const std::string& xs, const std::string& ys) {
-  Fe<F> mx, my, ym, yp, t, k, kt, x, y;
+  using G = TeGroup<F>;
+  Fe<F> mx, my, x, y;
   to_mont<F>(mx, xs); to_mont<F>(my, ys);
-  fe_sub(ym, my, mx); fe_add(yp, my, mx); fe_mul(t, mx, my);   // te_store_niels (gen_kernels.h)
-  fe_set_const<F>(k, F::K2D); fe_mul(kt, t, k);
-  TeNiels<F> b;
-  resident<F>(b.ym, ym); resident<F>(b.yp, yp); resident<F>(b.kt, kt); resident<F>(x, mx);
-  fe_add(y, b.ym, x); fe_carry(y);                              // k_te_check_curve
-  if (!te_on_curve<F>(x, y)) return CHECK_OFF_CURVE;
-  return te_point_times_order_is_zero<F, Fr>(b) ? 0 : CHECK_OFF_SUBGROUP;
+  typename G::Base n, b;
+  G::base_from_affine(n, mx, my, false);                        // TePolicy::store_resident (kernels.h)
+  resident<F>(b.ym, n.ym); resident<F>(b.yp, n.yp); resident<F>(b.kt, n.kt); resident<F>(x, mx);
+  fe_add(y, b.ym, x);                                           // TePolicy::load_resident_affine
+  if (!G::on_curve(x, y)) return CHECK_OFF_CURVE;
+  return group_times_order_is_zero<G, Fr>(b) ? 0 : CHECK_OFF_SUBGROUP;
 }
 
 int main() {

@@ -1,4 +1,4 @@
-"""msmz_points_mul on the GPU (k_points_mul / k_te_points_mul, csrc/mul_kernels.h): downloaded records against the
+"""msmz_points_mul on the GPU (k_points_mul over either group policy, csrc/mul_kernels.h): downloaded records against the
 oracle's [s]P (+ Q) (tests/points_mul_util.py over oracle/bigint_ref.py) at the sizes that exercise the whole-wave
 normalisation, the IPA fold, the result used as an ordinary point set, the closed form over generated inputs, the
 errors and a multi-engine context."""
