@@ -114,7 +114,7 @@ int msmz_test_sort(msmz_ctx* ctx, const uint8_t* scalars_le32, uint64_t n, int c
                    uint32_t* geom, uint32_t* off, uint64_t off_cap, uint32_t* refs, uint64_t refs_cap);
 
 /* The bucket sort alone at every geometry an MSM runs it in: the engine's own Planner::make_plan, sort_layout and
- * sort_phase (k_hist, k_bin_scan or the three-launch scan, k_coarse, k_fine; or the fallback k_digits, k_scan_*,
+ * BucketSort::run of csrc/sort.h (k_hist, k_bin_scan or the three-launch scan, k_coarse, k_fine; or the fallback k_digits, k_scan_*,
  * k_scatter), the template instances an MSM launches.  Pure integers: no point is read.  msmz_test_sort above is this
  * hook with nprob = 1, factor = 1, pts_n = n and no bound or fold.
  *   scalars_le32: nprob * n scalars, problem after problem;  n: 1 .. 2^22;  nprob: 1 .. 64 (a batched MSM);
@@ -145,7 +145,7 @@ int msmz_test_sort(msmz_ctx* ctx, const uint8_t* scalars_le32, uint64_t n, int c
  * MSMZ_ERR_ARG, before any launch: a null scalars / args, n, nprob, c, scalar_bits or factor out of range, pts_n < n or
  * > 2^30, an index + (F - 1) * copy_stride that leaves 31 bits, a plan make_plan refuses or with more than 2^26 entries,
  * a capacity below the above.  MSMZ_ERR_UNSUPPORTED: GLV on a curve without endomorphism; nprob > 1 or factor > 1 where
- * the layout is not two-level (sort_phase refuses them). */
+ * the layout is not two-level (BucketSort::run refuses them). */
 enum {
   MSMZ_TS_C = 0, MSMZ_TS_K = 1, MSMZ_TS_KEFF = 2, MSMZ_TS_L = 3, MSMZ_TS_NB = 4, MSMZ_TS_FB = 5, MSMZ_TS_FBT = 6,
   MSMZ_TS_NCB = 7, MSMZ_TS_NCBT = 8, MSMZ_TS_NBINS = 9, MSMZ_TS_SBINS = 10, MSMZ_TS_FBINS = 11, MSMZ_TS_FINE_TOP = 12,

@@ -20,32 +20,10 @@
 #include "multi.h"
 #include "plan.h"
 #include "resident.h"
+#include "run.h"
+#include "sort.h"
 
 namespace msmz {
-
-// Named events of an MSM's stages, created once per engine; a timed MSM records them in stream order.
-struct StageEvents {
-  hipEvent_t sort0, hist_end, scan_end, coarse_end, sort_end;   // sort: digits / histogram, scan, scatter
-  hipEvent_t plan0, plan_end;                                    // plan (incl. its host round trip)
-  hipEvent_t round_end[32];                                      // tree round r (recorded for non-empty rounds)
-  hipEvent_t acc_end, red_end;                                   // accumulation, bucket reduction
-  std::vector<hipEvent_t*> all() {
-    std::vector<hipEvent_t*> v{&sort0, &hist_end, &scan_end, &coarse_end, &sort_end, &plan0, &plan_end, &acc_end, &red_end};
-    for (hipEvent_t& e : round_end) v.push_back(&e);
-    return v;
-  }
-};
-
-// One MSM call's run state, beside its Plan (the planner's output): whether it is timed, its stage events, and the
-// device totals fetch_meta reads back.  n_pairs: the additions of the accumulation (the tree rounds' pairs; msmBasic:
-// the entries).
-struct Run {
-  bool timing = false;
-  StageEvents ev{};
-  uint32_t max_bucket = 0, n_entries = 0, rounds = 0;
-  uint32_t round_pairs[32] = {}, round_base[32] = {};
-  uint64_t n_pairs = 0;
-};
 
 // What an MSM attempt asks of its caller besides its status: nothing, the same MSM again with windows for the proven
 // GLV bound (a GLV half was longer than assumed), or this sub-batch's problems one by one (its plan does not batch).
@@ -113,79 +91,8 @@ class Engine : public ResidentSets<Cfg> {
     if ((st = Base::init_sets())) return st;
     for (hipEvent_t* e : ev_.all()) MSMZ_HIP(hipEventCreate(e));
     if ((st = h_res_.ensure((size_t)2 * kMaxWindows * XW * 4))) return st;   // the results of one problem
-    // Kernels that stage more than the default dynamic-LDS allowance get their limit raised ONCE, here, right after
-    // hipSetDevice -- not lazily inside the first MSM and not on every MSM.  static + dynamic LDS is checked against
-    // the device's per-workgroup LDS, so a kernel that cannot launch fails context creation with its name.
-    if ((st = raise_lds_limit((const void*)k_fine, "k_fine", kFineLds))) return st;
-    if constexpr (!TE) {
-      if ((st = raise_lds_limit((const void*)k_fine_seg, "k_fine_seg", kFineLds))) return st;
-    }
-    if ((st = raise_sort_limits<false, 0>()) || (st = raise_sort_limits<false, 16>()) || (st = raise_sort_limits<false, 17>())) return st;
-    if constexpr (Fr::HAS_GLV) {
-      if ((st = raise_sort_limits<true, 0>()) || (st = raise_sort_limits<true, 16>())) return st;
-    }
+    if ((st = sort_.init(device_))) return st;   // (the sort kernels' LDS limits, once)
     return meta_.ensure(sizeof(MsmMeta) + kTraceBytes * 65536);
-  }
- private:
-  template <bool GLV, int C>
-  int raise_sort_limits() {
-    int st;
-    if ((st = raise_lds_limit((const void*)k_coarse<Fr, GLV, C>, GLV ? "k_coarse<glv>" : "k_coarse", kCoarseLdsMax))) return st;
-    if ((st = raise_lds_limit((const void*)k_hist<Fr, GLV, C>, GLV ? "k_hist<glv>" : "k_hist", kHistLdsMax))) return st;
-    if constexpr (!TE) {   // the segmented variants (msm_segments: the batched pipeline is Weierstrass only)
-      if ((st = raise_lds_limit((const void*)k_coarse_seg<Fr, GLV, C>, GLV ? "k_coarse_seg<glv>" : "k_coarse_seg", kCoarseLdsMax))) return st;
-      if ((st = raise_lds_limit((const void*)k_hist_seg<Fr, GLV, C>, GLV ? "k_hist_seg<glv>" : "k_hist_seg", kHistLdsMax))) return st;
-    }
-    return MSMZ_OK;
-  }
-  // dynamic LDS the sort kernels may be launched with (sort_phase never asks for more: SORT_MAX_BINS caps nbins)
-  static constexpr size_t kFineLds = ((size_t)(1 << FINE_MAX_BITS) + FINE_STAGE) * 4;
-  static constexpr size_t kCoarseLdsMax = (size_t)2 * SORT_MAX_BINS * 4;
-  static constexpr size_t kHistLdsMax = (size_t)SORT_MAX_BINS * 4;
-#ifdef MSMZ_TRACE
-  static constexpr size_t kTraceBytes = 128;   // per workgroup, behind the buffers the sort kernels receive (tools/wg_timeline.py)
-#else
-  static constexpr size_t kTraceBytes = 0;
-#endif
-
-#ifdef MSMZ_TRACE
-  // appends one section {name[32], n, n x 16 stamps} to the file MSMZ_TRACE_OUT names (`first` truncates it)
-  int trace_dump(const char* name, const void* d_stamps, uint32_t n_wgs, bool first) {
-    const char* path = getenv("MSMZ_TRACE_OUT");
-    if (!path) return MSMZ_OK;
-    MSMZ_HIP(hipStreamSynchronize(stream_));
-    std::vector<uint64_t> t((size_t)n_wgs * 16);
-    MSMZ_HIP(hipMemcpy(t.data(), d_stamps, t.size() * 8, hipMemcpyDeviceToHost));
-    if (FILE* f = fopen(path, first ? "wb" : "ab")) {
-      char nm[32] = {};
-      strncpy(nm, name, 31);
-      const uint64_t n = n_wgs;
-      fwrite(nm, 1, 32, f);
-      fwrite(&n, 8, 1, f);
-      fwrite(t.data(), 8, t.size(), f);
-      fclose(f);
-    }
-    return MSMZ_OK;
-  }
-#endif
-
-  int raise_lds_limit(const void* fn, const char* name, size_t dyn_max) {
-    hipFuncAttributes fa;
-    memset(&fa, 0, sizeof(fa));
-    MSMZ_HIP(hipFuncGetAttributes(&fa, fn));
-    hipDeviceProp_t prop;
-    MSMZ_HIP(hipGetDeviceProperties(&prop, device_));
-    // per-workgroup LDS of the device: gfx950 reports 160 KiB as the opt-in maximum (64 KiB is the default allowance)
-    size_t dev_max = prop.sharedMemPerBlock;
-    if (prop.sharedMemPerBlockOptin > dev_max) dev_max = prop.sharedMemPerBlockOptin;
-    if (prop.maxSharedMemoryPerMultiProcessor > dev_max) dev_max = prop.maxSharedMemoryPerMultiProcessor;
-    if (fa.sharedSizeBytes + dyn_max > dev_max) {
-      fprintf(stderr, "msmz: %s needs %zu B static + %zu B dynamic LDS, the device offers %zu B per workgroup\n", name,
-              (size_t)fa.sharedSizeBytes, dyn_max, dev_max);
-      return MSMZ_ERR_HIP;
-    }
-    MSMZ_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_max));
-    return MSMZ_OK;
   }
 
  public:
@@ -531,164 +438,11 @@ class Engine : public ResidentSets<Cfg> {
     run.ev = ev_;
     return run;
   }
-  void mark(const Run& run, hipEvent_t e) {
-    if (run.timing) (void)hipEventRecord(e, stream_);
-  }
+  void mark(const Run& run, hipEvent_t e) { run.mark(e, stream_); }
   static float elapsed(hipEvent_t a, hipEvent_t b) {
     float ms = 0;
     (void)hipEventElapsedTime(&ms, a, b);
     return ms;
-  }
-
-  // scalars -> sorted references `refs_` + bucket offsets `off_` (+ meta->max_bucket); the sort's stage events.  No host
-  // round trip.  pl.nprob > 1 (batched MSM): problem p reads scalars [p n, (p + 1) n); its bins follow problem p - 1's in
-  // ONE exclusive scan, so refs_ / off_ come out as one dense sort of pl.nprob * nb buckets.  The two-level sort only.
-  // `sl`: the planner's sort layout of pl; copy_stride: records per copy of a precomputed point set.
-  // d_segs (segmented MSM): problem p's descriptor; d_scalars is then the whole set, pl.n the longest segment.
-  int sort_phase(const Plan& pl, const SortLayout& sl, const uint32_t* d_scalars, Run& run, uint32_t copy_stride,
-                 const SegDesc* d_segs = nullptr) {
-    const uint32_t n = pl.n, M = pl.M, nb = pl.nb, nblocks = pl.nblocks, P = pl.nprob;
-    const int c = pl.c, K = pl.K;
-    int st;
-    if ((st = refs_.ensure((size_t)P * K * M * 4))) return st;
-    if ((st = off_.ensure(((size_t)P * nb + 1) * 4))) return st;
-    MsmMeta* d_meta = meta_.template as<MsmMeta>();
-    MSMZ_HIP(hipMemsetAsync(d_meta, 0, sizeof(MsmMeta), stream_));
-    if (!sl.two_level && (P > 1 || pl.F > 1)) return MSMZ_ERR_ARG;   // (msm_batch only batches plans the two-level sort handles)
-    if (d_segs && (TE || !sl.two_level)) return MSMZ_ERR_ARG;         // (run_segments: the batched pipeline only)
-    const uint32_t nbins = sl.nbins, fbins = sl.fbins;
-    const uint32_t n_half = pl.glv ? n : 0xffffffffu;
-    if (sl.two_level) {
-      const SortGeom& g = sl.geom;
-      const size_t pbins = (size_t)P * g.sbins;   // bins of all problems
-      if ((st = packed_.ensure((size_t)P * K * M * 4))) return st;
-      if ((st = bins_.ensure((pbins + 2) * 4 + kTraceBytes * pbins))) return st;
-      if ((st = counts_.ensure(pbins * 4))) return st;
-      uint32_t* d_counts = counts_.as<uint32_t>();
-      MSMZ_HIP(hipMemsetAsync(d_counts, 0, pbins * 4, stream_));
-      mark(run, run.ev.sort0);
-      const uint32_t per_tile = pl.glv ? COARSE_TILE / 2 : COARSE_TILE;   // scalars per workgroup (k_hist and k_coarse)
-      const uint32_t tiles = (n + per_tile - 1) / per_tile;
-      if ((st = tilecnt_.ensure((size_t)P * tiles * nbins * 2))) return st;
-      if ((st = tileoff_.ensure((size_t)P * tiles * nbins * 4 + kTraceBytes * tiles))) return st;   // the tiles' runs inside the bins
-      const int cspec = sl.cspec;
-      auto launch_sort = [&](auto glvc, auto cc, bool coarse) {
-        constexpr bool G = decltype(glvc)::value;
-        constexpr int C = decltype(cc)::value;
-        if constexpr (!TE) {
-          if (d_segs) {
-            if (!coarse)
-              hipLaunchKernelGGL((k_hist_seg<Fr, G, C>), dim3(tiles, P), dim3(COARSE_T), (size_t)nbins * 4, stream_, d_counts,
-                                 tilecnt_.as<uint16_t>(), tileoff_.as<uint32_t>(), d_meta, d_scalars, g, nbins, d_segs);
-            else
-              hipLaunchKernelGGL((k_coarse_seg<Fr, G, C>), dim3(tiles, P), dim3(COARSE_T), (size_t)2 * nbins * 4, stream_,
-                                 packed_.as<uint32_t>(), tileoff_.as<uint32_t>(), bins_.as<uint32_t>(),
-                                 tilecnt_.as<uint16_t>(), d_scalars, g, nbins, d_segs);
-            return;
-          }
-        }
-        if (!coarse)
-          hipLaunchKernelGGL((k_hist<Fr, G, C>), dim3(tiles, P), dim3(COARSE_T), (size_t)nbins * 4, stream_, d_counts,
-                             tilecnt_.as<uint16_t>(), tileoff_.as<uint32_t>(), d_meta, d_scalars, g, nbins);
-        else   // dynamic LDS <= kCoarseLdsMax (nbins <= SORT_MAX_BINS): the limit init() raised
-          hipLaunchKernelGGL((k_coarse<Fr, G, C>), dim3(tiles, P), dim3(COARSE_T), (size_t)2 * nbins * 4, stream_,
-                             packed_.as<uint32_t>(), tileoff_.as<uint32_t>(), bins_.as<uint32_t>(), tilecnt_.as<uint16_t>(),
-                             d_scalars, g, nbins);
-      };
-      auto dispatch_sort = [&](bool coarse) {
-        using std::integral_constant;
-        if (pl.glv) {
-          if constexpr (Fr::HAS_GLV) {
-            if (cspec == 16) launch_sort(std::true_type{}, integral_constant<int, 16>{}, coarse);
-            else launch_sort(std::true_type{}, integral_constant<int, 0>{}, coarse);
-          }
-        } else if (cspec == 17) {
-          launch_sort(std::false_type{}, integral_constant<int, 17>{}, coarse);
-        } else if (cspec == 16) {
-          launch_sort(std::false_type{}, integral_constant<int, 16>{}, coarse);
-        } else {
-          launch_sort(std::false_type{}, integral_constant<int, 0>{}, coarse);
-        }
-      };
-      dispatch_sort(false);
-      mark(run, run.ev.hist_end);
-      MSMZ_HIP(hipGetLastError());
-      if (pbins <= (size_t)SORT_MAX_BINS) {
-        hipLaunchKernelGGL(k_bin_scan, dim3(1), dim3(1024), 0, stream_, bins_.as<uint32_t>(), d_counts, (uint32_t)pbins,
-                           &d_meta->n_entries);
-      } else {   // a batch with more bins than one workgroup scans: the three-launch scan
-        const uint32_t sblocks = (uint32_t)((pbins + SCAN_TILE - 1) / SCAN_TILE);
-        if ((st = partials_.ensure((size_t)sblocks * 4))) return st;
-        hipLaunchKernelGGL(k_scan_partials, dim3(sblocks, 1), dim3(SCAN_T), 0, stream_, partials_.as<uint32_t>(), d_counts,
-                           (uint32_t)pbins, 0, sblocks);
-        hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(SCAN_T), 0, stream_, partials_.as<uint32_t>(), sblocks,
-                           &d_meta->n_entries);
-        hipLaunchKernelGGL(k_scan_apply, dim3(sblocks, 1), dim3(SCAN_T), 0, stream_, bins_.as<uint32_t>(),
-                           partials_.as<uint32_t>(), d_counts, (uint32_t)pbins, 0, sblocks, (size_t)0, (uint32_t*)nullptr);
-      }
-      mark(run, run.ev.scan_end);
-      MSMZ_HIP(hipGetLastError());
-      dispatch_sort(true);
-      mark(run, run.ev.coarse_end);
-      MSMZ_HIP(hipGetLastError());
-      {
-        const size_t lds = kFineLds;
-        if (d_segs)
-          hipLaunchKernelGGL(k_fine_seg, dim3(fbins, P), dim3(FINE_T), lds, stream_, refs_.as<uint32_t>(),
-                             off_.as<uint32_t>(), &d_meta->max_bucket, packed_.as<uint32_t>(), bins_.as<uint32_t>(), g.fb,
-                             g.fbt, sl.fine_top, fbins, g.idx_bits, n_half, pl.endo_delta, g.F, g.mbits, copy_stride, d_segs);
-        else
-          hipLaunchKernelGGL(k_fine, dim3(fbins, P), dim3(FINE_T), lds, stream_, refs_.as<uint32_t>(), off_.as<uint32_t>(),
-                             &d_meta->max_bucket, packed_.as<uint32_t>(), bins_.as<uint32_t>(), g.fb, g.fbt, sl.fine_top,
-                             fbins, g.idx_bits, n_half, pl.endo_delta, g.F, g.mbits, copy_stride);
-      }
-#ifdef MSMZ_TRACE
-      // development aid: workgroup time stamps of k_coarse / k_fine (tools/wg_timeline.py)
-      if ((st = trace_dump("k_coarse", tileoff_.as<uint32_t>() + (size_t)P * tiles * nbins, tiles, true))) return st;
-      if ((st = trace_dump("k_fine", bins_.as<uint32_t>() + ((P * g.sbins + 2) & ~1u), fbins, false))) return st;
-#endif
-    } else {
-      // fallback (window sizes whose coarse bins do not fit the LDS staging): digits materialized, one global
-      // atomic per entry
-      if (pl.fold_shift != 0) return MSMZ_ERR_ARG;   // (make_plan only folds when the two-level sort applies)
-      if ((st = digits_.ensure((size_t)K * M * 4))) return st;
-      if ((st = counts_.ensure(((size_t)nb + 1) * 4))) return st;
-      if ((st = cursor_.ensure((size_t)nb * 4))) return st;
-      if ((st = partials_.ensure((size_t)32 * nblocks * 4))) return st;
-      MSMZ_HIP(hipMemsetAsync(counts_.p, 0, ((size_t)nb + 1) * 4, stream_));
-      MSMZ_HIP(hipMemsetAsync(cursor_.p, 0, (size_t)nb * 4, stream_));
-      const uint32_t dgrid = (n + 256 * DIGITS_ITEMS - 1) / (256 * DIGITS_ITEMS);
-      mark(run, run.ev.sort0);
-      if (pl.glv) {
-        if constexpr (Fr::HAS_GLV)
-          hipLaunchKernelGGL((k_digits<Fr, true>), dim3(dgrid), dim3(256), 0, stream_, digits_.as<uint32_t>(),
-                             counts_.as<uint32_t>(), d_meta, d_scalars, n, c, K, pl.spread, pl.sbits ? pl.sbits : 256);
-      } else {
-        hipLaunchKernelGGL((k_digits<Fr, false>), dim3(dgrid), dim3(256), 0, stream_, digits_.as<uint32_t>(),
-                           counts_.as<uint32_t>(), d_meta, d_scalars, n, c, K, pl.spread, pl.sbits ? pl.sbits : 256);
-      }
-      mark(run, run.ev.hist_end);
-      MSMZ_HIP(hipGetLastError());
-      hipLaunchKernelGGL(k_scan_partials, dim3(nblocks, 1), dim3(SCAN_T), 0, stream_, partials_.as<uint32_t>(),
-                         counts_.as<uint32_t>(), nb, 0, nblocks);
-      hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(SCAN_T), 0, stream_, partials_.as<uint32_t>(), nblocks,
-                         &d_meta->n_entries);
-      hipLaunchKernelGGL(k_scan_apply, dim3(nblocks, 1), dim3(SCAN_T), 0, stream_, off_.as<uint32_t>(),
-                         partials_.as<uint32_t>(), counts_.as<uint32_t>(), nb, 0, nblocks, (size_t)0,
-                         &d_meta->max_bucket);
-      mark(run, run.ev.scan_end);
-      MSMZ_HIP(hipGetLastError());
-      {
-        dim3 grid((M + 256 * 4 - 1) / (256 * 4), K);
-        hipLaunchKernelGGL(k_scatter, grid, dim3(256), 0, stream_, refs_.as<uint32_t>(), cursor_.as<uint32_t>(),
-                           off_.as<uint32_t>(), digits_.as<uint32_t>(), M, c, pl.spread, n_half, pl.endo_delta);
-      }
-      mark(run, run.ev.coarse_end);
-      MSMZ_HIP(hipGetLastError());
-    }
-    mark(run, run.ev.sort_end);
-    MSMZ_HIP(hipGetLastError());
-    return MSMZ_OK;
   }
 
   // read the device-side totals (one host round trip)
@@ -902,11 +656,12 @@ class Engine : public ResidentSets<Cfg> {
     }
   }
 
-  // The schedule of the tree rounds (plan_kernels.h) for the sorted buckets in off_ / refs_ (nb of them, all problems'),
+  // The schedule of the tree rounds (plan_kernels.h) for the sorted buckets d_off / d_refs (nb of them, all problems'),
   // cut into workgroups as pc says: desc_ <- one descriptor per addition of every round (room for desc_records), bfin_ <-
   // what the rounds leave of each bucket, meta <- rounds, entries, round sizes and bases.  Reads meta->max_bucket, which
   // the sort left.  No host round trip.
-  int plan_phase(const PlanChunks& pc, uint32_t nb, int tail_skip, size_t desc_records, Run& run) {
+  int plan_phase(const PlanChunks& pc, const uint32_t* d_off, const uint32_t* d_refs, uint32_t nb, int tail_skip,
+                 size_t desc_records, Run& run) {
     int st;
     MsmMeta* d_meta = meta_.template as<MsmMeta>();
     mark(run, run.ev.plan0);
@@ -916,14 +671,13 @@ class Engine : public ResidentSets<Cfg> {
     if ((st = rscan_.ensure(((size_t)PLAN_RMAX * n_chunks + pair_words) * 4 + kTraceBytes * n_chunks))) return st;
     if ((st = desc_.ensure(desc_records * 8))) return st;
     if ((st = bfin_.ensure((size_t)nb * 16))) return st;
-    hipLaunchKernelGGL(k_plan_count, dim3(n_chunks), dim3(PLAN_T), 0, stream_, rscan_.as<uint32_t>(), off_.as<uint32_t>(),
-                       nb, n_chunks, d_meta, tail_skip, pc);
+    hipLaunchKernelGGL(k_plan_count, dim3(n_chunks), dim3(PLAN_T), 0, stream_, rscan_.as<uint32_t>(), d_off, nb,
+                       n_chunks, d_meta, tail_skip, pc);
     hipLaunchKernelGGL(k_plan_emit, dim3(n_chunks), dim3(PLAN_T), 0, stream_, desc_.as<uint2>(), bfin_.as<uint4>(),
-                       d_meta, rscan_.as<uint32_t>(), off_.as<uint32_t>(), refs_.as<uint32_t>(), nb, n_chunks,
-                       tail_skip, rscan_.as<uint32_t>() + (size_t)PLAN_RMAX * n_chunks, pc);
+                       d_meta, rscan_.as<uint32_t>(), d_off, d_refs, nb, n_chunks, tail_skip, rscan_.as<uint32_t>() + (size_t)PLAN_RMAX * n_chunks, pc);
     MSMZ_HIP(hipGetLastError());
 #ifdef MSMZ_TRACE
-    if ((st = trace_dump("k_plan_emit", rscan_.as<uint32_t>() + (size_t)PLAN_RMAX * n_chunks + pair_words, n_chunks, false))) return st;
+    if ((st = trace_dump(stream_, "k_plan_emit", rscan_.as<uint32_t>() + (size_t)PLAN_RMAX * n_chunks + pair_words, n_chunks, false))) return st;
 #endif
     return MSMZ_OK;
   }
@@ -959,14 +713,14 @@ class Engine : public ResidentSets<Cfg> {
     const size_t f2_records = opt.reserved[0] == 1 ? (size_t)13 * pl.Keff * ((pl.L + 1) / 2) + 256 : 0;
     if ((st = slots_.ensure(((size_t)nprob * pl.K * pl.M + 64 + f2_records) * SlotFmt<F>::WORDS * 4))) return st;
     Run run = new_run(opt);
-    if ((st = sort_phase(pl, sl, d_scalars, run, (uint32_t)pts.copy_stride, d_segs))) return st;
-    const uint32_t nb = pl.nb * nprob;   // buckets of all problems
     MsmMeta* d_meta = meta_.template as<MsmMeta>();
+    if ((st = sort_.run(pl, sl, d_scalars, run, stream_, d_meta, (uint32_t)pts.copy_stride, d_segs))) return st;
+    const uint32_t nb = pl.nb * nprob;   // buckets of all problems
 
     // ---- plan: descriptors of every pair of every round + what is left of each bucket (plan_kernels.h)
     // the batched-affine first reduction level (opt.reserved[0] = 1) wants ONE sum per bucket: no rounds skipped
     const int tail_skip = want_2d ? tail_skip_2d_ : 0;
-    if ((st = plan_phase(planner_.plan_chunks(pl), nb, tail_skip, (size_t)nprob * pl.K * pl.M, run))) return st;
+    if ((st = plan_phase(planner_.plan_chunks(pl), sort_.off(), sort_.refs(), nb, tail_skip, (size_t)nprob * pl.K * pl.M, run))) return st;
     if ((st = fetch_meta(run))) return st;      // the ONE host round trip before the final fetch
     if (h_meta_->error & 4u) return MSMZ_ERR_RANGE;
     if (h_meta_->error & 2u) {
@@ -988,7 +742,7 @@ class Engine : public ResidentSets<Cfg> {
         snprintf(nm, sizeof nm, "k_batch_add round %d", r);
         const int B = batch_b(pairs);
         const uint32_t wgs = (pairs + MSMZ_BATCH_T * B - 1) / (MSMZ_BATCH_T * B);
-        if ((st = trace_dump(nm, d_meta + 1, wgs < 65536 ? wgs : 65536, false))) return st;
+        if ((st = trace_dump(stream_, nm, d_meta + 1, wgs < 65536 ? wgs : 65536, false))) return st;
       }
 #endif
       mark(run, run.ev.round_end[r]);
@@ -1026,26 +780,21 @@ class Engine : public ResidentSets<Cfg> {
     int st = planner_.make_plan(pl, n64, false, opt, (uint32_t)pts.n, false);
     if (st) return st;
     Run run = new_run(opt);
-    if ((st = sort_phase(pl, planner_.sort_layout(pl), d_scalars, run, 0)) || (st = fetch_meta(run))) return st;
+    MsmMeta* d_meta = meta_.template as<MsmMeta>();
+    if ((st = sort_.run(pl, planner_.sort_layout(pl), d_scalars, run, stream_, d_meta, 0)) || (st = fetch_meta(run))) return st;
     if (h_meta_->error & 4u) return MSMZ_ERR_RANGE;
     run.n_pairs = run.n_entries;   // (no tree rounds: every entry is added into its chunk's accumulator)
-    if ((st = partials_.ensure((size_t)32 * pl.nblocks * 4))) return st;
     constexpr int AW = P::ACC_WORDS;
-    const uint32_t nb = pl.nb, nblocks = pl.nblocks;
-    MsmMeta* d_meta = meta_.template as<MsmMeta>();
+    const uint32_t nb = pl.nb;
     mark(run, run.ev.plan0);
     // chunk offsets: cscan[g] = sum_{g' < g} ceil(size / 2^chunk_shift); chunks of 64 entries unless some bucket is
     // very long (then ~sqrt of it: bounds both the chunk and the number of partial sums one reduction thread adds)
     int chunk_shift = chunk_shift_override_ > 0 ? chunk_shift_override_ : ACC_CHUNK_SHIFT;
     while ((1ull << (2 * chunk_shift)) < run.max_bucket) chunk_shift++;
-    const int scan_mode = 2 | (chunk_shift << 4);
     if ((st = rscan_.ensure(((size_t)nb + 1) * 4))) return st;
-    hipLaunchKernelGGL(k_scan_partials, dim3(nblocks, 1), dim3(SCAN_T), 0, stream_, partials_.as<uint32_t>(),
-                       off_.as<uint32_t>(), nb, scan_mode, nblocks);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(SCAN_T), 0, stream_, partials_.as<uint32_t>(), nblocks,
-                       d_meta->round_pairs);
-    hipLaunchKernelGGL(k_scan_apply, dim3(nblocks, 1), dim3(SCAN_T), 0, stream_, rscan_.as<uint32_t>(),
-                       partials_.as<uint32_t>(), off_.as<uint32_t>(), nb, scan_mode, nblocks, (size_t)0, (uint32_t*)nullptr);
+    if ((st = scan_exclusive(stream_, partials_, rscan_.as<uint32_t>(), sort_.off(), nb, chunk_shift, d_meta->round_pairs,
+                             nullptr)))
+      return st;
     MSMZ_HIP(hipMemcpyAsync(h_meta_.p, d_meta, sizeof(MsmMeta), hipMemcpyDeviceToHost, stream_));
     MSMZ_HIP(hipStreamSynchronize(stream_));
     const uint32_t n_chunks = h_meta_->round_pairs[0];
@@ -1053,8 +802,8 @@ class Engine : public ResidentSets<Cfg> {
     if ((st = slots_.ensure((size_t)(n_chunks + 1) * AW * 4))) return st;
     if (n_chunks > 0) {
       hipLaunchKernelGGL((k_bucket_accumulate<P>), dim3((n_chunks + 127) / 128), dim3(128), 0, stream_,
-                         slots_.as<uint32_t>(), d_points, refs_.as<uint32_t>(), off_.as<uint32_t>(),
-                         rscan_.as<uint32_t>(), nb, n_chunks, chunk_shift);
+                         slots_.as<uint32_t>(), d_points, sort_.refs(), sort_.off(), rscan_.as<uint32_t>(), nb,
+                         n_chunks, chunk_shift);
     }
     mark(run, run.ev.acc_end);
     // every bucket is visited twice: buckets of several chunk accumulators (large inputs: Pallas 2^22 has 4,
@@ -1189,7 +938,8 @@ class Engine : public ResidentSets<Cfg> {
                         env_int("MSMZ_NO_FBT", 0) != 0, env_int("MSMZ_NO_PLAN_TOP", 0) != 0,
                         env_int("MSMZ_NO_SORT_SPECIAL", 0) != 0, env_int("MSMZ_FB", 0), (uint32_t)env_int("MSMZ_S1", 0),
                         (uint32_t)env_int("MSMZ_R2_NC", 0)}};
-  DevBuf bsum_, f2desc_, tilecnt_, tileoff_, final_, desc_, bfin_, packed_, bins_, digits_, counts_, off_, cursor_, refs_, rscan_, partials_, slots_, red_[4];
+  BucketSort<Fr, TE> sort_;   // the sort stage: its buffers, the sorted references and bucket offsets included
+  DevBuf bsum_, f2desc_, final_, desc_, bfin_, rscan_, partials_, slots_, red_[4];   // (partials_: msmBasic's chunk scan)
   DevBuf segs_;         // run_segments: the descriptor table of a sub-batch ...
   PinnedBuf h_segs_;    // ... and its pinned host copy (rewritten only after the sub-batch's final fetch)
   TestHooks<Cfg> hooks_{*this};

@@ -90,15 +90,10 @@
                                                      uint32_t, uint32_t*);                                        \
   PFX template __global__ void k_test_accs_out<P>(uint32_t*, const uint32_t*, uint32_t);
 
-// sort kernels: window size 0 = any, 16 / 17 = the defaults of large inputs (window loop unrolled)
-#define MSMZ_INST_SORT(Fr, GLV, C, PFX)                                                                           \
-  PFX template __global__ void k_hist<Fr, GLV, C>(uint32_t*, uint16_t*, uint32_t*, MsmMeta*, const uint32_t*, SortGeom, uint32_t); \
-  PFX template __global__ void k_coarse<Fr, GLV, C>(uint32_t*, const uint32_t*, const uint32_t*, const uint16_t*, const uint32_t*, SortGeom, uint32_t);
-
-// ... and their segmented variants (msmz_msm_segments: the batched pipeline, Weierstrass curves only)
-#define MSMZ_INST_SORT_SEG(Fr, GLV, C, PFX)                                                                       \
-  PFX template __global__ void k_hist_seg<Fr, GLV, C>(uint32_t*, uint16_t*, uint32_t*, MsmMeta*, const uint32_t*, SortGeom, uint32_t, const SegDesc*); \
-  PFX template __global__ void k_coarse_seg<Fr, GLV, C>(uint32_t*, const uint32_t*, const uint32_t*, const uint16_t*, const uint32_t*, SortGeom, uint32_t, const SegDesc*);
+// one instance of the sort kernels (the list: MSMZ_SORT_INSTANCES, sort_kernels.h)
+#define MSMZ_INST_SORT(Fr, PFX, GLV, C, SEG)                                                                      \
+  PFX template __global__ void k_hist<Fr, GLV, C, SEG>(uint32_t*, uint16_t*, uint32_t*, MsmMeta*, const uint32_t*, SortGeom, uint32_t, const SegDesc*); \
+  PFX template __global__ void k_coarse<Fr, GLV, C, SEG>(uint32_t*, const uint32_t*, const uint32_t*, const uint16_t*, const uint32_t*, SortGeom, uint32_t, const SegDesc*);
 
 // the recurrence kernels of one mode (scan_kernels.h): AM = how the multiplier arrives, HB = is there an addend
 #define MSMZ_INST_SCAN(Fr, AM, HB, PFX)                                                                           \
@@ -107,9 +102,7 @@
 
 #define MSMZ_INST_SCALAR(Fr, PFX)                                                                                 \
   PFX template __global__ void k_digits<Fr, false>(uint32_t*, uint32_t*, MsmMeta*, const uint32_t*, uint32_t, int, int, int, int); \
-  MSMZ_INST_SORT(Fr, false, 0, PFX)                                                                               \
-  MSMZ_INST_SORT(Fr, false, 16, PFX)                                                                              \
-  MSMZ_INST_SORT(Fr, false, 17, PFX)                                                                              \
+  MSMZ_SORT_INSTANCES(MSMZ_INST_SORT, Fr, PFX)                                                                    \
   PFX template __global__ void k_check_scalars<Fr>(uint32_t*, const uint32_t*, uint32_t);                         \
   PFX template __global__ void k_gen_scalars<Fr>(uint32_t*, uint32_t, uint64_t, GenMap);                          \
   PFX template __global__ void k_import_scalars<Fr>(uint32_t*, const uint8_t*, uint64_t, int, uint32_t, int, uint32_t*); \
@@ -144,13 +137,7 @@
   MSMZ_INST_MISC_P(F, Fr, WeierPolicy<F>, PFX)                                                                    \
   PFX template __global__ void k_precompute_copy<F>(uint32_t*, const uint32_t*, uint32_t, int, int);              \
   PFX template __global__ void k_digits<Fr, true>(uint32_t*, uint32_t*, MsmMeta*, const uint32_t*, uint32_t, int, int, int, int); \
-  MSMZ_INST_SORT(Fr, true, 0, PFX)                                                                                \
-  MSMZ_INST_SORT(Fr, true, 16, PFX)                                                                               \
-  MSMZ_INST_SORT_SEG(Fr, true, 0, PFX)                                                                            \
-  MSMZ_INST_SORT_SEG(Fr, true, 16, PFX)                                                                           \
-  MSMZ_INST_SORT_SEG(Fr, false, 0, PFX)                                                                           \
-  MSMZ_INST_SORT_SEG(Fr, false, 16, PFX)                                                                          \
-  MSMZ_INST_SORT_SEG(Fr, false, 17, PFX)                                                                          \
+  MSMZ_SORT_INSTANCES_WEIERSTRASS(MSMZ_INST_SORT, Fr, PFX)                                                        \
   PFX template __global__ void k_test_digits<Fr, true>(uint32_t*, const uint32_t*, uint32_t, int, int);           \
   PFX template __global__ void k_test_slots_in<F>(uint32_t*, const uint32_t*, const uint8_t*, uint32_t, uint32_t*); \
   PFX template __global__ void k_test_slots_out<F>(uint32_t*, const uint32_t*, uint32_t, uint32_t);

@@ -10,7 +10,8 @@
 //                        -- which copies 116-byte points; here 4-byte references are sorted and points are gathered
 //                        on first use)
 //   k_digits, k_scan_*,  fallback sort for window sizes whose coarse bins do not fit the LDS staging (digits
-//   k_scatter            materialized, one global atomic per entry); k_scan_* also serve the msmBasic path's chunk offsets
+//   k_scatter            materialized, one global atomic per entry; k_digits: sort_kernels.h); k_scan_* also serve the
+//                        msmBasic path's chunk offsets
 //   k_plan_count,        (plan_kernels.h) the schedule of the tree rounds as data: rounds decided on the device, one
 //   k_plan_emit          {locA, locB} descriptor per addition (msm-batched-affine.ts:232-247), final locations per bucket
 //   k_batch_add          (batch_kernels.h) one tree round of batched-affine additions, with a workgroup-wide Montgomery
@@ -96,6 +97,14 @@ __device__ __forceinline__ void store_words(uint32_t* dst, const uint32_t* src, 
     u32x4 v = {src[4 * i], src[4 * i + 1], src[4 * i + 2], src[4 * i + 3]};
     if (NT) __builtin_nontemporal_store(v, d4 + i * cs); else d4[i * cs] = v;
   }
+}
+
+// record i of a scalar set (32 bytes, 16-byte aligned) -> s[0 .. 8): two 16-byte loads
+__device__ __forceinline__ void load_scalar(uint32_t* s, const uint32_t* set, uint64_t i) {
+  const uint4* p4 = reinterpret_cast<const uint4*>(set + i * 8);
+  const uint4 a = p4[0], b = p4[1];
+  s[0] = a.x; s[1] = a.y; s[2] = a.z; s[3] = a.w;
+  s[4] = b.x; s[5] = b.y; s[6] = b.z; s[7] = b.w;
 }
 
 // load an affine point record; returns true if it is the point at infinity
@@ -275,108 +284,29 @@ __device__ __forceinline__ void store_fe4(uint32_t* rec, const Fe<F>& a, const F
   store_words<F>(rec + 2 * F::NW, w);
 }
 
-// ------------------------------------------------------------------------------------------------ digits (fallback sort)
-// Used only when the window size leaves more coarse bins than the LDS-staged sort handles (sort_kernels.h): the
-// digits are materialized, digits[k*M + i] for i in [0, M) -- M = N (no GLV) or 2N (GLV: entry N+i is the
-// endomorphism half) -- and counts[] is the per-bucket histogram (one global atomic per entry).
-// `spread` = sb > 0: the top window has few significant bits, so its entries are dealt over 2^sb
-// sub-windows K-1 .. K-1+2^sb-1 by the low bits of the point index (every sub-window keeps the weight
-// 2^(c(K-1))); this keeps bucket sizes balanced (the job of splitBuckets' special case for the sparse top
-// window, msm-common.ts:105-112, 146-174).
-constexpr int DIGITS_ITEMS = 8;
-
-template <class Fr, bool GLV>
-__global__ void __launch_bounds__(256) k_digits(uint32_t* digits, uint32_t* counts, MsmMeta* meta, const uint32_t* scalars,
-                                                uint32_t n, int c, int K, int spread, int sbits) {
-  const uint32_t L = 1u << (c - 1);
-  const uint32_t M = GLV ? 2 * n : n;
-  const uint32_t smask = (1u << spread) - 1u;
-  uint32_t bad = 0;
-#pragma unroll 1
-  for (int item = 0; item < DIGITS_ITEMS; item++) {
-    const uint32_t i = (blockIdx.x * DIGITS_ITEMS + item) * 256 + threadIdx.x;
-    if (i >= n) continue;
-    uint32_t s[8];
-    {
-      const uint4* p4 = reinterpret_cast<const uint4*>(scalars + (size_t)i * 8);
-      uint4 a = p4[0], b = p4[1];
-      s[0] = a.x; s[1] = a.y; s[2] = a.z; s[3] = a.w;
-      s[4] = b.x; s[5] = b.y; s[6] = b.z; s[7] = b.w;
-    }
-    if (words_geq<8>(s, Fr::Q) || words_geq_pow2(s, sbits)) {   // flagged, and no digit (as DigitStream::clear)
-      bad |= 4u;
-#pragma unroll
-      for (int j = 0; j < 8; j++) s[j] = 0;
-    }
-    constexpr int HALVES = GLV ? 2 : 1;
-    constexpr int HW = GLV ? 4 : 8;
-    uint32_t h[HALVES][HW], neg[HALVES];
-    if constexpr (GLV) {
-      glv_decompose<Fr>(h[0], h[1], neg[0], neg[1], s);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; j++) h[0][j] = s[j];
-      neg[0] = 0;
-    }
-#pragma unroll
-    for (int half = 0; half < HALVES; half++) {
-      uint32_t carry = 0;
-      for (int k = 0; k < K; k++) {
-        uint32_t l = extract_bits<HW>(h[half], k * c, c) + carry;
-        if (l > L) {
-          l = 2 * L - l;
-          carry = 1;
-        } else {
-          carry = 0;
-        }
-        // the half scalar's own sign flips every digit's sign
-        const uint32_t ng = (carry ^ neg[half]) & (l != 0 ? 1u : 0u);
-        const uint32_t entry = half * n + i;
-        digits[(size_t)k * M + entry] = l | (ng << 31);
-        if (l != 0) {
-          const uint32_t kw = k == K - 1 ? (uint32_t)k + (entry & smask) : (uint32_t)k;
-          atomicAdd(&counts[kw * L + (l - 1)], 1u);
-        }
-      }
-      // does the scalar fit K windows?  (a carry out of the last one, or bits beyond it)
-      if (carry) bad |= 2u;
-      for (int pos = K * c; pos < 32 * HW; pos += 16)
-        if (extract_bits<HW>(h[half], pos, 16) != 0) bad |= 2u;
-    }
-  }
-  if (bad) atomicOr(&meta->error, bad);
-}
-
 // upload-time range check of resident scalars (scalarsFromBytes, parallel.ts:114-133: values < group order)
 template <class Fr>
 __global__ void __launch_bounds__(256) k_check_scalars(uint32_t* err, const uint32_t* scalars, uint32_t n) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   uint32_t s[8];
-  const uint4* p4 = reinterpret_cast<const uint4*>(scalars + (size_t)i * 8);
-  const uint4 a = p4[0], b = p4[1];
-  s[0] = a.x; s[1] = a.y; s[2] = a.z; s[3] = a.w;
-  s[4] = b.x; s[5] = b.y; s[6] = b.z; s[7] = b.w;
+  load_scalar(s, scalars, i);
   if (words_geq<8>(s, Fr::Q)) atomicOr(err, 4u);
 }
 
 // ------------------------------------------------------------------------------------------------ scans
-// Exclusive scan of n values v(g) in three launches; out has n + 1 entries (out[n] = total).
-//   mode 0: v(g) = in[g]                                   (bucket sizes -> offsets)
-//   mode 1: v(g) = pairs in round r of bucket g, r = blockIdx.y, from bucket offsets `in`
-//           pairs_m(s) = floor((s + m - 1) / (2m)), m = 2^r  (number of j with j*2m + m < s)
+// Exclusive scan of n values v(g) in three launches (scan_exclusive, sort.h); out has n + 1 entries (out[n] = total).
+//   chunk_shift = SCAN_VALUES: v(g) = in[g]                           (bucket sizes -> offsets)
+//   chunk_shift >= 0:          v(g) = chunks of 2^chunk_shift entries in bucket g, from bucket offsets `in`
+//                                                                     (msmBasic accumulation)
 //   (SCAN_T threads x SCAN_ITEMS values per workgroup: plan.h)
+constexpr int SCAN_VALUES = -1;
 
-__device__ __forceinline__ uint32_t scan_value(const uint32_t* in, uint32_t g, uint32_t n, int mode, int r) {
+__device__ __forceinline__ uint32_t scan_value(const uint32_t* in, uint32_t g, uint32_t n, int chunk_shift) {
   if (g >= n) return 0;
-  if (mode == 0) return in[g];
-  uint32_t s = in[g + 1] - in[g];
-  if ((mode & 15) == 2) {                // chunks of 2^(mode >> 4) entries (msmBasic accumulation)
-    const int sh = mode >> 4;
-    return (s + (1u << sh) - 1u) >> sh;
-  }
-  uint32_t m = 1u << r;
-  return (s + m - 1) >> (r + 1);
+  if (chunk_shift == SCAN_VALUES) return in[g];
+  const uint32_t s = in[g + 1] - in[g];
+  return (s + (1u << chunk_shift) - 1u) >> chunk_shift;
 }
 
 template <int T = 256>
@@ -403,57 +333,52 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* t
   return base + x - v;
 }
 
-static __global__ void __launch_bounds__(SCAN_T) k_scan_partials(uint32_t* partials, const uint32_t* in, uint32_t n, int mode,
-                                                          uint32_t nblocks) {
+static __global__ void __launch_bounds__(SCAN_T) k_scan_partials(uint32_t* partials, const uint32_t* in, uint32_t n,
+                                                                 int chunk_shift) {
   __shared__ uint32_t lds[SCAN_T / 64];
-  const int r = blockIdx.y;
   uint32_t base = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
   uint32_t sum = 0;
 #pragma unroll
-  for (int j = 0; j < SCAN_ITEMS; j++) sum += scan_value(in, base + j, n, mode, r);
+  for (int j = 0; j < SCAN_ITEMS; j++) sum += scan_value(in, base + j, n, chunk_shift);
   uint32_t total;
   block_exclusive_scan(sum, &total, lds);
-  if (threadIdx.x == 0) partials[(size_t)r * nblocks + blockIdx.x] = total;
+  if (threadIdx.x == 0) partials[blockIdx.x] = total;
 }
 
-// one block per round: exclusive scan of the per-tile partials (in place); writes the grand total
-static __global__ void __launch_bounds__(SCAN_T) k_scan_top(uint32_t* partials, uint32_t nblocks, uint32_t* totals) {
+// one workgroup: exclusive scan of the per-tile partials (in place); writes the grand total
+static __global__ void __launch_bounds__(SCAN_T) k_scan_top(uint32_t* partials, uint32_t nblocks, uint32_t* total_out) {
   __shared__ uint32_t lds[SCAN_T / 64];
-  const int r = blockIdx.x;
-  uint32_t* p = partials + (size_t)r * nblocks;
   uint32_t running = 0;
   for (uint32_t start = 0; start < nblocks; start += SCAN_T) {
     uint32_t idx = start + threadIdx.x;
-    uint32_t v = idx < nblocks ? p[idx] : 0;
+    uint32_t v = idx < nblocks ? partials[idx] : 0;
     uint32_t total;
     uint32_t ex = block_exclusive_scan(v, &total, lds);
-    if (idx < nblocks) p[idx] = running + ex;
+    if (idx < nblocks) partials[idx] = running + ex;
     running += total;
   }
-  if (threadIdx.x == 0) totals[r] = running;
+  if (threadIdx.x == 0) *total_out = running;
 }
 
+// max_out (may be null): atomicMax with the largest value
 static __global__ void __launch_bounds__(SCAN_T) k_scan_apply(uint32_t* out, const uint32_t* partials, const uint32_t* in,
-                                                       uint32_t n, int mode, uint32_t nblocks, size_t out_stride,
-                                                       uint32_t* max_out) {
+                                                              uint32_t n, int chunk_shift, uint32_t* max_out) {
   __shared__ uint32_t lds[SCAN_T / 64];
-  const int r = blockIdx.y;
   uint32_t base = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
   uint32_t v[SCAN_ITEMS], sum = 0, mx = 0;
 #pragma unroll
   for (int j = 0; j < SCAN_ITEMS; j++) {
-    v[j] = scan_value(in, base + j, n, mode, r);
+    v[j] = scan_value(in, base + j, n, chunk_shift);
     sum += v[j];
     mx = v[j] > mx ? v[j] : mx;
   }
   uint32_t total;
-  uint32_t ex = block_exclusive_scan(sum, &total, lds) + partials[(size_t)r * nblocks + blockIdx.x];
-  uint32_t* o = out + (size_t)r * out_stride;
+  uint32_t ex = block_exclusive_scan(sum, &total, lds) + partials[blockIdx.x];
 #pragma unroll
   for (int j = 0; j < SCAN_ITEMS; j++) {
-    if (base + j < n) o[base + j] = ex;
+    if (base + j < n) out[base + j] = ex;
     ex += v[j];
-    if (base + j + 1 == n) o[n] = ex;
+    if (base + j + 1 == n) out[n] = ex;
   }
   if (max_out != nullptr && mx != 0) atomicMax(max_out, mx);
 }

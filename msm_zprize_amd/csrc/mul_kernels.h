@@ -85,10 +85,7 @@ template <class Fr>
 __device__ __forceinline__ void mul_load_scalar(uint32_t* s, const uint32_t* scalars, const MulScalar& bc, uint32_t i,
                                                 uint32_t* err) {
   if (scalars) {
-    const uint4* p4 = reinterpret_cast<const uint4*>(scalars + (size_t)i * 8);
-    const uint4 a = p4[0], b = p4[1];
-    s[0] = a.x; s[1] = a.y; s[2] = a.z; s[3] = a.w;
-    s[4] = b.x; s[5] = b.y; s[6] = b.z; s[7] = b.w;
+    load_scalar(s, scalars, i);
     if (words_geq<8>(s, Fr::Q)) atomicOr(err, 4u);
   } else {
 #pragma unroll

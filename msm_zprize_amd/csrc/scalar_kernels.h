@@ -54,10 +54,7 @@ static_assert((1 << MULTI_BLOCK_SHIFT) % SPOW_RUN == 0, "a run of powers stays i
 // record i of a scalar set -> s; true if it is >= q
 template <class Fr>
 __device__ __forceinline__ bool fr_load(uint32_t* s, const uint32_t* set, uint64_t i) {
-  const uint4* p4 = reinterpret_cast<const uint4*>(set + i * 8);
-  const uint4 a = p4[0], b = p4[1];
-  s[0] = a.x; s[1] = a.y; s[2] = a.z; s[3] = a.w;
-  s[4] = b.x; s[5] = b.y; s[6] = b.z; s[7] = b.w;
+  load_scalar(s, set, i);
   return words_geq<8>(s, Fr::Q);
 }
 

@@ -15,6 +15,7 @@
 //   k_coarse      THE bucket scatter: reads scalars again (32 B each), slices all K windows, ranks a tile's entries
 //                 per bin in LDS and writes (fine | negate | index) words in contiguous runs: 32 B in + 4 K B out per
 //                 scalar, nothing else
+//   k_digits      the fallback sort's slicer (with k_scan_* and k_scatter of kernels.h): the digits materialized
 //   k_fine        one workgroup per coarse bin (<= 2048 buckets, <= 37888 entries): entries pulled into registers
 //                 with all loads in flight at once, LDS histogram -> bucket offsets `off`, every reference placed at
 //                 its sorted position in LDS, streamed out coalesced; also the largest bucket size
@@ -95,10 +96,7 @@ struct DigitStream {
   // it, k_hist and k_coarse alike so that counts and staging agree.
   __device__ __forceinline__ bool load(const uint32_t* scalars, uint32_t i, int sbits) {
     uint32_t s[8];
-    const uint4* p4 = reinterpret_cast<const uint4*>(scalars + (size_t)i * 8);
-    const uint4 a = p4[0], b = p4[1];
-    s[0] = a.x; s[1] = a.y; s[2] = a.z; s[3] = a.w;
-    s[4] = b.x; s[5] = b.y; s[6] = b.z; s[7] = b.w;
+    load_scalar(s, scalars, i);
     carry = 0;
     if constexpr (GLV) {
       uint32_t n0, n1;
@@ -186,6 +184,51 @@ struct DigitStream {
   }
 };
 
+// ------------------------------------------------------------------------------------------------ digits (fallback sort)
+// Used only when the window size leaves more coarse bins than the LDS-staged sort handles: the digits are materialized,
+// digits[k*M + i] for i in [0, M) -- M = N (no GLV) or 2N (GLV: entry N+i is the endomorphism half) -- and counts[] is
+// the per-bucket histogram (one global atomic per entry).  The error bits are k_hist's: |= 4 for a scalar that
+// DigitStream::load refuses (cleared: all its digits are 0), |= 2 for one that does not fit K windows.
+// `spread` = sb > 0: the top window has few significant bits, so its entries are dealt over 2^sb
+// sub-windows K-1 .. K-1+2^sb-1 by the low bits of the point index (every sub-window keeps the weight
+// 2^(c(K-1))); this keeps bucket sizes balanced (the job of splitBuckets' special case for the sparse top
+// window, msm-common.ts:105-112, 146-174).
+constexpr int DIGITS_ITEMS = 8;
+
+template <class Fr, bool GLV>
+__global__ void __launch_bounds__(256) k_digits(uint32_t* digits, uint32_t* counts, MsmMeta* meta, const uint32_t* scalars,
+                                                uint32_t n, int c, int K, int spread, int sbits) {
+  const uint32_t L = 1u << (c - 1);
+  const uint32_t M = GLV ? 2 * n : n;
+  const uint32_t smask = (1u << spread) - 1u;
+  uint32_t bad = 0;
+#pragma unroll 1
+  for (int item = 0; item < DIGITS_ITEMS; item++) {
+    const uint32_t i = (blockIdx.x * DIGITS_ITEMS + item) * 256 + threadIdx.x;
+    if (i >= n) continue;
+    DigitStream<Fr, GLV> ds;
+    if (!ds.load(scalars, i, sbits)) {
+      bad |= 4u;
+      ds.clear();
+    }
+#pragma unroll
+    for (int half = 0; half < DigitStream<Fr, GLV>::HALVES; half++) {
+      const uint32_t entry = half * n + i;
+      for (int k = 0; k < K; k++) {
+        uint32_t ng;
+        const uint32_t l = ds.next(half, k, c, L, ng);
+        digits[(size_t)k * M + entry] = l | (ng << 31);
+        if (l != 0) {
+          const uint32_t kw = k == K - 1 ? (uint32_t)k + (entry & smask) : (uint32_t)k;
+          atomicAdd(&counts[kw * L + (l - 1)], 1u);
+        }
+      }
+    }
+    if (ds.overflows(K, c)) bad |= 2u;
+  }
+  if (bad) atomicOr(&meta->error, bad);
+}
+
 // (Measured: matching equal keys across the wave with ballots so that one lane per key issues the LDS atomic costs
 // ~80 VALU instructions per wave instruction and made k_hist 2.2x and k_coarse 1.5x SLOWER than plain per-lane LDS
 // atomics, which cost ~24 LDS cycles per wave instruction here.)
@@ -196,6 +239,17 @@ __device__ __forceinline__ uint32_t coarse_bin(const SortGeom& g, int k, uint32_
   if (k == g.K - 1) return (uint32_t)k * g.ncb + (entry & ((1u << g.spread) - 1u)) * g.ncbt + (bi >> g.fbt);
   return (uint32_t)k * g.ncb + (bi >> g.fb);
 }
+
+// THE list of the compiled instances (GLV, C, SEG) of k_hist and k_coarse, as X(args..., GLV, C, SEG): it drives the
+// explicit instantiations (instantiate.h), the raising of the LDS limits and the launch dispatch (sort.h).  C = 0: any
+// window size; 16 / 17: the defaults of large inputs (window loop unrolled).  k_fine has SEG alone.
+#define MSMZ_SORT_INSTANCES(X, ...) \
+  X(__VA_ARGS__, false, 0, false) X(__VA_ARGS__, false, 16, false) X(__VA_ARGS__, false, 17, false)
+// ... and what only the Weierstrass curves have: GLV, and the segmented MSM (the batched pipeline)
+#define MSMZ_SORT_INSTANCES_WEIERSTRASS(X, ...)                                                     \
+  X(__VA_ARGS__, true, 0, false) X(__VA_ARGS__, true, 16, false)                                    \
+  X(__VA_ARGS__, false, 0, true) X(__VA_ARGS__, false, 16, true) X(__VA_ARGS__, false, 17, true)    \
+  X(__VA_ARGS__, true, 0, true) X(__VA_ARGS__, true, 16, true)
 
 // ------------------------------------------------------------------------------------------------ histogram
 // counts[bin] += entries; meta->error |= 2 when a scalar does not fit K windows (a GLV half above the assumed
@@ -305,16 +359,11 @@ __device__ __forceinline__ void hist_tile(uint32_t* counts, uint16_t* tile_count
     if (b < nbins) roff[b] = r[q];
   }
 }
-template <class Fr, bool GLV, int C>
+// (the kernels are thin wrappers: written as the kernel itself, the same body compiles to slightly different code)
+template <class Fr, bool GLV, int C, bool SEG>
 __global__ void __launch_bounds__(COARSE_T, 8) k_hist(uint32_t* counts, uint16_t* tile_counts, uint32_t* tile_offs, MsmMeta* meta,
-                                                 const uint32_t* scalars, SortGeom g, uint32_t nbins) {
-  hist_tile<Fr, GLV, C, false>(counts, tile_counts, tile_offs, meta, scalars, g, nbins, nullptr);
-}
-template <class Fr, bool GLV, int C>
-__global__ void __launch_bounds__(COARSE_T, 8) k_hist_seg(uint32_t* counts, uint16_t* tile_counts, uint32_t* tile_offs,
-                                                          MsmMeta* meta, const uint32_t* scalars, SortGeom g, uint32_t nbins,
-                                                          const SegDesc* segs) {
-  hist_tile<Fr, GLV, C, true>(counts, tile_counts, tile_offs, meta, scalars, g, nbins, segs);
+                                                      const uint32_t* scalars, SortGeom g, uint32_t nbins, const SegDesc* segs) {
+  hist_tile<Fr, GLV, C, SEG>(counts, tile_counts, tile_offs, meta, scalars, g, nbins, segs);
 }
 
 // exclusive scan of nbins <= SORT_MAX_BINS counts by one workgroup; base[nbins] = total = number of entries
@@ -554,18 +603,11 @@ __device__ __forceinline__ void coarse_tile(uint32_t* packed_out, const uint32_t
   }
   MSMZ_STAMP(trace, 4);
 }
-template <class Fr, bool GLV, int C>
+template <class Fr, bool GLV, int C, bool SEG>
 __global__ void __launch_bounds__(COARSE_T, 8) k_coarse(uint32_t* packed_out, const uint32_t* tile_offs, const uint32_t* bin_base,
                                                         const uint16_t* tile_counts, const uint32_t* scalars, SortGeom g,
-                                                        uint32_t nbins) {
-  coarse_tile<Fr, GLV, C, false>(packed_out, tile_offs, bin_base, tile_counts, scalars, g, nbins, nullptr);
-}
-template <class Fr, bool GLV, int C>
-__global__ void __launch_bounds__(COARSE_T, 8) k_coarse_seg(uint32_t* packed_out, const uint32_t* tile_offs,
-                                                            const uint32_t* bin_base, const uint16_t* tile_counts,
-                                                            const uint32_t* scalars, SortGeom g, uint32_t nbins,
-                                                            const SegDesc* segs) {
-  coarse_tile<Fr, GLV, C, true>(packed_out, tile_offs, bin_base, tile_counts, scalars, g, nbins, segs);
+                                                        uint32_t nbins, const SegDesc* segs) {
+  coarse_tile<Fr, GLV, C, SEG>(packed_out, tile_offs, bin_base, tile_counts, scalars, g, nbins, segs);
 }
 
 // ------------------------------------------------------------------------------------------------ fine sort
@@ -741,20 +783,13 @@ static __device__ __forceinline__ void fine_bin(uint32_t* refs, uint32_t* off, u
     MSMZ_STAMP(trace, 5);
   }
 }
+template <bool SEG>
 static __global__ void __launch_bounds__(FINE_T) k_fine(uint32_t* refs, uint32_t* off, uint32_t* max_bucket,
-                                                 const uint32_t* packed, const uint32_t* bin_base, int fb, int fbt,
-                                                 uint32_t top_bin, uint32_t n_bins, int idx_bits, uint32_t n_half,
-                                                 uint32_t endo_delta, uint32_t group, int mbits, uint32_t copy_stride) {
-  fine_bin<false>(refs, off, max_bucket, packed, bin_base, fb, fbt, top_bin, n_bins, idx_bits, n_half, endo_delta, group,
-                  mbits, copy_stride, nullptr);
+                                                        const uint32_t* packed, const uint32_t* bin_base, int fb, int fbt,
+                                                        uint32_t top_bin, uint32_t n_bins, int idx_bits, uint32_t n_half,
+                                                        uint32_t endo_delta, uint32_t group, int mbits, uint32_t copy_stride,
+                                                        const SegDesc* segs) {
+  fine_bin<SEG>(refs, off, max_bucket, packed, bin_base, fb, fbt, top_bin, n_bins, idx_bits, n_half, endo_delta, group, mbits,
+                copy_stride, segs);
 }
-static __global__ void __launch_bounds__(FINE_T) k_fine_seg(uint32_t* refs, uint32_t* off, uint32_t* max_bucket,
-                                                     const uint32_t* packed, const uint32_t* bin_base, int fb, int fbt,
-                                                     uint32_t top_bin, uint32_t n_bins, int idx_bits, uint32_t n_half,
-                                                     uint32_t endo_delta, uint32_t group, int mbits, uint32_t copy_stride,
-                                                     const SegDesc* segs) {
-  fine_bin<true>(refs, off, max_bucket, packed, bin_base, fb, fbt, top_bin, n_bins, idx_bits, n_half, endo_delta, group,
-                 mbits, copy_stride, segs);
-}
-
 }  // namespace msmz

@@ -73,7 +73,7 @@ struct Staging {
 };
 
 // The hooks of one engine.  A friend of Engine<Cfg>: the hooks launch on its stream, into its buffers, and run its own
-// phases (sort_phase, plan_phase, launch_batch_add_b, bucket_sums, the two halves of reduce_2d, reduce_levels).  Its planner and its
+// sort stage (BucketSort::run, sort.h) and phases (plan_phase, launch_batch_add_b, bucket_sums, the two halves of reduce_2d, reduce_levels).  Its planner and its
 // reduction thresholds they only read, and vary in copies.
 template <class Cfg>
 class TestHooks : public ITestHooks {
@@ -165,17 +165,17 @@ class TestHooks : public ITestHooks {
     memcpy(geom, g8, sizeof(g8));
     if (off) {
       if (off_cap < (uint64_t)nb + 1) return MSMZ_ERR_ARG;
-      MSMZ_HIP(hipMemcpy(off, eng_.off_.p, ((size_t)nb + 1) * 4, hipMemcpyDeviceToHost));
+      MSMZ_HIP(hipMemcpy(off, eng_.sort_.off(), ((size_t)nb + 1) * 4, hipMemcpyDeviceToHost));
     }
     if (refs) {
       if (refs_cap < n_entries) return MSMZ_ERR_ARG;
-      if (n_entries) MSMZ_HIP(hipMemcpy(refs, eng_.refs_.p, (size_t)n_entries * 4, hipMemcpyDeviceToHost));
+      if (n_entries) MSMZ_HIP(hipMemcpy(refs, eng_.sort_.refs(), (size_t)n_entries * 4, hipMemcpyDeviceToHost));
     }
     return MSMZ_OK;
   }
 
   // The bucket sort at any geometry an MSM plans (msmz_test.h): the planner's plan and layout for the caller's options,
-  // then the engine's own sort_phase.  Everything the kernels index with comes from that plan; what the caller controls
+  // then the engine's sort stage (BucketSort::run, sort.h).  Everything the kernels index with comes from that plan; what the caller controls
   // beyond it (capacities, pts_n, copy_stride) is checked here before anything is launched.
   int test_sort_ex(const msmz_test_sort_args& a) override {
     const uint64_t n = a.n, pts_n = a.pts_n ? a.pts_n : a.n;
@@ -220,7 +220,9 @@ class TestHooks : public ITestHooks {
     const int is = sg.in(a.scalars_le32, (size_t)32 * pl.nprob * n);
     if ((st = sg.upload())) return st;
     Run run = eng_.new_run(opt);
-    if ((st = eng_.sort_phase(pl, sl, sg.at<const uint32_t>(is), run, a.copy_stride)) || (st = eng_.fetch_meta(run)))
+    if ((st = eng_.sort_.run(pl, sl, sg.at<const uint32_t>(is), run, eng_.stream_, eng_.meta_.template as<MsmMeta>(),
+                             a.copy_stride)) ||
+        (st = eng_.fetch_meta(run)))
       return st;
     const uint32_t n_entries = run.n_entries;
     if (n_entries > cap_entries) return MSMZ_ERR_HIP;   // (a broken count: nothing is copied by it)
@@ -229,12 +231,12 @@ class TestHooks : public ITestHooks {
       a.meta[1] = n_entries;
       a.meta[2] = run.max_bucket;
     }
-    if (a.off) MSMZ_HIP(hipMemcpy(a.off, eng_.off_.p, n_off * 4, hipMemcpyDeviceToHost));
-    if (a.refs && n_entries) MSMZ_HIP(hipMemcpy(a.refs, eng_.refs_.p, (size_t)n_entries * 4, hipMemcpyDeviceToHost));
+    if (a.off) MSMZ_HIP(hipMemcpy(a.off, eng_.sort_.off(), n_off * 4, hipMemcpyDeviceToHost));
+    if (a.refs && n_entries) MSMZ_HIP(hipMemcpy(a.refs, eng_.sort_.refs(), (size_t)n_entries * 4, hipMemcpyDeviceToHost));
     if (sl.two_level) {
-      if (a.bins) MSMZ_HIP(hipMemcpy(a.bins, eng_.bins_.p, n_bins * 4, hipMemcpyDeviceToHost));
+      if (a.bins) MSMZ_HIP(hipMemcpy(a.bins, eng_.sort_.bins(), n_bins * 4, hipMemcpyDeviceToHost));
       if (a.packed && n_entries)
-        MSMZ_HIP(hipMemcpy(a.packed, eng_.packed_.p, (size_t)n_entries * 4, hipMemcpyDeviceToHost));
+        MSMZ_HIP(hipMemcpy(a.packed, eng_.sort_.packed(), (size_t)n_entries * 4, hipMemcpyDeviceToHost));
     }
     return MSMZ_OK;
   }
@@ -424,8 +426,8 @@ class TestHooks : public ITestHooks {
     return sg.download();
   }
 
-  // The tree-round schedule on caller-built buckets (msmz_test.h): off / refs go where the sort would have left them,
-  // with the largest bucket in the meta block, then the engine's own plan_phase runs.  Everything the two kernels index
+  // The tree-round schedule on caller-built buckets (msmz_test.h): off / refs go to device buffers of this call, the
+  // largest bucket into the meta block as the sort would have left it, then the engine's own plan_phase runs on them.  Everything the two kernels index
   // with is checked here first: they trust off, the chunk geometry and the capacities.
   int test_plan(const msmz_test_plan_args& a) override {
     if (TE) return MSMZ_ERR_UNSUPPORTED;
@@ -465,10 +467,11 @@ class TestHooks : public ITestHooks {
 
     MSMZ_HIP(hipSetDevice(eng_.device_));
     int st;
-    if ((st = eng_.off_.ensure(((size_t)nb + 1) * 4)) || (st = eng_.refs_.ensure(((size_t)n_entries + 1) * 4))) return st;
-    MSMZ_HIP(hipMemcpyAsync(eng_.off_.p, a.off, ((size_t)nb + 1) * 4, hipMemcpyHostToDevice, eng_.stream_));
+    DevBuf d_off, d_refs;   // (freed on every return)
+    if ((st = d_off.ensure(((size_t)nb + 1) * 4)) || (st = d_refs.ensure(((size_t)n_entries + 1) * 4))) return st;
+    MSMZ_HIP(hipMemcpyAsync(d_off.p, a.off, ((size_t)nb + 1) * 4, hipMemcpyHostToDevice, eng_.stream_));
     if (n_entries)
-      MSMZ_HIP(hipMemcpyAsync(eng_.refs_.p, a.refs, (size_t)n_entries * 4, hipMemcpyHostToDevice, eng_.stream_));
+      MSMZ_HIP(hipMemcpyAsync(d_refs.p, a.refs, (size_t)n_entries * 4, hipMemcpyHostToDevice, eng_.stream_));
     MsmMeta hm;
     memset(&hm, 0, sizeof(hm));
     hm.max_bucket = max_bucket;   // (error = 0: as after a clean sort)
@@ -483,7 +486,7 @@ class TestHooks : public ITestHooks {
     msmz_opts opt;
     memset(&opt, 0, sizeof(opt));
     Run run = eng_.new_run(opt);
-    if ((st = eng_.plan_phase(pc, nb, a.tail_skip, desc_records, run))) return st;
+    if ((st = eng_.plan_phase(pc, d_off.as<uint32_t>(), d_refs.as<uint32_t>(), nb, a.tail_skip, desc_records, run))) return st;
     MSMZ_HIP(hipMemcpyAsync(a.meta, eng_.meta_.p, sizeof(MsmMeta), hipMemcpyDeviceToHost, eng_.stream_));
     if (total) MSMZ_HIP(hipMemcpyAsync(a.desc, eng_.desc_.p, (size_t)total * 8, hipMemcpyDeviceToHost, eng_.stream_));
     MSMZ_HIP(hipMemcpyAsync(a.bfin, eng_.bfin_.p, (size_t)nb * 16, hipMemcpyDeviceToHost, eng_.stream_));

@@ -369,7 +369,7 @@ struct Engine {
   }
 
 
-  // the layout sort_phase computed inline (its two-level branch)
+  // the layout the sort stage once computed inline (its two-level branch)
   struct Sort {
     bool sort2;
     SortGeom g;

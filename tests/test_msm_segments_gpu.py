@@ -130,17 +130,24 @@ def _via_python(d, segs, options, safe=True, which="full", points=None):
 
 
 # ------------------------------------------------------------------------------------------------ one class, one pipeline
-@pytest.mark.parametrize("safe", [1, 0])
-@pytest.mark.parametrize("glv", [0, 1])
-@pytest.mark.parametrize("label", WEIER)
-def test_one_class_is_one_pipeline(data, label, glv, safe):
+# (label, glv, safe, c, segments): the whole class at the planner's window size -- small inputs: the generic sort kernels --
+# and its two shortest members (2048 and 2049 entries: one tile wholly past the shorter one's end, on either tile size)
+# at the window sizes the sort kernels are specialized for, which only a forced c reaches at these lengths
+ONE_CLASS = [(label, glv, safe, 0, CLASS) for safe in (1, 0) for glv in (0, 1) for label in WEIER] + \
+            [("bls12-377", 0, 1, 16, CLASS[:2]), ("bls12-377", 0, 1, 17, CLASS[:2]), ("bls12-377", 1, 1, 16, CLASS[:2])]
+
+
+@pytest.mark.parametrize("label,glv,safe,c,segs", ONE_CLASS,
+                         ids=[f"{l}-{g}-{s}" + (f"-c{c}" if c else "") for l, g, s, c, _ in ONE_CLASS])
+def test_one_class_is_one_pipeline(data, label, glv, safe, c, segs):
     """lengths {2048, 2049, 3000, 4095} at unaligned offsets: trailing empty tiles, a ragged last tile, GLV images read
     at first_p behind a set larger than any segment"""
     d = data(label)
     r0, s0 = passes(d.curve)
-    got = _via_python(d, CLASS, {"glv": glv}, bool(safe))
+    got = _via_python(d, segs, {"glv": glv, "c": c} if c else {"glv": glv}, bool(safe))
     assert passes(d.curve) == (r0, s0 + 1)
-    for k, seg in enumerate(CLASS):
+    assert not c or d.curve.Parallel.lastBatchLog.c == c
+    for k, seg in enumerate(segs):
         assert got[k] == d.want(seg), (k, seg)
 
 

@@ -1,6 +1,6 @@
 """The bucket sort stage by stage, at every geometry an MSM runs it in: msmz_test_sort_ex (include/msmz_test.h) drives
-the engine's own make_plan / sort_layout / sort_phase on caller-built scalars, and every word it returns is compared with
-the host model oracle/sort_ref.py (pinned without a GPU by tests/test_sort_ref_cpu.py).
+the engine's own make_plan / sort_layout / sort stage (BucketSort::run, csrc/sort.h) on caller-built scalars, and every
+word it returns is compared with the host model oracle/sort_ref.py (pinned without a GPU by tests/test_sort_ref_cpu.py).
 
 The comparison is exact and complete: for every problem and every bucket the multiset of reference words, the bucket
 offsets, the scanned bin bases, the packed words of every bin, the entry count, the largest bucket and the error word.  A
@@ -9,7 +9,7 @@ failure names the first stage that disagrees (histogram / scan, k_coarse, k_fine
 Every case names the regimes it is there for, and the test asserts from the reported geometry (and the model's bin
 sizes) that they were reached: a planner change that moves a case out of its regime fails here.
 
-Checked against three one-value mutations of sort_phase's launches (never an address or a count): k_fine without
+Checked against three one-value mutations of BucketSort::run's launches (never an address or a count): k_fine without
 endo_delta (named by glv-prefix, pre-F2-glv-prefix at "k_fine"), k_fine without copy_stride (all five pre-* cases at
 "k_fine"), k_scatter without endo_delta (fallback-glv-prefix at "fallback sort"); bin bases and packed words still agreed,
 so each was attributed to the right stage."""
@@ -119,6 +119,8 @@ CASES += [
     # ---- scalars >= the group order: flagged, no entry
     case("flag-q", "bls12-381", 2 * 2048 + 1, 13, ["flag>=q"], mix="geq"),
     case("flag-q-glv", "bls12-377", 2 * 1024 + 1, 16, ["flag>=q"], mix="geq", glv=1),
+    case("fallback-flag-q", "bls12-377", 1500, 10, ["fallback", "flag>=q"], fallback=1, mix="geq"),
+    case("fallback-flag-q-glv", "bls12-377", 1500, 10, ["fallback", "flag>=q"], fallback=1, mix="geq", glv=1),
 ]
 # ---- caller-given bounds: 2^bits - 1 sorts, 2^bits is flagged and leaves no entry
 for bits in (64, 128):
