@@ -315,7 +315,8 @@ int msmz_check_points(msmz_ctx* ctx, uint64_t points_handle, uint64_t first, uin
  * ed-on-bls12-377: the identity (0, 1)).  The addition of Q is complete: Q = [s]P (a doubling), Q = -[s]P and either
  * operand at infinity are covered.  The inputs need not lie in the subgroup: a point of small order multiplies to what
  * the group law gives.  Of sets with endomorphism images only the base points are read.  Scalars are read whole: plain
- * double-and-add over all bits of the group order's length, one thread per point, 64 points sharing one field inversion.
+ * double-and-add over all bits of the group order's length, one thread per point, 64 points sharing one field inversion
+ * (msmz_points_mul_opts below: shorter chains for bounded scalars and for points known to lie in the subgroup).
  * MSMZ_ERR_ARG, before any launch: a null ctx, descriptor or out_handle; n == 0; an unknown handle or one of the wrong
  * kind; a range [first, first + n) beyond its set; scalars_handle == 0 with a null `scalar`; n beyond the limit of
  * msmz_upload_points.  MSMZ_ERR_UNSUPPORTED: a precomputed handle as P or Q.  MSMZ_ERR_RANGE: the broadcast scalar >= q
@@ -334,6 +335,33 @@ typedef struct msmz_mul {
   uint64_t first_q;
 } msmz_mul;
 int msmz_points_mul(msmz_ctx* ctx, const msmz_mul* m, uint64_t n, uint64_t* out_handle);
+
+/* msmz_points_mul with what the caller knows about its inputs; opts == NULL is msmz_points_mul.
+ * Everything documented there holds, plus:
+ * scalar_bits = b (all four curves): "every scalar of this call is below 2^b".  The chain then walks min(b, bit length
+ * of q) bits instead of all of them -- a 128-bit challenge costs half.  0 = no bound, and b >= the bit length of q means
+ * the same.  The result is byte-identical to the call without the bound.  MSMZ_ERR_RANGE: the broadcast scalar >= 2^b
+ * (found on the host, nothing launched), or a resident scalar >= 2^b inside the addressed range (found by the kernel,
+ * exactly like one >= q: no handle is created, the context stays usable).
+ * MSMZ_MUL_SUBGROUP: the caller vouches that every finite P_i of the range lies in the prime-order subgroup
+ * (msmz_check_points with MSMZ_CHECK_SUBGROUP earns that vouch); Q is not constrained.  On the three Weierstrass curves
+ * the engine may then split s = (+-)k0 + (+-)k1 lambda and walk both halves jointly over the table
+ * {(+-)P, (+-)phi P, their sum}: 126 (BLS12-377) or 128 steps instead of 253 / 255.  For such inputs the result is
+ * byte-identical to the plain call.  For a P_i outside the subgroup record i is UNSPECIFIED -- some point of the curve, or
+ * infinity -- while the call still returns MSMZ_OK, nothing faults and every other record is right.  ed-on-bls12-377 has
+ * no endomorphism: the flag is accepted and changes nothing.
+ * Which chain runs: a bound b <= the proven length of the GLV halves (126 / 128) -> the plain chain of b steps; else the
+ * flag on a Weierstrass curve -> the GLV chain; else the plain chain of min(b, bit length of q) steps.
+ * MSMZ_ERR_ARG: unknown bits in flags, a non-zero reserved word, scalar_bits < 0 or > 256.
+ * Multi-device contexts pass the options to every engine. */
+enum { MSMZ_MUL_SUBGROUP = 1 };
+typedef struct msmz_mul_opts {
+  uint32_t flags;        /* MSMZ_MUL_* */
+  int32_t scalar_bits;   /* every scalar of this call is below 2^scalar_bits; 0 = no bound */
+  int32_t reserved[2];   /* must be 0 */
+} msmz_mul_opts;
+int msmz_points_mul_opts(msmz_ctx* ctx, const msmz_mul* m, uint64_t n, const msmz_mul_opts* opts /* nullable */,
+                         uint64_t* out_handle);
 
 /* Arithmetic mod q over resident scalar sets: linear combinations, inner products and powers of
  * one ratio, so that a prover's witness fold a' = a_lo + u^-1 a_hi, its cross terms <a_lo, b_hi>, a random linear

@@ -40,9 +40,12 @@ export interface ParallelApi {
    * byte per point, bit 0 = not on the curve, bit 1 = on the curve but outside the subgroup */
   checkPoints(points: DeviceArray, n?: number, options?: { subgroup?: boolean; first?: number; verdicts?: boolean }): Promise<CheckResult>;
   /** a new point array: out[i] = [s_i] points[firstPoint + i] (+ addend[firstAddend + i]); scalars: a resident scalar
-   * array or one bigint below the group order for every point; addend may be `points` itself (an IPA fold) */
+   * array or one bigint below the group order for every point; addend may be `points` itself (an IPA fold);
+   * scalarBits: every scalar is below 2^scalarBits (the chain walks that many bits); subgroup: the caller vouches that
+   * every point lies in the prime-order subgroup (the Weierstrass curves then run the GLV chain) */
   mulPoints(scalars: DeviceArray | bigint, points: DeviceArray, n?: number,
-            options?: { addend?: DeviceArray | null; firstPoint?: number; firstScalar?: number; firstAddend?: number }): Promise<DeviceArray>;
+            options?: { addend?: DeviceArray | null; firstPoint?: number; firstScalar?: number; firstAddend?: number;
+                        scalarBits?: number; subgroup?: boolean }): Promise<DeviceArray>;
   /** out[firstOut + i] = a_i x[firstX + i] (+ b_i y[firstY + i]) mod the group order; a, b: one bigint for every entry or
    * a resident scalar array; without `out` a new array, with it that range is overwritten (it may be an input's range
    * exactly, or apart from it) */

@@ -364,8 +364,12 @@ function createCurve(params, kind) {
      * out[i] = [s_i] points[firstPoint + i] (+ addend[firstAddend + i]), i < n.  `scalars` is a resident scalar array
      * (s_i = scalars[firstScalar + i]) or a bigint below the group order: one scalar for every point.  `addend` may be
      * `points` itself (an IPA fold: mulPoints(u, G, n, {addend: G, firstPoint: n})).  The result is an ordinary point
-     * array. */
-    async mulPoints(scalars, points, n, { addend = null, firstPoint = 0, firstScalar = 0, firstAddend = 0 } = {}) {
+     * array.  scalarBits = b: every scalar of the call is below 2^b and the chain walks b bits only (0 = no bound; a
+     * scalar that breaks it fails the call).  subgroup: the caller vouches that every finite point of the range lies
+     * in the prime-order subgroup (checkPoints says so); the Weierstrass curves then run the GLV chain, about half as
+     * long, and for a point outside the subgroup that row of the result is unspecified. */
+    async mulPoints(scalars, points, n, { addend = null, firstPoint = 0, firstScalar = 0, firstAddend = 0, scalarBits = 0,
+                                          subgroup = false } = {}) {
       if (!isPoints(points))
         throw TypeError("mulPoints: `points` is a resident point array (pointsFromBytes / randomPointsFast)");
       if (addend !== null && !isPoints(addend))
@@ -376,8 +380,11 @@ function createCurve(params, kind) {
       if (broadcast && (scalars < 0n || scalars >= params.order)) throw Error(`mulPoints: the scalar ${scalars} is not in [0, group order)`);
       n = scanRanges("mulPoints", [["firstPoint", firstPoint, points], ["firstScalar", firstScalar, broadcast ? null : scalars],
                                    ["firstAddend", firstAddend, addend]], n, null, Infinity);   // (no bound on n here)
+      if (typeof subgroup !== "boolean") throw TypeError(`mulPoints: subgroup = ${subgroup} (true: every point lies in the prime-order subgroup)`);
+      const bits = scalarBitsArg({ scalarBits }, "mulPoints");
+      if (bits && broadcast && scalars >> BigInt(bits)) throw Error(`mulPoints: the scalar ${scalars} is not below 2^${bits} (scalarBits)`);
       const h = N.mulPoints(ctx, points.handle, firstPoint, broadcast ? scalarBuf(scalars) : scalars.handle,
-                            firstScalar, addend === null ? 0 : addend.handle, firstAddend, n);
+                            firstScalar, addend === null ? 0 : addend.handle, firstAddend, n, bits, subgroup ? 1 : 0);
       return DeviceArray.make(curve, h, n, "points");
     },
     /** arithmetic mod the group order over resident scalar arrays (include/msmz.h msmz_scalars_combine):

@@ -46,6 +46,13 @@ class MsmzMul(C.Structure):   # msmz_mul (include/msmz.h): out_i = [s_i] P_i (+ 
                 ("first_s", C.c_uint64), ("scalar", C.c_char_p), ("addend_handle", C.c_uint64), ("first_q", C.c_uint64)]
 
 
+MSMZ_MUL_SUBGROUP = 1
+
+
+class MsmzMulOpts(C.Structure):   # msmz_mul_opts (include/msmz.h): the caller's bound on the scalars and vouch for the points
+    _fields_ = [("flags", C.c_uint32), ("scalar_bits", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class MsmzScalarTerm(C.Structure):   # msmz_scalar_term (include/msmz.h): one term c (.) v of msmz_scalars_combine
     _fields_ = [("handle", C.c_uint64), ("first", C.c_uint64), ("coeff_handle", C.c_uint64), ("coeff_first", C.c_uint64),
                 ("coeff", C.c_char_p)]
@@ -141,6 +148,8 @@ EXPORTS = {
     "msmz_check_points": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                     C.POINTER(MsmzCheckResult), C.c_char_p]),
     "msmz_points_mul": (C.c_int, [C.c_void_p, C.POINTER(MsmzMul), C.c_uint64, C.POINTER(C.c_uint64)]),
+    "msmz_points_mul_opts": (C.c_int, [C.c_void_p, C.POINTER(MsmzMul), C.c_uint64, C.POINTER(MsmzMulOpts),
+                                       C.POINTER(C.c_uint64)]),
     "msmz_scalars_combine": (C.c_int, [C.c_void_p, C.POINTER(MsmzScalarTerm), C.POINTER(MsmzScalarTerm), C.c_uint64,
                                        C.c_uint64, C.POINTER(C.c_uint64)]),
     "msmz_scalars_dot": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_char_p]),

@@ -81,8 +81,8 @@ class IEngine {
   // msmz_check_points over base points [first, first + count) of a plain point handle
   virtual int check_points(uint64_t h, uint64_t first, uint64_t count, uint32_t what, msmz_check_result* out,
                            uint8_t* verdicts) = 0;
-  // msmz_points_mul: a new plain point handle, record i = [s_i] P_i (+ Q_i)
-  virtual int points_mul(const msmz_mul& m, uint64_t n, uint64_t* h) = 0;
+  // msmz_points_mul / msmz_points_mul_opts: a new plain point handle, record i = [s_i] P_i (+ Q_i); o: all zero = none
+  virtual int points_mul(const msmz_mul& m, const msmz_mul_opts& o, uint64_t n, uint64_t* h) = 0;
   // msmz_scalars_combine / _dot / _powers: arithmetic mod q over resident scalar sets (scalar_kernels.h); `map` as for
   // random_scalars
   virtual int scalars_combine(const msmz_scalar_term& x, const msmz_scalar_term* y, uint64_t n, uint64_t first_out,

@@ -128,7 +128,8 @@
   PFX template __global__ void k_import_points<P>(uint32_t*, const uint8_t*, uint64_t, const uint8_t*, uint32_t, int, int, uint32_t*); \
   PFX template __global__ void k_check_curve<P>(uint8_t*, CheckResult*, const uint32_t*, uint32_t, uint32_t);     \
   PFX template __global__ void k_check_subgroup<P, Fr>(uint8_t*, CheckResult*, const uint32_t*, uint32_t, uint32_t); \
-  PFX template __global__ void k_points_mul<P, Fr>(uint32_t*, const uint32_t*, const uint32_t*, MulScalar, const uint32_t*, uint32_t, int, uint32_t*); \
+  PFX template __global__ void k_points_mul<P, Fr, false>(uint32_t*, const uint32_t*, const uint32_t*, MulScalar, const uint32_t*, uint32_t, int, int, uint32_t*); \
+  PFX template __global__ void k_points_mul<P, Fr, true>(uint32_t*, const uint32_t*, const uint32_t*, MulScalar, const uint32_t*, uint32_t, int, int, uint32_t*); \
   MSMZ_INST_TEST(F, Fr, P, PFX)                                                                                   \
   MSMZ_INST_SCALAR(Fr, PFX)
 
@@ -136,6 +137,7 @@
 #define MSMZ_INST_MISC(F, Fr, PFX)                                                                                \
   MSMZ_INST_MISC_P(F, Fr, WeierPolicy<F>, PFX)                                                                    \
   PFX template __global__ void k_precompute_copy<F>(uint32_t*, const uint32_t*, uint32_t, int, int);              \
+  PFX template __global__ void k_points_mul_glv<WeierPolicy<F>, Fr>(uint32_t*, const uint32_t*, const uint32_t*, MulGlvScalar, const uint32_t*, uint32_t, int, int, uint32_t*); \
   PFX template __global__ void k_digits<Fr, true>(uint32_t*, uint32_t*, MsmMeta*, const uint32_t*, uint32_t, int, int, int, int); \
   MSMZ_SORT_INSTANCES_WEIERSTRASS(MSMZ_INST_SORT, Fr, PFX)                                                        \
   PFX template __global__ void k_test_digits<Fr, true>(uint32_t*, const uint32_t*, uint32_t, int, int);           \

@@ -213,7 +213,14 @@ int msmz_check_points(msmz_ctx* c, uint64_t ph, uint64_t first, uint64_t count, 
 }
 
 int msmz_points_mul(msmz_ctx* c, const msmz_mul* m, uint64_t n, uint64_t* h) {
-  return c && m ? c->engine->points_mul(*m, n, h) : MSMZ_ERR_ARG;
+  return msmz_points_mul_opts(c, m, n, nullptr, h);
+}
+int msmz_points_mul_opts(msmz_ctx* c, const msmz_mul* m, uint64_t n, const msmz_mul_opts* opts, uint64_t* h) {
+  const msmz_mul_opts o = opts ? *opts : msmz_mul_opts{};
+  if (!c || !m) return MSMZ_ERR_ARG;
+  if ((o.flags & ~(uint32_t)MSMZ_MUL_SUBGROUP) || o.reserved[0] || o.reserved[1] || o.scalar_bits < 0 || o.scalar_bits > 256)
+    return MSMZ_ERR_ARG;
+  return c->engine->points_mul(*m, o, n, h);
 }
 
 int msmz_scalars_combine(msmz_ctx* c, const msmz_scalar_term* x, const msmz_scalar_term* y, uint64_t n, uint64_t first_out,

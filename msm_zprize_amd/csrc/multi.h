@@ -323,9 +323,10 @@ class MultiEngine : public IEngine {
     });
   }
 
-  // Every engine multiplies its own share of the points; the result is dealt like an upload.  Index i of P, s and Q lives
-  // on one device only when all three ranges start at a block-cycle boundary; only first = 0 is taken.
-  int points_mul(const msmz_mul& m, uint64_t n, uint64_t* h) override {
+  // Every engine multiplies its own share of the points, under the call's options; the result is dealt like an upload.
+  // Index i of P, s and Q lives on one device only when all three ranges start at a block-cycle boundary; only first = 0
+  // is taken.
+  int points_mul(const msmz_mul& m, const msmz_mul_opts& o, uint64_t n, uint64_t* h) override {
     if (!h || n == 0) return MSMZ_ERR_ARG;
     const MHandle* P = get(m.points_handle, 0);
     const MHandle* Q = m.addend_handle ? get(m.addend_handle, 0) : nullptr;
@@ -340,7 +341,7 @@ class MultiEngine : public IEngine {
       mine.points_handle = P->sub[g];
       mine.scalars_handle = S ? S->sub[g] : 0;
       mine.addend_handle = Q ? Q->sub[g] : 0;
-      return e->points_mul(mine, cnt, sub);
+      return e->points_mul(mine, o, cnt, sub);
     });
   }
 

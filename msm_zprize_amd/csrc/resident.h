@@ -271,9 +271,10 @@ class ResidentSets : public IEngine {
   }
 
   // ------------------------------------------------------------------------------------------ per-point multiplication
-  // msmz_points_mul: a new plain point handle, record i = [s_i] P_i (+ Q_i).  One launch; the error word (a resident
-  // scalar >= q) comes back behind the ONE host wait, like that of an upload.
-  int points_mul(const msmz_mul& m, uint64_t n, uint64_t* h) override {
+  // msmz_points_mul(_opts): a new plain point handle, record i = [s_i] P_i (+ Q_i).  One launch of the chain that
+  // points_mul_chain picks from the options (mul_kernels.h); the error word (a resident scalar >= q or >= the caller's
+  // bound) comes back behind the ONE host wait, like that of an upload.  (msmz.hip has checked the options' ranges.)
+  int points_mul(const msmz_mul& m, const msmz_mul_opts& o, uint64_t n, uint64_t* h) override {
     if (!h || !points_fit(n)) return MSMZ_ERR_ARG;
     const Handle* pts = handles_.get(m.points_handle, 0);
     const Handle* add = m.addend_handle ? handles_.get(m.addend_handle, 0) : nullptr;
@@ -284,16 +285,33 @@ class ResidentSets : public IEngine {
     const uint32_t* d_q = add ? handles_.range(m.addend_handle, 0, m.first_q, n, PW_WORDS) : nullptr;
     const uint32_t* S = m.scalars_handle ? handles_.range(m.scalars_handle, 1, m.first_s, n, 8) : nullptr;
     if (!d_p || (add && !d_q) || (m.scalars_handle && !S)) return MSMZ_ERR_ARG;
+    const MulChain chain = points_mul_chain<Fr>((o.flags & MSMZ_MUL_SUBGROUP) != 0, o.scalar_bits);
+    const int bound = o.scalar_bits == 0 || o.scalar_bits >= Fr::BITS ? Fr::BITS : o.scalar_bits;
     MulScalar bc{};
-    if (!S)
+    if (!S) {
       if (int st = read_fr(m.scalar, bc.w, false)) return st;
+      if (words_geq_pow2(bc.w, bound)) return MSMZ_ERR_RANGE;
+    }
     MSMZ_HIP(hipSetDevice(device_));
     Handle hd;
     if (int st = new_points(n, &hd)) return st;
     const dim3 grid((uint32_t)((n + 255) / 256)), block(256);   // whole blocks: every wave reaches the inversion entire
-    const int st = checked([&](uint32_t* d_err) {   // a resident scalar >= group order
-      hipLaunchKernelGGL((k_points_mul<P, Fr>), grid, block, 0, stream_, hd.mem.as<uint32_t>(), d_p, S, bc, d_q, (uint32_t)n,
-                         hd.has_endo ? 1 : 0, d_err);
+    const int st = checked([&](uint32_t* d_err) {   // a resident scalar >= group order, or >= 2^bound
+      if constexpr (Fr::HAS_GLV) {
+        if (chain.kind == MUL_CHAIN_GLV) {
+          MulGlvScalar g{};
+          if (!S) glv_decompose<Fr>(g.k0, g.k1, g.neg0, g.neg1, bc.w);
+          hipLaunchKernelGGL((k_points_mul_glv<P, Fr>), grid, block, 0, stream_, hd.mem.as<uint32_t>(), d_p, S, g, d_q,
+                             (uint32_t)n, hd.has_endo ? 1 : 0, bound, d_err);
+          return;
+        }
+      }
+      if (chain.steps == Fr::BITS)   // no bound: the instance with compile-time loop bounds
+        hipLaunchKernelGGL((k_points_mul<P, Fr, false>), grid, block, 0, stream_, hd.mem.as<uint32_t>(), d_p, S, bc, d_q,
+                           (uint32_t)n, hd.has_endo ? 1 : 0, chain.steps, d_err);
+      else
+        hipLaunchKernelGGL((k_points_mul<P, Fr, true>), grid, block, 0, stream_, hd.mem.as<uint32_t>(), d_p, S, bc, d_q,
+                           (uint32_t)n, hd.has_endo ? 1 : 0, chain.steps, d_err);
     });
     return st ? st : add_handle(std::move(hd), h);
   }

@@ -17,7 +17,7 @@ include/msmz.h -- this module contains no arithmetic.
 import ctypes as C
 
 from . import _native
-from ._native import MsmzCheckResult, MsmzLog, MsmzMul, MsmzNtt, MsmzOpts, MsmzScalarRec, MsmzScalarTerm, MsmzSegment, MsmzSrc, lib
+from ._native import MsmzCheckResult, MsmzLog, MsmzMul, MsmzMulOpts, MsmzNtt, MsmzOpts, MsmzScalarRec, MsmzScalarTerm, MsmzSegment, MsmzSrc, lib
 from ._native import check as _check   # (`check=` is a public keyword of pointsFromBytes / pointsFromTensor)
 
 _state = {"devices": None}
@@ -224,15 +224,21 @@ class _Parallel:
         return CheckResult(bad is None, int(res.off_curve), int(res.off_subgroup), bad, buf.raw if verdicts else None)
 
     # -- per-point multiplication (msmz_points_mul, include/msmz.h) -----------------------------------
-    def mulPoints(self, scalars, points, N=None, addend=None, firstPoint=0, firstScalar=0, firstAddend=0):
+    def mulPoints(self, scalars, points, N=None, addend=None, firstPoint=0, firstScalar=0, firstAddend=0, scalarBits=0,
+                  subgroup=False):
         """A new resident point array: out[i] = [s_i] points[firstPoint + i] (+ addend[firstAddend + i]), i < N.
         `scalars` is a resident scalar array (s_i = scalars[firstScalar + i]) or a Python int below the group order:
         one scalar for every point.  `addend` may be `points` itself (an IPA fold: mulPoints(u, G, N, addend=G,
-        firstPoint=N)).  The result is an ordinary point array: msm, msmBatch, precomputePoints, checkPoints take it."""
+        firstPoint=N)).  The result is an ordinary point array: msm, msmBatch, precomputePoints, checkPoints take it.
+        scalarBits = b: every scalar of the call is below 2^b, and the chain walks b bits only (0 = no bound; a scalar
+        that breaks the bound fails the call).  subgroup=True: the caller vouches that every finite point of the range
+        lies in the prime-order subgroup (checkPoints(..., subgroup=True) says so); the Weierstrass curves then run the
+        GLV chain, about half as long.  For a point outside the subgroup that row of the result is unspecified."""
         a = mul_points_args(scalars, points, N, addend, firstPoint, firstScalar, firstAddend, self._c.params["order"])
+        o = mul_points_opts(scalars, scalarBits, subgroup)
         m = MsmzMul(points.handle, a["firstPoint"], 0 if a["scalar"] is not None else scalars.handle, a["firstScalar"],
                     a["scalar"], 0 if addend is None else addend.handle, a["firstAddend"])
-        return _resident(self._c, "points", a["N"], "msmz_points_mul", C.byref(m), a["N"])
+        return _resident(self._c, "points", a["N"], "msmz_points_mul_opts", C.byref(m), a["N"], C.byref(o))
 
     # -- arithmetic mod q over resident scalar arrays (msmz_scalars_*, include/msmz.h) -----------------
     def combineScalars(self, a, x, b=None, y=None, N=None, firstX=0, firstY=0, out=None, firstOut=0, firstA=0, firstB=0):
@@ -552,6 +558,20 @@ def mul_points_args(scalars, points, N, addend, firstPoint, firstScalar, firstAd
                               ("firstAddend", firstAddend, addend)], N, limit=None)
     return {"N": N, "firstPoint": firstPoint, "firstScalar": firstScalar, "firstAddend": firstAddend,
             "scalar": scalars.to_bytes(32, "little") if broadcast else None}
+
+
+def mul_points_opts(scalars, scalarBits, subgroup):
+    """scalarBits and subgroup of mulPoints -> msmz_mul_opts, checked before anything reaches the device: the bound as
+    scalar_bits_arg checks it, a broadcast scalar against the bound, the vouch a bool."""
+    if not isinstance(subgroup, bool):
+        raise TypeError(f"mulPoints: subgroup = {subgroup!r} (True: every point lies in the prime-order subgroup)")
+    bits = scalar_bits_arg({"scalarBits": scalarBits}, "mulPoints")
+    if bits and _is_int(scalars) and scalars >> bits:
+        raise ValueError(f"mulPoints: the scalar {scalars} is not below 2^{bits} (scalarBits)")
+    o = MsmzMulOpts()
+    o.flags = _native.MSMZ_MUL_SUBGROUP if subgroup else 0
+    o.scalar_bits = bits
+    return o
 
 
 def msm_segments_args(scalars, points, segments):

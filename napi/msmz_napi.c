@@ -458,19 +458,23 @@ static napi_value CheckPoints(napi_env env, napi_callback_info info) {
 }
 
 /* mulPoints(ctx, pointsHandle, firstPoint, scalarsHandle | 32-byte Buffer, firstScalar, addendHandle (0 = none),
-   firstAddend, n) -> handle of a new point set, record i = [s_i] P_i (+ Q_i)  (msmz_points_mul; a Buffer is the one
-   scalar, little-endian, for every point) */
+   firstAddend, n, scalarBits (0 = no bound), flags (MSMZ_MUL_*)) -> handle of a new point set, record i = [s_i] P_i
+   (+ Q_i)  (msmz_points_mul_opts; a Buffer is the one scalar, little-endian, for every point) */
 static napi_value MulPoints(napi_env env, napi_callback_info info) {
   napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
   msmz_mul m; memset(&m, 0, sizeof(m));
-  uint64_t n, h = 0;
-  if (!get_args(env, info, 8, argv, &ctx) || !get_u64(env, argv[1], &m.points_handle) || !get_u64(env, argv[2], &m.first_p) ||
+  msmz_mul_opts o; memset(&o, 0, sizeof(o));
+  uint64_t n, bits, flags, h = 0;
+  if (!get_args(env, info, 10, argv, &ctx) || !get_u64(env, argv[1], &m.points_handle) || !get_u64(env, argv[2], &m.first_p) ||
       !get_u64(env, argv[4], &m.first_s) || !get_u64(env, argv[5], &m.addend_handle) || !get_u64(env, argv[6], &m.first_q) ||
       !get_u64(env, argv[7], &n) || !scalar_or_handle(env, argv[3], &m.scalar, &m.scalars_handle) ||
-      (!m.scalar && !m.scalars_handle))
+      (!m.scalar && !m.scalars_handle) || !get_u64(env, argv[8], &bits) || bits > 256 || !get_u64(env, argv[9], &flags) ||
+      flags > 0xffffffffu)
     return BAD_ARG(env, "mulPoints");
-  int st = msmz_points_mul(ctx, &m, n, &h);
-  if (st) return throw_status(env, st, "msmz_points_mul");
+  o.scalar_bits = (int32_t)bits;
+  o.flags = (uint32_t)flags;
+  int st = msmz_points_mul_opts(ctx, &m, n, &o, &h);
+  if (st) return throw_status(env, st, "msmz_points_mul_opts");
   return make_handle(env, h);
 }
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What msmz_points_mul costs.  All four curves, generated resident sets, ONE process.
+"""What msmz_points_mul and msmz_points_mul_opts cost.  All four curves, generated resident sets, ONE process.
 
     python tools/points_mul_report.py [--out FILE] [--reps R] [--logn 16 20] [--curves LABEL ...]
 
@@ -10,8 +10,14 @@ every call is freed outside the timed region):
     mul broadcast   one full-width scalar for every point, no addend
     subgroup check  msmz_check_points(SUBGROUP) of the same set: the yardstick.  A chain of the same length (BITS
                     doublings, wt(q) additions; Pallas, cofactor 1, runs none), no normalisation, no store.
+and through msmz_points_mul_opts (the chain each call runs is points_mul_chain's):
+    mul subgroup, mul+addend subgroup, mul broadcast subgroup
+                    the three legs above under MSMZ_MUL_SUBGROUP: the GLV chain on the Weierstrass curves
+    mul broadcast 128-bit   one scalar below 2^128 with scalar_bits = 128
+    mul 64-bit      resident scalars below 2^64 with scalar_bits = 64
 Beside each leg: the field products of the cost MODEL (squarings counted as products; points_mul_products of
-csrc/mul_kernels.h: a scalar of Hamming weight BITS / 2, the addend, 19 / 18 products for the wave-wide normalisation)
+csrc/mul_kernels.h: a scalar of Hamming weight BITS / 2, the addend, 19 / 18 products for the wave-wide normalisation;
+points_mul_products_glv / _bounded for the legs with options)
 and the fraction of the measured fe_mul peak (profiles/r01_ubench_fp_modmul.txt) that rate would be.  The model is a
 model: a wave pays for the addition whenever ANY of its lanes has the bit set, which the count ignores.
 One JSON line per leg, to stdout and appended to --out (default profiles/points_mul_report.jsonl).
@@ -30,12 +36,24 @@ sys.path.insert(0, ROOT)
 PEAK_GMODMUL = {"bls12-377": 72.0, "bls12-381": 67.0, "pallas": 165.0, "ed-on-bls12-377": 165.0}
 
 
-def mul_products(params, addend):
-    """field products per output point: the model of points_mul_products (csrc/mul_kernels.h)"""
-    bits = params["order"].bit_length()
+GLV_PROVEN_BITS = {"bls12-377": 126, "pallas": 128, "bls12-381": 128}   # Fr::GLV_PROVEN_BITS (csrc/constants_gen.h)
+MSMZ_MUL_SUBGROUP = 1
+
+
+def mul_products(params, addend, bits=None):
+    """field products per output point: the model of points_mul_products / points_mul_products_bounded (csrc/mul_kernels.h)"""
+    bits = bits or params["order"].bit_length()
     if params["kind"] == "twisted-edwards":
         return bits * 9 + (bits // 2) * 7 + (7 if addend else 0) + 18
     return bits * 9 + (bits // 2) * 10 + (10 if addend else 0) + 19
+
+
+def glv_products(params, addend):
+    """points_mul_products_glv (csrc/mul_kernels.h); the curve without an endomorphism runs the plain chain"""
+    h = GLV_PROVEN_BITS.get(params["label"])
+    if not h:
+        return mul_products(params, addend)
+    return h * 9 + (3 * h // 4) * 10 + 1 + 14 + 3 + (10 if addend else 0) + 19
 
 
 def check_products(params):
@@ -56,7 +74,8 @@ def main():
     ap.add_argument("--curves", nargs="+", default=None)
     args = ap.parse_args()
     import msm_zprize_amd as m
-    from msm_zprize_amd._native import MsmzCheckResult, MsmzMul, check, lib
+    import random
+    from msm_zprize_amd._native import MsmzCheckResult, MsmzMul, MsmzMulOpts, check, lib
     m.startThreads()
     rows = []
     for params in m.curves.ALL_CURVES:
@@ -64,16 +83,22 @@ def main():
             continue
         curve = (m.Weierstrass if params["kind"] == "weierstrass" else m.TwistedEdwards).create(params)
         u = (params["order"] * 5 // 7).to_bytes(32, "little")   # full width, about half its bits set
+        u128 = ((1 << 128) * 5 // 7).to_bytes(32, "little")
         for logn in args.logn:
             n = 1 << logn
             pts = curve.Parallel.randomPointsFast(n, 11)
             add = curve.Parallel.randomPointsFast(n, 12)
             sc = curve.Parallel.randomScalars(n, 13)
+            sc64 = curve.Parallel.scalarsFromBytes(random.Random(14).randbytes(8 * n), n, width=8)
 
-            def mul(desc):
+            def mul(desc, flags=None, bits=0):
                 h = C.c_uint64()
+                opts = None if flags is None else MsmzMulOpts(flags, bits)
                 t0 = time.perf_counter()
-                check(lib().msmz_points_mul(curve._ctx, C.byref(desc), n, C.byref(h)), "msmz_points_mul")
+                if opts is None:
+                    check(lib().msmz_points_mul(curve._ctx, C.byref(desc), n, C.byref(h)), "msmz_points_mul")
+                else:
+                    check(lib().msmz_points_mul_opts(curve._ctx, C.byref(desc), n, C.byref(opts), C.byref(h)), "msmz_points_mul_opts")
                 ms = (time.perf_counter() - t0) * 1e3
                 check(lib().msmz_free(curve._ctx, h.value), "msmz_free")
                 return ms
@@ -90,7 +115,17 @@ def main():
             legs = [("mul", lambda: mul(MsmzMul(pts.handle, 0, sc.handle, 0, None, 0, 0)), mul_products(params, False)),
                     ("mul+addend", lambda: mul(MsmzMul(pts.handle, 0, sc.handle, 0, None, add.handle, 0)), mul_products(params, True)),
                     ("mul broadcast", lambda: mul(MsmzMul(pts.handle, 0, 0, 0, u, 0, 0)), mul_products(params, False)),
-                    ("subgroup check", subgroup, check_products(params))]
+                    ("subgroup check", subgroup, check_products(params)),
+                    ("mul subgroup", lambda: mul(MsmzMul(pts.handle, 0, sc.handle, 0, None, 0, 0), MSMZ_MUL_SUBGROUP),
+                     glv_products(params, False)),
+                    ("mul+addend subgroup", lambda: mul(MsmzMul(pts.handle, 0, sc.handle, 0, None, add.handle, 0), MSMZ_MUL_SUBGROUP),
+                     glv_products(params, True)),
+                    ("mul broadcast subgroup", lambda: mul(MsmzMul(pts.handle, 0, 0, 0, u, 0, 0), MSMZ_MUL_SUBGROUP),
+                     glv_products(params, False)),
+                    ("mul broadcast 128-bit", lambda: mul(MsmzMul(pts.handle, 0, 0, 0, u128, 0, 0), 0, 128),
+                     mul_products(params, False, 128)),
+                    ("mul 64-bit", lambda: mul(MsmzMul(pts.handle, 0, sc64.handle, 0, None, 0, 0), 0, 64),
+                     mul_products(params, False, 64))]
             for name, call, prod in legs:
                 call()
                 ms = statistics.median(call() for _ in range(args.reps))
@@ -101,7 +136,7 @@ def main():
                        "model_fraction_of_peak": round(rate / PEAK_GMODMUL[params["label"]], 4), "reps": args.reps}
                 rows.append(row)
                 print(json.dumps(row), flush=True)
-            for a in (pts, add, sc):
+            for a in (pts, add, sc, sc64):
                 a.free()
         curve.close()
     with open(args.out, "a") as f:
