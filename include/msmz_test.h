@@ -206,7 +206,7 @@ int msmz_test_batch_add(msmz_ctx* ctx, int safe, int B, const uint8_t* points_xy
 
 /* The bucket reduction alone, on caller-built buckets: the line sums and the weighted sums of the two-dimensional
  * reduction (csrc/reduce2d_kernels.h) and the upper levels (k_reduce_quad / k_reduce_quad16 / k_reduce_tail), through
- * the engine's own reduce_2d / reduce_levels and the template instances an MSM launches.  Run it before and after
+ * the engine's own reduction stage (BucketReduce, csrc/reduce.h) and the template instances an MSM launches.  Run it before and after
  * touching a reduction kernel: it names the problem and the line an MSM's single result point cannot.
  *
  * 2-D modes: window size c (2 .. 16) fixes L = 2^(c-1), H = 2^ceil((c-1)/2), D = L / H as the planner's split does;
@@ -221,7 +221,7 @@ int msmz_test_batch_add(msmz_ctx* ctx, int safe, int B, const uint8_t* points_xy
  *     flag, its neutral element is (0, 1)), each stored as an accumulator record; bucket g is the sum of records
  *     cscan[g] .. cscan[g+1]-1 (nsets * L + 1 offsets).  Drives k_reduce2d_partial_acc with chunk ranges.
  *   MSMZ_TR_ACCS_SUMMED: the same through k_bucket_sums and the one-accumulator-per-bucket mode of that kernel.
- * MSMZ_TR_LEVELS: reduce_levels alone on `nsets` problems (1 .. 64) of n_in entries (1 .. 4096):  points_xy = the
+ * MSMZ_TR_LEVELS: BucketReduce::levels alone on `nsets` problems (1 .. 64) of n_in entries (1 .. 4096):  points_xy = the
  *   nsets * n_in rows, then the nsets * n_in C inputs (n_points = 2 * nsets * n_in); result j = sum_e (C_e + e row_e).
  * scale (nullable; ACCS, ACCS_SUMMED, LEVELS): one canonical field element lambda != 0 per input point; the record is
  *   stored as (lambda^2 x, lambda^3 y, lambda^2, lambda^3), resp. (lambda x, lambda y, lambda, lambda x y), so that

@@ -1,7 +1,7 @@
 // Host-side MSM engine: the pipeline of one GPU (sort, plan, tree rounds, bucket reduction) over the resident sets of
-// ResidentSets (resident.h), from which it derives; it owns the pipeline's device buffers, sequences the kernels on the
-// one HIP stream and finishes the K window sums on the host.  This replaces the reference's SPMD worker runtime
-// (src/threads/threads.ts:132-359, src/parallel.ts:291-320) and the JS orchestration inside
+// ResidentSets (resident.h), from which it derives; it owns the buffers its stages share, sequences the stages (sort.h,
+// reduce.h) and its own kernels on the one HIP stream and finishes the K window sums on the host.  This replaces the
+// reference's SPMD worker runtime (src/threads/threads.ts:132-359, src/parallel.ts:291-320) and the JS orchestration inside
 // `msm` (src/msm-batched-affine.ts:74-328): barriers between phases become stream order, the
 // per-thread bucket split (msm-common.ts:88-188) becomes grid sizing.
 #pragma once
@@ -19,6 +19,7 @@
 #include "host64.h"
 #include "multi.h"
 #include "plan.h"
+#include "reduce.h"
 #include "resident.h"
 #include "run.h"
 #include "sort.h"
@@ -59,14 +60,6 @@ static int host_point_add(const uint8_t* a, int ai, const uint8_t* b, int bi, ui
   memcpy(out, w, sizeof(w));
   return MSMZ_OK;
 }
-
-// Which kernel a level of the bucket reduction runs; none changes a result.  The engine holds one, constant, which the
-// MSM paths pass to the reduction; a test hook passes a copy with its caller's values.
-struct ReduceKnobs {
-  uint32_t tail_n;           // entries per window at which k_reduce_tail takes over
-  uint32_t quad16_max;       // levels with at most this many groups use k_reduce_quad16
-  uint32_t pairsum_x4_max;   // pair-sum levels with at most this many additions use DPP quads
-};
 
 template <class Cfg>
 class TestHooks;   // test_hooks.h
@@ -457,52 +450,13 @@ class Engine : public ResidentSets<Cfg> {
     return MSMZ_OK;
   }
 
-  // reduce levels on accumulator records: rows in red_[cur*2], C in red_[cur*2+1]; ends with one entry per window
-  template <class P>
-  int reduce_levels(const ReduceKnobs& rk, int& cur, uint32_t n_in, uint32_t nprob) {
-    constexpr int AW = P::ACC_WORDS;
-    int st;
-    while (n_in > rk.tail_n) {
-      const uint32_t S = 4;   // quads handle short tails too
-      uint32_t g2 = (n_in + S - 1) / S;
-      int nxt = cur ^ 1;
-      if ((st = red_[nxt * 2].ensure((size_t)nprob * g2 * AW * 4))) return st;
-      if ((st = red_[nxt * 2 + 1].ensure((size_t)nprob * g2 * AW * 4))) return st;
-      uint32_t total = nprob * g2;
-      if (total <= rk.quad16_max) {
-        // small level: latency-bound, one DPP quad per addition
-        hipLaunchKernelGGL((k_reduce_quad16<P>), dim3((total * 16 + 63) / 64), dim3(64), 0, stream_,
-                           red_[nxt * 2].as<uint32_t>(), red_[nxt * 2 + 1].as<uint32_t>(),
-                           red_[cur * 2].as<uint32_t>(), red_[cur * 2 + 1].as<uint32_t>(), n_in, g2, total);
-      } else {
-        hipLaunchKernelGGL((k_reduce_quad<P>), dim3((total * 4 + 63) / 64), dim3(64), 0, stream_,
-                           red_[nxt * 2].as<uint32_t>(), red_[nxt * 2 + 1].as<uint32_t>(),
-                           red_[cur * 2].as<uint32_t>(), red_[cur * 2 + 1].as<uint32_t>(), n_in, g2, total);
-      }
-      n_in = g2;
-      cur = nxt;
-    }
-    // the last levels (<= REDUCE_TAIL_N entries per window) in ONE launch, one workgroup per window; leaves the
-    // window sums in final_
-    {
-      const int nxt = cur ^ 1;
-      if ((st = red_[nxt * 2].ensure((size_t)nprob * n_in * AW * 4))) return st;
-      if ((st = red_[nxt * 2 + 1].ensure((size_t)nprob * n_in * AW * 4))) return st;
-      if ((st = final_.ensure((size_t)nprob * AW * 4))) return st;
-      hipLaunchKernelGGL((k_reduce_tail<P>), dim3(nprob), dim3(REDUCE_TAIL_T), 0, stream_, red_[cur * 2].as<uint32_t>(),
-                         red_[cur * 2 + 1].as<uint32_t>(), red_[nxt * 2].as<uint32_t>(), red_[nxt * 2 + 1].as<uint32_t>(),
-                         final_.as<uint32_t>(), n_in, n_in);
-    }
-    return MSMZ_OK;
-  }
-
   // copy the window results of all pl.nprob problems (the C entries of the last level; its rows are multiples of the
   // weight unit and not needed) to h_res_, and the meta block to the host
   int fetch_window_sums(const Plan& pl, size_t per_problem) {
     const size_t words = pl.nprob * per_problem * XW;
     if (int st = h_res_.ensure(words * 4)) return st;
     MSMZ_HIP(hipGetLastError());
-    MSMZ_HIP(hipMemcpyAsync(h_res_.p, final_.p, words * 4, hipMemcpyDeviceToHost, stream_));
+    MSMZ_HIP(hipMemcpyAsync(h_res_.p, reduce_.final(), words * 4, hipMemcpyDeviceToHost, stream_));
     MSMZ_HIP(hipMemcpyAsync(h_meta_.p, meta_.p, sizeof(MsmMeta), hipMemcpyDeviceToHost, stream_));
     MSMZ_HIP(hipStreamSynchronize(stream_));
     return MSMZ_OK;
@@ -553,79 +507,6 @@ class Engine : public ResidentSets<Cfg> {
     return MSMZ_OK;
   }
 
-  // Two-dimensional bucket reduction (reduce2d_kernels.h): line sums, then the weighted sums over H lines of 2 Keff
-  // problems with the upper-level kernels.  Leaves result 2 kw (rows) / 2 kw + 1 (columns) of bucket set kw in final_.
-  // basic = true: the buckets are sums of partial accumulators (msmBasic path: slots_ + rscan_), else the affine bucket
-  // sums of the tree rounds (bfin_).  sp: the planner's split of pl (planner_.split_2d); rk: which kernel a level runs.
-  template <class P>
-  int reduce_2d(const Plan& pl, const Split2d& sp, const ReduceKnobs& rk, const uint32_t* d_points, bool basic = false,
-                bool summed = false) {
-    const R2Geom g = r2_geom(pl, sp);
-    int rows = 0;
-    if (int st = line_sums_2d<P>(g, rk, d_points, basic, summed, &rows)) return st;
-    return weighted_sums_2d<P>(g, rk, rows);
-  }
-  static R2Geom r2_geom(const Plan& pl, const Split2d& sp) {
-    R2Geom g;
-    g.L = pl.L;
-    g.H = sp.H;
-    g.D = sp.D;
-    g.NC = sp.NC;
-    g.chr = sp.D / sp.NC;
-    g.chc = sp.H / sp.NC;
-    g.nprob = 2u * pl.nprob * (uint32_t)pl.Keff;   // (all bucket sets of a batch)
-    return g;
-  }
-  // first half: the partial sums of every line's chunks, then their pair sums; *rows = the red_ buffer (0 or 2) that
-  // holds the g.nprob * g.H line sums
-  template <class P>
-  int line_sums_2d(const R2Geom& g, const ReduceKnobs& rk, const uint32_t* d_points, bool basic, bool summed, int* rows) {
-    const uint32_t lines = g.nprob * g.H;
-    const uint32_t total = lines * g.NC;
-    int st;
-    // ping-pong between red_[0] and red_[2] (rows of the level machinery); C inputs of the first level = infinity
-    if ((st = red_[0].ensure((size_t)total * XW * 4))) return st;
-    if ((st = red_[2].ensure((size_t)total * XW * 4))) return st;
-    if (basic && summed) {   // one accumulator per bucket in bsum_ (k_bucket_sums)
-      hipLaunchKernelGGL((k_reduce2d_partial_acc<P>), dim3((total + 127) / 128), dim3(128), 0, stream_,
-                         red_[0].as<uint32_t>(), bsum_.as<uint32_t>(), (const uint32_t*)nullptr, g, total);
-    } else if (basic) {
-      hipLaunchKernelGGL((k_reduce2d_partial_acc<P>), dim3((total + 127) / 128), dim3(128), 0, stream_,
-                         red_[0].as<uint32_t>(), slots_.as<uint32_t>(), rscan_.as<uint32_t>(), g, total);
-    } else {
-      if constexpr (!TE)
-        hipLaunchKernelGGL((k_reduce2d_partial<F>), dim3((total + 127) / 128), dim3(128), 0, stream_,
-                           red_[0].as<uint32_t>(), slots_.as<uint32_t>(), d_points, bfin_.as<uint4>(), g, total);
-    }
-    int src = 0;
-    for (uint32_t n = total / 2; n >= lines && g.NC > 1; n /= 2) {
-      const int dst = src ^ 2;
-      if (n <= rk.pairsum_x4_max) {
-        hipLaunchKernelGGL((k_pairsum_x4<P>), dim3((n * 4 + 63) / 64), dim3(64), 0, stream_, red_[dst].as<uint32_t>(),
-                           red_[src].as<uint32_t>(), n);
-      } else {
-        hipLaunchKernelGGL((k_pairsum<P>), dim3((n + 127) / 128), dim3(128), 0, stream_, red_[dst].as<uint32_t>(),
-                           red_[src].as<uint32_t>(), n);
-      }
-      src = dst;
-      if (n == lines) break;
-    }
-    *rows = src;
-    return MSMZ_OK;
-  }
-  // second half, the upper levels: rows = the line sums in red_[crow] (weight unit 1), C = infinity (all-zero records)
-  template <class P>
-  int weighted_sums_2d(const R2Geom& g, const ReduceKnobs& rk, int crow) {
-    const uint32_t lines = g.nprob * g.H;
-    const int ccol = crow + 1;
-    int st;
-    if ((st = red_[ccol].ensure((size_t)lines * XW * 4))) return st;
-    hipLaunchKernelGGL((k_fill_neutral<P>), dim3((lines + 255) / 256), dim3(256), 0, stream_, red_[ccol].as<uint32_t>(), lines);
-    int cur = crow >> 1;   // reduce_levels addresses rows as red_[cur * 2], C as red_[cur * 2 + 1]
-    if ((st = reduce_levels<P>(rk, cur, g.H, g.nprob))) return st;
-    MSMZ_HIP(hipGetLastError());
-    return MSMZ_OK;
-  }
   // the log of one MSM (or sub-batch): its plan, its run's totals and (timed) its stage events.  scatter_kernel_ms: the
   // scatter kernel alone (k_coarse / k_scatter), without k_fine.
   static void fill_log(msmz_log* log, const Plan& pl, const Run& run, float host_ms) {
@@ -732,15 +613,16 @@ class Engine : public ResidentSets<Cfg> {
     mark(run, run.ev.plan_end);
     const uint32_t R = run.rounds;
     for (uint32_t r = 0; r < R; r++) run.n_pairs += run.round_pairs[r];
+    const BatchAdder<Cfg> adder = batch_adder();   // (slots_ has its final size: nothing below grows it)
     for (uint32_t r = 0; r < R; r++) {
       const uint32_t pairs = run.round_pairs[r];
       if (pairs == 0) continue;
-      launch_batch_add(pairs, opt.safe != 0, d_points, desc_.as<uint2>() + run.round_base[r], run.round_base[r], d_meta);
+      adder.launch(pairs, opt.safe != 0, d_points, desc_.as<uint2>() + run.round_base[r], run.round_base[r], d_meta);
 #ifdef MSMZ_TRACE
       {
         char nm[32];
         snprintf(nm, sizeof nm, "k_batch_add round %d", r);
-        const int B = batch_b(pairs);
+        const int B = adder.batch_b(pairs);
         const uint32_t wgs = (pairs + MSMZ_BATCH_T * B - 1) / (MSMZ_BATCH_T * B);
         if ((st = trace_dump(stream_, nm, d_meta + 1, wgs < 65536 ? wgs : 65536, false))) return st;
       }
@@ -749,10 +631,11 @@ class Engine : public ResidentSets<Cfg> {
     }
     mark(run, run.ev.acc_end);
 
-    // ---- bucket reduction
+    // ---- bucket reduction (reduce.h)
+    const BucketSource buckets = BucketSource::locations(slots_.as<uint32_t>(), d_points, bfin_.as<uint4>());
     if (want_2d) {
       // two-dimensional: row / column sums of the buckets, then two half-length weighted sums per bucket set
-      if ((st = reduce_2d<WeierPolicy<F>>(pl, planner_.split_2d(pl), reduce_knobs_, d_points))) return st;
+      if ((st = reduce_.run_2d(planner_.r2_geom(pl), reduce_knobs_, buckets, stream_))) return st;
     } else {
       // level 1 from affine bucket sums, then XYZZ levels down to one entry per window.  The weight-L bucket is folded
       // into element L/2, which must be the FIRST element of its group
@@ -760,11 +643,8 @@ class Engine : public ResidentSets<Cfg> {
       if (S1 > 8) S1 = 8;
       while (S1 > 1 && S1 * 2 > pl.L) S1 >>= 1;
       const uint32_t groups = (pl.L + S1 - 1) / S1;   // elements are weights 0..L-1 (weight L folded into L/2)
-      if ((st = red_[0].ensure((size_t)pl.Keff * groups * XW * 4))) return st;
-      if ((st = red_[1].ensure((size_t)pl.Keff * groups * XW * 4))) return st;
-      if ((st = reduce_first_affine(pl, d_points, S1, groups, run.n_pairs, d_meta))) return st;
-      int cur = 0;
-      if ((st = reduce_levels<WeierPolicy<F>>(reduce_knobs_, cur, groups, (uint32_t)pl.Keff))) return st;
+      if ((st = reduce_.first_affine(pl, S1, groups, run.n_pairs, adder, slots_.bytes, buckets, d_meta))) return st;
+      if ((st = reduce_.levels(reduce_knobs_, groups, (uint32_t)pl.Keff, stream_))) return st;
     }
     return finish_msm(pl, run, want_2d, out, out_inf, log);
   }
@@ -809,119 +689,22 @@ class Engine : public ResidentSets<Cfg> {
     // every bucket is visited twice: buckets of several chunk accumulators (large inputs: Pallas 2^22 has 4,
     // ed-on-bls12-377 2^24 has 8) are first summed into one accumulator each, in bucket order
     const bool summed = (uint64_t)n_chunks * 2 > (uint64_t)nb * 3 && !no_bucket_sums_;
-    if (summed && (st = bucket_sums<P>(nb))) return st;
-    if ((st = reduce_2d<P>(pl, planner_.split_2d(pl), reduce_knobs_, d_points, true, summed))) return st;
+    BucketSource buckets = BucketSource::chunks(slots_.as<uint32_t>(), rscan_.as<uint32_t>());
+    if (summed && (st = reduce_.bucket_sums(buckets, nb, stream_, &buckets))) return st;
+    if ((st = reduce_.run_2d(planner_.r2_geom(pl), reduce_knobs_, buckets, stream_))) return st;
     return finish_msm(pl, run, true, out, out_inf, log);
   }
-  // bsum_[g] = sum of the chunk accumulators slots_[rscan_[g] .. rscan_[g+1]) of bucket g < nb
-  template <class P>
-  int bucket_sums(uint32_t nb) {
-    if (int st = bsum_.ensure((size_t)nb * P::ACC_WORDS * 4)) return st;
-    hipLaunchKernelGGL((k_bucket_sums<P>), dim3((nb + 127) / 128), dim3(128), 0, stream_, bsum_.as<uint32_t>(),
-                       slots_.as<uint32_t>(), rscan_.as<uint32_t>(), nb);
-    return MSMZ_OK;
-  }
-
-  // Batched-affine first level of the bucket reduction (reduce_affine.h): S - 1 chain steps and
-  // a short pair tree, every launch over Keff * groups (x pairs per group) additions; results behind the tree rounds'
-  // records.  Leaves the scaled (row, tri) XYZZ records in red_[0] / red_[1] for reduce_levels.
-  int reduce_first_affine(const Plan& pl, const uint32_t* d_points, uint32_t S, uint32_t groups, uint64_t tree_pairs,
-                          MsmMeta* d_meta) {
-    F2Geom g;
-    memset(&g, 0, sizeof(g));
-    g.L = pl.L;
-    g.S = S;
-    g.groups = groups;
-    g.NG = (uint32_t)pl.Keff * groups;
-    g.inf_slot = (uint32_t)((tree_pairs + 63) / 64 * 64);
-    g.out0 = g.inf_slot + 64;
-    uint32_t n_launch = 0, dsum = 0, osum = 0;
-    for (uint32_t step = 1; step < S; step++) {
-      g.ppg[n_launch] = 1;
-      g.desc_off[n_launch] = dsum;
-      g.out_off[n_launch] = osum;
-      dsum += g.NG;
-      osum += g.NG;
-      n_launch++;
-    }
-    for (uint32_t n = S - 1; n > 1; n = n / 2 + (n & 1)) {
-      g.ppg[n_launch] = n / 2;
-      g.desc_off[n_launch] = dsum;
-      g.out_off[n_launch] = osum;
-      dsum += g.NG * (n / 2);
-      osum += g.NG * (n / 2);
-      n_launch++;
-    }
-    g.n_launches = n_launch;
-    g.desc_off[n_launch] = dsum;   // (row, tri) locations of every group
-    dsum += g.NG;
-    if ((uint64_t)g.out0 + osum + 64 >= (1ull << 30)) return MSMZ_ERR_ARG;
-    int st;
-    if ((st = f2desc_.ensure((size_t)dsum * 8))) return st;
-    // slots_ may have to grow: its contents (the tree rounds' results) must survive -> it was sized for this in advance
-    if (((size_t)g.out0 + osum + 64) * SlotFmt<F>::WORDS * 4 > slots_.bytes) return MSMZ_ERR_HIP;
-    MSMZ_HIP(hipMemsetAsync(slots_.as<uint32_t>() + slot_words(g.inf_slot), 0, (size_t)64 * SlotFmt<F>::WORDS * 4, stream_));
-    hipLaunchKernelGGL(k_reduce_affine_desc, dim3((g.NG + 255) / 256), dim3(256), 0, stream_, f2desc_.as<uint2>(),
-                       bfin_.as<uint4>(), g);
-    for (uint32_t i = 0; i < n_launch; i++)
-      launch_batch_add(g.NG * g.ppg[i], true, d_points, f2desc_.as<uint2>() + g.desc_off[i], g.out0 + g.out_off[i], d_meta);
-    hipLaunchKernelGGL((k_reduce_affine_finish<F>), dim3((g.NG + 127) / 128), dim3(128), 0, stream_, red_[0].as<uint32_t>(),
-                       red_[1].as<uint32_t>(), slots_.as<uint32_t>(), d_points, f2desc_.as<uint2>() + g.desc_off[n_launch],
-                       bfin_.as<uint4>(), g);
-    MSMZ_HIP(hipGetLastError());
-    return MSMZ_OK;
-  }
-  static size_t slot_words(uint32_t rec) {   // host twin of slot_offset<F> (rec a multiple of 64)
-    return (size_t)(rec >> 6) * (SlotFmt<F>::CH * 64) * 4;
-  }
-
-  // pairs per thread of a launch of `pairs` batched-affine additions: as many as keep >= ~2 workgroups per CU in
-  // flight, capped at BMAX = 16 (measured per round at 2^20: 7.6 M pairs B = 8..16, 3.7 M: 16, 1.8 M: 8, 0.9 M: 4,
-  // < 0.3 M: 2; 32 is slower everywhere)
-  int batch_b(uint32_t pairs) const {
-    constexpr int T = MSMZ_BATCH_T, BMAX = MSMZ_BATCH_BMAX;
-    int B = 1;
-    while (B < BMAX && (uint64_t)pairs >= (uint64_t)T * (B * 2) * batch_min_wgs_) B *= 2;
-    if (batch_b_override_ > 0) B = batch_b_override_ < BMAX ? batch_b_override_ : BMAX;
-    return B;
-  }
-
-  // one launch of batched-affine additions: pairs `dsc[0 .. pairs)`, results in slot records out_base + t
-  void launch_batch_add(uint32_t pairs, bool safe, const uint32_t* d_points, const uint2* dsc, uint32_t out_base,
-                        MsmMeta* d_meta) {
-    launch_batch_add_b(batch_b(pairs), pairs, safe, d_points, dsc, out_base, d_meta);
-  }
-  // ... with B pairs per thread (1 <= B <= MSMZ_BATCH_BMAX)
-  void launch_batch_add_b(int B, uint32_t pairs, bool safe, const uint32_t* d_points, const uint2* dsc,
-                          uint32_t out_base, MsmMeta* d_meta) {
-    constexpr int T = MSMZ_BATCH_T, OCC = MSMZ_BATCH_OCC, BMAX = MSMZ_BATCH_BMAX;
-    dim3 grid((pairs + T * B - 1) / (T * B)), block(T);
-    if constexpr (!TE) {
-      if (safe) {
-        hipLaunchKernelGGL((k_batch_add<F, T, true, OCC, BMAX>), grid, block, 0, stream_, slots_.as<uint32_t>(),
-                           d_points, dsc, out_base, pairs, B, d_meta);
-      } else {
-        hipLaunchKernelGGL((k_batch_add<F, T, false, OCC, BMAX>), grid, block, 0, stream_, slots_.as<uint32_t>(),
-                           d_points, dsc, out_base, pairs, B, d_meta);
-      }
-    }
-  }
+  // the launcher of batched-affine additions into slots_ as it is now (batch_add.h)
+  BatchAdder<Cfg> batch_adder() const { return {stream_, slots_.template as<uint32_t>(), batch_min_wgs_, batch_b_override_}; }
 
   // shared state -------------------------------------------------------------------------------
   int curve_id_;
   StageEvents ev_{};
-  // Tuning knobs (the planning ones: PlanKnobs, plan.h).  A release build uses the constants; a development build
-  // (-DMSMZ_DEV, tools/build_variant.sh) reads MSMZ_* environment variables when the context is created.  None of them
-  // changes a result.
-#ifdef MSMZ_DEV
-  static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
-#else
-  static int env_int(const char*, int dflt) { return dflt; }
-#endif
+  // Tuning knobs (the planning ones: PlanKnobs, plan.h; which kernel a reduction level runs: ReduceKnobs, reduce.h), each
+  // through env_int (plan.h).  None of them changes a result.
   uint32_t batch_min_wgs_ = (uint32_t)env_int("MSMZ_BATCH_WGS", 512);
   int chunk_shift_override_ = env_int("MSMZ_CHUNK_SHIFT", 0);
-  const ReduceKnobs reduce_knobs_{(uint32_t)env_int("MSMZ_TAIL_N", REDUCE_TAIL_N), (uint32_t)env_int("MSMZ_QUAD16", 8192),
-                                  (uint32_t)env_int("MSMZ_PAIRSUM_X4", 16384)};
+  const ReduceKnobs reduce_knobs_{};
   Host64<F> host64_;
   bool no_bucket_sums_ = env_int("MSMZ_NO_BUCKET_SUMS", 0) != 0;
   // rounds left to the 2-D reduction's loader: at most 2 (a bucket's final-location record holds 4 partial sums)
@@ -939,7 +722,10 @@ class Engine : public ResidentSets<Cfg> {
                         env_int("MSMZ_NO_SORT_SPECIAL", 0) != 0, env_int("MSMZ_FB", 0), (uint32_t)env_int("MSMZ_S1", 0),
                         (uint32_t)env_int("MSMZ_R2_NC", 0)}};
   BucketSort<Fr, TE> sort_;   // the sort stage: its buffers, the sorted references and bucket offsets included
-  DevBuf bsum_, f2desc_, final_, desc_, bfin_, rscan_, partials_, slots_, red_[4];   // (partials_: msmBasic's chunk scan)
+  BucketReduce<Cfg> reduce_;  // the bucket reduction: its level buffers and the window results included
+  // what the stages share: the tree rounds' descriptors and final locations, the plan's / msmBasic's chunk scan (and its
+  // scratch partials_), the slot records (msmBasic: chunk accumulators)
+  DevBuf desc_, bfin_, rscan_, partials_, slots_;
   DevBuf segs_;         // run_segments: the descriptor table of a sub-batch ...
   PinnedBuf h_segs_;    // ... and its pinned host copy (rewritten only after the sub-batch's final fetch)
   TestHooks<Cfg> hooks_{*this};

@@ -20,14 +20,15 @@
 //                        (msm-batched-affine.ts:232-270; curve-affine.ts:376-522; inverse.ts:220-271)
 //   k_reduce_quad(16),   upper levels of the bucket reduction  sum_l l*B_l  (above reduce2d_kernels.h's line sums, or
 //   k_reduce_tail        reduce_affine.h's first level) by grouped running sums in XYZZ / extended coordinates, a quad
-//                        of lanes per group / per addition; the last levels in one launch
+//                        of lanes per group / per addition; the last levels in one launch; host side of all of the
+//                        reduction: BucketReduce, reduce.h
 //                        (msm-batched-affine.ts:544-571 reduceBucketsColumnProjective)
 //   k_reduce_affine_*    (reduce_affine.h) optional batched-affine first level (reduceBucketsAffine,
 //                        msm-batched-affine-single-thread.ts:522-667)
 //   k_bucket_accumulate  msmBasic path: buckets in XYZZ / extended coordinates (msm-basic.ts:106-128)
 //   k_test_*             (test_kernels.h) stage-level test hooks of include/msmz_test.h, launched from test_hooks.h
 //                        (msmz_test_plan and msmz_test_reduce launch no kernel of their own: they run the engine's
-//                        plan_phase / reduction on caller-built buckets)
+//                        plan_phase / its reduction stage, reduce.h, on caller-built buckets)
 //
 // Bucket numbering: global bucket g = k*L + (l-1) for window k and digit l in [1, L], L = 2^(c-1).
 // Sorted references: ref = point_index | (negate << 31).

@@ -3,6 +3,7 @@
 // limits and POD argument structs that host and kernels share (the kernel headers include this file).
 #pragma once
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 
 #include "../../include/msmz.h"
@@ -155,8 +156,16 @@ struct SortLayout {
   bool fits = false, two_level = false;
 };
 
-// Planning knobs.  Default-constructed = a release build; a development build (-DMSMZ_DEV) fills them from MSMZ_*
-// environment variables (engine.h).  None of them changes a result.
+// A tuning knob's value: a release build uses the constant; a development build (-DMSMZ_DEV, tools/build_variant.sh)
+// reads the MSMZ_* environment variable when the context is created.
+#ifdef MSMZ_DEV
+static inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
+#else
+static inline int env_int(const char*, int dflt) { return dflt; }
+#endif
+
+// Planning knobs.  Default-constructed = a release build; a development build fills them from MSMZ_* environment
+// variables (engine.h).  None of them changes a result.
 struct PlanKnobs {
   bool no_spread = false, no_fold = false, no_window_model = false, force_atomic_sort = false;
   bool no_fbt = false;            // top window's bins as wide as the others
@@ -494,6 +503,19 @@ struct Planner {
     }
     s.NC = nc;
     return s;
+  }
+  // ... as the kernels of the 2-D reduction take it: two problems (rows, columns) per bucket set of the batch
+  R2Geom r2_geom(const Plan& pl) const {
+    const Split2d sp = split_2d(pl);
+    R2Geom g;
+    g.L = pl.L;
+    g.H = sp.H;
+    g.D = sp.D;
+    g.NC = sp.NC;
+    g.chr = sp.D / sp.NC;
+    g.chc = sp.H / sp.NC;
+    g.nprob = 2u * pl.nprob * (uint32_t)pl.Keff;
+    return g;
   }
 
   // problems of the next sub-batch over a point set of pts_n points (`factor` copies; <= 1: plain): the window size

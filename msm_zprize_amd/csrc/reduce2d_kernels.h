@@ -24,126 +24,117 @@
 
 namespace msmz {
 
+// What thread t of the partial-sum kernels does: chunk `chunk` of line `line` of problem `prob` (bucket set kw, rows or
+// columns), i.e. the buckets of weights j0, j0 + step, ... (count of them); fold: and the single bucket of weight
+// L = H D, folded in as 2 * (H/2) * D by the first chunk of row H/2.  A plain sum may group buckets any way, so
+// the chunks of a ROW are interleaved (chunk q = buckets q, q + NC, q + 2 NC, ... of the row) and those of a COLUMN are
+// dealt so that neighbouring lanes hold neighbouring columns: either way the lanes of a wave read neighbouring buckets
+// in the same step (coalesced final-location words, neighbouring records).
+struct R2Chunk {
+  uint32_t prob, kw, line, chunk, j0, step, count;
+  bool fold;
+};
+__device__ __forceinline__ R2Chunk r2_chunk(const R2Geom& g, uint32_t t) {
+  R2Chunk c;
+  const uint32_t per_prob = g.H * g.NC;
+  c.prob = t / per_prob;
+  const uint32_t u = t - c.prob * per_prob;
+  c.kw = c.prob >> 1;
+  const bool col = (c.prob & 1u) != 0;
+  c.j0 = c.step = c.count = 0;
+  if (!col) {
+    c.line = u / g.NC;
+    c.chunk = u - c.line * g.NC;
+    c.j0 = c.line * g.D + c.chunk;
+    c.step = g.NC;
+    c.count = g.chr;
+  } else if (u < g.D * g.NC) {
+    c.chunk = u / g.D;
+    c.line = u - c.chunk * g.D;
+    c.j0 = c.chunk * g.chc * g.D + c.line;
+    c.step = g.D;
+    c.count = g.chc;
+  } else {
+    // lines D .. H-1 of the column problem do not exist: infinity, so that both problems have H entries
+    const uint32_t v = u - g.D * g.NC;
+    c.line = g.D + v / g.NC;
+    c.chunk = v - (v / g.NC) * g.NC;
+  }
+  c.fold = !col && c.line == g.H / 2 && c.chunk == 0;
+  return c;
+}
+
+// acc += accs[q0 .. q1), accumulator records in the policy's memory format
+template <class P>
+__device__ __forceinline__ void add_accs(typename P::Acc& acc, const uint32_t* accs, uint32_t q0, uint32_t q1) {
+  typename P::Acc tmp, p;
+  for (uint32_t q = q0; q < q1; q++) {
+    P::load(p, accs + (size_t)q * P::ACC_WORDS);
+    P::add(tmp, acc, p);
+    acc = tmp;
+  }
+}
+
 template <class F>
 __global__ void __launch_bounds__(128, MSMZ_REDUCE_OCC) k_reduce2d_partial(uint32_t* part, const uint32_t* slots,
                                                                            const uint32_t* points, const uint4* bfin,
                                                                            R2Geom g, uint32_t total) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= total) return;
-  const uint32_t per_prob = g.H * g.NC;
-  const uint32_t prob = t / per_prob, u = t - prob * per_prob;
-  const uint32_t kw = prob >> 1;
-  const bool col = (prob & 1u) != 0;
-  // the thread's buckets: weights j0, j0 + step, ... (count of them).  A plain sum may group buckets any way, so the
-  // chunks of a ROW are interleaved (chunk q = buckets q, q + NC, q + 2 NC, ... of the row) and those of a COLUMN are
-  // dealt so that neighbouring lanes hold neighbouring columns: either way the lanes of a wave read neighbouring
-  // buckets in the same step (coalesced final-location words, neighbouring records).
-  uint32_t line, chunk, j0 = 0, step = 0, count = 0;
-  if (!col) {
-    line = u / g.NC;
-    chunk = u - line * g.NC;
-    j0 = line * g.D + chunk;
-    step = g.NC;
-    count = g.chr;
-  } else if (u < g.D * g.NC) {
-    chunk = u / g.D;
-    line = u - chunk * g.D;
-    j0 = chunk * g.chc * g.D + line;
-    step = g.D;
-    count = g.chc;
-  } else {
-    // lines D .. H-1 of the column problem do not exist: infinity, so that both problems have H entries
-    const uint32_t v = u - g.D * g.NC;
-    line = g.D + v / g.NC;
-    chunk = v - (v / g.NC) * g.NC;
-  }
+  const R2Chunk c = r2_chunk(g, t);
   Xyzz<F> acc;
   xyzz_set_inf(acc);
   // (A software pipeline -- final-location word two buckets ahead, record one bucket ahead -- measured no faster than
   // this plain loop once the chunks were interleaved: the kernel is bound by the multiplier at 2 waves per SIMD, and the
   // other wave covers the two dependent loads of a bucket.)
 #pragma unroll 1
-  for (uint32_t i = 0; i < count; i++) {
-    const uint32_t j = j0 + i * step;
-    if (j >= 1) add_bucket<F>(acc, kw * g.L + (j - 1), slots, points, bfin);
+  for (uint32_t i = 0; i < c.count; i++) {
+    const uint32_t j = c.j0 + i * c.step;
+    if (j >= 1) add_bucket<F>(acc, c.kw * g.L + (j - 1), slots, points, bfin);
   }
-  if (!col && line == g.H / 2 && chunk == 0) {
-    // the single bucket of weight L = H D is folded in as 2 * (H/2) * D
-    for (int twice = 0; twice < 2; twice++) add_bucket<F>(acc, kw * g.L + (g.L - 1), slots, points, bfin);
+  if (c.fold) {
+    for (int twice = 0; twice < 2; twice++) add_bucket<F>(acc, c.kw * g.L + (g.L - 1), slots, points, bfin);
   }
-  WeierPolicy<F>::store(part + ((size_t)(prob * g.H + line) * g.NC + chunk) * 4 * F::NW, acc);
+  WeierPolicy<F>::store(part + ((size_t)(c.prob * g.H + c.line) * g.NC + c.chunk) * 4 * F::NW, acc);
 }
 
 // The same partial sums for the msmBasic path (msm-basic.ts:106-128 buckets in XYZZ / extended coordinates): bucket g is
-// the sum of the partial accumulators accs[cscan[g] .. cscan[g+1]) that k_bucket_accumulate left of it.
+// the sum of the partial accumulators accs[cscan[g] .. cscan[g+1]) that k_bucket_accumulate left of it (cscan == nullptr:
+// accs holds ONE accumulator per bucket, in bucket order -- the sums k_bucket_sums formed).
 template <class P>
 __global__ void __launch_bounds__(128, MSMZ_REDUCE_OCC) k_reduce2d_partial_acc(uint32_t* part, const uint32_t* accs,
                                                                                const uint32_t* cscan, R2Geom g,
                                                                                uint32_t total) {
-  constexpr int XW = P::ACC_WORDS;
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= total) return;
-  const uint32_t per_prob = g.H * g.NC;
-  const uint32_t prob = t / per_prob, u = t - prob * per_prob;
-  const uint32_t kw = prob >> 1;
-  const bool col = (prob & 1u) != 0;
-  uint32_t line, chunk, j0 = 0, step = 0, count = 0;
-  if (!col) {
-    line = u / g.NC;
-    chunk = u - line * g.NC;
-    j0 = line * g.D + chunk;
-    step = g.NC;
-    count = g.chr;
-  } else if (u < g.D * g.NC) {
-    chunk = u / g.D;
-    line = u - chunk * g.D;
-    j0 = chunk * g.chc * g.D + line;
-    step = g.D;
-    count = g.chc;
-  } else {
-    const uint32_t v = u - g.D * g.NC;
-    line = g.D + v / g.NC;
-    chunk = v - (v / g.NC) * g.NC;
-  }
-  typename P::Acc acc, tmp, p;
+  const R2Chunk c = r2_chunk(g, t);
+  typename P::Acc acc;
   P::set_identity(acc);
-  auto add_bucket_acc = [&](size_t gb) {
-    const uint32_t q0 = cscan ? cscan[gb] : (uint32_t)gb, q1 = cscan ? cscan[gb + 1] : (uint32_t)gb + 1u;
-    for (uint32_t q = q0; q < q1; q++) {
-      P::load(p, accs + (size_t)q * XW);
-      P::add(tmp, acc, p);
-      acc = tmp;
-    }
-  };
-  // the chunk ranges of the next bucket are requested one step ahead (cscan == nullptr: accs holds ONE accumulator
-  // per bucket, in bucket order -- the sums k_bucket_sums formed)
-  uint32_t qa = 0, qb = 0;
-  auto range = [&](uint32_t i, uint32_t& a, uint32_t& b) {
-    const uint32_t j = j0 + i * step;
+  // [a, b) = the accumulators of the bucket of weight j of this set (none for weight 0)
+  auto range = [&](uint32_t j, uint32_t& a, uint32_t& b) {
     a = b = 0;
-    if (i < count && j >= 1) {
-      const size_t gb = (size_t)kw * g.L + (j - 1);
+    if (j >= 1) {
+      const size_t gb = (size_t)c.kw * g.L + (j - 1);
       a = cscan ? cscan[gb] : (uint32_t)gb;
       b = cscan ? cscan[gb + 1] : (uint32_t)gb + 1u;
     }
   };
-  range(0, qa, qb);
+  // the chunk ranges of the next bucket are requested one step ahead
+  uint32_t qa = 0, qb = 0;
+  if (c.count) range(c.j0, qa, qb);
 #pragma unroll 1
-  for (uint32_t i = 0; i < count; i++) {
-    uint32_t na, nb;
-    range(i + 1, na, nb);
-    for (uint32_t q = qa; q < qb; q++) {
-      P::load(p, accs + (size_t)q * XW);
-      P::add(tmp, acc, p);
-      acc = tmp;
-    }
+  for (uint32_t i = 0; i < c.count; i++) {
+    uint32_t na = 0, nb = 0;
+    if (i + 1 < c.count) range(c.j0 + (i + 1) * c.step, na, nb);
+    add_accs<P>(acc, accs, qa, qb);
     qa = na;
     qb = nb;
   }
-  if (!col && line == g.H / 2 && chunk == 0) {
-    for (int twice = 0; twice < 2; twice++) add_bucket_acc((size_t)kw * g.L + (g.L - 1));
+  if (c.fold) {
+    range(g.L, qa, qb);
+    for (int twice = 0; twice < 2; twice++) add_accs<P>(acc, accs, qa, qb);
   }
-  P::store(part + ((size_t)(prob * g.H + line) * g.NC + chunk) * XW, acc);
+  P::store(part + ((size_t)(c.prob * g.H + c.line) * g.NC + c.chunk) * P::ACC_WORDS, acc);
 }
 
 // Buckets of several partial accumulators (large msmBasic inputs): one accumulator per bucket, in bucket order, so that

@@ -72,9 +72,10 @@ struct Staging {
   }
 };
 
-// The hooks of one engine.  A friend of Engine<Cfg>: the hooks launch on its stream, into its buffers, and run its own
-// sort stage (BucketSort::run, sort.h) and phases (plan_phase, launch_batch_add_b, bucket_sums, the two halves of reduce_2d, reduce_levels).  Its planner and its
-// reduction thresholds they only read, and vary in copies.
+// The hooks of one engine.  A friend of Engine<Cfg>: the hooks launch on its stream, stage through stage_ and meta_, fill
+// the buffers its stages share (slots_, bfin_, rscan_, desc_) as inputs, and run its own sort stage (BucketSort::run,
+// sort.h), reduction stage (the public interface of BucketReduce, reduce.h), batch adder (batch_adder, batch_add.h) and
+// plan_phase.  Its planner and its reduction thresholds they only read, and vary in copies.
 template <class Cfg>
 class TestHooks : public ITestHooks {
   using E = Engine<Cfg>;
@@ -301,8 +302,8 @@ class TestHooks : public ITestHooks {
         (st = eng_.fetch_error(&err)))
       return st;
     if (err) return MSMZ_ERR_RANGE;   // a coordinate >= p
-    eng_.launch_batch_add_b(B, (uint32_t)n_pairs, safe != 0, d_pts.as<uint32_t>(), sg.at<const uint2>(idesc),
-                          (uint32_t)out_base, d_meta);
+    eng_.batch_adder().launch((uint32_t)n_pairs, safe != 0, d_pts.as<uint32_t>(), sg.at<const uint2>(idesc),
+                              (uint32_t)out_base, d_meta, B);
     MSMZ_HIP(hipGetLastError());
     if constexpr (!TE)
       hipLaunchKernelGGL((k_test_slots_out<F>), dim3((n_pairs + 255) / 256), dim3(256), 0, eng_.stream_,
@@ -321,7 +322,7 @@ class TestHooks : public ITestHooks {
     if (TE && locs) return MSMZ_ERR_UNSUPPORTED;
     if (a.tail_n > 4096 || a.quad16_max > CAP || a.pairsum_x4_max > CAP) return MSMZ_ERR_ARG;
     if (a.n_points > CAP || a.n_slots > CAP || (a.n_points && !a.points_xy) || (a.n_slots && !a.slots_xy)) return MSMZ_ERR_ARG;
-    // geometry: a plan of `nsets` bucket sets of window size c, as far as the 2-D reduction / reduce_levels read one
+    // geometry: a plan of `nsets` bucket sets of window size c, as far as Planner::r2_geom and the hook read one
     Plan pl{};
     pl.nprob = 1;
     pl.F = 1;
@@ -339,7 +340,7 @@ class TestHooks : public ITestHooks {
       nb = pl.nb = a.nsets * pl.L;
       Planner<Fr> pr = eng_.planner_;
       if (a.nc) pr.k.r2_nc = a.nc;
-      g = E::r2_geom(pl, pr.split_2d(pl));
+      g = pr.r2_geom(pl);
       if (a.nc != 0 && ((a.nc & (a.nc - 1)) != 0 || a.nc > g.D)) return MSMZ_ERR_ARG;
       n_res = 2 * a.nsets;
       // every location / chunk range names a supplied operand: the kernels read whatever these point at
@@ -386,11 +387,13 @@ class TestHooks : public ITestHooks {
                            d_scale ? d_scale + first * NW : nullptr, (uint32_t)n, &d_meta->error);
     };
     DevBuf d_pts;   // LOCATIONS: the resident point set (freed on every return)
+    BucketReduce<Cfg>& red = eng_.reduce_;
     if (levels) {
       const size_t n = (size_t)a.nsets * a.n_in;
-      if ((st = eng_.red_[0].ensure(n * AW * 4)) || (st = eng_.red_[1].ensure(n * AW * 4))) return st;
-      accs_in(eng_.red_[0].template as<uint32_t>(), 0, n);
-      accs_in(eng_.red_[1].template as<uint32_t>(), n, n);
+      uint32_t *rows, *c;
+      if ((st = red.level_inputs(n, &rows, &c))) return st;
+      accs_in(rows, 0, n);
+      accs_in(c, n, n);
     } else if (locs) {
       if ((st = eng_.bfin_.ensure((size_t)nb * 16))) return st;
       MSMZ_HIP(hipMemcpyAsync(eng_.bfin_.p, a.loc, (size_t)nb * 16, hipMemcpyHostToDevice, eng_.stream_));
@@ -408,21 +411,22 @@ class TestHooks : public ITestHooks {
     if (err) return MSMZ_ERR_ARG;          // a zero scale
 
     if (levels) {
-      int cur = 0;
-      if ((st = eng_.template reduce_levels<P>(rk, cur, a.n_in, a.nsets))) return st;
+      if ((st = red.levels(rk, a.n_in, a.nsets, eng_.stream_))) return st;
     } else {
-      const bool summed = a.mode == MSMZ_TR_ACCS_SUMMED;
-      if (summed && (st = eng_.template bucket_sums<P>(nb))) return st;
-      int rows = 0;   // the red_ buffer that holds the line sums: read out here, before the weighted levels reuse it
-      if ((st = eng_.template line_sums_2d<P>(g, rk, d_pts.as<uint32_t>(), !locs, summed, &rows))) return st;
+      const uint32_t* slots = eng_.slots_.template as<uint32_t>();
+      BucketSource src = locs ? BucketSource::locations(slots, d_pts.as<uint32_t>(), eng_.bfin_.template as<uint4>())
+                              : BucketSource::chunks(slots, eng_.rscan_.template as<uint32_t>());
+      if (a.mode == MSMZ_TR_ACCS_SUMMED && (st = red.bucket_sums(src, nb, eng_.stream_, &src))) return st;
+      const uint32_t* lines;   // read out here, before the weighted levels reuse them
+      if ((st = red.line_sums(g, rk, src, eng_.stream_, &lines))) return st;
       if (n_lines)
         hipLaunchKernelGGL((k_test_accs_out<P>), dim3((n_lines + 63) / 64), dim3(64), 0, eng_.stream_,
-                           sg.at<uint32_t>(ilines), eng_.red_[rows].template as<uint32_t>(), n_lines);
-      if ((st = eng_.template weighted_sums_2d<P>(g, rk, rows))) return st;
+                           sg.at<uint32_t>(ilines), lines, n_lines);
+      if ((st = red.weighted_sums(g, rk, eng_.stream_))) return st;
     }
     MSMZ_HIP(hipGetLastError());
     hipLaunchKernelGGL((k_test_accs_out<P>), dim3((n_res + 63) / 64), dim3(64), 0, eng_.stream_, sg.at<uint32_t>(ires),
-                       eng_.final_.template as<uint32_t>(), n_res);
+                       red.final(), n_res);
     return sg.download();
   }
 
@@ -508,7 +512,7 @@ class TestHooks : public ITestHooks {
     int st;
     if ((st = d_pts.ensure((np ? np : 1) * E::PW_WORDS * 4))) return st;
     if ((st = eng_.slots_.ensure(((size_t)recs + 64) * SlotFmt<F>::WORDS * 4))) return st;
-    MSMZ_HIP(hipMemsetAsync(eng_.slots_.p, 0xa5, E::slot_words((recs + 63u) & ~63u) * 4, eng_.stream_));
+    MSMZ_HIP(hipMemsetAsync(eng_.slots_.p, 0xa5, slot_words<F>((recs + 63u) & ~63u) * 4, eng_.stream_));
     uint32_t* d_error = &eng_.meta_.template as<MsmMeta>()->error;
     if constexpr (!TE) {
       if (np)

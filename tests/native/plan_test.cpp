@@ -6,7 +6,8 @@
 // (SortGeom, bins, k_fine's top bin, specialized window size, two-level or fallback), plan chunks, the 2-D split, the
 // first reduction group, batch_size and precompute_params.  Also asserted: a folded plan is two-level; a shape
 // precompute_params accepts plans two-level for the assumed and the proven GLV bit length; a sub-batch of batch_size
-// fits kMaxBatchEntries; a two-level layout has at most SORT_MAX_BINS bins.  Exit code = number of mismatches.
+// fits kMaxBatchEntries; a two-level layout has at most SORT_MAX_BINS bins; the invariants of the 2-D reduction's
+// geometry (r2_geom_cases).  Exit code = number of mismatches.
 #include <cstdio>
 #include <cstdint>
 #include <cstring>
@@ -590,7 +591,33 @@ static void replay(const char* name) {
     }
 }
 
+// Planner::r2_geom, the 2-D reduction's kernel argument: the split of split_2d (with and without an r2_nc override) cut
+// into whole chunks along both directions, two problems per bucket set of the batch
+static void r2_geom_cases() {
+  for (uint32_t nc : {0u, 1u, 4u, 64u})
+    for (int c : {2, 3, 8, 9, 17})
+      for (uint32_t nprob : {1u, 3u}) {
+        Planner<Bls377Fr> pr;
+        pr.k.r2_nc = nc;
+        Plan pl{};
+        pl.c = c;
+        pl.L = 1u << (c - 1);
+        pl.K = pl.Keff = 5;
+        pl.nprob = nprob;
+        pl.nb = (uint32_t)pl.Keff * pl.L;
+        const Split2d sp = pr.split_2d(pl);
+        const R2Geom g = pr.r2_geom(pl);
+        shapes++;
+        const bool split = g.L == pl.L && g.H == sp.H && g.D == sp.D && g.NC == sp.NC && g.H == 1u << ((c - 1 + 1) / 2);
+        const bool whole = g.H * g.D == g.L && g.chr * g.NC == g.D && g.chc * g.NC == g.H && g.chr >= 1 && g.chc >= 1;
+        const bool chunks = (g.NC & (g.NC - 1)) == 0 && g.NC <= g.D && (nc == 0 || g.NC == (nc < g.D ? nc : g.D));
+        if (!split || !whole || !chunks || g.nprob != 2u * nprob * (uint32_t)pl.Keff)
+          mismatch("r2_geom", "bls12-377", 0, c, 0, 0, (int)nc, nprob, 1);
+      }
+}
+
 int main() {
+  r2_geom_cases();
   replay<Bls377Fr, false>("bls12-377");
   replay<PallasFr, false>("pallas");
   replay<Bls381Fr, false>("bls12-381");

@@ -1,5 +1,5 @@
-"""The bucket reduction alone (reduce_2d / reduce_levels of csrc/engine.h and the kernels of csrc/reduce2d_kernels.h and
-csrc/kernels.h) through msmz_test_reduce (csrc/test_hooks.h), on caller-built buckets, stage by stage against oracle/bigint_ref.py.
+"""The bucket reduction alone (BucketReduce of csrc/reduce.h: run_2d's two halves and levels; the kernels of
+csrc/reduce2d_kernels.h and csrc/kernels.h) through msmz_test_reduce (csrc/test_hooks.h), on caller-built buckets, stage by stage against oracle/bigint_ref.py.
 
 A whole MSM shows the reduction only through one point: which level kernel ran is decided by thresholds a release
 build cannot move, every bucket sum of a large MSM is a distinct random point, and the row / column result of a bucket
@@ -14,9 +14,10 @@ Mutations run against this module on an MI355X (one at a time, values only -- no
 store changes --, each in a scratch build, `pytest -x`) and the first test that failed:
   (a) xyzz_add_x4: the `!dbl && fe_is_zero(P)` branch never taken (P = Q undetected on the generic lanes)
         test_geometry[bls12-377-locations]: c=5 sets=1 NC=4, WEIGHTED SUM wrong, all line sums right, problems 0, 1
-  (b) k_reduce2d_partial / _acc: the `line == g.H / 2` fold of the weight-L bucket moved to line 0
+  (b) k_reduce2d_partial / _acc (since then one place, r2_chunk's `fold`): the `line == g.H / 2` fold of the weight-L
+      bucket moved to line 0
         test_geometry[bls12-377-locations]: c=2, LINE SUM wrong in problem 0 (rows), lines 0 and 1
-  (c) k_reduce2d_partial_acc: the look-ahead `range(i + 1, ...)` -> `range(i, ...)`
+  (c) k_reduce2d_partial_acc: the look-ahead one bucket too early, `range(i + 1, ...)` -> `range(i, ...)`
         test_geometry[bls12-377-accs]: c=2, LINE SUM wrong in problem 1 (columns), line 0
   (d) k_fill_neutral storing an all-zero record (not a point on twisted Edwards)
         test_geometry[ed-on-bls12-377-accs]: c=2, WEIGHTED SUM wrong, all line sums right (Weierstrass runs pass)
@@ -517,7 +518,7 @@ LEVEL_KERNELS = [(t, q, 0) for t in (1, 4, 32, 4096) for q in (1, 1 << 20)]
 @pytest.mark.parametrize("nprob", [1, 3, 33])
 @pytest.mark.parametrize("label", ALL)
 def test_levels_shapes(ctxs, label, nprob):
-    """reduce_levels on n_in entries that are not a power of four, with non-neutral C inputs (the form reduce_affine.h
+    """BucketReduce::levels on n_in entries that are not a power of four, with non-neutral C inputs (the form reduce_affine.h
     feeds it), every level kernel forced"""
     for n_in in N_INS:
         rng = np.random.default_rng(n_in * 64 + nprob)
