@@ -47,8 +47,9 @@ enum {
   MSMZ_ERR_UNSUPPORTED = 4,  /* option combination not available for this curve */
   MSMZ_ERR_DEGENERATE = 5,   /* msmUnsafe hit P + (+-P): a batch inversion saw a zero denominator
                                 (the reference traps with wasm `unreachable`, inverse.ts:198-199) */
-  MSMZ_ERR_RANGE = 6         /* a scalar is >= the group order (or >= 2^bits of msmz_opts.reserved[1]) / a coordinate is >= p;
+  MSMZ_ERR_RANGE = 6,        /* a scalar is >= the group order (or >= 2^bits of msmz_opts.reserved[1]) / a coordinate is >= p;
                                 imported Montgomery residues: the residue itself is >= q / >= p */
+  MSMZ_ERR_POINT = 7         /* a compressed record is not a point of the curve: no square root, or a sign bit on a zero root */
 };
 
 enum { MSMZ_BUCKETS_AFFINE = 0, MSMZ_BUCKETS_PROJECTIVE = 1 };
@@ -129,6 +130,13 @@ int msmz_random_scalars(msmz_ctx* ctx, uint64_t n, uint64_t seed, uint64_t* hand
 int msmz_download_points(msmz_ctx* ctx, uint64_t handle, uint64_t first, uint64_t count, uint8_t* xy_le,
                          uint8_t* is_inf /* nullable */);
 int msmz_download_scalars(msmz_ctx* ctx, uint64_t handle, uint64_t first, uint64_t count, uint8_t* scalars_le32);
+/* msmz_download_points with compressed records (below, MSMZ_SRC_COMPRESSED): out receives count * fe_bytes bytes, the
+ * wire coordinate with the sign bit in bit 7 of the last byte; flags = 0 (sign = larger root) or MSMZ_SRC_SIGN_PARITY
+ * (sign = odd), anything else is MSMZ_ERR_ARG.  The range rules are those of msmz_download_points.  A point at infinity
+ * is written as all-zero bytes with is_inf = 1; is_inf is nullable but the bytes alone do not tell infinity from the
+ * point (0, 1) of BLS12-377, which also compresses to zeros.  ed-on-bls12-377 has no infinity: is_inf is all 0. */
+int msmz_download_points_compressed(msmz_ctx* ctx, uint64_t handle, uint64_t first, uint64_t count, uint8_t* out,
+                                    uint8_t* is_inf /* nullable */, uint32_t flags);
 int msmz_free(msmz_ctx* ctx, uint64_t handle);
 
 /* Import: make a resident handle of records where the caller has them, in the form they have.
@@ -148,6 +156,22 @@ int msmz_free(msmz_ctx* ctx, uint64_t handle);
  *   MSMZ_SRC_MONTGOMERY   records are 64-bit-limb Montgomery residues (arkworks / sppark style; little-endian limbs =
  *                         little-endian bytes): scalars v * 2^256 mod q (width 32 only), coordinates
  *                         v * 2^(8 fe_bytes) mod p.  Converted on the GPU.
+ *   MSMZ_SRC_COMPRESSED   points only: a record is ONE coordinate, fe_bytes little-endian canonical
+ *                         bytes -- x on the Weierstrass curves, y on ed-on-bls12-377 -- with the sign of the other
+ *                         coordinate in bit 7 of the last byte (free in all four fields).  `width` is 0 or fe_bytes.  The
+ *                         GPU recovers the other coordinate (one field square root per point) and the handle is an
+ *                         ordinary point handle: msmz_download_points returns x || y.  sign = 1 means the canonical value
+ *                         of the recovered coordinate is larger than (p - 1) / 2 (believed to match arkworks' YIsNegative
+ *                         flag and zcash's "lexicographically largest"; neither library was run against this); with
+ *                         MSMZ_SRC_SIGN_PARITY it means that value is odd (believed to match pasta_curves).  A recovered
+ *                         coordinate of 0 takes sign 0 only.  There is no infinity bit in the record: infinity is is_inf,
+ *                         and a flagged record is not decompressed, its bytes may be anything (on ed-on-bls12-377, which has
+ *                         no point at infinity, it becomes the identity (0, 1)).  An arkworks record with
+ *                         its infinity flag in bit 6 is a coordinate >= p on BLS12-377 / BLS12-381: MSMZ_ERR_RANGE.
+ *                         Not with MSMZ_SRC_MONTGOMERY; MSMZ_SRC_SIGN_PARITY needs MSMZ_SRC_COMPRESSED; either flag on a
+ *                         scalar source is MSMZ_ERR_ARG.  MSMZ_ERR_RANGE: a coordinate >= p once the sign bit is masked
+ *                         off.  MSMZ_ERR_POINT: a record with no square root, or a sign bit on a zero root.  Both are found
+ *                         by the kernel, RANGE wins when both occur; no handle is created, the context stays usable.
  * Every import returns after the GPU has read the source: it may be overwritten or freed at once.
  * Errors.  MSMZ_ERR_ARG, before anything is launched: a null descriptor / pointer / handle pointer, n == 0 (scalars:
  * n >= 2^32; points: the limits of msmz_upload_points), unknown flag bits, a stream without MSMZ_SRC_DEVICE, a pointer not
@@ -165,12 +189,14 @@ int msmz_free(msmz_ctx* ctx, uint64_t handle);
 enum {
   MSMZ_SRC_DEVICE = 1,
   MSMZ_SRC_MONTGOMERY = 2,
-  MSMZ_SRC_DEFAULT_STREAM = 4   /* with MSMZ_SRC_DEVICE and a NULL stream: the data is produced on the null stream */
+  MSMZ_SRC_DEFAULT_STREAM = 4,  /* with MSMZ_SRC_DEVICE and a NULL stream: the data is produced on the null stream */
+  MSMZ_SRC_COMPRESSED = 8,      /* points: records are one coordinate + sign bit */
+  MSMZ_SRC_SIGN_PARITY = 16     /* with MSMZ_SRC_COMPRESSED: the sign bit is the parity, not "the larger root" */
 };
 typedef struct msmz_src {
   const void* ptr;        /* first record */
   uint64_t stride;        /* bytes from one record to the next; 0 = packed (= the width) */
-  uint32_t width;         /* scalars: bytes per record, 4..32, a multiple of 4; points: 0 or 2 * fe_bytes */
+  uint32_t width;         /* scalars: bytes per record, 4..32, a multiple of 4; points: 0 or 2 * fe_bytes (compressed: fe_bytes) */
   uint32_t flags;         /* MSMZ_SRC_* */
   void* stream;           /* MSMZ_SRC_DEVICE: the hipStream_t whose work produces the data; NULL = the data is ready */
   const uint8_t* is_inf;  /* points only, nullable: one flag byte per point, packed, same memory space as ptr; checked but

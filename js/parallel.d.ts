@@ -8,6 +8,8 @@ export type BigintPoint = { x: bigint; y: bigint; isZero?: boolean };
 export interface NttOptions { inverse?: boolean; shift?: bigint | null; root?: bigint | null; nIn?: number | null; count?: number;
                               first?: number; out?: DeviceArray | null; firstOut?: number }
 /** the checked arguments of Parallel.ntt (host only) */
+/** compressed / sign of pointsFromBytes and pointsToCompressedBytes, checked before any call */
+export function compressedArgs(who: string, compressed?: boolean, sign?: "largest" | "parity", montgomery?: boolean): { compressed: boolean; sign: "largest" | "parity" };
 export function nttArgs(x: { handle: unknown; n: number; kind: string }, logN: number, options: NttOptions | undefined, order: bigint):
   { logN: number; flags: number; nIn: number; count: number; first: number; firstOut: number; root: bigint | null; shift: bigint | null };
 export interface DeviceArray extends Array<DeviceArray> { readonly n: number; readonly kind: "points" | "scalars" | "precomputed";
@@ -24,6 +26,12 @@ export interface ParallelApi {
   pointsFromBytes(bytes: Uint8Array, n?: number, isInf?: Uint8Array): Promise<DeviceArray>;
   /** coordinates as 64-bit-limb Montgomery residues v * 2^(8 feBytes) mod p, converted on the GPU */
   pointsFromBytes(bytes: Uint8Array, n: number | undefined, options: { montgomery?: boolean; isInf?: Uint8Array }): Promise<DeviceArray>;
+  /** compressed records of feBytes bytes: one coordinate (x; y on the twisted Edwards curve) with the sign of the other in
+   * bit 7 of the last byte; sign "largest" (default): the canonical value is above (p - 1) / 2, "parity": it is odd.  The
+   * GPU recovers the other coordinate; a record that is no point throws with code "7" */
+  pointsFromBytes(bytes: Uint8Array, n: number | undefined, options: { compressed: true; sign?: "largest" | "parity"; isInf?: Uint8Array }): Promise<DeviceArray>;
+  /** points [first, first + count) as compressed records; a point at infinity is an all-zero record with isInf 1 */
+  pointsToCompressedBytes(points: DeviceArray, options?: { first?: number; count?: number; sign?: "largest" | "parity" }): Promise<{ records: Uint8Array; isInf: Uint8Array }>;
   scalarsFromBytes(bytes: Uint8Array, n?: number): Promise<DeviceArray>;
   /** `width` bytes per scalar on the wire (4..32, a multiple of 4); montgomery: 32-byte records v * 2^256 mod q */
   scalarsFromBytes(bytes: Uint8Array, n: number | undefined, options: { width?: number; montgomery?: boolean }): Promise<DeviceArray>;

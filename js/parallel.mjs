@@ -90,6 +90,15 @@ function scanRanges(who, ranges, n, out = null, limit = 2 ** 32) {
 /** The arguments of Parallel.ntt -> {logN, flags, nIn, count, first, firstOut, root, shift}, checked before anything
  * reaches the device (msm_zprize_amd/parallel.py ntt_args is the same function).  root / shift: a bigint or null.  Whether
  * `root` is a primitive root of unity, and whether the field has transforms of this length, is the library's to say. */
+/** compressed / sign of pointsFromBytes and pointsToCompressedBytes, checked before any call -> {compressed, sign} */
+export function compressedArgs(who, compressed = false, sign = "largest", montgomery = false) {
+  if (typeof compressed !== "boolean") throw TypeError(`${who}: compressed is true or false`);
+  if (sign !== "largest" && sign !== "parity") throw Error(`${who}: sign is "largest" or "parity", got ${String(sign)}`);
+  if (!compressed && sign !== "largest") throw Error(`${who}: sign "parity" describes compressed records (compressed: true)`);
+  if (compressed && montgomery) throw Error(`${who}: compressed records are canonical, not Montgomery residues`);
+  return { compressed, sign };
+}
+
 export function nttArgs(x, logN, { inverse = false, shift = null, root = null, nIn = null, count = 1, first = 0, out = null, firstOut = 0 } = {}, order) {
   const who = "ntt";
   // (anything with the three fields of a resident array will do here: Parallel.ntt asks for the real thing first)
@@ -524,15 +533,37 @@ function createCurve(params, kind) {
     async pointsFromBytes(bytes, n, isInf) {
       if (typeof bytes === "number")   // (pointPtr, pointInputPtr, n)
         return fromPointer("pointsFromBytes", bytes, n, isInf, 2 * fb, (b) => N.uploadPoints(ctx, b, null, isInf), "points");
-      // (bytes, n?, {montgomery, isInf}): coordinates as 64-bit-limb Montgomery residues v * 2^(8 feBytes) mod p
-      let montgomery = false;
+      // (bytes, n?, {montgomery, compressed, sign, isInf}): coordinates as 64-bit-limb Montgomery residues
+      // v * 2^(8 feBytes) mod p; or compressed records of feBytes bytes, one coordinate (x; y on the twisted Edwards
+      // curve) with the sign of the other in bit 7 of the last byte -- sign "largest": the canonical value is above
+      // (p - 1) / 2, "parity": it is odd.  The GPU recovers the other coordinate; a record that is no point throws with
+      // code "7".
+      let montgomery = false, compressed = false, sign = "largest";
       if (isInf && typeof isInf === "object" && !ArrayBuffer.isView(isInf) && !Array.isArray(isInf)) {
-        montgomery = !!isInf.montgomery; isInf = isInf.isInf;
+        montgomery = !!isInf.montgomery;
+        ({ compressed, sign } = compressedArgs("pointsFromBytes", isInf.compressed, isInf.sign, montgomery));
+        isInf = isInf.isInf;
+      }
+      if (compressed) {
+        n = n === undefined ? Math.floor(bytes.length / fb) : n;
+        if (!(n > 0) || bytes.length < fb * n || (isInf && isInf.length < n)) throw Error(`pointsFromBytes: ${bytes.length} bytes for ${n} compressed points`);
+        return DeviceArray.make(curve, N.importPointsCompressed(ctx, Buffer.from(bytes), isInf ? Buffer.from(isInf) : null, n, sign === "parity"), n, "points");
       }
       n = n === undefined ? Math.floor(bytes.length / (2 * fb)) : n;
       if (!(n > 0) || bytes.length < 2 * fb * n || (isInf && isInf.length < n)) throw Error(`pointsFromBytes: ${bytes.length} bytes for ${n} points`);
       if (montgomery) return DeviceArray.make(curve, N.importPoints(ctx, Buffer.from(bytes), isInf ? Buffer.from(isInf) : null, n, true), n, "points");
       return DeviceArray.make(curve, N.uploadPoints(ctx, Buffer.from(bytes), isInf ? Buffer.from(isInf) : null, n), n, "points");
+    },
+    /** points [first, first + count) of a resident point array as compressed records (msmz_download_points_compressed):
+     * {records: Buffer of count * feBytes, isInf: Buffer of count}; infinity is an all-zero record with flag 1 */
+    async pointsToCompressedBytes(points, { first = 0, count, sign } = {}) {
+      if (!(points instanceof DeviceArray) || points.kind !== "points")
+        throw TypeError("pointsToCompressedBytes: `points` is a resident point array (pointsFromBytes / randomPointsFast)");
+      ({ sign } = compressedArgs("pointsToCompressedBytes", true, sign, false));
+      count = count === undefined ? points.n - first : count;
+      if (!Number.isInteger(first) || !Number.isInteger(count) || first < 0 || count <= 0 || first + count > points.n)
+        throw Error(`pointsToCompressedBytes: points [${first}, +${count}) of an array of ${points.n}`);
+      return N.downloadPointsCompressed(ctx, points.handle, first, count, fb, sign === "parity");
     },
     /** parallel.ts:114-133: 32 bytes little-endian per scalar */
     async scalarsFromBytes(bytes, n, count) {

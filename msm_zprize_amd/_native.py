@@ -26,6 +26,8 @@ class MsmzLog(C.Structure):
 
 
 MSMZ_SRC_DEVICE, MSMZ_SRC_MONTGOMERY, MSMZ_SRC_DEFAULT_STREAM = 1, 2, 4
+MSMZ_SRC_COMPRESSED, MSMZ_SRC_SIGN_PARITY = 8, 16   # compressed point records and their second sign convention
+MSMZ_ERR_POINT = 7                                  # a compressed record is not a point of the curve
 
 
 class MsmzSrc(C.Structure):   # msmz_src (include/msmz.h): where an imported set lies and in which form
@@ -128,6 +130,8 @@ EXPORTS = {
     "msmz_random_points": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "msmz_random_scalars": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "msmz_download_points": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_char_p, C.c_char_p]),
+    "msmz_download_points_compressed": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_char_p, C.c_char_p,
+                                                  C.c_uint32]),
     "msmz_download_scalars": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_char_p]),
     "msmz_free": (C.c_int, [C.c_void_p, C.c_uint64]),
     "msmz_msm": (C.c_int, [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(MsmzOpts), C.c_char_p,

@@ -17,6 +17,7 @@
 // (src/curve-twisted-edwards.ts:84-165, EFD add-2008-hwcd-3 with k = 2d).
 #pragma once
 #include "fp.h"
+#include "sqrt.h"
 
 namespace msmz {
 
@@ -447,6 +448,35 @@ MSMZ_HD bool te_on_curve(const Fe<F>& x, const Fe<F>& y) {
   return fe_is_zero(yy);
 }
 
+// ------------------------------------------------------------------------------------------------ compressed points
+// A compressed record is one coordinate (the "wire" coordinate: x on the Weierstrass curves, y on the twisted Edwards
+// curve) plus the sign of the other.  Two conventions for the sign of a canonical value c in [0, p):
+//   largest (parity = 0)  sign = 1 iff c > (p - 1) / 2
+//   parity  (parity = 1)  sign = 1 iff c is odd
+// Of the two roots c and p - c exactly one has either sign (p is odd), except for c = 0, whose only sign is 0.
+constexpr int DECOMPRESS_OK = 0, DECOMPRESS_NOT_A_POINT = 1;
+
+// the sign of the Montgomery residue m under the convention; *zero: the value is 0                               [1M]
+template <class F>
+MSMZ_HD bool fe_wire_sign(bool* zero, const Fe<F>& m, int parity) {
+  Fe<F> t;
+  uint32_t w[F::NW];
+  fe_from_mont(t, m);
+  fe_to_canon_words<F>(w, t);
+  *zero = words_is_zero<F::NW>(w);
+  return parity ? (w[0] & 1u) != 0 : words_geq<F::NW>(w, F::PHALF1);
+}
+
+// r <- the one of r, -r whose sign is `sign`; a sign bit on the root 0 is refused (encodings are unique)
+template <class F>
+MSMZ_HD int fe_choose_root(Fe<F>& r, bool sign, int parity) {
+  bool zero;
+  const bool have = fe_wire_sign<F>(&zero, r, parity);
+  if (zero) return sign ? DECOMPRESS_NOT_A_POINT : DECOMPRESS_OK;
+  if (have != sign) fe_neg(r, r);
+  return DECOMPRESS_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ the group, once
 // What the two curve forms share, under one static interface, host and device: code that walks a scalar, checks a
 // point or builds a table is written once over a group G.  Every member forwards to the formulas above.
@@ -475,6 +505,18 @@ struct WeierGroup {
   static MSMZ_HD void from_affine(Acc& p, const Fe<F>& x, const Fe<F>& y) { xyzz_from_affine(p, Affine<F>{x, y}); }
   static MSMZ_HD void base_from_affine(Base& b, const Fe<F>& x, const Fe<F>& y, bool inf) { b = Base{{x, y}, inf}; }
   static MSMZ_HD bool on_curve(const Fe<F>& x, const Fe<F>& y) { return weier_on_curve(Affine<F>{x, y}); }
+  // (x, y) from the wire coordinate x (a Montgomery residue) and the sign of y: y^2 = x^3 + b   [1M + 1S + fe_sqrt + 1M]
+  static MSMZ_HD int decompress(Fe<F>& x, Fe<F>& y, const Fe<F>& wire, bool sign, int parity) {
+    Fe<F> xx, rhs, b;
+    x = wire;
+    fe_sqr(xx, x);
+    fe_mul(rhs, xx, x);
+    fe_set_const<F>(b, F::B);
+    fe_add(rhs, rhs, b);
+    fe_carry(rhs);
+    if (!fe_sqrt<F>(y, rhs)) return DECOMPRESS_NOT_A_POINT;
+    return fe_choose_root<F>(y, sign, parity);
+  }
   static MSMZ_HD const Fe<F>& denominator(const Acc& p) { return p.ZZZ; }
   static MSMZ_HD void affine_from_inverse(Fe<F>& x, Fe<F>& y, const Acc& p, const Fe<F>& zi3) {
     Fe<F> t, zi2;
@@ -529,6 +571,24 @@ struct TeGroup {
     Fe<F> yc = y;   // (y = (y - x) + x of a record: two lazy values added)
     fe_carry(yc);
     return te_on_curve<F>(x, yc);
+  }
+  // (x, y) from the wire coordinate y and the sign of x: x^2 = (y^2 - 1) / (d y^2 + 1).  The denominator is never zero:
+  // -1 / d is a non-residue (d is one, -1 is not; asserted by tools/gen_constants.py).  [2M + 1S + fe_inverse + fe_sqrt + 1M]
+  static MSMZ_HD int decompress(Fe<F>& x, Fe<F>& y, const Fe<F>& wire, bool sign, int parity) {
+    Fe<F> yy, one, d, num, den, inv, q;
+    y = wire;
+    fe_sqr(yy, y);
+    fe_set_const<F>(one, F::ONE);
+    fe_set_const<F>(d, F::D);
+    fe_sub(num, yy, one);
+    fe_mul(den, yy, d);
+    fe_add(den, den, one);
+    fe_carry(num);
+    fe_carry(den);
+    if (!fe_inverse<F>(inv, den)) return DECOMPRESS_NOT_A_POINT;
+    fe_mul(q, num, inv);
+    if (!fe_sqrt<F>(x, q)) return DECOMPRESS_NOT_A_POINT;
+    return fe_choose_root<F>(x, sign, parity);
   }
   static MSMZ_HD const Fe<F>& denominator(const Acc& p) { return p.Z; }
   static MSMZ_HD void affine_from_inverse(Fe<F>& x, Fe<F>& y, const Acc& p, const Fe<F>& zi) {

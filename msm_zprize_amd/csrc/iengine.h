@@ -24,14 +24,18 @@ struct GenMap {
 // from one record to the next, defaults resolved.  What the pointer points at is the engine's to ask (ResidentSets::vouch).
 static inline int src_check(const msmz_src* s, int point_fe_bytes, uint32_t* width, uint64_t* stride) {
   if (!s || !s->ptr) return MSMZ_ERR_ARG;
-  if (s->flags & ~(uint32_t)(MSMZ_SRC_DEVICE | MSMZ_SRC_MONTGOMERY | MSMZ_SRC_DEFAULT_STREAM)) return MSMZ_ERR_ARG;
+  const uint32_t point_flags = point_fe_bytes ? MSMZ_SRC_COMPRESSED | MSMZ_SRC_SIGN_PARITY : 0u;   // (refused on scalars)
+  if (s->flags & ~(uint32_t)(MSMZ_SRC_DEVICE | MSMZ_SRC_MONTGOMERY | MSMZ_SRC_DEFAULT_STREAM | point_flags)) return MSMZ_ERR_ARG;
+  const bool compressed = (s->flags & MSMZ_SRC_COMPRESSED) != 0;
+  if (compressed ? (s->flags & MSMZ_SRC_MONTGOMERY) != 0 : (s->flags & MSMZ_SRC_SIGN_PARITY) != 0) return MSMZ_ERR_ARG;
   const bool dev = (s->flags & MSMZ_SRC_DEVICE) != 0;
   if (!dev && (s->stream || (s->flags & MSMZ_SRC_DEFAULT_STREAM))) return MSMZ_ERR_ARG;
   if (s->stream && (s->flags & MSMZ_SRC_DEFAULT_STREAM)) return MSMZ_ERR_ARG;
   uint32_t w = s->width;
   if (point_fe_bytes) {
-    if (w != 0 && w != 2u * (uint32_t)point_fe_bytes) return MSMZ_ERR_ARG;
-    w = 2u * (uint32_t)point_fe_bytes;
+    const uint32_t rec = (compressed ? 1u : 2u) * (uint32_t)point_fe_bytes;   // one coordinate + sign bit, or x || y
+    if (w != 0 && w != rec) return MSMZ_ERR_ARG;
+    w = rec;
   } else {
     if (w < 4 || w > 32 || (w & 3u) || s->is_inf) return MSMZ_ERR_ARG;
     if ((s->flags & MSMZ_SRC_MONTGOMERY) && w != 32) return MSMZ_ERR_ARG;
@@ -61,6 +65,9 @@ class IEngine {
   virtual int random_points(uint64_t n, uint64_t seed, const GenMap& map, uint64_t* h) = 0;
   virtual int random_scalars(uint64_t n, uint64_t seed, const GenMap& map, uint64_t* h) = 0;
   virtual int download_points(uint64_t h, uint64_t first, uint64_t count, uint8_t* xy, uint8_t* inf) = 0;
+  // msmz_download_points_compressed: count records of fe_bytes, flags = 0 or MSMZ_SRC_SIGN_PARITY
+  virtual int download_points_compressed(uint64_t h, uint64_t first, uint64_t count, uint8_t* out, uint8_t* inf,
+                                         uint32_t flags) = 0;
   virtual int download_scalars(uint64_t h, uint64_t first, uint64_t count, uint8_t* s) = 0;
   virtual int free_handle(uint64_t h) = 0;
   // `batch` MSMs over the same first n points (msmz_msm_batch): vector k = resident entries [k n, (k + 1) n), or host

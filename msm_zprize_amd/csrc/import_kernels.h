@@ -63,4 +63,76 @@ __global__ void __launch_bounds__(256) k_import_points(uint32_t* out, const uint
   P::store_resident(out, i, n, x, y, flagged, endo);
 }
 
+// Compressed records (msmz_import_points with MSMZ_SRC_COMPRESSED): F::NW little-endian words at
+// src + i * stride, the wire coordinate (x; y on the twisted Edwards curve) with the sign of the other coordinate in
+// bit 7 of the last byte, which every field leaves free.  The bit is masked off, the coordinate range-checked (bit 2 of
+// *err), the point recovered by P::decompress -- one fe_sqrt per point (sqrt.h), the same instructions in every lane --
+// and a record without a root or with a sign bit on a zero root raises bit 3 of *err.  The result goes through
+// P::store_resident exactly as k_import_points writes it.  A flagged record is not read: it becomes the infinity record
+// (the identity (0, 1) on the twisted Edwards curve, which has no point at infinity).  A refused record stores the
+// same: the set is discarded, but every word written is defined.  One thread per point; the tables of the square root
+// are read from constant memory (no LDS), everything else stays in registers.
+template <class P>
+__global__ void __launch_bounds__(256) k_import_points_compressed(uint32_t* out, const uint8_t* src, uint64_t stride,
+                                                                  const uint8_t* is_inf, uint32_t n, int endo,
+                                                                  int parity, uint32_t* err) {
+  using F = typename P::F;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  bool flagged = is_inf != nullptr && is_inf[i] != 0;
+  Fe<F> x, y;
+  bool good = false;
+  if (!flagged) {
+    uint32_t w[F::NW];
+    import_load<F::NW>(w, src, stride, i, F::NW);
+    const bool sign = (w[F::NW - 1] >> 31) != 0;
+    w[F::NW - 1] &= 0x7fffffffu;
+    if (words_geq<F::NW>(w, F::PW)) {
+      atomicOr(err, 4u);
+    } else {
+      Fe<F> c, f, wire;
+      fe_unpack<F>(c, w);
+      import_factor<F>(f, 0);
+      fe_mul(wire, c, f);
+      good = P::decompress(x, y, wire, sign, parity) == DECOMPRESS_OK;
+      if (!good) atomicOr(err, 8u);
+    }
+  }
+  if (!good) {
+    fe_zero(x);
+    fe_set_const<F>(y, F::ONE);
+    flagged = true;
+  }
+  P::store_resident(out, i, n, x, y, flagged, endo);
+}
+
+// resident records -> compressed records of F::NW words (the inverse of the above; msmz_download_points_compressed) and
+// one flag byte per point: the point at infinity is the all-zero record with flag 1.  (The flag cannot be read off the
+// bytes: (0, 1) of BLS12-377 compresses to all-zero bytes under the `largest` convention.)
+template <class P>
+__global__ void __launch_bounds__(256) k_points_compress(uint32_t* out, uint8_t* inf_out, const uint32_t* in, uint32_t n,
+                                                         int parity) {
+  using F = typename P::F;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Fe<F> x, y;
+  const bool inf = P::load_resident_affine(x, y, in + (size_t)i * P::IN_WORDS);
+  uint32_t w[F::NW];
+  if (inf) {
+#pragma unroll
+    for (int j = 0; j < F::NW; j++) w[j] = 0;
+  } else {
+    Fe<F> t;
+    bool zero;
+    fe_carry(y);   // (a twisted-Edwards y is (y - x) + x of a record: two lazy values added)
+    fe_from_mont(t, P::TE ? y : x);
+    fe_to_canon_words<F>(w, t);
+    if (fe_wire_sign<F>(&zero, P::TE ? x : y, parity)) w[F::NW - 1] |= 0x80000000u;   // (the value 0 has sign 0)
+  }
+  uint32_t* o = out + (size_t)i * F::NW;
+#pragma unroll
+  for (int j = 0; j < F::NW; j += 4) *reinterpret_cast<uint4*>(o + j) = make_uint4(w[j], w[j + 1], w[j + 2], w[j + 3]);
+  inf_out[i] = inf ? 1 : 0;
+}
+
 }  // namespace msmz

@@ -126,6 +126,8 @@
   PFX template __global__ void k_points_to_resident<P>(uint32_t*, const uint32_t*, const uint8_t*, uint32_t, int, uint32_t*); \
   PFX template __global__ void k_points_from_resident<P>(uint32_t*, const uint32_t*, uint32_t);                   \
   PFX template __global__ void k_import_points<P>(uint32_t*, const uint8_t*, uint64_t, const uint8_t*, uint32_t, int, int, uint32_t*); \
+  PFX template __global__ void k_import_points_compressed<P>(uint32_t*, const uint8_t*, uint64_t, const uint8_t*, uint32_t, int, int, uint32_t*); \
+  PFX template __global__ void k_points_compress<P>(uint32_t*, uint8_t*, const uint32_t*, uint32_t, int);         \
   PFX template __global__ void k_check_curve<P>(uint8_t*, CheckResult*, const uint32_t*, uint32_t, uint32_t);     \
   PFX template __global__ void k_check_subgroup<P, Fr>(uint8_t*, CheckResult*, const uint32_t*, uint32_t, uint32_t); \
   PFX template __global__ void k_points_mul<P, Fr, false>(uint32_t*, const uint32_t*, const uint32_t*, MulScalar, const uint32_t*, uint32_t, int, int, uint32_t*); \

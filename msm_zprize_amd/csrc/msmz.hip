@@ -57,6 +57,7 @@ const char* msmz_strerror(int status) {
     case MSMZ_ERR_UNSUPPORTED: return "option combination not supported for this curve";
     case MSMZ_ERR_DEGENERATE: return "unsafe batched addition hit a zero denominator (equal or opposite points); use safe=1";
     case MSMZ_ERR_RANGE: return "scalar >= group order or coordinate >= field modulus";
+    case MSMZ_ERR_POINT: return "a compressed record is not a point of the curve";
     default: return "unknown status";
   }
 }
@@ -156,6 +157,10 @@ int msmz_random_scalars(msmz_ctx* c, uint64_t n, uint64_t seed, uint64_t* h) {
 }
 int msmz_download_points(msmz_ctx* c, uint64_t h, uint64_t first, uint64_t count, uint8_t* xy, uint8_t* inf) {
   return c ? c->engine->download_points(h, first, count, xy, inf) : MSMZ_ERR_ARG;
+}
+int msmz_download_points_compressed(msmz_ctx* c, uint64_t h, uint64_t first, uint64_t count, uint8_t* out, uint8_t* inf,
+                                    uint32_t flags) {
+  return c ? c->engine->download_points_compressed(h, first, count, out, inf, flags) : MSMZ_ERR_ARG;
 }
 int msmz_download_scalars(msmz_ctx* c, uint64_t h, uint64_t first, uint64_t count, uint8_t* s) {
   return c ? c->engine->download_scalars(h, first, count, s) : MSMZ_ERR_ARG;

@@ -182,6 +182,16 @@ class MultiEngine : public IEngine {
     });
   }
 
+  int download_points_compressed(uint64_t hd, uint64_t first, uint64_t count, uint8_t* out, uint8_t* inf,
+                                 uint32_t flags) override {
+    const MHandle* pts = range(hd, 0, first, count);
+    if (!pts || !out || (flags & ~(uint32_t)MSMZ_SRC_SIGN_PARITY)) return MSMZ_ERR_ARG;
+    return for_range(*pts, first, count, [&](IEngine* e, uint64_t sub, uint64_t li, uint64_t gi, uint64_t len) {
+      return e->download_points_compressed(sub, li, len, out + (gi - first) * (size_t)fb_,
+                                           inf ? inf + (gi - first) : nullptr, flags);
+    });
+  }
+
   int download_scalars(uint64_t hd, uint64_t first, uint64_t count, uint8_t* s) override {
     const MHandle* sc = range(hd, 1, first, count);
     if (!sc || !s) return MSMZ_ERR_ARG;
@@ -486,7 +496,7 @@ class MultiEngine : public IEngine {
     msmz_src hs{};
     hs.ptr = recs.data();
     hs.width = (uint32_t)(recs.size() / n);
-    hs.flags = s.flags & MSMZ_SRC_MONTGOMERY;
+    hs.flags = s.flags & (MSMZ_SRC_MONTGOMERY | MSMZ_SRC_COMPRESSED | MSMZ_SRC_SIGN_PARITY);   // (the form of the records)
     hs.is_inf = flags.empty() ? nullptr : flags.data();
     return make_set(point_fe_bytes ? 0 : 1, n, h, [&](uint32_t g, IEngine* e, uint64_t cnt, uint64_t* sub) {
       const GenMap split{G_, g, MULTI_BLOCK_SHIFT};
@@ -591,7 +601,8 @@ class MultiEngine : public IEngine {
     });
   }
 
-  // run fn(g, engine) on every device's thread concurrently; first non-zero status wins
+  // run fn(g, engine) on every device's thread concurrently; first non-zero status wins (but MSMZ_ERR_RANGE on any
+  // device beats MSMZ_ERR_POINT, as it does inside one engine's compressed import)
   int for_all(const std::function<int(uint32_t, IEngine*)>& fn) {
     for (uint32_t g = 0; g < G_; g++) {
       Worker* w = workers_[g];
@@ -600,7 +611,7 @@ class MultiEngine : public IEngine {
     int st = MSMZ_OK;
     for (uint32_t g = 0; g < G_; g++) {
       const int s = workers_[g]->wait();
-      if (s && !st) st = s;
+      if (s && (!st || (st == MSMZ_ERR_POINT && s == MSMZ_ERR_RANGE))) st = s;
     }
     return st;
   }

@@ -129,9 +129,14 @@ class ResidentSets : public IEngine {
     if ((st = src_check(&s, FE_BYTES, &v.width, &v.stride)) || (st = new_points(n, &hd)) ||
         (st = import_view(s, FE_BYTES, n, split, &v)))
       return st;
-    st = checked([&](uint32_t* d_err) {   // a coordinate (either form) >= p
-      hipLaunchKernelGGL((k_import_points<P>), dim3((n + 255) / 256), dim3(256), 0, stream_, hd.mem.as<uint32_t>(), v.ptr,
-                         v.stride, v.is_inf, (uint32_t)n, hd.has_endo ? 1 : 0, mont, d_err);
+    st = checked([&](uint32_t* d_err) {   // a coordinate (either form) >= p; a compressed record that is no point
+      if (s.flags & MSMZ_SRC_COMPRESSED)
+        hipLaunchKernelGGL((k_import_points_compressed<P>), dim3((n + 255) / 256), dim3(256), 0, stream_,
+                           hd.mem.as<uint32_t>(), v.ptr, v.stride, v.is_inf, (uint32_t)n, hd.has_endo ? 1 : 0,
+                           (s.flags & MSMZ_SRC_SIGN_PARITY) ? 1 : 0, d_err);
+      else
+        hipLaunchKernelGGL((k_import_points<P>), dim3((n + 255) / 256), dim3(256), 0, stream_, hd.mem.as<uint32_t>(), v.ptr,
+                           v.stride, v.is_inf, (uint32_t)n, hd.has_endo ? 1 : 0, mont, d_err);
     });
     return st ? st : add_handle(std::move(hd), h);
   }
@@ -215,6 +220,28 @@ class ResidentSets : public IEngine {
         inf[i] = z ? 1 : 0;
       }
     }
+    return MSMZ_OK;
+  }
+
+  // the records of download_points as one coordinate + sign bit each (k_points_compress); the infinity flags come from
+  // the kernel, behind the records in the staging buffer
+  int download_points_compressed(uint64_t hd, uint64_t first, uint64_t count, uint8_t* out, uint8_t* inf,
+                                 uint32_t flags) override {
+    const Handle* pts = handles_.get(hd, 0);
+    if (!pts || !out || (flags & ~(uint32_t)MSMZ_SRC_SIGN_PARITY)) return MSMZ_ERR_ARG;
+    const uint64_t have = pts->factor ? pts->copy_stride * pts->factor : pts->n * (pts->has_endo ? 2 : 1);
+    if (!in_range(first, count, have)) return MSMZ_ERR_ARG;
+    if (count == 0) return MSMZ_OK;
+    MSMZ_HIP(hipSetDevice(device_));
+    if (int st = stage_.ensure(count * FE_BYTES + count)) return st;
+    const uint32_t* recs = pts->mem.template as<const uint32_t>() + first * PW_WORDS;
+    uint8_t* d_inf = stage_.as<uint8_t>() + count * FE_BYTES;
+    hipLaunchKernelGGL((k_points_compress<P>), dim3((count + 255) / 256), dim3(256), 0, stream_, stage_.as<uint32_t>(),
+                       d_inf, recs, (uint32_t)count, flags ? 1 : 0);
+    MSMZ_HIP(hipGetLastError());
+    MSMZ_HIP(hipMemcpyAsync(out, stage_.p, count * FE_BYTES, hipMemcpyDeviceToHost, stream_));
+    if (inf) MSMZ_HIP(hipMemcpyAsync(inf, d_inf, count, hipMemcpyDeviceToHost, stream_));
+    MSMZ_HIP(hipStreamSynchronize(stream_));
     return MSMZ_OK;
   }
 
@@ -592,7 +619,8 @@ class ResidentSets : public IEngine {
   }
 
  private:
-  // zeroes the error word, runs launch(its device address), fetches it: MSMZ_ERR_RANGE if a kernel raised a bit
+  // zeroes the error word, runs launch(its device address), fetches it: MSMZ_ERR_RANGE if a kernel raised a bit; bit 3
+  // alone (k_import_points_compressed: a record that is no point) is MSMZ_ERR_POINT, so RANGE wins when both occur
   template <class Launch>
   int checked(Launch launch) {
     uint32_t* d_err = &meta_.as<MsmMeta>()->error;
@@ -600,7 +628,7 @@ class ResidentSets : public IEngine {
     launch(d_err);
     uint32_t err = 0;
     if (int st = fetch_error(&err)) return st;
-    return err ? MSMZ_ERR_RANGE : MSMZ_OK;
+    return (err & ~8u) ? MSMZ_ERR_RANGE : err ? MSMZ_ERR_POINT : MSMZ_OK;
   }
 
   // The 64-byte result record of dot, recurrence and inverse at the head of `buf` (`bytes` with its scratch): zeroed in

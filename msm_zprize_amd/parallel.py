@@ -114,6 +114,25 @@ class _Affine:
         raw, flags = buf.raw, inf.raw
         return [self._c._point(raw, i, flags[i] != 0, zero_rule=False) for i in range(count)]
 
+    def toCompressedBytes(self, arr, first=0, count=None, sign="largest"):
+        """Points [first, first + count) of a resident point array as compressed records (msmz_download_points_compressed):
+        -> (count * fe_bytes bytes, count flag bytes).  A record is the wire coordinate (x; y on the twisted Edwards
+        curve), little-endian, with the sign of the other coordinate in bit 7 of the last byte; sign="largest": the bit
+        says the canonical value is above (p - 1) / 2, sign="parity": that it is odd.  A point at infinity is an
+        all-zero record with flag 1.  pointsFromBytes(..., compressed=True, sign=sign, is_inf=flags) reads them back."""
+        first, count = compressed_range_args(arr, first, count, "toCompressedBytes")
+        flag = sign_arg(sign, "toCompressedBytes")
+        fb = self._c.fe_bytes
+        buf = C.create_string_buffer(fb * count)
+        inf = C.create_string_buffer(count)
+        _check(lib().msmz_download_points_compressed(self._c._ctx, arr.handle, first, count, buf, inf, flag),
+               "msmz_download_points_compressed")
+        return buf.raw, inf.raw
+
+    def compressPoint(self, point, sign="largest"):
+        """An MSM result (or any {x, y, isZero}) as one compressed record, on the host: -> (fe_bytes bytes, isZero)."""
+        return compress_point(self._c.params, point, sign)
+
 
 class _Parallel:
     """Curve.Parallel (parallel.ts:135-145 / 250-258)."""
@@ -128,23 +147,29 @@ class _Parallel:
     def randomScalars(self, n, seed=0x6D736D7A):
         return _resident(self._c, "scalars", n, "msmz_random_scalars", n, seed)
 
-    def pointsFromBytes(self, data, n=None, is_inf=None, montgomery=False, check=None):
+    def pointsFromBytes(self, data, n=None, is_inf=None, montgomery=False, check=None, compressed=False, sign="largest"):
         """parallel.ts:97-112: x||y little-endian canonical, 2*fe_bytes per point.  montgomery=True: the coordinates are
         64-bit-limb Montgomery residues v * 2^(8 fe_bytes) mod p (msmz_import_points), converted on the GPU.
+        compressed=True: fe_bytes per point, one coordinate (x; y on the twisted Edwards curve) with the sign of the
+        other in bit 7 of the last byte -- sign="largest": set iff the canonical value is above (p - 1) / 2,
+        sign="parity": iff it is odd; the GPU recovers the other coordinate and the array is an ordinary point array.  A
+        record that is no point raises MsmzError (MSMZ_ERR_POINT).
         check="curve" / "subgroup": validate the new set on the GPU (checkPoints); a set that fails is freed and
         ValueError names its first bad point.  None (the default) validates nothing."""
         what = check_arg(check, "pointsFromBytes")
+        form = compressed_arg(compressed, sign, montgomery, "pointsFromBytes")
         if what:
-            return self._checked(self.pointsFromBytes(data, n, is_inf, montgomery), what, "pointsFromBytes")
+            return self._checked(self.pointsFromBytes(data, n, is_inf, montgomery, None, compressed, sign), what, "pointsFromBytes")
         fb = self._c.fe_bytes
-        n = len(data) // (2 * fb) if n is None else n
-        if n <= 0 or len(data) < 2 * fb * n:
-            raise ValueError(f"pointsFromBytes: {len(data)} bytes for {n} points of {2 * fb} bytes")
+        rec = fb if compressed else 2 * fb
+        n = len(data) // rec if n is None else n
+        if n <= 0 or len(data) < rec * n:
+            raise ValueError(f"pointsFromBytes: {len(data)} bytes for {n} points of {rec} bytes")
         if is_inf is not None and len(is_inf) < n:
             raise ValueError(f"pointsFromBytes: {len(is_inf)} infinity flags for {n} points")
         data, flags = bytes(data), None if is_inf is None else bytes(is_inf)
-        if montgomery:
-            src = MsmzSrc(C.cast(C.c_char_p(data), C.c_void_p), 0, 2 * fb, _native.MSMZ_SRC_MONTGOMERY, None,
+        if montgomery or compressed:
+            src = MsmzSrc(C.cast(C.c_char_p(data), C.c_void_p), 0, rec, form | (_native.MSMZ_SRC_MONTGOMERY if montgomery else 0), None,
                           None if flags is None else C.cast(C.c_char_p(flags), C.c_void_p))
             return _resident(self._c, "points", n, "msmz_import_points", C.byref(src), n)
         return _resident(self._c, "points", n, "msmz_upload_points", data, flags, n)
@@ -168,6 +193,7 @@ class _Parallel:
     # -- imports: the data where it is, in the form it has (msmz_import_*, include/msmz.h) ------------
     def _src(self, view):
         flags = (_native.MSMZ_SRC_DEVICE if view["device"] else 0) | (_native.MSMZ_SRC_MONTGOMERY if view["montgomery"] else 0)
+        flags |= view.get("form", 0)   # (compressed records and their sign convention)
         stream = None
         if view["device"]:
             if view["stream"]:
@@ -200,14 +226,18 @@ class _Parallel:
                "msmz_import_scalars_into")
         return dst
 
-    def pointsFromTensor(self, t, montgomery=False, is_inf=None, check=None):
+    def pointsFromTensor(self, t, montgomery=False, is_inf=None, check=None, compressed=False, sign="largest"):
         """A resident point array from a torch tensor of n rows of 2 * fe_bytes bytes (x || y, little-endian), read where
-        it lies (msmz_import_points); montgomery=True: coordinates v * 2^(8 fe_bytes) mod p.  is_inf: optional 1-D
-        contiguous 1-byte tensor of n flags on the same device.  check: as pointsFromBytes."""
+        it lies (msmz_import_points); montgomery=True: coordinates v * 2^(8 fe_bytes) mod p.  compressed=True: rows of
+        fe_bytes bytes, one coordinate and a sign bit, `sign` as in pointsFromBytes.  is_inf: optional 1-D contiguous
+        1-byte tensor of n flags on the same device.  check: as pointsFromBytes."""
         what = check_arg(check, "pointsFromTensor")
+        form = compressed_arg(compressed, sign, montgomery, "pointsFromTensor")
         if what:
-            return self._checked(self.pointsFromTensor(t, montgomery, is_inf), what, "pointsFromTensor")
-        view = tensor_view(t, self._c.devices, "points", self._c.fe_bytes, montgomery, "pointsFromTensor", is_inf)
+            return self._checked(self.pointsFromTensor(t, montgomery, is_inf, None, compressed, sign), what, "pointsFromTensor")
+        view = tensor_view(t, self._c.devices, "points", self._c.fe_bytes, montgomery, "pointsFromTensor", is_inf,
+                           compressed=compressed)
+        view["form"] = form
         return _resident(self._c, "points", view["n"], "msmz_import_points", C.byref(self._src(view)), view["n"])
 
     # -- validation (msmz_check_points, include/msmz.h) ---------------------------------------------
@@ -842,7 +872,58 @@ def is_device_list(scalarsList):
     return bool(vecs) and any(on_gpu) and all(g or isinstance(v, DeviceArray) for g, v in zip(on_gpu, vecs))
 
 
-def tensor_view(t, devices, kind, fe_bytes, montgomery, who, is_inf=None):
+def sign_arg(sign, who):
+    """the sign convention of compressed records -> 0 ("largest") or MSMZ_SRC_SIGN_PARITY ("parity")"""
+    if sign == "largest" and isinstance(sign, str):
+        return 0
+    if sign == "parity" and isinstance(sign, str):
+        return _native.MSMZ_SRC_SIGN_PARITY
+    raise ValueError(f"{who}: sign is 'largest' or 'parity', got {sign!r}")
+
+
+def compressed_arg(compressed, sign, montgomery, who):
+    """compressed= / sign= of pointsFromBytes and pointsFromTensor -> the msmz_src form flags (0: x || y records)"""
+    if not isinstance(compressed, bool):
+        raise TypeError(f"{who}: compressed is True or False, got {type(compressed).__name__}")
+    flag = sign_arg(sign, who)
+    if not compressed:
+        if flag:
+            raise ValueError(f"{who}: sign='parity' describes compressed records (compressed=True)")
+        return 0
+    if montgomery:
+        raise ValueError(f"{who}: compressed records are canonical, not Montgomery residues")
+    return _native.MSMZ_SRC_COMPRESSED | flag
+
+
+def compressed_range_args(arr, first, count, who):
+    """points [first, first + count) of a resident point array, count=None: to its end -> (first, count)"""
+    if not _is_array(arr, "points"):
+        raise TypeError(f"{who}: expected a resident point array")
+    if not _is_int(first) or first < 0 or first >= len(arr):
+        raise ValueError(f"{who}: first = {first!r} of an array of {len(arr)}")
+    count = len(arr) - first if count is None else count
+    if not _is_int(count) or count <= 0 or first + count > len(arr):
+        raise ValueError(f"{who}: points [{first}, +{count!r}) of an array of {len(arr)}")
+    return first, count
+
+
+def compress_point(params, point, sign="largest"):
+    """{x, y, isZero} -> (one compressed record of fe_bytes bytes, isZero), as msmz_download_points_compressed writes it:
+    the wire coordinate (x; y on the twisted Edwards curve) little-endian, the sign of the other in bit 7 of the last
+    byte; infinity is the all-zero record.  Pure Python, for MSM results."""
+    parity = sign_arg(sign, "compressPoint") != 0
+    p, fb = params["modulus"], params["fe_bytes"]
+    if point.get("isZero") and params["kind"] == "weierstrass":
+        return bytes(fb), True
+    x, y = point["x"], point["y"]
+    if not (_is_int(x) and _is_int(y) and 0 <= x < p and 0 <= y < p):
+        raise ValueError("compressPoint: coordinates are ints in [0, p)")
+    wire, other = (x, y) if params["kind"] == "weierstrass" else (y, x)
+    bit = (other & 1) if parity else int(other > (p - 1) // 2)
+    return (wire | (bit << (8 * fb - 1))).to_bytes(fb, "little"), False
+
+
+def tensor_view(t, devices, kind, fe_bytes, montgomery, who, is_inf=None, compressed=False):
     """The arguments of an import from a tensor, checked before anything reaches the device.  `t` needs the tensor
     attributes used here (dim, shape, stride, element_size, device, data_ptr), so a fake will do; torch is imported only
     to ask a GPU tensor's current stream.  -> dict(ptr, n, width, stride (bytes), device, stream, montgomery[, is_inf])."""
@@ -865,8 +946,8 @@ def tensor_view(t, devices, kind, fe_bytes, montgomery, who, is_inf=None):
         raise ValueError(f"{who}: an empty tensor")
     if kind == "scalars":
         scalar_width_arg(width, montgomery, who)
-    elif width != 2 * fe_bytes:
-        raise ValueError(f"{who}: rows of {width} bytes, a point is {2 * fe_bytes}")
+    elif width != (fe_bytes if compressed else 2 * fe_bytes):
+        raise ValueError(f"{who}: rows of {width} bytes, a point is {fe_bytes if compressed else 2 * fe_bytes}")
     stride = int(t.stride(0)) * item if n > 1 else width
     if stride < width or stride % 4 or stride >= 1 << 24:
         raise ValueError(f"{who}: rows {stride} bytes apart (a multiple of 4, at least the width {width}, below 2^24)")

@@ -209,6 +209,25 @@ static napi_value ImportPoints(napi_env env, napi_callback_info info) {
   return make_handle(env, h);
 }
 
+/* importPointsCompressed(ctx, buffer, infBufferOrNull, n, parity) -> handle: n records of fe_bytes, one coordinate with
+ * the sign of the other in bit 7 of the last byte (msmz_import_points with MSMZ_SRC_COMPRESSED); parity: the sign bit
+ * means "odd", not "the larger root" */
+static napi_value ImportPointsCompressed(napi_env env, napi_callback_info info) {
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  if (!get_args(env, info, 5, argv, &ctx)) return BAD_ARG(env, "importPointsCompressed");
+  void *rec, *inf; size_t reclen, inflen; uint64_t n, h = 0; bool parity = false;
+  const int fe = msmz_ctx_fe_bytes(ctx);
+  if (!opt_buffer(env, argv[1], &rec, &reclen)) return BAD_ARG(env, "importPointsCompressed");
+  opt_buffer(env, argv[2], &inf, &inflen);
+  if (!get_u64(env, argv[3], &n) || napi_get_value_bool(env, argv[4], &parity) != napi_ok || fe <= 0 || n == 0 ||
+      reclen / (size_t)fe < n || (inf != NULL && inflen < n))
+    return BAD_ARG(env, "importPointsCompressed");
+  msmz_src src = {rec, 0, (uint32_t)fe, MSMZ_SRC_COMPRESSED | (parity ? MSMZ_SRC_SIGN_PARITY : 0u), NULL, (const uint8_t*)inf};
+  int st = msmz_import_points(ctx, &src, n, &h);
+  if (st) return throw_status(env, st, "msmz_import_points");
+  return make_handle(env, h);
+}
+
 /* randomPoints(ctx, n, seed) / randomScalars(ctx, n, seed) -> handle */
 static napi_value random_common(napi_env env, napi_callback_info info, int scalars) {
   napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
@@ -234,6 +253,24 @@ static napi_value DownloadPoints(napi_env env, napi_callback_info info) {
   int st = msmz_download_points(ctx, h, first, count, (uint8_t*)data, NULL);
   if (st) return throw_status(env, st, "msmz_download_points");
   return buf;
+}
+/* downloadPointsCompressed(ctx, handle, first, count, feBytes, parity) -> {records: Buffer(count * feBytes), isInf: Buffer(count)} */
+static napi_value DownloadPointsCompressed(napi_env env, napi_callback_info info) {
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  uint64_t h, first, count; bool parity = false;
+  if (!get_args(env, info, 6, argv, &ctx) || !get_u64(env, argv[1], &h) || !get_u64(env, argv[2], &first) ||
+      !get_u64(env, argv[3], &count) || !is_fe_bytes(env, argv[4], msmz_ctx_fe_bytes(ctx)) ||
+      napi_get_value_bool(env, argv[5], &parity) != napi_ok)
+    return BAD_ARG(env, "downloadPointsCompressed");
+  void *data, *flags; napi_value rec, inf, out;
+  NAPI_CALL(env, napi_create_buffer(env, (size_t)msmz_ctx_fe_bytes(ctx) * (size_t)count, &data, &rec));
+  NAPI_CALL(env, napi_create_buffer(env, (size_t)count, &flags, &inf));
+  int st = msmz_download_points_compressed(ctx, h, first, count, (uint8_t*)data, (uint8_t*)flags, parity ? MSMZ_SRC_SIGN_PARITY : 0u);
+  if (st) return throw_status(env, st, "msmz_download_points_compressed");
+  NAPI_CALL(env, napi_create_object(env, &out));
+  NAPI_CALL(env, napi_set_named_property(env, out, "records", rec));
+  NAPI_CALL(env, napi_set_named_property(env, out, "isInf", inf));
+  return out;
 }
 static napi_value DownloadScalars(napi_env env, napi_callback_info info) {
   napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
@@ -633,6 +670,7 @@ static napi_value Init(napi_env env, napi_value exports) {
   static const struct { const char* name; napi_callback fn; } fns[] = {
       {"create", Create}, {"destroy", Destroy}, {"uploadPoints", UploadPoints}, {"uploadScalars", UploadScalars},
       {"importScalars", ImportScalars}, {"importPoints", ImportPoints},
+      {"importPointsCompressed", ImportPointsCompressed}, {"downloadPointsCompressed", DownloadPointsCompressed},
       {"randomPoints", RandomPoints}, {"randomScalars", RandomScalars}, {"downloadPoints", DownloadPoints},
       {"downloadScalars", DownloadScalars}, {"free", Free}, {"msm", Msm}, {"msmBatch", MsmBatch}, {"msmSegments", MsmSegments},
       {"precomputePoints", PrecomputePoints}, {"precomputedInfo", PrecomputedInfo}, {"checkPoints", CheckPoints},

@@ -108,7 +108,118 @@ def iarr(name, vals):
     return "  static constexpr int32_t %s[%d] = {%s};" % (name, len(vals), body)
 
 
-def field_struct(name, p, nwords, N, W, extra=()):
+def iarr2(name, rows):
+    body = ",\n".join("    {%s}" % ", ".join(str(v) for v in r) for r in rows)
+    return "  static constexpr int32_t %s[%d][%d] = {\n%s};" % (name, len(rows), len(rows[0]), body)
+
+
+SQRT_WINDOW = 4   # bits per digit of the discrete logarithm (sqrt.h); fields with a smaller 2-adicity use that
+
+
+def sliding_schedule(e, w=3):
+    """e > 0 as a left-to-right sliding-window schedule over the odd powers 1, 3, .. 2^w - 1: entries (squarings, index)
+    = "square that many times, then multiply by x^(2 index + 1)"; index 2^(w-1) = no product (trailing zero bits).  The
+    first entry starts the accumulator at its power."""
+    bits = bin(e)[2:]
+    out, pend, i = [], 0, 0
+    while i < len(bits):
+        if bits[i] == "0":
+            pend, i = pend + 1, i + 1
+            continue
+        j = min(i + w, len(bits))
+        while bits[j - 1] == "0":
+            j -= 1
+        out.append((pend + (j - i), (int(bits[i:j], 2) - 1) // 2))
+        pend, i = 0, j
+    if pend:
+        out.append((pend, 1 << (w - 1)))
+    return out
+
+
+def run_schedule(sched, x, p, w=3):
+    acc = None
+    for sq, idx in sched:
+        if acc is None:
+            acc = pow(x, 2 * idx + 1, p)
+            continue
+        acc = pow(acc, 1 << sq, p)
+        if idx < (1 << (w - 1)):
+            acc = acc * pow(x, 2 * idx + 1, p) % p
+    return acc
+
+
+def sqrt_constants(p):
+    """The tables of fe_sqrt (sqrt.h): Tonelli-Shanks with the discrete logarithm in the 2^S-th roots of unity taken by
+    C-bit digits.  p - 1 = 2^S t, w = g^t for a non-residue g, NWIN = ceil(S / C) digits.  The logarithm e is handled as
+    E = e << DELTA, DELTA = C NWIN - S, so that every digit of E is C bits wide and the short one is at the bottom (its
+    low DELTA bits are zero).  INV[k][d] = w^-((d << C (NWIN-1-k)) >> DELTA); KEY[d] identifies zeta^d, zeta = w^(2^(S-C))
+    the primitive 2^C-th root, by the low word of its canonical Montgomery residue."""
+    S = ((p - 1) & -(p - 1)).bit_length() - 1
+    t = (p - 1) >> S
+    C = min(SQRT_WINDOW, S)
+    NWIN = -(-S // C)
+    DELTA = C * NWIN - S
+    g = 2
+    while pow(g, (p - 1) // 2, p) != p - 1:
+        g += 1
+    assert pow(g, (p - 1) // 2, p) == p - 1, "the non-residue used is one"
+    w = pow(g, t, p)
+    assert pow(w, 1 << (S - 1), p) == p - 1, "w has order exactly 2^S"
+    winv = pow(w, -1, p)
+    inv = [[pow(winv, (d << (C * (NWIN - 1 - k))) >> DELTA, p) for d in range(1 << C)] for k in range(NWIN)]
+    for k in range(NWIN):
+        for d in range(1 << C):
+            assert inv[k][d] * pow(w, (d << (C * (NWIN - 1 - k))) >> DELTA, p) % p == 1, "every entry is what its index says"
+    zeta = pow(w, 1 << (S - C), p)
+    roots = [pow(zeta, d, p) for d in range(1 << C)]
+    assert roots[1 << (C - 1)] == p - 1 and len(set(roots)) == 1 << C
+    assert all(inv[0][d] * roots[d] % p == 1 for d in range(1 << C))
+    e = (t - 1) // 2
+    sched = sliding_schedule(e)
+    assert all(sq < 256 for sq, _ in sched) and sched[0][1] < 4
+    return dict(S=S, t=t, C=C, NWIN=NWIN, DELTA=DELTA, g=g, w=w, inv=inv, roots=roots, e=e, sched=sched)
+
+
+def sqrt_model(a, p, k):
+    """Integer model of fe_sqrt, step for step (self-check of the tables and of the window arithmetic)."""
+    C, NWIN, DELTA = k["C"], k["NWIN"], k["DELTA"]
+    u = run_schedule(k["sched"], a, p) if a % p else 0
+    r = u * a % p
+    v = u * r % p
+    if a % p == 0:
+        return 0
+    E = 0
+    for lo, hi in ((0, NWIN // 2), (NWIN // 2, NWIN)):
+        xs = {}
+        y = pow(v, 1 << (C * (NWIN - hi)), p) if hi > lo else v
+        for i in range(hi - 1, lo - 1, -1):
+            xs[i] = y
+            y = pow(y, 1 << C, p)
+        for i in range(lo, hi):
+            y = xs[i]
+            for j in range(i):
+                y = y * k["inv"][i - j][(E >> (C * j)) & ((1 << C) - 1)] % p
+            E |= k["roots"].index(y) << (C * i)
+    if (E >> DELTA) & 1:
+        return None
+    H = E >> 1
+    for j in range(NWIN):
+        r = r * k["inv"][NWIN - 1 - j][(H >> (C * j)) & ((1 << C) - 1)] % p
+    return r
+
+
+def sqrt_products(k):
+    """field products of one fe_sqrt, squarings counted as products, from the loop bounds of sqrt.h"""
+    C, NWIN = k["C"], k["NWIN"]
+    power = 4 + sum(sq for sq, _ in k["sched"][1:]) + sum(1 for _, i in k["sched"][1:] if i < 4)
+    chain = 0
+    for lo, hi in ((0, NWIN // 2), (NWIN // 2, NWIN)):
+        if hi > lo:
+            chain += C * (NWIN - hi) + C * (hi - 1 - lo)
+    return power + 2 + chain + NWIN * (NWIN - 1) // 2 + NWIN
+
+
+def field_struct(name, p, nwords, N, W, extra=(), rng=None):
     """Base-field constants.  Arithmetic radix is 2^W with N signed lazy limbs (R = 2^(N*W));
     the memory format is `nwords` saturated 32-bit words (= nwords/2 64-bit limbs, little endian)."""
     R = 1 << (N * W)
@@ -135,6 +246,27 @@ def field_struct(name, p, nwords, N, W, extra=()):
            iarr("R2STD", limbs_w(R * R * pow(1 << (32 * nwords), -1, p) % p, N, W))]
     for nm, val in extra:
         out.append(iarr(nm, limbs_w(val * R % p, N, W)))
+    # square roots (sqrt.h) and the sign of a compressed coordinate
+    k = sqrt_constants(p)
+    for a in [0, 1, 4, p - 1, k["g"]] + [rng.randrange(p) for _ in range(200)] + \
+            [pow(k["w"], (1 << (k["S"] - j)) % (1 << k["S"]), p) * pow(rng.randrange(1, p), 1 << (k["S"] + 1), p) % p for j in range(k["S"] + 1)]:
+        r = sqrt_model(a, p, k)
+        assert (r is None) == (a % p != 0 and pow(a, (p - 1) // 2, p) == p - 1), hex(a)
+        assert r is None or r * r % p == a % p, hex(a)
+    keys = [(v * R % p) & 0xFFFFFFFF for v in k["roots"]]
+    assert len(set(keys)) == len(keys) and 0 not in keys, "the low word tells the 2^C-th roots apart (and from zero)"
+    out += ["  static constexpr int SQRT_S = %d;      // p - 1 = 2^SQRT_S * t, t odd" % k["S"],
+            "  static constexpr int SQRT_C = %d;      // bits per digit of the discrete logarithm" % k["C"],
+            "  static constexpr int SQRT_N = %d;      // digits: ceil(SQRT_S / SQRT_C)" % k["NWIN"],
+            "  static constexpr int SQRT_DELTA = %d;  // SQRT_C * SQRT_N - SQRT_S: the logarithm is kept shifted left by this" % k["DELTA"],
+            "  static constexpr int SQRT_PRODUCTS = %d;  // field products of one fe_sqrt (squarings included), from its loop bounds" % sqrt_products(k),
+            "  static constexpr int SQRT_SCHED_LEN = %d;  // sliding-window schedule of a^((t - 1) / 2): (squarings, odd-power index; 4 = none)" % len(k["sched"]),
+            "  static constexpr uint8_t SQRT_SCHED[%d] = {%s};" % (2 * len(k["sched"]), ", ".join("%d, %d" % e for e in k["sched"])),
+            "  // SQRT_INV[k * 2^C + d] = w^-((d << C (N-1-k)) >> DELTA), w = %d^t of order 2^S; Montgomery limbs" % k["g"],
+            iarr2("SQRT_INV", [limbs_w(v * R % p, N, W) for row in k["inv"] for v in row]),
+            "  // low word of the canonical Montgomery residue of zeta^d, zeta = w^(2^(S-C)): distinct, non-zero (asserted)",
+            arr("SQRT_KEY", keys),
+            arr("PHALF1", limbs((p + 1) // 2, nwords)) + "  // (p + 1) / 2: a canonical value >= this is the 'larger' root"]
     out.append("};")
     return "\n".join(out)
 
@@ -159,9 +291,12 @@ def main():
             extra += [("B", c["b"]), ("B3", 3 * c["b"] % p), ("BETA", c["endomorphism"]["beta"])]
         else:
             extra += [("D", c["d"]), ("K2D", 2 * c["d"] % p)]
+            # decompression divides by d y^2 + 1 (TeGroup::decompress): never zero, as -1/d is a non-residue
+            assert pow(c["d"], (p - 1) // 2, p) == p - 1, "d must be a quadratic non-residue"
+            assert pow(p - 1, (p - 1) // 2, p) == 1, "-1 must be a quadratic residue"
         L.append("// %s base field: p = 0x%x" % (c["label"], p))
         N, W = {12: (14, 28), 8: (9, 29)}[n]
-        L.append(field_struct(tag + "Fp", p, n, N, W, extra))
+        L.append(field_struct(tag + "Fp", p, n, N, W, extra, rng))
         L.append("")
         # scalar field
         L.append("struct %sFr {" % tag)
