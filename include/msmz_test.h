@@ -59,7 +59,9 @@ int msmz_test_field_limbs(msmz_ctx* ctx, int op, const int32_t* a, const int32_t
 
 /* GLV half-scalar bound (src/wasm/glv.ts:216-226 `maxBits`).  The engine sizes the windows for halves below 2^127 and
  * lets the slicing kernel flag a longer half, in which case the MSM is redone with windows for the analytic bound
- * (GLV_PROVEN_BITS, tools/gen_constants.py).  No real scalar is known to take that path, so this hook shrinks the
+ * (GLV_PROVEN_BITS, tools/gen_constants.py).  No scalar below the group order can take that path: the exact supremum
+ * of the halves is below 2^127 on all three curves (oracle/glv_edges.py supremum, pinned by
+ * tests/test_glv_edges_cpu.py::test_supremum_facts).  The path stays as a guard, so this hook shrinks the
  * ASSUMED bit length (8 .. 127; 0 restores the default): ordinary halves then overflow, the flag is raised and the
  * redone MSM must still equal the oracle.  msmz_test_retries = number of MSMs (per-engine passes) redone so far. */
 int msmz_test_set_glv_bits(msmz_ctx* ctx, int bits);

@@ -383,7 +383,8 @@ def test_batched_affine_bucket_reduction(curves, label):
 def test_glv_half_longer_than_assumed_is_redone(label):
     """The engine sizes the GLV windows for halves below 2^127 and redoes the MSM with the analytic bound
     (src/wasm/glv.ts:216-226 `maxBits`; tools/gen_constants.py glv_proven_bits) when the slicing kernel flags a
-    longer half.  No real scalar is known to take that path, so the test hook shrinks the ASSUMED length: ordinary
+    longer half.  No scalar below the group order can take that path (the supremum of the halves is below 2^127:
+    tests/test_glv_edges_cpu.py::test_supremum_facts), so the test hook shrinks the ASSUMED length: ordinary
     halves overflow, the flag is raised, and the redone MSM must still equal the oracle."""
     import msm_zprize_amd as m
     from msm_zprize_amd._native import lib

@@ -250,7 +250,7 @@ def build_scalars(cs, g, q, rng):
 
 def halves_of(curve, cs, words_p):
     """the (half-)scalars of one problem: the scalar itself, or the device's GLV halves (any valid split is acceptable;
-    tests/test_stages_gpu.py checks the split)"""
+    tests/test_glv_edges_gpu.py checks the split, and this sort, against the integer model of the split)"""
     n = cs["n"]
     if not cs["glv"]:
         return [(words_p, np.zeros(n, dtype=np.uint8))]
