@@ -56,6 +56,16 @@ enum {
 };
 int msmz_test_field_limbs(msmz_ctx* ctx, int op, const int32_t* a, const int32_t* b, uint64_t n, int32_t* out_raw,
                           uint8_t* out_canon);
+/* The row form of the field routines (msm_zprize_amd/csrc/fp_rows.h): an element is spread over the 16 lanes of a DPP
+ * row, limb j in lane j, and the four rows of a wave run four elements at once.  Operands and outputs are raw limbs as
+ * for msmz_test_field_limbs.  MUL: out_raw = the limbs of fe_mul_row(a, b), out_canon its canonical value (through
+ * fe_store_row).  ROUNDTRIP: the first NW int32 of a[i] are memory words; out_raw = the words after fe_load_row ->
+ * fe_store_row (the rest zero), out_canon their canonical value.  IS_ZERO: out_raw[0] = fe_is_zero_row(a), out_canon 0.
+ * live_rows (1 .. 15): a wave takes one element in each row whose bit is set and runs the other rows on zero operands;
+ * 15 = four elements per wave. */
+enum { MSMZ_TFR_MUL = 0, MSMZ_TFR_ROUNDTRIP = 1, MSMZ_TFR_IS_ZERO = 2 };
+int msmz_test_field_rows(msmz_ctx* ctx, int op, const int32_t* a, const int32_t* b, uint64_t n, uint32_t live_rows,
+                         int32_t* out_raw, uint8_t* out_canon);
 
 /* GLV half-scalar bound (src/wasm/glv.ts:216-226 `maxBits`).  The engine sizes the windows for halves below 2^127 and
  * lets the slicing kernel flag a longer half, in which case the MSM is redone with windows for the analytic bound
@@ -184,7 +194,9 @@ int msmz_test_point(msmz_ctx* ctx, int op, const uint8_t* a_xy, const uint8_t* a
  * on odd ones, in registers.  out: canonical affine (x || y), all-zero = infinity (Weierstrass). */
 enum {
   MSMZ_TPR_ADD = 0, MSMZ_TPR_ADD_X4 = 1, MSMZ_TPR_MADD = 2, MSMZ_TPR_DBL = 3, MSMZ_TPR_DBL_X4 = 4,
-  MSMZ_TPR_MDBL = 5 /* Weierstrass only */, MSMZ_TPR_CHAIN = 6, MSMZ_TPR_CHAIN_X4 = 7
+  MSMZ_TPR_MDBL = 5 /* Weierstrass only */, MSMZ_TPR_CHAIN = 6, MSMZ_TPR_CHAIN_X4 = 7,
+  /* the row form (kernels.h, "row-form point addition"): one wave per addition, a field element per DPP row */
+  MSMZ_TPR_ADD_ROWS = 8, MSMZ_TPR_DBL_ROWS = 9, MSMZ_TPR_CHAIN_ROWS = 10
 };
 int msmz_test_point_raw(msmz_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, const uint8_t* neg, uint64_t n,
                         int L, uint8_t* out_xy);
@@ -207,7 +219,8 @@ int msmz_test_batch_add(msmz_ctx* ctx, int safe, int B, const uint8_t* points_xy
                         const uint32_t* desc, uint64_t n_pairs, uint64_t out_base, uint8_t* out_xy, uint32_t* error);
 
 /* The bucket reduction alone, on caller-built buckets: the line sums and the weighted sums of the two-dimensional
- * reduction (csrc/reduce2d_kernels.h) and the upper levels (k_reduce_quad / k_reduce_quad16 / k_reduce_tail), through
+ * reduction (csrc/reduce2d_kernels.h) and the upper levels (k_reduce_quad / k_reduce_quad16 / k_reduce_rows /
+ * k_reduce_tail), through
  * the engine's own reduction stage (BucketReduce, csrc/reduce.h) and the template instances an MSM launches.  Run it before and after
  * touching a reduction kernel: it names the problem and the line an MSM's single result point cannot.
  *
@@ -231,7 +244,9 @@ int msmz_test_batch_add(msmz_ctx* ctx, int safe, int B, const uint8_t* points_xy
  * Level selection, each 0 = the engine's value, for this call only: nc = chunks per line (a power of two <= D);
  *   tail_n = entries per problem at which k_reduce_tail takes over (1 .. 4096); quad16_max = levels with at most this
  *   many groups run k_reduce_quad16, larger ones k_reduce_quad; pairsum_x4_max = pair-sum launches of at most this many
- *   additions run k_pairsum_x4, larger ones k_pairsum (both 1 .. 2^20).
+ *   additions run k_pairsum_x4, larger ones k_pairsum (both 1 .. 2^20); rows_max = levels of at most this many groups
+ *   (1 .. 2^20, and within quad16_max) run the row form k_reduce_rows, also below tail_n, so that k_reduce_tail starts
+ *   at the first level that is too large for it or at one entry; 1 keeps the row form to levels of a single group.
  * out_xy: the results as canonical affine (x || y; Weierstrass: all-zero = infinity), 2 * nsets for the 2-D modes,
  *   nsets for LEVELS.  lines_xy (nullable, 2-D modes): the 2 * nsets * H line sums after the pair-sum launches, problem
  *   by problem.
@@ -254,6 +269,7 @@ typedef struct msmz_test_reduce_args {
   const uint32_t* cscan;
   uint8_t* out_xy;
   uint8_t* lines_xy;
+  uint32_t rows_max;   /* appended: callers that leave it 0 get the engine's value */
 } msmz_test_reduce_args;
 int msmz_test_reduce(msmz_ctx* ctx, const msmz_test_reduce_args* args);
 

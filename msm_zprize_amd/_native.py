@@ -86,7 +86,7 @@ class MsmzTestReduceArgs(C.Structure):   # msmz_test_reduce_args (include/msmz_t
                 ("points_xy", C.c_char_p), ("points_inf", C.c_char_p), ("n_points", C.c_uint64),
                 ("slots_xy", C.c_char_p), ("slots_inf", C.c_char_p), ("n_slots", C.c_uint64),
                 ("scale", C.c_char_p), ("loc", C.c_void_p), ("cscan", C.c_void_p),
-                ("out_xy", C.c_void_p), ("lines_xy", C.c_void_p)]
+                ("out_xy", C.c_void_p), ("lines_xy", C.c_void_p), ("rows_max", C.c_uint32)]
 
 
 class MsmzTestPlanArgs(C.Structure):   # msmz_test_plan_args (include/msmz_test.h)
@@ -177,6 +177,8 @@ EXPORTS = {
     "msmz_test_field": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_uint64, C.c_char_p]),
     "msmz_test_field_limbs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                         C.c_char_p]),
+    "msmz_test_field_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
+                                       C.c_char_p]),
     "msmz_test_glv": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_char_p, C.c_char_p, C.c_char_p]),
     "msmz_test_digits": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "msmz_test_sort": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,

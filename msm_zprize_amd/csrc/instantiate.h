@@ -59,6 +59,8 @@
                                                   uint32_t, uint32_t, uint32_t);                                 \
   PFX template __global__ void k_reduce_tail<P>(uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t, \
                                                 uint32_t);                                                       \
+  PFX template __global__ void k_reduce_rows<P>(uint32_t*, uint32_t*, const uint32_t*, const uint32_t*, uint32_t, \
+                                                uint32_t, uint32_t);                                             \
   PFX template __global__ void k_pairsum<P>(uint32_t*, const uint32_t*, uint32_t);                               \
   PFX template __global__ void k_fill_neutral<P>(uint32_t*, uint32_t);                                           \
   PFX template __global__ void k_bucket_sums<P>(uint32_t*, const uint32_t*, const uint32_t*, uint32_t);          \
@@ -80,6 +82,8 @@
   PFX template __global__ void k_test_field<F>(uint32_t*, const uint32_t*, const uint32_t*, uint32_t, int, uint32_t*); \
   PFX template __global__ void k_test_field_limbs<F>(int32_t*, uint32_t*, const int32_t*, const int32_t*, uint32_t,  \
                                                       int, uint32_t*);                                            \
+  PFX template __global__ void k_test_field_rows<F>(int32_t*, uint32_t*, const int32_t*, const int32_t*, uint32_t,   \
+                                                     int, uint32_t);                                              \
   PFX template __global__ void k_test_glv<Fr>(uint32_t*, uint32_t*, uint8_t*, const uint32_t*, uint32_t);         \
   PFX template __global__ void k_test_digits<Fr, false>(uint32_t*, const uint32_t*, uint32_t, int, int);          \
   PFX template __global__ void k_test_point<P>(uint32_t*, const uint32_t*, const uint32_t*, const uint8_t*,   \

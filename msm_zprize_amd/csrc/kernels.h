@@ -23,6 +23,8 @@
 //                        of lanes per group / per addition; the last levels in one launch; host side of all of the
 //                        reduction: BucketReduce, reduce.h
 //                        (msm-batched-affine.ts:544-571 reduceBucketsColumnProjective)
+//   k_reduce_rows        the same levels with one WAVE per addition and a field element per DPP row (fp_rows.h): the
+//                        smallest levels, whose waves stand alone on their SIMDs
 //   k_reduce_affine_*    (reduce_affine.h) optional batched-affine first level (reduceBucketsAffine,
 //                        msm-batched-affine-single-thread.ts:522-667)
 //   k_bucket_accumulate  msmBasic path: buckets in XYZZ / extended coordinates (msm-basic.ts:106-128)
@@ -37,6 +39,7 @@
 #include "constants_gen.h"
 #include "plan.h"
 #include "curve.h"
+#include "fp_rows.h"
 #include "scalar.h"
 
 namespace msmz {
@@ -538,22 +541,7 @@ __device__ __forceinline__ void load_operand_x(Fe<F>& x, uint32_t loc, const uin
 // becomes two multiply-adds per lane, and the carry chain a 13-step ripple of `row_shr:1` DPP moves shared by all
 // four rows.  Same algorithm and invariants as fe_inverse; ~4x shorter latency than running it limb by limb on
 // the scalar unit (it is on the critical path of every batch: forward pass -> product tree -> inversion -> back).
-template <int W, int N>
-__device__ __forceinline__ int32_t limb_row_ripple(int32_t val, int j) {
-  constexpr int32_t MASK = (1 << W) - 1;
-  const bool low = j < N - 1;          // limbs below the (signed) top limb are reduced to [0, 2^W)
-  // a carry moves up one limb per pass; after the second pass a further carry needs a limb within 4 of 2^W,
-  // so the loop almost always ends after two or three passes (and always within N - 1)
-#pragma unroll 1
-  for (int pass = 0; pass < N - 1; pass++) {
-    const int32_t c = low ? (val >> W) : 0;
-    val = low ? (val & MASK) : val;
-    val += __builtin_amdgcn_update_dpp(0, c, 0x111, 0xf, 0xf, true);   // row_shr:1: lane j takes lane j-1's carry
-    if (__ballot(low && (uint32_t)val > (uint32_t)MASK) == 0) break;
-  }
-  return val;
-}
-
+// The carry ripple, limb_row_ripple, is the one of the row-form field arithmetic (fp_rows.h).
 template <class F>
 __device__ __forceinline__ bool fe_inverse_wave(Fe<F>& r, const Fe<F>& x) {
   constexpr int N = F::N, W = F::W;
@@ -823,6 +811,124 @@ __device__ __forceinline__ void te_add_x4(TeExt<F>& r, const TeExt<F>& p, const 
   fe_quad_bcast<3>(r.Z, m);
 }
 
+// ------------------------------------------------------------------------------------------------ row-form point addition
+// The 4-lane addition with every field element spread over a DPP row (fp_rows.h): ONE addition per wave.  All four
+// rows hold the same operands, one register per coordinate; row s computes product slot s of a dependency level --
+// the slots of xyzz_add_x4 / te_add_x4 above -- and the products travel between the rows with fe_from_row.  A product
+// is ~2 N dependent multiply-adds deep instead of ~2 N^2, at ~5 times the wave-instructions: for levels of so few
+// additions that their waves are alone on their SIMDs, never for a level that keeps the VALUs busy.
+template <class F>
+struct AccRow {
+  int32_t c[4];   // XYZZ: X, Y, ZZ, ZZZ; extended twisted Edwards: X, Y, Z, T -- the order of the accumulator records
+};
+
+__device__ __forceinline__ int32_t row_sel4(int s, int32_t a0, int32_t a1, int32_t a2, int32_t a3) {
+  const int32_t lo = (s & 1) ? a1 : a0, hi = (s & 1) ? a3 : a2;
+  return (s & 2) ? hi : lo;
+}
+
+template <class F>
+__device__ __forceinline__ void acc_load_row(AccRow<F>& a, const uint32_t* rec, const RowLane<F>& k) {
+#pragma unroll
+  for (int i = 0; i < 4; i++) a.c[i] = fe_load_row<F>(rec + i * F::NW, k);
+}
+
+// every row holds the accumulator; row 0 writes it
+template <class F>
+__device__ __forceinline__ void acc_store_row(uint32_t* rec, const AccRow<F>& a, const RowLane<F>& k) {
+  const bool write = (__lane_id() & 48u) == 0;
+#pragma unroll
+  for (int i = 0; i < 4; i++) fe_store_row<F>(rec + i * F::NW, a.c[i], k, write);
+}
+
+// the product levels of xyzz_add_x4 (addition, or doubling of p), no edge cases
+template <class F>
+__device__ __forceinline__ void xyzz_core_rows(AccRow<F>& r, const AccRow<F>& p, const AccRow<F>& q, bool dbl,
+                                               int32_t& P, int32_t& R, const RowLane<F>& k) {
+  const int s = (int)(__lane_id() >> 4);
+  const int32_t pX = p.c[0], pY = p.c[1], pZZ = p.c[2], pZZZ = p.c[3];
+  const int32_t qX = q.c[0], qY = q.c[1], qZZ = q.c[2], qZZZ = q.c[3];
+  // level 1
+  int32_t m = fe_mul_row<F>(row_sel4(s, pX, qX, pY, qY), row_sel4(s, qZZ, pZZ, qZZZ, pZZZ), k);
+  const int32_t U1 = fe_from_row(m, 0), U2 = fe_from_row(m, 1), S1 = fe_from_row(m, 2), S2 = fe_from_row(m, 3);
+  P = U2 - U1;
+  R = S2 - S1;
+  const int32_t U = fe_carry_row<F>(pY + pY, k);
+  // level 2
+  int32_t a = row_sel4(s, P, R, pZZ, pZZZ), b = row_sel4(s, P, R, qZZ, qZZZ);
+  int32_t t = (s & 1) ? pX : U;
+  m = fe_mul_row<F>(dbl ? t : a, dbl ? t : b, k);
+  const int32_t PP = fe_from_row(m, 0);          // doubling: V
+  int32_t RR = fe_from_row(m, 1);                // doubling: XX
+  const int32_t Zm = fe_from_row(m, 2), Zc = fe_from_row(m, 3);
+  const int32_t M = fe_carry_row<F>(RR + RR + RR, k);
+  // level 3
+  a = row_sel4(s, P, U1, Zm, Zm);
+  t = row_sel4(s, U, pX, M, pZZ);
+  m = fe_mul_row<F>(dbl ? t : a, (dbl && s == 2) ? M : PP, k);
+  const int32_t PPP = fe_from_row(m, 0);         // doubling: W
+  const int32_t Q = fe_from_row(m, 1);           // doubling: S
+  t = fe_from_row(m, 2);                         // addition: ZZ3; doubling: M^2
+  int32_t u = fe_from_row(m, 3);                 // doubling: ZZ3
+  r.c[2] = dbl ? u : t;
+  RR = dbl ? t : RR;
+  u = fe_carry_row<F>(RR - (dbl ? 0 : PPP) - Q - Q, k);   // X3
+  t = fe_carry_row<F>(Q - u, k);
+  // level 4
+  a = row_sel4(s, R, S1, Zc, Zc);
+  m = row_sel4(s, M, pY, pZZZ, pZZZ);
+  m = fe_mul_row<F>(dbl ? m : a, s == 0 ? t : PPP, k);
+  r.c[3] = fe_from_row(m, 2);
+  r.c[1] = fe_carry_row<F>(fe_from_row(m, 0) - fe_from_row(m, 1), k);
+  r.c[0] = u;
+}
+
+// r = p + q, or (dbl, q == p) r = 2p; the edge cases exactly as xyzz_add_x4.  One addition per wave, so every branch
+// below is uniform over the wave and the row routines keep their 64 lanes.
+template <class F>
+__device__ __forceinline__ void xyzz_add_rows(AccRow<F>& r, const AccRow<F>& p, const AccRow<F>& q, bool dbl,
+                                              const RowLane<F>& k) {
+  const bool pinf = fe_is_zero_row<F>(p.c[2], k), qinf = fe_is_zero_row<F>(q.c[2], k);
+  int32_t P, R;
+  xyzz_core_rows<F>(r, p, q, dbl, P, R, k);
+  if (pinf) {
+    r = q;
+  } else if (qinf) {
+    r = p;
+  } else if (!dbl && fe_is_zero_row<F>(P, k)) {
+    if (fe_is_zero_row<F>(R, k)) {
+      xyzz_core_rows<F>(r, p, p, true, P, R, k);
+    } else {
+      r.c[0] = k.one;
+      r.c[1] = k.one;
+      r.c[2] = 0;
+      r.c[3] = 0;
+    }
+  }
+}
+
+template <class F>
+__device__ __forceinline__ void te_add_rows(AccRow<F>& r, const AccRow<F>& p, const AccRow<F>& q, bool,
+                                            const RowLane<F>& k) {   // the unified addition doubles as well
+  const int s = (int)(__lane_id() >> 4);
+  const int32_t pX = p.c[0], pY = p.c[1], pZ = p.c[2], pT = p.c[3];
+  const int32_t qX = q.c[0], qY = q.c[1], qZ = q.c[2], qT = q.c[3];
+  const int32_t t = fe_carry_row<F>(pY - pX, k), u = fe_carry_row<F>(qY - qX, k);
+  const int32_t v = fe_carry_row<F>(pY + pX, k), w = fe_carry_row<F>(qY + qX, k);
+  int32_t m = fe_mul_row<F>(row_sel4(s, t, v, pT, pZ), row_sel4(s, u, w, qT, qZ), k);
+  const int32_t A = fe_from_row(m, 0), B = fe_from_row(m, 1), TT = fe_from_row(m, 2);
+  int32_t D = fe_from_row(m, 3);
+  const int32_t C = fe_mul_row<F>(TT, row_const<F>(F::K2D, k.j), k);   // the same product in every row
+  D = D + D;
+  const int32_t E = fe_carry_row<F>(B - A, k), Fv = fe_carry_row<F>(D - C, k);
+  const int32_t G = fe_carry_row<F>(D + C, k), H = fe_carry_row<F>(B + A, k);
+  m = fe_mul_row<F>(row_sel4(s, E, G, E, Fv), row_sel4(s, Fv, H, H, G), k);
+  r.c[0] = fe_from_row(m, 0);
+  r.c[1] = fe_from_row(m, 1);
+  r.c[3] = fe_from_row(m, 2);
+  r.c[2] = fe_from_row(m, 3);
+}
+
 // ------------------------------------------------------------------------------------------------ group policies
 // Every kernel that works on resident point records or on accumulator records is written once over a "group policy":
 // the group of curve.h (accumulator type, formulas) plus the device record formats.
@@ -847,6 +953,10 @@ struct WeierPolicy : WeierGroup<F_> {
   static constexpr int ACC_WORDS = 4 * F::NW;
   static constexpr int ACC_OCC = 1;   // k_bucket_accumulate: no register cap (the XYZZ mixed addition spills below ~120)
   static __device__ __forceinline__ void add_x4(Acc& r, const Acc& a, const Acc& b, int s, bool dbl) { xyzz_add_x4(r, a, b, s, dbl); }
+  // the row form: one addition per wave (AccRow: one register per coordinate, the same in all four rows)
+  using Row = AccRow<F>;
+  static __device__ __forceinline__ void add_rows(Row& r, const Row& a, const Row& b, bool dbl, const RowLane<F>& k) { xyzz_add_rows(r, a, b, dbl, k); }
+  static __device__ __forceinline__ void identity_row(Row& a, const RowLane<F>& k) { a.c[0] = a.c[1] = k.one; a.c[2] = a.c[3] = 0; }
   static __device__ __forceinline__ void madd(Acc& r, const Acc& a, const uint32_t* rec, uint32_t neg) {
     Affine<F> p;
     bool inf = load_affine<F>(p, rec, neg);
@@ -900,6 +1010,9 @@ struct TePolicy : TeGroup<F_> {
   // in a same-box A/B at 2^24, 6 waves spill)
   static constexpr int ACC_OCC = 1;
   static __device__ __forceinline__ void add_x4(Acc& r, const Acc& a, const Acc& b, int s, bool dbl) { te_add_x4(r, a, b, s, dbl); }
+  using Row = AccRow<F>;
+  static __device__ __forceinline__ void add_rows(Row& r, const Row& a, const Row& b, bool dbl, const RowLane<F>& k) { te_add_rows(r, a, b, dbl, k); }
+  static __device__ __forceinline__ void identity_row(Row& a, const RowLane<F>& k) { a.c[0] = a.c[3] = 0; a.c[1] = a.c[2] = k.one; }
   static __device__ __forceinline__ void madd(Acc& r, const Acc& a, const uint32_t* rec, uint32_t neg) {
     Base n;
     Fe<F> x;
@@ -1213,6 +1326,84 @@ __global__ void __launch_bounds__(REDUCE_TAIL_T, 1) k_reduce_tail(uint32_t* r0, 
   for (uint32_t j = threadIdx.x; j < (uint32_t)XW; j += REDUCE_TAIL_T) c_final[(size_t)k * XW + j] = cin[j];
 }
 
+// The same levels in the row form (add_rows of the policy): one WAVE per addition, element q of a group in wave q of
+// four, the steps and the dataflow of reduce_group16.  Operands travel between the four waves through LDS: a wave
+// publishes one accumulator (4 coordinates x 16 limbs, lazy limbs as they are) and reads its partner's after a
+// barrier; two buffers in turn, so one barrier per step is enough (a wave reaches the next write of a buffer only
+// through the barrier after its partners' reads of it).  For levels of so few groups that their waves stand alone on their SIMDs: a product level is then ~3 times
+// shorter than the 4-lane form's (profiles/reduce_rows_ab.txt).
+constexpr int ROWS_PUB_WORDS = 2 * 4 * 4 * 16;   // LDS words per group: 2 buffers x 4 waves x 4 coordinates x 16 lanes
+template <class P>
+__device__ __forceinline__ void reduce_group_rows(uint32_t* rows_out, uint32_t* c_out, const uint32_t* rows_in,
+                                                  const uint32_t* c_in, uint32_t n_in, uint32_t A, bool live, uint32_t q,
+                                                  int32_t* pub, const RowLane<typename P::F>& rk) {
+  using F = typename P::F;
+  using Row = typename P::Row;
+  constexpr int XW = P::ACC_WORDS;
+  const uint32_t e = A * 4 + q;
+  const int lj = (int)(__lane_id() & 15u);
+  Row r, c, v, w, got, ident;
+  P::identity_row(ident, rk);
+  r = ident;
+  c = ident;
+  if (live && e < n_in) {   // uniform over the wave
+    acc_load_row<F>(r, rows_in + (size_t)e * XW, rk);
+    acc_load_row<F>(c, c_in + (size_t)e * XW, rk);
+  }
+  auto exchange = [&](int step, const Row& mine, uint32_t src) {
+    int32_t* buf = pub + (step & 1) * (4 * 4 * 16);
+    if (__lane_id() < 16u) {
+#pragma unroll
+      for (int i = 0; i < 4; i++) buf[(q * 4 + i) * 16 + lj] = mine.c[i];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; i++) got.c[i] = buf[(src * 4 + i) * 16 + lj];
+  };
+  {
+    const uint32_t src[4] = {1, 3, 3, 2};
+    exchange(0, q == 2 ? c : r, src[q]);
+    P::add_rows(v, q == 3 ? c : r, got, false, rk);   // W0 s01, W1 b, W2 a, W3 c23
+  }
+  {
+    const uint32_t src[4] = {2, 0, 2, 3};
+    exchange(1, q == 0 ? c : v, src[q]);
+    if (q == 3) got = ident;
+    Row lhs = (q == 1) ? c : v;
+    if (q == 3) lhs = ident;
+    P::add_rows(w, lhs, got, q == 2, rk);             // W0 row, W1 c01, W2 2a, W3 0
+  }
+  {
+    const uint32_t src[4] = {0, 3, 1, 3};
+    exchange(2, q == 0 ? w : v, src[q]);
+    P::add_rows(r, w, got, q == 0, rk);               // W0 2 row, W1 cs, W2 tri
+  }
+  {
+    const uint32_t src[4] = {0, 2, 2, 3};
+    exchange(3, r, src[q]);
+    P::add_rows(c, r, got, q == 0, rk);               // W0 4 row, W1 C' = cs + tri
+  }
+  if (live && q == 0) acc_store_row<F>(rows_out + (size_t)A * XW, c, rk);
+  if (live && q == 1) acc_store_row<F>(c_out + (size_t)A * XW, c, rk);
+}
+
+// one level: one 256-thread workgroup per group
+template <class P>
+__global__ void __launch_bounds__(256) k_reduce_rows(uint32_t* rows_out, uint32_t* c_out, const uint32_t* rows_in,
+                                                     const uint32_t* c_in, uint32_t n_in, uint32_t groups, uint32_t total) {
+  constexpr int XW = P::ACC_WORDS;
+  __shared__ int32_t pub[ROWS_PUB_WORDS];
+  const RowLane<typename P::F> rk = row_lane<typename P::F>();
+  const uint32_t grp = blockIdx.x;   // < total
+  const uint32_t k = grp / groups, A = grp - k * groups;
+  reduce_group_rows<P>(rows_out + (size_t)k * groups * XW, c_out + (size_t)k * groups * XW,
+                       rows_in + (size_t)k * n_in * XW, c_in + (size_t)k * n_in * XW, n_in, A, true, threadIdx.x >> 6,
+                       pub, rk);
+}
+
+// (A row form of k_reduce_tail -- 1024 threads, four groups per pass -- puts four waves on every SIMD of its one CU and
+// measured 27 us per level against 16 us for a launch of k_reduce_rows: the last levels run as launches of this
+// kernel, profiles/reduce_rows_ab.txt.)
 
 }  // namespace msmz
 

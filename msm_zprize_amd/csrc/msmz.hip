@@ -312,6 +312,10 @@ int msmz_test_field_limbs(msmz_ctx* c, int op, const int32_t* a, const int32_t* 
                           uint8_t* canon) {
   return c ? c->engine->test_hooks()->test_field_limbs(op, a, b, n, raw, canon) : MSMZ_ERR_ARG;
 }
+int msmz_test_field_rows(msmz_ctx* c, int op, const int32_t* a, const int32_t* b, uint64_t n, uint32_t live_rows,
+                         int32_t* raw, uint8_t* canon) {
+  return c ? c->engine->test_hooks()->test_field_rows(op, a, b, n, live_rows, raw, canon) : MSMZ_ERR_ARG;
+}
 int msmz_test_glv(msmz_ctx* c, const uint8_t* s, uint64_t n, uint8_t* s0, uint8_t* s1, uint8_t* neg) {
   return c ? c->engine->test_hooks()->test_glv(s, n, s0, s1, neg) : MSMZ_ERR_ARG;
 }

@@ -23,6 +23,11 @@ struct ReduceKnobs {
   uint32_t quad16_max = (uint32_t)env_int("MSMZ_QUAD16", 8192);        // levels of at most this many groups: k_reduce_quad16
   uint32_t pairsum_x4_max = (uint32_t)env_int("MSMZ_PAIRSUM_X4", 16384);   // pair-sum levels of at most this many
                                                                            // additions use DPP quads
+  // levels of at most this many groups (and within quad16_max) run the row form, k_reduce_rows: one wave per addition.
+  // It wins while its waves stand alone on their SIMDs -- 16-20 us a level up to 480 groups against 45-47 us for
+  // k_reduce_quad16, 55 against 47 us at 1920 (profiles/reduce_rows_ab.txt) -- and a launch per level is then shorter
+  // than a level inside k_reduce_tail, so such levels run as launches below tail_n too, down to one entry.
+  uint32_t rows_max = (uint32_t)env_int("MSMZ_ROWS_MAX", 512);
 };
 
 // The buckets the 2-D reduction sums, in the three forms an accumulation leaves them in.  The memory stays the caller's.
@@ -111,13 +116,18 @@ class BucketReduce {
   // with one entry per problem in final()
   int levels(const ReduceKnobs& rk, uint32_t n_in, uint32_t nprob, hipStream_t stream) {
     int st;
-    while (n_in > rk.tail_n) {
+    const uint32_t rows_max = rk.rows_max < rk.quad16_max ? rk.rows_max : rk.quad16_max;
+    while (n_in > rk.tail_n || (n_in > 1 && (uint64_t)nprob * ((n_in + 3) / 4) <= rows_max)) {
       const uint32_t S = 4;   // quads handle short tails too
       const uint32_t g2 = (n_in + S - 1) / S;
       const int nxt = cur_ ^ 1;
       if ((st = rows_room(nxt, (size_t)nprob * g2)) || (st = carry_room(nxt, (size_t)nprob * g2))) return st;
       const uint32_t total = nprob * g2;
-      if (total <= rk.quad16_max) {
+      if (total <= rows_max) {
+        // smallest levels: every wave alone on its SIMD, one wave per addition
+        hipLaunchKernelGGL((k_reduce_rows<P>), dim3(total), dim3(256), 0, stream, rows(nxt), carry(nxt), rows(cur_),
+                           carry(cur_), n_in, g2, total);
+      } else if (total <= rk.quad16_max) {
         // small level: latency-bound, one DPP quad per addition
         hipLaunchKernelGGL((k_reduce_quad16<P>), dim3((total * 16 + 63) / 64), dim3(64), 0, stream, rows(nxt), carry(nxt),
                            rows(cur_), carry(cur_), n_in, g2, total);

@@ -8,12 +8,13 @@
 
 namespace msmz {
 
-// The eleven msmz_test_* stage entry points of an engine whatever its curve; arguments as in msmz_test.h and TestHooks.
+// The twelve msmz_test_* stage entry points of an engine whatever its curve; arguments as in msmz_test.h and TestHooks.
 class ITestHooks {
  public:
   virtual ~ITestHooks() {}
   virtual int test_field(int, const uint8_t*, const uint8_t*, uint64_t, uint8_t*) = 0;
   virtual int test_field_limbs(int, const int32_t*, const int32_t*, uint64_t, int32_t*, uint8_t*) = 0;
+  virtual int test_field_rows(int, const int32_t*, const int32_t*, uint64_t, uint32_t, int32_t*, uint8_t*) = 0;
   virtual int test_glv(const uint8_t*, uint64_t, uint8_t*, uint8_t*, uint8_t*) = 0;
   virtual int test_digits(const uint8_t*, uint64_t, int, int, int, uint32_t*) = 0;
   virtual int test_sort(const uint8_t*, uint64_t, int, int, int, uint32_t*, uint32_t*, uint64_t, uint32_t*, uint64_t) = 0;
@@ -110,6 +111,22 @@ class TestHooks : public ITestHooks {
     hipLaunchKernelGGL((k_test_field_limbs<F>), dim3((n + 63) / 64), dim3(64), 0, eng_.stream_, sg.at<int32_t>(iraw),
                        sg.at<uint32_t>(icanon), sg.at<const int32_t>(ia), sg.at<const int32_t>(ib), (uint32_t)n, op,
                        eng_.slots_.template as<uint32_t>());
+    return sg.download();
+  }
+
+  int test_field_rows(int op, const int32_t* a, const int32_t* b, uint64_t n, uint32_t live_rows, int32_t* raw,
+                      uint8_t* canon) override {
+    if (!a || !b || !raw || !canon || n == 0 || n > (1u << 22) || op < 0 || op >= TFR_COUNT || live_rows == 0 ||
+        live_rows > 15)
+      return MSMZ_ERR_ARG;
+    const size_t lb = (size_t)4 * F::N * n, eb = (size_t)E::FE_BYTES * n;
+    Staging sg = staging();
+    const int ia = sg.in(a, lb), ib = sg.in(b, lb), iraw = sg.out(raw, lb), icanon = sg.out(canon, eb);
+    if (int st = sg.upload()) return st;
+    const uint32_t per_wave = (uint32_t)__builtin_popcount(live_rows);
+    hipLaunchKernelGGL((k_test_field_rows<F>), dim3((uint32_t)((n + per_wave - 1) / per_wave)), dim3(64), 0, eng_.stream_,
+                       sg.at<int32_t>(iraw), sg.at<uint32_t>(icanon), sg.at<const int32_t>(ia), sg.at<const int32_t>(ib),
+                       (uint32_t)n, op, live_rows);
     return sg.download();
   }
 
@@ -266,7 +283,7 @@ class TestHooks : public ITestHooks {
     const int ia = sg.in(a, rb), ib = sg.in(b, rb), ineg = sg.in(neg, n), io = sg.out(out, pb);
     if (int st = sg.upload()) return st;
     const bool x4 = op == TPR_ADD_X4 || op == TPR_DBL_X4 || op == TPR_CHAIN_X4;
-    const uint64_t threads = x4 ? 4 * n : n;
+    const uint64_t threads = op >= TPR_ADD_ROWS ? 64 * n : x4 ? 4 * n : n;   // rows: one wave = one workgroup per element
     hipLaunchKernelGGL((k_test_point_raw<P>), dim3((threads + 63) / 64), dim3(64), 0, eng_.stream_,
                        sg.at<uint32_t>(io), sg.at<const uint32_t>(ia), sg.at<const uint32_t>(ib),
                        sg.at<const uint8_t>(ineg), (uint32_t)n, op, L);
@@ -320,7 +337,7 @@ class TestHooks : public ITestHooks {
     const bool levels = a.mode == MSMZ_TR_LEVELS, locs = a.mode == MSMZ_TR_LOCATIONS;
     if (a.mode < MSMZ_TR_LOCATIONS || a.mode > MSMZ_TR_LEVELS || !a.out_xy) return MSMZ_ERR_ARG;
     if (TE && locs) return MSMZ_ERR_UNSUPPORTED;
-    if (a.tail_n > 4096 || a.quad16_max > CAP || a.pairsum_x4_max > CAP) return MSMZ_ERR_ARG;
+    if (a.tail_n > 4096 || a.quad16_max > CAP || a.pairsum_x4_max > CAP || a.rows_max > CAP) return MSMZ_ERR_ARG;
     if (a.n_points > CAP || a.n_slots > CAP || (a.n_points && !a.points_xy) || (a.n_slots && !a.slots_xy)) return MSMZ_ERR_ARG;
     // geometry: a plan of `nsets` bucket sets of window size c, as far as Planner::r2_geom and the hook read one
     Plan pl{};
@@ -365,6 +382,7 @@ class TestHooks : public ITestHooks {
     if (a.tail_n) rk.tail_n = a.tail_n;
     if (a.quad16_max) rk.quad16_max = a.quad16_max;
     if (a.pairsum_x4_max) rk.pairsum_x4_max = a.pairsum_x4_max;
+    if (a.rows_max) rk.rows_max = a.rows_max;
     const uint32_t n_lines = levels || !a.lines_xy ? 0 : n_res * g.H;
 
     const size_t np = a.n_points, ns = a.n_slots, rec = (size_t)RW * 4;

@@ -19,7 +19,7 @@ enum {   // point ops (msmz_test_point)
 };
 enum {   // point ops on memory-format operands (msmz_test_point_raw)
   TPR_ADD = 0, TPR_ADD_X4 = 1, TPR_MADD = 2, TPR_DBL = 3, TPR_DBL_X4 = 4, TPR_MDBL = 5, TPR_CHAIN = 6, TPR_CHAIN_X4 = 7,
-  TPR_COUNT = 8
+  TPR_ADD_ROWS = 8, TPR_DBL_ROWS = 9, TPR_CHAIN_ROWS = 10, TPR_COUNT = 11
 };
 
 // Operands / results are NW memory words per element (little endian).  Inputs are lazy Montgomery residues: any
@@ -146,6 +146,56 @@ __global__ void __launch_bounds__(64) k_test_field_limbs(int32_t* raw, uint32_t*
   for (int j = 0; j < NW; j++) canon[(size_t)i * NW + j] = cw[j];
 }
 
+// row-form field routines (fp_rows.h) on raw limbs (msmz_test_field_rows): one element per DPP row, lane j = limb j.
+// A wave takes as many elements as live_rows has bits, one in each row whose bit is set; the other rows run on zero
+// operands.  a, b, raw: N int32 per element (ROUNDTRIP: the NW memory words in the first NW of them); canon: NW words.
+enum { TFR_MUL = 0, TFR_ROUNDTRIP = 1, TFR_IS_ZERO = 2, TFR_COUNT = 3 };
+template <class F>
+__global__ void __launch_bounds__(64) k_test_field_rows(int32_t* raw, uint32_t* canon, const int32_t* a_in,
+                                                        const int32_t* b_in, uint32_t n, int op, uint32_t live_rows) {
+  constexpr int N = F::N, NW = F::NW;
+  __shared__ uint32_t sw[4][NW];
+  const RowLane<F> rk = row_lane<F>();
+  const uint32_t row = threadIdx.x >> 4;
+  const uint32_t i = blockIdx.x * (uint32_t)__popc(live_rows) + (uint32_t)__popc(live_rows & ((1u << row) - 1u));
+  const bool live = ((live_rows >> row) & 1u) != 0 && i < n;
+  const size_t at = (size_t)(live ? i : 0) * N;   // all 64 lanes stay active: the row routines need whole waves
+  int32_t a = 0, b = 0, r = 0;
+  if (live && rk.j < N) {
+    a = a_in[at + rk.j];
+    b = b_in[at + rk.j];
+  }
+  switch (op) {
+    case TFR_MUL:
+      r = fe_mul_row<F>(a, b, rk);
+      fe_store_row<F>(sw[row], r, rk);
+      break;
+    case TFR_ROUNDTRIP: {
+      const int32_t x = fe_load_row<F>(reinterpret_cast<const uint32_t*>(a_in + at), rk);
+      fe_store_row<F>(sw[row], live ? x : 0, rk);
+      break;
+    }
+    default: {
+      const bool z = fe_is_zero_row<F>(a, rk);
+      r = (rk.j == 0 && z) ? 1 : 0;
+      if (rk.j < NW) sw[row][rk.j] = 0;
+      break;
+    }
+  }
+  __syncthreads();
+  if (!live) return;
+  if (op == TFR_ROUNDTRIP) r = rk.j < NW ? (int32_t)sw[row][rk.j] : 0;
+  if (rk.j < N) raw[at + rk.j] = r;
+  if (rk.j == 0) {
+    uint32_t w[NW];
+#pragma unroll
+    for (int j = 0; j < NW; j++) w[j] = sw[row][j];
+    if (op != TFR_IS_ZERO) words_canon<F>(w);
+#pragma unroll
+    for (int j = 0; j < NW; j++) canon[(size_t)i * NW + j] = w[j];
+  }
+}
+
 // GLV decomposition of n scalars: out0/out1 = |s0|, |s1| (4 words each), neg[2i], neg[2i+1] = their signs
 template <class Fr>
 __global__ void __launch_bounds__(256) k_test_glv(uint32_t* s0, uint32_t* s1, uint8_t* neg, const uint32_t* scalars,
@@ -259,6 +309,7 @@ __global__ void __launch_bounds__(64) k_test_point(uint32_t* out, const uint32_t
 // infinity) or a Niels record [y-x | y+x | 2dxy | 0] (TE MADD).  neg[i] (nullable): negate the MADD / MDBL record as the
 // bucket accumulation does.  CHAIN: L steps r <- r + b (even steps), r <- 2r (odd steps) in registers, from r = a,
 // with the scalar or the 4-lane formulas.  out[i] = canonical affine (x | y) of the result; all-zero = infinity.
+// The *_ROWS ops run the row form (add_rows of the policy): one wave per element, launched as one workgroup each.
 template <class P>
 __global__ void __launch_bounds__(64) k_test_point_raw(uint32_t* out, const uint32_t* a_in, const uint32_t* b_in,
                                                        const uint8_t* neg, uint32_t n, int op, int L) {
@@ -279,6 +330,35 @@ __global__ void __launch_bounds__(64) k_test_point_raw(uint32_t* out, const uint
     for (int k = 0; k < 4; k++) fe_unpack<F>(c[k], rec + k * NW);
   };
   Acc a, b, r;
+  if (op >= TPR_ADD_ROWS) {   // uniform over the launch
+    __shared__ uint32_t rec[4 * NW];
+    const RowLane<F> rk = row_lane<F>();
+    typename P::Row ra, rb, rr;
+    acc_load_row<F>(ra, a_in + (size_t)blockIdx.x * 4 * NW, rk);
+    acc_load_row<F>(rb, b_in + (size_t)blockIdx.x * 4 * NW, rk);
+    if (op == TPR_ADD_ROWS) {
+      P::add_rows(rr, ra, rb, false, rk);
+    } else if (op == TPR_DBL_ROWS) {
+      P::add_rows(rr, ra, ra, true, rk);
+    } else {
+      rr = ra;
+#pragma unroll 1
+      for (int k = 0; k < L; k++) {
+        typename P::Row u;
+        if (k & 1) P::add_rows(u, rr, rr, true, rk); else P::add_rows(u, rr, rb, false, rk);
+        rr = u;
+      }
+    }
+    acc_store_row<F>(rec, rr, rk);
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    load(r, rec);
+    uint32_t w[2 * NW];
+    (void)P::to_affine_canon(w, r);
+#pragma unroll
+    for (int j = 0; j < 2 * NW; j++) out[(size_t)blockIdx.x * 2 * NW + j] = w[j];
+    return;
+  }
   load(a, arec);
   switch (op) {
     case TPR_ADD: load(b, brec); P::add(r, a, b); break;
