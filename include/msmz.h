@@ -333,7 +333,8 @@ int msmz_check_points(msmz_ctx* ctx, uint64_t points_handle, uint64_t first, uin
 /* Per-point scalar multiplication of resident point sets:
  *     out_i = [s_i] P_i (+ Q_i),   i = 0 .. n-1,   P_i = record first_p + i of points_handle, s_i and Q_i likewise
  * -- a NEW point set made from resident ones: IPA generator folding (G'_i = G_lo,i + [u] G_hi,i: one handle as P and Q,
- * first_p = n, first_q = 0, the broadcast u), SRS re-randomisation (P_i -> [tau^i] P_i), fixed-base vectors.
+ * first_p = n, first_q = 0, the broadcast u), SRS re-randomisation (P_i -> [tau^i] P_i).  (Fixed-base vectors [s_i] B
+ * for ONE base are msmz_points_fixed_base's, below: the same result from a window table at a fraction of the cost.)
  * Result: a new plain point handle of n base points, exactly what msmz_upload_points of the same affine points leaves
  * (the endomorphism images behind them on the Weierstrass curves, Niels records on the twisted Edwards curve); every
  * function that takes a point handle takes it.  It owns its memory, and the call returns after the GPU has finished.
@@ -388,6 +389,43 @@ typedef struct msmz_mul_opts {
 } msmz_mul_opts;
 int msmz_points_mul_opts(msmz_ctx* ctx, const msmz_mul* m, uint64_t n, const msmz_mul_opts* opts /* nullable */,
                          uint64_t* out_handle);
+
+/* Fixed-base multiplication: a point set from a resident scalar set and ONE base,
+ *     out_i = [s_(first_s + i)] B,   i = 0 .. n-1
+ * -- a KZG SRS [tau^i]G from the powers msmz_scalars_powers leaves resident, Pedersen and ElGamal vectors, the fixed-base
+ * half of a Groth16 setup, a test SRS with known discrete logs.  msmz_points_mul over n copies of B gives the same set
+ * by a chain of 253 / 255 doublings per point; this call builds a window table of multiples of B once (kept for the
+ * next call) and pays K = 16 to 32 mixed additions per point.
+ * The base: record base_index of the plain point handle base_handle; or, with base_handle == 0, the canonical
+ * little-endian x || y at base_xy_le (2 * fe_bytes; on the Weierstrass curves the all-zero record is the point at
+ * infinity, as in a download), or the curve's generator when that is NULL too.  B is taken as given: it need not lie
+ * in the subgroup, and a base of small order or at infinity multiplies to what the group law gives.
+ * Result: a new plain point handle of n base points, byte for byte what msmz_points_mul leaves for n copies of B and the
+ * same scalars -- the endomorphism images behind the base points, Niels records on ed-on-bls12-377, [0]B and every
+ * multiple of an infinite B the infinity record / (0, 1).  Every function that takes a point handle takes it.
+ * scalar_bits = b: "every scalar of the range is below 2^b", as in msmz_mul_opts: fewer windows, the same bytes.
+ * MSMZ_ERR_ARG, before any launch: a null ctx, f or out_handle; n == 0 or beyond the limit of msmz_upload_points; an
+ * unknown handle or one of the wrong kind; a scalar range beyond its set; base_index beyond the base points of
+ * base_handle (or non-zero without one); both base_handle and base_xy_le; non-zero flags; scalar_bits < 0 or > 256.
+ * MSMZ_ERR_UNSUPPORTED: a precomputed handle as base.  MSMZ_ERR_RANGE: a coordinate of base_xy_le >= p (found on the
+ * host); a resident scalar >= q or >= 2^b inside the range (found by the kernel: no handle is created, *out_handle is as
+ * it was, the context stays usable; scalars outside the range are not read).
+ * The engine keeps the tables of the last few (base, window width, windows): a second call on the same base, and any
+ * call on the generator after the first, skips the build.  A table is at most 64 MiB of device memory.
+ * Multi-device contexts: the base is resolved to bytes once (one record is downloaded if it is resident), every engine
+ * multiplies its own share of the scalars, and the result is dealt like an upload; first_s != 0 is MSMZ_ERR_UNSUPPORTED
+ * there (the stance of msmz_points_mul).  Like the rest of the multi-device code this has run as several engines on ONE
+ * GPU only. */
+typedef struct msmz_fixed_base {
+  uint64_t base_handle;       /* plain point handle holding B, or 0 */
+  uint64_t base_index;        /* B = base-point record base_index of base_handle (0 when base_handle == 0) */
+  const uint8_t* base_xy_le;  /* base_handle == 0: canonical x || y of B (2 * fe_bytes); NULL = the curve's generator */
+  uint64_t scalars_handle;    /* resident scalar set, required */
+  uint64_t first_s;
+  int32_t scalar_bits;        /* every scalar of the range is below 2^scalar_bits; 0 = no bound (as msmz_mul_opts) */
+  uint32_t flags;             /* must be 0 */
+} msmz_fixed_base;            /* 48 bytes */
+int msmz_points_fixed_base(msmz_ctx* ctx, const msmz_fixed_base* f, uint64_t n, uint64_t* out_handle);
 
 /* Arithmetic mod q over resident scalar sets: linear combinations, inner products and powers of
  * one ratio, so that a prover's witness fold a' = a_lo + u^-1 a_hi, its cross terms <a_lo, b_hi>, a random linear

@@ -109,6 +109,17 @@ void msmz_test_scalar_scan_geometry(uint32_t* rec_tile, uint32_t* rec_pass, uint
  *   msmz_test_ntt_geometry: *pass_log = the most stages one pass runs (NTT_PASS_LOG; a tile is 2^pass_log entries). */
 int msmz_test_ntt_plan(int curve_id, uint32_t log_n, uint32_t* n_passes, uint32_t* stages);
 void msmz_test_ntt_geometry(uint32_t* pass_log);
+/* msmz_points_fixed_base (msm_zprize_amd/csrc/fixed_base.h).
+ *   msmz_test_fixed_base_plan: what the planner picks for n points of a curve and a bound of `bits` (0 or >= the bit
+ *     length of q: none) -- the window width, the windows K = ceil((bound + 1) / c) and the table's entries
+ *     K 2^(c-1).  Needs no context.  MSMZ_ERR_ARG: an unknown curve, a null pointer, n == 0, bits < 0 or > 256.
+ *   msmz_test_set_fixed_base_window: later calls on this context cut their digits c wide (4 .. 16) whatever the planner
+ *     says; 0 = the planner's choice again.  MSMZ_ERR_ARG: another c, or one whose full-width table passes 64 MiB.
+ *   msmz_test_fixed_base_tables: *built = the tables this context has built so far (a call served from the cache adds
+ *     none; a multi-device context: the sum over its engines). */
+int msmz_test_fixed_base_plan(int curve_id, uint64_t n, int bits, int32_t* c, int32_t* K, uint64_t* entries);
+int msmz_test_set_fixed_base_window(msmz_ctx* ctx, int c);
+int msmz_test_fixed_base_tables(msmz_ctx* ctx, uint64_t* built);
 /* out[i] = op(a[i], b[i]) for i < n; a, b, out: n * fe_bytes */
 int msmz_test_field(msmz_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out);
 /* GLV split of n 32-byte scalars: s0, s1 = magnitudes (16 bytes each), neg = 2 sign bytes per scalar

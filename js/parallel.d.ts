@@ -54,6 +54,12 @@ export interface ParallelApi {
   mulPoints(scalars: DeviceArray | bigint, points: DeviceArray, n?: number,
             options?: { addend?: DeviceArray | null; firstPoint?: number; firstScalar?: number; firstAddend?: number;
                         scalarBits?: number; subgroup?: boolean }): Promise<DeviceArray>;
+  /** a new point array: out[i] = [scalars[firstScalar + i]] B for ONE base B -- null (the curve's generator), an affine
+   * point, or point `baseIndex` of a resident point array -- from a window table of multiples of B; scalarBits: every
+   * scalar of the range is below 2^scalarBits */
+  fixedBaseMul(scalars: DeviceArray, n?: number,
+               options?: { base?: DeviceArray | { x: bigint; y: bigint; isZero?: boolean } | null; baseIndex?: number;
+                           firstScalar?: number; scalarBits?: number }): Promise<DeviceArray>;
   /** out[firstOut + i] = a_i x[firstX + i] (+ b_i y[firstY + i]) mod the group order; a, b: one bigint for every entry or
    * a resident scalar array; without `out` a new array, with it that range is overwritten (it may be an input's range
    * exactly, or apart from it) */

@@ -396,6 +396,36 @@ function createCurve(params, kind) {
                             firstScalar, addend === null ? 0 : addend.handle, firstAddend, n, bits, subgroup ? 1 : 0);
       return DeviceArray.make(curve, h, n, "points");
     },
+    /** fixed-base multiplication (include/msmz.h msmz_points_fixed_base): a new resident point array,
+     * out[i] = [scalars[firstScalar + i]] B, i < n, for ONE base B -- an SRS [tau^i]G from scalarPowers(tau, n), Pedersen
+     * vectors, points with known discrete logs.  `base`: null (the curve's generator), an affine point {x, y, isZero},
+     * or a resident point array, of which B is point `baseIndex`.  B need not lie in the subgroup.  The result is what
+     * mulPoints leaves for n copies of B, from a window table of multiples of B (kept for the next call on the same
+     * base) instead of a chain per point.  scalarBits = b: every scalar of the range is below 2^b (0 = no bound; a
+     * scalar that breaks it fails the call). */
+    async fixedBaseMul(scalars, n, { base = null, baseIndex = 0, firstScalar = 0, scalarBits = 0 } = {}) {
+      if (!isScalars(scalars)) throw TypeError("fixedBaseMul: `scalars` is a resident scalar array");
+      let b = null;
+      if (isPoints(base)) {
+        if (!Number.isInteger(baseIndex) || baseIndex < 0 || baseIndex >= base.n)
+          throw Error(`fixedBaseMul: baseIndex = ${baseIndex} of a point array of ${base.n}`);
+        b = base.handle;
+      } else if (base !== null) {
+        if (typeof base !== "object" || base instanceof DeviceArray || typeof base.x !== "bigint" || typeof base.y !== "bigint")
+          throw TypeError("fixedBaseMul: `base` is null (the generator), an affine point {x, y, isZero} or a resident point array");
+        if (baseIndex !== 0) throw Error("fixedBaseMul: baseIndex without a resident point array");
+        const zero = !!base.isZero;
+        for (const v of [base.x, base.y])
+          if (!zero && (v < 0n || v >= params.modulus)) throw Error("fixedBaseMul: a coordinate of the base is not in [0, field modulus)");
+        b = zero ? Buffer.alloc(2 * fb) : Buffer.concat([bigintToBytes(base.x, fb), bigintToBytes(base.y, fb)]);
+      } else if (baseIndex !== 0) {
+        throw Error("fixedBaseMul: baseIndex without a resident point array");
+      }
+      n = scanRanges("fixedBaseMul", [["firstScalar", firstScalar, scalars]], n, null, Infinity);
+      const bits = scalarBitsArg({ scalarBits }, "fixedBaseMul");
+      const h = N.fixedBaseMul(ctx, scalars.handle, firstScalar, n, b, isPoints(base) ? baseIndex : 0, bits);
+      return DeviceArray.make(curve, h, n, "points");
+    },
     /** arithmetic mod the group order over resident scalar arrays (include/msmz.h msmz_scalars_combine):
      * out[firstOut + i] = a_i x[firstX + i] (+ b_i y[firstY + i]), i < n.  `a` and `b` are bigints below the group order
      * (one coefficient for every entry) or resident scalar arrays (a_i = a[firstA + i]).  Without `out` the result is a

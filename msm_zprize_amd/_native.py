@@ -55,6 +55,11 @@ class MsmzMulOpts(C.Structure):   # msmz_mul_opts (include/msmz.h): the caller's
     _fields_ = [("flags", C.c_uint32), ("scalar_bits", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class MsmzFixedBase(C.Structure):   # msmz_fixed_base (include/msmz.h): out_i = [s_i] B for one base B
+    _fields_ = [("base_handle", C.c_uint64), ("base_index", C.c_uint64), ("base_xy_le", C.c_char_p),
+                ("scalars_handle", C.c_uint64), ("first_s", C.c_uint64), ("scalar_bits", C.c_int32), ("flags", C.c_uint32)]
+
+
 class MsmzScalarTerm(C.Structure):   # msmz_scalar_term (include/msmz.h): one term c (.) v of msmz_scalars_combine
     _fields_ = [("handle", C.c_uint64), ("first", C.c_uint64), ("coeff_handle", C.c_uint64), ("coeff_first", C.c_uint64),
                 ("coeff", C.c_char_p)]
@@ -154,6 +159,7 @@ EXPORTS = {
     "msmz_points_mul": (C.c_int, [C.c_void_p, C.POINTER(MsmzMul), C.c_uint64, C.POINTER(C.c_uint64)]),
     "msmz_points_mul_opts": (C.c_int, [C.c_void_p, C.POINTER(MsmzMul), C.c_uint64, C.POINTER(MsmzMulOpts),
                                        C.POINTER(C.c_uint64)]),
+    "msmz_points_fixed_base": (C.c_int, [C.c_void_p, C.POINTER(MsmzFixedBase), C.c_uint64, C.POINTER(C.c_uint64)]),
     "msmz_scalars_combine": (C.c_int, [C.c_void_p, C.POINTER(MsmzScalarTerm), C.POINTER(MsmzScalarTerm), C.c_uint64,
                                        C.c_uint64, C.POINTER(C.c_uint64)]),
     "msmz_scalars_dot": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_char_p]),
@@ -174,6 +180,10 @@ EXPORTS = {
     "msmz_test_scalar_scan_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "msmz_test_ntt_plan": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "msmz_test_ntt_geometry": (None, [C.POINTER(C.c_uint32)]),
+    "msmz_test_fixed_base_plan": (C.c_int, [C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_uint64)]),
+    "msmz_test_set_fixed_base_window": (C.c_int, [C.c_void_p, C.c_int]),
+    "msmz_test_fixed_base_tables": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "msmz_test_field": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_uint64, C.c_char_p]),
     "msmz_test_field_limbs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                         C.c_char_p]),

@@ -90,6 +90,8 @@ class IEngine {
                            uint8_t* verdicts) = 0;
   // msmz_points_mul / msmz_points_mul_opts: a new plain point handle, record i = [s_i] P_i (+ Q_i); o: all zero = none
   virtual int points_mul(const msmz_mul& m, const msmz_mul_opts& o, uint64_t n, uint64_t* h) = 0;
+  // msmz_points_fixed_base: a new plain point handle, record i = [s_i] B (msmz.hip has checked flags and scalar_bits)
+  virtual int points_fixed_base(const msmz_fixed_base&, uint64_t, uint64_t*) { return MSMZ_ERR_UNSUPPORTED; }
   // msmz_scalars_combine / _dot / _powers: arithmetic mod q over resident scalar sets (scalar_kernels.h); `map` as for
   // random_scalars
   virtual int scalars_combine(const msmz_scalar_term& x, const msmz_scalar_term* y, uint64_t n, uint64_t first_out,
@@ -111,6 +113,9 @@ class IEngine {
     if (range_passes) *range_passes = 0;
     if (sub_batches) *sub_batches = 0;
   }
+  // msmz_test_set_fixed_base_window / msmz_test_fixed_base_tables: the forced window width, the tables built so far
+  virtual int test_set_fixed_base_window(int) { return MSMZ_ERR_UNSUPPORTED; }
+  virtual uint64_t test_fixed_base_tables() { return 0; }
   virtual ITestHooks* test_hooks() = 0;
 };
 

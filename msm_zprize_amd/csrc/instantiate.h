@@ -3,6 +3,7 @@
 // `extern template` declarations.
 #pragma once
 #include "check_kernels.h"
+#include "fixed_kernels.h"
 #include "gen_kernels.h"
 #include "import_kernels.h"
 #include "kernels.h"
@@ -152,11 +153,15 @@
 
 #define MSMZ_INST_MISC_TE(F, Fr, PFX) MSMZ_INST_MISC_P(F, Fr, TePolicy<F>, PFX)
 
-#define MSMZ_INST_GEN_P(P, PFX)                                                  \
+// the generators, and the fixed-base kernels beside them (fixed_kernels.h)
+#define MSMZ_INST_GEN_P(P, Fr, PFX)                                              \
   PFX template __global__ void k_gen_table<P>(uint32_t*, const uint32_t*);       \
-  PFX template __global__ void k_gen_points<P>(uint32_t*, const uint32_t*, uint32_t, uint64_t, int, GenMap);
-#define MSMZ_INST_GEN(F, Fr, PFX) MSMZ_INST_GEN_P(WeierPolicy<F>, PFX)
-#define MSMZ_INST_GEN_TE(F, Fr, PFX) MSMZ_INST_GEN_P(TePolicy<F>, PFX)
+  PFX template __global__ void k_gen_points<P>(uint32_t*, const uint32_t*, uint32_t, uint64_t, int, GenMap); \
+  PFX template __global__ void k_fixed_table<P>(uint32_t*, const uint32_t*, uint32_t, int); \
+  PFX template __global__ void k_fixed_mul<P, Fr, false>(uint32_t*, const uint32_t*, const uint32_t*, uint32_t, int, int, int, int, uint32_t*); \
+  PFX template __global__ void k_fixed_mul<P, Fr, true>(uint32_t*, const uint32_t*, const uint32_t*, uint32_t, int, int, int, int, uint32_t*);
+#define MSMZ_INST_GEN(F, Fr, PFX) MSMZ_INST_GEN_P(WeierPolicy<F>, Fr, PFX)
+#define MSMZ_INST_GEN_TE(F, Fr, PFX) MSMZ_INST_GEN_P(TePolicy<F>, Fr, PFX)
 
 #define MSMZ_EXTERN extern
 #define MSMZ_DEFINE

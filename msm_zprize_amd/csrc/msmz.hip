@@ -228,6 +228,12 @@ int msmz_points_mul_opts(msmz_ctx* c, const msmz_mul* m, uint64_t n, const msmz_
   return c->engine->points_mul(*m, o, n, h);
 }
 
+int msmz_points_fixed_base(msmz_ctx* c, const msmz_fixed_base* f, uint64_t n, uint64_t* h) {
+  if (!c || !f || !h) return MSMZ_ERR_ARG;
+  if (f->flags || f->scalar_bits < 0 || f->scalar_bits > 256) return MSMZ_ERR_ARG;
+  return c->engine->points_fixed_base(*f, n, h);
+}
+
 int msmz_scalars_combine(msmz_ctx* c, const msmz_scalar_term* x, const msmz_scalar_term* y, uint64_t n, uint64_t first_out,
                          uint64_t* out_handle) {
   return c && x && out_handle ? c->engine->scalars_combine(*x, y, n, first_out, out_handle) : MSMZ_ERR_ARG;
@@ -293,6 +299,31 @@ void msmz_test_scalar_scan_geometry(uint32_t* rec_tile, uint32_t* rec_pass, uint
   if (rec_tile) *rec_tile = SREC_TILE;
   if (rec_pass) *rec_pass = SREC_PASS;
   if (inv_chunk) *inv_chunk = SINV_CHUNK;
+}
+
+int msmz_test_fixed_base_plan(int curve_id, uint64_t n, int bits, int32_t* cc, int32_t* K, uint64_t* entries) {
+  if (!cc || !K || !entries || n == 0 || bits < 0 || bits > 256) return MSMZ_ERR_ARG;
+  auto of = [&](auto cfg) {
+    using Cfg = decltype(cfg);
+    const FixedPlan p = fixed_base_plan(n, fixed_base_bits(bits, Cfg::Fr::BITS), Cfg::TE, 2 * Cfg::F::NW * 4);
+    *cc = p.c;
+    *K = p.K;
+    *entries = p.entries;
+    return (int)MSMZ_OK;
+  };
+  switch (curve_id) {
+    case MSMZ_BLS12_377_G1: return of(CfgBls377{});
+    case MSMZ_PALLAS: return of(CfgPallas{});
+    case MSMZ_BLS12_381_G1: return of(CfgBls381{});
+    case MSMZ_ED_ON_BLS12_377: return of(CfgEd377{});
+    default: return MSMZ_ERR_ARG;
+  }
+}
+int msmz_test_set_fixed_base_window(msmz_ctx* c, int cc) { return c ? c->engine->test_set_fixed_base_window(cc) : MSMZ_ERR_ARG; }
+int msmz_test_fixed_base_tables(msmz_ctx* c, uint64_t* built) {
+  if (!c || !built) return MSMZ_ERR_ARG;
+  *built = c->engine->test_fixed_base_tables();
+  return MSMZ_OK;
 }
 
 int msmz_test_set_glv_bits(msmz_ctx* c, int bits) { return c ? c->engine->test_set_glv_bits(bits) : MSMZ_ERR_ARG; }

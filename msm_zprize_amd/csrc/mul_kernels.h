@@ -1,7 +1,8 @@
 // Per-point scalar multiplication of a resident point set (msmz_points_mul, msmz_points_mul_opts, include/msmz.h;
 // DESIGN.md section 16):
 //     out_i = [s_i] P_i (+ Q_i),   i = 0 .. n-1
-// a NEW point set made from resident ones -- IPA generator folding, SRS re-randomisation, fixed-base vectors.
+// a NEW point set made from resident ones -- IPA generator folding, SRS re-randomisation.  (Fixed-base vectors [s_i]B
+// for one base B: fixed_kernels.h, a window table instead of a chain per point.)
 //
 // The first part of this file is host/device code (MSMZ_HD): the chain [s]P over all or the low `bits` bits, the GLV
 // table and joint chain, the final addition, the choice of chain and the cost models, which

@@ -355,6 +355,36 @@ class MultiEngine : public IEngine {
     });
   }
 
+  // msmz_points_fixed_base: the base becomes bytes once (a resident one: the one record is downloaded from the engine
+  // that holds it; a record at infinity comes back all zero, which is how the engines read it), then every engine
+  // multiplies its own share of the scalars from its own table, and the result is dealt like an upload.
+  int points_fixed_base(const msmz_fixed_base& f, uint64_t n, uint64_t* h) override {
+    if (!h || n == 0) return MSMZ_ERR_ARG;
+    if (f.base_handle ? f.base_xy_le != nullptr : f.base_index != 0) return MSMZ_ERR_ARG;
+    const MHandle* S = get(f.scalars_handle, 1);
+    if (!S || !in_range(f.first_s, n, S->n)) return MSMZ_ERR_ARG;
+    std::vector<uint8_t> xy;
+    if (f.base_handle) {
+      const MHandle* B = get(f.base_handle, 0);
+      if (!B) return MSMZ_ERR_ARG;
+      if (B->factor) return MSMZ_ERR_UNSUPPORTED;
+      if (!in_range(f.base_index, 1, B->n)) return MSMZ_ERR_ARG;
+    }
+    if (f.first_s) return MSMZ_ERR_UNSUPPORTED;
+    if (f.base_handle) {
+      xy.resize(2 * (size_t)fb_);
+      if (int st = download_points(f.base_handle, f.base_index, 1, xy.data(), nullptr)) return st;
+    }
+    return make_set(0, n, h, [&](uint32_t g, IEngine* e, uint64_t cnt, uint64_t* sub) {
+      msmz_fixed_base mine = f;
+      mine.base_handle = 0;
+      mine.base_index = 0;
+      if (!xy.empty()) mine.base_xy_le = xy.data();
+      mine.scalars_handle = S->sub[g];
+      return e->points_fixed_base(mine, cnt, sub);
+    });
+  }
+
   // Every engine combines its own share.  Entry i of every operand and of the destination lives on one device only when
   // all ranges start at 0 (as points_mul), and an existing destination is then written whole: n is its length.
   int scalars_combine(const msmz_scalar_term& x, const msmz_scalar_term* y, uint64_t n, uint64_t first_out,
@@ -474,6 +504,14 @@ class MultiEngine : public IEngine {
   }
   int test_set_limits(uint64_t pass_entries, uint64_t batch_entries) override {
     return on_every([&](IEngine* e) { return e->test_set_limits(pass_entries, batch_entries); });
+  }
+  int test_set_fixed_base_window(int c) override {
+    return on_every([&](IEngine* e) { return e->test_set_fixed_base_window(c); });
+  }
+  uint64_t test_fixed_base_tables() override {
+    uint64_t built = 0;
+    for (Worker* w : workers_) built += w->eng->test_fixed_base_tables();
+    return built;
   }
   void test_passes(uint64_t* range_passes, uint64_t* sub_batches) override {
     uint64_t rp = 0, sb = 0;

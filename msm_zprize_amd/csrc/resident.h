@@ -13,6 +13,7 @@
 #include "../../include/msmz.h"
 #include "kernels.h"
 #include "gen_kernels.h"
+#include "fixed_kernels.h"
 #include "import_kernels.h"
 #include "check_kernels.h"
 #include "mul_kernels.h"
@@ -342,6 +343,65 @@ class ResidentSets : public IEngine {
     });
     return st ? st : add_handle(std::move(hd), h);
   }
+
+  // ------------------------------------------------------------------------------------------ fixed-base multiplication
+  // msmz_points_fixed_base: a new plain point handle, record i = [s_(first_s + i)] B.  The base becomes canonical bytes
+  // (a resident one: one record downloaded), the planner (fixed_base.h) picks the window width for n and the bound, the
+  // table comes from the cache or is built now, and ONE launch of k_fixed_mul makes the points; its error word (a
+  // resident scalar >= q or >= the caller's bound) comes back behind the ONE host wait, like that of msmz_points_mul.
+  int points_fixed_base(const msmz_fixed_base& f, uint64_t n, uint64_t* h) override {
+    if (!h || !points_fit(n)) return MSMZ_ERR_ARG;
+    if (f.base_handle ? f.base_xy_le != nullptr : f.base_index != 0) return MSMZ_ERR_ARG;
+    const uint32_t* S = handles_.range(f.scalars_handle, 1, f.first_s, n, 8);
+    if (!S) return MSMZ_ERR_ARG;
+    FixedKey key{};
+    if (f.base_handle) {
+      const Handle* b = handles_.get(f.base_handle, 0);
+      if (!b) return MSMZ_ERR_ARG;
+      if (b->factor) return MSMZ_ERR_UNSUPPORTED;   // derived data
+      if (!in_range(f.base_index, 1, b->n)) return MSMZ_ERR_ARG;   // (base points only)
+      if (int st = download_points(f.base_handle, f.base_index, 1, reinterpret_cast<uint8_t*>(key.xy), nullptr)) return st;
+    } else if (f.base_xy_le) {
+      memcpy(key.xy, f.base_xy_le, sizeof(key.xy));
+      if (words_geq<NW>(key.xy, F::PW) || words_geq<NW>(key.xy + NW, F::PW)) return MSMZ_ERR_RANGE;
+    } else {
+      Fe<F> g, t;
+      fe_set_const<F>(g, F::GX);
+      fe_from_mont(t, g);
+      fe_to_canon_words<F>(key.xy, t);
+      fe_set_const<F>(g, F::GY);
+      fe_from_mont(t, g);
+      fe_to_canon_words<F>(key.xy + NW, t);
+    }
+    const int bits = fixed_base_bits(f.scalar_bits, Fr::BITS);
+    const FixedPlan plan = fixed_window_ ? fixed_base_plan_forced(fixed_window_, bits, RW * 4)
+                                         : fixed_base_plan(n, bits, TE, RW * 4);
+    if (plan.c == 0) return MSMZ_ERR_ARG;   // (a forced width only: the planner always finds one)
+    key.c = plan.c;
+    key.K = plan.K;
+    MSMZ_HIP(hipSetDevice(device_));
+    const uint32_t* table = nullptr;
+    if (int st = fixed_table(key, plan, &table)) return st;
+    Handle hd;
+    if (int st = new_points(n, &hd)) return st;
+    const dim3 grid((uint32_t)((n + 255) / 256)), block(256);   // whole blocks: every wave reaches the inversion entire
+    const int st = checked([&](uint32_t* d_err) {   // a resident scalar >= group order, or >= 2^bits
+      if (bits == Fr::BITS)
+        hipLaunchKernelGGL((k_fixed_mul<P, Fr, false>), grid, block, 0, stream_, hd.mem.as<uint32_t>(), table, S, (uint32_t)n,
+                           hd.has_endo ? 1 : 0, plan.c, plan.K, bits, d_err);
+      else
+        hipLaunchKernelGGL((k_fixed_mul<P, Fr, true>), grid, block, 0, stream_, hd.mem.as<uint32_t>(), table, S, (uint32_t)n,
+                           hd.has_endo ? 1 : 0, plan.c, plan.K, bits, d_err);
+    });
+    return st ? st : add_handle(std::move(hd), h);
+  }
+
+  int test_set_fixed_base_window(int c) override {
+    if (c != 0 && fixed_base_plan_forced(c, Fr::BITS, RW * 4).c == 0) return MSMZ_ERR_ARG;
+    fixed_window_ = c;
+    return MSMZ_OK;
+  }
+  uint64_t test_fixed_base_tables() override { return fixed_built_; }
 
   // ------------------------------------------------------------------------------------------ scalar-set arithmetic
   // msmz_scalars_combine: out_i = x.c_i x.v_i (+ y.c_i y.v_i) into a new scalar handle or over a range of an existing
@@ -819,6 +879,69 @@ class ResidentSets : public IEngine {
     return MSMZ_OK;
   }
 
+  // The window table of a base (k_fixed_table) from the cache or built now.  The key: the base's canonical words (on the
+  // Weierstrass curves all zero = the point at infinity), the window width and the number of windows.  At most
+  // FIXED_CACHE tables are kept, the one unused longest goes first; all are freed with the engine.
+  static constexpr size_t FIXED_CACHE = 4;
+  struct FixedKey {
+    uint32_t xy[RW];
+    int c, K;
+  };
+  struct FixedTable {
+    FixedKey key;
+    DevBuf mem;
+  };
+  int fixed_table(const FixedKey& key, const FixedPlan& plan, const uint32_t** table) {
+    for (auto it = fixed_cache_.begin(); it != fixed_cache_.end(); ++it) {
+      if (it->key.c == key.c && it->key.K == key.K && !memcmp(it->key.xy, key.xy, sizeof(key.xy))) {
+        FixedTable hit = std::move(*it);   // to the back: the table that leaves is the one unused longest
+        fixed_cache_.erase(it);
+        fixed_cache_.push_back(std::move(hit));
+        *table = fixed_cache_.back().mem.template as<const uint32_t>();
+        return MSMZ_OK;
+      }
+    }
+    // the bases 2^(ck) B on the host (as ensure_gen_table does for G), the multiples on the device; a base that has
+    // reached infinity (B at infinity or of small order) is the all-zero record
+    std::vector<uint32_t> bases((size_t)plan.K * RW, 0);
+    Fe<F> cx, cy, x, y;
+    fe_unpack<F>(cx, key.xy);
+    fe_unpack<F>(cy, key.xy + NW);
+    fe_to_mont(x, cx);
+    fe_to_mont(y, cy);
+    typename P::Acc g, t;
+    if (!TE && words_point_is_inf<F>(key.xy)) P::set_identity(g);
+    else P::from_affine(g, x, y);
+    for (int k = 0; k < plan.K; k++) {
+      if (TE || !fe_is_zero_mod_p(P::denominator(g))) {
+        Fe<F> inv;
+        fe_inverse(inv, P::denominator(g));
+        P::affine_from_inverse(x, y, g, inv);
+        fe_store<F>(bases.data() + (size_t)k * RW, x);
+        fe_store<F>(bases.data() + (size_t)k * RW + NW, y);
+      }
+      for (int j = 0; j < plan.c; j++) {
+        P::dbl(t, g);
+        g = t;
+      }
+    }
+    FixedTable ft;
+    ft.key = key;
+    if (int st = ft.mem.ensure((size_t)plan.entries * RW * 4)) return st;
+    if (int st = stage_.ensure(bases.size() * 4)) return st;
+    MSMZ_HIP(hipMemcpyAsync(stage_.p, bases.data(), bases.size() * 4, hipMemcpyHostToDevice, stream_));
+    hipLaunchKernelGGL((k_fixed_table<P>), dim3((uint32_t)((plan.entries + 255) / 256)), dim3(256), 0, stream_,
+                       ft.mem.template as<uint32_t>(), stage_.as<const uint32_t>(), (uint32_t)plan.entries, plan.c);
+    // (`bases` is pageable: the copy has left it when the call returns; the wait keeps the cache free of a table whose
+    // build failed, and frees the entry that leaves with nothing in flight)
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream_) != hipSuccess) return MSMZ_ERR_HIP;
+    fixed_built_++;
+    if (fixed_cache_.size() == FIXED_CACHE) fixed_cache_.pop_front();
+    fixed_cache_.push_back(std::move(ft));
+    *table = fixed_cache_.back().mem.template as<const uint32_t>();
+    return MSMZ_OK;
+  }
+
   int ensure_gen_table() {
     if (gen_table_.p) return MSMZ_OK;
     int st = gen_table_.ensure((size_t)GEN_WINDOWS * GEN_TABLE * RW * 4);
@@ -864,6 +987,9 @@ class ResidentSets : public IEngine {
   hipEvent_t import_ev_ = nullptr;     // orders stream_ behind the stream that produces an imported device source
   std::vector<uint8_t> import_pack_;   // host packing of a strided host source
   DevBuf gen_table_;
+  std::deque<FixedTable> fixed_cache_;  // points_fixed_base: the window tables of the last FIXED_CACHE (base, c, K)
+  uint64_t fixed_built_ = 0;           // ... the tables built so far, and the forced window width (0 = the planner's)
+  int fixed_window_ = 0;
   DevBuf sdot_;                        // scalars_dot: its result record, then one partial sum per tile
   DevBuf sscan_;                       // scalars_recurrence / _inverse: the result record, then aggregates and incoming values
   DevBuf ntt_scratch_;                 // scalars_ntt: one or two copies of the batch between the passes of a plan

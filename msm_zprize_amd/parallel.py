@@ -17,7 +17,7 @@ include/msmz.h -- this module contains no arithmetic.
 import ctypes as C
 
 from . import _native
-from ._native import MsmzCheckResult, MsmzLog, MsmzMul, MsmzMulOpts, MsmzNtt, MsmzOpts, MsmzScalarRec, MsmzScalarTerm, MsmzSegment, MsmzSrc, lib
+from ._native import MsmzCheckResult, MsmzFixedBase, MsmzLog, MsmzMul, MsmzMulOpts, MsmzNtt, MsmzOpts, MsmzScalarRec, MsmzScalarTerm, MsmzSegment, MsmzSrc, lib
 from ._native import check as _check   # (`check=` is a public keyword of pointsFromBytes / pointsFromTensor)
 
 _state = {"devices": None}
@@ -269,6 +269,19 @@ class _Parallel:
         m = MsmzMul(points.handle, a["firstPoint"], 0 if a["scalar"] is not None else scalars.handle, a["firstScalar"],
                     a["scalar"], 0 if addend is None else addend.handle, a["firstAddend"])
         return _resident(self._c, "points", a["N"], "msmz_points_mul_opts", C.byref(m), a["N"], C.byref(o))
+
+    # -- fixed-base multiplication (msmz_points_fixed_base, include/msmz.h) ---------------------------
+    def fixedBaseMul(self, scalars, base=None, N=None, firstScalar=0, scalarBits=0):
+        """A new resident point array: out[i] = [scalars[firstScalar + i]] B, i < N, for ONE base B -- an SRS
+        [tau^i]G from scalarPowers(tau, N), Pedersen vectors, points with known discrete logs.  `base`: None (the
+        curve's generator), an affine point {x, y, isZero} as msm returns it, or (array, index): a point of a resident
+        point array.  B need not lie in the subgroup.  The result is what mulPoints leaves for N copies of B, from a
+        window table of multiples of B (kept for the next call on the same base) instead of a chain per point.
+        scalarBits = b: every scalar of the range is below 2^b (0 = no bound; a scalar that breaks it fails the call)."""
+        a = fixed_base_args(scalars, base, N, firstScalar, self._c.params["modulus"], self._c.fe_bytes)
+        bits = scalar_bits_arg({"scalarBits": scalarBits}, "fixedBaseMul")
+        f = MsmzFixedBase(a["baseHandle"], a["baseIndex"], a["baseBytes"], scalars.handle, a["firstScalar"], bits, 0)
+        return _resident(self._c, "points", a["N"], "msmz_points_fixed_base", C.byref(f), a["N"])
 
     # -- arithmetic mod q over resident scalar arrays (msmz_scalars_*, include/msmz.h) -----------------
     def combineScalars(self, a, x, b=None, y=None, N=None, firstX=0, firstY=0, out=None, firstOut=0, firstA=0, firstB=0):
@@ -588,6 +601,33 @@ def mul_points_args(scalars, points, N, addend, firstPoint, firstScalar, firstAd
                               ("firstAddend", firstAddend, addend)], N, limit=None)
     return {"N": N, "firstPoint": firstPoint, "firstScalar": firstScalar, "firstAddend": firstAddend,
             "scalar": scalars.to_bytes(32, "little") if broadcast else None}
+
+
+def fixed_base_args(scalars, base, N, firstScalar, field, fe_bytes):
+    """Arguments of fixedBaseMul -> dict(N, firstScalar, baseHandle, baseIndex, baseBytes), checked before anything
+    reaches the device.  baseBytes: x || y of an affine base, little-endian (all zero for isZero: the point at infinity
+    of a Weierstrass curve), None for the generator or a resident base."""
+    if not _is_array(scalars, "scalars"):
+        raise TypeError("fixedBaseMul: `scalars` is a resident scalar array (scalarsFromBytes, scalarPowers, ...)")
+    handle, index, data = 0, 0, None
+    if isinstance(base, tuple):
+        if len(base) != 2 or not _is_array(base[0], "points"):
+            raise TypeError("fixedBaseMul: a resident base is (point array, index); a precomputed array is derived data")
+        if not _is_int(base[1]) or not 0 <= base[1] < len(base[0]):
+            raise ValueError(f"fixedBaseMul: base index {base[1]!r} of a point array of {len(base[0])}")
+        handle, index = base[0].handle, base[1]
+    elif isinstance(base, dict):
+        if not all(k in base for k in ("x", "y")) or not _is_int(base["x"]) or not _is_int(base["y"]):
+            raise TypeError("fixedBaseMul: an affine base is {x, y, isZero} with int coordinates")
+        zero = bool(base.get("isZero", False))
+        for name in ("x", "y"):
+            if not zero and not 0 <= base[name] < field:
+                raise ValueError(f"fixedBaseMul: the base's {name} is not in [0, field modulus)")
+        data = bytes(2 * fe_bytes) if zero else base["x"].to_bytes(fe_bytes, "little") + base["y"].to_bytes(fe_bytes, "little")
+    elif base is not None:
+        raise TypeError("fixedBaseMul: `base` is None (the generator), an affine point {x, y, isZero} or (point array, index)")
+    N = _ranges("fixedBaseMul", [("firstScalar", firstScalar, scalars)], N, limit=None)
+    return {"N": N, "firstScalar": firstScalar, "baseHandle": handle, "baseIndex": index, "baseBytes": data}
 
 
 def mul_points_opts(scalars, scalarBits, subgroup):

@@ -515,6 +515,33 @@ static napi_value MulPoints(napi_env env, napi_callback_info info) {
   return make_handle(env, h);
 }
 
+/* fixedBaseMul(ctx, scalarsHandle, firstScalar, n, base (null = the generator, a Buffer of 2 * fe_bytes = x || y
+   little-endian, or the handle of a resident point array), baseIndex, scalarBits (0 = no bound)) -> handle of a new
+   point set, record i = [s_(firstScalar + i)] B  (msmz_points_fixed_base) */
+static napi_value FixedBaseMul(napi_env env, napi_callback_info info) {
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  msmz_fixed_base f; memset(&f, 0, sizeof(f));
+  uint64_t n, bits, h = 0;
+  if (!get_args(env, info, 7, argv, &ctx) || !get_u64(env, argv[1], &f.scalars_handle) || !get_u64(env, argv[2], &f.first_s) ||
+      !get_u64(env, argv[3], &n) || !get_u64(env, argv[5], &f.base_index) || !get_u64(env, argv[6], &bits) || bits > 256)
+    return BAD_ARG(env, "fixedBaseMul");
+  napi_valuetype t;
+  NAPI_CALL(env, napi_typeof(env, argv[4], &t));
+  void* xy = NULL; size_t len = 0;
+  if (t == napi_null || t == napi_undefined) {
+    /* the generator */
+  } else if (opt_buffer(env, argv[4], &xy, &len)) {
+    if (len != 2 * (size_t)msmz_ctx_fe_bytes(ctx)) return BAD_ARG(env, "fixedBaseMul");
+    f.base_xy_le = (const uint8_t*)xy;
+  } else if (!get_u64(env, argv[4], &f.base_handle) || !f.base_handle) {
+    return BAD_ARG(env, "fixedBaseMul");
+  }
+  f.scalar_bits = (int32_t)bits;
+  int st = msmz_points_fixed_base(ctx, &f, n, &h);
+  if (st) return throw_status(env, st, "msmz_points_fixed_base");
+  return make_handle(env, h);
+}
+
 /* scalarsCombine(ctx, xHandle, xFirst, xCoeff, xCoeffFirst, yHandle (0 = no second term), yFirst, yCoeff, yCoeffFirst, n,
    firstOut, outHandle (0 = a new array)) -> handle of the array written: entry i = xCoeff_i x_i (+ yCoeff_i y_i)
    (msmz_scalars_combine).  A coefficient: a 32-byte Buffer (one scalar for every entry, little-endian), null (1), or
@@ -674,7 +701,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"randomPoints", RandomPoints}, {"randomScalars", RandomScalars}, {"downloadPoints", DownloadPoints},
       {"downloadScalars", DownloadScalars}, {"free", Free}, {"msm", Msm}, {"msmBatch", MsmBatch}, {"msmSegments", MsmSegments},
       {"precomputePoints", PrecomputePoints}, {"precomputedInfo", PrecomputedInfo}, {"checkPoints", CheckPoints},
-      {"mulPoints", MulPoints}, {"scalarsCombine", ScalarsCombine}, {"scalarsDot", ScalarsDot},
+      {"mulPoints", MulPoints}, {"fixedBaseMul", FixedBaseMul}, {"scalarsCombine", ScalarsCombine}, {"scalarsDot", ScalarsDot},
       {"scalarsPowers", ScalarsPowers}, {"scalarsRecurrence", ScalarsRecurrence}, {"scalarsInverse", ScalarsInverse},
       {"scalarsNtt", ScalarsNtt}, {"scalarsRootOfUnity", ScalarsRootOfUnity},
       {"pointAdd", PointAdd}, {"feBytes", FeBytes}};
