@@ -210,6 +210,49 @@ int msmz_import_points(msmz_ctx* ctx, const msmz_src* src, uint64_t n, uint64_t*
  * multi-device context: MSMZ_ERR_UNSUPPORTED, as _into) */
 int msmz_alloc_scalars(msmz_ctx* ctx, uint64_t n, uint64_t* handle);
 
+/* Export: the way out that mirrors the imports.  Entries [first, first + n) of a resident set are
+ * written where the caller wants them, in the form it wants: record i is entry first + i, at ptr + i * stride.  The
+ * descriptor is msmz_src read in the other direction -- the same fields at the same offsets, the same MSMZ_SRC_* flags:
+ *   flags 0               ptr (and is_inf) are host memory; only `width` bytes per record cross PCIe; a strided
+ *                         destination is filled from a packed copy on the host and the bytes between records are not
+ *                         touched.
+ *   MSMZ_SRC_DEVICE       ptr (and is_inf) are memory of the context's GPU, or pinned / registered host memory it can
+ *                         address; the engine asks the runtime, as for a source, about the (n - 1) * stride + width bytes
+ *                         (is_inf: n bytes) it will write, and refuses anything else with MSMZ_ERR_ARG: nothing is
+ *                         launched.  Ordering: `stream` is the stream whose queued work last reads or writes the
+ *                         destination (MSMZ_SRC_DEFAULT_STREAM: the null stream) -- the engine records an event there and
+ *                         its own stream waits for it before the kernel writes.
+ *   MSMZ_SRC_MONTGOMERY   64-bit-limb Montgomery residues: scalars v * 2^256 mod q (width 32 only), coordinates
+ *                         v * 2^(8 fe_bytes) mod p -- the exact inverse of the import.
+ *   MSMZ_SRC_COMPRESSED   points only: one coordinate + sign bit, byte for byte msmz_download_points_compressed
+ *                         (MSMZ_SRC_SIGN_PARITY: its second convention).  Not with MSMZ_SRC_MONTGOMERY.
+ * Every export returns after the GPU has written everything (one host wait, the one that brings the error word): any
+ * stream may read the destination afterwards.
+ * Scalars: little-endian, `width` bytes (4..32, a multiple of 4).  An entry of the range that does not fit `width` bytes,
+ * or is >= q, fails the call with MSMZ_ERR_RANGE (found by the kernel): the addressed records are then unspecified,
+ * nothing outside them is written, the context stays usable.  Entries outside the range are not read.  A host export
+ * with flags 0, width 32 and stride 0 gives byte for byte what msmz_download_scalars gives.
+ * Points: the range rules of msmz_download_points (endomorphism images and the copies of a precomputed handle stay
+ * readable); x || y canonical, Montgomery, or compressed.  Infinity on the Weierstrass curves is the all-zero record in
+ * every form, with is_inf[i] = 1 where is_inf is given; on ed-on-bls12-377 the identity is (0, 1) in the requested form
+ * and is_inf is all 0.  A host export with flags 0 and stride 0 is byte for byte msmz_download_points.
+ * msmz_import_points of an exported buffer with the same flags and its is_inf gives a set that downloads identically.
+ * MSMZ_ERR_ARG, before any launch and with the destination untouched: a null ctx, dst or ptr; n == 0; an unknown handle
+ * or one of the wrong kind; a range beyond the set; every descriptor fault listed for a source above (is_inf on scalars
+ * and the compressed flags on scalars included); memory the runtime does not vouch for.
+ * Multi-device contexts: a host destination works (every engine exports its own blocks of 2^16 records); a device
+ * destination is MSMZ_ERR_UNSUPPORTED. */
+typedef struct msmz_dst {
+  void* ptr;         /* first record */
+  uint64_t stride;   /* bytes from one record to the next; 0 = packed (= the width) */
+  uint32_t width;    /* scalars: 4..32, a multiple of 4; points: 0 or 2 * fe_bytes (compressed: 0 or fe_bytes) */
+  uint32_t flags;    /* MSMZ_SRC_* */
+  void* stream;      /* MSMZ_SRC_DEVICE: the hipStream_t whose queued work last reads or writes the destination */
+  uint8_t* is_inf;   /* points only, nullable: one flag byte per point, packed, same memory space as ptr */
+} msmz_dst;
+int msmz_export_scalars(msmz_ctx* ctx, uint64_t handle, uint64_t first, uint64_t n, const msmz_dst* dst);
+int msmz_export_points(msmz_ctx* ctx, uint64_t handle, uint64_t first, uint64_t n, const msmz_dst* dst);
+
 /* The MSM: sum_i scalar_i * point_i over the first n entries.  Scalars either come from a host
  * buffer (copied to the GPU inside the call) or are already resident (scalars_handle).
  * out_xy_le: 2*fe_bytes.  Curve.Parallel.msm / msmUnsafe / msmProjective. */

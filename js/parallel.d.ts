@@ -35,6 +35,12 @@ export interface ParallelApi {
   scalarsFromBytes(bytes: Uint8Array, n?: number): Promise<DeviceArray>;
   /** `width` bytes per scalar on the wire (4..32, a multiple of 4); montgomery: 32-byte records v * 2^256 mod q */
   scalarsFromBytes(bytes: Uint8Array, n: number | undefined, options: { width?: number; montgomery?: boolean }): Promise<DeviceArray>;
+  /** entries [first, first + n) as n * width little-endian bytes (the host route of msmz_export_scalars); a scalar that does
+   * not fit `width` bytes throws with code "6"; montgomery: 32-byte records v * 2^256 mod q in 64-bit limbs */
+  scalarsToBytes(scalars: DeviceArray, options?: { first?: number; n?: number; width?: number; montgomery?: boolean }): Promise<Uint8Array>;
+  /** points [first, first + n) as x || y records (montgomery: coordinates v * 2^(8 feBytes) mod p in 64-bit limbs) and their
+   * infinity flags (the host route of msmz_export_points); a point at infinity is an all-zero record with isInf 1 */
+  pointsToBytes(points: DeviceArray, options?: { first?: number; n?: number; montgomery?: boolean }): Promise<{ records: Uint8Array; isInf: Uint8Array }>;
   /** pointer-style routes of src/parallel.ts:89-133: pointers are numbers in a virtual address space */
   getPointer(size: number): Promise<number>;
   getScalarPointer(size: number): Promise<number>;

@@ -615,6 +615,28 @@ function createCurve(params, kind) {
       if (!(n > 0) || bytes.length < 32 * n) throw Error(`scalarsFromBytes: ${bytes.length} bytes for ${n} scalars`);
       return DeviceArray.make(curve, N.uploadScalars(ctx, Buffer.from(bytes), n), n, "scalars");
     },
+    /** entries [first, first + n) of a resident scalar array as n * width little-endian bytes (msmz_export_scalars, the
+     * host route): only `width` bytes per scalar cross PCIe, and a scalar that does not fit them throws with code "6";
+     * montgomery: 32-byte records v * 2^256 mod q in 64-bit limbs.  The defaults return what Scalar.toBigints reads. */
+    async scalarsToBytes(scalars, { first = 0, n, width = 32, montgomery = false } = {}) {
+      if (!(scalars instanceof DeviceArray) || scalars.kind !== "scalars")
+        throw TypeError("scalarsToBytes: `scalars` is a resident scalar array");
+      n = scanRanges("scalarsToBytes", [["first", first, scalars]], n);
+      if (typeof montgomery !== "boolean") throw TypeError("scalarsToBytes: montgomery is true or false");
+      if (!Number.isInteger(width) || width < 4 || width > 32 || width % 4) throw Error(`scalarsToBytes: width = ${width} (4..32 bytes, a multiple of 4)`);
+      if (montgomery && width !== 32) throw Error(`scalarsToBytes: Montgomery scalars are 32-byte records, not ${width}`);
+      return N.exportScalars(ctx, scalars.handle, first, n, width, montgomery);
+    },
+    /** points [first, first + n) of a resident point array (msmz_export_points, the host route): {records: Buffer of
+     * n * 2 * feBytes (x || y; montgomery: coordinates v * 2^(8 feBytes) mod p in 64-bit limbs), isInf: Buffer of n};
+     * infinity is an all-zero record with flag 1.  pointsFromBytes(records, n, {montgomery, isInf}) reads them back. */
+    async pointsToBytes(points, { first = 0, n, montgomery = false } = {}) {
+      if (!(points instanceof DeviceArray) || points.kind !== "points")
+        throw TypeError("pointsToBytes: `points` is a resident point array (pointsFromBytes / randomPointsFast)");
+      n = scanRanges("pointsToBytes", [["first", first, points]], n, null, 2 ** 31);
+      if (typeof montgomery !== "boolean") throw TypeError("pointsToBytes: montgomery is true or false");
+      return N.exportPoints(ctx, points.handle, first, n, fb, montgomery);
+    },
     /** msm-batched-affine.ts:74-328 with safe additions */
     msm: (scalars, points, n, verbose = false, options) => msmCommon(scalars, points, n, verbose, options, 1, 0),
     /** msm-batched-affine.ts:574-586 */

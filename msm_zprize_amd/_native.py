@@ -35,6 +35,10 @@ class MsmzSrc(C.Structure):   # msmz_src (include/msmz.h): where an imported set
                 ("stream", C.c_void_p), ("is_inf", C.c_void_p)]
 
 
+class MsmzDst(C.Structure):   # msmz_dst (include/msmz.h): msmz_src read in the other direction, where an export goes
+    _fields_ = list(MsmzSrc._fields_)
+
+
 MSMZ_CHECK_CURVE, MSMZ_CHECK_SUBGROUP = 1, 2
 NO_INDEX = (1 << 64) - 1   # msmz_check_result.first_bad: no bad point
 
@@ -138,6 +142,8 @@ EXPORTS = {
     "msmz_download_points_compressed": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_char_p, C.c_char_p,
                                                   C.c_uint32]),
     "msmz_download_scalars": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_char_p]),
+    "msmz_export_scalars": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(MsmzDst)]),
+    "msmz_export_points": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(MsmzDst)]),
     "msmz_free": (C.c_int, [C.c_void_p, C.c_uint64]),
     "msmz_msm": (C.c_int, [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(MsmzOpts), C.c_char_p,
                            C.POINTER(C.c_int), C.POINTER(MsmzLog)]),

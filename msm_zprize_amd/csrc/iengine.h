@@ -2,6 +2,7 @@
 // the multi-device context (MultiEngine, multi.h) both implement, with the two small things its signatures need -- how a
 // device-side generator maps local to global indices, and the checks of an import source that need no device.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include <vector>
 
@@ -22,7 +23,15 @@ struct GenMap {
 // The checks of an import source (msmz_src, include/msmz.h) that need no device: flags, pointer alignment, width and
 // stride.  points: fe_bytes of the curve, 0 for a scalar source.  *width / *stride: the record's bytes and the bytes
 // from one record to the next, defaults resolved.  What the pointer points at is the engine's to ask (ResidentSets::vouch).
-static inline int src_check(const msmz_src* s, int point_fe_bytes, uint32_t* width, uint64_t* stride) {
+// (msmz_dst is msmz_src read in the other direction -- the same fields at the same offsets, asserted here -- so one body
+// checks both: src_check and dst_check below)
+static_assert(sizeof(msmz_dst) == sizeof(msmz_src) && offsetof(msmz_dst, ptr) == offsetof(msmz_src, ptr) &&
+                  offsetof(msmz_dst, stride) == offsetof(msmz_src, stride) && offsetof(msmz_dst, width) == offsetof(msmz_src, width) &&
+                  offsetof(msmz_dst, flags) == offsetof(msmz_src, flags) && offsetof(msmz_dst, stream) == offsetof(msmz_src, stream) &&
+                  offsetof(msmz_dst, is_inf) == offsetof(msmz_src, is_inf),
+              "msmz_dst mirrors msmz_src");
+template <class Desc>
+static inline int desc_check(const Desc* s, int point_fe_bytes, uint32_t* width, uint64_t* stride) {
   if (!s || !s->ptr) return MSMZ_ERR_ARG;
   const uint32_t point_flags = point_fe_bytes ? MSMZ_SRC_COMPRESSED | MSMZ_SRC_SIGN_PARITY : 0u;   // (refused on scalars)
   if (s->flags & ~(uint32_t)(MSMZ_SRC_DEVICE | MSMZ_SRC_MONTGOMERY | MSMZ_SRC_DEFAULT_STREAM | point_flags)) return MSMZ_ERR_ARG;
@@ -45,6 +54,13 @@ static inline int src_check(const msmz_src* s, int point_fe_bytes, uint32_t* wid
   *width = w;
   *stride = s->stride ? s->stride : w;
   return MSMZ_OK;
+}
+static inline int src_check(const msmz_src* s, int point_fe_bytes, uint32_t* width, uint64_t* stride) {
+  return desc_check(s, point_fe_bytes, width, stride);
+}
+// The same checks of an export destination (msmz_dst): the descriptor faults are those of a source.
+static inline int dst_check(const msmz_dst* d, int point_fe_bytes, uint32_t* width, uint64_t* stride) {
+  return desc_check(d, point_fe_bytes, width, stride);
 }
 
 class IEngine {
@@ -69,6 +85,10 @@ class IEngine {
   virtual int download_points_compressed(uint64_t h, uint64_t first, uint64_t count, uint8_t* out, uint8_t* inf,
                                          uint32_t flags) = 0;
   virtual int download_scalars(uint64_t h, uint64_t first, uint64_t count, uint8_t* s) = 0;
+  // msmz_export_scalars / msmz_export_points: entries [first, first + n) into the caller's memory, host or device, in
+  // the form the destination names (the defaults: an engine that has no exports)
+  virtual int export_scalars(uint64_t, uint64_t, uint64_t, const msmz_dst&) { return MSMZ_ERR_UNSUPPORTED; }
+  virtual int export_points(uint64_t, uint64_t, uint64_t, const msmz_dst&) { return MSMZ_ERR_UNSUPPORTED; }
   virtual int free_handle(uint64_t h) = 0;
   // `batch` MSMs over the same first n points (msmz_msm_batch): vector k = resident entries [k n, (k + 1) n), or host
   // buffer entries [k host_stride, k host_stride + n) (host_stride 0 = n); out: batch results, out_inf: batch flags

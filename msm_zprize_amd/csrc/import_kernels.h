@@ -109,15 +109,13 @@ __global__ void __launch_bounds__(256) k_import_points_compressed(uint32_t* out,
 // resident records -> compressed records of F::NW words (the inverse of the above; msmz_download_points_compressed) and
 // one flag byte per point: the point at infinity is the all-zero record with flag 1.  (The flag cannot be read off the
 // bytes: (0, 1) of BLS12-377 compresses to all-zero bytes under the `largest` convention.)
+// (the per-record body, shared with k_export_points of export_kernels.h: w = the compressed record of the resident
+// record at `rec`, -> is it the point at infinity)
 template <class P>
-__global__ void __launch_bounds__(256) k_points_compress(uint32_t* out, uint8_t* inf_out, const uint32_t* in, uint32_t n,
-                                                         int parity) {
+__device__ __forceinline__ bool compress_record(uint32_t* w, const uint32_t* rec, int parity) {
   using F = typename P::F;
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
   Fe<F> x, y;
-  const bool inf = P::load_resident_affine(x, y, in + (size_t)i * P::IN_WORDS);
-  uint32_t w[F::NW];
+  const bool inf = P::load_resident_affine(x, y, rec);
   if (inf) {
 #pragma unroll
     for (int j = 0; j < F::NW; j++) w[j] = 0;
@@ -129,6 +127,17 @@ __global__ void __launch_bounds__(256) k_points_compress(uint32_t* out, uint8_t*
     fe_to_canon_words<F>(w, t);
     if (fe_wire_sign<F>(&zero, P::TE ? x : y, parity)) w[F::NW - 1] |= 0x80000000u;   // (the value 0 has sign 0)
   }
+  return inf;
+}
+
+template <class P>
+__global__ void __launch_bounds__(256) k_points_compress(uint32_t* out, uint8_t* inf_out, const uint32_t* in, uint32_t n,
+                                                         int parity) {
+  using F = typename P::F;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t w[F::NW];
+  const bool inf = compress_record<P>(w, in + (size_t)i * P::IN_WORDS, parity);
   uint32_t* o = out + (size_t)i * F::NW;
 #pragma unroll
   for (int j = 0; j < F::NW; j += 4) *reinterpret_cast<uint4*>(o + j) = make_uint4(w[j], w[j + 1], w[j + 2], w[j + 3]);

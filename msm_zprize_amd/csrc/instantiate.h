@@ -3,6 +3,7 @@
 // `extern template` declarations.
 #pragma once
 #include "check_kernels.h"
+#include "export_kernels.h"
 #include "fixed_kernels.h"
 #include "gen_kernels.h"
 #include "import_kernels.h"
@@ -111,6 +112,7 @@
   PFX template __global__ void k_check_scalars<Fr>(uint32_t*, const uint32_t*, uint32_t);                         \
   PFX template __global__ void k_gen_scalars<Fr>(uint32_t*, uint32_t, uint64_t, GenMap);                          \
   PFX template __global__ void k_import_scalars<Fr>(uint32_t*, const uint8_t*, uint64_t, int, uint32_t, int, uint32_t*); \
+  PFX template __global__ void k_export_scalars<Fr>(uint8_t*, uint64_t, int, const uint32_t*, uint32_t, int, uint32_t*); \
   PFX template __global__ void k_scalars_combine<Fr>(uint32_t*, ScalarTerm, ScalarTerm, uint32_t, uint32_t*);     \
   PFX template __global__ void k_scalars_dot<Fr>(uint32_t*, const uint32_t*, const uint32_t*, uint32_t, uint32_t*); \
   PFX template __global__ void k_scalars_dot_fold<Fr>(uint32_t*, const uint32_t*, uint32_t, int);                 \
@@ -133,6 +135,7 @@
   PFX template __global__ void k_import_points<P>(uint32_t*, const uint8_t*, uint64_t, const uint8_t*, uint32_t, int, int, uint32_t*); \
   PFX template __global__ void k_import_points_compressed<P>(uint32_t*, const uint8_t*, uint64_t, const uint8_t*, uint32_t, int, int, uint32_t*); \
   PFX template __global__ void k_points_compress<P>(uint32_t*, uint8_t*, const uint32_t*, uint32_t, int);         \
+  PFX template __global__ void k_export_points<P>(uint8_t*, uint64_t, uint8_t*, const uint32_t*, uint32_t, int); \
   PFX template __global__ void k_check_curve<P>(uint8_t*, CheckResult*, const uint32_t*, uint32_t, uint32_t);     \
   PFX template __global__ void k_check_subgroup<P, Fr>(uint8_t*, CheckResult*, const uint32_t*, uint32_t, uint32_t); \
   PFX template __global__ void k_points_mul<P, Fr, false>(uint32_t*, const uint32_t*, const uint32_t*, MulScalar, const uint32_t*, uint32_t, int, int, uint32_t*); \

@@ -165,6 +165,12 @@ int msmz_download_points_compressed(msmz_ctx* c, uint64_t h, uint64_t first, uin
 int msmz_download_scalars(msmz_ctx* c, uint64_t h, uint64_t first, uint64_t count, uint8_t* s) {
   return c ? c->engine->download_scalars(h, first, count, s) : MSMZ_ERR_ARG;
 }
+int msmz_export_scalars(msmz_ctx* c, uint64_t h, uint64_t first, uint64_t n, const msmz_dst* d) {
+  return c && d ? c->engine->export_scalars(h, first, n, *d) : MSMZ_ERR_ARG;
+}
+int msmz_export_points(msmz_ctx* c, uint64_t h, uint64_t first, uint64_t n, const msmz_dst* d) {
+  return c && d ? c->engine->export_points(h, first, n, *d) : MSMZ_ERR_ARG;
+}
 int msmz_free(msmz_ctx* c, uint64_t h) { return c ? c->engine->free_handle(h) : MSMZ_ERR_ARG; }
 
 int msmz_msm(msmz_ctx* c, uint64_t ph, const uint8_t* scalars, uint64_t n, const msmz_opts* o, uint8_t* out,

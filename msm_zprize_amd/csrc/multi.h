@@ -200,6 +200,15 @@ class MultiEngine : public IEngine {
     });
   }
 
+  // msmz_export_scalars / _points to a host destination: every engine exports its own blocks to
+  // ptr + (global index - first) * stride, as the downloads do.  A device destination is refused.
+  int export_scalars(uint64_t hd, uint64_t first, uint64_t n, const msmz_dst& d) override {
+    return export_any(hd, 1, 0, first, n, d);
+  }
+  int export_points(uint64_t hd, uint64_t first, uint64_t n, const msmz_dst& d) override {
+    return export_any(hd, 0, fb_, first, n, d);
+  }
+
   int free_handle(uint64_t hd) override {
     auto it = handles_.find(hd);
     if (it == handles_.end()) return MSMZ_ERR_ARG;
@@ -539,6 +548,22 @@ class MultiEngine : public IEngine {
     return make_set(point_fe_bytes ? 0 : 1, n, h, [&](uint32_t g, IEngine* e, uint64_t cnt, uint64_t* sub) {
       const GenMap split{G_, g, MULTI_BLOCK_SHIFT};
       return point_fe_bytes ? e->import_points(hs, cnt, sub, &split) : e->import_scalars(hs, cnt, sub, &split);
+    });
+  }
+
+  int export_any(uint64_t hd, int kind, int point_fe_bytes, uint64_t first, uint64_t n, const msmz_dst& d) {
+    uint32_t width = 0;
+    uint64_t stride = 0;
+    if (int st = dst_check(&d, point_fe_bytes, &width, &stride)) return st;
+    const MHandle* set = range(hd, kind, first, n);
+    if (!set || n == 0) return MSMZ_ERR_ARG;
+    if (d.flags & MSMZ_SRC_DEVICE) return MSMZ_ERR_UNSUPPORTED;
+    return for_range(*set, first, n, [&](IEngine* e, uint64_t sub, uint64_t li, uint64_t gi, uint64_t len) {
+      msmz_dst piece = d;
+      piece.ptr = (uint8_t*)d.ptr + (gi - first) * stride;
+      piece.stride = stride;
+      piece.is_inf = d.is_inf ? d.is_inf + (gi - first) : nullptr;
+      return kind ? e->export_scalars(sub, li, len, piece) : e->export_points(sub, li, len, piece);
     });
   }
 

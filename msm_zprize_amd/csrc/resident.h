@@ -15,6 +15,7 @@
 #include "gen_kernels.h"
 #include "fixed_kernels.h"
 #include "import_kernels.h"
+#include "export_kernels.h"
 #include "check_kernels.h"
 #include "mul_kernels.h"
 #include "scalar_kernels.h"
@@ -253,6 +254,44 @@ class ResidentSets : public IEngine {
     MSMZ_HIP(hipSetDevice(device_));
     MSMZ_HIP(hipMemcpy(s, src, count * 32, hipMemcpyDeviceToHost));
     return MSMZ_OK;
+  }
+
+  // ------------------------------------------------------------------------------------------ exports
+  // msmz_export_scalars: entries [first, first + n) of a scalar set, `width` bytes each, where the destination says.
+  // One launch (k_export_scalars); its error word (an entry >= q, or one that does not fit the width) comes back behind
+  // the ONE host wait, after which everything has been written.
+  int export_scalars(uint64_t hd, uint64_t first, uint64_t n, const msmz_dst& d) override {
+    ExportView v;
+    if (int st = dst_check(&d, 0, &v.width, &v.stride)) return st;
+    const uint32_t* src = handles_.range(hd, 1, first, n, 8);
+    if (!src || n == 0 || n >> 32) return MSMZ_ERR_ARG;
+    MSMZ_HIP(hipSetDevice(device_));
+    if (int st = export_view(d, n, &v)) return st;
+    return export_run(d, n, v, [&](uint32_t* d_err) {
+      hipLaunchKernelGGL((k_export_scalars<Fr>), dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream_, v.ptr, v.stride,
+                         (int)(v.width / 4), src, (uint32_t)n, (d.flags & MSMZ_SRC_MONTGOMERY) ? 1 : 0, d_err);
+    });
+  }
+
+  // msmz_export_points: records [first, first + n) of a point set under the range rules of download_points, as x || y
+  // (canonical or Montgomery) or compressed, with the flag bytes if the destination has room for them.  One launch
+  // (k_export_points); no kernel raises an error bit here, the fetch of the error word is the host wait.
+  int export_points(uint64_t hd, uint64_t first, uint64_t n, const msmz_dst& d) override {
+    ExportView v;
+    if (int st = dst_check(&d, FE_BYTES, &v.width, &v.stride)) return st;
+    const Handle* pts = handles_.get(hd, 0);
+    if (!pts || n == 0) return MSMZ_ERR_ARG;
+    // the endomorphism images stay readable; a precomputed set: all its copies
+    const uint64_t have = pts->factor ? pts->copy_stride * pts->factor : pts->n * (pts->has_endo ? 2 : 1);
+    if (!in_range(first, n, have)) return MSMZ_ERR_ARG;
+    MSMZ_HIP(hipSetDevice(device_));
+    if (int st = export_view(d, n, &v)) return st;
+    const uint32_t* recs = pts->mem.template as<const uint32_t>() + first * PW_WORDS;
+    const int form = (int)(d.flags & (MSMZ_SRC_MONTGOMERY | MSMZ_SRC_COMPRESSED | MSMZ_SRC_SIGN_PARITY));
+    return export_run(d, n, v, [&](uint32_t*) {
+      hipLaunchKernelGGL((k_export_points<P>), dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream_, v.ptr, v.stride,
+                         v.is_inf, recs, (uint32_t)n, form);
+    });
   }
 
   int free_handle(uint64_t hd) override {
@@ -831,6 +870,69 @@ class ResidentSets : public IEngine {
     });
   }
 
+  // where the export kernel writes: the caller's device memory, or the packed staging records of a host destination
+  struct ExportView {
+    uint8_t* ptr = nullptr;
+    uint64_t stride = 0;
+    uint32_t width = 0;
+    uint8_t* is_inf = nullptr;
+  };
+
+  // import_view mirrored (the descriptor has passed dst_check, which filled width and stride).  Device destination: the
+  // pointers are vouched for -- the (n - 1) * stride + width bytes the kernel will write, n flag bytes -- and stream_
+  // waits for an event recorded on the stream that last touches the destination (no host wait); the kernel writes in
+  // place.  Host destination: the kernel writes packed records into stage_, the flag bytes behind them.
+  int export_view(const msmz_dst& d, uint64_t n, ExportView* v) {
+    if (d.flags & MSMZ_SRC_DEVICE) {
+      const void* dp = nullptr;
+      int st;
+      if ((st = vouch(d.ptr, (n - 1) * v->stride + v->width, false, &dp))) return st;
+      v->ptr = (uint8_t*)dp;
+      if (d.is_inf) {
+        if ((st = vouch(d.is_inf, n, false, &dp))) return st;
+        v->is_inf = (uint8_t*)dp;
+      }
+      if (d.stream || (d.flags & MSMZ_SRC_DEFAULT_STREAM)) {
+        MSMZ_HIP(hipEventRecord(import_ev_, (hipStream_t)d.stream));
+        MSMZ_HIP(hipStreamWaitEvent(stream_, import_ev_, 0));
+      }
+      return MSMZ_OK;
+    }
+    if (int st = stage_.ensure((size_t)n * v->width + n)) return st;
+    v->ptr = stage_.as<uint8_t>();
+    v->stride = v->width;   // (the caller's stride is the host scatter's: export_run)
+    if (d.is_inf) v->is_inf = v->ptr + (size_t)n * v->width;
+    return MSMZ_OK;
+  }
+
+  // the export kernel over a view, then the way home of a host destination -- ONE device-to-host copy of the packed
+  // records (and flag bytes), straight into a packed destination without flags, else into a host landing from which the
+  // records are scattered at the caller's stride (bytes between records are not touched) -- behind the error-word fetch
+  // of checked(): when it returns everything has been written.  After an error nothing is scattered.
+  template <class Launch>
+  int export_run(const msmz_dst& d, uint64_t n, const ExportView& v, Launch launch) {
+    const bool host = !(d.flags & MSMZ_SRC_DEVICE);
+    const size_t w = v.width, bytes = (size_t)n * w + (d.is_inf ? n : 0);
+    const uint64_t stride = d.stride ? d.stride : w;
+    const bool direct = host && stride == w && !d.is_inf;
+    if (host && !direct) import_pack_.resize(bytes);
+    hipError_t copied = hipSuccess;
+    const int st = checked([&](uint32_t* d_err) {
+      launch(d_err);
+      if (host) copied = hipMemcpyAsync(direct ? d.ptr : (void*)import_pack_.data(), stage_.p, bytes, hipMemcpyDeviceToHost, stream_);
+    });
+    if (st) return st;
+    if (copied != hipSuccess) return MSMZ_ERR_HIP;
+    if (host && !direct) {
+      uint8_t* out = (uint8_t*)d.ptr;
+      if (stride == w) memcpy(out, import_pack_.data(), (size_t)n * w);
+      else
+        for (uint64_t i = 0; i < n; i++) memcpy(out + i * stride, import_pack_.data() + i * w, w);
+      if (d.is_inf) memcpy(d.is_inf, import_pack_.data() + (size_t)n * w, n);
+    }
+    return MSMZ_OK;
+  }
+
   // a table of powers (ntt_kernels.h) into device memory, queued on stream_: k_scalars_powers from the spec's base
   void ntt_fill(uint32_t* dst, const NttTableSpec& s) {
     FrPowTable table;
@@ -984,8 +1086,8 @@ class ResidentSets : public IEngine {
   PinnedBuf h_res_;                    // pinned landing of a result record here, of the window results of an MSM
 
  private:
-  hipEvent_t import_ev_ = nullptr;     // orders stream_ behind the stream that produces an imported device source
-  std::vector<uint8_t> import_pack_;   // host packing of a strided host source
+  hipEvent_t import_ev_ = nullptr;     // orders stream_ behind the stream that produces an imported device source (or last touches an export's destination)
+  std::vector<uint8_t> import_pack_;   // host packing of a strided host source; the packed landing of a host export
   DevBuf gen_table_;
   std::deque<FixedTable> fixed_cache_;  // points_fixed_base: the window tables of the last FIXED_CACHE (base, c, K)
   uint64_t fixed_built_ = 0;           // ... the tables built so far, and the forced window width (0 = the planner's)

@@ -240,6 +240,95 @@ class _Parallel:
         view["form"] = form
         return _resident(self._c, "points", view["n"], "msmz_import_points", C.byref(self._src(view)), view["n"])
 
+    # -- exports: resident data into the caller's memory, in the form it wants (msmz_export_*, include/msmz.h) --------
+    def _dst(self, view):
+        s = self._src(view)   # (msmz_dst is msmz_src read in the other direction: the same fields and flags)
+        return _native.MsmzDst(s.ptr, s.stride, s.width, s.flags, s.stream, s.is_inf)
+
+    def _host_export(self, name, arr, first, N, rec, flags, want_inf):
+        """msmz_export_<name> of entries [first, first + N) into fresh host buffers -> (N * rec bytes, N flag bytes or None)"""
+        buf = C.create_string_buffer(rec * N)
+        inf = C.create_string_buffer(N) if want_inf else None
+        dst = _native.MsmzDst(C.addressof(buf), 0, rec, flags, None, C.addressof(inf) if want_inf else None)
+        _check(getattr(lib(), name)(self._c._ctx, arr.handle, first, N, C.byref(dst)), name)
+        return buf.raw, inf.raw if want_inf else None
+
+    def scalarsToBytes(self, scalars, first=0, N=None, width=32, montgomery=False):
+        """Entries [first, first + N) of a resident scalar array as N * width little-endian bytes (msmz_export_scalars, the
+        host route): only `width` bytes per scalar cross PCIe, and a scalar that does not fit them raises MsmzError
+        (MSMZ_ERR_RANGE).  montgomery=True: 32-byte records v * 2^256 mod q in 64-bit limbs.  The defaults return what
+        Scalar.toBigints reads."""
+        first, N = export_range_args(scalars, "scalars", first, N, "scalarsToBytes")
+        width = scalar_width_arg(width, montgomery, "scalarsToBytes")
+        flags = _native.MSMZ_SRC_MONTGOMERY if montgomery else 0
+        return self._host_export("msmz_export_scalars", scalars, first, N, width, flags, False)[0]
+
+    def pointsToBytes(self, points, first=0, N=None, montgomery=False):
+        """Points [first, first + N) of a resident point array -> (N * 2 * fe_bytes bytes x || y, N flag bytes)
+        (msmz_export_points, the host route).  montgomery=True: coordinates v * 2^(8 fe_bytes) mod p in 64-bit limbs,
+        what pointsFromBytes(..., montgomery=True, is_inf=flags) reads back.  A point at infinity is an all-zero record
+        with flag 1."""
+        first, N = export_range_args(points, "points", first, N, "pointsToBytes")
+        if not isinstance(montgomery, bool):
+            raise TypeError("pointsToBytes: `montgomery` is a bool")
+        flags = _native.MSMZ_SRC_MONTGOMERY if montgomery else 0
+        return self._host_export("msmz_export_points", points, first, N, 2 * self._c.fe_bytes, flags, True)
+
+    def _new_tensor(self, who, shape):
+        import torch   # (only here and in tensor_view: the package imports without torch)
+        if len(self._c.devices) != 1:
+            raise ValueError(f"{who}: a context of {len(self._c.devices)} devices exports to host memory only; pass a CPU "
+                             f"tensor as `out`")
+        return torch.empty(shape, dtype=torch.uint8, device=f"cuda:{self._c.devices[0]}")
+
+    def scalarsToTensor(self, scalars, out=None, first=0, N=None, width=32, montgomery=False):
+        """Entries [first, first + N) of a resident scalar array into a torch tensor, written where it lies
+        (msmz_export_scalars) -> the tensor.  `out`: any tensor scalarsFromTensor reads -- 2-D (n, k) with a contiguous
+        last dimension (k * itemsize = the record's bytes, 4..32) and possibly strided rows, or 1-D of an 8-byte dtype --
+        on the context's GPU (written there, ordered after the work queued on torch's current stream; nothing passes
+        through the host) or on the CPU (the host route: `width` bytes per scalar cross PCIe); N=None: as many entries as
+        `out` has rows; bytes between strided rows are not touched.  out=None: a new (N, width) uint8 tensor on the
+        context's GPU; `width` names the record of that tensor only, an `out` brings its own.  A scalar that does not
+        fit the record raises MsmzError (MSMZ_ERR_RANGE).  montgomery=True: 32-byte records v * 2^256 mod q in 64-bit
+        limbs, what scalarsFromTensor(..., montgomery=True) reads.  The call returns when the GPU has written everything:
+        any stream may read the tensor.  torch is imported before this package loads its library, as for
+        scalarsFromTensor."""
+        who = "scalarsToTensor"
+        if out is None:
+            first, N = export_range_args(scalars, "scalars", first, N, who)
+            width = scalar_width_arg(width, montgomery, who)
+            out = self._new_tensor(who, (N, width))
+        view = export_tensor_view(scalars, "scalars", out, first, N, self._c.devices, self._c.fe_bytes, montgomery, who)
+        _check(lib().msmz_export_scalars(self._c._ctx, scalars.handle, first, view["n"], C.byref(self._dst(view))),
+               "msmz_export_scalars")
+        return out
+
+    def pointsToTensor(self, points, out=None, first=0, N=None, montgomery=False, compressed=False, sign="largest",
+                       is_inf=None):
+        """Points [first, first + N) of a resident point array into a torch tensor of rows of 2 * fe_bytes bytes (x || y;
+        montgomery=True: coordinates v * 2^(8 fe_bytes) mod p) or, compressed=True, of fe_bytes bytes (one coordinate
+        and a sign bit, `sign` as in toCompressedBytes), written where the tensor lies (msmz_export_points).  `out`: as
+        pointsFromTensor reads it, GPU or CPU, rows possibly strided; None: a new uint8 tensor on the context's GPU.
+        is_inf: a contiguous 1-D one-byte tensor on the same device that receives the infinity flags, or True: one is
+        made.  -> the tensor, or (tensor, flags) when is_inf is given.  pointsFromTensor(tensor, ..., is_inf=flags) with
+        the same form reads the set back."""
+        who = "pointsToTensor"
+        form = compressed_arg(compressed, sign, montgomery, who)
+        if out is None:
+            first, N = export_range_args(points, "points", first, N, who)
+            out = self._new_tensor(who, (N, self._c.fe_bytes * (1 if compressed else 2)))
+        if is_inf is True:
+            import torch
+            is_inf = torch.empty((int(out.shape[0]),), dtype=torch.uint8, device=out.device)
+        elif is_inf is False:
+            is_inf = None
+        view = export_tensor_view(points, "points", out, first, N, self._c.devices, self._c.fe_bytes, montgomery, who,
+                                  is_inf, compressed)
+        view["form"] = form
+        _check(lib().msmz_export_points(self._c._ctx, points.handle, first, view["n"], C.byref(self._dst(view))),
+               "msmz_export_points")
+        return out if is_inf is None else (out, is_inf)
+
     # -- validation (msmz_check_points, include/msmz.h) ---------------------------------------------
     def checkPoints(self, points, N=None, subgroup=True, first=0, verdicts=False):
         """Are points [first, first + N) of a resident point array on the curve and (subgroup=True) in the subgroup of
@@ -1011,6 +1100,28 @@ def tensor_view(t, devices, kind, fe_bytes, montgomery, who, is_inf=None, compre
     if on_gpu:
         import torch
         view["stream"] = int(torch.cuda.current_stream(t.device).cuda_stream)
+    return view
+
+
+def export_range_args(arr, kind, first, N, who):
+    """Entries [first, first + N) of a resident array of `kind` ("scalars" / "points"), N=None: to its end -> (first, N),
+    through the range checks every operation over resident arrays shares (_ranges)."""
+    if not _is_array(arr, kind):
+        raise TypeError(f"{who}: `{kind}` is a resident {kind[:-1]} array")
+    return first, _ranges(who, [("first", first, arr)], N, limit=1 << 32 if kind == "scalars" else None)
+
+
+def export_tensor_view(arr, kind, out, first, N, devices, fe_bytes, montgomery, who, is_inf=None, compressed=False):
+    """The arguments of an export into the tensor `out`, checked before anything reaches the device: `out` as tensor_view
+    accepts it, the range as export_range_args (N=None: as many entries as `out` has rows), and `out` has a row for every
+    entry.  -> the dict of tensor_view with n = N."""
+    if not _is_array(arr, kind):
+        raise TypeError(f"{who}: `{kind}` is a resident {kind[:-1]} array")
+    view = tensor_view(out, devices, kind, fe_bytes, montgomery, who, is_inf, compressed=compressed)
+    first, N = export_range_args(arr, kind, first, view["n"] if N is None else N, who)
+    if N > view["n"]:
+        raise ValueError(f"{who}: {N} entries into a tensor of {view['n']} rows")
+    view["n"] = N
     return view
 
 

@@ -285,6 +285,44 @@ static napi_value DownloadScalars(napi_env env, napi_callback_info info) {
   return buf;
 }
 
+/* exportScalars(ctx, handle, first, count, width, montgomery) -> Buffer(count * width): msmz_export_scalars on the host
+ * route (N-API has no device pointers); a scalar that does not fit `width` bytes is MSMZ_ERR_RANGE */
+static napi_value ExportScalars(napi_env env, napi_callback_info info) {
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  uint64_t h, first, count, width; bool mont = false;
+  if (!get_args(env, info, 6, argv, &ctx) || !get_u64(env, argv[1], &h) || !get_u64(env, argv[2], &first) ||
+      !get_u64(env, argv[3], &count) || !get_u64(env, argv[4], &width) || napi_get_value_bool(env, argv[5], &mont) != napi_ok ||
+      width < 4 || width > 32 || count == 0 || count >> 32)
+    return BAD_ARG(env, "exportScalars");
+  void* data; napi_value buf;
+  NAPI_CALL(env, napi_create_buffer(env, (size_t)width * (size_t)count, &data, &buf));
+  msmz_dst dst = {data, 0, (uint32_t)width, mont ? MSMZ_SRC_MONTGOMERY : 0u, NULL, NULL};
+  int st = msmz_export_scalars(ctx, h, first, count, &dst);
+  if (st) return throw_status(env, st, "msmz_export_scalars");
+  return buf;
+}
+
+/* exportPoints(ctx, handle, first, count, feBytes, montgomery) -> {records: Buffer(count * 2 * feBytes), isInf: Buffer(count)}:
+ * msmz_export_points on the host route, x || y canonical or as 64-bit-limb Montgomery residues */
+static napi_value ExportPoints(napi_env env, napi_callback_info info) {
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  uint64_t h, first, count; bool mont = false;
+  if (!get_args(env, info, 6, argv, &ctx) || !get_u64(env, argv[1], &h) || !get_u64(env, argv[2], &first) ||
+      !get_u64(env, argv[3], &count) || !is_fe_bytes(env, argv[4], msmz_ctx_fe_bytes(ctx)) ||
+      napi_get_value_bool(env, argv[5], &mont) != napi_ok || count == 0 || count >> 31)
+    return BAD_ARG(env, "exportPoints");
+  void *data, *flags; napi_value rec, inf, out;
+  NAPI_CALL(env, napi_create_buffer(env, 2 * (size_t)msmz_ctx_fe_bytes(ctx) * (size_t)count, &data, &rec));
+  NAPI_CALL(env, napi_create_buffer(env, (size_t)count, &flags, &inf));
+  msmz_dst dst = {data, 0, 0, mont ? MSMZ_SRC_MONTGOMERY : 0u, NULL, (uint8_t*)flags};
+  int st = msmz_export_points(ctx, h, first, count, &dst);
+  if (st) return throw_status(env, st, "msmz_export_points");
+  NAPI_CALL(env, napi_create_object(env, &out));
+  NAPI_CALL(env, napi_set_named_property(env, out, "records", rec));
+  NAPI_CALL(env, napi_set_named_property(env, out, "isInf", inf));
+  return out;
+}
+
 static napi_value Free(napi_env env, napi_callback_info info) {
   napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
   uint64_t h;
@@ -699,7 +737,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"importScalars", ImportScalars}, {"importPoints", ImportPoints},
       {"importPointsCompressed", ImportPointsCompressed}, {"downloadPointsCompressed", DownloadPointsCompressed},
       {"randomPoints", RandomPoints}, {"randomScalars", RandomScalars}, {"downloadPoints", DownloadPoints},
-      {"downloadScalars", DownloadScalars}, {"free", Free}, {"msm", Msm}, {"msmBatch", MsmBatch}, {"msmSegments", MsmSegments},
+      {"downloadScalars", DownloadScalars}, {"exportScalars", ExportScalars}, {"exportPoints", ExportPoints}, {"free", Free}, {"msm", Msm}, {"msmBatch", MsmBatch}, {"msmSegments", MsmSegments},
       {"precomputePoints", PrecomputePoints}, {"precomputedInfo", PrecomputedInfo}, {"checkPoints", CheckPoints},
       {"mulPoints", MulPoints}, {"fixedBaseMul", FixedBaseMul}, {"scalarsCombine", ScalarsCombine}, {"scalarsDot", ScalarsDot},
       {"scalarsPowers", ScalarsPowers}, {"scalarsRecurrence", ScalarsRecurrence}, {"scalarsInverse", ScalarsInverse},

@@ -243,7 +243,9 @@ def field_struct(name, p, nwords, N, W, extra=(), rng=None):
            iarr("P4", limbs_w(4 * p, N, W)),
            # imported 64-bit-limb Montgomery coordinates v * R_std, R_std = 2^(32 nwords): one product with
            # R^2 / R_std takes them to v * R, as R2 takes canonical ones
-           iarr("R2STD", limbs_w(R * R * pow(1 << (32 * nwords), -1, p) % p, N, W))]
+           iarr("R2STD", limbs_w(R * R * pow(1 << (32 * nwords), -1, p) % p, N, W)),
+           # ... and the way out (export_kernels.h): one product of a resident v * R with R_std leaves v * R_std
+           iarr("RSTD", limbs_w((1 << (32 * nwords)) % p, N, W))]
     for nm, val in extra:
         out.append(iarr(nm, limbs_w(val * R % p, N, W)))
     # square roots (sqrt.h) and the sign of a compressed coordinate
