@@ -608,6 +608,82 @@ int msmz_scalars_ntt(msmz_ctx* ctx, const msmz_ntt* t, uint64_t first_out, uint6
  * curve or a null pointer; MSMZ_ERR_UNSUPPORTED: log_n > S */
 int msmz_scalars_root_of_unity(int curve_id, uint32_t log_n, uint8_t* out_le32);
 
+/* Multilinear polynomials over resident scalar sets: eq tables, evaluation, binding one variable
+ * and the round polynomial of a sumcheck, so that a Spartan / HyperPlonk / GKR prover or a multilinear opening keeps its
+ * tables on the device between its MSMs.  The reference has no analogue.
+ *
+ * Conventions.  A multilinear polynomial in v variables is a range of n = 2^v entries of a scalar handle; entry i is
+ * f(b_0, .., b_(v-1)) with i = sum_j b_j 2^j, so variable 0 is the lowest index bit.  v <= 31 (a set has fewer than 2^32
+ * entries); v = 0 is a constant.  eq(r, i) = prod_j (b_j r_j + (1 - b_j)(1 - r_j)).  Points and challenges are 32-byte
+ * little-endian values below q from the host, a point of v variables v of them in a row, r_0 first.  Everything written
+ * is below q; sums are exact mod q, so two calls return the same bytes whatever the order of the reduction.
+ *
+ * msmz_scalars_eq_table: a new scalar handle of 2^n_vars entries, entry i = scale * eq(r, i) (scale NULL = 1).
+ * n_vars == 0 gives one entry equal to scale, and point_le32 may then be NULL.
+ *
+ * msmz_scalars_mle_eval: f(r) = sum_i f_i eq(r, i) over entries [first, first + 2^n_vars) of `handle`, as 32 bytes.  The
+ * table is not materialised; the bytes are those of msmz_scalars_dot against msmz_scalars_eq_table(r).
+ *
+ * msmz_scalars_mle_bind: binds one variable of `count` tables to r.  Input table k is entries [first + k 2^v,
+ * first + (k + 1) 2^v) of `handle`, output table k entries [first_out + k 2^(v-1), first_out + (k + 1) 2^(v-1)).
+ *   default (the high variable, v - 1):   out_i = f_i + r (f_(i+h) - f_i),  h = 2^(v-1)
+ *   MSMZ_MLE_LOW (variable 0):            out_i = f_(2i) + r (f_(2i+1) - f_(2i))      (arkworks' fix_variables order)
+ * One Montgomery product per output.  *out_handle == 0 makes a new handle of count 2^(v-1) entries (first_out must be 0);
+ * otherwise only the destination range is written.  With count == 1 and the high variable the destination may be
+ * exactly the low half of the source, [first, first + h) of the same handle (in place), or disjoint from the whole
+ * source.  Every other overlap of the destination with the source is MSMZ_ERR_ARG: any with MSMZ_MLE_LOW or count > 1,
+ * the high half, a partial overlap with either half.
+ *
+ * msmz_scalars_sumcheck_round: with tables f_0 .. f_(n_tables-1), each 2^v entries from tables[j].first of
+ * tables[j].handle, and terms T = (c_T, mask_T), bit j of the mask making f_j a factor ("a list of products of
+ * multilinear polynomials"; Spartan's eq (A B - C) is two terms over four tables), d = the largest popcount of a mask:
+ *   g(t) = sum_(i < 2^(v-1)) sum_T c_T prod_(j in T) ((1 - t) f_j[lo(i)] + t f_j[hi(i)]),   t = 0 .. d
+ * with (lo, hi) = (i, i + 2^(v-1)): the round sums out the high variable; MSMZ_MLE_LOW: (2i, 2i + 1), variable 0.
+ * *degree = d and evals_le32 receives d + 1 values of 32 bytes; it has room for (MSMZ_SUMCHECK_MAX_DEGREE + 1) * 32
+ * bytes and the bytes beyond d + 1 values are left as they were.  Tables may share a handle and may overlap.  A prover's
+ * round: sumcheck_round, a challenge from its transcript, mle_bind of every table with the same flag, n_vars - 1.
+ *
+ * MSMZ_ERR_ARG, before any launch: a null ctx, descriptor, point (n_vars > 0), r, tables, terms or output pointer;
+ * n_vars > 31, or 0 where bind and sumcheck_round need >= 1; unknown flag bits; an unknown handle or one that is not a
+ * scalar set; a range beyond its set; count == 0 or count 2^v >= 2^32; n_tables outside 1 .. MSMZ_SUMCHECK_MAX_TABLES;
+ * n_terms outside 1 .. MSMZ_SUMCHECK_MAX_TERMS; a mask that is 0, has bits at or above n_tables or more than
+ * MSMZ_SUMCHECK_MAX_DEGREE of them; first_out != 0 with a new handle; the overlaps above.  MSMZ_ERR_RANGE: a host value
+ * (point, scale, r, coefficient) >= q, found on the host with nothing launched; or a resident entry >= q inside an
+ * addressed range, found by the kernel (entries outside are not read): then no handle is created, *out_handle, *degree
+ * and the output bytes are as they were, an in-place destination is unspecified and the context stays usable.
+ * MSMZ_ERR_UNSUPPORTED: a multi-device context -- the two halves of every pair live in different blocks of 2^16 entries
+ * (the stance of msmz_scalars_recurrence).  Each call returns behind one host wait. */
+enum { MSMZ_MLE_LOW = 1 };
+enum { MSMZ_SUMCHECK_MAX_TABLES = 6, MSMZ_SUMCHECK_MAX_DEGREE = 4, MSMZ_SUMCHECK_MAX_TERMS = 8 };
+typedef struct msmz_mle_bind {
+  uint64_t handle, first;  /* `count` tables of 2^n_vars entries each, table k at first + k * 2^n_vars */
+  uint32_t n_vars;         /* >= 1 */
+  uint32_t count;          /* >= 1 */
+  uint32_t flags;          /* MSMZ_MLE_LOW or 0 */
+  const uint8_t* r;        /* the challenge, 32 bytes little-endian, < q */
+} msmz_mle_bind;           /* 40 bytes */
+typedef struct msmz_sumcheck_table {
+  uint64_t handle, first;
+} msmz_sumcheck_table;
+typedef struct msmz_sumcheck_term {
+  const uint8_t* coeff;    /* 32 bytes little-endian, < q; NULL = 1 */
+  uint32_t mask;           /* bit j: table j is a factor */
+} msmz_sumcheck_term;      /* 16 bytes */
+typedef struct msmz_sumcheck {
+  const msmz_sumcheck_table* tables;
+  uint32_t n_tables;       /* 1 .. MSMZ_SUMCHECK_MAX_TABLES */
+  uint32_t n_vars;         /* >= 1 */
+  const msmz_sumcheck_term* terms;
+  uint32_t n_terms;        /* 1 .. MSMZ_SUMCHECK_MAX_TERMS */
+  uint32_t flags;          /* MSMZ_MLE_LOW or 0: the variable the round sums out */
+} msmz_sumcheck;           /* 32 bytes */
+int msmz_scalars_eq_table(msmz_ctx* ctx, const uint8_t* point_le32, uint32_t n_vars, const uint8_t* scale_le32,
+                          uint64_t* handle);
+int msmz_scalars_mle_eval(msmz_ctx* ctx, uint64_t handle, uint64_t first, uint32_t n_vars, const uint8_t* point_le32,
+                          uint8_t* out_le32);
+int msmz_scalars_mle_bind(msmz_ctx* ctx, const msmz_mle_bind* b, uint64_t first_out, uint64_t* out_handle);
+int msmz_scalars_sumcheck_round(msmz_ctx* ctx, const msmz_sumcheck* s, uint32_t* degree, uint8_t* evals_le32);
+
 /* Host-side group addition of two canonical affine results: combines per-GPU partial sums
  * (the reference's "partition sum" step, msm-batched-affine.ts:300-307). */
 int msmz_point_add(int curve_id, const uint8_t* a_xy_le, int a_is_inf, const uint8_t* b_xy_le, int b_is_inf,

@@ -109,6 +109,13 @@ void msmz_test_scalar_scan_geometry(uint32_t* rec_tile, uint32_t* rec_pass, uint
  *   msmz_test_ntt_geometry: *pass_log = the most stages one pass runs (NTT_PASS_LOG; a tile is 2^pass_log entries). */
 int msmz_test_ntt_plan(int curve_id, uint32_t log_n, uint32_t* n_passes, uint32_t* stages);
 void msmz_test_ntt_geometry(uint32_t* pass_log);
+/* The geometry of the multilinear calls (csrc/mle_kernels.h), for the same purpose (every pointer nullable; needs no
+ * context):
+ *   run       : consecutive eq values one thread of msmz_scalars_eq_table / _mle_eval owns (MLE_RUN);
+ *   eval_tile : entries one workgroup of msmz_scalars_mle_eval sums into one partial sum (MLE_TILE);
+ *   round_tile: pair indices one workgroup of msmz_scalars_sumcheck_round sums into one partial sum per value
+ *               (MSC_TILE).  The second level of both is that of msmz_scalars_dot (partials_per_pass above). */
+void msmz_test_mle_geometry(uint32_t* run, uint32_t* eval_tile, uint32_t* round_tile);
 /* msmz_points_fixed_base (msm_zprize_amd/csrc/fixed_base.h).
  *   msmz_test_fixed_base_plan: what the planner picks for n points of a curve and a bound of `bits` (0 or >= the bit
  *     length of q: none) -- the window width, the windows K = ceil((bound + 1) / c) and the table's entries

@@ -12,6 +12,20 @@ export interface NttOptions { inverse?: boolean; shift?: bigint | null; root?: b
 export function compressedArgs(who: string, compressed?: boolean, sign?: "largest" | "parity", montgomery?: boolean): { compressed: boolean; sign: "largest" | "parity" };
 export function nttArgs(x: { handle: unknown; n: number; kind: string }, logN: number, options: NttOptions | undefined, order: bigint):
   { logN: number; flags: number; nIn: number; count: number; first: number; firstOut: number; root: bigint | null; shift: bigint | null };
+/** the limits of the multilinear calls (include/msmz.h) */
+export const MLE_MAX_VARS: 31, SUMCHECK_MAX_TABLES: 6, SUMCHECK_MAX_DEGREE: 4, SUMCHECK_MAX_TERMS: 8;
+type ScalarsLike = { handle: unknown; n: number; kind: string };
+export interface MleBindOptions { nVars?: number | null; count?: number; low?: boolean; first?: number; out?: DeviceArray | null; firstOut?: number }
+export interface SumcheckOptions { nVars?: number | null; low?: boolean }
+/** a term of a sumcheck: [coefficient or null (1), mask], bit j of the mask making table j a factor (at most 4) */
+export type SumcheckTerm = [bigint | null, number];
+/** the checked arguments of Parallel.eqTable / evaluateMle / bindMle / sumcheckRound (host only) */
+export function eqTableArgs(point: bigint[], scale: bigint, order: bigint): { nVars: number; scale: bigint | null };
+export function mleEvalArgs(f: ScalarsLike, point: bigint[], options: { first?: number } | undefined, order: bigint): { nVars: number; first: number };
+export function mleBindArgs(f: ScalarsLike, r: bigint, options: MleBindOptions | undefined, order: bigint):
+  { nVars: number; count: number; flags: number; first: number; firstOut: number; n: number };
+export function sumcheckRoundArgs(tables: (ScalarsLike | [ScalarsLike, number])[], terms: SumcheckTerm[], options: SumcheckOptions | undefined, order: bigint):
+  { tables: [ScalarsLike, number][]; nVars: number; terms: SumcheckTerm[]; flags: number; degree: number };
 export interface DeviceArray extends Array<DeviceArray> { readonly n: number; readonly kind: "points" | "scalars" | "precomputed";
   /** precomputed point sets only (msmz_precomputed_info) */
   readonly info?: { c: number; glv: number; factor: number; K: number; records: number; scalarBits: number }; free(): void }
@@ -94,6 +108,21 @@ export interface ParallelApi {
   /** `count` number-theoretic transforms of length 2^logN over resident scalar arrays, natural order in and out
    * (msmz_scalars_ntt); returns the array written */
   ntt(x: DeviceArray, logN: number, options?: NttOptions): Promise<DeviceArray>;
+  /** Multilinear polynomials over resident scalar arrays (include/msmz.h msmz_scalars_eq_table / _mle_eval / _mle_bind /
+   * _sumcheck_round).  A polynomial in v variables is 2^v consecutive entries, entry i its value at the bits of i,
+   * variable 0 the lowest bit; eq(r, i) = prod_j (b_j r_j + (1 - b_j)(1 - r_j)).  eqTable: a new array, entry i =
+   * scale eq(point, i) (at most 31 variables; [] gives the one entry scale). */
+  eqTable(point: bigint[], scale?: bigint): Promise<DeviceArray>;
+  /** f(point) = sum_i f[first + i] eq(point, i); the table is not made */
+  evaluateMle(f: DeviceArray, point: bigint[], options?: { first?: number }): Promise<bigint>;
+  /** binds the high variable of `count` tables of 2^nVars entries to r: out_i = f_i + r (f_(i+h) - f_i), h = 2^(nVars-1);
+   * low: variable 0, out_i = f_(2i) + r (f_(2i+1) - f_(2i)).  `out` may be `f` only for one table, the high variable and
+   * firstOut == first (the low half is overwritten), or a range apart from the source.  Returns the array written. */
+  bindMle(f: DeviceArray, r: bigint, options?: MleBindOptions): Promise<DeviceArray>;
+  /** the round polynomial g(0) .. g(d) of a sumcheck over sum_i sum_T c_T prod_(j in T) tables[j][i]: 1 to 6 tables
+   * (arrays or [array, first] pairs), 1 to 8 terms of at most 4 factors, d the most factors of a term; the round sums
+   * out the high variable, with `low` variable 0 */
+  sumcheckRound(tables: (DeviceArray | [DeviceArray, number])[], terms: SumcheckTerm[], options?: SumcheckOptions): Promise<bigint[]>;
   /** the default primitive 2^logN-th root of unity of the scalar field (msmz_scalars_root_of_unity) */
   rootOfUnity(logN: number): bigint;
   msmBatch(scalarsList: DeviceArray | Uint8Array[], points: DeviceArray, n: number, options?: MsmOptions & { batch?: number }): Promise<BigintPoint[]>;

@@ -133,6 +133,108 @@ export function nttArgs(x, logN, { inverse = false, shift = null, root = null, n
   return { logN, flags: (inverse ? 1 : 0) | (shift !== null ? 2 : 0), nIn, count, first, firstOut, root, shift };
 }
 
+/** the limits of the multilinear calls (include/msmz.h) */
+export const MLE_MAX_VARS = 31, SUMCHECK_MAX_TABLES = 6, SUMCHECK_MAX_DEGREE = 4, SUMCHECK_MAX_TERMS = 8;
+const looksLikeScalars = (v) => v !== null && typeof v === "object" && v.kind === "scalars" && Number.isInteger(v.n) && v.handle !== undefined;
+
+/** a point of a multilinear polynomial: an array of at most 31 bigints below the group order -> its number of variables */
+function mlePoint(who, point, order) {
+  if (!Array.isArray(point) || !point.every((r) => typeof r === "bigint")) throw TypeError(`${who}: \`point\` is an array of bigints, one per variable`);
+  if (point.length > MLE_MAX_VARS) throw Error(`${who}: ${point.length} variables (at most ${MLE_MAX_VARS})`);
+  point.forEach((r, j) => {
+    if (r < 0n || r >= order) throw Error(`${who}: point[${j}] = ${r} is not in [0, group order)`);
+  });
+  return point.length;
+}
+const mleFirst = (who, name, first, arr) => {
+  if (!Number.isInteger(first) || first < 0) throw Error(`${who}: ${name} = ${first}`);
+  if (arr === null && first !== 0) throw Error(`${who}: ${name} = ${first} without the array it indexes`);
+};
+function mleVars(who, nVars, have, what) {
+  if (nVars === null || nVars === undefined) {
+    if (have < 2 || 2 ** Math.round(Math.log2(have)) !== have) throw Error(`${who}: nVars is needed: ${what} ${have} entries, not a power of two >= 2`);
+    return Math.round(Math.log2(have));
+  }
+  if (!Number.isInteger(nVars) || nVars < 1 || nVars > MLE_MAX_VARS) throw Error(`${who}: nVars = ${nVars} (1..${MLE_MAX_VARS})`);
+  return nVars;
+}
+
+/** The arguments of Parallel.eqTable -> {nVars, scale}, of Parallel.evaluateMle -> {nVars, first}, of Parallel.bindMle ->
+ * {nVars, count, flags, first, firstOut, n} and of Parallel.sumcheckRound -> {tables, nVars, terms, flags, degree}, checked
+ * before anything reaches the device (msm_zprize_amd/parallel.py eq_table_args, mle_eval_args, mle_bind_args and
+ * sumcheck_round_args are the same functions). */
+export function eqTableArgs(point, scale, order) {
+  const nVars = mlePoint("eqTable", point, order);
+  if (typeof scale !== "bigint") throw TypeError("eqTable: `scale` is a bigint");
+  if (scale < 0n || scale >= order) throw Error(`eqTable: scale = ${scale} is not in [0, group order)`);
+  return { nVars, scale: scale === 1n ? null : scale };
+}
+export function mleEvalArgs(f, point, { first = 0 } = {}, order) {
+  const who = "evaluateMle";
+  if (!looksLikeScalars(f)) throw TypeError(`${who}: \`f\` is a resident scalar array`);
+  const nVars = mlePoint(who, point, order);
+  mleFirst(who, "first", first, f);
+  if (2 ** nVars > f.n - first) throw Error(`${who}: entries [${first}, +${2 ** nVars}) of an array of ${f.n}`);
+  return { nVars, first };
+}
+export function mleBindArgs(f, r, { nVars = null, count = 1, low = false, first = 0, out = null, firstOut = 0 } = {}, order) {
+  const who = "bindMle";
+  if (!looksLikeScalars(f)) throw TypeError(`${who}: \`f\` is a resident scalar array`);
+  if (out !== null && !looksLikeScalars(out)) throw TypeError(`${who}: \`out\` is a resident scalar array or null`);
+  if (typeof r !== "bigint") throw TypeError(`${who}: \`r\` is a bigint`);
+  if (typeof low !== "boolean") throw TypeError(`${who}: \`low\` is a boolean`);
+  if (r < 0n || r >= order) throw Error(`${who}: r = ${r} is not in [0, group order)`);
+  if (!Number.isInteger(count) || count < 1) throw Error(`${who}: count = ${count}`);
+  mleFirst(who, "first", first, f);
+  mleFirst(who, "firstOut", firstOut, out);
+  const have = f.n - first;
+  if (nVars === null && (have < 0 || have % count !== 0)) throw Error(`${who}: nVars is needed: ${have} entries are not ${count} equal tables`);
+  nVars = mleVars(who, nVars, nVars === null ? have / count : 0, "a table would hold");
+  const n = 2 ** nVars, h = n / 2;
+  if (count * n >= 2 ** 32) throw Error(`${who}: count = ${count} tables of ${n} entries (count * 2^nVars < 2^32)`);
+  if (count * n > have) throw Error(`${who}: entries [${first}, +${count * n}) of an array of ${f.n}`);
+  if (out !== null) {
+    if (count * h > out.n - firstOut) throw Error(`${who}: entries [${firstOut}, +${count * h}) of an array of ${out.n}`);
+    const inPlace = count === 1 && !low && firstOut === first;
+    const apart = firstOut + count * h <= first || first + count * n <= firstOut;
+    if (out.handle === f.handle && !inPlace && !apart)
+      throw Error(`${who}: the destination [${firstOut}, +${count * h}) overlaps the source [${first}, +${count * n}); it may be the low half of ONE table bound in its high variable, or apart from the source`);
+  }
+  return { nVars, count, flags: low ? 1 : 0, first, firstOut, n: count * h };
+}
+export function sumcheckRoundArgs(tables, terms, { nVars = null, low = false } = {}, order) {
+  const who = "sumcheckRound";
+  if (!Array.isArray(tables) || !Array.isArray(terms)) throw TypeError(`${who}: \`tables\` and \`terms\` are arrays`);
+  if (typeof low !== "boolean") throw TypeError(`${who}: \`low\` is a boolean`);
+  const tabs = tables.map((t) => {
+    // (a resident array IS an Array of one element, itself: a pair is a plain array of two)
+    const [arr, first] = Array.isArray(t) && !looksLikeScalars(t) && t.length === 2 ? t : [t, 0];
+    if (!looksLikeScalars(arr)) throw TypeError(`${who}: a table is a resident scalar array or an [array, first] pair`);
+    mleFirst(who, "first", first, arr);
+    return [arr, first];
+  });
+  if (tabs.length < 1 || tabs.length > SUMCHECK_MAX_TABLES) throw Error(`${who}: ${tabs.length} tables (1..${SUMCHECK_MAX_TABLES})`);
+  if (terms.length < 1 || terms.length > SUMCHECK_MAX_TERMS) throw Error(`${who}: ${terms.length} terms (1..${SUMCHECK_MAX_TERMS})`);
+  let degree = 0;
+  const out = terms.map((t) => {
+    if (!Array.isArray(t) || t.length !== 2) throw TypeError(`${who}: a term is a pair [coefficient, mask]`);
+    const [c, mask] = t;
+    if (c !== null && typeof c !== "bigint") throw TypeError(`${who}: a coefficient is a bigint or null (1)`);
+    if (!Number.isInteger(mask)) throw TypeError(`${who}: a mask is an integer, bit j for table j`);
+    if (c !== null && (c < 0n || c >= order)) throw Error(`${who}: the coefficient ${c} is not in [0, group order)`);
+    let factors = 0;
+    for (let m = mask; m > 0; m = Math.floor(m / 2)) factors += m % 2;
+    if (mask <= 0 || mask >= 2 ** tabs.length || factors > SUMCHECK_MAX_DEGREE)
+      throw Error(`${who}: mask = ${mask}: 1..${SUMCHECK_MAX_DEGREE} of the ${tabs.length} tables`);
+    degree = Math.max(degree, factors);
+    return [c, mask];
+  });
+  nVars = mleVars(who, nVars, tabs[0][0].n - tabs[0][1], "the first table holds");
+  for (const [arr, first] of tabs)
+    if (2 ** nVars > arr.n - first) throw Error(`${who}: entries [${first}, +${2 ** nVars}) of an array of ${arr.n}`);
+  return { tables: tabs, nVars, terms: out, flags: low ? 1 : 0, degree };
+}
+
 /** A GPU-resident input array; destructures like the reference's pointer arrays: `let [ptr] = ...` */
 class DeviceArray extends Array {
   static make(curve, handle, n, kind) {
@@ -538,6 +640,54 @@ function createCurve(params, kind) {
     rootOfUnity(logN) {
       if (!Number.isInteger(logN) || logN < 0 || logN >= 2 ** 32) throw Error(`rootOfUnity: logN = ${logN}`);
       return bytesToBigint(N.scalarsRootOfUnity(params.curveId, logN), 0, 32);
+    },
+    /** a new resident scalar array of 2^point.length entries: entry i = scale eq(point, i) mod the group order, eq(r, i) =
+     * prod_j (b_j r_j + (1 - b_j)(1 - r_j)) over the bits b_j of i, variable 0 the lowest bit (msmz_scalars_eq_table) */
+    async eqTable(point, scale = 1n) {
+      const t = eqTableArgs(point, scale, params.order);
+      const h = N.scalarsEqTable(ctx, Buffer.concat(point.map(scalarBuf)), t.nVars, t.scale === null ? null : scalarBuf(t.scale));
+      return DeviceArray.make(curve, h, 2 ** t.nVars, "scalars");
+    },
+    /** f(point) = sum_i f[first + i] eq(point, i) over 2^point.length entries as a bigint; the eq table is not made
+     * (msmz_scalars_mle_eval) */
+    async evaluateMle(f, point, options = {}) {
+      if (!isScalars(f)) throw TypeError("evaluateMle: `f` is a resident scalar array");
+      const t = mleEvalArgs(f, point, options, params.order);
+      return bytesToBigint(N.scalarsMleEval(ctx, f.handle, t.first, Buffer.concat(point.map(scalarBuf)), t.nVars), 0, 32);
+    },
+    /** binds one variable of `count` tables of 2^nVars entries (table k at f[first + k 2^nVars]) to the bigint r
+     * (msmz_scalars_mle_bind): out_i = f_i + r (f_(i+h) - f_i), h = 2^(nVars-1), or with `low` out_i = f_(2i) +
+     * r (f_(2i+1) - f_(2i)).  Without `out` the result is a new array of count h entries; `out` may be `f` only with
+     * count 1, the high variable and firstOut == first (the low half is overwritten), or over a range apart from the
+     * source.  Returns the array written. */
+    async bindMle(f, r, options = {}) {
+      if (!isScalars(f)) throw TypeError("bindMle: `f` is a resident scalar array");
+      if (options.out !== undefined && options.out !== null && !isScalars(options.out)) throw TypeError("bindMle: `out` is a resident scalar array or null");
+      const t = mleBindArgs(f, r, options, params.order);
+      const out = options.out === undefined ? null : options.out;
+      const h = N.scalarsMleBind(ctx, f.handle, t.first, t.nVars, t.count, t.flags, scalarBuf(r), t.firstOut, out === null ? 0 : out.handle);
+      return out === null ? DeviceArray.make(curve, h, t.n, "scalars") : out;
+    },
+    /** the round polynomial of a sumcheck over sum_i sum_T c_T prod_(j in T) tables[j][i] (msmz_scalars_sumcheck_round):
+     * an array of d + 1 bigints g(0) .. g(d).  `tables`: 1 to 6 resident scalar arrays or [array, first] pairs; `terms`:
+     * 1 to 8 pairs [c, mask], c a bigint or null (1), bit j of mask making table j a factor, at most 4 factors; d = the
+     * most factors of a term.  The round sums out the high variable, with `low` variable 0; bindMle with the same `low`
+     * goes on to the next round. */
+    async sumcheckRound(tables, terms, options = {}) {
+      const t = sumcheckRoundArgs(tables, terms, options, params.order);
+      for (const [arr] of t.tables) if (!isScalars(arr)) throw TypeError("sumcheckRound: a table is a resident scalar array");
+      const tb = Buffer.alloc(16 * t.tables.length), masks = Buffer.alloc(4 * t.terms.length), unit = Buffer.alloc(t.terms.length);
+      t.tables.forEach(([arr, first], j) => {
+        tb.writeBigUInt64LE(BigInt(arr.handle), 16 * j);
+        tb.writeBigUInt64LE(BigInt(first), 16 * j + 8);
+      });
+      const coeffs = Buffer.concat(t.terms.map(([c, mask], k) => {
+        masks.writeUInt32LE(mask, 4 * k);
+        unit[k] = c === null ? 1 : 0;
+        return scalarBuf(c === null ? 1n : c);
+      }));
+      const r = N.scalarsSumcheckRound(ctx, tb, t.tables.length, t.nVars, masks, coeffs, unit, t.terms.length, t.flags);
+      return Array.from({ length: r.length / 32 }, (_, k) => bytesToBigint(r, 32 * k, 32));
     },
     /** batched MSM: B scalar vectors against one point set (include/msmz.h msmz_msm_batch); safe additions */
     msmBatch: (scalarsList, points, n, options) => msmBatchCommon(scalarsList, points, n, options, 1),

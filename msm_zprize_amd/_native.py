@@ -85,6 +85,28 @@ class MsmzNtt(C.Structure):   # msmz_ntt (include/msmz.h): `count` transforms of
                 ("n_in", C.c_uint64), ("count", C.c_uint32), ("root", C.c_char_p), ("shift", C.c_char_p)]
 
 
+MSMZ_MLE_LOW = 1
+MSMZ_SUMCHECK_MAX_TABLES, MSMZ_SUMCHECK_MAX_DEGREE, MSMZ_SUMCHECK_MAX_TERMS = 6, 4, 8
+
+
+class MsmzMleBind(C.Structure):   # msmz_mle_bind (include/msmz.h): `count` tables of 2^n_vars entries, one variable bound to r
+    _fields_ = [("handle", C.c_uint64), ("first", C.c_uint64), ("n_vars", C.c_uint32), ("count", C.c_uint32),
+                ("flags", C.c_uint32), ("r", C.c_char_p)]
+
+
+class MsmzSumcheckTable(C.Structure):   # msmz_sumcheck_table: one table of a round
+    _fields_ = [("handle", C.c_uint64), ("first", C.c_uint64)]
+
+
+class MsmzSumcheckTerm(C.Structure):   # msmz_sumcheck_term: coeff * the product of the tables of `mask`
+    _fields_ = [("coeff", C.c_char_p), ("mask", C.c_uint32)]
+
+
+class MsmzSumcheck(C.Structure):   # msmz_sumcheck (include/msmz.h): the round polynomial of a sum of products
+    _fields_ = [("tables", C.POINTER(MsmzSumcheckTable)), ("n_tables", C.c_uint32), ("n_vars", C.c_uint32),
+                ("terms", C.POINTER(MsmzSumcheckTerm)), ("n_terms", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class MsmzSegment(C.Structure):   # msmz_segment (include/msmz.h): one problem of msmz_msm_segments
     _fields_ = [("first_p", C.c_uint64), ("first_s", C.c_uint64), ("n", C.c_uint64)]
 
@@ -176,6 +198,10 @@ EXPORTS = {
                                        C.POINTER(C.c_uint64)]),
     "msmz_scalars_ntt": (C.c_int, [C.c_void_p, C.POINTER(MsmzNtt), C.c_uint64, C.POINTER(C.c_uint64)]),
     "msmz_scalars_root_of_unity": (C.c_int, [C.c_int, C.c_uint32, C.c_char_p]),
+    "msmz_scalars_eq_table": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32, C.c_char_p, C.POINTER(C.c_uint64)]),
+    "msmz_scalars_mle_eval": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_char_p, C.c_char_p]),
+    "msmz_scalars_mle_bind": (C.c_int, [C.c_void_p, C.POINTER(MsmzMleBind), C.c_uint64, C.POINTER(C.c_uint64)]),
+    "msmz_scalars_sumcheck_round": (C.c_int, [C.c_void_p, C.POINTER(MsmzSumcheck), C.POINTER(C.c_uint32), C.c_char_p]),
     "msmz_point_add": (C.c_int, [C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.POINTER(C.c_int)]),
     # stage-level test hooks (include/msmz_test.h)
     "msmz_test_set_glv_bits": (C.c_int, [C.c_void_p, C.c_int]),
@@ -186,6 +212,7 @@ EXPORTS = {
     "msmz_test_scalar_scan_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "msmz_test_ntt_plan": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "msmz_test_ntt_geometry": (None, [C.POINTER(C.c_uint32)]),
+    "msmz_test_mle_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "msmz_test_fixed_base_plan": (C.c_int, [C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                             C.POINTER(C.c_uint64)]),
     "msmz_test_set_fixed_base_window": (C.c_int, [C.c_void_p, C.c_int]),

@@ -125,6 +125,13 @@ class IEngine {
                               uint64_t* n_zero) = 0;
   // msmz_scalars_ntt: number-theoretic transforms over ranges of a scalar set (ntt_kernels.h)
   virtual int scalars_ntt(const msmz_ntt& t, uint64_t first_out, uint64_t* out_handle) = 0;
+  // msmz_scalars_eq_table / _mle_eval / _mle_bind / _sumcheck_round: multilinear polynomials over ranges of a scalar set
+  // (mle_kernels.h).  The defaults: a context that has none -- a multi-device one, where the two halves of every pair
+  // live in different blocks of 2^16 entries.
+  virtual int scalars_eq_table(const uint8_t*, uint32_t, const uint8_t*, uint64_t*) { return MSMZ_ERR_UNSUPPORTED; }
+  virtual int scalars_mle_eval(uint64_t, uint64_t, uint32_t, const uint8_t*, uint8_t*) { return MSMZ_ERR_UNSUPPORTED; }
+  virtual int scalars_mle_bind(const msmz_mle_bind&, uint64_t, uint64_t*) { return MSMZ_ERR_UNSUPPORTED; }
+  virtual int scalars_sumcheck_round(const msmz_sumcheck&, uint32_t*, uint8_t*) { return MSMZ_ERR_UNSUPPORTED; }
   // tests (include/msmz_test.h); the stage-level hooks are one engine's (a multi-device context: its first engine's)
   virtual int test_set_glv_bits(int) { return MSMZ_ERR_UNSUPPORTED; }
   virtual int test_retries() { return 0; }

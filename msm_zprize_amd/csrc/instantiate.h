@@ -8,6 +8,7 @@
 #include "gen_kernels.h"
 #include "import_kernels.h"
 #include "kernels.h"
+#include "mle_kernels.h"
 #include "mul_kernels.h"
 #include "ntt_kernels.h"
 #include "scalar_kernels.h"
@@ -127,6 +128,16 @@
   PFX template __global__ void k_scalars_rec_carry<Fr, true, true>(uint32_t*, uint32_t*, const uint32_t*, const uint32_t*, FrConst, uint32_t); \
   PFX template __global__ void k_scalars_inverse<Fr>(uint32_t*, const uint32_t*, uint32_t, uint32_t*);         \
   PFX template __global__ void k_ntt_pass<Fr>(NttArgs);
+
+// the multilinear kernels (mle_kernels.h), a translation unit of their own (kern_mle.hip); NT = the tables of a round
+#define MSMZ_INST_SUMCHECK(Fr, NT, PFX)                                                                           \
+  PFX template __global__ void k_scalars_sumcheck_round<Fr, NT>(uint32_t*, ScTables, FrScTerms, uint32_t, int, uint32_t*);
+#define MSMZ_INST_MLE(F, Fr, PFX)                                                                                 \
+  PFX template __global__ void k_scalars_eq_table<Fr>(uint32_t*, FrConst, FrEqPoint, uint32_t);                   \
+  PFX template __global__ void k_scalars_mle_eval<Fr>(uint32_t*, const uint32_t*, FrEqPoint, uint32_t, uint32_t*); \
+  PFX template __global__ void k_scalars_mle_bind<Fr>(uint32_t*, const uint32_t*, FrConst, uint32_t, uint32_t, int, uint32_t*); \
+  MSMZ_INST_SUMCHECK(Fr, 1, PFX) MSMZ_INST_SUMCHECK(Fr, 2, PFX) MSMZ_INST_SUMCHECK(Fr, 3, PFX)                    \
+  MSMZ_INST_SUMCHECK(Fr, 4, PFX) MSMZ_INST_SUMCHECK(Fr, 5, PFX) MSMZ_INST_SUMCHECK(Fr, 6, PFX)
 
 // every curve, by policy P = WeierPolicy<F> / TePolicy<F>
 #define MSMZ_INST_MISC_P(F, Fr, P, PFX)                                                                           \

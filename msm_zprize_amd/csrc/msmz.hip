@@ -1,10 +1,10 @@
 // C ABI of the MSM engine (include/msmz.h): curve dispatch + argument checking.
 #include "instantiate.h"
 namespace msmz {
-#define X(F, Fr) MSMZ_INST_BATCH(F, Fr, MSMZ_EXTERN) MSMZ_INST_REDUCE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MISC(F, Fr, MSMZ_EXTERN) MSMZ_INST_GEN(F, Fr, MSMZ_EXTERN)
+#define X(F, Fr) MSMZ_INST_BATCH(F, Fr, MSMZ_EXTERN) MSMZ_INST_REDUCE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MISC(F, Fr, MSMZ_EXTERN) MSMZ_INST_GEN(F, Fr, MSMZ_EXTERN) MSMZ_INST_MLE(F, Fr, MSMZ_EXTERN)
 MSMZ_WEIERSTRASS_FIELDS(X)
 #undef X
-#define X(F, Fr) MSMZ_INST_REDUCE_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MISC_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_GEN_TE(F, Fr, MSMZ_EXTERN)
+#define X(F, Fr) MSMZ_INST_REDUCE_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MISC_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_GEN_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MLE(F, Fr, MSMZ_EXTERN)
 MSMZ_TE_FIELDS(X)
 #undef X
 }  // namespace msmz
@@ -260,6 +260,23 @@ int msmz_scalars_inverse(msmz_ctx* c, uint64_t h, uint64_t first, uint64_t n, ui
 }
 int msmz_scalars_ntt(msmz_ctx* c, const msmz_ntt* t, uint64_t first_out, uint64_t* out_handle) {
   return c && t && out_handle ? c->engine->scalars_ntt(*t, first_out, out_handle) : MSMZ_ERR_ARG;
+}
+int msmz_scalars_eq_table(msmz_ctx* c, const uint8_t* point, uint32_t n_vars, const uint8_t* scale, uint64_t* h) {
+  return c && h ? c->engine->scalars_eq_table(point, n_vars, scale, h) : MSMZ_ERR_ARG;
+}
+int msmz_scalars_mle_eval(msmz_ctx* c, uint64_t h, uint64_t first, uint32_t n_vars, const uint8_t* point, uint8_t* out) {
+  return c && out ? c->engine->scalars_mle_eval(h, first, n_vars, point, out) : MSMZ_ERR_ARG;
+}
+int msmz_scalars_mle_bind(msmz_ctx* c, const msmz_mle_bind* b, uint64_t first_out, uint64_t* out_handle) {
+  return c && b && out_handle ? c->engine->scalars_mle_bind(*b, first_out, out_handle) : MSMZ_ERR_ARG;
+}
+int msmz_scalars_sumcheck_round(msmz_ctx* c, const msmz_sumcheck* s, uint32_t* degree, uint8_t* evals) {
+  return c && s && degree && evals ? c->engine->scalars_sumcheck_round(*s, degree, evals) : MSMZ_ERR_ARG;
+}
+void msmz_test_mle_geometry(uint32_t* run, uint32_t* eval_tile, uint32_t* round_tile) {
+  if (run) *run = MLE_RUN;
+  if (eval_tile) *eval_tile = MLE_TILE;
+  if (round_tile) *round_tile = MSC_TILE;
 }
 
 // the 2-adicity of a curve's scalar field, or -1; w (nullable): the default 2^log_n-th root of unity, log_n <= that

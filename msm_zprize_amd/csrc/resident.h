@@ -19,6 +19,7 @@
 #include "check_kernels.h"
 #include "mul_kernels.h"
 #include "scalar_kernels.h"
+#include "mle_kernels.h"
 #include "ntt_kernels.h"
 #include "iengine.h"
 #include "store.h"
@@ -661,6 +662,138 @@ class ResidentSets : public IEngine {
     return st || !hd.mem.p ? st : add_handle(std::move(hd), out_handle);
   }
 
+  // ------------------------------------------------------------------------------------------ multilinear polynomials
+  // msmz_scalars_eq_table: a new scalar handle, entry i = scale eq(r, i).  The host brings the point to Montgomery form;
+  // it travels as a kernel argument (k_scalars_eq_table, mle_kernels.h).  One launch, no error word: nothing is read.
+  int scalars_eq_table(const uint8_t* point, uint32_t n_vars, const uint8_t* scale, uint64_t* h) override {
+    if (!h || n_vars > (uint32_t)MLE_MAX_VARS || (n_vars && !point)) return MSMZ_ERR_ARG;
+    FrConst s{};
+    FrEqPoint pt;
+    s.w[0] = 1;
+    int st;
+    if ((scale && (st = read_fr(scale, s.w, false))) || (st = read_point(point, n_vars, &pt))) return st;
+    const uint64_t n = 1ull << n_vars;
+    MSMZ_HIP(hipSetDevice(device_));
+    Handle hd;
+    if ((st = new_scalars(n, &hd))) return st;
+    const uint64_t threads = (n + MLE_RUN - 1) / MLE_RUN;
+    hipLaunchKernelGGL((k_scalars_eq_table<Fr>), dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, stream_,
+                       hd.mem.as<uint32_t>(), s, pt, n_vars);
+    MSMZ_HIP(hipGetLastError());
+    MSMZ_HIP(hipStreamSynchronize(stream_));
+    return add_handle(std::move(hd), h);
+  }
+
+  // msmz_scalars_mle_eval: scalars_dot with the second operand generated -- one partial sum per tile of MLE_TILE
+  // entries, the same fold, the same result record behind ONE host wait.
+  int scalars_mle_eval(uint64_t xh, uint64_t first, uint32_t n_vars, const uint8_t* point, uint8_t* out) override {
+    if (!out || n_vars > (uint32_t)MLE_MAX_VARS || (n_vars && !point)) return MSMZ_ERR_ARG;
+    const uint64_t n = 1ull << n_vars;
+    const uint32_t* X = handles_.range(xh, 1, first, n, 8);
+    if (!X) return MSMZ_ERR_ARG;
+    FrEqPoint pt;
+    if (int st = read_point(point, n_vars, &pt)) return st;
+    MSMZ_HIP(hipSetDevice(device_));
+    const uint32_t tiles = (uint32_t)((n + MLE_TILE - 1) / MLE_TILE);
+    // words 0..7: the result, word 8: the error word, from word 16: the partial sums
+    const int st = recorded(sdot_, 64 + (size_t)tiles * 32, [&](uint32_t* d_res) {
+      hipLaunchKernelGGL((k_scalars_mle_eval<Fr>), dim3(tiles), dim3(SDOT_THREADS), 0, stream_, d_res + 16, X, pt, n_vars, d_res + 8);
+      hipLaunchKernelGGL((k_scalars_dot_fold<Fr>), dim3(1), dim3(SDOT_THREADS), 0, stream_, d_res, d_res + 16, tiles, 1);
+    });
+    if (st) return st;
+    memcpy(out, h_res_.p, 32);
+    return MSMZ_OK;
+  }
+
+  // msmz_scalars_mle_bind: one launch, one thread per output; the error word (a resident record >= q) comes back behind
+  // the ONE host wait.  One table and the high variable: the two halves are two sources of `resolve`, so the destination
+  // may be a half exactly or apart from both -- and the high half is refused here, as the header says.  Any other shape:
+  // the whole source is one range of another length than the destination, which `resolve` lets meet nowhere.
+  int scalars_mle_bind(const msmz_mle_bind& b, uint64_t first_out, uint64_t* out_handle) override {
+    if (!out_handle || !b.r || b.n_vars == 0 || b.n_vars > (uint32_t)MLE_MAX_VARS || b.count == 0 ||
+        (b.flags & ~(uint32_t)MSMZ_MLE_LOW))
+      return MSMZ_ERR_ARG;
+    const uint64_t n = 1ull << b.n_vars, h = n >> 1, total_in = n * b.count, total_out = h * b.count;
+    if (total_in >> 32) return MSMZ_ERR_ARG;
+    const bool low = (b.flags & MSMZ_MLE_LOW) != 0;
+    const uint32_t* in = nullptr;
+    uint32_t* out = nullptr;
+    if (b.count == 1 && !low) {
+      const uint32_t* hi = nullptr;
+      if (!handles_.range(b.handle, 1, b.first, n, 8)) return MSMZ_ERR_ARG;   // (the whole source: first + h cannot wrap)
+      if (*out_handle == b.handle && first_out == b.first + h) return MSMZ_ERR_ARG;
+      if (int st = resolve({{b.handle, b.first, &in}, {b.handle, b.first + h, &hi}}, h, first_out, *out_handle, &out)) return st;
+    } else if (int st = resolve({{b.handle, b.first, &in, total_in}}, total_out, first_out, *out_handle, &out)) {
+      return st;
+    }
+    FrConst r{};
+    if (int st = read_fr(b.r, r.w, true)) return st;
+    MSMZ_HIP(hipSetDevice(device_));
+    Handle hd;
+    if (int st = fresh_out(total_out, &hd, &out)) return st;
+    const int st = checked([&](uint32_t* d_err) {   // a resident record >= group order
+      hipLaunchKernelGGL((k_scalars_mle_bind<Fr>), dim3((uint32_t)((total_out + 255) / 256)), dim3(256), 0, stream_, out, in, r,
+                         b.n_vars, (uint32_t)total_out, low ? 1 : 0, d_err);
+    });
+    return st || !hd.mem.p ? st : add_handle(std::move(hd), out_handle);
+  }
+
+  // msmz_scalars_sumcheck_round: degree + 1 partial sums per tile of MSC_TILE pair indices, one workgroup of the fold per
+  // value; the values and the error word share a record of MSC_HEAD_BYTES in front of the partial sums and come back in
+  // ONE copy behind ONE host wait.  The coefficients go to c 2^(256 f) here (fr_sc_coeff), f the factors of the term.
+  int scalars_sumcheck_round(const msmz_sumcheck& s, uint32_t* degree, uint8_t* evals) override {
+    if (!degree || !evals || !s.tables || !s.terms || s.n_tables < 1 || s.n_tables > (uint32_t)MSC_MAX_TABLES ||
+        s.n_terms < 1 || s.n_terms > (uint32_t)MSC_MAX_TERMS || s.n_vars == 0 || s.n_vars > (uint32_t)MLE_MAX_VARS ||
+        (s.flags & ~(uint32_t)MSMZ_MLE_LOW))
+      return MSMZ_ERR_ARG;
+    const uint64_t n = 1ull << s.n_vars;
+    ScTables tab{};
+    for (uint32_t j = 0; j < s.n_tables; j++)
+      if (!(tab.p[j] = handles_.range(s.tables[j].handle, 1, s.tables[j].first, n, 8))) return MSMZ_ERR_ARG;
+    FrScTerms T{};
+    T.n_terms = s.n_terms;
+    for (uint32_t k = 0; k < s.n_terms; k++) {
+      const uint32_t m = s.terms[k].mask, f = (uint32_t)__builtin_popcount(m);
+      if (m == 0 || (m >> s.n_tables) || f > (uint32_t)MSC_MAX_DEGREE) return MSMZ_ERR_ARG;
+      T.mask[k] = m;
+      if (f > T.degree) T.degree = f;
+    }
+    for (uint32_t k = 0; k < s.n_terms; k++) {
+      uint32_t c[8] = {1, 0, 0, 0, 0, 0, 0, 0};
+      if (s.terms[k].coeff)
+        if (int st = read_fr(s.terms[k].coeff, c, false)) return st;
+      fr_sc_coeff<Fr>(T.coeff[k], c, __builtin_popcount(T.mask[k]));
+    }
+    MSMZ_HIP(hipSetDevice(device_));
+    const uint32_t half = (uint32_t)(n >> 1), tiles = (half + MSC_TILE - 1) / MSC_TILE, values = T.degree + 1;
+    const int low = (s.flags & MSMZ_MLE_LOW) ? 1 : 0;
+    const int st = recorded(sdot_, MSC_HEAD_BYTES + (size_t)values * tiles * 32, [&](uint32_t* d_res) {
+      uint32_t* partial = d_res + MSC_HEAD_BYTES / 4;
+      uint32_t* d_err = d_res + MSC_ERR_WORD;
+#define MSMZ_SC_LAUNCH(NT)                                                                                           \
+  case NT:                                                                                                           \
+    hipLaunchKernelGGL((k_scalars_sumcheck_round<Fr, NT>), dim3(tiles), dim3(SDOT_THREADS), 0, stream_, partial, tab, T, \
+                       half, low, d_err);                                                                            \
+    break
+      switch (s.n_tables) {
+        MSMZ_SC_LAUNCH(1);
+        MSMZ_SC_LAUNCH(2);
+        MSMZ_SC_LAUNCH(3);
+        MSMZ_SC_LAUNCH(4);
+        MSMZ_SC_LAUNCH(5);
+        MSMZ_SC_LAUNCH(6);
+      }
+#undef MSMZ_SC_LAUNCH
+      static_assert(MSC_MAX_TABLES == 6, "one instance per table count");
+      hipLaunchKernelGGL((k_scalars_dot_fold<Fr>), dim3(values), dim3(SDOT_THREADS), 0, stream_, d_res, (const uint32_t*)partial,
+                         tiles, 0);
+    }, MSC_HEAD_BYTES, MSC_ERR_WORD);
+    if (st) return st;
+    *degree = T.degree;
+    memcpy(evals, h_res_.p, (size_t)values * 32);
+    return MSMZ_OK;
+  }
+
  protected:
   // Host -> device copy of this engine's `n` local records of `rec` bytes.  split == nullptr: one contiguous copy.
   // Otherwise the engine is shard `split->shard` of `split->nshards` inside a multi-device context (multi.h): its local
@@ -732,16 +865,17 @@ class ResidentSets : public IEngine {
 
   // The 64-byte result record of dot, recurrence and inverse at the head of `buf` (`bytes` with its scratch): zeroed in
   // stream order, written by launch(its device address), copied to h_res_ (pinned: Engine::init sized it for far more)
-  // behind ONE wait.  Word 8 is the error word: MSMZ_ERR_RANGE if a resident record was >= the group order.
+  // behind ONE wait.  Word 8 is the error word: MSMZ_ERR_RANGE if a resident record was >= the group order.  (A
+  // sumcheck round has several values to bring back: its record is `head` bytes with the error word at `err_word`.)
   template <class Launch>
-  int recorded(DevBuf& buf, size_t bytes, Launch launch) {
+  int recorded(DevBuf& buf, size_t bytes, Launch launch, size_t head = 64, int err_word = 8) {
     if (int st = buf.ensure(bytes)) return st;
-    MSMZ_HIP(hipMemsetAsync(buf.p, 0, 64, stream_));
+    MSMZ_HIP(hipMemsetAsync(buf.p, 0, head, stream_));
     launch(buf.as<uint32_t>());
     MSMZ_HIP(hipGetLastError());
-    MSMZ_HIP(hipMemcpyAsync(h_res_.p, buf.p, 64, hipMemcpyDeviceToHost, stream_));
+    MSMZ_HIP(hipMemcpyAsync(h_res_.p, buf.p, head, hipMemcpyDeviceToHost, stream_));
     MSMZ_HIP(hipStreamSynchronize(stream_));
-    return h_res_.template as<const uint32_t>()[8] ? MSMZ_ERR_RANGE : MSMZ_OK;
+    return h_res_.template as<const uint32_t>()[err_word] ? MSMZ_ERR_RANGE : MSMZ_OK;
   }
 
   // a broadcast scalar of the caller's (32 bytes, canonical): out = its words, or its Montgomery form; >= q is refused
@@ -753,6 +887,17 @@ class ResidentSets : public IEngine {
     else memcpy(out, c, 32);
     return MSMZ_OK;
   }
+
+  // the point of an eq table or an evaluation (n_vars values of 32 bytes, each < q) in the form the kernels take
+  static int read_point(const uint8_t* point, uint32_t n_vars, FrEqPoint* pt) {
+    memset(pt, 0, sizeof(*pt));
+    for (uint32_t j = 0; j < n_vars; j++)
+      if (int st = read_fr(point + (size_t)32 * j, pt->r[j], true)) return st;
+    return MSMZ_OK;
+  }
+  static_assert(MSC_MAX_TABLES == MSMZ_SUMCHECK_MAX_TABLES && MSC_MAX_DEGREE == MSMZ_SUMCHECK_MAX_DEGREE &&
+                    MSC_MAX_TERMS == MSMZ_SUMCHECK_MAX_TERMS,
+                "the limits of include/msmz.h are those of mle_kernels.h");
 
   // The operands of combine, recurrence, inverse and ntt.  Every source is a range of n records of a scalar set that does
   // not overlap the destination in part (entry i is read, then written: equal starts are in place).  The destination:

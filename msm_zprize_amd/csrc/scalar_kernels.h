@@ -176,10 +176,13 @@ __global__ void __launch_bounds__(SDOT_THREADS) k_scalars_dot(uint32_t* partial,
 }
 
 // result = the sum of `count` partial sums, times 2^256 if to_canon (the ONE conversion of a product sum).  One
-// workgroup; thread t adds partials t, t + SDOT_PASS, ...
+// workgroup; thread t adds partials t, t + SDOT_PASS, ...  A grid of several workgroups folds as many sums at once
+// (the values of a sumcheck round, mle_kernels.h): workgroup b takes partials [b count, (b + 1) count) into record b.
 template <class Fr>
 __global__ void __launch_bounds__(SDOT_THREADS) k_scalars_dot_fold(uint32_t* result, const uint32_t* partial,
                                                                    uint32_t count, int to_canon) {
+  result += (size_t)blockIdx.x * 8;
+  partial += (size_t)blockIdx.x * count * 8;
   uint32_t acc[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) acc[j] = 0;

@@ -470,6 +470,51 @@ class _Parallel:
         _check(lib().msmz_scalars_root_of_unity(self._c.params["curve_id"], logN, buf), "msmz_scalars_root_of_unity")
         return int.from_bytes(buf.raw, "little")
 
+    # -- multilinear polynomials over resident scalar arrays (msmz_scalars_eq_table / _mle_*, _sumcheck_round) --
+    def eqTable(self, point, scale=1):
+        """A new resident scalar array of 2^len(point) entries: entry i = scale eq(point, i) mod the group order,
+        eq(r, i) = prod_j (b_j r_j + (1 - b_j)(1 - r_j)) over the bits b_j of i -- variable 0 is the lowest index bit.
+        `point` is a list of at most 31 ints below the group order ([] gives the one entry `scale`)."""
+        t = eq_table_args(point, scale, self._c.params["order"])
+        return _resident(self._c, "scalars", 1 << t["nVars"], "msmz_scalars_eq_table", t["point"], t["nVars"], t["scale"])
+
+    def evaluateMle(self, f, point, first=0):
+        """f(point) = sum_i f[first + i] eq(point, i) over 2^len(point) entries, as a Python int; the eq table is not
+        made.  The same value as innerProduct(f, eqTable(point))."""
+        t = mle_eval_args(f, point, first, self._c.params["order"])
+        buf = C.create_string_buffer(32)
+        _check(lib().msmz_scalars_mle_eval(self._c._ctx, f.handle, t["first"], t["nVars"], t["point"], buf),
+               "msmz_scalars_mle_eval")
+        return int.from_bytes(buf.raw, "little")
+
+    def bindMle(self, f, r, nVars=None, count=1, low=False, first=0, out=None, firstOut=0):
+        """Binds one variable of `count` tables of 2^nVars entries (table k at f[first + k 2^nVars]) to the int r:
+        out_i = f_i + r (f_(i+h) - f_i), h = 2^(nVars-1) (the high variable), or with low=True
+        out_i = f_(2i) + r (f_(2i+1) - f_(2i)) (variable 0).  Output table k is out[firstOut + k h : ...].  nVars=None:
+        what the entries from `first` make of `count` equal tables.  out=None: a new array of count h entries; `out` may
+        be `f` itself only with count=1, low=False and firstOut == first (the low half is overwritten), or over a range
+        apart from the whole source.  Returns the array written."""
+        t = mle_bind_args(f, r, nVars, count, low, first, out, firstOut, self._c.params["order"])
+        b = _native.MsmzMleBind(f.handle, t["first"], t["nVars"], t["count"], t["flags"], t["r"])
+        return _resident(self._c, "scalars", t["N"], "msmz_scalars_mle_bind", C.byref(b), t["firstOut"], out=out)
+
+    def sumcheckRound(self, tables, terms, nVars=None, low=False):
+        """The round polynomial of a sumcheck over sum_i sum_T c_T prod_(j in T) tables[j][i]: a list of d + 1 ints
+        g(0) .. g(d), g(t) = sum_(i < 2^(nVars-1)) sum_T c_T prod_(j in T) ((1 - t) lo_j(i) + t hi_j(i)), where the round
+        sums out the high variable ((lo, hi) = entries (i, i + 2^(nVars-1))) or with low=True variable 0 ((2i, 2i + 1)).
+        `tables`: 1 to 6 resident scalar arrays or (array, first) pairs; `terms`: 1 to 8 pairs (c, mask), c an int below
+        the group order or None (1), bit j of mask making table j a factor, at most 4 factors; d = the most factors of a
+        term.  nVars=None: what the first table holds from its `first`.  Bind every table with bindMle(.., low=low) to go
+        on to the next round."""
+        t = sumcheck_round_args(tables, terms, nVars, low, self._c.params["order"])
+        tabs = (_native.MsmzSumcheckTable * len(t["tables"]))(*[_native.MsmzSumcheckTable(a.handle, f) for a, f in t["tables"]])
+        trms = (_native.MsmzSumcheckTerm * len(t["terms"]))(*[_native.MsmzSumcheckTerm(c, m) for c, m in t["terms"]])
+        s = _native.MsmzSumcheck(tabs, len(t["tables"]), t["nVars"], trms, len(t["terms"]), t["flags"])
+        degree = C.c_uint32(0)
+        buf = C.create_string_buffer(32 * (_native.MSMZ_SUMCHECK_MAX_DEGREE + 1))
+        _check(lib().msmz_scalars_sumcheck_round(self._c._ctx, C.byref(s), C.byref(degree), buf), "msmz_scalars_sumcheck_round")
+        return [int.from_bytes(buf.raw[32 * k:32 * k + 32], "little") for k in range(degree.value + 1)]
+
     def _checked(self, arr, what, who):
         try:
             res = self.checkPoints(arr, subgroup=bool(what & _native.MSMZ_CHECK_SUBGROUP))
@@ -923,6 +968,140 @@ def ntt_args(x, logN, inverse, shift, root, nIn, count, first, out, firstOut, or
             "nIn": nIn, "count": count, "first": first, "firstOut": firstOut,
             "root": None if root is None else root.to_bytes(32, "little"),
             "shift": None if shift is None else shift.to_bytes(32, "little")}
+
+
+MLE_MAX_VARS = 31   # a resident array has fewer than 2^32 entries
+
+
+def _mle_point(point, order, who):
+    """a point of a multilinear polynomial -> (its variables, its 32-byte values in a row)"""
+    if not isinstance(point, (list, tuple)) or not all(_is_int(r) for r in point):
+        raise TypeError(f"{who}: `point` is a list of ints, one per variable")
+    if len(point) > MLE_MAX_VARS:
+        raise ValueError(f"{who}: {len(point)} variables (at most {MLE_MAX_VARS})")
+    for j, r in enumerate(point):
+        if not 0 <= r < order:
+            raise ValueError(f"{who}: point[{j}] = {r} is not in [0, group order)")
+    return len(point), b"".join(r.to_bytes(32, "little") for r in point)
+
+
+def _mle_first(name, first, arr, who):
+    if not _is_int(first) or first < 0:
+        raise ValueError(f"{who}: {name} = {first!r}")
+    if arr is None and first != 0:
+        raise ValueError(f"{who}: {name} = {first} without the array it indexes")
+
+
+def eq_table_args(point, scale, order, who="eqTable"):
+    """Arguments of eqTable -> dict(nVars, point, scale), checked before anything reaches the device.  scale: its 32
+    little-endian bytes, or None for 1."""
+    n_vars, raw = _mle_point(point, order, who)
+    if not _is_int(scale):
+        raise TypeError(f"{who}: `scale` is an int")
+    if not 0 <= scale < order:
+        raise ValueError(f"{who}: scale = {scale} is not in [0, group order)")
+    return {"nVars": n_vars, "point": raw, "scale": None if scale == 1 else scale.to_bytes(32, "little")}
+
+
+def mle_eval_args(f, point, first, order, who="evaluateMle"):
+    """Arguments of evaluateMle -> dict(nVars, point, first), checked before anything reaches the device."""
+    if not _is_array(f, "scalars"):
+        raise TypeError(f"{who}: `f` is a resident scalar array")
+    n_vars, raw = _mle_point(point, order, who)
+    _mle_first("first", first, f, who)
+    if (1 << n_vars) > len(f) - first:
+        raise ValueError(f"{who}: entries [{first}, +{1 << n_vars}) of an array of {len(f)}")
+    return {"nVars": n_vars, "point": raw, "first": first}
+
+
+def _mle_vars(n_vars, have, who, what):
+    """nVars of bindMle / sumcheckRound, 1 .. 31; None: `have` entries must be a power of two, at least 2"""
+    if n_vars is None:
+        if have < 2 or have & (have - 1):
+            raise ValueError(f"{who}: nVars is needed: {what} {have} entries, not a power of two >= 2")
+        return have.bit_length() - 1
+    if not _is_int(n_vars) or not 1 <= n_vars <= MLE_MAX_VARS:
+        raise ValueError(f"{who}: nVars = {n_vars!r} (1..{MLE_MAX_VARS})")
+    return n_vars
+
+
+def mle_bind_args(f, r, nVars, count, low, first, out, firstOut, order, who="bindMle"):
+    """Arguments of bindMle -> dict(nVars, count, flags, first, firstOut, r, N), checked before anything reaches the
+    device.  N: the entries written, count 2^(nVars-1); r: its 32 little-endian bytes."""
+    if not _is_array(f, "scalars"):
+        raise TypeError(f"{who}: `f` is a resident scalar array")
+    if out is not None and not _is_array(out, "scalars"):
+        raise TypeError(f"{who}: `out` is a resident scalar array or None")
+    if not _is_int(r):
+        raise TypeError(f"{who}: `r` is an int")
+    if not isinstance(low, bool):
+        raise TypeError(f"{who}: `low` is a bool")
+    if not 0 <= r < order:
+        raise ValueError(f"{who}: r = {r} is not in [0, group order)")
+    if not _is_int(count) or count < 1:
+        raise ValueError(f"{who}: count = {count!r}")
+    _mle_first("first", first, f, who)
+    _mle_first("firstOut", firstOut, out, who)
+    have = len(f) - first
+    if nVars is None and (have < 0 or have % count):
+        raise ValueError(f"{who}: nVars is needed: {have} entries are not {count} equal tables")
+    nVars = _mle_vars(nVars, have // count if nVars is None else 0, who, "a table would hold")
+    n, h = 1 << nVars, 1 << (nVars - 1)
+    if count * n >= 1 << 32:
+        raise ValueError(f"{who}: count = {count} tables of {n} entries (count * 2^nVars < 2^32)")
+    if count * n > have:
+        raise ValueError(f"{who}: entries [{first}, +{count * n}) of an array of {len(f)}")
+    if out is not None:
+        if count * h > len(out) - firstOut:
+            raise ValueError(f"{who}: entries [{firstOut}, +{count * h}) of an array of {len(out)}")
+        in_place = count == 1 and not low and firstOut == first
+        apart = firstOut + count * h <= first or first + count * n <= firstOut
+        if out.handle == f.handle and not in_place and not apart:
+            raise ValueError(f"{who}: the destination [{firstOut}, +{count * h}) overlaps the source [{first}, +{count * n}); "
+                             "it may be the low half of ONE table bound in its high variable, or apart from the source")
+    return {"nVars": nVars, "count": count, "flags": _native.MSMZ_MLE_LOW if low else 0, "first": first,
+            "firstOut": firstOut, "r": r.to_bytes(32, "little"), "N": count * h}
+
+
+def sumcheck_round_args(tables, terms, nVars, low, order, who="sumcheckRound"):
+    """Arguments of sumcheckRound -> dict(tables, nVars, terms, flags, degree), checked before anything reaches the
+    device.  tables: [(array, first)]; terms: [(32 little-endian bytes or None, mask)]."""
+    if not isinstance(tables, (list, tuple)) or not isinstance(terms, (list, tuple)):
+        raise TypeError(f"{who}: `tables` and `terms` are lists")
+    if not isinstance(low, bool):
+        raise TypeError(f"{who}: `low` is a bool")
+    tabs = []
+    for t in tables:
+        arr, first = t if isinstance(t, tuple) and len(t) == 2 else (t, 0)
+        if not _is_array(arr, "scalars"):
+            raise TypeError(f"{who}: a table is a resident scalar array or an (array, first) pair")
+        _mle_first("first", first, arr, who)
+        tabs.append((arr, first))
+    if not 1 <= len(tabs) <= _native.MSMZ_SUMCHECK_MAX_TABLES:
+        raise ValueError(f"{who}: {len(tabs)} tables (1..{_native.MSMZ_SUMCHECK_MAX_TABLES})")
+    if not 1 <= len(terms) <= _native.MSMZ_SUMCHECK_MAX_TERMS:
+        raise ValueError(f"{who}: {len(terms)} terms (1..{_native.MSMZ_SUMCHECK_MAX_TERMS})")
+    out, degree = [], 0
+    for t in terms:
+        if not isinstance(t, (list, tuple)) or len(t) != 2:
+            raise TypeError(f"{who}: a term is a pair (coefficient, mask)")
+        c, mask = t
+        if c is not None and not _is_int(c):
+            raise TypeError(f"{who}: a coefficient is an int or None (1)")
+        if not _is_int(mask):
+            raise TypeError(f"{who}: a mask is an int, bit j for table j")
+        if c is not None and not 0 <= c < order:
+            raise ValueError(f"{who}: the coefficient {c} is not in [0, group order)")
+        factors = bin(mask).count("1") if mask > 0 else 0
+        if mask <= 0 or mask >> len(tabs) or factors > _native.MSMZ_SUMCHECK_MAX_DEGREE:
+            raise ValueError(f"{who}: mask = {mask:#b}: 1..{_native.MSMZ_SUMCHECK_MAX_DEGREE} of the {len(tabs)} tables")
+        degree = max(degree, factors)
+        out.append((None if c is None else c.to_bytes(32, "little"), mask))
+    nVars = _mle_vars(nVars, len(tabs[0][0]) - tabs[0][1], who, "the first table holds")
+    for arr, first in tabs:
+        if (1 << nVars) > len(arr) - first:
+            raise ValueError(f"{who}: entries [{first}, +{1 << nVars}) of an array of {len(arr)}")
+    return {"tables": tabs, "nVars": nVars, "terms": out, "flags": _native.MSMZ_MLE_LOW if low else 0, "degree": degree}
 
 
 def check_arg(check, who):

@@ -703,6 +703,111 @@ static napi_value ScalarsRootOfUnity(napi_env env, napi_callback_info info) {
   return buf;
 }
 
+/* a point of nVars variables: a Buffer of at least nVars * 32 bytes (none needed for 0 variables) */
+static int get_point(napi_env env, napi_value v, uint64_t n_vars, const uint8_t** out) {
+  void* p; size_t len;
+  *out = NULL;
+  if (n_vars > 31) return 0;
+  if (!opt_buffer(env, v, &p, &len)) return n_vars == 0;
+  *out = (const uint8_t*)p;
+  return len >= 32 * (size_t)n_vars;
+}
+
+/* scalarsEqTable(ctx, point (Buffer of nVars * 32 bytes), nVars, scale (32-byte Buffer or null = 1)) -> handle of a new
+   scalar array of 2^nVars entries, entry i = scale eq(point, i)  (msmz_scalars_eq_table) */
+static napi_value ScalarsEqTable(napi_env env, napi_callback_info info) {
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  const uint8_t *point, *scale;
+  uint64_t n_vars, h = 0;
+  if (!get_args(env, info, 4, argv, &ctx) || !get_u64(env, argv[2], &n_vars) || !get_point(env, argv[1], n_vars, &point) ||
+      !scalar_or_null(env, argv[3], &scale))
+    return BAD_ARG(env, "scalarsEqTable");
+  int st = msmz_scalars_eq_table(ctx, point, (uint32_t)n_vars, scale, &h);
+  if (st) return throw_status(env, st, "msmz_scalars_eq_table");
+  return make_handle(env, h);
+}
+
+/* scalarsMleEval(ctx, handle, first, point (Buffer of nVars * 32 bytes), nVars) -> 32-byte Buffer, little-endian: the
+   polynomial of entries [first, first + 2^nVars) at the point  (msmz_scalars_mle_eval) */
+static napi_value ScalarsMleEval(napi_env env, napi_callback_info info) {
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  const uint8_t* point;
+  uint64_t h, first, n_vars;
+  if (!get_args(env, info, 5, argv, &ctx) || !get_u64(env, argv[1], &h) || !get_u64(env, argv[2], &first) ||
+      !get_u64(env, argv[4], &n_vars) || !get_point(env, argv[3], n_vars, &point))
+    return BAD_ARG(env, "scalarsMleEval");
+  void* data; napi_value buf;
+  NAPI_CALL(env, napi_create_buffer(env, 32, &data, &buf));
+  int st = msmz_scalars_mle_eval(ctx, h, first, (uint32_t)n_vars, point, (uint8_t*)data);
+  if (st) return throw_status(env, st, "msmz_scalars_mle_eval");
+  return buf;
+}
+
+/* scalarsMleBind(ctx, handle, first, nVars, count, flags (1 = the low variable), r (32-byte Buffer), firstOut, outHandle
+   (0 = a new array)) -> handle of the array written: count tables of 2^(nVars-1) entries  (msmz_scalars_mle_bind) */
+static napi_value ScalarsMleBind(napi_env env, napi_callback_info info) {
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  msmz_mle_bind b; memset(&b, 0, sizeof(b));
+  uint64_t n_vars, count, flags, first_out, h = 0;
+  if (!get_args(env, info, 9, argv, &ctx) || !get_u64(env, argv[1], &b.handle) || !get_u64(env, argv[2], &b.first) ||
+      !get_u64(env, argv[3], &n_vars) || n_vars >> 32 || !get_u64(env, argv[4], &count) || count >> 32 ||
+      !get_u64(env, argv[5], &flags) || flags >> 32 || !scalar_or_null(env, argv[6], &b.r) || !b.r ||
+      !get_u64(env, argv[7], &first_out) || !get_u64(env, argv[8], &h))
+    return BAD_ARG(env, "scalarsMleBind");
+  b.n_vars = (uint32_t)n_vars; b.count = (uint32_t)count; b.flags = (uint32_t)flags;
+  int st = msmz_scalars_mle_bind(ctx, &b, first_out, &h);
+  if (st) return throw_status(env, st, "msmz_scalars_mle_bind");
+  return make_handle(env, h);
+}
+
+/* scalarsSumcheckRound(ctx, tables (Buffer: nTables records of sizeof(msmz_sumcheck_table) = 16 bytes, handle and first
+   as little-endian u64), nTables, nVars, masks (Buffer: nTerms little-endian u32), coeffs (Buffer: nTerms * 32 bytes),
+   unit (Buffer: nTerms bytes, 1 = the coefficient is 1 and its 32 bytes are not read), nTerms, flags (1 = the low
+   variable)) -> Buffer of (degree + 1) * 32 bytes: g(0) .. g(degree)  (msmz_scalars_sumcheck_round) */
+static napi_value ScalarsSumcheckRound(napi_env env, napi_callback_info info) {
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  uint64_t n_tables, n_vars, n_terms, flags;
+  void *tp, *mp, *cp, *up; size_t tl, ml, cl, ul;
+  if (!get_args(env, info, 9, argv, &ctx) || !opt_buffer(env, argv[1], &tp, &tl) || !get_u64(env, argv[2], &n_tables) ||
+      !get_u64(env, argv[3], &n_vars) || n_vars >> 32 || !opt_buffer(env, argv[4], &mp, &ml) ||
+      !opt_buffer(env, argv[5], &cp, &cl) || !opt_buffer(env, argv[6], &up, &ul) || !get_u64(env, argv[7], &n_terms) ||
+      !get_u64(env, argv[8], &flags) || flags >> 32 || n_tables < 1 || n_tables > MSMZ_SUMCHECK_MAX_TABLES ||
+      n_terms < 1 || n_terms > MSMZ_SUMCHECK_MAX_TERMS || tl < n_tables * sizeof(msmz_sumcheck_table) || ml < n_terms * 4 ||
+      cl < n_terms * 32 || ul < n_terms)
+    return BAD_ARG(env, "scalarsSumcheckRound");
+  msmz_sumcheck_table tables[MSMZ_SUMCHECK_MAX_TABLES];   /* (a Buffer need not be aligned) */
+  msmz_sumcheck_term terms[MSMZ_SUMCHECK_MAX_TERMS];
+  memcpy(tables, tp, (size_t)n_tables * sizeof(msmz_sumcheck_table));
+  for (uint64_t k = 0; k < n_terms; k++) {
+    memcpy(&terms[k].mask, (const uint8_t*)mp + 4 * k, 4);
+    terms[k].coeff = ((const uint8_t*)up)[k] ? NULL : (const uint8_t*)cp + 32 * k;
+  }
+  msmz_sumcheck s = {tables, (uint32_t)n_tables, (uint32_t)n_vars, terms, (uint32_t)n_terms, (uint32_t)flags};
+  uint8_t evals[(MSMZ_SUMCHECK_MAX_DEGREE + 1) * 32];
+  uint32_t degree = 0;
+  int st = msmz_scalars_sumcheck_round(ctx, &s, &degree, evals);
+  if (st) return throw_status(env, st, "msmz_scalars_sumcheck_round");
+  napi_value buf;
+  NAPI_CALL(env, napi_create_buffer_copy(env, ((size_t)degree + 1) * 32, evals, NULL, &buf));
+  return buf;
+}
+
+/* descriptorSizes() -> {mleBind, sumcheck, sumcheckTable, sumcheckTerm, maxTables, maxDegree, maxTerms}: what the addon
+   was compiled with, for the host to check its packing against (no context) */
+static napi_value DescriptorSizes(napi_env env, napi_callback_info info) {
+  (void)info;
+  napi_value res;
+  NAPI_CALL(env, napi_create_object(env, &res));
+  set_num(env, res, "mleBind", (double)sizeof(msmz_mle_bind));
+  set_num(env, res, "sumcheck", (double)sizeof(msmz_sumcheck));
+  set_num(env, res, "sumcheckTable", (double)sizeof(msmz_sumcheck_table));
+  set_num(env, res, "sumcheckTerm", (double)sizeof(msmz_sumcheck_term));
+  set_num(env, res, "maxTables", (double)MSMZ_SUMCHECK_MAX_TABLES);
+  set_num(env, res, "maxDegree", (double)MSMZ_SUMCHECK_MAX_DEGREE);
+  set_num(env, res, "maxTerms", (double)MSMZ_SUMCHECK_MAX_TERMS);
+  return res;
+}
+
 /* pointAdd(curveId, aXy|null, bXy|null, feBytes) -> {xy, isInf}  (null = infinity).  Refused: a curve id the library does
    not know, a feBytes that is not that curve's, an input Buffer shorter than the 2 * fe_bytes the library reads */
 static napi_value PointAdd(napi_env env, napi_callback_info info) {
@@ -742,6 +847,8 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"mulPoints", MulPoints}, {"fixedBaseMul", FixedBaseMul}, {"scalarsCombine", ScalarsCombine}, {"scalarsDot", ScalarsDot},
       {"scalarsPowers", ScalarsPowers}, {"scalarsRecurrence", ScalarsRecurrence}, {"scalarsInverse", ScalarsInverse},
       {"scalarsNtt", ScalarsNtt}, {"scalarsRootOfUnity", ScalarsRootOfUnity},
+      {"scalarsEqTable", ScalarsEqTable}, {"scalarsMleEval", ScalarsMleEval}, {"scalarsMleBind", ScalarsMleBind},
+      {"scalarsSumcheckRound", ScalarsSumcheckRound}, {"descriptorSizes", DescriptorSizes},
       {"pointAdd", PointAdd}, {"feBytes", FeBytes}};
   for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); i++) {
     napi_value f;
