@@ -684,6 +684,61 @@ int msmz_scalars_mle_eval(msmz_ctx* ctx, uint64_t handle, uint64_t first, uint32
 int msmz_scalars_mle_bind(msmz_ctx* ctx, const msmz_mle_bind* b, uint64_t first_out, uint64_t* out_handle);
 int msmz_scalars_sumcheck_round(msmz_ctx* ctx, const msmz_sumcheck* s, uint32_t* degree, uint8_t* evals_le32);
 
+/* Sparse matrices over resident scalar sets: y = M x and y = M^T x mod q with the matrix and both
+ * vectors on the device -- the step from a witness z to Az, Bz, Cz of an R1CS, the table of Spartan's second sumcheck
+ * (r_A A + r_B B + r_C C)^T eq(r_x), the QAP evaluations of Groth16, and any gather, selection or permutation of a
+ * scalar range (a 0/1 matrix with one entry per row).  The reference has no analogue.
+ *
+ * A matrix is a third kind of handle.  msmz_matrix_create builds it from nnz triples (row[k], col[k], val[k]) in any
+ * order; triples with the same (row, col) are kept apart and add up in the product.  The indices come from host memory,
+ * the values from entries [val_first, val_first + nnz) of a scalar handle, value k belonging to triple k; with
+ * val_handle == 0 every value is 1 (val_first must then be 0) and the product adds entries of x without multiplying.
+ * `flags` names the orientations to build: MSMZ_MAT_ROWS for the plain product, MSMZ_MAT_COLS for the transposed one,
+ * both, or 0 = MSMZ_MAT_ROWS.  Each orientation costs a sort on the host, O(nnz + n_rows + n_cols), and 8 bytes per
+ * non-zero on the device plus 32 per value.  The matrix copies what it needs: the index arrays and the value set may be
+ * changed or freed once the call has returned.  msmz_matrix_info reports what a matrix handle holds (every output
+ * pointer nullable; *flags = the orientations built).  msmz_free frees a matrix; every other call that is handed a
+ * matrix handle answers MSMZ_ERR_ARG, as for any handle of the wrong kind.
+ *
+ * msmz_matrix_mul:   out_i = sum over {k : row[k] == i} of val[k] * x[col[k]] mod q,   i < n_rows,
+ * with x = entries [x_first, x_first + n_cols) of x_handle; a row without a triple gives 0.  MSMZ_MATVEC_TRANSPOSE swaps
+ * the roles of row and col: x has n_rows entries and the result n_cols.  The plain product needs a matrix built with
+ * MSMZ_MAT_ROWS, the transposed one MSMZ_MAT_COLS; asking for the other is MSMZ_ERR_ARG.  Every entry written is below q;
+ * the sums are exact mod q, so two calls return the same bytes whatever the grouping of the additions.  The output rules
+ * are those of msmz_scalars_combine: *out_handle == 0 makes a new set of n_rows (n_cols) entries and first_out must be
+ * 0; otherwise only [first_out, first_out + n_rows) of that handle is written.  Because x is gathered, a destination
+ * that meets the x range of the same handle anywhere, the exact range included, is MSMZ_ERR_ARG.
+ *
+ * MSMZ_ERR_ARG, before any launch: a null ctx, descriptor, row, col or output pointer; nnz == 0 or nnz >= 2^32; n_rows or
+ * n_cols == 0; an index out of range (the triples are looked at in the caller's order and the first bad one decides,
+ * its row before its column; nothing beyond the status is reported); unknown flag bits; an unknown handle or one of
+ * the wrong kind; a range beyond its set; val_first != 0 without a value set; first_out != 0 with a new handle; the
+ * orientation and the overlap above.  MSMZ_ERR_RANGE from msmz_matrix_create: a value >= q inside [val_first,
+ * val_first + nnz), found by the kernel that packs the values (entries outside are not read).  MSMZ_ERR_RANGE from
+ * msmz_matrix_mul: an entry of x that some non-zero reads is >= q; entries of x that no non-zero references are not
+ * read.  After MSMZ_ERR_RANGE no handle is created, *handle / *out_handle is as it was, an in-place destination is
+ * unspecified and the context stays usable.  MSMZ_ERR_HIP from msmz_matrix_create also covers host memory the sort
+ * could not get (12 nnz + 8 max(n_rows, n_cols) bytes).  MSMZ_ERR_UNSUPPORTED: a multi-device context -- a gather reads
+ * across every block of 2^16 entries (the stance of msmz_scalars_recurrence).  One host wait per call. */
+enum { MSMZ_MAT_ROWS = 1, MSMZ_MAT_COLS = 2 };
+enum { MSMZ_MATVEC_TRANSPOSE = 1 };
+typedef struct msmz_sparse {
+  const uint32_t* row;             /* host memory, nnz entries, each < n_rows */
+  const uint32_t* col;             /* host memory, nnz entries, each < n_cols */
+  uint64_t val_handle, val_first;  /* values: entries [val_first, val_first + nnz) of a scalar set; val_handle == 0: every value is 1 */
+  uint64_t nnz;                    /* 1 .. 2^32 - 1 */
+  uint32_t n_rows, n_cols;         /* >= 1 */
+  uint32_t flags;                  /* MSMZ_MAT_ROWS | MSMZ_MAT_COLS; 0 means MSMZ_MAT_ROWS */
+} msmz_sparse;                     /* 56 bytes */
+typedef struct msmz_matvec {
+  uint64_t matrix;
+  uint64_t x_handle, x_first;      /* x: n_cols entries (n_rows with MSMZ_MATVEC_TRANSPOSE) of a scalar set */
+  uint32_t flags;                  /* MSMZ_MATVEC_TRANSPOSE or 0 */
+} msmz_matvec;                     /* 32 bytes */
+int msmz_matrix_create(msmz_ctx* ctx, const msmz_sparse* s, uint64_t* handle);
+int msmz_matrix_info(msmz_ctx* ctx, uint64_t handle, uint32_t* n_rows, uint32_t* n_cols, uint64_t* nnz, uint32_t* flags);
+int msmz_matrix_mul(msmz_ctx* ctx, const msmz_matvec* v, uint64_t first_out, uint64_t* out_handle);
+
 /* Host-side group addition of two canonical affine results: combines per-GPU partial sums
  * (the reference's "partition sum" step, msm-batched-affine.ts:300-307). */
 int msmz_point_add(int curve_id, const uint8_t* a_xy_le, int a_is_inf, const uint8_t* b_xy_le, int b_is_inf,

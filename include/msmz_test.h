@@ -116,6 +116,12 @@ void msmz_test_ntt_geometry(uint32_t* pass_log);
  *   round_tile: pair indices one workgroup of msmz_scalars_sumcheck_round sums into one partial sum per value
  *               (MSC_TILE).  The second level of both is that of msmz_scalars_dot (partials_per_pass above). */
 void msmz_test_mle_geometry(uint32_t* run, uint32_t* eval_tile, uint32_t* round_tile);
+/* The geometry of msmz_matrix_mul (csrc/matrix_kernels.h), for the same purpose (every pointer nullable; needs no
+ * context):
+ *   tile            : consecutive non-zeros one workgroup takes and leaves one carry for (MAT_TILE);
+ *   run             : consecutive non-zeros one thread walks (MAT_RUN);
+ *   carries_per_pass: tile carries the one workgroup of the fold takes per pass of its loop (MAT_FOLD_PASS). */
+void msmz_test_matrix_geometry(uint32_t* tile, uint32_t* run, uint32_t* carries_per_pass);
 /* msmz_points_fixed_base (msm_zprize_amd/csrc/fixed_base.h).
  *   msmz_test_fixed_base_plan: what the planner picks for n points of a curve and a bound of `bits` (0 or >= the bit
  *     length of q: none) -- the window width, the windows K = ceil((bound + 1) / c) and the table's entries

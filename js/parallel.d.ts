@@ -26,6 +26,14 @@ export function mleBindArgs(f: ScalarsLike, r: bigint, options: MleBindOptions |
   { nVars: number; count: number; flags: number; first: number; firstOut: number; n: number };
 export function sumcheckRoundArgs(tables: (ScalarsLike | [ScalarsLike, number])[], terms: SumcheckTerm[], options: SumcheckOptions | undefined, order: bigint):
   { tables: [ScalarsLike, number][]; nVars: number; terms: SumcheckTerm[]; flags: number; degree: number };
+/** a resident sparse matrix (msmz_matrix_create) */
+export interface SparseMatrix { readonly shape: [number, number]; readonly nnz: number; readonly orientations: "rows" | "cols" | "both"; readonly kind: "matrix"; free(): void }
+export interface SparseMatrixOptions { shape: [number, number]; orientations?: "rows" | "cols" | "both"; firstValue?: number }
+export interface MatVecOptions { firstX?: number; transpose?: boolean; out?: DeviceArray | null; firstOut?: number }
+/** the checked arguments of Parallel.sparseMatrix / matVec (host only) */
+export function sparseMatrixArgs(rows: number[] | Uint32Array, cols: number[] | Uint32Array, values: ScalarsLike | null, options: SparseMatrixOptions):
+  { rows: Uint8Array; cols: Uint8Array; nnz: number; shape: [number, number]; flags: number; firstValue: number };
+export function matVecArgs(matrix: { handle: unknown; shape: number[]; orientations: string; kind: string }, x: ScalarsLike, options?: MatVecOptions): { n: number; flags: number };
 export interface DeviceArray extends Array<DeviceArray> { readonly n: number; readonly kind: "points" | "scalars" | "precomputed";
   /** precomputed point sets only (msmz_precomputed_info) */
   readonly info?: { c: number; glv: number; factor: number; K: number; records: number; scalarBits: number }; free(): void }
@@ -123,6 +131,12 @@ export interface ParallelApi {
    * (arrays or [array, first] pairs), 1 to 8 terms of at most 4 factors, d the most factors of a term; the round sums
    * out the high variable, with `low` variable 0 */
   sumcheckRound(tables: (DeviceArray | [DeviceArray, number])[], terms: SumcheckTerm[], options?: SumcheckOptions): Promise<bigint[]>;
+  /** a resident sparse matrix from triples (rows[k], cols[k], values[k]) in any order, duplicates adding up
+   * (msmz_matrix_create); values: a resident scalar array, bigints (uploaded first) or null (every value is 1) */
+  sparseMatrix(rows: number[] | Uint32Array, cols: number[] | Uint32Array, values: DeviceArray | bigint[] | null, options: SparseMatrixOptions): Promise<SparseMatrix>;
+  /** out_i = sum over the non-zeros (i, j, v) of v x[firstX + j] mod the group order, with `transpose` over (j, i, v)
+   * (msmz_matrix_mul); the destination may not meet the x range.  Returns the array written. */
+  matVec(matrix: SparseMatrix, x: DeviceArray, options?: MatVecOptions): Promise<DeviceArray>;
   /** the default primitive 2^logN-th root of unity of the scalar field (msmz_scalars_root_of_unity) */
   rootOfUnity(logN: number): bigint;
   msmBatch(scalarsList: DeviceArray | Uint8Array[], points: DeviceArray, n: number, options?: MsmOptions & { batch?: number }): Promise<BigintPoint[]>;

@@ -235,6 +235,71 @@ export function sumcheckRoundArgs(tables, terms, { nVars = null, low = false } =
   return { tables: tabs, nVars, terms: out, flags: low ? 1 : 0, degree };
 }
 
+/** The arguments of Parallel.sparseMatrix -> {rows, cols (Buffers of little-endian u32), nnz, shape, flags, firstValue} and
+ * of Parallel.matVec -> {n, flags}, checked before anything reaches the device (msm_zprize_amd/parallel.py
+ * sparse_matrix_args and mat_vec_args are the same functions).  `values` here is a resident scalar array or null: a host
+ * list is uploaded by the caller first. */
+const ORIENTATIONS = { rows: 1, cols: 2, both: 3 };
+function indexBuffer(who, name, v, bound) {
+  if (!(Array.isArray(v) || v instanceof Uint32Array)) throw TypeError(`${who}: \`${name}\` is an array of integers or a Uint32Array`);
+  const buf = Buffer.alloc(4 * v.length);
+  for (let k = 0; k < v.length; k++) {
+    if (!Number.isInteger(v[k])) throw TypeError(`${who}: \`${name}\` is an array of integers or a Uint32Array`);
+    if (v[k] < 0 || v[k] >= bound) throw Error(`${who}: ${name}[${k}] = ${v[k]} is not in [0, ${bound})`);
+    buf.writeUInt32LE(v[k], 4 * k);
+  }
+  return buf;
+}
+export function sparseMatrixArgs(rows, cols, values, { shape = null, orientations = "rows", firstValue = 0 } = {}) {
+  const who = "sparseMatrix";
+  if (!Array.isArray(shape) || shape.length !== 2 || !shape.every(Number.isInteger)) throw TypeError(`${who}: \`shape\` is a pair of integers [nRows, nCols]`);
+  if (!Object.prototype.hasOwnProperty.call(ORIENTATIONS, orientations)) throw Error(`${who}: orientations = ${orientations} ("rows", "cols" or "both")`);
+  const [nRows, nCols] = shape;
+  if (nRows < 1 || nRows >= 2 ** 32) throw Error(`${who}: nRows = ${nRows}`);
+  if (nCols < 1 || nCols >= 2 ** 32) throw Error(`${who}: nCols = ${nCols}`);
+  if (values !== null && !looksLikeScalars(values)) throw TypeError(`${who}: \`values\` is a resident scalar array, an array of bigints or null`);
+  const r = indexBuffer(who, "rows", rows, nRows), c = indexBuffer(who, "cols", cols, nCols);
+  const nnz = rows.length;
+  if (cols.length !== nnz) throw Error(`${who}: ${nnz} rows but ${cols.length} cols`);
+  if (nnz < 1 || nnz >= 2 ** 32) throw Error(`${who}: N = ${nnz}`);
+  mleFirst(who, "firstValue", firstValue, values);
+  if (values !== null && nnz > values.n - firstValue) throw Error(`${who}: entries [${firstValue}, +${nnz}) from firstValue of an array of ${values.n}`);
+  return { rows: r, cols: c, nnz, shape: [nRows, nCols], flags: ORIENTATIONS[orientations], firstValue };
+}
+const looksLikeMatrix = (m) => m !== null && typeof m === "object" && m.kind === "matrix" && Array.isArray(m.shape) && typeof m.orientations === "string";
+export function matVecArgs(matrix, x, { firstX = 0, transpose = false, out = null, firstOut = 0 } = {}) {
+  const who = "matVec";
+  if (!looksLikeMatrix(matrix)) throw TypeError(`${who}: \`matrix\` is a sparse matrix (sparseMatrix)`);
+  if (!looksLikeScalars(x)) throw TypeError(`${who}: \`x\` is a resident scalar array`);
+  if (out !== null && !looksLikeScalars(out)) throw TypeError(`${who}: \`out\` is a resident scalar array or null`);
+  if (typeof transpose !== "boolean") throw TypeError(`${who}: \`transpose\` is a boolean`);
+  if (matrix.handle === null) throw Error(`${who}: the matrix was freed`);
+  const need = transpose ? "cols" : "rows";
+  if (matrix.orientations !== need && matrix.orientations !== "both")
+    throw Error(`${who}: transpose=${transpose} needs a matrix built with orientations "${need}" or "both", this one has "${matrix.orientations}"`);
+  const [nOut, nIn] = transpose ? [matrix.shape[1], matrix.shape[0]] : matrix.shape;
+  mleFirst(who, "firstX", firstX, x);
+  mleFirst(who, "firstOut", firstOut, out);
+  if (nIn > x.n - firstX) throw Error(`${who}: entries [${firstX}, +${nIn}) from firstX of an array of ${x.n}`);
+  if (out !== null) {
+    if (nOut > out.n - firstOut) throw Error(`${who}: entries [${firstOut}, +${nOut}) from firstOut of an array of ${out.n}`);
+    if (out.handle === x.handle && firstOut < firstX + nIn && firstX < firstOut + nOut)
+      throw Error(`${who}: the destination [${firstOut}, +${nOut}) overlaps the input range [${firstX}, +${nIn}) (firstX); x is gathered, so the two may not meet at all`);
+  }
+  return { n: nOut, flags: transpose ? 1 : 0 };
+}
+
+/** A GPU-resident sparse matrix (msmz_matrix_create): shape = [rows, columns], nnz, the orientations it was built for */
+class SparseMatrix {
+  constructor(curve, handle, shape, nnz, orientations) {
+    Object.assign(this, { curve, handle, shape, nnz, orientations, kind: "matrix" });
+  }
+  free() {
+    if (this.handle !== null) native().free(this.curve._ctx, this.handle);
+    this.handle = null;
+  }
+}
+
 /** A GPU-resident input array; destructures like the reference's pointer arrays: `let [ptr] = ...` */
 class DeviceArray extends Array {
   static make(curve, handle, n, kind) {
@@ -688,6 +753,43 @@ function createCurve(params, kind) {
       }));
       const r = N.scalarsSumcheckRound(ctx, tb, t.tables.length, t.nVars, masks, coeffs, unit, t.terms.length, t.flags);
       return Array.from({ length: r.length / 32 }, (_, k) => bytesToBigint(r, 32 * k, 32));
+    },
+    /** a resident sparse matrix of shape [nRows, nCols] from triples (rows[k], cols[k], values[k]) in any order, triples
+     * with the same (row, col) adding up (msmz_matrix_create).  values: a resident scalar array (value k =
+     * values[firstValue + k]), an array of bigints below the group order (uploaded first, freed afterwards) or null:
+     * every value is 1.  options: {shape, orientations: "rows" (for matVec) | "cols" (for transpose) | "both", firstValue} */
+    async sparseMatrix(rows, cols, values = null, options = {}) {
+      let vals = values, mine = false;
+      if (Array.isArray(values) && !(values instanceof DeviceArray)) {
+        values.forEach((v, k) => {
+          if (typeof v !== "bigint") throw TypeError("sparseMatrix: a value is a bigint");
+          if (v < 0n || v >= params.order) throw Error(`sparseMatrix: values[${k}] = ${v} is not in [0, group order)`);
+        });
+        if (values.length !== rows.length) throw Error(`sparseMatrix: ${rows.length} rows but ${values.length} values`);
+        if ((options.firstValue || 0) !== 0) throw Error(`sparseMatrix: firstValue = ${options.firstValue} without the array it indexes`);
+        sparseMatrixArgs(rows, cols, null, options);   // (every host check before the upload)
+        vals = await Parallel.scalarsFromBytes(Buffer.concat(values.map(scalarBuf)));
+        mine = true;
+      }
+      try {
+        const t = sparseMatrixArgs(rows, cols, vals, options);
+        if (vals !== null && !isScalars(vals)) throw TypeError("sparseMatrix: `values` is a resident scalar array, an array of bigints or null");
+        const h = N.matrixCreate(ctx, t.rows, t.cols, t.nnz, vals === null ? 0 : vals.handle, t.firstValue, t.shape[0], t.shape[1], t.flags);
+        return new SparseMatrix(curve, h, t.shape, t.nnz, options.orientations === undefined ? "rows" : options.orientations);
+      } finally {
+        if (mine) vals.free();
+      }
+    },
+    /** out[firstOut + i] = sum over the non-zeros (i, j, v) of v x[firstX + j] mod the group order; with `transpose` over
+     * (j, i, v) (msmz_matrix_mul).  Without `out` a new array; `out` may be `x` only over a range that does not meet the
+     * x range.  options: {firstX, transpose, out, firstOut}.  Returns the array written. */
+    async matVec(matrix, x, options = {}) {
+      const t = matVecArgs(matrix, x, options);
+      if (!(matrix instanceof SparseMatrix) || !isScalars(x)) throw TypeError("matVec: a sparse matrix and a resident scalar array");
+      const out = options.out === undefined ? null : options.out;
+      if (out !== null && !isScalars(out)) throw TypeError("matVec: `out` is a resident scalar array or null");
+      const h = N.matrixMul(ctx, matrix.handle, x.handle, options.firstX || 0, t.flags, options.firstOut || 0, out === null ? 0 : out.handle);
+      return out === null ? DeviceArray.make(curve, h, t.n, "scalars") : out;
     },
     /** batched MSM: B scalar vectors against one point set (include/msmz.h msmz_msm_batch); safe additions */
     msmBatch: (scalarsList, points, n, options) => msmBatchCommon(scalarsList, points, n, options, 1),

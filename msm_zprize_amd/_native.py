@@ -107,6 +107,20 @@ class MsmzSumcheck(C.Structure):   # msmz_sumcheck (include/msmz.h): the round p
                 ("terms", C.POINTER(MsmzSumcheckTerm)), ("n_terms", C.c_uint32), ("flags", C.c_uint32)]
 
 
+MSMZ_MAT_ROWS, MSMZ_MAT_COLS = 1, 2
+MSMZ_MATVEC_TRANSPOSE = 1
+
+
+class MsmzSparse(C.Structure):   # msmz_sparse (include/msmz.h): nnz triples (row, col, value) of a sparse matrix
+    _fields_ = [("row", C.POINTER(C.c_uint32)), ("col", C.POINTER(C.c_uint32)), ("val_handle", C.c_uint64),
+                ("val_first", C.c_uint64), ("nnz", C.c_uint64), ("n_rows", C.c_uint32), ("n_cols", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+class MsmzMatvec(C.Structure):   # msmz_matvec (include/msmz.h): one product of a matrix handle with a scalar range
+    _fields_ = [("matrix", C.c_uint64), ("x_handle", C.c_uint64), ("x_first", C.c_uint64), ("flags", C.c_uint32)]
+
+
 class MsmzSegment(C.Structure):   # msmz_segment (include/msmz.h): one problem of msmz_msm_segments
     _fields_ = [("first_p", C.c_uint64), ("first_s", C.c_uint64), ("n", C.c_uint64)]
 
@@ -202,6 +216,10 @@ EXPORTS = {
     "msmz_scalars_mle_eval": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_char_p, C.c_char_p]),
     "msmz_scalars_mle_bind": (C.c_int, [C.c_void_p, C.POINTER(MsmzMleBind), C.c_uint64, C.POINTER(C.c_uint64)]),
     "msmz_scalars_sumcheck_round": (C.c_int, [C.c_void_p, C.POINTER(MsmzSumcheck), C.POINTER(C.c_uint32), C.c_char_p]),
+    "msmz_matrix_create": (C.c_int, [C.c_void_p, C.POINTER(MsmzSparse), C.POINTER(C.c_uint64)]),
+    "msmz_matrix_info": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                   C.POINTER(C.c_uint32)]),
+    "msmz_matrix_mul": (C.c_int, [C.c_void_p, C.POINTER(MsmzMatvec), C.c_uint64, C.POINTER(C.c_uint64)]),
     "msmz_point_add": (C.c_int, [C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.POINTER(C.c_int)]),
     # stage-level test hooks (include/msmz_test.h)
     "msmz_test_set_glv_bits": (C.c_int, [C.c_void_p, C.c_int]),
@@ -212,6 +230,7 @@ EXPORTS = {
     "msmz_test_scalar_scan_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "msmz_test_ntt_plan": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "msmz_test_ntt_geometry": (None, [C.POINTER(C.c_uint32)]),
+    "msmz_test_matrix_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "msmz_test_mle_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "msmz_test_fixed_base_plan": (C.c_int, [C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                             C.POINTER(C.c_uint64)]),

@@ -132,6 +132,11 @@ class IEngine {
   virtual int scalars_mle_eval(uint64_t, uint64_t, uint32_t, const uint8_t*, uint8_t*) { return MSMZ_ERR_UNSUPPORTED; }
   virtual int scalars_mle_bind(const msmz_mle_bind&, uint64_t, uint64_t*) { return MSMZ_ERR_UNSUPPORTED; }
   virtual int scalars_sumcheck_round(const msmz_sumcheck&, uint32_t*, uint8_t*) { return MSMZ_ERR_UNSUPPORTED; }
+  // msmz_matrix_create / _matrix_info / _matrix_mul: sparse matrices against ranges of a scalar set (matrix_kernels.h).
+  // The defaults: a multi-device context has none -- a gather reads across every block of 2^16 entries.
+  virtual int matrix_create(const msmz_sparse&, uint64_t*) { return MSMZ_ERR_UNSUPPORTED; }
+  virtual int matrix_info(uint64_t, uint32_t*, uint32_t*, uint64_t*, uint32_t*) { return MSMZ_ERR_UNSUPPORTED; }
+  virtual int matrix_mul(const msmz_matvec&, uint64_t, uint64_t*) { return MSMZ_ERR_UNSUPPORTED; }
   // tests (include/msmz_test.h); the stage-level hooks are one engine's (a multi-device context: its first engine's)
   virtual int test_set_glv_bits(int) { return MSMZ_ERR_UNSUPPORTED; }
   virtual int test_retries() { return 0; }

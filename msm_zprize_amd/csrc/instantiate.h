@@ -8,6 +8,7 @@
 #include "gen_kernels.h"
 #include "import_kernels.h"
 #include "kernels.h"
+#include "matrix_kernels.h"
 #include "mle_kernels.h"
 #include "mul_kernels.h"
 #include "ntt_kernels.h"
@@ -138,6 +139,12 @@
   PFX template __global__ void k_scalars_mle_bind<Fr>(uint32_t*, const uint32_t*, FrConst, uint32_t, uint32_t, int, uint32_t*); \
   MSMZ_INST_SUMCHECK(Fr, 1, PFX) MSMZ_INST_SUMCHECK(Fr, 2, PFX) MSMZ_INST_SUMCHECK(Fr, 3, PFX)                    \
   MSMZ_INST_SUMCHECK(Fr, 4, PFX) MSMZ_INST_SUMCHECK(Fr, 5, PFX) MSMZ_INST_SUMCHECK(Fr, 6, PFX)
+
+// the sparse-matrix kernels (matrix_kernels.h), a translation unit of their own (kern_matrix.hip)
+#define MSMZ_INST_MATRIX(F, Fr, PFX)                                                                              \
+  PFX template __global__ void k_matrix_pack<Fr>(uint32_t*, const uint32_t*, const uint32_t*, uint32_t, uint32_t*); \
+  PFX template __global__ void k_matrix_mul<Fr>(uint32_t*, MatView, const uint32_t*, uint32_t, uint32_t*, uint32_t*); \
+  PFX template __global__ void k_matrix_fold<Fr>(uint32_t*, const uint32_t*, uint32_t);
 
 // every curve, by policy P = WeierPolicy<F> / TePolicy<F>
 #define MSMZ_INST_MISC_P(F, Fr, P, PFX)                                                                           \

@@ -1,10 +1,10 @@
 // C ABI of the MSM engine (include/msmz.h): curve dispatch + argument checking.
 #include "instantiate.h"
 namespace msmz {
-#define X(F, Fr) MSMZ_INST_BATCH(F, Fr, MSMZ_EXTERN) MSMZ_INST_REDUCE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MISC(F, Fr, MSMZ_EXTERN) MSMZ_INST_GEN(F, Fr, MSMZ_EXTERN) MSMZ_INST_MLE(F, Fr, MSMZ_EXTERN)
+#define X(F, Fr) MSMZ_INST_BATCH(F, Fr, MSMZ_EXTERN) MSMZ_INST_REDUCE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MISC(F, Fr, MSMZ_EXTERN) MSMZ_INST_GEN(F, Fr, MSMZ_EXTERN) MSMZ_INST_MLE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MATRIX(F, Fr, MSMZ_EXTERN)
 MSMZ_WEIERSTRASS_FIELDS(X)
 #undef X
-#define X(F, Fr) MSMZ_INST_REDUCE_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MISC_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_GEN_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MLE(F, Fr, MSMZ_EXTERN)
+#define X(F, Fr) MSMZ_INST_REDUCE_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MISC_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_GEN_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MLE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MATRIX(F, Fr, MSMZ_EXTERN)
 MSMZ_TE_FIELDS(X)
 #undef X
 }  // namespace msmz
@@ -272,6 +272,20 @@ int msmz_scalars_mle_bind(msmz_ctx* c, const msmz_mle_bind* b, uint64_t first_ou
 }
 int msmz_scalars_sumcheck_round(msmz_ctx* c, const msmz_sumcheck* s, uint32_t* degree, uint8_t* evals) {
   return c && s && degree && evals ? c->engine->scalars_sumcheck_round(*s, degree, evals) : MSMZ_ERR_ARG;
+}
+int msmz_matrix_create(msmz_ctx* c, const msmz_sparse* s, uint64_t* h) {
+  return c && s && h ? c->engine->matrix_create(*s, h) : MSMZ_ERR_ARG;
+}
+int msmz_matrix_info(msmz_ctx* c, uint64_t h, uint32_t* n_rows, uint32_t* n_cols, uint64_t* nnz, uint32_t* flags) {
+  return c ? c->engine->matrix_info(h, n_rows, n_cols, nnz, flags) : MSMZ_ERR_ARG;
+}
+int msmz_matrix_mul(msmz_ctx* c, const msmz_matvec* v, uint64_t first_out, uint64_t* out_handle) {
+  return c && v && out_handle ? c->engine->matrix_mul(*v, first_out, out_handle) : MSMZ_ERR_ARG;
+}
+void msmz_test_matrix_geometry(uint32_t* tile, uint32_t* run, uint32_t* carries_per_pass) {
+  if (tile) *tile = MAT_TILE;
+  if (run) *run = MAT_RUN;
+  if (carries_per_pass) *carries_per_pass = MAT_FOLD_PASS;
 }
 void msmz_test_mle_geometry(uint32_t* run, uint32_t* eval_tile, uint32_t* round_tile) {
   if (run) *run = MLE_RUN;

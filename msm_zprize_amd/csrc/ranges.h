@@ -18,4 +18,7 @@ static inline bool ranges_clash(uint64_t a, uint64_t na, uint64_t b, uint64_t nb
   return a < b ? b - a < na : a - b < nb;
 }
 
+// do [a, a + na) and [b, b + nb) meet at all?  For an operation that gathers: no entry may be both read and written.
+static inline bool ranges_meet(uint64_t a, uint64_t na, uint64_t b, uint64_t nb) { return a < b ? b - a < na : a - b < nb; }
+
 }  // namespace msmz

@@ -79,7 +79,7 @@ struct PinnedOne : PinnedBuf {
 };
 
 struct Handle {
-  int kind = 0;             // 0 = points, 1 = scalars
+  int kind = 0;             // 0 = points, 1 = scalars, 2 = a sparse matrix
   uint64_t n = 0;
   bool has_endo = false;    // points: records [n, 2n) hold the endomorphism images
   DevBuf mem;
@@ -89,6 +89,12 @@ struct Handle {
   int c = 0, glv = 0;
   uint64_t copy_stride = 0;
   int sbits = 0;   // scalar bit bound the copies were built for (Planner::bound: 0 = none)
+  // sparse matrix (msmz_matrix_create): n = its non-zeros; form[0] sorted by row (MSMZ_MAT_ROWS), form[1] by column
+  // (MSMZ_MAT_COLS), each n gathered indices, n segment indices and, with has_vals, n values of 8 words from byte
+  // offset mat_val_offset(n) (matrix_kernels.h); an orientation the matrix was not built for has an empty buffer
+  uint32_t n_rows = 0, n_cols = 0, mat_flags = 0;
+  bool has_vals = false;
+  DevBuf form[2];
 };
 
 // The handles of one engine by id.  Ids start at 1 and are never reused.

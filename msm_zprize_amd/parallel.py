@@ -64,6 +64,19 @@ class DeviceArray:
             self.handle = None
 
 
+class SparseMatrix:
+    """A device-resident sparse matrix (msmz_matrix_create): `shape` = (rows, columns), `nnz` its non-zeros, `orientations`
+    the products it was built for ("rows": M x, "cols": M^T x, "both")."""
+
+    def __init__(self, curve, handle, shape, nnz, orientations):
+        self.curve, self.handle, self.shape, self.nnz, self.orientations = curve, handle, shape, nnz, orientations
+
+    def free(self):
+        if self.handle is not None:
+            _check(lib().msmz_free(self.curve._ctx, self.handle), "msmz_free")
+            self.handle = None
+
+
 def _is_int(v):
     """an int, and not a bool"""
     return isinstance(v, int) and not isinstance(v, bool)
@@ -514,6 +527,37 @@ class _Parallel:
         buf = C.create_string_buffer(32 * (_native.MSMZ_SUMCHECK_MAX_DEGREE + 1))
         _check(lib().msmz_scalars_sumcheck_round(self._c._ctx, C.byref(s), C.byref(degree), buf), "msmz_scalars_sumcheck_round")
         return [int.from_bytes(buf.raw[32 * k:32 * k + 32], "little") for k in range(degree.value + 1)]
+
+    # -- sparse matrices against resident scalar arrays (msmz_matrix_create / _matrix_mul) -------------
+    def sparseMatrix(self, rows, cols, values=None, shape=None, orientations="rows", firstValue=0):
+        """A resident sparse matrix of shape = (nRows, nCols) from triples (rows[k], cols[k], values[k]) in any order;
+        triples with the same (row, col) add up.  rows / cols: lists of ints, or 1-D buffers of unsigned 32-bit ints
+        (array("I"), a numpy uint32 array).  values: a resident scalar array (value k = values[firstValue + k]), a list
+        of ints below the group order or of 32-byte little-endian records (uploaded first, freed afterwards), or None:
+        every value is 1.  orientations: "rows" builds for matVec(M, x), "cols" for matVec(M, x, transpose=True),
+        "both" for either.  The matrix keeps its own copy: `values` may be freed or overwritten afterwards."""
+        a = sparse_matrix_args(rows, cols, values, shape, orientations, firstValue, self._c.params["order"])
+        vals, mine = values, False
+        if a["upload"] is not None:
+            vals, mine = self.scalarsFromBytes(a["upload"], a["nnz"]), True
+        try:
+            s = _native.MsmzSparse(a["row"], a["col"], 0 if vals is None else vals.handle, a["firstValue"], a["nnz"],
+                                   a["shape"][0], a["shape"][1], a["flags"])
+            h = C.c_uint64(0)
+            _check(lib().msmz_matrix_create(self._c._ctx, C.byref(s), C.byref(h)), "msmz_matrix_create")
+        finally:
+            if mine:
+                vals.free()
+        return SparseMatrix(self._c, h.value, a["shape"], a["nnz"], orientations)
+
+    def matVec(self, matrix, x, firstX=0, transpose=False, out=None, firstOut=0):
+        """out[firstOut + i] = sum over the non-zeros (i, j, v) of v x[firstX + j] mod the group order, i < nRows; with
+        transpose=True the sum runs over (j, i, v) and i < nCols.  out=None: a new resident scalar array; otherwise only
+        entries [firstOut, firstOut + nRows) of `out` are written, and they may not meet the x range if `out` is `x`
+        (x is gathered).  Returns the array written."""
+        a = mat_vec_args(matrix, x, firstX, transpose, out, firstOut)
+        v = _native.MsmzMatvec(matrix.handle, x.handle, firstX, a["flags"])
+        return _resident(self._c, "scalars", a["N"], "msmz_matrix_mul", C.byref(v), firstOut, out=out)
 
     def _checked(self, arr, what, who):
         try:
@@ -1102,6 +1146,111 @@ def sumcheck_round_args(tables, terms, nVars, low, order, who="sumcheckRound"):
         if (1 << nVars) > len(arr) - first:
             raise ValueError(f"{who}: entries [{first}, +{1 << nVars}) of an array of {len(arr)}")
     return {"tables": tabs, "nVars": nVars, "terms": out, "flags": _native.MSMZ_MLE_LOW if low else 0, "degree": degree}
+
+
+def _index_array(name, v, bound, who):
+    """row / column indices -> a ctypes array of uint32, every entry checked against `bound`"""
+    import array
+    if isinstance(v, (list, tuple)):
+        if not all(_is_int(i) for i in v):
+            raise TypeError(f"{who}: `{name}` is a list of ints or a buffer of unsigned 32-bit ints")
+        for k, i in enumerate(v):
+            if not 0 <= i < bound:
+                raise ValueError(f"{who}: {name}[{k}] = {i} is not in [0, {bound})")
+        buf = array.array("I", v)
+    else:
+        try:
+            m = memoryview(v)
+        except TypeError:
+            raise TypeError(f"{who}: `{name}` is a list of ints or a buffer of unsigned 32-bit ints") from None
+        if m.ndim != 1 or m.itemsize != 4 or m.format not in ("I", "L", "=I", "<I"):
+            raise TypeError(f"{who}: `{name}` is a list of ints or a 1-D buffer of unsigned 32-bit ints")
+        buf = array.array("I", m.tobytes())
+        if len(buf) and max(buf) >= bound:
+            k = next(k for k, i in enumerate(buf) if i >= bound)
+            raise ValueError(f"{who}: {name}[{k}] = {buf[k]} is not in [0, {bound})")
+    assert buf.itemsize == 4
+    return (C.c_uint32 * len(buf)).from_buffer(buf) if len(buf) else (C.c_uint32 * 1)()
+
+
+_ORIENTATIONS = {"rows": _native.MSMZ_MAT_ROWS, "cols": _native.MSMZ_MAT_COLS,
+                 "both": _native.MSMZ_MAT_ROWS | _native.MSMZ_MAT_COLS}
+
+
+def sparse_matrix_args(rows, cols, values, shape, orientations, firstValue, order, who="sparseMatrix"):
+    """Arguments of sparseMatrix -> dict(row, col, nnz, shape, flags, firstValue, upload), checked before anything
+    reaches the device.  row / col: ctypes arrays of uint32; upload: the 32-byte records of a host value list, or None
+    (`values` is a resident array or absent)."""
+    if not (isinstance(shape, (list, tuple)) and len(shape) == 2 and all(_is_int(d) for d in shape)):
+        raise TypeError(f"{who}: `shape` is a pair of ints (nRows, nCols)")
+    if orientations not in _ORIENTATIONS:
+        raise ValueError(f"{who}: orientations = {orientations!r} (\"rows\", \"cols\" or \"both\")")
+    n_rows, n_cols = shape
+    for name, d in (("nRows", n_rows), ("nCols", n_cols)):
+        if not 1 <= d < 1 << 32:
+            raise ValueError(f"{who}: {name} = {d}")
+    row = _index_array("rows", rows, n_rows, who)
+    col = _index_array("cols", cols, n_cols, who)
+    nnz = len(rows)
+    if len(cols) != nnz:
+        raise ValueError(f"{who}: {nnz} rows but {len(cols)} cols")
+    if not 1 <= nnz < 1 << 32:
+        raise ValueError(f"{who}: N = {nnz!r}")
+    upload = None
+    _mle_first("firstValue", firstValue, values if _is_array(values, "scalars") else None, who)
+    if _is_array(values, "scalars"):
+        if nnz > len(values) - firstValue:
+            raise ValueError(f"{who}: entries [{firstValue}, +{nnz}) from firstValue of an array of {len(values)}")
+    elif isinstance(values, (list, tuple)):
+        if len(values) != nnz:
+            raise ValueError(f"{who}: {nnz} rows but {len(values)} values")
+        recs = []
+        for k, v in enumerate(values):
+            if _is_int(v):
+                if not 0 <= v < order:
+                    raise ValueError(f"{who}: values[{k}] = {v} is not in [0, group order)")
+                recs.append(v.to_bytes(32, "little"))
+            elif isinstance(v, (bytes, bytearray)) and len(v) == 32:
+                if int.from_bytes(v, "little") >= order:
+                    raise ValueError(f"{who}: values[{k}] is not in [0, group order)")
+                recs.append(bytes(v))
+            else:
+                raise TypeError(f"{who}: a value is an int or 32 little-endian bytes")
+        upload = b"".join(recs)
+    elif values is not None:
+        raise TypeError(f"{who}: `values` is a resident scalar array, a list of ints or of 32-byte records, or None")
+    return {"row": row, "col": col, "nnz": nnz, "shape": (n_rows, n_cols), "flags": _ORIENTATIONS[orientations],
+            "firstValue": firstValue, "upload": upload}
+
+
+def mat_vec_args(matrix, x, firstX, transpose, out, firstOut, who="matVec"):
+    """Arguments of matVec -> dict(N, flags), checked before anything reaches the device.  N: the entries written."""
+    if not isinstance(matrix, SparseMatrix):
+        raise TypeError(f"{who}: `matrix` is a sparse matrix (sparseMatrix)")
+    if not _is_array(x, "scalars"):
+        raise TypeError(f"{who}: `x` is a resident scalar array")
+    if out is not None and not _is_array(out, "scalars"):
+        raise TypeError(f"{who}: `out` is a resident scalar array or None")
+    if not isinstance(transpose, bool):
+        raise TypeError(f"{who}: `transpose` is a bool")
+    if matrix.handle is None:
+        raise ValueError(f"{who}: the matrix was freed")
+    need = "cols" if transpose else "rows"
+    if matrix.orientations not in (need, "both"):
+        raise ValueError(f"{who}: transpose={transpose} needs a matrix built with orientations=\"{need}\" or \"both\", "
+                         f"this one has \"{matrix.orientations}\"")
+    n_out, n_in = matrix.shape if not transpose else matrix.shape[::-1]
+    _mle_first("firstX", firstX, x, who)
+    _mle_first("firstOut", firstOut, out, who)
+    if n_in > len(x) - firstX:
+        raise ValueError(f"{who}: entries [{firstX}, +{n_in}) from firstX of an array of {len(x)}")
+    if out is not None:
+        if n_out > len(out) - firstOut:
+            raise ValueError(f"{who}: entries [{firstOut}, +{n_out}) from firstOut of an array of {len(out)}")
+        if out.handle == x.handle and firstOut < firstX + n_in and firstX < firstOut + n_out:
+            raise ValueError(f"{who}: the destination [{firstOut}, +{n_out}) overlaps the input range [{firstX}, +{n_in}) "
+                             "(firstX); x is gathered, so the two may not meet at all")
+    return {"N": n_out, "flags": _native.MSMZ_MATVEC_TRANSPOSE if transpose else 0}
 
 
 def check_arg(check, who):

@@ -792,12 +792,82 @@ static napi_value ScalarsSumcheckRound(napi_env env, napi_callback_info info) {
   return buf;
 }
 
-/* descriptorSizes() -> {mleBind, sumcheck, sumcheckTable, sumcheckTerm, maxTables, maxDegree, maxTerms}: what the addon
-   was compiled with, for the host to check its packing against (no context) */
-static napi_value DescriptorSizes(napi_env env, napi_callback_info info) {
-  (void)info;
+/* matrixCreate(ctx, rows, cols (Buffers of nnz little-endian u32 each), nnz, valHandle (0 = every value is 1), valFirst,
+   nRows, nCols, flags (1 = rows, 2 = cols, 3 = both)) -> handle of a new sparse matrix  (msmz_matrix_create) */
+static napi_value MatrixCreate(napi_env env, napi_callback_info info) {
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  msmz_sparse s; memset(&s, 0, sizeof(s));
+  uint64_t n_rows, n_cols, flags, h = 0;
+  void *rp, *cp; size_t rl, cl;
+  if (!get_args(env, info, 9, argv, &ctx) || !opt_buffer(env, argv[1], &rp, &rl) || !opt_buffer(env, argv[2], &cp, &cl) ||
+      !get_u64(env, argv[3], &s.nnz) || s.nnz == 0 || s.nnz >> 32 || rl < 4 * s.nnz || cl < 4 * s.nnz ||
+      !get_u64(env, argv[4], &s.val_handle) || !get_u64(env, argv[5], &s.val_first) || !get_u64(env, argv[6], &n_rows) ||
+      n_rows >> 32 || !get_u64(env, argv[7], &n_cols) || n_cols >> 32 || !get_u64(env, argv[8], &flags) || flags >> 32)
+    return BAD_ARG(env, "matrixCreate");
+  uint32_t* idx = (uint32_t*)malloc(8 * (size_t)s.nnz);   /* (a Buffer need not be aligned) */
+  if (!idx) return throw_status(env, MSMZ_ERR_HIP, "matrixCreate");
+  memcpy(idx, rp, 4 * (size_t)s.nnz);
+  memcpy(idx + s.nnz, cp, 4 * (size_t)s.nnz);
+  s.row = idx; s.col = idx + s.nnz;
+  s.n_rows = (uint32_t)n_rows; s.n_cols = (uint32_t)n_cols; s.flags = (uint32_t)flags;
+  int st = msmz_matrix_create(ctx, &s, &h);
+  free(idx);
+  if (st) return throw_status(env, st, "msmz_matrix_create");
+  return make_handle(env, h);
+}
+
+/* matrixInfo(ctx, handle) -> {nRows, nCols, nnz, flags}  (msmz_matrix_info) */
+static napi_value MatrixInfo(napi_env env, napi_callback_info info) {
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  uint64_t h, nnz = 0;
+  uint32_t n_rows = 0, n_cols = 0, flags = 0;
+  if (!get_args(env, info, 2, argv, &ctx) || !get_u64(env, argv[1], &h)) return BAD_ARG(env, "matrixInfo");
+  int st = msmz_matrix_info(ctx, h, &n_rows, &n_cols, &nnz, &flags);
+  if (st) return throw_status(env, st, "msmz_matrix_info");
   napi_value res;
   NAPI_CALL(env, napi_create_object(env, &res));
+  set_num(env, res, "nRows", (double)n_rows);
+  set_num(env, res, "nCols", (double)n_cols);
+  set_num(env, res, "nnz", (double)nnz);
+  set_num(env, res, "flags", (double)flags);
+  return res;
+}
+
+/* matrixMul(ctx, matrix, xHandle, xFirst, flags (1 = transposed), firstOut, outHandle (0 = a new array)) -> handle of
+   the array written  (msmz_matrix_mul) */
+static napi_value MatrixMul(napi_env env, napi_callback_info info) {
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  msmz_matvec v; memset(&v, 0, sizeof(v));
+  uint64_t flags, first_out, h = 0;
+  if (!get_args(env, info, 7, argv, &ctx) || !get_u64(env, argv[1], &v.matrix) || !get_u64(env, argv[2], &v.x_handle) ||
+      !get_u64(env, argv[3], &v.x_first) || !get_u64(env, argv[4], &flags) || flags >> 32 ||
+      !get_u64(env, argv[5], &first_out) || !get_u64(env, argv[6], &h))
+    return BAD_ARG(env, "matrixMul");
+  v.flags = (uint32_t)flags;
+  int st = msmz_matrix_mul(ctx, &v, first_out, &h);
+  if (st) return throw_status(env, st, "msmz_matrix_mul");
+  return make_handle(env, h);
+}
+
+/* descriptorSizes() -> {mleBind, sumcheck, sumcheckTable, sumcheckTerm, maxTables, maxDegree, maxTerms}: what the addon
+   was compiled with, for the host to check its packing against (no context).  descriptorSizes("matrix") -> {sparse,
+   matvec, matRows, matCols, matvecTranspose}: the same for the descriptors and flags of the sparse-matrix calls (the
+   call without an argument answers what it always did). */
+static napi_value DescriptorSizes(napi_env env, napi_callback_info info) {
+  napi_value res, argv[MAX_ARGS];
+  size_t argc = MAX_ARGS;
+  char family[16] = "";
+  size_t got = 0;
+  NAPI_CALL(env, napi_create_object(env, &res));
+  if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) == napi_ok && argc >= 1 &&
+      napi_get_value_string_utf8(env, argv[0], family, sizeof(family), &got) == napi_ok && strcmp(family, "matrix") == 0) {
+    set_num(env, res, "sparse", (double)sizeof(msmz_sparse));
+    set_num(env, res, "matvec", (double)sizeof(msmz_matvec));
+    set_num(env, res, "matRows", (double)MSMZ_MAT_ROWS);
+    set_num(env, res, "matCols", (double)MSMZ_MAT_COLS);
+    set_num(env, res, "matvecTranspose", (double)MSMZ_MATVEC_TRANSPOSE);
+    return res;
+  }
   set_num(env, res, "mleBind", (double)sizeof(msmz_mle_bind));
   set_num(env, res, "sumcheck", (double)sizeof(msmz_sumcheck));
   set_num(env, res, "sumcheckTable", (double)sizeof(msmz_sumcheck_table));
@@ -849,6 +919,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"scalarsNtt", ScalarsNtt}, {"scalarsRootOfUnity", ScalarsRootOfUnity},
       {"scalarsEqTable", ScalarsEqTable}, {"scalarsMleEval", ScalarsMleEval}, {"scalarsMleBind", ScalarsMleBind},
       {"scalarsSumcheckRound", ScalarsSumcheckRound}, {"descriptorSizes", DescriptorSizes},
+      {"matrixCreate", MatrixCreate}, {"matrixInfo", MatrixInfo}, {"matrixMul", MatrixMul},
       {"pointAdd", PointAdd}, {"feBytes", FeBytes}};
   for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); i++) {
     napi_value f;
