@@ -90,6 +90,23 @@ int msmz_test_set_limits(msmz_ctx* ctx, uint64_t pass_entries, uint64_t batch_en
  *   range_passes: iterations of run_problems' range loop (an ordinary single-problem MSM adds 1);
  *   sub_batches : batched pipelines (more than one problem) that ran to a result (not PER_PROBLEM). */
 int msmz_test_passes(msmz_ctx* ctx, uint64_t* range_passes, uint64_t* sub_batches);
+/* Scratch is undefined at the start of every call: this makes it so.  pattern 0..255:
+ *   (a) fills every device scratch buffer the context's engines own with the byte, over its whole capacity (the
+ *       allocation's headroom included), on the engine's stream, and waits;
+ *   (b) arms the context: from now on every device buffer that is newly allocated -- scratch that grows, the memory of
+ *       every new handle (result sets, precomputed sets, matrix forms), a new cached table -- is filled with the byte
+ *       before anything else touches it.
+ * pattern -1 disarms (and fills nothing); any other value is MSMZ_ERR_ARG, as is a null context.  Not filled by (a),
+ * because they hold what stays valid across calls: the records of existing handles, the twiddle and fixed-base table
+ * caches, the generator table; pinned host memory is outside the hook.  *buffers / *bytes (either nullable): the
+ * buffers of non-zero capacity that (a) filled and the bytes written; a multi-device context: summed over its engines.
+ * Launches nothing but memsets; a context never armed pays one test of a flag where a buffer is allocated. */
+int msmz_test_poison(msmz_ctx* ctx, int pattern, uint64_t* buffers, uint64_t* bytes);
+/* What fill (a) of msmz_test_poison would write on engine `engine` (0 .. msmz_ctx_n_devices - 1) of the context alone,
+ * without writing it: its scratch buffers of non-zero capacity and their bytes (either pointer nullable).  So a test can
+ * hold the sums that a multi-device context reports against its engines' own counts.  MSMZ_ERR_ARG: a null context, no
+ * such engine. */
+int msmz_test_scratch(msmz_ctx* ctx, int engine, uint64_t* buffers, uint64_t* bytes);
 /* The geometry of msmz_scalars_dot (csrc/scalar_kernels.h), so a test can size itself at its edges (either pointer
  * nullable; needs no context):
  *   tile_elements    : elements one workgroup of the first level sums into one partial sum (SDOT_TILE);

@@ -225,6 +225,8 @@ EXPORTS = {
     "msmz_test_set_glv_bits": (C.c_int, [C.c_void_p, C.c_int]),
     "msmz_test_retries": (C.c_int, [C.c_void_p]),
     "msmz_test_set_limits": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
+    "msmz_test_poison": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "msmz_test_scratch": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "msmz_test_passes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "msmz_test_scalar_dot_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "msmz_test_scalar_scan_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

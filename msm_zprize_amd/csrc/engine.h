@@ -74,6 +74,7 @@ class Engine : public ResidentSets<Cfg> {
   using typename Base::Fr;
   using Base::NW, Base::RW, Base::FE_BYTES, Base::TE, Base::PW_WORDS;
   using Base::device_, Base::stream_, Base::handles_, Base::stage_, Base::meta_, Base::h_meta_, Base::h_res_;
+  using Base::poison_;
   using Base::copy_h2d, Base::fetch_error, Base::new_handle, Base::add_handle;
   static constexpr int XW = 4 * NW;      // XYZZ / extended record words
  public:
@@ -82,6 +83,7 @@ class Engine : public ResidentSets<Cfg> {
   int init() {
     int st;
     if ((st = Base::init_sets())) return st;
+    each_scratch([&](DevBuf& b) { b.poison = &poison_; });
     for (hipEvent_t* e : ev_.all()) MSMZ_HIP(hipEventCreate(e));
     if ((st = h_res_.ensure((size_t)2 * kMaxWindows * XW * 4))) return st;   // the results of one problem
     if ((st = sort_.init(device_))) return st;   // (the sort kernels' LDS limits, once)
@@ -271,6 +273,37 @@ class Engine : public ResidentSets<Cfg> {
     if (sub_batches) *sub_batches = sub_batches_;
   }
   ITestHooks* test_hooks() override { return &hooks_; }
+  // msmz_test_poison: arm (or disarm) the allocations to come, and fill what every stage holds now, headroom included
+  int test_poison(int pattern, uint64_t* buffers, uint64_t* bytes) override {   // (pattern: checked by msmz_test_poison)
+    uint64_t nbuf = 0, nbytes = 0;
+    poison_.pattern = pattern;
+    if (pattern >= 0) {
+      MSMZ_HIP(hipSetDevice(device_));
+      hipError_t e = hipSuccess;
+      each_scratch([&](DevBuf& b) {
+        if (b.bytes == 0 || e != hipSuccess) return;
+        e = hipMemsetAsync(b.p, pattern, b.bytes, stream_);
+        nbuf++;
+        nbytes += b.bytes;
+      });
+      MSMZ_HIP(e);
+      MSMZ_HIP(hipStreamSynchronize(stream_));
+    }
+    if (buffers) *buffers = nbuf;
+    if (bytes) *bytes = nbytes;
+    return MSMZ_OK;
+  }
+  // msmz_test_scratch: the scratch buffers that hold memory now and their capacities (what a fill would write)
+  int test_scratch(int engine, uint64_t* buffers, uint64_t* bytes) override {
+    if (engine != 0) return MSMZ_ERR_ARG;
+    uint64_t nbuf = 0, nbytes = 0;
+    each_scratch([&](DevBuf& b) {
+      if (b.bytes) nbuf++, nbytes += b.bytes;
+    });
+    if (buffers) *buffers = nbuf;
+    if (bytes) *bytes = nbytes;
+    return MSMZ_OK;
+  }
 
   // ------------------------------------------------------------------------------------------ what only the engine calls
  private:
@@ -422,6 +455,15 @@ class Engine : public ResidentSets<Cfg> {
     *redo = Redo::NONE;
     st = attempt(1, redo);
     return *redo == Redo::PROVEN_BITS ? MSMZ_ERR_ARG : st;
+  }
+
+  // f(buffer) for every scratch buffer of the engine: the resident-set operations', the stages' and the pipeline's own
+  template <class Fn>
+  void each_scratch(Fn f) {
+    Base::each_scratch(f);
+    sort_.each_scratch(f);
+    reduce_.each_scratch(f);
+    f(desc_), f(bfin_), f(rscan_), f(partials_), f(slots_), f(segs_);
   }
 
   // ------------------------------------------------------------------------------------------ shared phases

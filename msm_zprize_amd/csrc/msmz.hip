@@ -373,6 +373,13 @@ int msmz_test_passes(msmz_ctx* c, uint64_t* range_passes, uint64_t* sub_batches)
   c->engine->test_passes(range_passes, sub_batches);
   return MSMZ_OK;
 }
+int msmz_test_poison(msmz_ctx* c, int pattern, uint64_t* buffers, uint64_t* bytes) {
+  if (!c || pattern < -1 || pattern > 255) return MSMZ_ERR_ARG;   // (the outputs stay as they were)
+  return c->engine->test_poison(pattern, buffers, bytes);
+}
+int msmz_test_scratch(msmz_ctx* c, int engine, uint64_t* buffers, uint64_t* bytes) {
+  return c ? c->engine->test_scratch(engine, buffers, bytes) : MSMZ_ERR_ARG;
+}
 int msmz_test_field(msmz_ctx* c, int op, const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out) {
   return c ? c->engine->test_hooks()->test_field(op, a, b, n, out) : MSMZ_ERR_ARG;
 }

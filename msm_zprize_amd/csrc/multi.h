@@ -533,6 +533,23 @@ class MultiEngine : public IEngine {
     if (range_passes) *range_passes = rp;
     if (sub_batches) *sub_batches = sb;
   }
+  int test_poison(int pattern, uint64_t* buffers, uint64_t* bytes) override {   // every engine's; the sums
+    uint64_t tb = 0, ty = 0;
+    const int st = on_every([&](IEngine* e) {
+      uint64_t nb = 0, by = 0;
+      const int s = e->test_poison(pattern, &nb, &by);
+      tb += nb, ty += by;
+      return s;
+    });
+    if (st) return st;
+    if (buffers) *buffers = tb;
+    if (bytes) *bytes = ty;
+    return MSMZ_OK;
+  }
+  int test_scratch(int engine, uint64_t* buffers, uint64_t* bytes) override {   // one engine's own
+    if (engine < 0 || (uint32_t)engine >= G_) return MSMZ_ERR_ARG;
+    return workers_[engine]->eng->test_scratch(0, buffers, bytes);
+  }
   ITestHooks* test_hooks() override { return workers_[0]->eng->test_hooks(); }
 
  private:

@@ -206,6 +206,13 @@ class BucketReduce {
   // the window results of the last levels() (run_2d, weighted_sums): one accumulator record per problem
   const uint32_t* final() const { return final_.as<uint32_t>(); }
 
+  // f(buffer) for every device buffer of the stage: all scratch, undefined at the start of every reduction
+  template <class Fn>
+  void each_scratch(Fn f) {
+    for (DevBuf& b : red_) f(b);
+    f(final_), f(bsum_), f(f2desc_);
+  }
+
  private:
   // level pair p in {0, 1}: the rows and the C (running-sum) records of a level; a level reads one pair and writes the other
   uint32_t* rows(int p) const { return red_[p * 2].as<uint32_t>(); }

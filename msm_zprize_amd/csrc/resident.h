@@ -47,7 +47,17 @@ class ResidentSets : public IEngine {
     MSMZ_HIP(hipSetDevice(device_));
     MSMZ_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
     MSMZ_HIP(hipEventCreateWithFlags(&import_ev_, hipEventDisableTiming));
+    poison_.stream = stream_;
+    gen_table_.poison = &poison_;   // (the scratch buffers: bound by Engine::init, through its each_scratch)
     return h_meta_.ensure(sizeof(MsmMeta));
+  }
+
+  // f(buffer) for every scratch buffer of the operations here: undefined at the start of every call.  Not
+  // among them, because they hold what stays valid across calls: the records of the handles, gen_table_ and the two
+  // caches -- those are bound to poison_ too, so a NEW one is filled when the engine is armed, but never refilled.
+  template <class Fn>
+  void each_scratch(Fn f) {
+    f(stage_), f(meta_), f(sdot_), f(mat_carry_), f(sscan_), f(ntt_scratch_), f(ntt_coset_), f(check_);
   }
 
  public:
@@ -811,6 +821,7 @@ class ResidentSets : public IEngine {
     const uint32_t flags = s.flags ? s.flags : (uint32_t)MSMZ_MAT_ROWS;
     MSMZ_HIP(hipSetDevice(device_));
     Handle hd;
+    hd.form[0].poison = hd.form[1].poison = &poison_;
     hd.kind = 2, hd.n = nnz, hd.n_rows = s.n_rows, hd.n_cols = s.n_cols, hd.mat_flags = flags, hd.has_vals = vals != nullptr;
     std::vector<uint32_t> host[2];   // per form: seg, gidx, perm in a row; alive until the wait below
     const size_t val_off = mat_val_offset(nnz);
@@ -927,9 +938,8 @@ class ResidentSets : public IEngine {
   // a new handle and its device memory (owned by it: an error before add_handle frees it)
   int new_handle(Handle* hd, int kind, uint64_t n, bool endo, size_t bytes) {
     *hd = Handle{kind, n, endo};
-    MSMZ_HIP(hipMalloc(&hd->mem.p, bytes));
-    hd->mem.bytes = bytes;
-    return MSMZ_OK;
+    hd->mem.poison = hd->form[0].poison = hd->form[1].poison = &poison_;
+    return hd->mem.alloc_exact(bytes);
   }
   int new_points(uint64_t n, Handle* hd) {
     if (!points_fit(n)) return MSMZ_ERR_ARG;
@@ -1203,6 +1213,7 @@ class ResidentSets : public IEngine {
       }
     }
     NttTwiddles c;
+    c.mem.poison = &poison_;
     c.log_n = plan.log_n;
     memcpy(c.w, w, 32);
     if (int st = c.mem.ensure((size_t)ntt_twiddle_entries(plan) * 32)) return st;
@@ -1271,6 +1282,7 @@ class ResidentSets : public IEngine {
       }
     }
     FixedTable ft;
+    ft.mem.poison = &poison_;
     ft.key = key;
     if (int st = ft.mem.ensure((size_t)plan.entries * RW * 4)) return st;
     if (int st = stage_.ensure(bases.size() * 4)) return st;
@@ -1323,6 +1335,7 @@ class ResidentSets : public IEngine {
   int device_;
   hipStream_t stream_ = nullptr;
   HandleTable handles_;
+  Poison poison_;                      // msmz_test_poison: armed or not; every device buffer of the engine points here
   DevBuf stage_;                       // host data on its way to a kernel, results on their way back
   DevBuf meta_;                        // MsmMeta: the error word every kernel here reports through; the pipeline's totals
   PinnedOne<MsmMeta> h_meta_;          // ... and its pinned landing

@@ -206,6 +206,12 @@ class BucketSort {
   const uint32_t* bins() const { return bins_.as<uint32_t>(); }
   const uint32_t* packed() const { return packed_.as<uint32_t>(); }
 
+  // f(buffer) for every device buffer of the stage: all scratch, undefined at the start of every run()
+  template <class Fn>
+  void each_scratch(Fn f) {
+    f(packed_), f(bins_), f(counts_), f(tilecnt_), f(tileoff_), f(digits_), f(cursor_), f(refs_), f(off_), f(partials_);
+  }
+
  private:
   // dynamic LDS the sort kernels may be launched with (run() never asks for more: SORT_MAX_BINS caps nbins)
   static constexpr size_t kFineLds = ((size_t)(1 << FINE_MAX_BITS) + FINE_STAGE) * 4;

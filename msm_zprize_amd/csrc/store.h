@@ -23,18 +23,34 @@ namespace msmz {
     }                                                                                      \
   } while (0)
 
+// msmz_test_poison (include/msmz_test.h): the byte an armed engine fills every device buffer with that ensure newly
+// allocates (-1: not armed), on the engine's stream.  One per engine; a DevBuf bound to it points here (`poison`).
+struct Poison {
+  int pattern = -1;
+  hipStream_t stream = nullptr;
+};
+
 // Memory owned by one object, grow-only: freed when it goes out of scope, so every error path releases it.  DEVICE:
 // device memory, grown with headroom.  Otherwise pinned host memory: where a device-to-host copy lands, or a
-// host-to-device copy starts, without a second host wait.
+// host-to-device copy starts, without a second host wait.  What a new allocation holds is undefined ("Scratch
+// is undefined at the start of every call"): a device buffer bound to an armed Poison is filled to show it.
 template <bool DEVICE>
-struct OwnedBuf {
+struct PoisonRef {                  // (only a device buffer carries one)
+  const Poison* poison = nullptr;   // the owning engine's, or null: never filled
+};
+template <>
+struct PoisonRef<false> {};
+
+template <bool DEVICE>
+struct OwnedBuf : PoisonRef<DEVICE> {
   void* p = nullptr;
   size_t bytes = 0;
   OwnedBuf() = default;
-  OwnedBuf(OwnedBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr, o.bytes = 0; }
+  OwnedBuf(OwnedBuf&& o) noexcept : PoisonRef<DEVICE>(o), p(o.p), bytes(o.bytes) { o.p = nullptr, o.bytes = 0; }
   OwnedBuf& operator=(OwnedBuf&& o) noexcept {
     if (this != &o) {
       release();
+      PoisonRef<DEVICE>::operator=(o);
       p = o.p, bytes = o.bytes;
       o.p = nullptr, o.bytes = 0;
     }
@@ -57,7 +73,21 @@ struct OwnedBuf {
       MSMZ_HIP(hipHostMalloc(&p, need));
     }
     bytes = sz;
+    if constexpr (DEVICE) MSMZ_HIP(fill_if_armed());
     return MSMZ_OK;
+  }
+  // exactly `need` bytes for an empty buffer: the records of a new handle, which never grow
+  int alloc_exact(size_t need) {
+    static_assert(DEVICE, "handles live on the device");
+    MSMZ_HIP(hipMalloc(&p, need));
+    bytes = need;
+    MSMZ_HIP(fill_if_armed());
+    return MSMZ_OK;
+  }
+  // msmz_test_poison: what was just allocated, filled with the armed engine's byte before anything else touches it
+  hipError_t fill_if_armed() {
+    const Poison* a = this->poison;
+    return a && a->pattern >= 0 ? hipMemsetAsync(p, a->pattern, bytes, a->stream) : hipSuccess;
   }
   void release() {
     if (p) (void)(DEVICE ? hipFree(p) : hipHostFree(p));
