@@ -739,6 +739,51 @@ int msmz_matrix_create(msmz_ctx* ctx, const msmz_sparse* s, uint64_t* handle);
 int msmz_matrix_info(msmz_ctx* ctx, uint64_t handle, uint32_t* n_rows, uint32_t* n_cols, uint64_t* nnz, uint32_t* flags);
 int msmz_matrix_mul(msmz_ctx* ctx, const msmz_matvec* v, uint64_t first_out, uint64_t* out_handle);
 
+/* Lookup arguments: the multiplicities of a column in a table.  For a table t = entries
+ * [table_first, table_first + table_n) of a scalar set and a column f = entries [col_first, col_first + col_n) of one,
+ * msmz_scalars_lookup makes the vector m that a logUp argument (Halo2 lookups, Plonky3, Lasso's offline memory
+ * checking) commits to, with nothing but the result words crossing to the host.  The reference has no analogue.
+ *
+ * The output is a scalar set of table_n entries, each a canonical 32-byte value:
+ *     m_j = #{ i < col_n : f_i = t_j }   if j is the lowest index among the table entries that hold the value t_j,
+ *     m_j = 0                            for every later duplicate of a table value.
+ * With that rule  sum_j m_j / (beta + t_j) = sum_i 1 / (beta + f_i)  holds whenever n_missing == 0, and the result does
+ * not depend on any execution order: two calls return the same bytes.  Values are compared as integers below q.
+ *
+ * A query, not a check (the stance of msmz_check_points): a column entry that equals no table entry is not an error.
+ * The call returns MSMZ_OK with the counts of what was found and, if `res` is given, n_missing, first_missing and
+ * n_distinct.  If `positions` is given, positions[i] = the index, relative to table_first, of the FIRST table entry
+ * equal to f_i, 0xffffffff where there is none.
+ *
+ * The output rules are those of msmz_scalars_combine: *out_handle == 0 makes a new set of table_n entries and first_out
+ * must be 0; otherwise only [first_out, first_out + table_n) of that handle is written.  One exception: both inputs are
+ * gathered, so a destination that meets the table range or the column range of the same handle anywhere, the exact
+ * range included, is MSMZ_ERR_ARG.  Table and column may share a handle and may overlap each other.
+ *
+ * MSMZ_ERR_ARG, before any launch: a null ctx, descriptor or out_handle; table_n == 0, col_n == 0, table_n > 2^30 or
+ * col_n >= 2^32; non-zero flags; an unknown handle or one that is not a scalar set; a range beyond its set; first_out
+ * != 0 with a new handle; the overlap above.  MSMZ_ERR_RANGE: a resident entry >= q inside either addressed range,
+ * found by the kernels (entries outside the ranges are not read); no handle is created, *out_handle, *res and
+ * positions are as they were, an in-place destination is unspecified and the context stays usable.
+ * MSMZ_ERR_UNSUPPORTED: a multi-device context -- a probe reads across every block of 2^16 entries (the stance of
+ * msmz_matrix_mul).  Device scratch: 4 S bytes for the index, S the power of two with 2 table_n <= S < 4 table_n, 4
+ * table_n for the counts and, with positions, 4 col_n.  One host wait per call: the error word, the three result words
+ * and the positions come back behind it. */
+typedef struct msmz_lookup {
+  uint64_t table_handle, table_first, table_n;  /* t: entries [table_first, table_first + table_n) of a scalar set */
+  uint64_t col_handle, col_first, col_n;        /* f: the looked-up values */
+  uint32_t* positions;   /* nullable, HOST memory, col_n words: index (relative to table_first) of the first table
+                            entry equal to f_i, 0xffffffff where there is none */
+  uint32_t flags;        /* must be 0 */
+} msmz_lookup;           /* 64 bytes */
+typedef struct msmz_lookup_result {
+  uint64_t n_missing;      /* entries of f that equal no table entry */
+  uint64_t first_missing;  /* the LOWEST such i (relative to col_first), ~0 if none */
+  uint64_t n_distinct;     /* distinct values among the table entries */
+} msmz_lookup_result;      /* 24 bytes */
+int msmz_scalars_lookup(msmz_ctx* ctx, const msmz_lookup* l, uint64_t first_out, uint64_t* out_handle,
+                        msmz_lookup_result* res /* nullable */);
+
 /* Host-side group addition of two canonical affine results: combines per-GPU partial sums
  * (the reference's "partition sum" step, msm-batched-affine.ts:300-307). */
 int msmz_point_add(int curve_id, const uint8_t* a_xy_le, int a_is_inf, const uint8_t* b_xy_le, int b_is_inf,

@@ -139,6 +139,20 @@ void msmz_test_mle_geometry(uint32_t* run, uint32_t* eval_tile, uint32_t* round_
  *   run             : consecutive non-zeros one thread walks (MAT_RUN);
  *   carries_per_pass: tile carries the one workgroup of the fold takes per pass of its loop (MAT_FOLD_PASS). */
 void msmz_test_matrix_geometry(uint32_t* tile, uint32_t* run, uint32_t* carries_per_pass);
+/* msmz_scalars_lookup (csrc/lookup_kernels.h); both need no context.
+ *   msmz_test_lookup_geometry: min_slots = the slots of the smallest index (a table of one entry: lk_slots(1));
+ *     threads_per_workgroup = the threads of a workgroup of all three kernels (LK_THREADS).  Every pointer nullable.
+ *   msmz_test_lookup_small_table: the largest table whose counts k_lookup_count_small keeps in LDS (LK_SMALL_TABLE; one
+ *     entry more and k_lookup_count runs); *passes = the passes of threads_per_workgroup column entries a workgroup of it
+ *     takes at the least (LK_SMALL_PASSES), *max_groups = the most workgroups it launches (LK_SMALL_GROUPS): a column of
+ *     more than passes * threads * max_groups entries makes every workgroup loop longer.  Both pointers nullable.
+ *   msmz_test_lookup_slot: the first slot the engine probes for the canonical value le32 (32 little-endian bytes) in a
+ *     table of table_n entries, from the host by the same hash the kernels run -- for tests that build tables whose keys
+ *     all start at one slot, or at the last slot.  0xffffffff for an unknown curve, a null pointer, a value >= q or a
+ *     table_n that msmz_scalars_lookup refuses. */
+void msmz_test_lookup_geometry(uint32_t* min_slots, uint32_t* threads_per_workgroup);
+uint32_t msmz_test_lookup_small_table(uint32_t* passes, uint32_t* max_groups);
+uint32_t msmz_test_lookup_slot(int curve_id, const uint8_t* le32, uint64_t table_n);
 /* msmz_points_fixed_base (msm_zprize_amd/csrc/fixed_base.h).
  *   msmz_test_fixed_base_plan: what the planner picks for n points of a curve and a bound of `bits` (0 or >= the bit
  *     length of q: none) -- the window width, the windows K = ceil((bound + 1) / c) and the table's entries

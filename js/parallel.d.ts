@@ -34,6 +34,10 @@ export interface MatVecOptions { firstX?: number; transpose?: boolean; out?: Dev
 export function sparseMatrixArgs(rows: number[] | Uint32Array, cols: number[] | Uint32Array, values: ScalarsLike | null, options: SparseMatrixOptions):
   { rows: Uint8Array; cols: Uint8Array; nnz: number; shape: [number, number]; flags: number; firstValue: number };
 export function matVecArgs(matrix: { handle: unknown; shape: number[]; orientations: string; kind: string }, x: ScalarsLike, options?: MatVecOptions): { n: number; flags: number };
+export interface LookupOptions { firstColumn?: number; n?: number | null; firstTable?: number; tableN?: number | null; out?: DeviceArray | null; firstOut?: number; positions?: boolean }
+export interface LookupInfo { missing: number; firstMissing: number | null; distinct: number; positions?: Uint32Array }
+/** the checked arguments of Parallel.lookupMultiplicities (host only) */
+export function lookupArgs(column: ScalarsLike, table: ScalarsLike, options?: LookupOptions): { n: number; tableN: number };
 export interface DeviceArray extends Array<DeviceArray> { readonly n: number; readonly kind: "points" | "scalars" | "precomputed";
   /** precomputed point sets only (msmz_precomputed_info) */
   readonly info?: { c: number; glv: number; factor: number; K: number; records: number; scalarBits: number }; free(): void }
@@ -137,6 +141,10 @@ export interface ParallelApi {
   /** out_i = sum over the non-zeros (i, j, v) of v x[firstX + j] mod the group order, with `transpose` over (j, i, v)
    * (msmz_matrix_mul); the destination may not meet the x range.  Returns the array written. */
   matVec(matrix: SparseMatrix, x: DeviceArray, options?: MatVecOptions): Promise<DeviceArray>;
+  /** the multiplicities of a column in a table (msmz_scalars_lookup): m[j] = #{i : column[i] = table[j]} at the first
+   * index of each table value, 0 at later duplicates; a column entry in no table is counted in info.missing, not refused.
+   * The destination may meet neither input range. */
+  lookupMultiplicities(column: DeviceArray, table: DeviceArray, options?: LookupOptions): Promise<[DeviceArray, LookupInfo]>;
   /** the default primitive 2^logN-th root of unity of the scalar field (msmz_scalars_root_of_unity) */
   rootOfUnity(logN: number): bigint;
   msmBatch(scalarsList: DeviceArray | Uint8Array[], points: DeviceArray, n: number, options?: MsmOptions & { batch?: number }): Promise<BigintPoint[]>;

@@ -289,6 +289,34 @@ export function matVecArgs(matrix, x, { firstX = 0, transpose = false, out = nul
   return { n: nOut, flags: transpose ? 1 : 0 };
 }
 
+/** The arguments of Parallel.lookupMultiplicities -> {n, tableN}, checked before anything reaches the device
+ * (msm_zprize_amd/parallel.py lookup_args is the same function).  n: the column entries looked up; tableN: the table
+ * entries, which is also the entries written. */
+export function lookupArgs(column, table, { firstColumn = 0, n = null, firstTable = 0, tableN = null, out = null, firstOut = 0, positions = false } = {}) {
+  const who = "lookupMultiplicities";
+  if (!looksLikeScalars(column)) throw TypeError(`${who}: \`column\` is a resident scalar array`);
+  if (!looksLikeScalars(table)) throw TypeError(`${who}: \`table\` is a resident scalar array`);
+  if (out !== null && !looksLikeScalars(out)) throw TypeError(`${who}: \`out\` is a resident scalar array or null`);
+  if (typeof positions !== "boolean") throw TypeError(`${who}: \`positions\` is a boolean`);
+  mleFirst(who, "firstColumn", firstColumn, column);
+  mleFirst(who, "firstTable", firstTable, table);
+  mleFirst(who, "firstOut", firstOut, out);
+  const size = (name, v, first, arr, limit) => {
+    const k = v === null ? arr.n - first : v;
+    if (!Number.isInteger(k) || k < 1 || k > limit) throw Error(`${who}: ${name} = ${k}`);
+    if (k > arr.n - first) throw Error(`${who}: entries [${first}, +${k}) of an array of ${arr.n} (${name})`);
+    return k;
+  };
+  const N = size("n", n, firstColumn, column, 2 ** 32 - 1), T = size("tableN", tableN, firstTable, table, 2 ** 30);
+  if (out !== null) {
+    if (T > out.n - firstOut) throw Error(`${who}: entries [${firstOut}, +${T}) from firstOut of an array of ${out.n}`);
+    for (const [name, arr, first, len] of [["table", table, firstTable, T], ["column", column, firstColumn, N]])
+      if (out.handle === arr.handle && firstOut < first + len && first < firstOut + T)
+        throw Error(`${who}: the destination [${firstOut}, +${T}) overlaps the ${name} range [${first}, +${len}); both inputs are gathered, so it may meet neither at all`);
+  }
+  return { n: N, tableN: T };
+}
+
 /** A GPU-resident sparse matrix (msmz_matrix_create): shape = [rows, columns], nnz, the orientations it was built for */
 class SparseMatrix {
   constructor(curve, handle, shape, nnz, orientations) {
@@ -790,6 +818,27 @@ function createCurve(params, kind) {
       if (out !== null && !isScalars(out)) throw TypeError("matVec: `out` is a resident scalar array or null");
       const h = N.matrixMul(ctx, matrix.handle, x.handle, options.firstX || 0, t.flags, options.firstOut || 0, out === null ? 0 : out.handle);
       return out === null ? DeviceArray.make(curve, h, t.n, "scalars") : out;
+    },
+    /** [m, info] for the column f = column[firstColumn, +n) and the table t = table[firstTable, +tableN): m a resident
+     * scalar array of tableN entries, m[j] = #{i : f[i] = t[j]} if j is the lowest index among the table entries that hold
+     * t[j] and 0 for every later duplicate -- the vector a logUp argument commits to (msmz_scalars_lookup).  info =
+     * {missing, firstMissing (null if none), distinct} and, with positions: true, positions: a Uint32Array, the index of
+     * the first table entry equal to f[i] or 0xffffffff.  A column entry that is in no table is not an error.  `out` may
+     * meet neither the table range nor the column range of the same array.
+     * options: {firstColumn, n, firstTable, tableN, out, firstOut, positions} */
+    async lookupMultiplicities(column, table, options = {}) {
+      const t = lookupArgs(column, table, options);
+      if (!isScalars(column) || !isScalars(table)) throw TypeError("lookupMultiplicities: resident scalar arrays");
+      const out = options.out === undefined ? null : options.out;
+      if (out !== null && !isScalars(out)) throw TypeError("lookupMultiplicities: `out` is a resident scalar array or null");
+      const r = N.scalarsLookup(ctx, table.handle, options.firstTable || 0, t.tableN, column.handle, options.firstColumn || 0, t.n,
+                                options.firstOut || 0, out === null ? 0 : out.handle, options.positions === true);
+      const info = { missing: r.missing, firstMissing: r.firstMissing < 0 ? null : r.firstMissing, distinct: r.distinct };
+      if (r.positions !== null) {
+        info.positions = new Uint32Array(t.n);
+        for (let i = 0; i < t.n; i++) info.positions[i] = r.positions.readUInt32LE(4 * i);
+      }
+      return [out === null ? DeviceArray.make(curve, r.handle, t.tableN, "scalars") : out, info];
     },
     /** batched MSM: B scalar vectors against one point set (include/msmz.h msmz_msm_batch); safe additions */
     msmBatch: (scalarsList, points, n, options) => msmBatchCommon(scalarsList, points, n, options, 1),

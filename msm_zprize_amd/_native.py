@@ -121,6 +121,19 @@ class MsmzMatvec(C.Structure):   # msmz_matvec (include/msmz.h): one product of 
     _fields_ = [("matrix", C.c_uint64), ("x_handle", C.c_uint64), ("x_first", C.c_uint64), ("flags", C.c_uint32)]
 
 
+LOOKUP_NONE = 0xffffffff   # msmz_lookup.positions: no table entry equals this column entry
+
+
+class MsmzLookup(C.Structure):   # msmz_lookup (include/msmz.h): a table range, a column range, where the positions go
+    _fields_ = [("table_handle", C.c_uint64), ("table_first", C.c_uint64), ("table_n", C.c_uint64),
+                ("col_handle", C.c_uint64), ("col_first", C.c_uint64), ("col_n", C.c_uint64),
+                ("positions", C.POINTER(C.c_uint32)), ("flags", C.c_uint32)]
+
+
+class MsmzLookupResult(C.Structure):   # msmz_lookup_result (include/msmz.h)
+    _fields_ = [("n_missing", C.c_uint64), ("first_missing", C.c_uint64), ("n_distinct", C.c_uint64)]
+
+
 class MsmzSegment(C.Structure):   # msmz_segment (include/msmz.h): one problem of msmz_msm_segments
     _fields_ = [("first_p", C.c_uint64), ("first_s", C.c_uint64), ("n", C.c_uint64)]
 
@@ -220,6 +233,8 @@ EXPORTS = {
     "msmz_matrix_info": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                    C.POINTER(C.c_uint32)]),
     "msmz_matrix_mul": (C.c_int, [C.c_void_p, C.POINTER(MsmzMatvec), C.c_uint64, C.POINTER(C.c_uint64)]),
+    "msmz_scalars_lookup": (C.c_int, [C.c_void_p, C.POINTER(MsmzLookup), C.c_uint64, C.POINTER(C.c_uint64),
+                                      C.POINTER(MsmzLookupResult)]),
     "msmz_point_add": (C.c_int, [C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.POINTER(C.c_int)]),
     # stage-level test hooks (include/msmz_test.h)
     "msmz_test_set_glv_bits": (C.c_int, [C.c_void_p, C.c_int]),
@@ -233,6 +248,9 @@ EXPORTS = {
     "msmz_test_ntt_plan": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "msmz_test_ntt_geometry": (None, [C.POINTER(C.c_uint32)]),
     "msmz_test_matrix_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "msmz_test_lookup_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "msmz_test_lookup_slot": (C.c_uint32, [C.c_int, C.c_char_p, C.c_uint64]),
+    "msmz_test_lookup_small_table": (C.c_uint32, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "msmz_test_mle_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "msmz_test_fixed_base_plan": (C.c_int, [C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                             C.POINTER(C.c_uint64)]),

@@ -8,6 +8,7 @@
 #include "gen_kernels.h"
 #include "import_kernels.h"
 #include "kernels.h"
+#include "lookup_kernels.h"
 #include "matrix_kernels.h"
 #include "mle_kernels.h"
 #include "mul_kernels.h"
@@ -145,6 +146,13 @@
   PFX template __global__ void k_matrix_pack<Fr>(uint32_t*, const uint32_t*, const uint32_t*, uint32_t, uint32_t*); \
   PFX template __global__ void k_matrix_mul<Fr>(uint32_t*, MatView, const uint32_t*, uint32_t, uint32_t*, uint32_t*); \
   PFX template __global__ void k_matrix_fold<Fr>(uint32_t*, const uint32_t*, uint32_t);
+
+// the lookup kernels (lookup_kernels.h), a translation unit of their own (kern_lookup.hip)
+#define MSMZ_INST_LOOKUP(F, Fr, PFX)                                                                              \
+  PFX template __global__ void k_lookup_insert<Fr>(uint32_t*, uint32_t, const uint32_t*, uint32_t, uint32_t*);    \
+  PFX template __global__ void k_lookup_count<Fr>(uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t, const uint32_t*, const uint32_t*, uint32_t); \
+  PFX template __global__ void k_lookup_count_small<Fr>(uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t, const uint32_t*, uint32_t, const uint32_t*, uint32_t); \
+  PFX template __global__ void k_lookup_emit<Fr>(uint32_t*, const uint32_t*, uint32_t);
 
 // every curve, by policy P = WeierPolicy<F> / TePolicy<F>
 #define MSMZ_INST_MISC_P(F, Fr, P, PFX)                                                                           \

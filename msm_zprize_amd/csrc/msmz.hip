@@ -1,10 +1,10 @@
 // C ABI of the MSM engine (include/msmz.h): curve dispatch + argument checking.
 #include "instantiate.h"
 namespace msmz {
-#define X(F, Fr) MSMZ_INST_BATCH(F, Fr, MSMZ_EXTERN) MSMZ_INST_REDUCE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MISC(F, Fr, MSMZ_EXTERN) MSMZ_INST_GEN(F, Fr, MSMZ_EXTERN) MSMZ_INST_MLE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MATRIX(F, Fr, MSMZ_EXTERN)
+#define X(F, Fr) MSMZ_INST_BATCH(F, Fr, MSMZ_EXTERN) MSMZ_INST_REDUCE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MISC(F, Fr, MSMZ_EXTERN) MSMZ_INST_GEN(F, Fr, MSMZ_EXTERN) MSMZ_INST_MLE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MATRIX(F, Fr, MSMZ_EXTERN) MSMZ_INST_LOOKUP(F, Fr, MSMZ_EXTERN)
 MSMZ_WEIERSTRASS_FIELDS(X)
 #undef X
-#define X(F, Fr) MSMZ_INST_REDUCE_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MISC_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_GEN_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MLE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MATRIX(F, Fr, MSMZ_EXTERN)
+#define X(F, Fr) MSMZ_INST_REDUCE_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MISC_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_GEN_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MLE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MATRIX(F, Fr, MSMZ_EXTERN) MSMZ_INST_LOOKUP(F, Fr, MSMZ_EXTERN)
 MSMZ_TE_FIELDS(X)
 #undef X
 }  // namespace msmz
@@ -281,6 +281,34 @@ int msmz_matrix_info(msmz_ctx* c, uint64_t h, uint32_t* n_rows, uint32_t* n_cols
 }
 int msmz_matrix_mul(msmz_ctx* c, const msmz_matvec* v, uint64_t first_out, uint64_t* out_handle) {
   return c && v && out_handle ? c->engine->matrix_mul(*v, first_out, out_handle) : MSMZ_ERR_ARG;
+}
+int msmz_scalars_lookup(msmz_ctx* c, const msmz_lookup* l, uint64_t first_out, uint64_t* out_handle, msmz_lookup_result* res) {
+  return c && l && out_handle ? c->engine->scalars_lookup(*l, first_out, out_handle, res) : MSMZ_ERR_ARG;
+}
+void msmz_test_lookup_geometry(uint32_t* min_slots, uint32_t* threads_per_workgroup) {
+  if (min_slots) *min_slots = lk_slots(1);
+  if (threads_per_workgroup) *threads_per_workgroup = LK_THREADS;
+}
+uint32_t msmz_test_lookup_small_table(uint32_t* passes, uint32_t* max_groups) {
+  if (passes) *passes = LK_SMALL_PASSES;
+  if (max_groups) *max_groups = LK_SMALL_GROUPS;
+  return LK_SMALL_TABLE;
+}
+uint32_t msmz_test_lookup_slot(int curve_id, const uint8_t* le32, uint64_t table_n) {
+  if (!le32 || table_n == 0 || table_n > LK_MAX_TABLE) return LK_EMPTY;
+  uint32_t w[8];
+  memcpy(w, le32, 32);
+  auto of = [&](auto fr) {
+    using Fr = decltype(fr);
+    return words_geq<8>(w, Fr::Q) ? LK_EMPTY : lk_first_slot(w, lk_slots(table_n) - 1);
+  };
+  switch (curve_id) {
+    case MSMZ_BLS12_377_G1: return of(Bls377Fr{});
+    case MSMZ_PALLAS: return of(PallasFr{});
+    case MSMZ_BLS12_381_G1: return of(Bls381Fr{});
+    case MSMZ_ED_ON_BLS12_377: return of(Ed377Fr{});
+    default: return LK_EMPTY;
+  }
 }
 void msmz_test_matrix_geometry(uint32_t* tile, uint32_t* run, uint32_t* carries_per_pass) {
   if (tile) *tile = MAT_TILE;

@@ -20,6 +20,7 @@
 #include "check_kernels.h"
 #include "mul_kernels.h"
 #include "scalar_kernels.h"
+#include "lookup_kernels.h"
 #include "matrix_kernels.h"
 #include "mle_kernels.h"
 #include "ntt_kernels.h"
@@ -58,6 +59,7 @@ class ResidentSets : public IEngine {
   template <class Fn>
   void each_scratch(Fn f) {
     f(stage_), f(meta_), f(sdot_), f(mat_carry_), f(sscan_), f(ntt_scratch_), f(ntt_coset_), f(check_);
+    f(lookup_slots_), f(lookup_count_), f(lookup_res_);
   }
 
  public:
@@ -903,6 +905,62 @@ class ResidentSets : public IEngine {
     return st || !hd.mem.p ? st : add_handle(std::move(hd), out_handle);
   }
 
+  // ------------------------------------------------------------------------------------------ lookup arguments
+  // msmz_scalars_lookup: the index and the counts are cleared (scratch is undefined at the start of a call), then
+  // k_lookup_insert, k_lookup_count (k_lookup_count_small for a table of at most LK_SMALL_TABLE entries) and k_lookup_emit; the error word, the three result words and, if asked for, the
+  // positions behind them come back in ONE copy behind the ONE host wait.  Both inputs are gathered, so the destination
+  // may meet neither range at all.
+  int scalars_lookup(const msmz_lookup& l, uint64_t first_out, uint64_t* out_handle, msmz_lookup_result* res) override {
+    if (!out_handle || l.flags || l.table_n == 0 || l.col_n == 0 || l.table_n > LK_MAX_TABLE || l.col_n >> 32) return MSMZ_ERR_ARG;
+    const uint64_t tn = l.table_n, cn = l.col_n;
+    if (*out_handle && ((*out_handle == l.table_handle && ranges_meet(l.table_first, tn, first_out, tn)) ||
+                        (*out_handle == l.col_handle && ranges_meet(l.col_first, cn, first_out, tn))))
+      return MSMZ_ERR_ARG;
+    const uint32_t* T = nullptr;
+    const uint32_t* Fc = nullptr;
+    uint32_t* out = nullptr;
+    if (int st = resolve({{l.table_handle, l.table_first, &T, tn}, {l.col_handle, l.col_first, &Fc, cn}}, tn, first_out,
+                         *out_handle, &out))
+      return st;
+    MSMZ_HIP(hipSetDevice(device_));
+    const uint32_t slots = lk_slots(tn);
+    const size_t res_bytes = (size_t)LK_RES_WORDS * 4 + (l.positions ? cn * 4 : 0);
+    if (int st = lookup_slots_.ensure((size_t)slots * 4)) return st;
+    if (int st = lookup_count_.ensure(tn * 4)) return st;
+    if (int st = lookup_res_.ensure(res_bytes)) return st;
+    if (int st = h_lookup_.ensure(res_bytes)) return st;
+    Handle hd;
+    if (int st = fresh_out(tn, &hd, &out)) return st;
+    uint32_t* d_res = lookup_res_.as<uint32_t>();
+    uint32_t* d_pos = l.positions ? d_res + LK_RES_WORDS : nullptr;
+    MSMZ_HIP(hipMemsetAsync(lookup_slots_.p, 0xff, (size_t)slots * 4, stream_));
+    MSMZ_HIP(hipMemsetAsync(lookup_count_.p, 0, tn * 4, stream_));
+    MSMZ_HIP(hipMemsetAsync(d_res, 0, LK_RES_WORDS * 4, stream_));
+    MSMZ_HIP(hipMemsetAsync(d_res + LK_RES_FIRST, 0xff, 4, stream_));
+    const dim3 block(LK_THREADS), tgrid((uint32_t)((tn + LK_THREADS - 1) / LK_THREADS)),
+        cgrid((uint32_t)((cn + LK_THREADS - 1) / LK_THREADS));
+    hipLaunchKernelGGL((k_lookup_insert<Fr>), tgrid, block, 0, stream_, lookup_slots_.as<uint32_t>(), slots - 1, T, (uint32_t)tn, d_res);
+    if (tn <= LK_SMALL_TABLE)
+      hipLaunchKernelGGL((k_lookup_count_small<Fr>), dim3(lk_small_groups(cn)), block, 0, stream_, lookup_count_.as<uint32_t>(),
+                         d_res, d_pos, lookup_slots_.as<uint32_t>(), slots - 1, T, (uint32_t)tn, Fc, (uint32_t)cn);
+    else
+      hipLaunchKernelGGL((k_lookup_count<Fr>), cgrid, block, 0, stream_, lookup_count_.as<uint32_t>(), d_res, d_pos,
+                         lookup_slots_.as<uint32_t>(), slots - 1, T, Fc, (uint32_t)cn);
+    hipLaunchKernelGGL((k_lookup_emit<Fr>), tgrid, block, 0, stream_, out, (const uint32_t*)lookup_count_.as<uint32_t>(), (uint32_t)tn);
+    MSMZ_HIP(hipGetLastError());
+    MSMZ_HIP(hipMemcpyAsync(h_lookup_.p, d_res, res_bytes, hipMemcpyDeviceToHost, stream_));
+    MSMZ_HIP(hipStreamSynchronize(stream_));
+    const uint32_t* w = h_lookup_.as<const uint32_t>();
+    if (w[LK_RES_ERR]) return MSMZ_ERR_RANGE;   // (hd frees a fresh destination)
+    if (l.positions) memcpy(l.positions, w + LK_RES_WORDS, cn * 4);
+    if (res) {
+      res->n_missing = w[LK_RES_MISSING];
+      res->first_missing = w[LK_RES_FIRST] == LK_EMPTY ? UINT64_MAX : w[LK_RES_FIRST];
+      res->n_distinct = w[LK_RES_DISTINCT];
+    }
+    return hd.mem.p ? add_handle(std::move(hd), out_handle) : MSMZ_OK;
+  }
+
  protected:
   // Host -> device copy of this engine's `n` local records of `rec` bytes.  split == nullptr: one contiguous copy.
   // Otherwise the engine is shard `split->shard` of `split->nshards` inside a multi-device context (multi.h): its local
@@ -1356,6 +1414,10 @@ class ResidentSets : public IEngine {
   std::deque<NttTwiddles> ntt_cache_;  // ... and the twiddle tables of the last NTT_CACHE (log_n, root) pairs
   DevBuf check_;                       // check_points: its result record, then one verdict byte per point
   PinnedBuf h_check_;                  // pinned landing of the result record and the verdict bytes behind it
+  DevBuf lookup_slots_;                // scalars_lookup: the hash index, one table index or LK_EMPTY per slot
+  DevBuf lookup_count_;                // ... one count per table entry
+  DevBuf lookup_res_;                  // ... the error word and the three result words, then one position per column entry
+  PinnedBuf h_lookup_;                 // pinned landing of the result words and the positions behind them
 };
 
 }  // namespace msmz

@@ -559,6 +559,33 @@ class _Parallel:
         v = _native.MsmzMatvec(matrix.handle, x.handle, firstX, a["flags"])
         return _resident(self._c, "scalars", a["N"], "msmz_matrix_mul", C.byref(v), firstOut, out=out)
 
+    # -- lookup arguments: the multiplicities of a column in a table (msmz_scalars_lookup) -------------
+    def lookupMultiplicities(self, column, table, *, firstColumn=0, N=None, firstTable=0, tableN=None, out=None, firstOut=0,
+                             positions=False):
+        """(multiplicities, info) for the column f = column[firstColumn : firstColumn + N] and the table t =
+        table[firstTable : firstTable + tableN] (N, tableN = None: to the end of the array): a resident scalar array m of
+        tableN entries, m[j] = #{i : f[i] == t[j]} if j is the lowest index among the table entries that hold t[j] and 0
+        for every later duplicate -- the vector a logUp argument commits to, sum_j m_j / (beta + t_j) = sum_i 1 / (beta +
+        f_i).  info = {"missing": entries of f that equal no table entry (not an error), "firstMissing": the lowest such
+        index or None, "distinct": the distinct values of t}, and with positions=True "positions": a numpy uint32 array,
+        positions[i] = the index of the first table entry equal to f[i], 0xffffffff where there is none.  out=None: a new
+        array; otherwise entries [firstOut, firstOut + tableN) of `out`, which may meet neither the table range nor the
+        column range of the same array.  Table and column may be one array and may overlap."""
+        a = lookup_args(column, table, firstColumn, N, firstTable, tableN, out, firstOut, positions)
+        pos = None
+        if positions:
+            import numpy as np
+            pos = np.empty(a["N"], dtype=np.uint32)
+        l = _native.MsmzLookup(table.handle, firstTable, a["tableN"], column.handle, firstColumn, a["N"],
+                               None if pos is None else pos.ctypes.data_as(C.POINTER(C.c_uint32)), 0)
+        res = _native.MsmzLookupResult()
+        m = _resident(self._c, "scalars", a["tableN"], "msmz_scalars_lookup", C.byref(l), firstOut, after=(C.byref(res),), out=out)
+        info = {"missing": int(res.n_missing), "distinct": int(res.n_distinct),
+                "firstMissing": None if res.first_missing == _native.NO_INDEX else int(res.first_missing)}
+        if positions:
+            info["positions"] = pos
+        return m, info
+
     def _checked(self, arr, what, who):
         try:
             res = self.checkPoints(arr, subgroup=bool(what & _native.MSMZ_CHECK_SUBGROUP))
@@ -1251,6 +1278,40 @@ def mat_vec_args(matrix, x, firstX, transpose, out, firstOut, who="matVec"):
             raise ValueError(f"{who}: the destination [{firstOut}, +{n_out}) overlaps the input range [{firstX}, +{n_in}) "
                              "(firstX); x is gathered, so the two may not meet at all")
     return {"N": n_out, "flags": _native.MSMZ_MATVEC_TRANSPOSE if transpose else 0}
+
+
+def lookup_args(column, table, firstColumn, N, firstTable, tableN, out, firstOut, positions, who="lookupMultiplicities"):
+    """Arguments of lookupMultiplicities -> dict(N, tableN), checked before anything reaches the device.  N: the column
+    entries looked up; tableN: the table entries, which is also the entries written."""
+    if not _is_array(column, "scalars"):
+        raise TypeError(f"{who}: `column` is a resident scalar array")
+    if not _is_array(table, "scalars"):
+        raise TypeError(f"{who}: `table` is a resident scalar array")
+    if out is not None and not _is_array(out, "scalars"):
+        raise TypeError(f"{who}: `out` is a resident scalar array or None")
+    if not isinstance(positions, bool):
+        raise TypeError(f"{who}: `positions` is a bool")
+    _mle_first("firstColumn", firstColumn, column, who)
+    _mle_first("firstTable", firstTable, table, who)
+    _mle_first("firstOut", firstOut, out, who)
+    sizes = {}
+    for name, n, first, arr, limit in (("N", N, firstColumn, column, (1 << 32) - 1), ("tableN", tableN, firstTable, table, 1 << 30)):
+        if n is None:
+            n = len(arr) - first
+        if not _is_int(n) or not 1 <= n <= limit:
+            raise ValueError(f"{who}: {name} = {n!r}")
+        if n > len(arr) - first:
+            raise ValueError(f"{who}: entries [{first}, +{n}) of an array of {len(arr)} ({name})")
+        sizes[name] = n
+    if out is not None:
+        n_out = sizes["tableN"]
+        if n_out > len(out) - firstOut:
+            raise ValueError(f"{who}: entries [{firstOut}, +{n_out}) from firstOut of an array of {len(out)}")
+        for name, arr, first, n in (("table", table, firstTable, sizes["tableN"]), ("column", column, firstColumn, sizes["N"])):
+            if out.handle == arr.handle and firstOut < first + n and first < firstOut + n_out:
+                raise ValueError(f"{who}: the destination [{firstOut}, +{n_out}) overlaps the {name} range [{first}, +{n}); "
+                                 "both inputs are gathered, so it may meet neither at all")
+    return sizes
 
 
 def check_arg(check, who):

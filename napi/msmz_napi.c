@@ -849,18 +849,58 @@ static napi_value MatrixMul(napi_env env, napi_callback_info info) {
   return make_handle(env, h);
 }
 
+/* scalarsLookup(ctx, tableHandle, tableFirst, tableN, colHandle, colFirst, colN, firstOut, outHandle (0 = a new array),
+   wantPositions) -> {handle, missing, firstMissing (-1 = none), distinct, positions: Buffer of colN little-endian u32 or
+   null}  (msmz_scalars_lookup) */
+static napi_value ScalarsLookup(napi_env env, napi_callback_info info) {
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  msmz_lookup l; memset(&l, 0, sizeof(l));
+  uint64_t first_out, h = 0;
+  if (!get_args(env, info, 10, argv, &ctx) || !get_u64(env, argv[1], &l.table_handle) || !get_u64(env, argv[2], &l.table_first) ||
+      !get_u64(env, argv[3], &l.table_n) || !get_u64(env, argv[4], &l.col_handle) || !get_u64(env, argv[5], &l.col_first) ||
+      !get_u64(env, argv[6], &l.col_n) || l.col_n == 0 || l.col_n >> 32 || !get_u64(env, argv[7], &first_out) ||
+      !get_u64(env, argv[8], &h))
+    return BAD_ARG(env, "scalarsLookup");
+  bool want = false;
+  NAPI_CALL(env, napi_get_value_bool(env, argv[9], &want));
+  void* data = NULL; napi_value buf;
+  if (want) NAPI_CALL(env, napi_create_buffer(env, 4 * (size_t)l.col_n, &data, &buf));
+  else NAPI_CALL(env, napi_get_null(env, &buf));
+  l.positions = (uint32_t*)data;
+  msmz_lookup_result r; memset(&r, 0, sizeof(r));
+  int st = msmz_scalars_lookup(ctx, &l, first_out, &h, &r);
+  if (st) return throw_status(env, st, "msmz_scalars_lookup");
+  napi_value res;
+  NAPI_CALL(env, napi_create_object(env, &res));
+  NAPI_CALL(env, napi_set_named_property(env, res, "handle", make_handle(env, h)));
+  set_num(env, res, "missing", (double)r.n_missing);
+  set_num(env, res, "firstMissing", r.first_missing == UINT64_MAX ? -1.0 : (double)r.first_missing);
+  set_num(env, res, "distinct", (double)r.n_distinct);
+  NAPI_CALL(env, napi_set_named_property(env, res, "positions", buf));
+  return res;
+}
+
 /* descriptorSizes() -> {mleBind, sumcheck, sumcheckTable, sumcheckTerm, maxTables, maxDegree, maxTerms}: what the addon
    was compiled with, for the host to check its packing against (no context).  descriptorSizes("matrix") -> {sparse,
-   matvec, matRows, matCols, matvecTranspose}: the same for the descriptors and flags of the sparse-matrix calls (the
-   call without an argument answers what it always did). */
+   matvec, matRows, matCols, matvecTranspose}: the same for the descriptors and flags of the sparse-matrix calls;
+   descriptorSizes("lookup") -> {lookup, lookupResult, none}: the two descriptors of scalarsLookup and the position of a
+   column entry that is in no table (the call without an argument answers what it always did). */
 static napi_value DescriptorSizes(napi_env env, napi_callback_info info) {
   napi_value res, argv[MAX_ARGS];
   size_t argc = MAX_ARGS;
   char family[16] = "";
   size_t got = 0;
   NAPI_CALL(env, napi_create_object(env, &res));
-  if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) == napi_ok && argc >= 1 &&
-      napi_get_value_string_utf8(env, argv[0], family, sizeof(family), &got) == napi_ok && strcmp(family, "matrix") == 0) {
+  if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok || argc < 1 ||
+      napi_get_value_string_utf8(env, argv[0], family, sizeof(family), &got) != napi_ok)
+    family[0] = 0;
+  if (strcmp(family, "lookup") == 0) {
+    set_num(env, res, "lookup", (double)sizeof(msmz_lookup));
+    set_num(env, res, "lookupResult", (double)sizeof(msmz_lookup_result));
+    set_num(env, res, "none", (double)0xffffffffu);
+    return res;
+  }
+  if (strcmp(family, "matrix") == 0) {
     set_num(env, res, "sparse", (double)sizeof(msmz_sparse));
     set_num(env, res, "matvec", (double)sizeof(msmz_matvec));
     set_num(env, res, "matRows", (double)MSMZ_MAT_ROWS);
@@ -920,6 +960,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"scalarsEqTable", ScalarsEqTable}, {"scalarsMleEval", ScalarsMleEval}, {"scalarsMleBind", ScalarsMleBind},
       {"scalarsSumcheckRound", ScalarsSumcheckRound}, {"descriptorSizes", DescriptorSizes},
       {"matrixCreate", MatrixCreate}, {"matrixInfo", MatrixInfo}, {"matrixMul", MatrixMul},
+      {"scalarsLookup", ScalarsLookup},
       {"pointAdd", PointAdd}, {"feBytes", FeBytes}};
   for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); i++) {
     napi_value f;
