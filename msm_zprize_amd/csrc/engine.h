@@ -68,8 +68,9 @@ template <class Cfg>
 class Engine : public ResidentSets<Cfg> {
   friend class TestHooks<Cfg>;
   using Base = ResidentSets<Cfg>;
-  // what the pipeline uses of the resident sets: the curve's types and record sizes, the device and its stream, the
-  // handle table, the staging buffer, the meta block with its pinned landing, and the pinned results
+  // what the pipeline uses of the resident sets' core (SetsCore, sets_core.h): the curve's types and record sizes, the
+  // device and its stream, the handle table, the staging buffer, the meta block with its pinned landing, and the pinned
+  // results
   using typename Base::F;
   using typename Base::Fr;
   using Base::NW, Base::RW, Base::FE_BYTES, Base::TE, Base::PW_WORDS;

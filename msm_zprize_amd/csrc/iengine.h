@@ -1,4 +1,4 @@
-// What a context is to the C ABI (msmz.hip): the interface one engine (ResidentSets / Engine, resident.h / engine.h) and
+// What a context is to the C ABI (msmz.hip): the interface one engine (Engine, engine.h, over resident.h and sets_core.h) and
 // the multi-device context (MultiEngine, multi.h) both implement, with the two small things its signatures need -- how a
 // device-side generator maps local to global indices, and the checks of an import source that need no device.
 #pragma once
@@ -75,7 +75,7 @@ class IEngine {
   virtual int gather_src(const msmz_src& s, int point_fe_bytes, uint64_t n, std::vector<uint8_t>* recs,
                          std::vector<uint8_t>* flags) = 0;
   // `split` (uploads and host-scalar MSMs): the engine is one shard of a multi-device context and `n` counts its LOCAL
-  // records; the host buffer is the caller's whole array, from which the engine copies its own blocks (ResidentSets::copy_h2d)
+  // records; the host buffer is the caller's whole array, from which the engine copies its own blocks (SetsCore::copy_h2d)
   virtual int upload_points(const uint8_t* xy, const uint8_t* inf, uint64_t n, uint64_t* h, const GenMap* split = nullptr) = 0;
   virtual int upload_scalars(const uint8_t* s, uint64_t n, uint64_t* h, const GenMap* split = nullptr) = 0;
   virtual int random_points(uint64_t n, uint64_t seed, const GenMap& map, uint64_t* h) = 0;

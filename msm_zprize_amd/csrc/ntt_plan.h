@@ -1,7 +1,7 @@
 // The plan of a number-theoretic transform over a resident scalar set (msmz_scalars_ntt, include/msmz.h; DESIGN.md
 // section 20): log_n -> the train of passes, each with its stages, its column width and its strides.  Host only, no
 // HIP: tests/native/ntt_test.cpp compiles it for the CPU.  This is the single place that decides the split; the engine
-// (ResidentSets::scalars_ntt) launches one kernel per pass of the plan and ntt_kernels.h reads nothing but an NttPass.
+// (NttOps::scalars_ntt, ntt_ops.h) launches one kernel per pass of the plan and ntt_kernels.h reads nothing but an NttPass.
 //
 // The split.  n = R_1 R_2 ... R_P with R_j = 2^(s_j).  Write an input index i = sum_j i_j S_j with S_j = R_(j+1) .. R_P
 // (i_1 is the most significant digit) and an output index k = sum_j k_j T_j with T_j = R_1 .. R_(j-1) (k_1 is the least

@@ -1,6 +1,6 @@
 // What one engine keeps on its device and hands out by id: owning device and pinned host buffers, the handle of a
 // resident set, and the table of handles.  Everything here frees itself, on whatever device is selected at the time:
-// the engine's destructor selects its own first (ResidentSets::~ResidentSets, resident.h).
+// the engine's destructor selects its own first (SetsCore::~SetsCore, sets_core.h).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -29,7 +29,7 @@ template <int NW> static void print(const uint32_t* w) {
   for (int i = NW - 1; i >= 0; i--) printf("%08x", w[i]);
 }
 
-// The table of one (curve, base, c): the bases 2^(ck) B as ResidentSets::fixed_table computes them on the host, and the
+// The table of one (curve, base, c): the bases 2^(ck) B as PointOps::window_bases (point_ops.h) computes them on the host, and the
 // entries as k_fixed_table computes and stores them -- built when first read, since a test reads a few hundred of the
 // up to 2^19.
 template <class G> struct Table {

@@ -1,6 +1,6 @@
 // Host-side driver for the number-theoretic transform: the planner (msm_zprize_amd/csrc/ntt_plan.h), the roots of unity
 // and the per-thread bodies of ntt_kernels.h (load, radix-4 / radix-2 steps, store, the two-level powers), compiled for
-// the CPU from the same templates and chained exactly as k_ntt_pass and ResidentSets::scalars_ntt chain them: one tile
+// the CPU from the same templates and chained exactly as k_ntt_pass and NttOps::scalars_ntt (ntt_ops.h) chain them: one tile
 // memory of NTT_LDS_WORDS words per plane, NTT_THREADS virtual threads per phase, one pass after the other through
 // scratch.  Driven by tests/test_ntt_cpu.py through stdin/stdout, one request per line, values as hex:
 //   geometry                      ->  NTT_PASS_LOG NTT_RUN_LOG NTT_THREADS NTT_LDS_WORDS NTT_MAX_PASSES   (decimal)

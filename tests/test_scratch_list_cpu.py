@@ -1,5 +1,6 @@
 """msmz_test_poison (include/msmz_test.h) fills every device scratch buffer of a context.  Which buffers those are is said
-once, by the each_scratch visitors of the classes that own them (csrc/resident.h, sort.h, reduce.h, engine.h).  This test
+once, by the each_scratch visitors of the classes that own them (csrc/sets_core.h, the five family stages that
+resident.h holds, sort.h, reduce.h, engine.h).  This test
 keeps that enumeration complete: every DevBuf member declared in csrc/*.h is either named in a visitor of its own file or
 listed below as kept on purpose, so a scratch buffer added without the hook fails here, without a GPU."""
 import os
@@ -11,7 +12,8 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 KEPT = {
     ("store.h", "mem"),        # Handle::mem: the records of a resident set
     ("store.h", "form"),       # Handle::form[2]: the two sorted forms of a sparse matrix
-    ("resident.h", "mem"),     # NttTwiddles::mem and FixedTable::mem: the twiddle cache and the fixed-base table cache
+    ("ntt_ops.h", "mem"),      # NttTwiddles::mem: the twiddle cache
+    ("point_ops.h", "mem"),    # FixedTable::mem: the fixed-base table cache
     ("resident.h", "gen_table_"),   # the generator's window table, built once by the first random_points
     # function-local buffers of the stage hooks, freed on every return
     ("test_hooks.h", "d_pts"), ("test_hooks.h", "d_off"), ("test_hooks.h", "d_refs"),
@@ -48,8 +50,9 @@ def test_the_scan_sees_the_declarations():
     """the patterns find what the code is known to declare: arrays, lists on one line, members of nested structs"""
     found = {(f, n) for f in _headers() for n in _declared(open(os.path.join(CSRC, f)).read())}
     for want in (("reduce.h", "red_"), ("reduce.h", "f2desc_"), ("sort.h", "partials_"), ("sort.h", "packed_"),
-                 ("engine.h", "slots_"), ("engine.h", "segs_"), ("resident.h", "ntt_coset_"), ("resident.h", "meta_"),
-                 ("store.h", "form"), ("resident.h", "mem"), ("test_hooks.h", "d_refs")):
+                 ("engine.h", "slots_"), ("engine.h", "segs_"), ("ntt_ops.h", "ntt_coset_"), ("sets_core.h", "meta_"),
+                 ("store.h", "form"), ("ntt_ops.h", "mem"), ("point_ops.h", "mem"), ("resident.h", "gen_table_"),
+                 ("test_hooks.h", "d_refs")):
         assert want in found, want
     assert _declared("  DevBuf a_, b_[4], c_;   // x\n  DevBuf& r;\n  DevBuf f();\n") == ["a_", "b_", "c_"]
     assert _visited("  void each_scratch(Fn f) {\n    for (DevBuf& b : red_) f(b);\n    f(x_), f(y_);\n  }\n") == {"red_", "x_", "y_"}
@@ -72,16 +75,26 @@ def test_every_device_buffer_is_poisoned_or_kept():
     declared_all = {(f, n) for f in _headers() for n in _declared(open(os.path.join(CSRC, f)).read())}
     assert not (KEPT & visited_all)
     assert KEPT <= declared_all, KEPT - declared_all
-    assert len(visited_all) >= 28   # 8 (resident.h) + 10 (sort.h) + 4 names (reduce.h: red_[4] is one) + 6 (engine.h)
+    # 2 (sets_core.h) + 1 (point_ops.h) + 2 (scalar_ops.h) + 2 (ntt_ops.h) + 1 (matrix_ops.h) + 3 (lookup_ops.h)
+    # + 10 (sort.h) + 4 names (reduce.h: red_[4] is one) + 6 (engine.h)
+    assert len(visited_all) >= 31
+    # every buffer of the resident sets is visited in the file that owns it, and resident.h itself has none to visit
+    for want in (("sets_core.h", "stage_"), ("sets_core.h", "meta_"), ("point_ops.h", "check_"), ("scalar_ops.h", "sdot_"),
+                 ("scalar_ops.h", "sscan_"), ("ntt_ops.h", "ntt_scratch_"), ("ntt_ops.h", "ntt_coset_"),
+                 ("matrix_ops.h", "mat_carry_"), ("lookup_ops.h", "lookup_slots_"), ("lookup_ops.h", "lookup_count_"),
+                 ("lookup_ops.h", "lookup_res_")):
+        assert want in visited_all, want
+    assert not {n for f, n in visited_all if f == "resident.h"}
 
 
 def test_the_kept_names_are_the_members_they_are_meant_to_be():
     """the kept list goes by file and name, and `mem` is a name that a new scratch buffer could take: the file of the
-    caches declares it exactly twice, inside the two cache entries, and the handle's file declares mem and form once"""
-    text = open(os.path.join(CSRC, "resident.h")).read()
-    assert _declared(text).count("mem") == 2
-    for struct in ("NttTwiddles", "FixedTable"):
+    file of each cache declares it exactly once, inside the cache entry, and the handle's file declares mem and form once"""
+    for f, struct in (("ntt_ops.h", "NttTwiddles"), ("point_ops.h", "FixedTable")):
+        text = open(os.path.join(CSRC, f)).read()
+        assert _declared(text).count("mem") == 1, f
         assert re.search(r"struct\s+%s\s*\{[^{}]*?^\s*DevBuf\s+mem;" % struct, text, re.M), struct
+    assert _declared(open(os.path.join(CSRC, "resident.h")).read()) == ["gen_table_"]
     text = open(os.path.join(CSRC, "store.h")).read()
     assert sorted(_declared(text)) == ["form", "mem"]
     assert re.search(r"struct\s+Handle\s*\{[^{}]*?^\s*DevBuf\s+mem;[^{}]*?^\s*DevBuf\s+form\[2\];", text, re.M)
@@ -97,3 +110,14 @@ def test_the_engine_visits_its_stages():
     body = VISITOR.search(text).group(1)
     for call in ("Base::each_scratch(f)", "sort_.each_scratch(f)", "reduce_.each_scratch(f)"):
         assert call in body, call
+
+
+def test_the_resident_sets_visit_their_stages():
+    """ResidentSets::each_scratch reaches the core's list and that of each of its five stages"""
+    text = open(os.path.join(CSRC, "resident.h")).read()
+    body = VISITOR.search(text).group(1)
+    for call in ("Core::each_scratch(f)", "point_ops_.each_scratch(f)", "scalar_ops_.each_scratch(f)",
+                 "ntt_ops_.each_scratch(f)", "matrix_ops_.each_scratch(f)", "lookup_ops_.each_scratch(f)"):
+        assert call in body, call
+    for f in ("sets_core.h", "point_ops.h", "scalar_ops.h", "ntt_ops.h", "matrix_ops.h", "lookup_ops.h"):
+        assert len(VISITOR.findall(open(os.path.join(CSRC, f)).read())) == 1, f

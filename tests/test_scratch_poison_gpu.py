@@ -1067,7 +1067,8 @@ def _family_counts(mod, label, workload):
 def test_fill_reaches_the_buffers_of_every_family(mod):
     """*buffers is at least the number of scratch buffers the family's code path ensures, *bytes at least the sum of
     their ensure arguments for the shape: the fill is not a no-op.  Counted from the code (csrc/engine.h, sort.h,
-    reduce.h, resident.h); the byte sums use only the terms that the shape fixes without the planner."""
+    reduce.h, sets_core.h and the family stages that resident.h holds); the byte sums use only the terms that the shape
+    fixes without the planner."""
     label = "bls12-377"
     fe = 48
     n = N_SET
