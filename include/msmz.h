@@ -784,6 +784,60 @@ typedef struct msmz_lookup_result {
 int msmz_scalars_lookup(msmz_ctx* ctx, const msmz_lookup* l, uint64_t first_out, uint64_t* out_handle,
                         msmz_lookup_result* res /* nullable */);
 
+/* Gate expressions: a sum of products of rotated columns, entry by entry.  The constraint
+ * expression of a PLONK-ish prover -- q_L a + q_R b + q_M a b + q_O c + q_C, a permutation step Z(wX) prod(..) - Z(X)
+ * prod(..), an S-box gate a^5 -- evaluated over columns that are ranges of resident scalar sets, in one launch, between
+ * the coset NTT of the columns and the inverse NTT of the quotient.  The reference has no analogue.
+ *
+ *     out_i = sum over terms T of  c_T * prod over factors f of T of  col_(f.column)[(i + f.rot) mod n]   mod q,   i < n.
+ *
+ * Every column is a range of n entries, [first, first + n) of its handle, and a rotation is cyclic inside that range;
+ * rot is any int32 and is reduced to [0, n) on the host; n need not be a power of two.  On an extended coset of size
+ * 4 n' the rows of the original domain lie 4 apart: the caller passes 4 * rot.  A factor may repeat within a term
+ * (a a a a a), the same column may appear at several rotations, columns may share a handle and may overlap each other.
+ * A column that no factor names is not read and need not be below q.  A term without factors is the constant c_T.  The
+ * operands of an expression are the distinct pairs (column, rot mod n) over all its terms; there may be at most
+ * MSMZ_EXPR_MAX_OPERANDS of them.  Every value written is canonical, below q, and the sums are exact, so two calls
+ * return the same bytes.
+ *
+ * The output rules are those of msmz_scalars_combine: *out_handle == 0 makes a new set of n entries and first_out must
+ * be 0; otherwise only [first_out, first_out + n) of that handle is written.  A destination on the handle of a column
+ * that some factor names: if every factor of that column has rot = 0 (mod n), the destination may be exactly the
+ * column's range or lie apart from it, and a partial overlap is MSMZ_ERR_ARG; if any factor of the column is rotated,
+ * the destination must not meet the column's range at all (as for the gathers of msmz_matrix_mul and
+ * msmz_scalars_lookup).  A column that no factor names may overlap anything.  So accumulation needs no flag:
+ * out = y * out + gate is the term (y, [out at rotation 0]) next to the gate's terms, evaluated in place.
+ *
+ * MSMZ_ERR_ARG, before any launch: a null ctx, descriptor, columns, terms or out_handle, or null factors with n_factors
+ * != 0; n_columns, n_terms, n_factors or n outside the bounds below; a column index >= n_columns; non-zero flags or
+ * reserved; more than MSMZ_EXPR_MAX_OPERANDS operands; an unknown handle or one that is not a scalar set; a range
+ * beyond its set (every column's, named or not); first_out != 0 with a new handle; the overlaps above.  MSMZ_ERR_RANGE:
+ * a coefficient >= q (checked on the host after all of the former; nothing is launched), or a resident entry >= q
+ * inside the range of a column that some factor names, found by the kernel (entries outside are not read).  After
+ * MSMZ_ERR_RANGE no handle is created, *out_handle is as it was, an in-place destination is unspecified and the context
+ * stays usable.  MSMZ_ERR_UNSUPPORTED: a multi-device context when any operand is rotated -- a rotation reads across
+ * the blocks of 2^16 entries; with every rotation = 0 (mod n) the call takes the element-wise route of
+ * msmz_scalars_combine there: every first must be 0 and the output a new handle or a whole existing one.  One host wait
+ * per call. */
+enum { MSMZ_EXPR_MAX_COLUMNS = 16, MSMZ_EXPR_MAX_TERMS = 32, MSMZ_EXPR_MAX_DEGREE = 8, MSMZ_EXPR_MAX_OPERANDS = 32 };
+typedef struct msmz_expr_column { uint64_t handle, first; } msmz_expr_column;          /* 16 bytes */
+typedef struct msmz_expr_factor { uint32_t column; int32_t rot; } msmz_expr_factor;    /*  8 bytes */
+typedef struct msmz_expr_term {
+  const uint8_t* coeff;             /* 32 bytes LE, < q; NULL = 1 */
+  const msmz_expr_factor* factors;  /* n_factors of them; may be NULL when n_factors == 0 */
+  uint32_t n_factors;               /* 0 .. MSMZ_EXPR_MAX_DEGREE; 0 = the constant coeff */
+  uint32_t reserved;                /* must be 0 */
+} msmz_expr_term;                   /* 24 bytes */
+typedef struct msmz_expr {
+  const msmz_expr_column* columns;  /* n_columns of them, each a range of n entries */
+  uint32_t n_columns;               /* 1 .. MSMZ_EXPR_MAX_COLUMNS */
+  uint32_t n_terms;                 /* 1 .. MSMZ_EXPR_MAX_TERMS */
+  const msmz_expr_term* terms;
+  uint64_t n;                       /* 1 .. 2^32 - 1 */
+  uint32_t flags;                   /* must be 0 */
+} msmz_expr;                        /* 40 bytes */
+int msmz_scalars_expr(msmz_ctx* ctx, const msmz_expr* e, uint64_t first_out, uint64_t* out_handle);
+
 /* Host-side group addition of two canonical affine results: combines per-GPU partial sums
  * (the reference's "partition sum" step, msm-batched-affine.ts:300-307). */
 int msmz_point_add(int curve_id, const uint8_t* a_xy_le, int a_is_inf, const uint8_t* b_xy_le, int b_is_inf,

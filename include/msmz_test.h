@@ -153,6 +153,10 @@ void msmz_test_matrix_geometry(uint32_t* tile, uint32_t* run, uint32_t* carries_
 void msmz_test_lookup_geometry(uint32_t* min_slots, uint32_t* threads_per_workgroup);
 uint32_t msmz_test_lookup_small_table(uint32_t* passes, uint32_t* max_groups);
 uint32_t msmz_test_lookup_slot(int curve_id, const uint8_t* le32, uint64_t table_n);
+/* msmz_scalars_expr (csrc/expr_kernels.h); needs no context.  threads_per_workgroup = the output entries of one workgroup
+ * of k_scalars_expr; register_slots = the largest operand count that takes the register-resident kernel
+ * (k_scalars_expr_slots; 0 would mean there is none and every expression takes k_scalars_expr). */
+void msmz_test_expr_geometry(uint32_t* threads_per_workgroup, uint32_t* register_slots);
 /* msmz_points_fixed_base (msm_zprize_amd/csrc/fixed_base.h).
  *   msmz_test_fixed_base_plan: what the planner picks for n points of a curve and a bound of `bits` (0 or >= the bit
  *     length of q: none) -- the window width, the windows K = ceil((bound + 1) / c) and the table's entries

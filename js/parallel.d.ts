@@ -35,6 +35,15 @@ export function sparseMatrixArgs(rows: number[] | Uint32Array, cols: number[] | 
   { rows: Uint8Array; cols: Uint8Array; nnz: number; shape: [number, number]; flags: number; firstValue: number };
 export function matVecArgs(matrix: { handle: unknown; shape: number[]; orientations: string; kind: string }, x: ScalarsLike, options?: MatVecOptions): { n: number; flags: number };
 export interface LookupOptions { firstColumn?: number; n?: number | null; firstTable?: number; tableN?: number | null; out?: DeviceArray | null; firstOut?: number; positions?: boolean }
+export interface ExprOptions { n?: number | null; out?: DeviceArray | null; firstOut?: number }
+export type ExprColumn = ScalarsLike | [ScalarsLike, number];
+export type ExprFactor = number | [number, number];
+export type ExprTerm = [bigint | null, ExprFactor[]];
+/** the limits of Parallel.evaluateExpression (include/msmz.h MSMZ_EXPR_MAX_*) */
+export const EXPR_MAX_COLUMNS: number, EXPR_MAX_TERMS: number, EXPR_MAX_DEGREE: number, EXPR_MAX_OPERANDS: number;
+/** the checked arguments of Parallel.evaluateExpression (host only) */
+export function exprArgs(columns: ExprColumn[], terms: ExprTerm[], options: ExprOptions | undefined, order: bigint):
+  { columns: [ScalarsLike, number][]; terms: [bigint | null, [number, number][]][]; n: number };
 export interface LookupInfo { missing: number; firstMissing: number | null; distinct: number; positions?: Uint32Array }
 /** the checked arguments of Parallel.lookupMultiplicities (host only) */
 export function lookupArgs(column: ScalarsLike, table: ScalarsLike, options?: LookupOptions): { n: number; tableN: number };
@@ -145,6 +154,9 @@ export interface ParallelApi {
    * index of each table value, 0 at later duplicates; a column entry in no table is counted in info.missing, not refused.
    * The destination may meet neither input range. */
   lookupMultiplicities(column: DeviceArray, table: DeviceArray, options?: LookupOptions): Promise<[DeviceArray, LookupInfo]>;
+  /** a sum of products of rotated columns, entry by entry (msmz_scalars_expr): out[i] = sum_T c_T prod_f
+   * column_f[(i + rot_f) mod n]; `out` may be a column read at rotation 0 only (in place) or apart from every column read */
+  evaluateExpression(columns: (DeviceArray | [DeviceArray, number])[], terms: ExprTerm[], options?: ExprOptions): Promise<DeviceArray>;
   /** the default primitive 2^logN-th root of unity of the scalar field (msmz_scalars_root_of_unity) */
   rootOfUnity(logN: number): bigint;
   msmBatch(scalarsList: DeviceArray | Uint8Array[], points: DeviceArray, n: number, options?: MsmOptions & { batch?: number }): Promise<BigintPoint[]>;

@@ -317,6 +317,71 @@ export function lookupArgs(column, table, { firstColumn = 0, n = null, firstTabl
   return { n: N, tableN: T };
 }
 
+/** The arguments of Parallel.evaluateExpression -> {columns: [[array, first]], terms: [[bigint | null, [[column, rot]]]], n},
+ * checked before anything reaches the device (msm_zprize_amd/parallel.py expr_args is the same function). */
+export const EXPR_MAX_COLUMNS = 16, EXPR_MAX_TERMS = 32, EXPR_MAX_DEGREE = 8, EXPR_MAX_OPERANDS = 32;
+export function exprArgs(columns, terms, { n = null, out = null, firstOut = 0 } = {}, order) {
+  const who = "evaluateExpression";
+  if (!Array.isArray(columns) || looksLikeScalars(columns) || !Array.isArray(terms)) throw TypeError(`${who}: \`columns\` and \`terms\` are arrays`);
+  if (out !== null && !looksLikeScalars(out)) throw TypeError(`${who}: \`out\` is a resident scalar array or null`);
+  const cols = columns.map((c) => {
+    // (a resident array IS an Array of one element, itself: a pair is a plain array of two)
+    const [arr, first] = Array.isArray(c) && !looksLikeScalars(c) && c.length === 2 ? c : [c, 0];
+    if (!looksLikeScalars(arr)) throw TypeError(`${who}: a column is a resident scalar array or an [array, first] pair`);
+    return [arr, first];
+  });
+  if (cols.length < 1 || cols.length > EXPR_MAX_COLUMNS) throw Error(`${who}: ${cols.length} columns (1..${EXPR_MAX_COLUMNS})`);
+  if (terms.length < 1 || terms.length > EXPR_MAX_TERMS) throw Error(`${who}: ${terms.length} terms (1..${EXPR_MAX_TERMS})`);
+  const parsed = terms.map((t) => {
+    if (!Array.isArray(t) || t.length !== 2 || !Array.isArray(t[1])) throw TypeError(`${who}: a term is a pair [coefficient, [factors]]`);
+    const [c, factors] = t;
+    if (c !== null && typeof c !== "bigint") throw TypeError(`${who}: a coefficient is a bigint or null (1)`);
+    if (c !== null && (c < 0n || c >= order)) throw Error(`${who}: the coefficient ${c} is not in [0, group order)`);
+    const fs = factors.map((f) => {
+      const [col, rot] = Array.isArray(f) && f.length === 2 ? f : [f, 0];
+      if (!Number.isInteger(col) || !Number.isInteger(rot)) throw TypeError(`${who}: a factor is a column index or a pair [column, rot] of integers`);
+      if (col < 0 || col >= cols.length) throw Error(`${who}: a factor names column ${col} of ${cols.length}`);
+      if (rot < -(2 ** 31) || rot >= 2 ** 31) throw Error(`${who}: rot = ${rot} is no int32`);
+      return [col, rot];
+    });
+    if (fs.length > EXPR_MAX_DEGREE) throw Error(`${who}: a term of ${fs.length} factors (0..${EXPR_MAX_DEGREE})`);
+    return [c, fs];
+  });
+  cols.forEach(([arr, first], k) => {
+    mleFirst(who, `the first of column ${k}`, first, arr);
+    if (first >= arr.n) throw Error(`${who}: the first of column ${k} = ${first} but the array holds ${arr.n}`);
+  });
+  mleFirst(who, "firstOut", firstOut, out);
+  if (out !== null && firstOut >= out.n) throw Error(`${who}: firstOut = ${firstOut} but the array holds ${out.n}`);
+  if (n === null) {
+    const lengths = [...new Set(cols.map(([arr, first]) => arr.n - first))].sort((a, b) => a - b);
+    if (lengths.length !== 1) throw Error(`${who}: N is needed when the columns hold different numbers of entries: ${lengths}`);
+    n = lengths[0];
+  }
+  if (!Number.isInteger(n) || n < 1 || n >= 2 ** 32) throw Error(`${who}: N = ${n}`);
+  cols.forEach(([arr, first], k) => {
+    if (n > arr.n - first) throw Error(`${who}: entries [${first}, +${n}) from the first of column ${k} of an array of ${arr.n}`);
+  });
+  if (out !== null && n > out.n - firstOut) throw Error(`${who}: entries [${firstOut}, +${n}) from firstOut of an array of ${out.n}`);
+  const mod = (rot) => ((rot % n) + n) % n;
+  const operands = new Set();
+  for (const [, fs] of parsed) for (const [col, rot] of fs) operands.add(`${col}:${mod(rot)}`);
+  if (operands.size > EXPR_MAX_OPERANDS)
+    throw Error(`${who}: the terms read ${operands.size} distinct (column, rot mod N) pairs (at most ${EXPR_MAX_OPERANDS})`);
+  if (out !== null)
+    cols.forEach(([arr, first], k) => {
+      const rots = [...operands].filter((o) => o.startsWith(`${k}:`)).map((o) => Number(o.split(":")[1]));
+      if (arr.handle !== out.handle || rots.length === 0) return;
+      if (rots.every((r) => r === 0)) {
+        if (first !== firstOut && Math.abs(first - firstOut) < n)
+          throw Error(`${who}: the destination [${firstOut}, +${n}) overlaps the input range [${first}, +${n}) (column ${k}) in part; it may be that range exactly or apart from it`);
+      } else if (Math.abs(first - firstOut) < n) {
+        throw Error(`${who}: the destination [${firstOut}, +${n}) overlaps the input range [${first}, +${n}) (column ${k}); the column is read rotated, so the two may not meet at all`);
+      }
+    });
+  return { columns: cols, terms: parsed, n };
+}
+
 /** A GPU-resident sparse matrix (msmz_matrix_create): shape = [rows, columns], nnz, the orientations it was built for */
 class SparseMatrix {
   constructor(curve, handle, shape, nnz, orientations) {
@@ -839,6 +904,40 @@ function createCurve(params, kind) {
         for (let i = 0; i < t.n; i++) info.positions[i] = r.positions.readUInt32LE(4 * i);
       }
       return [out === null ? DeviceArray.make(curve, r.handle, t.tableN, "scalars") : out, info];
+    },
+    /** out[firstOut + i] = sum_T c_T prod_(f in T) column_f[(i + rot_f) mod n] mod the group order, i < n: the constraint
+     * expression of a PLONK-ish prover entry by entry, in one launch (msmz_scalars_expr).  columns: 1 to 16 resident
+     * scalar arrays or [array, first] pairs; terms: 1 to 32 pairs [c, factors], c a bigint below the group order or null
+     * (1), factors an array of at most 8 column indices or [column, rot] pairs ([] makes the term the constant c; a
+     * factor may repeat).  A rotation is cyclic inside the column's n entries and any int32; over an extended coset of
+     * size 4 n pass 4 rot.  At most 32 distinct (column, rot mod n) pairs in all.  Without `out` a new array; `out` may
+     * be a column read at rotation 0 only, over exactly its range (out = y out + gate is the term [y, [out]] next to the
+     * gate's, in place), or apart from every column the terms read.  options: {n, out, firstOut}.  Returns the array written. */
+    async evaluateExpression(columns, terms, options = {}) {
+      const t = exprArgs(columns, terms, options, params.order);
+      for (const [arr] of t.columns) if (!isScalars(arr)) throw TypeError("evaluateExpression: a column is a resident scalar array");
+      const out = options.out === undefined ? null : options.out;
+      if (out !== null && !isScalars(out)) throw TypeError("evaluateExpression: `out` is a resident scalar array or null");
+      const cb = Buffer.alloc(16 * t.columns.length), counts = Buffer.alloc(t.terms.length), unit = Buffer.alloc(t.terms.length);
+      t.columns.forEach(([arr, first], j) => {
+        cb.writeBigUInt64LE(BigInt(arr.handle), 16 * j);
+        cb.writeBigUInt64LE(BigInt(first), 16 * j + 8);
+      });
+      const fb = Buffer.alloc(8 * Math.max(1, t.terms.reduce((s, [, fs]) => s + fs.length, 0)));
+      let at = 0;
+      const coeffs = Buffer.concat(t.terms.map(([c, fs], k) => {
+        counts[k] = fs.length;
+        unit[k] = c === null ? 1 : 0;
+        for (const [col, rot] of fs) {
+          fb.writeUInt32LE(col, 8 * at);
+          fb.writeInt32LE(rot, 8 * at + 4);
+          at++;
+        }
+        return scalarBuf(c === null ? 1n : c);
+      }));
+      const h = N.scalarsExpr(ctx, cb, t.columns.length, fb, counts, coeffs, unit, t.terms.length, t.n, options.firstOut || 0,
+                              out === null ? 0 : out.handle);
+      return out === null ? DeviceArray.make(curve, h, t.n, "scalars") : out;
     },
     /** batched MSM: B scalar vectors against one point set (include/msmz.h msmz_msm_batch); safe additions */
     msmBatch: (scalarsList, points, n, options) => msmBatchCommon(scalarsList, points, n, options, 1),

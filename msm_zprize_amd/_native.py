@@ -134,6 +134,30 @@ class MsmzLookupResult(C.Structure):   # msmz_lookup_result (include/msmz.h)
     _fields_ = [("n_missing", C.c_uint64), ("first_missing", C.c_uint64), ("n_distinct", C.c_uint64)]
 
 
+MSMZ_EXPR_MAX_COLUMNS, MSMZ_EXPR_MAX_TERMS, MSMZ_EXPR_MAX_DEGREE, MSMZ_EXPR_MAX_OPERANDS = 16, 32, 8, 32
+
+
+class MsmzExprColumn(C.Structure):   # msmz_expr_column: one column of an expression, n entries from `first`
+    _fields_ = [("handle", C.c_uint64), ("first", C.c_uint64)]
+
+
+class MsmzExprFactor(C.Structure):   # msmz_expr_factor: a column read `rot` rows ahead (cyclically)
+    _fields_ = [("column", C.c_uint32), ("rot", C.c_int32)]
+
+
+class MsmzExprTerm(C.Structure):   # msmz_expr_term: coeff * the product of its factors
+    _fields_ = [("coeff", C.c_char_p), ("factors", C.POINTER(MsmzExprFactor)), ("n_factors", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class MsmzExpr(C.Structure):   # msmz_expr (include/msmz.h): a sum of products of rotated columns
+    _fields_ = [("columns", C.POINTER(MsmzExprColumn)), ("n_columns", C.c_uint32), ("n_terms", C.c_uint32),
+                ("terms", C.POINTER(MsmzExprTerm)), ("n", C.c_uint64), ("flags", C.c_uint32)]
+
+
+assert (C.sizeof(MsmzExprColumn), C.sizeof(MsmzExprFactor), C.sizeof(MsmzExprTerm), C.sizeof(MsmzExpr)) == (16, 8, 24, 40)
+
+
 class MsmzSegment(C.Structure):   # msmz_segment (include/msmz.h): one problem of msmz_msm_segments
     _fields_ = [("first_p", C.c_uint64), ("first_s", C.c_uint64), ("n", C.c_uint64)]
 
@@ -235,6 +259,7 @@ EXPORTS = {
     "msmz_matrix_mul": (C.c_int, [C.c_void_p, C.POINTER(MsmzMatvec), C.c_uint64, C.POINTER(C.c_uint64)]),
     "msmz_scalars_lookup": (C.c_int, [C.c_void_p, C.POINTER(MsmzLookup), C.c_uint64, C.POINTER(C.c_uint64),
                                       C.POINTER(MsmzLookupResult)]),
+    "msmz_scalars_expr": (C.c_int, [C.c_void_p, C.POINTER(MsmzExpr), C.c_uint64, C.POINTER(C.c_uint64)]),
     "msmz_point_add": (C.c_int, [C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.POINTER(C.c_int)]),
     # stage-level test hooks (include/msmz_test.h)
     "msmz_test_set_glv_bits": (C.c_int, [C.c_void_p, C.c_int]),
@@ -248,6 +273,7 @@ EXPORTS = {
     "msmz_test_ntt_plan": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "msmz_test_ntt_geometry": (None, [C.POINTER(C.c_uint32)]),
     "msmz_test_matrix_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "msmz_test_expr_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "msmz_test_lookup_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "msmz_test_lookup_slot": (C.c_uint32, [C.c_int, C.c_char_p, C.c_uint64]),
     "msmz_test_lookup_small_table": (C.c_uint32, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

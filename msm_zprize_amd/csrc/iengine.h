@@ -140,6 +140,9 @@ class IEngine {
   // msmz_scalars_lookup: the multiplicities of a column in a table (lookup_kernels.h).  The default: a multi-device
   // context has none -- a probe reads across every block of 2^16 entries.
   virtual int scalars_lookup(const msmz_lookup&, uint64_t, uint64_t*, msmz_lookup_result*) { return MSMZ_ERR_UNSUPPORTED; }
+  // msmz_scalars_expr: a sum of products of rotated columns, entry by entry (expr_kernels.h).  The default: a context
+  // that has none.
+  virtual int scalars_expr(const msmz_expr&, uint64_t, uint64_t*) { return MSMZ_ERR_UNSUPPORTED; }
   // tests (include/msmz_test.h); the stage-level hooks are one engine's (a multi-device context: its first engine's)
   virtual int test_set_glv_bits(int) { return MSMZ_ERR_UNSUPPORTED; }
   virtual int test_retries() { return 0; }

@@ -4,6 +4,7 @@
 #pragma once
 #include "check_kernels.h"
 #include "export_kernels.h"
+#include "expr_kernels.h"
 #include "fixed_kernels.h"
 #include "gen_kernels.h"
 #include "import_kernels.h"
@@ -153,6 +154,11 @@
   PFX template __global__ void k_lookup_count<Fr>(uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t, const uint32_t*, const uint32_t*, uint32_t); \
   PFX template __global__ void k_lookup_count_small<Fr>(uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t, const uint32_t*, uint32_t, const uint32_t*, uint32_t); \
   PFX template __global__ void k_lookup_emit<Fr>(uint32_t*, const uint32_t*, uint32_t);
+
+// the gate-expression kernels (expr_kernels.h), a translation unit of their own (kern_expr.hip)
+#define MSMZ_INST_EXPR(F, Fr, PFX)                                                                                \
+  PFX template __global__ void k_scalars_expr<Fr>(uint32_t*, ExprProgram, uint32_t*);                             \
+  PFX template __global__ void k_scalars_expr_slots<Fr, EXPR_REGISTER_SLOTS>(uint32_t*, ExprProgram, uint32_t*);
 
 // every curve, by policy P = WeierPolicy<F> / TePolicy<F>
 #define MSMZ_INST_MISC_P(F, Fr, P, PFX)                                                                           \

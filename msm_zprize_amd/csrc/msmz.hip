@@ -1,10 +1,10 @@
 // C ABI of the MSM engine (include/msmz.h): curve dispatch + argument checking.
 #include "instantiate.h"
 namespace msmz {
-#define X(F, Fr) MSMZ_INST_BATCH(F, Fr, MSMZ_EXTERN) MSMZ_INST_REDUCE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MISC(F, Fr, MSMZ_EXTERN) MSMZ_INST_GEN(F, Fr, MSMZ_EXTERN) MSMZ_INST_MLE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MATRIX(F, Fr, MSMZ_EXTERN) MSMZ_INST_LOOKUP(F, Fr, MSMZ_EXTERN)
+#define X(F, Fr) MSMZ_INST_BATCH(F, Fr, MSMZ_EXTERN) MSMZ_INST_REDUCE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MISC(F, Fr, MSMZ_EXTERN) MSMZ_INST_GEN(F, Fr, MSMZ_EXTERN) MSMZ_INST_MLE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MATRIX(F, Fr, MSMZ_EXTERN) MSMZ_INST_LOOKUP(F, Fr, MSMZ_EXTERN) MSMZ_INST_EXPR(F, Fr, MSMZ_EXTERN)
 MSMZ_WEIERSTRASS_FIELDS(X)
 #undef X
-#define X(F, Fr) MSMZ_INST_REDUCE_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MISC_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_GEN_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MLE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MATRIX(F, Fr, MSMZ_EXTERN) MSMZ_INST_LOOKUP(F, Fr, MSMZ_EXTERN)
+#define X(F, Fr) MSMZ_INST_REDUCE_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MISC_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_GEN_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MLE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MATRIX(F, Fr, MSMZ_EXTERN) MSMZ_INST_LOOKUP(F, Fr, MSMZ_EXTERN) MSMZ_INST_EXPR(F, Fr, MSMZ_EXTERN)
 MSMZ_TE_FIELDS(X)
 #undef X
 }  // namespace msmz
@@ -284,6 +284,13 @@ int msmz_matrix_mul(msmz_ctx* c, const msmz_matvec* v, uint64_t first_out, uint6
 }
 int msmz_scalars_lookup(msmz_ctx* c, const msmz_lookup* l, uint64_t first_out, uint64_t* out_handle, msmz_lookup_result* res) {
   return c && l && out_handle ? c->engine->scalars_lookup(*l, first_out, out_handle, res) : MSMZ_ERR_ARG;
+}
+int msmz_scalars_expr(msmz_ctx* c, const msmz_expr* e, uint64_t first_out, uint64_t* out_handle) {
+  return c && e && out_handle ? c->engine->scalars_expr(*e, first_out, out_handle) : MSMZ_ERR_ARG;
+}
+void msmz_test_expr_geometry(uint32_t* threads_per_workgroup, uint32_t* register_slots) {
+  if (threads_per_workgroup) *threads_per_workgroup = EXPR_THREADS;
+  if (register_slots) *register_slots = EXPR_REGISTER_SLOTS;
 }
 void msmz_test_lookup_geometry(uint32_t* min_slots, uint32_t* threads_per_workgroup) {
   if (min_slots) *min_slots = lk_slots(1);

@@ -27,6 +27,35 @@
 
 namespace msmz {
 
+// The checks of msmz_scalars_expr that need no handle, for the multi-device context: what expr_compile (expr_kernels.h)
+// refuses, in its order -- that header is device code and cannot be included here, half way through kernels.h.
+// named[c] = 0: no factor reads column c, 1: at rotation 0 only, 3: rotated; *rotated: some factor is.
+static inline int expr_precheck(const msmz_expr& e, uint8_t named[MSMZ_EXPR_MAX_COLUMNS], bool* rotated) {
+  if (!e.columns || !e.terms || e.n_columns < 1 || e.n_columns > (uint32_t)MSMZ_EXPR_MAX_COLUMNS || e.n_terms < 1 ||
+      e.n_terms > (uint32_t)MSMZ_EXPR_MAX_TERMS || e.n == 0 || e.n >> 32 || e.flags)
+    return MSMZ_ERR_ARG;
+  memset(named, 0, MSMZ_EXPR_MAX_COLUMNS);
+  std::vector<uint64_t> operands;   // (column << 32 | rot mod n), distinct
+  for (uint32_t k = 0; k < e.n_terms; k++) {
+    const msmz_expr_term& t = e.terms[k];
+    if (t.reserved || t.n_factors > (uint32_t)MSMZ_EXPR_MAX_DEGREE || (t.n_factors && !t.factors)) return MSMZ_ERR_ARG;
+    for (uint32_t f = 0; f < t.n_factors; f++) {
+      const uint32_t col = t.factors[f].column;
+      if (col >= e.n_columns) return MSMZ_ERR_ARG;
+      int64_t r = (int64_t)t.factors[f].rot % (int64_t)e.n;
+      if (r < 0) r += (int64_t)e.n;
+      named[col] |= r ? 3 : 1;
+      if (r) *rotated = true;
+      const uint64_t key = (uint64_t)col << 32 | (uint64_t)r;
+      bool seen = false;
+      for (uint64_t o : operands) seen = seen || o == key;
+      if (!seen) operands.push_back(key);
+      if (operands.size() > (size_t)MSMZ_EXPR_MAX_OPERANDS) return MSMZ_ERR_ARG;
+    }
+  }
+  return MSMZ_OK;
+}
+
 // Problems per sub-batch of a batched MSM: at most `cap` entries (problems x entries_per_problem) per sub-batch, and the
 // `remaining` problems dealt into equally large sub-batches (64 problems with room for 40 -> 2 x 32, not 40 + 24).
 static inline uint32_t batch_split(uint32_t remaining, uint64_t entries_per_problem, uint64_t cap) {
@@ -490,6 +519,54 @@ class MultiEngine : public IEngine {
       *n_zero = 0;
       for (uint64_t z : zeros) *n_zero += z;
     }
+    if (dst) return st;   // (written in place: the handle stays the caller's)
+    return finish_handle(st, mh, out_handle);
+  }
+
+  // A gate expression without a rotated operand is element-wise: every engine evaluates its own share, as
+  // scalars_combine (every range from 0, an existing destination written whole).  A rotation reads across the
+  // boundaries between blocks of 2^16 entries, which live on different engines: refused, after every check that needs
+  // no engine.  The engines get the factors with rotation 0: a multiple of n is no multiple of a share's length.
+  int scalars_expr(const msmz_expr& e, uint64_t first_out, uint64_t* out_handle) override {
+    if (!out_handle) return MSMZ_ERR_ARG;
+    uint8_t named[MSMZ_EXPR_MAX_COLUMNS];
+    bool rotated = false;
+    if (int st = expr_precheck(e, named, &rotated)) return st;
+    const bool fresh = *out_handle == 0;
+    if (fresh && first_out != 0) return MSMZ_ERR_ARG;
+    const MHandle* col[MSMZ_EXPR_MAX_COLUMNS];
+    bool shifted = first_out != 0;
+    for (uint32_t c = 0; c < e.n_columns; c++) {
+      if (!(col[c] = range(e.columns[c].handle, 1, e.columns[c].first, e.n))) return MSMZ_ERR_ARG;
+      const uint64_t first = e.columns[c].first;   // (named[c] == 1: read at rotation 0 only; 3: read rotated)
+      if (e.columns[c].handle == *out_handle && named[c] &&
+          (named[c] & 2 ? ranges_meet(first, e.n, first_out, e.n) : partial_overlap(first, first_out, e.n)))
+        return MSMZ_ERR_ARG;
+      shifted = shifted || e.columns[c].first;
+    }
+    const MHandle* dst = nullptr;
+    if (!fresh && !(dst = range(*out_handle, 1, first_out, e.n))) return MSMZ_ERR_ARG;
+    if (rotated || shifted || (dst && dst->n != e.n)) return MSMZ_ERR_UNSUPPORTED;
+    std::vector<msmz_expr_factor> factors;
+    std::vector<msmz_expr_term> terms(e.terms, e.terms + e.n_terms);
+    for (const msmz_expr_term& t : terms)
+      for (uint32_t f = 0; f < t.n_factors; f++) factors.push_back({t.factors[f].column, 0});
+    size_t at = 0;
+    for (msmz_expr_term& t : terms) {
+      t.factors = t.n_factors ? factors.data() + at : nullptr;
+      at += t.n_factors;
+    }
+    MHandle mh = new_set(1, e.n);
+    int st = for_shares(e.n, [&](uint32_t g, IEngine* eng, uint64_t cnt) {
+      msmz_expr_column sub[MSMZ_EXPR_MAX_COLUMNS];
+      for (uint32_t c = 0; c < e.n_columns; c++) sub[c] = {col[c]->sub[g], 0};
+      msmz_expr mine = e;
+      mine.columns = sub;
+      mine.terms = terms.data();
+      mine.n = cnt;
+      if (dst) mh.sub[g] = dst->sub[g];
+      return eng->scalars_expr(mine, 0, &mh.sub[g]);
+    });
     if (dst) return st;   // (written in place: the handle stays the caller's)
     return finish_handle(st, mh, out_handle);
   }

@@ -2,7 +2,7 @@
 // uploads, imports from host or device memory, generators, downloads and exports.  What every operation on them shares
 // (the ONE HIP stream, the handle table, the result-record path) is SetsCore (sets_core.h), from which this derives; the
 // operations that are not data movement are family stages it holds and forwards to (point_ops.h, scalar_ops.h, ntt_ops.h,
-// matrix_ops.h, lookup_ops.h).  Every entry point returns with the stream drained.  Engine<Cfg> (engine.h) derives from
+// matrix_ops.h, lookup_ops.h, expr_ops.h).  Every entry point returns with the stream drained.  Engine<Cfg> (engine.h) derives from
 // this and adds the MSM pipeline, which runs on the same stream and reports through the same error word.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -21,6 +21,7 @@
 #include "ntt_ops.h"
 #include "matrix_ops.h"
 #include "lookup_ops.h"
+#include "expr_ops.h"
 
 namespace msmz {
 
@@ -37,7 +38,7 @@ class ResidentSets : public SetsCore<Cfg> {
   using Core::points_fit, Core::new_points, Core::new_scalars, Core::add_handle, Core::wait_after;
 
   explicit ResidentSets(int device) : Core(device), point_ops_(*this), scalar_ops_(*this), ntt_ops_(*this, scalar_ops_),
-                                      matrix_ops_(*this), lookup_ops_(*this) {}
+                                      matrix_ops_(*this), lookup_ops_(*this), expr_ops_(*this) {}
 
   // the core, then the event that orders stream_ behind a caller's (Engine::init goes on from here)
   int init_sets() {
@@ -336,6 +337,9 @@ class ResidentSets : public SetsCore<Cfg> {
   int scalars_lookup(const msmz_lookup& l, uint64_t first_out, uint64_t* out, msmz_lookup_result* res) override {
     return lookup_ops_.scalars_lookup(l, first_out, out, res);
   }
+  int scalars_expr(const msmz_expr& e, uint64_t first_out, uint64_t* out) override {
+    return expr_ops_.scalars_expr(e, first_out, out);
+  }
 
  private:
   // where the import kernel reads: the caller's device memory, or the packed staging copy of a host source
@@ -522,6 +526,7 @@ class ResidentSets : public SetsCore<Cfg> {
   NttOps<Cfg> ntt_ops_;
   MatrixOps<Cfg> matrix_ops_;
   LookupOps<Cfg> lookup_ops_;
+  ExprOps<Cfg> expr_ops_;   // (owns no buffer: nothing for each_scratch)
   hipEvent_t import_ev_ = nullptr;     // orders stream_ behind the stream that produces an imported device source (or last touches an export's destination)
   std::vector<uint8_t> import_pack_;   // host packing of a strided host source; the packed landing of a host export
   DevBuf gen_table_;

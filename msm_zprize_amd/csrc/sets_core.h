@@ -1,7 +1,7 @@
 // What every family of operations on the resident sets of one engine needs, and nothing a single family owns: the device
 // and its ONE HIP stream, the handle table, the staging buffer, the meta block, and the one way a result comes home.
 // ResidentSets<Cfg> (resident.h) derives from this and keeps the sets themselves; the family stages (point_ops.h,
-// scalar_ops.h, ntt_ops.h, matrix_ops.h, lookup_ops.h) are built with a reference to it.
+// scalar_ops.h, ntt_ops.h, matrix_ops.h, lookup_ops.h, expr_ops.h) are built with a reference to it.
 //
 // The result-record contract.  Every entry point returns with the stream drained, and reaches its ONE host wait through
 // one of three helpers: drained() (nothing comes back), checked() (the 4-byte error word of the meta block) or recorded()
@@ -26,6 +26,7 @@ template <class Cfg> class ScalarOps;
 template <class Cfg> class NttOps;
 template <class Cfg> class MatrixOps;
 template <class Cfg> class LookupOps;
+template <class Cfg> class ExprOps;
 
 template <class Cfg>
 class SetsCore : public IEngine {
@@ -34,6 +35,7 @@ class SetsCore : public IEngine {
   friend class NttOps<Cfg>;
   friend class MatrixOps<Cfg>;
   friend class LookupOps<Cfg>;
+  friend class ExprOps<Cfg>;
 
  protected:
   using F = typename Cfg::F;

@@ -586,6 +586,26 @@ class _Parallel:
             info["positions"] = pos
         return m, info
 
+    # -- gate expressions: sums of products of rotated columns (msmz_scalars_expr) ---------------------
+    def evaluateExpression(self, columns, terms, N=None, out=None, firstOut=0):
+        """out[firstOut + i] = sum_T c_T prod_(f in T) column_f[(i + rot_f) mod N] mod the group order, i < N: the
+        constraint expression of a PLONK-ish prover, entry by entry, in one launch.  `columns`: 1 to 16 resident scalar
+        arrays or (array, first) pairs, each read as the N entries from its `first`; `terms`: 1 to 32 pairs (c, factors),
+        c an int below the group order or None (1), factors a list of at most 8 column indices or (column, rot) pairs
+        ([] makes the term the constant c; a factor may repeat: [0] * 5 is a^5).  A rotation is cyclic inside the
+        column's N entries and any int32; over an extended coset of size 4 n pass 4 rot.  All terms together may read at
+        most 32 distinct (column, rot mod N) pairs.  N=None: every column holds the same number of entries from its
+        `first`, and that is N.  out=None: a new array of N entries; otherwise `out` may be a column that is read at
+        rotation 0 only, over exactly its range (out = y out + gate is the term (y, [out]) next to the gate's, in
+        place), or lie apart from every column the terms read.  Returns the array written."""
+        a = expr_args(columns, terms, N, out, firstOut, self._c.params["order"])
+        cols = (_native.MsmzExprColumn * len(a["columns"]))(*[_native.MsmzExprColumn(c.handle, f) for c, f in a["columns"]])
+        facs = [(_native.MsmzExprFactor * max(1, len(fs)))(*[_native.MsmzExprFactor(c, r) for c, r in fs]) for _, fs in a["terms"]]
+        trms = (_native.MsmzExprTerm * len(a["terms"]))(*[_native.MsmzExprTerm(c, fa if fs else None, len(fs), 0)
+                                                          for (c, fs), fa in zip(a["terms"], facs)])
+        e = _native.MsmzExpr(cols, len(a["columns"]), len(a["terms"]), trms, a["N"], 0)
+        return _resident(self._c, "scalars", a["N"], "msmz_scalars_expr", C.byref(e), firstOut, out=out)
+
     def _checked(self, arr, what, who):
         try:
             res = self.checkPoints(arr, subgroup=bool(what & _native.MSMZ_CHECK_SUBGROUP))
@@ -1312,6 +1332,73 @@ def lookup_args(column, table, firstColumn, N, firstTable, tableN, out, firstOut
                 raise ValueError(f"{who}: the destination [{firstOut}, +{n_out}) overlaps the {name} range [{first}, +{n}); "
                                  "both inputs are gathered, so it may meet neither at all")
     return sizes
+
+
+def expr_args(columns, terms, N, out, firstOut, order, who="evaluateExpression"):
+    """Arguments of evaluateExpression -> dict(columns, terms, N), checked before anything reaches the device.  columns:
+    [(array, first)]; terms: [(32 little-endian bytes or None, [(column, rot)])]."""
+    if not isinstance(columns, (list, tuple)) or not isinstance(terms, (list, tuple)):
+        raise TypeError(f"{who}: `columns` and `terms` are lists")
+    if out is not None and not _is_array(out, "scalars"):
+        raise TypeError(f"{who}: `out` is a resident scalar array or None")
+    cols = []
+    for c in columns:
+        arr, first = c if isinstance(c, tuple) and len(c) == 2 else (c, 0)
+        if not _is_array(arr, "scalars"):
+            raise TypeError(f"{who}: a column is a resident scalar array or an (array, first) pair")
+        cols.append((arr, first))
+    if not 1 <= len(cols) <= _native.MSMZ_EXPR_MAX_COLUMNS:
+        raise ValueError(f"{who}: {len(cols)} columns (1..{_native.MSMZ_EXPR_MAX_COLUMNS})")
+    if not 1 <= len(terms) <= _native.MSMZ_EXPR_MAX_TERMS:
+        raise ValueError(f"{who}: {len(terms)} terms (1..{_native.MSMZ_EXPR_MAX_TERMS})")
+    parsed = []
+    for t in terms:
+        if not isinstance(t, (list, tuple)) or len(t) != 2 or not isinstance(t[1], (list, tuple)):
+            raise TypeError(f"{who}: a term is a pair (coefficient, [factors])")
+        c, factors = t
+        if c is not None and not _is_int(c):
+            raise TypeError(f"{who}: a coefficient is an int or None (1)")
+        if c is not None and not 0 <= c < order:
+            raise ValueError(f"{who}: the coefficient {c} is not in [0, group order)")
+        fs = []
+        for f in factors:
+            col, rot = f if isinstance(f, tuple) and len(f) == 2 else (f, 0)
+            if not _is_int(col) or not _is_int(rot):
+                raise TypeError(f"{who}: a factor is a column index or a pair (column, rot) of ints")
+            if not 0 <= col < len(cols):
+                raise ValueError(f"{who}: a factor names column {col} of {len(cols)}")
+            if not -(1 << 31) <= rot < 1 << 31:
+                raise ValueError(f"{who}: rot = {rot} is no int32")
+            fs.append((col, rot))
+        if len(fs) > _native.MSMZ_EXPR_MAX_DEGREE:
+            raise ValueError(f"{who}: a term of {len(fs)} factors (0..{_native.MSMZ_EXPR_MAX_DEGREE})")
+        parsed.append((None if c is None else c.to_bytes(32, "little"), fs))
+    ranges = [(f"the first of column {k}", first, arr) for k, (arr, first) in enumerate(cols)]
+    if N is None:
+        for name, first, arr in ranges:   # (so that the lengths below are those of valid ranges)
+            _mle_first(name, first, arr, who)
+        lengths = {len(arr) - first for arr, first in cols}
+        if len(lengths) != 1:
+            raise ValueError(f"{who}: N is needed when the columns hold different numbers of entries: {sorted(lengths)}")
+        N = lengths.pop()
+    N = _ranges(who, ranges + [("firstOut", firstOut, out)], N, limit=1 << 32)
+    operands = {(col, rot % N) for _, fs in parsed for col, rot in fs}
+    if len(operands) > _native.MSMZ_EXPR_MAX_OPERANDS:
+        raise ValueError(f"{who}: the terms read {len(operands)} distinct (column, rot mod N) pairs "
+                         f"(at most {_native.MSMZ_EXPR_MAX_OPERANDS})")
+    if out is not None:
+        for k, (arr, first) in enumerate(cols):
+            rots = {rot for col, rot in operands if col == k}
+            if arr.handle != out.handle or not rots:
+                continue
+            if rots == {0}:
+                if first != firstOut and abs(first - firstOut) < N:
+                    raise ValueError(f"{who}: the destination [{firstOut}, +{N}) overlaps the input range [{first}, +{N}) "
+                                     f"(column {k}) in part; it may be that range exactly or apart from it")
+            elif abs(first - firstOut) < N:
+                raise ValueError(f"{who}: the destination [{firstOut}, +{N}) overlaps the input range [{first}, +{N}) "
+                                 f"(column {k}); the column is read rotated, so the two may not meet at all")
+    return {"columns": cols, "terms": parsed, "N": N}
 
 
 def check_arg(check, who):

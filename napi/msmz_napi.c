@@ -880,11 +880,49 @@ static napi_value ScalarsLookup(napi_env env, napi_callback_info info) {
   return res;
 }
 
+/* scalarsExpr(ctx, columns (Buffer: nColumns records of sizeof(msmz_expr_column) = 16 bytes, handle and first as
+   little-endian u64), nColumns, factors (Buffer: the factors of all terms in a row, sizeof(msmz_expr_factor) = 8 bytes
+   each, column as little-endian u32 and rot as i32), counts (Buffer: nTerms bytes, the factors of each term), coeffs
+   (Buffer: nTerms * 32 bytes), unit (Buffer: nTerms bytes, 1 = the coefficient is 1 and its 32 bytes are not read),
+   nTerms, n, firstOut, outHandle (0 = a new array)) -> handle of the array written  (msmz_scalars_expr) */
+static napi_value ScalarsExpr(napi_env env, napi_callback_info info) {
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  uint64_t n_columns, n_terms, n, first_out, h = 0;
+  void *colp, *fp, *kp, *cp, *up; size_t coll, fl, kl, cl, ul;
+  if (!get_args(env, info, 11, argv, &ctx) || !opt_buffer(env, argv[1], &colp, &coll) || !get_u64(env, argv[2], &n_columns) ||
+      !opt_buffer(env, argv[3], &fp, &fl) || !opt_buffer(env, argv[4], &kp, &kl) || !opt_buffer(env, argv[5], &cp, &cl) ||
+      !opt_buffer(env, argv[6], &up, &ul) || !get_u64(env, argv[7], &n_terms) || !get_u64(env, argv[8], &n) ||
+      !get_u64(env, argv[9], &first_out) || !get_u64(env, argv[10], &h) || n_columns < 1 || n_columns > MSMZ_EXPR_MAX_COLUMNS ||
+      n_terms < 1 || n_terms > MSMZ_EXPR_MAX_TERMS || coll < n_columns * sizeof(msmz_expr_column) || kl < n_terms ||
+      cl < n_terms * 32 || ul < n_terms)
+    return BAD_ARG(env, "scalarsExpr");
+  msmz_expr_column columns[MSMZ_EXPR_MAX_COLUMNS];   /* (a Buffer need not be aligned) */
+  msmz_expr_factor factors[MSMZ_EXPR_MAX_TERMS * MSMZ_EXPR_MAX_DEGREE];
+  msmz_expr_term terms[MSMZ_EXPR_MAX_TERMS];
+  memcpy(columns, colp, (size_t)n_columns * sizeof(msmz_expr_column));
+  size_t at = 0;
+  for (uint64_t k = 0; k < n_terms; k++) {
+    const size_t nf = ((const uint8_t*)kp)[k];
+    if (nf > MSMZ_EXPR_MAX_DEGREE || fl < (at + nf) * sizeof(msmz_expr_factor)) return BAD_ARG(env, "scalarsExpr");
+    memcpy(factors + at, (const uint8_t*)fp + at * sizeof(msmz_expr_factor), nf * sizeof(msmz_expr_factor));
+    terms[k].coeff = ((const uint8_t*)up)[k] ? NULL : (const uint8_t*)cp + 32 * k;
+    terms[k].factors = nf ? factors + at : NULL;
+    terms[k].n_factors = (uint32_t)nf;
+    terms[k].reserved = 0;
+    at += nf;
+  }
+  msmz_expr e = {columns, (uint32_t)n_columns, (uint32_t)n_terms, terms, n, 0};
+  int st = msmz_scalars_expr(ctx, &e, first_out, &h);
+  if (st) return throw_status(env, st, "msmz_scalars_expr");
+  return make_handle(env, h);
+}
+
 /* descriptorSizes() -> {mleBind, sumcheck, sumcheckTable, sumcheckTerm, maxTables, maxDegree, maxTerms}: what the addon
    was compiled with, for the host to check its packing against (no context).  descriptorSizes("matrix") -> {sparse,
    matvec, matRows, matCols, matvecTranspose}: the same for the descriptors and flags of the sparse-matrix calls;
    descriptorSizes("lookup") -> {lookup, lookupResult, none}: the two descriptors of scalarsLookup and the position of a
-   column entry that is in no table (the call without an argument answers what it always did). */
+   column entry that is in no table; descriptorSizes("expr") -> {exprColumn, exprFactor, exprTerm, expr, maxColumns,
+   maxTerms, maxDegree, maxOperands} (the call without an argument answers what it always did). */
 static napi_value DescriptorSizes(napi_env env, napi_callback_info info) {
   napi_value res, argv[MAX_ARGS];
   size_t argc = MAX_ARGS;
@@ -898,6 +936,17 @@ static napi_value DescriptorSizes(napi_env env, napi_callback_info info) {
     set_num(env, res, "lookup", (double)sizeof(msmz_lookup));
     set_num(env, res, "lookupResult", (double)sizeof(msmz_lookup_result));
     set_num(env, res, "none", (double)0xffffffffu);
+    return res;
+  }
+  if (strcmp(family, "expr") == 0) {   /* the descriptors and limits of scalarsExpr */
+    set_num(env, res, "exprColumn", (double)sizeof(msmz_expr_column));
+    set_num(env, res, "exprFactor", (double)sizeof(msmz_expr_factor));
+    set_num(env, res, "exprTerm", (double)sizeof(msmz_expr_term));
+    set_num(env, res, "expr", (double)sizeof(msmz_expr));
+    set_num(env, res, "maxColumns", (double)MSMZ_EXPR_MAX_COLUMNS);
+    set_num(env, res, "maxTerms", (double)MSMZ_EXPR_MAX_TERMS);
+    set_num(env, res, "maxDegree", (double)MSMZ_EXPR_MAX_DEGREE);
+    set_num(env, res, "maxOperands", (double)MSMZ_EXPR_MAX_OPERANDS);
     return res;
   }
   if (strcmp(family, "matrix") == 0) {
@@ -960,7 +1009,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"scalarsEqTable", ScalarsEqTable}, {"scalarsMleEval", ScalarsMleEval}, {"scalarsMleBind", ScalarsMleBind},
       {"scalarsSumcheckRound", ScalarsSumcheckRound}, {"descriptorSizes", DescriptorSizes},
       {"matrixCreate", MatrixCreate}, {"matrixInfo", MatrixInfo}, {"matrixMul", MatrixMul},
-      {"scalarsLookup", ScalarsLookup},
+      {"scalarsLookup", ScalarsLookup}, {"scalarsExpr", ScalarsExpr},
       {"pointAdd", PointAdd}, {"feBytes", FeBytes}};
   for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); i++) {
     napi_value f;
