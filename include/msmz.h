@@ -684,6 +684,48 @@ int msmz_scalars_mle_eval(msmz_ctx* ctx, uint64_t handle, uint64_t first, uint32
 int msmz_scalars_mle_bind(msmz_ctx* ctx, const msmz_mle_bind* b, uint64_t first_out, uint64_t* out_handle);
 int msmz_scalars_sumcheck_round(msmz_ctx* ctx, const msmz_sumcheck* s, uint32_t* degree, uint8_t* evals_le32);
 
+/* msmz_scalars_sumcheck_step: one step of a sumcheck prover in one call -- every table of round k
+ * is bound to the challenge r_k and the polynomial of round k + 1 comes back, behind one host wait.  A prover's loop is
+ * msmz_scalars_sumcheck_round once, then one step per challenge; the tables are read once and the bound tables written
+ * once, where mle_bind per table followed by sumcheck_round reads the bound tables again.
+ *
+ * With source tables f_0 .. f_(n_tables-1) of v = n_vars variables (tables[j]: 2^v entries from `first` of `handle`),
+ * destinations out_0 .. (out[j]: 2^(v-1) entries from `first` of `handle`, an EXISTING scalar set; msmz_alloc_scalars
+ * makes one -- the call creates no handle), the challenge r and the order `flags` names for BOTH halves of the step:
+ *   1. Bind.  out_j receives exactly what msmz_scalars_mle_bind writes for table j (count 1) with the same r and flag.
+ *   2. Next round.  *degree and evals_le32 receive exactly what msmz_scalars_sumcheck_round returns over out_0 ..
+ *      (n_vars - 1 variables) with the same terms and flag: byte for byte the result of the two-call route.
+ *   3. Last variable, n_vars == 1.  The bound tables have one entry each and no variable is left to sum: *degree = 0 and
+ *      the one value is sum_T c_T prod_(j in T) out_j[0], the final claim the verifier checks (the round body on a pair
+ *      with hi = lo and degree 0).
+ * evals_le32 has room for (MSMZ_SUMCHECK_MAX_DEGREE + 1) * 32 bytes; the bytes beyond *degree + 1 values stay as they were.
+ *
+ * Destinations.  out == NULL: every table in place, out_j = the low half [first, first + 2^(v-1)) of its own source.
+ * A destination range is disjoint from every other destination range and from the source range of every OTHER table
+ * index; against its own source it is disjoint, or exactly the source's low half -- and that only in the high order
+ * (flags == 0).  Every other overlap is MSMZ_ERR_ARG before any launch: the high half, a partial overlap, any in-place
+ * destination with MSMZ_MLE_LOW (out == NULL included).  Sources may overlap each other as far as these rules allow (two
+ * tables may be one range when their destinations are apart from it and from each other).
+ *
+ * Errors, as the four calls above.  MSMZ_ERR_ARG, before any launch: a null ctx, descriptor, tables, terms, r or output
+ * pointer; n_vars == 0 or > 31; unknown flag bits; n_tables, n_terms or a mask outside the limits of sumcheck_round; an
+ * unknown handle or one that is not a scalar set; a source or destination range beyond its set; the overlaps above.
+ * MSMZ_ERR_RANGE: r or a coefficient >= q, found on the host with nothing launched; or a resident entry >= q inside a
+ * source range, found by the kernel (entries outside are not read): then *degree and the output bytes are as they were,
+ * the destinations are unspecified and the context stays usable.  MSMZ_ERR_UNSUPPORTED: a multi-device context. */
+typedef struct msmz_sumcheck_step {
+  const msmz_sumcheck_table* tables;  /* sources: n_tables ranges of 2^n_vars entries */
+  const msmz_sumcheck_table* out;     /* destinations: n_tables ranges of 2^(n_vars-1) entries of EXISTING scalar
+                                         sets; NULL = every table in place (its own low half; high order only) */
+  uint32_t n_tables;                  /* 1 .. MSMZ_SUMCHECK_MAX_TABLES */
+  uint32_t n_vars;                    /* >= 1: the variables the SOURCE tables have */
+  const msmz_sumcheck_term* terms;
+  uint32_t n_terms;                   /* 1 .. MSMZ_SUMCHECK_MAX_TERMS */
+  uint32_t flags;                     /* MSMZ_MLE_LOW or 0: the order of BOTH the bind and the round */
+  const uint8_t* r;                   /* the challenge for the variable bound, 32 bytes LE, < q */
+} msmz_sumcheck_step;                 /* 48 bytes */
+int msmz_scalars_sumcheck_step(msmz_ctx* ctx, const msmz_sumcheck_step* s, uint32_t* degree, uint8_t* evals_le32);
+
 /* Sparse matrices over resident scalar sets: y = M x and y = M^T x mod q with the matrix and both
  * vectors on the device -- the step from a witness z to Az, Bz, Cz of an R1CS, the table of Spartan's second sumcheck
  * (r_A A + r_B B + r_C C)^T eq(r_x), the QAP evaluations of Groth16, and any gather, selection or permutation of a

@@ -133,6 +133,10 @@ void msmz_test_ntt_geometry(uint32_t* pass_log);
  *   round_tile: pair indices one workgroup of msmz_scalars_sumcheck_round sums into one partial sum per value
  *               (MSC_TILE).  The second level of both is that of msmz_scalars_dot (partials_per_pass above). */
 void msmz_test_mle_geometry(uint32_t* run, uint32_t* eval_tile, uint32_t* round_tile);
+/* The geometry of msmz_scalars_sumcheck_step (csrc/mle_kernels.h), for the same purpose (nullable; needs no context):
+ *   step_tile: NEW pair indices (those of the bound tables, 2^(n_vars-2) of them) one workgroup binds and sums into one
+ *              partial sum per value -- the round's tile, over them. */
+void msmz_test_sumcheck_step_geometry(uint32_t* step_tile);
 /* The geometry of msmz_matrix_mul (csrc/matrix_kernels.h), for the same purpose (every pointer nullable; needs no
  * context):
  *   tile            : consecutive non-zeros one workgroup takes and leaves one carry for (MAT_TILE);

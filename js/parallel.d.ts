@@ -26,6 +26,11 @@ export function mleBindArgs(f: ScalarsLike, r: bigint, options: MleBindOptions |
   { nVars: number; count: number; flags: number; first: number; firstOut: number; n: number };
 export function sumcheckRoundArgs(tables: (ScalarsLike | [ScalarsLike, number])[], terms: SumcheckTerm[], options: SumcheckOptions | undefined, order: bigint):
   { tables: [ScalarsLike, number][]; nVars: number; terms: SumcheckTerm[]; flags: number; degree: number };
+export interface SumcheckStepOptions { nVars?: number | null; out?: (DeviceArray | [DeviceArray, number])[] | null; low?: boolean }
+/** the checked arguments of Parallel.sumcheckStep (host only): those of sumcheckRound, r, the destinations and their overlap rules */
+export function sumcheckStepArgs(tables: (ScalarsLike | [ScalarsLike, number])[], terms: SumcheckTerm[], r: bigint,
+  options: { nVars?: number | null; out?: (ScalarsLike | [ScalarsLike, number])[] | null; low?: boolean } | undefined, order: bigint):
+  { tables: [ScalarsLike, number][]; out: [ScalarsLike, number][] | null; nVars: number; terms: SumcheckTerm[]; flags: number; degree: number };
 /** a resident sparse matrix (msmz_matrix_create) */
 export interface SparseMatrix { readonly shape: [number, number]; readonly nnz: number; readonly orientations: "rows" | "cols" | "both"; readonly kind: "matrix"; free(): void }
 export interface SparseMatrixOptions { shape: [number, number]; orientations?: "rows" | "cols" | "both"; firstValue?: number }
@@ -144,6 +149,14 @@ export interface ParallelApi {
    * (arrays or [array, first] pairs), 1 to 8 terms of at most 4 factors, d the most factors of a term; the round sums
    * out the high variable, with `low` variable 0 */
   sumcheckRound(tables: (DeviceArray | [DeviceArray, number])[], terms: SumcheckTerm[], options?: SumcheckOptions): Promise<bigint[]>;
+  /** one step of a sumcheck prover (msmz_scalars_sumcheck_step): binds every table to r as bindMle does and returns the
+   * polynomial sumcheckRound gives over the bound tables; without `out` in place (high order only); nVars 1: the final claim */
+  sumcheckStep(tables: (DeviceArray | [DeviceArray, number])[], terms: SumcheckTerm[], r: bigint, options?: SumcheckStepOptions):
+    Promise<{ degree: number; values: bigint[] }>;
+  /** a whole sumcheck on the prover's side: one sumcheckRound, then one sumcheckStep per challenge = await challenge(values);
+   * the tables are consumed (in place, or with `low` through one scratch array per table that is freed again) */
+  sumcheckProve(tables: (DeviceArray | [DeviceArray, number])[], terms: SumcheckTerm[], nVars: number | null,
+    challenge: (values: bigint[]) => bigint | Promise<bigint>, options?: { low?: boolean }): Promise<{ polys: bigint[][]; challenges: bigint[]; claim: bigint }>;
   /** a resident sparse matrix from triples (rows[k], cols[k], values[k]) in any order, duplicates adding up
    * (msmz_matrix_create); values: a resident scalar array, bigints (uploaded first) or null (every value is 1) */
   sparseMatrix(rows: number[] | Uint32Array, cols: number[] | Uint32Array, values: DeviceArray | bigint[] | null, options: SparseMatrixOptions): Promise<SparseMatrix>;

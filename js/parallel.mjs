@@ -202,8 +202,7 @@ export function mleBindArgs(f, r, { nVars = null, count = 1, low = false, first 
   }
   return { nVars, count, flags: low ? 1 : 0, first, firstOut, n: count * h };
 }
-export function sumcheckRoundArgs(tables, terms, { nVars = null, low = false } = {}, order) {
-  const who = "sumcheckRound";
+export function sumcheckRoundArgs(tables, terms, { nVars = null, low = false } = {}, order, who = "sumcheckRound") {
   if (!Array.isArray(tables) || !Array.isArray(terms)) throw TypeError(`${who}: \`tables\` and \`terms\` are arrays`);
   if (typeof low !== "boolean") throw TypeError(`${who}: \`low\` is a boolean`);
   const tabs = tables.map((t) => {
@@ -233,6 +232,40 @@ export function sumcheckRoundArgs(tables, terms, { nVars = null, low = false } =
   for (const [arr, first] of tabs)
     if (2 ** nVars > arr.n - first) throw Error(`${who}: entries [${first}, +${2 ** nVars}) of an array of ${arr.n}`);
   return { tables: tabs, nVars, terms: out, flags: low ? 1 : 0, degree };
+}
+
+/** The arguments of Parallel.sumcheckStep -> {tables, out, nVars, terms, flags, degree}: those of sumcheckRound, then r,
+ * then the destinations and the overlap rules of include/msmz.h, checked before anything reaches the device
+ * (msm_zprize_amd/parallel.py sumcheck_step_args is the same function).  out: [[array, first]] or null (every table in
+ * place); degree: that of the polynomial returned (0 when nVars is 1). */
+export function sumcheckStepArgs(tables, terms, r, { nVars = null, out = null, low = false } = {}, order, who = "sumcheckStep") {
+  const t = sumcheckRoundArgs(tables, terms, { nVars, low }, order, who);
+  if (typeof r !== "bigint") throw TypeError(`${who}: \`r\` is a bigint`);
+  if (out !== null && !Array.isArray(out)) throw TypeError(`${who}: \`out\` is an array with one destination per table, or null`);
+  const outs = (out || []).map((o) => {
+    const [arr, first] = Array.isArray(o) && !looksLikeScalars(o) && o.length === 2 ? o : [o, 0];
+    if (!looksLikeScalars(arr)) throw TypeError(`${who}: a destination is a resident scalar array or an [array, first] pair`);
+    mleFirst(who, "first", first, arr);
+    return [arr, first];
+  });
+  if (r < 0n || r >= order) throw Error(`${who}: r = ${r} is not in [0, group order)`);
+  const tabs = t.tables, n = 2 ** t.nVars, h = n / 2;
+  if (out !== null && outs.length !== tabs.length) throw Error(`${who}: ${outs.length} destinations for ${tabs.length} tables`);
+  const dst = out === null ? tabs : outs;
+  for (const [arr, first] of outs)
+    if (h > arr.n - first) throw Error(`${who}: entries [${first}, +${h}) of an array of ${arr.n}`);
+  const meet = (a, fa, na, b, fb, nb) => a.handle === b.handle && fa < fb + nb && fb < fa + na;
+  dst.forEach(([d, df], j) => {
+    for (let k = 0; k < j; k++)
+      if (meet(d, df, h, dst[k][0], dst[k][1], h)) throw Error(`${who}: the destinations of tables ${k} and ${j} overlap`);
+    tabs.forEach(([s, sf], k) => {
+      if (!meet(d, df, h, s, sf, n)) return;
+      if (k !== j) throw Error(`${who}: the destination of table ${j} overlaps table ${k}`);
+      if (low || df !== sf)
+        throw Error(`${who}: the destination of table ${j} overlaps its table; it may be the table's low half [${sf}, +${h}) with low = false, or apart from it`);
+    });
+  });
+  return { ...t, out: out === null ? null : outs, degree: t.nVars > 1 ? t.degree : 0 };
 }
 
 /** The arguments of Parallel.sparseMatrix -> {rows, cols (Buffers of little-endian u32), nnz, shape, flags, firstValue} and
@@ -846,6 +879,61 @@ function createCurve(params, kind) {
       }));
       const r = N.scalarsSumcheckRound(ctx, tb, t.tables.length, t.nVars, masks, coeffs, unit, t.terms.length, t.flags);
       return Array.from({ length: r.length / 32 }, (_, k) => bytesToBigint(r, 32 * k, 32));
+    },
+    /** one step of a sumcheck prover in one call (msmz_scalars_sumcheck_step): binds every table of 2^nVars entries to the
+     * bigint r, as bindMle with the same `low` does, and returns {degree, values}, the polynomial sumcheckRound gives over
+     * the bound tables.  options: {nVars, out, low}; `out`: one resident scalar array or [array, first] pair per table,
+     * each apart from every other destination and every other table, and apart from its own table or exactly its low
+     * half (high order only); without `out` every table is bound in place (high order only).  nVars 1 is the last step:
+     * {degree: 0, values: [the final claim]}. */
+    async sumcheckStep(tables, terms, r, options = {}) {
+      const t = sumcheckStepArgs(tables, terms, r, options, params.order);
+      for (const [arr] of [...t.tables, ...(t.out || [])]) if (!isScalars(arr)) throw TypeError("sumcheckStep: a table is a resident scalar array");
+      const pack = (pairs) => {
+        const b = Buffer.alloc(16 * pairs.length);
+        pairs.forEach(([arr, first], j) => {
+          b.writeBigUInt64LE(BigInt(arr.handle), 16 * j);
+          b.writeBigUInt64LE(BigInt(first), 16 * j + 8);
+        });
+        return b;
+      };
+      const masks = Buffer.alloc(4 * t.terms.length), unit = Buffer.alloc(t.terms.length);
+      const coeffs = Buffer.concat(t.terms.map(([c, mask], k) => {
+        masks.writeUInt32LE(mask, 4 * k);
+        unit[k] = c === null ? 1 : 0;
+        return scalarBuf(c === null ? 1n : c);
+      }));
+      const res = N.scalarsSumcheckStep(ctx, pack(t.tables), t.out === null ? null : pack(t.out), t.tables.length, t.nVars, masks,
+        coeffs, unit, t.terms.length, t.flags, scalarBuf(r));
+      const values = Array.from({ length: res.length / 32 }, (_, k) => bytesToBigint(res, 32 * k, 32));
+      return { degree: values.length - 1, values };
+    },
+    /** the prover's side of a whole sumcheck: one sumcheckRound, then one sumcheckStep per variable with r =
+     * await challenge(values of the round before), a bigint below the group order -- the transcript is the caller's.
+     * Returns {polys, challenges, claim}.  A host loop and nothing else; the tables are consumed: in the high order they
+     * are bound in place, with `low` the steps go back and forth between each table and one scratch array per table,
+     * allocated here and freed before returning.  The tables lie apart from each other. */
+    async sumcheckProve(tables, terms, nVars, challenge, { low = false } = {}) {
+      const t = sumcheckRoundArgs(tables, terms, { nVars, low }, params.order, "sumcheckProve");
+      if (typeof challenge !== "function") throw TypeError("sumcheckProve: `challenge` is a function of the round's values returning a bigint");
+      let cur = t.tables;
+      const polys = [await Parallel.sumcheckRound(cur, terms, { nVars: t.nVars, low })], challenges = [];
+      let claim = null, spare = [];
+      try {
+        if (low) spare = cur.map(() => DeviceArray.make(curve, N.allocScalars(ctx, 2 ** (t.nVars - 1)), 2 ** (t.nVars - 1), "scalars"));
+        let other = spare.map((a) => [a, 0]);
+        for (let v = t.nVars; v >= 1; v--) {
+          const r = await challenge([...polys[polys.length - 1]]);
+          const { values } = await Parallel.sumcheckStep(cur, terms, r, { nVars: v, out: low ? other : null, low });
+          challenges.push(r);
+          if (v > 1) polys.push(values);
+          else claim = values[0];
+          if (low) [cur, other] = [other, cur];
+        }
+      } finally {
+        for (const a of spare) a.free();
+      }
+      return { polys, challenges, claim };
     },
     /** a resident sparse matrix of shape [nRows, nCols] from triples (rows[k], cols[k], values[k]) in any order, triples
      * with the same (row, col) adding up (msmz_matrix_create).  values: a resident scalar array (value k =

@@ -107,6 +107,12 @@ class MsmzSumcheck(C.Structure):   # msmz_sumcheck (include/msmz.h): the round p
                 ("terms", C.POINTER(MsmzSumcheckTerm)), ("n_terms", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class MsmzSumcheckStep(C.Structure):   # msmz_sumcheck_step (include/msmz.h): bind every table to r, the next round's polynomial
+    _fields_ = [("tables", C.POINTER(MsmzSumcheckTable)), ("out", C.POINTER(MsmzSumcheckTable)), ("n_tables", C.c_uint32),
+                ("n_vars", C.c_uint32), ("terms", C.POINTER(MsmzSumcheckTerm)), ("n_terms", C.c_uint32), ("flags", C.c_uint32),
+                ("r", C.c_char_p)]
+
+
 MSMZ_MAT_ROWS, MSMZ_MAT_COLS = 1, 2
 MSMZ_MATVEC_TRANSPOSE = 1
 
@@ -253,6 +259,7 @@ EXPORTS = {
     "msmz_scalars_mle_eval": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_char_p, C.c_char_p]),
     "msmz_scalars_mle_bind": (C.c_int, [C.c_void_p, C.POINTER(MsmzMleBind), C.c_uint64, C.POINTER(C.c_uint64)]),
     "msmz_scalars_sumcheck_round": (C.c_int, [C.c_void_p, C.POINTER(MsmzSumcheck), C.POINTER(C.c_uint32), C.c_char_p]),
+    "msmz_scalars_sumcheck_step": (C.c_int, [C.c_void_p, C.POINTER(MsmzSumcheckStep), C.POINTER(C.c_uint32), C.c_char_p]),
     "msmz_matrix_create": (C.c_int, [C.c_void_p, C.POINTER(MsmzSparse), C.POINTER(C.c_uint64)]),
     "msmz_matrix_info": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                    C.POINTER(C.c_uint32)]),
@@ -278,6 +285,7 @@ EXPORTS = {
     "msmz_test_lookup_slot": (C.c_uint32, [C.c_int, C.c_char_p, C.c_uint64]),
     "msmz_test_lookup_small_table": (C.c_uint32, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "msmz_test_mle_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "msmz_test_sumcheck_step_geometry": (None, [C.POINTER(C.c_uint32)]),
     "msmz_test_fixed_base_plan": (C.c_int, [C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                             C.POINTER(C.c_uint64)]),
     "msmz_test_set_fixed_base_window": (C.c_int, [C.c_void_p, C.c_int]),

@@ -125,13 +125,14 @@ class IEngine {
                               uint64_t* n_zero) = 0;
   // msmz_scalars_ntt: number-theoretic transforms over ranges of a scalar set (ntt_kernels.h)
   virtual int scalars_ntt(const msmz_ntt& t, uint64_t first_out, uint64_t* out_handle) = 0;
-  // msmz_scalars_eq_table / _mle_eval / _mle_bind / _sumcheck_round: multilinear polynomials over ranges of a scalar set
-  // (mle_kernels.h).  The defaults: a context that has none -- a multi-device one, where the two halves of every pair
+  // msmz_scalars_eq_table / _mle_eval / _mle_bind / _sumcheck_round / _sumcheck_step: multilinear polynomials over ranges
+  // of a scalar set (mle_kernels.h).  The defaults: a context that has none -- a multi-device one, where the two halves of every pair
   // live in different blocks of 2^16 entries.
   virtual int scalars_eq_table(const uint8_t*, uint32_t, const uint8_t*, uint64_t*) { return MSMZ_ERR_UNSUPPORTED; }
   virtual int scalars_mle_eval(uint64_t, uint64_t, uint32_t, const uint8_t*, uint8_t*) { return MSMZ_ERR_UNSUPPORTED; }
   virtual int scalars_mle_bind(const msmz_mle_bind&, uint64_t, uint64_t*) { return MSMZ_ERR_UNSUPPORTED; }
   virtual int scalars_sumcheck_round(const msmz_sumcheck&, uint32_t*, uint8_t*) { return MSMZ_ERR_UNSUPPORTED; }
+  virtual int scalars_sumcheck_step(const msmz_sumcheck_step&, uint32_t*, uint8_t*) { return MSMZ_ERR_UNSUPPORTED; }
   // msmz_matrix_create / _matrix_info / _matrix_mul: sparse matrices against ranges of a scalar set (matrix_kernels.h).
   // The defaults: a multi-device context has none -- a gather reads across every block of 2^16 entries.
   virtual int matrix_create(const msmz_sparse&, uint64_t*) { return MSMZ_ERR_UNSUPPORTED; }

@@ -135,12 +135,17 @@
 // the multilinear kernels (mle_kernels.h), a translation unit of their own (kern_mle.hip); NT = the tables of a round
 #define MSMZ_INST_SUMCHECK(Fr, NT, PFX)                                                                           \
   PFX template __global__ void k_scalars_sumcheck_round<Fr, NT>(uint32_t*, ScTables, FrScTerms, uint32_t, int, uint32_t*);
+#define MSMZ_INST_SUMCHECK_STEP(Fr, NT, PFX)   /* NT = 1 .. MSC_STEP_FUSED_TABLES */                               \
+  PFX template __global__ void k_scalars_sumcheck_step<Fr, NT>(uint32_t*, ScOuts, ScTables, FrScTerms, FrConst, uint32_t, int, uint32_t*);
 #define MSMZ_INST_MLE(F, Fr, PFX)                                                                                 \
   PFX template __global__ void k_scalars_eq_table<Fr>(uint32_t*, FrConst, FrEqPoint, uint32_t);                   \
   PFX template __global__ void k_scalars_mle_eval<Fr>(uint32_t*, const uint32_t*, FrEqPoint, uint32_t, uint32_t*); \
   PFX template __global__ void k_scalars_mle_bind<Fr>(uint32_t*, const uint32_t*, FrConst, uint32_t, uint32_t, int, uint32_t*); \
+  PFX template __global__ void k_scalars_sumcheck_last<Fr>(uint32_t*, ScOuts, ScTables, FrScTerms, FrConst, uint32_t, uint32_t*); \
   MSMZ_INST_SUMCHECK(Fr, 1, PFX) MSMZ_INST_SUMCHECK(Fr, 2, PFX) MSMZ_INST_SUMCHECK(Fr, 3, PFX)                    \
-  MSMZ_INST_SUMCHECK(Fr, 4, PFX) MSMZ_INST_SUMCHECK(Fr, 5, PFX) MSMZ_INST_SUMCHECK(Fr, 6, PFX)
+  MSMZ_INST_SUMCHECK(Fr, 4, PFX) MSMZ_INST_SUMCHECK(Fr, 5, PFX) MSMZ_INST_SUMCHECK(Fr, 6, PFX)                    \
+  MSMZ_INST_SUMCHECK_STEP(Fr, 1, PFX) MSMZ_INST_SUMCHECK_STEP(Fr, 2, PFX) MSMZ_INST_SUMCHECK_STEP(Fr, 3, PFX)     \
+  MSMZ_INST_SUMCHECK_STEP(Fr, 4, PFX) MSMZ_INST_SUMCHECK_STEP(Fr, 5, PFX)
 
 // the sparse-matrix kernels (matrix_kernels.h), a translation unit of their own (kern_matrix.hip)
 #define MSMZ_INST_MATRIX(F, Fr, PFX)                                                                              \

@@ -1,10 +1,11 @@
-// Multilinear polynomials over resident scalar sets (msmz_scalars_eq_table / _mle_eval / _mle_bind / _sumcheck_round,
-// include/msmz.h).  A polynomial in v variables is a range of 2^v records, entry i =
+// Multilinear polynomials over resident scalar sets (msmz_scalars_eq_table / _mle_eval / _mle_bind / _sumcheck_round /
+// _sumcheck_step, include/msmz.h; DESIGN.md sections 24 and 30).  A polynomial in v variables is a range of 2^v records, entry i =
 // f(b_0, .., b_(v-1)) with i = sum b_j 2^j: variable 0 is the lowest index bit.
 //     eq_table:        out_i = scale eq(r, i),   eq(r, i) = prod_j (b_j r_j + (1 - b_j)(1 - r_j))
 //     mle_eval:        sum_i f_i eq(r, i)        (the table is generated, never stored)
 //     mle_bind:        out_i = lo + r (hi - lo)  over pairs (i, i + h) or (2i, 2i + 1)
 //     sumcheck_round:  g(t) = sum_i sum_T c_T prod_(j in T) (lo_j + t (hi_j - lo_j)),  t = 0 .. d
+//     sumcheck_step:   mle_bind of every table, and sumcheck_round over what it wrote, in one pass
 // all mod q with the F_q functions of fr.h, on canonical 8-word records.  The first part of this file is host/device
 // code: the geometry, the run of eq values one thread owns, the bind of one pair and the round body of one pair index,
 // which tests/native/mle_test.cpp runs on the CPU.  The kernels follow, for the device compiler only.
@@ -25,6 +26,9 @@ constexpr int MSC_TILE = SDOT_THREADS * MSC_E;
 constexpr int MSC_MAX_TABLES = 6;
 constexpr int MSC_MAX_DEGREE = 4;
 constexpr int MSC_MAX_TERMS = 8;
+// sumcheck_step: the table counts k_scalars_sumcheck_step is instantiated for.  With more tables the compiler has no
+// allocation of it without scratch, and the host queues the bind and round kernels instead.
+constexpr int MSC_STEP_FUSED_TABLES = 5;
 // the head of the result buffer of a round: MSC_MAX_DEGREE + 1 values, then the error word
 constexpr int MSC_ERR_WORD = (MSC_MAX_DEGREE + 1) * 8;
 constexpr int MSC_HEAD_BYTES = 256;
@@ -132,6 +136,66 @@ MSMZ_HD void fr_sc_pair(uint32_t (&acc)[MSC_MAX_DEGREE + 1][8], uint32_t (&cur)[
       }
     }
   });
+}
+
+// The step body of one NEW pair index: the two entries of every bound table that make the pair (lo, hi) of the next
+// round are bound from their source pairs, stored, and go into fr_sc_pair as they are -- two fr_bind per table, then the
+// round body.  load(J, K, dst) brings source record K of table J (0, 1: lo and hi of the pair that binds into the new
+// lo; 2, 3: of the one that binds into the new hi) and returns whether it was >= q; store(J, K, src) takes the bound
+// entry K (0: the new lo, 1: the new hi); J and K are integral constants.  A table's first pair is loaded, bound and
+// stored before its second is loaded: with the temporary, three records of a table are live at most, and once the loop
+// is through the live set is that of the round (cur, hi, acc).  Returns whether any record was >= q.
+template <class Fr, int NT, class Load, class Store>
+MSMZ_HD bool fr_sc_step(uint32_t (&acc)[MSC_MAX_DEGREE + 1][8], const FrScTerms& T, const uint32_t* r_mont, Load load,
+                        Store store) {
+  uint32_t cur[NT][8], hi[NT][8];
+  bool bad = false;
+  static_for<0, NT>([&](auto J) {
+    uint32_t t[8];
+    bad |= load(J, std::integral_constant<int, 0>{}, cur[J]);
+    bad |= load(J, std::integral_constant<int, 1>{}, t);
+    fr_bind<Fr>(cur[J], cur[J], t, r_mont);
+    store(J, std::integral_constant<int, 0>{}, cur[J]);
+    bad |= load(J, std::integral_constant<int, 2>{}, hi[J]);
+    bad |= load(J, std::integral_constant<int, 3>{}, t);
+    fr_bind<Fr>(hi[J], hi[J], t, r_mont);
+    store(J, std::integral_constant<int, 1>{}, hi[J]);
+  });
+  fr_sc_pair<Fr, NT>(acc, cur, hi, T);
+  return bad;
+}
+
+// The last step, source tables of ONE variable: every table has one bound entry and no variable is left to sum.  The
+// value is the round body on a pair with hi = lo and degree 0 (fr_sc_step with both source pairs the same and
+// T.degree == 0; tests/native/sumcheck_step_test.cpp holds the two against each other): acc += sum_T c_T prod_(j in T)
+// bound_j, the products in the order of fr_sc_pair.  One pair of loops over tables and terms with nothing indexed in
+// registers, so one function serves every table count: load(j, k, dst) brings source record k (0, 1) of table j and
+// returns whether it was >= q, store(j, src) takes the bound entry, bound(j, dst) brings it back.
+template <class Fr, class Load, class Store, class Bound>
+MSMZ_HD bool fr_sc_last(uint32_t* acc, const FrScTerms& T, uint32_t n_tables, const uint32_t* r_mont, Load load, Store store,
+                        Bound bound) {
+  bool bad = false;
+  for (uint32_t j = 0; j < n_tables; j++) {
+    uint32_t lo[8], hi[8];
+    bad |= load(j, 0, lo);
+    bad |= load(j, 1, hi);
+    fr_bind<Fr>(lo, lo, hi, r_mont);
+    store(j, lo);
+  }
+  for (uint32_t k = 0; k < T.n_terms; k++) {
+    uint32_t p[8];
+#pragma unroll
+    for (int w = 0; w < 8; w++) p[w] = T.coeff[k][w];
+    for (uint32_t j = 0; j < n_tables; j++) {
+      if ((T.mask[k] >> j) & 1u) {
+        uint32_t v[8];
+        bound(j, v);
+        fr_mont_mul<Fr>(p, p, v);
+      }
+    }
+    fr_add<Fr>(acc, acc, p);
+  }
+  return bad;
 }
 
 }  // namespace msmz
@@ -255,6 +319,82 @@ __global__ void __launch_bounds__(SDOT_THREADS) k_scalars_sumcheck_round(uint32_
       __syncthreads();   // (fr_block_sum's LDS words are free for the next value)
     }
   });
+}
+
+// the destinations of a step: the first record of each range
+struct ScOuts {
+  uint32_t* p[MSC_MAX_TABLES];
+};
+
+// msmz_scalars_sumcheck_step: binds every table to r and leaves the partial sums of the NEXT round, the one over the
+// bound tables, where k_scalars_sumcheck_round leaves them (the same tiles, the same fold).  quarter = 2^(n_vars - 2) new
+// pair indices, thread and tile geometry of the round over them; h = 2 quarter entries per bound table.  New pair index
+// i reads the source records `at` and writes the bound entries `to`:
+//     high variable:  at = (i, i + h, i + quarter, i + quarter + h), to = (i, i + quarter)
+//     low:            at = (4i, 4i + 1, 4i + 2, 4i + 3),             to = (2i, 2i + 1)
+// each of them i times a uniform factor plus a uniform offset, formed where it is used (a source table has at most 2^31
+// entries: 32 bits hold every index).  A destination may be its own table's low half in the high order: the records a
+// thread writes, i and i + quarter, are among the four it reads and among no other thread's, and each is read before it
+// is written (fr_sc_step).  n_vars >= 2: the last step is k_scalars_sumcheck_last.  A record >= q raises bit 2 of *err.
+template <class Fr, int NT>
+__global__ void __launch_bounds__(SDOT_THREADS) k_scalars_sumcheck_step(uint32_t* partial, ScOuts out, ScTables tab,
+                                                                        FrScTerms T, FrConst r_mont, uint32_t quarter,
+                                                                        int low, uint32_t* err) {
+  const uint32_t base = blockIdx.x * MSC_TILE + threadIdx.x;
+  const uint32_t h = 2 * quarter;
+  const uint32_t at_mul = low ? 4u : 1u, to_mul = low ? 2u : 1u;
+  const uint32_t at1 = low ? 1u : h, at2 = low ? 2u : quarter, at3 = low ? 3u : quarter + h, to1 = low ? 1u : quarter;
+  uint32_t acc[MSC_MAX_DEGREE + 1][8];
+#pragma unroll
+  for (int t = 0; t <= MSC_MAX_DEGREE; t++) {
+#pragma unroll
+    for (int w = 0; w < 8; w++) acc[t][w] = 0;
+  }
+  bool bad = false;
+#pragma unroll 1
+  for (int e = 0; e < MSC_E; e++) {
+    const uint32_t i = base + (uint32_t)e * SDOT_THREADS;
+    if (i < quarter) {
+      bad |= fr_sc_step<Fr, NT>(
+          acc, T, r_mont.w,
+          [&](auto J, auto K, uint32_t* dst) {
+            constexpr int k = decltype(K)::value;
+            return fr_load<Fr>(dst, tab.p[J], i * at_mul + (k == 0 ? 0u : k == 1 ? at1 : k == 2 ? at2 : at3));
+          },
+          [&](auto J, auto K, const uint32_t* src) {
+            fr_store(out.p[J], i * to_mul + (decltype(K)::value ? to1 : 0u), src);
+          });
+    }
+  }
+  if (bad) atomicOr(err, 4u);
+  static_for<0, MSC_MAX_DEGREE + 1>([&](auto Tt) {
+    constexpr int t = decltype(Tt)::value;
+    if ((uint32_t)t <= T.degree) {   // (uniform: every thread of the workgroup reaches the same block sums)
+      fr_block_sum<Fr>(acc[t]);
+      if (threadIdx.x == 0) fr_store(partial, (uint64_t)t * gridDim.x + blockIdx.x, acc[t]);
+      __syncthreads();   // (fr_block_sum's LDS words are free for the next value)
+    }
+  });
+}
+
+// The last step of msmz_scalars_sumcheck_step (n_vars == 1): ONE thread binds entries (0, 1) of every table into entry 0
+// of its destination and leaves the terms over the bound entries in partial record 0 (fr_sc_last); the tables and the
+// terms are read with uniform indices from the argument segment.  A destination is apart from every other table's
+// source and from every other destination, so table j's bind reads the source as it was, in place too, and the bound
+// entries read back are the thread's own writes.  Folded like a round of one tile and one value.
+template <class Fr>
+__global__ void __launch_bounds__(64) k_scalars_sumcheck_last(uint32_t* partial, ScOuts out, ScTables tab, FrScTerms T,
+                                                              FrConst r_mont, uint32_t n_tables, uint32_t* err) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  uint32_t acc[8];
+#pragma unroll
+  for (int w = 0; w < 8; w++) acc[w] = 0;
+  const bool bad = fr_sc_last<Fr>(
+      acc, T, n_tables, r_mont.w, [&](uint32_t j, int k, uint32_t* dst) { return fr_load<Fr>(dst, tab.p[j], k); },
+      [&](uint32_t j, const uint32_t* src) { fr_store(out.p[j], 0, src); },
+      [&](uint32_t j, uint32_t* dst) { load_scalar(dst, out.p[j], 0); });
+  if (bad) atomicOr(err, 4u);
+  fr_store(partial, 0, acc);
 }
 
 }  // namespace msmz

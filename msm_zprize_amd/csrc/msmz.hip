@@ -273,6 +273,9 @@ int msmz_scalars_mle_bind(msmz_ctx* c, const msmz_mle_bind* b, uint64_t first_ou
 int msmz_scalars_sumcheck_round(msmz_ctx* c, const msmz_sumcheck* s, uint32_t* degree, uint8_t* evals) {
   return c && s && degree && evals ? c->engine->scalars_sumcheck_round(*s, degree, evals) : MSMZ_ERR_ARG;
 }
+int msmz_scalars_sumcheck_step(msmz_ctx* c, const msmz_sumcheck_step* s, uint32_t* degree, uint8_t* evals) {
+  return c && s && degree && evals ? c->engine->scalars_sumcheck_step(*s, degree, evals) : MSMZ_ERR_ARG;
+}
 int msmz_matrix_create(msmz_ctx* c, const msmz_sparse* s, uint64_t* h) {
   return c && s && h ? c->engine->matrix_create(*s, h) : MSMZ_ERR_ARG;
 }
@@ -326,6 +329,9 @@ void msmz_test_mle_geometry(uint32_t* run, uint32_t* eval_tile, uint32_t* round_
   if (run) *run = MLE_RUN;
   if (eval_tile) *eval_tile = MLE_TILE;
   if (round_tile) *round_tile = MSC_TILE;
+}
+void msmz_test_sumcheck_step_geometry(uint32_t* step_tile) {
+  if (step_tile) *step_tile = MSC_TILE;
 }
 
 // the 2-adicity of a curve's scalar field, or -1; w (nullable): the default 2^log_n-th root of unity, log_n <= that

@@ -1,7 +1,7 @@
 // The arithmetic mod q over resident scalar sets, as one stage: linear combinations, inner products, powers, recurrences,
-// batch inversion, and the multilinear four (eq table, evaluation, binding, sumcheck round), which share the inner
-// product's record and fold (sdot_, k_scalars_dot_fold).  ScalarOps owns sdot_ and sscan_ and reaches the engine through
-// the SetsCore it is built with (sets_core.h); ResidentSets (resident.h) forwards the IEngine methods here.
+// batch inversion, and the multilinear calls (eq table, evaluation, binding, sumcheck round and step), which share the
+// inner product's record and fold (sdot_, k_scalars_dot_fold).  ScalarOps owns sdot_ and sscan_ and reaches the engine
+// through the SetsCore it is built with (sets_core.h); ResidentSets (resident.h) forwards the IEngine methods here.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -266,19 +266,8 @@ class ScalarOps {
     for (uint32_t j = 0; j < s.n_tables; j++)
       if (!(tab.p[j] = core_.handles_.range(s.tables[j].handle, 1, s.tables[j].first, n, 8))) return MSMZ_ERR_ARG;
     FrScTerms T{};
-    T.n_terms = s.n_terms;
-    for (uint32_t k = 0; k < s.n_terms; k++) {
-      const uint32_t m = s.terms[k].mask, f = (uint32_t)__builtin_popcount(m);
-      if (m == 0 || (m >> s.n_tables) || f > (uint32_t)MSC_MAX_DEGREE) return MSMZ_ERR_ARG;
-      T.mask[k] = m;
-      if (f > T.degree) T.degree = f;
-    }
-    for (uint32_t k = 0; k < s.n_terms; k++) {
-      uint32_t c[8] = {1, 0, 0, 0, 0, 0, 0, 0};
-      if (s.terms[k].coeff)
-        if (int st = Core::read_fr(s.terms[k].coeff, c, false)) return st;
-      fr_sc_coeff<Fr>(T.coeff[k], c, __builtin_popcount(T.mask[k]));
-    }
+    if (int st = read_masks(s.terms, s.n_terms, s.n_tables, &T)) return st;
+    if (int st = read_coeffs(s.terms, &T)) return st;
     MSMZ_HIP(hipSetDevice(core_.device_));
     hipStream_t stream = core_.stream_;
     const uint32_t half = (uint32_t)(n >> 1), tiles = (half + MSC_TILE - 1) / MSC_TILE, values = T.degree + 1;
@@ -312,7 +301,109 @@ class ScalarOps {
     return MSMZ_OK;
   }
 
+  // msmz_scalars_sumcheck_step: mle_bind of every table and sumcheck_round over what it wrote, in ONE launch plus the
+  // fold (k_scalars_sumcheck_step, mle_kernels.h; k_scalars_sumcheck_last for tables of one variable) -- the record, the
+  // partial sums, the fold and the ONE host wait are the round's, over quarter = 2^(n_vars - 2) new pair indices.  Every
+  // argument check, the overlap rules of the header among them, comes before the host values are read (MSMZ_ERR_RANGE)
+  // and both before anything is queued.
+  int scalars_sumcheck_step(const msmz_sumcheck_step& s, uint32_t* degree, uint8_t* evals) {
+    if (!degree || !evals || !s.tables || !s.terms || !s.r || s.n_tables < 1 || s.n_tables > (uint32_t)MSC_MAX_TABLES ||
+        s.n_terms < 1 || s.n_terms > (uint32_t)MSC_MAX_TERMS || s.n_vars == 0 || s.n_vars > (uint32_t)MLE_MAX_VARS ||
+        (s.flags & ~(uint32_t)MSMZ_MLE_LOW))
+      return MSMZ_ERR_ARG;
+    const uint64_t n = 1ull << s.n_vars, h = n >> 1;
+    const bool low = (s.flags & MSMZ_MLE_LOW) != 0, last = s.n_vars == 1;
+    const msmz_sumcheck_table* dst = s.out ? s.out : s.tables;   // (in place: the low half starts where the source does)
+    ScTables tab{};
+    ScOuts out{};
+    for (uint32_t j = 0; j < s.n_tables; j++) {
+      if (!(tab.p[j] = core_.handles_.range(s.tables[j].handle, 1, s.tables[j].first, n, 8))) return MSMZ_ERR_ARG;
+      if (!(out.p[j] = core_.handles_.range(dst[j].handle, 1, dst[j].first, h, 8))) return MSMZ_ERR_ARG;
+    }
+    for (uint32_t j = 0; j < s.n_tables; j++) {
+      for (uint32_t k = 0; k < s.n_tables; k++) {
+        if (k < j && dst[j].handle == dst[k].handle && ranges_meet(dst[j].first, h, dst[k].first, h)) return MSMZ_ERR_ARG;
+        if (dst[j].handle != s.tables[k].handle || !ranges_meet(dst[j].first, h, s.tables[k].first, n)) continue;
+        // a destination on a source: its own, as the low half, in the high order, and nothing else
+        if (k != j || low || dst[j].first != s.tables[j].first) return MSMZ_ERR_ARG;
+      }
+    }
+    FrScTerms T{};
+    if (int st = read_masks(s.terms, s.n_terms, s.n_tables, &T)) return st;
+    FrConst r{};
+    if (int st = Core::read_fr(s.r, r.w, true)) return st;
+    if (int st = read_coeffs(s.terms, &T)) return st;
+    if (last) T.degree = 0;   // no variable is left: the one value is the terms over the one-entry tables
+    MSMZ_HIP(hipSetDevice(core_.device_));
+    hipStream_t stream = core_.stream_;
+    const uint32_t quarter = last ? 1u : (uint32_t)(h >> 1), tiles = (quarter + MSC_TILE - 1) / MSC_TILE, values = T.degree + 1;
+    typename Core::Record rec;
+    rec.head = MSC_HEAD_BYTES, rec.err_word = MSC_ERR_WORD;
+    const int st = core_.recorded(sdot_, MSC_HEAD_BYTES + (size_t)values * tiles * 32, [&](uint32_t* d_res) {
+      uint32_t* partial = d_res + MSC_HEAD_BYTES / 4;
+      uint32_t* d_err = d_res + MSC_ERR_WORD;
+      if (last) {
+        hipLaunchKernelGGL((k_scalars_sumcheck_last<Fr>), dim3(1), dim3(64), 0, stream, partial, out, tab, T, r, s.n_tables, d_err);
+      } else if (s.n_tables > (uint32_t)MSC_STEP_FUSED_TABLES) {
+        // the table counts the fused kernel does not have without scratch: the bind kernel per table and the round kernel
+        // over the destinations, queued behind each other -- the same bytes written and returned, the same ONE wait
+        ScTables bound{};
+        for (uint32_t j = 0; j < s.n_tables; j++) {
+          bound.p[j] = out.p[j];
+          hipLaunchKernelGGL((k_scalars_mle_bind<Fr>), Core::blocks_of(h), dim3(kBlock), 0, stream, out.p[j], tab.p[j], r, s.n_vars,
+                             (uint32_t)h, low ? 1 : 0, d_err);
+        }
+        hipLaunchKernelGGL((k_scalars_sumcheck_round<Fr, MSC_MAX_TABLES>), dim3(tiles), dim3(SDOT_THREADS), 0, stream, partial,
+                           bound, T, quarter, low ? 1 : 0, d_err);
+        static_assert(MSC_STEP_FUSED_TABLES + 1 == MSC_MAX_TABLES, "one table count takes this route");
+      } else {
+#define MSMZ_SC_LAUNCH(NT)                                                                                             \
+  case NT:                                                                                                             \
+    hipLaunchKernelGGL((k_scalars_sumcheck_step<Fr, NT>), dim3(tiles), dim3(SDOT_THREADS), 0, stream, partial, out, tab, T, \
+                       r, quarter, low ? 1 : 0, d_err);                                                                \
+    break
+        switch (s.n_tables) {
+          MSMZ_SC_LAUNCH(1);
+          MSMZ_SC_LAUNCH(2);
+          MSMZ_SC_LAUNCH(3);
+          MSMZ_SC_LAUNCH(4);
+          MSMZ_SC_LAUNCH(5);
+        }
+#undef MSMZ_SC_LAUNCH
+        static_assert(MSC_STEP_FUSED_TABLES == 5, "one instance per table count");
+      }
+      hipLaunchKernelGGL((k_scalars_dot_fold<Fr>), dim3(values), dim3(SDOT_THREADS), 0, stream, d_res, (const uint32_t*)partial,
+                         tiles, 0);
+    }, rec);
+    if (st) return st;
+    *degree = T.degree;
+    memcpy(evals, core_.h_res_.p, (size_t)values * 32);
+    return MSMZ_OK;
+  }
+
  private:
+  // the masks of a round's terms into T, with its degree (MSMZ_ERR_ARG), and then the coefficients, c 2^(256 f) for a
+  // term of f factors (fr_sc_coeff; MSMZ_ERR_RANGE): two steps, so that a caller finishes its argument checks in between
+  static int read_masks(const msmz_sumcheck_term* terms, uint32_t n_terms, uint32_t n_tables, FrScTerms* T) {
+    T->n_terms = n_terms;
+    for (uint32_t k = 0; k < n_terms; k++) {
+      const uint32_t m = terms[k].mask, f = (uint32_t)__builtin_popcount(m);
+      if (m == 0 || (m >> n_tables) || f > (uint32_t)MSC_MAX_DEGREE) return MSMZ_ERR_ARG;
+      T->mask[k] = m;
+      if (f > T->degree) T->degree = f;
+    }
+    return MSMZ_OK;
+  }
+  static int read_coeffs(const msmz_sumcheck_term* terms, FrScTerms* T) {
+    for (uint32_t k = 0; k < T->n_terms; k++) {
+      uint32_t c[8] = {1, 0, 0, 0, 0, 0, 0, 0};
+      if (terms[k].coeff)
+        if (int st = Core::read_fr(terms[k].coeff, c, false)) return st;
+      fr_sc_coeff<Fr>(T->coeff[k], c, __builtin_popcount(T->mask[k]));
+    }
+    return MSMZ_OK;
+  }
+
   // the point of an eq table or an evaluation (n_vars values of 32 bytes, each < q) in the form the kernels take
   static int read_point(const uint8_t* point, uint32_t n_vars, FrEqPoint* pt) {
     memset(pt, 0, sizeof(*pt));

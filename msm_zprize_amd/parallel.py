@@ -528,6 +528,57 @@ class _Parallel:
         _check(lib().msmz_scalars_sumcheck_round(self._c._ctx, C.byref(s), C.byref(degree), buf), "msmz_scalars_sumcheck_round")
         return [int.from_bytes(buf.raw[32 * k:32 * k + 32], "little") for k in range(degree.value + 1)]
 
+    def sumcheckStep(self, tables, terms, nVars, r, out=None, low=False):
+        """One step of a sumcheck prover in one call (msmz_scalars_sumcheck_step): binds every table of 2^nVars entries
+        to the int r, as bindMle(.., low=low) does, and returns (degree, [g(0) .. g(degree)]), the polynomial
+        sumcheckRound(.., nVars - 1, low) gives over the bound tables -- the same ints as the two-call route.  `tables`
+        and `terms` are sumcheckRound's.  `out`: one resident scalar array or (array, first) pair per table, receiving
+        its 2^(nVars-1) bound entries; each apart from every other destination and from every other table, and apart
+        from its own table or exactly that table's low half (low=False only).  out=None: every table in place, its low
+        half overwritten (low=False only).  nVars=None: what the first table holds.  nVars == 1 is the last step: the
+        bound tables have one entry each and (0, [sum_T c_T prod_(j in T) bound_j]) comes back, the final claim."""
+        t = sumcheck_step_args(tables, terms, nVars, r, out, low, self._c.params["order"])
+        as_tables = lambda pairs: (_native.MsmzSumcheckTable * len(pairs))(*[_native.MsmzSumcheckTable(a.handle, f) for a, f in pairs])
+        tabs, outs = as_tables(t["tables"]), None if t["out"] is None else as_tables(t["out"])
+        trms = (_native.MsmzSumcheckTerm * len(t["terms"]))(*[_native.MsmzSumcheckTerm(c, m) for c, m in t["terms"]])
+        s = _native.MsmzSumcheckStep(tabs, outs, len(t["tables"]), t["nVars"], trms, len(t["terms"]), t["flags"], t["r"])
+        degree = C.c_uint32(0)
+        buf = C.create_string_buffer(32 * (_native.MSMZ_SUMCHECK_MAX_DEGREE + 1))
+        _check(lib().msmz_scalars_sumcheck_step(self._c._ctx, C.byref(s), C.byref(degree), buf), "msmz_scalars_sumcheck_step")
+        return degree.value, [int.from_bytes(buf.raw[32 * k:32 * k + 32], "little") for k in range(degree.value + 1)]
+
+    def sumcheckProve(self, tables, terms, nVars, challenge, low=False):
+        """The prover's side of a whole sumcheck over sum_i sum_T c_T prod_(j in T) tables[j][i]: one sumcheckRound, then
+        one sumcheckStep per variable with r = challenge(values of the round before), an int below the group order --
+        the transcript is the caller's.  Returns (polys, challenges, claim): the nVars round polynomials as lists of
+        ints, the nVars challenges, and the final claim sum_T c_T prod_(j in T) f_j(r).  A host loop and nothing else.
+        The tables are consumed: low=False binds them in place; low=True goes back and forth between each table and
+        one scratch array per table, allocated here and freed before returning.  The tables lie apart from each other."""
+        t = sumcheck_round_args(tables, terms, nVars, low, self._c.params["order"], "sumcheckProve")
+        if not callable(challenge):
+            raise TypeError("sumcheckProve: `challenge` is a function of the round's values returning an int")
+        cur, n_vars = t["tables"], t["nVars"]
+        polys, challenges, claim = [self.sumcheckRound(cur, terms, n_vars, low)], [], None
+        spare = []
+        try:
+            if low:
+                spare = [_resident(self._c, "scalars", 1 << (n_vars - 1), "msmz_alloc_scalars", 1 << (n_vars - 1)) for _ in cur]
+            other = [(a, 0) for a in spare]
+            for v in range(n_vars, 0, -1):
+                r = challenge(list(polys[-1]))
+                _, values = self.sumcheckStep(cur, terms, v, r, other if low else None, low)
+                challenges.append(r)
+                if v > 1:
+                    polys.append(values)
+                else:
+                    claim = values[0]
+                if low:
+                    cur, other = other, cur
+        finally:
+            for a in spare:
+                a.free()
+        return polys, challenges, claim
+
     # -- sparse matrices against resident scalar arrays (msmz_matrix_create / _matrix_mul) -------------
     def sparseMatrix(self, rows, cols, values=None, shape=None, orientations="rows", firstValue=0):
         """A resident sparse matrix of shape = (nRows, nCols) from triples (rows[k], cols[k], values[k]) in any order;
@@ -1193,6 +1244,48 @@ def sumcheck_round_args(tables, terms, nVars, low, order, who="sumcheckRound"):
         if (1 << nVars) > len(arr) - first:
             raise ValueError(f"{who}: entries [{first}, +{1 << nVars}) of an array of {len(arr)}")
     return {"tables": tabs, "nVars": nVars, "terms": out, "flags": _native.MSMZ_MLE_LOW if low else 0, "degree": degree}
+
+
+def sumcheck_step_args(tables, terms, nVars, r, out, low, order, who="sumcheckStep"):
+    """Arguments of sumcheckStep -> dict(tables, out, nVars, terms, flags, degree, r), checked before anything reaches the
+    device: those of sumcheckRound, then r, then the destinations and the overlap rules of include/msmz.h.  out:
+    [(array, first)] or None (every table in place); degree: that of the polynomial returned (0 when nVars == 1)."""
+    t = sumcheck_round_args(tables, terms, nVars, low, order, who)
+    if not _is_int(r):
+        raise TypeError(f"{who}: `r` is an int")
+    if out is not None and not isinstance(out, (list, tuple)):
+        raise TypeError(f"{who}: `out` is a list with one destination per table, or None")
+    outs = []
+    for o in out or ():
+        arr, first = o if isinstance(o, tuple) and len(o) == 2 else (o, 0)
+        if not _is_array(arr, "scalars"):
+            raise TypeError(f"{who}: a destination is a resident scalar array or an (array, first) pair")
+        _mle_first("first", first, arr, who)
+        outs.append((arr, first))
+    if not 0 <= r < order:
+        raise ValueError(f"{who}: r = {r} is not in [0, group order)")
+    tabs, n, h = t["tables"], 1 << t["nVars"], 1 << (t["nVars"] - 1)
+    if out is not None and len(outs) != len(tabs):
+        raise ValueError(f"{who}: {len(outs)} destinations for {len(tabs)} tables")
+    dst = tabs if out is None else outs
+    for arr, first in outs:
+        if h > len(arr) - first:
+            raise ValueError(f"{who}: entries [{first}, +{h}) of an array of {len(arr)}")
+    meet = lambda a, fa, na, b, fb, nb: a.handle == b.handle and fa < fb + nb and fb < fa + na
+    for j, (d, df) in enumerate(dst):
+        for k in range(j):
+            if meet(d, df, h, dst[k][0], dst[k][1], h):
+                raise ValueError(f"{who}: the destinations of tables {k} and {j} overlap")
+        for k, (s, sf) in enumerate(tabs):
+            if not meet(d, df, h, s, sf, n):
+                continue
+            if k != j:
+                raise ValueError(f"{who}: the destination of table {j} overlaps table {k}")
+            if low or df != sf:
+                raise ValueError(f"{who}: the destination of table {j} overlaps its table; it may be the table's low half "
+                                 f"[{sf}, +{h}) with low=False, or apart from it")
+    return {**t, "out": None if out is None else outs, "r": r.to_bytes(32, "little"),
+            "degree": t["degree"] if t["nVars"] > 1 else 0}
 
 
 def _index_array(name, v, bound, who):

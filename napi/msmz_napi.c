@@ -792,6 +792,57 @@ static napi_value ScalarsSumcheckRound(napi_env env, napi_callback_info info) {
   return buf;
 }
 
+/* allocScalars(ctx, n) -> handle of a new scalar array of n entries whose contents are unspecified, for a call that
+   writes into an existing array  (msmz_alloc_scalars) */
+static napi_value AllocScalars(napi_env env, napi_callback_info info) {
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  uint64_t n, h = 0;
+  if (!get_args(env, info, 2, argv, &ctx) || !get_u64(env, argv[1], &n)) return BAD_ARG(env, "allocScalars");
+  int st = msmz_alloc_scalars(ctx, n, &h);
+  if (st) return throw_status(env, st, "msmz_alloc_scalars");
+  return make_handle(env, h);
+}
+
+/* scalarsSumcheckStep(ctx, tables, outs (a Buffer like tables: one destination per table, or null: every table in place),
+   nTables, nVars, masks, coeffs, unit, nTerms, flags, r (32-byte Buffer)) -- tables, masks, coeffs, unit and flags as
+   scalarsSumcheckRound takes them -> Buffer of (degree + 1) * 32 bytes: the polynomial of the next round over the bound
+   tables, or with nVars == 1 the one value that is left  (msmz_scalars_sumcheck_step) */
+static napi_value ScalarsSumcheckStep(napi_env env, napi_callback_info info) {
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  uint64_t n_tables, n_vars, n_terms, flags;
+  const uint8_t* r;
+  void *tp, *op, *mp, *cp, *up; size_t tl, ol = 0, ml, cl, ul;
+  napi_valuetype out_type;
+  if (!get_args(env, info, 11, argv, &ctx) || !opt_buffer(env, argv[1], &tp, &tl) || napi_typeof(env, argv[2], &out_type) != napi_ok ||
+      !get_u64(env, argv[3], &n_tables) || !get_u64(env, argv[4], &n_vars) || n_vars >> 32 ||
+      !opt_buffer(env, argv[5], &mp, &ml) || !opt_buffer(env, argv[6], &cp, &cl) || !opt_buffer(env, argv[7], &up, &ul) ||
+      !get_u64(env, argv[8], &n_terms) || !get_u64(env, argv[9], &flags) || flags >> 32 ||
+      !scalar_or_null(env, argv[10], &r) || !r || n_tables < 1 || n_tables > MSMZ_SUMCHECK_MAX_TABLES || n_terms < 1 ||
+      n_terms > MSMZ_SUMCHECK_MAX_TERMS || tl < n_tables * sizeof(msmz_sumcheck_table) || ml < n_terms * 4 || cl < n_terms * 32 ||
+      ul < n_terms)
+    return BAD_ARG(env, "scalarsSumcheckStep");
+  const int in_place = out_type == napi_null || out_type == napi_undefined;
+  if (!in_place && (!opt_buffer(env, argv[2], &op, &ol) || ol < n_tables * sizeof(msmz_sumcheck_table)))
+    return BAD_ARG(env, "scalarsSumcheckStep");
+  msmz_sumcheck_table tables[MSMZ_SUMCHECK_MAX_TABLES], outs[MSMZ_SUMCHECK_MAX_TABLES];   /* (a Buffer need not be aligned) */
+  msmz_sumcheck_term terms[MSMZ_SUMCHECK_MAX_TERMS];
+  memcpy(tables, tp, (size_t)n_tables * sizeof(msmz_sumcheck_table));
+  if (!in_place) memcpy(outs, op, (size_t)n_tables * sizeof(msmz_sumcheck_table));
+  for (uint64_t k = 0; k < n_terms; k++) {
+    memcpy(&terms[k].mask, (const uint8_t*)mp + 4 * k, 4);
+    terms[k].coeff = ((const uint8_t*)up)[k] ? NULL : (const uint8_t*)cp + 32 * k;
+  }
+  msmz_sumcheck_step s = {tables, in_place ? NULL : outs, (uint32_t)n_tables, (uint32_t)n_vars, terms, (uint32_t)n_terms,
+                          (uint32_t)flags, r};
+  uint8_t evals[(MSMZ_SUMCHECK_MAX_DEGREE + 1) * 32];
+  uint32_t degree = 0;
+  int st = msmz_scalars_sumcheck_step(ctx, &s, &degree, evals);
+  if (st) return throw_status(env, st, "msmz_scalars_sumcheck_step");
+  napi_value buf;
+  NAPI_CALL(env, napi_create_buffer_copy(env, ((size_t)degree + 1) * 32, evals, NULL, &buf));
+  return buf;
+}
+
 /* matrixCreate(ctx, rows, cols (Buffers of nnz little-endian u32 each), nnz, valHandle (0 = every value is 1), valFirst,
    nRows, nCols, flags (1 = rows, 2 = cols, 3 = both)) -> handle of a new sparse matrix  (msmz_matrix_create) */
 static napi_value MatrixCreate(napi_env env, napi_callback_info info) {
@@ -922,7 +973,8 @@ static napi_value ScalarsExpr(napi_env env, napi_callback_info info) {
    matvec, matRows, matCols, matvecTranspose}: the same for the descriptors and flags of the sparse-matrix calls;
    descriptorSizes("lookup") -> {lookup, lookupResult, none}: the two descriptors of scalarsLookup and the position of a
    column entry that is in no table; descriptorSizes("expr") -> {exprColumn, exprFactor, exprTerm, expr, maxColumns,
-   maxTerms, maxDegree, maxOperands} (the call without an argument answers what it always did). */
+   maxTerms, maxDegree, maxOperands}; descriptorSizes("sumcheckStep") -> {sumcheckStep, sumcheckTable, sumcheckTerm}
+   (the call without an argument answers what it always did). */
 static napi_value DescriptorSizes(napi_env env, napi_callback_info info) {
   napi_value res, argv[MAX_ARGS];
   size_t argc = MAX_ARGS;
@@ -947,6 +999,12 @@ static napi_value DescriptorSizes(napi_env env, napi_callback_info info) {
     set_num(env, res, "maxTerms", (double)MSMZ_EXPR_MAX_TERMS);
     set_num(env, res, "maxDegree", (double)MSMZ_EXPR_MAX_DEGREE);
     set_num(env, res, "maxOperands", (double)MSMZ_EXPR_MAX_OPERANDS);
+    return res;
+  }
+  if (strcmp(family, "sumcheckStep") == 0) {   /* the descriptors of scalarsSumcheckStep */
+    set_num(env, res, "sumcheckStep", (double)sizeof(msmz_sumcheck_step));
+    set_num(env, res, "sumcheckTable", (double)sizeof(msmz_sumcheck_table));
+    set_num(env, res, "sumcheckTerm", (double)sizeof(msmz_sumcheck_term));
     return res;
   }
   if (strcmp(family, "matrix") == 0) {
@@ -1007,7 +1065,8 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"scalarsPowers", ScalarsPowers}, {"scalarsRecurrence", ScalarsRecurrence}, {"scalarsInverse", ScalarsInverse},
       {"scalarsNtt", ScalarsNtt}, {"scalarsRootOfUnity", ScalarsRootOfUnity},
       {"scalarsEqTable", ScalarsEqTable}, {"scalarsMleEval", ScalarsMleEval}, {"scalarsMleBind", ScalarsMleBind},
-      {"scalarsSumcheckRound", ScalarsSumcheckRound}, {"descriptorSizes", DescriptorSizes},
+      {"scalarsSumcheckRound", ScalarsSumcheckRound}, {"scalarsSumcheckStep", ScalarsSumcheckStep}, {"allocScalars", AllocScalars},
+      {"descriptorSizes", DescriptorSizes},
       {"matrixCreate", MatrixCreate}, {"matrixInfo", MatrixInfo}, {"matrixMul", MatrixMul},
       {"scalarsLookup", ScalarsLookup}, {"scalarsExpr", ScalarsExpr},
       {"pointAdd", PointAdd}, {"feBytes", FeBytes}};
