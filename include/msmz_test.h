@@ -172,6 +172,16 @@ void msmz_test_expr_geometry(uint32_t* threads_per_workgroup, uint32_t* register
 int msmz_test_fixed_base_plan(int curve_id, uint64_t n, int bits, int32_t* c, int32_t* K, uint64_t* entries);
 int msmz_test_set_fixed_base_window(msmz_ctx* ctx, int c);
 int msmz_test_fixed_base_tables(msmz_ctx* ctx, uint64_t* built);
+/* The caches of an engine and the grid of a transform, for tests that fill a cache past its size or run more vectors
+ * than a launch has rows of workgroups.
+ *   msmz_test_cache_geometry (every pointer nullable; needs no context): ntt_sets = the twiddle sets an engine keeps,
+ *     the oldest leaves first (NTT_CACHE); fixed_tables = the fixed-base tables it keeps, the one unused longest leaves
+ *     first (FIXED_CACHE); ntt_grid_vectors = the most vectors of a batch that get a workgroup row of their own in a pass
+ *     of msmz_scalars_ntt (NTT_GRID_VECTORS): with a larger count a workgroup takes every ntt_grid_vectors-th vector.
+ *   msmz_test_ntt_tables: *built = the twiddle sets this context has built so far (a transform served from the cache adds
+ *     none; a multi-device context: the sum over its engines). */
+void msmz_test_cache_geometry(uint32_t* ntt_sets, uint32_t* fixed_tables, uint32_t* ntt_grid_vectors);
+int msmz_test_ntt_tables(msmz_ctx* ctx, uint64_t* built);
 /* out[i] = op(a[i], b[i]) for i < n; a, b, out: n * fe_bytes */
 int msmz_test_field(msmz_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t* out);
 /* GLV split of n 32-byte scalars: s0, s1 = magnitudes (16 bytes each), neg = 2 sign bytes per scalar

@@ -290,6 +290,8 @@ EXPORTS = {
                                             C.POINTER(C.c_uint64)]),
     "msmz_test_set_fixed_base_window": (C.c_int, [C.c_void_p, C.c_int]),
     "msmz_test_fixed_base_tables": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "msmz_test_ntt_tables": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "msmz_test_cache_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "msmz_test_field": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_uint64, C.c_char_p]),
     "msmz_test_field_limbs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                         C.c_char_p]),

@@ -133,6 +133,8 @@ struct FixedPlan {
   uint64_t entries;
 };
 
+constexpr uint32_t FIXED_CACHE = 4;   // window tables an engine keeps (PointOps::fixed_table, point_ops.h)
+
 // the table of n points with scalars below 2^bits (bits as fixed_base_bits gives it): the c in [4, 16] with the fewest
 // products for table and points together, among those whose table fits FIXED_TABLE_CAP; the smaller c on a tie.  For
 // fixed bits c does not fall as n grows: a wider window has no more additions per point and a larger table.

@@ -155,6 +155,8 @@ class IEngine {
   // msmz_test_set_fixed_base_window / msmz_test_fixed_base_tables: the forced window width, the tables built so far
   virtual int test_set_fixed_base_window(int) { return MSMZ_ERR_UNSUPPORTED; }
   virtual uint64_t test_fixed_base_tables() { return 0; }
+  // msmz_test_ntt_tables: the twiddle sets built so far
+  virtual uint64_t test_ntt_tables() { return 0; }
   // msmz_test_poison: fill every scratch buffer with `pattern` and arm the allocations to come (-1: disarm)
   virtual int test_poison(int, uint64_t*, uint64_t*) { return MSMZ_ERR_UNSUPPORTED; }
   // msmz_test_scratch: the scratch buffers of engine `engine` of the context that hold memory, and their bytes

@@ -404,6 +404,17 @@ int msmz_test_fixed_base_tables(msmz_ctx* c, uint64_t* built) {
   return MSMZ_OK;
 }
 
+int msmz_test_ntt_tables(msmz_ctx* c, uint64_t* built) {
+  if (!c || !built) return MSMZ_ERR_ARG;
+  *built = c->engine->test_ntt_tables();
+  return MSMZ_OK;
+}
+void msmz_test_cache_geometry(uint32_t* ntt_sets, uint32_t* fixed_tables, uint32_t* ntt_grid_vectors) {
+  if (ntt_sets) *ntt_sets = NTT_CACHE;
+  if (fixed_tables) *fixed_tables = FIXED_CACHE;
+  if (ntt_grid_vectors) *ntt_grid_vectors = NTT_GRID_VECTORS;
+}
+
 int msmz_test_set_glv_bits(msmz_ctx* c, int bits) { return c ? c->engine->test_set_glv_bits(bits) : MSMZ_ERR_ARG; }
 int msmz_test_retries(msmz_ctx* c) { return c ? c->engine->test_retries() : -1; }
 int msmz_test_set_limits(msmz_ctx* c, uint64_t pass_entries, uint64_t batch_entries) {

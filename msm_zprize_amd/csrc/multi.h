@@ -599,6 +599,11 @@ class MultiEngine : public IEngine {
     for (Worker* w : workers_) built += w->eng->test_fixed_base_tables();
     return built;
   }
+  uint64_t test_ntt_tables() override {
+    uint64_t built = 0;
+    for (Worker* w : workers_) built += w->eng->test_ntt_tables();
+    return built;
+  }
   void test_passes(uint64_t* range_passes, uint64_t* sub_batches) override {
     uint64_t rp = 0, sb = 0;
     for (Worker* w : workers_) {

@@ -94,7 +94,7 @@ class NttOps {
       for (uint32_t j = 0; j < P; j++) {
         uint32_t* dst = j + 1 == P ? out : scratch[j & 1];
         const NttArgs a = ntt_pass_args(call, j, src, stride, dst);
-        const dim3 grid(ntt_pass_tiles(a.pass), t.count < 65535u ? t.count : 65535u);
+        const dim3 grid(ntt_pass_tiles(a.pass), t.count < NTT_GRID_VECTORS ? t.count : NTT_GRID_VECTORS);
         hipLaunchKernelGGL((k_ntt_pass<Fr>), grid, dim3(NTT_THREADS), 0, core_.stream_, a);
         src = dst;
         stride = n;
@@ -102,6 +102,8 @@ class NttOps {
     });
     return st || !hd.mem.p ? st : core_.add_handle(std::move(hd), out_handle);
   }
+
+  uint64_t test_ntt_tables() const { return ntt_built_; }
 
  private:
   // a table of powers (ntt_kernels.h) into device memory, queued on the stream
@@ -113,7 +115,6 @@ class NttOps {
 
   // *tables = the three twiddle tables of `plan` for the root w (the inverse root of an inverse transform), from the
   // cache or built now.  At most NTT_CACHE sets are kept, the oldest goes first; all are freed with the engine.
-  static constexpr size_t NTT_CACHE = 8;
   struct NttTwiddles {
     uint32_t log_n;
     uint32_t w[8];
@@ -141,6 +142,7 @@ class NttOps {
     // (no wait on the way through: the transform's own is the one wait.  A failed launch drains what was queued, and c
     // frees its memory)
     if (const hipError_t e = hipGetLastError(); e != hipSuccess) return core_.wait_after(e);
+    ntt_built_++;
     if (ntt_cache_.size() == NTT_CACHE) {
       // (the set that leaves may still be read by a transform in flight only if the stream has work: every entry point
       // returns with the stream drained, so it has none)
@@ -156,6 +158,7 @@ class NttOps {
   DevBuf ntt_scratch_;                 // one or two copies of the batch between the passes of a plan
   DevBuf ntt_coset_;                   // the two-level powers of the coset shift of the call in progress
   std::deque<NttTwiddles> ntt_cache_;  // the twiddle tables of the last NTT_CACHE (log_n, root) pairs
+  uint64_t ntt_built_ = 0;             // ... the sets built so far (msmz_test_ntt_tables)
 };
 
 }  // namespace msmz

@@ -29,6 +29,8 @@ constexpr int NTT_RUN_LOG = 2;                    // a strided pass moves runs o
 constexpr int NTT_STRIDED_LOG = NTT_PASS_LOG - NTT_RUN_LOG;   // ... and therefore covers at most 8 stages
 constexpr int NTT_MAX_LOG = 32;                   // indices of a set fit 32 bits
 constexpr int NTT_MAX_PASSES = (NTT_MAX_LOG + NTT_STRIDED_LOG - 1) / NTT_STRIDED_LOG;   // 4
+constexpr uint32_t NTT_GRID_VECTORS = 65535;     // grid.y of a pass at the most: a workgroup takes every NTT_GRID_VECTORS-th vector
+constexpr uint32_t NTT_CACHE = 8;                // twiddle sets an engine keeps (NttOps::ntt_twiddles, ntt_ops.h)
 
 // One pass, as the kernel receives it (by value).  n / R_j columns, tiles of C = 2^log_c of them.
 struct NttPass {

@@ -205,7 +205,6 @@ class PointOps {
   // The window table of a base (k_fixed_table) from the cache or built now.  The key: the base's canonical words (on the
   // Weierstrass curves all zero = the point at infinity), the window width and the number of windows.  At most
   // FIXED_CACHE tables are kept, the one unused longest goes first; all are freed with the engine.
-  static constexpr size_t FIXED_CACHE = 4;
   struct FixedKey {
     uint32_t xy[RW];
     int c, K;

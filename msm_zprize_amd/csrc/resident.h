@@ -303,6 +303,7 @@ class ResidentSets : public SetsCore<Cfg> {
   int points_fixed_base(const msmz_fixed_base& f, uint64_t n, uint64_t* h) override { return point_ops_.points_fixed_base(f, n, h); }
   int test_set_fixed_base_window(int c) override { return point_ops_.test_set_fixed_base_window(c); }
   uint64_t test_fixed_base_tables() override { return point_ops_.test_fixed_base_tables(); }
+  uint64_t test_ntt_tables() override { return ntt_ops_.test_ntt_tables(); }
   int scalars_combine(const msmz_scalar_term& x, const msmz_scalar_term* y, uint64_t n, uint64_t first_out, uint64_t* out) override {
     return scalar_ops_.scalars_combine(x, y, n, first_out, out);
   }

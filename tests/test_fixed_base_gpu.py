@@ -1,7 +1,7 @@
 """msmz_points_fixed_base on the GPU (k_fixed_table, k_fixed_mul; csrc/fixed_kernels.h): downloads against the oracle's
 [s]B (tests/fixed_base_util.py) at the wave and block edges of the shared inversion, over every kind of base and forced
-window widths; byte for byte against msmz_points_mul over n copies of B; the bit bound and its errors; the table cache;
-an SRS end to end; multi-engine contexts; the argument errors."""
+window widths; byte for byte against msmz_points_mul over n copies of B; the bit bound and its errors; the table cache,
+filled, overfilled and reordered by a hit; an SRS end to end; multi-engine contexts; the argument errors."""
 import ctypes as C
 import random
 
@@ -273,6 +273,62 @@ def test_tables_are_cached(mod, label):
         assert st == 0 and _built(curve) == 3
         assert _raw(curve, h5, 0, n) == _raw(curve, h6, 0, n)
         _free(curve, h1, h2, h3, h4, h5, h6)
+        sa.free()
+    finally:
+        curve.close()
+
+
+def _cache_tables():
+    """the tables an engine keeps, from msmz_test_cache_geometry"""
+    t = C.c_uint32(0)
+    _lib().msmz_test_cache_geometry(None, C.byref(t), None)
+    return t.value
+
+
+@pytest.mark.parametrize("label", ["pallas", "ed-on-bls12-377"])
+def test_table_cache_evicts_the_one_unused_longest(mod, label):
+    """fixed_tables + 1 bases at n = 65 on a context of its own.  With four tables: build A, B, C, D; hit A; build E.  Then
+    A is still cached (built unchanged) and B is not (built + 1, which makes C the table that leaves): D is served from
+    the cache and C is built again.  Every result against the oracle's [s]B, so a table freed under a call, or the table
+    of another base handed out, shows as wrong points.  Then the same sequence under a forced window width: an equal
+    base under another width is another key, so every first use builds although the planner's tables are cached"""
+    T = _cache_tables()
+    assert T >= 3
+    curve, params = _create(mod, label), P.CURVES[label]
+    try:
+        n = 65
+        rng = random.Random(17 + FB.ALL.index(label))
+        scalars = FB.gpu_scalars(params, n, 5)
+        sa = curve.Parallel.scalarsFromBigints(scalars)
+        g = U.generator(params)
+        bases = [U.scale(params, rng.randrange(2, params["order"]), g) for _ in range(T + 1)]
+        assert len({(b["x"], b["y"]) for b in bases}) == T + 1
+        want = [[FB.expected(label, s, b) for s in scalars] for b in bases]
+
+        def use(k, builds, what):
+            before = _built(curve)
+            st, h = _fixed(curve, sa, n, xy=_xy(params, bases[k]))
+            assert st == 0 and h != 0, (what, k)
+            assert _built(curve) - before == builds, (what, k, "built")
+            _assert_equal(params, _points(curve, h, n), want[k], (what, k))
+            _free(curve, h)
+
+        cc, K, entries = C.c_int32(), C.c_int32(), C.c_uint64()
+        assert _lib().msmz_test_fixed_base_plan(params["curve_id"], n, 0, C.byref(cc), C.byref(K), C.byref(entries)) == 0
+        forced = 4 if cc.value != 4 else 5
+        assert _built(curve) == 0
+        for width in (0, forced):
+            _window(curve, width)
+            for k in range(T):
+                use(k, 1, (width, "fill"))
+            use(0, 0, (width, "hit the oldest"))
+            use(T, 1, (width, "overflow"))          # the oldest not hit, bases[1], leaves
+            use(0, 0, (width, "hit before the overflow: kept"))
+            use(1, 1, (width, "the oldest not hit: gone"))   # bases[2] leaves
+            use(3, 0, (width, "still cached"))
+            use(2, 1, (width, "left with the rebuild"))
+        assert _built(curve) == 2 * (T + 3)
+        _window(curve, 0)
         sa.free()
     finally:
         curve.close()

@@ -379,3 +379,19 @@ def test_null_context_is_a_bad_argument(lib):
     h = C.c_uint64(77)
     assert lib.msmz_scalars_ntt(None, C.byref(t), 0, C.byref(h)) == 1
     assert h.value == 77
+
+
+def test_cache_hooks_need_no_device(lib):
+    """msmz_test_cache_geometry answers without a context, every pointer nullable; msmz_test_ntt_tables without a context
+    or a counter is MSMZ_ERR_ARG and writes nothing.  (What the values mean is held by the GPU tests that fill the caches
+    and the grid past them.)"""
+    from msm_zprize_amd import _native
+    for name in ("msmz_test_cache_geometry", "msmz_test_ntt_tables"):
+        assert name in _native.EXPORTS and getattr(lib, name) is not None
+    a, b, c = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    lib.msmz_test_cache_geometry(C.byref(a), C.byref(b), C.byref(c))
+    lib.msmz_test_cache_geometry(None, None, None)
+    assert a.value >= 2 and b.value >= 3 and 1 <= c.value <= 65535   # (grid.y of a launch has 16 bits)
+    built = C.c_uint64(5)
+    assert lib.msmz_test_ntt_tables(None, C.byref(built)) == 1 and built.value == 5
+    assert lib.msmz_test_ntt_tables(None, None) == 1

@@ -3,7 +3,9 @@ a transform over Python integers, bit-exact, at every size up to two stages past
 the calls that were there before (innerProduct of the input with scalarPowers of g w^k, the transform of a unit vector,
 the round trip) at the smallest full two-pass size and the smallest three-pass size; cosets, short inputs, batches,
 ranges and in-place destinations, two uses (a polynomial product, a commitment from evaluations), the errors, and a
-two-engine context.  Sizes come from msmz_test_ntt_plan and msmz_test_ntt_geometry."""
+two-engine context; more vectors than a launch has rows of workgroups, so that a workgroup's loop over its vectors goes
+round again; more (log_n, root) keys than the twiddle cache keeps.  Sizes come from msmz_test_ntt_plan,
+msmz_test_ntt_geometry and msmz_test_cache_geometry."""
 import ctypes as C
 import random
 
@@ -256,6 +258,142 @@ def test_batch_equals_one_at_a_time(curves, count):
     y = par.ntt(x, log_n, nIn=n_in, count=count)
     assert _raw(curve, y, 0, count * n) == one_by_one(n_in)
     y.free(); x.free()
+
+
+def _cache_geometry():
+    """(twiddle sets an engine keeps, fixed-base tables it keeps, vectors that get a workgroup row of their own)"""
+    a, b, c = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    _lib().msmz_test_cache_geometry(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
+def _assert_vectors(got, want, n, what):
+    """two downloads of whole vectors of n entries: equal, or the first vectors that differ"""
+    if got != want:
+        assert len(got) == len(want), what
+        bad = [v for v in range(len(want) // (32 * n)) if got[32 * n * v:32 * n * (v + 1)] != want[32 * n * v:32 * n * (v + 1)]]
+        raise AssertionError((what, "vectors that differ", len(bad), bad[:4], bad[-2:]))
+
+
+@pytest.mark.parametrize("label", ["bls12-377", "pallas"])
+def test_more_vectors_than_workgroup_rows(curves, label):
+    """count = ntt_grid_vectors + 2 transforms of 8 entries (n_in = 5): k_ntt_pass launches ntt_grid_vectors rows of
+    workgroups, and the rows of vectors 0 and 1 go round their loop a second time, for vectors ntt_grid_vectors and
+    ntt_grid_vectors + 1 -- the only place where the barrier behind the store, the error flag carried from one trip to the
+    next and the two strides of a second trip (in_stride = 5, out_stride = 8) are exercised.
+
+    Forward on a coset into a new handle, every entry against the Python-integer transform (vector v is m_v times one of
+    four base vectors, so its transform is m_v times that vector's); the inverse on the coset back to the zero-padded
+    inputs; a plain transform in place with n_in = n; log_n = 0, where a vector is one entry and a pass has no stage.  One
+    entry >= q in the first vector of a second trip (and, apart from it, in vector 1: a first trip with a clean second one
+    behind it) is MSMZ_ERR_RANGE and leaves no handle; the source set ends in such an entry one past the addressed
+    range throughout, which is never read.
+
+    A plan of two passes at this count would need more than 2^27 entries and as much again in scratch: it is left out.
+    The loop over the vectors is the same code in every pass."""
+    curve, q = curves(label), S.order(label)
+    par = curve.Parallel
+    G = _cache_geometry()[2]
+    count, log_n, n, n_in, g = G + 2, 3, 8, 5, 7
+    assert count * n == 524296 and G + 1 < count
+    w = N.root(label, log_n)
+    rng = random.Random(G + S.ALL.index(label))
+    base = [N.inputs(label, n_in, 3)] + [[rng.randrange(q) for _ in range(n_in)] for _ in range(3)]
+    mult = [1, 1, 1, 1] + [rng.randrange(1, q) for _ in range(count - 4)]
+    mult[G], mult[G + 1] = q - 1, 2   # (vector G = - vector 3, vector G + 1 = twice vector 0: neither equals a first trip's)
+    xs = [m * b % q for v, m in enumerate(mult) for b in base[v % 4]]
+    x = _upload(curve, xs + [0])
+    _plant(curve, x, count * n_in, q)   # one past the addressed range, for every call below
+
+    def scaled(vectors):
+        return S.encode([m * t % q for v, m in enumerate(mult) for t in vectors[v % 4]])
+    raw_in = S.encode(xs)
+    # forward on a coset, n_in < n
+    y = par.ntt(x, log_n, shift=g, nIn=n_in, count=count)
+    assert len(y) == count * n
+    _assert_vectors(_raw(curve, y, 0, count * n), scaled([N.transform(q, b, n, w, False, g) for b in base]), n, "forward")
+    # the inverse back: the zero-padded inputs
+    padded = b"".join(raw_in[32 * n_in * v:32 * n_in * (v + 1)] + bytes(32 * (n - n_in)) for v in range(count))
+    back = par.ntt(y, log_n, inverse=True, shift=g, count=count)
+    _assert_vectors(_raw(curve, back, 0, count * n), padded, n, "inverse")
+    y.free()
+    # plain, in place, n_in = n
+    assert par.ntt(back, log_n, count=count, out=back) is back
+    _assert_vectors(_raw(curve, back, 0, count * n), scaled([N.transform(q, b, n, w) for b in base]), n, "in place")
+    back.free()
+    # one entry per vector, no stage
+    for inverse in (False, True):
+        one = par.ntt(x, 0, count=count, inverse=inverse)
+        _assert_vectors(_raw(curve, one, 0, count), raw_in[:32 * count], 1, ("log_n = 0", inverse))
+        one.free()
+    # an entry >= q in a second trip, and in a first trip that a clean second trip follows
+    for vector in (G, 1):
+        bad = _upload(curve, xs)
+        _plant(curve, bad, vector * n_in + 2, q + vector)
+        for flags, shift, cnt in ((COSET, g, count), (0, None, G + 1)):
+            assert _ntt(curve, bad, log_n, flags, n_in, cnt, shift=shift) == (MSMZ_ERR_RANGE, 0), (vector, flags, cnt)
+        _good_call_is_correct(curve, label)
+        bad.free()
+    # the call after it, over the same rows
+    y = par.ntt(x, log_n, shift=g, nIn=n_in, count=count)
+    _assert_vectors(_raw(curve, y, 0, count * n), scaled([N.transform(q, b, n, w, False, g) for b in base]), n, "afterwards")
+    y.free(); x.free()
+
+
+# ---------------------------------------------------------------------------------------------- the twiddle cache
+def _ntt_built(curve):
+    b = C.c_uint64(1 << 40)
+    assert _lib().msmz_test_ntt_tables(curve._ctx, C.byref(b)) == 0
+    return b.value
+
+
+@pytest.mark.parametrize("armed", [False, True], ids=["plain", "poisoned"])
+@pytest.mark.parametrize("ends", ["one-pass", "two-pass"])
+def test_twiddle_cache_evicts_the_oldest(mod, ends, armed):
+    """ntt_sets + 1 keys on a context of its own, each transform against the Python-integer one and each building one
+    set; the first key again is built again (its set left when the last one came) and is right; the keys used last are
+    served from the cache; the second key, which left when the first came back, is built again: first in, first out.  An
+    inverse transform of a cached size builds one more set (the inverse root is another key), a custom root equal to
+    the default one builds none.  `two-pass`: the first and the last key are the two smallest sizes of two passes, so
+    that the set which leaves, and the one built in its place, are large ones.  `poisoned`: the same with
+    msmz_test_poison armed at 0xa5, so that a set freed and handed out again, or read before it is filled, shows"""
+    from test_scratch_poison_gpu import fresh, poison
+    label = "bls12-377"
+    q = S.order(label)
+    sets = _cache_geometry()[0]
+    limit = _sizes()[0]
+    keys = list(range(1, sets + 2))
+    if ends == "two-pass":
+        keys[0], keys[-1] = limit + 1, limit + 2
+    assert len(set(keys)) == sets + 1 and max(keys) <= N.two_adicity(label)
+    with fresh(mod, label) as curve:
+        if armed:
+            poison(curve, 0xa5)
+        par = curve.Parallel
+
+        def run(log_n, builds, what, inverse=False, root=None):
+            n = 1 << log_n
+            xs = N.inputs(label, n, 300 + log_n)
+            x = _upload(curve, xs)
+            before = _ntt_built(curve)
+            y = par.ntt(x, log_n, inverse=inverse, root=root)
+            assert _ntt_built(curve) - before == builds, (what, log_n, "built")
+            want = N.transform(q, xs, n, N.root(label, log_n), inverse)
+            assert _raw(curve, y, 0, n) == S.encode(want), (what, log_n)
+            x.free(); y.free()
+
+        assert _ntt_built(curve) == 0
+        for k in keys:
+            run(k, 1, "fill")
+        run(keys[0], 1, "the oldest has left")          # keys[1] leaves
+        run(keys[0], 0, "the most recent")
+        run(keys[-1], 0, "the one before it")
+        run(keys[1], 1, "first in, first out")          # keys[2] leaves
+        run(keys[-1], 1, "the inverse root is another key", inverse=True)   # keys[3] leaves
+        run(keys[-1], 0, "the inverse root, cached", inverse=True)
+        run(keys[-1], 0, "the default root, given", root=N.root(label, keys[-1]))
+        run(keys[0], 0, "still cached")
+        assert _ntt_built(curve) == sets + 4
 
 
 # ---------------------------------------------------------------------------------------------- ranges

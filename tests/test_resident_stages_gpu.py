@@ -9,7 +9,8 @@ The list: a point check with verdicts whose tail forces h_res_ to grow, a plain 
 growth), a lookup with positions, an inner product, a recurrence with its last value, a transform of two passes forward
 and back followed by a second recurrence (a transform reports through the error word of the meta block: it no longer
 touches the recurrence's record), a fixed-base multiplication whose base is a resident record (fetched through the core,
-as a download is), and a sparse matrix-vector product.
+as a download is), and a sparse matrix-vector product; then the two calls that came after the list was first written and
+share sdot_ and the landing with the calls above: a gate expression with rotated columns and a sumcheck step in place.
 
 The scalar field of ed-on-bls12-377 has two-adicity 1 (tests/test_ntt_gpu.py): no transform of more than two entries
 exists there, so on that curve the transform of the list is the one of length 2, a single pass."""
@@ -19,6 +20,7 @@ import random
 import pytest
 
 import check_points_util as U
+import expr_util as EX
 import fixed_base_util as FB
 import lookup_util as LK
 import matrix_util as MX
@@ -26,6 +28,7 @@ import ntt_util as NT
 import points_mul_util as M
 import scalar_ops_util as S
 import scalar_scan_util as SC
+import sumcheck_step_util as SS
 from oracle import c_oracle, prng
 from oracle import params as P
 from test_scratch_poison_gpu import _lib, _pt, _raw_points, _raw_scalars, _strip, _upload, fresh, scratch
@@ -39,6 +42,7 @@ SEED_P, SEED_S = 11, 12
 # is 16 bytes and one verdict byte per point follows it: 2^16 + 3 points need 65555, so the landing has to grow.
 N_CHECK = (1 << 16) + 3
 N_MSM, N_COL, N_TABLE, N_VEC, N_FIXED, BASE_INDEX, N_MAT, NNZ = 1 << 10, 3000, 257, 3000, 65, 5, 64, 300
+STEP_VARS = 11   # the sumcheck step: tables of 2^11 entries, the first entries of the two vectors
 
 
 def _h_res_initial(params):
@@ -100,6 +104,14 @@ class Data:
         self.vals = MX.values_for(NNZ, q, rng)
         self.mx = MX.x_for(N_MAT, q, rng)
         self.matvec = S.encode(MX.matvec(self.rows, self.cols, self.vals, self.mx, N_MAT, q))
+        # ---- the gate expression: one wire of a permutation step over the two vectors, Z rotated by one row
+        self.expr_terms = EX.permutation_wire(rng.randrange(q), rng.randrange(q), q, z=0, w=1, sigma=1, ident=0)
+        self.expr = S.encode(EX.model([self.xs, self.ys], self.expr_terms, N_VEC, q))
+        # ---- the sumcheck step: both tables bound in place, the next round over the bound tables
+        self.step_terms = SS.mixed_terms(2, q, rng)
+        self.step_r = rng.randrange(q)
+        assert N_VEC >= 1 << STEP_VARS
+        self.step = SS.step([self.xs[:1 << STEP_VARS], self.ys[:1 << STEP_VARS]], self.step_terms, self.step_r, q)
 
     def transform(self, L):
         if self.log_n is None:
@@ -209,7 +221,25 @@ def _matvec(c):
     m.free()
 
 
-STEPS = [_check, _msm, _lookup, _dot, _recurrence, _transform, _fixed_base, _matvec]
+def _expr(c):
+    out = c.par.evaluateExpression([c.x, c.y], c.d.expr_terms, N_VEC)
+    assert _raw_scalars(c.curve, out) == c.d.expr
+    out.free()
+
+
+def _sumcheck_step(c):
+    d = c.d
+    n = 1 << STEP_VARS
+    f, g = _upload(c.curve, d.xs[:n]), _upload(c.curve, d.ys[:n])   # (copies: the step binds its tables in place)
+    bound, want_degree, want_values = d.step
+    degree, values = c.par.sumcheckStep([f, g], d.step_terms, STEP_VARS, d.step_r)
+    assert (degree, values) == (want_degree, want_values)
+    for arr, b, src in ((f, bound[0], d.xs), (g, bound[1], d.ys)):
+        assert _raw_scalars(c.curve, arr) == S.encode(b + src[n // 2:n])   # the low half bound, the high half as it was
+        arr.free()
+
+
+STEPS = [_check, _msm, _lookup, _dot, _recurrence, _transform, _fixed_base, _matvec, _expr, _sumcheck_step]
 
 
 @pytest.mark.parametrize("label", LABELS)
