@@ -880,6 +880,40 @@ typedef struct msmz_expr {
 } msmz_expr;                        /* 40 bytes */
 int msmz_scalars_expr(msmz_ctx* ctx, const msmz_expr* e, uint64_t first_out, uint64_t* out_handle);
 
+/* msmz_scalars_dot_many: every inner product of n_rows row vectors with n_cols column vectors in
+ * one call -- the product of a dense n_rows x n matrix with a dense n x n_cols matrix mod q, n large, both counts small:
+ * many committed polynomials at a few challenge points (columns = power vectors), many multilinear tables at one point
+ * (one column = the eq table), Hyrax's L M, the cross terms of a folding scheme.  A vector is entries
+ * [first, first + n) of the scalar set `handle`.
+ *     result[r * n_cols + c] = sum_(i < n) rows[r][i] * cols[c][i] mod q,  canonical
+ * Each value is byte for byte what msmz_scalars_dot(rows[r], cols[c], n) returns; the sums are exact, so two calls give
+ * the same bytes.  Vectors may share handles, overlap and be one range (rows[r] == cols[c]: a sum of squares).  A column
+ * value is read once per block of rows, not once per row, and the whole call has ONE host wait.
+ *
+ * Destinations, at least one of them: out_le32 (nullable) receives n_rows * n_cols * 32 bytes, row-major; out_handle
+ * (nullable) as everywhere: *out_handle == 0 makes a new scalar set of n_rows * n_cols entries (first_out must be 0),
+ * otherwise entries [first_out, first_out + n_rows * n_cols) of that set are written and no other.  A destination range
+ * that meets any input range of the same handle is refused, whatever the order of the writes would be.  With
+ * out_handle == NULL first_out must be 0.
+ *
+ * MSMZ_ERR_ARG, before any launch: a null ctx, descriptor, rows or cols; both destinations null; n_rows or n_cols
+ * outside their limits; n == 0 or >= 2^32; unknown flag bits; first_out != 0 without an existing destination set; an
+ * unknown handle or one that is not a scalar set; a range beyond its set; the overlap above.  MSMZ_ERR_RANGE: a resident
+ * entry >= q inside an addressed range, found by the kernel: then no handle is made, *out_handle and out_le32 are as
+ * they were, a destination range of an existing set is unspecified and the context stays usable.
+ * MSMZ_ERR_UNSUPPORTED: a multi-device context.  A sum of one vector alone stays msmz_scalars_dot with y_handle == 0. */
+enum { MSMZ_DOT_MANY_MAX_ROWS = 128, MSMZ_DOT_MANY_MAX_COLS = 8 };
+typedef struct msmz_scalar_vec { uint64_t handle, first; } msmz_scalar_vec;   /* 16 bytes */
+typedef struct msmz_dot_many {
+  const msmz_scalar_vec* rows;
+  uint32_t n_rows;              /* 1 .. MSMZ_DOT_MANY_MAX_ROWS */
+  const msmz_scalar_vec* cols;
+  uint32_t n_cols;              /* 1 .. MSMZ_DOT_MANY_MAX_COLS */
+  uint64_t n;                   /* entries of every vector, 1 .. 2^32 - 1 */
+  uint32_t flags;               /* must be 0 */
+} msmz_dot_many;                /* 48 bytes */
+int msmz_scalars_dot_many(msmz_ctx* ctx, const msmz_dot_many* d, uint8_t* out_le32, uint64_t first_out, uint64_t* out_handle);
+
 /* Host-side group addition of two canonical affine results: combines per-GPU partial sums
  * (the reference's "partition sum" step, msm-batched-affine.ts:300-307). */
 int msmz_point_add(int curve_id, const uint8_t* a_xy_le, int a_is_inf, const uint8_t* b_xy_le, int b_is_inf,

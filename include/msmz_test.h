@@ -137,6 +137,16 @@ void msmz_test_mle_geometry(uint32_t* run, uint32_t* eval_tile, uint32_t* round_
  *   step_tile: NEW pair indices (those of the bound tables, 2^(n_vars-2) of them) one workgroup binds and sums into one
  *              partial sum per value -- the round's tile, over them. */
 void msmz_test_sumcheck_step_geometry(uint32_t* step_tile);
+/* msmz_scalars_dot_many (csrc/dot_kernels.h).
+ *   msmz_test_dot_many_geometry (every pointer nullable; needs no context): tile_elements = the element indices of one
+ *     tile (that of msmz_scalars_dot); max_groups = the most workgroups along n a call launches, each striding over the
+ *     tiles (DOT_MANY_GROUPS); rows_per_block[c - 1], c = 1 .. MSMZ_DOT_MANY_MAX_COLS (8 words) = the rows of a thread's
+ *     register block for c columns (dot_many_rg).
+ *   msmz_test_set_dot_many_groups: lowers max_groups for later calls on this context (1 .. the built-in value; 0 = the
+ *     built-in value again), so that a vector of a few tiles makes every workgroup stride more than once.  Changes no
+ *     result.  MSMZ_ERR_ARG: a null context, a larger value; MSMZ_ERR_UNSUPPORTED: a multi-device context. */
+void msmz_test_dot_many_geometry(uint32_t* tile_elements, uint32_t* max_groups, uint32_t* rows_per_block);
+int msmz_test_set_dot_many_groups(msmz_ctx* ctx, uint32_t max_groups);
 /* The geometry of msmz_matrix_mul (csrc/matrix_kernels.h), for the same purpose (every pointer nullable; needs no
  * context):
  *   tile            : consecutive non-zeros one workgroup takes and leaves one carry for (MAT_TILE);

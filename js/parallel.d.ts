@@ -31,6 +31,10 @@ export interface SumcheckStepOptions { nVars?: number | null; out?: (DeviceArray
 export function sumcheckStepArgs(tables: (ScalarsLike | [ScalarsLike, number])[], terms: SumcheckTerm[], r: bigint,
   options: { nVars?: number | null; out?: (ScalarsLike | [ScalarsLike, number])[] | null; low?: boolean } | undefined, order: bigint):
   { tables: [ScalarsLike, number][]; out: [ScalarsLike, number][] | null; nVars: number; terms: SumcheckTerm[]; flags: number; degree: number };
+/** the checked arguments of Parallel.innerProducts (host only), in the order of msmz_scalars_dot_many */
+export function dotManyArgs(rows: (ScalarsLike | [ScalarsLike, number])[], cols: (ScalarsLike | [ScalarsLike, number])[], n?: number | null,
+  options?: { out?: ScalarsLike | null; firstOut?: number }, who?: string):
+  { rows: [ScalarsLike, number][]; cols: [ScalarsLike, number][]; n: number; firstOut: number };
 /** a resident sparse matrix (msmz_matrix_create) */
 export interface SparseMatrix { readonly shape: [number, number]; readonly nnz: number; readonly orientations: "rows" | "cols" | "both"; readonly kind: "matrix"; free(): void }
 export interface SparseMatrixOptions { shape: [number, number]; orientations?: "rows" | "cols" | "both"; firstValue?: number }
@@ -115,6 +119,13 @@ export interface ParallelApi {
   innerProduct(x: DeviceArray, y?: DeviceArray | null, n?: number, options?: { firstX?: number; firstY?: number }): Promise<bigint>;
   /** a new scalar array: entry i = base ratio^i mod the group order */
   scalarPowers(ratio: bigint, n: number, base?: bigint): Promise<DeviceArray>;
+  /** every inner product of 1 to 128 row vectors with 1 to 8 column vectors in one call (msmz_scalars_dot_many):
+   * result[r][c] = sum_i rows[r][i] cols[c][i]; with `out` the values go row-major into out[firstOut ..] and `out` comes back */
+  innerProducts(rows: (DeviceArray | [DeviceArray, number])[], cols: (DeviceArray | [DeviceArray, number])[], n?: number | null): Promise<bigint[][]>;
+  innerProducts(rows: (DeviceArray | [DeviceArray, number])[], cols: (DeviceArray | [DeviceArray, number])[], n: number | null,
+    options: { out: DeviceArray; firstOut?: number }): Promise<DeviceArray>;
+  /** result[r][c] = p_r(z_c) for coefficient vectors polys[r] and 1 to 8 points: one scalarPowers per point, one innerProducts call */
+  evaluatePolynomials(polys: (DeviceArray | [DeviceArray, number])[], points: bigint[], n?: number | null): Promise<bigint[][]>;
   /** y_i = a_i y_(i-1) + b_i mod the group order from y_(-1) = init (reverse: y_i = a_i y_(i+1) + b_i from y_n = init);
    * a: a resident scalar array, one bigint for every entry or null (1); b: a resident scalar array or null; entry i of the
    * result is y_i, with `exclusive` the value before the step at i -> [the array written, the final y] */

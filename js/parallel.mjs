@@ -268,6 +268,43 @@ export function sumcheckStepArgs(tables, terms, r, { nVars = null, out = null, l
   return { ...t, out: out === null ? null : outs, degree: t.nVars > 1 ? t.degree : 0 };
 }
 
+/** The arguments of Parallel.innerProducts -> {rows, cols ([[array, first]]), n, firstOut}, checked before anything reaches
+ * the device, in the order of msmz_scalars_dot_many (include/msmz.h): the types, the two counts, n, firstOut without an
+ * array, every range inside its array, and a destination range that meets no input range
+ * (msm_zprize_amd/parallel.py inner_products_args is the same function). */
+export const DOT_MANY_MAX_ROWS = 128, DOT_MANY_MAX_COLS = 8;
+export function dotManyArgs(rows, cols, n = null, { out = null, firstOut = 0 } = {}, who = "innerProducts") {
+  const vectors = (vs, name) => {
+    if (!Array.isArray(vs)) throw TypeError(`${who}: \`${name}\` is an array of resident scalar arrays or [array, first] pairs`);
+    return vs.map((v) => {
+      const [arr, first] = Array.isArray(v) && v.length === 2 ? v : [v, 0];
+      if (!looksLikeScalars(arr) || !Number.isInteger(first))
+        throw TypeError(`${who}: a vector of \`${name}\` is a resident scalar array or an [array, first] pair`);
+      return [arr, first];
+    });
+  };
+  const rv = vectors(rows, "rows"), cv = vectors(cols, "cols");
+  if (out !== null && !looksLikeScalars(out)) throw TypeError(`${who}: \`out\` is a resident scalar array or null`);
+  if (n !== null && !Number.isInteger(n)) throw TypeError(`${who}: \`n\` is an integer or null`);
+  if (!Number.isInteger(firstOut)) throw TypeError(`${who}: \`firstOut\` is an integer`);
+  if (rv.length < 1 || rv.length > DOT_MANY_MAX_ROWS) throw Error(`${who}: ${rv.length} rows (1 to ${DOT_MANY_MAX_ROWS})`);
+  if (cv.length < 1 || cv.length > DOT_MANY_MAX_COLS) throw Error(`${who}: ${cv.length} columns (1 to ${DOT_MANY_MAX_COLS})`);
+  const all = [...rv, ...cv];
+  for (const [arr, first] of all) if (first < 0 || first > arr.n) throw Error(`${who}: first = ${first} of an array of ${arr.n}`);
+  if (n === null) n = Math.min(...all.map(([arr, first]) => arr.n - first));
+  if (n < 1 || n >= 2 ** 32) throw Error(`${who}: n = ${n}`);
+  if (firstOut < 0 || (out === null && firstOut !== 0)) throw Error(`${who}: firstOut = ${firstOut}${out === null ? " without the array it indexes" : ""}`);
+  for (const [arr, first] of all) if (n > arr.n - first) throw Error(`${who}: entries [${first}, +${n}) of an array of ${arr.n}`);
+  if (out !== null) {
+    const results = rv.length * cv.length;
+    if (firstOut > out.n || results > out.n - firstOut) throw Error(`${who}: entries [${firstOut}, +${results}) of an array of ${out.n}`);
+    for (const [arr, first] of all)
+      if (arr.handle === out.handle && first < firstOut + results && firstOut < first + n)
+        throw Error(`${who}: the destination [${firstOut}, +${results}) meets the input range [${first}, +${n}) of the same array`);
+  }
+  return { rows: rv, cols: cv, n, firstOut };
+}
+
 /** The arguments of Parallel.sparseMatrix -> {rows, cols (Buffers of little-endian u32), nnz, shape, flags, firstValue} and
  * of Parallel.matVec -> {n, flags}, checked before anything reaches the device (msm_zprize_amd/parallel.py
  * sparse_matrix_args and mat_vec_args are the same functions).  `values` here is a resident scalar array or null: a host
@@ -756,6 +793,50 @@ function createCurve(params, kind) {
       n = scanRanges("innerProduct", [["firstX", firstX, x], ["firstY", firstY, y]], n);
       const r = N.scalarsDot(ctx, x.handle, firstX, y === null ? 0 : y.handle, firstY, n);
       return bytesToBigint(r, 0, 32);
+    },
+    /** every inner product of a family of row vectors with a family of column vectors in one call
+     * (msmz_scalars_dot_many): result[r][c] = sum_i rows[r][i] cols[c][i] mod the group order, i < n, each what
+     * innerProduct gives for that pair.  rows (1 to 128) and cols (1 to 8): resident scalar arrays or [array, first]
+     * pairs; they may share arrays, overlap and be one range.  n null: what the shortest vector leaves.  Without `out`:
+     * an array of rows.length arrays of bigints.  With `out`, a resident scalar array, entries [firstOut, firstOut +
+     * rows.length cols.length) of it receive the values row-major (the range meets no input range) and `out` comes
+     * back.  Many multilinear tables at one point: eqTable(point), then innerProducts(tables, [eq]). */
+    async innerProducts(rows, cols, n = null, options = {}) {
+      const t = dotManyArgs(rows, cols, n, options);
+      for (const [arr] of [...t.rows, ...t.cols]) if (!isScalars(arr)) throw TypeError("innerProducts: a vector is a resident scalar array");
+      const pack = (pairs) => {
+        const b = Buffer.alloc(16 * pairs.length);
+        pairs.forEach(([arr, first], j) => {
+          b.writeBigUInt64LE(BigInt(arr.handle), 16 * j);
+          b.writeBigUInt64LE(BigInt(first), 16 * j + 8);
+        });
+        return b;
+      };
+      const out = options.out === undefined ? null : options.out, nr = t.rows.length, nc = t.cols.length;
+      if (out !== null) {
+        if (!isScalars(out)) throw TypeError("innerProducts: `out` is a resident scalar array");
+        N.scalarsDotMany(ctx, pack(t.rows), nr, pack(t.cols), nc, t.n, 1, out.handle, t.firstOut);
+        return out;
+      }
+      const r = N.scalarsDotMany(ctx, pack(t.rows), nr, pack(t.cols), nc, t.n, 0, 0, 0);
+      return Array.from({ length: nr }, (_, j) => Array.from({ length: nc }, (_, c) => bytesToBigint(r, 32 * (j * nc + c), 32)));
+    },
+    /** result[r][c] = p_r(z_c) for polynomials in coefficient form: polys[r] a resident scalar array or [array, first]
+     * pair whose entry i is the coefficient of X^i, i < n; points: 1 to 8 bigints below the group order.  One power
+     * vector per point (scalarPowers), ONE innerProducts call, and the vectors are freed again.  In evaluation form the
+     * same call serves: pass the barycentric weight vectors of the points as `cols` of innerProducts. */
+    async evaluatePolynomials(polys, points, n = null) {
+      const t = dotManyArgs(polys, Array.isArray(polys) ? polys.slice(0, 1) : polys, n, {}, "evaluatePolynomials");
+      if (!Array.isArray(points) || !points.every((z) => typeof z === "bigint")) throw TypeError("evaluatePolynomials: `points` is an array of bigints");
+      if (points.length < 1 || points.length > DOT_MANY_MAX_COLS) throw Error(`evaluatePolynomials: ${points.length} points (1 to ${DOT_MANY_MAX_COLS})`);
+      for (const z of points) if (z < 0n || z >= params.order) throw Error(`evaluatePolynomials: the point ${z} is not in [0, group order)`);
+      const powers = [];
+      try {
+        for (const z of points) powers.push(await Parallel.scalarPowers(z, t.n));
+        return await Parallel.innerProducts(t.rows, powers, t.n);
+      } finally {
+        for (const a of powers) a.free();
+      }
     },
     /** a new resident scalar array: entry i = base ratio^i mod the group order (msmz_scalars_powers; 0^0 = 1) */
     async scalarPowers(ratio, n, base = 1n) {

@@ -163,6 +163,20 @@ class MsmzExpr(C.Structure):   # msmz_expr (include/msmz.h): a sum of products o
 
 assert (C.sizeof(MsmzExprColumn), C.sizeof(MsmzExprFactor), C.sizeof(MsmzExprTerm), C.sizeof(MsmzExpr)) == (16, 8, 24, 40)
 
+MSMZ_DOT_MANY_MAX_ROWS, MSMZ_DOT_MANY_MAX_COLS = 128, 8
+
+
+class MsmzScalarVec(C.Structure):   # msmz_scalar_vec: one vector of msmz_dot_many, entries [first, first + n) of `handle`
+    _fields_ = [("handle", C.c_uint64), ("first", C.c_uint64)]
+
+
+class MsmzDotMany(C.Structure):   # msmz_dot_many (include/msmz.h): every inner product of rows x cols
+    _fields_ = [("rows", C.POINTER(MsmzScalarVec)), ("n_rows", C.c_uint32), ("cols", C.POINTER(MsmzScalarVec)),
+                ("n_cols", C.c_uint32), ("n", C.c_uint64), ("flags", C.c_uint32)]
+
+
+assert (C.sizeof(MsmzScalarVec), C.sizeof(MsmzDotMany)) == (16, 48)
+
 
 class MsmzSegment(C.Structure):   # msmz_segment (include/msmz.h): one problem of msmz_msm_segments
     _fields_ = [("first_p", C.c_uint64), ("first_s", C.c_uint64), ("n", C.c_uint64)]
@@ -260,6 +274,7 @@ EXPORTS = {
     "msmz_scalars_mle_bind": (C.c_int, [C.c_void_p, C.POINTER(MsmzMleBind), C.c_uint64, C.POINTER(C.c_uint64)]),
     "msmz_scalars_sumcheck_round": (C.c_int, [C.c_void_p, C.POINTER(MsmzSumcheck), C.POINTER(C.c_uint32), C.c_char_p]),
     "msmz_scalars_sumcheck_step": (C.c_int, [C.c_void_p, C.POINTER(MsmzSumcheckStep), C.POINTER(C.c_uint32), C.c_char_p]),
+    "msmz_scalars_dot_many": (C.c_int, [C.c_void_p, C.POINTER(MsmzDotMany), C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "msmz_matrix_create": (C.c_int, [C.c_void_p, C.POINTER(MsmzSparse), C.POINTER(C.c_uint64)]),
     "msmz_matrix_info": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                    C.POINTER(C.c_uint32)]),
@@ -286,6 +301,8 @@ EXPORTS = {
     "msmz_test_lookup_small_table": (C.c_uint32, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "msmz_test_mle_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "msmz_test_sumcheck_step_geometry": (None, [C.POINTER(C.c_uint32)]),
+    "msmz_test_dot_many_geometry": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "msmz_test_set_dot_many_groups": (C.c_int, [C.c_void_p, C.c_uint32]),
     "msmz_test_fixed_base_plan": (C.c_int, [C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                             C.POINTER(C.c_uint64)]),
     "msmz_test_set_fixed_base_window": (C.c_int, [C.c_void_p, C.c_int]),

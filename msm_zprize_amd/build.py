@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libmsmz.so")
 SOURCES = ["msmz.hip", "kern_batch.hip", "kern_reduce.hip", "kern_misc.hip", "kern_gen.hip", "kern_mle.hip", "kern_matrix.hip",
-           "kern_lookup.hip", "kern_expr.hip"]
+           "kern_lookup.hip", "kern_expr.hip", "kern_dot.hip"]
 # (source, curve id) translation units; curve 3 (twisted Edwards) has no batched-affine kernels
 UNITS = [("msmz.hip", None)] + [(f, c) for c in (0, 1, 2, 3) for f in SOURCES[1:] if not (f == "kern_batch.hip" and c == 3)]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))   # every header: a change to any of them rebuilds

@@ -144,6 +144,9 @@ class IEngine {
   // msmz_scalars_expr: a sum of products of rotated columns, entry by entry (expr_kernels.h).  The default: a context
   // that has none.
   virtual int scalars_expr(const msmz_expr&, uint64_t, uint64_t*) { return MSMZ_ERR_UNSUPPORTED; }
+  // msmz_scalars_dot_many: every inner product of a family of row vectors with a family of column vectors
+  // (dot_kernels.h).  The default: a context that has none -- a multi-device one.
+  virtual int scalars_dot_many(const msmz_dot_many&, uint8_t*, uint64_t, uint64_t*) { return MSMZ_ERR_UNSUPPORTED; }
   // tests (include/msmz_test.h); the stage-level hooks are one engine's (a multi-device context: its first engine's)
   virtual int test_set_glv_bits(int) { return MSMZ_ERR_UNSUPPORTED; }
   virtual int test_retries() { return 0; }
@@ -155,6 +158,8 @@ class IEngine {
   // msmz_test_set_fixed_base_window / msmz_test_fixed_base_tables: the forced window width, the tables built so far
   virtual int test_set_fixed_base_window(int) { return MSMZ_ERR_UNSUPPORTED; }
   virtual uint64_t test_fixed_base_tables() { return 0; }
+  // msmz_test_set_dot_many_groups: the most workgroups along n of msmz_scalars_dot_many (0 = the built-in value)
+  virtual int test_set_dot_many_groups(uint32_t) { return MSMZ_ERR_UNSUPPORTED; }
   // msmz_test_ntt_tables: the twiddle sets built so far
   virtual uint64_t test_ntt_tables() { return 0; }
   // msmz_test_poison: fill every scratch buffer with `pattern` and arm the allocations to come (-1: disarm)

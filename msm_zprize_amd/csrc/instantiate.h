@@ -3,6 +3,7 @@
 // `extern template` declarations.
 #pragma once
 #include "check_kernels.h"
+#include "dot_kernels.h"
 #include "export_kernels.h"
 #include "expr_kernels.h"
 #include "fixed_kernels.h"
@@ -164,6 +165,14 @@
 #define MSMZ_INST_EXPR(F, Fr, PFX)                                                                                \
   PFX template __global__ void k_scalars_expr<Fr>(uint32_t*, ExprProgram, uint32_t*);                             \
   PFX template __global__ void k_scalars_expr_slots<Fr, EXPR_REGISTER_SLOTS>(uint32_t*, ExprProgram, uint32_t*);
+
+// the batched inner products (dot_kernels.h), a translation unit of their own (kern_dot.hip); NC = the columns
+#define MSMZ_INST_DOT_MANY(Fr, NC, PFX)                                                                           \
+  PFX template __global__ void k_scalars_dot_many<Fr, NC>(uint32_t*, DotManyVecs, uint32_t, uint32_t, uint32_t, uint32_t*);
+#define MSMZ_INST_DOT(F, Fr, PFX)                                                                                 \
+  MSMZ_INST_DOT_MANY(Fr, 1, PFX) MSMZ_INST_DOT_MANY(Fr, 2, PFX) MSMZ_INST_DOT_MANY(Fr, 3, PFX)                    \
+  MSMZ_INST_DOT_MANY(Fr, 4, PFX) MSMZ_INST_DOT_MANY(Fr, 5, PFX) MSMZ_INST_DOT_MANY(Fr, 6, PFX)                    \
+  MSMZ_INST_DOT_MANY(Fr, 7, PFX) MSMZ_INST_DOT_MANY(Fr, 8, PFX)
 
 // every curve, by policy P = WeierPolicy<F> / TePolicy<F>
 #define MSMZ_INST_MISC_P(F, Fr, P, PFX)                                                                           \

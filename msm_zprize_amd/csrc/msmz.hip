@@ -1,10 +1,10 @@
 // C ABI of the MSM engine (include/msmz.h): curve dispatch + argument checking.
 #include "instantiate.h"
 namespace msmz {
-#define X(F, Fr) MSMZ_INST_BATCH(F, Fr, MSMZ_EXTERN) MSMZ_INST_REDUCE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MISC(F, Fr, MSMZ_EXTERN) MSMZ_INST_GEN(F, Fr, MSMZ_EXTERN) MSMZ_INST_MLE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MATRIX(F, Fr, MSMZ_EXTERN) MSMZ_INST_LOOKUP(F, Fr, MSMZ_EXTERN) MSMZ_INST_EXPR(F, Fr, MSMZ_EXTERN)
+#define X(F, Fr) MSMZ_INST_BATCH(F, Fr, MSMZ_EXTERN) MSMZ_INST_REDUCE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MISC(F, Fr, MSMZ_EXTERN) MSMZ_INST_GEN(F, Fr, MSMZ_EXTERN) MSMZ_INST_MLE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MATRIX(F, Fr, MSMZ_EXTERN) MSMZ_INST_LOOKUP(F, Fr, MSMZ_EXTERN) MSMZ_INST_EXPR(F, Fr, MSMZ_EXTERN) MSMZ_INST_DOT(F, Fr, MSMZ_EXTERN)
 MSMZ_WEIERSTRASS_FIELDS(X)
 #undef X
-#define X(F, Fr) MSMZ_INST_REDUCE_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MISC_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_GEN_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MLE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MATRIX(F, Fr, MSMZ_EXTERN) MSMZ_INST_LOOKUP(F, Fr, MSMZ_EXTERN) MSMZ_INST_EXPR(F, Fr, MSMZ_EXTERN)
+#define X(F, Fr) MSMZ_INST_REDUCE_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MISC_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_GEN_TE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MLE(F, Fr, MSMZ_EXTERN) MSMZ_INST_MATRIX(F, Fr, MSMZ_EXTERN) MSMZ_INST_LOOKUP(F, Fr, MSMZ_EXTERN) MSMZ_INST_EXPR(F, Fr, MSMZ_EXTERN) MSMZ_INST_DOT(F, Fr, MSMZ_EXTERN)
 MSMZ_TE_FIELDS(X)
 #undef X
 }  // namespace msmz
@@ -290,6 +290,18 @@ int msmz_scalars_lookup(msmz_ctx* c, const msmz_lookup* l, uint64_t first_out, u
 }
 int msmz_scalars_expr(msmz_ctx* c, const msmz_expr* e, uint64_t first_out, uint64_t* out_handle) {
   return c && e && out_handle ? c->engine->scalars_expr(*e, first_out, out_handle) : MSMZ_ERR_ARG;
+}
+int msmz_scalars_dot_many(msmz_ctx* c, const msmz_dot_many* d, uint8_t* out_le32, uint64_t first_out, uint64_t* out_handle) {
+  return c && d ? c->engine->scalars_dot_many(*d, out_le32, first_out, out_handle) : MSMZ_ERR_ARG;
+}
+void msmz_test_dot_many_geometry(uint32_t* tile_elements, uint32_t* max_groups, uint32_t* rows_per_block) {
+  if (tile_elements) *tile_elements = SDOT_TILE;
+  if (max_groups) *max_groups = DOT_MANY_GROUPS;
+  if (rows_per_block)
+    for (int nc = 1; nc <= DOT_MANY_MAX_COLS; nc++) rows_per_block[nc - 1] = (uint32_t)dot_many_rg(nc);
+}
+int msmz_test_set_dot_many_groups(msmz_ctx* c, uint32_t max_groups) {
+  return c ? c->engine->test_set_dot_many_groups(max_groups) : MSMZ_ERR_ARG;
 }
 void msmz_test_expr_geometry(uint32_t* threads_per_workgroup, uint32_t* register_slots) {
   if (threads_per_workgroup) *threads_per_workgroup = EXPR_THREADS;

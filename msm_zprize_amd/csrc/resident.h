@@ -332,6 +332,10 @@ class ResidentSets : public SetsCore<Cfg> {
   int scalars_sumcheck_step(const msmz_sumcheck_step& s, uint32_t* degree, uint8_t* evals) override {
     return scalar_ops_.scalars_sumcheck_step(s, degree, evals);
   }
+  int scalars_dot_many(const msmz_dot_many& d, uint8_t* out_le32, uint64_t first_out, uint64_t* out) override {
+    return scalar_ops_.scalars_dot_many(d, out_le32, first_out, out);
+  }
+  int test_set_dot_many_groups(uint32_t g) override { return scalar_ops_.test_set_dot_many_groups(g); }
   int scalars_ntt(const msmz_ntt& t, uint64_t first_out, uint64_t* out) override { return ntt_ops_.scalars_ntt(t, first_out, out); }
   int matrix_create(const msmz_sparse& s, uint64_t* h) override { return matrix_ops_.matrix_create(s, h); }
   int matrix_info(uint64_t h, uint32_t* n_rows, uint32_t* n_cols, uint64_t* nnz, uint32_t* flags) override {

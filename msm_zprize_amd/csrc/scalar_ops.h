@@ -10,6 +10,7 @@
 
 #include "../../include/msmz.h"
 #include "scalar_kernels.h"
+#include "dot_kernels.h"
 #include "mle_kernels.h"
 #include "sets_core.h"
 
@@ -79,6 +80,78 @@ class ScalarOps {
     });
     if (st) return st;
     memcpy(out, core_.h_res_.p, 32);
+    return MSMZ_OK;
+  }
+
+  // msmz_scalars_dot_many: every inner product of d.n_rows row vectors with d.n_cols column vectors.  ONE launch of
+  // k_scalars_dot_many (dot_kernels.h; the grid of dot_many_plan) leaves `groups` partial sums per result, ONE launch
+  // of k_scalars_dot_fold, one workgroup per result, folds them and converts; a resident destination gets a copy on
+  // the stream.  The record is that of scalars_dot (word 8: the error word) with the results as its tail, so they and
+  // the error word come back in ONE copy behind ONE host wait.  Every check comes before anything is queued.
+  int scalars_dot_many(const msmz_dot_many& d, uint8_t* out_le32, uint64_t first_out, uint64_t* out_handle) {
+    HandleTable& handles = core_.handles_;
+    if (!d.rows || !d.cols || (!out_le32 && !out_handle)) return MSMZ_ERR_ARG;
+    if (d.n_rows < 1 || d.n_rows > (uint32_t)DOT_MANY_MAX_ROWS || d.n_cols < 1 || d.n_cols > (uint32_t)DOT_MANY_MAX_COLS ||
+        d.n == 0 || d.n >> 32 || d.flags)
+      return MSMZ_ERR_ARG;
+    const uint64_t dest = out_handle ? *out_handle : 0, results = (uint64_t)d.n_rows * d.n_cols;
+    if (!dest && first_out != 0) return MSMZ_ERR_ARG;
+    DotManyVecs V{};
+    for (uint32_t r = 0; r < d.n_rows; r++)
+      if (!(V.row[r] = handles.range(d.rows[r].handle, 1, d.rows[r].first, d.n, 8))) return MSMZ_ERR_ARG;
+    for (uint32_t c = 0; c < d.n_cols; c++)
+      if (!(V.col[c] = handles.range(d.cols[c].handle, 1, d.cols[c].first, d.n, 8))) return MSMZ_ERR_ARG;
+    uint32_t* out = nullptr;
+    if (dest) {
+      if (!(out = handles.range(dest, 1, first_out, results, 8))) return MSMZ_ERR_ARG;
+      for (uint32_t k = 0; k < d.n_rows + d.n_cols; k++) {   // no entry is both read and written, whatever the order
+        const msmz_scalar_vec& v = k < d.n_rows ? d.rows[k] : d.cols[k - d.n_rows];
+        if (v.handle == dest && ranges_meet(v.first, d.n, first_out, results)) return MSMZ_ERR_ARG;
+      }
+    }
+    const DotManyPlan p = dot_many_plan(d.n, d.n_rows, d.n_cols, dot_many_groups_);
+    MSMZ_HIP(hipSetDevice(core_.device_));
+    Handle hd;
+    if (out_handle)
+      if (int st = core_.fresh_out(results, &hd, &out)) return st;
+    hipStream_t stream = core_.stream_;
+    typename Core::Record rec;
+    rec.tail = (size_t)results * 32;
+    // words 0..7: unused, word 8: the error word, from word 16: the results, behind them the partial sums
+    const int st = core_.recorded(sdot_, (size_t)p.scratch_bytes, [&](uint32_t* d_res) {
+      uint32_t* d_results = d_res + DOT_MANY_HEAD_BYTES / 4;
+      uint32_t* partial = d_results + results * 8;
+      const dim3 grid(p.groups, p.row_groups);
+#define MSMZ_DOT_LAUNCH(NC)                                                                                            \
+  case NC:                                                                                                             \
+    hipLaunchKernelGGL((k_scalars_dot_many<Fr, NC>), grid, dim3(SDOT_THREADS), 0, stream, partial, V, d.n_rows,        \
+                       (uint32_t)d.n, p.tiles, d_res + 8);                                                             \
+    break
+      switch (p.nc) {
+        MSMZ_DOT_LAUNCH(1);
+        MSMZ_DOT_LAUNCH(2);
+        MSMZ_DOT_LAUNCH(3);
+        MSMZ_DOT_LAUNCH(4);
+        MSMZ_DOT_LAUNCH(5);
+        MSMZ_DOT_LAUNCH(6);
+        MSMZ_DOT_LAUNCH(7);
+        MSMZ_DOT_LAUNCH(8);
+      }
+#undef MSMZ_DOT_LAUNCH
+      static_assert(DOT_MANY_MAX_COLS == 8, "one instance per column count");
+      hipLaunchKernelGGL((k_scalars_dot_fold<Fr>), dim3((uint32_t)results), dim3(SDOT_THREADS), 0, stream, d_results,
+                         (const uint32_t*)partial, p.groups, 1);
+      if (out) (void)hipMemcpyAsync(out, d_results, (size_t)results * 32, hipMemcpyDeviceToDevice, stream);
+    }, rec);
+    if (st) return st;
+    if (out_le32) memcpy(out_le32, (const uint8_t*)core_.h_res_.p + DOT_MANY_HEAD_BYTES, (size_t)results * 32);
+    return hd.mem.p ? core_.add_handle(std::move(hd), out_handle) : (int)MSMZ_OK;
+  }
+
+  // msmz_test_set_dot_many_groups: the most workgroups along n of scalars_dot_many, for later calls (0: the built-in value)
+  int test_set_dot_many_groups(uint32_t g) {
+    if (g > DOT_MANY_GROUPS) return MSMZ_ERR_ARG;
+    dot_many_groups_ = g ? g : DOT_MANY_GROUPS;
     return MSMZ_OK;
   }
 
@@ -415,8 +488,13 @@ class ScalarOps {
                     MSC_MAX_TERMS == MSMZ_SUMCHECK_MAX_TERMS,
                 "the limits of include/msmz.h are those of mle_kernels.h");
 
+  static_assert(MSMZ_DOT_MANY_MAX_ROWS == DOT_MANY_MAX_ROWS && MSMZ_DOT_MANY_MAX_COLS == DOT_MANY_MAX_COLS,
+                "the limits of include/msmz.h are those of dot_kernels.h");
+
   Core& core_;
-  DevBuf sdot_;    // scalars_dot and the multilinear four: the result record, then the partial sums per tile
+  uint32_t dot_many_groups_ = DOT_MANY_GROUPS;   // (msmz_test_set_dot_many_groups lowers it)
+  DevBuf sdot_;    // scalars_dot, scalars_dot_many (at most DOT_MANY_SCRATCH_MAX) and the multilinear calls: the result
+                   // record, then the partial sums
   DevBuf sscan_;   // scalars_recurrence / _inverse: the result record, then aggregates and incoming values
 };
 

@@ -407,6 +407,53 @@ class _Parallel:
                "msmz_scalars_dot")
         return int.from_bytes(buf.raw, "little")
 
+    def innerProducts(self, rows, cols, N=None, out=None, firstOut=0):
+        """Every inner product of a family of row vectors with a family of column vectors in one call
+        (msmz_scalars_dot_many): result[r][c] = sum_i rows[r][i] cols[c][i] mod the group order, i < N, each value what
+        innerProduct gives for that pair.  `rows` (1 to 128) and `cols` (1 to 8) are lists of resident scalar arrays or
+        (array, first) pairs; vectors may share arrays, overlap and be one range.  N=None: what the shortest vector
+        leaves.  out=None: a list of len(rows) lists of ints.  With `out`, a resident scalar array, entries
+        [firstOut, firstOut + len(rows) len(cols)) of it receive the values row-major (no other entry is written; the
+        range may meet no input range) and `out` comes back -- for combineScalars or evaluateExpression without a
+        crossing to the host.  Many multilinear tables at one point: eqTable(point), then innerProducts(tables, [eq])."""
+        t = inner_products_args(rows, cols, N, out, firstOut)
+        as_vecs = lambda pairs: (_native.MsmzScalarVec * len(pairs))(*[_native.MsmzScalarVec(a.handle, f) for a, f in pairs])
+        rv, cv = as_vecs(t["rows"]), as_vecs(t["cols"])
+        d = _native.MsmzDotMany(rv, len(t["rows"]), cv, len(t["cols"]), t["N"], 0)
+        if out is not None:
+            h = C.c_uint64(out.handle)
+            _check(lib().msmz_scalars_dot_many(self._c._ctx, C.byref(d), None, firstOut, C.byref(h)), "msmz_scalars_dot_many")
+            return out
+        nr, nc = len(t["rows"]), len(t["cols"])
+        buf = C.create_string_buffer(32 * nr * nc)
+        _check(lib().msmz_scalars_dot_many(self._c._ctx, C.byref(d), buf, 0, None), "msmz_scalars_dot_many")
+        raw = buf.raw
+        return [[int.from_bytes(raw[32 * (r * nc + c):32 * (r * nc + c) + 32], "little") for c in range(nc)] for r in range(nr)]
+
+    def evaluatePolynomials(self, polys, points, N=None):
+        """result[r][c] = p_r(z_c) for polynomials in coefficient form: polys[r] a resident scalar array or (array,
+        first) pair whose entry i is the coefficient of X^i, i < N, points[c] an int below the group order (1 to 8 of
+        them).  One power vector per point (scalarPowers), ONE innerProducts call, and the vectors are freed again.  In
+        evaluation form the same call serves: pass the barycentric weight vectors of the points as `cols` of
+        innerProducts."""
+        q = self._c.params["order"]
+        t = inner_products_args(polys, polys[:1] if isinstance(polys, (list, tuple)) else polys, N, None, 0, "evaluatePolynomials")
+        if not isinstance(points, (list, tuple)) or not all(_is_int(z) for z in points):
+            raise TypeError("evaluatePolynomials: `points` is a list of ints")
+        if not 1 <= len(points) <= _native.MSMZ_DOT_MANY_MAX_COLS:
+            raise ValueError(f"evaluatePolynomials: {len(points)} points (1 to {_native.MSMZ_DOT_MANY_MAX_COLS})")
+        for z in points:
+            if not 0 <= z < q:
+                raise ValueError(f"evaluatePolynomials: the point {z} is not in [0, group order)")
+        powers = []
+        try:
+            for z in points:
+                powers.append(self.scalarPowers(z, t["N"]))
+            return self.innerProducts(t["rows"], powers, t["N"])
+        finally:
+            for a in powers:
+                a.free()
+
     def scalarPowers(self, ratio, N, base=1):
         """A new resident scalar array: entry i = base ratio^i mod the group order (0^0 = 1)."""
         q = self._c.params["order"]
@@ -989,6 +1036,55 @@ def combine_scalars_args(a, x, b, y, N, firstX, firstY, out, firstOut, firstA, f
     if y is not None:
         terms.append((y, firstY) + (coeffs[1][0], firstB if coeffs[1][0] is not None else 0, coeffs[1][1]))
     return {"N": N, "firstOut": firstOut, "terms": terms}
+
+
+def inner_products_args(rows, cols, N, out, firstOut, who="innerProducts"):
+    """Arguments of innerProducts -> dict(rows, cols, N, firstOut), rows and cols as [(array, first)], checked before
+    anything reaches the device, in the order of msmz_scalars_dot_many (include/msmz.h): the types, the two counts, N,
+    firstOut without an array, every range inside its array, and a destination range that meets no input range."""
+    def vectors(vs, name):
+        if not isinstance(vs, (list, tuple)):
+            raise TypeError(f"{who}: `{name}` is a list of resident scalar arrays or (array, first) pairs")
+        pairs = []
+        for v in vs:
+            arr, first = v if isinstance(v, tuple) and len(v) == 2 else (v, 0)
+            if not _is_array(arr, "scalars") or not _is_int(first):
+                raise TypeError(f"{who}: a vector of `{name}` is a resident scalar array or an (array, first) pair")
+            pairs.append((arr, first))
+        return pairs
+
+    rv, cv = vectors(rows, "rows"), vectors(cols, "cols")
+    if out is not None and not _is_array(out, "scalars"):
+        raise TypeError(f"{who}: `out` is a resident scalar array or None")
+    if N is not None and not _is_int(N):
+        raise TypeError(f"{who}: `N` is an int or None")
+    if not _is_int(firstOut):
+        raise TypeError(f"{who}: `firstOut` is an int")
+    if not 1 <= len(rv) <= _native.MSMZ_DOT_MANY_MAX_ROWS:
+        raise ValueError(f"{who}: {len(rv)} rows (1 to {_native.MSMZ_DOT_MANY_MAX_ROWS})")
+    if not 1 <= len(cv) <= _native.MSMZ_DOT_MANY_MAX_COLS:
+        raise ValueError(f"{who}: {len(cv)} columns (1 to {_native.MSMZ_DOT_MANY_MAX_COLS})")
+    for arr, first in rv + cv:
+        if not 0 <= first <= len(arr):
+            raise ValueError(f"{who}: first = {first} of an array of {len(arr)}")
+    if N is None:
+        N = min(len(arr) - first for arr, first in rv + cv)
+    if not 1 <= N < 1 << 32:
+        raise ValueError(f"{who}: N = {N}")
+    if firstOut < 0 or (out is None and firstOut != 0):
+        raise ValueError(f"{who}: firstOut = {firstOut}" + ("" if out is not None else " without the array it indexes"))
+    for arr, first in rv + cv:
+        if N > len(arr) - first:
+            raise ValueError(f"{who}: entries [{first}, +{N}) of an array of {len(arr)}")
+    if out is not None:
+        results = len(rv) * len(cv)
+        if firstOut > len(out) or results > len(out) - firstOut:
+            raise ValueError(f"{who}: entries [{firstOut}, +{results}) of an array of {len(out)}")
+        for arr, first in rv + cv:
+            if arr.handle == out.handle and first < firstOut + results and firstOut < first + N:
+                raise ValueError(f"{who}: the destination [{firstOut}, +{results}) meets the input range [{first}, +{N}) "
+                                 f"of the same array")
+    return {"rows": rv, "cols": cv, "N": N, "firstOut": firstOut}
 
 
 def _ranges(who, ranges, N, out=None, limit=1 << 32):

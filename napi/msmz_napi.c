@@ -843,6 +843,37 @@ static napi_value ScalarsSumcheckStep(napi_env env, napi_callback_info info) {
   return buf;
 }
 
+/* scalarsDotMany(ctx, rows, nRows, cols, nCols (Buffers of msmz_scalar_vec: handle, first as little-endian u64 pairs), n,
+   resident (0: the values come back as a Buffer of nRows * nCols * 32 bytes, row-major; 1: they go to a scalar array),
+   outHandle (resident: the array written, 0 = a new one of nRows * nCols entries), firstOut)
+   -> the Buffer, or the handle written  (msmz_scalars_dot_many) */
+static napi_value ScalarsDotMany(napi_env env, napi_callback_info info) {
+  napi_value argv[MAX_ARGS]; msmz_ctx* ctx;
+  uint64_t n_rows, n_cols, n, resident, h, first_out;
+  void *rp, *cp; size_t rl, cl;
+  if (!get_args(env, info, 9, argv, &ctx) || !opt_buffer(env, argv[1], &rp, &rl) || !get_u64(env, argv[2], &n_rows) ||
+      !opt_buffer(env, argv[3], &cp, &cl) || !get_u64(env, argv[4], &n_cols) || !get_u64(env, argv[5], &n) ||
+      !get_u64(env, argv[6], &resident) || resident > 1 || !get_u64(env, argv[7], &h) || !get_u64(env, argv[8], &first_out) ||
+      n_rows < 1 || n_rows > MSMZ_DOT_MANY_MAX_ROWS || n_cols < 1 || n_cols > MSMZ_DOT_MANY_MAX_COLS ||
+      rl < n_rows * sizeof(msmz_scalar_vec) || cl < n_cols * sizeof(msmz_scalar_vec))
+    return BAD_ARG(env, "scalarsDotMany");
+  msmz_scalar_vec rows[MSMZ_DOT_MANY_MAX_ROWS], cols[MSMZ_DOT_MANY_MAX_COLS];   /* (a Buffer need not be aligned) */
+  memcpy(rows, rp, (size_t)n_rows * sizeof(msmz_scalar_vec));
+  memcpy(cols, cp, (size_t)n_cols * sizeof(msmz_scalar_vec));
+  msmz_dot_many d = {rows, (uint32_t)n_rows, cols, (uint32_t)n_cols, n, 0};
+  if (resident) {
+    int st = msmz_scalars_dot_many(ctx, &d, NULL, first_out, &h);
+    if (st) return throw_status(env, st, "msmz_scalars_dot_many");
+    return make_handle(env, h);
+  }
+  uint8_t out[MSMZ_DOT_MANY_MAX_ROWS * MSMZ_DOT_MANY_MAX_COLS * 32];   /* 32 KiB */
+  int st = msmz_scalars_dot_many(ctx, &d, out, first_out, NULL);
+  if (st) return throw_status(env, st, "msmz_scalars_dot_many");
+  napi_value buf;
+  NAPI_CALL(env, napi_create_buffer_copy(env, (size_t)(n_rows * n_cols) * 32, out, NULL, &buf));
+  return buf;
+}
+
 /* matrixCreate(ctx, rows, cols (Buffers of nnz little-endian u32 each), nnz, valHandle (0 = every value is 1), valFirst,
    nRows, nCols, flags (1 = rows, 2 = cols, 3 = both)) -> handle of a new sparse matrix  (msmz_matrix_create) */
 static napi_value MatrixCreate(napi_env env, napi_callback_info info) {
@@ -973,7 +1004,8 @@ static napi_value ScalarsExpr(napi_env env, napi_callback_info info) {
    matvec, matRows, matCols, matvecTranspose}: the same for the descriptors and flags of the sparse-matrix calls;
    descriptorSizes("lookup") -> {lookup, lookupResult, none}: the two descriptors of scalarsLookup and the position of a
    column entry that is in no table; descriptorSizes("expr") -> {exprColumn, exprFactor, exprTerm, expr, maxColumns,
-   maxTerms, maxDegree, maxOperands}; descriptorSizes("sumcheckStep") -> {sumcheckStep, sumcheckTable, sumcheckTerm}
+   maxTerms, maxDegree, maxOperands}; descriptorSizes("sumcheckStep") -> {sumcheckStep, sumcheckTable, sumcheckTerm};
+   descriptorSizes("dotMany") -> {dotMany, scalarVec, maxRows, maxCols}
    (the call without an argument answers what it always did). */
 static napi_value DescriptorSizes(napi_env env, napi_callback_info info) {
   napi_value res, argv[MAX_ARGS];
@@ -999,6 +1031,13 @@ static napi_value DescriptorSizes(napi_env env, napi_callback_info info) {
     set_num(env, res, "maxTerms", (double)MSMZ_EXPR_MAX_TERMS);
     set_num(env, res, "maxDegree", (double)MSMZ_EXPR_MAX_DEGREE);
     set_num(env, res, "maxOperands", (double)MSMZ_EXPR_MAX_OPERANDS);
+    return res;
+  }
+  if (strcmp(family, "dotMany") == 0) {   /* the descriptors and limits of scalarsDotMany */
+    set_num(env, res, "dotMany", (double)sizeof(msmz_dot_many));
+    set_num(env, res, "scalarVec", (double)sizeof(msmz_scalar_vec));
+    set_num(env, res, "maxRows", (double)MSMZ_DOT_MANY_MAX_ROWS);
+    set_num(env, res, "maxCols", (double)MSMZ_DOT_MANY_MAX_COLS);
     return res;
   }
   if (strcmp(family, "sumcheckStep") == 0) {   /* the descriptors of scalarsSumcheckStep */
@@ -1068,7 +1107,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"scalarsSumcheckRound", ScalarsSumcheckRound}, {"scalarsSumcheckStep", ScalarsSumcheckStep}, {"allocScalars", AllocScalars},
       {"descriptorSizes", DescriptorSizes},
       {"matrixCreate", MatrixCreate}, {"matrixInfo", MatrixInfo}, {"matrixMul", MatrixMul},
-      {"scalarsLookup", ScalarsLookup}, {"scalarsExpr", ScalarsExpr},
+      {"scalarsLookup", ScalarsLookup}, {"scalarsExpr", ScalarsExpr}, {"scalarsDotMany", ScalarsDotMany},
       {"pointAdd", PointAdd}, {"feBytes", FeBytes}};
   for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); i++) {
     napi_value f;
